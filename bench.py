@@ -504,6 +504,34 @@ def element_rate(script="element_bench.sh", args=("20000", "8", str(CC_THRESHOLD
         return {"error": repr(e)[:200]}
 
 
+DUMP_MAX_BYTES = 64_000_000
+
+
+def dump_outputs(ctx, out_dir, batch, d_boxes, d_counts, d_mask):
+    """What a caller of the timed path receives from one step, as float arrays: counts[b], boxes[b, MAX_BOXES, 5] (left, top,
+    width, height, area_px; the rows past a frame's count are zero, not the buffer's stale contents) and the mask[b, H, W].
+    A batch whose arrays would pass DUMP_MAX_BYTES is written as a fixed, seeded sample of its frames, in batch order;
+    frames.npy names the frames written."""
+    from cova_amd import _lib as L
+    counts = np.zeros(batch, dtype=np.int32)
+    boxes = np.zeros((batch, MAX_BOXES), dtype=L.BOX_DTYPE)
+    mask = np.zeros((batch, H_MB, W_MB), dtype=np.uint8)
+    ctx.d2h(counts, d_counts)
+    ctx.d2h(boxes, d_boxes)
+    ctx.d2h(mask, d_mask)
+    fields = np.stack([boxes[f] for f in L.BOX_DTYPE.names], axis=-1).astype(np.float32)
+    fields[np.arange(MAX_BOXES)[None, :] >= counts[:, None]] = 0.0
+    per_frame = 8 + 8 + MAX_BOXES * 5 * 4 + H_MB * W_MB * 4          # frames, counts (float64), boxes, mask (float32)
+    keep = np.arange(batch)
+    if batch * per_frame > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(batch, DUMP_MAX_BYTES // per_frame, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "frames.npy"), keep.astype(np.float64))
+    np.save(os.path.join(out_dir, "counts.npy"), counts[keep].astype(np.float64))
+    np.save(os.path.join(out_dir, "boxes.npy"), fields[keep])
+    np.save(os.path.join(out_dir, "mask.npy"), mask[keep].astype(np.float32))
+
+
 def rank_line(mine):
     """One rank's object on stderr as ONE write (line + newline together: eight ranks share the pipe, and print() sends the newline
     separately -- two ranks' lines then run into each other)."""
@@ -530,6 +558,9 @@ def main():
                          "barrier, MAX over ranks, gather, the aggregate line's shape -- no kernel runs and the line carries no rate")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-legs", action="store_true", help="only the timed workload (profiling runs)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (boxes, counts, mask of its batch; at most 64 MB: a seeded "
+                         "sample of the frames of a larger batch) as DIR/<name>.npy")
     args = ap.parse_args()
     os.environ.setdefault("OMP_NUM_THREADS", str(effective_cores()))   # before anything loads libgomp (the oracle, torch)
 
@@ -716,34 +747,28 @@ def main():
     ctx.set_lanes(NL)
     t_w = time.perf_counter()
     n_w = 0
-    while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s:
+    # (the warm-up ends on a whole cycle of lanes x batches, so that the timed region starts on the same lane and batch in
+    # every run: its last step -- what --dump-outputs writes -- is then the same computation for the same arguments)
+    while n_w < args.warmup or time.perf_counter() - t_w < args.min_warmup_s or turn[0] % (2 * NL):
         step()
         n_w += 1
         if n_w % 64 == 0:
             ctx.sync()
-    # ---- timed region: K steps between barriers; only the dominant kernel carries HIP events (2 per step).  A K-step region
-    # of a few tens of milliseconds is repeated (at least five times while it is shorter than 50 ms) and the MEDIAN region
-    # counts: `steps` stays K, every repeat is a complete barrier-to-barrier measurement of K steps.
+    # ---- timed region: exactly K = --steps steps between barriers; only the dominant kernel carries HIP events (2 per step)
     ctx.profile(True, only=dominant)
-    regions, ev_regions = [], []
-    while True:
-        barrier()
-        t0 = time.perf_counter()
-        ctx.timer_start(0)
-        for _ in range(args.steps):
-            step()
-        ctx.timer_stop(0)
-        barrier()
-        regions.append(grp.max(time.perf_counter() - t0))     # the slowest rank's region (every rank appends the same number)
-        ev_regions.append(ctx.timer_ms(0))
-        if len(regions) >= 5 or (len(regions) >= 1 and regions[0] >= 0.05):
-            break
-    order = sorted(range(len(regions)), key=lambda i: regions[i])
-    mid = order[len(order) // 2]
-    elapsed = regions[mid]
-    ev_ms = ev_regions[mid]
+    barrier()
+    t0 = time.perf_counter()
+    ctx.timer_start(0)
+    for _ in range(args.steps):
+        step()
+    ctx.timer_stop(0)
+    barrier()
+    elapsed = grp.max(time.perf_counter() - t0)     # the slowest rank's region
+    ev_ms = ctx.timer_ms(0)
     dom_ms, dom_n = ctx.profile_read()[dominant]
     ctx.profile(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs, B, d_boxes[turn[0] % NL], d_counts[turn[0] % NL], d_mask[turn[0] % NL])
     # the same K steps with ONE batch (unchanged stack table: no validation upload after the first step), for comparison
     alternate[0] = False
     for _ in range(2 * NL):
@@ -754,7 +779,7 @@ def main():
         step()
     barrier()
     elapsed_cached = grp.max(time.perf_counter() - t0)
-    # ---- one lane: a step on its own, measured like the timed region (warm clocks, alternating batches, median of five
+    # ---- one lane: a step on its own (warm clocks, alternating batches as in the timed region; the median of five
     # barrier-to-barrier regions of K steps) -- rounds 1-3 timed 50 steps right after start-up, before the clocks had settled
     ctx.set_lanes(1)
     alternate[0] = True
@@ -944,8 +969,8 @@ def main():
             **({"rehearsal": f"{world} ranks shared the GPUs present on this box: NOT a scaling result"} if args.rehearse_on_one_gpu else {}),
             **({"ranks": all_ranks, "control_plane": "gloo on CPU tensors (rendezvous, barrier, MAX over ranks, gather of these objects); "
                                                       "no RCCL communicator exists"} if world > 1 else {}),
-            "timed_regions_s": [round(r, 5) for r in regions],
-            "timed_region": f"median of {len(regions)} barrier-to-barrier regions of {args.steps} steps each",
+            "timed_regions_s": [round(elapsed, 5)],
+            "timed_region": f"one barrier-to-barrier region of {args.steps} steps",
             "ms_per_step_one_batch": round(elapsed_cached / args.steps * 1e3, 4),
             "shader_clock_mhz_under_load": round(clock_mhz, 1),
             "blobnet_mfma_util_whole_net": round(total_flop / step_s / 1e12 / MFMA_PEAK_TFLOPS, 4),

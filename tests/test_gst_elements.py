@@ -351,10 +351,10 @@ def test_blobnetfilter_concurrent_streams(tmp_path, weights_flat, n_streams, bat
     assert many["pad0_sum"] == alone["pad0_sum"]
 
 
-DEMO = "/root/reference/demo/1m.mp4"
+DEMO = os.path.join(ROOT, "tests", "golden", "demo_excerpt.mp4")    # demo/1m.mp4's first 176 access units (tests/golden/gen_demo_excerpt.py)
+N_AU = 176
 
 
-@pytest.mark.skipif(not os.path.exists(DEMO), reason="reference demo video not present (GPU box)")
 def test_config_1_through_the_elements_entropy_decoder_metapreprocess_tfrecordsink(tmp_path):
     """BASELINE config 1 through the plugin: the access units of demo/1m.mp4 (decode order, as qtdemux ! h264parse would hand them
     over) -> h264entropydec -> metapreprocess timestep=4 -> tfrecordsink.  The decoder element reorders into output order; every
@@ -365,14 +365,14 @@ def test_config_1_through_the_elements_entropy_decoder_metapreprocess_tfrecordsi
     data = np.fromfile(DEMO, dtype=np.uint8)
     h = C.c_void_p()
     assert lib.covahip_h264_open_mp4(data.ctypes.data, data.size, C.byref(h)) == 0
-    n_au = 300                                   # the first GoP and the start of the second: one IDR in the middle of the run
+    n_au = 2 * N_AU                              # the excerpt twice over (a closed GoP): one IDR in the middle of the run
     raw = data.tobytes()
     at = raw.find(b"avcC")
     avcc = raw[at + 4:at - 4 + struct.unpack(">I", raw[at - 4:at])[0]]
     recs_in = []
     off, size, sync = C.c_uint64(), C.c_uint32(), C.c_int()
     for s in range(n_au):
-        lib.covahip_h264_sample(h, s, C.byref(off), C.byref(size), C.byref(sync))
+        lib.covahip_h264_sample(h, s % N_AU, C.byref(off), C.byref(size), C.byref(sync))
         recs_in.append(("B", s * CLK, 0 if sync.value else 1, raw[off.value:off.value + size.value]))
     _write(tmp_path / "in.rec", recs_in)
     caps = f"video/x-h264,stream-format=avc,alignment=au,framerate=30/1,codec_data=(buffer){avcc.hex()}"
@@ -382,14 +382,14 @@ def test_config_1_through_the_elements_entropy_decoder_metapreprocess_tfrecordsi
     outs = _read(tmp_path / "out.rec")
     assert len(outs) == n_au - 3
     # what the C-ABI front end says: records per access unit and the output order
-    order = np.zeros(1802, np.int32)
+    order = np.zeros(N_AU, np.int32)
     n = C.c_int()
-    assert lib.covahip_h264_display_order(h, order.ctypes.data, 1802, C.byref(n)) == 0
-    order = [int(s) for s in order if s < n_au]
-    assert sorted(order[:n_au]) == list(range(n_au))       # the first 300 access units are the first 300 output pictures (closed GoPs)
+    assert lib.covahip_h264_display_order(h, order.ctypes.data, N_AU, C.byref(n)) == 0
+    assert sorted(order.tolist()) == list(range(N_AU))    # the excerpt's access units are its output pictures (a closed cut)
+    order = [int(s) + r * N_AU for r in range(2) for s in order]
     rec = np.zeros((n_au, 45, 80, 4), np.uint8)
     for s in range(n_au):
-        assert lib.covahip_h264_decode_records(h, s, rec[s].ctypes.data, rec[s].nbytes) == 0
+        assert lib.covahip_h264_decode_records(h, s % N_AU, rec[s].ctypes.data, rec[s].nbytes) == 0
     for k, (kind, pts, flags, payload) in enumerate(outs):
         cur = k + 3
         assert pts == order[cur] * CLK                      # the stacked frame carries the timestamp of its current picture
