@@ -390,6 +390,44 @@ int covahip_filter_forward_frames_packed(covahip_ctx *ctx, const uint16_t *d_rec
                          max_boxes, d_logits, d_mask, true);
 }
 
+// Developer read-back (include/covahip_dev.h): one activation buffer of lane 0's workspace, for stage-by-stage tests.
+int covahip_dev_blobnet_buffer(covahip_ctx *ctx, int which, int index, void **dptr, size_t *bytes, int32_t dims[5]) {
+    if (!ctx || !dptr || !bytes || !dims) return COVAHIP_ERR_INVALID_ARG;
+    covahip_blobnet *m = ctx->blobnet;
+    if (!m) return COVAHIP_ERR_NOT_LOADED;
+    const BnWorkspace &ws = m->ws[0];
+    int64_t d[5] = {0, 0, 0, 0, 0};
+    size_t elem = sizeof(__half);
+    void *p = nullptr;
+    if (which == 0 && index == 0) {          // P: [frames][H_1][W_1][16]
+        p = ws.pbuf;
+        d[0] = (int64_t)ws.pbuf_frames; d[1] = m->lv[1].H; d[2] = m->lv[1].W; d[3] = m->enc_c[1];
+    } else if (which == 1 && index >= 1 && index <= BN_LEVELS) {   // act[i]: [B][T][H_i][W_i][C_i], act[4]: [B][H_4][W_4][128]
+        p = ws.act[index];
+        const BnLevelGeom g = m->lv[index];
+        if (index < BN_LEVELS) { d[0] = m->max_batch; d[1] = BN_T; d[2] = g.H; d[3] = g.W; d[4] = m->enc_c[index]; }
+        else { d[0] = m->max_batch; d[1] = g.H; d[2] = g.W; d[3] = m->enc_c[index]; }
+    } else if (which == 2 && index >= 0 && index < BN_LEVELS - 1) {   // dact[j]: [B][Hd][Wd][Cout_j]
+        p = ws.dact[index];
+        const BnLevelGeom g = m->lv[BN_LEVELS - 1 - index];
+        d[0] = m->max_batch; d[1] = g.H; d[2] = g.W; d[3] = m->dec_co[index];
+    } else if (which == 3 && index == 0) {   // part: fp32 [B][H_1 + 1][W_1 + 1][4]
+        p = ws.part;
+        elem = sizeof(float);
+        d[0] = m->max_batch; d[1] = m->lv[1].H + 1; d[2] = m->lv[1].W + 1; d[3] = 4;
+    } else {
+        return COVAHIP_ERR_INVALID_ARG;
+    }
+    size_t n = p ? elem : 0;
+    for (int k = 0; k < 5; k++) {
+        dims[k] = p ? (int32_t)d[k] : 0;
+        if (d[k]) n *= (size_t)d[k];
+    }
+    *dptr = p;
+    *bytes = n;
+    return COVAHIP_OK;
+}
+
 // Developer probe (include/covahip_dev.h): the same carrier-frame step `iters` times as stream launches and as launches of ONE
 // captured HIP graph of it -- what the gaps between the six launches of a step cost on their own.
 int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_frames, const int32_t *stack_index, int batch,

@@ -186,6 +186,17 @@ class BlobNetInfer:
         level-1 kernel computes from it (round 5 default; another summation order, not another value)."""
         L.check(self._lib.covahip_blobnet_set_impl(self.ctx.handle, {"mfma": 1, "dec_separate": 4, "enc1_legacy": 5, "enc_general_tiles": 6, "enc23_separate": 7, "enc23_force": 8, "tail_skip_tensor": 9, "tail_band_tiles": 10}[impl]), "set_impl")
 
+    def read_buffer(self, which: int, index: int = 0) -> np.ndarray:
+        """Developer read-back (include/covahip_dev.h): a copy of one buffer of lane 0's workspace -- which = 0 P, 1 act[index],
+        2 dact[index], 3 part -- as fp16 (fp32 for part) in its full allocated shape."""
+        p, n, dims = C.c_void_p(), C.c_size_t(), (C.c_int32 * 5)()
+        L.check(self._lib.covahip_dev_blobnet_buffer(self.ctx.handle, which, index, C.byref(p), C.byref(n), dims),
+                "covahip_dev_blobnet_buffer", self.ctx.handle)
+        out = np.empty(tuple(d for d in dims if d), dtype=np.float32 if which == 3 else np.float16)
+        assert p.value and out.nbytes == n.value, (which, index, n.value, tuple(dims))
+        self.ctx.d2h(out, p.value)
+        return out
+
     @property
     def macs_per_frame(self) -> int:
         v = C.c_int64()

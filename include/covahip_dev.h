@@ -36,6 +36,13 @@ int covahip_dev_bboxcc_overflow(covahip_ctx *ctx, int32_t *out4);
  * COVAHIP_ERR_UNSUPPORTED. */
 int covahip_blobnet_set_enc_plan(covahip_ctx *ctx, int level, int nbands, int nbuf);
 
+/* Device pointer, byte size and dims of one activation buffer of lane 0's BlobNet workspace (the buffers the primary-stream calls
+ * write; layouts: BnWorkspace in cova_amd/csrc/blobnet.h): which = 0 P (pooled level 0 per carrier frame, index 0), 1 act[index]
+ * (1..4), 2 dact[index] (0..2), 3 part (fp32 partial logits, index 0).  dims: up to 5, unused = 0; a buffer not allocated yet
+ * gives a null pointer, 0 bytes and all-zero dims.  No synchronisation: the caller reads it after the forward it inspects has
+ * finished.  (tests/test_gpu_stages.py) */
+int covahip_dev_blobnet_buffer(covahip_ctx *ctx, int which, int index, void **dptr, size_t *bytes, int32_t dims[5]);
+
 /* Shader clock (MHz) the chip holds right now: one wave runs a dependent chain for about busy_us microseconds on a stream
  * of its own -- beside whatever the ctx has in flight -- and brackets it with s_memtime / s_memrealtime
  * (MI355X_MICROARCH.md, DVFS give-back).  bench.py prints it so that step times of different boxes can be compared. */
