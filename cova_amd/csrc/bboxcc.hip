@@ -280,7 +280,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
             COVAHIP_CHECK_HIP(ctx, hipGetLastError());
             ln.cc_stat_batch = batch;
             ln.cc_stat_cap = cap;
-            ln.cc_second_skipped = second && !second_now;
+            ln.cc_second_skipped = !second_now;   // skipped, or not planned because four waves at 4 x cap do not fit LDS
         } else {
             ln.cc_stat_batch = 0;
         }
@@ -317,8 +317,8 @@ extern "C" int covahip_dev_bboxcc_overflow(covahip_ctx *ctx, int32_t *out4) {
     int rc = covahip_sync_all(ctx);
     if (rc) return rc;
     const CtxLane &ln = ctx->lanes[0];
-    // (everything has drained: the words are those of the last large-batch call; a frame that overflowed pass 1 while the
-    // second-chance pass was skipped counts as having overflowed both)
+    // (everything has drained: the words are those of the last large-batch call; a frame that overflowed pass 1 while no
+    // second-chance pass ran -- skipped, or not planned at all -- went straight to pass 3 and counts as having overflowed both)
     out4[0] = ln.cc_stat_batch;
     out4[1] = ln.cc_stat && ln.cc_stat_batch ? ln.cc_stat[0] : 0;
     out4[2] = ln.cc_stat && ln.cc_stat_batch ? ln.cc_stat[ln.cc_second_skipped ? 0 : 1] : 0;

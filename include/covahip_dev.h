@@ -23,11 +23,14 @@ int covahip_blobnet_set_impl(covahip_ctx *ctx, int impl);
 
 /* bboxcc kernel choice: cap > 0 = run capacity of the wave-per-frame kernel's first pass (frames with more runs get a
  * second chance at four times the capacity, then the workgroup kernel), cap < 0 = workgroup-per-frame kernel only,
- * 0 = automatic (default: 128, or 512 when more than a quarter of the previous call's frames overflowed). */
+ * 0 = automatic (default: 128; 192, 256 or 512 when more than a quarter of the previous call's frames on the lane had more
+ * than 128, 192 or 256 runs, counted on one frame in sixteen). */
 int covahip_bboxcc_set_wave_cap(covahip_ctx *ctx, int cap);
 /* Overflow statistics of the last large-batch covahip_bboxcc call (device pointers): out4 = {batch, frames that overflowed
  * pass 1, frames that overflowed pass 2 too, capacity of pass 1}; batch = 0 when that call ran a kernel that cannot
- * overflow.  Synchronises the ctx.  (tools/bboxcc_sweep.py) */
+ * overflow.  When that call ran no second-chance pass (skipped because the call before it had no overflow, or not planned
+ * because four waves at four times the capacity do not fit LDS), pass 3 labelled every frame that overflowed pass 1, and
+ * those count as having overflowed pass 2 too: out4[2] = out4[1].  Synchronises the ctx.  (tools/bboxcc_sweep.py) */
 int covahip_dev_bboxcc_overflow(covahip_ctx *ctx, int32_t *out4);
 
 /* Encoder band plan of level 1..3 (tools/plan_sweep.sh): nbands bands of pool-window rows per frame, nbuf = 1 or 2 LDS
