@@ -69,6 +69,12 @@ class AssocCfg(C.Structure):
                 ("scale_factor", C.c_float)]
 
 
+class TrainCfg(C.Structure):
+    _fields_ = [("h_mb", C.c_int32), ("w_mb", C.c_int32), ("max_batch", C.c_int32), ("lr", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("eps", C.c_float), ("bn_momentum", C.c_float), ("bn_eps", C.c_float), ("dropout", C.c_float),
+                ("smooth", C.c_float), ("seed", C.c_uint64)]
+
+
 # name -> (restype, argtypes); every symbol include/covahip.h declares
 _P = C.c_void_p
 _SZ = C.c_size_t
@@ -167,6 +173,13 @@ PROTOTYPES = {
     "covahip_gopfilter_take_track_export": (_SZ, [_P, _P, _SZ, C.POINTER(C.c_int)]),
     "covahip_gopfilter_counters": (C.c_int, [_P, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
                                              C.POINTER(C.c_uint64)]),
+    "covahip_train_default_cfg": (None, [C.POINTER(TrainCfg)]),
+    "covahip_train_create": (C.c_int, [_P, C.POINTER(TrainCfg), _P, _SZ, C.POINTER(_P)]),
+    "covahip_train_step": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(C.c_float), C.c_int]),
+    "covahip_train_metrics": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "covahip_train_weights": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ)]),
+    "covahip_train_grads": (C.c_int, [_P, _P, _SZ]),
+    "covahip_train_destroy": (None, [_P]),
 }
 
 # developer switches (include/covahip_dev.h): bound for tools/ and tests/, not part of the drop-in boundary

@@ -1,0 +1,973 @@
+// BlobNet training step on gfx950: forward, backward and Adam in fp32 (include/covahip.h, "BlobNet training").
+//
+// Layout: every activation is channels-first, NCTHW for the encoder ([B][C][T][H][W]) and NCHW for the decoder (T = 1: the
+// decoder only sees the t = 0 slice of each encoder level, tests/torch_blobnet.py).  Channels-first keeps each channel's
+// (T, H, W) block contiguous, which is what the per-channel reductions (BN, biases) walk, and it is the index order the
+// dropout hash is defined over.
+//
+// Determinism: no float atomics.  Every reduction is a fixed split of its range into slabs (one workgroup each, fixed-order
+// tree inside), followed by a sequential sum of the slabs; the split depends on the geometry and the batch only.  The only
+// atomics are the integer TP / FP / FN counters of the metrics.
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "internal.h"
+
+namespace {
+
+constexpr int TT = 4;                 // timestep
+constexpr int NL = 4;                 // encoder levels / decoder blocks
+constexpr size_t N_PARAMS = 320305;
+constexpr uint32_t W_MAGIC = 0x57485643;  // "CVHW"
+constexpr int ENC_C[NL + 1] = {3, 16, 32, 64, 128};
+constexpr int DEC_CI[NL] = {128, 128, 64, 32};
+constexpr int DEC_CO[NL] = {64, 32, 16, 16};
+constexpr int BLK = 256;
+constexpr int RED_CHUNK = 4096;       // elements per slab of a channel reduction
+constexpr int WG_CHUNK = 1024;        // positions per slab of a weight gradient
+constexpr int TMIX_BLOCKS_MAX = 512;
+
+// ------------------------------------------------------------------------------------------------ dropout hash
+__host__ __device__ inline uint64_t splitmix64(uint64_t z) {
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+uint64_t drop_key(uint64_t seed, uint64_t step, int site) { return splitmix64(seed ^ splitmix64((step << 8) | (uint64_t)site)); }
+struct Drop {
+    uint64_t key;
+    uint32_t thr;   // keep iff the hash's top 24 bits >= thr
+    float scale;    // 1 / (1 - p)
+};
+__device__ inline float keep(const Drop &d, uint64_t idx) {
+    return (uint32_t)(splitmix64(d.key + idx) >> 40) >= d.thr ? d.scale : 0.f;
+}
+
+inline unsigned nblk(int64_t n) { return (unsigned)((n + BLK - 1) / BLK); }
+
+// ------------------------------------------------------------------------------------------------ kernels
+// u8 [B][T*H][W][4] -> clip(x, 0, 6) / 6 of bytes 0..2, [B][3][T][H][W]
+__global__ void k_input(const uint8_t *__restrict__ st, float *__restrict__ x, int B, int H, int W) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)B * 3 * TT * hw;
+    if (i >= n) return;
+    const int64_t s = i % hw;
+    const int t = (int)((i / hw) % TT), ch = (int)((i / (hw * TT)) % 3);
+    const int64_t b = i / (hw * TT * 3);
+    const float v = (float)st[((b * TT + t) * hw + s) * 4 + ch];
+    x[i] = fminf(v, 6.f) / 6.f;
+}
+
+// conv 3x3 "same" + bias + ReLU per (b, t) slice; k: Keras [3][3][Ci][Co]
+__global__ void k_conv3_fwd(const float *__restrict__ x, const float *__restrict__ k, const float *__restrict__ bias,
+                            float *__restrict__ out, int B, int Ci, int Co, int H, int W) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)B * Co * TT * hw;
+    if (i >= n) return;
+    const int xx = (int)(i % W), yy = (int)((i / W) % H);
+    const int t = (int)((i / hw) % TT), co = (int)((i / (hw * TT)) % Co);
+    const int64_t b = i / (hw * TT * Co);
+    float acc = bias[co];
+    for (int ci = 0; ci < Ci; ci++) {
+        const float *xp = x + ((b * Ci + ci) * TT + t) * hw;
+        for (int ky = 0; ky < 3; ky++) {
+            const int y = yy + ky - 1;
+            if (y < 0 || y >= H) continue;
+            for (int kx = 0; kx < 3; kx++) {
+                const int xq = xx + kx - 1;
+                if (xq < 0 || xq >= W) continue;
+                acc += xp[(int64_t)y * W + xq] * k[((ky * 3 + kx) * Ci + ci) * Co + co];
+            }
+        }
+    }
+    out[i] = fmaxf(acc, 0.f);
+}
+
+// dX of the conv: dx[b][ci][t][y][x] = sum dA[b][co][t][y-ky+1][x-kx+1] * k[ky][kx][ci][co]
+__global__ void k_conv3_dgrad(const float *__restrict__ dA, const float *__restrict__ k, float *__restrict__ dx, int B, int Ci,
+                              int Co, int H, int W) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)B * Ci * TT * hw;
+    if (i >= n) return;
+    const int xx = (int)(i % W), yy = (int)((i / W) % H);
+    const int t = (int)((i / hw) % TT), ci = (int)((i / (hw * TT)) % Ci);
+    const int64_t b = i / (hw * TT * Ci);
+    float acc = 0.f;
+    for (int co = 0; co < Co; co++) {
+        const float *gp = dA + ((b * Co + co) * TT + t) * hw;
+        for (int ky = 0; ky < 3; ky++) {
+            const int y = yy - ky + 1;
+            if (y < 0 || y >= H) continue;
+            for (int kx = 0; kx < 3; kx++) {
+                const int xq = xx - kx + 1;
+                if (xq < 0 || xq >= W) continue;
+                acc += gp[(int64_t)y * W + xq] * k[((ky * 3 + kx) * Ci + ci) * Co + co];
+            }
+        }
+    }
+    dx[i] = acc;
+}
+
+// dK slabs of the conv: slab s covers positions [s*chunk, (s+1)*chunk) of the B*T*H*W positions; one thread per weight
+__global__ void k_conv3_wgrad(const float *__restrict__ dA, const float *__restrict__ x, float *__restrict__ slab, int B, int Ci,
+                              int Co, int H, int W, int64_t chunk) {
+    const int nw = 9 * Ci * Co;
+    const int wi = blockIdx.x * BLK + threadIdx.x;
+    if (wi >= nw) return;
+    const int co = wi % Co, ci = (wi / Co) % Ci, kk = wi / (Co * Ci), ky = kk / 3, kx = kk % 3;
+    const int64_t hw = (int64_t)H * W, P = (int64_t)B * TT * hw;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+    float acc = 0.f;
+    for (int64_t p = p0; p < p1; p++) {
+        const int64_t s = p % hw, bt = p / hw;
+        const int64_t b = bt / TT, t = bt % TT;
+        const int y = (int)(s / W) + ky - 1, xq = (int)(s % W) + kx - 1;
+        if (y < 0 || y >= H || xq < 0 || xq >= W) continue;
+        acc += dA[((b * Co + co) * TT + t) * hw + s] * x[((b * Ci + ci) * TT + t) * hw + (int64_t)y * W + xq];
+    }
+    slab[(int64_t)blockIdx.y * nw + wi] = acc;
+}
+
+// out[i] = sum over slabs s of slab[s][i], in slab order
+__global__ void k_sum_slabs(const float *__restrict__ slab, int nslab, int n, float *__restrict__ out) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    float acc = 0.f;
+    for (int s = 0; s < nslab; s++) acc += slab[(int64_t)s * n + i];
+    out[i] = acc;
+}
+
+// Per-channel reductions of a [N][C][S] tensor: slab p of channel c covers elements [p*chunk, (p+1)*chunk) of its N*S.
+enum RedMode { R_SUM = 0, R_SQDEV = 1, R_BNBWD = 2, R_FINALW = 3, R_LOSS = 4 };
+__global__ void k_reduce(int mode, int N, int C, int64_t S, const float *__restrict__ x, const float *__restrict__ g, int Cg,
+                         const float *__restrict__ aux, const uint8_t *__restrict__ gt, float *__restrict__ part, int NP,
+                         int64_t chunk) {
+    __shared__ float sa[BLK], sb[BLK];
+    const int c = blockIdx.y, p = blockIdx.x;
+    const int64_t M = (int64_t)N * S;
+    const int64_t e0 = (int64_t)p * chunk, e1 = e0 + chunk < M ? e0 + chunk : M;
+    float a = 0.f, bsum = 0.f;
+    for (int64_t e = e0 + threadIdx.x; e < e1; e += BLK) {
+        const int64_t n = e / S, s = e % S;
+        const int64_t xi = (n * C + c) * S + s;
+        switch (mode) {
+        case R_SUM: a += x[xi]; break;
+        case R_SQDEV: { const float v = x[xi] - aux[c]; a += v * v; } break;
+        case R_BNBWD: {
+            const float gv = g[(n * Cg + c) * S + s];
+            a += gv;
+            bsum += gv * (x[xi] - aux[c]) * aux[C + c];
+        } break;
+        case R_FINALW: a += x[xi] * g[n * S + s]; break;
+        case R_LOSS: {   // N = 1, C = batch: x = logits, gt = labels
+            const float pr = 1.f / (1.f + expf(-x[xi]));
+            const float yv = (float)gt[xi];
+            a += yv * pr;
+            bsum += yv + pr;
+        } break;
+        }
+    }
+    sa[threadIdx.x] = a;
+    sb[threadIdx.x] = bsum;
+    __syncthreads();
+    for (int w = BLK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w) {
+            sa[threadIdx.x] += sa[threadIdx.x + w];
+            sb[threadIdx.x] += sb[threadIdx.x + w];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        part[((int64_t)c * NP + p) * 2] = sa[0];
+        part[((int64_t)c * NP + p) * 2 + 1] = sb[0];
+    }
+}
+
+enum FinMode { F_MEAN = 0, F_VAR = 1, F_SUM2 = 2, F_SUM = 3 };
+// stat: [2][C].  F_MEAN: stat[0] = mean.  F_VAR: stat[1] = 1/sqrt(var + eps), g0/g1 = batch mean / biased variance, mov0/mov1
+// moving statistics (variance with n/(n-1)).  F_SUM2: stat = (sum a, sum b), g0 = sum b, g1 = sum a (BN gamma / beta
+// gradients).  F_SUM: g0 = sum a.
+__global__ void k_finalize(int mode, int C, int NP, const float *__restrict__ part, double M, float *stat, float *g0, float *g1,
+                           float *mov0, float *mov1, float mom, float eps) {
+    const int c = blockIdx.x * BLK + threadIdx.x;
+    if (c >= C) return;
+    float a = 0.f, b = 0.f;
+    for (int p = 0; p < NP; p++) {
+        a += part[((int64_t)c * NP + p) * 2];
+        b += part[((int64_t)c * NP + p) * 2 + 1];
+    }
+    if (mode == F_MEAN) {
+        stat[c] = (float)(a / M);
+    } else if (mode == F_VAR) {
+        const float var = (float)(a / M), mean = stat[c];
+        stat[C + c] = 1.f / sqrtf(var + eps);
+        g0[c] = mean;
+        g1[c] = var;
+        mov0[c] = mom * mov0[c] + (1.f - mom) * mean;
+        mov1[c] = mom * mov1[c] + (1.f - mom) * (float)(var * (M / (M - 1.0)));
+    } else if (mode == F_SUM2) {
+        stat[c] = a;
+        stat[C + c] = b;
+        if (g0) g0[c] = b;
+        if (g1) g1[c] = a;
+    } else {
+        g0[c] = a;
+    }
+}
+
+// BN apply + 2x2 max-pool (valid) + zero row on top / column on the left for odd sizes, with the window argmax (first maximum in
+// row-major order; -1 on pad positions).  c: [B][C][T][H][W] -> p: [B][C][T][Hp][Wp]
+__global__ void k_bn_pool(const float *__restrict__ c, const float *__restrict__ stat, const float *__restrict__ gamma,
+                          const float *__restrict__ beta, float *__restrict__ p, int8_t *__restrict__ arg, int B, int C, int H, int W,
+                          int Hp, int Wp) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t hwp = (int64_t)Hp * Wp, n = (int64_t)B * C * TT * hwp;
+    if (i >= n) return;
+    const int px = (int)(i % Wp), py = (int)((i / Wp) % Hp);
+    const int64_t bct = i / hwp;
+    const int ch = (int)((bct / TT) % C);
+    const int pt = H & 1, pl = W & 1;
+    if (py < pt || px < pl) {
+        p[i] = 0.f;
+        arg[i] = -1;
+        return;
+    }
+    const float mean = stat[ch], inv = stat[C + ch], ga = gamma[ch], be = beta[ch];
+    const float *src = c + bct * (int64_t)H * W + (int64_t)(2 * (py - pt)) * W + 2 * (px - pl);
+    float best = 0.f;
+    int bk = 0;
+    for (int k = 0; k < 4; k++) {
+        const float v = (src[(k >> 1) * W + (k & 1)] - mean) * inv * ga + be;
+        if (k == 0 || v > best) { best = v; bk = k; }
+    }
+    p[i] = best;
+    arg[i] = (int8_t)bk;
+}
+
+// gradient of the pool: each pre-pool element takes its window's gradient if it was the argmax; dropped rows / columns get 0
+__global__ void k_pool_bwd(const float *__restrict__ dp, const int8_t *__restrict__ arg, float *__restrict__ dn, int B, int C, int H,
+                           int W, int Hp, int Wp) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t hw = (int64_t)H * W, n = (int64_t)B * C * TT * hw;
+    if (i >= n) return;
+    const int xx = (int)(i % W), yy = (int)((i / W) % H);
+    const int64_t bct = i / hw;
+    const int pt = H & 1, pl = W & 1;
+    float v = 0.f;
+    if (yy < 2 * (Hp - pt) && xx < 2 * (Wp - pl)) {
+        const int64_t pi = bct * Hp * Wp + (int64_t)(yy / 2 + pt) * Wp + (xx / 2 + pl);
+        if (arg[pi] == (yy & 1) * 2 + (xx & 1)) v = dp[pi];
+    }
+    dn[i] = v;
+}
+
+// BN backward apply: out = gamma * invstd / M * (M * g - sum g - xhat * sum g*xhat), times (x > 0) when relu_in (the BN input is
+// the post-ReLU conv output).  g has Cg channels per sample (a channel range of a concat buffer), out has C.  g and out may be
+// the same buffer (the encoder runs it in place: each thread reads its own element before it writes it), so neither is restrict.
+__global__ void k_bn_bwd(const float *g, int Cg, const float *__restrict__ x, const float *__restrict__ stat,
+                         const float *__restrict__ red, const float *__restrict__ gamma, float *out, int B, int C,
+                         int64_t S, int relu_in) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * C * S;
+    if (i >= n) return;
+    const int64_t s = i % S;
+    const int ch = (int)((i / S) % C);
+    const int64_t b = i / (S * C);
+    const float M = (float)((double)B * S);
+    const float mean = stat[ch], inv = stat[C + ch];
+    const float xv = x[i], xh = (xv - mean) * inv;
+    const float gv = g[(b * Cg + ch) * S + s];
+    float d = gamma[ch] * inv / M * (M * gv - red[ch] - xh * red[C + ch]);
+    if (relu_in && !(xv > 0.f)) d = 0.f;
+    out[i] = d;
+}
+
+// PointWiseTN forward per (b, c, y, x): o = relu(drop(relu(drop(relu(p @ w1)) @ w2)) + p); the t = 0 slice also goes to the
+// decoder's concat buffer (channel c_off + c of Ctot).  Dropout indices: NCTHW of the layer's output.
+__global__ void k_tmix_fwd(const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
+                           float *__restrict__ e, float *__restrict__ skip, int Ctot, int c_off, int B, int C, int64_t hw, Drop d1,
+                           Drop d2) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * C * hw;
+    if (i >= n) return;
+    const int64_t s = i % hw, bc = i / hw;
+    float pv[TT], u[TT], v[TT];
+    for (int t = 0; t < TT; t++) pv[t] = p[(bc * TT + t) * hw + s];
+    for (int j = 0; j < TT; j++) {
+        float a = 0.f;
+        for (int k = 0; k < TT; k++) a += pv[k] * w1[k * TT + j];
+        u[j] = fmaxf(a, 0.f) * keep(d1, (uint64_t)((bc * TT + j) * hw + s));
+    }
+    for (int j = 0; j < TT; j++) {
+        float a = 0.f;
+        for (int k = 0; k < TT; k++) a += u[k] * w2[k * TT + j];
+        v[j] = fmaxf(a, 0.f) * keep(d2, (uint64_t)((bc * TT + j) * hw + s));
+    }
+    for (int t = 0; t < TT; t++) e[(bc * TT + t) * hw + s] = fmaxf(v[t] + pv[t], 0.f);
+    if (skip) {
+        const int64_t b = bc / C, c = bc % C;
+        skip[(b * Ctot + c_off + c) * hw + s] = fmaxf(v[0] + pv[0], 0.f);
+    }
+}
+
+// PointWiseTN backward: recomputes the forward from p, takes de (full T, may be null) plus the concat buffer's gradient of the
+// t = 0 slice (dskip, may be null), writes dp and one slab of the 32 weight gradients (w1 then w2) per workgroup.
+__global__ void k_tmix_bwd(const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
+                           const float *__restrict__ de, const float *__restrict__ dskip, int Ctot, int c_off, float *__restrict__ dp,
+                           float *__restrict__ slab, int B, int C, int64_t hw, int64_t chunk, Drop d1, Drop d2) {
+    __shared__ float red[32][BLK + 1];
+    float gw[32];
+    for (int q = 0; q < 32; q++) gw[q] = 0.f;
+    const int64_t n = (int64_t)B * C * hw;
+    const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
+    for (int64_t i = i0 + threadIdx.x; i < i1; i += BLK) {
+        const int64_t s = i % hw, bc = i / hw;
+        float pv[TT], pu[TT], m1[TT], u[TT], pvv[TT], m2[TT], o[TT];
+        for (int t = 0; t < TT; t++) pv[t] = p[(bc * TT + t) * hw + s];
+        for (int j = 0; j < TT; j++) {
+            float a = 0.f;
+            for (int k = 0; k < TT; k++) a += pv[k] * w1[k * TT + j];
+            pu[j] = a;
+            m1[j] = keep(d1, (uint64_t)((bc * TT + j) * hw + s));
+            u[j] = fmaxf(a, 0.f) * m1[j];
+        }
+        for (int j = 0; j < TT; j++) {
+            float a = 0.f;
+            for (int k = 0; k < TT; k++) a += u[k] * w2[k * TT + j];
+            pvv[j] = a;
+            m2[j] = keep(d2, (uint64_t)((bc * TT + j) * hw + s));
+            o[j] = fmaxf(a, 0.f) * m2[j] + pv[j];
+        }
+        float dov[TT], dpre2[TT], du[TT], dpre1[TT], dpv[TT];
+        for (int t = 0; t < TT; t++) {
+            float g = de ? de[(bc * TT + t) * hw + s] : 0.f;
+            if (t == 0 && dskip) {
+                const int64_t b = bc / C, c = bc % C;
+                g += dskip[(b * Ctot + c_off + c) * hw + s];
+            }
+            dov[t] = o[t] > 0.f ? g : 0.f;
+            dpv[t] = dov[t];
+            dpre2[t] = pvv[t] > 0.f ? dov[t] * m2[t] : 0.f;
+        }
+        for (int k = 0; k < TT; k++) {
+            float a = 0.f;
+            for (int j = 0; j < TT; j++) {
+                gw[16 + k * TT + j] += u[k] * dpre2[j];
+                a += dpre2[j] * w2[k * TT + j];
+            }
+            du[k] = a;
+        }
+        for (int j = 0; j < TT; j++) dpre1[j] = pu[j] > 0.f ? du[j] * m1[j] : 0.f;
+        for (int k = 0; k < TT; k++) {
+            float a = 0.f;
+            for (int j = 0; j < TT; j++) {
+                gw[k * TT + j] += pv[k] * dpre1[j];
+                a += dpre1[j] * w1[k * TT + j];
+            }
+            dp[(bc * TT + k) * hw + s] = dpv[k] + a;
+        }
+    }
+    for (int q = 0; q < 32; q++) red[q][threadIdx.x] = gw[q];
+    __syncthreads();
+    for (int w = BLK / 2; w > 0; w >>= 1) {
+        if (threadIdx.x < w)
+            for (int q = 0; q < 32; q++) red[q][threadIdx.x] += red[q][threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x < 32) slab[(int64_t)blockIdx.x * 32 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// decoder block input: zd = dropout(relu(z)), index = NCHW of z
+__global__ void k_drop_relu(const float *__restrict__ z, float *__restrict__ zd, int64_t n, Drop d) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i >= n) return;
+    zd[i] = fmaxf(z[i], 0.f) * keep(d, (uint64_t)i);
+}
+
+// convT 4x4 stride 2 (valid, output 2*in + 2) + bias, cropped at (cy, cx); K: Keras [4][4][Co][Ci]
+__global__ void k_convT_fwd(const float *__restrict__ zd, const float *__restrict__ K, const float *__restrict__ bias,
+                            float *__restrict__ y, int B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * Co * Ho * Wo;
+    if (i >= n) return;
+    const int ox = (int)(i % Wo) + cx, oy = (int)((i / Wo) % Ho) + cy;
+    const int co = (int)((i / ((int64_t)Ho * Wo)) % Co);
+    const int64_t b = i / ((int64_t)Ho * Wo * Co);
+    float acc = bias[co];
+    for (int ky = oy & 1; ky < 4; ky += 2) {
+        const int iy = (oy - ky) >> 1;
+        if (iy < 0 || iy >= Hi) continue;
+        for (int kx = ox & 1; kx < 4; kx += 2) {
+            const int ix = (ox - kx) >> 1;
+            if (ix < 0 || ix >= Wi) continue;
+            const float *kp = K + ((ky * 4 + kx) * Co + co) * Ci;
+            const float *zp = zd + b * Ci * Hi * Wi + (int64_t)iy * Wi + ix;
+            for (int ci = 0; ci < Ci; ci++) acc += zp[(int64_t)ci * Hi * Wi] * kp[ci];
+        }
+    }
+    y[i] = acc;
+}
+
+// gradient of the block input z: convT data gradient times the dropout mask and relu(z)'
+__global__ void k_convT_dgrad(const float *__restrict__ dy, const float *__restrict__ K, const float *__restrict__ z,
+                              float *__restrict__ dz, int B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, Drop d) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * Ci * Hi * Wi;
+    if (i >= n) return;
+    const float m = z[i] > 0.f ? keep(d, (uint64_t)i) : 0.f;
+    if (m == 0.f) {
+        dz[i] = 0.f;
+        return;
+    }
+    const int ix = (int)(i % Wi), iy = (int)((i / Wi) % Hi);
+    const int ci = (int)((i / ((int64_t)Hi * Wi)) % Ci);
+    const int64_t b = i / ((int64_t)Hi * Wi * Ci);
+    float acc = 0.f;
+    for (int ky = 0; ky < 4; ky++) {
+        const int yy = 2 * iy + ky - cy;
+        if (yy < 0 || yy >= Ho) continue;
+        for (int kx = 0; kx < 4; kx++) {
+            const int xx = 2 * ix + kx - cx;
+            if (xx < 0 || xx >= Wo) continue;
+            const float *gp = dy + b * Co * Ho * Wo + (int64_t)yy * Wo + xx;
+            const float *kp = K + (ky * 4 + kx) * Co * Ci + ci;
+            for (int co = 0; co < Co; co++) acc += gp[(int64_t)co * Ho * Wo] * kp[co * Ci];
+        }
+    }
+    dz[i] = acc * m;
+}
+
+// dK slabs of the convT: one thread per weight [ky][kx][co][ci], slab = a range of the B*Hi*Wi input positions
+__global__ void k_convT_wgrad(const float *__restrict__ zd, const float *__restrict__ dy, float *__restrict__ slab, int B, int Ci,
+                              int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, int64_t chunk) {
+    const int nw = 16 * Co * Ci;
+    const int wi = blockIdx.x * BLK + threadIdx.x;
+    if (wi >= nw) return;
+    const int ci = wi % Ci, co = (wi / Ci) % Co, kk = wi / (Ci * Co), ky = kk / 4, kx = kk % 4;
+    const int64_t hwi = (int64_t)Hi * Wi, P = (int64_t)B * hwi;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+    float acc = 0.f;
+    for (int64_t p = p0; p < p1; p++) {
+        const int64_t b = p / hwi, s = p % hwi;
+        const int iy = (int)(s / Wi), ix = (int)(s % Wi);
+        const int yy = 2 * iy + ky - cy, xx = 2 * ix + kx - cx;
+        if (yy < 0 || yy >= Ho || xx < 0 || xx >= Wo) continue;
+        acc += zd[(b * Ci + ci) * hwi + s] * dy[((b * Co + co) * Ho + yy) * (int64_t)Wo + xx];
+    }
+    slab[(int64_t)blockIdx.y * nw + wi] = acc;
+}
+
+// decoder BN apply into channels [0, C) of the next block's concat buffer (Ctot channels)
+__global__ void k_bn_apply(const float *__restrict__ y, const float *__restrict__ stat, const float *__restrict__ gamma,
+                           const float *__restrict__ beta, float *__restrict__ z, int Ctot, int B, int C, int64_t S) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * C * S;
+    if (i >= n) return;
+    const int64_t s = i % S;
+    const int ch = (int)((i / S) % C);
+    const int64_t b = i / (S * C);
+    z[(b * Ctot + ch) * S + s] = (y[i] - stat[ch]) * stat[C + ch] * gamma[ch] + beta[ch];
+}
+
+// 1x1 conv 16 -> 1 of the last block's output: logits [B][H*W]
+__global__ void k_final_fwd(const float *__restrict__ y, const float *__restrict__ fk, const float *__restrict__ fb,
+                            float *__restrict__ logit, int B, int64_t hw) {
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i >= (int64_t)B * hw) return;
+    const int64_t b = i / hw, s = i % hw;
+    float acc = fb[0];
+    for (int c = 0; c < 16; c++) acc += y[(b * 16 + c) * hw + s] * fk[c];
+    logit[i] = acc;
+}
+
+// loss = mean over samples of (1 - (I + sm) / (S - I + sm)) * sm; red = [I per sample][S per sample]
+__global__ void k_loss(const float *__restrict__ red, int B, float sm, float *__restrict__ loss) {
+    if (threadIdx.x || blockIdx.x) return;
+    float acc = 0.f;
+    for (int b = 0; b < B; b++) {
+        const float I = red[b], S = red[B + b];
+        acc += (1.f - (I + sm) / (S - I + sm)) * sm;
+    }
+    loss[0] = acc / (float)B;
+}
+
+// d loss / d logit and d loss / d y3 (= dlogit * final kernel); TP / FP / FN counts at sigmoid > 0.5 (integer atomics)
+__global__ void k_final_bwd(const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
+                            const float *__restrict__ fk, float *__restrict__ dlogit, float *__restrict__ dy, int B, int64_t hw,
+                            float sm, unsigned long long *__restrict__ counts) {
+    __shared__ unsigned cnt[3];
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i < (int64_t)B * hw) {
+        const int64_t b = i / hw, s = i % hw;
+        const float l = logit[i];
+        const float pr = 1.f / (1.f + expf(-l));
+        const float yv = (float)gt[i];
+        const float I = red[b], S = red[B + b];
+        const float Nn = I + sm, D = S - I + sm;
+        const float dp = -(sm / (float)B) * (yv * D - Nn * (1.f - yv)) / (D * D);
+        const float dl = dp * pr * (1.f - pr);
+        dlogit[i] = dl;
+        for (int c = 0; c < 16; c++) dy[(b * 16 + c) * hw + s] = dl * fk[c];
+        const bool pos = pr > 0.5f, lab = gt[i] != 0;
+        if (pos && lab) atomicAdd(&cnt[0], 1u);
+        if (pos && !lab) atomicAdd(&cnt[1], 1u);
+        if (!pos && lab) atomicAdd(&cnt[2], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
+// Keras Adam over the flat parameter buffer; lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) from the host
+__global__ void k_adam(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                       const uint8_t *__restrict__ trainable, int n, float lr_t, float b1, float b2, float eps) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (i >= n || !trainable[i]) return;
+    const float gi = g[i];
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
+// ------------------------------------------------------------------------------------------------ host state
+struct EncOff { size_t k, b, gamma, beta, mean, var, w1, w2; };
+struct DecOff { size_t k, b, gamma, beta, mean, var; };
+
+}  // namespace
+
+struct covahip_train {
+    covahip_ctx *ctx = nullptr;
+    covahip_train_cfg cfg{};
+    int H[NL + 1], W[NL + 1];
+    int cy[NL], cx[NL];
+    EncOff eo[NL];
+    DecOff dof[NL];
+    size_t fk = 0, fb = 0;
+    int64_t step = 0;          // steps taken (Adam's t - 1, the dropout hash's step)
+    std::vector<void *> allocs;
+    float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
+    uint8_t *trainable = nullptr;
+    // activations ([B][C][T][H][W] encoder, [B][C][H][W] decoder) and their gradients
+    float *x0 = nullptr, *c[NL] = {}, *p[NL] = {}, *e[NL] = {};
+    int8_t *arg[NL] = {};
+    float *z[NL] = {}, *zd[NL] = {}, *y[NL] = {}, *logit = nullptr;
+    float *dc[NL] = {}, *dp[NL] = {}, *de[NL] = {}, *dz[NL] = {}, *dy[NL] = {}, *dlogit = nullptr;
+    float *stat = nullptr;     // [7 BN layers][2][128]: mean, invstd
+    float *red = nullptr;      // [2][max(128, max_batch)]: BN backward sums / per-sample loss sums
+    float *slab = nullptr;
+    size_t slab_floats = 0;
+    float *d_loss = nullptr;
+    unsigned long long *d_counts = nullptr;
+    uint8_t *d_stack = nullptr, *d_gt = nullptr;
+    float *h_out = nullptr;    // pinned: loss + counts
+    long long last_counts[3] = {0, 0, 0};
+};
+
+namespace {
+
+template <class T>
+int talloc(covahip_train *tr, T **p, size_t n) {
+    void *q = nullptr;
+    COVAHIP_CHECK_HIP(tr->ctx, hipMalloc(&q, n * sizeof(T) > 0 ? n * sizeof(T) : 16));
+    tr->allocs.push_back(q);
+    *p = (T *)q;
+    return COVAHIP_OK;
+}
+
+void free_train(covahip_train *tr) {
+    for (void *q : tr->allocs) hipFree(q);
+    if (tr->h_out) hipHostFree(tr->h_out);
+    delete tr;
+}
+
+void layout(covahip_train *tr) {
+    size_t off = 0;
+    for (int i = 0; i < NL; i++) {
+        const size_t ci = ENC_C[i], co = ENC_C[i + 1];
+        EncOff &o = tr->eo[i];
+        o.k = off; off += 9 * ci * co;
+        o.b = off; off += co;
+        o.gamma = off; off += co;
+        o.beta = off; off += co;
+        o.mean = off; off += co;
+        o.var = off; off += co;
+        o.w1 = off; off += TT * TT;
+        o.w2 = off; off += TT * TT;
+    }
+    for (int j = 0; j < NL; j++) {
+        const size_t ci = DEC_CI[j], co = DEC_CO[j];
+        DecOff &o = tr->dof[j];
+        o.k = off; off += 16 * co * ci;
+        o.b = off; off += co;
+        if (j < NL - 1) {
+            o.gamma = off; off += co;
+            o.beta = off; off += co;
+            o.mean = off; off += co;
+            o.var = off; off += co;
+        }
+    }
+    tr->fk = off; off += 16;
+    tr->fb = off; off += 1;
+}
+
+Drop make_drop(const covahip_train *tr, int site) {
+    const double p = tr->cfg.dropout;
+    Drop d;
+    d.key = drop_key(tr->cfg.seed, (uint64_t)tr->step, site);
+    d.thr = (uint32_t)std::llround(p * 16777216.0);
+    d.scale = (float)(1.0 / (1.0 - p));
+    return d;
+}
+
+// slabs of a channel reduction over N*S elements per channel
+inline int red_slabs(int64_t M) {
+    int64_t np = (M + RED_CHUNK - 1) / RED_CHUNK;
+    return (int)(np < 1 ? 1 : np);
+}
+inline int wg_slabs(int64_t P) {   // at most 4096 slabs (the grid's y extent), longer ones on large grids
+    int64_t ns = (P + WG_CHUNK - 1) / WG_CHUNK;
+    return (int)(ns < 1 ? 1 : ns > 4096 ? 4096 : ns);
+}
+
+struct Run {
+    covahip_train *tr;
+    hipStream_t s;
+    int rc = COVAHIP_OK;
+    bool ok() {
+        if (rc) return false;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) {
+            tr->ctx->last_hip_error = std::string("train kernel launch: ") + hipGetErrorString(e);
+            rc = COVAHIP_ERR_HIP;
+        }
+        return rc == COVAHIP_OK;
+    }
+    // per-channel reduction of [N][C][S] + finalize
+    void reduce(int mode, int N, int C, int64_t S, const float *x, const float *g, int Cg, const float *aux, const uint8_t *gt,
+                int fmode, float *stat, float *g0, float *g1, float *mov0, float *mov1) {
+        const int64_t M = (int64_t)N * S;
+        const int NP = red_slabs(M);
+        const int64_t chunk = (M + NP - 1) / NP;
+        k_reduce<<<dim3(NP, C), BLK, 0, s>>>(mode, N, C, S, x, g, Cg, aux, gt, tr->slab, NP, chunk);
+        k_finalize<<<nblk(C), BLK, 0, s>>>(fmode, C, NP, tr->slab, (double)M, stat, g0, g1, mov0, mov1, tr->cfg.bn_momentum,
+                                           tr->cfg.bn_eps);
+    }
+};
+
+int run_step(covahip_train *tr, int B, float lr) {
+    Run r{tr, tr->ctx->stream};
+    const hipStream_t s = r.s;
+    float *P = tr->params, *G = tr->grads;
+    const int H0 = tr->H[0], W0 = tr->W[0];
+    const float sm = tr->cfg.smooth;
+    auto stat = [&](int layer) { return tr->stat + layer * 256; };
+    if (hipMemsetAsync(tr->d_counts, 0, 3 * sizeof(unsigned long long), s) != hipSuccess) return COVAHIP_ERR_HIP;
+
+    // ---------------------------------------------------------------- forward
+    k_input<<<nblk((int64_t)B * 3 * TT * H0 * W0), BLK, 0, s>>>(tr->d_stack, tr->x0, B, H0, W0);
+    for (int i = 0; i < NL; i++) {
+        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
+        const EncOff &o = tr->eo[i];
+        const float *xin = i ? tr->e[i - 1] : tr->x0;
+        const int64_t S = (int64_t)TT * H * W;
+        k_conv3_fwd<<<nblk(B * Co * S), BLK, 0, s>>>(xin, P + o.k, P + o.b, tr->c[i], B, Ci, Co, H, W);
+        r.reduce(R_SUM, B, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), nullptr, nullptr, nullptr, nullptr);
+        r.reduce(R_SQDEV, B, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), G + o.mean, G + o.var, P + o.mean,
+                 P + o.var);
+        k_bn_pool<<<nblk((int64_t)B * Co * TT * Hp * Wp), BLK, 0, s>>>(tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
+                                                                      B, Co, H, W, Hp, Wp);
+        const int zj = NL - 1 - i;   // the decoder block whose input concat holds this level's t = 0 slice
+        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
+        k_tmix_fwd<<<nblk((int64_t)B * Co * Hp * Wp), BLK, 0, s>>>(tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
+                                                                 B, Co, (int64_t)Hp * Wp, make_drop(tr, 2 * i), make_drop(tr, 2 * i + 1));
+        if (!r.ok()) return r.rc;
+    }
+    for (int j = 0; j < NL; j++) {
+        const int Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
+        const DecOff &o = tr->dof[j];
+        const int64_t nin = (int64_t)B * Ci * Hi * Wi, So = (int64_t)Ho * Wo;
+        k_drop_relu<<<nblk(nin), BLK, 0, s>>>(tr->z[j], tr->zd[j], nin, make_drop(tr, 2 * NL + j));
+        k_convT_fwd<<<nblk(B * Co * So), BLK, 0, s>>>(tr->zd[j], P + o.k, P + o.b, tr->y[j], B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                      tr->cx[j]);
+        if (j < NL - 1) {
+            r.reduce(R_SUM, B, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), nullptr, nullptr, nullptr, nullptr);
+            r.reduce(R_SQDEV, B, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), G + o.mean, G + o.var,
+                     P + o.mean, P + o.var);
+            k_bn_apply<<<nblk(B * Co * So), BLK, 0, s>>>(tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1], B,
+                                                         Co, So);
+        }
+        if (!r.ok()) return r.rc;
+    }
+    const int64_t hw = (int64_t)H0 * W0;
+    k_final_fwd<<<nblk(B * hw), BLK, 0, s>>>(tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, B, hw);
+    r.reduce(R_LOSS, 1, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, nullptr, nullptr, nullptr, nullptr);
+    k_loss<<<1, 1, 0, s>>>(tr->red, B, sm, tr->d_loss);
+
+    // ---------------------------------------------------------------- backward
+    k_final_bwd<<<nblk(B * hw), BLK, 0, s>>>(tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], B, hw, sm,
+                                            tr->d_counts);
+    r.reduce(R_FINALW, B, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, G + tr->fk, nullptr, nullptr, nullptr);
+    r.reduce(R_SUM, B, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + tr->fb, nullptr, nullptr, nullptr);
+    if (!r.ok()) return r.rc;
+    for (int j = NL - 1; j >= 0; j--) {
+        const int Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
+        const DecOff &o = tr->dof[j];
+        const int64_t So = (int64_t)Ho * Wo;
+        if (j < NL - 1) {   // BN of this block: its output gradient is channel range [0, Co) of the next block's dz
+            r.reduce(R_BNBWD, B, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, G + o.gamma,
+                     G + o.beta, nullptr, nullptr);
+            k_bn_bwd<<<nblk(B * Co * So), BLK, 0, s>>>(tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma, tr->dy[j],
+                                                       B, Co, So, 0);
+        }
+        r.reduce(R_SUM, B, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + o.b, nullptr, nullptr, nullptr);
+        const int64_t Pp = (int64_t)B * Hi * Wi;
+        const int ns = wg_slabs(Pp);
+        const int nw = 16 * Co * Ci;
+        k_convT_wgrad<<<dim3(nblk(nw), ns), BLK, 0, s>>>(tr->zd[j], tr->dy[j], tr->slab, B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j],
+                                                        (Pp + ns - 1) / ns);
+        k_sum_slabs<<<nblk(nw), BLK, 0, s>>>(tr->slab, ns, nw, G + o.k);
+        k_convT_dgrad<<<nblk(Pp * Ci), BLK, 0, s>>>(tr->dy[j], P + o.k, tr->z[j], tr->dz[j], B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j],
+                                                   make_drop(tr, 2 * NL + j));
+        if (!r.ok()) return r.rc;
+    }
+    for (int i = NL - 1; i >= 0; i--) {
+        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
+        const EncOff &o = tr->eo[i];
+        const int zj = NL - 1 - i;
+        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
+        const int64_t n = (int64_t)B * Co * Hp * Wp;
+        const int nb = (int)std::min<int64_t>(TMIX_BLOCKS_MAX, std::max<int64_t>(1, (n + 4 * BLK - 1) / (4 * BLK)));
+        k_tmix_bwd<<<nb, BLK, 0, s>>>(tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj], DEC_CI[zj], c_off,
+                                      tr->dp[i], tr->slab, B, Co, (int64_t)Hp * Wp, (n + nb - 1) / nb, make_drop(tr, 2 * i),
+                                      make_drop(tr, 2 * i + 1));
+        k_sum_slabs<<<1, BLK, 0, s>>>(tr->slab, nb, 32, G + o.w1);
+        const int64_t S = (int64_t)TT * H * W;
+        k_pool_bwd<<<nblk(B * Co * S), BLK, 0, s>>>(tr->dp[i], tr->arg[i], tr->dc[i], B, Co, H, W, Hp, Wp);
+        r.reduce(R_BNBWD, B, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, G + o.gamma, G + o.beta, nullptr, nullptr);
+        k_bn_bwd<<<nblk(B * Co * S), BLK, 0, s>>>(tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], B, Co, S, 1);
+        r.reduce(R_SUM, B, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + o.b, nullptr, nullptr, nullptr);
+        const float *xin = i ? tr->e[i - 1] : tr->x0;
+        const int64_t Pp = (int64_t)B * S;
+        const int ns = wg_slabs(Pp);
+        const int nw = 9 * Ci * Co;
+        k_conv3_wgrad<<<dim3(nblk(nw), ns), BLK, 0, s>>>(tr->dc[i], xin, tr->slab, B, Ci, Co, H, W, (Pp + ns - 1) / ns);
+        k_sum_slabs<<<nblk(nw), BLK, 0, s>>>(tr->slab, ns, nw, G + o.k);
+        if (i > 0) k_conv3_dgrad<<<nblk((int64_t)B * Ci * S), BLK, 0, s>>>(tr->dc[i], P + o.k, tr->de[i - 1], B, Ci, Co, H, W);
+        if (!r.ok()) return r.rc;
+    }
+
+    // ---------------------------------------------------------------- Adam
+    const double t = (double)(tr->step + 1);
+    const double lr_t = lr * std::sqrt(1.0 - std::pow((double)tr->cfg.beta2, t)) / (1.0 - std::pow((double)tr->cfg.beta1, t));
+    k_adam<<<nblk((int64_t)N_PARAMS), BLK, 0, s>>>(P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, (float)lr_t, tr->cfg.beta1,
+                                                   tr->cfg.beta2, tr->cfg.eps);
+    if (!r.ok()) return r.rc;
+    return COVAHIP_OK;
+}
+
+bool finite_pos(float v) { return std::isfinite(v) && v > 0.f; }
+
+int validate_cfg(const covahip_train_cfg *c) {
+    if (c->h_mb < 16 || c->w_mb < 16 || c->h_mb > 1024 || c->w_mb > 1024 || c->max_batch <= 0) return COVAHIP_ERR_INVALID_ARG;
+    if (!std::isfinite(c->lr) || c->lr < 0.f) return COVAHIP_ERR_INVALID_ARG;
+    if (!(c->beta1 >= 0.f && c->beta1 < 1.f) || !(c->beta2 >= 0.f && c->beta2 < 1.f) || !finite_pos(c->eps)) return COVAHIP_ERR_INVALID_ARG;
+    if (!(c->bn_momentum >= 0.f && c->bn_momentum <= 1.f) || !finite_pos(c->bn_eps)) return COVAHIP_ERR_INVALID_ARG;
+    if (!(c->dropout >= 0.f && c->dropout < 1.f) || !finite_pos(c->smooth)) return COVAHIP_ERR_INVALID_ARG;
+    return COVAHIP_OK;
+}
+
+int create_body(covahip_train *tr, const float *h_w) {
+    covahip_ctx *ctx = tr->ctx;
+    const covahip_train_cfg &cf = tr->cfg;
+    const int64_t B = cf.max_batch;
+    tr->H[0] = cf.h_mb;
+    tr->W[0] = cf.w_mb;
+    for (int i = 0; i < NL; i++) {
+        tr->H[i + 1] = (tr->H[i] + 1) / 2;
+        tr->W[i + 1] = (tr->W[i] + 1) / 2;
+    }
+    for (int j = 0; j < NL; j++) {   // convT output 2 * in + 2, surplus cropped ceil(p / 2) top / left (decoder.py)
+        const int ph = 2 * tr->H[NL - j] + 2 - tr->H[NL - 1 - j], pw = 2 * tr->W[NL - j] + 2 - tr->W[NL - 1 - j];
+        if (ph < 0 || pw < 0) return COVAHIP_ERR_UNSUPPORTED;
+        tr->cy[j] = ph / 2 + ph % 2;
+        tr->cx[j] = pw / 2 + pw % 2;
+    }
+    layout(tr);
+    int rc;
+#define TA(p, n) if ((rc = talloc(tr, &(p), (size_t)(n)))) return rc
+    TA(tr->params, N_PARAMS);
+    TA(tr->grads, N_PARAMS);
+    TA(tr->adam_m, N_PARAMS);
+    TA(tr->adam_v, N_PARAMS);
+    TA(tr->trainable, N_PARAMS);
+    const int64_t hw0 = (int64_t)tr->H[0] * tr->W[0];
+    TA(tr->x0, B * 3 * TT * hw0);
+    size_t slab = 0;
+    for (int i = 0; i < NL; i++) {
+        const int64_t Co = ENC_C[i + 1], S = (int64_t)TT * tr->H[i] * tr->W[i], Sp = (int64_t)TT * tr->H[i + 1] * tr->W[i + 1];
+        TA(tr->c[i], B * Co * S);
+        TA(tr->dc[i], B * Co * S);
+        TA(tr->p[i], B * Co * Sp);
+        TA(tr->arg[i], B * Co * Sp);
+        TA(tr->e[i], B * Co * Sp);
+        TA(tr->dp[i], B * Co * Sp);
+        TA(tr->de[i], B * Co * Sp);
+        slab = std::max(slab, (size_t)Co * red_slabs(B * S) * 2);
+        slab = std::max(slab, (size_t)9 * ENC_C[i] * Co * wg_slabs(B * S));
+        slab = std::max(slab, (size_t)TMIX_BLOCKS_MAX * 32);
+    }
+    for (int j = 0; j < NL; j++) {
+        const int64_t Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int64_t Si = (int64_t)tr->H[NL - j] * tr->W[NL - j], So = (int64_t)tr->H[NL - 1 - j] * tr->W[NL - 1 - j];
+        TA(tr->z[j], B * Ci * Si);
+        TA(tr->zd[j], B * Ci * Si);
+        TA(tr->dz[j], B * Ci * Si);
+        TA(tr->y[j], B * Co * So);
+        TA(tr->dy[j], B * Co * So);
+        slab = std::max(slab, (size_t)Co * red_slabs(B * So) * 2);
+        slab = std::max(slab, (size_t)16 * Ci * Co * wg_slabs(B * Si));
+    }
+    slab = std::max(slab, (size_t)B * red_slabs(hw0) * 2);
+    TA(tr->logit, B * hw0);
+    TA(tr->dlogit, B * hw0);
+    TA(tr->stat, 7 * 256);
+    TA(tr->red, 2 * std::max<int64_t>(128, B));
+    TA(tr->slab, slab);
+    tr->slab_floats = slab;
+    TA(tr->d_loss, 1);
+    TA(tr->d_counts, 3);
+    TA(tr->d_stack, B * TT * hw0 * 4);
+    TA(tr->d_gt, B * hw0);
+#undef TA
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_out, 16 * sizeof(float), hipHostMallocDefault));
+    // BN moving statistics are not trained
+    std::vector<uint8_t> tmask(N_PARAMS, 1);
+    for (int i = 0; i < NL; i++) std::fill(tmask.begin() + tr->eo[i].mean, tmask.begin() + tr->eo[i].w1, 0);
+    for (int j = 0; j < NL - 1; j++) std::fill(tmask.begin() + tr->dof[j].mean, tmask.begin() + tr->dof[j].var + DEC_CO[j], 0);
+    const hipStream_t s = ctx->stream;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params, h_w, N_PARAMS * sizeof(float), hipMemcpyHostToDevice, s));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->trainable, tmask.data(), N_PARAMS, hipMemcpyHostToDevice, s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_m, 0, N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_v, 0, N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // tmask leaves scope
+    return COVAHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void covahip_train_default_cfg(covahip_train_cfg *cfg) {
+    if (!cfg) return;
+    cfg->h_mb = 45;
+    cfg->w_mb = 80;
+    cfg->max_batch = 4;
+    cfg->lr = 1e-3f;
+    cfg->beta1 = 0.9f;
+    cfg->beta2 = 0.999f;
+    cfg->eps = 1e-7f;
+    cfg->bn_momentum = 0.99f;
+    cfg->bn_eps = 1e-3f;
+    cfg->dropout = 0.2f;
+    cfg->smooth = 100.f;
+    cfg->seed = 0;
+}
+
+int covahip_train_create(covahip_ctx *ctx, const covahip_train_cfg *cfg, const void *cvhw, size_t cvhw_bytes, covahip_train **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !cfg || !cvhw || !out) return COVAHIP_ERR_INVALID_ARG;
+    if (int rc = validate_cfg(cfg)) return rc;
+    if (cvhw_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
+    uint32_t hdr[16];
+    std::memcpy(hdr, cvhw, 64);
+    static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
+    for (int i = 0; i < 13; i++)
+        if (hdr[i] != want[i]) return COVAHIP_ERR_BAD_WEIGHTS;
+    if (cvhw_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    covahip_train *tr = new covahip_train();
+    tr->ctx = ctx;
+    tr->cfg = *cfg;
+    const int rc = create_body(tr, reinterpret_cast<const float *>(static_cast<const uint8_t *>(cvhw) + 64));
+    if (rc) {
+        hipStreamSynchronize(ctx->stream);
+        (void)hipGetLastError();
+        free_train(tr);
+        return rc;
+    }
+    *out = tr;
+    return COVAHIP_OK;
+}
+
+int covahip_train_step(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, int batch, float lr, float *loss, int mem_kind) {
+    if (!tr || !stack || !gt || !loss || batch <= 0 || batch > tr->cfg.max_batch || !std::isfinite(lr) || lr < 0.f)
+        return COVAHIP_ERR_INVALID_ARG;
+    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    const size_t hw = (size_t)tr->H[0] * tr->W[0];
+    const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)batch * TT * hw * 4, kind, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)batch * hw, kind, ctx->stream));
+    if (int rc = run_step(tr, batch, lr)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_out, tr->d_loss, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_out + 2, tr->d_counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    *loss = tr->h_out[0];
+    unsigned long long cnt[3];
+    std::memcpy(cnt, tr->h_out + 2, sizeof(cnt));
+    for (int k = 0; k < 3; k++) tr->last_counts[k] = (long long)cnt[k];
+    tr->step++;
+    return COVAHIP_OK;
+}
+
+int covahip_train_metrics(covahip_train *tr, int64_t tp_fp_fn[3]) {
+    if (!tr || !tp_fp_fn) return COVAHIP_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; k++) tp_fp_fn[k] = tr->last_counts[k];
+    return COVAHIP_OK;
+}
+
+int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n) {
+    if (!tr || !n) return COVAHIP_ERR_INVALID_ARG;
+    const size_t need = 64 + N_PARAMS * sizeof(float);
+    *n = need;
+    if (!cvhw || cap < need) return COVAHIP_ERR_OVERFLOW;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    const uint32_t hdr[16] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS, 0, 0, 0};
+    std::memcpy(cvhw, hdr, 64);
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + 64, tr->params, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost,
+                                          ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return COVAHIP_OK;
+}
+
+int covahip_train_grads(covahip_train *tr, float *flat, size_t n) {
+    if (!tr || !flat || n != N_PARAMS) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(flat, tr->grads, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return COVAHIP_OK;
+}
+
+void covahip_train_destroy(covahip_train *tr) {
+    if (!tr) return;
+    hipSetDevice(tr->ctx->device);
+    covahip_sync_all(tr->ctx);
+    free_train(tr);
+}
+
+}  // extern "C"

@@ -1,0 +1,402 @@
+"""BlobNet training for the front end this build runs behind (utils/train-blobnet.py, utils/data/*.py of the reference).
+
+  read_tfrecords  TFRecord files as `tfrecordsink` / covahip_tfrecord_example write them -> frames + labels
+  slide           utils/data/slide.py slide_dataset(skip=True): non-overlapping stacks of T = 4 frames, newest first
+  init_weights    the Keras default initialisation of the reference model, as a flat weight array (cova_amd/weights.py order)
+  Trainer         the training step on the GPU (covahip_train_*: forward, backward and Adam in HIP) and the epoch loop
+
+    python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
+
+writes a weight file that covahip_blobnet_load / BlobNetInfer / the blobnetfilter element load unchanged.
+No TensorFlow or protobuf is needed: the record framing and the Example message are parsed here.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import functools
+import math
+import struct
+import sys
+
+import numpy as np
+
+from . import _lib as L
+from . import weights as W
+
+FEATURES = ("mb_type", "mv_x", "mv_y", "gt")
+
+# ------------------------------------------------------------------------------------------------ TFRecord reader
+_CRC_TABLE = []
+for _i in range(256):
+    _c = _i
+    for _ in range(8):
+        _c = (_c >> 1) ^ 0x82F63B78 if _c & 1 else _c >> 1
+    _CRC_TABLE.append(_c)
+
+
+_CRC_NP = np.array(_CRC_TABLE, dtype=np.uint32)
+
+
+def _crc_raw_bytes(c: int, data) -> int:
+    """The CRC register after `data`, one byte at a time from register c (no pre / post inversion)."""
+    tab = _CRC_TABLE
+    for b in data:
+        c = tab[(c ^ b) & 0xFF] ^ (c >> 8)
+    return c
+
+
+@functools.lru_cache(maxsize=16)
+def _shift_tables(n: int) -> np.ndarray:
+    """[4][256] tables of the linear map 'register after n zero bytes': shift(r) = xor of T[k][(r >> 8k) & 255]."""
+    basis = np.array([1 << i for i in range(32)], dtype=np.uint32)
+    r = basis.copy()
+    for _ in range(n):
+        r = _CRC_NP[r & 0xFF] ^ (r >> np.uint32(8))
+    tabs = np.zeros((4, 256), dtype=np.uint32)
+    v = np.arange(256, dtype=np.uint32)
+    for k in range(4):
+        for bit in range(8):
+            tabs[k] ^= np.where((v >> np.uint32(bit)) & np.uint32(1), r[8 * k + bit], np.uint32(0))
+    return tabs
+
+
+def crc32c(data: bytes) -> int:
+    """CRC-32C (Castagnoli, reflected), as TFRecord frames use it.
+
+    Long inputs are cut into n equal chunks whose registers (from 0) are computed side by side in numpy; the register is
+    linear over GF(2), so the chunks fold in order as r = shift_L(r) ^ chunk_k, with shift_L the map of L zero bytes.
+    About 30 MB/s on a one-frame 45x80 record, 60 MB/s on an eight-frame one, 150 MB/s on 1 MB (a byte loop: 10 MB/s)."""
+    data = memoryview(data).cast("B")
+    size = len(data)
+    if size < 2048:
+        return _crc_raw_bytes(0xFFFFFFFF, data) ^ 0xFFFFFFFF
+    L = 1 << max(5, (int(math.isqrt(size)) // 2).bit_length() - 1)   # chunk length: a power of two near sqrt(size) / 2
+    n = size // L
+    chunks = np.frombuffer(data[:n * L], dtype=np.uint8).reshape(n, L)
+    r = np.zeros(n, dtype=np.uint32)
+    for j in range(L):
+        r = _CRC_NP[(r ^ chunks[:, j]) & 0xFF] ^ (r >> np.uint32(8))
+    t0, t1, t2, t3 = (list(map(int, t)) for t in _shift_tables(L))
+    c = 0xFFFFFFFF
+    for ck in r.tolist():
+        c = t0[c & 0xFF] ^ t1[(c >> 8) & 0xFF] ^ t2[(c >> 16) & 0xFF] ^ t3[c >> 24] ^ ck
+    return _crc_raw_bytes(c, data[n * L:]) ^ 0xFFFFFFFF
+
+
+def masked_crc32c(data: bytes) -> int:
+    c = crc32c(data)
+    return (((c >> 15) | (c << 17)) + 0xA282EAD8) & 0xFFFFFFFF
+
+
+def _varint(buf: bytes, pos: int):
+    v = shift = 0
+    while True:
+        if pos >= len(buf):
+            raise ValueError("truncated varint")
+        b = buf[pos]
+        pos += 1
+        v |= (b & 0x7F) << shift
+        if not b & 0x80:
+            return v, pos
+        shift += 7
+        if shift > 63:
+            raise ValueError("varint too long")
+
+
+def _fields(buf: bytes):
+    """(field number, payload) of the length-delimited fields of a protobuf message; other wire types are skipped."""
+    pos = 0
+    while pos < len(buf):
+        key, pos = _varint(buf, pos)
+        field, wt = key >> 3, key & 7
+        if wt == 2:
+            n, pos = _varint(buf, pos)
+            if pos + n > len(buf):
+                raise ValueError("truncated field")
+            yield field, buf[pos:pos + n]
+            pos += n
+        elif wt == 0:
+            _, pos = _varint(buf, pos)
+        elif wt == 1:
+            pos += 8
+        elif wt == 5:
+            pos += 4
+        else:
+            raise ValueError(f"unsupported wire type {wt}")
+    if pos != len(buf):
+        raise ValueError("truncated message")
+
+
+def parse_example(payload: bytes) -> dict:
+    """tf.train.Example -> {feature name: [bytes, ...]} for its bytes_list features."""
+    out = {}
+    for f, features in _fields(payload):               # Example.features
+        if f != 1:
+            continue
+        for g, entry in _fields(features):             # Features.feature (map entry)
+            if g != 1:
+                continue
+            key, value = None, b""
+            for h, v in _fields(entry):
+                if h == 1:
+                    key = v.decode()
+                elif h == 2:
+                    value = v
+            strings = []
+            for k, blist in _fields(value):            # Feature.bytes_list
+                if k == 1:
+                    strings += [s for m, s in _fields(blist) if m == 1]   # BytesList.value
+            out[key] = strings
+    return out
+
+
+def iter_records(data: bytes):
+    """Payloads of a TFRecord file: u64 length, masked CRC of the length, payload, masked CRC of the payload."""
+    pos = 0
+    while pos < len(data):
+        if pos + 12 > len(data):
+            raise ValueError(f"truncated record header at byte {pos}")
+        (n,) = struct.unpack_from("<Q", data, pos)
+        (c1,) = struct.unpack_from("<I", data, pos + 8)
+        if masked_crc32c(data[pos:pos + 8]) != c1:
+            raise ValueError(f"length CRC mismatch at byte {pos}")
+        if pos + 12 + n + 4 > len(data):
+            raise ValueError(f"truncated record at byte {pos}")
+        payload = data[pos + 12:pos + 12 + n]
+        (c2,) = struct.unpack_from("<I", data, pos + 12 + n)
+        if masked_crc32c(payload) != c2:
+            raise ValueError(f"payload CRC mismatch at byte {pos}")
+        yield payload
+        pos += 12 + n + 4
+
+
+def read_tfrecords(paths, h_mb: int, w_mb: int):
+    """frames u8 [F][h][w][4] (bytes 0..2 = mb_type / mv_x / mv_y, byte 3 = 0) and gt u8 [F][h][w] of every string of
+    every record, in file and record order -- one frame per record or several (the sink's `gop` form, zero-filled strings
+    included, as utils/data/parse.py decodes them).  A CRC mismatch, a truncated record or a string of the wrong size raises."""
+    if isinstance(paths, (str, bytes)) or hasattr(paths, "__fspath__"):
+        paths = [paths]
+    hw = h_mb * w_mb
+    frames, gts = [], []
+    for path in paths:
+        with open(path, "rb") as f:
+            data = f.read()
+        for payload in iter_records(data):
+            ex = parse_example(payload)
+            missing = [k for k in FEATURES if k not in ex]
+            if missing:
+                raise ValueError(f"{path}: record lacks features {missing}")
+            n = len(ex["mb_type"])
+            if any(len(ex[k]) != n for k in FEATURES):
+                raise ValueError(f"{path}: features of different lengths")
+            for k in FEATURES:
+                for s in ex[k]:
+                    if len(s) != hw:
+                        raise ValueError(f"{path}: {k} string of {len(s)} bytes, expected {h_mb}x{w_mb}")
+            for i in range(n):
+                fr = np.zeros((h_mb, w_mb, 4), np.uint8)
+                for ch in range(3):
+                    fr[..., ch] = np.frombuffer(ex[FEATURES[ch]][i], np.uint8).reshape(h_mb, w_mb)
+                frames.append(fr)
+                gts.append(np.frombuffer(ex["gt"][i], np.uint8).reshape(h_mb, w_mb))
+    if not frames:
+        return np.zeros((0, h_mb, w_mb, 4), np.uint8), np.zeros((0, h_mb, w_mb), np.uint8)
+    return np.stack(frames), np.stack(gts)
+
+
+def slide(frames: np.ndarray, gt: np.ndarray, t: int = W.T):
+    """slide_dataset(skip=True): frames [4k..4k+3] -> one stack [4k+3, 4k+2, 4k+1, 4k] (row block i = frame newest - i, the
+    metapreprocess layout [t*h][w][4]) labelled with frame 4k+3's gt.  A trailing incomplete group is dropped."""
+    n = frames.shape[0] // t
+    f, h, w, _ = frames.shape
+    g = frames[:n * t].reshape(n, t, h, w, 4)[:, ::-1]
+    stacks = np.ascontiguousarray(g.reshape(n, t * h, w, 4))
+    labels = np.ascontiguousarray(gt[t - 1:n * t:t])
+    return stacks, labels
+
+
+# ------------------------------------------------------------------------------------------------ initialisation
+def _truncated_normal(rng, std, shape):
+    """Normal(0, std) resampled until inside 2 std (tf.random.truncated_normal)."""
+    out = rng.normal(0.0, std, shape)
+    bad = np.abs(out) > 2 * std
+    while bad.any():
+        out[bad] = rng.normal(0.0, std, int(bad.sum()))
+        bad = np.abs(out) > 2 * std
+    return out
+
+
+def he_normal(rng, fan_in, shape):
+    """Keras VarianceScaling(2, fan_in, truncated_normal): std sqrt(2 / fan_in) after the truncation at 2 sigma."""
+    return _truncated_normal(rng, math.sqrt(2.0 / fan_in) / 0.87962566103423978, shape)
+
+
+def glorot_uniform(rng, fan_in, fan_out, shape):
+    lim = math.sqrt(6.0 / (fan_in + fan_out))
+    return rng.uniform(-lim, lim, shape)
+
+
+def init_weights(seed: int = 0) -> np.ndarray:
+    """Keras-default initialisation of the reference model: he_normal conv / convT kernels (Keras fan_in: 9 * Cin for the
+    Conv3D kernel [1,3,3,Cin,Cout], 16 * Cout for the Conv3DTranspose kernel [1,4,4,Cout,Cin]), glorot_uniform Conv1D
+    kernels (fan 4 / 4) and final 1x1 kernel (fan 16 / 1), zero biases, BN gamma 1 / beta 0 / mean 0 / var 1."""
+    rng = np.random.default_rng(seed)
+    t = {}
+    for name, shape in W.tensor_specs().items():
+        kind = name.split(".", 1)[1]
+        if kind == "conv.kernel":
+            t[name] = he_normal(rng, shape[0] * shape[1] * shape[2], shape)
+        elif kind == "up.kernel":
+            t[name] = he_normal(rng, shape[0] * shape[1] * shape[2], shape)
+        elif kind in ("tmix.w1", "tmix.w2"):
+            t[name] = glorot_uniform(rng, W.T, W.T, shape)
+        elif name == "final.kernel":
+            t[name] = glorot_uniform(rng, 16, 1, shape)
+        elif kind in ("bn.gamma", "bn.var"):
+            t[name] = np.ones(shape)
+        else:                                   # biases, beta, mean
+            t[name] = np.zeros(shape)
+    return W.flatten(t)
+
+
+# ------------------------------------------------------------------------------------------------ host logic of the step
+def keras_lr(epoch: int, base: float = 1e-3) -> float:
+    """The reference's LearningRateScheduler: lr constant for epochs 0..9, times e^-0.1 at each later epoch."""
+    return base * math.exp(-0.1 * max(0, epoch - 9))
+
+
+def adam_lr_t(lr: float, step: int, beta1: float = 0.9, beta2: float = 0.999) -> float:
+    """Keras Adam's step size at step t = step + 1: lr * sqrt(1 - b2^t) / (1 - b1^t)."""
+    t = step + 1
+    return lr * math.sqrt(1.0 - beta2 ** t) / (1.0 - beta1 ** t)
+
+
+def trainable_mask() -> np.ndarray:
+    """True for every trained weight; False for the BN moving statistics."""
+    parts = []
+    for name, shape in W.tensor_specs().items():
+        parts.append(np.full(int(np.prod(shape)), not name.endswith((".bn.mean", ".bn.var"))))
+    return np.concatenate(parts)
+
+
+# ------------------------------------------------------------------------------------------------ GPU trainer
+class Trainer:
+    """BlobNet training on the GPU over covahip_train_*.  `step` counts the steps taken (the dropout hash's step)."""
+
+    def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, max_batch: int = 4, weights_flat: np.ndarray | None = None,
+                 seed: int = 0, dropout: float = 0.2, lr: float = 1e-3):
+        self.ctx, self.h, self.w, self.max_batch = ctx, h_mb, w_mb, max_batch
+        self._lib = L.lib()
+        cfg = L.TrainCfg()
+        self._lib.covahip_train_default_cfg(C.byref(cfg))
+        cfg.h_mb, cfg.w_mb, cfg.max_batch, cfg.dropout, cfg.seed, cfg.lr = h_mb, w_mb, max_batch, dropout, seed, lr
+        self.cfg = cfg
+        if weights_flat is None:
+            weights_flat = init_weights(seed)
+        blob = W.to_bytes(weights_flat)
+        h = C.c_void_p()
+        L.check(self._lib.covahip_train_create(ctx.handle, C.byref(cfg), blob, len(blob), C.byref(h)), "covahip_train_create",
+                ctx.handle)
+        self.handle = h
+        self.step_count = 0
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):      # (a trainer outliving its closed ctx is not freed)
+                self._lib.covahip_train_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def step(self, stack: np.ndarray, gt: np.ndarray, lr: float | None = None) -> float:
+        """One training step on stack u8 [B][4h][w][4] with labels u8 [B][h][w]; returns the loss before the update."""
+        stack = np.ascontiguousarray(stack, dtype=np.uint8)
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        b = stack.shape[0]
+        assert stack.shape == (b, W.T * self.h, self.w, 4) and gt.shape == (b, self.h, self.w), (stack.shape, gt.shape)
+        loss = C.c_float()
+        L.check(self._lib.covahip_train_step(self.handle, stack.ctypes.data, gt.ctypes.data, b, self.cfg.lr if lr is None else lr,
+                                             C.byref(loss), L.MEM_HOST), "covahip_train_step", self.ctx.handle)
+        self.step_count += 1
+        return float(loss.value)
+
+    def metrics(self):
+        """(TP, FP, FN) of the last step at sigmoid > 0.5."""
+        v = (C.c_int64 * 3)()
+        L.check(self._lib.covahip_train_metrics(self.handle, v), "covahip_train_metrics")
+        return int(v[0]), int(v[1]), int(v[2])
+
+    def weights(self) -> np.ndarray:
+        """The current weights (moving statistics in the BN mean / var slots), flat."""
+        return W.from_bytes(self.weights_bytes())
+
+    def weights_bytes(self) -> bytes:
+        n = C.c_size_t()
+        self._lib.covahip_train_weights(self.handle, None, 0, C.byref(n))
+        buf = np.zeros(n.value, np.uint8)
+        L.check(self._lib.covahip_train_weights(self.handle, buf.ctypes.data, n.value, C.byref(n)), "covahip_train_weights",
+                self.ctx.handle)
+        return buf.tobytes()
+
+    def grads(self) -> np.ndarray:
+        """The last step's gradients, flat; BN mean / var slots = the batch mean / biased batch variance."""
+        out = np.empty(W.N_PARAMS, np.float32)
+        L.check(self._lib.covahip_train_grads(self.handle, out.ctypes.data, out.size), "covahip_train_grads", self.ctx.handle)
+        return out
+
+    def fit(self, records, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None):
+        """records = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]) (slide's output), in order, the last batch partial as in
+        Keras.  Per epoch: the sample-weighted mean loss and precision / recall at 0.5 of the training predictions."""
+        stacks, labels = records
+        n = stacks.shape[0]
+        if n == 0:
+            raise ValueError("no training samples")
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
+        history = []
+        for ep in range(epochs):
+            lr = schedule(ep, self.cfg.lr) if schedule is keras_lr else schedule(ep)
+            tot = 0.0
+            tp = fp = fn = 0
+            for i in range(0, n, batch):
+                xb, yb = stacks[i:i + batch], labels[i:i + batch]
+                tot += self.step(xb, yb, lr) * xb.shape[0]
+                a, b_, c = self.metrics()
+                tp, fp, fn = tp + a, fp + b_, fn + c
+            rec = {"epoch": ep, "lr": lr, "loss": tot / n, "precision": tp / max(1, tp + fp), "recall": tp / max(1, tp + fn)}
+            history.append(rec)
+            if log:
+                log(f"epoch {ep + 1}/{epochs}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
+                    f"recall {rec['recall']:.4f} lr {lr:.3g}")
+        return history
+
+
+def main(argv=None) -> int:
+    ap = argparse.ArgumentParser(prog="python -m cova_amd.train", description=__doc__.split("\n")[0])
+    ap.add_argument("records", nargs="+", help="TFRecord files written by tfrecordsink gt=LABELS")
+    ap.add_argument("-o", "--output", required=True, help="weight file to write (CVHW)")
+    ap.add_argument("--epochs", type=int, default=20)
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--h-mb", type=int, default=45)
+    ap.add_argument("--w-mb", type=int, default=80)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    from .elements import Context
+
+    frames, gt = read_tfrecords(a.records, a.h_mb, a.w_mb)
+    stacks, labels = slide(frames, gt)
+    print(f"{frames.shape[0]} frames -> {stacks.shape[0]} samples of {a.h_mb}x{a.w_mb}", file=sys.stderr)
+    ctx = Context(a.device)
+    tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed)
+    tr.fit((stacks, labels), epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr))
+    with open(a.output, "wb") as f:
+        f.write(tr.weights_bytes())
+    tr.close()
+    ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -242,6 +242,60 @@ size_t covahip_frame_serialize(uint64_t range_start, uint64_t oldest, const cova
 /* Bbox::iou (bbox.rs:39-56). */
 float covahip_bbox_iou(const covahip_bbox *a, const covahip_bbox *b);
 
+/* ------------------------------------------------------------ BlobNet training
+ * One training step of the reference architecture on the GPU: what utils/train-blobnet.py does with Keras (a BlobNet has to be
+ * trained on the front end it runs behind, see the entropy-decode section).  fp32 throughout (master weights, activations,
+ * gradients); forward, backward and the optimiser are HIP kernels on the ctx's stream, ordered behind all lanes.
+ *
+ * Semantics (utils/model/{blobnet,encoder,decoder,pointwise}.py in training mode; layer order, odd-size padding and decoder crop as covahip_blobnet_forward):
+ *   - input: the u8 stack of covahip_blobnet_forward, clip(x, 0, 6) / 6 of bytes 0..2;
+ *   - encoder level: conv 3x3 + bias -> ReLU -> BatchNorm -> 2x2 max-pool (gradient to the first maximum in row-major window
+ *     order) -> zero row on top / column on the left for odd sizes -> PointWiseTN (Conv1D(4) + ReLU -> Dropout -> Conv1D(4) +
+ *     ReLU -> Dropout -> + x -> ReLU);
+ *   - decoder block: ReLU -> Dropout -> convT 4x4 stride 2 + bias -> crop; blocks 0..2 then BatchNorm -> concat with the t = 0
+ *     slice of the matching encoder level; after block 3 the 1x1 conv 16 -> 1 -> sigmoid;
+ *   - BatchNorm: batch mean and biased variance over (N, T, H, W), eps bn_eps; moving = m * moving + (1 - m) * batch, the
+ *     variance's batch value taken unbiased (n / (n - 1)) as TF's fused kernel and torch do -- the reference does not pin this;
+ *   - loss: Jaccard distance per sample, I = sum y*p, S = sum (y + p) over H x W, (1 - (I + s) / (S - I + s)) * s with
+ *     s = smooth, averaged over the batch; y = the label byte as a float;
+ *   - Adam in the Keras form: var -= lr * sqrt(1 - b2^t) / (1 - b1^t) * m / (sqrt(v) + eps); BN gamma and beta are trained,
+ *     the moving statistics are not;
+ *   - Dropout: inverted (kept values scaled by 1 / (1 - p)), p = cfg.dropout (0: off).  The mask is a counter-based hash,
+ *     no device RNG state, so a step is reproducible:
+ *         splitmix64(z): z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB;
+ *                        return z ^ z >> 31                                          (all mod 2^64)
+ *         key  = splitmix64(seed ^ splitmix64(step << 8 | site))
+ *         keep = (splitmix64(key + index) >> 40) >= round(p * 2^24)
+ *     step = steps this trainer has taken before (0 for the first); site = 2i / 2i + 1 for the two dropouts of encoder level i,
+ *     8 + j for decoder block j; index = the element's NCTHW offset in the dropped tensor: [B][C][T][H][W] of the Conv1D output
+ *     (T = its output channel) for the encoder, [B][C_in][H][W] of the block input for the decoder.
+ * Geometry: 16 <= h_mb, w_mb <= 1024.  Activation memory is sized for max_batch at creation (about 5 MB per sample at 45x80). */
+typedef struct covahip_train covahip_train;
+typedef struct covahip_train_cfg {
+    int32_t h_mb, w_mb, max_batch;
+    float lr, beta1, beta2, eps;    /* Adam (lr: what covahip_train_default_cfg's callers use; each step takes its own) */
+    float bn_momentum, bn_eps;
+    float dropout, smooth;
+    uint64_t seed;                  /* dropout hash */
+} covahip_train_cfg;
+/* The reference's settings: 45x80, batch 4, lr 1e-3, Adam 0.9 / 0.999 / 1e-7, BN 0.99 / 1e-3, dropout 0.2, smooth 100. */
+void covahip_train_default_cfg(covahip_train_cfg *cfg);
+/* cvhw: the initial weights, a weight file as covahip_blobnet_load takes it (COVAHIP_ERR_BAD_WEIGHTS otherwise). */
+int covahip_train_create(covahip_ctx *ctx, const covahip_train_cfg *cfg, const void *cvhw, size_t cvhw_bytes,
+                         covahip_train **out);
+/* One step on stack u8 [batch][4*h_mb][w_mb][4] and labels gt u8 [batch][h_mb][w_mb] (mem_kind applies to both), with learning
+ * rate lr (the epoch schedule is the caller's).  *loss = the batch's loss before the update.  Synchronous. */
+int covahip_train_step(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, int batch, float lr, float *loss, int mem_kind);
+/* True positives, false positives, false negatives of the last step's predictions at sigmoid > 0.5. */
+int covahip_train_metrics(covahip_train *tr, int64_t tp_fp_fn[3]);
+/* The current weights as a weight file (moving statistics in the BN mean / var slots); *n = its size.  COVAHIP_ERR_OVERFLOW
+ * when cvhw is NULL or cap < *n. */
+int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n);
+/* The last step's gradients, n = 320305 floats in weight-file order; the BN mean / var slots hold the step's batch mean and
+ * biased batch variance. */
+int covahip_train_grads(covahip_train *tr, float *flat, size_t n);
+void covahip_train_destroy(covahip_train *tr);
+
 /* ------------------------------------------------------ sink formats, track export
  * Data formats either side of the hot path.               */
 /* tfrecordsink (cova-rs/gst-plugins/src/tfrecordsink/imp.rs:69-198): one framed TFRecord record =

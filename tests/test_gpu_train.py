@@ -1,0 +1,246 @@
+"""BlobNet training on the GPU (covahip_train_*): gradients against torch autograd in f64, optimiser state, determinism,
+learning on labelled synthetic streams, export into the fp16 inference path, and the record -> train -> infer loop."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+from cova_amd import synth, train as T, weights as W
+from cova_amd.elements import BlobNetInfer, Context, tfrecord_example
+from tests import torch_blobnet as TB
+from tests import torch_blobnet_train as TT
+from tests.golden_util import GOLDEN, blobnet_tolerance
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = Context(0)
+    yield c
+    c.close()
+
+
+def _relerr(a, b):
+    a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+    nb = np.linalg.norm(b)
+    return np.linalg.norm(a - b) / (nb if nb > 0 else 1.0)
+
+
+def _tensor_errors(g, g_ref):
+    gu, ru = W.unflatten(g), W.unflatten(g_ref.astype(np.float32))
+    return {k: _relerr(gu[k], ru[k]) for k in gu}
+
+
+def _batch(h, w, b, seed):
+    stack = synth.stacked_batch(b, h, w, seed=seed, streams=b)
+    gt = synth.random_masks(b, h, w, 0.3, seed=seed)
+    return stack, gt
+
+
+@pytest.mark.parametrize("hw", [(45, 80), (68, 120)])
+def test_gradients_match_torch_f64(ctx, hw):
+    h, w = hw
+    seed = 11
+    flat = T.init_weights(3)
+    stack, gt = _batch(h, w, 3, 5)
+    tr = T.Trainer(ctx, h, w, max_batch=3, weights_flat=flat, seed=seed, dropout=0.2)
+    loss = tr.step(stack, gt)
+    g = tr.grads()
+    tr.close()
+    ref_loss, g_ref, _ = TT.grads_flat(flat, stack, gt, h, w, seed=seed, step=0, p=0.2)
+    assert abs(loss - ref_loss) <= 1e-5 * abs(ref_loss), (loss, ref_loss)
+    errs = _tensor_errors(g, g_ref)
+    # the convT bias of decoder blocks 0..2 feeds a training-mode BatchNorm, which subtracts it again: its exact gradient is zero
+    # and both sides hold rounding residue.  There the error is taken relative to the gradient of the BN's beta -- the sum whose
+    # cancellation the bias gradient is.
+    gu, ru = W.unflatten(g), W.unflatten(g_ref.astype(np.float32))
+    for j in range(3):
+        k = f"dec{j}.up.bias"
+        errs[k] = np.linalg.norm(gu[k].astype(np.float64) - ru[k]) / np.linalg.norm(ru[f"dec{j}.bn.beta"].astype(np.float64))
+    print(f"{h}x{w}: loss {loss:.6f} (ref {ref_loss:.6f}), worst tensor {max(errs, key=errs.get)} {max(errs.values()):.2e}")
+    bad = {k: v for k, v in errs.items() if not v <= 1e-3}
+    assert not bad, bad
+
+
+def test_optimiser_state_after_three_steps(ctx):
+    h, w, b = 45, 80, 2
+    flat = T.init_weights(4)
+    tr = T.Trainer(ctx, h, w, max_batch=b, weights_flat=flat, seed=2, dropout=0.2)
+    wts = flat.astype(np.float64).copy()
+    wts_biased = wts.copy()                 # the same moving variance updated with the biased batch variance
+    m = np.zeros_like(wts)
+    v = np.zeros_like(wts)
+    train = T.trainable_mask()
+    stat_names = [n for n in W.tensor_specs() if n.endswith((".bn.mean", ".bn.var"))]
+    lr = 1e-3
+    for k in range(3):
+        stack, gt = _batch(h, w, b, 20 + k)
+        tr.step(stack, gt, lr)
+        g = tr.grads().astype(np.float64)
+        # Adam (Keras form) on the trained weights
+        m[train] = 0.9 * m[train] + 0.1 * g[train]
+        v[train] = 0.999 * v[train] + 0.001 * g[train] ** 2
+        wts[train] -= T.adam_lr_t(lr, k) * m[train] / (np.sqrt(v[train]) + 1e-7)
+        # moving statistics: 0.99 * moving + 0.01 * batch, the variance's batch value unbiased
+        gu = W.unflatten(g)
+        off = 0
+        for name, shape in W.tensor_specs().items():
+            n = int(np.prod(shape))
+            if name in stat_names:
+                batch_v = gu[name].astype(np.float64)
+                if name.endswith(".var"):
+                    cnt = b * (W.T if name.startswith("enc") else 1) * _level_hw(name, h, w)
+                    batch_v = batch_v * cnt / (cnt - 1)
+                wts[off:off + n] = 0.99 * wts[off:off + n] + 0.01 * batch_v.reshape(-1)
+                wts_biased[off:off + n] = 0.99 * wts_biased[off:off + n] + 0.01 * gu[name].astype(np.float64).reshape(-1)
+            off += n
+    got = tr.weights()
+    tr.close()
+    errs = _tensor_errors(got, wts)
+    # the moving statistics start at mean 0 / var 1 and move by 1 % of a batch value per step: compare what they moved by, so
+    # that the n / (n - 1) of the variance update is resolved (at decoder block 0, n = 120 here: a 0.8 % change of the increment)
+    init, gu, wu, ref_biased = W.unflatten(flat), W.unflatten(got), W.unflatten(wts), W.unflatten(wts_biased)
+    for name in stat_names:
+        errs[name] = _relerr(gu[name].astype(np.float64) - init[name], wu[name] - init[name])
+        if name == "dec0.bn.var":   # the test tells the unbiased update from the biased one
+            assert _relerr(ref_biased[name] - init[name], wu[name] - init[name]) > 3e-3
+    bad = {k: v for k, v in errs.items() if not v <= 1e-3}
+    assert not bad, bad
+
+
+def _level_hw(name, h, w):
+    """H*W of the tensor a BN layer normalises: encoder level i at its conv resolution, decoder block j at its output."""
+    lv = [(h, w)]
+    for _ in range(4):
+        lv.append(((lv[-1][0] + 1) // 2, (lv[-1][1] + 1) // 2))
+    if name.startswith("enc"):
+        hh, ww = lv[int(name[3])]
+    else:
+        hh, ww = lv[3 - int(name[3])]
+    return hh * ww
+
+
+def test_bit_identical_runs(ctx):
+    h, w, b = 45, 80, 4
+    flat = T.init_weights(9)
+    outs = []
+    for _ in range(2):
+        tr = T.Trainer(ctx, h, w, max_batch=b, weights_flat=flat, seed=5, dropout=0.2)
+        losses = [tr.step(*_batch(h, w, b, 40 + k)) for k in range(10)]
+        outs.append((losses, tr.weights(), tr.grads()))
+        tr.close()
+    assert outs[0][0] == outs[1][0]
+    assert (outs[0][1].view(np.uint32) == outs[1][1].view(np.uint32)).all()
+    assert (outs[0][2].view(np.uint32) == outs[1][2].view(np.uint32)).all()
+
+
+def _ellipse_data(n_frames, h, w, seed, n_objects=6):
+    """synth.carrier_frames restated step for step (the same frames, asserted below), also returning each frame's label: the
+    union of the ellipses' insides.  The background keeps the generator's motion-vector noise (1..3 on ~10 % of the
+    macroblocks per component), so the label is the geometry, not 'mv byte nonzero'."""
+    rng = np.random.default_rng(seed)
+    f = np.zeros((n_frames, h, w, 4), dtype=np.uint8)
+    bg_type = rng.integers(0, 8, size=f.shape[:3], dtype=np.uint8)
+    f[..., 0] = np.where(rng.random(f.shape[:3]) < 0.8, 0, bg_type)
+    for c in (1, 2):
+        mv = rng.integers(1, 4, size=f.shape[:3], dtype=np.uint8)
+        f[..., c] = np.where(rng.random(f.shape[:3]) < 0.9, 0, mv)
+    f[..., 3] = rng.integers(0, 256, size=f.shape[:3], dtype=np.uint8)
+    gt = np.zeros((n_frames, h, w), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for _ in range(n_objects):
+        cy, cx = rng.uniform(0, h), rng.uniform(0, w)
+        ry, rx = rng.uniform(1, 10), rng.uniform(1, 10)
+        vy, vx = rng.uniform(-2, 2), rng.uniform(-2, 2)
+        for i in range(n_frames):
+            inside = ((yy - (cy + vy * i)) / ry) ** 2 + ((xx - (cx + vx * i)) / rx) ** 2 <= 1.0
+            n = int(inside.sum())
+            if n == 0:
+                continue
+            f[i, inside, 0] = rng.integers(1, 8, size=n, dtype=np.uint8)
+            f[i, inside, 1] = rng.integers(1, 13, size=n, dtype=np.uint8)
+            f[i, inside, 2] = rng.integers(1, 13, size=n, dtype=np.uint8)
+            gt[i, inside] = 1
+    assert (f == synth.carrier_frames(n_frames, h, w, seed=seed, n_objects=n_objects)).all()
+    return f, gt
+
+
+def _streams(seeds, n_frames, h, w):
+    """Every overlapping window of several independent streams."""
+    parts = [_stacks(*_ellipse_data(n_frames, h, w, s)) for s in seeds]
+    return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
+
+
+def _stacks(frames, gt):
+    """Every overlapping window (more samples than slide's non-overlapping ones)."""
+    n = frames.shape[0] - 3
+    st = np.stack([frames[i:i + 4][::-1].reshape(4 * frames.shape[1], frames.shape[2], 4) for i in range(n)])
+    return np.ascontiguousarray(st), np.ascontiguousarray(gt[3:])
+
+
+def _iou(mask, gt):
+    inter = (mask.astype(bool) & gt.astype(bool)).sum(axis=(1, 2))
+    union = (mask.astype(bool) | gt.astype(bool)).sum(axis=(1, 2))
+    return float(np.mean(np.where(union > 0, inter / np.maximum(union, 1), 1.0)))
+
+
+LEARN_STEPS = 600
+
+
+def test_learns_synthetic_ellipses(ctx):
+    h, w, b = 45, 80, 8
+    tr_x, tr_y = _streams(range(100, 108), 40, h, w)          # 8 streams x 37 windows
+    te_x, te_y = _streams((777, 778), 20, h, w)               # 2 held-out streams x 17 windows
+    flat0 = T.init_weights(1)
+    net = BlobNetInfer(ctx, flat0, h, w, max_batch=te_x.shape[0])
+    iou0 = _iou(net.infer(te_x, want_logits=False)[1], te_y)
+    tr = T.Trainer(ctx, h, w, max_batch=b, weights_flat=flat0, seed=1)
+    rng = np.random.default_rng(0)
+    for k in range(LEARN_STEPS):
+        idx = rng.choice(tr_x.shape[0], b, replace=False)
+        tr.step(tr_x[idx], tr_y[idx])
+    flat = tr.weights()
+    tr.close()
+    net = BlobNetInfer(ctx, flat, h, w, max_batch=te_x.shape[0])
+    iou = _iou(net.infer(te_x, want_logits=False)[1], te_y)
+    print(f"held-out IoU: {iou0:.3f} at initialisation -> {iou:.3f} after {LEARN_STEPS} steps")
+    assert iou >= 0.5 and iou >= 3 * iou0, (iou0, iou)
+    # export into the fp16 inference path: within the inference tolerance of the f32 composition on the same file
+    logits, _ = net.infer(te_x[:8])
+    ref = TB.forward(flat, te_x[:8], h, w)
+    atol, rtol = blobnet_tolerance(ref)
+    err = np.abs(logits - ref)
+    assert (err <= atol + rtol * np.abs(ref)).all(), float((err - atol - rtol * np.abs(ref)).max())
+
+
+def test_records_to_weights_end_to_end(ctx, tmp_path):
+    z = np.load(os.path.join(GOLDEN, "demo_records_excerpt.npz"))
+    frames = z["records"]
+    h, w = frames.shape[1:3]
+    gt = ((frames[..., 1] != 0) | (frames[..., 2] != 0)).astype(np.uint8)    # derived label: "mv byte nonzero"
+    path = tmp_path / "demo.tfrecord"
+    with open(path, "wb") as f:
+        for i in range(0, frames.shape[0], 8):                                  # gop form, 8 frames per record
+            f.write(tfrecord_example(frames[i:i + 8], gt[i:i + 8], gop=8))
+    fr, g = T.read_tfrecords([str(path)], h, w)
+    assert (fr[..., :3] == frames[..., :3]).all() and (g == gt).all()
+    stacks, labels = T.slide(fr, g)
+    tr = T.Trainer(ctx, h, w, max_batch=4, seed=0)
+    with pytest.raises(ValueError):
+        tr.fit((stacks, labels), epochs=1, batch=8)
+    hist = tr.fit((stacks, labels), epochs=5, batch=4)                          # 16 samples: 4 steps per epoch, 20 steps
+    tr.close()
+    losses = [r["loss"] for r in hist]
+    assert losses[-1] < losses[0], losses
+    out = tmp_path / "blobnet.cvhw"
+    r = subprocess.run([sys.executable, "-m", "cova_amd.train", str(path), "-o", str(out), "--epochs", "2", "--h-mb", str(h),
+                        "--w-mb", str(w)], cwd=ROOT, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    flat = W.from_bytes(out.read_bytes())
+    net = BlobNetInfer(ctx, flat, h, w, max_batch=4)
+    _, mask = net.infer(stacks[:4], want_logits=False)
+    assert mask.shape == (4, h, w)
