@@ -17,15 +17,20 @@ the other lane (own HIP stream and activation workspace) and its launches fill t
 the way the reference keeps sixteen BlobNet engines busy on one GPU (experiment/cova/config.yaml:33-34).  `value` =
 frames of all K steps / wall time; `ms_per_step_one_lane` is a step on its own (--lanes 1 times that).
 
-    python bench.py                       # N=1, defaults finish in a few minutes
+    python bench.py                       # N=1: the timed workload and its result line only, seconds
+    python bench.py --full                # ... and every other measurement and check, a few minutes
     python bench.py --gpus N              # starts the N ranks itself (torch.distributed.run as a child process)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Beside `value` the line carries, as extra keys measured outside the timed region on rank 0: the other entry point,
-the PCIe-inclusive rates (pageable host call, pinned pipelined covahip_pipe, through the GStreamer batching
-element), BASELINE configs[1] (BlobNet only, b=32) and the reference's default geometry (45x80, b=512), a leg with
-mixed-sign BN gammas (the ALLPOS=false kernel variants), and the CPU baselines of SURVEY.md section 8(d).
+A plain run sets up, warms up, times the K steps, writes the --dump-outputs arrays and prints the line: `value`,
+`ms_per_step` and what describes the run.  With --full the line also carries, as extra keys measured outside the timed region: a step on
+one lane and on one batch, per-kernel times and the roofline, the shader clock under load, and on rank 0 the other entry
+point, bboxcc at large batch, board power, the PCIe-inclusive rates (pageable host call, pinned pipelined covahip_pipe,
+through the GStreamer batching element), BASELINE configs[1] (BlobNet only, b=32) and the reference's default geometry
+(45x80, b=512), a leg with mixed-sign BN gammas (the ALLPOS=false kernel variants), and the CPU baselines of SURVEY.md
+section 8(d); it also checks that standalone bboxcc, every lane and both entry points give the same boxes.  The timed
+region is the same in both kinds of run.
 """
 from __future__ import annotations
 
@@ -556,8 +561,13 @@ def main():
     ap.add_argument("--control-plane-only", action="store_true",
                     help="rehearsal of the N-rank CONTROL path alone, without a GPU: rendezvous, stream partition, NUMA / core split, "
                          "barrier, MAX over ranks, gather, the aggregate line's shape -- no kernel runs and the line carries no rate")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-legs", action="store_true", help="only the timed workload (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the timed workload, every other measurement and check (one-lane and per-kernel times, roofline, "
+                         "other entry point, configurations and weights, PCIe-inclusive and GStreamer rates, CPU baselines, "
+                         "cross-checks); a plain run does only what `value` and `ms_per_step` need")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra-legs", action="store_true",
+                    help="with --full: skip the rank-0 legs outside the timed workload (profiling runs)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="write what the last timed step computed (boxes, counts, mask of its batch; at most 64 MB: a seeded "
                          "sample of the frames of a larger batch) as DIR/<name>.npy")
@@ -582,7 +592,7 @@ def main():
     # ---- host-only legs first, before this process loads the HIP library: the GStreamer element bench (a child
     # process with a GPU context of its own) and the CPU tracking baseline (forked workers)
     pre = {}
-    if env_world == 1:
+    if env_world == 1 and args.full:
         if not args.no_extra_legs:
             pre["through_gstreamer_elements"] = element_rate()
             # BASELINE config 4: metapreprocess -> BlobNet -> bboxcc -> cova (embedded SORT + GoP filter) per stream, the
@@ -680,7 +690,7 @@ def main():
     NL = max(1, min(4, args.lanes))
     flat = W.random_init(1234)
     extras = {}
-    if rank == 0 and not args.no_extra_legs:
+    if rank == 0 and args.full and not args.no_extra_legs:
         extras = extra_legs(ctx, flat, max(20, args.steps // 4))
     net = BlobNetInfer(ctx, flat, H_MB, W_MB, max_batch=B)
     # synthetic metapreprocess output: 8 independent streams interleaved, distinct per rank
@@ -731,6 +741,7 @@ def main():
         grp.barrier()        # torch.cuda.synchronize() + dist.barrier() when world > 1
 
     # ---- one lane: per-kernel times of a step on its own (profiled pass, not timed), the dominant kernel, the step latency
+    # (in every run, --full or not: the timed region below carries the dominant kernel's HIP events)
     for _ in range(3):
         step()
     ctx.profile(True)
@@ -769,193 +780,137 @@ def main():
     ctx.profile(False)
     if args.dump_outputs and rank == 0:
         dump_outputs(ctx, args.dump_outputs, B, d_boxes[turn[0] % NL], d_counts[turn[0] % NL], d_mask[turn[0] % NL])
-    # the same K steps with ONE batch (unchanged stack table: no validation upload after the first step), for comparison
-    alternate[0] = False
-    for _ in range(2 * NL):
-        step()
-    barrier()
-    t0 = time.perf_counter()
-    for _ in range(args.steps):
-        step()
-    barrier()
-    elapsed_cached = grp.max(time.perf_counter() - t0)
-    # ---- one lane: a step on its own (warm clocks, alternating batches as in the timed region; the median of five
-    # barrier-to-barrier regions of K steps) -- rounds 1-3 timed 50 steps right after start-up, before the clocks had settled
-    ctx.set_lanes(1)
-    alternate[0] = True
-    t_w = time.perf_counter()
-    while time.perf_counter() - t_w < args.min_warmup_s:
-        for _ in range(32):
+    if args.full:
+        # the same K steps with ONE batch (unchanged stack table: no validation upload after the first step), for comparison
+        alternate[0] = False
+        for _ in range(2 * NL):
             step()
-        ctx.sync()
-    regions1 = []
-    for _ in range(5):
         barrier()
         t0 = time.perf_counter()
         for _ in range(args.steps):
             step()
         barrier()
-        regions1.append(grp.max(time.perf_counter() - t0))
-    serial_ms = sorted(regions1)[len(regions1) // 2] / args.steps * 1e3
-    # per-kernel times of a step on its own, warm (the pass before the timed region only picked the dominant kernel)
-    ctx.profile(True)
-    for _ in range(20):
-        step()
-    ctx.sync()
-    per_kernel_us = {k: t / n * 1e3 for k, (t, n) in ctx.profile_read().items()}
-    ctx.profile(False)
-    alternate[0] = False
-    ctx.set_lanes(NL)
-    for _ in range(2 * NL):
-        step()
-    barrier()
-    # (the legs and cross-checks below stay on the first batch)
-    # shader clock under this load: a probe wave beside 60 more steps (untimed)
-    for _ in range(60):
-        step()
-    clock_mhz = ctx.clock_mhz(300)
-    ctx.sync()
-
-    # ---- bboxcc roofline (outside the timed region).  Inside the hot path bboxcc runs in the same launch as the last
-    # decoder block; standalone it is timed (a) on the masks the last step left in HBM (b = 256: one frame per CU,
-    # latency bound) and (b) at B = 65,536 sparse-blob masks, where the byte rate of the wave-per-frame kernel shows.
-    from cova_amd.elements import BboxCc
-    ctx.set_lanes(1)
-    cc = BboxCc(ctx, CC_THRESHOLD, MAX_BOXES)
-    d_boxes2 = ctx.malloc(B * MAX_BOXES * 20)
-    d_counts2 = ctx.malloc(B * 4)
-    cc_ms = timed_steps(ctx, lambda: cc.regionprops_device(d_mask[0], B, H_MB, W_MB, d_boxes2, d_counts2), args.steps, 3)
-    counts2 = np.zeros(B, dtype=np.int32)
-    ctx.d2h(counts2, d_counts2)
-    counts = np.zeros(B, dtype=np.int32)
-    ctx.d2h(counts, d_counts[0])
-    assert (counts == counts2).all(), "fused decoder tail and standalone bboxcc disagree"
-    for k in range(1, NL):
-        ctx.d2h(counts2, d_counts[k])
-        assert (counts == counts2).all(), "the lanes disagree"
-    ctx.free(d_boxes2); ctx.free(d_counts2)
-
-    rank0 = {}
-    if rank == 0 and not args.no_extra_legs:
-        # bboxcc at large batch (SURVEY.md section 8d asks for the sweep; tools/bboxcc_sweep.py has all of it)
-        from tools.bboxcc_sweep import make_masks
-        BB = 65536
-        masks = np.tile(make_masks("blobs", 256), (BB // 256, 1, 1))
-        d_m, d_b, d_c = ctx.malloc(masks.nbytes), ctx.malloc(BB * 64 * 20), ctx.malloc(BB * 4)
-        ctx.h2d(d_m, masks)
-        cc64 = BboxCc(ctx, CC_THRESHOLD, 64)
-        ms = timed_steps(ctx, lambda: cc64.regionprops_device(d_m, BB, H_MB, W_MB, d_b, d_c), 5, 2)
-        rank0["bboxcc_B65536_sparse_blobs"] = {"ns_per_frame": round(ms * 1e6 / BB, 2), "GBps": round(BB * H_MB * W_MB / ms / 1e6, 1),
-                                               "frac_of_8TBs": round(BB * H_MB * W_MB / ms / 1e6 / HBM_PEAK_GBS, 4)}
-        for p in (d_m, d_b, d_c):
-            ctx.free(p)
-        # the other entry point on the SAME 256 stacks: one lane (the latency of a step on its own) and NL lanes
-        ms1 = timed_steps(ctx, other, max(20, args.steps // 2))
-        ctx.set_lanes(NL)
-        msn = timed_steps(ctx, other, args.steps, 2 * NL)
+        elapsed_cached = grp.max(time.perf_counter() - t0)
+        # ---- one lane: a step on its own (warm clocks, alternating batches as in the timed region; the median of five
+        # barrier-to-barrier regions of K steps) -- rounds 1-3 timed 50 steps right after start-up, before the clocks had settled
         ctx.set_lanes(1)
-        ctx.d2h(counts2, d_counts[0])
-        assert (counts == counts2).all(), "carrier-frame entry and stacked entry disagree"
-        rank0["stacked_entry" if args.entry == "frames" else "carrier_frame_entry"] = {
-            "frames_per_s": round(B / msn * 1e3, 1), "ms_per_step": round(msn, 4), "ms_per_step_one_lane": round(ms1, 4),
-            "carrier_frames_per_step": int(frames.shape[0]), "carrier_input_bytes_per_step": int(frames.nbytes),
-            "stacked_input_bytes_per_step": int(stack.nbytes)}
-        # board power while the timed workload loops ("The roof over the step is the board's power"): with NL lanes
-        # the board sits at or near its cap, and power x step time is the same with one lane
-        ctx.set_lanes(NL)
-        pw_n = board_power_under(ctx, step)
-        ctx.set_lanes(1)
-        pw_1 = board_power_under(ctx, step)
-        if pw_n and pw_1:
-            rank0["board_power"] = {f"{NL}_lanes": pw_n, "one_lane": pw_1,
-                                    "note": "hwmon power sensor of this GPU sampled every 10 ms over a 2 s loop of the timed step "
-                                            "(untimed leg; the first 0.8 s dropped)"}
-        # PCIe-inclusive rates (never `value`)
-        net.filter(stack, CC_THRESHOLD, max_boxes=MAX_BOXES)        # warm the staging buffers
-        t1 = time.perf_counter()
+        alternate[0] = True
+        t_w = time.perf_counter()
+        while time.perf_counter() - t_w < args.min_warmup_s:
+            for _ in range(32):
+                step()
+            ctx.sync()
+        regions1 = []
         for _ in range(5):
-            net.filter(stack, CC_THRESHOLD, max_boxes=MAX_BOXES)
-        rank0["frames_per_s_pcie_inclusive_host_buffers"] = round(5 * B / (time.perf_counter() - t1), 1)
+            barrier()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                step()
+            barrier()
+            regions1.append(grp.max(time.perf_counter() - t0))
+        serial_ms = sorted(regions1)[len(regions1) // 2] / args.steps * 1e3
+        # per-kernel times of a step on its own, warm (the pass before the timed region only picked the dominant kernel)
+        ctx.profile(True)
+        for _ in range(20):
+            step()
+        ctx.sync()
+        per_kernel_us = {k: t / n * 1e3 for k, (t, n) in ctx.profile_read().items()}
+        ctx.profile(False)
+        alternate[0] = False
         ctx.set_lanes(NL)
-        rank0["frames_per_s_pcie_inclusive_pipelined_carrier_frames"] = pipelined_host_rate(net, frames, index, args.steps)
+        for _ in range(2 * NL):
+            step()
+        barrier()
+        # (the legs and cross-checks below stay on the first batch)
+        # shader clock under this load: a probe wave beside 60 more steps (untimed)
+        for _ in range(60):
+            step()
+        clock_mhz = ctx.clock_mhz(300)
+        ctx.sync()
+
+        # ---- bboxcc roofline (outside the timed region).  Inside the hot path bboxcc runs in the same launch as the last
+        # decoder block; standalone it is timed (a) on the masks the last step left in HBM (b = 256: one frame per CU,
+        # latency bound) and (b) at B = 65,536 sparse-blob masks, where the byte rate of the wave-per-frame kernel shows.
+        from cova_amd.elements import BboxCc
         ctx.set_lanes(1)
+        cc = BboxCc(ctx, CC_THRESHOLD, MAX_BOXES)
+        d_boxes2 = ctx.malloc(B * MAX_BOXES * 20)
+        d_counts2 = ctx.malloc(B * 4)
+        cc_ms = timed_steps(ctx, lambda: cc.regionprops_device(d_mask[0], B, H_MB, W_MB, d_boxes2, d_counts2), args.steps, 3)
+        counts2 = np.zeros(B, dtype=np.int32)
+        ctx.d2h(counts2, d_counts2)
+        counts = np.zeros(B, dtype=np.int32)
+        ctx.d2h(counts, d_counts[0])
+        assert (counts == counts2).all(), "fused decoder tail and standalone bboxcc disagree"
+        for k in range(1, NL):
+            ctx.d2h(counts2, d_counts[k])
+            assert (counts == counts2).all(), "the lanes disagree"
+        ctx.free(d_boxes2); ctx.free(d_counts2)
+
+        rank0 = {}
+        if rank == 0 and not args.no_extra_legs:
+            # bboxcc at large batch (SURVEY.md section 8d asks for the sweep; tools/bboxcc_sweep.py has all of it)
+            from tools.bboxcc_sweep import make_masks
+            BB = 65536
+            masks = np.tile(make_masks("blobs", 256), (BB // 256, 1, 1))
+            d_m, d_b, d_c = ctx.malloc(masks.nbytes), ctx.malloc(BB * 64 * 20), ctx.malloc(BB * 4)
+            ctx.h2d(d_m, masks)
+            cc64 = BboxCc(ctx, CC_THRESHOLD, 64)
+            ms = timed_steps(ctx, lambda: cc64.regionprops_device(d_m, BB, H_MB, W_MB, d_b, d_c), 5, 2)
+            rank0["bboxcc_B65536_sparse_blobs"] = {"ns_per_frame": round(ms * 1e6 / BB, 2), "GBps": round(BB * H_MB * W_MB / ms / 1e6, 1),
+                                                   "frac_of_8TBs": round(BB * H_MB * W_MB / ms / 1e6 / HBM_PEAK_GBS, 4)}
+            for p in (d_m, d_b, d_c):
+                ctx.free(p)
+            # the other entry point on the SAME 256 stacks: one lane (the latency of a step on its own) and NL lanes
+            ms1 = timed_steps(ctx, other, max(20, args.steps // 2))
+            ctx.set_lanes(NL)
+            msn = timed_steps(ctx, other, args.steps, 2 * NL)
+            ctx.set_lanes(1)
+            ctx.d2h(counts2, d_counts[0])
+            assert (counts == counts2).all(), "carrier-frame entry and stacked entry disagree"
+            rank0["stacked_entry" if args.entry == "frames" else "carrier_frame_entry"] = {
+                "frames_per_s": round(B / msn * 1e3, 1), "ms_per_step": round(msn, 4), "ms_per_step_one_lane": round(ms1, 4),
+                "carrier_frames_per_step": int(frames.shape[0]), "carrier_input_bytes_per_step": int(frames.nbytes),
+                "stacked_input_bytes_per_step": int(stack.nbytes)}
+            # board power while the timed workload loops ("The roof over the step is the board's power"): with NL lanes
+            # the board sits at or near its cap, and power x step time is the same with one lane
+            ctx.set_lanes(NL)
+            pw_n = board_power_under(ctx, step)
+            ctx.set_lanes(1)
+            pw_1 = board_power_under(ctx, step)
+            if pw_n and pw_1:
+                rank0["board_power"] = {f"{NL}_lanes": pw_n, "one_lane": pw_1,
+                                        "note": "hwmon power sensor of this GPU sampled every 10 ms over a 2 s loop of the timed step "
+                                                "(untimed leg; the first 0.8 s dropped)"}
+            # PCIe-inclusive rates (never `value`)
+            net.filter(stack, CC_THRESHOLD, max_boxes=MAX_BOXES)        # warm the staging buffers
+            t1 = time.perf_counter()
+            for _ in range(5):
+                net.filter(stack, CC_THRESHOLD, max_boxes=MAX_BOXES)
+            rank0["frames_per_s_pcie_inclusive_host_buffers"] = round(5 * B / (time.perf_counter() - t1), 1)
+            ctx.set_lanes(NL)
+            rank0["frames_per_s_pcie_inclusive_pipelined_carrier_frames"] = pipelined_host_rate(net, frames, index, args.steps)
+            ctx.set_lanes(1)
 
     # ---- one object per rank (stderr, and gathered into the aggregate line): what it owns and what it measured on its own clock
     n_streams = 8 * world
     mine = {"rank": rank, "local_rank": local_rank, "device": dev, "streams": streams_of_rank(n_streams, rank, world),
             "frames_per_step": B, "ms_per_step_own_clock": round(ev_ms / args.steps, 4),
             "frames_per_s_own_clock": round(B * args.steps / (ev_ms * 1e-3), 1),
-            "ms_per_step_one_lane": round(serial_ms, 4), "numa_node": pin.get("numa_node"), "cpus": pin.get("cpus"),
-            "pinned": pin.get("pinned"), "input_seed": seed}
+            "numa_node": pin.get("numa_node"), "cpus": pin.get("cpus"), "pinned": pin.get("pinned"), "input_seed": seed}
+    if args.full:
+        mine["ms_per_step_one_lane"] = round(serial_ms, 4)
     if world > 1:
         rank_line(mine)
     all_ranks = grp.gather(mine)
 
     if rank == 0:
-        macs = kernel_macs_per_frame()
-        kbytes = kernel_bytes_per_frame()
-        hs, ws = level_dims()
-        # carrier path: level 0 up to the pool once per carrier frame; level 1 + level 0's temporal MLP + the gather per stack
-        nfr = frames.shape[0] if args.entry == "frames" else T * B     # (the stacked tensor is T * B carrier frames)
-        macs["enc0p_mfma"] = hs[0] * ws[0] * 9 * 3 * 16 * nfr / B
-        kbytes["enc0p_mfma"] = (hs[0] * ws[0] * 4 + hs[1] * ws[1] * 16 * 2) * nfr / B
-        macs["enc1_mfma"] += hs[1] * ws[1] * 16 * 32            # + level 0's temporal MLP (applied while staging)
-        # + the level-0 skip connection: as fp32 partial logits, four per grid position of the last block (round 5; the level-1 kernel
-        # runs the skip half of the folded last block, (H1 + 1)(W1 + 1) x 4 taps x 16 channels x 4 parities MAC, counted as executed
-        # work of this kernel, not as algorithmic FLOP -- those stay with the last block)
-        part_bytes = (hs[1] + 1) * (ws[1] + 1) * 16
-        kbytes["enc1_mfma"] += part_bytes
-        kbytes["dec3_bboxcc_fused"] = kbytes["dec3_final_mfma"] = hs[1] * ws[1] * 16 * 2 + part_bytes + H_MB * W_MB
-        dom_s = dom_ms / dom_n * 1e-3
-        cc_s = cc_ms * 1e-3
-        cc_gbs = B * H_MB * W_MB / cc_s / 1e9
-        total_flop = 2.0 * net.macs_per_frame * B
-        # what the timed entry executes: the carrier-frame entry runs level 0's convolution once per carrier frame
-        # (nfr slices) instead of once per (stack, T slice) (4 B slices)
-        executed_flop = total_flop - (2.0 * hs[0] * ws[0] * 9 * 3 * 16 * (T * B - nfr) if args.entry == "frames" else 0.0)
-        # ... and the last decoder block + final conv as ONE folded 32 -> 1 transposed conv (16.8 M -> 1.1 M MAC per frame)
-        fold_alg, fold_exec = dec3_fold_macs_per_frame()
-        executed_flop -= 2.0 * (fold_alg - fold_exec) * B
-        # every kernel of a step against both roofs, from the warm one-lane per-kernel pass (HIP events: ~2 us of event
-        # overhead per launch are inside these times -- the rocprofv3 figures in profiles/ are the ones without)
-        kernels = {}
-        for k, us in sorted(per_kernel_us.items()):
-            if k not in macs:
-                continue
-            fl, by = 2.0 * macs[k] * B, kbytes[k] * B
-            # frac_hbm is priced on the bytes the fabric counters saw for this launch (the committed FETCH_SIZE x 2 + WRITE_SIZE
-            # summary, b = 256): the structural count below it includes re-reads that L2 absorbs (level 1 gathers every P slice
-            # four times: 109 MB structural, 71 MB on the fabric) and is no HBM figure
-            cnt, cnt_src = committed_traffic(k, args.entry) if B == BATCH else (None, None)
-            kernels[k] = {"us_alone": round(us, 2), "alg_flop": fl, "frac_mfma": round(fl / (us * 1e-6) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                          "hbm_bytes_counter": cnt, "hbm_bytes_counter_source": cnt_src,
-                          "frac_hbm": round(cnt / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if cnt else None,
-                          "bytes_structural": by, "frac_hbm_structural": round(by / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
-        if "dec3_bboxcc_fused" in kernels:
-            kernels["dec3_bboxcc_fused"]["executed_flop"] = 2.0 * fold_exec * B
-            kernels["dec3_bboxcc_fused"]["note"] = "alg_flop = convT 32->16 + 1x1 as written; executed folded; bboxcc runs in the same launch"
         step_s = elapsed / args.steps
-        other_entry = rank0.get("stacked_entry" if args.entry == "frames" else "carrier_frame_entry", {})
-        dom_flop = 2.0 * macs[dominant] * B
-        ach_tflops = dom_flop / dom_s / 1e12
-        dom_bytes = kbytes[dominant] * B
-        dom_traffic, dom_traffic_src = committed_traffic(dominant, args.entry) if B == BATCH else (None, None)
-        cc_traffic, _ = committed_traffic("bboxcc_kernel", "stack") if B == BATCH else (None, None)
-        serial_dom_s = per_kernel_us[dominant] * 1e-6
         line = {
             "metric": "compressed-domain frames/sec (BlobNet+bboxcc) at 1080p b=256",
             "value": round(world * B * args.steps / elapsed, 1),
             "unit": "frames/s",
-            # the literal BASELINE config-3 input (pre-stacked tensors) and a step on its own, right beside `value`
-            "value_stacked_entry": other_entry.get("frames_per_s") if args.entry == "frames" else round(world * B * args.steps / elapsed, 1),
-            "ms_per_step_stacked_entry": other_entry.get("ms_per_step") if args.entry == "frames" else round(elapsed / args.steps * 1e3, 4),
-            "ms_per_step_one_lane": round(serial_ms, 4),
-            "value_one_lane": round(world * B / serial_ms * 1e3, 1),
             "schema": 6,
-            "schema_note": ("6 (round 6): roofline.alone / roofline.in_situ are both explicit; roofline.achieved / frac / avg_launch_us repeat "
-                            "roofline.alone (the dominant launch alone on the chip, as in round 5; rounds 1-4 printed the in-situ figure "
-                            "under those names); kernels{}.frac_hbm is priced on counter bytes (hbm_bytes_counter), the structural count "
-                            "moved to bytes_structural"),
             "n_gpus": world,
             "steps": args.steps,
             "warmup": args.warmup,
@@ -971,81 +926,143 @@ def main():
                                                       "no RCCL communicator exists"} if world > 1 else {}),
             "timed_regions_s": [round(elapsed, 5)],
             "timed_region": f"one barrier-to-barrier region of {args.steps} steps",
-            "ms_per_step_one_batch": round(elapsed_cached / args.steps * 1e3, 4),
-            "shader_clock_mhz_under_load": round(clock_mhz, 1),
-            "blobnet_mfma_util_whole_net": round(total_flop / step_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
-            "blobnet_mfma_util_whole_net_executed": round(executed_flop / step_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
-            "blobnet_mfma_util_whole_net_one_lane": round(total_flop / (serial_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-            "blobnet_mfma_util_whole_net_one_lane_executed": round(executed_flop / (serial_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
-            "algorithmic_flop_per_step": total_flop,
-            "executed_flop_per_step": executed_flop,
-            "per_kernel_us": {k: round(v, 2) for k, v in sorted(per_kernel_us.items())},
-            "per_kernel_us_note": ("HIP events around every launch of 20 one-lane steps, warm: the event pair costs ~2 us per launch, so "
-                                   "the sum exceeds ms_per_step_one_lane; kernel times without it: profiles/r*/kernel_stats_frames_lanes1.csv (rocprofv3)"),
-            "launches_per_step": len(per_kernel_us),
-            "kernels": kernels,
-        }
-        line.update({k: rank0.pop(k) for k in ("stacked_entry", "carrier_frame_entry") if k in rank0})
-        line.update({
-            # SURVEY.md section 8(d) prices the BlobNet kernels against the MFMA roof; the same launch against
-            # the HBM roof (compulsory bytes of the kernel / time) is given beside it, with the tighter one named.
-            # The dominant kernel's roofline is a property of the kernel: the headline figures are the launch ALONE on the chip
-            # (HIP events on its own stream in the warm one-lane timed pass; profiles/r*/kernel_stats_frames_lanes1.csv is the
-            # rocprofv3 view of the same).  Inside the multi-lane timed region the launch shares the CUs with other steps' launches
-            # and its bracket also holds queueing: that figure is given beside it, not instead of it.
-            "roofline": {"kernel": dominant, "bound": "mfma", "achieved": round(dom_flop / serial_dom_s / 1e12, 2),
-                         "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(dom_flop / serial_dom_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
-                         "traffic": dom_traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_source": dom_traffic_src,
-                         "algorithmic_flop_per_launch": dom_flop, "avg_launch_us": round(serial_dom_s * 1e6, 2),
-                         "measured": "HIP events on the launch's own stream, the launch alone on the chip (20 one-lane steps after the timed regions, warm)",
-                         "alone": {"avg_launch_us": round(serial_dom_s * 1e6, 2), "achieved": round(dom_flop / serial_dom_s / 1e12, 2),
-                                   "frac": round(dom_flop / serial_dom_s / 1e12 / MFMA_PEAK_TFLOPS, 4)},
-                         "in_situ": {"lanes": NL, "avg_launch_us": round(dom_s * 1e6, 2), "achieved": round(ach_tflops, 2),
-                                     "frac": round(ach_tflops / MFMA_PEAK_TFLOPS, 4)},
-                         f"in_situ_{NL}_lanes": {"avg_launch_us": round(dom_s * 1e6, 2), "launches_timed": dom_n,
-                                                 "achieved": round(ach_tflops, 2), "frac": round(ach_tflops / MFMA_PEAK_TFLOPS, 4),
-                                                 "measured": (f"HIP events inside the timed region; with {NL} lanes the launch shares the chip with "
-                                                              "the other lanes' launches, so its duration is longer than on its own")},
-                         "hbm_view": {"algorithmic_bytes_per_launch": dom_bytes,
-                                      "achieved_GBs": round(dom_bytes / serial_dom_s / 1e9, 1),
-                                      "frac_of_8TBs": round(dom_bytes / serial_dom_s / 1e9 / HBM_PEAK_GBS, 4)},
-                         "tighter_roof": "hbm" if dom_bytes / (HBM_PEAK_GBS * 1e9) > dom_flop / (MFMA_PEAK_TFLOPS * 1e12) else "mfma"},
-            "roofline_bboxcc": {"kernel": "bboxcc_kernel", "bound": "hbm", "achieved": round(cc_gbs, 2),
-                                "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(cc_gbs / HBM_PEAK_GBS, 5),
-                                "traffic": cc_traffic, "algorithmic_bytes_per_launch": B * H_MB * W_MB,
-                                "avg_launch_us": round(cc_s * 1e6, 2),
-                                "note": "standalone kernel on the step's masks (in the hot path bboxcc runs inside the last "
-                                        "decoder block's launch); b=256 masks are 2.09 MB: latency bound -- the byte rate is "
-                                        "bboxcc_B65536_sparse_blobs"},
-            "blobnet_mfma_util_note": "BlobNet FLOP (algorithmic: SURVEY.md 8d; executed: level 0 once per carrier frame, last decoder block + final conv folded) over the "
-                                      "WHOLE step time (bboxcc included: it shares a launch)",
             "hip_event_ms_per_step_rank0": round(ev_ms / args.steps, 4),
-            "boxes_per_frame_mean": float(counts.mean()),
+            "full": args.full,
             "device": ctx.info(),
-        })
-        line.update(rank0)
-        line.update(extras)
-        for k in ("through_gstreamer_elements", "full_filter_chain", "native_chain_c_abi_only", "pcie_inclusive_c_driver"):
-            if k in pre:
-                line[k] = pre[k]
-        if not args.no_cpu_baseline and world == 1:
-            line["cpu_baseline"] = cpu_baseline(flat, stack)
-            line["cpu_baseline"].update(pre.get("cpu_tracking", {}))
-            cb = line["cpu_baseline"]
-            if "bboxcc_sort_nstreams_frames_per_s" in cb:
-                # the whole chain on the host's cores: BlobNet and the per-stream bboxcc + SORT share them
-                cb["full_chain_frames_per_s"] = round(1.0 / (1.0 / cb["value"] + 1.0 / cb["bboxcc_sort_nstreams_frames_per_s"]), 2)
-            if "frames_per_s_full_chain" in pre.get("full_filter_chain", {}):
-                fc = pre["full_filter_chain"]
-                fc["vs_cpu_full_chain"] = round(fc["frames_per_s_full_chain"] / cb.get("full_chain_frames_per_s", cb["value"]), 1)
-            line["gpu_over_cpu"] = round(line["value"] / world / line["cpu_baseline"]["value"], 1)
-        nc = pre.get("native_chain_c_abi_only", {})
-        if "cpu_us_per_frame" in nc and world == 1:   # process CPU time per frame (eight worker threads, OpenMP waits and the HIP runtime's threads included)
-            nc["host_cores_one_gpu_would_need"] = round(line["value"] * nc["cpu_us_per_frame"] * 1e-6, 1)
-        fc = pre.get("full_filter_chain", {})
-        if "frames_per_s_full_chain" in fc and world == 1:
-            fc["host_cores_one_gpu_would_need"] = int(line["value"] / max(1.0, fc["frames_per_s_full_chain"]) * min(16, effective_cores()))
+        }
+        if args.full:
+            macs = kernel_macs_per_frame()
+            kbytes = kernel_bytes_per_frame()
+            hs, ws = level_dims()
+            # carrier path: level 0 up to the pool once per carrier frame; level 1 + level 0's temporal MLP + the gather per stack
+            nfr = frames.shape[0] if args.entry == "frames" else T * B     # (the stacked tensor is T * B carrier frames)
+            macs["enc0p_mfma"] = hs[0] * ws[0] * 9 * 3 * 16 * nfr / B
+            kbytes["enc0p_mfma"] = (hs[0] * ws[0] * 4 + hs[1] * ws[1] * 16 * 2) * nfr / B
+            macs["enc1_mfma"] += hs[1] * ws[1] * 16 * 32            # + level 0's temporal MLP (applied while staging)
+            # + the level-0 skip connection: as fp32 partial logits, four per grid position of the last block (round 5; the level-1 kernel
+            # runs the skip half of the folded last block, (H1 + 1)(W1 + 1) x 4 taps x 16 channels x 4 parities MAC, counted as executed
+            # work of this kernel, not as algorithmic FLOP -- those stay with the last block)
+            part_bytes = (hs[1] + 1) * (ws[1] + 1) * 16
+            kbytes["enc1_mfma"] += part_bytes
+            kbytes["dec3_bboxcc_fused"] = kbytes["dec3_final_mfma"] = hs[1] * ws[1] * 16 * 2 + part_bytes + H_MB * W_MB
+            dom_s = dom_ms / dom_n * 1e-3
+            cc_s = cc_ms * 1e-3
+            cc_gbs = B * H_MB * W_MB / cc_s / 1e9
+            total_flop = 2.0 * net.macs_per_frame * B
+            # what the timed entry executes: the carrier-frame entry runs level 0's convolution once per carrier frame
+            # (nfr slices) instead of once per (stack, T slice) (4 B slices)
+            executed_flop = total_flop - (2.0 * hs[0] * ws[0] * 9 * 3 * 16 * (T * B - nfr) if args.entry == "frames" else 0.0)
+            # ... and the last decoder block + final conv as ONE folded 32 -> 1 transposed conv (16.8 M -> 1.1 M MAC per frame)
+            fold_alg, fold_exec = dec3_fold_macs_per_frame()
+            executed_flop -= 2.0 * (fold_alg - fold_exec) * B
+            # every kernel of a step against both roofs, from the warm one-lane per-kernel pass (HIP events: ~2 us of event
+            # overhead per launch are inside these times -- the rocprofv3 figures in profiles/ are the ones without)
+            kernels = {}
+            for k, us in sorted(per_kernel_us.items()):
+                if k not in macs:
+                    continue
+                fl, by = 2.0 * macs[k] * B, kbytes[k] * B
+                # frac_hbm is priced on the bytes the fabric counters saw for this launch (the committed FETCH_SIZE x 2 + WRITE_SIZE
+                # summary, b = 256): the structural count below it includes re-reads that L2 absorbs (level 1 gathers every P slice
+                # four times: 109 MB structural, 71 MB on the fabric) and is no HBM figure
+                cnt, cnt_src = committed_traffic(k, args.entry) if B == BATCH else (None, None)
+                kernels[k] = {"us_alone": round(us, 2), "alg_flop": fl, "frac_mfma": round(fl / (us * 1e-6) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                              "hbm_bytes_counter": cnt, "hbm_bytes_counter_source": cnt_src,
+                              "frac_hbm": round(cnt / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4) if cnt else None,
+                              "bytes_structural": by, "frac_hbm_structural": round(by / (us * 1e-6) / 1e9 / HBM_PEAK_GBS, 4)}
+            if "dec3_bboxcc_fused" in kernels:
+                kernels["dec3_bboxcc_fused"]["executed_flop"] = 2.0 * fold_exec * B
+                kernels["dec3_bboxcc_fused"]["note"] = "alg_flop = convT 32->16 + 1x1 as written; executed folded; bboxcc runs in the same launch"
+            other_entry = rank0.get("stacked_entry" if args.entry == "frames" else "carrier_frame_entry", {})
+            dom_flop = 2.0 * macs[dominant] * B
+            ach_tflops = dom_flop / dom_s / 1e12
+            dom_bytes = kbytes[dominant] * B
+            dom_traffic, dom_traffic_src = committed_traffic(dominant, args.entry) if B == BATCH else (None, None)
+            cc_traffic, _ = committed_traffic("bboxcc_kernel", "stack") if B == BATCH else (None, None)
+            serial_dom_s = per_kernel_us[dominant] * 1e-6
+            line.update({
+                # the literal BASELINE config-3 input (pre-stacked tensors) and a step on its own, right beside `value`
+                "value_stacked_entry": other_entry.get("frames_per_s") if args.entry == "frames" else round(world * B * args.steps / elapsed, 1),
+                "ms_per_step_stacked_entry": other_entry.get("ms_per_step") if args.entry == "frames" else round(elapsed / args.steps * 1e3, 4),
+                "ms_per_step_one_lane": round(serial_ms, 4),
+                "value_one_lane": round(world * B / serial_ms * 1e3, 1),
+                "schema_note": ("6 (round 6): roofline.alone / roofline.in_situ are both explicit; roofline.achieved / frac / avg_launch_us repeat "
+                                "roofline.alone (the dominant launch alone on the chip, as in round 5; rounds 1-4 printed the in-situ figure "
+                                "under those names); kernels{}.frac_hbm is priced on counter bytes (hbm_bytes_counter), the structural count "
+                                "moved to bytes_structural"),
+                "ms_per_step_one_batch": round(elapsed_cached / args.steps * 1e3, 4),
+                "shader_clock_mhz_under_load": round(clock_mhz, 1),
+                "blobnet_mfma_util_whole_net": round(total_flop / step_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                "blobnet_mfma_util_whole_net_executed": round(executed_flop / step_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                "blobnet_mfma_util_whole_net_one_lane": round(total_flop / (serial_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                "blobnet_mfma_util_whole_net_one_lane_executed": round(executed_flop / (serial_ms * 1e-3) / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                "algorithmic_flop_per_step": total_flop,
+                "executed_flop_per_step": executed_flop,
+                "per_kernel_us": {k: round(v, 2) for k, v in sorted(per_kernel_us.items())},
+                "per_kernel_us_note": ("HIP events around every launch of 20 one-lane steps, warm: the event pair costs ~2 us per launch, so "
+                                       "the sum exceeds ms_per_step_one_lane; kernel times without it: profiles/r*/kernel_stats_frames_lanes1.csv (rocprofv3)"),
+                "launches_per_step": len(per_kernel_us),
+                "kernels": kernels,
+            })
+            line.update({k: rank0.pop(k) for k in ("stacked_entry", "carrier_frame_entry") if k in rank0})
+            line.update({
+                # SURVEY.md section 8(d) prices the BlobNet kernels against the MFMA roof; the same launch against
+                # the HBM roof (compulsory bytes of the kernel / time) is given beside it, with the tighter one named.
+                # The dominant kernel's roofline is a property of the kernel: the headline figures are the launch ALONE on the chip
+                # (HIP events on its own stream in the warm one-lane timed pass; profiles/r*/kernel_stats_frames_lanes1.csv is the
+                # rocprofv3 view of the same).  Inside the multi-lane timed region the launch shares the CUs with other steps' launches
+                # and its bracket also holds queueing: that figure is given beside it, not instead of it.
+                "roofline": {"kernel": dominant, "bound": "mfma", "achieved": round(dom_flop / serial_dom_s / 1e12, 2),
+                             "peak": MFMA_PEAK_TFLOPS, "unit": "TFLOP/s", "frac": round(dom_flop / serial_dom_s / 1e12 / MFMA_PEAK_TFLOPS, 4),
+                             "traffic": dom_traffic, "traffic_unit": "HBM bytes per launch (rocprofv3 FETCH_SIZE x2 + WRITE_SIZE)",
+                             "traffic_source": dom_traffic_src,
+                             "algorithmic_flop_per_launch": dom_flop, "avg_launch_us": round(serial_dom_s * 1e6, 2),
+                             "measured": "HIP events on the launch's own stream, the launch alone on the chip (20 one-lane steps after the timed regions, warm)",
+                             "alone": {"avg_launch_us": round(serial_dom_s * 1e6, 2), "achieved": round(dom_flop / serial_dom_s / 1e12, 2),
+                                       "frac": round(dom_flop / serial_dom_s / 1e12 / MFMA_PEAK_TFLOPS, 4)},
+                             "in_situ": {"lanes": NL, "avg_launch_us": round(dom_s * 1e6, 2), "achieved": round(ach_tflops, 2),
+                                         "frac": round(ach_tflops / MFMA_PEAK_TFLOPS, 4)},
+                             f"in_situ_{NL}_lanes": {"avg_launch_us": round(dom_s * 1e6, 2), "launches_timed": dom_n,
+                                                     "achieved": round(ach_tflops, 2), "frac": round(ach_tflops / MFMA_PEAK_TFLOPS, 4),
+                                                     "measured": (f"HIP events inside the timed region; with {NL} lanes the launch shares the chip with "
+                                                                  "the other lanes' launches, so its duration is longer than on its own")},
+                             "hbm_view": {"algorithmic_bytes_per_launch": dom_bytes,
+                                          "achieved_GBs": round(dom_bytes / serial_dom_s / 1e9, 1),
+                                          "frac_of_8TBs": round(dom_bytes / serial_dom_s / 1e9 / HBM_PEAK_GBS, 4)},
+                             "tighter_roof": "hbm" if dom_bytes / (HBM_PEAK_GBS * 1e9) > dom_flop / (MFMA_PEAK_TFLOPS * 1e12) else "mfma"},
+                "roofline_bboxcc": {"kernel": "bboxcc_kernel", "bound": "hbm", "achieved": round(cc_gbs, 2),
+                                    "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(cc_gbs / HBM_PEAK_GBS, 5),
+                                    "traffic": cc_traffic, "algorithmic_bytes_per_launch": B * H_MB * W_MB,
+                                    "avg_launch_us": round(cc_s * 1e6, 2),
+                                    "note": "standalone kernel on the step's masks (in the hot path bboxcc runs inside the last "
+                                            "decoder block's launch); b=256 masks are 2.09 MB: latency bound -- the byte rate is "
+                                            "bboxcc_B65536_sparse_blobs"},
+                "blobnet_mfma_util_note": "BlobNet FLOP (algorithmic: SURVEY.md 8d; executed: level 0 once per carrier frame, last decoder block + final conv folded) over the "
+                                          "WHOLE step time (bboxcc included: it shares a launch)",
+                "boxes_per_frame_mean": float(counts.mean()),
+            })
+            line.update(rank0)
+            line.update(extras)
+            for k in ("through_gstreamer_elements", "full_filter_chain", "native_chain_c_abi_only", "pcie_inclusive_c_driver"):
+                if k in pre:
+                    line[k] = pre[k]
+            if not args.no_cpu_baseline and world == 1:
+                line["cpu_baseline"] = cpu_baseline(flat, stack)
+                line["cpu_baseline"].update(pre.get("cpu_tracking", {}))
+                cb = line["cpu_baseline"]
+                if "bboxcc_sort_nstreams_frames_per_s" in cb:
+                    # the whole chain on the host's cores: BlobNet and the per-stream bboxcc + SORT share them
+                    cb["full_chain_frames_per_s"] = round(1.0 / (1.0 / cb["value"] + 1.0 / cb["bboxcc_sort_nstreams_frames_per_s"]), 2)
+                if "frames_per_s_full_chain" in pre.get("full_filter_chain", {}):
+                    fc = pre["full_filter_chain"]
+                    fc["vs_cpu_full_chain"] = round(fc["frames_per_s_full_chain"] / cb.get("full_chain_frames_per_s", cb["value"]), 1)
+                line["gpu_over_cpu"] = round(line["value"] / world / line["cpu_baseline"]["value"], 1)
+            nc = pre.get("native_chain_c_abi_only", {})
+            if "cpu_us_per_frame" in nc and world == 1:   # process CPU time per frame (eight worker threads, OpenMP waits and the HIP runtime's threads included)
+                nc["host_cores_one_gpu_would_need"] = round(line["value"] * nc["cpu_us_per_frame"] * 1e-6, 1)
+            fc = pre.get("full_filter_chain", {})
+            if "frames_per_s_full_chain" in fc and world == 1:
+                fc["host_cores_one_gpu_would_need"] = int(line["value"] / max(1.0, fc["frames_per_s_full_chain"]) * min(16, effective_cores()))
         # the long strings last, so that the numbers survive a truncated log
         line["config"] = {"workload": ("temporal stacking as a GPU gather + BlobNet + bboxcc fused (covahip_filter_forward_frames): carrier "
                                        "frames of 8 streams + stack table, 256 output frames, 1080p macroblock grid 68x120, T=4, inputs "

@@ -167,6 +167,30 @@ def test_bench_two_ranks_rehearsed_on_this_gpu():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_the_timed_workload_only(tmp_path):
+    """bench.py without --full: the timed steps, the dumped outputs and one line whose headline keys agree with each other;
+    none of the --full legs (one-lane pass, roofline, other entry point, CPU baselines, element rates) runs."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+    lines = [json.loads(l) for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    line = lines[0]
+    assert line["full"] is False and line["n_gpus"] == 1 and line["steps"] == 5 and line["warmup"] == 2
+    assert line["unit"] == "frames/s" and line["higher_is_better"] is True and line["dtype"] == "f16"
+    assert abs(line["value"] - line["config"]["batch_per_gpu"] / (line["ms_per_step"] * 1e-3)) / line["value"] < 1e-3
+    for k in ("ms_per_step_one_lane", "per_kernel_us", "roofline", "stacked_entry", "cpu_baseline", "full_filter_chain"):
+        assert k not in line, k
+    assert sorted(os.listdir(tmp_path)) == ["boxes.npy", "counts.npy", "frames.npy", "mask.npy"]
+    assert np.load(tmp_path / "counts.npy").shape == (B,)
+
+
+@pytest.mark.gpu
 def test_sysfs_gpu_enumeration_agrees_with_the_runtime(ctx):
     """A rank pins itself to its GPU's NUMA node BEFORE it touches the GPU: the PCI address comes from the KFD
     topology in sysfs (cova_amd.multigpu.kfd_gpu_bus_ids), not from a HIP call.  Where the topology is readable its device order
