@@ -75,6 +75,11 @@ class TrainCfg(C.Structure):
                 ("smooth", C.c_float), ("seed", C.c_uint64)]
 
 
+class MogCfg(C.Structure):
+    _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
+                ("var_threshold", C.c_float)]
+
+
 # name -> (restype, argtypes); every symbol include/covahip.h declares
 _P = C.c_void_p
 _SZ = C.c_size_t
@@ -180,6 +185,11 @@ PROTOTYPES = {
     "covahip_train_weights": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "covahip_train_grads": (C.c_int, [_P, _P, _SZ]),
     "covahip_train_destroy": (None, [_P]),
+    "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
+    "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
+    "covahip_mog_apply": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_mog_reset": (C.c_int, [_P, C.c_int]),
+    "covahip_mog_destroy": (None, [_P]),
 }
 
 # developer switches (include/covahip_dev.h): bound for tools/ and tests/, not part of the drop-in boundary
@@ -193,6 +203,8 @@ DEV_PROTOTYPES = {
     "covahip_dev_bboxcc_overflow": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "covahip_dev_pipe_queue_plan": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "covahip_dev_blobnet_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
+    "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),
+    "covahip_dev_mog_state": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
 }
 
 _lib = None

@@ -1,0 +1,289 @@
+"""MoG training labels on the GPU: utils/generate-mog.py of the reference, the first step of its "train from scratch" flow.
+
+  MogLabeler   covahip_mog_*: per-pixel MOG2 at 640x360, close 4x4, open 6x6, hole fill and the ::8 subsample to the 45x80
+               labels `tfrecordsink gt=` reads, for several independent videos (streams) per call
+  read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
+
+    ffmpeg -i VIDEO -f rawvideo -pix_fmt bgr24 - | python -m cova_amd.mog --size 1280x720 -:VIDEO_gt.dump
+    python -m cova_amd.mog --size 1280x720 a.bgr b.bgr:labels_b.dump ... [--streams S] [--chunk F]
+
+Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
+to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Pixel decoding is not done here:
+the labeller takes decoded BGR frames, which is what cv.VideoCapture hands generate-mog.py.
+"""
+from __future__ import annotations
+
+import argparse
+import ctypes as C
+import os
+import sys
+import time
+
+import numpy as np
+
+from . import _lib as L
+
+WORK_W, WORK_H = 640, 360
+LABEL_H, LABEL_W = 45, 80
+NMIX = 5
+SIZES = ((640, 360), (1280, 720), (1920, 1080))
+MAX_STREAMS = 1024
+
+
+def _ptr(a: np.ndarray) -> int:
+    return a.ctypes.data
+
+
+class MogLabeler:
+    """covahip_mog_* over one ctx: `streams` videos of src_w x src_h BGR24 frames advance per `apply` call."""
+
+    def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0):
+        self.ctx = ctx
+        self._lib = L.lib()
+        cfg = L.MogCfg()
+        self._lib.covahip_mog_default_cfg(C.byref(cfg))
+        cfg.src_w, cfg.src_h, cfg.n_streams, cfg.history, cfg.var_threshold = src_w, src_h, streams, history, var_threshold
+        h = C.c_void_p()
+        L.check(self._lib.covahip_mog_create(ctx.handle, C.byref(cfg), C.byref(h)), "covahip_mog_create", ctx.handle)
+        self.handle = h
+        self.src_w, self.src_h, self.streams = src_w, src_h, streams
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):      # (a labeller outliving its closed ctx is not freed)
+                self._lib.covahip_mog_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def _n_valid(self, n_valid, n_frames):
+        if n_valid is None:
+            return None
+        nv = np.ascontiguousarray(n_valid, dtype=np.int32)
+        if nv.shape != (self.streams,):
+            raise ValueError(f"n_valid has shape {nv.shape}, expected ({self.streams},)")
+        return nv
+
+    def apply(self, frames: np.ndarray, n_valid=None, labels: np.ndarray | None = None) -> np.ndarray:
+        """frames u8 [F][S][src_h][src_w][3] -> labels u8 [F][S][45][80].  n_valid[s] <= F: stream s takes only its first
+        n_valid[s] frames, and its labels past them are left as `labels` holds them (zeros when no `labels` is given)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        want = (self.streams, self.src_h, self.src_w, 3)
+        if frames.ndim != 5 or frames.shape[1:] != want:
+            raise ValueError(f"frames of shape {frames.shape}, expected [F]{list(want)}")
+        n = frames.shape[0]
+        if labels is None:
+            labels = np.zeros((n, self.streams, LABEL_H, LABEL_W), np.uint8)
+        elif labels.shape != (n, self.streams, LABEL_H, LABEL_W) or labels.dtype != np.uint8 or not labels.flags.c_contiguous:
+            raise ValueError("labels must be a C-contiguous u8 array [F][S][45][80]")
+        nv = self._n_valid(n_valid, n)
+        L.check(self._lib.covahip_mog_apply(self.handle, _ptr(frames), n, None if nv is None else _ptr(nv), _ptr(labels),
+                                            L.MEM_HOST), "covahip_mog_apply", self.ctx.handle)
+        return labels
+
+    def apply_device(self, d_frames: int, n_frames: int, d_labels: int, n_valid=None):
+        """The same on device pointers (frames u8 [F][S][src_h][src_w][3], labels u8 [F][S][45][80] on the ctx's GPU)."""
+        nv = self._n_valid(n_valid, n_frames)
+        L.check(self._lib.covahip_mog_apply(self.handle, d_frames, n_frames, None if nv is None else _ptr(nv), d_labels,
+                                            L.MEM_DEVICE), "covahip_mog_apply", self.ctx.handle)
+
+    def reset(self, s: int):
+        """Stream slot s starts a new video: model zeroed, frame count 0."""
+        L.check(self._lib.covahip_mog_reset(self.handle, s), "covahip_mog_reset", self.ctx.handle)
+
+    def state(self, s: int) -> dict:
+        """Stream s's model: W f32 [5][360][640], V f32 [5][360][640], M f32 [5][3][360][640], nmodes u8 [360][640], n."""
+        W = np.empty((NMIX, WORK_H, WORK_W), np.float32)
+        V = np.empty_like(W)
+        M = np.empty((NMIX, 3, WORK_H, WORK_W), np.float32)
+        nm = np.empty((WORK_H, WORK_W), np.uint8)
+        n = C.c_int64()
+        L.check(self._lib.covahip_dev_mog_state(self.handle, s, _ptr(W), _ptr(V), _ptr(M), _ptr(nm), C.byref(n)),
+                "covahip_dev_mog_state", self.ctx.handle)
+        return {"W": W, "V": V, "M": M, "nmodes": nm, "n": int(n.value)}
+
+    def debug_masks(self):
+        """(raw, filled) of the last apply call, u8 [F][S][360][640]: the MOG2 mask (0 / 255) and the mask after close, open
+        and hole fill (0 / 1)."""
+        nf = C.c_int()
+        L.check(self._lib.covahip_dev_mog_masks(self.handle, None, None, 0, C.byref(nf)), "covahip_dev_mog_masks")
+        shape = (nf.value, self.streams, WORK_H, WORK_W)
+        raw = np.empty(shape, np.uint8)
+        filled = np.empty(shape, np.uint8)
+        L.check(self._lib.covahip_dev_mog_masks(self.handle, _ptr(raw), _ptr(filled), raw.nbytes, C.byref(nf)),
+                "covahip_dev_mog_masks", self.ctx.handle)
+        return raw, filled
+
+
+# ------------------------------------------------------------------------------------------------ raw BGR24 input
+class _Bgr24Source:
+    """Whole frames of a raw BGR24 stream; a trailing partial frame raises ValueError."""
+
+    def __init__(self, src, w: int, h: int):
+        self.name = src if isinstance(src, str) else getattr(src, "name", "<stream>")
+        if src == "-":
+            self.f, self.own = sys.stdin.buffer, False
+        elif isinstance(src, (str, bytes, os.PathLike)):
+            self.f, self.own = open(src, "rb"), True
+        else:
+            self.f, self.own = src, False
+        self.frame_bytes = w * h * 3
+        self.frames = 0
+
+    def read_into(self, out: np.ndarray) -> bool:
+        """Fills out (one frame, C-contiguous) and returns True, or returns False at the end of the stream."""
+        mv = memoryview(out).cast("B")
+        got = 0
+        while got < self.frame_bytes:
+            n = self.f.readinto(mv[got:])
+            if not n:
+                break
+            got += n
+        if got == 0:
+            return False
+        if got < self.frame_bytes:
+            raise ValueError(f"{self.name}: truncated input, {got} bytes after {self.frames} frames of {self.frame_bytes}")
+        self.frames += 1
+        return True
+
+    def close(self):
+        if self.own:
+            self.f.close()
+
+
+def read_bgr24(path_or_stdin, w: int, h: int, chunk: int):
+    """Yields u8 [k][h][w][3] chunks, 1 <= k <= chunk, of a raw BGR24 stream (a path, "-" for stdin, or a binary file
+    object), to its end.  A trailing partial frame raises ValueError."""
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    src = _Bgr24Source(path_or_stdin, w, h)
+    try:
+        buf = np.empty((chunk, h, w, 3), np.uint8)
+        while True:
+            k = 0
+            while k < chunk and src.read_into(buf[k]):
+                k += 1
+            if k == 0:
+                return
+            yield buf[:k].copy()
+            if k < chunk:
+                return
+    finally:
+        src.close()
+
+
+# ------------------------------------------------------------------------------------------------ command line
+def parse_size(text: str):
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"size {text!r} is not WxH") from None
+    if (w, h) not in SIZES:
+        raise argparse.ArgumentTypeError(f"unsupported size {w}x{h}: one of " + ", ".join(f"{a}x{b}" for a, b in SIZES))
+    return w, h
+
+
+def parse_io(arg: str):
+    """IN[:OUT] -> (IN, OUT); OUT defaults to IN's name with `_gt.dump`."""
+    src, sep, out = arg.rpartition(":")
+    if not sep:
+        src, out = arg, ""
+    if not src:
+        raise argparse.ArgumentTypeError(f"{arg!r}: no input")
+    if not out:
+        if src == "-":
+            raise argparse.ArgumentTypeError("stdin ('-') needs an output: -:OUT_gt.dump")
+        out = os.path.splitext(src)[0] + "_gt.dump"
+    return src, out
+
+
+def _args(argv):
+    ap = argparse.ArgumentParser(prog="python -m cova_amd.mog", description=__doc__.split("\n")[0])
+    ap.add_argument("inputs", nargs="+", type=parse_io, metavar="IN[:OUT]",
+                    help="raw BGR24 video ('-' = stdin); OUT defaults to IN's name with _gt.dump")
+    ap.add_argument("--size", type=parse_size, required=True, help="source size: 640x360, 1280x720 or 1920x1080")
+    ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
+    ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
+    ap.add_argument("--history", type=int, default=9000)
+    ap.add_argument("--var-threshold", type=float, default=32.0)
+    ap.add_argument("--device", type=int, default=0)
+    a = ap.parse_args(argv)
+    if a.streams is None:
+        a.streams = min(len(a.inputs), 8)
+    if not 1 <= a.streams <= MAX_STREAMS:
+        ap.error(f"--streams must be in [1, {MAX_STREAMS}]")
+    if a.chunk < 1:
+        ap.error("--chunk must be >= 1")
+    if a.history < 1:
+        ap.error("--history must be >= 1")
+    if not (np.isfinite(a.var_threshold) and a.var_threshold > 0):
+        ap.error("--var-threshold must be > 0")
+    if sum(src == "-" for src, _ in a.inputs) > 1:
+        ap.error("stdin ('-') can be read once")
+    outs = [out for _, out in a.inputs]
+    if len(set(outs)) != len(outs):
+        ap.error("two inputs write the same output")
+    return a
+
+
+def main(argv=None) -> int:
+    a = _args(argv)
+    from .elements import Context
+
+    w, h = a.size
+    S = min(a.streams, len(a.inputs))
+    pending = list(a.inputs)
+    ctx = Context(a.device)
+    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold)
+    frames = np.empty((a.chunk, S, h, w, 3), np.uint8)
+    labels = np.zeros((a.chunk, S, LABEL_H, LABEL_W), np.uint8)
+    slots = [None] * S           # (source, output file, output name, start time) per stream slot
+
+    def open_next(s):
+        if not pending:
+            slots[s] = None
+            return
+        src, out = pending.pop(0)
+        slots[s] = (_Bgr24Source(src, w, h), open(out, "wb"), out, time.perf_counter())
+        mog.reset(s)
+
+    def finish(s):
+        src, f, out, t0 = slots[s]
+        src.close()
+        f.close()
+        dt = time.perf_counter() - t0
+        print(f"{src.name}: {src.frames} frames, {src.frames / dt if dt > 0 else 0.0:.1f} frames/s -> {out}", file=sys.stderr)
+
+    try:
+        for s in range(S):
+            open_next(s)
+        while any(slots):
+            nv = np.zeros(S, np.int32)
+            for s in range(S):
+                while slots[s] is not None:
+                    k = 0
+                    while k < a.chunk and slots[s][0].read_into(frames[k, s]):
+                        k += 1
+                    if k:
+                        nv[s] = k
+                        break
+                    finish(s)          # this video has ended: the slot takes the next one
+                    open_next(s)
+            if not nv.any():
+                break
+            mog.apply(frames[:int(nv.max())], n_valid=nv, labels=labels[:int(nv.max())])
+            for s in range(S):
+                if nv[s]:
+                    slots[s][1].write(np.ascontiguousarray(labels[:nv[s], s]).tobytes())
+    finally:
+        for s in range(S):
+            if slots[s] is not None:
+                slots[s][0].close()
+                slots[s][1].close()
+        mog.close()
+        ctx.close()
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

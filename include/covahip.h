@@ -296,6 +296,66 @@ int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n);
 int covahip_train_grads(covahip_train *tr, float *flat, size_t n);
 void covahip_train_destroy(covahip_train *tr);
 
+/* ------------------------------------------------------------ MoG labels
+ * The training labels of the reference's "train from scratch" flow, made on the GPU: what utils/generate-mog.py does with
+ * OpenCV to a decoded video, per frame in decode-output order, per video:
+ *   1. resize to 640x360 (cv.resize INTER_LINEAR).  Three source sizes, any other is COVAHIP_ERR_UNSUPPORTED:
+ *        640x360 copy; 1280x720 (OpenCV's area-fast path at an exact 2x scale) (a + b + c + d + 2) >> 2 per channel over the
+ *        2x2 block; 1920x1080 (linear weights (1, 0) at an exact 3x scale) source pixel (3x + 1, 3y + 1);
+ *   2. MOG2 of createBackgroundSubtractorMOG2(history, var_threshold, detectShadows = false), apply() with the default
+ *      learning rate (below);
+ *   3. fg = mask > 0;
+ *   4. close with a 4x4 ones kernel, then open with a 6x6 ones kernel.  OpenCV's anchor k/2, the same offsets for erode and
+ *      dilate: the window at x covers x - 2 .. x + 1 (4x4) and x - 3 .. x + 2 (6x6) in both axes; outside the image is 0 for
+ *      dilate and 1 for erode;
+ *   5. contour fill (findContours RETR_EXTERNAL + drawContours FILLED) as hole filling: foreground 8-connected, background
+ *      4-connected, every background 4-component that does not touch the image edge becomes 1;
+ *   6. label[i][j] = filled[8i][8j]: 45x80 bytes of 0 / 1 per frame, the file `tfrecordsink gt=` reads (frames one after the
+ *      other, as ndarray.tofile writes them).
+ * MOG2 (the CPU path of OpenCV 4.x MOG2Invoker, nmixtures 5).  All values f32 unless noted, every product and sum rounded on
+ * its own (no fused multiply-add), divisions correctly rounded:
+ *   constants Tb = var_threshold, TB = 0.9, Tg = 9, varInit = 15, varMin = 4, varMax = 75, fCT = 0.05f;
+ *   per frame: n += 1 (this stream's frames, from 1); lr = 1.0 / min(2n, history) in double; alphaT = (float)lr;
+ *     alpha1 = 1 - alphaT; prune = (float)(-lr * (double)0.05f).  The model starts all zero with nmodes = 0, so frame 1 is
+ *     all foreground;
+ *   per pixel, data = the three channels as float:
+ *     1. fits = false, bg = false, tw = 0;
+ *     2. for mode = 0 while mode < nmodes (the bound shrinks when a mode is pruned):
+ *          w = alpha1 * W[mode] + prune; swaps = 0;
+ *          if !fits: d = M[mode] - data per channel; dist2 = (d0*d0 + d1*d1) + d2*d2;
+ *            if tw < TB && dist2 < Tb * V[mode]: bg = true;
+ *            if dist2 < Tg * V[mode]: fits = true; w += alphaT; k = alphaT / w; M[mode] -= k * d per channel;
+ *              V[mode] = min(max(V + k * (dist2 - V), varMin), varMax);
+ *              for i = mode down to 1: stop if w < W[i-1], else swap entries i and i-1 (weight, variance, mean), swaps++;
+ *          if w < -prune: w = 0, nmodes--;
+ *          W[mode - swaps] = w; tw += w;
+ *     3. inv = |tw| > FLT_EPSILON ? 1 / tw : 0; W[i] *= inv for i < nmodes;
+ *     4. if !fits: slot m = nmodes == 5 ? 4 : nmodes++; if nmodes == 1: W[m] = 1, else W[m] = alphaT and W[i] *= alpha1 for
+ *        i < nmodes - 1; M[m] = data; V[m] = varInit; for i = nmodes - 1 down to 1: stop if alphaT < W[i-1], else swap;
+ *     5. mask = bg ? 0 : 255.
+ * Streams: n_streams independent videos advance in one call, each with its own model and frame count.  Memory: about 23 MB of
+ * model per stream.  Every call is synchronous. */
+enum { COVAHIP_MOG_MAX_STREAMS = 1024, COVAHIP_MOG_LABEL_H = 45, COVAHIP_MOG_LABEL_W = 80 };
+typedef struct covahip_mog covahip_mog;
+typedef struct covahip_mog_cfg {
+    int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 BGR24 */
+    int32_t n_streams;          /* independent videos advanced per call, 1 .. COVAHIP_MOG_MAX_STREAMS */
+    int32_t history;            /* 9000 (generate-mog.py); >= 1 */
+    float   var_threshold;      /* 32; finite and > 0 */
+} covahip_mog_cfg;
+/* generate-mog.py's settings: 1280x720 sources, one stream, history 9000, var_threshold 32. */
+void covahip_mog_default_cfg(covahip_mog_cfg *cfg);
+/* COVAHIP_ERR_UNSUPPORTED for another source size, COVAHIP_ERR_INVALID_ARG for streams, history or var_threshold out of range. */
+int  covahip_mog_create(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out);
+/* frames u8 [n_frames][n_streams][src_h][src_w][3]; labels u8 [n_frames][n_streams][45][80] (mem_kind applies to both; n_valid is
+ * always a host pointer).  n_valid[s] <= n_frames: frames past it are ignored for stream s and their labels untouched (NULL = all).
+ * n_frames >= 1.  Host frames are staged in launches of up to 1 GiB of frames. */
+int  covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const int32_t *n_valid,
+                       uint8_t *labels, int mem_kind);
+/* Next video in that slot: model zeroed, n = 0. */
+int  covahip_mog_reset(covahip_mog *m, int stream);
+void covahip_mog_destroy(covahip_mog *m);
+
 /* ------------------------------------------------------ sink formats, track export
  * Data formats either side of the hot path.               */
 /* tfrecordsink (cova-rs/gst-plugins/src/tfrecordsink/imp.rs:69-198): one framed TFRecord record =

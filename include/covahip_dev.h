@@ -62,6 +62,16 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
 struct covahip_pipe;
 int covahip_dev_pipe_queue_plan(struct covahip_pipe *pipe, int *lanes_on_upload_queue, int *lanes_on_result_queue);
 
+/* MoG labels (covahip_mog_apply) of the last call, expanded from its bit planes: raw = the MOG2 mask (0 / 255) and filled = the
+ * mask after close, open and hole fill (0 / 1), each u8 [n_frames][n_streams][360][640] (either may be NULL; cap = bytes of
+ * each; COVAHIP_ERR_OVERFLOW when too small).  *n_frames = that call's n_frames.  Frames past a stream's n_valid hold nothing
+ * meaningful.  (tests/test_gpu_mog.py) */
+struct covahip_mog;
+int covahip_dev_mog_masks(struct covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t cap, int *n_frames);
+/* One stream's model: W f32 [5][230400], V f32 [5][230400], M f32 [5][3][230400], nmodes u8 [230400] and n (frames seen);
+ * any pointer may be NULL. */
+int covahip_dev_mog_state(struct covahip_mog *m, int stream, float *W, float *V, float *M, uint8_t *nmodes, int64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,224 @@
+"""numpy float32 oracle of the MoG label generator (utils/generate-mog.py of the reference; the contract in include/covahip.h,
+"MoG labels").  Vectorised over pixels, looped over the five modes; every scalar is an np.float32 and every product and sum is
+rounded on its own (numpy never fuses), so this is the arithmetic the HIP kernels in cova_amd/csrc/mog.hip must match bit for bit.
+
+  resize_bgr      the three supported INTER_LINEAR cases: 640x360 copy, 1280x720 2x2 mean, 1920x1080 centre pick
+  Mog2            createBackgroundSubtractorMOG2(history, varThreshold, detectShadows=False).apply, nmixtures 5
+  dilate / erode  rectangular kernels with OpenCV's anchor k/2 (window x - k/2 .. x + k - 1 - k/2), neutral border
+  fill_holes      background 4-components not touching the image edge become foreground
+  post            close 4x4, open 6x6, fill, ::8 subsample
+"""
+from __future__ import annotations
+
+import numpy as np
+
+WORK_W, WORK_H = 640, 360
+LABEL_W, LABEL_H = 80, 45
+NMIX = 5
+F32 = np.float32
+
+TB = F32(0.9)
+TG = F32(9.0)
+VAR_INIT = F32(15.0)
+VAR_MIN = F32(4.0)
+VAR_MAX = F32(75.0)
+FCT = F32(0.05)
+FLT_EPSILON = F32(np.finfo(np.float32).eps)
+
+
+def resize_bgr(frame: np.ndarray) -> np.ndarray:
+    """u8 [h][w][3] -> u8 [360][640][3] as cv.resize(frame, (640, 360)) does for the three supported sizes."""
+    h, w, _ = frame.shape
+    if (w, h) == (640, 360):
+        return frame.copy()
+    if (w, h) == (1280, 720):
+        f = frame.astype(np.uint32)
+        s = f[0::2, 0::2] + f[0::2, 1::2] + f[1::2, 0::2] + f[1::2, 1::2]
+        return ((s + 2) >> 2).astype(np.uint8)
+    if (w, h) == (1920, 1080):
+        return frame[1::3, 1::3].copy()
+    raise ValueError(f"unsupported source size {w}x{h}")
+
+
+def learning_rates(n: int, history: int):
+    """(alphaT, prune) of the n-th frame of a stream (n from 1): lr = 1 / min(2n, history) in double."""
+    lr = 1.0 / min(2 * n, history)
+    return F32(lr), F32(-lr * float(FCT))
+
+
+class Mog2:
+    """The per-pixel mixture model over P pixels.  W, V: [5][P]; M: [5][3][P]; nmodes: [P]; n: frames seen."""
+
+    def __init__(self, npix: int = WORK_W * WORK_H, history: int = 9000, var_threshold: float = 32.0):
+        self.P = npix
+        self.history = history
+        self.Tb = F32(var_threshold)
+        self.W = np.zeros((NMIX, npix), F32)
+        self.V = np.zeros((NMIX, npix), F32)
+        self.M = np.zeros((NMIX, 3, npix), F32)
+        self.nmodes = np.zeros(npix, np.int32)
+        self.n = 0
+
+    def _swap(self, sel, i, j):
+        if not sel.any():
+            return
+        for a in (self.W, self.V):
+            ai, aj = a[i].copy(), a[j].copy()
+            a[i] = np.where(sel, aj, ai)
+            a[j] = np.where(sel, ai, aj)
+        mi, mj = self.M[i].copy(), self.M[j].copy()
+        self.M[i] = np.where(sel, mj, mi)
+        self.M[j] = np.where(sel, mi, mj)
+
+    def apply(self, frame: np.ndarray) -> np.ndarray:
+        """frame u8 [360][640][3] (BGR, already resized; any [..][3] of P pixels) -> mask u8 of the frame's shape without
+        the channels, 0 background / 255 foreground."""
+        self.n += 1
+        alphaT, prune = learning_rates(self.n, self.history)
+        alpha1 = F32(1) - alphaT
+        data = frame.reshape(-1, 3).T.astype(F32)            # [3][P]
+        W, V, M, nm = self.W, self.V, self.M, self.nmodes
+        P = self.P
+        fits = np.zeros(P, bool)
+        bg = np.zeros(P, bool)
+        tw = np.zeros(P, F32)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            for mode in range(NMIX):
+                act = mode < nm                                   # the bound shrinks when a mode is pruned
+                if not act.any():
+                    break
+                w = alpha1 * W[mode] + prune
+                chk = act & ~fits
+                d = M[mode] - data
+                dist2 = (d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]
+                var = V[mode]
+                bg |= chk & (tw < TB) & (dist2 < self.Tb * var)
+                fit = chk & (dist2 < TG * var)
+                fits |= fit
+                w = np.where(fit, w + alphaT, w)
+                k = alphaT / w
+                M[mode] = np.where(fit, M[mode] - k * d, M[mode])
+                vn = var + k * (dist2 - var)
+                vn = np.where(vn < VAR_MIN, VAR_MIN, vn)
+                vn = np.where(VAR_MAX < vn, VAR_MAX, vn)
+                V[mode] = np.where(fit, vn, var)
+                swaps = np.zeros(P, np.int32)
+                go = fit.copy()
+                for i in range(mode, 0, -1):
+                    go &= ~(w < W[i - 1])
+                    self._swap(go, i, i - 1)
+                    swaps += go
+                prn = act & (w < -prune)
+                w = np.where(prn, F32(0), w)
+                nm -= prn.astype(np.int32)
+                for j in range(mode + 1):
+                    sel = act & (mode - swaps == j)
+                    W[j] = np.where(sel, w, W[j])
+                tw = np.where(act, tw + w, tw)
+            inv = np.where(np.abs(tw) > FLT_EPSILON, F32(1) / tw, F32(0)).astype(F32)
+            for i in range(NMIX):
+                W[i] = np.where(i < nm, W[i] * inv, W[i])
+        nf = ~fits
+        m = np.where(nm == NMIX, NMIX - 1, nm)
+        nm += (nf & (nm < NMIX)).astype(np.int32)
+        for j in range(NMIX):
+            sel = nf & (m == j)
+            W[j] = np.where(sel, np.where(nm == 1, F32(1), alphaT), W[j])
+            M[j] = np.where(sel, data, M[j])
+            V[j] = np.where(sel, VAR_INIT, V[j])
+        for i in range(NMIX):
+            sc = nf & (nm > 1) & (i < nm - 1)
+            W[i] = np.where(sc, W[i] * alpha1, W[i])
+        go = nf.copy()
+        for i in range(NMIX - 1, 0, -1):
+            a = go & (i < nm)
+            stop = a & (alphaT < W[i - 1])
+            self._swap(a & ~stop, i, i - 1)
+            go &= ~stop
+        return np.where(bg, 0, 255).astype(np.uint8).reshape(frame.shape[:-1])
+
+
+# ------------------------------------------------------------------------------------------------ post-processing
+def _shift(a: np.ndarray, dy: int, dx: int, fill: bool) -> np.ndarray:
+    """out[y][x] = a[y + dy][x + dx], `fill` outside."""
+    h, w = a.shape
+    out = np.full_like(a, fill)
+    ys, yd = (slice(dy, h), slice(0, h - dy)) if dy >= 0 else (slice(0, h + dy), slice(-dy, h))
+    xs, xd = (slice(dx, w), slice(0, w - dx)) if dx >= 0 else (slice(0, w + dx), slice(-dx, w))
+    out[yd, xd] = a[ys, xs]
+    return out
+
+
+def dilate(a: np.ndarray, k: int) -> np.ndarray:
+    """k x k ones kernel, anchor k/2: out(x) = OR of a over x - k/2 .. x + k - 1 - k/2 in both axes, 0 outside."""
+    a = a.astype(bool)
+    out = np.zeros_like(a)
+    for dy in range(-(k // 2), k - k // 2):
+        for dx in range(-(k // 2), k - k // 2):
+            out |= _shift(a, dy, dx, False)
+    return out
+
+
+def erode(a: np.ndarray, k: int) -> np.ndarray:
+    """The same window as dilate, AND, 1 outside."""
+    a = a.astype(bool)
+    out = np.ones_like(a)
+    for dy in range(-(k // 2), k - k // 2):
+        for dx in range(-(k // 2), k - k // 2):
+            out &= _shift(a, dy, dx, True)
+    return out
+
+
+def fill_holes(fg: np.ndarray) -> np.ndarray:
+    """Background is 4-connected: every background pixel not 4-connected to the image edge through background becomes 1."""
+    bgm = ~fg.astype(bool)
+    r = np.zeros_like(bgm)
+    r[0], r[-1], r[:, 0], r[:, -1] = bgm[0], bgm[-1], bgm[:, 0], bgm[:, -1]
+    while True:
+        grow = r | _shift(r, 1, 0, False) | _shift(r, -1, 0, False) | _shift(r, 0, 1, False) | _shift(r, 0, -1, False)
+        grow &= bgm
+        if (grow == r).all():
+            return ~r
+        # long corridors: run along rows and columns before the next 4-neighbour step
+        r = grow
+        for axis in (0, 1):
+            r = _runs(r, bgm, axis)
+
+
+def _runs(r: np.ndarray, m: np.ndarray, axis: int) -> np.ndarray:
+    """Every run of m along `axis` that holds a pixel of r becomes part of r."""
+    rr = np.moveaxis(r, axis, -1)
+    mm = np.moveaxis(m, axis, -1)
+    n = mm.shape[-1]
+    starts = np.concatenate([np.ones(mm.shape[:-1] + (1,), bool), ~mm[..., :-1]], axis=-1) & mm
+    run_id = np.cumsum(starts, axis=-1) * mm                     # 1-based id of the run within its line, 0 off the mask
+    hit = np.zeros(mm.shape[:-1] + (n + 1,), bool)
+    np.put_along_axis(hit, np.where(rr, run_id, 0), True, axis=-1)
+    hit[..., 0] = False
+    out = np.take_along_axis(hit, run_id, axis=-1) & mm
+    return np.moveaxis(out, -1, axis)
+
+
+def post(mask: np.ndarray):
+    """mask u8 [360][640] (0 / 255) -> (filled u8 [360][640] of 0 / 1, labels u8 [45][80])."""
+    fg = mask > 0
+    cl = erode(dilate(fg, 4), 4)
+    op = dilate(erode(cl, 6), 6)
+    filled = fill_holes(op).astype(np.uint8)
+    return filled, np.ascontiguousarray(filled[::8, ::8])
+
+
+def label_video(frames: np.ndarray, history: int = 9000, var_threshold: float = 32.0, model: Mog2 | None = None):
+    """frames u8 [F][h][w][3] -> (raw masks [F][360][640], filled [F][360][640], labels [F][45][80], the model)."""
+    mdl = model if model is not None else Mog2(history=history, var_threshold=var_threshold)
+    raws, fills, labels = [], [], []
+    for fr in frames:
+        raw = mdl.apply(resize_bgr(fr))
+        fl, lab = post(raw)
+        raws.append(raw)
+        fills.append(fl)
+        labels.append(lab)
+    shp = (0, WORK_H, WORK_W)
+    if not raws:
+        return np.zeros(shp, np.uint8), np.zeros(shp, np.uint8), np.zeros((0, LABEL_H, LABEL_W), np.uint8), mdl
+    return np.stack(raws), np.stack(fills), np.stack(labels), mdl

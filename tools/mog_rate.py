@@ -1,0 +1,111 @@
+#!/usr/bin/env python
+"""MoG label throughput on one GPU: 640x360 working frames per second of covahip_mog_apply at several stream counts.
+
+    python tools/mog_rate.py [--streams 1,8,64 --sizes 1280x720,640x360 --frames 1024 --reps 3] [--oracle-frames 3]
+
+Two cases per (source size, streams), one JSON line each:
+  device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
+  host     frames from (pageable) host memory, wall clock of the call: the H2D copy and the label read-back included.
+Each call advances every stream by frames / streams frames, so the model is read and written once per call.  The line also has
+each kernel's share of the device call (HIP-event brackets, covahip_profile_*).  --oracle-frames > 0 adds a line with the numpy
+oracle's (tests/mog_ref.py) frames/s on this machine's CPU.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import numpy as np  # noqa: E402
+
+from cova_amd import mog  # noqa: E402
+from cova_amd.elements import Context  # noqa: E402
+
+
+def clip(n, w, h, seed=0):
+    """n distinct BGR frames: a textured background with noise and a moving block."""
+    rng = np.random.default_rng(seed)
+    base = rng.integers(30, 200, (h // 8, w // 8, 3)).repeat(8, 0).repeat(8, 1).astype(np.int16)
+    out = np.empty((n, h, w, 3), np.uint8)
+    for t in range(n):
+        f = base + rng.integers(-3, 4, base.shape, dtype=np.int16)
+        x = (t * w // 16) % (w - w // 8)
+        f[h // 3:h // 3 + h // 6, x:x + w // 8] = (250, 40, 90)
+        out[t] = np.clip(f, 0, 255).astype(np.uint8)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", default="1,8,64")
+    ap.add_argument("--sizes", default="1280x720,640x360")
+    ap.add_argument("--frames", type=int, default=1024, help="working frames per call (all streams)")
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--oracle-frames", type=int, default=3)
+    ap.add_argument("--no-host", action="store_true")
+    a = ap.parse_args()
+    ctx = Context(0)
+    for size in a.sizes.split(","):
+        w, h = mog.parse_size(size)
+        pool = clip(8, w, h)
+        for S in (int(s) for s in a.streams.split(",")):
+            F = max(8, a.frames // S)
+            frames = np.empty((F, S, h, w, 3), np.uint8)
+            for f in range(F):
+                frames[f] = pool[(f + np.arange(S)) % len(pool)]
+            labels = np.zeros((F, S, 45, 80), np.uint8)
+            m = mog.MogLabeler(ctx, w, h, streams=S)
+            d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
+            ctx.h2d(d_f, frames)
+            m.apply_device(d_f, F, d_l)                      # warm-up (buffers, code objects)
+            ms = []
+            for _ in range(a.reps):
+                ctx.timer_start(0)
+                m.apply_device(d_f, F, d_l)
+                ctx.timer_stop(0)
+                ms.append(ctx.timer_ms(0))
+            ctx.profile(True)
+            m.apply_device(d_f, F, d_l)
+            prof = ctx.profile_read()
+            ctx.profile(False)
+            tot = sum(v[0] for k, v in prof.items() if k.startswith("mog_"))
+            med = statistics.median(ms)
+            rec = {"case": "device", "src": size, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+                   "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms],
+                   "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
+                   "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
+            print(json.dumps(rec), flush=True)
+            ctx.free(d_f)
+            ctx.free(d_l)
+            if not a.no_host:
+                m.apply(frames, labels=labels)
+                wall = []
+                for _ in range(a.reps):
+                    t0 = time.perf_counter()
+                    m.apply(frames, labels=labels)
+                    wall.append((time.perf_counter() - t0) * 1e3)
+                med = statistics.median(wall)
+                print(json.dumps({"case": "host", "src": size, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+                                  "frames_per_s": round(F * S / med * 1e3, 1), "in_gb_per_s": round(frames.nbytes / med / 1e6, 2),
+                                  "ms_all": [round(x, 3) for x in wall]}), flush=True)
+            m.close()
+            del frames
+    ctx.close()
+    if a.oracle_frames > 0:
+        from tests import mog_ref as R
+        vid = clip(a.oracle_frames + 1, 1280, 720)
+        mdl = R.Mog2()
+        R.post(mdl.apply(R.resize_bgr(vid[0])))
+        t0 = time.perf_counter()
+        for f in vid[1:]:
+            R.post(mdl.apply(R.resize_bgr(f)))
+        dt = time.perf_counter() - t0
+        print(json.dumps({"case": "oracle_cpu", "src": "1280x720", "frames": a.oracle_frames,
+                          "frames_per_s": round(a.oracle_frames / dt, 2)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
