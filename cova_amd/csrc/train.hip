@@ -189,11 +189,13 @@ enum FinMode { F_MEAN = 0, F_VAR = 1, F_SUM2 = 2, F_SUM = 3 };
 // stat: [2][C].  F_MEAN: stat[0] = mean.  F_VAR: stat[1] = 1/sqrt(var + eps), g0/g1 = batch mean / biased variance, mov0/mov1
 // moving statistics (variance with n/(n-1)).  F_SUM2: stat = (sum a, sum b), g0 = sum b, g1 = sum a (BN gamma / beta
 // gradients).  F_SUM: g0 = sum a.
+// The slabs are summed in double: a channel of a large batch has over a thousand of them (1,125 at encoder level 0 of 45x80 at
+// batch 320), and a float running sum over that many moves the batch statistics far enough to flip ReLU / max-pool decisions.
 __global__ void k_finalize(int mode, int C, int NP, const float *__restrict__ part, double M, float *stat, float *g0, float *g1,
                            float *mov0, float *mov1, float mom, float eps) {
     const int c = blockIdx.x * BLK + threadIdx.x;
     if (c >= C) return;
-    float a = 0.f, b = 0.f;
+    double a = 0.0, b = 0.0;
     for (int p = 0; p < NP; p++) {
         a += part[((int64_t)c * NP + p) * 2];
         b += part[((int64_t)c * NP + p) * 2 + 1];
@@ -208,12 +210,12 @@ __global__ void k_finalize(int mode, int C, int NP, const float *__restrict__ pa
         mov0[c] = mom * mov0[c] + (1.f - mom) * mean;
         mov1[c] = mom * mov1[c] + (1.f - mom) * (float)(var * (M / (M - 1.0)));
     } else if (mode == F_SUM2) {
-        stat[c] = a;
-        stat[C + c] = b;
-        if (g0) g0[c] = b;
-        if (g1) g1[c] = a;
+        stat[c] = (float)a;
+        stat[C + c] = (float)b;
+        if (g0) g0[c] = (float)b;
+        if (g1) g1[c] = (float)a;
     } else {
-        g0[c] = a;
+        g0[c] = (float)a;
     }
 }
 

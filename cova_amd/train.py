@@ -321,6 +321,14 @@ class Trainer:
         self.step_count += 1
         return float(loss.value)
 
+    def step_device(self, d_stack: int, d_gt: int, batch: int, lr: float | None = None) -> float:
+        """The same on device pointers (stack u8 [batch][4h][w][4], labels u8 [batch][h][w] on the ctx's GPU)."""
+        loss = C.c_float()
+        L.check(self._lib.covahip_train_step(self.handle, d_stack, d_gt, batch, self.cfg.lr if lr is None else lr, C.byref(loss),
+                                             L.MEM_DEVICE), "covahip_train_step", self.ctx.handle)
+        self.step_count += 1
+        return float(loss.value)
+
     def metrics(self):
         """(TP, FP, FN) of the last step at sigmoid > 0.5."""
         v = (C.c_int64 * 3)()
