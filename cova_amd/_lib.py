@@ -153,6 +153,13 @@ PROTOTYPES = {
     "covahip_carrier_write_records": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _SZ]),
     "covahip_carrier_pack": (None, [_P, _SZ, _P]),
     "covahip_filter_forward_frames_packed": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
+    "covahip_blobnet_load_set": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "covahip_blobnet_num_models": (C.c_int, [_P, _P]),
+    "covahip_pipe_model_ids": (C.c_int, [_P, C.c_int, _P]),
+    "covahip_blobnet_forward_m": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_filter_forward_m": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_filter_forward_frames_m": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_filter_forward_frames_packed_m": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "covahip_stack_new": (C.c_int, [_SZ, C.c_uint, C.c_uint, C.POINTER(_P)]),
     "covahip_stack_free": (None, [_P]),
     "covahip_stack_push": (C.c_int, [_P, _P, _SZ, _P, _SZ, C.POINTER(C.c_int)]),

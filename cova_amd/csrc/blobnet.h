@@ -34,10 +34,17 @@ struct BnWorkspace {
     hipEvent_t ev_index = nullptr;    // upload of h_index done (the next call may overwrite it)
     std::vector<int32_t> last_table;  // the table that is resident in d_index (an unchanged table is not uploaded again)
     int last_n_frames = 0;
+    // model ids of a mixed batch (model sets): u8 [batch] per stack, then u8 [n_frames] per carrier frame
+    uint8_t *d_models = nullptr;
+    uint8_t *h_models = nullptr;      // pinned host copy it is uploaded from
+    size_t models_cap = 0;            // capacity of both
+    hipEvent_t ev_models = nullptr;   // upload of h_models done
+    std::vector<uint8_t> last_models; // the ids resident in d_models (unchanged ids are not uploaded again)
 };
 
 struct covahip_blobnet {
     int H = 0, W = 0, max_batch = 0;
+    int n_models = 1;   // models of the set; their prepared weights lie Prepared::total bytes apart from d_prepared on
     BnLevelGeom lv[BN_LEVELS + 1];
     int enc_c[BN_LEVELS + 1] = {3, 16, 32, 64, 128};
     int dec_ci[BN_LEVELS] = {128, 128, 64, 32};
@@ -69,7 +76,8 @@ inline bool bn_level1_on_enc1(const covahip_ctx *ctx, const covahip_blobnet *m) 
 }
 
 // blobnet_mfma.hip
-int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *h_weights);
+// n_models parameter blobs of one geometry; allpos[level] is the AND over the set and every model is prepared with it
+int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *const *h_weights, int n_models);
 void blobnet_release_mfma(covahip_ctx *ctx, covahip_blobnet *m);
 // cc != nullptr: bboxcc is wanted on the mask; *cc_done tells whether the forward already ran it (fused tail)
 struct BnCcTail {
@@ -90,6 +98,12 @@ struct BnInput {
     const int32_t *h_index = nullptr;
     bool packed = false;   // carrier frames as two-byte records (covahip_carrier_pack) instead of the decoder's four bytes
     bool dry = false;
+    // model sets: either ONE model for the whole batch (model_ids == nullptr; its weights are `model` strides past model 0), or a
+    // mixed batch: u8 model id per stack [batch] and per carrier frame [n_frames], on the device (the MS = true kernels)
+    int model = 0;
+    const uint8_t *model_ids = nullptr;
+    const uint8_t *frame_models = nullptr;
+    bool mixed = false;    // dry: plan the mixed-batch kernels
 };
 int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const BnInput &in, int batch, float *d_logits,
                          uint8_t *d_mask, const BnCcTail *cc = nullptr, bool *cc_done = nullptr);

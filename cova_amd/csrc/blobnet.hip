@@ -32,6 +32,9 @@ static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
         if (ws.d_index) hipFree(ws.d_index);
         if (ws.h_index) hipHostFree(ws.h_index);
         if (ws.ev_index) hipEventDestroy(ws.ev_index);
+        if (ws.d_models) hipFree(ws.d_models);
+        if (ws.h_models) hipHostFree(ws.h_models);
+        if (ws.ev_models) hipEventDestroy(ws.ev_models);
     }
     delete m;
 }
@@ -51,16 +54,82 @@ int covahip_blobnet_geometry(covahip_ctx *ctx, int *h, int *w) {
     return COVAHIP_OK;
 }
 
+// Model sets: every id of a call names a model of the set.
+static int check_model_ids(const covahip_blobnet *m, const uint8_t *model_ids, int batch) {
+    if (model_ids)
+        for (int b = 0; b < batch; b++)
+            if (model_ids[b] >= m->n_models) return COVAHIP_ERR_INVALID_ARG;
+    return COVAHIP_OK;
+}
+
+// The model ids of a call (host array, one per stack; null: model 0) -> in.  A batch of ONE model runs the single-model kernels on
+// that model's weights (in.model); a mixed batch gets its ids per stack and per carrier frame uploaded to the lane's workspace
+// (in.model_ids, in.frame_models; ids equal to the resident ones are not uploaded again).  table: the stack -> frame table of a
+// carrier-frame call, null for the stacked entry (stack b = frames 4b .. 4b+3).  Level 0 runs once per carrier frame, so a frame
+// that stacks of two models read is an error; a frame no stack reads runs under model 0.
+static int resolve_models(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const uint8_t *model_ids, int batch,
+                          const int32_t *table, int n_frames, BnInput &in) {
+    in.model = 0;
+    in.model_ids = nullptr;
+    in.frame_models = nullptr;
+    if (!model_ids) return COVAHIP_OK;
+    if (int rc = check_model_ids(m, model_ids, batch)) return rc;
+    bool uniform = true;
+    for (int b = 1; b < batch && uniform; b++) uniform = model_ids[b] == model_ids[0];
+    if (uniform) {
+        in.model = model_ids[0];
+        return COVAHIP_OK;
+    }
+    std::vector<uint8_t> ids((size_t)batch + n_frames, 0);
+    std::vector<uint8_t> seen((size_t)n_frames, 0);
+    std::copy(model_ids, model_ids + batch, ids.begin());
+    for (int b = 0; b < batch; b++)
+        for (int t = 0; t < BN_T; t++) {
+            const int f = table ? table[(size_t)b * BN_T + t] : b * BN_T + t;
+            uint8_t &fm = ids[(size_t)batch + f];
+            if (seen[f] && fm != model_ids[b]) return COVAHIP_ERR_INVALID_ARG;
+            seen[f] = 1;
+            fm = model_ids[b];
+        }
+    if (!(ws.d_models && ids == ws.last_models)) {
+        if (ws.d_models) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ws.ev_models));   // the pinned copy is free again
+        if (ids.size() > ws.models_cap) {
+            if (ws.d_models) {
+                COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                hipFree(ws.d_models);
+                hipHostFree(ws.h_models);
+                ws.d_models = nullptr; ws.h_models = nullptr; ws.models_cap = 0;
+                ws.last_models.clear();
+            }
+            const size_t cap = std::max(ids.size(), (size_t)m->max_batch * (1 + BN_T));
+            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.d_models, cap));
+            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ws.h_models, cap, hipHostMallocDefault));
+            ws.models_cap = cap;
+            if (!ws.ev_models) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ws.ev_models, hipEventDisableTiming));
+        }
+        std::copy(ids.begin(), ids.end(), ws.h_models);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ws.d_models, ws.h_models, ids.size(), hipMemcpyHostToDevice, ctx->stream));
+        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ws.ev_models, ctx->stream));
+        ws.last_models = std::move(ids);
+    }
+    in.model_ids = ws.d_models;
+    in.frame_models = ws.d_models + batch;
+    return COVAHIP_OK;
+}
+
 // BlobNet forward (+ optionally bboxcc) on device pointers, asynchronous on the ctx stream.
 static int ensure_pbuf(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, int n_frames);
-static int filter_dev(covahip_ctx *ctx, const BnInput &in, int batch, float *d_logits, uint8_t *d_mask,
-                      bool with_cc, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes) {
+static int filter_dev(covahip_ctx *ctx, BnInput &in, int batch, float *d_logits, uint8_t *d_mask,
+                      bool with_cc, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes,
+                      const uint8_t *model_ids = nullptr) {
     covahip_blobnet *m = ctx->blobnet;
     if (!m) return COVAHIP_ERR_NOT_LOADED;
     if (batch > m->max_batch) return COVAHIP_ERR_INVALID_ARG;
     if (batch == 0) return COVAHIP_OK;
     if (in.stack) {   // the stacked tensor is batch * T carrier frames (blobnet_mfma.hip)
-        const int rc = ensure_pbuf(ctx, m, m->ws[ctx->cur_lane], batch * BN_T);
+        int rc = resolve_models(ctx, m, m->ws[ctx->cur_lane], model_ids, batch, nullptr, batch * BN_T, in);
+        if (rc) return rc;
+        rc = ensure_pbuf(ctx, m, m->ws[ctx->cur_lane], batch * BN_T);
         if (rc) return rc;
     }
     BnCcTail tail{area_thresh, max_boxes, d_boxes, d_counts};
@@ -78,7 +147,7 @@ static int filter_dev(covahip_ctx *ctx, const BnInput &in, int batch, float *d_l
 // out-of-bounds read on the GPU) and uploads it.  stack_index == nullptr: one stream in order.  A table equal to the
 // one resident in this lane's workspace is not uploaded again.
 static int prepare_frames(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const uint8_t *d_frames, int n_frames,
-                          const int32_t *stack_index, int batch, BnInput &in) {
+                          const int32_t *stack_index, int batch, BnInput &in, const uint8_t *model_ids = nullptr) {
     if (n_frames < BN_T || n_frames > BN_T * m->max_batch) return COVAHIP_ERR_INVALID_ARG;
     if (!stack_index && batch != n_frames - (BN_T - 1)) return COVAHIP_ERR_INVALID_ARG;
     std::vector<int32_t> table((size_t)batch * BN_T);
@@ -88,6 +157,8 @@ static int prepare_frames(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws,
             if (f < 0 || f >= n_frames) return COVAHIP_ERR_INVALID_ARG;
             table[(size_t)b * BN_T + t] = f;
         }
+    // model ids per stack and per frame (a frame shared across models is rejected here, before anything is uploaded or launched)
+    if (int rc = resolve_models(ctx, m, ws, model_ids, batch, table.data(), n_frames, in)) return rc;
     // small batches: the table travels in the level-1 kernel's arguments (blobnet_mfma.hip); the device copy below is for
     // larger ones and for the round-1..3 level-1 kernel
     const bool by_value = batch <= BN_KTAB_STACKS && n_frames <= 65535 && bn_level1_on_enc1(ctx, m);
@@ -149,10 +220,10 @@ static int ensure_pbuf(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, in
 }
 
 int covahip_blobnet_forward_dev(covahip_ctx *ctx, const uint8_t *d_stack, int batch, float *d_logits,
-                                uint8_t *d_mask) {
+                                uint8_t *d_mask, const uint8_t *model_ids) {
     BnInput in;
     in.stack = d_stack;
-    return filter_dev(ctx, in, batch, d_logits, d_mask, false, 0, nullptr, nullptr, 0);
+    return filter_dev(ctx, in, batch, d_logits, d_mask, false, 0, nullptr, nullptr, 0, model_ids);
 }
 
 // HBM workspace of one lane: activations stay resident; pad rows/columns are zeroed once here and never written
@@ -188,7 +259,7 @@ int covahip_blobnet_grow_lanes(covahip_ctx *ctx, int n_lanes) {
 
 // Geometry, HBM workspace and prepared weights of a model.  Every limit of the kernels is checked here (a
 // planning-only pass of the forward for batch 1 and max_batch), so an unsupported grid fails at load time.
-static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *h_w, int h_mb, int w_mb, int max_batch) {
+static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *const *h_w, int n_models, int h_mb, int w_mb, int max_batch) {
     m->H = h_mb;
     m->W = w_mb;
     m->max_batch = max_batch;
@@ -218,13 +289,14 @@ static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *h_w, i
         const int rc = alloc_workspace(ctx, m, m->ws[k]);
         if (rc) return rc;
     }
-    int rc = blobnet_prepare_mfma(ctx, m, h_w);
+    int rc = blobnet_prepare_mfma(ctx, m, h_w, n_models);
     if (rc) return rc;
-    BnInput plan;   // planning only, both input forms, smallest and largest batch
+    BnInput plan;   // planning only, both input forms, smallest and largest batch (a set: also the mixed-batch kernels)
     plan.dry = true;
-    for (int pass = 0; pass < 4 && !rc; pass++) {
+    for (int pass = 0; pass < (n_models > 1 ? 8 : 4) && !rc; pass++) {
         const int b = (pass & 1) ? max_batch : 1;
         plan.n_frames = (pass & 2) ? b + BN_T - 1 : 0;   // both entry points
+        plan.mixed = (pass & 4) != 0;
         rc = blobnet_forward_mfma(ctx, m, m->ws[0], plan, b, nullptr, nullptr, nullptr, nullptr);
     }
     return rc;
@@ -232,26 +304,45 @@ static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *h_w, i
 
 extern "C" {
 
-int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_bytes, int h_mb, int w_mb, int t,
-                         int max_batch) {
-    if (!ctx || !weights || h_mb <= 0 || w_mb <= 0 || max_batch <= 0) return COVAHIP_ERR_INVALID_ARG;
-    if (t != BN_T) return COVAHIP_ERR_UNSUPPORTED;
-    if (h_mb < 16 || w_mb < 16 || h_mb > 1024 || w_mb > 1024) return COVAHIP_ERR_UNSUPPORTED;
-    if (weights_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
+// A CVHW blob's header and size; the parameters behind the 64-byte header.
+static const float *check_blob(const void *weights, size_t weights_bytes) {
+    if (!weights || weights_bytes < 64) return nullptr;
     uint32_t hdr[16];
     std::memcpy(hdr, weights, 64);
     static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
     for (int i = 0; i < 13; i++)
-        if (hdr[i] != want[i]) return COVAHIP_ERR_BAD_WEIGHTS;
-    if (weights_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
-    const float *h_w = reinterpret_cast<const float *>(static_cast<const uint8_t *>(weights) + 64);
+        if (hdr[i] != want[i]) return nullptr;
+    if (weights_bytes != 64 + N_PARAMS * sizeof(float)) return nullptr;
+    return reinterpret_cast<const float *>(static_cast<const uint8_t *>(weights) + 64);
+}
+
+int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_bytes, int h_mb, int w_mb, int t,
+                         int max_batch) {
+    if (!ctx || !weights) return COVAHIP_ERR_INVALID_ARG;
+    if (t == BN_T && h_mb >= 16 && w_mb >= 16 && h_mb <= 1024 && w_mb <= 1024 && max_batch > 0 && !check_blob(weights, weights_bytes))
+        return COVAHIP_ERR_BAD_WEIGHTS;   // a bad blob alone leaves the model loaded before in place
+    return covahip_blobnet_load_set(ctx, 1, &weights, &weights_bytes, h_mb, w_mb, t, max_batch);
+}
+
+int covahip_blobnet_load_set(covahip_ctx *ctx, int n_models, const void *const *weights, const size_t *weights_bytes, int h_mb,
+                             int w_mb, int t, int max_batch) {
+    if (!ctx || !weights || !weights_bytes || h_mb <= 0 || w_mb <= 0 || max_batch <= 0) return COVAHIP_ERR_INVALID_ARG;
+    if (n_models < 1 || n_models > COVAHIP_MAX_MODELS) return COVAHIP_ERR_INVALID_ARG;
+    for (int k = 0; k < n_models; k++)
+        if (!weights[k]) return COVAHIP_ERR_INVALID_ARG;
+    if (t != BN_T) return COVAHIP_ERR_UNSUPPORTED;
+    if (h_mb < 16 || w_mb < 16 || h_mb > 1024 || w_mb > 1024) return COVAHIP_ERR_UNSUPPORTED;
+    std::vector<const float *> h_w(n_models);
+    bool bad = false;
+    for (int k = 0; k < n_models; k++) bad = bad || !(h_w[k] = check_blob(weights[k], weights_bytes[k]));
 
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     covahip_blobnet_destroy(ctx);
+    if (bad) return COVAHIP_ERR_BAD_WEIGHTS;   // (whatever the ctx held is gone: the same rule as a failed build below)
     // The model is built on the side and attached to the ctx only when every step succeeded: a failed
     // load leaves the ctx without a model (COVAHIP_ERR_NOT_LOADED afterwards), never with half of one.
     covahip_blobnet *m = new covahip_blobnet();
-    int rc = build_model(ctx, m, h_w, h_mb, w_mb, max_batch);
+    int rc = build_model(ctx, m, h_w.data(), n_models, h_mb, w_mb, max_batch);
     if (rc == COVAHIP_OK && hipStreamSynchronize(ctx->stream) != hipSuccess) rc = COVAHIP_ERR_HIP;
     if (rc) {
         hipStreamSynchronize(ctx->stream);
@@ -260,6 +351,13 @@ int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_b
         return rc;
     }
     ctx->blobnet = m;
+    return COVAHIP_OK;
+}
+
+int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models) {
+    if (!ctx || !n_models) return COVAHIP_ERR_INVALID_ARG;
+    if (!ctx->blobnet) return COVAHIP_ERR_NOT_LOADED;
+    *n_models = ctx->blobnet->n_models;
     return COVAHIP_OK;
 }
 
@@ -292,7 +390,7 @@ int covahip_blobnet_set_impl(covahip_ctx *ctx, int impl) {
 // The hot path on device pointers, on ctx->stream with the current lane's workspace (the caller has placed the call).
 static int filter_placed(covahip_ctx *ctx, covahip_blobnet *m, const uint8_t *d_src, int n_frames, const int32_t *stack_index,
                          int batch, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes, float *d_logits,
-                         uint8_t *d_mask, bool packed = false) {
+                         uint8_t *d_mask, bool packed = false, const uint8_t *model_ids = nullptr) {
     if (!d_mask) {
         CtxLane &l = ctx->lane();
         int rc = covahip_ensure_buffer(ctx, &l.cc_scratch, &l.cc_scratch_bytes, (size_t)batch * m->H * m->W);
@@ -301,25 +399,26 @@ static int filter_placed(covahip_ctx *ctx, covahip_blobnet *m, const uint8_t *d_
     }
     BnInput in;
     if (n_frames > 0) {
-        int rc = prepare_frames(ctx, m, m->ws[ctx->cur_lane], d_src, n_frames, stack_index, batch, in);
+        int rc = prepare_frames(ctx, m, m->ws[ctx->cur_lane], d_src, n_frames, stack_index, batch, in, model_ids);
         if (rc) return rc;
         in.packed = packed;
     } else {
         in.stack = d_src;
     }
-    return filter_dev(ctx, in, batch, d_logits, d_mask, true, area_thresh, d_boxes, d_counts, max_boxes);
+    return filter_dev(ctx, in, batch, d_logits, d_mask, true, area_thresh, d_boxes, d_counts, max_boxes, n_frames > 0 ? nullptr : model_ids);
 }
 
 // Shared body of covahip_filter_forward / covahip_filter_forward_frames: `src` is the stacked tensor (n_frames == 0)
 // or the carrier frames.
 static int filter_any(covahip_ctx *ctx, const uint8_t *src, int n_frames, const int32_t *stack_index, int batch,
                       int area_thresh, covahip_box *boxes, int32_t *counts, int max_boxes, float *logits, uint8_t *mask,
-                      int mem_kind) {
+                      int mem_kind, const uint8_t *model_ids = nullptr) {
     if (!ctx || batch < 0 || max_boxes < 0 || n_frames < 0) return COVAHIP_ERR_INVALID_ARG;
     covahip_blobnet *m = ctx->blobnet;
     if (!m) return COVAHIP_ERR_NOT_LOADED;
     if (batch == 0) return COVAHIP_OK;
     if (!src || !counts || (!boxes && max_boxes > 0) || batch > m->max_batch) return COVAHIP_ERR_INVALID_ARG;
+    if (int rc = check_model_ids(m, model_ids, batch)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     const bool by_frames = n_frames > 0;
     const size_t hw = (size_t)m->H * m->W;
@@ -336,7 +435,7 @@ static int filter_any(covahip_ctx *ctx, const uint8_t *src, int n_frames, const 
     if (mem_kind == COVAHIP_MEM_DEVICE) {
         LaneScope lane(ctx);
         if (!lane.ok()) return COVAHIP_ERR_HIP;
-        return filter_placed(ctx, m, src, n_frames, stack_index, batch, area_thresh, boxes, counts, max_boxes, logits, mask);
+        return filter_placed(ctx, m, src, n_frames, stack_index, batch, area_thresh, boxes, counts, max_boxes, logits, mask, false, model_ids);
     }
     if (int rc = covahip_primary_op(ctx)) return rc;
     const uint8_t *d_src = src;
@@ -352,7 +451,8 @@ static int filter_any(covahip_ctx *ctx, const uint8_t *src, int n_frames, const 
     int32_t *d_counts = (int32_t *)(base + al(mask_bytes) + al(logit_bytes) + al(box_bytes));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->stage_in, src, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     d_src = (const uint8_t *)ctx->stage_in;
-    rc = filter_placed(ctx, m, d_src, n_frames, stack_index, batch, area_thresh, d_boxes, d_counts, max_boxes, d_logits, d_mask);
+    rc = filter_placed(ctx, m, d_src, n_frames, stack_index, batch, area_thresh, d_boxes, d_counts, max_boxes, d_logits, d_mask, false,
+                       model_ids);
     if (rc) return rc;
     if (logits) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(logits, d_logits, logit_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (mask) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -368,6 +468,11 @@ int covahip_filter_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batc
     return filter_any(ctx, rgba_stack, 0, nullptr, batch, area_thresh, boxes, counts, max_boxes, logits, mask, mem_kind);
 }
 
+int covahip_filter_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const uint8_t *model_ids, int batch, int area_thresh,
+                             covahip_box *boxes, int32_t *counts, int max_boxes, float *logits, uint8_t *mask, int mem_kind) {
+    return filter_any(ctx, rgba_stack, 0, nullptr, batch, area_thresh, boxes, counts, max_boxes, logits, mask, mem_kind, model_ids);
+}
+
 int covahip_filter_forward_frames(covahip_ctx *ctx, const uint8_t *frames, int n_frames, const int32_t *stack_index,
                                   int batch, int area_thresh, covahip_box *boxes, int32_t *counts, int max_boxes,
                                   float *logits, uint8_t *mask, int mem_kind) {
@@ -375,19 +480,35 @@ int covahip_filter_forward_frames(covahip_ctx *ctx, const uint8_t *frames, int n
     return filter_any(ctx, frames, n_frames, stack_index, batch, area_thresh, boxes, counts, max_boxes, logits, mask, mem_kind);
 }
 
+int covahip_filter_forward_frames_m(covahip_ctx *ctx, const uint8_t *frames, int n_frames, const int32_t *stack_index,
+                                    const uint8_t *model_ids, int batch, int area_thresh, covahip_box *boxes, int32_t *counts,
+                                    int max_boxes, float *logits, uint8_t *mask, int mem_kind) {
+    if (n_frames <= 0) return COVAHIP_ERR_INVALID_ARG;
+    return filter_any(ctx, frames, n_frames, stack_index, batch, area_thresh, boxes, counts, max_boxes, logits, mask, mem_kind,
+                      model_ids);
+}
+
 int covahip_filter_forward_frames_packed(covahip_ctx *ctx, const uint16_t *d_records, int n_frames, const int32_t *stack_index,
                                          int batch, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes,
                                          float *d_logits, uint8_t *d_mask) {
+    return covahip_filter_forward_frames_packed_m(ctx, d_records, n_frames, stack_index, nullptr, batch, area_thresh, d_boxes,
+                                                  d_counts, max_boxes, d_logits, d_mask);
+}
+
+int covahip_filter_forward_frames_packed_m(covahip_ctx *ctx, const uint16_t *d_records, int n_frames, const int32_t *stack_index,
+                                           const uint8_t *model_ids, int batch, int area_thresh, covahip_box *d_boxes,
+                                           int32_t *d_counts, int max_boxes, float *d_logits, uint8_t *d_mask) {
     if (!ctx || batch < 0 || max_boxes < 0 || n_frames <= 0) return COVAHIP_ERR_INVALID_ARG;
     covahip_blobnet *m = ctx->blobnet;
     if (!m) return COVAHIP_ERR_NOT_LOADED;
     if (batch == 0) return COVAHIP_OK;
     if (!d_records || !d_counts || (!d_boxes && max_boxes > 0) || batch > m->max_batch) return COVAHIP_ERR_INVALID_ARG;
+    if (int rc = check_model_ids(m, model_ids, batch)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     LaneScope lane(ctx);
     if (!lane.ok()) return COVAHIP_ERR_HIP;
     return filter_placed(ctx, m, reinterpret_cast<const uint8_t *>(d_records), n_frames, stack_index, batch, area_thresh, d_boxes, d_counts,
-                         max_boxes, d_logits, d_mask, true);
+                         max_boxes, d_logits, d_mask, true, model_ids);
 }
 
 // Developer read-back (include/covahip_dev.h): one activation buffer of lane 0's workspace, for stage-by-stage tests.
@@ -488,14 +609,20 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
 
 int covahip_blobnet_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, float *logits, uint8_t *mask,
                             int mem_kind) {
+    return covahip_blobnet_forward_m(ctx, rgba_stack, nullptr, batch, logits, mask, mem_kind);
+}
+
+int covahip_blobnet_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const uint8_t *model_ids, int batch, float *logits,
+                              uint8_t *mask, int mem_kind) {
     if (!ctx || batch < 0) return COVAHIP_ERR_INVALID_ARG;
     covahip_blobnet *m = ctx->blobnet;
     if (!m) return COVAHIP_ERR_NOT_LOADED;
     if (batch == 0) return COVAHIP_OK;
     if (!rgba_stack || batch > m->max_batch) return COVAHIP_ERR_INVALID_ARG;
+    if (int rc = check_model_ids(m, model_ids, batch)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int prc = covahip_primary_op(ctx)) return prc;   // BlobNet alone runs on the primary stream (lane 0's workspace)
-    if (mem_kind == COVAHIP_MEM_DEVICE) return covahip_blobnet_forward_dev(ctx, rgba_stack, batch, logits, mask);
+    if (mem_kind == COVAHIP_MEM_DEVICE) return covahip_blobnet_forward_dev(ctx, rgba_stack, batch, logits, mask, model_ids);
     if (mem_kind != COVAHIP_MEM_HOST) return COVAHIP_ERR_INVALID_ARG;
     const size_t hw = (size_t)m->H * m->W;
     const size_t in_bytes = (size_t)batch * BN_T * hw * 4;
@@ -510,7 +637,7 @@ int covahip_blobnet_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int bat
     float *d_logits = (float *)((uint8_t *)ctx->stage_out + al(mask_bytes));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->stage_in, rgba_stack, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = covahip_blobnet_forward_dev(ctx, (const uint8_t *)ctx->stage_in, batch, logits ? d_logits : nullptr,
-                                     mask ? d_mask : nullptr);
+                                     mask ? d_mask : nullptr, model_ids);
     if (rc) return rc;
     if (logits) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(logits, d_logits, logit_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (mask) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(mask, d_mask, mask_bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -83,6 +83,20 @@ inline _Float16 f2h(float v) { return (_Float16)v; }
 __device__ __forceinline__ uint32_t fdiv(uint32_t n, uint32_t mul) { return mul ? __umulhi(n, mul) : n; }
 inline uint32_t magic(uint32_t d) { return d <= 1 ? 0u : (uint32_t)(((1ull << 32) / d) + 1); }
 
+// Model sets ("Model sets"): the K models' prepared weights lie back to back, `stride` bytes apart (Prepared::total).
+// A kernel instantiated with MS = true reads the model id of its item (a stack, or a carrier frame for enc0p_mfma) from the u8 table
+// `mid` and offsets every weight pointer by id * stride.  The item is workgroup-uniform, so the offset is made a scalar.  MS = false
+// is the single-model kernel: no table, offset 0.
+template <bool MS>
+__device__ __forceinline__ uint32_t model_off(const uint8_t *mid, uint32_t stride, int idx) {
+    if constexpr (!MS) return 0u;
+    else return __builtin_amdgcn_readfirstlane((uint32_t)mid[idx] * stride);
+}
+template <typename T>
+__device__ __forceinline__ const T *at_model(const T *ptr, uint32_t off) {
+    return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(ptr) + off);
+}
+
 // relu -> BN affine -> 2x2 max-pool of the four conv outputs of one window.  BN runs between ReLU and the pool
 // (encoder.py:61-66) and gamma may be negative.  The BN scale s of a channel is folded into its weights and bias on the host
 // WHATEVER ITS SIGN (a' = s * conv, b' = s * bias), which turns the per-pixel expression relu(conv + bias) * s + shift into
@@ -273,6 +287,8 @@ struct EncArgs {
     const int32_t *pidx;
     __half *skip;
     const float *tm_pre;
+    const uint8_t *model_ids;   // MS: model id per stack [B]
+    uint32_t mstride;     // MS: bytes between two models' prepared weights
 };
 
 struct DecArgs {
@@ -291,6 +307,12 @@ struct DecArgs {
     int scr_off;         // blocks 0..2: byte offset of the per-wave store transpose scratch (2 KB per wave)
     int mask_off;        // last block: byte offset of the band's mask rows in LDS
     const float *part;   // last block without a skip input (C2 == 0): the skip half's share of the logits, fp32 [B][Hi + 1][Wi + 1][4 parities] (Enc1Args::part)
+};
+// Model sets (model_off): the decoder kernels' own argument behind DecArgs / at the end of Dec3ccArgs, so that the single-model
+// kernels keep their argument layout
+struct DecMs {
+    const uint8_t *model_ids;   // model id per stack [B]
+    uint32_t mstride;           // bytes between two models' prepared weights
 };
 
 #ifdef PHASE_TIMING
@@ -366,17 +388,20 @@ struct Enc0pArgs {
     int nbands, TC;
     uint32_t mWp, mNb, mW4;
     int scr_off;        // per-wave output scratch (1 KB per wave) behind the tile
+    const uint8_t *model_ids; // MS: model id per carrier frame [F]
+    uint32_t mstride;   // MS: bytes between two models' prepared weights
 };
-template <bool ALLPOS, bool PACKED>
+template <bool ALLPOS, bool PACKED, bool MS = false>
 __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     WGSPAN_BEGIN();
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int TC = p.TC;
-    const half8 be0 = p.wfrag[lane], be1 = p.wfrag[64 + lane];
-    const half8 bo0 = p.wfrag[128 + lane], bo1 = p.wfrag[192 + lane];
+    half8 be0 = p.wfrag[lane], be1 = p.wfrag[64 + lane];
+    half8 bo0 = p.wfrag[128 + lane], bo1 = p.wfrag[192 + lane];
     const int co = lane & 15;
-    const float e0 = p.epi[co], e1 = p.epi[16 + co], e2 = p.epi[32 + co];
+    float e0 = p.epi[co], e1 = p.epi[16 + co], e2 = p.epi[32 + co];
+    [[maybe_unused]] uint32_t moff_cur = 0;   // MS: the model whose weights are in registers (model 0 above)
     // the lane's part of its fragment addresses: window m >> 1 of a tile, conv row m & 1; g: K half (kernel row) and pixel pair
     const int m = lane & 15, g = lane >> 4;
     const uint32_t lc0 = (uint32_t)((((m & 1) + (g >> 1)) * TC + 2 * (m >> 1) + 2 * (g & 1)) * 8);
@@ -384,6 +409,16 @@ __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
     const int n_items = p.F * p.nbands;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int f = fdiv(item, p.mNb), band = item - f * p.nbands;
+        if constexpr (MS) {   // uniform branch: the frame's model differs from the one in registers
+            const uint32_t mo = model_off<MS>(p.model_ids, p.mstride, f);
+            if (mo != moff_cur) {
+                moff_cur = mo;
+                const half8 *wf = at_model(p.wfrag, mo);
+                const float *ep = at_model(p.epi, mo);
+                be0 = wf[lane]; be1 = wf[64 + lane]; bo0 = wf[128 + lane]; bo1 = wf[192 + lane];
+                e0 = ep[co]; e1 = ep[16 + co]; e2 = ep[32 + co];
+            }
+        }
         const int y0 = 2 * ((band * p.Hp) / p.nbands);
         const int rows = 2 * (((band + 1) * p.Hp) / p.nbands) - y0;
         const int n2 = rows + 2;
@@ -512,7 +547,7 @@ __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
 //     [tile base: wave-uniform] + [lane constant of the tap, set once per kernel] ^ [channel chunk << 5] + [T slice: immediate],
 // i.e. one add per tap and one xor per further channel chunk per tile, where the general form below evaluates the swizzle and
 // the pixel address for every tap of every tile (216 of the 270 vector instructions of a level-2 tile's matrix part).
-template <int CIN, int COUT, int TPAR, int OCC, int NWV, bool WIDE, bool ALLPOS, bool PRE = false, int TSZ = 0>
+template <int CIN, int COUT, int TPAR, int OCC, int NWV, bool WIDE, bool ALLPOS, bool PRE = false, int TSZ = 0, bool MS = false>
 __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
     constexpr int WGS = NWV * 64;
     constexpr int NT = COUT / 32, MG = NWV / NT, KC = CIN / 16, KSTEPS = 9 * KC;
@@ -616,7 +651,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
     if (more && dbl) {
         stage(it.b, it.band, smem, lane);
         wait_vmem();
-        if constexpr (PRE) mlp_own(smem, it.band, load_tmix(p.tm_pre, lane));
+        if constexpr (PRE) mlp_own(smem, it.band, load_tmix(at_model(p.tm_pre, model_off<MS>(p.model_ids, p.mstride, it.b)), lane));
     }
     // one buffer: the first band is requested BEFORE the weight fragments (36 - 144 registers per lane, every workgroup of
     // the launch pulling the same 37 - 295 KB through L2 at once), so that both are in flight together
@@ -626,8 +661,8 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ks++) bf[ks] = p.wfrag[(ntile * KSTEPS + ks) * 64 + lane];
     const int co = ntile * 32 + (lane & 31);
-    const float e0 = p.epi[co], e1 = p.epi[COUT + co], e2 = p.epi[2 * COUT + co];   // see pool4
-    const TmixW tm = load_tmix(p.epi + 3 * COUT, lane);
+    float e0 = p.epi[co], e1 = p.epi[COUT + co], e2 = p.epi[2 * COUT + co];   // see pool4
+    TmixW tm = load_tmix(p.epi + 3 * COUT, lane);
     // TSZ > 0: the lane's part of a fragment address per tap: pixel (lane's window of the tile, position, tap) of tile (0, 0),
     // xor the 16-byte chunk (kh ^ swizzle) -- the K half kh and the swizzle meet in the chunk bits, which the pixel address
     // leaves clear
@@ -647,6 +682,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
 #endif
     while (more) {
         const int b = it.b, band = it.band;
+        [[maybe_unused]] const uint32_t moff = model_off<MS>(p.model_ids, p.mstride, b);
         // balanced bands of whole pool-window rows
         const int y0 = 2 * ((band * p.Hp) / p.nbands);
         const int rows = 2 * (((band + 1) * p.Hp) / p.nbands) - y0;
@@ -660,7 +696,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
         // the weights of the level below's temporal MLP: fetched here so that the loads are in flight together with the
         // band's (they are waited for with it), not on their own between two barriers
         TmixW tmp;
-        if constexpr (PRE) tmp = load_tmix(p.tm_pre, ll);
+        if constexpr (PRE) tmp = load_tmix(at_model(p.tm_pre, moff), ll);
         if (!dbl) {
             if (!first_staged) {
                 lds_barrier();
@@ -691,7 +727,8 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
         auto landed = [&]() {
             if (in_flight) {
                 wait_vmem();
-                if constexpr (PRE) mlp_own(smem + cur * p.buf_stride, it.band, tmp);   // `cur` already names the next item's buffer
+                if constexpr (PRE && MS) mlp_own(smem + cur * p.buf_stride, it.band, load_tmix(at_model(p.tm_pre, model_off<MS>(p.model_ids, p.mstride, it.b)), ll));
+                else if constexpr (PRE) mlp_own(smem + cur * p.buf_stride, it.band, tmp);   // `cur` already names the next item's buffer
                 in_flight = false;
             }
         };
@@ -710,6 +747,14 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
             }
         }
         PHASE_MARK(5);   // skip slice out
+        if constexpr (MS) {   // this stack's weights, loaded where the staging's registers are free again (one copy, no spill)
+            const half8 *wf = at_model(p.wfrag, moff);
+            const float *ep = at_model(p.epi, moff);
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ks++) bf[ks] = wf[(ntile * KSTEPS + ks) * 64 + lane];
+            e0 = ep[co]; e1 = ep[COUT + co]; e2 = ep[2 * COUT + co];
+            tm = load_tmix(ep + 3 * COUT, lane);
+        }
         // ---- compute
         const int nwin = (rows / 2) * p.Wp;
         const int ntc = (p.Wp + 7) >> 3;                    // TSZ > 0: tile columns of a window row
@@ -973,6 +1018,8 @@ struct Enc1Args {
     const half8 *wtail;  // [2 K steps][64 lanes]: A fragments of the folded skip half (prep_tail)
     uint32_t mXe;        // magic of 2 * Wp (columns of the grid rows the edge pass walks)
     uint16_t ktab[BN_KTAB_STACKS * BN_T];
+    const uint8_t *model_ids;   // MS: model id per stack [B]
+    uint32_t mstride;     // MS: bytes between two models' prepared weights
 };
 // Per-lane constants live in a small LDS table behind the scratch instead of registers (hipcc keeps every loop-invariant
 // load in a register for the whole kernel):
@@ -984,7 +1031,7 @@ constexpr int E1_CONST = 2560;
 #ifndef E1_ABL
 #define E1_ABL 0   // developer builds (tools/ablate_enc1.sh): 1 no temporal MLP, 3 no tile epilogue, 4 no tiles, 5 no staging
 #endif
-template <bool ALLPOS>
+template <bool ALLPOS, bool MS = false>
 __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
     constexpr int NWV = 8, WGS = NWV * 64, MG = NWV;
     constexpr int AD = 4;
@@ -1007,6 +1054,22 @@ __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
             *reinterpret_cast<half4 *>(cst + 384 + (tid & 4) * 16 + i * 16 + 8) = a2;
         }
     }
+    // MS: the same table of the model `mo` bytes past model 0, rewritten between two barriers when the stack's model changes
+    [[maybe_unused]] auto load_cst = [&](uint32_t mo) {
+        const float *epi = at_model(p.epi, mo);
+        if (tid < 96) reinterpret_cast<float *>(cst)[tid] = epi[tid];
+        if (p.part && tid >= 256 && tid < 384) reinterpret_cast<half8 *>(cst + 512)[tid - 256] = at_model(p.wtail, mo)[tid - 256];
+        if (tid >= 128 && tid < 136) {
+            const int i = tid & 3;
+            const float *tmw = (tid & 4) ? at_model(p.tm_pre, mo) : epi + 96;
+            half4 a1, a2;
+#pragma unroll
+            for (int t = 0; t < BN_T; t++) { a1[t] = (_Float16)tmw[t * BN_T + i]; a2[t] = (_Float16)tmw[16 + t * BN_T + i]; }
+            *reinterpret_cast<half4 *>(cst + 384 + (tid & 4) * 16 + i * 16) = a1;
+            *reinterpret_cast<half4 *>(cst + 384 + (tid & 4) * 16 + i * 16 + 8) = a2;
+        }
+    };
+    [[maybe_unused]] uint32_t moff_cur = 0;
     const int RCr = 2 * (p.W + 2);
     const uint32_t plane = (uint32_t)p.H * p.W * 32;
 #ifdef PHASE_TIMING
@@ -1017,6 +1080,15 @@ __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
     ItemIter it;
     for (bool more = it.start(p.plan, p.B, p.nbands); more; more = it.next(p.plan, p.B, p.nbands)) {
         const int b = it.b, band = it.band;
+        [[maybe_unused]] const uint32_t moff = model_off<MS>(p.model_ids, p.mstride, b);
+        if constexpr (MS) {   // uniform branch (the item is the workgroup's): every wave has left the previous item before the table changes
+            if (moff != moff_cur) {
+                moff_cur = moff;
+                lds_barrier();
+                load_cst(moff);
+                lds_barrier();
+            }
+        }
         const int y0 = 2 * ((band * p.Hp) / p.nbands);
         const int rows = 2 * (((band + 1) * p.Hp) / p.nbands) - y0;
         const int n2 = rows + 2;
@@ -1122,7 +1194,7 @@ __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
         // weight fragments of both N tiles, (re)loaded per item (the temporal MLP needs the registers)
         half8 bf[2][5];
         {
-            const half8 *wp = p.wfrag + ll;
+            const half8 *wp = (MS ? at_model(p.wfrag, moff) : p.wfrag) + ll;
             asm volatile("" : "+v"(wp));
 #pragma unroll
             for (int nt = 0; nt < 2; nt++)
@@ -1335,8 +1407,10 @@ struct Enc23Args {
     int H4, W4, oy4, ox4;
     Swz swz2, swz3;      // periodic swizzles of the ring and of level 3's band (choose_swz_periodic)
     int ring_off, xchg_off, scr_off;   // LDS: [band3: BN_T * E3_TSZ][ring: BN_T * E23_TSZ2 (level 3's store scratch reuses it)][xchg: 4 KB]
+    const uint8_t *model_ids;   // MS: model id per stack [B]
+    uint32_t mstride;           // MS: bytes between two models' prepared weights
 };
-template <bool AP2, bool AP3>
+template <bool AP2, bool AP3, bool MS = false>
 __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[];
     WGSPAN_BEGIN();
@@ -1349,6 +1423,7 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
     const int tc2 = wave & 1, nt2 = (wave >> 1) & 1, th = wave >> 2;   // level 2: tile column, N tile, T half
     const int nt3 = wave & 3, mg3 = wave >> 2;                         // level 3: N tile, M group
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
+        [[maybe_unused]] const uint32_t moff = model_off<MS>(p.model_ids, p.mstride, b);
         int ll = lane;
         asm volatile("" : "+v"(ll));
         lds_barrier();   // the previous frame's level 3 has left the band and its scratch (= the ring)
@@ -1407,14 +1482,15 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
             }
             half8 bf[18];
             {
-                const half8 *wp = p.wf2 + nt2 * 18 * 64 + ll;
+                const half8 *wp = at_model(p.wf2, moff) + nt2 * 18 * 64 + ll;
                 asm volatile("" : "+v"(wp));
 #pragma unroll
                 for (int ks = 0; ks < 18; ks++) bf[ks] = wp[ks * 64];
             }
             const int co = nt2 * 32 + (ll & 31);
-            const float e0 = p.epi2[co], e1 = p.epi2[64 + co], e2 = p.epi2[128 + co];
-            const TmixW tm = load_tmix(p.epi2 + 192, ll);
+            const float *const epi2 = at_model(p.epi2, moff);
+            const float e0 = epi2[co], e1 = epi2[64 + co], e2 = epi2[128 + co];
+            const TmixW tm = load_tmix(epi2 + 192, ll);
             int s0 = 0;   // ring slot of the step's first row (input row 2s - 1)
             for (int s = 0; s < p.Hp2; s++) {
                 lds_barrier();   // the step's rows are in the ring; every wave has left step s - 1 (its ring rows, the exchange area)
@@ -1507,7 +1583,7 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
             const int yl = (m0 >> 1) & 1, xl = 2 * (m0 >> 2) + (m0 & 1);
             half8 bf[36];   // requested in front of the barrier that completes the band
             {
-                const half8 *wp = p.wf3 + nt3 * 36 * 64 + ll;
+                const half8 *wp = at_model(p.wf3, moff) + nt3 * 36 * 64 + ll;
                 asm volatile("" : "+v"(wp));
 #pragma unroll
                 for (int ks = 0; ks < 36; ks++) bf[ks] = wp[ks * 64];
@@ -1526,8 +1602,9 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
                 }
             }
             const int co = nt3 * 32 + (ll & 31);
-            const float e0 = p.epi3[co], e1 = p.epi3[128 + co], e2 = p.epi3[256 + co];
-            const TmixW tm = load_tmix(p.epi3 + 384, ll);
+            const float *const epi3 = at_model(p.epi3, moff);
+            const float e0 = epi3[co], e1 = epi3[128 + co], e2 = epi3[256 + co];
+            const TmixW tm = load_tmix(epi3 + 384, ll);
             uint32_t kq[9];
 #pragma unroll
             for (int tap = 0; tap < 9; tap++) {
@@ -1612,8 +1689,8 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
 // of 4 consecutive output channels -> one (u,v) decomposition per lane per tile and 8-byte packed
 // stores.  The last block (FINAL) has the final 1x1 conv folded in (no non-linearity between
 // them): 4 rows = the 4 parities, output = logit (+ threshold).
-template <int C1, int C2, int COUT, bool FINAL>
-__global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 4) * 64, 2) void dec_mfma(DecArgs p) {
+template <int C1, int C2, int COUT, bool FINAL, bool MS = false>
+__global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 4) * 64, 2) void dec_mfma(DecArgs p, DecMs pm) {
     constexpr int C = C1 + C2, MT = FINAL ? 1 : 4 * COUT / 32, NW = MT > 4 ? MT : 4, PG = NW / MT;
     constexpr int KC = C / 16, KSTEPS = 4 * KC, CPP = C / 8, PS = C * 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1636,11 +1713,28 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
             eb[r] = p.epi[COUT + n % COUT];
         }
     }
-    const float fbias = FINAL ? p.epi[0] : 0.f;
+    float fbias = FINAL ? p.epi[0] : 0.f;
 
     const int n_items = p.B * p.nbands;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int b = fdiv(item, p.mNb), band = item - b * p.nbands;
+        if constexpr (MS) {   // every item takes its stack's weights: one copy in registers, no second one kept for a compare
+            const uint32_t moff = model_off<MS>(pm.model_ids, pm.mstride, b);
+            const half8 *wfr = at_model(p.wfrag, moff);
+            const float *ep = at_model(p.epi, moff);
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = wfr[(mtile * KSTEPS + ks) * 64 + lane];
+            if constexpr (!FINAL) {
+#pragma unroll
+                for (int r = 0; r < 16; r++) {
+                    const int n = mtile * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+                    es[r] = ep[n % COUT];
+                    eb[r] = ep[COUT + n % COUT];
+                }
+            } else {
+                fbias = ep[0];
+            }
+        }
         const int u0 = band * GH / p.nbands, u1 = (band + 1) * GH / p.nbands;
         const int nu = u1 - u0;   // grid rows of this band; tile rows = nu + 1 (input rows u0-1 .. u1-1)
         lds_barrier();
@@ -1796,6 +1890,8 @@ struct Dec012Args {
     DecLvl lv[3];
     int B, scr_off;
     const void *zero;
+    const uint8_t *model_ids;   // MS: model id per stack [B]
+    uint32_t mstride;           // MS: bytes between two models' prepared weights
 };
 
 // The border of a block's tile (the zero padding of the transposed convolution's input) is written once per launch:
@@ -1971,6 +2067,7 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
     }
 }
 
+template <bool MS = false>
 __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1985,13 +2082,14 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
     dec012_zero_border<128>(t1, p.lv[1], tid);
     dec012_zero_border<64>(t2, p.lv[2], tid);
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
+        [[maybe_unused]] const uint32_t moff = model_off<MS>(p.model_ids, p.mstride, b);
         // the previous frame's last block has left its tiles.  The FIRST frame of a workgroup (at b <= CUs the only one) has nothing
         // to wait for: its weights and tile requests go out at once (round 6)
         if (b != (int)blockIdx.x) lds_barrier();
         PHASE_MARK(0);
         {
             Dec012W<128, 64> w0;
-            dec012_load(w0, p.wf[0], p.epi[0], wave, lane);   // in flight together with the tiles
+            dec012_load(w0, at_model(p.wf[0], moff), at_model(p.epi[0], moff), wave, lane);   // in flight together with the tiles
             // (the rows of the three tiles start at different waves so that the requests spread evenly)
             dec012_stage<0, 128>(t0, p.skip[0] + (size_t)b * p.Ts[0] * p.lv[0].Hi * p.lv[0].Wi * 128, p.lv[0], wave, lane, 0);
             dec012_stage<64, 64>(t1, p.skip[1] + (size_t)b * p.Ts[1] * p.lv[1].Hi * p.lv[1].Wi * 64, p.lv[1], wave, lane, p.lv[0].Hi & 7);
@@ -2006,7 +2104,7 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
         PHASE_MARK(3);       // block 0: tiles
         {
             Dec012W<128, 32> w1;
-            dec012_load(w1, p.wf[1], p.epi[1], wave, lane);
+            dec012_load(w1, at_model(p.wf[1], moff), at_model(p.epi[1], moff), wave, lane);
             lds_barrier();   // block 0's output is in block 1's tile
 #ifdef PHASE_TIMING
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2017,7 +2115,7 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
         PHASE_MARK(5);       // block 1: tiles
         {
             Dec012W<64, 16> w2;
-            dec012_load(w2, p.wf[2], p.epi[2], wave, lane);
+            dec012_load(w2, at_model(p.wf[2], moff), at_model(p.epi[2], moff), wave, lane);
             lds_barrier();
 #ifdef PHASE_TIMING
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2052,6 +2150,7 @@ struct Dec3ccArgs {
     int tile_bytes;            // one band buffer; two of them at LDS offsets 0 and tile_bytes
     int mfull_off, cc_off;     // LDS offsets of the frame's mask bytes and of bboxcc's region
     int part_off;              // PART: LDS offset of the frame's partial logits (fp32 [Hd][Wd], DecArgs::part)
+    DecMs ms;                  // MS: the stacks' models
 };
 
 // WV: the run-based bboxcc body (bboxcc_wave.h) instead of the block-based one (bboxcc_body.h); one body per instantiation, so
@@ -2059,7 +2158,7 @@ struct Dec3ccArgs {
 // PART (round 5): the block's input is its "up" half alone (16 channels, half the tile, half the products, the whole frame in
 // one buffer); the skip half's share of every logit comes as fp32 partial logits from the level-1 kernel (Enc1Args::part),
 // lands in LDS beside the tile and is added in the epilogue.
-template <bool WV, bool PART>
+template <bool WV, bool PART, bool MS = false>
 __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) {
     constexpr int C1 = 16, C2 = PART ? 0 : 16, C = C1 + C2, NW = ccbody::CC_THREADS / 64;
     constexpr int KC = C / 16, KSTEPS = 4 * KC, CPP = C / 8, PS = C * 2;
@@ -2069,7 +2168,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
     const int TC = p.Wi + 2;
     const int GW = p.Wi + 1, GH = p.Hi + 1;
     const int kh = lane >> 5;
-    const float fbias = p.epi[0];
+    float fbias = p.epi[0];
     uint8_t *const mfull = smem + q.mfull_off;
     WGSPAN_BEGIN();
 #ifdef PHASE_TIMING
@@ -2079,8 +2178,15 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
         // the weight fragments are (re)loaded per frame: their registers are free again while bboxcc runs
         half8 wf[KSTEPS];
+        if constexpr (MS) {
+            const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
+            fbias = at_model(p.epi, moff)[0];
 #pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = p.wfrag[ks * 64 + lane];
+            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = at_model(p.wfrag, moff)[ks * 64 + lane];
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = p.wfrag[ks * 64 + lane];
+        }
         auto stage = [&](int band, uint8_t *buf) {   // LDS-DMA of concat(up, skip[t=0]) rows u0-1 .. u1-1
             const int u0 = band * GH / p.nbands, u1 = (band + 1) * GH / p.nbands;
             const int RC = TC * CPP;
@@ -2206,6 +2312,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
 // Same products in the same order, same logit expression: logits, mask, boxes and their order are bit-identical to dec3cc_mfma<true,
 // true> (tests/test_gpu_blobnet.py).  Taken when the partial-logit form runs, the frame's tile fits one buffer, a grid row has at
 // most 64 positions and the run-based bboxcc body takes the shape.
+template <bool MS = false>
 __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArgs q) {
     constexpr int NW = ccbody::CC_THREADS / 64, PS = 32;   // 16 channels per pixel
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -2213,7 +2320,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int TC = p.Wi + 2, GW = p.Wi + 1, GH = p.Hi + 1;
     const int kh = lane >> 5, pos = lane & 31;
-    const float fbias = p.epi[0];
+    const float fbias0 = p.epi[0];
     uint32_t *const planes = reinterpret_cast<uint32_t *>(smem + q.mfull_off);   // [2 BH + 2][E lo, E hi, O lo, O hi], pixel row y at y + 1
     const f32x4 *const part = reinterpret_cast<const f32x4 *>(smem + q.part_off);
     WGSPAN_BEGIN();
@@ -2232,9 +2339,11 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
         }
     const int row_b = TC * PS;
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
+        const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
+        const float fbias = MS ? at_model(p.epi, moff)[0] : fbias0;
         half8 wf[4];   // (re)loaded per frame: their registers are free again while bboxcc runs
 #pragma unroll
-        for (int ks = 0; ks < 4; ks++) wf[ks] = p.wfrag[ks * 64 + lane];
+        for (int ks = 0; ks < 4; ks++) wf[ks] = (MS ? at_model(p.wfrag, moff) : p.wfrag)[ks * 64 + lane];
         if (b != (int)blockIdx.x) lds_barrier();   // the previous frame's bboxcc is done with the tile buffer it reuses
         PHASE_MARK(0);
         {   // the frame's partial logits: one 16-byte piece per grid position
@@ -2666,34 +2775,37 @@ int set_lds(covahip_ctx *ctx, K kernel, size_t lds) {
         if (!dry) hipLaunchKernelGGL(__VA_ARGS__);   \
     } while (0)
 
-int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *w) {
+int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *const *ws, int n_models) {
     // host view of the parameter blob (same order as bind_params in blobnet.hip)
     struct HE { const float *k, *b, *gamma, *beta, *mean, *var, *w1, *w2; } he[BN_LEVELS];
     struct HD { const float *k, *b, *gamma, *beta, *mean, *var; } hd[BN_LEVELS];
-    const float *p = w;
-    for (int i = 0; i < BN_LEVELS; i++) {
-        const int ci = m->enc_c[i], co = m->enc_c[i + 1];
-        he[i].k = p; p += 9 * ci * co;
-        he[i].b = p; p += co;
-        he[i].gamma = p; p += co;
-        he[i].beta = p; p += co;
-        he[i].mean = p; p += co;
-        he[i].var = p; p += co;
-        he[i].w1 = p; p += 16;
-        he[i].w2 = p; p += 16;
-    }
-    for (int j = 0; j < BN_LEVELS; j++) {
-        const int ci = m->dec_ci[j], co = m->dec_co[j];
-        hd[j].k = p; p += 16 * ci * co;
-        hd[j].b = p; p += co;
-        if (j < BN_LEVELS - 1) {
-            hd[j].gamma = p; p += co;
-            hd[j].beta = p; p += co;
-            hd[j].mean = p; p += co;
-            hd[j].var = p; p += co;
+    const float *fk = nullptr, *fb = nullptr;
+    auto view = [&](const float *w) {
+        const float *p = w;
+        for (int i = 0; i < BN_LEVELS; i++) {
+            const int ci = m->enc_c[i], co = m->enc_c[i + 1];
+            he[i].k = p; p += 9 * ci * co;
+            he[i].b = p; p += co;
+            he[i].gamma = p; p += co;
+            he[i].beta = p; p += co;
+            he[i].mean = p; p += co;
+            he[i].var = p; p += co;
+            he[i].w1 = p; p += 16;
+            he[i].w2 = p; p += 16;
         }
-    }
-    const float *fk = p, *fb = p + 16;
+        for (int j = 0; j < BN_LEVELS; j++) {
+            const int ci = m->dec_ci[j], co = m->dec_co[j];
+            hd[j].k = p; p += 16 * ci * co;
+            hd[j].b = p; p += co;
+            if (j < BN_LEVELS - 1) {
+                hd[j].gamma = p; p += co;
+                hd[j].beta = p; p += co;
+                hd[j].mean = p; p += co;
+                hd[j].var = p; p += co;
+            }
+        }
+        fk = p; fb = p + 16;
+    };
 
     Prepared *pr = new Prepared();
     size_t off = 0;
@@ -2717,33 +2829,41 @@ int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *w) {
     pr->zero = off; off = align256(off + 256);
     pr->total = off;
 
-    std::vector<uint8_t> host(off, 0);
-    for (int i = 0; i < BN_LEVELS; i++) {
-        pr->allpos[i] = true;
-        for (int c = 0; c < m->enc_c[i + 1]; c++) pr->allpos[i] = pr->allpos[i] && he[i].gamma[c] >= 0.f;
+    // the K models lie `off` bytes apart; allpos (which kernel template and which epilogue form) is shared by the set
+    std::vector<uint8_t> host_all(off * (size_t)n_models, 0);
+    for (int i = 0; i < BN_LEVELS; i++) pr->allpos[i] = true;
+    for (int k = 0; k < n_models; k++) {
+        view(ws[k]);
+        for (int i = 0; i < BN_LEVELS; i++)
+            for (int c = 0; c < m->enc_c[i + 1]; c++) pr->allpos[i] = pr->allpos[i] && he[i].gamma[c] >= 0.f;
     }
-    prep_enc0(pr->allpos[0], he[0].k, he[0].b, he[0].gamma, he[0].beta, he[0].mean, he[0].var, he[0].w1, he[0].w2,
-              (_Float16 *)(host.data() + pr->enc[0].wfrag), (float *)(host.data() + pr->enc[0].epi));
-    for (int i = 1; i < BN_LEVELS; i++)
-        prep_enc(pr->allpos[i], m->enc_c[i], m->enc_c[i + 1], he[i].k, he[i].b, he[i].gamma, he[i].beta, he[i].mean, he[i].var,
-                 he[i].w1, he[i].w2, (_Float16 *)(host.data() + pr->enc[i].wfrag),
-                 (float *)(host.data() + pr->enc[i].epi));
-    if (m->enc_c[1] == 16 && m->enc_c[2] == 32)
-        prep_enc1w(pr->allpos[1], he[1].k, he[1].b, he[1].gamma, he[1].beta, he[1].mean, he[1].var,
-                   (_Float16 *)(host.data() + pr->enc1w));
-    for (int j = 0; j < BN_LEVELS - 1; j++)
-        prep_dec(m->dec_ci[j], m->dec_co[j], hd[j].k, hd[j].b, hd[j].gamma, hd[j].beta, hd[j].mean, hd[j].var,
-                 (_Float16 *)(host.data() + pr->dec[j].wfrag), (float *)(host.data() + pr->dec[j].epi));
-    prep_final(m->dec_ci[3], m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host.data() + pr->final_w),
-               (float *)(host.data() + pr->final_epi));
-    if (m->dec_ci[3] == 32) {   // the last block's input = concat(up 16, skip 16): decoder.py:122-134
-        prep_final(32, m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host.data() + pr->final_w_up), nullptr, 0, 16);
-        prep_tail(32, m->dec_co[3], hd[3].k, fk, 16, (_Float16 *)(host.data() + pr->tail_w));
+    for (int k = 0; k < n_models; k++) {
+        view(ws[k]);
+        uint8_t *const host = host_all.data() + (size_t)k * off;
+        prep_enc0(pr->allpos[0], he[0].k, he[0].b, he[0].gamma, he[0].beta, he[0].mean, he[0].var, he[0].w1, he[0].w2,
+                  (_Float16 *)(host + pr->enc[0].wfrag), (float *)(host + pr->enc[0].epi));
+        for (int i = 1; i < BN_LEVELS; i++)
+            prep_enc(pr->allpos[i], m->enc_c[i], m->enc_c[i + 1], he[i].k, he[i].b, he[i].gamma, he[i].beta, he[i].mean, he[i].var,
+                     he[i].w1, he[i].w2, (_Float16 *)(host + pr->enc[i].wfrag),
+                     (float *)(host + pr->enc[i].epi));
+        if (m->enc_c[1] == 16 && m->enc_c[2] == 32)
+            prep_enc1w(pr->allpos[1], he[1].k, he[1].b, he[1].gamma, he[1].beta, he[1].mean, he[1].var,
+                       (_Float16 *)(host + pr->enc1w));
+        for (int j = 0; j < BN_LEVELS - 1; j++)
+            prep_dec(m->dec_ci[j], m->dec_co[j], hd[j].k, hd[j].b, hd[j].gamma, hd[j].beta, hd[j].mean, hd[j].var,
+                     (_Float16 *)(host + pr->dec[j].wfrag), (float *)(host + pr->dec[j].epi));
+        prep_final(m->dec_ci[3], m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w),
+                   (float *)(host + pr->final_epi));
+        if (m->dec_ci[3] == 32) {   // the last block's input = concat(up 16, skip 16): decoder.py:122-134
+            prep_final(32, m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w_up), nullptr, 0, 16);
+            prep_tail(32, m->dec_co[3], hd[3].k, fk, 16, (_Float16 *)(host + pr->tail_w));
+        }
     }
-    COVAHIP_CHECK_HIP(ctx, hipMalloc(&m->d_prepared, off));
-    COVAHIP_CHECK_HIP(ctx, hipMemcpy(m->d_prepared, host.data(), off, hipMemcpyHostToDevice));
-    m->prepared_bytes = off;
-    m->prep = pr;
+    m->prep = pr;   // (released with the model whatever happens below)
+    COVAHIP_CHECK_HIP(ctx, hipMalloc(&m->d_prepared, host_all.size()));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpy(m->d_prepared, host_all.data(), host_all.size(), hipMemcpyHostToDevice));
+    m->prepared_bytes = host_all.size();
+    m->n_models = n_models;
     return COVAHIP_OK;
 }
 
@@ -2761,8 +2881,12 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
     const bool by_frames = inp.frames != nullptr || (dry && inp.n_frames > 0);
     __half *const *act = ws.act;
     __half *const *dact = ws.dact;
-    const uint8_t *prep = (const uint8_t *)m->d_prepared;
     const Prepared *pr = m->prep;
+    // model sets: a batch of one model runs the single-model kernels on that model's weights; a mixed batch runs the MS = true
+    // instantiations, which take every item's weights from its model (inp.model_ids per stack, inp.frame_models per carrier frame)
+    const bool ms = inp.model_ids != nullptr || (dry && inp.mixed);
+    const uint8_t *prep = (const uint8_t *)m->d_prepared + (ms ? 0 : (size_t)inp.model * pr->total);
+    const uint32_t mstride = (uint32_t)pr->total;
     const int num_cu = ctx->props.multiProcessorCount;
 
     // ---------------- encoder
@@ -2796,13 +2920,19 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         a.F = n_frames; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[1].H; a.Wo = m->lv[1].W;
         a.oy = H & 1; a.ox = W & 1; a.nbands = nbands; a.TC = TC;
         a.mWp = magic(Wp); a.mNb = magic(nbands); a.mW4 = magic(W / 4); a.scr_off = (int)tile_bytes;
+        a.model_ids = inp.frame_models; a.mstride = mstride;
         const size_t lds = tile_bytes + (size_t)(WG0 / 64) * 1024;
         // three persistent workgroups per CU: measured 13.9 - 14.6 us at 280 frames against 15.0 with four (the kernel sits
         // on its latency floor: band count 3 .. 7 and 2 .. 4 workgroups per CU all land within 1.5 us)
         const int grid = std::min(n_frames * nbands, 3 * num_cu);
         {
             ProfScope ps(ctx, "enc0p_mfma");
-            if (inp.packed) {
+            if (ms) {
+                if (inp.packed && pr->allpos[0]) LAUNCH((enc0p_mfma<true, true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
+                else if (inp.packed) LAUNCH((enc0p_mfma<false, true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
+                else if (pr->allpos[0]) LAUNCH((enc0p_mfma<true, false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
+                else LAUNCH((enc0p_mfma<false, false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
+            } else if (inp.packed) {
                 if (pr->allpos[0]) LAUNCH((enc0p_mfma<true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
                 else LAUNCH((enc0p_mfma<false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
             } else {
@@ -2826,7 +2956,9 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
             // that fill their tile columns (45 x 80: 10 of 16 and 5 of 8 windows, 3 % slower than the two launches at b = 512).
             // fuse_enc23 == 2 (developer switch "enc23_force", the tests) takes it whenever it fits
             const bool pays = 4 * batch >= 3 * num_cu && 20 * Wp >= 17 * 8 * ((Wp + 7) / 8) && 20 * Wp3 >= 17 * 8 * ((Wp3 + 7) / 8);
-            if ((pays || m->fuse_enc23 == 2) && (W + 2) * 64 <= E23_RP2 && Wp <= 16 && Hp >= 1 && Hp3 >= 1 && Wp3 >= 1 &&
+            // a mixed batch (model sets) takes it whenever it fits: the two-launch form's level-3 kernel cannot hold a per-stack model's
+            // fragments without spilling ("Model sets")
+            if ((pays || m->fuse_enc23 == 2 || ms) && (W + 2) * 64 <= E23_RP2 && Wp <= 16 && Hp >= 1 && Hp3 >= 1 && Wp3 >= 1 &&
                 (size_t)std::max(2 * Hp3 + 2, H3 + 1) * (W3 + 2) * 128 <= (size_t)E3_TSZ && lds <= 160 * 1024 - 256) {
                 Enc23Args a;
                 a.in = act[2]; a.mid = act[3]; a.out = act[4];
@@ -2838,7 +2970,21 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
                 a.H4 = m->lv[4].H; a.W4 = m->lv[4].W; a.oy4 = H3 & 1; a.ox4 = W3 & 1;
                 a.swz2 = choose_swz_periodic(32, 30, Wp); a.swz3 = choose_swz_periodic(64, W3, Wp3);
                 a.ring_off = BN_T * E3_TSZ; a.xchg_off = a.ring_off + BN_T * E23_TSZ2; a.scr_off = a.ring_off;
+                a.model_ids = inp.model_ids; a.mstride = mstride;
                 const bool ap2 = pr->allpos[2], ap3 = pr->allpos[3];
+                if (ms) {
+                    int rc = ap2 ? (ap3 ? set_lds(ctx, enc23_mfma<true, true, true>, lds) : set_lds(ctx, enc23_mfma<true, false, true>, lds))
+                                 : (ap3 ? set_lds(ctx, enc23_mfma<false, true, true>, lds) : set_lds(ctx, enc23_mfma<false, false, true>, lds));
+                    if (rc) return rc;
+                    const int grid = std::min(batch, num_cu);
+                    ProfScope ps(ctx, "enc23_mfma");
+                    if (ap2 && ap3) LAUNCH((enc23_mfma<true, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    else if (ap2) LAUNCH((enc23_mfma<true, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    else if (ap3) LAUNCH((enc23_mfma<false, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    else LAUNCH((enc23_mfma<false, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+                    break;
+                }
                 int rc = ap2 ? (ap3 ? set_lds(ctx, enc23_mfma<true, true>, lds) : set_lds(ctx, enc23_mfma<true, false>, lds))
                              : (ap3 ? set_lds(ctx, enc23_mfma<false, true>, lds) : set_lds(ctx, enc23_mfma<false, false>, lds));
                 if (rc) return rc;
@@ -2889,6 +3035,16 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
                     return COVAHIP_ERR_INVALID_ARG;
                 }
                 const size_t lds = (size_t)BN_T * E1_TSZ + 8 * 1024 + E1_CONST;   // (twice this fits a CU's 160 KB)
+                a.model_ids = inp.model_ids; a.mstride = mstride;
+                if (ms) {
+                    int rc = pr->allpos[1] ? set_lds(ctx, enc1_mfma<true, true>, lds) : set_lds(ctx, enc1_mfma<false, true>, lds);
+                    if (rc) return rc;
+                    ProfScope ps(ctx, "enc1_mfma");
+                    if (pr->allpos[1]) LAUNCH((enc1_mfma<true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    else LAUNCH((enc1_mfma<false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+                    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+                    continue;
+                }
                 int rc = pr->allpos[1] ? set_lds(ctx, enc1_mfma<true>, lds) : set_lds(ctx, enc1_mfma<false>, lds);
                 if (rc) return rc;
                 ProfScope ps(ctx, "enc1_mfma");
@@ -2959,8 +3115,43 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         a.plan = make_plan(grid, num_cu, wgs_per_cu, batch, nbands, Hp);
         a.swz = rowtiles ? choose_swz_periodic(cin, W, Wp) : choose_swz(true, cin, W, Wp, RB / 2);
         a.pidx = d_index; a.skip = act[1]; a.tm_pre = (const float *)(prep + pr->enc[0].epi) + 48;
+        a.model_ids = inp.model_ids; a.mstride = mstride;
         int rc = COVAHIP_OK;
-        if (i == 1) {
+        const bool ap = pr->allpos[i];
+        if (ms && i == 1) {
+            if (by_frames && !d_index && !dry) return COVAHIP_ERR_INVALID_ARG;
+            rc = ap ? set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, true, true, 0, true>, lds) : set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, false, true, 0, true>, lds);
+            if (rc) return rc;
+            ProfScope ps(ctx, "enc1_mfma");
+            if (ap) LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, true, true, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+            else LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, false, true, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+        } else if (ms && i == 2 && rowtiles) {
+            rc = ap ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ, true>, lds)
+                    : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ, true>, lds);
+            if (rc) return rc;
+            ProfScope ps(ctx, "enc2_mfma");
+            if (ap) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
+            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
+        } else if (ms && i == 2) {
+            rc = ap ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true, false, 0, true>, lds) : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false, false, 0, true>, lds);
+            if (rc) return rc;
+            ProfScope ps(ctx, "enc2_mfma");
+            if (ap) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true, false, 0, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
+            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false, false, 0, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
+        } else if (ms && rowtiles) {
+            rc = ap ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ, true>, lds)
+                    : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ, true>, lds);
+            if (rc) return rc;
+            ProfScope ps(ctx, "enc3_mfma");
+            if (ap) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+        } else if (ms) {
+            rc = ap ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true, false, 0, true>, lds) : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false, false, 0, true>, lds);
+            if (rc) return rc;
+            ProfScope ps(ctx, "enc3_mfma");
+            if (ap) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true, false, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false, false, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
+        } else if (i == 1) {
             // (a null table means "stack b = frames 4b .. 4b+3" to this kernel: a carrier-frame call must bring its table)
             if (by_frames && !d_index && !dry) return COVAHIP_ERR_INVALID_ARG;
             // the round-1..3 level-1 kernel: grids wider than enc1_mfma's LDS row, developer band plans, set_impl(5)
@@ -3022,10 +3213,12 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         const size_t lds = off + 8 * 2048;
         if (lds <= 160 * 1024 - 256) {
             a.out = dact[2]; a.B = batch; a.zero = prep + pr->zero;
-            int rc = set_lds(ctx, dec012_mfma, lds);
+            a.model_ids = inp.model_ids; a.mstride = mstride;
+            int rc = ms ? set_lds(ctx, dec012_mfma<true>, lds) : set_lds(ctx, dec012_mfma<>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec012_mfma");
-            LAUNCH(dec012_mfma, dim3(std::min(batch, num_cu)), dim3(512), lds, ctx->stream, a);
+            if (ms) LAUNCH(dec012_mfma<true>, dim3(std::min(batch, num_cu)), dim3(512), lds, ctx->stream, a);
+            else LAUNCH(dec012_mfma<>, dim3(std::min(batch, num_cu)), dim3(512), lds, ctx->stream, a);
             COVAHIP_CHECK_HIP(ctx, hipGetLastError());
             first_dec = 3;
         }
@@ -3047,6 +3240,7 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         a.epi = (const float *)(prep + (last ? pr->final_epi : pr->dec[j].epi));
         a.B = batch; a.Hi = in.H; a.Wi = in.W; a.Hd = out.H; a.Wd = out.W; a.cy = m->dec_cy[j]; a.cx = m->dec_cx[j];
         a.Ts = j == 0 ? 1 : BN_T;
+        const DecMs am{inp.model_ids, mstride};
         const int GH = in.H + 1;
         const size_t row_bytes = (size_t)(in.W + 2) * ci_j * 2;
         // band planner.  A workgroup keeps its M-tile's weight fragments in registers, so the weights
@@ -3075,20 +3269,23 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         const int grid = std::min(items, (heavy ? 1 : 4) * num_cu);
         int rc;
         if (j == 0) {
-            rc = set_lds(ctx, dec_mfma<0, 128, 64, false>, lds);
+            rc = ms ? set_lds(ctx, dec_mfma<0, 128, 64, false, true>, lds) : set_lds(ctx, dec_mfma<0, 128, 64, false>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec0_mfma");
-            LAUNCH((dec_mfma<0, 128, 64, false>), dim3(grid), dim3(512), lds, ctx->stream, a);
+            if (ms) LAUNCH((dec_mfma<0, 128, 64, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a, am);
+            else LAUNCH((dec_mfma<0, 128, 64, false>), dim3(grid), dim3(512), lds, ctx->stream, a, am);
         } else if (j == 1) {
-            rc = set_lds(ctx, dec_mfma<64, 64, 32, false>, lds);
+            rc = ms ? set_lds(ctx, dec_mfma<64, 64, 32, false, true>, lds) : set_lds(ctx, dec_mfma<64, 64, 32, false>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec1_mfma");
-            LAUNCH((dec_mfma<64, 64, 32, false>), dim3(grid), dim3(256), lds, ctx->stream, a);
+            if (ms) LAUNCH((dec_mfma<64, 64, 32, false, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
+            else LAUNCH((dec_mfma<64, 64, 32, false>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
         } else if (j == 2) {
-            rc = set_lds(ctx, dec_mfma<32, 32, 16, false>, lds);
+            rc = ms ? set_lds(ctx, dec_mfma<32, 32, 16, false, true>, lds) : set_lds(ctx, dec_mfma<32, 32, 16, false>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec2_mfma");
-            LAUNCH((dec_mfma<32, 32, 16, false>), dim3(grid), dim3(256), lds, ctx->stream, a);
+            if (ms) LAUNCH((dec_mfma<32, 32, 16, false, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
+            else LAUNCH((dec_mfma<32, 32, 16, false>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
         } else if (cc && m->fuse_tail && [&]() -> bool {
                        // last block + bboxcc in one launch when the frame's LDS plan fits: two band buffers (which
                        // bboxcc's region reuses) + the frame's mask bytes
@@ -3117,6 +3314,7 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
                        if (!best_nb) return false;
                        const size_t tb = (((size_t)((GH + best_nb - 1) / best_nb) + 1) * row_bytes + 15) & ~(size_t)15;
                        t.d = a;
+                       t.ms = am;
                        t.d.nbands = best_nb; t.d.mNb = magic(best_nb);
                        t.d.swz = choose_swz(false, ci_j, in.W, 0, (GH + best_nb - 1) / best_nb);
                        t.boxes = cc->boxes; t.counts = cc->counts;
@@ -3131,9 +3329,18 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
                            (size_t)t.wg.rows_bytes <= mfull && (!d_mask || (reinterpret_cast<uintptr_t>(d_mask) & 3) == 0)) {
                            t.d.swz = Swz{3, 1, 0, 0, 0};            // s = (xx >> 3) & 1 (what the staging of both forms evaluates)
                            t.d.mRC = magic(out.W / 4);               // the mask expansion's division
-                           if (set_lds(ctx, dec3cc_rows_mfma, tl)) return false;
+                           if (ms ? set_lds(ctx, dec3cc_rows_mfma<true>, tl) : set_lds(ctx, dec3cc_rows_mfma<>, tl)) return false;
                            ProfScope ps(ctx, "dec3_bboxcc_fused");
-                           LAUNCH(dec3cc_rows_mfma, grid3, wg3, tl, ctx->stream, t);
+                           if (ms) LAUNCH(dec3cc_rows_mfma<true>, grid3, wg3, tl, ctx->stream, t);
+                           else LAUNCH(dec3cc_rows_mfma<>, grid3, wg3, tl, ctx->stream, t);
+                           return true;
+                       }
+                       if (ms) {
+                           auto k = t.use_wv ? (half ? dec3cc_mfma<true, true, true> : dec3cc_mfma<true, false, true>)
+                                             : (half ? dec3cc_mfma<false, true, true> : dec3cc_mfma<false, false, true>);
+                           if (set_lds(ctx, k, tl)) return false;
+                           ProfScope ps(ctx, "dec3_bboxcc_fused");
+                           LAUNCH(k, grid3, wg3, tl, ctx->stream, t);
                            return true;
                        }
                        if (half) {
@@ -3151,15 +3358,17 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
                    }()) {
             if (cc_done) *cc_done = true;
         } else if (half) {
-            rc = set_lds(ctx, dec_mfma<16, 0, 16, true>, lds);
+            rc = ms ? set_lds(ctx, dec_mfma<16, 0, 16, true, true>, lds) : set_lds(ctx, dec_mfma<16, 0, 16, true>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec3_final_mfma");
-            LAUNCH((dec_mfma<16, 0, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a);
+            if (ms) LAUNCH((dec_mfma<16, 0, 16, true, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
+            else LAUNCH((dec_mfma<16, 0, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
         } else {
-            rc = set_lds(ctx, dec_mfma<16, 16, 16, true>, lds);
+            rc = ms ? set_lds(ctx, dec_mfma<16, 16, 16, true, true>, lds) : set_lds(ctx, dec_mfma<16, 16, 16, true>, lds);
             if (rc) return rc;
             ProfScope ps(ctx, "dec3_final_mfma");
-            LAUNCH((dec_mfma<16, 16, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a);
+            if (ms) LAUNCH((dec_mfma<16, 16, 16, true, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
+            else LAUNCH((dec_mfma<16, 16, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
         }
         COVAHIP_CHECK_HIP(ctx, hipGetLastError());
     }

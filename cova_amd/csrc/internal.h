@@ -124,6 +124,6 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);
 int covahip_blobnet_forward_dev(covahip_ctx *ctx, const uint8_t *d_stack, int batch, float *d_logits,
-                                uint8_t *d_mask);
+                                uint8_t *d_mask, const uint8_t *model_ids = nullptr);
 int covahip_blobnet_geometry(covahip_ctx *ctx, int *h, int *w);
 int covahip_blobnet_grow_lanes(covahip_ctx *ctx, int n_lanes);   // workspaces of lanes [0, n_lanes) of the loaded model

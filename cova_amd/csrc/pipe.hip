@@ -16,6 +16,7 @@
 // Reference pipeline stage this stands for: nvstreammux -> nvinfer(BlobNet) -> nvstreamdemux -> maskcopy -> bboxcc
 // (pipeline/cova/pipeline.py:139-261), with metapreprocess' stacking (imp.rs:288-332) as the GPU-side gather of
 // covahip_filter_forward_frames.
+#include <cstring>
 #include <algorithm>
 #include <chrono>
 #include <ctime>
@@ -115,6 +116,7 @@ static bool streams_share_queue(hipStream_t a, hipStream_t b) { return streams_s
 struct Slot {
     uint8_t *h_frames = nullptr;
     int32_t *h_index = nullptr;
+    uint8_t *h_models = nullptr;     // model id per stack [max_batch] (model sets): zeroed by acquire, read by submit
     int32_t *h_meta = nullptr;       // counts [B] | offsets [B + 1] | pad to 64 B | packed boxes: ONE pinned allocation (and one
     covahip_box *h_packed = nullptr; // device allocation of the same shape), so that one copy brings all of it back
     uint8_t *h_mask = nullptr;
@@ -157,6 +159,7 @@ void covahip_pipe_destroy(covahip_pipe *p) {
     for (Slot &s : p->slots) {
         if (s.h_frames) hipHostFree(s.h_frames);
         if (s.h_index) hipHostFree(s.h_index);
+        if (s.h_models) hipHostFree(s.h_models);
         if (s.h_meta) hipHostFree(s.h_meta);   // (h_packed / d_packed point into the meta allocations)
         if (s.h_mask) hipHostFree(s.h_mask);
         if (s.d_frames) hipFree(s.d_frames);
@@ -234,6 +237,7 @@ int covahip_pipe_create(covahip_ctx *ctx, int max_batch, int max_frames, int max
     for (Slot &s : p->slots) {
         bool ok = hipHostMalloc((void **)&s.h_frames, (size_t)max_frames * p->frame_bytes, hipHostMallocDefault) == hipSuccess &&
                   hipHostMalloc((void **)&s.h_index, (size_t)max_batch * BN_T * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
+                  hipHostMalloc((void **)&s.h_models, (size_t)max_batch, hipHostMallocDefault) == hipSuccess &&
                   hipHostMalloc((void **)&s.h_meta, meta_bytes + (size_t)max_batch * max_boxes * sizeof(covahip_box), hipHostMallocDefault) == hipSuccess &&
                   hipMalloc((void **)&s.d_frames, (size_t)max_frames * p->frame_bytes) == hipSuccess &&
                   hipMalloc((void **)&s.d_boxes, (size_t)max_batch * max_boxes * sizeof(covahip_box)) == hipSuccess &&
@@ -318,10 +322,17 @@ int covahip_pipe_acquire(covahip_pipe *p, int *slot, uint8_t **frames, int32_t *
             *slot = i;
             *frames = p->slots[i].h_frames;
             *stack_index = p->slots[i].h_index;
+            std::memset(p->slots[i].h_models, 0, (size_t)p->max_batch);   // every stack on model 0 unless the caller says otherwise
             return COVAHIP_OK;
         }
     }
     return COVAHIP_ERR_OVERFLOW;   // every slot is acquired or in flight: collect one first
+}
+
+int covahip_pipe_model_ids(covahip_pipe *p, int slot, uint8_t **model_ids) {
+    if (!p || !model_ids || slot < 0 || slot >= p->n_slots || p->slots[slot].state != 1) return COVAHIP_ERR_INVALID_ARG;
+    *model_ids = p->slots[slot].h_models;
+    return COVAHIP_OK;
 }
 
 int covahip_pipe_submit(covahip_pipe *p, int slot, int n_frames, int batch, int area_thresh) {
@@ -338,10 +349,11 @@ int covahip_pipe_submit(covahip_pipe *p, int slot, int n_frames, int batch, int 
     if (!lane.ok()) return COVAHIP_ERR_HIP;
     PIPE_CHECK(hipStreamWaitEvent(ctx->stream, s.ev_in, 0));
     int32_t *d_counts = s.d_meta, *d_offsets = s.d_meta + p->max_batch;
-    int rc = p->packed ? covahip_filter_forward_frames_packed(ctx, reinterpret_cast<const uint16_t *>(s.d_frames), n_frames, s.h_index, batch,
-                                                              area_thresh, s.d_boxes, d_counts, p->max_boxes, nullptr, s.d_mask)
-                       : covahip_filter_forward_frames(ctx, s.d_frames, n_frames, s.h_index, batch, area_thresh, s.d_boxes, d_counts,
-                                                       p->max_boxes, nullptr, s.d_mask, COVAHIP_MEM_DEVICE);
+    int rc = p->packed ? covahip_filter_forward_frames_packed_m(ctx, reinterpret_cast<const uint16_t *>(s.d_frames), n_frames, s.h_index,
+                                                                s.h_models, batch, area_thresh, s.d_boxes, d_counts, p->max_boxes, nullptr,
+                                                                s.d_mask)
+                       : covahip_filter_forward_frames_m(ctx, s.d_frames, n_frames, s.h_index, s.h_models, batch, area_thresh, s.d_boxes,
+                                                         d_counts, p->max_boxes, nullptr, s.d_mask, COVAHIP_MEM_DEVICE);
     if (rc) return rc;
     {
         ProfScope ps(ctx, "pack_boxes");

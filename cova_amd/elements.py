@@ -30,6 +30,10 @@ def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
 
 
+def _optr(a: np.ndarray | None) -> int | None:
+    return None if a is None else a.ctypes.data
+
+
 # ---------------------------------------------------------------------------------- ctx
 class Context:
     """One GPU context (device + HIP stream + BlobNet workspace)."""
@@ -164,13 +168,28 @@ class BlobNetInfer:
     """Stands where `nvinfer` (BlobNet TensorRT engine) + `maskcopy` stand in the reference
     pipeline: batched RGBA stacks in, GRAY8 {0,1} masks (and optionally logits) out."""
 
-    def __init__(self, ctx: Context, weights_flat: np.ndarray, h_mb: int, w_mb: int, max_batch: int,
+    def __init__(self, ctx: Context, weights_flat, h_mb: int, w_mb: int, max_batch: int,
                  timestep: int = 4):
+        """weights_flat: one model's weights, or a list of them: a model set (covahip_blobnet_load_set) whose stacks name
+        their model with the model_ids argument of the forward methods (None: model 0)."""
         self.ctx, self.h, self.w, self.t, self.max_batch = ctx, h_mb, w_mb, timestep, max_batch
         self._lib = L.lib()
-        blob = W.to_bytes(weights_flat)
-        L.check(self._lib.covahip_blobnet_load(ctx.handle, blob, len(blob), h_mb, w_mb, timestep, max_batch),
-                "covahip_blobnet_load", ctx.handle)
+        if isinstance(weights_flat, (list, tuple)):
+            blobs = [W.to_bytes(w) for w in weights_flat]
+            ptrs = (C.c_char_p * max(1, len(blobs)))(*blobs)
+            sizes = (C.c_size_t * max(1, len(blobs)))(*[len(b) for b in blobs])
+            L.check(self._lib.covahip_blobnet_load_set(ctx.handle, len(blobs), ptrs, sizes, h_mb, w_mb, timestep, max_batch),
+                    "covahip_blobnet_load_set", ctx.handle)
+        else:
+            blob = W.to_bytes(weights_flat)
+            L.check(self._lib.covahip_blobnet_load(ctx.handle, blob, len(blob), h_mb, w_mb, timestep, max_batch),
+                    "covahip_blobnet_load", ctx.handle)
+
+    @property
+    def num_models(self) -> int:
+        v = C.c_int()
+        L.check(self._lib.covahip_blobnet_num_models(self.ctx.handle, C.byref(v)), "covahip_blobnet_num_models")
+        return v.value
 
     def set_enc_plan(self, level: int, nbands: int, nbuf: int = 1):
         """Developer switch (include/covahip_dev.h): band plan of encoder level 1..3; nbands = 0 -> automatic."""
@@ -203,35 +222,47 @@ class BlobNetInfer:
         L.check(self._lib.covahip_blobnet_macs_per_frame(self.ctx.handle, C.byref(v)), "macs_per_frame")
         return v.value
 
-    def infer(self, stack: np.ndarray, want_logits: bool = True):
-        """stack u8 [B][t*h][w][4] (host) -> (logits f32 [B][h][w] | None, mask u8 [B][h][w])."""
+    def infer(self, stack: np.ndarray, want_logits: bool = True, model_ids=None):
+        """stack u8 [B][t*h][w][4] (host) -> (logits f32 [B][h][w] | None, mask u8 [B][h][w]).  model_ids: u8 [B], the model of
+        every stack of a model set (None: model 0)."""
         stack = np.ascontiguousarray(stack, dtype=np.uint8)
         b = stack.shape[0]
         assert stack.shape == (b, self.t * self.h, self.w, 4), stack.shape
         logits = np.empty((b, self.h, self.w), dtype=np.float32) if want_logits else None
         mask = np.empty((b, self.h, self.w), dtype=np.uint8)
-        L.check(self._lib.covahip_blobnet_forward(self.ctx.handle, _ptr(stack), b, _ptr(logits) if want_logits else None,
-                                                  _ptr(mask), L.MEM_HOST), "covahip_blobnet_forward", self.ctx.handle)
+        ids = _ids(model_ids, b)
+        L.check(self._lib.covahip_blobnet_forward_m(self.ctx.handle, _ptr(stack), _optr(ids), b, _ptr(logits) if want_logits else None,
+                                                    _ptr(mask), L.MEM_HOST), "covahip_blobnet_forward_m", self.ctx.handle)
         return logits, mask
 
-    def infer_device(self, d_stack: int, batch: int, d_logits: int | None, d_mask: int | None):
-        L.check(self._lib.covahip_blobnet_forward(self.ctx.handle, d_stack, batch, d_logits, d_mask, L.MEM_DEVICE),
-                "covahip_blobnet_forward", self.ctx.handle)
+    def infer_device(self, d_stack: int, batch: int, d_logits: int | None, d_mask: int | None, model_ids=None):
+        ids = _ids(model_ids, batch)
+        L.check(self._lib.covahip_blobnet_forward_m(self.ctx.handle, d_stack, _optr(ids), batch, d_logits, d_mask, L.MEM_DEVICE),
+                "covahip_blobnet_forward_m", self.ctx.handle)
 
-    def filter(self, stack: np.ndarray, cc_threshold: int, max_boxes: int = 256, want_mask: bool = False):
-        """Fused BlobNet -> mask -> bboxcc on host buffers: returns (boxes [B][max_boxes], counts [B], mask|None)."""
+    def filter(self, stack: np.ndarray, cc_threshold: int, max_boxes: int = 256, want_mask: bool = False, model_ids=None):
+        """Fused BlobNet -> mask -> bboxcc on host buffers: returns (boxes [B][max_boxes], counts [B], mask|None).  model_ids:
+        u8 [B], the model of every stack of a model set (None: model 0)."""
+        return self.filter_full(stack, cc_threshold, max_boxes, want_mask, False, model_ids)[:3]
+
+    def filter_full(self, stack: np.ndarray, cc_threshold: int, max_boxes: int = 256, want_mask: bool = False,
+                    want_logits: bool = False, model_ids=None):
+        """filter() that also hands back the logits: returns (boxes, counts, mask|None, logits f32 [B][h][w] | None)."""
         stack = np.ascontiguousarray(stack, dtype=np.uint8)
         b = stack.shape[0]
         boxes = np.zeros((b, max_boxes), dtype=L.BOX_DTYPE)
         counts = np.zeros(b, dtype=np.int32)
         mask = np.empty((b, self.h, self.w), dtype=np.uint8) if want_mask else None
-        L.check(self._lib.covahip_filter_forward(self.ctx.handle, _ptr(stack), b, cc_threshold, _ptr(boxes), _ptr(counts),
-                                                 max_boxes, None, _ptr(mask) if want_mask else None, L.MEM_HOST),
-                "covahip_filter_forward", self.ctx.handle)
-        return boxes, counts, mask
+        logits = np.empty((b, self.h, self.w), dtype=np.float32) if want_logits else None
+        ids = _ids(model_ids, b)
+        L.check(self._lib.covahip_filter_forward_m(self.ctx.handle, _ptr(stack), _optr(ids), b, cc_threshold, _ptr(boxes), _ptr(counts),
+                                                   max_boxes, _ptr(logits) if want_logits else None, _ptr(mask) if want_mask else None,
+                                                   L.MEM_HOST),
+                "covahip_filter_forward_m", self.ctx.handle)
+        return boxes, counts, mask, logits
 
     def filter_frames(self, frames: np.ndarray, stack_index: np.ndarray | None, cc_threshold: int, max_boxes: int = 256,
-                      want_mask: bool = False, want_logits: bool = False):
+                      want_mask: bool = False, want_logits: bool = False, model_ids=None):
         """The hot path fed with carrier frames u8 [F][h][w][4] (host) and the stack -> frame index table i32 [B][4]
         (None: one stream in order): returns (boxes, counts, mask|None, logits|None) like filter()."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
@@ -243,26 +274,46 @@ class BlobNetInfer:
         counts = np.zeros(b, dtype=np.int32)
         mask = np.empty((b, self.h, self.w), dtype=np.uint8) if want_mask else None
         logits = np.empty((b, self.h, self.w), dtype=np.float32) if want_logits else None
-        L.check(self._lib.covahip_filter_forward_frames(self.ctx.handle, _ptr(frames), f, None if idx is None else _ptr(idx), b,
-                                                        cc_threshold, _ptr(boxes), _ptr(counts), max_boxes,
-                                                        _ptr(logits) if want_logits else None,
-                                                        _ptr(mask) if want_mask else None, L.MEM_HOST),
-                "covahip_filter_forward_frames", self.ctx.handle)
+        ids = _ids(model_ids, b)
+        L.check(self._lib.covahip_filter_forward_frames_m(self.ctx.handle, _ptr(frames), f, None if idx is None else _ptr(idx),
+                                                          _optr(ids), b, cc_threshold, _ptr(boxes), _ptr(counts), max_boxes,
+                                                          _ptr(logits) if want_logits else None,
+                                                          _ptr(mask) if want_mask else None, L.MEM_HOST),
+                "covahip_filter_forward_frames_m", self.ctx.handle)
         return boxes, counts, mask, logits
 
     def filter_frames_device(self, d_frames: int, n_frames: int, stack_index: np.ndarray | None, batch: int, cc_threshold: int,
-                             d_boxes: int, d_counts: int, max_boxes: int, d_mask: int | None = None):
+                             d_boxes: int, d_counts: int, max_boxes: int, d_mask: int | None = None, model_ids=None,
+                             d_logits: int | None = None, packed: bool = False):
+        """Device pointers; packed: d_frames holds two-byte records (pack_frames, covahip_filter_forward_frames_packed_m)."""
         idx = None if stack_index is None else np.ascontiguousarray(stack_index, dtype=np.int32).reshape(-1, 4)
-        L.check(self._lib.covahip_filter_forward_frames(self.ctx.handle, d_frames, n_frames, None if idx is None else _ptr(idx),
-                                                        batch, cc_threshold, d_boxes, d_counts, max_boxes, None, d_mask,
-                                                        L.MEM_DEVICE),
-                "covahip_filter_forward_frames", self.ctx.handle)
+        ids = _ids(model_ids, batch)
+        if packed:
+            L.check(self._lib.covahip_filter_forward_frames_packed_m(self.ctx.handle, d_frames, n_frames, None if idx is None else _ptr(idx),
+                                                                     _optr(ids), batch, cc_threshold, d_boxes, d_counts, max_boxes,
+                                                                     d_logits, d_mask),
+                    "covahip_filter_forward_frames_packed_m", self.ctx.handle)
+            return
+        L.check(self._lib.covahip_filter_forward_frames_m(self.ctx.handle, d_frames, n_frames, None if idx is None else _ptr(idx),
+                                                          _optr(ids), batch, cc_threshold, d_boxes, d_counts, max_boxes, d_logits,
+                                                          d_mask, L.MEM_DEVICE),
+                "covahip_filter_forward_frames_m", self.ctx.handle)
 
     def filter_device(self, d_stack: int, batch: int, cc_threshold: int, d_boxes: int, d_counts: int, max_boxes: int,
-                      d_mask: int | None = None):
-        L.check(self._lib.covahip_filter_forward(self.ctx.handle, d_stack, batch, cc_threshold, d_boxes, d_counts,
-                                                 max_boxes, None, d_mask, L.MEM_DEVICE),
-                "covahip_filter_forward", self.ctx.handle)
+                      d_mask: int | None = None, model_ids=None, d_logits: int | None = None):
+        ids = _ids(model_ids, batch)
+        L.check(self._lib.covahip_filter_forward_m(self.ctx.handle, d_stack, _optr(ids), batch, cc_threshold, d_boxes, d_counts,
+                                                   max_boxes, d_logits, d_mask, L.MEM_DEVICE),
+                "covahip_filter_forward_m", self.ctx.handle)
+
+
+def _ids(model_ids, batch: int):
+    """model_ids of a call: None, or u8 [batch] (one model per stack of a model set)."""
+    if model_ids is None:
+        return None
+    ids = np.ascontiguousarray(model_ids, dtype=np.uint8).reshape(-1)
+    assert ids.shape == (batch,), (ids.shape, batch)
+    return ids
 
 
 def pack_frames(frames: np.ndarray) -> np.ndarray:
@@ -292,6 +343,7 @@ class FilterPipe:
             L.check(self._lib.covahip_pipe_set_blocking_wait(h, 1), "covahip_pipe_set_blocking_wait", net.ctx.handle)
         self._batch = {}
         self._views = {}     # slot -> numpy views of its pinned input buffers (the addresses never change)
+        self._mviews = {}    # slot -> numpy view of its pinned model ids
         self._rviews = {}    # slot -> full-size numpy views of its result buffers
         self._held = []      # collected slots whose result views are still handed out
 
@@ -330,6 +382,15 @@ class FilterPipe:
             index = np.ctypeslib.as_array(C.cast(ip.value, C.POINTER(C.c_int32)), shape=(self.max_batch * 4,)).reshape(self.max_batch, 4)
             self._views[slot.value] = (frames, index)
         return (slot.value,) + self._views[slot.value]
+
+    def model_ids(self, slot: int) -> np.ndarray:
+        """The acquired slot's model ids u8 [max_batch] (covahip_pipe_model_ids): a view of its pinned buffer, zeroed by acquire(),
+        filled in place next to the frames and the stack index, read by submit()."""
+        if slot not in self._mviews:
+            mp = C.c_void_p()
+            L.check(self._lib.covahip_pipe_model_ids(self._h, slot, C.byref(mp)), "covahip_pipe_model_ids")
+            self._mviews[slot] = np.ctypeslib.as_array(C.cast(mp, C.POINTER(C.c_uint8)), shape=(self.max_batch,))
+        return self._mviews[slot]
 
     def submit(self, slot: int, n_frames: int, batch: int, cc_threshold: int):
         L.check(self._lib.covahip_pipe_submit(self._h, slot, n_frames, batch, cc_threshold), "covahip_pipe_submit", self.net.ctx.handle)

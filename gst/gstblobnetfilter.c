@@ -74,6 +74,9 @@ struct _GstBlobNetFilter {
     guint64 done __attribute__((aligned(64)));   /* frames whose bytes (and table rows) are in the slot; a flush waits for done == frames taken */
     gboolean flushing __attribute__((aligned(64)));   /* lock held: same as the bit in `state`, for the threads that wait on flush_cond */
     gchar *weights;
+    gchar *pad_weights;   /* pad-model-weights: "IDX=PATH;IDX=PATH" (model sets: sink_IDX runs the model of PATH) */
+    guint8 *pad_model;    /* model of sink pad idx [BF_MAX_PAD_MAP] when pad-model-weights is set, else NULL */
+    uint8_t *pm;          /* model ids of the slot being filled (covahip_pipe_model_ids) */
     guint gpu_id, batch_size, cc_threshold, max_boxes;
     guint64 timeout_us;
     covahip_ctx *ctx;
@@ -105,7 +108,9 @@ struct _GstBlobNetFilter {
 };
 typedef struct { GstElementClass parent_class; } GstBlobNetFilterClass;
 G_DEFINE_TYPE(GstBlobNetFilter, gst_blobnetfilter, GST_TYPE_ELEMENT)
-enum { BF_PROP_0, BF_PROP_WEIGHTS, BF_PROP_GPU, BF_PROP_BATCH, BF_PROP_TIMEOUT, BF_PROP_CC, BF_PROP_MAXBOXES, BF_PROP_BATCHES, BF_PROP_TIMING };
+enum { BF_PROP_0, BF_PROP_WEIGHTS, BF_PROP_GPU, BF_PROP_BATCH, BF_PROP_TIMEOUT, BF_PROP_CC, BF_PROP_MAXBOXES, BF_PROP_BATCHES, BF_PROP_TIMING,
+       BF_PROP_PAD_WEIGHTS };
+#define BF_MAX_PAD_MAP 1024   /* sink pads pad-model-weights can name: sink_0 .. sink_1023 */
 
 #define BF_ST_BITS 21
 #define BF_ST_MASK ((1ull << BF_ST_BITS) - 1)
@@ -117,6 +122,53 @@ enum { BF_PROP_0, BF_PROP_WEIGHTS, BF_PROP_GPU, BF_PROP_BATCH, BF_PROP_TIMEOUT, 
 static inline guint64 bf_state(GstBlobNetFilter *s) { return __atomic_load_n(&s->state, __ATOMIC_ACQUIRE); }
 
 static BfPad *bf_pad_of(GstBlobNetFilter *s, GstPad *sink) { return (BfPad *)gst_pad_get_element_private(sink); }
+
+/* pad-model-weights: distinct files become the models of one set, model-weights-file model 0; s->pad_model maps each pad to its
+ * model.  Loads the set (or the one model when the property is unset). */
+static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
+    if (!s->pad_weights || !*s->pad_weights)
+        return covahip_blobnet_load(s->ctx, blob0, len0, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+    GPtrArray *paths = g_ptr_array_new_with_free_func(g_free);
+    GPtrArray *blobs = g_ptr_array_new_with_free_func(g_free);
+    GArray *sizes = g_array_new(FALSE, FALSE, sizeof(size_t));
+    gchar **items = g_strsplit(s->pad_weights, ";", -1);
+    int rc = COVAHIP_OK;
+    s->pad_model = g_new0(guint8, BF_MAX_PAD_MAP);
+    g_ptr_array_add(paths, g_strdup(s->weights));
+    gchar *copy0 = g_malloc(len0 ? len0 : 1);
+    memcpy(copy0, blob0, len0);
+    g_ptr_array_add(blobs, copy0);
+    g_array_append_val(sizes, len0);
+    for (gchar **it = items; *it && rc == COVAHIP_OK; it++) {
+        gchar *item = g_strstrip(*it);
+        if (!*item) continue;
+        gchar *eq = strchr(item, '=');
+        gchar *end = NULL;
+        const guint64 idx = eq ? g_ascii_strtoull(item, &end, 10) : 0;
+        if (!eq || end != eq || end == item || idx >= BF_MAX_PAD_MAP || !eq[1]) { rc = COVAHIP_ERR_INVALID_ARG; break; }
+        const gchar *path = g_strstrip(eq + 1);
+        guint k = 0;
+        while (k < paths->len && strcmp((const gchar *)g_ptr_array_index(paths, k), path) != 0) k++;
+        if (k == paths->len) {
+            gchar *b = NULL;
+            gsize n = 0;
+            if (k >= COVAHIP_MAX_MODELS || !g_file_get_contents(path, &b, &n, NULL)) { rc = COVAHIP_ERR_BAD_WEIGHTS; break; }
+            g_ptr_array_add(paths, g_strdup(path));
+            g_ptr_array_add(blobs, b);
+            size_t nn = n;
+            g_array_append_val(sizes, nn);
+        }
+        s->pad_model[idx] = (guint8)k;
+    }
+    g_strfreev(items);
+    if (rc == COVAHIP_OK)
+        rc = covahip_blobnet_load_set(s->ctx, (int)blobs->len, (const void *const *)blobs->pdata, (const size_t *)sizes->data, s->h_mb,
+                                      s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+    g_ptr_array_free(paths, TRUE);
+    g_ptr_array_free(blobs, TRUE);
+    g_array_free(sizes, TRUE);
+    return rc;
+}
 
 static gboolean bf_ensure_model(GstBlobNetFilter *s) {   /* lock held */
     gchar *blob = NULL;
@@ -136,13 +188,14 @@ static gboolean bf_ensure_model(GstBlobNetFilter *s) {   /* lock held */
     }
     /* two batches in flight: every pipe slot owns its output buffers (the ctx default is one lane, include/covahip.h) */
     rc = covahip_ctx_set_lanes(s->ctx, BF_LANES);
-    if (rc == COVAHIP_OK) rc = covahip_blobnet_load(s->ctx, blob, len, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+    if (rc == COVAHIP_OK) rc = bf_load_models(s, blob, len);
     g_free(blob);
     if (rc == COVAHIP_OK) rc = covahip_pipe_create(s->ctx, (int)s->batch_size, BF_TIMESTEP * (int)s->batch_size, (int)s->max_boxes, BF_SLOTS, 0, &s->pipe);
     if (rc == COVAHIP_OK) rc = covahip_pipe_set_packed(s->pipe, 1);
     /* the collector sleeps while it waits for the GPU instead of spinning on the completion signal (BLOBNETFILTER_SPIN=1: the old way) */
     if (rc == COVAHIP_OK && !g_getenv("BLOBNETFILTER_SPIN")) rc = covahip_pipe_set_blocking_wait(s->pipe, 1);
     if (rc == COVAHIP_OK) rc = covahip_pipe_acquire(s->pipe, &s->slot, &s->pf, &s->pi);
+    if (rc == COVAHIP_OK && s->pad_model) rc = covahip_pipe_model_ids(s->pipe, s->slot, &s->pm);
     if (rc != COVAHIP_OK) {
         GST_ELEMENT_ERROR(s, LIBRARY, INIT, ("covahip: %s (%s)", covahip_strerror(rc), covahip_last_hip_error(s->ctx)), (NULL));
         return FALSE;
@@ -340,6 +393,7 @@ static GstFlowReturn bf_flush(GstBlobNetFilter *s) {   /* caller: lock held, s->
         if (s->push_ret != GST_FLOW_OK) { ret = s->push_ret; break; }   /* a failed element waits for nothing */
         g_mutex_lock(&s->pipe_lock);
         rc = covahip_pipe_acquire(s->pipe, &s->slot, &s->pf, &s->pi);
+        if (rc == COVAHIP_OK && s->pad_model) rc = covahip_pipe_model_ids(s->pipe, s->slot, &s->pm);
         g_mutex_unlock(&s->pipe_lock);
         if (rc == COVAHIP_OK) {
             for (guint i = 0; i < s->pads->len; i++) {
@@ -402,6 +456,7 @@ static gboolean bf_try_reserve(GstBlobNetFilter *s, BfPad *p, GstBuffer *buf, ui
             row[k + 1] = p->hist_pos[k];
         }
         s->meta[ns].pad = p->idx;
+        if (s->pad_model) s->pm[ns] = p->idx < BF_MAX_PAD_MAP ? s->pad_model[p->idx] : 0;   /* model sets: the pad's model */
         s->meta[ns].pts = GST_BUFFER_PTS(buf);
         s->meta[ns].duration = GST_BUFFER_DURATION(buf);
         if (ns == 0) {
@@ -702,6 +757,7 @@ static void bf_set_property(GObject *o, guint id, const GValue *v, GParamSpec *p
     g_mutex_lock(&s->lock);
     switch (id) {
     case BF_PROP_WEIGHTS: g_free(s->weights); s->weights = g_value_dup_string(v); break;
+    case BF_PROP_PAD_WEIGHTS: if (!s->pipe) { g_free(s->pad_weights); s->pad_weights = g_value_dup_string(v); } break;
     case BF_PROP_GPU: s->gpu_id = g_value_get_uint(v); break;
     case BF_PROP_BATCH: if (!s->pipe) s->batch_size = g_value_get_uint(v); break;
     case BF_PROP_TIMEOUT: s->timeout_us = g_value_get_uint64(v); break;
@@ -715,6 +771,7 @@ static void bf_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps) {
     GstBlobNetFilter *s = (GstBlobNetFilter *)o;
     switch (id) {
     case BF_PROP_WEIGHTS: g_value_set_string(v, s->weights); break;
+    case BF_PROP_PAD_WEIGHTS: g_value_set_string(v, s->pad_weights); break;
     case BF_PROP_GPU: g_value_set_uint(v, s->gpu_id); break;
     case BF_PROP_BATCH: g_value_set_uint(v, s->batch_size); break;
     case BF_PROP_TIMEOUT: g_value_set_uint64(v, s->timeout_us); break;
@@ -748,6 +805,8 @@ static void bf_finalize(GObject *o) {
     g_ptr_array_free(s->pads, TRUE);
     g_free(s->meta);
     g_free(s->weights);
+    g_free(s->pad_weights);
+    g_free(s->pad_model);
     g_mutex_clear(&s->lock);
     g_cond_clear(&s->cond);
     g_cond_clear(&s->flush_cond);
@@ -780,6 +839,9 @@ static void gst_blobnetfilter_class_init(GstBlobNetFilterClass *k) {
     e->change_state = bf_change_state;
     g_object_class_install_property(g, BF_PROP_WEIGHTS, g_param_spec_string("model-weights-file", "Weights",
         "BlobNet weight blob (cova_amd/weights.py format)", NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
+    g_object_class_install_property(g, BF_PROP_PAD_WEIGHTS, g_param_spec_string("pad-model-weights", "Per-pad weights",
+        "Model sets: \"IDX=PATH;IDX=PATH\" runs sink_IDX on the weights in PATH (distinct files are loaded once, as one set, at start); "
+        "pads it does not name use model-weights-file", NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_GPU, g_param_spec_uint("gpu-id", "GPU id", "HIP device to run on", 0, 15, 0,
         G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_BATCH, g_param_spec_uint("batch-size", "Batch size",

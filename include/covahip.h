@@ -127,10 +127,28 @@ int covahip_profile_read(covahip_ctx *ctx, covahip_kernel_time *out, int cap, in
  * Limits of the kernels, all checked HERE (COVAHIP_ERR_UNSUPPORTED), never at forward time:
  *   16 <= h_mb, w_mb <= 1024; w_mb a multiple of 4 (the first level reads 16-byte groups of four
  *   macroblocks); one band of every level must fit the 160 KB of LDS of a CU (holds far beyond 4K grids).
- * A ctx holds ONE model: loading again replaces it.  Use one ctx per model (element instance).
- * A failed load leaves the ctx without a model (later calls return COVAHIP_ERR_NOT_LOADED).  */
+ * A ctx holds ONE model or ONE model set (covahip_blobnet_load_set): loading again replaces it.
+ * A failed load leaves the ctx without a model (later calls return COVAHIP_ERR_NOT_LOADED).  A malformed blob
+ * (COVAHIP_ERR_BAD_WEIGHTS) is rejected before anything changes: the model loaded before stays.  */
 int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_bytes, int h_mb, int w_mb,
                          int t, int max_batch);
+/* Model sets: one ctx holds K models of ONE geometry and max_batch (e.g. one BlobNet per camera), and every stack of a
+ * batch names its model, so streams of different models share one batch and one launch of each kernel.
+ *   1 <= n_models <= COVAHIP_MAX_MODELS; weights[k] / weights_bytes[k]: model k's blob (format as above).
+ *   Replaces whatever the ctx held.  All or nothing: one malformed blob is COVAHIP_ERR_BAD_WEIGHTS and, like any
+ *   other failure here, leaves the ctx with no model.
+ *   covahip_blobnet_load is a set of one.  The forward entries without _m run every stack on model 0.
+ * The _m entries below take model_ids: a HOST array u8 [batch], the model of output stack b (like stack_index, read
+ * during the call); NULL = model 0 everywhere.  An id >= n_models is COVAHIP_ERR_INVALID_ARG.  A stack's result is
+ * the result of a ctx loaded with its model alone, bit for bit.
+ * Carrier-frame entries: level 0 runs ONCE per carrier frame, so a frame has exactly one model: a frame that stacks
+ * of two different models reference is COVAHIP_ERR_INVALID_ARG (checked on the host with stack_index).  Frames no
+ * stack references may run under any model; nothing of them is visible.                                          */
+#define COVAHIP_MAX_MODELS 256
+int covahip_blobnet_load_set(covahip_ctx *ctx, int n_models, const void *const *weights, const size_t *weights_bytes,
+                             int h_mb, int w_mb, int t, int max_batch);
+/* Models of the loaded set (1 after covahip_blobnet_load). */
+int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models);
 /* rgba_stack: u8 [batch][t*h_mb][w_mb][4] -- metapreprocess output (row block k =
  *   frame i-k; byte 0/1/2 = mb_type/mv_x/mv_y, byte 3 ignored).
  * logits (may be NULL): f32 [batch][h_mb][w_mb] pre-sigmoid output.
@@ -139,6 +157,9 @@ int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_b
  * covahip_ctx_sync); synchronous for host pointers.                               */
 int covahip_blobnet_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, float *logits,
                             uint8_t *mask, int mem_kind);
+/* covahip_blobnet_forward with a model per stack (model_ids: see covahip_blobnet_load_set). */
+int covahip_blobnet_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const uint8_t *model_ids, int batch,
+                              float *logits, uint8_t *mask, int mem_kind);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc
@@ -165,6 +186,10 @@ int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int 
 int covahip_filter_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, int area_thresh,
                            covahip_box *boxes, int32_t *counts, int max_boxes, float *logits,
                            uint8_t *mask, int mem_kind);
+/* covahip_filter_forward with a model per stack (model_ids: see covahip_blobnet_load_set). */
+int covahip_filter_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const uint8_t *model_ids, int batch,
+                             int area_thresh, covahip_box *boxes, int32_t *counts, int max_boxes, float *logits,
+                             uint8_t *mask, int mem_kind);
 
 /* The same hot path fed with CARRIER frames instead of stacks: metapreprocess' temporal stacking (timestep 4,
  * cova-rs/gst-plugins/src/metapreprocess/imp.rs:288-332) becomes an index gather on the GPU.  With gamma = 1 a
@@ -178,6 +203,10 @@ int covahip_filter_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batc
 int covahip_filter_forward_frames(covahip_ctx *ctx, const uint8_t *frames, int n_frames, const int32_t *stack_index,
                                   int batch, int area_thresh, covahip_box *boxes, int32_t *counts, int max_boxes,
                                   float *logits, uint8_t *mask, int mem_kind);
+/* covahip_filter_forward_frames with a model per stack (model_ids: see covahip_blobnet_load_set; one model per frame). */
+int covahip_filter_forward_frames_m(covahip_ctx *ctx, const uint8_t *frames, int n_frames, const int32_t *stack_index,
+                                    const uint8_t *model_ids, int batch, int area_thresh, covahip_box *boxes,
+                                    int32_t *counts, int max_boxes, float *logits, uint8_t *mask, int mem_kind);
 
 /* Pipelined host-buffer form of the carrier-frame hot path, for a caller that batches frames continuously (the
  * batching element gst/gstcova.c `blobnetfilter`; stands where nvstreammux -> nvinfer -> nvstreamdemux -> maskcopy
@@ -210,6 +239,10 @@ int covahip_pipe_set_packed(covahip_pipe *p, int on);
 int covahip_pipe_set_blocking_wait(covahip_pipe *p, int on);
 int covahip_pipe_acquire(covahip_pipe *pipe, int *slot, uint8_t **frames, int32_t **stack_index);
 int covahip_pipe_submit(covahip_pipe *pipe, int slot, int n_frames, int batch, int area_thresh);
+/* Model sets (covahip_blobnet_load_set): the PINNED model id array u8 [max_batch] of an ACQUIRED slot, filled in place like
+ * stack_index.  acquire zeroes it (every stack on model 0); submit reads the first `batch` ids with the rules of
+ * covahip_filter_forward_frames_m (an id >= the set's size, or a frame shared across models, fails the submit). */
+int covahip_pipe_model_ids(covahip_pipe *pipe, int slot, uint8_t **model_ids);
 /* Gives an ACQUIRED slot back without submitting it (after a failed covahip_pipe_submit, or when the caller shuts down with
  * a partly filled batch). */
 int covahip_pipe_abort(covahip_pipe *pipe, int slot);
@@ -469,6 +502,10 @@ void covahip_carrier_pack(const uint8_t *frame, size_t n_mb, uint16_t *records);
 int covahip_filter_forward_frames_packed(covahip_ctx *ctx, const uint16_t *d_records, int n_frames, const int32_t *stack_index,
                                          int batch, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes,
                                          float *d_logits, uint8_t *d_mask);
+/* ... with a model per stack (model_ids: see covahip_blobnet_load_set; one model per frame). */
+int covahip_filter_forward_frames_packed_m(covahip_ctx *ctx, const uint16_t *d_records, int n_frames, const int32_t *stack_index,
+                                           const uint8_t *model_ids, int batch, int area_thresh, covahip_box *d_boxes,
+                                           int32_t *d_counts, int max_boxes, float *d_logits, uint8_t *d_mask);
 
 /* ------------------------------------------------- metapreprocess stacking
  * Host state of the `metapreprocess` element (cova-rs/gst-plugins/src/metapreprocess/
