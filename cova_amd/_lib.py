@@ -191,6 +191,12 @@ PROTOTYPES = {
     "covahip_train_metrics": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "covahip_train_weights": (C.c_int, [_P, _P, _SZ, C.POINTER(_SZ)]),
     "covahip_train_grads": (C.c_int, [_P, _P, _SZ]),
+    "covahip_train_create_set": (C.c_int, [_P, C.POINTER(TrainCfg), C.c_int, _P, _P, _P, C.POINTER(_P)]),
+    "covahip_train_num_models": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "covahip_train_step_set": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int]),
+    "covahip_train_metrics_m": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int64)]),
+    "covahip_train_weights_m": (C.c_int, [_P, C.c_int, _P, _SZ, C.POINTER(_SZ)]),
+    "covahip_train_grads_m": (C.c_int, [_P, C.c_int, _P, _SZ]),
     "covahip_train_destroy": (None, [_P]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),

@@ -8,6 +8,14 @@
 // Determinism: no float atomics.  Every reduction is a fixed split of its range into slabs (one workgroup each, fixed-order
 // tree inside), followed by a sequential sum of the slabs; the split depends on the geometry and the batch only.  The only
 // atomics are the integer TP / FP / FN counters of the metrics.
+//
+// Training sets: a trainer holds K models of one geometry and every kernel takes one step of all of them in one launch.  The
+// model is the grid's z index.  Model m's slice of every buffer lies m * max_batch samples (m * N_PARAMS for parameters,
+// gradients and Adam moments) behind model 0's, and a kernel moves its pointers there once, then runs the code of a solo step
+// with the model's own batch b from the per-step table (MStep): element counts, slab counts and chunk lengths are all computed
+// from b in the kernel, so model m's arithmetic and summation order are those of a solo trainer at batch b.  Grids are sized
+// for the step's largest batch; a workgroup outside its model's extent (all of them when b = 0) leaves at once.
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -47,12 +55,77 @@ __device__ inline float keep(const Drop &d, uint64_t idx) {
 
 inline unsigned nblk(int64_t n) { return (unsigned)((n + BLK - 1) / BLK); }
 
+// ------------------------------------------------------------------------------------------------ per-model step table
+constexpr int N_SITES = 12;           // dropout sites: 2 per encoder level, 1 per decoder block
+constexpr int STAT_STRIDE = 7 * 256;  // floats of BN batch statistics per model: [7 layers][2][128]
+struct MStep {                        // one per model and step, uploaded with the step
+    int32_t b;                        // the model's batch this step (0: skipped, nothing of it is touched)
+    int32_t first;                    // its first sample in the packed stack / label input
+    float lr_t;                       // Adam's lr * sqrt(1 - b2^t) / (1 - b1^t) at the model's own t
+    uint32_t pad;
+    uint64_t key[N_SITES];            // drop_key(seed, step, site) of the model
+};
+// A set of one takes its step's values as kernel arguments instead (tab = null, nothing uploaded) and runs the kernels'
+// SET = false instantiation, which has no table loads and no offsets: the solo step of covahip_train_create as it was.
+struct Mdl {
+    const MStep *tab;                 // null: a set of one, its values below and in DropS::key
+    int maxB;                         // samples between two models' slices of an activation buffer
+    int64_t slab_stride;              // floats between two models' slab workspaces
+    int32_t solo_b;                   // (its chunk lengths come with each launch, solo_chunk, as the host knows its batch)
+    float solo_lr_t;
+};
+struct DropS {                        // a dropout site; the key comes from the model's table entry
+    int site;
+    uint32_t thr;
+    float scale;
+    uint64_t key;                     // the key of a set of one
+};
+// Every kernel has two instantiations ("Training sets": one shared instantiation cost the solo step 3 %).
+template <bool SET> __device__ inline int model_b(const Mdl &md) { return SET ? md.tab[blockIdx.z].b : md.solo_b; }
+template <bool SET> __device__ inline int model_first(const Mdl &md) { return SET ? md.tab[blockIdx.z].first : 0; }
+template <bool SET> __device__ inline float model_lr_t(const Mdl &md) { return SET ? md.tab[blockIdx.z].lr_t : md.solo_lr_t; }
+template <bool SET> __device__ inline Drop model_drop(const Mdl &md, const DropS &d) {
+    return Drop{SET ? md.tab[blockIdx.z].key[d.site] : d.key, d.thr, d.scale};
+}
+// A wave-uniform 64-bit value handed back through scalar registers, opaque to the optimiser: for the chunk lengths (out of a
+// 64-bit division, which the compiler does in vector registers) and for the per-model offsets below.
+__device__ inline int64_t uniform64(int64_t v) {
+    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v);
+    const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)v >> 32));
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+// offset of this workgroup's model in a buffer of `per` elements per sample
+// `per` is written as the int product of a kernel's extents where they are ints (at most 2^29 at 1024x1024): sign-extending
+// an extent itself up here makes the compiler reuse the 64-bit value in the index arithmetic of the loops, which then
+// multiplies high halves per element -- 8 - 11 % on the latency-bound convT weight-gradient launches of a batch-4 step.
+#define MOFF(per) (SET ? uniform64((int64_t)blockIdx.z * md.maxB * (int64_t)(per)) : (int64_t)0)
+#define POFF (SET ? uniform64((int64_t)blockIdx.z * (int64_t)N_PARAMS) : (int64_t)0)
+__host__ __device__ inline int64_t red_stride(int maxB) { return 2 * (int64_t)(maxB > 128 ? maxB : 128); }
+
+// slabs of a channel reduction over M = N*S elements per channel
+__host__ __device__ inline int red_slabs(int64_t M) {
+    int64_t np = (M + RED_CHUNK - 1) / RED_CHUNK;
+    return (int)(np < 1 ? 1 : np);
+}
+__host__ __device__ inline int wg_slabs(int64_t P) {   // at most 4096 slabs (the grid's y extent), longer ones on large grids
+    int64_t ns = (P + WG_CHUNK - 1) / WG_CHUNK;
+    return (int)(ns < 1 ? 1 : ns > 4096 ? 4096 : ns);
+}
+__host__ __device__ inline int tmix_blocks(int64_t n) {   // workgroups (= weight-gradient slabs) of k_tmix_bwd over n positions
+    int64_t nb = (n + 4 * BLK - 1) / (4 * BLK);
+    return (int)(nb < 1 ? 1 : nb > TMIX_BLOCKS_MAX ? TMIX_BLOCKS_MAX : nb);
+}
+
 // ------------------------------------------------------------------------------------------------ kernels
 // u8 [B][T*H][W][4] -> clip(x, 0, 6) / 6 of bytes 0..2, [B][3][T][H][W]
-__global__ void k_input(const uint8_t *__restrict__ st, float *__restrict__ x, int B, int H, int W) {
+template <bool SET>
+__global__ void k_input(Mdl md, const uint8_t *__restrict__ st, float *__restrict__ x, int H, int W) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t hw = (int64_t)H * W, n = (int64_t)B * 3 * TT * hw;
     if (i >= n) return;
+    st += (int64_t)model_first<SET>(md) * TT * hw * 4;
+    x += MOFF(3 * TT * hw);
     const int64_t s = i % hw;
     const int t = (int)((i / hw) % TT), ch = (int)((i / (hw * TT)) % 3);
     const int64_t b = i / (hw * TT * 3);
@@ -61,11 +134,17 @@ __global__ void k_input(const uint8_t *__restrict__ st, float *__restrict__ x, i
 }
 
 // conv 3x3 "same" + bias + ReLU per (b, t) slice; k: Keras [3][3][Ci][Co]
-__global__ void k_conv3_fwd(const float *__restrict__ x, const float *__restrict__ k, const float *__restrict__ bias,
-                            float *__restrict__ out, int B, int Ci, int Co, int H, int W) {
+template <bool SET>
+__global__ void k_conv3_fwd(Mdl md, const float *__restrict__ x, const float *__restrict__ k, const float *__restrict__ bias,
+                            float *__restrict__ out, int Ci, int Co, int H, int W) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t hw = (int64_t)H * W, n = (int64_t)B * Co * TT * hw;
     if (i >= n) return;
+    x += MOFF(Ci * TT * hw);
+    out += MOFF(Co * TT * hw);
+    k += POFF;
+    bias += POFF;
     const int xx = (int)(i % W), yy = (int)((i / W) % H);
     const int t = (int)((i / hw) % TT), co = (int)((i / (hw * TT)) % Co);
     const int64_t b = i / (hw * TT * Co);
@@ -86,11 +165,16 @@ __global__ void k_conv3_fwd(const float *__restrict__ x, const float *__restrict
 }
 
 // dX of the conv: dx[b][ci][t][y][x] = sum dA[b][co][t][y-ky+1][x-kx+1] * k[ky][kx][ci][co]
-__global__ void k_conv3_dgrad(const float *__restrict__ dA, const float *__restrict__ k, float *__restrict__ dx, int B, int Ci,
+template <bool SET>
+__global__ void k_conv3_dgrad(Mdl md, const float *__restrict__ dA, const float *__restrict__ k, float *__restrict__ dx, int Ci,
                               int Co, int H, int W) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t hw = (int64_t)H * W, n = (int64_t)B * Ci * TT * hw;
     if (i >= n) return;
+    dA += MOFF(Co * TT * hw);
+    dx += MOFF(Ci * TT * hw);
+    k += POFF;
     const int xx = (int)(i % W), yy = (int)((i / W) % H);
     const int t = (int)((i / hw) % TT), ci = (int)((i / (hw * TT)) % Ci);
     const int64_t b = i / (hw * TT * Ci);
@@ -110,14 +194,22 @@ __global__ void k_conv3_dgrad(const float *__restrict__ dA, const float *__restr
     dx[i] = acc;
 }
 
-// dK slabs of the conv: slab s covers positions [s*chunk, (s+1)*chunk) of the B*T*H*W positions; one thread per weight
-__global__ void k_conv3_wgrad(const float *__restrict__ dA, const float *__restrict__ x, float *__restrict__ slab, int B, int Ci,
-                              int Co, int H, int W, int64_t chunk) {
+// dK slabs of the conv: slab s covers positions [s*chunk, (s+1)*chunk) of the B*T*H*W positions; one thread per weight.
+// The slab count and chunk follow the model's own batch (wg_slabs of its positions).
+template <bool SET>
+__global__ void k_conv3_wgrad(Mdl md, const float *__restrict__ dA, const float *__restrict__ x, float *__restrict__ slab, int Ci,
+                              int Co, int H, int W, int64_t solo_chunk) {
+    const int B = model_b<SET>(md);
     const int nw = 9 * Ci * Co;
     const int wi = blockIdx.x * BLK + threadIdx.x;
-    if (wi >= nw) return;
-    const int co = wi % Co, ci = (wi / Co) % Ci, kk = wi / (Co * Ci), ky = kk / 3, kx = kk % 3;
     const int64_t hw = (int64_t)H * W, P = (int64_t)B * TT * hw;
+    const int ns = wg_slabs(P);
+    if (B == 0 || (int)blockIdx.y >= ns || wi >= nw) return;
+    const int64_t chunk = SET ? uniform64((P + ns - 1) / ns) : solo_chunk;
+    dA += MOFF(Co * TT * hw);
+    x += MOFF(Ci * TT * hw);
+    slab += blockIdx.z * md.slab_stride;
+    const int co = wi % Co, ci = (wi / Co) % Ci, kk = wi / (Co * Ci), ky = kk / 3, kx = kk % 3;
     const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
     float acc = 0.f;
     for (int64_t p = p0; p < p1; p++) {
@@ -130,10 +222,16 @@ __global__ void k_conv3_wgrad(const float *__restrict__ dA, const float *__restr
     slab[(int64_t)blockIdx.y * nw + wi] = acc;
 }
 
-// out[i] = sum over slabs s of slab[s][i], in slab order
-__global__ void k_sum_slabs(const float *__restrict__ slab, int nslab, int n, float *__restrict__ out) {
+// out[i] = sum over slabs s of slab[s][i], in slab order.  The model's slab count: wg_slabs (tmix: tmix_blocks) of its batch
+// times `per` positions per sample.
+template <bool SET>
+__global__ void k_sum_slabs(Mdl md, const float *__restrict__ slab, int64_t per, int tmix, int n, float *__restrict__ out) {
+    const int B = model_b<SET>(md);
     const int i = blockIdx.x * BLK + threadIdx.x;
-    if (i >= n) return;
+    if (B == 0 || i >= n) return;
+    const int nslab = tmix ? tmix_blocks(B * per) : wg_slabs(B * per);
+    slab += blockIdx.z * md.slab_stride;
+    out += POFF;
     float acc = 0.f;
     for (int s = 0; s < nslab; s++) acc += slab[(int64_t)s * n + i];
     out[i] = acc;
@@ -141,12 +239,23 @@ __global__ void k_sum_slabs(const float *__restrict__ slab, int nslab, int n, fl
 
 // Per-channel reductions of a [N][C][S] tensor: slab p of channel c covers elements [p*chunk, (p+1)*chunk) of its N*S.
 enum RedMode { R_SUM = 0, R_SQDEV = 1, R_BNBWD = 2, R_FINALW = 3, R_LOSS = 4 };
-__global__ void k_reduce(int mode, int N, int C, int64_t S, const float *__restrict__ x, const float *__restrict__ g, int Cg,
-                         const float *__restrict__ aux, const uint8_t *__restrict__ gt, float *__restrict__ part, int NP,
-                         int64_t chunk) {
+// N = the model's batch and C = Cc, but for R_LOSS, where N = 1 and C = the model's batch (Cc: the grid's y extent).
+template <bool SET>
+__global__ void k_reduce(Mdl md, int mode, int Cc, int64_t S, const float *__restrict__ x, const float *__restrict__ g, int Cg,
+                         const float *__restrict__ aux, const uint8_t *__restrict__ gt, float *__restrict__ part, int64_t solo_chunk) {
     __shared__ float sa[BLK], sb[BLK];
+    const int Bm = model_b<SET>(md);
+    const int N = mode == R_LOSS ? 1 : Bm, C = mode == R_LOSS ? Bm : Cc;
     const int c = blockIdx.y, p = blockIdx.x;
     const int64_t M = (int64_t)N * S;
+    const int NP = red_slabs(M);
+    if (Bm == 0 || c >= C || p >= NP) return;
+    const int64_t chunk = SET ? uniform64((M + NP - 1) / NP) : solo_chunk;
+    x += MOFF(mode == R_LOSS ? S : Cc * S);
+    if (g) g += MOFF(Cg * S);
+    if (aux) aux += blockIdx.z * STAT_STRIDE;
+    if (gt) gt += (int64_t)model_first<SET>(md) * S;
+    part += blockIdx.z * md.slab_stride;
     const int64_t e0 = (int64_t)p * chunk, e1 = e0 + chunk < M ? e0 + chunk : M;
     float a = 0.f, bsum = 0.f;
     for (int64_t e = e0 + threadIdx.x; e < e1; e += BLK) {
@@ -191,10 +300,24 @@ enum FinMode { F_MEAN = 0, F_VAR = 1, F_SUM2 = 2, F_SUM = 3 };
 // gradients).  F_SUM: g0 = sum a.
 // The slabs are summed in double: a channel of a large batch has over a thousand of them (1,125 at encoder level 0 of 45x80 at
 // batch 320), and a float running sum over that many moves the batch statistics far enough to flip ReLU / max-pool decisions.
-__global__ void k_finalize(int mode, int C, int NP, const float *__restrict__ part, double M, float *stat, float *g0, float *g1,
-                           float *mov0, float *mov1, float mom, float eps) {
+// lossmode: the slabs of k_reduce(R_LOSS) (C = the model's batch, one sample per "channel").  stat is a model's BN statistics
+// or its `red` block (stat_stride floats per model); g0 / g1 / mov0 / mov1 point into gradients / parameters.
+template <bool SET>
+__global__ void k_finalize(Mdl md, int mode, int lossmode, int Cc, int64_t S, const float *__restrict__ part, float *stat,
+                           int64_t stat_stride, float *g0, float *g1, float *mov0, float *mov1, float mom, float eps) {
+    const int Bm = model_b<SET>(md);
+    const int C = lossmode ? Bm : Cc;
     const int c = blockIdx.x * BLK + threadIdx.x;
-    if (c >= C) return;
+    if (Bm == 0 || c >= C) return;
+    const int64_t Mi = (int64_t)(lossmode ? 1 : Bm) * S;
+    const int NP = red_slabs(Mi);
+    const double M = (double)Mi;
+    part += blockIdx.z * md.slab_stride;
+    if (stat) stat += blockIdx.z * stat_stride;
+    if (g0) g0 += POFF;
+    if (g1) g1 += POFF;
+    if (mov0) mov0 += POFF;
+    if (mov1) mov1 += POFF;
     double a = 0.0, b = 0.0;
     for (int p = 0; p < NP; p++) {
         a += part[((int64_t)c * NP + p) * 2];
@@ -221,12 +344,20 @@ __global__ void k_finalize(int mode, int C, int NP, const float *__restrict__ pa
 
 // BN apply + 2x2 max-pool (valid) + zero row on top / column on the left for odd sizes, with the window argmax (first maximum in
 // row-major order; -1 on pad positions).  c: [B][C][T][H][W] -> p: [B][C][T][Hp][Wp]
-__global__ void k_bn_pool(const float *__restrict__ c, const float *__restrict__ stat, const float *__restrict__ gamma,
-                          const float *__restrict__ beta, float *__restrict__ p, int8_t *__restrict__ arg, int B, int C, int H, int W,
+template <bool SET>
+__global__ void k_bn_pool(Mdl md, const float *__restrict__ c, const float *__restrict__ stat, const float *__restrict__ gamma,
+                          const float *__restrict__ beta, float *__restrict__ p, int8_t *__restrict__ arg, int C, int H, int W,
                           int Hp, int Wp) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t hwp = (int64_t)Hp * Wp, n = (int64_t)B * C * TT * hwp;
     if (i >= n) return;
+    c += MOFF(C * TT * H * W);
+    p += MOFF(C * TT * hwp);
+    arg += MOFF(C * TT * hwp);
+    stat += blockIdx.z * STAT_STRIDE;
+    gamma += POFF;
+    beta += POFF;
     const int px = (int)(i % Wp), py = (int)((i / Wp) % Hp);
     const int64_t bct = i / hwp;
     const int ch = (int)((bct / TT) % C);
@@ -249,11 +380,16 @@ __global__ void k_bn_pool(const float *__restrict__ c, const float *__restrict__
 }
 
 // gradient of the pool: each pre-pool element takes its window's gradient if it was the argmax; dropped rows / columns get 0
-__global__ void k_pool_bwd(const float *__restrict__ dp, const int8_t *__restrict__ arg, float *__restrict__ dn, int B, int C, int H,
+template <bool SET>
+__global__ void k_pool_bwd(Mdl md, const float *__restrict__ dp, const int8_t *__restrict__ arg, float *__restrict__ dn, int C, int H,
                            int W, int Hp, int Wp) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t hw = (int64_t)H * W, n = (int64_t)B * C * TT * hw;
     if (i >= n) return;
+    dp += MOFF(C * TT * Hp * Wp);
+    arg += MOFF(C * TT * Hp * Wp);
+    dn += MOFF(C * TT * hw);
     const int xx = (int)(i % W), yy = (int)((i / W) % H);
     const int64_t bct = i / hw;
     const int pt = H & 1, pl = W & 1;
@@ -268,12 +404,20 @@ __global__ void k_pool_bwd(const float *__restrict__ dp, const int8_t *__restric
 // BN backward apply: out = gamma * invstd / M * (M * g - sum g - xhat * sum g*xhat), times (x > 0) when relu_in (the BN input is
 // the post-ReLU conv output).  g has Cg channels per sample (a channel range of a concat buffer), out has C.  g and out may be
 // the same buffer (the encoder runs it in place: each thread reads its own element before it writes it), so neither is restrict.
-__global__ void k_bn_bwd(const float *g, int Cg, const float *__restrict__ x, const float *__restrict__ stat,
-                         const float *__restrict__ red, const float *__restrict__ gamma, float *out, int B, int C,
+template <bool SET>
+__global__ void k_bn_bwd(Mdl md, const float *g, int Cg, const float *__restrict__ x, const float *__restrict__ stat,
+                         const float *__restrict__ red, const float *__restrict__ gamma, float *out, int C,
                          int64_t S, int relu_in) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t n = (int64_t)B * C * S;
     if (i >= n) return;
+    g += MOFF(Cg * S);
+    x += MOFF(C * S);
+    out += MOFF(C * S);
+    stat += blockIdx.z * STAT_STRIDE;
+    red += blockIdx.z * red_stride(md.maxB);
+    gamma += POFF;
     const int64_t s = i % S;
     const int ch = (int)((i / S) % C);
     const int64_t b = i / (S * C);
@@ -288,12 +432,20 @@ __global__ void k_bn_bwd(const float *g, int Cg, const float *__restrict__ x, co
 
 // PointWiseTN forward per (b, c, y, x): o = relu(drop(relu(drop(relu(p @ w1)) @ w2)) + p); the t = 0 slice also goes to the
 // decoder's concat buffer (channel c_off + c of Ctot).  Dropout indices: NCTHW of the layer's output.
-__global__ void k_tmix_fwd(const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
-                           float *__restrict__ e, float *__restrict__ skip, int Ctot, int c_off, int B, int C, int64_t hw, Drop d1,
-                           Drop d2) {
+template <bool SET>
+__global__ void k_tmix_fwd(Mdl md, const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
+                           float *__restrict__ e, float *__restrict__ skip, int Ctot, int c_off, int C, int64_t hw, DropS s1,
+                           DropS s2) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t n = (int64_t)B * C * hw;
     if (i >= n) return;
+    const Drop d1 = model_drop<SET>(md, s1), d2 = model_drop<SET>(md, s2);
+    p += MOFF(C * TT * hw);
+    e += MOFF(C * TT * hw);
+    if (skip) skip += MOFF(Ctot * hw);
+    w1 += POFF;
+    w2 += POFF;
     const int64_t s = i % hw, bc = i / hw;
     float pv[TT], u[TT], v[TT];
     for (int t = 0; t < TT; t++) pv[t] = p[(bc * TT + t) * hw + s];
@@ -316,13 +468,26 @@ __global__ void k_tmix_fwd(const float *__restrict__ p, const float *__restrict_
 
 // PointWiseTN backward: recomputes the forward from p, takes de (full T, may be null) plus the concat buffer's gradient of the
 // t = 0 slice (dskip, may be null), writes dp and one slab of the 32 weight gradients (w1 then w2) per workgroup.
-__global__ void k_tmix_bwd(const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
+template <bool SET>
+__global__ void k_tmix_bwd(Mdl md, const float *__restrict__ p, const float *__restrict__ w1, const float *__restrict__ w2,
                            const float *__restrict__ de, const float *__restrict__ dskip, int Ctot, int c_off, float *__restrict__ dp,
-                           float *__restrict__ slab, int B, int C, int64_t hw, int64_t chunk, Drop d1, Drop d2) {
+                           float *__restrict__ slab, int C, int64_t hw, int64_t solo_chunk, DropS s1, DropS s2) {
     __shared__ float red[32][BLK + 1];
+    const int B = model_b<SET>(md);
+    const int64_t n = (int64_t)B * C * hw;
+    const int nb = tmix_blocks(n);   // the model's own split of its n positions
+    if (B == 0 || (int)blockIdx.x >= nb) return;
+    const int64_t chunk = SET ? uniform64((n + nb - 1) / nb) : solo_chunk;
+    const Drop d1 = model_drop<SET>(md, s1), d2 = model_drop<SET>(md, s2);
+    p += MOFF(C * TT * hw);
+    dp += MOFF(C * TT * hw);
+    if (de) de += MOFF(C * TT * hw);
+    if (dskip) dskip += MOFF(Ctot * hw);
+    slab += blockIdx.z * md.slab_stride;
+    w1 += POFF;
+    w2 += POFF;
     float gw[32];
     for (int q = 0; q < 32; q++) gw[q] = 0.f;
-    const int64_t n = (int64_t)B * C * hw;
     const int64_t i0 = (int64_t)blockIdx.x * chunk, i1 = i0 + chunk < n ? i0 + chunk : n;
     for (int64_t i = i0 + threadIdx.x; i < i1; i += BLK) {
         const int64_t s = i % hw, bc = i / hw;
@@ -382,18 +547,29 @@ __global__ void k_tmix_bwd(const float *__restrict__ p, const float *__restrict_
 }
 
 // decoder block input: zd = dropout(relu(z)), index = NCHW of z
-__global__ void k_drop_relu(const float *__restrict__ z, float *__restrict__ zd, int64_t n, Drop d) {
+template <bool SET>
+__global__ void k_drop_relu(Mdl md, const float *__restrict__ z, float *__restrict__ zd, int64_t per, DropS ds) {
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = model_b<SET>(md) * per;
     if (i >= n) return;
+    const Drop d = model_drop<SET>(md, ds);
+    z += MOFF(per);
+    zd += MOFF(per);
     zd[i] = fmaxf(z[i], 0.f) * keep(d, (uint64_t)i);
 }
 
 // convT 4x4 stride 2 (valid, output 2*in + 2) + bias, cropped at (cy, cx); K: Keras [4][4][Co][Ci]
-__global__ void k_convT_fwd(const float *__restrict__ zd, const float *__restrict__ K, const float *__restrict__ bias,
-                            float *__restrict__ y, int B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx) {
+template <bool SET>
+__global__ void k_convT_fwd(Mdl md, const float *__restrict__ zd, const float *__restrict__ K, const float *__restrict__ bias,
+                            float *__restrict__ y, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t n = (int64_t)B * Co * Ho * Wo;
     if (i >= n) return;
+    zd += MOFF(Ci * Hi * Wi);
+    y += MOFF(Co * Ho * Wo);
+    K += POFF;
+    bias += POFF;
     const int ox = (int)(i % Wo) + cx, oy = (int)((i / Wo) % Ho) + cy;
     const int co = (int)((i / ((int64_t)Ho * Wo)) % Co);
     const int64_t b = i / ((int64_t)Ho * Wo * Co);
@@ -413,11 +589,18 @@ __global__ void k_convT_fwd(const float *__restrict__ zd, const float *__restric
 }
 
 // gradient of the block input z: convT data gradient times the dropout mask and relu(z)'
-__global__ void k_convT_dgrad(const float *__restrict__ dy, const float *__restrict__ K, const float *__restrict__ z,
-                              float *__restrict__ dz, int B, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, Drop d) {
+template <bool SET>
+__global__ void k_convT_dgrad(Mdl md, const float *__restrict__ dy, const float *__restrict__ K, const float *__restrict__ z,
+                              float *__restrict__ dz, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, DropS ds) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t n = (int64_t)B * Ci * Hi * Wi;
     if (i >= n) return;
+    const Drop d = model_drop<SET>(md, ds);
+    dy += MOFF(Co * Ho * Wo);
+    z += MOFF(Ci * Hi * Wi);
+    dz += MOFF(Ci * Hi * Wi);
+    K += POFF;
     const float m = z[i] > 0.f ? keep(d, (uint64_t)i) : 0.f;
     if (m == 0.f) {
         dz[i] = 0.f;
@@ -442,13 +625,20 @@ __global__ void k_convT_dgrad(const float *__restrict__ dy, const float *__restr
 }
 
 // dK slabs of the convT: one thread per weight [ky][kx][co][ci], slab = a range of the B*Hi*Wi input positions
-__global__ void k_convT_wgrad(const float *__restrict__ zd, const float *__restrict__ dy, float *__restrict__ slab, int B, int Ci,
-                              int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, int64_t chunk) {
+template <bool SET>
+__global__ void k_convT_wgrad(Mdl md, const float *__restrict__ zd, const float *__restrict__ dy, float *__restrict__ slab, int Ci,
+                              int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx, int64_t solo_chunk) {
+    const int B = model_b<SET>(md);
     const int nw = 16 * Co * Ci;
     const int wi = blockIdx.x * BLK + threadIdx.x;
-    if (wi >= nw) return;
-    const int ci = wi % Ci, co = (wi / Ci) % Co, kk = wi / (Ci * Co), ky = kk / 4, kx = kk % 4;
     const int64_t hwi = (int64_t)Hi * Wi, P = (int64_t)B * hwi;
+    const int ns = wg_slabs(P);
+    if (B == 0 || (int)blockIdx.y >= ns || wi >= nw) return;
+    const int64_t chunk = SET ? uniform64((P + ns - 1) / ns) : solo_chunk;
+    zd += MOFF(Ci * hwi);
+    dy += MOFF(Co * Ho * Wo);
+    slab += blockIdx.z * md.slab_stride;
+    const int ci = wi % Ci, co = (wi / Ci) % Co, kk = wi / (Ci * Co), ky = kk / 4, kx = kk % 4;
     const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
     float acc = 0.f;
     for (int64_t p = p0; p < p1; p++) {
@@ -462,11 +652,18 @@ __global__ void k_convT_wgrad(const float *__restrict__ zd, const float *__restr
 }
 
 // decoder BN apply into channels [0, C) of the next block's concat buffer (Ctot channels)
-__global__ void k_bn_apply(const float *__restrict__ y, const float *__restrict__ stat, const float *__restrict__ gamma,
-                           const float *__restrict__ beta, float *__restrict__ z, int Ctot, int B, int C, int64_t S) {
+template <bool SET>
+__global__ void k_bn_apply(Mdl md, const float *__restrict__ y, const float *__restrict__ stat, const float *__restrict__ gamma,
+                           const float *__restrict__ beta, float *__restrict__ z, int Ctot, int C, int64_t S) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     const int64_t n = (int64_t)B * C * S;
     if (i >= n) return;
+    y += MOFF(C * S);
+    z += MOFF(Ctot * S);
+    stat += blockIdx.z * STAT_STRIDE;
+    gamma += POFF;
+    beta += POFF;
     const int64_t s = i % S;
     const int ch = (int)((i / S) % C);
     const int64_t b = i / (S * C);
@@ -474,10 +671,16 @@ __global__ void k_bn_apply(const float *__restrict__ y, const float *__restrict_
 }
 
 // 1x1 conv 16 -> 1 of the last block's output: logits [B][H*W]
-__global__ void k_final_fwd(const float *__restrict__ y, const float *__restrict__ fk, const float *__restrict__ fb,
-                            float *__restrict__ logit, int B, int64_t hw) {
+template <bool SET>
+__global__ void k_final_fwd(Mdl md, const float *__restrict__ y, const float *__restrict__ fk, const float *__restrict__ fb,
+                            float *__restrict__ logit, int64_t hw) {
+    const int B = model_b<SET>(md);
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
     if (i >= (int64_t)B * hw) return;
+    y += MOFF(16 * hw);
+    logit += MOFF(hw);
+    fk += POFF;
+    fb += POFF;
     const int64_t b = i / hw, s = i % hw;
     float acc = fb[0];
     for (int c = 0; c < 16; c++) acc += y[(b * 16 + c) * hw + s] * fk[c];
@@ -485,8 +688,12 @@ __global__ void k_final_fwd(const float *__restrict__ y, const float *__restrict
 }
 
 // loss = mean over samples of (1 - (I + sm) / (S - I + sm)) * sm; red = [I per sample][S per sample]
-__global__ void k_loss(const float *__restrict__ red, int B, float sm, float *__restrict__ loss) {
-    if (threadIdx.x || blockIdx.x) return;
+template <bool SET>
+__global__ void k_loss(Mdl md, const float *__restrict__ red, float sm, float *__restrict__ loss) {
+    const int B = model_b<SET>(md);
+    if (threadIdx.x || blockIdx.x || B == 0) return;
+    red += blockIdx.z * red_stride(md.maxB);
+    loss += blockIdx.z;
     float acc = 0.f;
     for (int b = 0; b < B; b++) {
         const float I = red[b], S = red[B + b];
@@ -496,10 +703,20 @@ __global__ void k_loss(const float *__restrict__ red, int B, float sm, float *__
 }
 
 // d loss / d logit and d loss / d y3 (= dlogit * final kernel); TP / FP / FN counts at sigmoid > 0.5 (integer atomics)
-__global__ void k_final_bwd(const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
-                            const float *__restrict__ fk, float *__restrict__ dlogit, float *__restrict__ dy, int B, int64_t hw,
+template <bool SET>
+__global__ void k_final_bwd(Mdl md, const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
+                            const float *__restrict__ fk, float *__restrict__ dlogit, float *__restrict__ dy, int64_t hw,
                             float sm, unsigned long long *__restrict__ counts) {
     __shared__ unsigned cnt[3];
+    const int B = model_b<SET>(md);
+    if ((int64_t)blockIdx.x * BLK >= (int64_t)B * hw) return;   // the whole workgroup: before the barrier
+    logit += MOFF(hw);
+    dlogit += MOFF(hw);
+    dy += MOFF(16 * hw);
+    gt += (int64_t)model_first<SET>(md) * hw;
+    red += blockIdx.z * red_stride(md.maxB);
+    fk += POFF;
+    counts += 3 * blockIdx.z;
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
@@ -524,10 +741,16 @@ __global__ void k_final_bwd(const float *__restrict__ logit, const uint8_t *__re
 }
 
 // Keras Adam over the flat parameter buffer; lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) from the host
-__global__ void k_adam(float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
-                       const uint8_t *__restrict__ trainable, int n, float lr_t, float b1, float b2, float eps) {
+template <bool SET>
+__global__ void k_adam(Mdl md, float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                       const uint8_t *__restrict__ trainable, int n, float b1, float b2, float eps) {
     const int i = blockIdx.x * BLK + threadIdx.x;
-    if (i >= n || !trainable[i]) return;
+    if (model_b<SET>(md) == 0 || i >= n || !trainable[i]) return;
+    const float lr_t = model_lr_t<SET>(md);
+    w += POFF;
+    g += POFF;
+    m += POFF;
+    v += POFF;
     const float gi = g[i];
     const float mi = b1 * m[i] + (1.f - b1) * gi;
     const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
@@ -545,29 +768,35 @@ struct DecOff { size_t k, b, gamma, beta, mean, var; };
 struct covahip_train {
     covahip_ctx *ctx = nullptr;
     covahip_train_cfg cfg{};
+    int K = 1;                 // models; model m's slice of every buffer below lies m * max_batch samples (m * N_PARAMS for
+                               // params / grads / adam_*) behind model 0's
     int H[NL + 1], W[NL + 1];
     int cy[NL], cx[NL];
     EncOff eo[NL];
     DecOff dof[NL];
     size_t fk = 0, fb = 0;
-    int64_t step = 0;          // steps taken (Adam's t - 1, the dropout hash's step)
+    std::vector<int64_t> step;         // per model: steps taken (Adam's t - 1, the dropout hash's step)
+    std::vector<uint64_t> seed;        // per model: dropout seed
+    std::vector<long long> last_counts;   // per model: TP, FP, FN of its last step
     std::vector<void *> allocs;
     float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
-    uint8_t *trainable = nullptr;
+    uint8_t *trainable = nullptr;      // one mask for all models
     // activations ([B][C][T][H][W] encoder, [B][C][H][W] decoder) and their gradients
     float *x0 = nullptr, *c[NL] = {}, *p[NL] = {}, *e[NL] = {};
     int8_t *arg[NL] = {};
     float *z[NL] = {}, *zd[NL] = {}, *y[NL] = {}, *logit = nullptr;
     float *dc[NL] = {}, *dp[NL] = {}, *de[NL] = {}, *dz[NL] = {}, *dy[NL] = {}, *dlogit = nullptr;
-    float *stat = nullptr;     // [7 BN layers][2][128]: mean, invstd
-    float *red = nullptr;      // [2][max(128, max_batch)]: BN backward sums / per-sample loss sums
-    float *slab = nullptr;
+    float *stat = nullptr;     // per model [7 BN layers][2][128]: mean, invstd
+    float *red = nullptr;      // per model [2][max(128, max_batch)]: BN backward sums / per-sample loss sums
+    float *slab = nullptr;     // per model slab_floats
     size_t slab_floats = 0;
-    float *d_loss = nullptr;
-    unsigned long long *d_counts = nullptr;
-    uint8_t *d_stack = nullptr, *d_gt = nullptr;
-    float *h_out = nullptr;    // pinned: loss + counts
-    long long last_counts[3] = {0, 0, 0};
+    float *d_loss = nullptr;                  // [K]
+    unsigned long long *d_counts = nullptr;   // [K][3]
+    uint8_t *d_stack = nullptr, *d_gt = nullptr;   // packed: the step's samples, model 0's first
+    MStep *d_tab = nullptr;    // [K]
+    MStep *h_tab = nullptr;    // pinned
+    float *h_loss = nullptr;   // pinned [K]
+    unsigned long long *h_counts = nullptr;   // pinned [K][3]
 };
 
 namespace {
@@ -583,7 +812,9 @@ int talloc(covahip_train *tr, T **p, size_t n) {
 
 void free_train(covahip_train *tr) {
     for (void *q : tr->allocs) hipFree(q);
-    if (tr->h_out) hipHostFree(tr->h_out);
+    if (tr->h_tab) hipHostFree(tr->h_tab);
+    if (tr->h_loss) hipHostFree(tr->h_loss);
+    if (tr->h_counts) hipHostFree(tr->h_counts);
     delete tr;
 }
 
@@ -617,28 +848,28 @@ void layout(covahip_train *tr) {
     tr->fb = off; off += 1;
 }
 
-Drop make_drop(const covahip_train *tr, int site) {
+DropS make_drop(const covahip_train *tr, int site) {
     const double p = tr->cfg.dropout;
-    Drop d;
-    d.key = drop_key(tr->cfg.seed, (uint64_t)tr->step, site);
+    DropS d;
+    d.site = site;
+    d.key = tr->h_tab[0].key[site];   // read by the kernels of a set of one only
     d.thr = (uint32_t)std::llround(p * 16777216.0);
     d.scale = (float)(1.0 / (1.0 - p));
     return d;
 }
 
-// slabs of a channel reduction over N*S elements per channel
-inline int red_slabs(int64_t M) {
-    int64_t np = (M + RED_CHUNK - 1) / RED_CHUNK;
-    return (int)(np < 1 ? 1 : np);
-}
-inline int wg_slabs(int64_t P) {   // at most 4096 slabs (the grid's y extent), longer ones on large grids
-    int64_t ns = (P + WG_CHUNK - 1) / WG_CHUNK;
-    return (int)(ns < 1 ? 1 : ns > 4096 ? 4096 : ns);
-}
+// launch the set or the solo instantiation of kernel k
+#define KL(k, grid, block, ...)                                     \
+    do {                                                            \
+        if (tr->K > 1) k<true><<<grid, block, 0, s>>>(__VA_ARGS__); \
+        else k<false><<<grid, block, 0, s>>>(__VA_ARGS__);          \
+    } while (0)
 
 struct Run {
     covahip_train *tr;
     hipStream_t s;
+    Mdl md;
+    int B;   // the step's largest batch: sizes the grids
     int rc = COVAHIP_OK;
     bool ok() {
         if (rc) return false;
@@ -649,73 +880,81 @@ struct Run {
         }
         return rc == COVAHIP_OK;
     }
-    // per-channel reduction of [N][C][S] + finalize
-    void reduce(int mode, int N, int C, int64_t S, const float *x, const float *g, int Cg, const float *aux, const uint8_t *gt,
-                int fmode, float *stat, float *g0, float *g1, float *mov0, float *mov1) {
-        const int64_t M = (int64_t)N * S;
+    dim3 g1(int64_t n) const { return dim3(nblk(n), 1, tr->K); }
+    // per-channel reduction of [b][C][S] (R_LOSS: [1][b][S]) + finalize; every model splits by its own batch in the kernels
+    void reduce(int mode, int C, int64_t S, const float *x, const float *g, int Cg, const float *aux, const uint8_t *gt,
+                int fmode, float *stat, int64_t stat_stride, float *g0, float *g1_, float *mov0, float *mov1) {
+        const int loss = mode == R_LOSS;
+        const int Cmax = loss ? B : C;
+        const int64_t M = (int64_t)(loss ? 1 : B) * S;
         const int NP = red_slabs(M);
-        const int64_t chunk = (M + NP - 1) / NP;
-        k_reduce<<<dim3(NP, C), BLK, 0, s>>>(mode, N, C, S, x, g, Cg, aux, gt, tr->slab, NP, chunk);
-        k_finalize<<<nblk(C), BLK, 0, s>>>(fmode, C, NP, tr->slab, (double)M, stat, g0, g1, mov0, mov1, tr->cfg.bn_momentum,
-                                           tr->cfg.bn_eps);
+        KL(k_reduce, (dim3(NP, Cmax, tr->K)), BLK, md, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP);
+        KL(k_finalize, (g1(Cmax)), BLK, md, fmode, loss, Cmax, S, tr->slab, stat, stat_stride, g0, g1_, mov0, mov1,
+                                           tr->cfg.bn_momentum, tr->cfg.bn_eps);
     }
 };
 
-int run_step(covahip_train *tr, int B, float lr) {
-    Run r{tr, tr->ctx->stream};
+// One step of every model with a non-zero batch in tr->h_tab (K > 1: already uploaded to d_tab); B = the largest batch.
+int run_step(covahip_train *tr, int B) {
+    Run r{tr, tr->ctx->stream,
+          Mdl{tr->K > 1 ? tr->d_tab : nullptr, tr->cfg.max_batch, (int64_t)tr->slab_floats, tr->h_tab[0].b, tr->h_tab[0].lr_t}, B};
     const hipStream_t s = r.s;
+    const Mdl md = r.md;
+    const int K = tr->K;
     float *P = tr->params, *G = tr->grads;
     const int H0 = tr->H[0], W0 = tr->W[0];
     const float sm = tr->cfg.smooth;
+    const int64_t RS = red_stride(tr->cfg.max_batch);
     auto stat = [&](int layer) { return tr->stat + layer * 256; };
-    if (hipMemsetAsync(tr->d_counts, 0, 3 * sizeof(unsigned long long), s) != hipSuccess) return COVAHIP_ERR_HIP;
+    if (hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), s) != hipSuccess) return COVAHIP_ERR_HIP;
 
     // ---------------------------------------------------------------- forward
-    k_input<<<nblk((int64_t)B * 3 * TT * H0 * W0), BLK, 0, s>>>(tr->d_stack, tr->x0, B, H0, W0);
+    KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
     for (int i = 0; i < NL; i++) {
         const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
         const EncOff &o = tr->eo[i];
         const float *xin = i ? tr->e[i - 1] : tr->x0;
         const int64_t S = (int64_t)TT * H * W;
-        k_conv3_fwd<<<nblk(B * Co * S), BLK, 0, s>>>(xin, P + o.k, P + o.b, tr->c[i], B, Ci, Co, H, W);
-        r.reduce(R_SUM, B, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), nullptr, nullptr, nullptr, nullptr);
-        r.reduce(R_SQDEV, B, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), G + o.mean, G + o.var, P + o.mean,
+        KL(k_conv3_fwd, (r.g1(B * Co * S)), BLK, md, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
+        r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
+        r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
                  P + o.var);
-        k_bn_pool<<<nblk((int64_t)B * Co * TT * Hp * Wp), BLK, 0, s>>>(tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
-                                                                      B, Co, H, W, Hp, Wp);
+        KL(k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, md, tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
+                                                                      Co, H, W, Hp, Wp);
         const int zj = NL - 1 - i;   // the decoder block whose input concat holds this level's t = 0 slice
         const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
-        k_tmix_fwd<<<nblk((int64_t)B * Co * Hp * Wp), BLK, 0, s>>>(tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
-                                                                 B, Co, (int64_t)Hp * Wp, make_drop(tr, 2 * i), make_drop(tr, 2 * i + 1));
+        KL(k_tmix_fwd, (r.g1((int64_t)B * Co * Hp * Wp)), BLK, md, tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
+                                                                 Co, (int64_t)Hp * Wp, make_drop(tr, 2 * i), make_drop(tr, 2 * i + 1));
         if (!r.ok()) return r.rc;
     }
     for (int j = 0; j < NL; j++) {
         const int Ci = DEC_CI[j], Co = DEC_CO[j];
         const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
         const DecOff &o = tr->dof[j];
-        const int64_t nin = (int64_t)B * Ci * Hi * Wi, So = (int64_t)Ho * Wo;
-        k_drop_relu<<<nblk(nin), BLK, 0, s>>>(tr->z[j], tr->zd[j], nin, make_drop(tr, 2 * NL + j));
-        k_convT_fwd<<<nblk(B * Co * So), BLK, 0, s>>>(tr->zd[j], P + o.k, P + o.b, tr->y[j], B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+        const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
+        KL(k_drop_relu, (r.g1(B * per)), BLK, md, tr->z[j], tr->zd[j], per, make_drop(tr, 2 * NL + j));
+        KL(k_convT_fwd, (r.g1(B * Co * So)), BLK, md, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
                                                       tr->cx[j]);
         if (j < NL - 1) {
-            r.reduce(R_SUM, B, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), nullptr, nullptr, nullptr, nullptr);
-            r.reduce(R_SQDEV, B, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), G + o.mean, G + o.var,
+            r.reduce(R_SUM, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), STAT_STRIDE, nullptr, nullptr, nullptr,
+                     nullptr);
+            r.reduce(R_SQDEV, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), STAT_STRIDE, G + o.mean, G + o.var,
                      P + o.mean, P + o.var);
-            k_bn_apply<<<nblk(B * Co * So), BLK, 0, s>>>(tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1], B,
+            KL(k_bn_apply, (r.g1(B * Co * So)), BLK, md, tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1],
                                                          Co, So);
         }
         if (!r.ok()) return r.rc;
     }
     const int64_t hw = (int64_t)H0 * W0;
-    k_final_fwd<<<nblk(B * hw), BLK, 0, s>>>(tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, B, hw);
-    r.reduce(R_LOSS, 1, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, nullptr, nullptr, nullptr, nullptr);
-    k_loss<<<1, 1, 0, s>>>(tr->red, B, sm, tr->d_loss);
+    KL(k_final_fwd, (r.g1(B * hw)), BLK, md, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
+    r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, RS, nullptr, nullptr, nullptr, nullptr);
+    KL(k_loss, (dim3(1, 1, K)), 1, md, tr->red, sm, tr->d_loss);
 
     // ---------------------------------------------------------------- backward
-    k_final_bwd<<<nblk(B * hw), BLK, 0, s>>>(tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], B, hw, sm,
+    KL(k_final_bwd, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
                                             tr->d_counts);
-    r.reduce(R_FINALW, B, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, G + tr->fk, nullptr, nullptr, nullptr);
-    r.reduce(R_SUM, B, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + tr->fb, nullptr, nullptr, nullptr);
+    r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
+    r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fb, nullptr, nullptr, nullptr);
     if (!r.ok()) return r.rc;
     for (int j = NL - 1; j >= 0; j--) {
         const int Ci = DEC_CI[j], Co = DEC_CO[j];
@@ -723,20 +962,20 @@ int run_step(covahip_train *tr, int B, float lr) {
         const DecOff &o = tr->dof[j];
         const int64_t So = (int64_t)Ho * Wo;
         if (j < NL - 1) {   // BN of this block: its output gradient is channel range [0, Co) of the next block's dz
-            r.reduce(R_BNBWD, B, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, G + o.gamma,
+            r.reduce(R_BNBWD, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, RS, G + o.gamma,
                      G + o.beta, nullptr, nullptr);
-            k_bn_bwd<<<nblk(B * Co * So), BLK, 0, s>>>(tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma, tr->dy[j],
-                                                       B, Co, So, 0);
+            KL(k_bn_bwd, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma,
+                                                       tr->dy[j], Co, So, 0);
         }
-        r.reduce(R_SUM, B, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + o.b, nullptr, nullptr, nullptr);
-        const int64_t Pp = (int64_t)B * Hi * Wi;
+        r.reduce(R_SUM, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
+        const int64_t per = (int64_t)Hi * Wi, Pp = (int64_t)B * per;
         const int ns = wg_slabs(Pp);
         const int nw = 16 * Co * Ci;
-        k_convT_wgrad<<<dim3(nblk(nw), ns), BLK, 0, s>>>(tr->zd[j], tr->dy[j], tr->slab, B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j],
-                                                        (Pp + ns - 1) / ns);
-        k_sum_slabs<<<nblk(nw), BLK, 0, s>>>(tr->slab, ns, nw, G + o.k);
-        k_convT_dgrad<<<nblk(Pp * Ci), BLK, 0, s>>>(tr->dy[j], P + o.k, tr->z[j], tr->dz[j], B, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j],
-                                                   make_drop(tr, 2 * NL + j));
+        KL(k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                           tr->cx[j], (Pp + ns - 1) / ns);
+        KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, per, 0, nw, G + o.k);
+        KL(k_convT_dgrad, (r.g1(Pp * Ci)), BLK, md, tr->dy[j], P + o.k, tr->z[j], tr->dz[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                   tr->cx[j], make_drop(tr, 2 * NL + j));
         if (!r.ok()) return r.rc;
     }
     for (int i = NL - 1; i >= 0; i--) {
@@ -744,31 +983,29 @@ int run_step(covahip_train *tr, int B, float lr) {
         const EncOff &o = tr->eo[i];
         const int zj = NL - 1 - i;
         const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
-        const int64_t n = (int64_t)B * Co * Hp * Wp;
-        const int nb = (int)std::min<int64_t>(TMIX_BLOCKS_MAX, std::max<int64_t>(1, (n + 4 * BLK - 1) / (4 * BLK)));
-        k_tmix_bwd<<<nb, BLK, 0, s>>>(tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj], DEC_CI[zj], c_off,
-                                      tr->dp[i], tr->slab, B, Co, (int64_t)Hp * Wp, (n + nb - 1) / nb, make_drop(tr, 2 * i),
-                                      make_drop(tr, 2 * i + 1));
-        k_sum_slabs<<<1, BLK, 0, s>>>(tr->slab, nb, 32, G + o.w1);
+        const int64_t tper = (int64_t)Co * Hp * Wp;
+        const int nb = tmix_blocks(B * tper);
+        KL(k_tmix_bwd, (dim3(nb, 1, K)), BLK, md, tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj],
+                                                  DEC_CI[zj], c_off, tr->dp[i], tr->slab, Co, (int64_t)Hp * Wp, (B * tper + nb - 1) / nb, make_drop(tr, 2 * i),
+                                                  make_drop(tr, 2 * i + 1));
+        KL(k_sum_slabs, (dim3(1, 1, K)), BLK, md, tr->slab, tper, 1, 32, G + o.w1);
         const int64_t S = (int64_t)TT * H * W;
-        k_pool_bwd<<<nblk(B * Co * S), BLK, 0, s>>>(tr->dp[i], tr->arg[i], tr->dc[i], B, Co, H, W, Hp, Wp);
-        r.reduce(R_BNBWD, B, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, G + o.gamma, G + o.beta, nullptr, nullptr);
-        k_bn_bwd<<<nblk(B * Co * S), BLK, 0, s>>>(tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], B, Co, S, 1);
-        r.reduce(R_SUM, B, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, G + o.b, nullptr, nullptr, nullptr);
+        KL(k_pool_bwd, (r.g1(B * Co * S)), BLK, md, tr->dp[i], tr->arg[i], tr->dc[i], Co, H, W, Hp, Wp);
+        r.reduce(R_BNBWD, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, RS, G + o.gamma, G + o.beta, nullptr, nullptr);
+        KL(k_bn_bwd, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], Co, S, 1);
+        r.reduce(R_SUM, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
         const float *xin = i ? tr->e[i - 1] : tr->x0;
         const int64_t Pp = (int64_t)B * S;
         const int ns = wg_slabs(Pp);
         const int nw = 9 * Ci * Co;
-        k_conv3_wgrad<<<dim3(nblk(nw), ns), BLK, 0, s>>>(tr->dc[i], xin, tr->slab, B, Ci, Co, H, W, (Pp + ns - 1) / ns);
-        k_sum_slabs<<<nblk(nw), BLK, 0, s>>>(tr->slab, ns, nw, G + o.k);
-        if (i > 0) k_conv3_dgrad<<<nblk((int64_t)B * Ci * S), BLK, 0, s>>>(tr->dc[i], P + o.k, tr->de[i - 1], B, Ci, Co, H, W);
+        KL(k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
+        KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, S, 0, nw, G + o.k);
+        if (i > 0) KL(k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, md, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
         if (!r.ok()) return r.rc;
     }
 
-    // ---------------------------------------------------------------- Adam
-    const double t = (double)(tr->step + 1);
-    const double lr_t = lr * std::sqrt(1.0 - std::pow((double)tr->cfg.beta2, t)) / (1.0 - std::pow((double)tr->cfg.beta1, t));
-    k_adam<<<nblk((int64_t)N_PARAMS), BLK, 0, s>>>(P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, (float)lr_t, tr->cfg.beta1,
+    // ---------------------------------------------------------------- Adam (lr_t per model in the table)
+    KL(k_adam, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
                                                    tr->cfg.beta2, tr->cfg.eps);
     if (!r.ok()) return r.rc;
     return COVAHIP_OK;
@@ -785,10 +1022,23 @@ int validate_cfg(const covahip_train_cfg *c) {
     return COVAHIP_OK;
 }
 
-int create_body(covahip_train *tr, const float *h_w) {
+// COVAHIP_OK if `cvhw` is a weight file of the trained architecture
+int check_blob(const void *cvhw, size_t cvhw_bytes) {
+    if (cvhw_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
+    uint32_t hdr[16];
+    std::memcpy(hdr, cvhw, 64);
+    static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
+    for (int i = 0; i < 13; i++)
+        if (hdr[i] != want[i]) return COVAHIP_ERR_BAD_WEIGHTS;
+    if (cvhw_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
+    return COVAHIP_OK;
+}
+
+int create_body(covahip_train *tr, const void *const *blobs) {
     covahip_ctx *ctx = tr->ctx;
     const covahip_train_cfg &cf = tr->cfg;
-    const int64_t B = cf.max_batch;
+    const int K = tr->K;
+    const int64_t B = (int64_t)K * cf.max_batch;   // samples all models hold together
     tr->H[0] = cf.h_mb;
     tr->W[0] = cf.w_mb;
     for (int i = 0; i < NL; i++) {
@@ -801,16 +1051,24 @@ int create_body(covahip_train *tr, const float *h_w) {
         tr->cy[j] = ph / 2 + ph % 2;
         tr->cx[j] = pw / 2 + pw % 2;
     }
+    const int64_t hw0 = (int64_t)tr->H[0] * tr->W[0];
+    // A set's totals must stay inside what is 32-bit on the way: the samples of all models (the `first` column of the step
+    // table, the packed input's sample index), the x extent of the largest elementwise grid of one model (level 0's conv
+    // output) and the y extent of the per-sample loss reduction (one row per sample of a model).
+    if (B > INT32_MAX / 2 || ((int64_t)cf.max_batch * 16 * TT * hw0 + BLK - 1) / BLK > INT32_MAX || (K > 1 && cf.max_batch > 65535))
+        return COVAHIP_ERR_UNSUPPORTED;
     layout(tr);
+    tr->step.assign(K, 0);
+    tr->last_counts.assign((size_t)K * 3, 0);
     int rc;
 #define TA(p, n) if ((rc = talloc(tr, &(p), (size_t)(n)))) return rc
-    TA(tr->params, N_PARAMS);
-    TA(tr->grads, N_PARAMS);
-    TA(tr->adam_m, N_PARAMS);
-    TA(tr->adam_v, N_PARAMS);
+    TA(tr->params, K * N_PARAMS);
+    TA(tr->grads, K * N_PARAMS);
+    TA(tr->adam_m, K * N_PARAMS);
+    TA(tr->adam_v, K * N_PARAMS);
     TA(tr->trainable, N_PARAMS);
-    const int64_t hw0 = (int64_t)tr->H[0] * tr->W[0];
     TA(tr->x0, B * 3 * TT * hw0);
+    const int64_t mb = cf.max_batch;   // the slab workspace is per model: sized for one model's largest batch
     size_t slab = 0;
     for (int i = 0; i < NL; i++) {
         const int64_t Co = ENC_C[i + 1], S = (int64_t)TT * tr->H[i] * tr->W[i], Sp = (int64_t)TT * tr->H[i + 1] * tr->W[i + 1];
@@ -821,8 +1079,8 @@ int create_body(covahip_train *tr, const float *h_w) {
         TA(tr->e[i], B * Co * Sp);
         TA(tr->dp[i], B * Co * Sp);
         TA(tr->de[i], B * Co * Sp);
-        slab = std::max(slab, (size_t)Co * red_slabs(B * S) * 2);
-        slab = std::max(slab, (size_t)9 * ENC_C[i] * Co * wg_slabs(B * S));
+        slab = std::max(slab, (size_t)Co * red_slabs(mb * S) * 2);
+        slab = std::max(slab, (size_t)9 * ENC_C[i] * Co * wg_slabs(mb * S));
         slab = std::max(slab, (size_t)TMIX_BLOCKS_MAX * 32);
     }
     for (int j = 0; j < NL; j++) {
@@ -833,33 +1091,89 @@ int create_body(covahip_train *tr, const float *h_w) {
         TA(tr->dz[j], B * Ci * Si);
         TA(tr->y[j], B * Co * So);
         TA(tr->dy[j], B * Co * So);
-        slab = std::max(slab, (size_t)Co * red_slabs(B * So) * 2);
-        slab = std::max(slab, (size_t)16 * Ci * Co * wg_slabs(B * Si));
+        slab = std::max(slab, (size_t)Co * red_slabs(mb * So) * 2);
+        slab = std::max(slab, (size_t)16 * Ci * Co * wg_slabs(mb * Si));
     }
-    slab = std::max(slab, (size_t)B * red_slabs(hw0) * 2);
+    slab = std::max(slab, (size_t)mb * red_slabs(hw0) * 2);
     TA(tr->logit, B * hw0);
     TA(tr->dlogit, B * hw0);
-    TA(tr->stat, 7 * 256);
-    TA(tr->red, 2 * std::max<int64_t>(128, B));
-    TA(tr->slab, slab);
+    TA(tr->stat, (size_t)K * STAT_STRIDE);
+    TA(tr->red, (size_t)K * red_stride(cf.max_batch));
+    TA(tr->slab, (size_t)K * slab);
     tr->slab_floats = slab;
-    TA(tr->d_loss, 1);
-    TA(tr->d_counts, 3);
+    TA(tr->d_loss, K);
+    TA(tr->d_counts, (size_t)K * 3);
     TA(tr->d_stack, B * TT * hw0 * 4);
     TA(tr->d_gt, B * hw0);
+    TA(tr->d_tab, K);
 #undef TA
-    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_out, 16 * sizeof(float), hipHostMallocDefault));
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_tab, (size_t)K * sizeof(MStep), hipHostMallocDefault));
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_loss, (size_t)K * sizeof(float), hipHostMallocDefault));
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_counts, (size_t)K * 3 * sizeof(unsigned long long), hipHostMallocDefault));
     // BN moving statistics are not trained
     std::vector<uint8_t> tmask(N_PARAMS, 1);
     for (int i = 0; i < NL; i++) std::fill(tmask.begin() + tr->eo[i].mean, tmask.begin() + tr->eo[i].w1, 0);
     for (int j = 0; j < NL - 1; j++) std::fill(tmask.begin() + tr->dof[j].mean, tmask.begin() + tr->dof[j].var + DEC_CO[j], 0);
     const hipStream_t s = ctx->stream;
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params, h_w, N_PARAMS * sizeof(float), hipMemcpyHostToDevice, s));
+    for (int k = 0; k < K; k++)
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params + (size_t)k * N_PARAMS, static_cast<const uint8_t *>(blobs[k]) + 64,
+                                              N_PARAMS * sizeof(float), hipMemcpyHostToDevice, s));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->trainable, tmask.data(), N_PARAMS, hipMemcpyHostToDevice, s));
-    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, N_PARAMS * sizeof(float), s));
-    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_m, 0, N_PARAMS * sizeof(float), s));
-    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_v, 0, N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, (size_t)K * N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_m, 0, (size_t)K * N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_v, 0, (size_t)K * N_PARAMS * sizeof(float), s));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // tmask leaves scope
+    return COVAHIP_OK;
+}
+
+// The step of a set: batches / lrs / losses have K entries, the samples are packed in model order.
+int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int *batches, const float *lrs, float *losses,
+              int mem_kind) {
+    const int K = tr->K;
+    int64_t total = 0;
+    int bmax = 0;
+    for (int k = 0; k < K; k++) {
+        if (batches[k] < 0 || batches[k] > tr->cfg.max_batch || !std::isfinite(lrs[k]) || lrs[k] < 0.f) return COVAHIP_ERR_INVALID_ARG;
+        total += batches[k];
+        bmax = std::max(bmax, batches[k]);
+    }
+    if (total == 0) return COVAHIP_ERR_INVALID_ARG;
+    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    int first = 0;
+    for (int k = 0; k < K; k++) {
+        MStep &ms = tr->h_tab[k];
+        ms.b = batches[k];
+        ms.first = first;
+        first += batches[k];
+        const double t = (double)(tr->step[k] + 1);
+        const double lr_t = lrs[k] * std::sqrt(1.0 - std::pow((double)tr->cfg.beta2, t)) / (1.0 - std::pow((double)tr->cfg.beta1, t));
+        ms.lr_t = (float)lr_t;
+        ms.pad = 0;
+        for (int site = 0; site < N_SITES; site++) ms.key[site] = drop_key(tr->seed[k], (uint64_t)tr->step[k], site);
+    }
+    const size_t hw = (size_t)tr->H[0] * tr->W[0];
+    const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    if (K > 1)
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_tab, tr->h_tab, (size_t)K * sizeof(MStep), hipMemcpyHostToDevice, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * TT * hw * 4, kind, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, kind, ctx->stream));
+    if (int rc = run_step(tr, bmax)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_loss, tr->d_loss, (size_t)K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_counts, tr->d_counts, (size_t)K * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
+                                          ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int k = 0; k < K; k++) {
+        if (!batches[k]) {   // skipped: its loss slot was not written, its metrics and step stay
+            losses[k] = 0.f;
+            continue;
+        }
+        losses[k] = tr->h_loss[k];
+        for (int q = 0; q < 3; q++) tr->last_counts[(size_t)k * 3 + q] = (long long)tr->h_counts[(size_t)k * 3 + q];
+        tr->step[k]++;
+    }
     return COVAHIP_OK;
 }
 
@@ -883,23 +1197,25 @@ void covahip_train_default_cfg(covahip_train_cfg *cfg) {
     cfg->seed = 0;
 }
 
-int covahip_train_create(covahip_ctx *ctx, const covahip_train_cfg *cfg, const void *cvhw, size_t cvhw_bytes, covahip_train **out) {
+int covahip_train_create_set(covahip_ctx *ctx, const covahip_train_cfg *cfg, int n_models, const void *const *weights,
+                             const size_t *weights_bytes, const uint64_t *seeds, covahip_train **out) {
     if (out) *out = nullptr;
-    if (!ctx || !cfg || !cvhw || !out) return COVAHIP_ERR_INVALID_ARG;
+    if (!ctx || !cfg || !weights || !weights_bytes || !out || n_models < 1 || n_models > COVAHIP_MAX_MODELS)
+        return COVAHIP_ERR_INVALID_ARG;
+    for (int k = 0; k < n_models; k++)
+        if (!weights[k]) return COVAHIP_ERR_INVALID_ARG;
     if (int rc = validate_cfg(cfg)) return rc;
-    if (cvhw_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
-    uint32_t hdr[16];
-    std::memcpy(hdr, cvhw, 64);
-    static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
-    for (int i = 0; i < 13; i++)
-        if (hdr[i] != want[i]) return COVAHIP_ERR_BAD_WEIGHTS;
-    if (cvhw_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
+    for (int k = 0; k < n_models; k++)
+        if (int rc = check_blob(weights[k], weights_bytes[k])) return rc;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     covahip_train *tr = new covahip_train();
     tr->ctx = ctx;
     tr->cfg = *cfg;
-    const int rc = create_body(tr, reinterpret_cast<const float *>(static_cast<const uint8_t *>(cvhw) + 64));
+    tr->K = n_models;
+    tr->seed.resize(n_models);
+    for (int k = 0; k < n_models; k++) tr->seed[k] = seeds ? seeds[k] : cfg->seed;
+    const int rc = create_body(tr, weights);
     if (rc) {
         hipStreamSynchronize(ctx->stream);
         (void)hipGetLastError();
@@ -910,37 +1226,39 @@ int covahip_train_create(covahip_ctx *ctx, const covahip_train_cfg *cfg, const v
     return COVAHIP_OK;
 }
 
+int covahip_train_create(covahip_ctx *ctx, const covahip_train_cfg *cfg, const void *cvhw, size_t cvhw_bytes, covahip_train **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !cfg || !cvhw || !out) return COVAHIP_ERR_INVALID_ARG;
+    return covahip_train_create_set(ctx, cfg, 1, &cvhw, &cvhw_bytes, nullptr, out);
+}
+
+int covahip_train_num_models(covahip_train *tr, int *n_models) {
+    if (!tr || !n_models) return COVAHIP_ERR_INVALID_ARG;
+    *n_models = tr->K;
+    return COVAHIP_OK;
+}
+
+int covahip_train_step_set(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *batches, const float *lrs,
+                           float *losses, int mem_kind) {
+    if (!tr || !stack || !gt || !batches || !lrs || !losses) return COVAHIP_ERR_INVALID_ARG;
+    return step_body(tr, stack, gt, batches, lrs, losses, mem_kind);
+}
+
 int covahip_train_step(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, int batch, float lr, float *loss, int mem_kind) {
-    if (!tr || !stack || !gt || !loss || batch <= 0 || batch > tr->cfg.max_batch || !std::isfinite(lr) || lr < 0.f)
-        return COVAHIP_ERR_INVALID_ARG;
-    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
-    covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
-    const size_t hw = (size_t)tr->H[0] * tr->W[0];
-    const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)batch * TT * hw * 4, kind, ctx->stream));
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)batch * hw, kind, ctx->stream));
-    if (int rc = run_step(tr, batch, lr)) return rc;
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_out, tr->d_loss, sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_out + 2, tr->d_counts, 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    *loss = tr->h_out[0];
-    unsigned long long cnt[3];
-    std::memcpy(cnt, tr->h_out + 2, sizeof(cnt));
-    for (int k = 0; k < 3; k++) tr->last_counts[k] = (long long)cnt[k];
-    tr->step++;
+    if (!tr || !stack || !gt || !loss || batch <= 0 || tr->K != 1) return COVAHIP_ERR_INVALID_ARG;
+    return step_body(tr, stack, gt, &batch, &lr, loss, mem_kind);
+}
+
+int covahip_train_metrics_m(covahip_train *tr, int model, int64_t tp_fp_fn[3]) {
+    if (!tr || !tp_fp_fn || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
+    for (int k = 0; k < 3; k++) tp_fp_fn[k] = tr->last_counts[(size_t)model * 3 + k];
     return COVAHIP_OK;
 }
 
-int covahip_train_metrics(covahip_train *tr, int64_t tp_fp_fn[3]) {
-    if (!tr || !tp_fp_fn) return COVAHIP_ERR_INVALID_ARG;
-    for (int k = 0; k < 3; k++) tp_fp_fn[k] = tr->last_counts[k];
-    return COVAHIP_OK;
-}
+int covahip_train_metrics(covahip_train *tr, int64_t tp_fp_fn[3]) { return covahip_train_metrics_m(tr, 0, tp_fp_fn); }
 
-int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n) {
-    if (!tr || !n) return COVAHIP_ERR_INVALID_ARG;
+int covahip_train_weights_m(covahip_train *tr, int model, void *cvhw, size_t cap, size_t *n) {
+    if (!tr || !n || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
     const size_t need = 64 + N_PARAMS * sizeof(float);
     *n = need;
     if (!cvhw || cap < need) return COVAHIP_ERR_OVERFLOW;
@@ -949,21 +1267,26 @@ int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n) 
     if (int rc = covahip_primary_op(ctx)) return rc;
     const uint32_t hdr[16] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS, 0, 0, 0};
     std::memcpy(cvhw, hdr, 64);
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + 64, tr->params, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost,
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + 64, tr->params + (size_t)model * N_PARAMS,
+                                          N_PARAMS * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return COVAHIP_OK;
+}
+
+int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n) { return covahip_train_weights_m(tr, 0, cvhw, cap, n); }
+
+int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n) {
+    if (!tr || !flat || n != N_PARAMS || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(flat, tr->grads + (size_t)model * N_PARAMS, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost,
                                           ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return COVAHIP_OK;
 }
 
-int covahip_train_grads(covahip_train *tr, float *flat, size_t n) {
-    if (!tr || !flat || n != N_PARAMS) return COVAHIP_ERR_INVALID_ARG;
-    covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(flat, tr->grads, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return COVAHIP_OK;
-}
+int covahip_train_grads(covahip_train *tr, float *flat, size_t n) { return covahip_train_grads_m(tr, 0, flat, n); }
 
 void covahip_train_destroy(covahip_train *tr) {
     if (!tr) return;

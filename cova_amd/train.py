@@ -4,10 +4,16 @@
   slide           utils/data/slide.py slide_dataset(skip=True): non-overlapping stacks of T = 4 frames, newest first
   init_weights    the Keras default initialisation of the reference model, as a flat weight array (cova_amd/weights.py order)
   Trainer         the training step on the GPU (covahip_train_*: forward, backward and Adam in HIP) and the epoch loop
+  TrainerSet      K models of one geometry in one trainer (covahip_train_create_set): one launch of each kernel per step of all
 
     python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
 
 writes a weight file that covahip_blobnet_load / BlobNetInfer / the blobnetfilter element load unchanged.
+
+    python -m cova_amd.train --set -o OUTDIR CAM0.tfrecord CAM1.tfrecord CAM2a.tfrecord,CAM2b.tfrecord
+
+trains one model per argument (several files of one model joined with commas; model k initialised and seeded with --seed + k)
+and writes OUTDIR/CAM0.cvhw, OUTDIR/CAM1.cvhw, OUTDIR/CAM2a.cvhw: a model set for covahip_blobnet_load_set / BlobNetInfer([...]).
 No TensorFlow or protobuf is needed: the record framing and the Example message are parsed here.
 """
 from __future__ import annotations
@@ -16,6 +22,7 @@ import argparse
 import ctypes as C
 import functools
 import math
+import os
 import struct
 import sys
 
@@ -380,17 +387,230 @@ class Trainer:
         return history
 
 
-def main(argv=None) -> int:
+def set_epoch_plan(sizes, batch: int):
+    """The steps of one epoch of a training set: a list of per-step lists [(start_k, count_k) for each model].  Model k walks
+    its sizes[k] samples in order in batches of `batch`, the last one partial, exactly as Trainer.fit does; once its epoch is
+    over it sits out the remaining steps with count 0.  The epoch has as many steps as the largest data set needs."""
+    if batch < 1:
+        raise ValueError("batch must be at least 1")
+    if not sizes or min(sizes) < 1:
+        raise ValueError("every model of a set needs at least one training sample")
+    steps = max(-(-n // batch) for n in sizes)
+    return [[(min(i * batch, n), max(0, min(batch, n - i * batch))) for n in sizes] for i in range(steps)]
+
+
+class TrainerSet:
+    """K BlobNet models of one geometry trained side by side over covahip_train_create_set: a step takes one step of every
+    model in one launch of each kernel.  Model k is bit-identical to a Trainer made from the same weights and seed and fed
+    model k's steps alone (include/covahip.h, "Training sets")."""
+
+    def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, weights=None, n_models: int | None = None, seeds=None,
+                 max_batch: int = 4, dropout: float = 0.2, lr: float = 1e-3):
+        """weights: a list of flat weight arrays, one per model; or n_models with weights None: model k = init_weights(seeds[k]).
+        seeds: the dropout seed per model (default 0, 1, ..)."""
+        if weights is None:
+            if n_models is None:
+                raise ValueError("TrainerSet needs weights=[...] or n_models=K")
+            if seeds is None:
+                seeds = list(range(n_models))
+            weights = [init_weights(int(sd)) for sd in seeds]
+        k = len(weights)
+        if n_models is not None and n_models != k:
+            raise ValueError(f"n_models = {n_models} but {k} weight arrays")
+        if seeds is None:
+            seeds = list(range(k))
+        if len(seeds) != k:
+            raise ValueError(f"{len(seeds)} seeds for {k} models")
+        self.ctx, self.h, self.w, self.max_batch, self.n_models = ctx, h_mb, w_mb, max_batch, k
+        self.seeds = [int(sd) for sd in seeds]
+        self._lib = L.lib()
+        cfg = L.TrainCfg()
+        self._lib.covahip_train_default_cfg(C.byref(cfg))
+        cfg.h_mb, cfg.w_mb, cfg.max_batch, cfg.dropout, cfg.lr = h_mb, w_mb, max_batch, dropout, lr
+        cfg.seed = self.seeds[0] if k else 0
+        self.cfg = cfg
+        blobs = [W.to_bytes(w) for w in weights]
+        ptrs = (C.c_char_p * max(1, k))(*blobs)
+        sizes = (C.c_size_t * max(1, k))(*[len(b) for b in blobs])
+        sd = (C.c_uint64 * max(1, k))(*self.seeds)
+        h = C.c_void_p()
+        L.check(self._lib.covahip_train_create_set(ctx.handle, C.byref(cfg), k, ptrs, sizes, sd, C.byref(h)),
+                "covahip_train_create_set", ctx.handle)
+        self.handle = h
+        self.step_counts = [0] * k
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):      # (a trainer outliving its closed ctx is not freed)
+                self._lib.covahip_train_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    def _lrs(self, lrs):
+        if lrs is None:
+            lrs = self.cfg.lr
+        if np.isscalar(lrs):
+            lrs = [lrs] * self.n_models
+        if len(lrs) != self.n_models:
+            raise ValueError(f"{len(lrs)} learning rates for {self.n_models} models")
+        return np.ascontiguousarray(lrs, dtype=np.float32)
+
+    def _step(self, p_stack, p_gt, batches, lrs, kind):
+        batches = np.ascontiguousarray(batches, dtype=np.int32)
+        if batches.shape != (self.n_models,):
+            raise ValueError(f"{batches.size} batches for {self.n_models} models")
+        lrs = self._lrs(lrs)
+        losses = np.zeros(self.n_models, np.float32)
+        L.check(self._lib.covahip_train_step_set(self.handle, p_stack, p_gt, batches.ctypes.data, lrs.ctypes.data,
+                                                 losses.ctypes.data, kind), "covahip_train_step_set", self.ctx.handle)
+        for k in range(self.n_models):
+            self.step_counts[k] += int(batches[k] > 0)
+        return [float(v) for v in losses]
+
+    def step(self, stacks_per_model, labels_per_model, lrs=None):
+        """One step of every model: stacks_per_model[k] u8 [b_k][4h][w][4] and labels_per_model[k] u8 [b_k][h][w]; an empty
+        entry (or None) = model k sits this step out.  lrs: one rate for all, or one per model.  Returns the losses before
+        the update (0 for a skipped model)."""
+        if len(stacks_per_model) != self.n_models or len(labels_per_model) != self.n_models:
+            raise ValueError(f"a step of this set takes {self.n_models} entries")
+        xs, ys, batches = [], [], []
+        for x, y in zip(stacks_per_model, labels_per_model):
+            b = 0 if x is None else len(x)
+            batches.append(b)
+            if b:
+                x = np.ascontiguousarray(x, dtype=np.uint8)
+                y = np.ascontiguousarray(y, dtype=np.uint8)
+                assert x.shape == (b, W.T * self.h, self.w, 4) and y.shape == (b, self.h, self.w), (x.shape, y.shape)
+                xs.append(x)
+                ys.append(y)
+        if not xs:
+            raise ValueError("a set step needs at least one model with samples")
+        stack = xs[0] if len(xs) == 1 else np.concatenate(xs)
+        gt = ys[0] if len(ys) == 1 else np.concatenate(ys)
+        return self._step(stack.ctypes.data, gt.ctypes.data, batches, lrs, L.MEM_HOST)
+
+    def step_device(self, d_stack: int, d_gt: int, batches, lrs=None):
+        """The same on device pointers: the samples packed in model order (sum(batches) stacks, then as many labels)."""
+        return self._step(d_stack, d_gt, batches, lrs, L.MEM_DEVICE)
+
+    def metrics(self, k: int):
+        """(TP, FP, FN) of model k's last step at sigmoid > 0.5."""
+        v = (C.c_int64 * 3)()
+        L.check(self._lib.covahip_train_metrics_m(self.handle, k, v), "covahip_train_metrics_m")
+        return int(v[0]), int(v[1]), int(v[2])
+
+    def weights(self, k: int) -> np.ndarray:
+        return W.from_bytes(self.weights_bytes(k))
+
+    def weights_bytes(self, k: int) -> bytes:
+        n = C.c_size_t()
+        rc = self._lib.covahip_train_weights_m(self.handle, k, None, 0, C.byref(n))
+        if rc != 7:                                    # the size query answers COVAHIP_ERR_OVERFLOW (7); a bad k does not
+            L.check(rc, "covahip_train_weights_m", self.ctx.handle)
+        buf = np.zeros(n.value, np.uint8)
+        L.check(self._lib.covahip_train_weights_m(self.handle, k, buf.ctypes.data, n.value, C.byref(n)), "covahip_train_weights_m",
+                self.ctx.handle)
+        return buf.tobytes()
+
+    def grads(self, k: int) -> np.ndarray:
+        out = np.empty(W.N_PARAMS, np.float32)
+        L.check(self._lib.covahip_train_grads_m(self.handle, k, out.ctypes.data, out.size), "covahip_train_grads_m", self.ctx.handle)
+        return out
+
+    def fit(self, records_per_model, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None):
+        """records_per_model[k] = (stacks, labels) of model k, as Trainer.fit takes them.  Every model walks its own data set in
+        order (set_epoch_plan); a model whose epoch is shorter sits out the rest of it.  Returns one history per model, each as
+        Trainer.fit's; model k's weights afterwards are those of Trainer.fit on records_per_model[k] alone, bit for bit."""
+        if len(records_per_model) != self.n_models:
+            raise ValueError(f"{len(records_per_model)} data sets for {self.n_models} models")
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
+        sizes = [int(r[0].shape[0]) for r in records_per_model]
+        if min(sizes) == 0:
+            raise ValueError("no training samples")
+        plan = set_epoch_plan(sizes, batch)
+        histories = [[] for _ in range(self.n_models)]
+        for ep in range(epochs):
+            lr = schedule(ep, self.cfg.lr) if schedule is keras_lr else schedule(ep)
+            tot = [0.0] * self.n_models
+            cnt = [[0, 0, 0] for _ in range(self.n_models)]
+            for st in plan:
+                xs = [records_per_model[k][0][a:a + n] for k, (a, n) in enumerate(st)]
+                ys = [records_per_model[k][1][a:a + n] for k, (a, n) in enumerate(st)]
+                losses = self.step(xs, ys, lr)
+                for k, (_, n) in enumerate(st):
+                    if n:
+                        tot[k] += losses[k] * n
+                        for q, v in enumerate(self.metrics(k)):
+                            cnt[k][q] += v
+            for k in range(self.n_models):
+                tp, fp, fn = cnt[k]
+                rec = {"epoch": ep, "lr": lr, "loss": tot[k] / sizes[k], "precision": tp / max(1, tp + fp),
+                       "recall": tp / max(1, tp + fn)}
+                histories[k].append(rec)
+                if log:
+                    log(f"epoch {ep + 1}/{epochs} model {k}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
+                        f"recall {rec['recall']:.4f} lr {lr:.3g}")
+        return histories
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cova_amd.train", description=__doc__.split("\n")[0])
-    ap.add_argument("records", nargs="+", help="TFRecord files written by tfrecordsink gt=LABELS")
-    ap.add_argument("-o", "--output", required=True, help="weight file to write (CVHW)")
+    ap.add_argument("records", nargs="+", help="TFRecord files written by tfrecordsink gt=LABELS; with --set one model per "
+                                               "argument, several files of one model joined with commas")
+    ap.add_argument("-o", "--output", required=True, help="weight file to write (CVHW); with --set the directory for one file per model")
+    ap.add_argument("--set", action="store_true", dest="as_set", help="train one model per argument in one training set")
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--h-mb", type=int, default=45)
     ap.add_argument("--w-mb", type=int, default=80)
     ap.add_argument("--device", type=int, default=0)
-    a = ap.parse_args(argv)
+    return ap.parse_args(argv)
+
+
+def set_jobs(records, outdir: str):
+    """--set: [(files of model k, its output path)] in argument order.  A model's output is OUTDIR/<stem of its first file>.cvhw;
+    two models that would share a name are an error."""
+    jobs, seen = [], set()
+    for arg in records:
+        files = [f for f in arg.split(",") if f]
+        if not files:
+            raise ValueError(f"empty model argument {arg!r}")
+        stem = os.path.splitext(os.path.basename(files[0]))[0]
+        if stem in seen:
+            raise ValueError(f"two models would be written to {stem}.cvhw")
+        seen.add(stem)
+        jobs.append((files, os.path.join(outdir, stem + ".cvhw")))
+    return jobs
+
+
+def main_set(a) -> int:
+    from .elements import Context
+
+    jobs = set_jobs(a.records, a.output)
+    records = []
+    for k, (files, _) in enumerate(jobs):
+        frames, gt = read_tfrecords(files, a.h_mb, a.w_mb)
+        records.append(slide(frames, gt))
+        print(f"model {k}: {frames.shape[0]} frames -> {records[-1][0].shape[0]} samples of {a.h_mb}x{a.w_mb}", file=sys.stderr)
+    os.makedirs(a.output, exist_ok=True)
+    ctx = Context(a.device)
+    ts = TrainerSet(ctx, a.h_mb, a.w_mb, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))], max_batch=a.batch)
+    ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr))
+    for k, (_, out) in enumerate(jobs):
+        with open(out, "wb") as f:
+            f.write(ts.weights_bytes(k))
+    ts.close()
+    ctx.close()
+    return 0
+
+
+def main(argv=None) -> int:
+    a = parse_args(argv)
+    if a.as_set:
+        return main_set(a)
     from .elements import Context
 
     frames, gt = read_tfrecords(a.records, a.h_mb, a.w_mb)

@@ -327,6 +327,36 @@ int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n);
 /* The last step's gradients, n = 320305 floats in weight-file order; the BN mean / var slots hold the step's batch mean and
  * biased batch variance. */
 int covahip_train_grads(covahip_train *tr, float *flat, size_t n);
+/* Training sets: one trainer holds K models of ONE geometry and cfg (e.g. one BlobNet per camera, the input of
+ * covahip_blobnet_load_set), each with its own weights, Adam moments, BN moving statistics, step counter, dropout seed and, per
+ * step, its own batch and learning rate.  A set step takes one step of every model in ONE launch of each kernel: the number of
+ * launches does not depend on K, and K small-batch trainings fill the GPU as one large batch would.
+ *   1 <= n_models <= COVAHIP_MAX_MODELS; weights[k] / weights_bytes[k]: model k's initial weight file; seeds[k]: its dropout seed
+ *   (seeds NULL: cfg->seed for every model).  All or nothing: a bad blob in any slot is COVAHIP_ERR_BAD_WEIGHTS, checked before
+ *   anything is allocated.  A set whose totals would pass a 32-bit sample index or a grid extent is COVAHIP_ERR_UNSUPPORTED.
+ *   Memory: K * max_batch samples of activations (about 5 MB each at 45x80) plus four parameter-sized buffers (1.3 MB each) per
+ *   model.
+ * Contract: model k of a set is BIT-IDENTICAL to the same model trained alone.  Its loss, gradients, TP / FP / FN, weights,
+ * moving statistics and Adam state after any sequence of set steps equal those of a covahip_train_create trainer with the same
+ * initial weights, the same cfg and seed = seeds[k], fed model k's (stack, gt, batch, lr) steps with the set steps in which it
+ * had batch 0 left out.  (Every reduction splits by the model's OWN batch, whatever the others take in that step.)
+ * covahip_train_create is a set of one; the entries without _m mean model 0.  covahip_train_step on a set of more than one
+ * model is COVAHIP_ERR_INVALID_ARG. */
+int covahip_train_create_set(covahip_ctx *ctx, const covahip_train_cfg *cfg, int n_models, const void *const *weights,
+                             const size_t *weights_bytes, const uint64_t *seeds, covahip_train **out);
+int covahip_train_num_models(covahip_train *tr, int *n_models);
+/* One step of every model k with batches[k] > 0.  Sample order: PACKED in model order -- stack holds the batches[0] stacks of
+ * model 0, then the batches[1] stacks of model 1 and so on (sum of batches stacks in all), gt likewise; mem_kind applies to both.
+ * batches / lrs / losses: HOST arrays of n_models entries.  0 <= batches[k] <= max_batch.  A model with batches[k] = 0 sits the
+ * step out: NOTHING of it changes (weights, moving statistics, Adam state, step counter, last gradients and metrics) and
+ * losses[k] = 0.  All batches 0, a batch above max_batch, a NULL array or a negative / non-finite lr: COVAHIP_ERR_INVALID_ARG.
+ * Synchronous. */
+int covahip_train_step_set(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *batches, const float *lrs,
+                           float *losses, int mem_kind);
+/* covahip_train_metrics / _weights / _grads of model `model` (its last step; outside [0, n_models): COVAHIP_ERR_INVALID_ARG). */
+int covahip_train_metrics_m(covahip_train *tr, int model, int64_t tp_fp_fn[3]);
+int covahip_train_weights_m(covahip_train *tr, int model, void *cvhw, size_t cap, size_t *n);
+int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n);
 void covahip_train_destroy(covahip_train *tr);
 
 /* ------------------------------------------------------------ MoG labels
