@@ -2767,13 +2767,38 @@ int set_lds(covahip_ctx *ctx, K kernel, size_t lds) {
     return COVAHIP_OK;
 }
 
-}  // namespace
+// Run-time bools as template arguments: with_bools(f, b0, b1, ..) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ..)
+// and returns its code, so that a generic lambda names a kernel family once and instantiates one kernel per combination of
+// its own bools (and no other: combinations that never run, such as PRE with CIN != 16, are kept apart by separate calls).
+template <typename F>
+int with_bools(F &&f) {
+    return f();
+}
+template <typename F, typename... Bs>
+int with_bools(F &&f, bool b, Bs... bs) {
+    return b ? with_bools([&](auto... rest) { return f(std::true_type{}, rest...); }, bs...)
+             : with_bools([&](auto... rest) { return f(std::false_type{}, rest...); }, bs...);
+}
 
-// planning-only passes (blobnet_forward_mfma with d_stack == nullptr) go through every check and launch nothing
-#define LAUNCH(...)                                  \
-    do {                                             \
-        if (!dry) hipLaunchKernelGGL(__VA_ARGS__);   \
-    } while (0)
+// Band planner of the encoder levels: bands of whole pool-window rows.  Workgroups are persistent (`slots` of them on the
+// device) and take items round-robin, so a launch lasts ceil(items / slots) rounds of one band each; a band costs its window
+// rows plus about one row of halo staging + barriers.  Returns the band count whose bands (of at most rb window rows) pass
+// fits(rb) and that minimises rounds x (rows + 1) -- the smallest such count -- or 0 when no band count fits.
+template <typename Fit>
+int plan_bands(int Hp, int batch, long long slots, Fit fits) {
+    long long best = -1;
+    int nbands = 0;
+    for (int nb = 1; nb <= Hp; nb++) {
+        const int rb = (Hp + nb - 1) / nb;  // max window rows per band
+        if (!fits(rb)) continue;
+        const long long rounds = ((long long)batch * nb + slots - 1) / slots;
+        const long long cost = rounds * (rb + 1);
+        if (best < 0 || cost < best) { best = cost; nbands = nb; }
+    }
+    return nbands;
+}
+
+}  // namespace
 
 int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *const *ws, int n_models) {
     // host view of the parameter blob (same order as bind_params in blobnet.hip)
@@ -2874,505 +2899,452 @@ void blobnet_release_mfma(covahip_ctx *, covahip_blobnet *m) {
     m->prep = nullptr;
 }
 
+// ------------------------------------------------------------------ the forward: one function per stage
+namespace {
+
+// What the stages of one forward share.  part_written is the one thing a stage tells a later one.
+struct Fwd {
+    covahip_ctx *ctx;
+    const covahip_blobnet *m;
+    const Prepared *pr;
+    BnWorkspace &ws;
+    const BnInput &inp;
+    int batch;
+    const uint8_t *prep;       // the batch's model; of a mixed batch model 0 (every item adds its model's mstride)
+    uint32_t mstride;
+    bool ms;                   // a mixed batch: the MS = true instantiations
+    bool dry;                  // planning only: every check runs, no kernel is launched
+    bool by_frames;
+    int num_cu;
+    const uint8_t *d_frames;   // carrier frames (the stacked tensor is B * T of them with an implicit table)
+    int n_frames;
+    const int32_t *d_index;
+    float *d_logits;
+    uint8_t *d_mask;
+    const BnCcTail *cc;
+    bool part_written = false;   // the level-1 kernel wrote partial logits instead of the level-0 skip tensor
+};
+
+// One launch: opens the kernel's dynamic-LDS limit (set_lds: nothing to do up to 64 KB), brackets the launch for the profile
+// as `name` and launches -- unless the pass is planning only, which goes through every check and still opens the limit (this
+// is how covahip_blobnet_load opens the kernels before the first forward).  Returns set_lds's code; the launch's own error
+// is launched()'s.
+template <typename K, typename... A>
+int launch(const Fwd &f, const char *name, K kernel, int grid, int block, size_t lds, const A &...args) {
+    if (int rc = set_lds(f.ctx, kernel, lds)) return rc;
+    ProfScope ps(f.ctx, name);
+    if (!f.dry) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, f.ctx->stream, args...);
+    return COVAHIP_OK;
+}
+// the end of a stage: launch()'s code, then the launch's own error
+int launched(const Fwd &f, int rc) {
+    if (rc) return rc;
+    COVAHIP_CHECK_HIP(f.ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+
+// Level 0 up to the pool runs ONCE per carrier frame (enc0p_mfma -> P); level 1 gathers the four frames of a stack,
+// applies level 0's temporal MLP while staging and writes the decoder's skip slice.  The stacked tensor of the other
+// entry point is B * T carrier frames with an implicit table (stack b = frames 4b .. 4b+3).
+int run_enc0p(const Fwd &f) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    const int H = m->lv[0].H, W = m->lv[0].W, Hp = H / 2, Wp = W / 2;
+    const int TC = ((W + 4 - 16 + 31) / 32) * 32 + 16;
+    if (W % 4) return COVAHIP_ERR_UNSUPPORTED;
+    // bands of whole pool-window rows: at most 2 * WG0 16-byte pieces per band (two per thread), <= 38 KB of LDS
+    int nbands = 0;
+    for (int nb = 1; nb <= Hp; nb++) {
+        const int rb = (Hp + nb - 1) / nb, n2 = 2 * rb + 2;
+        if (n2 * (W / 4) > 2 * WG0 || (size_t)n2 * TC * 8 > 30 * 1024) continue;
+        if ((long long)f.n_frames * nb < 2LL * f.num_cu && nb < Hp) continue;   // keep every CU busy
+        nbands = nb;
+        break;
+    }
+    if (!nbands) return COVAHIP_ERR_UNSUPPORTED;
+    const int rbmax = (Hp + nbands - 1) / nbands;
+    const size_t tile_bytes = (((size_t)(2 * rbmax + 2) * TC * 8) + 15) & ~(size_t)15;
+    Enc0pArgs a;
+    a.in = f.d_frames; a.out = f.ws.pbuf;
+    a.wfrag = (const half8 *)(f.prep + pr->enc[0].wfrag); a.epi = (const float *)(f.prep + pr->enc[0].epi);
+    a.F = f.n_frames; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[1].H; a.Wo = m->lv[1].W;
+    a.oy = H & 1; a.ox = W & 1; a.nbands = nbands; a.TC = TC;
+    a.mWp = magic(Wp); a.mNb = magic(nbands); a.mW4 = magic(W / 4); a.scr_off = (int)tile_bytes;
+    a.model_ids = f.inp.frame_models; a.mstride = f.mstride;
+    const size_t lds = tile_bytes + (size_t)(WG0 / 64) * 1024;
+    // three persistent workgroups per CU: measured 13.9 - 14.6 us at 280 frames against 15.0 with four (the kernel sits
+    // on its latency floor: band count 3 .. 7 and 2 .. 4 workgroups per CU all land within 1.5 us)
+    const int grid = std::min(f.n_frames * nbands, 3 * f.num_cu);
+    return launched(f, with_bools([&](auto AP, auto PACKED, auto MS) {
+        return launch(f, "enc0p_mfma", enc0p_mfma<AP.value, PACKED.value, MS.value>, grid, WG0, lds, a);
+    }, pr->allpos[0], f.inp.packed, f.ms));
+}
+
+// Level 1 on enc1_mfma: bands of at most three pool-window rows (E1_TR rows per T slice), two eight-wave workgroups per CU.
+// False: level 1 is run_enc_level's.  True: it ran, or failed with rc set.
+bool run_enc1_tile16(Fwd &f, int &rc) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    if (!bn_level1_on_enc1(f.ctx, m)) return false;   // (the predicate blobnet.hip's prepare_frames uses for the table by value)
+    const int H = m->lv[1].H, W = m->lv[1].W, Hp = H / 2, Wp = W / 2;
+    const int nbands = plan_bands(Hp, f.batch, 2LL * f.num_cu, [](int rb) { return 2 * rb + 2 <= E1_TR; });
+    if (!nbands) return false;
+    Enc1Args a;
+    a.in = f.ws.pbuf; a.out = f.ws.act[2];
+    a.wfrag = (const half8 *)(f.prep + pr->enc1w); a.epi = (const float *)(f.prep + pr->enc[1].epi);
+    a.B = f.batch; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[2].H; a.Wo = m->lv[2].W;
+    a.oy = H & 1; a.ox = W & 1; a.nbands = nbands;
+    a.mWp = magic(Wp); a.mRC = magic(2 * (W + 2));
+    a.scr_off = BN_T * E1_TSZ;
+    const int grid = std::min(f.batch * nbands, 2 * f.num_cu);
+    a.plan = make_plan(grid, f.num_cu, 2, f.batch, nbands, Hp);
+    a.pidx = f.d_index; a.skip = f.ws.act[1]; a.tm_pre = (const float *)(f.prep + pr->enc[0].epi) + 48;
+    // the level-0 skip connection as partial logits instead of a tensor (Enc1Args::part)
+    f.part_written = m->tail_part && f.ws.part && m->dec_ci[3] == 32 && m->dec_co[3] == 16 && m->enc_c[1] == 16;
+    a.part = f.part_written ? f.ws.part : nullptr;
+    a.wtail = (const half8 *)(f.prep + pr->tail_w);
+    a.mXe = magic(2 * Wp);
+    a.use_ktab = 0;
+    if (f.by_frames && f.inp.h_index && f.batch <= BN_KTAB_STACKS) {
+        a.use_ktab = 1;
+        for (int k = 0; k < f.batch * BN_T; k++) a.ktab[k] = (uint16_t)f.inp.h_index[k];
+    } else if (f.by_frames && !f.d_index && !f.dry) {
+        rc = COVAHIP_ERR_INVALID_ARG;
+        return true;
+    }
+    const size_t lds = (size_t)BN_T * E1_TSZ + 8 * 1024 + E1_CONST;   // (twice this fits a CU's 160 KB)
+    a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
+    rc = launched(f, with_bools([&](auto AP, auto MS) {
+        return launch(f, "enc1_mfma", enc1_mfma<AP.value, MS.value>, grid, 512, lds, a);
+    }, pr->allpos[1], f.ms));
+    return true;
+}
+
+// Levels 2 + 3 in one launch (enc23_mfma) when a ring row holds level 2's row, its windows make at most two tile columns
+// and level 3's band fits the compile-time slice stride; one workgroup per frame.
+// False: the levels are run_enc_level's.  True: both ran, or failed with rc set.
+bool run_enc23(const Fwd &f, int &rc) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    if (!(m->fuse_enc23 && m->enc_rowtiles && !f.ctx->enc_plan[2].nbands && !f.ctx->enc_plan[3].nbands && m->enc_c[2] == 32 &&
+          m->enc_c[3] == 64 && m->enc_c[4] == 128))
+        return false;
+    const int H = m->lv[2].H, W = m->lv[2].W, Hp = H / 2, Wp = W / 2;
+    const int H3 = m->lv[3].H, W3 = m->lv[3].W, Hp3 = H3 / 2, Wp3 = W3 / 2;
+    const size_t lds = (size_t)BN_T * E3_TSZ + (size_t)BN_T * E23_TSZ2 + 4096;
+    // ... and when it pays: one workgroup per frame wants about a frame per CU (a batch of 32 leaves seven CUs in eight idle
+    // where the two launches spread a frame's bands over them: 62 -> 76 us per step at b = 32), and row-aligned tiles want rows
+    // that fill their tile columns (45 x 80: 10 of 16 and 5 of 8 windows, 3 % slower than the two launches at b = 512).
+    // fuse_enc23 == 2 (developer switch "enc23_force", the tests) takes it whenever it fits
+    const bool pays = 4 * f.batch >= 3 * f.num_cu && 20 * Wp >= 17 * 8 * ((Wp + 7) / 8) && 20 * Wp3 >= 17 * 8 * ((Wp3 + 7) / 8);
+    // a mixed batch (model sets) takes it whenever it fits: the two-launch form's level-3 kernel cannot hold a per-stack model's
+    // fragments without spilling ("Model sets")
+    if (!((pays || m->fuse_enc23 == 2 || f.ms) && (W + 2) * 64 <= E23_RP2 && Wp <= 16 && Hp >= 1 && Hp3 >= 1 && Wp3 >= 1 &&
+          (size_t)std::max(2 * Hp3 + 2, H3 + 1) * (W3 + 2) * 128 <= (size_t)E3_TSZ && lds <= 160 * 1024 - 256))
+        return false;
+    Enc23Args a;
+    a.in = f.ws.act[2]; a.mid = f.ws.act[3]; a.out = f.ws.act[4];
+    a.wf2 = (const half8 *)(f.prep + pr->enc[2].wfrag); a.wf3 = (const half8 *)(f.prep + pr->enc[3].wfrag);
+    a.epi2 = (const float *)(f.prep + pr->enc[2].epi); a.epi3 = (const float *)(f.prep + pr->enc[3].epi);
+    a.B = f.batch;
+    a.H2 = H; a.W2 = W; a.Hp2 = Hp; a.Wp2 = Wp;
+    a.H3 = H3; a.W3 = W3; a.Hp3 = Hp3; a.Wp3 = Wp3; a.oy3 = H & 1; a.ox3 = W & 1;
+    a.H4 = m->lv[4].H; a.W4 = m->lv[4].W; a.oy4 = H3 & 1; a.ox4 = W3 & 1;
+    a.swz2 = choose_swz_periodic(32, 30, Wp); a.swz3 = choose_swz_periodic(64, W3, Wp3);
+    a.ring_off = BN_T * E3_TSZ; a.xchg_off = a.ring_off + BN_T * E23_TSZ2; a.scr_off = a.ring_off;
+    a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
+    const int grid = std::min(f.batch, f.num_cu);
+    rc = launched(f, with_bools([&](auto AP2, auto AP3, auto MS) {
+        return launch(f, "enc23_mfma", enc23_mfma<AP2.value, AP3.value, MS.value>, grid, 512, lds, a);
+    }, pr->allpos[2], pr->allpos[3], f.ms));
+    return true;
+}
+
+// Encoder level i = 1 .. 3 on enc_mfma.  Level 1 here is the round-1..3 level-1 kernel: grids wider than enc1_mfma's LDS
+// row, developer band plans, set_impl(5).
+int run_enc_level(const Fwd &f, int i) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    const int H = m->lv[i].H, W = m->lv[i].W, Hp = H / 2, Wp = W / 2;
+    const int cin = m->enc_c[i];
+    const size_t px_bytes = (size_t)cin * 2;
+    const int TC = W + 2;
+    // band height: largest even RB whose tile (RB+2 rows, all T) fits in ~78 KB of LDS
+    // (two workgroups per CU; the 64->128 level keeps 144 weight VGPRs per wave and runs one
+    //  workgroup per CU with up to 150 KB)
+    // output transpose scratch behind the tile: 2 KB per wave
+    static const int enc_waves[BN_LEVELS] = {0, 8, 4, 8};
+    int nbuf = 1, wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : 2;
+    int nbands = 0;
+    const size_t scr_bytes = (size_t)enc_waves[i] * 2048;
+    if (f.ctx->enc_plan[i].nbands) {
+        // developer override (covahip_blobnet_set_enc_plan)
+        nbands = std::min(f.ctx->enc_plan[i].nbands, Hp);
+        nbuf = f.ctx->enc_plan[i].nbuf;
+        const size_t need = (size_t)nbuf * BN_T * (2 * ((Hp + nbands - 1) / nbands) + 2) * TC * px_bytes + scr_bytes;
+        if (need > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
+        wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : (int)std::min<size_t>(2, (160 * 1024 - 256) / need);
+    } else {
+        // the band count that fits in LDS and minimises rounds x (rows + 1) (plan_bands)
+        const size_t lds_cap = (wgs_per_cu == 1 ? 150 * 1024 : 80 * 1024) - scr_bytes;
+        nbands = plan_bands(Hp, f.batch, (long long)wgs_per_cu * f.num_cu,
+                            [&](int rb) { return (size_t)BN_T * (2 * rb + 2) * TC * px_bytes <= lds_cap; });
+        if (!nbands) return COVAHIP_ERR_UNSUPPORTED;
+    }
+    const int RB = 2 * ((Hp + nbands - 1) / nbands);
+    // levels 2 and 3 on row-aligned tiles (enc_mfma<.., TSZ>) when a T slice of the band fits the kernel's compile-time
+    // slice stride and a row's windows fill its tile columns about as well as the general form's tiles fill a band
+    const int fix_tsz = i == 2 ? E2_TSZ : i == 3 ? E3_TSZ : 0;
+    bool rowtiles = false;
+    if (fix_tsz && m->enc_rowtiles && !f.ctx->enc_plan[i].nbands && cin == (i == 2 ? 32 : 64) && m->enc_c[i + 1] == 2 * cin &&
+        (size_t)(RB + 2) * TC * px_bytes <= (size_t)fix_tsz) {
+        long long t_rows = (long long)Hp * ((Wp + 7) / 8), t_gen = 0;
+        for (int k = 0; k < nbands; k++) t_gen += ((((k + 1) * Hp) / nbands - (k * Hp) / nbands) * Wp + 7) / 8;
+        rowtiles = t_rows <= t_gen;
+    }
+    const size_t tile_bytes = rowtiles ? (size_t)BN_T * fix_tsz : (((size_t)BN_T * (RB + 2) * TC * px_bytes) + 15) & ~(size_t)15;
+    const size_t lds = nbuf * tile_bytes + scr_bytes;
+    if (lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
+    const int items = f.batch * nbands;
+    const int grid = std::min(items, wgs_per_cu * f.num_cu);
+    EncArgs a;
+    a.in = i == 1 ? f.ws.pbuf : f.ws.act[i]; a.out = f.ws.act[i + 1];
+    a.wfrag = (const half8 *)(f.prep + pr->enc[i].wfrag); a.epi = (const float *)(f.prep + pr->enc[i].epi);
+    a.B = f.batch; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[i + 1].H; a.Wo = m->lv[i + 1].W;
+    a.oy = H & 1; a.ox = W & 1; a.To = (i == BN_LEVELS - 1) ? 1 : BN_T;
+    a.RB = RB; a.nbands = nbands; a.TR = RB + 2; a.TC = TC;
+    a.mWp = magic(Wp); a.mNb = magic(nbands); a.mRC = magic(TC * (cin / 8)); a.zero = f.prep + pr->zero;
+    a.nbuf = nbuf; a.buf_stride = (int)tile_bytes; a.scr_off = (int)(nbuf * tile_bytes);
+    a.plan = make_plan(grid, f.num_cu, wgs_per_cu, f.batch, nbands, Hp);
+    a.swz = rowtiles ? choose_swz_periodic(cin, W, Wp) : choose_swz(true, cin, W, Wp, RB / 2);
+    a.pidx = f.d_index; a.skip = f.ws.act[1]; a.tm_pre = (const float *)(f.prep + pr->enc[0].epi) + 48;
+    a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
+    const bool ap = pr->allpos[i];
+    // one arm per level: PRE (level 0's temporal MLP while staging) is level 1's alone, row tiles are levels 2's and 3's
+    if (i == 1) {
+        // (a null table means "stack b = frames 4b .. 4b+3" to this kernel: a carrier-frame call must bring its table)
+        if (f.by_frames && !f.d_index && !f.dry) return COVAHIP_ERR_INVALID_ARG;
+        return launched(f, with_bools([&](auto AP, auto MS) {
+            return launch(f, "enc1_mfma", enc_mfma<16, 32, 2, 4, 8, true, AP.value, true, 0, MS.value>, grid, 512, lds, a);
+        }, ap, f.ms));
+    }
+    if (i == 2)
+        return launched(f, with_bools([&](auto AP, auto ROWS, auto MS) {
+            return launch(f, "enc2_mfma", enc_mfma<32, 64, 4, 2, 4, true, AP.value, false, ROWS.value ? E2_TSZ : 0, MS.value>, grid, WG, lds, a);
+        }, ap, rowtiles, f.ms));
+    return launched(f, with_bools([&](auto AP, auto ROWS, auto MS) {
+        return launch(f, "enc3_mfma", enc_mfma<64, 128, 2, 2, 8, true, AP.value, false, ROWS.value ? E3_TSZ : 0, MS.value>, grid, 512, lds, a);
+    }, ap, rowtiles, f.ms));
+}
+
+// Decoder blocks 0..2 in one launch when a frame's three input tiles fit in LDS together.
+// False: the blocks are run_dec_block's.  True: they ran, or failed with rc set.
+bool run_dec012(const Fwd &f, int &rc) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    if (!(m->fuse_dec && m->dec_ci[0] == 128 && m->dec_ci[1] == 128 && m->dec_ci[2] == 64 && m->dec_co[0] == 64 &&
+          m->dec_co[1] == 32 && m->dec_co[2] == 16))
+        return false;
+    Dec012Args a;
+    size_t off = 0;
+    for (int j = 0; j < 3; j++) {
+        const BnLevelGeom in = m->lv[BN_LEVELS - j], out = m->lv[BN_LEVELS - 1 - j];
+        DecLvl &g = a.lv[j];
+        g.Hi = in.H; g.Wi = in.W; g.Hd = out.H; g.Wd = out.W; g.cy = m->dec_cy[j]; g.cx = m->dec_cx[j];
+        g.mGW = magic(in.W + 1);
+        g.mRC = magic((in.W + 2) * (m->dec_ci[j] / 8));
+        g.swz = choose_swz(false, m->dec_ci[j], in.W, 0, in.H + 1);
+        g.tile_off = (int)off;
+        off += (((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2) + 255) & ~(size_t)255;   // 256: dec012_block's xor addressing
+        a.skip[j] = f.ws.act[BN_LEVELS - j];
+        a.Ts[j] = j == 0 ? 1 : BN_T;
+        a.wf[j] = (const half8 *)(f.prep + pr->dec[j].wfrag);
+        a.epi[j] = (const float *)(f.prep + pr->dec[j].epi);
+    }
+    a.scr_off = (int)off;
+    const size_t lds = off + 8 * 2048;
+    if (lds > 160 * 1024 - 256) return false;
+    a.out = f.ws.dact[2]; a.B = f.batch; a.zero = f.prep + pr->zero;
+    a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
+    rc = launched(f, with_bools([&](auto MS) {
+        return launch(f, "dec012_mfma", dec012_mfma<MS.value>, std::min(f.batch, f.num_cu), 512, lds, a);
+    }, f.ms));
+    return true;
+}
+
+// Decoder block j on dec_mfma (the last one carries the folded final conv + threshold): its plan, which the fused tail
+// starts from, and its launch.
+struct DecPlan {
+    DecArgs a;
+    DecMs am;
+    BnLevelGeom in, out;
+    bool half;   // the last block on its "up" half + partial logits
+    int ci, GH, grid;
+    size_t row_bytes, lds;
+};
+int plan_dec_block(const Fwd &f, int j, DecPlan &p) {
+    const covahip_blobnet *m = f.m;
+    const Prepared *pr = f.pr;
+    const BnLevelGeom in = m->lv[BN_LEVELS - j], out = m->lv[BN_LEVELS - 1 - j];
+    const bool last = j == BN_LEVELS - 1;
+    const bool half = last && f.part_written;
+    const int ci_j = half ? m->dec_ci[j] / 2 : m->dec_ci[j];
+    DecArgs &a = p.a;
+    a.up = j == 0 ? nullptr : f.ws.dact[j - 1];
+    a.skip = f.ws.act[BN_LEVELS - j];
+    a.out = last ? nullptr : f.ws.dact[j];
+    a.logits = last ? f.d_logits : nullptr;
+    a.mask = last ? f.d_mask : nullptr;
+    a.wfrag = (const half8 *)(f.prep + (half ? pr->final_w_up : last ? pr->final_w : pr->dec[j].wfrag));
+    a.part = half ? f.ws.part : nullptr;
+    a.epi = (const float *)(f.prep + (last ? pr->final_epi : pr->dec[j].epi));
+    a.B = f.batch; a.Hi = in.H; a.Wi = in.W; a.Hd = out.H; a.Wd = out.W; a.cy = m->dec_cy[j]; a.cx = m->dec_cx[j];
+    a.Ts = j == 0 ? 1 : BN_T;
+    p.am = DecMs{f.inp.model_ids, f.mstride};
+    const int GH = in.H + 1;
+    const size_t row_bytes = (size_t)(in.W + 2) * ci_j * 2;
+    // band planner.  A workgroup keeps its M-tile's weight fragments in registers, so the weights
+    // cross the L2 -> CU path once per workgroup: block 0 (256 KB of fragments per workgroup) runs
+    // one workgroup per CU over whole frames.  The lighter blocks are bound by the latency of
+    // stage -> barrier -> compute, which only other workgroups on the CU can hide: bands of at most
+    // ~30 KB of LDS so that four to five of them are resident per CU.
+    const size_t wbytes = (size_t)(last ? 1 : 4 * m->dec_co[j] / 32) * (4 * ci_j / 16) * 1024;
+    const bool heavy = wbytes >= 192 * 1024 && (size_t)(GH + 1) * row_bytes <= 72 * 1024;
+    int nbands = 1;
+    if (!heavy)
+        while (nbands < GH && (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes > 30 * 1024 ||
+                               (long long)f.batch * nbands < 2LL * f.num_cu))
+            nbands++;
+    a.nbands = nbands; a.mNb = magic(nbands); a.mGW = magic(in.W + 1);
+    a.mRC = magic((in.W + 2) * (ci_j / 8)); a.zero = f.prep + pr->zero;
+    a.swz = choose_swz(false, ci_j, in.W, 0, (GH + nbands - 1) / nbands);
+    const size_t tile_bytes = (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes + 15) & ~(size_t)15;
+    const size_t mask_bytes = last ? ((((size_t)2 * ((GH + nbands - 1) / nbands) * out.W) + 15) & ~(size_t)15) : 0;
+    const size_t scr_bytes = last ? 0 : (size_t)std::max(4, 4 * m->dec_co[j] / 32) * 2048;   // one 2 KB transpose scratch per wave
+    p.lds = tile_bytes + mask_bytes + scr_bytes;
+    a.mask_off = (int)tile_bytes;
+    a.scr_off = (int)tile_bytes;
+    if (p.lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
+    p.in = in; p.out = out; p.half = half; p.ci = ci_j; p.GH = GH; p.row_bytes = row_bytes;
+    p.grid = std::min(f.batch * nbands, (heavy ? 1 : 4) * f.num_cu);
+    return COVAHIP_OK;
+}
+int launch_dec_block(const Fwd &f, int j, const DecPlan &p) {
+    if (j == 0)
+        return launched(f, with_bools([&](auto MS) {
+            return launch(f, "dec0_mfma", dec_mfma<0, 128, 64, false, MS.value>, p.grid, 512, p.lds, p.a, p.am);
+        }, f.ms));
+    if (j == 1)
+        return launched(f, with_bools([&](auto MS) {
+            return launch(f, "dec1_mfma", dec_mfma<64, 64, 32, false, MS.value>, p.grid, 256, p.lds, p.a, p.am);
+        }, f.ms));
+    if (j == 2)
+        return launched(f, with_bools([&](auto MS) {
+            return launch(f, "dec2_mfma", dec_mfma<32, 32, 16, false, MS.value>, p.grid, 256, p.lds, p.a, p.am);
+        }, f.ms));
+    return launched(f, with_bools([&](auto HALF, auto MS) {
+        return launch(f, "dec3_final_mfma", dec_mfma<16, HALF.value ? 0 : 16, 16, true, MS.value>, p.grid, 256, p.lds, p.a, p.am);
+    }, p.half, f.ms));
+}
+int run_dec_block(const Fwd &f, int j) {
+    DecPlan p;
+    if (int rc = plan_dec_block(f, j, p)) return rc;
+    return launch_dec_block(f, j, p);
+}
+
+// Last block + bboxcc in one launch when the frame's LDS plan fits: two band buffers (which bboxcc's region reuses) + the
+// frame's mask bytes.  p: the last block's own plan.  False: it does not fit -- a kernel whose LDS limit cannot be opened
+// counts as that -- and the block runs alone.
+bool run_tail_fused(const Fwd &f, const DecPlan &p) {
+    const BnLevelGeom in = p.in, out = p.out;
+    const int GH = p.GH;
+    Dec3ccArgs t;
+    size_t cc_bytes = ccbody::cc_plan(out.H, out.W, t.g);
+    // the run-based body (bboxcc_wave.h) when the shape allows it: worst-case run capacity, nothing overflows
+    t.use_wv = f.ctx->cc_wave_cap >= 0 && ccwave::wv_plan(out.H, out.W, ((out.H + 1) / 2) * ((out.W + 1) / 2), t.wg) ? 1 : 0;
+    if (t.use_wv) cc_bytes = (size_t)t.wg.wave_bytes;
+    if (!cc_bytes) return false;
+    const size_t mfull = ((size_t)out.H * out.W + 15) & ~(size_t)15;
+    const size_t partb = p.half ? (size_t)GH * (in.W + 1) * 16 : 0;   // partial logits beside the mask
+    int best_nb = 0;
+    long long best_cost = -1;
+    for (int nb = 1; nb <= GH; nb++) {
+        const size_t tb = (((size_t)((GH + nb - 1) / nb) + 1) * p.row_bytes + 15) & ~(size_t)15;
+        const size_t nbuf = nb == 1 ? 1 : 2;   // the whole frame in one buffer when it fits
+        if (std::max(nbuf * tb, cc_bytes) + mfull + partb > 160 * 1024 - 512) continue;
+        long long rounds = 0;   // tiles of 32 positions over 16 waves, band by band
+        for (int k = 0; k < nb; k++) {
+            const int nu = (k + 1) * GH / nb - k * GH / nb;
+            rounds += ((nu * (in.W + 1) + 31) / 32 + 15) / 16;
+        }
+        const long long cost = rounds * 8 + nb;   // a band costs a barrier + DMA issue on top of its tiles
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_nb = nb; }
+    }
+    if (!best_nb) return false;
+    const size_t tb = (((size_t)((GH + best_nb - 1) / best_nb) + 1) * p.row_bytes + 15) & ~(size_t)15;
+    t.d = p.a;
+    t.ms = p.am;
+    t.d.nbands = best_nb; t.d.mNb = magic(best_nb);
+    t.d.swz = choose_swz(false, p.ci, in.W, 0, (GH + best_nb - 1) / best_nb);
+    t.boxes = f.cc->boxes; t.counts = f.cc->counts;
+    t.area_thresh = f.cc->area_thresh; t.max_boxes = f.cc->max_boxes;
+    t.tile_bytes = (int)tb; t.cc_off = 0;
+    t.mfull_off = (int)std::max((best_nb == 1 ? 1 : 2) * tb, cc_bytes);
+    t.part_off = (int)((size_t)t.mfull_off + mfull);
+    const size_t tl = (size_t)t.part_off + partb;
+    const int grid = std::min(f.batch, 2 * f.num_cu);
+    // row tiles + ballots straight into bboxcc's planes (dec3cc_rows_mfma) when the shape allows it
+    if (p.half && t.use_wv && best_nb == 1 && in.W + 1 <= 64 && f.m->tail_rows && (out.W & 7) == 0 &&
+        (size_t)t.wg.rows_bytes <= mfull && (!f.d_mask || (reinterpret_cast<uintptr_t>(f.d_mask) & 3) == 0)) {
+        t.d.swz = Swz{3, 1, 0, 0, 0};            // s = (xx >> 3) & 1 (what the staging of both forms evaluates)
+        t.d.mRC = magic(out.W / 4);               // the mask expansion's division
+        return !with_bools([&](auto MS) {
+            return launch(f, "dec3_bboxcc_fused", dec3cc_rows_mfma<MS.value>, grid, ccbody::CC_THREADS, tl, t);
+        }, f.ms);
+    }
+    return !with_bools([&](auto WV, auto PART, auto MS) {
+        return launch(f, "dec3_bboxcc_fused", dec3cc_mfma<WV.value, PART.value, MS.value>, grid, ccbody::CC_THREADS, tl, t);
+    }, t.use_wv != 0, p.half, f.ms);
+}
+
+}  // namespace
+
+// The chain of DESIGN.md section 4: level 0 per carrier frame -> level 1 -> levels 2 and 3 -> decoder blocks 0 .. 2 -> the
+// last block; at each step the fused form first, and the launches it replaces where it does not apply.
 int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const BnInput &inp, int batch, float *d_logits,
                          uint8_t *d_mask, const BnCcTail *cc, bool *cc_done) {
     if (cc_done) *cc_done = false;
-    const bool dry = inp.dry;              // planning only: every check below runs, no kernel is launched
-    const bool by_frames = inp.frames != nullptr || (dry && inp.n_frames > 0);
-    __half *const *act = ws.act;
-    __half *const *dact = ws.dact;
     const Prepared *pr = m->prep;
+    const bool dry = inp.dry;
+    const bool by_frames = inp.frames != nullptr || (dry && inp.n_frames > 0);
     // model sets: a batch of one model runs the single-model kernels on that model's weights; a mixed batch runs the MS = true
     // instantiations, which take every item's weights from its model (inp.model_ids per stack, inp.frame_models per carrier frame)
     const bool ms = inp.model_ids != nullptr || (dry && inp.mixed);
-    const uint8_t *prep = (const uint8_t *)m->d_prepared + (ms ? 0 : (size_t)inp.model * pr->total);
-    const uint32_t mstride = (uint32_t)pr->total;
-    const int num_cu = ctx->props.multiProcessorCount;
+    Fwd f{ctx, m, pr, ws, inp, batch,
+          (const uint8_t *)m->d_prepared + (ms ? 0 : (size_t)inp.model * pr->total), (uint32_t)pr->total,
+          ms, dry, by_frames, ctx->props.multiProcessorCount,
+          by_frames ? inp.frames : inp.stack, by_frames ? inp.n_frames : batch * BN_T, by_frames ? inp.index : nullptr,
+          d_logits, d_mask, cc};
+    if ((size_t)f.n_frames > ws.pbuf_frames && !dry) return COVAHIP_ERR_INVALID_ARG;   // (the caller sizes P: blobnet.hip)
 
-    // ---------------- encoder
-    // Level 0 up to the pool runs ONCE per carrier frame (enc0p_mfma -> P); level 1 gathers the four frames of a stack,
-    // applies level 0's temporal MLP while staging and writes the decoder's skip slice.  The stacked tensor of the other
-    // entry point is B * T carrier frames with an implicit table (stack b = frames 4b .. 4b+3).
-    const uint8_t *const d_frames = by_frames ? inp.frames : inp.stack;
-    const int n_frames = by_frames ? inp.n_frames : batch * BN_T;
-    const int32_t *const d_index = by_frames ? inp.index : nullptr;
-    bool part_written = false;   // the level-1 kernel wrote partial logits instead of the level-0 skip tensor
-    if ((size_t)n_frames > ws.pbuf_frames && !dry) return COVAHIP_ERR_INVALID_ARG;   // (the caller sizes P: blobnet.hip)
-    {
-        const int H = m->lv[0].H, W = m->lv[0].W, Hp = H / 2, Wp = W / 2;
-        const int TC = ((W + 4 - 16 + 31) / 32) * 32 + 16;
-        if (W % 4) return COVAHIP_ERR_UNSUPPORTED;
-        // bands of whole pool-window rows: at most 2 * WG0 16-byte pieces per band (two per thread), <= 38 KB of LDS
-        int nbands = 0;
-        for (int nb = 1; nb <= Hp; nb++) {
-            const int rb = (Hp + nb - 1) / nb, n2 = 2 * rb + 2;
-            if (n2 * (W / 4) > 2 * WG0 || (size_t)n2 * TC * 8 > 30 * 1024) continue;
-            if ((long long)n_frames * nb < 2LL * num_cu && nb < Hp) continue;   // keep every CU busy
-            nbands = nb;
-            break;
-        }
-        if (!nbands) return COVAHIP_ERR_UNSUPPORTED;
-        const int rbmax = (Hp + nbands - 1) / nbands;
-        const size_t tile_bytes = (((size_t)(2 * rbmax + 2) * TC * 8) + 15) & ~(size_t)15;
-        Enc0pArgs a;
-        a.in = d_frames; a.out = ws.pbuf;
-        a.wfrag = (const half8 *)(prep + pr->enc[0].wfrag); a.epi = (const float *)(prep + pr->enc[0].epi);
-        a.F = n_frames; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[1].H; a.Wo = m->lv[1].W;
-        a.oy = H & 1; a.ox = W & 1; a.nbands = nbands; a.TC = TC;
-        a.mWp = magic(Wp); a.mNb = magic(nbands); a.mW4 = magic(W / 4); a.scr_off = (int)tile_bytes;
-        a.model_ids = inp.frame_models; a.mstride = mstride;
-        const size_t lds = tile_bytes + (size_t)(WG0 / 64) * 1024;
-        // three persistent workgroups per CU: measured 13.9 - 14.6 us at 280 frames against 15.0 with four (the kernel sits
-        // on its latency floor: band count 3 .. 7 and 2 .. 4 workgroups per CU all land within 1.5 us)
-        const int grid = std::min(n_frames * nbands, 3 * num_cu);
-        {
-            ProfScope ps(ctx, "enc0p_mfma");
-            if (ms) {
-                if (inp.packed && pr->allpos[0]) LAUNCH((enc0p_mfma<true, true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-                else if (inp.packed) LAUNCH((enc0p_mfma<false, true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-                else if (pr->allpos[0]) LAUNCH((enc0p_mfma<true, false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-                else LAUNCH((enc0p_mfma<false, false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-            } else if (inp.packed) {
-                if (pr->allpos[0]) LAUNCH((enc0p_mfma<true, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-                else LAUNCH((enc0p_mfma<false, true>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-            } else {
-                if (pr->allpos[0]) LAUNCH((enc0p_mfma<true, false>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-                else LAUNCH((enc0p_mfma<false, false>), dim3(grid), dim3(WG0), lds, ctx->stream, a);
-            }
-        }
-        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    int rc = run_enc0p(f);
+    if (rc) return rc;
+    if (!run_enc1_tile16(f, rc)) rc = run_enc_level(f, 1);
+    if (rc) return rc;
+    if (!run_enc23(f, rc)) {
+        rc = run_enc_level(f, 2);
+        if (!rc) rc = run_enc_level(f, 3);
     }
-    for (int i = 1; i < BN_LEVELS; i++) {
-        const int H = m->lv[i].H, W = m->lv[i].W, Hp = H / 2, Wp = W / 2;
-        const int cin = m->enc_c[i];
-        if (i == 2 && m->fuse_enc23 && m->enc_rowtiles && !ctx->enc_plan[2].nbands && !ctx->enc_plan[3].nbands && cin == 32 &&
-            m->enc_c[3] == 64 && m->enc_c[4] == 128) {
-            // levels 2 + 3 in one launch (enc23_mfma) when a ring row holds level 2's row, its windows make at most two tile columns
-            // and level 3's band fits the compile-time slice stride; one workgroup per frame
-            const int H3 = m->lv[3].H, W3 = m->lv[3].W, Hp3 = H3 / 2, Wp3 = W3 / 2;
-            const size_t lds = (size_t)BN_T * E3_TSZ + (size_t)BN_T * E23_TSZ2 + 4096;
-            // ... and when it pays: one workgroup per frame wants about a frame per CU (a batch of 32 leaves seven CUs in eight idle
-            // where the two launches spread a frame's bands over them: 62 -> 76 us per step at b = 32), and row-aligned tiles want rows
-            // that fill their tile columns (45 x 80: 10 of 16 and 5 of 8 windows, 3 % slower than the two launches at b = 512).
-            // fuse_enc23 == 2 (developer switch "enc23_force", the tests) takes it whenever it fits
-            const bool pays = 4 * batch >= 3 * num_cu && 20 * Wp >= 17 * 8 * ((Wp + 7) / 8) && 20 * Wp3 >= 17 * 8 * ((Wp3 + 7) / 8);
-            // a mixed batch (model sets) takes it whenever it fits: the two-launch form's level-3 kernel cannot hold a per-stack model's
-            // fragments without spilling ("Model sets")
-            if ((pays || m->fuse_enc23 == 2 || ms) && (W + 2) * 64 <= E23_RP2 && Wp <= 16 && Hp >= 1 && Hp3 >= 1 && Wp3 >= 1 &&
-                (size_t)std::max(2 * Hp3 + 2, H3 + 1) * (W3 + 2) * 128 <= (size_t)E3_TSZ && lds <= 160 * 1024 - 256) {
-                Enc23Args a;
-                a.in = act[2]; a.mid = act[3]; a.out = act[4];
-                a.wf2 = (const half8 *)(prep + pr->enc[2].wfrag); a.wf3 = (const half8 *)(prep + pr->enc[3].wfrag);
-                a.epi2 = (const float *)(prep + pr->enc[2].epi); a.epi3 = (const float *)(prep + pr->enc[3].epi);
-                a.B = batch;
-                a.H2 = H; a.W2 = W; a.Hp2 = Hp; a.Wp2 = Wp;
-                a.H3 = H3; a.W3 = W3; a.Hp3 = Hp3; a.Wp3 = Wp3; a.oy3 = H & 1; a.ox3 = W & 1;
-                a.H4 = m->lv[4].H; a.W4 = m->lv[4].W; a.oy4 = H3 & 1; a.ox4 = W3 & 1;
-                a.swz2 = choose_swz_periodic(32, 30, Wp); a.swz3 = choose_swz_periodic(64, W3, Wp3);
-                a.ring_off = BN_T * E3_TSZ; a.xchg_off = a.ring_off + BN_T * E23_TSZ2; a.scr_off = a.ring_off;
-                a.model_ids = inp.model_ids; a.mstride = mstride;
-                const bool ap2 = pr->allpos[2], ap3 = pr->allpos[3];
-                if (ms) {
-                    int rc = ap2 ? (ap3 ? set_lds(ctx, enc23_mfma<true, true, true>, lds) : set_lds(ctx, enc23_mfma<true, false, true>, lds))
-                                 : (ap3 ? set_lds(ctx, enc23_mfma<false, true, true>, lds) : set_lds(ctx, enc23_mfma<false, false, true>, lds));
-                    if (rc) return rc;
-                    const int grid = std::min(batch, num_cu);
-                    ProfScope ps(ctx, "enc23_mfma");
-                    if (ap2 && ap3) LAUNCH((enc23_mfma<true, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    else if (ap2) LAUNCH((enc23_mfma<true, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    else if (ap3) LAUNCH((enc23_mfma<false, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    else LAUNCH((enc23_mfma<false, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-                    break;
-                }
-                int rc = ap2 ? (ap3 ? set_lds(ctx, enc23_mfma<true, true>, lds) : set_lds(ctx, enc23_mfma<true, false>, lds))
-                             : (ap3 ? set_lds(ctx, enc23_mfma<false, true>, lds) : set_lds(ctx, enc23_mfma<false, false>, lds));
-                if (rc) return rc;
-                const int grid = std::min(batch, num_cu);
-                ProfScope ps(ctx, "enc23_mfma");
-                if (ap2 && ap3) LAUNCH((enc23_mfma<true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                else if (ap2) LAUNCH((enc23_mfma<true, false>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                else if (ap3) LAUNCH((enc23_mfma<false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                else LAUNCH((enc23_mfma<false, false>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-                break;   // level 3 ran in the same launch
-            }
-        }
-        if (i == 1 && bn_level1_on_enc1(ctx, m)) {   // (the predicate blobnet.hip's prepare_frames uses for the table by value)
-            // enc1_mfma: bands of at most three pool-window rows (E1_TR rows per T slice), two eight-wave workgroups per CU;
-            // same planner as below: rounds x (rows + 1)
-            const long long slots = 2LL * num_cu;
-            long long best = -1;
-            int nbands = 0;
-            for (int nb = 1; nb <= Hp; nb++) {
-                const int rb = (Hp + nb - 1) / nb;
-                if (2 * rb + 2 > E1_TR) continue;
-                const long long rounds = ((long long)batch * nb + slots - 1) / slots;
-                const long long cost = rounds * (rb + 1);
-                if (best < 0 || cost < best) { best = cost; nbands = nb; }
-            }
-            if (nbands) {
-                Enc1Args a;
-                a.in = ws.pbuf; a.out = act[2];
-                a.wfrag = (const half8 *)(prep + pr->enc1w); a.epi = (const float *)(prep + pr->enc[1].epi);
-                a.B = batch; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[2].H; a.Wo = m->lv[2].W;
-                a.oy = H & 1; a.ox = W & 1; a.nbands = nbands;
-                a.mWp = magic(Wp); a.mRC = magic(2 * (W + 2));
-                a.scr_off = BN_T * E1_TSZ;
-                const int grid = std::min(batch * nbands, 2 * num_cu);
-                a.plan = make_plan(grid, num_cu, 2, batch, nbands, Hp);
-                a.pidx = d_index; a.skip = act[1]; a.tm_pre = (const float *)(prep + pr->enc[0].epi) + 48;
-                // the level-0 skip connection as partial logits instead of a tensor (Enc1Args::part)
-                part_written = m->tail_part && ws.part && m->dec_ci[3] == 32 && m->dec_co[3] == 16 && m->enc_c[1] == 16;
-                a.part = part_written ? ws.part : nullptr;
-                a.wtail = (const half8 *)(prep + pr->tail_w);
-                a.mXe = magic(2 * Wp);
-                a.use_ktab = 0;
-                if (by_frames && inp.h_index && batch <= BN_KTAB_STACKS) {
-                    a.use_ktab = 1;
-                    for (int k = 0; k < batch * BN_T; k++) a.ktab[k] = (uint16_t)inp.h_index[k];
-                } else if (by_frames && !d_index && !dry) {
-                    return COVAHIP_ERR_INVALID_ARG;
-                }
-                const size_t lds = (size_t)BN_T * E1_TSZ + 8 * 1024 + E1_CONST;   // (twice this fits a CU's 160 KB)
-                a.model_ids = inp.model_ids; a.mstride = mstride;
-                if (ms) {
-                    int rc = pr->allpos[1] ? set_lds(ctx, enc1_mfma<true, true>, lds) : set_lds(ctx, enc1_mfma<false, true>, lds);
-                    if (rc) return rc;
-                    ProfScope ps(ctx, "enc1_mfma");
-                    if (pr->allpos[1]) LAUNCH((enc1_mfma<true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    else LAUNCH((enc1_mfma<false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-                    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-                    continue;
-                }
-                int rc = pr->allpos[1] ? set_lds(ctx, enc1_mfma<true>, lds) : set_lds(ctx, enc1_mfma<false>, lds);
-                if (rc) return rc;
-                ProfScope ps(ctx, "enc1_mfma");
-                if (pr->allpos[1]) LAUNCH(enc1_mfma<true>, dim3(grid), dim3(512), lds, ctx->stream, a);
-                else LAUNCH(enc1_mfma<false>, dim3(grid), dim3(512), lds, ctx->stream, a);
-                COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-                continue;
-            }
-        }
-        const size_t px_bytes = (size_t)cin * 2;
-        const int TC = W + 2;
-        // band height: largest even RB whose tile (RB+2 rows, all T) fits in ~78 KB of LDS
-        // (two workgroups per CU; the 64->128 level keeps 144 weight VGPRs per wave and runs one
-        //  workgroup per CU with up to 150 KB)
-        // output transpose scratch behind the tile: 2 KB per wave
-        static const int enc_waves[BN_LEVELS] = {0, 8, 4, 8};
-        int waves = enc_waves[i], nbuf = 1, wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : 2;
-        int nbands = 0, RB = 0;
-        size_t scr_bytes = (size_t)waves * 2048;
-        if (ctx->enc_plan[i].nbands) {
-            // developer override (covahip_blobnet_set_enc_plan)
-            nbands = std::min(ctx->enc_plan[i].nbands, Hp);
-            nbuf = ctx->enc_plan[i].nbuf;
-            RB = 2 * ((Hp + nbands - 1) / nbands);
-            const size_t need = (size_t)nbuf * BN_T * (RB + 2) * TC * px_bytes + scr_bytes;
-            if (need > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
-            wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : (int)std::min<size_t>(2, (160 * 1024 - 256) / need);
-        } else {
-            const size_t lds_cap = (wgs_per_cu == 1 ? 150 * 1024 : 80 * 1024) - scr_bytes;
-            // band planner: bands of whole pool-window rows.  Workgroups are persistent (wgs_per_cu per CU)
-            // and take items round-robin, so a launch lasts ceil(items / slots) rounds of one band each;
-            // a band costs its window rows plus about one row of halo staging + barriers.  Pick the band
-            // count that fits in LDS and minimises rounds x (rows + 1).
-            const long long slots = (long long)wgs_per_cu * num_cu;
-            long long best = -1;
-            for (int nb = 1; nb <= Hp; nb++) {
-                const int rb = (Hp + nb - 1) / nb;  // max window rows per band
-                if ((size_t)BN_T * (2 * rb + 2) * TC * px_bytes > lds_cap) continue;
-                const long long rounds = ((long long)batch * nb + slots - 1) / slots;
-                const long long cost = rounds * (rb + 1);
-                if (best < 0 || cost < best) { best = cost; nbands = nb; RB = 2 * rb; }
-            }
-            if (!nbands) return COVAHIP_ERR_UNSUPPORTED;
-        }
-        // levels 2 and 3 on row-aligned tiles (enc_mfma<.., TSZ>) when a T slice of the band fits the kernel's compile-time
-        // slice stride and a row's windows fill its tile columns about as well as the general form's tiles fill a band
-        const int fix_tsz = i == 2 ? E2_TSZ : i == 3 ? E3_TSZ : 0;
-        bool rowtiles = false;
-        if (fix_tsz && m->enc_rowtiles && !ctx->enc_plan[i].nbands && cin == (i == 2 ? 32 : 64) && m->enc_c[i + 1] == 2 * cin &&
-            (size_t)(RB + 2) * TC * px_bytes <= (size_t)fix_tsz) {
-            long long t_rows = (long long)Hp * ((Wp + 7) / 8), t_gen = 0;
-            for (int k = 0; k < nbands; k++) t_gen += ((((k + 1) * Hp) / nbands - (k * Hp) / nbands) * Wp + 7) / 8;
-            rowtiles = t_rows <= t_gen;
-        }
-        const size_t tile_bytes = rowtiles ? (size_t)BN_T * fix_tsz : (((size_t)BN_T * (RB + 2) * TC * px_bytes) + 15) & ~(size_t)15;
-        const size_t lds = nbuf * tile_bytes + scr_bytes;
-        if (lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
-        const int items = batch * nbands;
-        const int grid = std::min(items, wgs_per_cu * num_cu);
-        EncArgs a;
-        a.in = i == 1 ? ws.pbuf : act[i]; a.out = act[i + 1];
-        a.wfrag = (const half8 *)(prep + pr->enc[i].wfrag); a.epi = (const float *)(prep + pr->enc[i].epi);
-        a.B = batch; a.H = H; a.W = W; a.Hp = Hp; a.Wp = Wp; a.Ho = m->lv[i + 1].H; a.Wo = m->lv[i + 1].W;
-        a.oy = H & 1; a.ox = W & 1; a.To = (i == BN_LEVELS - 1) ? 1 : BN_T;
-        a.RB = RB; a.nbands = nbands; a.TR = RB + 2; a.TC = TC;
-        a.mWp = magic(Wp); a.mNb = magic(nbands); a.mRC = magic(TC * (cin / 8)); a.zero = prep + pr->zero;
-        a.nbuf = nbuf; a.buf_stride = (int)tile_bytes; a.scr_off = (int)(nbuf * tile_bytes);
-        a.plan = make_plan(grid, num_cu, wgs_per_cu, batch, nbands, Hp);
-        a.swz = rowtiles ? choose_swz_periodic(cin, W, Wp) : choose_swz(true, cin, W, Wp, RB / 2);
-        a.pidx = d_index; a.skip = act[1]; a.tm_pre = (const float *)(prep + pr->enc[0].epi) + 48;
-        a.model_ids = inp.model_ids; a.mstride = mstride;
-        int rc = COVAHIP_OK;
-        const bool ap = pr->allpos[i];
-        if (ms && i == 1) {
-            if (by_frames && !d_index && !dry) return COVAHIP_ERR_INVALID_ARG;
-            rc = ap ? set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, true, true, 0, true>, lds) : set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, false, true, 0, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc1_mfma");
-            if (ap) LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, true, true, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, false, true, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        } else if (ms && i == 2 && rowtiles) {
-            rc = ap ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ, true>, lds)
-                    : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc2_mfma");
-            if (ap) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-        } else if (ms && i == 2) {
-            rc = ap ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true, false, 0, true>, lds) : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false, false, 0, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc2_mfma");
-            if (ap) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true, false, 0, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false, false, 0, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-        } else if (ms && rowtiles) {
-            rc = ap ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ, true>, lds)
-                    : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc3_mfma");
-            if (ap) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        } else if (ms) {
-            rc = ap ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true, false, 0, true>, lds) : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false, false, 0, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc3_mfma");
-            if (ap) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true, false, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false, false, 0, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        } else if (i == 1) {
-            // (a null table means "stack b = frames 4b .. 4b+3" to this kernel: a carrier-frame call must bring its table)
-            if (by_frames && !d_index && !dry) return COVAHIP_ERR_INVALID_ARG;
-            // the round-1..3 level-1 kernel: grids wider than enc1_mfma's LDS row, developer band plans, set_impl(5)
-            rc = pr->allpos[i] ? set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, true, true>, lds) : set_lds(ctx, enc_mfma<16, 32, 2, 4, 8, true, false, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc1_mfma");
-            if (pr->allpos[i]) LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<16, 32, 2, 4, 8, true, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        } else if (i == 2 && rowtiles) {
-            rc = pr->allpos[i] ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ>, lds)
-                               : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc2_mfma");
-            if (pr->allpos[i]) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true, false, E2_TSZ>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false, false, E2_TSZ>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-        } else if (i == 2) {
-            rc = pr->allpos[i] ? set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, true>, lds) : set_lds(ctx, enc_mfma<32, 64, 4, 2, 4, true, false>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc2_mfma");
-            if (pr->allpos[i]) LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, true>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<32, 64, 4, 2, 4, true, false>), dim3(grid), dim3(WG), lds, ctx->stream, a);
-        } else if (rowtiles) {
-            rc = pr->allpos[i] ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ>, lds)
-                               : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc3_mfma");
-            if (pr->allpos[i]) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true, false, E3_TSZ>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false, false, E3_TSZ>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        } else {
-            rc = pr->allpos[i] ? set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, true>, lds) : set_lds(ctx, enc_mfma<64, 128, 2, 2, 8, true, false>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "enc3_mfma");
-            if (pr->allpos[i]) LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, true>), dim3(grid), dim3(512), lds, ctx->stream, a);
-            else LAUNCH((enc_mfma<64, 128, 2, 2, 8, true, false>), dim3(grid), dim3(512), lds, ctx->stream, a);
-        }
-        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    }
-    // ---------------- decoder blocks 0..2 in one launch when a frame's three input tiles fit in LDS together
-    int first_dec = 0;
-    if (m->fuse_dec && m->dec_ci[0] == 128 && m->dec_ci[1] == 128 && m->dec_ci[2] == 64 && m->dec_co[0] == 64 &&
-        m->dec_co[1] == 32 && m->dec_co[2] == 16) {
-        Dec012Args a;
-        size_t off = 0;
-        for (int j = 0; j < 3; j++) {
-            const BnLevelGeom in = m->lv[BN_LEVELS - j], out = m->lv[BN_LEVELS - 1 - j];
-            DecLvl &g = a.lv[j];
-            g.Hi = in.H; g.Wi = in.W; g.Hd = out.H; g.Wd = out.W; g.cy = m->dec_cy[j]; g.cx = m->dec_cx[j];
-            g.mGW = magic(in.W + 1);
-            g.mRC = magic((in.W + 2) * (m->dec_ci[j] / 8));
-            g.swz = choose_swz(false, m->dec_ci[j], in.W, 0, in.H + 1);
-            g.tile_off = (int)off;
-            off += (((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2) + 255) & ~(size_t)255;   // 256: dec012_block's xor addressing
-            a.skip[j] = act[BN_LEVELS - j];
-            a.Ts[j] = j == 0 ? 1 : BN_T;
-            a.wf[j] = (const half8 *)(prep + pr->dec[j].wfrag);
-            a.epi[j] = (const float *)(prep + pr->dec[j].epi);
-        }
-        a.scr_off = (int)off;
-        const size_t lds = off + 8 * 2048;
-        if (lds <= 160 * 1024 - 256) {
-            a.out = dact[2]; a.B = batch; a.zero = prep + pr->zero;
-            a.model_ids = inp.model_ids; a.mstride = mstride;
-            int rc = ms ? set_lds(ctx, dec012_mfma<true>, lds) : set_lds(ctx, dec012_mfma<>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec012_mfma");
-            if (ms) LAUNCH(dec012_mfma<true>, dim3(std::min(batch, num_cu)), dim3(512), lds, ctx->stream, a);
-            else LAUNCH(dec012_mfma<>, dim3(std::min(batch, num_cu)), dim3(512), lds, ctx->stream, a);
-            COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-            first_dec = 3;
-        }
-    }
-    // ---------------- decoder blocks 0..3 (the last one carries the folded final conv + threshold)
-    for (int j = first_dec; j < BN_LEVELS; j++) {
-        const BnLevelGeom in = m->lv[BN_LEVELS - j], out = m->lv[BN_LEVELS - 1 - j];
-        const bool last = j == BN_LEVELS - 1;
-        const bool half = last && part_written;                 // the last block on its "up" half + partial logits
-        const int ci_j = half ? m->dec_ci[j] / 2 : m->dec_ci[j];
-        DecArgs a;
-        a.up = j == 0 ? nullptr : dact[j - 1];
-        a.skip = act[BN_LEVELS - j];
-        a.out = last ? nullptr : dact[j];
-        a.logits = last ? d_logits : nullptr;
-        a.mask = last ? d_mask : nullptr;
-        a.wfrag = (const half8 *)(prep + (half ? pr->final_w_up : last ? pr->final_w : pr->dec[j].wfrag));
-        a.part = half ? ws.part : nullptr;
-        a.epi = (const float *)(prep + (last ? pr->final_epi : pr->dec[j].epi));
-        a.B = batch; a.Hi = in.H; a.Wi = in.W; a.Hd = out.H; a.Wd = out.W; a.cy = m->dec_cy[j]; a.cx = m->dec_cx[j];
-        a.Ts = j == 0 ? 1 : BN_T;
-        const DecMs am{inp.model_ids, mstride};
-        const int GH = in.H + 1;
-        const size_t row_bytes = (size_t)(in.W + 2) * ci_j * 2;
-        // band planner.  A workgroup keeps its M-tile's weight fragments in registers, so the weights
-        // cross the L2 -> CU path once per workgroup: block 0 (256 KB of fragments per workgroup) runs
-        // one workgroup per CU over whole frames.  The lighter blocks are bound by the latency of
-        // stage -> barrier -> compute, which only other workgroups on the CU can hide: bands of at most
-        // ~30 KB of LDS so that four to five of them are resident per CU.
-        const size_t wbytes = (size_t)(last ? 1 : 4 * m->dec_co[j] / 32) * (4 * ci_j / 16) * 1024;
-        const bool heavy = wbytes >= 192 * 1024 && (size_t)(GH + 1) * row_bytes <= 72 * 1024;
-        int nbands = 1;
-        if (!heavy)
-            while (nbands < GH && (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes > 30 * 1024 ||
-                                   (long long)batch * nbands < 2LL * num_cu))
-                nbands++;
-        a.nbands = nbands; a.mNb = magic(nbands); a.mGW = magic(in.W + 1);
-        a.mRC = magic((in.W + 2) * (ci_j / 8)); a.zero = prep + pr->zero;
-        a.swz = choose_swz(false, ci_j, in.W, 0, (GH + nbands - 1) / nbands);
-        const size_t tile_bytes = (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes + 15) & ~(size_t)15;
-        const size_t mask_bytes = last ? ((((size_t)2 * ((GH + nbands - 1) / nbands) * out.W) + 15) & ~(size_t)15) : 0;
-        const size_t scr_bytes = last ? 0 : (size_t)std::max(4, 4 * m->dec_co[j] / 32) * 2048;   // one 2 KB transpose scratch per wave
-        const size_t lds = tile_bytes + mask_bytes + scr_bytes;
-        a.mask_off = (int)tile_bytes;
-        a.scr_off = (int)tile_bytes;
-        if (lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
-        const int items = batch * nbands;
-        const int grid = std::min(items, (heavy ? 1 : 4) * num_cu);
-        int rc;
-        if (j == 0) {
-            rc = ms ? set_lds(ctx, dec_mfma<0, 128, 64, false, true>, lds) : set_lds(ctx, dec_mfma<0, 128, 64, false>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec0_mfma");
-            if (ms) LAUNCH((dec_mfma<0, 128, 64, false, true>), dim3(grid), dim3(512), lds, ctx->stream, a, am);
-            else LAUNCH((dec_mfma<0, 128, 64, false>), dim3(grid), dim3(512), lds, ctx->stream, a, am);
-        } else if (j == 1) {
-            rc = ms ? set_lds(ctx, dec_mfma<64, 64, 32, false, true>, lds) : set_lds(ctx, dec_mfma<64, 64, 32, false>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec1_mfma");
-            if (ms) LAUNCH((dec_mfma<64, 64, 32, false, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-            else LAUNCH((dec_mfma<64, 64, 32, false>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-        } else if (j == 2) {
-            rc = ms ? set_lds(ctx, dec_mfma<32, 32, 16, false, true>, lds) : set_lds(ctx, dec_mfma<32, 32, 16, false>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec2_mfma");
-            if (ms) LAUNCH((dec_mfma<32, 32, 16, false, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-            else LAUNCH((dec_mfma<32, 32, 16, false>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-        } else if (cc && m->fuse_tail && [&]() -> bool {
-                       // last block + bboxcc in one launch when the frame's LDS plan fits: two band buffers (which
-                       // bboxcc's region reuses) + the frame's mask bytes
-                       Dec3ccArgs t;
-                       size_t cc_bytes = ccbody::cc_plan(out.H, out.W, t.g);
-                       // the run-based body (bboxcc_wave.h) when the shape allows it: worst-case run capacity, nothing overflows
-                       t.use_wv = ctx->cc_wave_cap >= 0 && ccwave::wv_plan(out.H, out.W, ((out.H + 1) / 2) * ((out.W + 1) / 2), t.wg) ? 1 : 0;
-                       if (t.use_wv) cc_bytes = (size_t)t.wg.wave_bytes;
-                       if (!cc_bytes) return false;
-                       const size_t mfull = ((size_t)out.H * out.W + 15) & ~(size_t)15;
-                       const size_t partb = half ? (size_t)GH * (in.W + 1) * 16 : 0;   // partial logits beside the mask
-                       int best_nb = 0;
-                       long long best_cost = -1;
-                       for (int nb = 1; nb <= GH; nb++) {
-                           const size_t tb = (((size_t)((GH + nb - 1) / nb) + 1) * row_bytes + 15) & ~(size_t)15;
-                           const size_t nbuf = nb == 1 ? 1 : 2;   // the whole frame in one buffer when it fits
-                           if (std::max(nbuf * tb, cc_bytes) + mfull + partb > 160 * 1024 - 512) continue;
-                           long long rounds = 0;   // tiles of 32 positions over 16 waves, band by band
-                           for (int k = 0; k < nb; k++) {
-                               const int nu = (k + 1) * GH / nb - k * GH / nb;
-                               rounds += ((nu * (in.W + 1) + 31) / 32 + 15) / 16;
-                           }
-                           const long long cost = rounds * 8 + nb;   // a band costs a barrier + DMA issue on top of its tiles
-                           if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_nb = nb; }
-                       }
-                       if (!best_nb) return false;
-                       const size_t tb = (((size_t)((GH + best_nb - 1) / best_nb) + 1) * row_bytes + 15) & ~(size_t)15;
-                       t.d = a;
-                       t.ms = am;
-                       t.d.nbands = best_nb; t.d.mNb = magic(best_nb);
-                       t.d.swz = choose_swz(false, ci_j, in.W, 0, (GH + best_nb - 1) / best_nb);
-                       t.boxes = cc->boxes; t.counts = cc->counts;
-                       t.area_thresh = cc->area_thresh; t.max_boxes = cc->max_boxes;
-                       t.tile_bytes = (int)tb; t.cc_off = 0;
-                       t.mfull_off = (int)std::max((best_nb == 1 ? 1 : 2) * tb, cc_bytes);
-                       t.part_off = (int)((size_t)t.mfull_off + mfull);
-                       const size_t tl = (size_t)t.part_off + partb;
-                       const dim3 grid3(std::min(batch, 2 * num_cu)), wg3(ccbody::CC_THREADS);
-                       // row tiles + ballots straight into bboxcc's planes (dec3cc_rows_mfma) when the shape allows it
-                       if (half && t.use_wv && best_nb == 1 && in.W + 1 <= 64 && m->tail_rows && (out.W & 7) == 0 &&
-                           (size_t)t.wg.rows_bytes <= mfull && (!d_mask || (reinterpret_cast<uintptr_t>(d_mask) & 3) == 0)) {
-                           t.d.swz = Swz{3, 1, 0, 0, 0};            // s = (xx >> 3) & 1 (what the staging of both forms evaluates)
-                           t.d.mRC = magic(out.W / 4);               // the mask expansion's division
-                           if (ms ? set_lds(ctx, dec3cc_rows_mfma<true>, tl) : set_lds(ctx, dec3cc_rows_mfma<>, tl)) return false;
-                           ProfScope ps(ctx, "dec3_bboxcc_fused");
-                           if (ms) LAUNCH(dec3cc_rows_mfma<true>, grid3, wg3, tl, ctx->stream, t);
-                           else LAUNCH(dec3cc_rows_mfma<>, grid3, wg3, tl, ctx->stream, t);
-                           return true;
-                       }
-                       if (ms) {
-                           auto k = t.use_wv ? (half ? dec3cc_mfma<true, true, true> : dec3cc_mfma<true, false, true>)
-                                             : (half ? dec3cc_mfma<false, true, true> : dec3cc_mfma<false, false, true>);
-                           if (set_lds(ctx, k, tl)) return false;
-                           ProfScope ps(ctx, "dec3_bboxcc_fused");
-                           LAUNCH(k, grid3, wg3, tl, ctx->stream, t);
-                           return true;
-                       }
-                       if (half) {
-                           if (t.use_wv ? set_lds(ctx, dec3cc_mfma<true, true>, tl) : set_lds(ctx, dec3cc_mfma<false, true>, tl)) return false;
-                           ProfScope ps(ctx, "dec3_bboxcc_fused");
-                           if (t.use_wv) LAUNCH((dec3cc_mfma<true, true>), grid3, wg3, tl, ctx->stream, t);
-                           else LAUNCH((dec3cc_mfma<false, true>), grid3, wg3, tl, ctx->stream, t);
-                           return true;
-                       }
-                       if (t.use_wv ? set_lds(ctx, dec3cc_mfma<true, false>, tl) : set_lds(ctx, dec3cc_mfma<false, false>, tl)) return false;
-                       ProfScope ps(ctx, "dec3_bboxcc_fused");
-                       if (t.use_wv) LAUNCH((dec3cc_mfma<true, false>), grid3, wg3, tl, ctx->stream, t);
-                       else LAUNCH((dec3cc_mfma<false, false>), grid3, wg3, tl, ctx->stream, t);
-                       return true;
-                   }()) {
-            if (cc_done) *cc_done = true;
-        } else if (half) {
-            rc = ms ? set_lds(ctx, dec_mfma<16, 0, 16, true, true>, lds) : set_lds(ctx, dec_mfma<16, 0, 16, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec3_final_mfma");
-            if (ms) LAUNCH((dec_mfma<16, 0, 16, true, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-            else LAUNCH((dec_mfma<16, 0, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-        } else {
-            rc = ms ? set_lds(ctx, dec_mfma<16, 16, 16, true, true>, lds) : set_lds(ctx, dec_mfma<16, 16, 16, true>, lds);
-            if (rc) return rc;
-            ProfScope ps(ctx, "dec3_final_mfma");
-            if (ms) LAUNCH((dec_mfma<16, 16, 16, true, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-            else LAUNCH((dec_mfma<16, 16, 16, true>), dim3(grid), dim3(256), lds, ctx->stream, a, am);
-        }
-        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    }
-    return COVAHIP_OK;
+    if (rc) return rc;
+    if (!run_dec012(f, rc))
+        for (int j = 0; j < BN_LEVELS - 1 && !rc; j++) rc = run_dec_block(f, j);
+    if (rc) return rc;
+    DecPlan last;
+    rc = plan_dec_block(f, BN_LEVELS - 1, last);
+    if (rc) return rc;
+    if (!(cc && m->fuse_tail && run_tail_fused(f, last))) return launch_dec_block(f, BN_LEVELS - 1, last);
+    if (cc_done) *cc_done = true;   // bboxcc ran in the same launch
+    return launched(f, COVAHIP_OK);
 }
 
 #if defined(PHASE_TIMING) || defined(WGSPAN_ONLY)

@@ -71,13 +71,19 @@ CASES = [
 _RATIOS = {}   # stage -> worst ratio over the module (printed at the end for the record in the docstring)
 
 
+PROF_SCOPES = {"enc0p_mfma", "enc1_mfma", "enc2_mfma", "enc3_mfma", "enc23_mfma", "dec012_mfma", "dec0_mfma", "dec1_mfma", "dec2_mfma",
+               "dec3_final_mfma", "dec3_bboxcc_fused"}
+
+
 def _prof_scopes():
+    """The profile names blobnet_mfma.hip launches under: the second argument of its launch helper."""
     src = open(os.path.join(ROOT, "cova_amd", "csrc", "blobnet_mfma.hip")).read()
-    return set(re.findall(r'ProfScope ps\(ctx, "([a-z0-9_]+)"\)', src))
+    return set(re.findall(r'\blaunch\(f, "([a-z0-9_]+)"', src))
 
 
 def test_cases_cover_every_profile_scope():
     """Across the module every kernel of blobnet_mfma.hip's ProfScopes is REQUIRED to launch by some case."""
+    assert _prof_scopes() == PROF_SCOPES, sorted(_prof_scopes() ^ PROF_SCOPES)   # (an extraction that finds nothing proves nothing)
     must = ALWAYS.union(*(c[6] for c in CASES))
     assert _prof_scopes() <= must, sorted(_prof_scopes() - must)
 
