@@ -1202,25 +1202,27 @@ int covahip_gopfilter_counters(const covahip_gopfilter *g, uint64_t *dropped, ui
 #include <charconv>
 #include <string>
 
-namespace {
-
-uint32_t crc32c_table[256];
-bool crc32c_ready = false;
-uint32_t crc32c(const uint8_t *p, size_t n) {  // Castagnoli, reflected, as TFRecord uses it
-    if (!crc32c_ready) {
-        for (uint32_t i = 0; i < 256; i++) {
-            uint32_t c = i;
-            for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
-            crc32c_table[i] = c;
+// Castagnoli, reflected, as TFRecord uses it.  Declared in internal.h: the trainer's state blob (train.hip) ends with one.
+uint32_t covahip_crc32c(const uint8_t *p, size_t n) {
+    static const struct Table {
+        uint32_t t[256];
+        Table() {
+            for (uint32_t i = 0; i < 256; i++) {
+                uint32_t c = i;
+                for (int k = 0; k < 8; k++) c = (c & 1) ? (c >> 1) ^ 0x82F63B78u : c >> 1;
+                t[i] = c;
+            }
         }
-        crc32c_ready = true;
-    }
+    } table;
     uint32_t c = 0xFFFFFFFFu;
-    for (size_t i = 0; i < n; i++) c = crc32c_table[(c ^ p[i]) & 0xFF] ^ (c >> 8);
+    for (size_t i = 0; i < n; i++) c = table.t[(c ^ p[i]) & 0xFF] ^ (c >> 8);
     return c ^ 0xFFFFFFFFu;
 }
+
+namespace {
+
 uint32_t masked_crc(const uint8_t *p, size_t n) {
-    const uint32_t c = crc32c(p, n);
+    const uint32_t c = covahip_crc32c(p, n);
     return ((c >> 15) | (c << 17)) + 0xa282ead8u;
 }
 void put_varint(std::string &s, uint64_t v) {

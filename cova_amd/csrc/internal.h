@@ -117,6 +117,9 @@ int covahip_primary_op(covahip_ctx *ctx);
 // Blocks until every lane and the primary stream have drained.
 int covahip_sync_all(covahip_ctx *ctx);
 
+// hostlib.cpp: CRC-32C (Castagnoli, reflected) of n bytes, the TFRecord checksum before masking
+uint32_t covahip_crc32c(const uint8_t *p, size_t n);
+
 // bboxcc.hip
 int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, int h, int w, int area_thresh,
                           covahip_box *d_boxes, int32_t *d_counts, int max_boxes);

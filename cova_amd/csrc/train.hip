@@ -1,4 +1,5 @@
-// BlobNet training step on gfx950: forward, backward and Adam in fp32 (include/covahip.h, "BlobNet training").
+// BlobNet training step on gfx950: forward, backward and Adam in fp32 (include/covahip.h, "BlobNet training"); the evaluation
+// pass over the same forward kernels and the trainer's state blob ("Evaluation and resume").
 //
 // Layout: every activation is channels-first, NCTHW for the encoder ([B][C][T][H][W]) and NCHW for the decoder (T = 1: the
 // decoder only sees the t = 0 slice of each encoder level, tests/torch_blobnet.py).  Channels-first keeps each channel's
@@ -15,6 +16,7 @@
 // with the model's own batch b from the per-step table (MStep): element counts, slab counts and chunk lengths are all computed
 // from b in the kernel, so model m's arithmetic and summation order are those of a solo trainer at batch b.  Grids are sized
 // for the step's largest batch; a workgroup outside its model's extent (all of them when b = 0) leaves at once.
+#include <algorithm>
 #include <climits>
 #include <cmath>
 #include <cstring>
@@ -740,6 +742,60 @@ __global__ void k_final_bwd(Mdl md, const float *__restrict__ logit, const uint8
     if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
 
+// ------------------------------------------------------------------------------------------------ evaluation kernels
+// The evaluation pass (include/covahip.h, "Evaluation and resume") runs the forward kernels above unchanged.  Two things differ
+// from a training forward.  BatchNorm: k_eval_stat below fills `stat` from the moving statistics, in place of the reduce /
+// finalize launches that fill it from the batch.  Dropout: every site gets threshold 0 and scale 1; keep() compares an unsigned
+// value with >= 0, which holds for every hash, and returns the scale 1.0f, and x * 1.0f is x for every float (the products
+// dropped are ReLU outputs: no NaN payloads to quieten), so the site is the identity bit for bit.
+struct EvalBN {                       // where the seven BN layers keep their moving statistics in the flat parameters
+    int32_t mean[2 * NL - 1], var[2 * NL - 1], C[2 * NL - 1];
+};
+// stat[layer] = (moving mean, 1 / sqrt(moving variance + eps)): the expression k_finalize(F_VAR) forms from the batch variance
+template <bool SET>
+__global__ void k_eval_stat(Mdl md, const float *__restrict__ params, float *__restrict__ stat, EvalBN t, float eps) {
+    const int layer = blockIdx.x, c = threadIdx.x, C = t.C[layer];
+    if (model_b<SET>(md) == 0 || c >= C) return;
+    params += POFF;
+    stat += blockIdx.z * STAT_STRIDE + layer * 256;
+    stat[c] = params[t.mean[layer] + c];
+    stat[C + c] = 1.f / sqrtf(params[t.var[layer] + c] + eps);
+}
+
+// TP / FP / FN at sigmoid > 0.5 as k_final_bwd counts them (integer atomics; the counters run on over the chunks of one
+// evaluation), and the per-sample Jaccard distance as k_loss forms it, to sample_loss[model][sample of the chunk].
+// red = [I per sample][S per sample] of the model's chunk.
+template <bool SET>
+__global__ void k_eval_tail(Mdl md, const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
+                            int64_t hw, float sm, unsigned long long *__restrict__ counts, float *__restrict__ sample_loss) {
+    __shared__ unsigned cnt[3];
+    const int B = model_b<SET>(md);
+    if ((int64_t)blockIdx.x * BLK >= (int64_t)B * hw) return;   // the whole workgroup: before the barrier
+    logit += MOFF(hw);
+    gt += (int64_t)model_first<SET>(md) * hw;
+    red += blockIdx.z * red_stride(md.maxB);
+    counts += 3 * blockIdx.z;
+    if (blockIdx.x == 0) {
+        sample_loss += (int64_t)blockIdx.z * md.maxB;
+        for (int b = threadIdx.x; b < B; b += BLK) {
+            const float I = red[b], S = red[B + b];
+            sample_loss[b] = (1.f - (I + sm) / (S - I + sm)) * sm;
+        }
+    }
+    if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    if (i < (int64_t)B * hw) {
+        const float pr = 1.f / (1.f + expf(-logit[i]));
+        const bool pos = pr > 0.5f, lab = gt[i] != 0;
+        if (pos && lab) atomicAdd(&cnt[0], 1u);
+        if (pos && !lab) atomicAdd(&cnt[1], 1u);
+        if (!pos && lab) atomicAdd(&cnt[2], 1u);
+    }
+    __syncthreads();
+    if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
+}
+
 // Keras Adam over the flat parameter buffer; lr_t = lr * sqrt(1 - b2^t) / (1 - b1^t) from the host
 template <bool SET>
 __global__ void k_adam(Mdl md, float *__restrict__ w, const float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
@@ -796,6 +852,7 @@ struct covahip_train {
     MStep *d_tab = nullptr;    // [K]
     MStep *h_tab = nullptr;    // pinned
     float *h_loss = nullptr;   // pinned [K]
+    float *d_sample_loss = nullptr, *h_sample_loss = nullptr;   // evaluation: [K][max_batch] per-sample losses of a chunk (h_: pinned)
     unsigned long long *h_counts = nullptr;   // pinned [K][3]
 };
 
@@ -814,6 +871,7 @@ void free_train(covahip_train *tr) {
     for (void *q : tr->allocs) hipFree(q);
     if (tr->h_tab) hipHostFree(tr->h_tab);
     if (tr->h_loss) hipHostFree(tr->h_loss);
+    if (tr->h_sample_loss) hipHostFree(tr->h_sample_loss);
     if (tr->h_counts) hipHostFree(tr->h_counts);
     delete tr;
 }
@@ -1011,6 +1069,65 @@ int run_step(covahip_train *tr, int B) {
     return COVAHIP_OK;
 }
 
+// The inference-mode forward of one chunk of every model with a non-zero b in tr->h_tab (K > 1: already uploaded), then the
+// per-sample losses into d_sample_loss and TP / FP / FN added to d_counts.  Writes activations, stat, red and slab only, all of
+// which a training step rewrites before it reads them; never grads, parameters or Adam moments.
+int run_eval(covahip_train *tr, int B) {
+    Run r{tr, tr->ctx->stream, Mdl{tr->K > 1 ? tr->d_tab : nullptr, tr->cfg.max_batch, (int64_t)tr->slab_floats, tr->h_tab[0].b, 0.f}, B};
+    const hipStream_t s = r.s;
+    const Mdl md = r.md;
+    const float *P = tr->params;
+    const int H0 = tr->H[0], W0 = tr->W[0];
+    const DropS off{0, 0u, 1.f, 0};   // the identity (see k_eval_stat)
+    auto stat = [&](int layer) { return tr->stat + layer * 256; };
+    EvalBN bn;
+    for (int i = 0; i < NL; i++) {
+        bn.mean[i] = (int32_t)tr->eo[i].mean;
+        bn.var[i] = (int32_t)tr->eo[i].var;
+        bn.C[i] = ENC_C[i + 1];
+    }
+    for (int j = 0; j < NL - 1; j++) {
+        bn.mean[NL + j] = (int32_t)tr->dof[j].mean;
+        bn.var[NL + j] = (int32_t)tr->dof[j].var;
+        bn.C[NL + j] = DEC_CO[j];
+    }
+    KL(k_eval_stat, (dim3(2 * NL - 1, 1, tr->K)), 128, md, P, tr->stat, bn, tr->cfg.bn_eps);
+    KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
+    for (int i = 0; i < NL; i++) {
+        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
+        const EncOff &o = tr->eo[i];
+        const float *xin = i ? tr->e[i - 1] : tr->x0;
+        KL(k_conv3_fwd, (r.g1((int64_t)B * Co * TT * H * W)), BLK, md, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
+        KL(k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, md, tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
+                                                                      Co, H, W, Hp, Wp);
+        const int zj = NL - 1 - i;
+        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
+        KL(k_tmix_fwd, (r.g1((int64_t)B * Co * Hp * Wp)), BLK, md, tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
+                                                                 Co, (int64_t)Hp * Wp, off, off);
+        if (!r.ok()) return r.rc;
+    }
+    for (int j = 0; j < NL; j++) {
+        const int Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
+        const DecOff &o = tr->dof[j];
+        const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
+        KL(k_drop_relu, (r.g1(B * per)), BLK, md, tr->z[j], tr->zd[j], per, off);
+        KL(k_convT_fwd, (r.g1(B * Co * So)), BLK, md, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                      tr->cx[j]);
+        if (j < NL - 1)
+            KL(k_bn_apply, (r.g1(B * Co * So)), BLK, md, tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1],
+                                                         Co, So);
+        if (!r.ok()) return r.rc;
+    }
+    const int64_t hw = (int64_t)H0 * W0;
+    KL(k_final_fwd, (r.g1(B * hw)), BLK, md, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
+    r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, red_stride(tr->cfg.max_batch), nullptr, nullptr,
+             nullptr, nullptr);
+    KL(k_eval_tail, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
+    if (!r.ok()) return r.rc;
+    return COVAHIP_OK;
+}
+
 bool finite_pos(float v) { return std::isfinite(v) && v > 0.f; }
 
 int validate_cfg(const covahip_train_cfg *c) {
@@ -1103,12 +1220,14 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     tr->slab_floats = slab;
     TA(tr->d_loss, K);
     TA(tr->d_counts, (size_t)K * 3);
+    TA(tr->d_sample_loss, B);
     TA(tr->d_stack, B * TT * hw0 * 4);
     TA(tr->d_gt, B * hw0);
     TA(tr->d_tab, K);
 #undef TA
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_tab, (size_t)K * sizeof(MStep), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_loss, (size_t)K * sizeof(float), hipHostMallocDefault));
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_sample_loss, (size_t)B * sizeof(float), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_counts, (size_t)K * 3 * sizeof(unsigned long long), hipHostMallocDefault));
     // BN moving statistics are not trained
     std::vector<uint8_t> tmask(N_PARAMS, 1);
@@ -1175,6 +1294,107 @@ int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
         tr->step[k]++;
     }
     return COVAHIP_OK;
+}
+
+// Evaluation of counts[k] samples of model k (packed in model order), in chunks of max_batch per model.
+int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *counts, float *sample_loss, float *logits,
+              covahip_train_eval_result *out, int mem_kind) {
+    const int K = tr->K, mb = tr->cfg.max_batch;
+    std::vector<int64_t> base(K);
+    int64_t total = 0;
+    int32_t cmax = 0;
+    for (int k = 0; k < K; k++) {
+        if (counts[k] < 0) return COVAHIP_ERR_INVALID_ARG;
+        base[k] = total;
+        total += counts[k];
+        cmax = std::max(cmax, counts[k]);
+    }
+    if (total == 0 || total > INT32_MAX) return COVAHIP_ERR_INVALID_ARG;
+    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const size_t hw = (size_t)tr->H[0] * tr->W[0], stack_b = TT * hw * 4;
+    const bool host = mem_kind == COVAHIP_MEM_HOST;
+    const hipMemcpyKind in_kind = host ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+    const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    const int nchunks = (cmax + mb - 1) / mb;
+    std::vector<double> loss_sum(K, 0.0);
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), s));
+    for (int c = 0; c < nchunks; c++) {
+        int first = 0, bmax = 0;
+        for (int k = 0; k < K; k++) {
+            MStep &ms = tr->h_tab[k];
+            std::memset(&ms, 0, sizeof ms);   // keys and lr_t: unused
+            ms.b = (int32_t)std::min<int64_t>(mb, std::max<int64_t>(0, (int64_t)counts[k] - (int64_t)c * mb));
+            ms.first = first;
+            first += ms.b;
+            bmax = std::max(bmax, ms.b);
+        }
+        if (nchunks == 1) {   // the caller's packing is the chunk's
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * stack_b, in_kind, s));
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, in_kind, s));
+        } else {
+            for (int k = 0; k < K; k++) {
+                const MStep &ms = tr->h_tab[k];
+                if (!ms.b) continue;
+                const size_t src = (size_t)(base[k] + (int64_t)c * mb);
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack + (size_t)ms.first * stack_b, stack + src * stack_b, (size_t)ms.b * stack_b,
+                                                      in_kind, s));
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt + (size_t)ms.first * hw, gt + src * hw, (size_t)ms.b * hw, in_kind, s));
+            }
+        }
+        if (K > 1) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_tab, tr->h_tab, (size_t)K * sizeof(MStep), hipMemcpyHostToDevice, s));
+        if (int rc = run_eval(tr, bmax)) return rc;
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_sample_loss, tr->d_sample_loss, (size_t)K * mb * sizeof(float), hipMemcpyDeviceToHost, s));
+        for (int k = 0; k < K; k++) {
+            const int b = tr->h_tab[k].b;
+            if (!b) continue;
+            const size_t dst = (size_t)(base[k] + (int64_t)c * mb);
+            if (logits)
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(logits + dst * hw, tr->logit + (size_t)k * mb * hw, (size_t)b * hw * sizeof(float),
+                                                      out_kind, s));
+            if (sample_loss && !host)
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(sample_loss + dst, tr->d_sample_loss + (size_t)k * mb, (size_t)b * sizeof(float),
+                                                      out_kind, s));
+        }
+        COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // h_tab and h_sample_loss are reused by the next chunk
+        for (int k = 0; k < K; k++) {
+            const int b = tr->h_tab[k].b;
+            const float *sl = tr->h_sample_loss + (size_t)k * mb;
+            for (int i = 0; i < b; i++) loss_sum[k] += (double)sl[i];
+            if (b && sample_loss && host) std::memcpy(sample_loss + base[k] + (int64_t)c * mb, sl, (size_t)b * sizeof(float));
+        }
+    }
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_counts, tr->d_counts, (size_t)K * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    for (int k = 0; k < K; k++) {
+        covahip_train_eval_result &o = out[k];
+        o = covahip_train_eval_result{};
+        if (!counts[k]) continue;
+        o.loss = loss_sum[k] / (double)counts[k];
+        o.tp = (int64_t)tr->h_counts[(size_t)k * 3];
+        o.fp = (int64_t)tr->h_counts[(size_t)k * 3 + 1];
+        o.fn = (int64_t)tr->h_counts[(size_t)k * 3 + 2];
+        o.samples = counts[k];
+    }
+    return COVAHIP_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ trainer state blob
+constexpr uint32_t S_MAGIC = 0x53485643;  // "CVHS"
+constexpr uint32_t S_VERSION = 1;
+constexpr size_t S_HEADER = 64, S_MODEL = 16 + 3 * N_PARAMS * sizeof(float);
+size_t state_bytes(size_t n_models) { return S_HEADER + n_models * S_MODEL + 4; }
+
+template <class T>
+void put(uint8_t *p, size_t off, T v) { std::memcpy(p + off, &v, sizeof v); }
+template <class T>
+T get(const uint8_t *p, size_t off) {
+    T v;
+    std::memcpy(&v, p + off, sizeof v);
+    return v;
 }
 
 }  // namespace
@@ -1287,6 +1507,91 @@ int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n) {
 }
 
 int covahip_train_grads(covahip_train *tr, float *flat, size_t n) { return covahip_train_grads_m(tr, 0, flat, n); }
+
+int covahip_train_eval_set(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *counts, float *sample_loss,
+                           float *logits, covahip_train_eval_result *out, int mem_kind) {
+    if (!tr || !stack || !gt || !counts || !out) return COVAHIP_ERR_INVALID_ARG;
+    return eval_body(tr, stack, gt, counts, sample_loss, logits, out, mem_kind);
+}
+
+int covahip_train_eval(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, int n, float *sample_loss, float *logits,
+                       covahip_train_eval_result *out, int mem_kind) {
+    if (!tr || !stack || !gt || !out || n < 1 || tr->K != 1) return COVAHIP_ERR_INVALID_ARG;
+    const int32_t count = n;
+    return eval_body(tr, stack, gt, &count, sample_loss, logits, out, mem_kind);
+}
+
+int covahip_train_state_size(covahip_train *tr, size_t *n) {
+    if (!tr || !n) return COVAHIP_ERR_INVALID_ARG;
+    *n = state_bytes((size_t)tr->K);
+    return COVAHIP_OK;
+}
+
+int covahip_train_save_state(covahip_train *tr, uint64_t user_tag, void *buf, size_t cap, size_t *n) {
+    if (!tr || !n) return COVAHIP_ERR_INVALID_ARG;
+    const size_t need = state_bytes((size_t)tr->K);
+    *n = need;
+    if (!buf || cap < need) return COVAHIP_ERR_OVERFLOW;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    const covahip_train_cfg &cf = tr->cfg;
+    put<uint32_t>(p, 0, S_MAGIC);
+    put<uint32_t>(p, 4, S_VERSION);
+    put<uint32_t>(p, 8, (uint32_t)tr->K);
+    put<uint32_t>(p, 12, (uint32_t)N_PARAMS);
+    put<int32_t>(p, 16, cf.h_mb);
+    put<int32_t>(p, 20, cf.w_mb);
+    const float scalars[8] = {cf.lr, cf.beta1, cf.beta2, cf.eps, cf.bn_momentum, cf.bn_eps, cf.dropout, cf.smooth};
+    std::memcpy(p + 24, scalars, sizeof scalars);
+    put<uint64_t>(p, 56, user_tag);
+    const size_t pb = N_PARAMS * sizeof(float);
+    for (int k = 0; k < tr->K; k++) {
+        uint8_t *q = p + S_HEADER + (size_t)k * S_MODEL;
+        put<uint64_t>(q, 0, (uint64_t)tr->step[k]);
+        put<uint64_t>(q, 8, tr->seed[k]);
+        const float *src[3] = {tr->params, tr->adam_m, tr->adam_v};
+        for (int a = 0; a < 3; a++)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(q + 16 + a * pb, src[a] + (size_t)k * N_PARAMS, pb, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    put<uint32_t>(p, need - 4, covahip_crc32c(p, need - 4));
+    return COVAHIP_OK;
+}
+
+int covahip_train_load_state(covahip_train *tr, const void *buf, size_t n, uint64_t *user_tag) {
+    if (!tr || !buf) return COVAHIP_ERR_INVALID_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(buf);
+    if (n < S_HEADER + 4 || get<uint32_t>(p, 0) != S_MAGIC || get<uint32_t>(p, 4) != S_VERSION) return COVAHIP_ERR_BAD_DATA;
+    const uint32_t nm = get<uint32_t>(p, 8), np = get<uint32_t>(p, 12);
+    if (nm < 1 || nm > COVAHIP_MAX_MODELS || np == 0) return COVAHIP_ERR_BAD_DATA;
+    if (n != S_HEADER + (size_t)nm * (16 + 3 * (size_t)np * sizeof(float)) + 4) return COVAHIP_ERR_BAD_DATA;
+    if (get<uint32_t>(p, n - 4) != covahip_crc32c(p, n - 4)) return COVAHIP_ERR_BAD_DATA;
+    if ((int)nm != tr->K || np != N_PARAMS) return COVAHIP_ERR_INVALID_ARG;
+    for (int k = 0; k < tr->K; k++)
+        if (get<uint64_t>(p, S_HEADER + (size_t)k * S_MODEL) > (uint64_t)INT64_MAX) return COVAHIP_ERR_BAD_DATA;
+    covahip_ctx *ctx = tr->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    const size_t pb = N_PARAMS * sizeof(float);
+    for (int k = 0; k < tr->K; k++) {
+        const uint8_t *q = p + S_HEADER + (size_t)k * S_MODEL;
+        float *dst[3] = {tr->params, tr->adam_m, tr->adam_v};
+        for (int a = 0; a < 3; a++)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(dst[a] + (size_t)k * N_PARAMS, q + 16 + a * pb, pb, hipMemcpyHostToDevice, ctx->stream));
+    }
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, (size_t)tr->K * pb, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // buf is the caller's
+    for (int k = 0; k < tr->K; k++) {
+        const uint8_t *q = p + S_HEADER + (size_t)k * S_MODEL;
+        tr->step[k] = (int64_t)get<uint64_t>(q, 0);
+        tr->seed[k] = get<uint64_t>(q, 8);
+    }
+    std::fill(tr->last_counts.begin(), tr->last_counts.end(), 0);   // the loaded state describes no step
+    if (user_tag) *user_tag = get<uint64_t>(p, 56);
+    return COVAHIP_OK;
+}
 
 void covahip_train_destroy(covahip_train *tr) {
     if (!tr) return;

@@ -15,12 +15,25 @@ writes a weight file that covahip_blobnet_load / BlobNetInfer / the blobnetfilte
 trains one model per argument (several files of one model joined with commas; model k initialised and seeded with --seed + k)
 and writes OUTDIR/CAM0.cvhw, OUTDIR/CAM1.cvhw, OUTDIR/CAM2a.cvhw: a model set for covahip_blobnet_load_set / BlobNetInfer([...]).
 No TensorFlow or protobuf is needed: the record framing and the Example message are parsed here.
+
+Held-out evaluation and resume (include/covahip.h, "Evaluation and resume"):
+
+    python -m cova_amd.train RECORDS... -o blobnet.cvhw --val-frac 0.2 --keep best --checkpoint run.cvhs
+    python -m cova_amd.train RECORDS... -o blobnet.cvhw --val-frac 0.2 --keep best --checkpoint run.cvhs --resume run.cvhs
+    python -m cova_amd.train --eval-only blobnet.cvhw TODAY.tfrecord
+
+--val FILES names validation records instead of splitting a tail off (with --set one comma-joined argument per model).  Every
+epoch then reports the loss / precision / recall / IoU of the validation part in inference mode (moving BN statistics, no
+dropout); --keep best writes the weights of the epoch with the lowest validation loss.  --checkpoint writes the whole trainer
+state after every epoch and --resume continues from it, bit for bit where the interrupted run would have gone.  --eval-only
+trains nothing: it prints one JSON line per model with the score of a weight file on the given records.
 """
 from __future__ import annotations
 
 import argparse
 import ctypes as C
 import functools
+import json
 import math
 import os
 import struct
@@ -287,8 +300,148 @@ def trainable_mask() -> np.ndarray:
     return np.concatenate(parts)
 
 
+# ------------------------------------------------------------------------------------------------ validation split, state blob
+def split_tail(stacks: np.ndarray, labels: np.ndarray, frac: float):
+    """((train stacks, train labels), (validation stacks, validation labels)): the LAST ceil(frac * N) samples validate, the
+    rest trains.  A tail, not a shuffle: consecutive stacks of a camera are near-duplicates and a random split would leak.
+    A frac that leaves either part empty is a ValueError."""
+    n = int(stacks.shape[0])
+    if labels.shape[0] != n:
+        raise ValueError(f"{n} stacks but {labels.shape[0]} labels")
+    n_val = int(math.ceil(frac * n - 1e-9))
+    if not 0 < n_val < n:
+        raise ValueError(f"validation fraction {frac} of {n} samples leaves {n_val} to validate and {n - n_val} to train")
+    return (stacks[:n - n_val], labels[:n - n_val]), (stacks[n - n_val:], labels[n - n_val:])
+
+
+STATE_MAGIC = 0x53485643      # "CVHS"
+STATE_VERSION = 1
+STATE_HEADER = struct.Struct("<IIIIii8fQ")
+assert STATE_HEADER.size == 64
+
+
+def read_state_header(data: bytes) -> dict:
+    """The header, step counters and seeds of a trainer state blob (covahip_train_save_state), checked as the library checks
+    it on load.  Raises ValueError naming what is wrong: truncated, bad magic, unsupported version, size mismatch or CRC mismatch."""
+    if len(data) < 68:
+        raise ValueError(f"truncated state blob: {len(data)} bytes, a header and a checksum take 68")
+    magic, version, n_models, n_params, h_mb, w_mb, *scalars, user_tag = STATE_HEADER.unpack_from(data, 0)
+    if magic != STATE_MAGIC:
+        raise ValueError(f"bad magic {magic:#010x}: not a trainer state blob")
+    if version != STATE_VERSION:
+        raise ValueError(f"unsupported version {version} of the trainer state blob (this build reads {STATE_VERSION})")
+    per_model = 16 + 3 * 4 * n_params
+    want = 64 + n_models * per_model + 4
+    if len(data) != want:
+        kind = "truncated state blob" if len(data) < want else "size mismatch"
+        raise ValueError(f"{kind}: {len(data)} bytes, {n_models} models of {n_params} parameters take {want}")
+    (crc,) = struct.unpack_from("<I", data, want - 4)
+    if crc32c(memoryview(data)[:want - 4]) != crc:
+        raise ValueError("CRC mismatch: the state blob is corrupted")
+    out = {"version": version, "n_models": n_models, "n_params": n_params, "h_mb": h_mb, "w_mb": w_mb, "user_tag": user_tag}
+    out.update(zip(("lr", "beta1", "beta2", "eps", "bn_momentum", "bn_eps", "dropout", "smooth"), scalars))
+    steps_seeds = [struct.unpack_from("<QQ", data, 64 + k * per_model) for k in range(n_models)]
+    out["steps"] = [int(a) for a, _ in steps_seeds]
+    out["seeds"] = [int(b) for _, b in steps_seeds]
+    return out
+
+
+def _eval_dict(res) -> dict:
+    """loss and the micro-averaged precision / recall / IoU of a covahip_train_eval_result (0-denominators as fit treats them)."""
+    tp, fp, fn = int(res.tp), int(res.fp), int(res.fn)
+    return {"loss": float(res.loss), "precision": tp / max(1, tp + fp), "recall": tp / max(1, tp + fn),
+            "iou": tp / max(1, tp + fp + fn), "samples": int(res.samples)}
+
+
+def _val_fields(ev: dict) -> dict:
+    return {"val_" + k: ev[k] for k in ("loss", "precision", "recall", "iou")}
+
+
+def _val_text(rec: dict) -> str:
+    if "val_loss" not in rec:
+        return ""
+    return (f" val_loss {rec['val_loss']:.4f} val_precision {rec['val_precision']:.4f} val_recall {rec['val_recall']:.4f} "
+            f"val_iou {rec['val_iou']:.4f}")
+
+
+def _check_fit_args(val, keep):
+    if keep not in ("last", "best"):
+        raise ValueError(f"keep = {keep!r}: 'last' or 'best'")
+    if keep == "best" and val is None:
+        raise ValueError("keep='best' needs validation data (val=...): the best epoch is the one with the lowest val_loss")
+
+
+def _replace_file(path, data: bytes):
+    tmp = str(path) + ".tmp"
+    with open(tmp, "wb") as f:
+        f.write(data)
+    os.replace(tmp, path)
+
+
+WEIGHT_FILE_BYTES = 64 + 4 * W.N_PARAMS
+_BEST_HEAD = struct.Struct("<4sI")
+
+
+class _State:
+    """Trainer state and best-epoch bookkeeping shared by Trainer and TrainerSet (both hold .handle, .ctx, ._lib)."""
+
+    def state_bytes(self, epoch: int = 0) -> bytes:
+        """The whole trainer as one blob (weights, moving statistics, Adam moments, step counters, dropout seeds of every model);
+        `epoch` travels as the blob's user_tag."""
+        n = C.c_size_t()
+        L.check(self._lib.covahip_train_state_size(self.handle, C.byref(n)), "covahip_train_state_size")
+        buf = np.zeros(n.value, np.uint8)
+        L.check(self._lib.covahip_train_save_state(self.handle, epoch, buf.ctypes.data, n.value, C.byref(n)),
+                "covahip_train_save_state", self.ctx.handle)
+        return buf.tobytes()
+
+    def load_state_bytes(self, data: bytes) -> int:
+        """Continues where the trainer that saved `data` stood, bit for bit; returns the stored epoch.  A blob the library refuses
+        raises CovahipError and leaves this trainer as it was."""
+        tag = C.c_uint64()
+        L.check(self._lib.covahip_train_load_state(self.handle, data, len(data), C.byref(tag)), "covahip_train_load_state",
+                self.ctx.handle)
+        self._set_step_counts(read_state_header(data)["steps"])
+        return int(tag.value)
+
+    def save_state(self, path, epoch: int = 0) -> None:
+        _replace_file(path, self.state_bytes(epoch))
+
+    def load_state(self, path) -> int:
+        with open(path, "rb") as f:
+            return self.load_state_bytes(f.read())
+
+    # best epochs of fit(keep="best"): per model (val_loss, weight file bytes) or None
+    def _best_update(self, k: int, loss: float, weights_bytes) -> None:
+        if self._best[k] is None or loss < self._best[k][0]:      # ties: the earliest epoch stays
+            self._best[k] = (loss, weights_bytes())
+
+    def _best_save(self, checkpoint) -> None:
+        """Next to a checkpoint: CHECKPOINT.best, so that a resumed run knows the best epoch before the interruption."""
+        if any(b is None for b in self._best):
+            return
+        parts = [_BEST_HEAD.pack(b"CVHB", len(self._best))]
+        for loss, data in self._best:
+            parts += [struct.pack("<d", loss), data]
+        _replace_file(str(checkpoint) + ".best", b"".join(parts))
+
+    def _best_start(self, n_models: int, keep: str, checkpoint, start_epoch: int) -> None:
+        self._best = [None] * n_models
+        path = None if checkpoint is None else str(checkpoint) + ".best"
+        if keep != "best" or not start_epoch or path is None or not os.path.exists(path):
+            return
+        with open(path, "rb") as f:
+            data = f.read()
+        per = 8 + WEIGHT_FILE_BYTES
+        if len(data) != _BEST_HEAD.size + n_models * per or _BEST_HEAD.unpack_from(data)[:2] != (b"CVHB", n_models):
+            raise ValueError(f"{path}: not the best-epoch file of a {n_models}-model training")
+        for k in range(n_models):
+            o = _BEST_HEAD.size + k * per
+            self._best[k] = (struct.unpack_from("<d", data, o)[0], data[o + 8:o + per])
+
+
 # ------------------------------------------------------------------------------------------------ GPU trainer
-class Trainer:
+class Trainer(_State):
     """BlobNet training on the GPU over covahip_train_*.  `step` counts the steps taken (the dropout hash's step)."""
 
     def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, max_batch: int = 4, weights_flat: np.ndarray | None = None,
@@ -360,17 +513,69 @@ class Trainer:
         L.check(self._lib.covahip_train_grads(self.handle, out.ctypes.data, out.size), "covahip_train_grads", self.ctx.handle)
         return out
 
-    def fit(self, records, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None):
+    def _set_step_counts(self, steps):
+        self.step_count = steps[0]
+
+    def evaluate(self, records, want_sample_loss: bool = False, want_logits: bool = False) -> dict:
+        """Scores the current weights on records = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]), any N >= 1, in inference mode
+        (moving BN statistics, no dropout); training does not notice.  {"loss", "precision", "recall", "iou", "samples"}: the mean
+        per-sample Jaccard distance and the micro-averaged metrics at sigmoid > 0.5; plus "sample_loss" f32 [N] / "logits"
+        f32 [N][h][w] when asked for."""
+        stack = np.ascontiguousarray(records[0], dtype=np.uint8)
+        gt = np.ascontiguousarray(records[1], dtype=np.uint8)
+        n = stack.shape[0]
+        if n == 0:
+            raise ValueError("no samples to evaluate")
+        assert stack.shape == (n, W.T * self.h, self.w, 4) and gt.shape == (n, self.h, self.w), (stack.shape, gt.shape)
+        sl = np.empty(n, np.float32) if want_sample_loss else None
+        lg = np.empty((n, self.h, self.w), np.float32) if want_logits else None
+        res = L.TrainEvalResult()
+        L.check(self._lib.covahip_train_eval(self.handle, stack.ctypes.data, gt.ctypes.data, n, None if sl is None else sl.ctypes.data,
+                                             None if lg is None else lg.ctypes.data, C.byref(res), L.MEM_HOST), "covahip_train_eval",
+                self.ctx.handle)
+        return self._eval_out(res, sl, lg)
+
+    def evaluate_device(self, d_stack: int, d_gt: int, n: int, d_sample_loss: int | None = None, d_logits: int | None = None) -> dict:
+        """The same on device pointers (the optional outputs are device buffers of n and n * h * w floats)."""
+        res = L.TrainEvalResult()
+        L.check(self._lib.covahip_train_eval(self.handle, d_stack, d_gt, n, d_sample_loss, d_logits, C.byref(res), L.MEM_DEVICE),
+                "covahip_train_eval", self.ctx.handle)
+        return _eval_dict(res)
+
+    @staticmethod
+    def _eval_out(res, sl, lg) -> dict:
+        out = _eval_dict(res)
+        if sl is not None:
+            out["sample_loss"] = sl
+        if lg is not None:
+            out["logits"] = lg
+        return out
+
+    def best_weights_bytes(self) -> bytes:
+        """The weight file of the epoch with the lowest val_loss of the last fit(keep="best")."""
+        if not getattr(self, "_best", None) or self._best[0] is None:
+            raise ValueError("no best epoch: run fit(..., val=..., keep='best') first")
+        return self._best[0][1]
+
+    def fit(self, records, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None, val=None, keep: str = "last",
+            checkpoint=None, start_epoch: int = 0):
         """records = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]) (slide's output), in order, the last batch partial as in
-        Keras.  Per epoch: the sample-weighted mean loss and precision / recall at 0.5 of the training predictions."""
+        Keras.  Per epoch: the sample-weighted mean loss and precision / recall at 0.5 of the training predictions.
+        val = (stacks, labels): every epoch record gains val_loss / val_precision / val_recall / val_iou (evaluate on val after
+        the epoch).  keep="best": best_weights_bytes() returns the weights of the epoch with the lowest val_loss (ties: the
+        earliest).  checkpoint=PATH: the trainer state is written there after every epoch (and the best epoch so far to
+        PATH.best); load_state(PATH) returns the epoch to pass as start_epoch, which continues the schedule and the numbering:
+        the history returned then starts at that epoch."""
+        _check_fit_args(val, keep)
         stacks, labels = records
         n = stacks.shape[0]
         if n == 0:
             raise ValueError("no training samples")
         if not 1 <= batch <= self.max_batch:
             raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
+        self._best_start(1, keep, checkpoint, start_epoch)
         history = []
-        for ep in range(epochs):
+        for ep in range(start_epoch, epochs):
             lr = schedule(ep, self.cfg.lr) if schedule is keras_lr else schedule(ep)
             tot = 0.0
             tp = fp = fn = 0
@@ -380,10 +585,17 @@ class Trainer:
                 a, b_, c = self.metrics()
                 tp, fp, fn = tp + a, fp + b_, fn + c
             rec = {"epoch": ep, "lr": lr, "loss": tot / n, "precision": tp / max(1, tp + fp), "recall": tp / max(1, tp + fn)}
+            if val is not None:
+                rec.update(_val_fields(self.evaluate(val)))
+                if keep == "best":
+                    self._best_update(0, rec["val_loss"], self.weights_bytes)
+            if checkpoint is not None:
+                self.save_state(checkpoint, epoch=ep + 1)
+                self._best_save(checkpoint)
             history.append(rec)
             if log:
                 log(f"epoch {ep + 1}/{epochs}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
-                    f"recall {rec['recall']:.4f} lr {lr:.3g}")
+                    f"recall {rec['recall']:.4f}{_val_text(rec)} lr {lr:.3g}")
         return history
 
 
@@ -399,7 +611,7 @@ def set_epoch_plan(sizes, batch: int):
     return [[(min(i * batch, n), max(0, min(batch, n - i * batch))) for n in sizes] for i in range(steps)]
 
 
-class TrainerSet:
+class TrainerSet(_State):
     """K BlobNet models of one geometry trained side by side over covahip_train_create_set: a step takes one step of every
     model in one launch of each kernel.  Model k is bit-identical to a Trainer made from the same weights and seed and fed
     model k's steps alone (include/covahip.h, "Training sets")."""
@@ -518,20 +730,81 @@ class TrainerSet:
         L.check(self._lib.covahip_train_grads_m(self.handle, k, out.ctypes.data, out.size), "covahip_train_grads_m", self.ctx.handle)
         return out
 
-    def fit(self, records_per_model, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None):
-        """records_per_model[k] = (stacks, labels) of model k, as Trainer.fit takes them.  Every model walks its own data set in
-        order (set_epoch_plan); a model whose epoch is shorter sits out the rest of it.  Returns one history per model, each as
-        Trainer.fit's; model k's weights afterwards are those of Trainer.fit on records_per_model[k] alone, bit for bit."""
+    def _set_step_counts(self, steps):
+        self.step_counts = list(steps)
+
+    def evaluate(self, records_per_model, want_sample_loss: bool = False, want_logits: bool = False):
+        """Scores every model on its own samples in ONE call (one launch of each kernel per chunk of max_batch samples per
+        model): records_per_model[k] = (stacks, labels) of model k, any size; None or an empty entry = nothing for model k (its
+        dict holds zeros).  Returns one dict per model, as Trainer.evaluate's; model k's is bit-identical to Trainer.evaluate of
+        the same weights on the same samples."""
         if len(records_per_model) != self.n_models:
             raise ValueError(f"{len(records_per_model)} data sets for {self.n_models} models")
+        xs, ys, counts = [], [], []
+        for r in records_per_model:
+            n = 0 if r is None else len(r[0])
+            counts.append(n)
+            if n:
+                x = np.ascontiguousarray(r[0], dtype=np.uint8)
+                y = np.ascontiguousarray(r[1], dtype=np.uint8)
+                assert x.shape == (n, W.T * self.h, self.w, 4) and y.shape == (n, self.h, self.w), (x.shape, y.shape)
+                xs.append(x)
+                ys.append(y)
+        if not xs:
+            raise ValueError("an evaluation needs at least one model with samples")
+        stack = xs[0] if len(xs) == 1 else np.concatenate(xs)
+        gt = ys[0] if len(ys) == 1 else np.concatenate(ys)
+        total = sum(counts)
+        sl = np.empty(total, np.float32) if want_sample_loss else None
+        lg = np.empty((total, self.h, self.w), np.float32) if want_logits else None
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        res = (L.TrainEvalResult * self.n_models)()
+        L.check(self._lib.covahip_train_eval_set(self.handle, stack.ctypes.data, gt.ctypes.data, cnt.ctypes.data,
+                                                 None if sl is None else sl.ctypes.data, None if lg is None else lg.ctypes.data, res,
+                                                 L.MEM_HOST), "covahip_train_eval_set", self.ctx.handle)
+        outs, at = [], 0
+        for k, n in enumerate(counts):
+            outs.append(Trainer._eval_out(res[k], None if sl is None else sl[at:at + n], None if lg is None else lg[at:at + n]))
+            at += n
+        return outs
+
+    def evaluate_device(self, d_stack: int, d_gt: int, counts, d_sample_loss: int | None = None, d_logits: int | None = None):
+        """The same on device pointers: the samples packed in model order (sum(counts) stacks, then as many labels); the
+        optional outputs are device buffers in the same packing."""
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        if cnt.shape != (self.n_models,):
+            raise ValueError(f"{cnt.size} counts for {self.n_models} models")
+        res = (L.TrainEvalResult * self.n_models)()
+        L.check(self._lib.covahip_train_eval_set(self.handle, d_stack, d_gt, cnt.ctypes.data, d_sample_loss, d_logits, res,
+                                                 L.MEM_DEVICE), "covahip_train_eval_set", self.ctx.handle)
+        return [_eval_dict(r) for r in res]
+
+    def best_weights_bytes(self, k: int) -> bytes:
+        """Model k's weight file of ITS epoch with the lowest val_loss of the last fit(keep="best")."""
+        if not getattr(self, "_best", None) or self._best[k] is None:
+            raise ValueError("no best epoch: run fit(..., val=..., keep='best') first")
+        return self._best[k][1]
+
+    def fit(self, records_per_model, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None, val=None, keep: str = "last",
+            checkpoint=None, start_epoch: int = 0):
+        """records_per_model[k] = (stacks, labels) of model k, as Trainer.fit takes them.  Every model walks its own data set in
+        order (set_epoch_plan); a model whose epoch is shorter sits out the rest of it.  Returns one history per model, each as
+        Trainer.fit's; model k's weights afterwards are those of Trainer.fit on records_per_model[k] alone, bit for bit.
+        val (one (stacks, labels) per model), keep, checkpoint and start_epoch as Trainer.fit; the best epoch is per model."""
+        _check_fit_args(val, keep)
+        if len(records_per_model) != self.n_models:
+            raise ValueError(f"{len(records_per_model)} data sets for {self.n_models} models")
+        if val is not None and len(val) != self.n_models:
+            raise ValueError(f"{len(val)} validation sets for {self.n_models} models")
         if not 1 <= batch <= self.max_batch:
             raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
         sizes = [int(r[0].shape[0]) for r in records_per_model]
         if min(sizes) == 0:
             raise ValueError("no training samples")
         plan = set_epoch_plan(sizes, batch)
+        self._best_start(self.n_models, keep, checkpoint, start_epoch)
         histories = [[] for _ in range(self.n_models)]
-        for ep in range(epochs):
+        for ep in range(start_epoch, epochs):
             lr = schedule(ep, self.cfg.lr) if schedule is keras_lr else schedule(ep)
             tot = [0.0] * self.n_models
             cnt = [[0, 0, 0] for _ in range(self.n_models)]
@@ -544,14 +817,22 @@ class TrainerSet:
                         tot[k] += losses[k] * n
                         for q, v in enumerate(self.metrics(k)):
                             cnt[k][q] += v
+            evs = self.evaluate(val) if val is not None else None
             for k in range(self.n_models):
                 tp, fp, fn = cnt[k]
                 rec = {"epoch": ep, "lr": lr, "loss": tot[k] / sizes[k], "precision": tp / max(1, tp + fp),
                        "recall": tp / max(1, tp + fn)}
+                if evs is not None:
+                    rec.update(_val_fields(evs[k]))
+                    if keep == "best":
+                        self._best_update(k, rec["val_loss"], functools.partial(self.weights_bytes, k))
                 histories[k].append(rec)
                 if log:
                     log(f"epoch {ep + 1}/{epochs} model {k}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
-                        f"recall {rec['recall']:.4f} lr {lr:.3g}")
+                        f"recall {rec['recall']:.4f}{_val_text(rec)} lr {lr:.3g}")
+            if checkpoint is not None:
+                self.save_state(checkpoint, epoch=ep + 1)
+                self._best_save(checkpoint)
         return histories
 
 
@@ -559,7 +840,7 @@ def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cova_amd.train", description=__doc__.split("\n")[0])
     ap.add_argument("records", nargs="+", help="TFRecord files written by tfrecordsink gt=LABELS; with --set one model per "
                                                "argument, several files of one model joined with commas")
-    ap.add_argument("-o", "--output", required=True, help="weight file to write (CVHW); with --set the directory for one file per model")
+    ap.add_argument("-o", "--output", help="weight file to write (CVHW); with --set the directory for one file per model")
     ap.add_argument("--set", action="store_true", dest="as_set", help="train one model per argument in one training set")
     ap.add_argument("--epochs", type=int, default=20)
     ap.add_argument("--batch", type=int, default=4)
@@ -567,7 +848,80 @@ def parse_args(argv=None):
     ap.add_argument("--h-mb", type=int, default=45)
     ap.add_argument("--w-mb", type=int, default=80)
     ap.add_argument("--device", type=int, default=0)
-    return ap.parse_args(argv)
+    ap.add_argument("--val", nargs="+", metavar="FILES", help="validation records; with --set one comma-joined argument per model, "
+                                                              "in model order")
+    ap.add_argument("--val-frac", type=float, metavar="F", help="validate on the last ceil(F * N) samples (of every model) instead")
+    ap.add_argument("--keep", choices=("last", "best"), default="last", help="which epoch's weights to write: the last, or the one "
+                                                                             "with the lowest validation loss")
+    ap.add_argument("--checkpoint", metavar="PATH", help="write the trainer state here after every epoch")
+    ap.add_argument("--resume", metavar="PATH", help="load a trainer state and continue at its epoch, up to --epochs")
+    ap.add_argument("--eval-only", metavar="WEIGHTS", help="train nothing: score this weight file (with --set: a directory of "
+                                                           "weight files named as --set writes them) on the records, one JSON "
+                                                           "line per model")
+    a = ap.parse_args(argv)
+    if a.eval_only:
+        if a.resume:
+            ap.error("--resume continues a training; --eval-only trains nothing")
+        if a.val or a.val_frac is not None or a.checkpoint or a.keep != "last" or a.output:
+            ap.error("--eval-only takes the weights and the records only")
+        return a
+    if not a.output:
+        ap.error("-o / --output is required")
+    if a.val and a.val_frac is not None:
+        ap.error("--val and --val-frac exclude each other")
+    if a.keep == "best" and not a.val and a.val_frac is None:
+        ap.error("--keep best needs validation data: --val FILES or --val-frac F")
+    if a.val_frac is not None and not 0.0 < a.val_frac < 1.0:
+        ap.error("--val-frac must lie strictly between 0 and 1")
+    if a.val and a.as_set and len(a.val) != len(a.records):
+        ap.error(f"--val names {len(a.val)} models, the set has {len(a.records)}")
+    return a
+
+
+def _load(files, a):
+    frames, gt = read_tfrecords(files, a.h_mb, a.w_mb)
+    return frames.shape[0], slide(frames, gt)
+
+
+def _resume(trainer, a, n_models: int) -> int:
+    """--resume: the stored epoch, after the state has been loaded into `trainer`."""
+    if not a.resume:
+        return 0
+    with open(a.resume, "rb") as f:
+        data = f.read()
+    hdr = read_state_header(data)
+    if (hdr["h_mb"], hdr["w_mb"], hdr["n_models"]) != (a.h_mb, a.w_mb, n_models):
+        raise ValueError(f"{a.resume}: state of {hdr['n_models']} model(s) at {hdr['h_mb']}x{hdr['w_mb']}, this run trains "
+                         f"{n_models} at {a.h_mb}x{a.w_mb}")
+    epoch = trainer.load_state_bytes(data)
+    print(f"resumed {a.resume}: continuing at epoch {epoch + 1}/{a.epochs}", file=sys.stderr)
+    return epoch
+
+
+def main_eval(a) -> int:
+    from .elements import Context
+
+    if a.as_set:
+        jobs = set_jobs(a.records, a.eval_only)
+    else:
+        jobs = [(a.records, a.eval_only)]
+    flats, records = [], []
+    for files, path in jobs:
+        with open(path, "rb") as f:
+            flats.append(W.from_bytes(f.read()))
+        records.append(_load(files, a)[1])
+    ctx = Context(a.device)
+    if a.as_set:
+        ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=flats, max_batch=a.batch)
+        evs = ts.evaluate(records)
+    else:
+        ts = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, weights_flat=flats[0])
+        evs = [ts.evaluate(records[0])]
+    for (_, path), ev in zip(jobs, evs):
+        print(json.dumps({"weights": path, **ev}))
+    ts.close()
+    ctx.close()
+    return 0
 
 
 def set_jobs(records, outdir: str):
@@ -590,18 +944,26 @@ def main_set(a) -> int:
     from .elements import Context
 
     jobs = set_jobs(a.records, a.output)
-    records = []
+    records, val = [], ([] if a.val or a.val_frac is not None else None)
     for k, (files, _) in enumerate(jobs):
-        frames, gt = read_tfrecords(files, a.h_mb, a.w_mb)
-        records.append(slide(frames, gt))
-        print(f"model {k}: {frames.shape[0]} frames -> {records[-1][0].shape[0]} samples of {a.h_mb}x{a.w_mb}", file=sys.stderr)
+        n_frames, rec = _load(files, a)
+        if a.val:
+            val.append(_load([f for f in a.val[k].split(",") if f], a)[1])
+        elif a.val_frac is not None:
+            rec, v = split_tail(*rec, a.val_frac)
+            val.append(v)
+        records.append(rec)
+        print(f"model {k}: {n_frames} frames -> {rec[0].shape[0]} samples of {a.h_mb}x{a.w_mb}"
+              + (f", {val[k][0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
     os.makedirs(a.output, exist_ok=True)
     ctx = Context(a.device)
     ts = TrainerSet(ctx, a.h_mb, a.w_mb, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))], max_batch=a.batch)
-    ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr))
+    start = _resume(ts, a, len(jobs))
+    ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
+           checkpoint=a.checkpoint, start_epoch=start)
     for k, (_, out) in enumerate(jobs):
         with open(out, "wb") as f:
-            f.write(ts.weights_bytes(k))
+            f.write(ts.best_weights_bytes(k) if a.keep == "best" else ts.weights_bytes(k))
     ts.close()
     ctx.close()
     return 0
@@ -609,18 +971,27 @@ def main_set(a) -> int:
 
 def main(argv=None) -> int:
     a = parse_args(argv)
+    if a.eval_only:
+        return main_eval(a)
     if a.as_set:
         return main_set(a)
     from .elements import Context
 
-    frames, gt = read_tfrecords(a.records, a.h_mb, a.w_mb)
-    stacks, labels = slide(frames, gt)
-    print(f"{frames.shape[0]} frames -> {stacks.shape[0]} samples of {a.h_mb}x{a.w_mb}", file=sys.stderr)
+    n_frames, records = _load(a.records, a)
+    val = None
+    if a.val:
+        val = _load(a.val, a)[1]
+    elif a.val_frac is not None:
+        records, val = split_tail(*records, a.val_frac)
+    print(f"{n_frames} frames -> {records[0].shape[0]} samples of {a.h_mb}x{a.w_mb}"
+          + (f", {val[0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
     ctx = Context(a.device)
     tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed)
-    tr.fit((stacks, labels), epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr))
+    start = _resume(tr, a, 1)
+    tr.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
+           checkpoint=a.checkpoint, start_epoch=start)
     with open(a.output, "wb") as f:
-        f.write(tr.weights_bytes())
+        f.write(tr.best_weights_bytes() if a.keep == "best" else tr.weights_bytes())
     tr.close()
     ctx.close()
     return 0

@@ -357,6 +357,56 @@ int covahip_train_step_set(covahip_train *tr, const uint8_t *stack, const uint8_
 int covahip_train_metrics_m(covahip_train *tr, int model, int64_t tp_fp_fn[3]);
 int covahip_train_weights_m(covahip_train *tr, int model, void *cvhw, size_t cap, size_t *n);
 int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n);
+/* Evaluation and resume.
+ * Evaluation: the forward of the training step in INFERENCE mode, on samples the caller holds out.  Two differences from the
+ * step's forward: BatchNorm normalises with the model's MOVING mean / variance ((x - mean) * (1 / sqrt(var + bn_eps)) * gamma +
+ * beta, the expression of the step with the moving values in place of the batch's), and every dropout site is the identity.
+ * This is the arithmetic of covahip_blobnet_forward in fp32.  Per-sample loss = the Jaccard distance of the sample as the step
+ * forms it (I = sum y*p, S = sum (y + p) over H x W, (1 - (I + s) / (S - I + s)) * s, s = cfg.smooth); the result's loss is the
+ * mean of the per-sample values, summed in double on the host in sample order.  Valid before any step: it scores the weights
+ * the trainer was created with.
+ *   Contract A -- a sample's result depends on the sample and the model only.  Its logits, its sample_loss and its contribution
+ *   to TP / FP / FN are BIT-IDENTICAL whatever n, max_batch, the sample's position, mem_kind, and whether the model is evaluated
+ *   alone or as model k of a set next to others.  (Nothing in an inference-mode forward couples the samples of a batch.)
+ *   Contract B -- evaluation is invisible to training.  It changes no weight, no moving statistic, no Adam moment, no step
+ *   counter, and neither covahip_train_grads nor covahip_train_metrics (they keep describing the last TRAINING step).  A
+ *   training step after an evaluation is bit-identical to the same step without it. */
+typedef struct covahip_train_eval_result {
+    double  loss;            /* mean over the samples of the per-sample Jaccard distance (smooth = cfg.smooth) */
+    int64_t tp, fp, fn;      /* at sigmoid > 0.5 (logit > 0), summed over the samples                           */
+    int64_t samples;
+} covahip_train_eval_result;
+/* n >= 1 samples, ANY n (the library walks them in chunks of cfg.max_batch): stack u8 [n][4*h_mb][w_mb][4], gt u8 [n][h_mb][w_mb].
+ * sample_loss: f32 [n] or NULL.  logits: f32 [n][h_mb][w_mb] or NULL.  mem_kind applies to stack, gt, sample_loss and logits.
+ * Synchronous. */
+int covahip_train_eval(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, int n,
+                       float *sample_loss, float *logits, covahip_train_eval_result *out, int mem_kind);
+/* Every model of a set on its own samples in one launch of each kernel per chunk: counts[k] >= 0 samples of model k (HOST array
+ * of n_models entries, any size, not all 0), packed in model order as covahip_train_step_set takes them; sample_loss / logits in
+ * the same packing; out: HOST [n_models]; a model with counts[k] = 0 gets zeros.  covahip_train_eval on a set of more than one
+ * model is COVAHIP_ERR_INVALID_ARG (as covahip_train_step). */
+int covahip_train_eval_set(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *counts,
+                           float *sample_loss, float *logits, covahip_train_eval_result *out, int mem_kind);
+/* Trainer state: everything a training needs to continue, as ONE little-endian blob for the whole trainer (solo or set).
+ *   offset  0  u32 magic "CVHS" (0x53485643)     4  u32 version = 1        8  u32 n_models      12  u32 n_params = 320305
+ *          16  i32 h_mb    20  i32 w_mb          24  f32 lr, beta1, beta2, eps, bn_momentum, bn_eps, dropout, smooth (the
+ *          creating cfg, for information)        56  u64 user_tag (the caller's: an epoch number, say)
+ *          64  per model, n_models times: u64 step (steps taken: Adam's t, the dropout hash's step), u64 seed (dropout),
+ *              f32 params[n_params] (a weight file's payload, moving statistics included), f32 adam_m[n_params],
+ *              f32 adam_v[n_params]
+ *          end u32 CRC-32C (Castagnoli, as TFRecord frames use it, unmasked) of every byte before it
+ *   Contract C -- exact resume.  Take any trainer after any sequence of steps, save, and load the blob into a trainer created
+ *   with the same cfg and n_models from ANY initial weights and seeds.  From then on both trainers are bit-identical: losses,
+ *   gradients, metrics, weights, moving statistics, Adam state, for every model, including models that sat steps out.  The
+ *   seeds come from the blob.
+ * covahip_train_save_state: *n = the blob's size; COVAHIP_ERR_OVERFLOW when buf is NULL or cap < *n (as covahip_train_weights).
+ * covahip_train_load_state: all or nothing, validated before anything is copied.  Wrong magic / version / size / CRC:
+ * COVAHIP_ERR_BAD_DATA; n_models or n_params not the trainer's: COVAHIP_ERR_INVALID_ARG; the trainer is then untouched.  The
+ * geometry and cfg scalars of the header are not compared (the parameters do not depend on them).  After a load
+ * covahip_train_grads / _metrics describe no step: zeros.  *user_tag (may be NULL) = the tag given to save. */
+int covahip_train_state_size(covahip_train *tr, size_t *n);
+int covahip_train_save_state(covahip_train *tr, uint64_t user_tag, void *buf, size_t cap, size_t *n);
+int covahip_train_load_state(covahip_train *tr, const void *buf, size_t n, uint64_t *user_tag);
 void covahip_train_destroy(covahip_train *tr);
 
 /* ------------------------------------------------------------ MoG labels
