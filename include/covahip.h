@@ -125,8 +125,11 @@ int covahip_profile_read(covahip_ctx *ctx, covahip_kernel_time *out, int cap, in
  * h_mb x w_mb: macroblock grid (e.g. 68x120 for 1080p, 45x80 for 720p); t must be 4.
  * max_batch sizes the activation workspace held in HBM by the ctx.
  * Limits of the kernels, all checked HERE (COVAHIP_ERR_UNSUPPORTED), never at forward time:
- *   16 <= h_mb, w_mb <= 1024; w_mb a multiple of 4 (the first level reads 16-byte groups of four
- *   macroblocks); one band of every level must fit the 160 KB of LDS of a CU (holds far beyond 4K grids).
+ *   16 <= h_mb <= 1024; 16 <= w_mb <= 252, a multiple of 4 (the first level reads 16-byte groups of four
+ *   macroblocks).  The width limit is the LDS of a CU: a band of one pool-window row of every level must fit its
+ *   kernel's share of it, and level 1's is the first that does not (its 126 columns at w_mb = 252 fill the 64 KB
+ *   tile of its workgroup).  A 4K grid (135x240) loads; no height up to 1024 is refused.  The limit does not
+ *   depend on max_batch (tests/test_gpu_geometry_edges.py probes the range and runs its edges).
  * A ctx holds ONE model or ONE model set (covahip_blobnet_load_set): loading again replaces it.
  * A failed load leaves the ctx without a model (later calls return COVAHIP_ERR_NOT_LOADED).  A malformed blob
  * (COVAHIP_ERR_BAD_WEIGHTS) is rejected before anything changes: the model loaded before stays.  */
@@ -181,8 +184,8 @@ int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int 
                    covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind);
 
 /* Fused hot path = nvinfer(BlobNet) -> maskcopy -> bboxcc for one batch: the mask
- * stays on the GPU.  logits/mask may be NULL.  bboxcc's limit applies on top of the model's: a grid wider than 256
- * macroblocks loads (covahip_blobnet_forward works) but this call returns COVAHIP_ERR_UNSUPPORTED.   */
+ * stays on the GPU.  logits/mask may be NULL.  bboxcc's limit (w <= 256) lies beyond the model's (w_mb <= 252):
+ * every grid that loads runs here.                                                                  */
 int covahip_filter_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, int area_thresh,
                            covahip_box *boxes, int32_t *counts, int max_boxes, float *logits,
                            uint8_t *mask, int mem_kind);
