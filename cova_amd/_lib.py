@@ -79,6 +79,10 @@ class TrainEvalResult(C.Structure):
     _fields_ = [("loss", C.c_double), ("tp", C.c_int64), ("fp", C.c_int64), ("fn", C.c_int64), ("samples", C.c_int64)]
 
 
+class TrainPlan(C.Structure):
+    _fields_ = [("frozen_groups", C.c_uint32), ("bn_inference", C.c_uint32)]
+
+
 class MogCfg(C.Structure):
     _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
                 ("var_threshold", C.c_float)]
@@ -206,6 +210,8 @@ PROTOTYPES = {
     "covahip_train_state_size": (C.c_int, [_P, C.POINTER(_SZ)]),
     "covahip_train_save_state": (C.c_int, [_P, C.c_uint64, _P, _SZ, C.POINTER(_SZ)]),
     "covahip_train_load_state": (C.c_int, [_P, _P, _SZ, C.POINTER(C.c_uint64)]),
+    "covahip_train_set_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
+    "covahip_train_get_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
     "covahip_train_destroy": (None, [_P]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),

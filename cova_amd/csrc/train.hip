@@ -432,6 +432,29 @@ __global__ void k_bn_bwd(Mdl md, const float *g, int Cg, const float *__restrict
     out[i] = d;
 }
 
+// BN backward apply of a layer in inference mode (the training plan, include/covahip.h "Fine-tuning"): the layer normalised with
+// constants, so out = g * gamma * invstd with no batch-mean terms; times (x > 0) when relu_in.  stat[C + ch] = 1 / sqrt(moving
+// variance + eps) (k_plan_stat).  g and out may be the same buffer, as in k_bn_bwd.
+template <bool SET>
+__global__ void k_bn_bwd_inf(Mdl md, const float *g, int Cg, const float *__restrict__ x, const float *__restrict__ stat,
+                             const float *__restrict__ gamma, float *out, int C, int64_t S, int relu_in) {
+    const int B = model_b<SET>(md);
+    const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
+    const int64_t n = (int64_t)B * C * S;
+    if (i >= n) return;
+    g += MOFF(Cg * S);
+    x += MOFF(C * S);
+    out += MOFF(C * S);
+    stat += blockIdx.z * STAT_STRIDE;
+    gamma += POFF;
+    const int64_t s = i % S;
+    const int ch = (int)((i / S) % C);
+    const int64_t b = i / (S * C);
+    float d = g[(b * Cg + ch) * S + s] * (gamma[ch] * stat[C + ch]);
+    if (relu_in && !(x[i] > 0.f)) d = 0.f;
+    out[i] = d;
+}
+
 // PointWiseTN forward per (b, c, y, x): o = relu(drop(relu(drop(relu(p @ w1)) @ w2)) + p); the t = 0 slice also goes to the
 // decoder's concat buffer (channel c_off + c of Ctot).  Dropout indices: NCTHW of the layer's output.
 template <bool SET>
@@ -762,6 +785,24 @@ __global__ void k_eval_stat(Mdl md, const float *__restrict__ params, float *__r
     stat[C + c] = 1.f / sqrtf(params[t.var[layer] + c] + eps);
 }
 
+// The stat rows of the BN layers a training plan puts in inference mode (bit `layer` of layers), filled as k_eval_stat fills
+// them; the layer's mean / var gradient slots take the moving values the forward normalises with.  Once per step: an evaluation
+// or a state load between two steps cannot leave a stale row.
+template <bool SET>
+__global__ void k_plan_stat(Mdl md, const float *__restrict__ params, float *__restrict__ grads, float *__restrict__ stat, EvalBN t,
+                            uint32_t layers, float eps) {
+    const int layer = blockIdx.x, c = threadIdx.x, C = t.C[layer];
+    if (model_b<SET>(md) == 0 || !(layers >> layer & 1u) || c >= C) return;
+    params += POFF;
+    grads += POFF;
+    stat += blockIdx.z * STAT_STRIDE + layer * 256;
+    const float mean = params[t.mean[layer] + c], var = params[t.var[layer] + c];
+    stat[c] = mean;
+    stat[C + c] = 1.f / sqrtf(var + eps);
+    grads[t.mean[layer] + c] = mean;
+    grads[t.var[layer] + c] = var;
+}
+
 // TP / FP / FN at sigmoid > 0.5 as k_final_bwd counts them (integer atomics; the counters run on over the chunks of one
 // evaluation), and the per-sample Jaccard distance as k_loss forms it, to sample_loss[model][sample of the chunk].
 // red = [I per sample][S per sample] of the model's chunk.
@@ -815,6 +856,29 @@ __global__ void k_adam(Mdl md, float *__restrict__ w, const float *__restrict__ 
     w[i] -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
+// k_adam under a plan that freezes groups: mask 2 = a frozen slot, whose gradient reads 0 and whose weight and moments stay.
+template <bool SET>
+__global__ void k_adam_plan(Mdl md, float *__restrict__ w, float *__restrict__ g, float *__restrict__ m, float *__restrict__ v,
+                            const uint8_t *__restrict__ trainable, int n, float b1, float b2, float eps) {
+    const int i = blockIdx.x * BLK + threadIdx.x;
+    if (model_b<SET>(md) == 0 || i >= n || !trainable[i]) return;
+    const float lr_t = model_lr_t<SET>(md);
+    w += POFF;
+    g += POFF;
+    m += POFF;
+    v += POFF;
+    if (trainable[i] == 2) {
+        g[i] = 0.f;
+        return;
+    }
+    const float gi = g[i];
+    const float mi = b1 * m[i] + (1.f - b1) * gi;
+    const float vi = b2 * v[i] + (1.f - b2) * gi * gi;
+    m[i] = mi;
+    v[i] = vi;
+    w[i] -= lr_t * mi / (sqrtf(vi) + eps);
+}
+
 // ------------------------------------------------------------------------------------------------ host state
 struct EncOff { size_t k, b, gamma, beta, mean, var, w1, w2; };
 struct DecOff { size_t k, b, gamma, beta, mean, var; };
@@ -836,7 +900,9 @@ struct covahip_train {
     std::vector<long long> last_counts;   // per model: TP, FP, FN of its last step
     std::vector<void *> allocs;
     float *params = nullptr, *grads = nullptr, *adam_m = nullptr, *adam_v = nullptr;
-    uint8_t *trainable = nullptr;      // one mask for all models
+    uint8_t *trainable = nullptr;      // one mask for all models: 1 trained, 0 BN moving statistics, 2 frozen by the plan
+    uint32_t frozen = 0;               // the plan: frozen groups as given,
+    uint32_t bn_inf = 0;               // and the EFFECTIVE inference-mode BN layers (given | frozen & 0x7F)
     // activations ([B][C][T][H][W] encoder, [B][C][H][W] decoder) and their gradients
     float *x0 = nullptr, *c[NL] = {}, *p[NL] = {}, *e[NL] = {};
     int8_t *arg[NL] = {};
@@ -952,7 +1018,23 @@ struct Run {
     }
 };
 
+EvalBN bn_table(const covahip_train *tr) {
+    EvalBN bn;
+    for (int i = 0; i < NL; i++) {
+        bn.mean[i] = (int32_t)tr->eo[i].mean;
+        bn.var[i] = (int32_t)tr->eo[i].var;
+        bn.C[i] = ENC_C[i + 1];
+    }
+    for (int j = 0; j < NL - 1; j++) {
+        bn.mean[NL + j] = (int32_t)tr->dof[j].mean;
+        bn.var[NL + j] = (int32_t)tr->dof[j].var;
+        bn.C[NL + j] = DEC_CO[j];
+    }
+    return bn;
+}
+
 // One step of every model with a non-zero batch in tr->h_tab (K > 1: already uploaded to d_tab); B = the largest batch.
+// The launch schedule follows the training plan (include/covahip.h, "Fine-tuning"); the empty plan gives the full step.
 int run_step(covahip_train *tr, int B) {
     Run r{tr, tr->ctx->stream,
           Mdl{tr->K > 1 ? tr->d_tab : nullptr, tr->cfg.max_batch, (int64_t)tr->slab_floats, tr->h_tab[0].b, tr->h_tab[0].lr_t}, B};
@@ -964,9 +1046,25 @@ int run_step(covahip_train *tr, int B) {
     const float sm = tr->cfg.smooth;
     const int64_t RS = red_stride(tr->cfg.max_batch);
     auto stat = [&](int layer) { return tr->stat + layer * 256; };
+    // The plan.  enc_fz / dec_fz: the group is frozen; inf(layer): the BN layer normalises with its moving statistics.
+    // enc_live(i): something of encoder levels 0..i is trained, so the backward must reach level i; dec_live(j) likewise for
+    // decoder blocks 0..j.  need_dz[j]: block j's input gradient has a reader (the BN of block j - 1, or the encoder through
+    // the skip channels); need_dy[j]: block j's output gradient has one (its own weights, or need_dz[j]).
+    const uint32_t fz = tr->frozen, bninf = tr->bn_inf;
+    auto enc_fz = [&](int i) { return (fz >> i & 1u) != 0; };
+    auto dec_fz = [&](int j) { return (fz >> (NL + j) & 1u) != 0; };
+    auto inf = [&](int layer) { return (bninf >> layer & 1u) != 0; };
+    auto enc_live = [&](int i) { return (~fz & ((2u << i) - 1u)) != 0; };
+    auto dec_live = [&](int j) { return (~fz >> NL & ((2u << j) - 1u)) != 0; };
+    bool need_dz[NL], need_dy[NL];
+    for (int j = 0; j < NL; j++) {
+        need_dz[j] = enc_live(NL - 1) || (j > 0 && dec_live(j - 1));
+        need_dy[j] = !dec_fz(j) || need_dz[j];
+    }
     if (hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), s) != hipSuccess) return COVAHIP_ERR_HIP;
 
     // ---------------------------------------------------------------- forward
+    if (bninf) KL(k_plan_stat, (dim3(2 * NL - 1, 1, K)), 128, md, P, G, tr->stat, bn_table(tr), bninf, tr->cfg.bn_eps);
     KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
     for (int i = 0; i < NL; i++) {
         const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
@@ -974,9 +1072,11 @@ int run_step(covahip_train *tr, int B) {
         const float *xin = i ? tr->e[i - 1] : tr->x0;
         const int64_t S = (int64_t)TT * H * W;
         KL(k_conv3_fwd, (r.g1(B * Co * S)), BLK, md, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
-        r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
-        r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
-                 P + o.var);
+        if (!inf(i)) {
+            r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
+            r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
+                     P + o.var);
+        }
         KL(k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, md, tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
                                                                       Co, H, W, Hp, Wp);
         const int zj = NL - 1 - i;   // the decoder block whose input concat holds this level's t = 0 slice
@@ -994,10 +1094,12 @@ int run_step(covahip_train *tr, int B) {
         KL(k_convT_fwd, (r.g1(B * Co * So)), BLK, md, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
                                                       tr->cx[j]);
         if (j < NL - 1) {
-            r.reduce(R_SUM, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), STAT_STRIDE, nullptr, nullptr, nullptr,
-                     nullptr);
-            r.reduce(R_SQDEV, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), STAT_STRIDE, G + o.mean, G + o.var,
-                     P + o.mean, P + o.var);
+            if (!inf(NL + j)) {
+                r.reduce(R_SUM, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), STAT_STRIDE, nullptr, nullptr, nullptr,
+                         nullptr);
+                r.reduce(R_SQDEV, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), STAT_STRIDE, G + o.mean,
+                         G + o.var, P + o.mean, P + o.var);
+            }
             KL(k_bn_apply, (r.g1(B * Co * So)), BLK, md, tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1],
                                                          Co, So);
         }
@@ -1011,32 +1113,43 @@ int run_step(covahip_train *tr, int B) {
     // ---------------------------------------------------------------- backward
     KL(k_final_bwd, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
                                             tr->d_counts);
-    r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
-    r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fb, nullptr, nullptr, nullptr);
+    if (!dec_fz(NL - 1)) {
+        r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
+        r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fb, nullptr, nullptr, nullptr);
+    }
     if (!r.ok()) return r.rc;
-    for (int j = NL - 1; j >= 0; j--) {
+    for (int j = NL - 1; j >= 0 && need_dy[j]; j--) {
         const int Ci = DEC_CI[j], Co = DEC_CO[j];
         const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
         const DecOff &o = tr->dof[j];
         const int64_t So = (int64_t)Ho * Wo;
         if (j < NL - 1) {   // BN of this block: its output gradient is channel range [0, Co) of the next block's dz
-            r.reduce(R_BNBWD, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, RS, G + o.gamma,
-                     G + o.beta, nullptr, nullptr);
-            KL(k_bn_bwd, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma,
-                                                       tr->dy[j], Co, So, 0);
+            // the sums are gamma's and beta's gradients in either mode, and the batch-mean terms of a batch-mode layer
+            if (!dec_fz(j))
+                r.reduce(R_BNBWD, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, RS, G + o.gamma,
+                         G + o.beta, nullptr, nullptr);
+            if (inf(NL + j))
+                KL(k_bn_bwd_inf, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), P + o.gamma,
+                                                               tr->dy[j], Co, So, 0);
+            else
+                KL(k_bn_bwd, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma,
+                                                           tr->dy[j], Co, So, 0);
         }
-        r.reduce(R_SUM, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
         const int64_t per = (int64_t)Hi * Wi, Pp = (int64_t)B * per;
-        const int ns = wg_slabs(Pp);
-        const int nw = 16 * Co * Ci;
-        KL(k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                           tr->cx[j], (Pp + ns - 1) / ns);
-        KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, per, 0, nw, G + o.k);
-        KL(k_convT_dgrad, (r.g1(Pp * Ci)), BLK, md, tr->dy[j], P + o.k, tr->z[j], tr->dz[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                   tr->cx[j], make_drop(tr, 2 * NL + j));
+        if (!dec_fz(j)) {
+            r.reduce(R_SUM, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
+            const int ns = wg_slabs(Pp);
+            const int nw = 16 * Co * Ci;
+            KL(k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                               tr->cx[j], (Pp + ns - 1) / ns);
+            KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, per, 0, nw, G + o.k);
+        }
+        if (need_dz[j])
+            KL(k_convT_dgrad, (r.g1(Pp * Ci)), BLK, md, tr->dy[j], P + o.k, tr->z[j], tr->dz[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                       tr->cx[j], make_drop(tr, 2 * NL + j));
         if (!r.ok()) return r.rc;
     }
-    for (int i = NL - 1; i >= 0; i--) {
+    for (int i = NL - 1; i >= 0 && enc_live(i); i--) {
         const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
         const EncOff &o = tr->eo[i];
         const int zj = NL - 1 - i;
@@ -1046,25 +1159,35 @@ int run_step(covahip_train *tr, int B) {
         KL(k_tmix_bwd, (dim3(nb, 1, K)), BLK, md, tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj],
                                                   DEC_CI[zj], c_off, tr->dp[i], tr->slab, Co, (int64_t)Hp * Wp, (B * tper + nb - 1) / nb, make_drop(tr, 2 * i),
                                                   make_drop(tr, 2 * i + 1));
-        KL(k_sum_slabs, (dim3(1, 1, K)), BLK, md, tr->slab, tper, 1, 32, G + o.w1);
+        if (!enc_fz(i)) KL(k_sum_slabs, (dim3(1, 1, K)), BLK, md, tr->slab, tper, 1, 32, G + o.w1);
         const int64_t S = (int64_t)TT * H * W;
         KL(k_pool_bwd, (r.g1(B * Co * S)), BLK, md, tr->dp[i], tr->arg[i], tr->dc[i], Co, H, W, Hp, Wp);
-        r.reduce(R_BNBWD, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, RS, G + o.gamma, G + o.beta, nullptr, nullptr);
-        KL(k_bn_bwd, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], Co, S, 1);
-        r.reduce(R_SUM, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
-        const float *xin = i ? tr->e[i - 1] : tr->x0;
-        const int64_t Pp = (int64_t)B * S;
-        const int ns = wg_slabs(Pp);
-        const int nw = 9 * Ci * Co;
-        KL(k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
-        KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, S, 0, nw, G + o.k);
-        if (i > 0) KL(k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, md, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
+        if (!enc_fz(i))
+            r.reduce(R_BNBWD, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, RS, G + o.gamma, G + o.beta, nullptr, nullptr);
+        if (inf(i))
+            KL(k_bn_bwd_inf, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), P + o.gamma, tr->dc[i], Co, S, 1);
+        else
+            KL(k_bn_bwd, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], Co, S, 1);
+        if (!enc_fz(i)) {
+            r.reduce(R_SUM, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
+            const float *xin = i ? tr->e[i - 1] : tr->x0;
+            const int64_t Pp = (int64_t)B * S;
+            const int ns = wg_slabs(Pp);
+            const int nw = 9 * Ci * Co;
+            KL(k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
+            KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, S, 0, nw, G + o.k);
+        }
+        if (i > 0 && enc_live(i - 1)) KL(k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, md, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
         if (!r.ok()) return r.rc;
     }
 
     // ---------------------------------------------------------------- Adam (lr_t per model in the table)
-    KL(k_adam, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
-                                                   tr->cfg.beta2, tr->cfg.eps);
+    if (fz)
+        KL(k_adam_plan, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
+                                                            tr->cfg.beta2, tr->cfg.eps);
+    else
+        KL(k_adam, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
+                                                       tr->cfg.beta2, tr->cfg.eps);
     if (!r.ok()) return r.rc;
     return COVAHIP_OK;
 }
@@ -1080,17 +1203,7 @@ int run_eval(covahip_train *tr, int B) {
     const int H0 = tr->H[0], W0 = tr->W[0];
     const DropS off{0, 0u, 1.f, 0};   // the identity (see k_eval_stat)
     auto stat = [&](int layer) { return tr->stat + layer * 256; };
-    EvalBN bn;
-    for (int i = 0; i < NL; i++) {
-        bn.mean[i] = (int32_t)tr->eo[i].mean;
-        bn.var[i] = (int32_t)tr->eo[i].var;
-        bn.C[i] = ENC_C[i + 1];
-    }
-    for (int j = 0; j < NL - 1; j++) {
-        bn.mean[NL + j] = (int32_t)tr->dof[j].mean;
-        bn.var[NL + j] = (int32_t)tr->dof[j].var;
-        bn.C[NL + j] = DEC_CO[j];
-    }
+    const EvalBN bn = bn_table(tr);
     KL(k_eval_stat, (dim3(2 * NL - 1, 1, tr->K)), 128, md, P, tr->stat, bn, tr->cfg.bn_eps);
     KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
     for (int i = 0; i < NL; i++) {
@@ -1126,6 +1239,23 @@ int run_eval(covahip_train *tr, int B) {
     KL(k_eval_tail, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
     if (!r.ok()) return r.rc;
     return COVAHIP_OK;
+}
+
+// Adam's mask under a plan: 1 trained, 0 the BN moving statistics (never trained), 2 the tensors of a frozen group.
+std::vector<uint8_t> plan_mask(const covahip_train *tr, uint32_t frozen) {
+    std::vector<uint8_t> m(N_PARAMS, 1);
+    for (int i = 0; i < NL; i++) {
+        const EncOff &o = tr->eo[i];
+        if (frozen >> i & 1u) std::fill(m.begin() + o.k, m.begin() + o.w2 + TT * TT, 2);
+        std::fill(m.begin() + o.mean, m.begin() + o.w1, 0);
+    }
+    for (int j = 0; j < NL; j++) {
+        const DecOff &o = tr->dof[j];
+        const size_t end = j < NL - 1 ? tr->dof[j + 1].k : N_PARAMS;   // block 3's group ends with final.kernel / final.bias
+        if (frozen >> (NL + j) & 1u) std::fill(m.begin() + o.k, m.begin() + end, 2);
+        if (j < NL - 1) std::fill(m.begin() + o.mean, m.begin() + o.var + DEC_CO[j], 0);
+    }
+    return m;
 }
 
 bool finite_pos(float v) { return std::isfinite(v) && v > 0.f; }
@@ -1229,10 +1359,7 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_loss, (size_t)K * sizeof(float), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_sample_loss, (size_t)B * sizeof(float), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_counts, (size_t)K * 3 * sizeof(unsigned long long), hipHostMallocDefault));
-    // BN moving statistics are not trained
-    std::vector<uint8_t> tmask(N_PARAMS, 1);
-    for (int i = 0; i < NL; i++) std::fill(tmask.begin() + tr->eo[i].mean, tmask.begin() + tr->eo[i].w1, 0);
-    for (int j = 0; j < NL - 1; j++) std::fill(tmask.begin() + tr->dof[j].mean, tmask.begin() + tr->dof[j].var + DEC_CO[j], 0);
+    const std::vector<uint8_t> tmask = plan_mask(tr, 0);
     const hipStream_t s = ctx->stream;
     for (int k = 0; k < K; k++)
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params + (size_t)k * N_PARAMS, static_cast<const uint8_t *>(blobs[k]) + 64,
@@ -1507,6 +1634,29 @@ int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n) {
 }
 
 int covahip_train_grads(covahip_train *tr, float *flat, size_t n) { return covahip_train_grads_m(tr, 0, flat, n); }
+
+int covahip_train_set_plan(covahip_train *tr, const covahip_train_plan *plan) {
+    if (!tr || !plan) return COVAHIP_ERR_INVALID_ARG;
+    if ((plan->frozen_groups & ~0xFFu) || (plan->bn_inference & ~0x7Fu) || plan->frozen_groups == 0xFFu) return COVAHIP_ERR_INVALID_ARG;
+    if (plan->frozen_groups != tr->frozen) {   // the mask is uploaded first: a failure leaves the plan as it was
+        covahip_ctx *ctx = tr->ctx;
+        COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+        if (int rc = covahip_primary_op(ctx)) return rc;
+        const std::vector<uint8_t> m = plan_mask(tr, plan->frozen_groups);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->trainable, m.data(), N_PARAMS, hipMemcpyHostToDevice, ctx->stream));
+        COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // m leaves scope
+    }
+    tr->frozen = plan->frozen_groups;
+    tr->bn_inf = plan->bn_inference | (plan->frozen_groups & 0x7Fu);
+    return COVAHIP_OK;
+}
+
+int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan) {
+    if (!tr || !plan) return COVAHIP_ERR_INVALID_ARG;
+    plan->frozen_groups = tr->frozen;
+    plan->bn_inference = tr->bn_inf;
+    return COVAHIP_OK;
+}
 
 int covahip_train_eval_set(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *counts, float *sample_loss,
                            float *logits, covahip_train_eval_result *out, int mem_kind) {

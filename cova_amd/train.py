@@ -27,6 +27,16 @@ epoch then reports the loss / precision / recall / IoU of the validation part in
 dropout); --keep best writes the weights of the epoch with the lowest validation loss.  --checkpoint writes the whole trainer
 state after every epoch and --resume continues from it, bit for bit where the interrupted run would have gone.  --eval-only
 trains nothing: it prints one JSON line per model with the score of a weight file on the given records.
+
+Fine-tuning (include/covahip.h, "Fine-tuning"): adapt a deployed model to the camera --eval-only showed to have drifted,
+
+    python -m cova_amd.train NEWCAM.tfrecord -o adapted.cvhw --init blobnet.cvhw --freeze encoder --freeze-bn --epochs 5
+
+--init starts from a weight file instead of a fresh initialisation (with --set: one file for every model, or a directory of
+per-model files named as --set -o writes them).  --freeze takes layer groups (enc0..enc3, dec0..dec3, or encoder / decoder):
+their weights are not trained and no gradient work is spent on them.  --freeze-bn keeps every BatchNorm layer on the moving
+statistics of the base model instead of the statistics of a batch of 4.  --resume with the same flags continues exactly; the
+plan is not part of the checkpoint.
 """
 from __future__ import annotations
 
@@ -300,6 +310,49 @@ def trainable_mask() -> np.ndarray:
     return np.concatenate(parts)
 
 
+# ------------------------------------------------------------------------------------------------ training plan (fine-tuning)
+GROUPS = ("enc0", "enc1", "enc2", "enc3", "dec0", "dec1", "dec2", "dec3")   # bit order of covahip_train_plan.frozen_groups
+BN_LAYERS = GROUPS[:7]                                                       # ... and of .bn_inference (dec3 has no BN)
+_SHORTHANDS = {"encoder": GROUPS[:4], "decoder": GROUPS[4:]}
+
+
+def _plan_names(arg, valid, what):
+    if arg is None:
+        return []
+    if isinstance(arg, str):
+        arg = [n for n in arg.split(",") if n]
+    out = []
+    for name in arg:
+        if name == "all" and what == "bn_inference":
+            out += valid
+        elif name in _SHORTHANDS:
+            out += [n for n in _SHORTHANDS[name] if n in valid]
+        elif name in valid:
+            out.append(name)
+        else:
+            raise ValueError(f"{what}: unknown name {name!r} (one of {', '.join(valid)}, encoder, decoder"
+                             + (", all)" if what == "bn_inference" else ")"))
+    return out
+
+
+def plan_bits(freeze=(), bn_inference=()):
+    """(frozen_groups, bn_inference) of a covahip_train_plan from names: "enc0".."enc3", "dec0".."dec3" (bn_inference: up to
+    "dec2"), the shorthands "encoder" / "decoder", and bn_inference="all"; a comma-separated string or an iterable.  The
+    bn_inference bits are the ones given: the library adds the frozen groups' layers.  Unknown names and a plan that freezes
+    all eight groups (nothing left to train) are a ValueError."""
+    fz = sum({1 << GROUPS.index(n) for n in _plan_names(freeze, GROUPS, "freeze")})
+    bn = sum({1 << BN_LAYERS.index(n) for n in _plan_names(bn_inference, BN_LAYERS, "bn_inference")})
+    if fz == 0xFF:
+        raise ValueError("freeze: all eight groups frozen, nothing left to train")
+    return fz, bn
+
+
+def plan_names(frozen_groups: int, bn_inference: int) -> dict:
+    """{"freeze": names, "bn_inference": names} of plan bits, in bit order."""
+    return {"freeze": tuple(n for k, n in enumerate(GROUPS) if frozen_groups >> k & 1),
+            "bn_inference": tuple(n for k, n in enumerate(BN_LAYERS) if bn_inference >> k & 1)}
+
+
 # ------------------------------------------------------------------------------------------------ validation split, state blob
 def split_tail(stacks: np.ndarray, labels: np.ndarray, frac: float):
     """((train stacks, train labels), (validation stacks, validation labels)): the LAST ceil(frac * N) samples validate, the
@@ -407,6 +460,21 @@ class _State:
     def save_state(self, path, epoch: int = 0) -> None:
         _replace_file(path, self.state_bytes(epoch))
 
+    def set_plan(self, freeze=(), bn_inference=()) -> None:
+        """The training plan from the next step on (for every model of a set): `freeze` names layer groups that are not trained,
+        `bn_inference` BatchNorm layers that normalise with their moving statistics and leave them alone (plan_bits for the
+        names; a frozen group's BatchNorm is in inference mode anyway).  set_plan() restores full training.  The plan is not
+        part of the trainer state: set it again after creating the trainer a state is loaded into."""
+        fz, bn = plan_bits(freeze, bn_inference)
+        L.check(self._lib.covahip_train_set_plan(self.handle, C.byref(L.TrainPlan(fz, bn))), "covahip_train_set_plan", self.ctx.handle)
+
+    @property
+    def plan(self) -> dict:
+        """The effective plan as names: {"freeze": (...), "bn_inference": (...)}, the latter with the frozen groups' layers."""
+        p = L.TrainPlan()
+        L.check(self._lib.covahip_train_get_plan(self.handle, C.byref(p)), "covahip_train_get_plan")
+        return plan_names(p.frozen_groups, p.bn_inference)
+
     def load_state(self, path) -> int:
         with open(path, "rb") as f:
             return self.load_state_bytes(f.read())
@@ -445,7 +513,8 @@ class Trainer(_State):
     """BlobNet training on the GPU over covahip_train_*.  `step` counts the steps taken (the dropout hash's step)."""
 
     def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, max_batch: int = 4, weights_flat: np.ndarray | None = None,
-                 seed: int = 0, dropout: float = 0.2, lr: float = 1e-3):
+                 seed: int = 0, dropout: float = 0.2, lr: float = 1e-3, freeze=(), bn_inference=()):
+        plan_bits(freeze, bn_inference)             # a bad plan raises before anything is created
         self.ctx, self.h, self.w, self.max_batch = ctx, h_mb, w_mb, max_batch
         self._lib = L.lib()
         cfg = L.TrainCfg()
@@ -460,6 +529,8 @@ class Trainer(_State):
                 ctx.handle)
         self.handle = h
         self.step_count = 0
+        if freeze or bn_inference:
+            self.set_plan(freeze, bn_inference)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -617,9 +688,10 @@ class TrainerSet(_State):
     model k's steps alone (include/covahip.h, "Training sets")."""
 
     def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, weights=None, n_models: int | None = None, seeds=None,
-                 max_batch: int = 4, dropout: float = 0.2, lr: float = 1e-3):
+                 max_batch: int = 4, dropout: float = 0.2, lr: float = 1e-3, freeze=(), bn_inference=()):
         """weights: a list of flat weight arrays, one per model; or n_models with weights None: model k = init_weights(seeds[k]).
-        seeds: the dropout seed per model (default 0, 1, ..)."""
+        seeds: the dropout seed per model (default 0, 1, ..).  freeze / bn_inference: the training plan (set_plan)."""
+        plan_bits(freeze, bn_inference)
         if weights is None:
             if n_models is None:
                 raise ValueError("TrainerSet needs weights=[...] or n_models=K")
@@ -650,6 +722,8 @@ class TrainerSet(_State):
                 "covahip_train_create_set", ctx.handle)
         self.handle = h
         self.step_counts = [0] * k
+        if freeze or bn_inference:
+            self.set_plan(freeze, bn_inference)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -858,10 +932,19 @@ def parse_args(argv=None):
     ap.add_argument("--eval-only", metavar="WEIGHTS", help="train nothing: score this weight file (with --set: a directory of "
                                                            "weight files named as --set writes them) on the records, one JSON "
                                                            "line per model")
+    ap.add_argument("--init", metavar="WEIGHTS", help="start from this weight file instead of a fresh initialisation (with --set: "
+                                                      "one file for every model, or a directory of per-model files named as "
+                                                      "--set -o writes them)")
+    ap.add_argument("--freeze", metavar="GROUPS", help="layer groups that are not trained: enc0..enc3, dec0..dec3 joined with "
+                                                       "commas, or encoder / decoder")
+    ap.add_argument("--freeze-bn", action="store_true", help="every BatchNorm layer normalises with its moving statistics and "
+                                                             "leaves them alone")
     a = ap.parse_args(argv)
     if a.eval_only:
         if a.resume:
             ap.error("--resume continues a training; --eval-only trains nothing")
+        if a.init or a.freeze or a.freeze_bn:
+            ap.error("--init / --freeze / --freeze-bn shape a training; --eval-only trains nothing")
         if a.val or a.val_frac is not None or a.checkpoint or a.keep != "last" or a.output:
             ap.error("--eval-only takes the weights and the records only")
         return a
@@ -875,7 +958,35 @@ def parse_args(argv=None):
         ap.error("--val-frac must lie strictly between 0 and 1")
     if a.val and a.as_set and len(a.val) != len(a.records):
         ap.error(f"--val names {len(a.val)} models, the set has {len(a.records)}")
+    if a.init and a.resume:
+        ap.error("--init and --resume exclude each other: a checkpoint holds its own weights")
+    try:
+        plan_bits(a.freeze, "all" if a.freeze_bn else ())
+    except ValueError as e:
+        ap.error(str(e))
     return a
+
+
+def _plan_kw(a) -> dict:
+    """The Trainer / TrainerSet keywords of --freeze / --freeze-bn."""
+    return {"freeze": a.freeze or (), "bn_inference": "all" if a.freeze_bn else ()}
+
+
+def _read_weights(path) -> np.ndarray:
+    with open(path, "rb") as f:
+        return W.from_bytes(f.read())
+
+
+def init_paths(records, init: str):
+    """--init with --set: the weight file of every model, in argument order.  A directory holds one file per model, named as
+    --set -o names them (set_jobs); a file initialises every model.  A missing per-model file is a ValueError."""
+    if not os.path.isdir(init):
+        return [init] * len(records)
+    paths = [p for _, p in set_jobs(records, init)]
+    missing = [p for p in paths if not os.path.isfile(p)]
+    if missing:
+        raise ValueError(f"--init {init}: no weight file {', '.join(missing)}")
+    return paths
 
 
 def _load(files, a):
@@ -957,7 +1068,9 @@ def main_set(a) -> int:
               + (f", {val[k][0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
     os.makedirs(a.output, exist_ok=True)
     ctx = Context(a.device)
-    ts = TrainerSet(ctx, a.h_mb, a.w_mb, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))], max_batch=a.batch)
+    init = [_read_weights(p) for p in init_paths(a.records, a.init)] if a.init else None
+    ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=init, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))],
+                    max_batch=a.batch, **_plan_kw(a))
     start = _resume(ts, a, len(jobs))
     ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)
@@ -986,7 +1099,8 @@ def main(argv=None) -> int:
     print(f"{n_frames} frames -> {records[0].shape[0]} samples of {a.h_mb}x{a.w_mb}"
           + (f", {val[0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
     ctx = Context(a.device)
-    tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed)
+    tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed, weights_flat=_read_weights(a.init) if a.init else None,
+                 **_plan_kw(a))
     start = _resume(tr, a, 1)
     tr.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)

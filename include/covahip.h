@@ -410,6 +410,39 @@ int covahip_train_eval_set(covahip_train *tr, const uint8_t *stack, const uint8_
 int covahip_train_state_size(covahip_train *tr, size_t *n);
 int covahip_train_save_state(covahip_train *tr, uint64_t user_tag, void *buf, size_t cap, size_t *n);
 int covahip_train_load_state(covahip_train *tr, const void *buf, size_t n, uint64_t *user_tag);
+/* Fine-tuning: a training plan says which layer groups a step trains and which BatchNorm layers run in inference mode -- what
+ * Keras does with `trainable = False` (the variable is not given to the optimiser; a BatchNormalization layer normalises with
+ * its moving statistics and does not update them).  One plan per trainer: in a set it holds for every model, like cfg.
+ *   Groups: encoder level i = enc{i}.conv.kernel / .bias, enc{i}.bn.gamma / .beta, enc{i}.tmix.w1 / .w2; decoder block j =
+ *   dec{j}.up.kernel / .bias, dec{j}.bn.gamma / .beta, and for j = 3 final.kernel / final.bias.
+ *   A FROZEN group: none of its tensors and none of their Adam moments changes in a step, its slots in covahip_train_grads
+ *   read 0, and its BatchNorm is in inference mode: the effective bn_inference = given | (frozen_groups & 0x7F).  Gradients
+ *   still flow THROUGH it to trainable groups nearer the input.
+ *   A BN layer in INFERENCE MODE: forward (x - moving_mean) * (1 / sqrt(moving_var + bn_eps)) * gamma + beta, the expression
+ *   of covahip_train_eval; its moving statistics are not updated; backward dx = dy * gamma / sqrt(moving_var + bn_eps), no
+ *   batch-mean terms.  Where its group is not frozen gamma and beta are still trained: dgamma = sum dy * xhat, dbeta = sum dy
+ *   with xhat formed from the moving statistics.  Its mean / var slots of covahip_train_grads hold the moving values the
+ *   forward normalised with.  The convT bias in front of such a layer has a real, non-zero gradient (a batch-mode layer
+ *   subtracts the bias again).
+ *   Unchanged by any plan: the dropout hash (site, step) -- dropout stays active in frozen groups, this is training mode --,
+ *   Adam's t, the loss, TP / FP / FN.
+ *   Work follows the plan: no weight gradient is computed for a frozen group, and the backward pass stops where nothing
+ *   trainable lies nearer the input (encoder frozen: nothing of the encoder's backward runs).
+ * covahip_train_set_plan: takes effect from the next step and may be changed between steps; the default is the empty plan.
+ * Bits outside the fields, a NULL argument, or all eight groups frozen: COVAHIP_ERR_INVALID_ARG, the trainer untouched.
+ * covahip_train_get_plan: the EFFECTIVE plan (frozen_groups as given, bn_inference with the frozen groups' layers).
+ *   Contract D -- the empty plan is no plan.  A trainer that never sets a plan, or sets the empty one, is the trainer described
+ *   above, bit for bit: losses, gradients, weights, moving statistics, Adam state.
+ *   The other contracts hold under any plan: model k of a set equals the solo trainer with the same plan; evaluation
+ *   (Contracts A and B) does not depend on the plan; exact resume (Contract C) holds with the plan set again by the caller, as
+ *   the cfg is created again -- the plan is not in the state blob and covahip_train_load_state does not touch it.  A model
+ *   that sits a set step out keeps its last gradients, also in slots a newer plan freezes. */
+typedef struct covahip_train_plan {
+    uint32_t frozen_groups; /* bit i (0..3): encoder level i; bit 4 + j (j = 0..3): decoder block j */
+    uint32_t bn_inference;  /* bit i (0..3): enc{i}.bn; bit 4 + j (j = 0..2): dec{j}.bn              */
+} covahip_train_plan;
+int covahip_train_set_plan(covahip_train *tr, const covahip_train_plan *plan);
+int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan);
 void covahip_train_destroy(covahip_train *tr);
 
 /* ------------------------------------------------------------ MoG labels

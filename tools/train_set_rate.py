@@ -5,7 +5,8 @@ covahip_train_step calls on K solo trainers, one after the other in the same pro
     python tools/train_set_rate.py [--h-mb 45 --w-mb 80 --batch 4 --models 1,2,4,8,16 --steps 30 --warmup 5 --repeats 3]
 
 Device-pointer steps (the loss read-back included).  The two sides alternate, `--repeats` times per K: the spread of a side's
-rows is the box's noise.  One JSON line per K.  `--only set|solo` runs one side alone (a profiling run)."""
+rows is the box's noise.  One JSON line per K.  `--only set|solo` runs one side alone (a profiling run).  `--freeze GROUPS` /
+`--freeze-bn` put both sides under a training plan (cova_amd.train's flags of the same names)."""
 import argparse
 import json
 import os
@@ -39,8 +40,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--only", choices=("set", "solo"))
+    ap.add_argument("--freeze", default="")
+    ap.add_argument("--freeze-bn", action="store_true")
     a = ap.parse_args()
     h, w, b = a.h_mb, a.w_mb, a.batch
+    plan = {"freeze": a.freeze, "bn_inference": "all" if a.freeze_bn else ()}
     ctx = Context(0)
     for k in (int(x) for x in a.models.split(",")):
         stack = synth.stacked_batch(k * b, h, w, seed=3, streams=min(k * b, 8))
@@ -49,8 +53,8 @@ def main():
         ctx.h2d(d_stack, stack)
         ctx.h2d(d_gt, gt)
         flats = [T.init_weights(m) for m in range(k)]
-        ts = T.TrainerSet(ctx, h, w, weights=flats, seeds=list(range(k)), max_batch=b) if a.only != "solo" else None
-        solos = [T.Trainer(ctx, h, w, max_batch=b, weights_flat=flats[m], seed=m) for m in range(k)] if a.only != "set" else []
+        ts = T.TrainerSet(ctx, h, w, weights=flats, seeds=list(range(k)), max_batch=b, **plan) if a.only != "solo" else None
+        solos = [T.Trainer(ctx, h, w, max_batch=b, weights_flat=flats[m], seed=m, **plan) for m in range(k)] if a.only != "set" else []
         per_stack, per_gt = stack.nbytes // (k * b), gt.nbytes // (k * b)
 
         def solo_step():
@@ -63,7 +67,7 @@ def main():
                 set_ms.append(timed(lambda: ts.step_device(d_stack, d_gt, [b] * k), a.warmup, a.steps))
             if solos:
                 solo_ms.append(timed(solo_step, a.warmup, a.steps))
-        rec = {"h_mb": h, "w_mb": w, "batch": b, "models": k, "steps": a.steps}
+        rec = {"h_mb": h, "w_mb": w, "batch": b, "models": k, "steps": a.steps, **T.plan_names(*T.plan_bits(**plan))}
         if set_ms:
             rec.update(set_ms_per_step=[round(v, 3) for v in set_ms], set_samples_per_s=round(1e3 * k * b / min(set_ms)))
         if solo_ms:
