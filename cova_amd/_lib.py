@@ -83,6 +83,10 @@ class TrainPlan(C.Structure):
     _fields_ = [("frozen_groups", C.c_uint32), ("bn_inference", C.c_uint32)]
 
 
+class BlobNetPost(C.Structure):
+    _fields_ = [("logit_thresh", C.c_float), ("keep", C.c_void_p)]
+
+
 class MogCfg(C.Structure):
     _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
                 ("var_threshold", C.c_float)]
@@ -163,6 +167,8 @@ PROTOTYPES = {
     "covahip_filter_forward_frames_packed": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P]),
     "covahip_blobnet_load_set": (C.c_int, [_P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "covahip_blobnet_num_models": (C.c_int, [_P, _P]),
+    "covahip_blobnet_set_post": (C.c_int, [_P, C.c_int, C.POINTER(BlobNetPost)]),
+    "covahip_blobnet_get_post": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P, C.POINTER(C.c_int)]),
     "covahip_pipe_model_ids": (C.c_int, [_P, C.c_int, _P]),
     "covahip_blobnet_forward_m": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_filter_forward_m": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int]),
@@ -229,6 +235,7 @@ DEV_PROTOTYPES = {
     "covahip_dev_graph_probe": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.POINTER(C.c_float),
                                           C.POINTER(C.c_float)]),
     "covahip_dev_bboxcc_overflow": (C.c_int, [_P, C.POINTER(C.c_int32)]),
+    "covahip_dev_blobnet_tail_form": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "covahip_dev_pipe_queue_plan": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "covahip_dev_blobnet_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),

@@ -64,6 +64,14 @@ struct covahip_blobnet {
                           // and the batch / geometry make it pay; 0: never, 2: whenever they fit
     int enc_rowtiles = 1; // MFMA path: levels 2 and 3 on row-aligned tiles (enc_mfma<.., TSZ>) where the geometry suits them
     int64_t macs_per_frame = 0;
+    // per-model post-processing (covahip_blobnet_set_post): host copies of the settings, and -- from the first non-default
+    // setting on -- their device tables, one allocation: fp32 threshold per model | keep bytes u8 [n_models][H][W] | the same
+    // as bboxcc's parity planes, u32 [n_models][H][E lo, E hi, O lo, O hi] (what dec3cc_rows_mfma ANDs into its ballots)
+    std::vector<float> post_thr;                  // [n_models]
+    std::vector<std::vector<uint8_t>> post_keep;  // [n_models]: empty = keep everything, else H * W bytes of 0 / 1
+    bool post_on = false;                         // some model has a non-default setting: the POST = true kernels run
+    void *d_post = nullptr;
+    size_t post_keep_off = 0, post_planes_off = 0, post_keep_stride = 0, post_planes_stride = 0, post_bytes = 0;
 };
 
 // Whether encoder level 1 runs on enc1_mfma (16x16x32 tiles, fixed LDS row: grids of at most BN_E1_MAXW level-1 pixels) or on

@@ -5,6 +5,7 @@
 // row on top / zero column on the left when the pre-pool size is odd) and
 // utils/model/decoder.py:43-59 (convT output 2*in+2, crop ceil(p/2) top/left).
 #include <algorithm>
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -22,6 +23,7 @@ constexpr size_t N_PARAMS = 320305;
 static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
     if (!m) return;
     blobnet_release_mfma(ctx, m);
+    if (m->d_post) hipFree(m->d_post);
     for (BnWorkspace &ws : m->ws) {
         for (int i = 0; i <= BN_LEVELS; i++)
             if (ws.act[i]) hipFree(ws.act[i]);
@@ -291,6 +293,8 @@ static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *const 
     }
     int rc = blobnet_prepare_mfma(ctx, m, h_w, n_models);
     if (rc) return rc;
+    m->post_thr.assign(n_models, 0.f);   // per-model post-processing: the defaults
+    m->post_keep.assign(n_models, {});
     BnInput plan;   // planning only, both input forms, smallest and largest batch (a set: also the mixed-batch kernels)
     plan.dry = true;
     for (int pass = 0; pass < (n_models > 1 ? 8 : 4) && !rc; pass++) {
@@ -358,6 +362,84 @@ int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models) {
     if (!ctx || !n_models) return COVAHIP_ERR_INVALID_ARG;
     if (!ctx->blobnet) return COVAHIP_ERR_NOT_LOADED;
     *n_models = ctx->blobnet->n_models;
+    return COVAHIP_OK;
+}
+
+// Per-model post-processing (covahip.h).  The device tables are one allocation, made at the first non-default setting and
+// rewritten whole by every later call: the ctx is drained first, so nothing in flight reads them.
+//   fp32 threshold [n_models] | keep bytes u8 [n_models][H][W] | keep planes u32 [n_models][H][E lo, E hi, O lo, O hi]
+// A plane holds the even (E) or odd (O) pixels of a row, pixel 2k (2k + 1) at bit k: bboxcc's planes (bboxcc_wave.h), which
+// dec3cc_rows_mfma ballots its logits into.  That kernel takes rows of at most 128 pixels; the planes of a wider grid are not read.
+static int upload_post(covahip_ctx *ctx, covahip_blobnet *m) {
+    const size_t hw = (size_t)m->H * m->W, n = (size_t)m->n_models;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    if (!m->d_post) {
+        m->post_keep_stride = (hw + 15) & ~(size_t)15;
+        m->post_planes_stride = (size_t)m->H * 16;
+        m->post_keep_off = al(n * sizeof(float));
+        m->post_planes_off = al(m->post_keep_off + n * m->post_keep_stride);
+        m->post_bytes = m->post_planes_off + n * m->post_planes_stride;
+        COVAHIP_CHECK_HIP(ctx, hipMalloc(&m->d_post, m->post_bytes));
+    }
+    std::vector<uint8_t> host(m->post_bytes, 0);
+    std::memcpy(host.data(), m->post_thr.data(), n * sizeof(float));
+    for (size_t k = 0; k < n; k++) {
+        uint8_t *kb = host.data() + m->post_keep_off + k * m->post_keep_stride;
+        uint32_t *kp = reinterpret_cast<uint32_t *>(host.data() + m->post_planes_off + k * m->post_planes_stride);
+        const std::vector<uint8_t> &keep = m->post_keep[k];
+        for (int y = 0; y < m->H; y++)
+            for (int x = 0; x < m->W; x++) {
+                const bool on = keep.empty() || keep[(size_t)y * m->W + x];
+                kb[(size_t)y * m->W + x] = on ? 1 : 0;
+                if (on && x < 128) kp[y * 4 + 2 * (x & 1) + (x >> 6)] |= 1u << ((x >> 1) & 31);
+            }
+    }
+    COVAHIP_CHECK_HIP(ctx, hipMemcpy(m->d_post, host.data(), host.size(), hipMemcpyHostToDevice));
+    return COVAHIP_OK;
+}
+
+int covahip_blobnet_set_post(covahip_ctx *ctx, int model, const covahip_blobnet_post *post) {
+    if (!ctx) return COVAHIP_ERR_INVALID_ARG;
+    covahip_blobnet *m = ctx->blobnet;
+    if (!m) return COVAHIP_ERR_NOT_LOADED;
+    if (model < 0 || model >= m->n_models) return COVAHIP_ERR_INVALID_ARG;
+    if (post && !std::isfinite(post->logit_thresh)) return COVAHIP_ERR_INVALID_ARG;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_sync_all(ctx)) return rc;   // batches in flight keep the settings they were submitted with
+    const size_t hw = (size_t)m->H * m->W;
+    m->post_thr[model] = post ? post->logit_thresh : 0.f;
+    m->post_keep[model].clear();
+    if (post && post->keep) {
+        m->post_keep[model].resize(hw);
+        for (size_t i = 0; i < hw; i++) m->post_keep[model][i] = post->keep[i] ? 1 : 0;
+    }
+    bool on = false;
+    for (int k = 0; k < m->n_models; k++) on = on || m->post_thr[k] != 0.f || !m->post_keep[k].empty();
+    if (on || m->d_post) {
+        if (int rc = upload_post(ctx, m)) {   // (an allocation or a copy failed: the model falls back to the defaults rather than to half a table)
+            m->post_thr.assign(m->n_models, 0.f);
+            m->post_keep.assign(m->n_models, {});
+            m->post_on = false;
+            return rc;
+        }
+    }
+    m->post_on = on;
+    return COVAHIP_OK;
+}
+
+int covahip_blobnet_get_post(covahip_ctx *ctx, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_keep) {
+    if (!ctx) return COVAHIP_ERR_INVALID_ARG;
+    covahip_blobnet *m = ctx->blobnet;
+    if (!m) return COVAHIP_ERR_NOT_LOADED;
+    if (model < 0 || model >= m->n_models) return COVAHIP_ERR_INVALID_ARG;
+    const std::vector<uint8_t> &keep = m->post_keep[model];
+    if (logit_thresh) *logit_thresh = m->post_thr[model];
+    if (has_keep) *has_keep = keep.empty() ? 0 : 1;
+    if (keep_or_null) {
+        const size_t hw = (size_t)m->H * m->W;
+        if (keep.empty()) std::memset(keep_or_null, 1, hw);
+        else std::memcpy(keep_or_null, keep.data(), hw);
+    }
     return COVAHIP_OK;
 }
 
@@ -509,6 +591,12 @@ int covahip_filter_forward_frames_packed_m(covahip_ctx *ctx, const uint16_t *d_r
     if (!lane.ok()) return COVAHIP_ERR_HIP;
     return filter_placed(ctx, m, reinterpret_cast<const uint8_t *>(d_records), n_frames, stack_index, batch, area_thresh, d_boxes, d_counts,
                          max_boxes, d_logits, d_mask, true, model_ids);
+}
+
+int covahip_dev_blobnet_tail_form(covahip_ctx *ctx, int *form) {
+    if (!ctx || !form) return COVAHIP_ERR_INVALID_ARG;
+    *form = ctx->tail_form;
+    return COVAHIP_OK;
 }
 
 // Developer read-back (include/covahip_dev.h): one activation buffer of lane 0's workspace, for stage-by-stage tests.

@@ -35,6 +35,7 @@
 #include "bboxcc_body.h"
 #include "bboxcc_wave.h"
 #include "blobnet.h"
+#include "covahip_dev.h"
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
@@ -314,6 +315,41 @@ struct DecMs {
     const uint8_t *model_ids;   // model id per stack [B]
     uint32_t mstride;           // bytes between two models' prepared weights
 };
+// Per-model post-processing ("Per-model post-processing"; covahip_blobnet_set_post):
+//   mask = (logit > threshold of the stack's model) && keep map of the stack's model
+// in the kernels that turn logits into a mask, instantiated with POST = true.  Behind DecMs in the argument lists, for the same
+// reason (a POST = false kernel gets the empty DecNoPost).  A batch of one model gets that model's threshold by value and its keep pointers; a mixed batch (MS) gets model 0's
+// and takes every stack's through the model id, like the weights: thr_tab[id], keep + id * keep_stride, planes + id * planes_stride.
+// POST = false is the kernel without any of it: threshold 0, no keep map, these arguments are not read.
+struct DecPost {
+    float thr;                  // logit threshold of the batch's model
+    const float *thr_tab;       // MS: threshold per model
+    const uint8_t *keep;        // u8 [Hd][Wd], 1 = the macroblock may be foreground (always present: all ones without a keep map)
+    const uint32_t *planes;     // the same as bboxcc's parity planes: u32 [Hd][E lo, E hi, O lo, O hi] (dec3cc_rows_mfma)
+    uint32_t keep_stride, planes_stride;   // MS: bytes between two models' maps
+};
+// the argument of a POST = false kernel: nothing
+struct DecNoPost {};
+template <bool POST>
+using PostArg = std::conditional_t<POST, DecPost, DecNoPost>;
+// The settings of stack b: of the batch's model, or through the stack's model id (MS; a scalar, the stack is workgroup-uniform).
+// POST = false: the literal threshold 0 and no maps -- the flag-off kernels contain none of this.
+struct StackPost {
+    float thr;
+    const uint8_t *keep;
+    const uint32_t *planes;
+};
+template <bool POST, bool MS>
+__device__ __forceinline__ StackPost stack_post(const PostArg<POST> &pp, const uint8_t *mid, int b) {
+    if constexpr (!POST) {
+        return StackPost{0.f, nullptr, nullptr};
+    } else if constexpr (!MS) {
+        return StackPost{pp.thr, pp.keep, pp.planes};
+    } else {
+        const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)mid[b]);
+        return StackPost{pp.thr_tab[id], at_model(pp.keep, id * pp.keep_stride), at_model(pp.planes, id * pp.planes_stride)};
+    }
+}
 
 #ifdef PHASE_TIMING
 // developer build only (tools/phase_timing.sh): wall-clock ticks (s_memrealtime, 100 MHz) per phase of the item loop,
@@ -1689,8 +1725,9 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
 // of 4 consecutive output channels -> one (u,v) decomposition per lane per tile and 8-byte packed
 // stores.  The last block (FINAL) has the final 1x1 conv folded in (no non-linearity between
 // them): 4 rows = the 4 parities, output = logit (+ threshold).
-template <int C1, int C2, int COUT, bool FINAL, bool MS = false>
-__global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 4) * 64, 2) void dec_mfma(DecArgs p, DecMs pm) {
+template <int C1, int C2, int COUT, bool FINAL, bool MS = false, bool POST = false>
+__global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 4) * 64, 2) void dec_mfma(DecArgs p, DecMs pm, PostArg<POST> pp) {
+    static_assert(FINAL || !POST, "post-processing belongs to the block that writes the mask");
     constexpr int C = C1 + C2, MT = FINAL ? 1 : 4 * COUT / 32, NW = MT > 4 ? MT : 4, PG = NW / MT;
     constexpr int KC = C / 16, KSTEPS = 4 * KC, CPP = C / 8, PS = C * 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -1718,6 +1755,7 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
     const int n_items = p.B * p.nbands;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
         const int b = fdiv(item, p.mNb), band = item - b * p.nbands;
+        [[maybe_unused]] const StackPost sp = stack_post<POST, MS>(pp, pm.model_ids, b);
         if constexpr (MS) {   // every item takes its stack's weights: one copy in registers, no second one kept for a compare
             const uint32_t moff = model_off<MS>(pm.model_ids, pm.mstride, b);
             const half8 *wfr = at_model(p.wfrag, moff);
@@ -1808,7 +1846,9 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
                             float l = acc[r] + fbias;
                             if constexpr (C2 == 0) l += pl[r];
                             if (p.logits) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l;
-                            mrows[(Y - Yb) * p.Wd + X] = l > 0.f ? 1 : 0;   // band mask, assembled in LDS
+                            bool fg = l > sp.thr;
+                            if constexpr (POST) fg = fg && sp.keep[Y * p.Wd + X];
+                            mrows[(Y - Yb) * p.Wd + X] = fg ? 1 : 0;   // band mask, assembled in LDS
                         }
                     }
                 }
@@ -2158,8 +2198,8 @@ struct Dec3ccArgs {
 // PART (round 5): the block's input is its "up" half alone (16 channels, half the tile, half the products, the whole frame in
 // one buffer); the skip half's share of every logit comes as fp32 partial logits from the level-1 kernel (Enc1Args::part),
 // lands in LDS beside the tile and is added in the epilogue.
-template <bool WV, bool PART, bool MS = false>
-__global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) {
+template <bool WV, bool PART, bool MS = false, bool POST = false>
+__global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q, PostArg<POST> qp) {
     constexpr int C1 = 16, C2 = PART ? 0 : 16, C = C1 + C2, NW = ccbody::CC_THREADS / 64;
     constexpr int KC = C / 16, KSTEPS = 4 * KC, CPP = C / 8, PS = C * 2;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -2176,6 +2216,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
 #endif
 
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
+        const StackPost sp = stack_post<POST, MS>(qp, q.ms.model_ids, b);
         // the weight fragments are (re)loaded per frame: their registers are free again while bboxcc runs
         half8 wf[KSTEPS];
         if constexpr (MS) {
@@ -2260,7 +2301,9 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
                             float l = acc[r] + fbias;
                             if constexpr (PART) l += pl[r];
                             if (p.logits) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l;
-                            mfull[Y * p.Wd + X] = l > 0.f ? 1 : 0;
+                            bool fg = l > sp.thr;
+                            if constexpr (POST) fg = fg && sp.keep[Y * p.Wd + X];
+                            mfull[Y * p.Wd + X] = fg ? 1 : 0;
                         }
                     }
                 }
@@ -2312,8 +2355,11 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q) 
 // Same products in the same order, same logit expression: logits, mask, boxes and their order are bit-identical to dec3cc_mfma<true,
 // true> (tests/test_gpu_blobnet.py).  Taken when the partial-logit form runs, the frame's tile fits one buffer, a grid row has at
 // most 64 positions and the run-based bboxcc body takes the shape.
-template <bool MS = false>
-__global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArgs q) {
+// POST: the ballot compares with the stack's threshold, and once the frame's ballots are complete its planes are ANDed with the
+// keep planes of the stack's model (same [row][E lo, E hi, O lo, O hi] layout, from HBM: one word per thread) -- before the mask
+// bytes are expanded from them and before bboxcc reads them.
+template <bool MS = false, bool POST = false>
+__global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArgs q, PostArg<POST> qp) {
     constexpr int NW = ccbody::CC_THREADS / 64, PS = 32;   // 16 channels per pixel
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DecArgs &p = q.d;
@@ -2341,6 +2387,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
         const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
         const float fbias = MS ? at_model(p.epi, moff)[0] : fbias0;
+        const StackPost sp = stack_post<POST, MS>(qp, q.ms.model_ids, b);
         half8 wf[4];   // (re)loaded per frame: their registers are free again while bboxcc runs
 #pragma unroll
         for (int ks = 0; ks < 4; ks++) wf[ks] = (MS ? at_model(p.wfrag, moff) : p.wfrag)[ks * 64 + lane];
@@ -2410,7 +2457,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
 #pragma unroll
             for (int r = 0; r < 4; r++) {
                 // bit v - 32 h of the ballot = output pixel (Y, 2 v + X0): plane X0 & 1, plane bit v + (X0 >> 1)
-                const uint64_t bits = (uint64_t)(uint32_t)__ballot(live && l[r] > 0.f) << (32 * h);
+                const uint64_t bits = (uint64_t)(uint32_t)__ballot(live && l[r] > sp.thr) << (32 * h);
                 const int Y = 2 * u + (r >> 1) - p.cy, X0 = (r & 1) - p.cx;
                 const int pln = X0 & 1, sh = X0 >> 1;                         // (arithmetic shift: floor)
                 const int nb = (p.Wd - pln + 1) >> 1;                          // pixels of this plane in a row
@@ -2425,6 +2472,10 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
         }
         PHASE_MARK(4);   // tiles
         lds_barrier();   // the frame's planes are complete; the tile buffer is free
+        if constexpr (POST) {   // pixel row y is plane row y + 1
+            for (int i = tid; i < 4 * p.Hd; i += NW * 64) planes[4 + i] &= sp.planes[i];
+            lds_barrier();
+        }
         PHASE_MARK(5);   // barrier
         if (p.mask) {    // four mask bytes per thread and store, out of the planes (W is a multiple of 8: ccwave::wv_plan)
             uint32_t *dst = reinterpret_cast<uint32_t *>(p.mask + (size_t)b * p.Hd * p.Wd);
@@ -2923,7 +2974,15 @@ struct Fwd {
     uint8_t *d_mask;
     const BnCcTail *cc;
     bool part_written = false;   // the level-1 kernel wrote partial logits instead of the level-0 skip tensor
+    bool post = false;           // some model has non-default post-processing: the POST = true kernels, with these arguments
+    DecPost pp{};
 };
+
+template <bool POST>
+PostArg<POST> post_arg(const Fwd &f) {
+    if constexpr (POST) return f.pp;
+    else return DecNoPost{};
+}
 
 // One launch: opens the kernel's dynamic-LDS limit (set_lds: nothing to do up to 64 KB), brackets the launch for the profile
 // as `name` and launches -- unless the pass is planning only, which goes through every check and still opens the limit (this
@@ -3232,19 +3291,20 @@ int plan_dec_block(const Fwd &f, int j, DecPlan &p) {
 int launch_dec_block(const Fwd &f, int j, const DecPlan &p) {
     if (j == 0)
         return launched(f, with_bools([&](auto MS) {
-            return launch(f, "dec0_mfma", dec_mfma<0, 128, 64, false, MS.value>, p.grid, 512, p.lds, p.a, p.am);
+            return launch(f, "dec0_mfma", dec_mfma<0, 128, 64, false, MS.value>, p.grid, 512, p.lds, p.a, p.am, DecNoPost{});
         }, f.ms));
     if (j == 1)
         return launched(f, with_bools([&](auto MS) {
-            return launch(f, "dec1_mfma", dec_mfma<64, 64, 32, false, MS.value>, p.grid, 256, p.lds, p.a, p.am);
+            return launch(f, "dec1_mfma", dec_mfma<64, 64, 32, false, MS.value>, p.grid, 256, p.lds, p.a, p.am, DecNoPost{});
         }, f.ms));
     if (j == 2)
         return launched(f, with_bools([&](auto MS) {
-            return launch(f, "dec2_mfma", dec_mfma<32, 32, 16, false, MS.value>, p.grid, 256, p.lds, p.a, p.am);
+            return launch(f, "dec2_mfma", dec_mfma<32, 32, 16, false, MS.value>, p.grid, 256, p.lds, p.a, p.am, DecNoPost{});
         }, f.ms));
-    return launched(f, with_bools([&](auto HALF, auto MS) {
-        return launch(f, "dec3_final_mfma", dec_mfma<16, HALF.value ? 0 : 16, 16, true, MS.value>, p.grid, 256, p.lds, p.a, p.am);
-    }, p.half, f.ms));
+    return launched(f, with_bools([&](auto HALF, auto MS, auto POST) {
+        return launch(f, "dec3_final_mfma", dec_mfma<16, HALF.value ? 0 : 16, 16, true, MS.value, POST.value>, p.grid, 256, p.lds, p.a,
+                      p.am, post_arg<POST.value>(f));
+    }, p.half, f.ms, f.post));
 }
 int run_dec_block(const Fwd &f, int j) {
     DecPlan p;
@@ -3298,13 +3358,15 @@ bool run_tail_fused(const Fwd &f, const DecPlan &p) {
         (size_t)t.wg.rows_bytes <= mfull && (!f.d_mask || (reinterpret_cast<uintptr_t>(f.d_mask) & 3) == 0)) {
         t.d.swz = Swz{3, 1, 0, 0, 0};            // s = (xx >> 3) & 1 (what the staging of both forms evaluates)
         t.d.mRC = magic(out.W / 4);               // the mask expansion's division
-        return !with_bools([&](auto MS) {
-            return launch(f, "dec3_bboxcc_fused", dec3cc_rows_mfma<MS.value>, grid, ccbody::CC_THREADS, tl, t);
-        }, f.ms);
+        if (!f.dry) f.ctx->tail_form = COVAHIP_DEV_TAIL_ROWS;
+        return !with_bools([&](auto MS, auto POST) {
+            return launch(f, "dec3_bboxcc_fused", dec3cc_rows_mfma<MS.value, POST.value>, grid, ccbody::CC_THREADS, tl, t, post_arg<POST.value>(f));
+        }, f.ms, f.post);
     }
-    return !with_bools([&](auto WV, auto PART, auto MS) {
-        return launch(f, "dec3_bboxcc_fused", dec3cc_mfma<WV.value, PART.value, MS.value>, grid, ccbody::CC_THREADS, tl, t);
-    }, t.use_wv != 0, p.half, f.ms);
+    if (!f.dry) f.ctx->tail_form = COVAHIP_DEV_TAIL_BANDS + (t.use_wv ? 2 : 0) + (p.half ? 1 : 0);
+    return !with_bools([&](auto WV, auto PART, auto MS, auto POST) {
+        return launch(f, "dec3_bboxcc_fused", dec3cc_mfma<WV.value, PART.value, MS.value, POST.value>, grid, ccbody::CC_THREADS, tl, t, post_arg<POST.value>(f));
+    }, t.use_wv != 0, p.half, f.ms, f.post);
 }
 
 }  // namespace
@@ -3326,6 +3388,19 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
           by_frames ? inp.frames : inp.stack, by_frames ? inp.n_frames : batch * BN_T, by_frames ? inp.index : nullptr,
           d_logits, d_mask, cc};
     if ((size_t)f.n_frames > ws.pbuf_frames && !dry) return COVAHIP_ERR_INVALID_ARG;   // (the caller sizes P: blobnet.hip)
+    // per-model post-processing: while every model has the defaults the kernels without it run, as before
+    f.post = m->post_on;
+    if (f.post) {
+        if (!m->d_post) return COVAHIP_ERR_INVALID_ARG;
+        const uint8_t *const dp = (const uint8_t *)m->d_post;
+        const size_t k = ms ? 0 : (size_t)inp.model;
+        f.pp.thr = m->post_thr[k];
+        f.pp.thr_tab = (const float *)dp;
+        f.pp.keep = dp + m->post_keep_off + k * m->post_keep_stride;
+        f.pp.planes = (const uint32_t *)(dp + m->post_planes_off + k * m->post_planes_stride);
+        f.pp.keep_stride = (uint32_t)m->post_keep_stride;
+        f.pp.planes_stride = (uint32_t)m->post_planes_stride;
+    }
 
     int rc = run_enc0p(f);
     if (rc) return rc;
@@ -3342,7 +3417,10 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
     DecPlan last;
     rc = plan_dec_block(f, BN_LEVELS - 1, last);
     if (rc) return rc;
-    if (!(cc && m->fuse_tail && run_tail_fused(f, last))) return launch_dec_block(f, BN_LEVELS - 1, last);
+    if (!(cc && m->fuse_tail && run_tail_fused(f, last))) {
+        if (!dry) ctx->tail_form = COVAHIP_DEV_TAIL_ALONE;
+        return launch_dec_block(f, BN_LEVELS - 1, last);
+    }
     if (cc_done) *cc_done = true;   // bboxcc ran in the same launch
     return launched(f, COVAHIP_OK);
 }

@@ -79,6 +79,7 @@ struct covahip_ctx {
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
     int cc_wave_cap = 0;       // bboxcc wave kernel: developer override of its run capacity
+    int tail_form = 0;         // which kernel ran the last decoder block of the last forward (covahip_dev_blobnet_tail_form)
     CtxLane &lane() { return lanes[cur_lane]; }
     struct { int nbands, nbuf; } enc_plan[4] = {};   // developer override of the encoder band plan per level (0 = automatic)
     covahip_blobnet *blobnet = nullptr;

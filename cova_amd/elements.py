@@ -164,6 +164,22 @@ class MetaPreprocess:
 
 
 # ------------------------------------------------------------------- nvinfer(BlobNet)
+def keep_from_rects(h_mb: int, w_mb: int, ignore=(), unit: int = 16) -> np.ndarray:
+    """A keep map u8 [h_mb][w_mb] for BlobNetInfer.set_post(): 1 everywhere except the macroblocks (unit x unit pixels) that
+    one of the pixel rectangles `ignore` = (left, top, width, height) overlaps at all.  Rectangles are clipped to the grid;
+    an empty one ignores nothing."""
+    keep = np.ones((h_mb, w_mb), dtype=np.uint8)
+    for left, top, width, height in ignore:
+        if width <= 0 or height <= 0:
+            continue
+        x0, y0 = max(0, int(left) // unit), max(0, int(top) // unit)
+        x1 = min(w_mb, (int(left) + int(width) + unit - 1) // unit)
+        y1 = min(h_mb, (int(top) + int(height) + unit - 1) // unit)
+        if x0 < x1 and y0 < y1:
+            keep[y0:y1, x0:x1] = 0
+    return keep
+
+
 class BlobNetInfer:
     """Stands where `nvinfer` (BlobNet TensorRT engine) + `maskcopy` stand in the reference
     pipeline: batched RGBA stacks in, GRAY8 {0,1} masks (and optionally logits) out."""
@@ -191,6 +207,45 @@ class BlobNetInfer:
         L.check(self._lib.covahip_blobnet_num_models(self.ctx.handle, C.byref(v)), "covahip_blobnet_num_models")
         return v.value
 
+    @staticmethod
+    def post_logit_thresh(prob_thresh=None, logit_thresh=None) -> float:
+        """The float32 logit threshold set_post() hands to the library: logit_thresh itself, or for a probability p in (0, 1)
+        log(p / (1 - p)) computed in double and rounded to float32 (0.5 -> 0.0, the default).  Giving both is a ValueError."""
+        if prob_thresh is not None and logit_thresh is not None:
+            raise ValueError("prob_thresh and logit_thresh are mutually exclusive")
+        if prob_thresh is not None:
+            p = float(prob_thresh)
+            if not 0.0 < p < 1.0:
+                raise ValueError(f"prob_thresh must lie in (0, 1), got {prob_thresh!r}")
+            return float(np.float32(np.log(np.float64(p) / (1.0 - np.float64(p)))))
+        return float(np.float32(0.0 if logit_thresh is None else logit_thresh))
+
+    def set_post(self, model: int = 0, *, prob_thresh=None, logit_thresh=None, keep=None):
+        """Per-model post-processing (covahip_blobnet_set_post): mask = (logit > threshold) & keep for the stacks of `model`.
+        The threshold is given as a probability or as a logit (neither: 0, i.e. p > 0.5); keep: u8 [h][w], non-zero = the
+        macroblock may be foreground (None: all; see keep_from_rects).  All three left out restores the defaults.  Waits
+        for everything the ctx has in flight first."""
+        thr = BlobNetInfer.post_logit_thresh(prob_thresh, logit_thresh)
+        post = L.BlobNetPost(thr, None)
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if keep.shape != (self.h, self.w):
+                raise ValueError(f"keep must be [{self.h}][{self.w}], got {keep.shape}")
+            post.keep = _ptr(keep)
+        L.check(self._lib.covahip_blobnet_set_post(self.ctx.handle, model, C.byref(post)), "covahip_blobnet_set_post", self.ctx.handle)
+
+    def reset_post(self, model: int = 0):
+        """The defaults of `model` (covahip_blobnet_set_post with NULL settings)."""
+        L.check(self._lib.covahip_blobnet_set_post(self.ctx.handle, model, None), "covahip_blobnet_set_post", self.ctx.handle)
+
+    def post(self, model: int = 0):
+        """The settings of `model`: (logit_thresh, keep u8 [h][w] of 0 / 1, or None without a keep map)."""
+        thr, has = C.c_float(), C.c_int()
+        keep = np.empty((self.h, self.w), dtype=np.uint8)
+        L.check(self._lib.covahip_blobnet_get_post(self.ctx.handle, model, C.byref(thr), _ptr(keep), C.byref(has)),
+                "covahip_blobnet_get_post", self.ctx.handle)
+        return thr.value, (keep if has.value else None)
+
     def set_enc_plan(self, level: int, nbands: int, nbuf: int = 1):
         """Developer switch (include/covahip_dev.h): band plan of encoder level 1..3; nbands = 0 -> automatic."""
         L.check(self._lib.covahip_blobnet_set_enc_plan(self.ctx.handle, level, nbands, nbuf), "covahip_blobnet_set_enc_plan")
@@ -204,6 +259,15 @@ class BlobNetInfer:
         "tail_skip_tensor": the last decoder block reads the level-0 skip tensor (rounds 1-4) instead of the partial logits the
         level-1 kernel computes from it (round 5 default; another summation order, not another value)."""
         L.check(self._lib.covahip_blobnet_set_impl(self.ctx.handle, {"mfma": 1, "dec_separate": 4, "enc1_legacy": 5, "enc_general_tiles": 6, "enc23_separate": 7, "enc23_force": 8, "tail_skip_tensor": 9, "tail_band_tiles": 10}[impl]), "set_impl")
+
+    TAIL_ALONE, TAIL_ROWS, TAIL_BANDS = 1, 2, 4
+
+    def tail_form(self) -> int:
+        """Developer read-back (include/covahip_dev.h): the kernel that ran the last decoder block of the last forward --
+        TAIL_ALONE dec_mfma<.., FINAL>, TAIL_ROWS dec3cc_rows_mfma, TAIL_BANDS + 2 * WV + PART dec3cc_mfma<WV, PART>."""
+        v = C.c_int()
+        L.check(self._lib.covahip_dev_blobnet_tail_form(self.ctx.handle, C.byref(v)), "covahip_dev_blobnet_tail_form")
+        return v.value
 
     def read_buffer(self, which: int, index: int = 0) -> np.ndarray:
         """Developer read-back (include/covahip_dev.h): a copy of one buffer of lane 0's workspace -- which = 0 P, 1 act[index],

@@ -25,6 +25,7 @@
 #include <gst/base/gstbasetransform.h>
 #include <gst/gst.h>
 #include <gst/video/video.h>
+#include <math.h>
 #include <string.h>
 
 #include "covahip.h"
@@ -75,7 +76,9 @@ struct _GstBlobNetFilter {
     gboolean flushing __attribute__((aligned(64)));   /* lock held: same as the bit in `state`, for the threads that wait on flush_cond */
     gchar *weights;
     gchar *pad_weights;   /* pad-model-weights: "IDX=PATH;IDX=PATH" (model sets: sink_IDX runs the model of PATH) */
-    guint8 *pad_model;    /* model of sink pad idx [BF_MAX_PAD_MAP] when pad-model-weights is set, else NULL */
+    gchar *pad_rects;     /* pad-ignore-rects: "IDX=l,t,w,h+l,t,w,h;IDX=..." in pixels (macroblocks a rectangle overlaps never become foreground) */
+    gchar *pad_thresh;    /* pad-mask-threshold: "IDX=P;IDX=P", the mask is where sigmoid(logit) > P */
+    guint8 *pad_model;    /* model of sink pad idx [BF_MAX_PAD_MAP] when a pad-* property is set, else NULL */
     uint8_t *pm;          /* model ids of the slot being filled (covahip_pipe_model_ids) */
     guint gpu_id, batch_size, cc_threshold, max_boxes;
     guint64 timeout_us;
@@ -109,7 +112,7 @@ struct _GstBlobNetFilter {
 typedef struct { GstElementClass parent_class; } GstBlobNetFilterClass;
 G_DEFINE_TYPE(GstBlobNetFilter, gst_blobnetfilter, GST_TYPE_ELEMENT)
 enum { BF_PROP_0, BF_PROP_WEIGHTS, BF_PROP_GPU, BF_PROP_BATCH, BF_PROP_TIMEOUT, BF_PROP_CC, BF_PROP_MAXBOXES, BF_PROP_BATCHES, BF_PROP_TIMING,
-       BF_PROP_PAD_WEIGHTS };
+       BF_PROP_PAD_WEIGHTS, BF_PROP_PAD_RECTS, BF_PROP_PAD_THRESH };
 #define BF_MAX_PAD_MAP 1024   /* sink pads pad-model-weights can name: sink_0 .. sink_1023 */
 
 #define BF_ST_BITS 21
@@ -123,50 +126,167 @@ static inline guint64 bf_state(GstBlobNetFilter *s) { return __atomic_load_n(&s-
 
 static BfPad *bf_pad_of(GstBlobNetFilter *s, GstPad *sink) { return (BfPad *)gst_pad_get_element_private(sink); }
 
-/* pad-model-weights: distinct files become the models of one set, model-weights-file model 0; s->pad_model maps each pad to its
- * model.  Loads the set (or the one model when the property is unset). */
-static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
-    if (!s->pad_weights || !*s->pad_weights)
-        return covahip_blobnet_load(s->ctx, blob0, len0, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
-    GPtrArray *paths = g_ptr_array_new_with_free_func(g_free);
-    GPtrArray *blobs = g_ptr_array_new_with_free_func(g_free);
-    GArray *sizes = g_array_new(FALSE, FALSE, sizeof(size_t));
-    gchar **items = g_strsplit(s->pad_weights, ";", -1);
-    int rc = COVAHIP_OK;
-    s->pad_model = g_new0(guint8, BF_MAX_PAD_MAP);
-    g_ptr_array_add(paths, g_strdup(s->weights));
-    gchar *copy0 = g_malloc(len0 ? len0 : 1);
-    memcpy(copy0, blob0, len0);
-    g_ptr_array_add(blobs, copy0);
-    g_array_append_val(sizes, len0);
-    for (gchar **it = items; *it && rc == COVAHIP_OK; it++) {
+/* One "IDX=VALUE;IDX=VALUE" property -> out[IDX] = VALUE (stripped, owned by out); order: every IDX once, as first named.
+ * FALSE: malformed. */
+static gboolean bf_parse_pad_map(const gchar *prop, gchar **out, GArray *order, guint8 *seen) {
+    if (!prop || !*prop) return TRUE;
+    gchar **items = g_strsplit(prop, ";", -1);
+    gboolean ok = TRUE;
+    for (gchar **it = items; *it && ok; it++) {
         gchar *item = g_strstrip(*it);
         if (!*item) continue;
         gchar *eq = strchr(item, '=');
         gchar *end = NULL;
         const guint64 idx = eq ? g_ascii_strtoull(item, &end, 10) : 0;
-        if (!eq || end != eq || end == item || idx >= BF_MAX_PAD_MAP || !eq[1]) { rc = COVAHIP_ERR_INVALID_ARG; break; }
-        const gchar *path = g_strstrip(eq + 1);
+        if (!eq || end != eq || end == item || idx >= BF_MAX_PAD_MAP || !*g_strstrip(eq + 1)) { ok = FALSE; break; }
+        g_free(out[idx]);
+        out[idx] = g_strdup(g_strstrip(eq + 1));
+        if (!seen[idx]) {
+            const guint i = (guint)idx;
+            seen[idx] = 1;
+            g_array_append_val(order, i);
+        }
+    }
+    g_strfreev(items);
+    return ok;
+}
+
+/* pad-ignore-rects value "l,t,w,h+l,t,w,h" (pixels) -> keep map u8 [h_mb][w_mb]: every macroblock a rectangle overlaps at all is 0;
+ * rectangles are clipped to the grid.  FALSE: malformed. */
+static gboolean bf_parse_rects(const gchar *value, int h_mb, int w_mb, guint8 *keep) {
+    memset(keep, 1, (size_t)h_mb * w_mb);
+    gchar **rects = g_strsplit(value, "+", -1);
+    gboolean ok = rects[0] != NULL;
+    for (gchar **r = rects; *r && ok; r++) {
+        gint64 v[4];
+        const gchar *q = g_strstrip(*r);
+        for (int i = 0; i < 4 && ok; i++) {
+            gchar *end = NULL;
+            v[i] = g_ascii_strtoll(q, &end, 10);
+            while (end != q && g_ascii_isspace(*end)) end++;
+            ok = end != q && *end == (i < 3 ? ',' : '\0') && v[i] > -(1 << 24) && v[i] < (1 << 24);
+            q = end + 1;
+        }
+        if (!ok || v[2] < 0 || v[3] < 0) { ok = FALSE; break; }
+        if (v[2] == 0 || v[3] == 0) continue;
+        const gint64 x0 = MAX(0, v[0]) / 16, y0 = MAX(0, v[1]) / 16;
+        const gint64 x1 = MIN((gint64)w_mb, (v[0] + v[2] + 15) / 16), y1 = MIN((gint64)h_mb, (v[1] + v[3] + 15) / 16);
+        for (gint64 y = y0; y < y1; y++)
+            for (gint64 x = x0; x < x1; x++) keep[y * w_mb + x] = 0;
+    }
+    g_strfreev(rects);
+    return ok;
+}
+
+/* pad-mask-threshold value: a probability in (0, 1) -> the logit threshold log(p / (1 - p)).  FALSE: malformed. */
+static gboolean bf_parse_threshold(const gchar *value, float *logit) {
+    gchar *end = NULL;
+    const gdouble p = g_ascii_strtod(value, &end);
+    if (end == value || *end || !(p > 0.0 && p < 1.0)) return FALSE;
+    *logit = (float)log(p / (1.0 - p));
+    return TRUE;
+}
+
+/* Model sets.  pad-model-weights, pad-ignore-rects and pad-mask-threshold give a sink pad its weights file, its ignore region and
+ * its mask threshold; every distinct (file, rects, threshold) triple becomes one model of the set (post-processing settings are
+ * per model, so two cameras on one file with different ignore regions are two models of the same weights: 0.64 MB each).  Model 0
+ * is model-weights-file with the default post-processing, and the model of every pad that no property names.  s->pad_model maps
+ * each pad to its model.  Models are numbered in the order the properties first name them, pad-model-weights first: a value of
+ * that property alone gives the ids it always gave.  Loads the set (or the one model when no property is set) and applies the settings. */
+static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
+    const gboolean any = (s->pad_weights && *s->pad_weights) || (s->pad_rects && *s->pad_rects) || (s->pad_thresh && *s->pad_thresh);
+    if (!any) return covahip_blobnet_load(s->ctx, blob0, len0, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+    typedef struct { gchar *path, *rects, *thr; guint file; } BfModel;
+    gchar **map[3];   /* per pad: weights file, rects, threshold */
+    for (int i = 0; i < 3; i++) map[i] = g_new0(gchar *, BF_MAX_PAD_MAP);
+    GPtrArray *paths = g_ptr_array_new_with_free_func(g_free);   /* distinct files ... */
+    GPtrArray *files = g_ptr_array_new_with_free_func(g_free);   /* ... and their bytes */
+    GArray *fsizes = g_array_new(FALSE, FALSE, sizeof(size_t));
+    GArray *models = g_array_new(FALSE, TRUE, sizeof(BfModel));
+    int rc = COVAHIP_OK;
+    GArray *order = g_array_new(FALSE, FALSE, sizeof(guint));
+    guint8 *seen = g_new0(guint8, BF_MAX_PAD_MAP);
+    if (!bf_parse_pad_map(s->pad_weights, map[0], order, seen) || !bf_parse_pad_map(s->pad_rects, map[1], order, seen) ||
+        !bf_parse_pad_map(s->pad_thresh, map[2], order, seen))
+        rc = COVAHIP_ERR_INVALID_ARG;
+    g_free(seen);
+    s->pad_model = g_new0(guint8, BF_MAX_PAD_MAP);
+    g_ptr_array_add(paths, g_strdup(s->weights));
+    gchar *copy0 = g_malloc(len0 ? len0 : 1);
+    memcpy(copy0, blob0, len0);
+    g_ptr_array_add(files, copy0);
+    size_t n0 = len0;
+    g_array_append_val(fsizes, n0);
+    BfModel m0 = {g_strdup(s->weights), g_strdup(""), g_strdup(""), 0};
+    g_array_append_val(models, m0);
+    for (guint o = 0; o < order->len && rc == COVAHIP_OK; o++) {
+        const guint idx = g_array_index(order, guint, o);
+        const gchar *path = map[0][idx] ? map[0][idx] : s->weights, *rects = map[1][idx] ? map[1][idx] : "", *thr = map[2][idx] ? map[2][idx] : "";
         guint k = 0;
-        while (k < paths->len && strcmp((const gchar *)g_ptr_array_index(paths, k), path) != 0) k++;
-        if (k == paths->len) {
-            gchar *b = NULL;
-            gsize n = 0;
-            if (k >= COVAHIP_MAX_MODELS || !g_file_get_contents(path, &b, &n, NULL)) { rc = COVAHIP_ERR_BAD_WEIGHTS; break; }
-            g_ptr_array_add(paths, g_strdup(path));
-            g_ptr_array_add(blobs, b);
-            size_t nn = n;
-            g_array_append_val(sizes, nn);
+        for (; k < models->len; k++) {
+            const BfModel *m = &g_array_index(models, BfModel, k);
+            if (!strcmp(m->path, path) && !strcmp(m->rects, rects) && !strcmp(m->thr, thr)) break;
+        }
+        if (k == models->len) {
+            if (k >= COVAHIP_MAX_MODELS) { rc = COVAHIP_ERR_BAD_WEIGHTS; break; }
+            guint f = 0;
+            while (f < paths->len && strcmp((const gchar *)g_ptr_array_index(paths, f), path) != 0) f++;
+            if (f == paths->len) {
+                gchar *b = NULL;
+                gsize n = 0;
+                if (!g_file_get_contents(path, &b, &n, NULL)) { rc = COVAHIP_ERR_BAD_WEIGHTS; break; }
+                g_ptr_array_add(paths, g_strdup(path));
+                g_ptr_array_add(files, b);
+                size_t nn = n;
+                g_array_append_val(fsizes, nn);
+            }
+            BfModel m = {g_strdup(path), g_strdup(rects), g_strdup(thr), f};
+            g_array_append_val(models, m);
         }
         s->pad_model[idx] = (guint8)k;
     }
-    g_strfreev(items);
-    if (rc == COVAHIP_OK)
-        rc = covahip_blobnet_load_set(s->ctx, (int)blobs->len, (const void *const *)blobs->pdata, (const size_t *)sizes->data, s->h_mb,
-                                      s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+    /* the settings of every model, checked before anything is loaded */
+    const size_t hw = (size_t)s->h_mb * s->w_mb;
+    guint8 *keeps = g_malloc(models->len * hw + 1);
+    float *thrs = g_new0(float, models->len);
+    for (guint k = 0; k < models->len && rc == COVAHIP_OK; k++) {
+        const BfModel *m = &g_array_index(models, BfModel, k);
+        if (*m->rects && !bf_parse_rects(m->rects, s->h_mb, s->w_mb, keeps + k * hw)) rc = COVAHIP_ERR_INVALID_ARG;
+        if (*m->thr && !bf_parse_threshold(m->thr, &thrs[k])) rc = COVAHIP_ERR_INVALID_ARG;
+    }
+    if (rc == COVAHIP_OK) {
+        const void **blobs = g_new0(const void *, models->len);
+        size_t *sizes = g_new0(size_t, models->len);
+        for (guint k = 0; k < models->len; k++) {
+            const BfModel *m = &g_array_index(models, BfModel, k);
+            blobs[k] = g_ptr_array_index(files, m->file);
+            sizes[k] = g_array_index(fsizes, size_t, m->file);
+        }
+        rc = covahip_blobnet_load_set(s->ctx, (int)models->len, blobs, sizes, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
+        g_free(blobs);
+        g_free(sizes);
+    }
+    for (guint k = 0; k < models->len && rc == COVAHIP_OK; k++) {
+        const BfModel *m = &g_array_index(models, BfModel, k);
+        if (!*m->rects && !*m->thr) continue;
+        covahip_blobnet_post post = {thrs[k], *m->rects ? keeps + k * hw : NULL};
+        rc = covahip_blobnet_set_post(s->ctx, (int)k, &post);
+    }
+    g_free(keeps);
+    g_free(thrs);
+    for (guint k = 0; k < models->len; k++) {
+        BfModel *m = &g_array_index(models, BfModel, k);
+        g_free(m->path); g_free(m->rects); g_free(m->thr);
+    }
+    g_array_free(models, TRUE);
     g_ptr_array_free(paths, TRUE);
-    g_ptr_array_free(blobs, TRUE);
-    g_array_free(sizes, TRUE);
+    g_ptr_array_free(files, TRUE);
+    g_array_free(fsizes, TRUE);
+    g_array_free(order, TRUE);
+    for (int i = 0; i < 3; i++) {
+        for (guint idx = 0; idx < BF_MAX_PAD_MAP; idx++) g_free(map[i][idx]);
+        g_free(map[i]);
+    }
     return rc;
 }
 
@@ -758,6 +878,8 @@ static void bf_set_property(GObject *o, guint id, const GValue *v, GParamSpec *p
     switch (id) {
     case BF_PROP_WEIGHTS: g_free(s->weights); s->weights = g_value_dup_string(v); break;
     case BF_PROP_PAD_WEIGHTS: if (!s->pipe) { g_free(s->pad_weights); s->pad_weights = g_value_dup_string(v); } break;
+    case BF_PROP_PAD_RECTS: if (!s->pipe) { g_free(s->pad_rects); s->pad_rects = g_value_dup_string(v); } break;
+    case BF_PROP_PAD_THRESH: if (!s->pipe) { g_free(s->pad_thresh); s->pad_thresh = g_value_dup_string(v); } break;
     case BF_PROP_GPU: s->gpu_id = g_value_get_uint(v); break;
     case BF_PROP_BATCH: if (!s->pipe) s->batch_size = g_value_get_uint(v); break;
     case BF_PROP_TIMEOUT: s->timeout_us = g_value_get_uint64(v); break;
@@ -772,6 +894,8 @@ static void bf_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps) {
     switch (id) {
     case BF_PROP_WEIGHTS: g_value_set_string(v, s->weights); break;
     case BF_PROP_PAD_WEIGHTS: g_value_set_string(v, s->pad_weights); break;
+    case BF_PROP_PAD_RECTS: g_value_set_string(v, s->pad_rects); break;
+    case BF_PROP_PAD_THRESH: g_value_set_string(v, s->pad_thresh); break;
     case BF_PROP_GPU: g_value_set_uint(v, s->gpu_id); break;
     case BF_PROP_BATCH: g_value_set_uint(v, s->batch_size); break;
     case BF_PROP_TIMEOUT: g_value_set_uint64(v, s->timeout_us); break;
@@ -806,6 +930,8 @@ static void bf_finalize(GObject *o) {
     g_free(s->meta);
     g_free(s->weights);
     g_free(s->pad_weights);
+    g_free(s->pad_rects);
+    g_free(s->pad_thresh);
     g_free(s->pad_model);
     g_mutex_clear(&s->lock);
     g_cond_clear(&s->cond);
@@ -842,6 +968,12 @@ static void gst_blobnetfilter_class_init(GstBlobNetFilterClass *k) {
     g_object_class_install_property(g, BF_PROP_PAD_WEIGHTS, g_param_spec_string("pad-model-weights", "Per-pad weights",
         "Model sets: \"IDX=PATH;IDX=PATH\" runs sink_IDX on the weights in PATH (distinct files are loaded once, as one set, at start); "
         "pads it does not name use model-weights-file", NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
+    g_object_class_install_property(g, BF_PROP_PAD_RECTS, g_param_spec_string("pad-ignore-rects", "Per-pad ignore region",
+        "\"IDX=l,t,w,h+l,t,w,h;IDX=...\": pixel rectangles of sink_IDX whose macroblocks never become foreground (a burned-in clock, a "
+        "neighbouring road); applied where the mask is made, at no extra launch", NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
+    g_object_class_install_property(g, BF_PROP_PAD_THRESH, g_param_spec_string("pad-mask-threshold", "Per-pad mask threshold",
+        "\"IDX=P;IDX=P\": the mask of sink_IDX is where sigmoid(logit) > P, 0 < P < 1 (the reference's segmentation-threshold; default 0.5)",
+        NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_GPU, g_param_spec_uint("gpu-id", "GPU id", "HIP device to run on", 0, 15, 0,
         G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_BATCH, g_param_spec_uint("batch-size", "Batch size",

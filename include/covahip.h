@@ -163,6 +163,30 @@ int covahip_blobnet_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int bat
 /* covahip_blobnet_forward with a model per stack (model_ids: see covahip_blobnet_load_set). */
 int covahip_blobnet_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const uint8_t *model_ids, int batch,
                               float *logits, uint8_t *mask, int mem_kind);
+/* Per-model post-processing: what turns a stack's logits into its mask.  For a stack b that runs on model m
+ *     mask[b, y, x] = (logit[b, y, x] > logit_thresh[m]) && keep[m][y, x]
+ * and the boxes are regionprops of THAT mask.  The logits output is not affected.  The reference carries the threshold
+ * per engine (segmentation-threshold in the files of config/blobnet); keep is the ignore region of a camera (a burned-in
+ * clock, a neighbouring road).  Both are applied inside the kernel that makes the mask: no launch is added, and while
+ * every model of the set has the defaults (threshold 0, keep everything) the forward runs the very kernels it ran
+ * before this call existed.
+ * The settings live in the ctx, per model of the loaded set (model 0 after covahip_blobnet_load), and apply to every
+ * entry that produces a mask or boxes from a model: covahip_blobnet_forward[_m], covahip_filter_forward[_m], the
+ * _frames / _frames_m / _frames_packed[_m] entries and covahip_pipe_submit.  covahip_bboxcc has no model and is not
+ * affected.  covahip_blobnet_load and covahip_blobnet_load_set reset every model to the defaults.
+ * covahip_blobnet_set_post waits for everything the ctx has in flight on all lanes, then updates the device tables:
+ * batches submitted before the call have the old settings, batches submitted after it the new ones.  Call it under the
+ * lock that guards acquire and submit.  post == NULL restores the defaults of that model.
+ *   COVAHIP_ERR_INVALID_ARG: NULL ctx, model outside the set, NaN or infinite threshold (nothing changes);
+ *   COVAHIP_ERR_NOT_LOADED: no model loaded.                                                                        */
+typedef struct covahip_blobnet_post {
+    float logit_thresh;     /* mask where logit > logit_thresh; 0 = the reference's p > 0.5; must be finite */
+    const uint8_t *keep;    /* HOST u8 [h_mb][w_mb], non-zero = this macroblock may be foreground; NULL = all */
+} covahip_blobnet_post;
+int covahip_blobnet_set_post(covahip_ctx *ctx, int model, const covahip_blobnet_post *post /* NULL = defaults */);
+/* The settings of a model.  logit_thresh, keep_or_null (u8 [h_mb][w_mb], written as 0 / 1; all 1 without a keep map)
+ * and has_keep (1 when a keep map is set) may each be NULL.                                                         */
+int covahip_blobnet_get_post(covahip_ctx *ctx, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_keep);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc

@@ -57,6 +57,14 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
                             int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes, uint8_t *d_mask, int iters,
                             float *ms_direct, float *ms_graph);
 
+/* Which kernel ran the last decoder block of the ctx's last BlobNet forward (the launch names of the profile do not tell the
+ * fused forms apart): ALONE = dec_mfma<.., FINAL> (no bboxcc in the launch), ROWS = dec3cc_rows_mfma, BANDS + 2 * WV + PART =
+ * dec3cc_mfma<WV, PART> (WV: the run-based bboxcc body, PART: partial logits instead of the skip tensor).  0: no forward yet. */
+#define COVAHIP_DEV_TAIL_ALONE 1
+#define COVAHIP_DEV_TAIL_ROWS 2
+#define COVAHIP_DEV_TAIL_BANDS 4
+int covahip_dev_blobnet_tail_form(covahip_ctx *ctx, int *form);
+
 /* What covahip_pipe_create's hardware-queue probe decided (pipe.hip, round 6): how many of the ctx's ACTIVE lanes share a hardware
  * queue with the pipe's upload stream / with its result stream.  0 / <= 1 with up to three lanes on the default four queues. */
 struct covahip_pipe;
