@@ -240,6 +240,7 @@ DEV_PROTOTYPES = {
     "covahip_dev_blobnet_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),
     "covahip_dev_mog_state": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "covahip_dev_mog_set_stage_budget": (C.c_int, [_P, _SZ]),
 }
 
 _lib = None

@@ -45,7 +45,7 @@ static_assert(NPIX % UPD_BLOCK == 0 && MW % 64 == 0 && NLAB == NWORD, "geometry"
 constexpr size_t OFF_W = 0, OFF_V = (size_t)NMIX * NPIX * 4, OFF_M = (size_t)2 * NMIX * NPIX * 4;
 constexpr size_t OFF_N = (size_t)5 * NMIX * NPIX * 4;
 constexpr size_t STATE_BYTES = OFF_N + NPIX;
-// device budget for host frames staged per update launch
+// device budget for host frames staged per update launch (covahip_dev_mog_set_stage_budget changes it per labeller)
 constexpr size_t STAGE_BUDGET = (size_t)1 << 30;
 
 constexpr float TB = 0.9f, TG = 9.0f, VAR_INIT = 15.0f, VAR_MIN = 4.0f, VAR_MAX = 75.0f, FCT = 0.05f;
@@ -398,6 +398,7 @@ struct covahip_mog {
     void *h_par = nullptr;         // pinned: (alphaT, prune) [F][S], then n_valid [S]
     size_t h_par_bytes = 0;
     int last_frames = 0;
+    size_t stage_budget = STAGE_BUDGET;   // bytes of host frames staged per update launch
 };
 
 namespace {
@@ -515,7 +516,7 @@ int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const
     } else {
         // host frames: staged in launches of as many frames as fit the budget (the model is read and written once per launch)
         const size_t step = (size_t)S * m->src_bytes;
-        const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, STAGE_BUDGET / step));
+        const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, m->stage_budget / step));
         if (int rc = covahip_ensure_buffer(ctx, &m->d_frames, &m->frames_bytes, (size_t)per * step)) return rc;
         for (int f0 = 0; f0 < n_frames; f0 += per) {
             const int nf = std::min(per, n_frames - f0);
@@ -577,6 +578,12 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
         for (size_t i = 0; i < FS * NWORD; i++)
             for (int b = 0; b < 64; b++) out[i * 64 + b] = (w[i] >> b) & 1ull ? one : 0;
     }
+    return COVAHIP_OK;
+}
+
+int covahip_dev_mog_set_stage_budget(covahip_mog *m, size_t bytes) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    m->stage_budget = bytes ? bytes : STAGE_BUDGET;
     return COVAHIP_OK;
 }
 

@@ -91,6 +91,10 @@ class MogLabeler:
         """Stream slot s starts a new video: model zeroed, frame count 0."""
         L.check(self._lib.covahip_mog_reset(self.handle, s), "covahip_mog_reset", self.ctx.handle)
 
+    def set_stage_budget(self, nbytes: int):
+        """Developer switch: device bytes of host frames staged per update launch of `apply` (0 = the default, 1 GiB)."""
+        L.check(self._lib.covahip_dev_mog_set_stage_budget(self.handle, nbytes), "covahip_dev_mog_set_stage_budget")
+
     def state(self, s: int) -> dict:
         """Stream s's model: W f32 [5][360][640], V f32 [5][360][640], M f32 [5][3][360][640], nmodes u8 [360][640], n."""
         W = np.empty((NMIX, WORK_H, WORK_W), np.float32)

@@ -79,6 +79,10 @@ int covahip_dev_mog_masks(struct covahip_mog *m, uint8_t *raw, uint8_t *filled, 
 /* One stream's model: W f32 [5][230400], V f32 [5][230400], M f32 [5][3][230400], nmodes u8 [230400] and n (frames seen);
  * any pointer may be NULL. */
 int covahip_dev_mog_state(struct covahip_mog *m, int stream, float *W, float *V, float *M, uint8_t *nmodes, int64_t *n);
+/* Device bytes of host frames that covahip_mog_apply (COVAHIP_MEM_HOST) stages per update launch; 0 restores the default of
+ * 1 GiB.  A call whose frames exceed it runs as several update launches of whole frame-steps (one frame of every stream), at
+ * least one per launch; the results do not depend on it.  (tests/test_gpu_mog_branches.py) */
+int covahip_dev_mog_set_stage_budget(struct covahip_mog *m, size_t bytes);
 
 #ifdef __cplusplus
 }

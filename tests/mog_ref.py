@@ -10,6 +10,8 @@ rounded on its own (numpy never fuses), so this is the arithmetic the HIP kernel
 """
 from __future__ import annotations
 
+import collections
+
 import numpy as np
 
 WORK_W, WORK_H = 640, 360
@@ -47,9 +49,13 @@ def learning_rates(n: int, history: int):
 
 
 class Mog2:
-    """The per-pixel mixture model over P pixels.  W, V: [5][P]; M: [5][3][P]; nmodes: [P]; n: frames seen."""
+    """The per-pixel mixture model over P pixels.  W, V: [5][P]; M: [5][3][P]; nmodes: [P]; n: frames seen.
 
-    def __init__(self, npix: int = WORK_W * WORK_H, history: int = 9000, var_threshold: float = 32.0):
+    With trace=True, `self.trace` is a collections.Counter of per-pixel events, summed over the apply calls: which branch of
+    the update each pixel took (tests/test_mog_branches_host.py lists them).  Tracing only reads: the arithmetic and the
+    results are the same with it on or off."""
+
+    def __init__(self, npix: int = WORK_W * WORK_H, history: int = 9000, var_threshold: float = 32.0, trace: bool = False):
         self.P = npix
         self.history = history
         self.Tb = F32(var_threshold)
@@ -58,6 +64,12 @@ class Mog2:
         self.M = np.zeros((NMIX, 3, npix), F32)
         self.nmodes = np.zeros(npix, np.int32)
         self.n = 0
+        self.trace = collections.Counter() if trace else None
+
+    def _count(self, name, sel):
+        c = int(np.count_nonzero(sel))
+        if c:
+            self.trace[name] += c
 
     def _swap(self, sel, i, j):
         if not sel.any():
@@ -81,6 +93,7 @@ class Mog2:
         P = self.P
         fits = np.zeros(P, bool)
         bg = np.zeros(P, bool)
+        tr = self.trace is not None
         tw = np.zeros(P, F32)
         with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
             for mode in range(NMIX):
@@ -94,11 +107,23 @@ class Mog2:
                 var = V[mode]
                 bg |= chk & (tw < TB) & (dist2 < self.Tb * var)
                 fit = chk & (dist2 < TG * var)
+                if tr:
+                    close = chk & (dist2 < self.Tb * var)
+                    self._count(f"fit_mode{mode}", fit)
+                    self._count(f"bg_at_mode{mode}", close & (tw < TB))
+                    self._count("bg_blocked_by_TB", close & ~(tw < TB))
+                    self._count("bgclose_not_fit", close & ~fit)
+                    self._count("fit_not_bgclose", fit & ~close)
+                    self._count("bg_edge", chk & (dist2 == self.Tb * var))
+                    self._count("fit_edge", chk & (dist2 == TG * var))
                 fits |= fit
                 w = np.where(fit, w + alphaT, w)
                 k = alphaT / w
                 M[mode] = np.where(fit, M[mode] - k * d, M[mode])
                 vn = var + k * (dist2 - var)
+                if tr:
+                    self._count("vmin", fit & (vn < VAR_MIN))
+                    self._count("vmax", fit & (VAR_MAX < vn))
                 vn = np.where(vn < VAR_MIN, VAR_MIN, vn)
                 vn = np.where(VAR_MAX < vn, VAR_MAX, vn)
                 V[mode] = np.where(fit, vn, var)
@@ -106,9 +131,16 @@ class Mog2:
                 go = fit.copy()
                 for i in range(mode, 0, -1):
                     go &= ~(w < W[i - 1])
+                    if tr:
+                        self._count("fit_sort_tie", go & (w == W[i - 1]))
                     self._swap(go, i, i - 1)
                     swaps += go
                 prn = act & (w < -prune)
+                if tr:
+                    for k_ in range(1, mode + 1):
+                        self._count(f"fit_swaps{k_}", fit & (swaps == k_))
+                    self._count(f"prune_mode{mode}", prn)
+                    self._count("prune_not_last", prn & (mode < nm - 1))
                 w = np.where(prn, F32(0), w)
                 nm -= prn.astype(np.int32)
                 for j in range(mode + 1):
@@ -116,9 +148,15 @@ class Mog2:
                     W[j] = np.where(sel, w, W[j])
                 tw = np.where(act, tw + w, tw)
             inv = np.where(np.abs(tw) > FLT_EPSILON, F32(1) / tw, F32(0)).astype(F32)
+            if tr:
+                self._count("tw_zero", ~(np.abs(tw) > FLT_EPSILON))
             for i in range(NMIX):
                 W[i] = np.where(i < nm, W[i] * inv, W[i])
         nf = ~fits
+        if tr:
+            for k_ in range(NMIX + 1):
+                self._count(f"new_at_nm{k_}", nf & (nm == k_))
+            nswaps = np.zeros(P, np.int32)
         m = np.where(nm == NMIX, NMIX - 1, nm)
         nm += (nf & (nm < NMIX)).astype(np.int32)
         for j in range(NMIX):
@@ -133,8 +171,14 @@ class Mog2:
         for i in range(NMIX - 1, 0, -1):
             a = go & (i < nm)
             stop = a & (alphaT < W[i - 1])
+            if tr:
+                self._count("new_sort_tie", a & (alphaT == W[i - 1]))
+                nswaps += a & ~stop
             self._swap(a & ~stop, i, i - 1)
             go &= ~stop
+        if tr:
+            for k_ in range(1, NMIX):
+                self._count(f"new_swaps{k_}", nswaps == k_)
         return np.where(bg, 0, 255).astype(np.uint8).reshape(frame.shape[:-1])
 
 
