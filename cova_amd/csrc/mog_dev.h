@@ -1,0 +1,351 @@
+// Device code shared by the MoG label kernels of mog.hip (the reference grid: 640x360 working frames) and mog_grid.hip (the
+// macroblock grid: half-resolution working frames): the MOG2 pixel update, the update kernel's body, and the morphology and
+// hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
+// include/covahip.h ("MoG labels").
+//
+// No contraction in this code: every product and sum is rounded on its own, as the x86 builds of OpenCV compute it (both
+// translation units are also built with -ffp-contract=off).  The f32 divisions go through double: the f64 quotient is
+// correctly rounded and 53 >= 2 * 24 + 2 bits, so rounding it to f32 gives the correctly rounded f32 quotient (double rounding
+// is innocuous for division at that width); unlike the f32 divide expansion this needs no f32 fused multiply-add, so the
+// update kernels' ISA has none at all (DESIGN.md checks it).
+#pragma once
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+
+#include <cfloat>
+#include <cstddef>
+#include <cstdint>
+
+#include "covahip.h"
+
+namespace mogdev {
+
+constexpr int NMIX = 5;
+constexpr int UPD_BLOCK = 256;
+constexpr float TB = 0.9f, TG = 9.0f, VAR_INIT = 15.0f, VAR_MIN = 4.0f, VAR_MAX = 75.0f, FCT = 0.05f;
+
+// A working geometry: W x H pixels, a row is W / 64 ballot words of the bit plane, one label per 8x8 block (the block's
+// top-left pixel; the last label row of a height that is no multiple of 8 reads the last started block).
+template <int W, int H>
+struct Geom {
+    static constexpr int MW = W, MH = H;
+    static constexpr int NPIX = MW * MH;
+    static constexpr int ROWW = MW / 64;               // 64-bit words per row
+    static constexpr int NWORD = NPIX / 64;            // words per frame
+    static constexpr int LW = (MW + 7) / 8, LH = (MH + 7) / 8, NLAB = LW * LH;
+    // state of one stream, structure of arrays: W[5][P], V[5][P], M[5][3][P] (f32), nmodes[P] (u8)
+    static constexpr size_t OFF_W = 0, OFF_V = (size_t)NMIX * NPIX * 4, OFF_M = (size_t)2 * NMIX * NPIX * 4;
+    static constexpr size_t OFF_N = (size_t)5 * NMIX * NPIX * 4;
+    static constexpr size_t STATE_BYTES = OFF_N + NPIX;
+    static_assert(NPIX % UPD_BLOCK == 0 && MW % 64 == 0 && 8 * (LH - 1) < MH && (LW - 1) / 8 < ROWW, "geometry");
+};
+
+// correctly rounded a / b through an f64 quotient (see the head of the file).  The empty asm keeps the optimiser from folding
+// the widened division back into the f32 one, whose expansion uses f32 fused multiply-adds.
+__device__ __forceinline__ float div_rn(float a, float b) {
+    double da = a, db = b;
+    asm("" : "+v"(da), "+v"(db));
+    return (float)(da / db);
+}
+
+struct Px { float c0, c1, c2; };
+
+// entries i and i - 1 trade places where `sel` (i is a constant after unrolling: the arrays stay in registers)
+__device__ __forceinline__ void swap_sel(float (&W)[NMIX], float (&V)[NMIX], float (&M)[NMIX][3], int i, bool sel) {
+    float a = W[i], b = W[i - 1];
+    W[i] = sel ? b : a;
+    W[i - 1] = sel ? a : b;
+    a = V[i], b = V[i - 1];
+    V[i] = sel ? b : a;
+    V[i - 1] = sel ? a : b;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        a = M[i][c], b = M[i - 1][c];
+        M[i][c] = sel ? b : a;
+        M[i - 1][c] = sel ? a : b;
+    }
+}
+
+// one MOG2 update of one pixel (include/covahip.h, "MoG labels"); returns true when the pixel is foreground
+__device__ __forceinline__ bool mog2_pixel(float (&W)[NMIX], float (&V)[NMIX], float (&M)[NMIX][3], int &nm, const Px &px,
+                                           float alphaT, float prune, float Tb) {
+    const float alpha1 = 1.f - alphaT;
+    bool fits = false, bg = false;
+    float tw = 0.f;
+#pragma unroll
+    for (int mode = 0; mode < NMIX; mode++) {
+        if (mode < nm) {                       // nm shrinks when a mode is pruned
+            float w = alpha1 * W[mode] + prune;
+            int swaps = 0;
+            if (!fits) {
+                const float d0 = M[mode][0] - px.c0, d1 = M[mode][1] - px.c1, d2 = M[mode][2] - px.c2;
+                const float dist2 = (d0 * d0 + d1 * d1) + d2 * d2;
+                const float var = V[mode];
+                if (tw < TB && dist2 < Tb * var) bg = true;
+                if (dist2 < TG * var) {
+                    fits = true;
+                    w = w + alphaT;
+                    const float k = div_rn(alphaT, w);
+                    M[mode][0] = M[mode][0] - k * d0;
+                    M[mode][1] = M[mode][1] - k * d1;
+                    M[mode][2] = M[mode][2] - k * d2;
+                    float vn = var + k * (dist2 - var);
+                    vn = vn < VAR_MIN ? VAR_MIN : vn;
+                    vn = VAR_MAX < vn ? VAR_MAX : vn;
+                    V[mode] = vn;
+                    bool go = true;
+#pragma unroll
+                    for (int i = mode; i > 0; i--) {
+                        go = go && !(w < W[i - 1]);
+                        swap_sel(W, V, M, i, go);
+                        swaps += go ? 1 : 0;
+                    }
+                }
+            }
+            if (w < -prune) {
+                w = 0.f;
+                nm--;
+            }
+#pragma unroll
+            for (int j = 0; j <= mode; j++)
+                if (mode - swaps == j) W[j] = w;
+            tw = tw + w;
+        }
+    }
+    const float inv = fabsf(tw) > FLT_EPSILON ? div_rn(1.f, tw) : 0.f;
+#pragma unroll
+    for (int i = 0; i < NMIX; i++)
+        if (i < nm) W[i] = W[i] * inv;
+    if (!fits) {
+        const int m = nm == NMIX ? NMIX - 1 : nm++;
+#pragma unroll
+        for (int j = 0; j < NMIX; j++)
+            if (j == m) {
+                W[j] = nm == 1 ? 1.f : alphaT;
+                M[j][0] = px.c0;
+                M[j][1] = px.c1;
+                M[j][2] = px.c2;
+                V[j] = VAR_INIT;
+            }
+        if (nm != 1) {
+#pragma unroll
+            for (int i = 0; i < NMIX - 1; i++)
+                if (i < nm - 1) W[i] = W[i] * alpha1;
+        }
+        bool go = true;
+#pragma unroll
+        for (int i = NMIX - 1; i > 0; i--) {
+            if (i < nm) {
+                const bool stop = alphaT < W[i - 1];
+                swap_sel(W, V, M, i, go && !stop);
+                go = go && !stop;
+            }
+        }
+    }
+    return !bg;
+}
+
+// The update kernel's body: one lane per working pixel and stream, grid (G::NPIX / UPD_BLOCK, S).  `load(frame, x, y)` gives
+// working pixel (x, y) of one source frame.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of
+// the call; bits: raw masks [F][S][G::NWORD].  A wave's 64 pixels lie in one row, so its ballot is one word of the plane.
+template <class G, class Load>
+__device__ __forceinline__ void update_body(Load load, const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
+                                            const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf, int S,
+                                            float Tb, unsigned long long *__restrict__ bits) {
+    constexpr int NPIX = G::NPIX;
+    const int s = blockIdx.y;
+    int fend = nvalid[s] - f0;
+    fend = fend < nf ? fend : nf;
+    if (fend <= 0) return;                     // the same for the whole block
+    const int p = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    const int x = p % G::MW, y = p / G::MW;
+    uint8_t *st = state + (size_t)s * G::STATE_BYTES;
+    const float *gW = reinterpret_cast<const float *>(st + G::OFF_W);
+    const float *gV = reinterpret_cast<const float *>(st + G::OFF_V);
+    const float *gM = reinterpret_cast<const float *>(st + G::OFF_M);
+    float W[NMIX], V[NMIX], M[NMIX][3];
+#pragma unroll
+    for (int k = 0; k < NMIX; k++) {
+        W[k] = gW[(size_t)k * NPIX + p];
+        V[k] = gV[(size_t)k * NPIX + p];
+#pragma unroll
+        for (int c = 0; c < 3; c++) M[k][c] = gM[(size_t)(k * 3 + c) * NPIX + p];
+    }
+    int nm = st[G::OFF_N + p];
+    const size_t fstride = (size_t)S * src_bytes;
+    const uint8_t *fr = frames + (size_t)s * src_bytes;
+    Px cur = load(fr, x, y);
+    for (int f = 0; f < fend; f++) {
+        Px nxt = cur;
+        if (f + 1 < fend) nxt = load(fr + (size_t)(f + 1) * fstride, x, y);   // next frame's pixel in flight
+        const float2 pr = par[(size_t)(f0 + f) * S + s];
+        const bool fg = mog2_pixel(W, V, M, nm, cur, pr.x, pr.y, Tb);
+        const unsigned long long word = __ballot(fg);
+        if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+        cur = nxt;
+    }
+    float *oW = reinterpret_cast<float *>(st + G::OFF_W);
+    float *oV = reinterpret_cast<float *>(st + G::OFF_V);
+    float *oM = reinterpret_cast<float *>(st + G::OFF_M);
+#pragma unroll
+    for (int k = 0; k < NMIX; k++) {
+        oW[(size_t)k * NPIX + p] = W[k];
+        oV[(size_t)k * NPIX + p] = V[k];
+#pragma unroll
+        for (int c = 0; c < 3; c++) oM[(size_t)(k * 3 + c) * NPIX + p] = M[k][c];
+    }
+    st[G::OFF_N + p] = (uint8_t)nm;
+}
+
+// ------------------------------------------------------------------------------------------------ post passes
+// Bit x of word w of a row is pixel 64 w + x.  A k x k window at x covers x - k/2 .. x + k - 1 - k/2 (OpenCV's anchor, the same
+// offsets for dilate and erode); outside the image is 0 for dilate and 1 for erode.  BLOCK = threads of the workgroup.
+template <class G, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void hpass(const unsigned long long *in, unsigned long long *out) {
+    constexpr int A = K / 2, B = K - 1 - K / 2;
+    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
+    for (int i = threadIdx.x; i < G::NWORD; i += BLOCK) {
+        const int w = i % G::ROWW;
+        const unsigned long long c = in[i];
+        const unsigned long long pv = w > 0 ? in[i - 1] : NEU;
+        const unsigned long long nx = w < G::ROWW - 1 ? in[i + 1] : NEU;
+        unsigned long long r = c;
+#pragma unroll
+        for (int d = -A; d <= B; d++) {
+            if (d == 0) continue;
+            const unsigned long long v = d > 0 ? (c >> d) | (nx << (64 - d)) : (c << -d) | (pv >> (64 + d));
+            r = DIL ? (r | v) : (r & v);
+        }
+        out[i] = r;
+    }
+}
+
+template <class G, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void vpass(const unsigned long long *in, unsigned long long *out) {
+    constexpr int A = K / 2, B = K - 1 - K / 2;
+    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
+    for (int i = threadIdx.x; i < G::NWORD; i += BLOCK) {
+        const int y = i / G::ROWW;
+        unsigned long long r = in[i];
+#pragma unroll
+        for (int d = -A; d <= B; d++) {
+            if (d == 0) continue;
+            const unsigned long long v = (y + d >= 0 && y + d < G::MH) ? in[i + d * G::ROWW] : NEU;
+            r = DIL ? (r | v) : (r & v);
+        }
+        out[i] = r;
+    }
+}
+
+// A (LDS, G::NWORD words, the raw mask; all threads have passed a barrier after writing it) becomes the mask after close 4x4
+// and open 6x6; T (LDS, the same size) becomes the background reached from the frame edge through 4-connected background,
+// so ~T is the filled mask.  Ends behind a barrier.  `changed` is one LDS int.
+template <class G, int BLOCK>
+__device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long long *T, int *changed) {
+    constexpr int ROWW = G::ROWW, NWORD = G::NWORD, MH = G::MH;
+    const int tid = threadIdx.x;
+    // close 4x4, open 6x6 (separable)
+    hpass<G, BLOCK, true, 4>(A, T);
+    __syncthreads();
+    vpass<G, BLOCK, true, 4>(T, A);
+    __syncthreads();
+    hpass<G, BLOCK, false, 4>(A, T);
+    __syncthreads();
+    vpass<G, BLOCK, false, 4>(T, A);
+    __syncthreads();
+    hpass<G, BLOCK, false, 6>(A, T);
+    __syncthreads();
+    vpass<G, BLOCK, false, 6>(T, A);
+    __syncthreads();
+    hpass<G, BLOCK, true, 6>(A, T);
+    __syncthreads();
+    vpass<G, BLOCK, true, 6>(T, A);
+    __syncthreads();
+    // hole fill: T = background reached from the frame edge through 4-connected background (~A)
+    for (int i = tid; i < NWORD; i += BLOCK) {
+        const int y = i / ROWW, w = i % ROWW;
+        unsigned long long edge = (y == 0 || y == MH - 1) ? ~0ull : 0ull;
+        if (w == 0) edge |= 1ull;
+        if (w == ROWW - 1) edge |= 1ull << 63;
+        T[i] = ~A[i] & edge;
+    }
+    for (;;) {
+        if (tid == 0) *changed = 0;
+        __syncthreads();
+        // vertical: one lane per word column sweeps down, then up
+        if (tid < ROWW) {
+            bool ch = false;
+            unsigned long long r = 0;
+            for (int y = 0; y < MH; y++) {
+                const int i = y * ROWW + tid;
+                const unsigned long long old = T[i], nw = old | (~A[i] & r);
+                if (nw != old) {
+                    T[i] = nw;
+                    ch = true;
+                }
+                r = nw;
+            }
+            r = 0;
+            for (int y = MH - 1; y >= 0; y--) {
+                const int i = y * ROWW + tid;
+                const unsigned long long old = T[i], nw = old | (~A[i] & r);
+                if (nw != old) {
+                    T[i] = nw;
+                    ch = true;
+                }
+                r = nw;
+            }
+            if (ch) *changed = 1;
+        }
+        __syncthreads();
+        // horizontal: one lane per row fills every background run that holds a reached pixel, carrying across words
+        for (int y = tid; y < MH; y += BLOCK) {
+            unsigned long long m[ROWW], sd[ROWW], up[ROWW];
+#pragma unroll
+            for (int w = 0; w < ROWW; w++) {
+                m[w] = ~A[y * ROWW + w];
+                sd[w] = T[y * ROWW + w];
+            }
+            unsigned long long c = 0;
+#pragma unroll
+            for (int w = 0; w < ROWW; w++) {           // towards higher x: m + seeds ripples through each seeded run
+                const unsigned long long s1 = sd[w] | (c & m[w] & 1ull);
+                const unsigned long long t = m[w] + s1;
+                up[w] = ((t ^ m[w]) | s1) & m[w];
+                c = t < m[w] ? 1ull : 0ull;           // carried out of bit 63: the run goes on in the next word
+            }
+            c = 0;
+            bool ch = false;
+#pragma unroll
+            for (int w = ROWW - 1; w >= 0; w--) {      // towards lower x: the same on bit-reversed words
+                const unsigned long long rm = __builtin_bitreverse64(m[w]);
+                const unsigned long long s1 = __builtin_bitreverse64(sd[w]) | (c & rm & 1ull);
+                const unsigned long long t = rm + s1;
+                const unsigned long long dn = __builtin_bitreverse64(((t ^ rm) | s1) & rm);
+                c = t < rm ? 1ull : 0ull;
+                const unsigned long long nw = sd[w] | up[w] | dn;
+                if (nw != sd[w]) {
+                    T[y * ROWW + w] = nw;
+                    ch = true;
+                }
+            }
+            if (ch) *changed = 1;
+        }
+        __syncthreads();
+        const int again = *changed;
+        __syncthreads();
+        if (!again) break;
+    }
+}
+
+}  // namespace mogdev
+
+// ------------------------------------------------------------------------------------------------ host side (mog_grid.hip)
+// The macroblock grid's kernels at working width `mw` (960 or 320; 640 runs mog.hip's own).  Pointers are device memory, the
+// layouts those of the kernels above; the launches go to ctx->stream and return without waiting.
+struct covahip_ctx;
+int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
+                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
+int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
+                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS);

@@ -1,0 +1,141 @@
+// MoG labels on the source's macroblock grid (COVAHIP_MOG_GRID_MACROBLOCK): the working image is half the source in both axes
+// ((a + b + c + d + 2) >> 2 per channel over the 2x2 block, the rule of the reference grid's 1280x720 case) and there is one
+// label per 16x16 macroblock of the source, i.e. per 8x8 block of the working image.  MOG2, morphology, hole fill and the
+// subsample are the device code of mog_dev.h, the same as in mog.hip, instantiated here for
+//   1920x1080 -> 960x540 working, 68x120 labels     and     640x360 -> 320x180 working, 23x40 labels.
+// (1280x720 -> 640x360 is the reference grid itself and runs mog.hip's kernels.)
+//
+//   k_mog_grid_update  as k_mog_update: one lane per working pixel and stream, the five modes in registers across the call.  A
+//                      row is 15 (5) waves wide, so a wave's ballot is still one word of the plane.
+//   k_mog_grid_post    one workgroup per (stream, frame) with both bit planes in dynamic LDS: 2 x 64,800 B at 960x540, above
+//                      the static limit and within a CU's 160 KiB, so one workgroup owns a CU there.  The label loop runs
+//                      over the labels, which are more than the words of a plane here (8,160 > 8,100; 920 > 900), and the
+//                      last label row reads working row 536 (176): the height is no multiple of 8.
+//
+// No contraction in this file (see mog_dev.h); it is built with the flags of mog.hip.
+#pragma clang fp contract(off)
+
+#include <hip/hip_runtime.h>
+
+#include <mutex>
+#include <utility>
+#include <vector>
+
+#include "covahip.h"
+#include "internal.h"
+#include "mog_dev.h"
+
+namespace {
+
+using namespace mogdev;
+
+// working pixel (x, y) of a frame of 2 MW x 2 MH: the rounded mean of its 2x2 block
+template <int MW>
+struct LoadHalf {
+    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
+        const uint8_t *a = fr + ((size_t)(2 * y) * (2 * MW) + 2 * x) * 3;
+        const uint8_t *b = a + 2 * MW * 3;
+        unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
+        unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
+        unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
+        return {(float)s0, (float)s1, (float)s2};
+    }
+};
+
+// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
+template <int MW, int MH>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__restrict__ frames, size_t src_bytes,
+                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                                               unsigned long long *__restrict__ bits) {
+    update_body<Geom<MW, MH>>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
+}
+
+template <class G>
+constexpr size_t post_lds() {
+    return (size_t)2 * G::NWORD * 8 + 16;      // the two planes and the `changed` word
+}
+
+// bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout; labels [F][S][LH][LW]
+template <int MW, int MH, int BLOCK>
+__global__ __launch_bounds__(BLOCK) void k_mog_grid_post(const unsigned long long *__restrict__ bits,
+                                                         unsigned long long *__restrict__ filled_bits, uint8_t *__restrict__ labels,
+                                                         const int32_t *__restrict__ nvalid, int S) {
+    using G = Geom<MW, MH>;
+    constexpr int NWORD = G::NWORD, NLAB = G::NLAB, LW = G::LW, ROWW = G::ROWW;
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    unsigned long long *A = reinterpret_cast<unsigned long long *>(smem), *T = A + NWORD;
+    int *changed = reinterpret_cast<int *>(T + NWORD);
+    const int fs = blockIdx.x;
+    const int f = fs / S, s = fs % S;
+    if (f >= nvalid[s]) return;
+    const int tid = threadIdx.x;
+    const unsigned long long *src = bits + (size_t)fs * NWORD;
+    for (int i = tid; i < NWORD; i += BLOCK) A[i] = src[i];
+    __syncthreads();
+    post_planes<G, BLOCK>(A, T, changed);
+    unsigned long long *dst = filled_bits + (size_t)fs * NWORD;
+    uint8_t *lab = labels + (size_t)fs * NLAB;
+    for (int i = tid; i < NWORD; i += BLOCK) dst[i] = ~T[i];
+    for (int i = tid; i < NLAB; i += BLOCK) {
+        const int r = i / LW, c = i % LW;              // label (r, c) = filled pixel (8 c, 8 r); 8 r < MH by Geom's assert
+        lab[i] = (uint8_t)((~T[8 * r * ROWW + c / 8] >> (8 * (c % 8))) & 1ull);
+    }
+}
+
+// workgroup sizes of the post kernel (the results do not depend on them): at 960x540 one workgroup owns the CU
+constexpr int POST_BLOCK_960 = 512, POST_BLOCK_320 = 256;
+
+template <typename K>
+int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
+    if (lds <= 64 * 1024) return COVAHIP_OK;
+    static std::mutex mu;
+    static std::vector<std::pair<int, const void *>> opened;
+    const void *fn = reinterpret_cast<const void *>(kernel);
+    std::lock_guard<std::mutex> lock(mu);
+    for (auto &o : opened)
+        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
+    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    opened.emplace_back(ctx->device, fn);
+    return COVAHIP_OK;
+}
+
+template <int MW, int MH, int BLOCK>
+int launch_post(covahip_ctx *ctx, const unsigned long long *bits, unsigned long long *filled_bits, uint8_t *labels,
+                const int32_t *nvalid, int S, size_t FS) {
+    constexpr size_t lds = post_lds<Geom<MW, MH>>();
+    static_assert(lds <= 160 * 1024 - 64, "the two planes must fit a CU's LDS");
+    if (int rc = open_lds(ctx, k_mog_grid_post<MW, MH, BLOCK>, lds)) return rc;
+    {
+        ProfScope ps(ctx, "mog_post");
+        k_mog_grid_post<MW, MH, BLOCK><<<dim3((unsigned)FS), BLOCK, lds, ctx->stream>>>(bits, filled_bits, labels, nvalid, S);
+    }
+    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+
+}  // namespace
+
+int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
+                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits) {
+    {
+        ProfScope ps(ctx, "mog_update");
+        if (mw == 960)
+            k_mog_grid_update<960, 540><<<dim3(Geom<960, 540>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
+                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
+        else if (mw == 320)
+            k_mog_grid_update<320, 180><<<dim3(Geom<320, 180>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
+                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
+        else
+            return COVAHIP_ERR_UNSUPPORTED;
+    }
+    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+
+int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
+                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS) {
+    if (mw == 960) return launch_post<960, 540, POST_BLOCK_960>(ctx, bits, filled_bits, labels, nvalid, S, FS);
+    if (mw == 320) return launch_post<320, 180, POST_BLOCK_320>(ctx, bits, filled_bits, labels, nvalid, S, FS);
+    return COVAHIP_ERR_UNSUPPORTED;
+}

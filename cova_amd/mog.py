@@ -1,11 +1,14 @@
 """MoG training labels on the GPU: utils/generate-mog.py of the reference, the first step of its "train from scratch" flow.
 
   MogLabeler   covahip_mog_*: per-pixel MOG2 at 640x360, close 4x4, open 6x6, hole fill and the ::8 subsample to the 45x80
-               labels `tfrecordsink gt=` reads, for several independent videos (streams) per call
+               labels `tfrecordsink gt=` reads, for several independent videos (streams) per call.  grid="macroblock" works
+               at half the source instead and labels the source's own macroblocks: 68x120 for 1920x1080
+  label_dims   (label_h, label_w) of a source size on either grid, without a GPU
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
 
     ffmpeg -i VIDEO -f rawvideo -pix_fmt bgr24 - | python -m cova_amd.mog --size 1280x720 -:VIDEO_gt.dump
     python -m cova_amd.mog --size 1280x720 a.bgr b.bgr:labels_b.dump ... [--streams S] [--chunk F]
+    python -m cova_amd.mog --size 1920x1080 --grid macroblock IN.bgr ...      (68x120 labels: what 1080p records need)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
 to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Pixel decoding is not done here:
@@ -28,6 +31,22 @@ LABEL_H, LABEL_W = 45, 80
 NMIX = 5
 SIZES = ((640, 360), (1280, 720), (1920, 1080))
 MAX_STREAMS = 1024
+GRIDS = {"reference": 0, "macroblock": 1}       # COVAHIP_MOG_GRID_*
+
+
+def work_dims(w: int, h: int, grid: str = "reference"):
+    """(work_w, work_h) of a w x h source: 640x360 on the reference grid, half the source on the macroblock grid."""
+    if grid not in GRIDS:
+        raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
+    if (w, h) not in SIZES:
+        raise ValueError(f"unsupported size {w}x{h}: one of " + ", ".join(f"{a}x{b}" for a, b in SIZES))
+    return (WORK_W, WORK_H) if grid == "reference" else (w // 2, h // 2)
+
+
+def label_dims(w: int, h: int, grid: str = "reference"):
+    """(label_h, label_w) of a w x h source: one label per 8x8 block of the working image (its top-left pixel)."""
+    ww, wh = work_dims(w, h, grid)
+    return (wh + 7) // 8, (ww + 7) // 8
 
 
 def _ptr(a: np.ndarray) -> int:
@@ -35,18 +54,27 @@ def _ptr(a: np.ndarray) -> int:
 
 
 class MogLabeler:
-    """covahip_mog_* over one ctx: `streams` videos of src_w x src_h BGR24 frames advance per `apply` call."""
+    """covahip_mog_* over one ctx: `streams` videos of src_w x src_h BGR24 frames advance per `apply` call.  `grid` is
+    "reference" (640x360 working frames, 45x80 labels) or "macroblock" (half the source, one label per macroblock of the
+    source); work_w, work_h, label_h and label_w say which shapes the labeller takes and gives."""
 
-    def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0):
+    def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0,
+                 grid: str = "reference"):
+        if grid not in GRIDS:
+            raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
         self.ctx = ctx
         self._lib = L.lib()
         cfg = L.MogCfg()
         self._lib.covahip_mog_default_cfg(C.byref(cfg))
         cfg.src_w, cfg.src_h, cfg.n_streams, cfg.history, cfg.var_threshold = src_w, src_h, streams, history, var_threshold
         h = C.c_void_p()
-        L.check(self._lib.covahip_mog_create(ctx.handle, C.byref(cfg), C.byref(h)), "covahip_mog_create", ctx.handle)
+        L.check(self._lib.covahip_mog_create_grid(ctx.handle, C.byref(cfg), GRIDS[grid], C.byref(h)), "covahip_mog_create_grid",
+                ctx.handle)
         self.handle = h
-        self.src_w, self.src_h, self.streams = src_w, src_h, streams
+        self.src_w, self.src_h, self.streams, self.grid = src_w, src_h, streams, grid
+        d = [C.c_int32() for _ in range(4)]
+        L.check(self._lib.covahip_mog_dims(h, *(C.byref(v) for v in d)), "covahip_mog_dims")
+        self.work_w, self.work_h, self.label_w, self.label_h = (int(v.value) for v in d)
 
     def close(self):
         if getattr(self, "handle", None):
@@ -65,7 +93,7 @@ class MogLabeler:
         return nv
 
     def apply(self, frames: np.ndarray, n_valid=None, labels: np.ndarray | None = None) -> np.ndarray:
-        """frames u8 [F][S][src_h][src_w][3] -> labels u8 [F][S][45][80].  n_valid[s] <= F: stream s takes only its first
+        """frames u8 [F][S][src_h][src_w][3] -> labels u8 [F][S][label_h][label_w].  n_valid[s] <= F: stream s takes only its first
         n_valid[s] frames, and its labels past them are left as `labels` holds them (zeros when no `labels` is given)."""
         frames = np.ascontiguousarray(frames, dtype=np.uint8)
         want = (self.streams, self.src_h, self.src_w, 3)
@@ -73,16 +101,17 @@ class MogLabeler:
             raise ValueError(f"frames of shape {frames.shape}, expected [F]{list(want)}")
         n = frames.shape[0]
         if labels is None:
-            labels = np.zeros((n, self.streams, LABEL_H, LABEL_W), np.uint8)
-        elif labels.shape != (n, self.streams, LABEL_H, LABEL_W) or labels.dtype != np.uint8 or not labels.flags.c_contiguous:
-            raise ValueError("labels must be a C-contiguous u8 array [F][S][45][80]")
+            labels = np.zeros((n, self.streams, self.label_h, self.label_w), np.uint8)
+        elif (labels.shape != (n, self.streams, self.label_h, self.label_w) or labels.dtype != np.uint8
+              or not labels.flags.c_contiguous):
+            raise ValueError(f"labels must be a C-contiguous u8 array [F][S][{self.label_h}][{self.label_w}]")
         nv = self._n_valid(n_valid, n)
         L.check(self._lib.covahip_mog_apply(self.handle, _ptr(frames), n, None if nv is None else _ptr(nv), _ptr(labels),
                                             L.MEM_HOST), "covahip_mog_apply", self.ctx.handle)
         return labels
 
     def apply_device(self, d_frames: int, n_frames: int, d_labels: int, n_valid=None):
-        """The same on device pointers (frames u8 [F][S][src_h][src_w][3], labels u8 [F][S][45][80] on the ctx's GPU)."""
+        """The same on device pointers (frames u8 [F][S][src_h][src_w][3], labels u8 [F][S][label_h][label_w] on the ctx's GPU)."""
         nv = self._n_valid(n_valid, n_frames)
         L.check(self._lib.covahip_mog_apply(self.handle, d_frames, n_frames, None if nv is None else _ptr(nv), d_labels,
                                             L.MEM_DEVICE), "covahip_mog_apply", self.ctx.handle)
@@ -96,22 +125,22 @@ class MogLabeler:
         L.check(self._lib.covahip_dev_mog_set_stage_budget(self.handle, nbytes), "covahip_dev_mog_set_stage_budget")
 
     def state(self, s: int) -> dict:
-        """Stream s's model: W f32 [5][360][640], V f32 [5][360][640], M f32 [5][3][360][640], nmodes u8 [360][640], n."""
-        W = np.empty((NMIX, WORK_H, WORK_W), np.float32)
+        """Stream s's model: W f32 [5][work_h][work_w], V the same, M f32 [5][3][work_h][work_w], nmodes u8 [work_h][work_w], n."""
+        W = np.empty((NMIX, self.work_h, self.work_w), np.float32)
         V = np.empty_like(W)
-        M = np.empty((NMIX, 3, WORK_H, WORK_W), np.float32)
-        nm = np.empty((WORK_H, WORK_W), np.uint8)
+        M = np.empty((NMIX, 3, self.work_h, self.work_w), np.float32)
+        nm = np.empty((self.work_h, self.work_w), np.uint8)
         n = C.c_int64()
         L.check(self._lib.covahip_dev_mog_state(self.handle, s, _ptr(W), _ptr(V), _ptr(M), _ptr(nm), C.byref(n)),
                 "covahip_dev_mog_state", self.ctx.handle)
         return {"W": W, "V": V, "M": M, "nmodes": nm, "n": int(n.value)}
 
     def debug_masks(self):
-        """(raw, filled) of the last apply call, u8 [F][S][360][640]: the MOG2 mask (0 / 255) and the mask after close, open
+        """(raw, filled) of the last apply call, u8 [F][S][work_h][work_w]: the MOG2 mask (0 / 255) and the mask after close, open
         and hole fill (0 / 1)."""
         nf = C.c_int()
         L.check(self._lib.covahip_dev_mog_masks(self.handle, None, None, 0, C.byref(nf)), "covahip_dev_mog_masks")
-        shape = (nf.value, self.streams, WORK_H, WORK_W)
+        shape = (nf.value, self.streams, self.work_h, self.work_w)
         raw = np.empty(shape, np.uint8)
         filled = np.empty(shape, np.uint8)
         L.check(self._lib.covahip_dev_mog_masks(self.handle, _ptr(raw), _ptr(filled), raw.nbytes, C.byref(nf)),
@@ -206,6 +235,9 @@ def _args(argv):
     ap.add_argument("inputs", nargs="+", type=parse_io, metavar="IN[:OUT]",
                     help="raw BGR24 video ('-' = stdin); OUT defaults to IN's name with _gt.dump")
     ap.add_argument("--size", type=parse_size, required=True, help="source size: 640x360, 1280x720 or 1920x1080")
+    ap.add_argument("--grid", choices=sorted(GRIDS), default="reference",
+                    help="reference: 45x80 labels whatever the source (the 1280x720 macroblock grid); macroblock: one label per "
+                         "macroblock of the source, which 1080p records need (1920x1080 -> 68x120)")
     ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
     ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
     ap.add_argument("--history", type=int, default=9000)
@@ -238,9 +270,9 @@ def main(argv=None) -> int:
     S = min(a.streams, len(a.inputs))
     pending = list(a.inputs)
     ctx = Context(a.device)
-    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold)
+    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid)
     frames = np.empty((a.chunk, S, h, w, 3), np.uint8)
-    labels = np.zeros((a.chunk, S, LABEL_H, LABEL_W), np.uint8)
+    labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)
     slots = [None] * S           # (source, output file, output name, start time) per stream slot
 
     def open_next(s):

@@ -485,6 +485,14 @@ void covahip_train_destroy(covahip_train *tr);
  *      4-connected, every background 4-component that does not touch the image edge becomes 1;
  *   6. label[i][j] = filled[8i][8j]: 45x80 bytes of 0 / 1 per frame, the file `tfrecordsink gt=` reads (frames one after the
  *      other, as ndarray.tofile writes them).
+ * That is the reference grid (COVAHIP_MOG_GRID_REFERENCE): 45x80 is the macroblock grid of a 1280x720 stream, whatever the
+ * source.  The macroblock grid (COVAHIP_MOG_GRID_MACROBLOCK) labels the source's own 16x16 macroblocks; it differs in two steps:
+ *   1. the working image is half the source in both axes, by the exact-2x rule above ((a + b + c + d + 2) >> 2 per channel over
+ *      the 2x2 block): 1920x1080 -> 960x540, 1280x720 -> 640x360 (the reference grid itself: the same labels, masks and model,
+ *      byte for byte), 640x360 -> 320x180; any other size is COVAHIP_ERR_UNSUPPORTED;
+ *   6. label[i][j] = filled[8i][8j] for every i, j with 8i < working height and 8j < working width, the pixel at the top-left
+ *      corner of macroblock (i, j): 68x120 (the last row reads working row 536), 45x80 and 23x40 (row 176) bytes per frame.
+ * Steps 2 - 5 are the same: the 4x4 / 6x6 kernels stay in working pixels, the same size relative to a macroblock.
  * MOG2 (the CPU path of OpenCV 4.x MOG2Invoker, nmixtures 5).  All values f32 unless noted, every product and sum rounded on
  * its own (no fused multiply-add), divisions correctly rounded:
  *   constants Tb = var_threshold, TB = 0.9, Tg = 9, varInit = 15, varMin = 4, varMax = 75, fCT = 0.05f;
@@ -507,7 +515,7 @@ void covahip_train_destroy(covahip_train *tr);
  *        i < nmodes - 1; M[m] = data; V[m] = varInit; for i = nmodes - 1 down to 1: stop if alphaT < W[i-1], else swap;
  *     5. mask = bg ? 0 : 255.
  * Streams: n_streams independent videos advance in one call, each with its own model and frame count.  Memory: about 23 MB of
- * model per stream.  Every call is synchronous. */
+ * model per stream (101 bytes per working pixel: 52 MB at 960x540).  Every call is synchronous. */
 enum { COVAHIP_MOG_MAX_STREAMS = 1024, COVAHIP_MOG_LABEL_H = 45, COVAHIP_MOG_LABEL_W = 80 };
 typedef struct covahip_mog covahip_mog;
 typedef struct covahip_mog_cfg {
@@ -520,6 +528,12 @@ typedef struct covahip_mog_cfg {
 void covahip_mog_default_cfg(covahip_mog_cfg *cfg);
 /* COVAHIP_ERR_UNSUPPORTED for another source size, COVAHIP_ERR_INVALID_ARG for streams, history or var_threshold out of range. */
 int  covahip_mog_create(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out);
+/* The same on either label grid; covahip_mog_create is the reference grid.  COVAHIP_ERR_INVALID_ARG for another `grid`.  apply,
+ * reset and destroy take either kind of labeller; in the comments below 45x80 stands for the labeller's label_h x label_w. */
+enum { COVAHIP_MOG_GRID_REFERENCE = 0, COVAHIP_MOG_GRID_MACROBLOCK = 1 };
+int  covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int grid, covahip_mog **out);
+/* The labeller's working size and label grid; any pointer may be NULL. */
+int  covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h);
 /* frames u8 [n_frames][n_streams][src_h][src_w][3]; labels u8 [n_frames][n_streams][45][80] (mem_kind applies to both; n_valid is
  * always a host pointer).  n_valid[s] <= n_frames: frames past it are ignored for stream s and their labels untouched (NULL = all).
  * n_frames >= 1.  Host frames are staged in launches of up to 1 GiB of frames. */

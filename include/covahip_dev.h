@@ -71,13 +71,13 @@ struct covahip_pipe;
 int covahip_dev_pipe_queue_plan(struct covahip_pipe *pipe, int *lanes_on_upload_queue, int *lanes_on_result_queue);
 
 /* MoG labels (covahip_mog_apply) of the last call, expanded from its bit planes: raw = the MOG2 mask (0 / 255) and filled = the
- * mask after close, open and hole fill (0 / 1), each u8 [n_frames][n_streams][360][640] (either may be NULL; cap = bytes of
- * each; COVAHIP_ERR_OVERFLOW when too small).  *n_frames = that call's n_frames.  Frames past a stream's n_valid hold nothing
+ * mask after close, open and hole fill (0 / 1), each u8 [n_frames][n_streams][work_h][work_w] of the labeller's own working size
+ * (covahip_mog_dims; 360 x 640 on the reference grid) (either may be NULL; cap = bytes of each; COVAHIP_ERR_OVERFLOW when too small).  *n_frames = that call's n_frames.  Frames past a stream's n_valid hold nothing
  * meaningful.  (tests/test_gpu_mog.py) */
 struct covahip_mog;
 int covahip_dev_mog_masks(struct covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t cap, int *n_frames);
-/* One stream's model: W f32 [5][230400], V f32 [5][230400], M f32 [5][3][230400], nmodes u8 [230400] and n (frames seen);
- * any pointer may be NULL. */
+/* One stream's model: W f32 [5][P], V f32 [5][P], M f32 [5][3][P], nmodes u8 [P] and n (frames seen), P = work_w * work_h of
+ * the labeller (covahip_mog_dims; 230400 on the reference grid); any pointer may be NULL. */
 int covahip_dev_mog_state(struct covahip_mog *m, int stream, float *W, float *V, float *M, uint8_t *nmodes, int64_t *n);
 /* Device bytes of host frames that covahip_mog_apply (COVAHIP_MEM_HOST) stages per update launch; 0 restores the default of
  * 1 GiB.  A call whose frames exceed it runs as several update launches of whole frame-steps (one frame of every stream), at

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
-"""MoG label throughput on one GPU: 640x360 working frames per second of covahip_mog_apply at several stream counts.
+"""MoG label throughput on one GPU: working frames per second of covahip_mog_apply at several stream counts.
 
     python tools/mog_rate.py [--streams 1,8,64 --sizes 1280x720,640x360 --frames 1024 --reps 3] [--oracle-frames 3]
+    python tools/mog_rate.py --grid macroblock --sizes 1920x1080 --frames 256      (960x540 working frames, 68x120 labels)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -42,6 +43,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", default="1,8,64")
     ap.add_argument("--sizes", default="1280x720,640x360")
+    ap.add_argument("--grid", choices=sorted(mog.GRIDS), default="reference")
     ap.add_argument("--frames", type=int, default=1024, help="working frames per call (all streams)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--oracle-frames", type=int, default=3)
@@ -56,8 +58,8 @@ def main():
             frames = np.empty((F, S, h, w, 3), np.uint8)
             for f in range(F):
                 frames[f] = pool[(f + np.arange(S)) % len(pool)]
-            labels = np.zeros((F, S, 45, 80), np.uint8)
-            m = mog.MogLabeler(ctx, w, h, streams=S)
+            labels = np.zeros((F, S) + mog.label_dims(w, h, a.grid), np.uint8)
+            m = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
             m.apply_device(d_f, F, d_l)                      # warm-up (buffers, code objects)
@@ -73,7 +75,7 @@ def main():
             ctx.profile(False)
             tot = sum(v[0] for k, v in prof.items() if k.startswith("mog_"))
             med = statistics.median(ms)
-            rec = {"case": "device", "src": size, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+            rec = {"case": "device", "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
                    "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms],
                    "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
                    "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
@@ -88,7 +90,7 @@ def main():
                     m.apply(frames, labels=labels)
                     wall.append((time.perf_counter() - t0) * 1e3)
                 med = statistics.median(wall)
-                print(json.dumps({"case": "host", "src": size, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+                print(json.dumps({"case": "host", "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
                                   "frames_per_s": round(F * S / med * 1e3, 1), "in_gb_per_s": round(frames.nbytes / med / 1e6, 2),
                                   "ms_all": [round(x, 3) for x in wall]}), flush=True)
             m.close()
