@@ -33,6 +33,8 @@ constexpr uint32_t W_MAGIC = 0x57485643;  // "CVHW"
 constexpr int ENC_C[NL + 1] = {3, 16, 32, 64, 128};
 constexpr int DEC_CI[NL] = {128, 128, 64, 32};
 constexpr int DEC_CO[NL] = {64, 32, 16, 16};
+// the 64-byte header of a weight file of the trained architecture; a reader checks the first 13 words
+constexpr uint32_t W_HEADER[16] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS, 0, 0, 0};
 constexpr int BLK = 256;
 constexpr int RED_CHUNK = 4096;       // elements per slab of a channel reduction
 constexpr int WG_CHUNK = 1024;        // positions per slab of a weight gradient
@@ -434,7 +436,7 @@ __global__ void k_bn_bwd(Mdl md, const float *g, int Cg, const float *__restrict
 
 // BN backward apply of a layer in inference mode (the training plan, include/covahip.h "Fine-tuning"): the layer normalised with
 // constants, so out = g * gamma * invstd with no batch-mean terms; times (x > 0) when relu_in.  stat[C + ch] = 1 / sqrt(moving
-// variance + eps) (k_plan_stat).  g and out may be the same buffer, as in k_bn_bwd.
+// variance + eps) (k_bn_stat).  g and out may be the same buffer, as in k_bn_bwd.
 template <bool SET>
 __global__ void k_bn_bwd_inf(Mdl md, const float *g, int Cg, const float *__restrict__ x, const float *__restrict__ stat,
                              const float *__restrict__ gamma, float *out, int C, int64_t S, int relu_in) {
@@ -712,7 +714,18 @@ __global__ void k_final_fwd(Mdl md, const float *__restrict__ y, const float *__
     logit[i] = acc;
 }
 
-// loss = mean over samples of (1 - (I + sm) / (S - I + sm)) * sm; red = [I per sample][S per sample]
+// A sample's loss: the Jaccard distance (1 - (I + sm) / (S - I + sm)) * sm of its I = sum y*p and S = sum y + p
+__device__ inline float jaccard_distance(float I, float S, float sm) { return (1.f - (I + sm) / (S - I + sm)) * sm; }
+
+// One position's share of the workgroup's TP / FP / FN counters (cnt[3] in LDS) at sigmoid > 0.5
+__device__ inline void count_confusion(unsigned *cnt, float pr, uint8_t label) {
+    const bool pos = pr > 0.5f, lab = label != 0;
+    if (pos && lab) atomicAdd(&cnt[0], 1u);
+    if (pos && !lab) atomicAdd(&cnt[1], 1u);
+    if (!pos && lab) atomicAdd(&cnt[2], 1u);
+}
+
+// loss = mean over samples of their Jaccard distance; red = [I per sample][S per sample]
 template <bool SET>
 __global__ void k_loss(Mdl md, const float *__restrict__ red, float sm, float *__restrict__ loss) {
     const int B = model_b<SET>(md);
@@ -720,10 +733,7 @@ __global__ void k_loss(Mdl md, const float *__restrict__ red, float sm, float *_
     red += blockIdx.z * red_stride(md.maxB);
     loss += blockIdx.z;
     float acc = 0.f;
-    for (int b = 0; b < B; b++) {
-        const float I = red[b], S = red[B + b];
-        acc += (1.f - (I + sm) / (S - I + sm)) * sm;
-    }
+    for (int b = 0; b < B; b++) acc += jaccard_distance(red[b], red[B + b], sm);
     loss[0] = acc / (float)B;
 }
 
@@ -756,51 +766,41 @@ __global__ void k_final_bwd(Mdl md, const float *__restrict__ logit, const uint8
         const float dl = dp * pr * (1.f - pr);
         dlogit[i] = dl;
         for (int c = 0; c < 16; c++) dy[(b * 16 + c) * hw + s] = dl * fk[c];
-        const bool pos = pr > 0.5f, lab = gt[i] != 0;
-        if (pos && lab) atomicAdd(&cnt[0], 1u);
-        if (pos && !lab) atomicAdd(&cnt[1], 1u);
-        if (!pos && lab) atomicAdd(&cnt[2], 1u);
+        count_confusion(cnt, pr, gt[i]);
     }
     __syncthreads();
     if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
 
 // ------------------------------------------------------------------------------------------------ evaluation kernels
-// The evaluation pass (include/covahip.h, "Evaluation and resume") runs the forward kernels above unchanged.  Two things differ
-// from a training forward.  BatchNorm: k_eval_stat below fills `stat` from the moving statistics, in place of the reduce /
-// finalize launches that fill it from the batch.  Dropout: every site gets threshold 0 and scale 1; keep() compares an unsigned
-// value with >= 0, which holds for every hash, and returns the scale 1.0f, and x * 1.0f is x for every float (the products
-// dropped are ReLU outputs: no NaN payloads to quieten), so the site is the identity bit for bit.
-struct EvalBN {                       // where the seven BN layers keep their moving statistics in the flat parameters
+// The evaluation pass (include/covahip.h, "Evaluation and resume") is the step's forward (forward() below) with two things
+// different.  BatchNorm: k_bn_stat below fills `stat` from the moving statistics, in place of the reduce / finalize launches
+// that fill it from the batch.  Dropout: every site gets threshold 0 and scale 1; keep() compares an unsigned value with >= 0,
+// which holds for every hash, and returns the scale 1.0f, and x * 1.0f is x for every float (the products dropped are ReLU
+// outputs: no NaN payloads to quieten), so the site is the identity bit for bit.
+struct BNTab {                        // where the seven BN layers keep their moving statistics in the flat parameters
     int32_t mean[2 * NL - 1], var[2 * NL - 1], C[2 * NL - 1];
 };
-// stat[layer] = (moving mean, 1 / sqrt(moving variance + eps)): the expression k_finalize(F_VAR) forms from the batch variance
+// The stat rows of the BN layers in inference mode (bit `layer` of layers: all seven in an evaluation, a training plan's in a
+// step): stat[layer] = (moving mean, 1 / sqrt(moving variance + eps)), the expression k_finalize(F_VAR) forms from the batch
+// variance.  grads (a step; null in an evaluation, which never writes gradients): the layer's mean / var gradient slots take
+// the moving values the forward normalises with.  Once per step: an evaluation or a state load between two steps cannot
+// leave a stale row.
 template <bool SET>
-__global__ void k_eval_stat(Mdl md, const float *__restrict__ params, float *__restrict__ stat, EvalBN t, float eps) {
-    const int layer = blockIdx.x, c = threadIdx.x, C = t.C[layer];
-    if (model_b<SET>(md) == 0 || c >= C) return;
-    params += POFF;
-    stat += blockIdx.z * STAT_STRIDE + layer * 256;
-    stat[c] = params[t.mean[layer] + c];
-    stat[C + c] = 1.f / sqrtf(params[t.var[layer] + c] + eps);
-}
-
-// The stat rows of the BN layers a training plan puts in inference mode (bit `layer` of layers), filled as k_eval_stat fills
-// them; the layer's mean / var gradient slots take the moving values the forward normalises with.  Once per step: an evaluation
-// or a state load between two steps cannot leave a stale row.
-template <bool SET>
-__global__ void k_plan_stat(Mdl md, const float *__restrict__ params, float *__restrict__ grads, float *__restrict__ stat, EvalBN t,
-                            uint32_t layers, float eps) {
+__global__ void k_bn_stat(Mdl md, const float *__restrict__ params, float *__restrict__ grads, float *__restrict__ stat, BNTab t,
+                          uint32_t layers, float eps) {
     const int layer = blockIdx.x, c = threadIdx.x, C = t.C[layer];
     if (model_b<SET>(md) == 0 || !(layers >> layer & 1u) || c >= C) return;
     params += POFF;
-    grads += POFF;
     stat += blockIdx.z * STAT_STRIDE + layer * 256;
     const float mean = params[t.mean[layer] + c], var = params[t.var[layer] + c];
     stat[c] = mean;
     stat[C + c] = 1.f / sqrtf(var + eps);
-    grads[t.mean[layer] + c] = mean;
-    grads[t.var[layer] + c] = var;
+    if (grads) {
+        grads += POFF;
+        grads[t.mean[layer] + c] = mean;
+        grads[t.var[layer] + c] = var;
+    }
 }
 
 // TP / FP / FN at sigmoid > 0.5 as k_final_bwd counts them (integer atomics; the counters run on over the chunks of one
@@ -818,21 +818,12 @@ __global__ void k_eval_tail(Mdl md, const float *__restrict__ logit, const uint8
     counts += 3 * blockIdx.z;
     if (blockIdx.x == 0) {
         sample_loss += (int64_t)blockIdx.z * md.maxB;
-        for (int b = threadIdx.x; b < B; b += BLK) {
-            const float I = red[b], S = red[B + b];
-            sample_loss[b] = (1.f - (I + sm) / (S - I + sm)) * sm;
-        }
+        for (int b = threadIdx.x; b < B; b += BLK) sample_loss[b] = jaccard_distance(red[b], red[B + b], sm);
     }
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
-    if (i < (int64_t)B * hw) {
-        const float pr = 1.f / (1.f + expf(-logit[i]));
-        const bool pos = pr > 0.5f, lab = gt[i] != 0;
-        if (pos && lab) atomicAdd(&cnt[0], 1u);
-        if (pos && !lab) atomicAdd(&cnt[1], 1u);
-        if (!pos && lab) atomicAdd(&cnt[2], 1u);
-    }
+    if (i < (int64_t)B * hw) count_confusion(cnt, 1.f / (1.f + expf(-logit[i])), gt[i]);
     __syncthreads();
     if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
@@ -924,6 +915,12 @@ struct covahip_train {
 
 namespace {
 
+// makes the ctx's device current and takes the primary-op gate: the start of every entry point that touches the GPU
+int enter(covahip_ctx *ctx) {
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return covahip_primary_op(ctx);
+}
+
 template <class T>
 int talloc(covahip_train *tr, T **p, size_t n) {
     void *q = nullptr;
@@ -982,19 +979,24 @@ DropS make_drop(const covahip_train *tr, int site) {
     return d;
 }
 
-// launch the set or the solo instantiation of kernel k
-#define KL(k, grid, block, ...)                                     \
-    do {                                                            \
-        if (tr->K > 1) k<true><<<grid, block, 0, s>>>(__VA_ARGS__); \
-        else k<false><<<grid, block, 0, s>>>(__VA_ARGS__);          \
+// launch the set or the solo instantiation of kernel k on Run r's stream, for r's models
+#define KL(r, k, grid, block, ...)                                                     \
+    do {                                                                               \
+        if ((r).tr->K > 1) k<true><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__);    \
+        else k<false><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__);                 \
     } while (0)
 
+// One pass (a step, or an evaluation chunk) over every model with a non-zero batch in tr->h_tab (K > 1: already uploaded to
+// d_tab); B = the largest batch.
 struct Run {
     covahip_train *tr;
     hipStream_t s;
     Mdl md;
-    int B;   // the step's largest batch: sizes the grids
+    int B;   // sizes the grids
     int rc = COVAHIP_OK;
+    Run(covahip_train *t, int bmax)
+        : tr(t), s(t->ctx->stream),
+          md{t->K > 1 ? t->d_tab : nullptr, t->cfg.max_batch, (int64_t)t->slab_floats, t->h_tab[0].b, t->h_tab[0].lr_t}, B(bmax) {}
     bool ok() {
         if (rc) return false;
         const hipError_t e = hipGetLastError();
@@ -1005,6 +1007,7 @@ struct Run {
         return rc == COVAHIP_OK;
     }
     dim3 g1(int64_t n) const { return dim3(nblk(n), 1, tr->K); }
+    float *stat(int layer) const { return tr->stat + layer * 256; }   // model 0's row of a BN layer
     // per-channel reduction of [b][C][S] (R_LOSS: [1][b][S]) + finalize; every model splits by its own batch in the kernels
     void reduce(int mode, int C, int64_t S, const float *x, const float *g, int Cg, const float *aux, const uint8_t *gt,
                 int fmode, float *stat, int64_t stat_stride, float *g0, float *g1_, float *mov0, float *mov1) {
@@ -1012,14 +1015,14 @@ struct Run {
         const int Cmax = loss ? B : C;
         const int64_t M = (int64_t)(loss ? 1 : B) * S;
         const int NP = red_slabs(M);
-        KL(k_reduce, (dim3(NP, Cmax, tr->K)), BLK, md, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP);
-        KL(k_finalize, (g1(Cmax)), BLK, md, fmode, loss, Cmax, S, tr->slab, stat, stat_stride, g0, g1_, mov0, mov1,
-                                           tr->cfg.bn_momentum, tr->cfg.bn_eps);
+        KL(*this, k_reduce, (dim3(NP, Cmax, tr->K)), BLK, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP);
+        KL(*this, k_finalize, (g1(Cmax)), BLK, fmode, loss, Cmax, S, tr->slab, stat, stat_stride, g0, g1_, mov0, mov1,
+                                                  tr->cfg.bn_momentum, tr->cfg.bn_eps);
     }
 };
 
-EvalBN bn_table(const covahip_train *tr) {
-    EvalBN bn;
+BNTab bn_table(const covahip_train *tr) {
+    BNTab bn;
     for (int i = 0; i < NL; i++) {
         bn.mean[i] = (int32_t)tr->eo[i].mean;
         bn.var[i] = (int32_t)tr->eo[i].var;
@@ -1033,19 +1036,77 @@ EvalBN bn_table(const covahip_train *tr) {
     return bn;
 }
 
-// One step of every model with a non-zero batch in tr->h_tab (K > 1: already uploaded to d_tab); B = the largest batch.
-// The launch schedule follows the training plan (include/covahip.h, "Fine-tuning"); the empty plan gives the full step.
-int run_step(covahip_train *tr, int B) {
-    Run r{tr, tr->ctx->stream,
-          Mdl{tr->K > 1 ? tr->d_tab : nullptr, tr->cfg.max_batch, (int64_t)tr->slab_floats, tr->h_tab[0].b, tr->h_tab[0].lr_t}, B};
-    const hipStream_t s = r.s;
-    const Mdl md = r.md;
-    const int K = tr->K;
+// What differs between the forward of a training step and of an evaluation chunk.
+struct Fwd {
+    uint32_t bn_inf;        // BN layers that normalise with their moving statistics: the plan's, or all seven
+    bool stat_to_grads;     // their moving values also go to the gradient slots (never in an evaluation: it leaves grads alone)
+    DropS drop[N_SITES];    // the dropout sites; an evaluation's are the identity (see k_bn_stat)
+};
+
+// The forward of every model of the run, up to the logits and the per-sample loss sums [I][S] in tr->red.  Writes activations,
+// stat, red and slab, and (batch-mode BN layers, stat_to_grads) moving statistics and gradient slots.
+int forward(Run &r, const Fwd &f) {
+    covahip_train *tr = r.tr;
+    const int B = r.B;
     float *P = tr->params, *G = tr->grads;
     const int H0 = tr->H[0], W0 = tr->W[0];
+    auto inf = [&](int layer) { return (f.bn_inf >> layer & 1u) != 0; };
+    if (f.bn_inf)
+        KL(r, k_bn_stat, (dim3(2 * NL - 1, 1, tr->K)), 128, P, f.stat_to_grads ? G : nullptr, tr->stat, bn_table(tr), f.bn_inf,
+                                                          tr->cfg.bn_eps);
+    KL(r, k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, tr->d_stack, tr->x0, H0, W0);
+    for (int i = 0; i < NL; i++) {
+        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
+        const EncOff &o = tr->eo[i];
+        const float *xin = i ? tr->e[i - 1] : tr->x0;
+        const int64_t S = (int64_t)TT * H * W;
+        KL(r, k_conv3_fwd, (r.g1(B * Co * S)), BLK, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
+        if (!inf(i)) {
+            r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, r.stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
+            r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, r.stat(i), nullptr, F_VAR, r.stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
+                     P + o.var);
+        }
+        KL(r, k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, tr->c[i], r.stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
+                                                                         Co, H, W, Hp, Wp);
+        const int zj = NL - 1 - i;   // the decoder block whose input concat holds this level's t = 0 slice
+        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
+        KL(r, k_tmix_fwd, (r.g1((int64_t)B * Co * Hp * Wp)), BLK, tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
+                                                                    Co, (int64_t)Hp * Wp, f.drop[2 * i], f.drop[2 * i + 1]);
+        if (!r.ok()) return r.rc;
+    }
+    for (int j = 0; j < NL; j++) {
+        const int Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
+        const DecOff &o = tr->dof[j];
+        const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
+        KL(r, k_drop_relu, (r.g1(B * per)), BLK, tr->z[j], tr->zd[j], per, f.drop[2 * NL + j]);
+        KL(r, k_convT_fwd, (r.g1(B * Co * So)), BLK, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j]);
+        if (j < NL - 1) {
+            if (!inf(NL + j)) {
+                r.reduce(R_SUM, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, r.stat(NL + j), STAT_STRIDE, nullptr, nullptr, nullptr,
+                         nullptr);
+                r.reduce(R_SQDEV, Co, So, tr->y[j], nullptr, 0, r.stat(NL + j), nullptr, F_VAR, r.stat(NL + j), STAT_STRIDE, G + o.mean,
+                         G + o.var, P + o.mean, P + o.var);
+            }
+            KL(r, k_bn_apply, (r.g1(B * Co * So)), BLK, tr->y[j], r.stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1], Co, So);
+        }
+        if (!r.ok()) return r.rc;
+    }
+    const int64_t hw = (int64_t)H0 * W0;
+    KL(r, k_final_fwd, (r.g1(B * hw)), BLK, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
+    r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, red_stride(tr->cfg.max_batch), nullptr, nullptr,
+             nullptr, nullptr);
+    return r.rc;
+}
+
+// One step: the forward, the loss, the backward and Adam.  The launch schedule follows the training plan (include/covahip.h,
+// "Fine-tuning"); the empty plan gives the full step.
+int run_step(covahip_train *tr, int B) {
+    Run r(tr, B);
+    const int K = tr->K;
+    float *P = tr->params, *G = tr->grads;
     const float sm = tr->cfg.smooth;
-    const int64_t RS = red_stride(tr->cfg.max_batch);
-    auto stat = [&](int layer) { return tr->stat + layer * 256; };
+    const int64_t RS = red_stride(tr->cfg.max_batch), hw = (int64_t)tr->H[0] * tr->W[0];
     // The plan.  enc_fz / dec_fz: the group is frozen; inf(layer): the BN layer normalises with its moving statistics.
     // enc_live(i): something of encoder levels 0..i is trained, so the backward must reach level i; dec_live(j) likewise for
     // decoder blocks 0..j.  need_dz[j]: block j's input gradient has a reader (the BN of block j - 1, or the encoder through
@@ -1061,57 +1122,15 @@ int run_step(covahip_train *tr, int B) {
         need_dz[j] = enc_live(NL - 1) || (j > 0 && dec_live(j - 1));
         need_dy[j] = !dec_fz(j) || need_dz[j];
     }
-    if (hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), s) != hipSuccess) return COVAHIP_ERR_HIP;
+    Fwd f{bninf, true, {}};
+    for (int site = 0; site < N_SITES; site++) f.drop[site] = make_drop(tr, site);
+    if (hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), r.s) != hipSuccess) return COVAHIP_ERR_HIP;
 
-    // ---------------------------------------------------------------- forward
-    if (bninf) KL(k_plan_stat, (dim3(2 * NL - 1, 1, K)), 128, md, P, G, tr->stat, bn_table(tr), bninf, tr->cfg.bn_eps);
-    KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
-    for (int i = 0; i < NL; i++) {
-        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
-        const EncOff &o = tr->eo[i];
-        const float *xin = i ? tr->e[i - 1] : tr->x0;
-        const int64_t S = (int64_t)TT * H * W;
-        KL(k_conv3_fwd, (r.g1(B * Co * S)), BLK, md, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
-        if (!inf(i)) {
-            r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
-            r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, stat(i), nullptr, F_VAR, stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
-                     P + o.var);
-        }
-        KL(k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, md, tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
-                                                                      Co, H, W, Hp, Wp);
-        const int zj = NL - 1 - i;   // the decoder block whose input concat holds this level's t = 0 slice
-        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
-        KL(k_tmix_fwd, (r.g1((int64_t)B * Co * Hp * Wp)), BLK, md, tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
-                                                                 Co, (int64_t)Hp * Wp, make_drop(tr, 2 * i), make_drop(tr, 2 * i + 1));
-        if (!r.ok()) return r.rc;
-    }
-    for (int j = 0; j < NL; j++) {
-        const int Ci = DEC_CI[j], Co = DEC_CO[j];
-        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
-        const DecOff &o = tr->dof[j];
-        const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
-        KL(k_drop_relu, (r.g1(B * per)), BLK, md, tr->z[j], tr->zd[j], per, make_drop(tr, 2 * NL + j));
-        KL(k_convT_fwd, (r.g1(B * Co * So)), BLK, md, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                      tr->cx[j]);
-        if (j < NL - 1) {
-            if (!inf(NL + j)) {
-                r.reduce(R_SUM, Co, So, tr->y[j], nullptr, 0, nullptr, nullptr, F_MEAN, stat(NL + j), STAT_STRIDE, nullptr, nullptr, nullptr,
-                         nullptr);
-                r.reduce(R_SQDEV, Co, So, tr->y[j], nullptr, 0, stat(NL + j), nullptr, F_VAR, stat(NL + j), STAT_STRIDE, G + o.mean,
-                         G + o.var, P + o.mean, P + o.var);
-            }
-            KL(k_bn_apply, (r.g1(B * Co * So)), BLK, md, tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1],
-                                                         Co, So);
-        }
-        if (!r.ok()) return r.rc;
-    }
-    const int64_t hw = (int64_t)H0 * W0;
-    KL(k_final_fwd, (r.g1(B * hw)), BLK, md, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
-    r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, RS, nullptr, nullptr, nullptr, nullptr);
-    KL(k_loss, (dim3(1, 1, K)), 1, md, tr->red, sm, tr->d_loss);
+    if (int rc = forward(r, f)) return rc;
+    KL(r, k_loss, (dim3(1, 1, K)), 1, tr->red, sm, tr->d_loss);
 
     // ---------------------------------------------------------------- backward
-    KL(k_final_bwd, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
+    KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
                                             tr->d_counts);
     if (!dec_fz(NL - 1)) {
         r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
@@ -1126,13 +1145,13 @@ int run_step(covahip_train *tr, int B) {
         if (j < NL - 1) {   // BN of this block: its output gradient is channel range [0, Co) of the next block's dz
             // the sums are gamma's and beta's gradients in either mode, and the batch-mean terms of a batch-mode layer
             if (!dec_fz(j))
-                r.reduce(R_BNBWD, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], stat(NL + j), nullptr, F_SUM2, tr->red, RS, G + o.gamma,
+                r.reduce(R_BNBWD, Co, So, tr->y[j], tr->dz[j + 1], DEC_CI[j + 1], r.stat(NL + j), nullptr, F_SUM2, tr->red, RS, G + o.gamma,
                          G + o.beta, nullptr, nullptr);
             if (inf(NL + j))
-                KL(k_bn_bwd_inf, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), P + o.gamma,
+                KL(r, k_bn_bwd_inf, (r.g1(B * Co * So)), BLK, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], r.stat(NL + j), P + o.gamma,
                                                                tr->dy[j], Co, So, 0);
             else
-                KL(k_bn_bwd, (r.g1(B * Co * So)), BLK, md, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], stat(NL + j), tr->red, P + o.gamma,
+                KL(r, k_bn_bwd, (r.g1(B * Co * So)), BLK, tr->dz[j + 1], DEC_CI[j + 1], tr->y[j], r.stat(NL + j), tr->red, P + o.gamma,
                                                            tr->dy[j], Co, So, 0);
         }
         const int64_t per = (int64_t)Hi * Wi, Pp = (int64_t)B * per;
@@ -1140,13 +1159,13 @@ int run_step(covahip_train *tr, int B) {
             r.reduce(R_SUM, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
             const int ns = wg_slabs(Pp);
             const int nw = 16 * Co * Ci;
-            KL(k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+            KL(r, k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
                                                                tr->cx[j], (Pp + ns - 1) / ns);
-            KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, per, 0, nw, G + o.k);
+            KL(r, k_sum_slabs, (r.g1(nw)), BLK, tr->slab, per, 0, nw, G + o.k);
         }
         if (need_dz[j])
-            KL(k_convT_dgrad, (r.g1(Pp * Ci)), BLK, md, tr->dy[j], P + o.k, tr->z[j], tr->dz[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                       tr->cx[j], make_drop(tr, 2 * NL + j));
+            KL(r, k_convT_dgrad, (r.g1(Pp * Ci)), BLK, tr->dy[j], P + o.k, tr->z[j], tr->dz[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                       tr->cx[j], f.drop[2 * NL + j]);
         if (!r.ok()) return r.rc;
     }
     for (int i = NL - 1; i >= 0 && enc_live(i); i--) {
@@ -1156,89 +1175,54 @@ int run_step(covahip_train *tr, int B) {
         const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
         const int64_t tper = (int64_t)Co * Hp * Wp;
         const int nb = tmix_blocks(B * tper);
-        KL(k_tmix_bwd, (dim3(nb, 1, K)), BLK, md, tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj],
-                                                  DEC_CI[zj], c_off, tr->dp[i], tr->slab, Co, (int64_t)Hp * Wp, (B * tper + nb - 1) / nb, make_drop(tr, 2 * i),
-                                                  make_drop(tr, 2 * i + 1));
-        if (!enc_fz(i)) KL(k_sum_slabs, (dim3(1, 1, K)), BLK, md, tr->slab, tper, 1, 32, G + o.w1);
+        KL(r, k_tmix_bwd, (dim3(nb, 1, K)), BLK, tr->p[i], P + o.w1, P + o.w2, i < NL - 1 ? tr->de[i] : nullptr, tr->dz[zj],
+                                                  DEC_CI[zj], c_off, tr->dp[i], tr->slab, Co, (int64_t)Hp * Wp, (B * tper + nb - 1) / nb, f.drop[2 * i],
+                                                  f.drop[2 * i + 1]);
+        if (!enc_fz(i)) KL(r, k_sum_slabs, (dim3(1, 1, K)), BLK, tr->slab, tper, 1, 32, G + o.w1);
         const int64_t S = (int64_t)TT * H * W;
-        KL(k_pool_bwd, (r.g1(B * Co * S)), BLK, md, tr->dp[i], tr->arg[i], tr->dc[i], Co, H, W, Hp, Wp);
+        KL(r, k_pool_bwd, (r.g1(B * Co * S)), BLK, tr->dp[i], tr->arg[i], tr->dc[i], Co, H, W, Hp, Wp);
         if (!enc_fz(i))
-            r.reduce(R_BNBWD, Co, S, tr->c[i], tr->dc[i], Co, stat(i), nullptr, F_SUM2, tr->red, RS, G + o.gamma, G + o.beta, nullptr, nullptr);
+            r.reduce(R_BNBWD, Co, S, tr->c[i], tr->dc[i], Co, r.stat(i), nullptr, F_SUM2, tr->red, RS, G + o.gamma, G + o.beta, nullptr, nullptr);
         if (inf(i))
-            KL(k_bn_bwd_inf, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), P + o.gamma, tr->dc[i], Co, S, 1);
+            KL(r, k_bn_bwd_inf, (r.g1(B * Co * S)), BLK, tr->dc[i], Co, tr->c[i], r.stat(i), P + o.gamma, tr->dc[i], Co, S, 1);
         else
-            KL(k_bn_bwd, (r.g1(B * Co * S)), BLK, md, tr->dc[i], Co, tr->c[i], stat(i), tr->red, P + o.gamma, tr->dc[i], Co, S, 1);
+            KL(r, k_bn_bwd, (r.g1(B * Co * S)), BLK, tr->dc[i], Co, tr->c[i], r.stat(i), tr->red, P + o.gamma, tr->dc[i], Co, S, 1);
         if (!enc_fz(i)) {
             r.reduce(R_SUM, Co, S, tr->dc[i], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
             const float *xin = i ? tr->e[i - 1] : tr->x0;
             const int64_t Pp = (int64_t)B * S;
             const int ns = wg_slabs(Pp);
             const int nw = 9 * Ci * Co;
-            KL(k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, md, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
-            KL(k_sum_slabs, (r.g1(nw)), BLK, md, tr->slab, S, 0, nw, G + o.k);
+            KL(r, k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
+            KL(r, k_sum_slabs, (r.g1(nw)), BLK, tr->slab, S, 0, nw, G + o.k);
         }
-        if (i > 0 && enc_live(i - 1)) KL(k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, md, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
+        if (i > 0 && enc_live(i - 1)) KL(r, k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
         if (!r.ok()) return r.rc;
     }
 
     // ---------------------------------------------------------------- Adam (lr_t per model in the table)
     if (fz)
-        KL(k_adam_plan, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
+        KL(r, k_adam_plan, (r.g1((int64_t)N_PARAMS)), BLK, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
                                                             tr->cfg.beta2, tr->cfg.eps);
     else
-        KL(k_adam, (r.g1((int64_t)N_PARAMS)), BLK, md, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
+        KL(r, k_adam, (r.g1((int64_t)N_PARAMS)), BLK, P, G, tr->adam_m, tr->adam_v, tr->trainable, (int)N_PARAMS, tr->cfg.beta1,
                                                        tr->cfg.beta2, tr->cfg.eps);
-    if (!r.ok()) return r.rc;
-    return COVAHIP_OK;
+    r.ok();
+    return r.rc;
 }
 
-// The inference-mode forward of one chunk of every model with a non-zero b in tr->h_tab (K > 1: already uploaded), then the
-// per-sample losses into d_sample_loss and TP / FP / FN added to d_counts.  Writes activations, stat, red and slab only, all of
-// which a training step rewrites before it reads them; never grads, parameters or Adam moments.
+// The inference-mode forward of one chunk, then the per-sample losses into d_sample_loss and TP / FP / FN added to d_counts.
+// Writes activations, stat, red and slab only, all of which a training step rewrites before it reads them; never grads,
+// parameters or Adam moments.
 int run_eval(covahip_train *tr, int B) {
-    Run r{tr, tr->ctx->stream, Mdl{tr->K > 1 ? tr->d_tab : nullptr, tr->cfg.max_batch, (int64_t)tr->slab_floats, tr->h_tab[0].b, 0.f}, B};
-    const hipStream_t s = r.s;
-    const Mdl md = r.md;
-    const float *P = tr->params;
-    const int H0 = tr->H[0], W0 = tr->W[0];
-    const DropS off{0, 0u, 1.f, 0};   // the identity (see k_eval_stat)
-    auto stat = [&](int layer) { return tr->stat + layer * 256; };
-    const EvalBN bn = bn_table(tr);
-    KL(k_eval_stat, (dim3(2 * NL - 1, 1, tr->K)), 128, md, P, tr->stat, bn, tr->cfg.bn_eps);
-    KL(k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, md, tr->d_stack, tr->x0, H0, W0);
-    for (int i = 0; i < NL; i++) {
-        const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
-        const EncOff &o = tr->eo[i];
-        const float *xin = i ? tr->e[i - 1] : tr->x0;
-        KL(k_conv3_fwd, (r.g1((int64_t)B * Co * TT * H * W)), BLK, md, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
-        KL(k_bn_pool, (r.g1((int64_t)B * Co * TT * Hp * Wp)), BLK, md, tr->c[i], stat(i), P + o.gamma, P + o.beta, tr->p[i], tr->arg[i],
-                                                                      Co, H, W, Hp, Wp);
-        const int zj = NL - 1 - i;
-        const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
-        KL(k_tmix_fwd, (r.g1((int64_t)B * Co * Hp * Wp)), BLK, md, tr->p[i], P + o.w1, P + o.w2, tr->e[i], tr->z[zj], DEC_CI[zj], c_off,
-                                                                 Co, (int64_t)Hp * Wp, off, off);
-        if (!r.ok()) return r.rc;
-    }
-    for (int j = 0; j < NL; j++) {
-        const int Ci = DEC_CI[j], Co = DEC_CO[j];
-        const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
-        const DecOff &o = tr->dof[j];
-        const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
-        KL(k_drop_relu, (r.g1(B * per)), BLK, md, tr->z[j], tr->zd[j], per, off);
-        KL(k_convT_fwd, (r.g1(B * Co * So)), BLK, md, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                      tr->cx[j]);
-        if (j < NL - 1)
-            KL(k_bn_apply, (r.g1(B * Co * So)), BLK, md, tr->y[j], stat(NL + j), P + o.gamma, P + o.beta, tr->z[j + 1], DEC_CI[j + 1],
-                                                         Co, So);
-        if (!r.ok()) return r.rc;
-    }
-    const int64_t hw = (int64_t)H0 * W0;
-    KL(k_final_fwd, (r.g1(B * hw)), BLK, md, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
-    r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, red_stride(tr->cfg.max_batch), nullptr, nullptr,
-             nullptr, nullptr);
-    KL(k_eval_tail, (r.g1(B * hw)), BLK, md, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
-    if (!r.ok()) return r.rc;
-    return COVAHIP_OK;
+    Run r(tr, B);
+    Fwd f{0x7Fu, false, {}};
+    for (DropS &d : f.drop) d = DropS{0, 0u, 1.f, 0};   // the identity (see k_bn_stat)
+    if (int rc = forward(r, f)) return rc;
+    const int64_t hw = (int64_t)tr->H[0] * tr->W[0];
+    KL(r, k_eval_tail, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
+    r.ok();
+    return r.rc;
 }
 
 // Adam's mask under a plan: 1 trained, 0 the BN moving statistics (never trained), 2 the tensors of a frozen group.
@@ -1274,9 +1258,8 @@ int check_blob(const void *cvhw, size_t cvhw_bytes) {
     if (cvhw_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
     uint32_t hdr[16];
     std::memcpy(hdr, cvhw, 64);
-    static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
     for (int i = 0; i < 13; i++)
-        if (hdr[i] != want[i]) return COVAHIP_ERR_BAD_WEIGHTS;
+        if (hdr[i] != W_HEADER[i]) return COVAHIP_ERR_BAD_WEIGHTS;
     if (cvhw_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
     return COVAHIP_OK;
 }
@@ -1372,6 +1355,26 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     return COVAHIP_OK;
 }
 
+// The per-model table of one pass: row k = model k's batch b[k] and its first sample in the packing; for a step (lrs not
+// null) also its Adam step size at its own t and its dropout keys, zeros otherwise.  Uploaded where the kernels read it (K > 1).
+int set_tab(covahip_train *tr, const int32_t *b, const float *lrs) {
+    int first = 0;
+    for (int k = 0; k < tr->K; k++) {
+        MStep &ms = tr->h_tab[k];
+        ms = MStep{};
+        ms.b = b[k];
+        ms.first = first;
+        first += b[k];
+        if (!lrs) continue;
+        const double t = (double)(tr->step[k] + 1);
+        ms.lr_t = (float)(lrs[k] * std::sqrt(1.0 - std::pow((double)tr->cfg.beta2, t)) / (1.0 - std::pow((double)tr->cfg.beta1, t)));
+        for (int site = 0; site < N_SITES; site++) ms.key[site] = drop_key(tr->seed[k], (uint64_t)tr->step[k], site);
+    }
+    if (tr->K > 1)
+        COVAHIP_CHECK_HIP(tr->ctx, hipMemcpyAsync(tr->d_tab, tr->h_tab, (size_t)tr->K * sizeof(MStep), hipMemcpyHostToDevice, tr->ctx->stream));
+    return COVAHIP_OK;
+}
+
 // The step of a set: batches / lrs / losses have K entries, the samples are packed in model order.
 int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int *batches, const float *lrs, float *losses,
               int mem_kind) {
@@ -1386,24 +1389,10 @@ int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     if (total == 0) return COVAHIP_ERR_INVALID_ARG;
     if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
-    int first = 0;
-    for (int k = 0; k < K; k++) {
-        MStep &ms = tr->h_tab[k];
-        ms.b = batches[k];
-        ms.first = first;
-        first += batches[k];
-        const double t = (double)(tr->step[k] + 1);
-        const double lr_t = lrs[k] * std::sqrt(1.0 - std::pow((double)tr->cfg.beta2, t)) / (1.0 - std::pow((double)tr->cfg.beta1, t));
-        ms.lr_t = (float)lr_t;
-        ms.pad = 0;
-        for (int site = 0; site < N_SITES; site++) ms.key[site] = drop_key(tr->seed[k], (uint64_t)tr->step[k], site);
-    }
+    if (int rc = enter(ctx)) return rc;
+    if (int rc = set_tab(tr, batches, lrs)) return rc;
     const size_t hw = (size_t)tr->H[0] * tr->W[0];
     const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    if (K > 1)
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_tab, tr->h_tab, (size_t)K * sizeof(MStep), hipMemcpyHostToDevice, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * TT * hw * 4, kind, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, kind, ctx->stream));
     if (int rc = run_step(tr, bmax)) return rc;
@@ -1439,8 +1428,7 @@ int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     if (total == 0 || total > INT32_MAX) return COVAHIP_ERR_INVALID_ARG;
     if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = enter(ctx)) return rc;
     const hipStream_t s = ctx->stream;
     const size_t hw = (size_t)tr->H[0] * tr->W[0], stack_b = TT * hw * 4;
     const bool host = mem_kind == COVAHIP_MEM_HOST;
@@ -1448,17 +1436,11 @@ int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     const hipMemcpyKind out_kind = host ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     const int nchunks = (cmax + mb - 1) / mb;
     std::vector<double> loss_sum(K, 0.0);
+    std::vector<int32_t> cb(K);   // the chunk's batch per model
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->d_counts, 0, (size_t)K * 3 * sizeof(unsigned long long), s));
     for (int c = 0; c < nchunks; c++) {
-        int first = 0, bmax = 0;
-        for (int k = 0; k < K; k++) {
-            MStep &ms = tr->h_tab[k];
-            std::memset(&ms, 0, sizeof ms);   // keys and lr_t: unused
-            ms.b = (int32_t)std::min<int64_t>(mb, std::max<int64_t>(0, (int64_t)counts[k] - (int64_t)c * mb));
-            ms.first = first;
-            first += ms.b;
-            bmax = std::max(bmax, ms.b);
-        }
+        for (int k = 0; k < K; k++) cb[k] = (int32_t)std::min<int64_t>(mb, std::max<int64_t>(0, (int64_t)counts[k] - (int64_t)c * mb));
+        if (int rc = set_tab(tr, cb.data(), nullptr)) return rc;   // keys and lr_t: unused
         if (nchunks == 1) {   // the caller's packing is the chunk's
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * stack_b, in_kind, s));
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, in_kind, s));
@@ -1472,8 +1454,7 @@ int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
                 COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt + (size_t)ms.first * hw, gt + src * hw, (size_t)ms.b * hw, in_kind, s));
             }
         }
-        if (K > 1) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_tab, tr->h_tab, (size_t)K * sizeof(MStep), hipMemcpyHostToDevice, s));
-        if (int rc = run_eval(tr, bmax)) return rc;
+        if (int rc = run_eval(tr, *std::max_element(cb.begin(), cb.end()))) return rc;
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_sample_loss, tr->d_sample_loss, (size_t)K * mb * sizeof(float), hipMemcpyDeviceToHost, s));
         for (int k = 0; k < K; k++) {
             const int b = tr->h_tab[k].b;
@@ -1554,8 +1535,7 @@ int covahip_train_create_set(covahip_ctx *ctx, const covahip_train_cfg *cfg, int
     if (int rc = validate_cfg(cfg)) return rc;
     for (int k = 0; k < n_models; k++)
         if (int rc = check_blob(weights[k], weights_bytes[k])) return rc;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = enter(ctx)) return rc;
     covahip_train *tr = new covahip_train();
     tr->ctx = ctx;
     tr->cfg = *cfg;
@@ -1610,10 +1590,8 @@ int covahip_train_weights_m(covahip_train *tr, int model, void *cvhw, size_t cap
     *n = need;
     if (!cvhw || cap < need) return COVAHIP_ERR_OVERFLOW;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
-    const uint32_t hdr[16] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS, 0, 0, 0};
-    std::memcpy(cvhw, hdr, 64);
+    if (int rc = enter(ctx)) return rc;
+    std::memcpy(cvhw, W_HEADER, 64);
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + 64, tr->params + (size_t)model * N_PARAMS,
                                           N_PARAMS * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1625,8 +1603,7 @@ int covahip_train_weights(covahip_train *tr, void *cvhw, size_t cap, size_t *n) 
 int covahip_train_grads_m(covahip_train *tr, int model, float *flat, size_t n) {
     if (!tr || !flat || n != N_PARAMS || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = enter(ctx)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(flat, tr->grads + (size_t)model * N_PARAMS, N_PARAMS * sizeof(float), hipMemcpyDeviceToHost,
                                           ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -1640,8 +1617,7 @@ int covahip_train_set_plan(covahip_train *tr, const covahip_train_plan *plan) {
     if ((plan->frozen_groups & ~0xFFu) || (plan->bn_inference & ~0x7Fu) || plan->frozen_groups == 0xFFu) return COVAHIP_ERR_INVALID_ARG;
     if (plan->frozen_groups != tr->frozen) {   // the mask is uploaded first: a failure leaves the plan as it was
         covahip_ctx *ctx = tr->ctx;
-        COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-        if (int rc = covahip_primary_op(ctx)) return rc;
+        if (int rc = enter(ctx)) return rc;
         const std::vector<uint8_t> m = plan_mask(tr, plan->frozen_groups);
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->trainable, m.data(), N_PARAMS, hipMemcpyHostToDevice, ctx->stream));
         COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // m leaves scope
@@ -1683,8 +1659,7 @@ int covahip_train_save_state(covahip_train *tr, uint64_t user_tag, void *buf, si
     *n = need;
     if (!buf || cap < need) return COVAHIP_ERR_OVERFLOW;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = enter(ctx)) return rc;
     uint8_t *p = static_cast<uint8_t *>(buf);
     const covahip_train_cfg &cf = tr->cfg;
     put<uint32_t>(p, 0, S_MAGIC);
@@ -1722,8 +1697,7 @@ int covahip_train_load_state(covahip_train *tr, const void *buf, size_t n, uint6
     for (int k = 0; k < tr->K; k++)
         if (get<uint64_t>(p, S_HEADER + (size_t)k * S_MODEL) > (uint64_t)INT64_MAX) return COVAHIP_ERR_BAD_DATA;
     covahip_ctx *ctx = tr->ctx;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = enter(ctx)) return rc;
     const size_t pb = N_PARAMS * sizeof(float);
     for (int k = 0; k < tr->K; k++) {
         const uint8_t *q = p + S_HEADER + (size_t)k * S_MODEL;

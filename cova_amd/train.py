@@ -3,8 +3,9 @@
   read_tfrecords  TFRecord files as `tfrecordsink` / covahip_tfrecord_example write them -> frames + labels
   slide           utils/data/slide.py slide_dataset(skip=True): non-overlapping stacks of T = 4 frames, newest first
   init_weights    the Keras default initialisation of the reference model, as a flat weight array (cova_amd/weights.py order)
-  Trainer         the training step on the GPU (covahip_train_*: forward, backward and Adam in HIP) and the epoch loop
-  TrainerSet      K models of one geometry in one trainer (covahip_train_create_set): one launch of each kernel per step of all
+  TrainerSet      K models of one geometry in one trainer (covahip_train_*: forward, backward and Adam in HIP, one launch of each
+                  kernel per step of all models) and the epoch loop
+  Trainer         one model: a TrainerSet of one
 
     python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
 
@@ -410,13 +411,6 @@ def _val_fields(ev: dict) -> dict:
     return {"val_" + k: ev[k] for k in ("loss", "precision", "recall", "iou")}
 
 
-def _val_text(rec: dict) -> str:
-    if "val_loss" not in rec:
-        return ""
-    return (f" val_loss {rec['val_loss']:.4f} val_precision {rec['val_precision']:.4f} val_recall {rec['val_recall']:.4f} "
-            f"val_iou {rec['val_iou']:.4f}")
-
-
 def _check_fit_args(val, keep):
     if keep not in ("last", "best"):
         raise ValueError(f"keep = {keep!r}: 'last' or 'best'")
@@ -436,7 +430,7 @@ _BEST_HEAD = struct.Struct("<4sI")
 
 
 class _State:
-    """Trainer state and best-epoch bookkeeping shared by Trainer and TrainerSet (both hold .handle, .ctx, ._lib)."""
+    """Trainer state and best-epoch bookkeeping of TrainerSet and Trainer (both hold .handle, .ctx, ._lib)."""
 
     def state_bytes(self, epoch: int = 0) -> bytes:
         """The whole trainer as one blob (weights, moving statistics, Adam moments, step counters, dropout seeds of every model);
@@ -508,172 +502,28 @@ class _State:
             self._best[k] = (struct.unpack_from("<d", data, o)[0], data[o + 8:o + per])
 
 
+def _eval_out(res, sl, lg) -> dict:
+    out = _eval_dict(res)
+    if sl is not None:
+        out["sample_loss"] = sl
+    if lg is not None:
+        out["logits"] = lg
+    return out
+
+
+def _epoch_text(ep: int, epochs: int, rec: dict, model=None) -> str:
+    """The log line of an epoch record; `model` tags the line of a set's model."""
+    val = "" if "val_loss" not in rec else (f" val_loss {rec['val_loss']:.4f} val_precision {rec['val_precision']:.4f} "
+                                            f"val_recall {rec['val_recall']:.4f} val_iou {rec['val_iou']:.4f}")
+    return (f"epoch {ep + 1}/{epochs}{'' if model is None else f' model {model}'}: loss {rec['loss']:.4f} "
+            f"precision {rec['precision']:.4f} recall {rec['recall']:.4f}{val} lr {rec['lr']:.3g}")
+
+
 # ------------------------------------------------------------------------------------------------ GPU trainer
-class Trainer(_State):
-    """BlobNet training on the GPU over covahip_train_*.  `step` counts the steps taken (the dropout hash's step)."""
-
-    def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, max_batch: int = 4, weights_flat: np.ndarray | None = None,
-                 seed: int = 0, dropout: float = 0.2, lr: float = 1e-3, freeze=(), bn_inference=()):
-        plan_bits(freeze, bn_inference)             # a bad plan raises before anything is created
-        self.ctx, self.h, self.w, self.max_batch = ctx, h_mb, w_mb, max_batch
-        self._lib = L.lib()
-        cfg = L.TrainCfg()
-        self._lib.covahip_train_default_cfg(C.byref(cfg))
-        cfg.h_mb, cfg.w_mb, cfg.max_batch, cfg.dropout, cfg.seed, cfg.lr = h_mb, w_mb, max_batch, dropout, seed, lr
-        self.cfg = cfg
-        if weights_flat is None:
-            weights_flat = init_weights(seed)
-        blob = W.to_bytes(weights_flat)
-        h = C.c_void_p()
-        L.check(self._lib.covahip_train_create(ctx.handle, C.byref(cfg), blob, len(blob), C.byref(h)), "covahip_train_create",
-                ctx.handle)
-        self.handle = h
-        self.step_count = 0
-        if freeze or bn_inference:
-            self.set_plan(freeze, bn_inference)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            if getattr(self.ctx, "handle", None):      # (a trainer outliving its closed ctx is not freed)
-                self._lib.covahip_train_destroy(self.handle)
-            self.handle = None
-
-    __del__ = close
-
-    def step(self, stack: np.ndarray, gt: np.ndarray, lr: float | None = None) -> float:
-        """One training step on stack u8 [B][4h][w][4] with labels u8 [B][h][w]; returns the loss before the update."""
-        stack = np.ascontiguousarray(stack, dtype=np.uint8)
-        gt = np.ascontiguousarray(gt, dtype=np.uint8)
-        b = stack.shape[0]
-        assert stack.shape == (b, W.T * self.h, self.w, 4) and gt.shape == (b, self.h, self.w), (stack.shape, gt.shape)
-        loss = C.c_float()
-        L.check(self._lib.covahip_train_step(self.handle, stack.ctypes.data, gt.ctypes.data, b, self.cfg.lr if lr is None else lr,
-                                             C.byref(loss), L.MEM_HOST), "covahip_train_step", self.ctx.handle)
-        self.step_count += 1
-        return float(loss.value)
-
-    def step_device(self, d_stack: int, d_gt: int, batch: int, lr: float | None = None) -> float:
-        """The same on device pointers (stack u8 [batch][4h][w][4], labels u8 [batch][h][w] on the ctx's GPU)."""
-        loss = C.c_float()
-        L.check(self._lib.covahip_train_step(self.handle, d_stack, d_gt, batch, self.cfg.lr if lr is None else lr, C.byref(loss),
-                                             L.MEM_DEVICE), "covahip_train_step", self.ctx.handle)
-        self.step_count += 1
-        return float(loss.value)
-
-    def metrics(self):
-        """(TP, FP, FN) of the last step at sigmoid > 0.5."""
-        v = (C.c_int64 * 3)()
-        L.check(self._lib.covahip_train_metrics(self.handle, v), "covahip_train_metrics")
-        return int(v[0]), int(v[1]), int(v[2])
-
-    def weights(self) -> np.ndarray:
-        """The current weights (moving statistics in the BN mean / var slots), flat."""
-        return W.from_bytes(self.weights_bytes())
-
-    def weights_bytes(self) -> bytes:
-        n = C.c_size_t()
-        self._lib.covahip_train_weights(self.handle, None, 0, C.byref(n))
-        buf = np.zeros(n.value, np.uint8)
-        L.check(self._lib.covahip_train_weights(self.handle, buf.ctypes.data, n.value, C.byref(n)), "covahip_train_weights",
-                self.ctx.handle)
-        return buf.tobytes()
-
-    def grads(self) -> np.ndarray:
-        """The last step's gradients, flat; BN mean / var slots = the batch mean / biased batch variance."""
-        out = np.empty(W.N_PARAMS, np.float32)
-        L.check(self._lib.covahip_train_grads(self.handle, out.ctypes.data, out.size), "covahip_train_grads", self.ctx.handle)
-        return out
-
-    def _set_step_counts(self, steps):
-        self.step_count = steps[0]
-
-    def evaluate(self, records, want_sample_loss: bool = False, want_logits: bool = False) -> dict:
-        """Scores the current weights on records = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]), any N >= 1, in inference mode
-        (moving BN statistics, no dropout); training does not notice.  {"loss", "precision", "recall", "iou", "samples"}: the mean
-        per-sample Jaccard distance and the micro-averaged metrics at sigmoid > 0.5; plus "sample_loss" f32 [N] / "logits"
-        f32 [N][h][w] when asked for."""
-        stack = np.ascontiguousarray(records[0], dtype=np.uint8)
-        gt = np.ascontiguousarray(records[1], dtype=np.uint8)
-        n = stack.shape[0]
-        if n == 0:
-            raise ValueError("no samples to evaluate")
-        assert stack.shape == (n, W.T * self.h, self.w, 4) and gt.shape == (n, self.h, self.w), (stack.shape, gt.shape)
-        sl = np.empty(n, np.float32) if want_sample_loss else None
-        lg = np.empty((n, self.h, self.w), np.float32) if want_logits else None
-        res = L.TrainEvalResult()
-        L.check(self._lib.covahip_train_eval(self.handle, stack.ctypes.data, gt.ctypes.data, n, None if sl is None else sl.ctypes.data,
-                                             None if lg is None else lg.ctypes.data, C.byref(res), L.MEM_HOST), "covahip_train_eval",
-                self.ctx.handle)
-        return self._eval_out(res, sl, lg)
-
-    def evaluate_device(self, d_stack: int, d_gt: int, n: int, d_sample_loss: int | None = None, d_logits: int | None = None) -> dict:
-        """The same on device pointers (the optional outputs are device buffers of n and n * h * w floats)."""
-        res = L.TrainEvalResult()
-        L.check(self._lib.covahip_train_eval(self.handle, d_stack, d_gt, n, d_sample_loss, d_logits, C.byref(res), L.MEM_DEVICE),
-                "covahip_train_eval", self.ctx.handle)
-        return _eval_dict(res)
-
-    @staticmethod
-    def _eval_out(res, sl, lg) -> dict:
-        out = _eval_dict(res)
-        if sl is not None:
-            out["sample_loss"] = sl
-        if lg is not None:
-            out["logits"] = lg
-        return out
-
-    def best_weights_bytes(self) -> bytes:
-        """The weight file of the epoch with the lowest val_loss of the last fit(keep="best")."""
-        if not getattr(self, "_best", None) or self._best[0] is None:
-            raise ValueError("no best epoch: run fit(..., val=..., keep='best') first")
-        return self._best[0][1]
-
-    def fit(self, records, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None, val=None, keep: str = "last",
-            checkpoint=None, start_epoch: int = 0):
-        """records = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]) (slide's output), in order, the last batch partial as in
-        Keras.  Per epoch: the sample-weighted mean loss and precision / recall at 0.5 of the training predictions.
-        val = (stacks, labels): every epoch record gains val_loss / val_precision / val_recall / val_iou (evaluate on val after
-        the epoch).  keep="best": best_weights_bytes() returns the weights of the epoch with the lowest val_loss (ties: the
-        earliest).  checkpoint=PATH: the trainer state is written there after every epoch (and the best epoch so far to
-        PATH.best); load_state(PATH) returns the epoch to pass as start_epoch, which continues the schedule and the numbering:
-        the history returned then starts at that epoch."""
-        _check_fit_args(val, keep)
-        stacks, labels = records
-        n = stacks.shape[0]
-        if n == 0:
-            raise ValueError("no training samples")
-        if not 1 <= batch <= self.max_batch:
-            raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
-        self._best_start(1, keep, checkpoint, start_epoch)
-        history = []
-        for ep in range(start_epoch, epochs):
-            lr = schedule(ep, self.cfg.lr) if schedule is keras_lr else schedule(ep)
-            tot = 0.0
-            tp = fp = fn = 0
-            for i in range(0, n, batch):
-                xb, yb = stacks[i:i + batch], labels[i:i + batch]
-                tot += self.step(xb, yb, lr) * xb.shape[0]
-                a, b_, c = self.metrics()
-                tp, fp, fn = tp + a, fp + b_, fn + c
-            rec = {"epoch": ep, "lr": lr, "loss": tot / n, "precision": tp / max(1, tp + fp), "recall": tp / max(1, tp + fn)}
-            if val is not None:
-                rec.update(_val_fields(self.evaluate(val)))
-                if keep == "best":
-                    self._best_update(0, rec["val_loss"], self.weights_bytes)
-            if checkpoint is not None:
-                self.save_state(checkpoint, epoch=ep + 1)
-                self._best_save(checkpoint)
-            history.append(rec)
-            if log:
-                log(f"epoch {ep + 1}/{epochs}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
-                    f"recall {rec['recall']:.4f}{_val_text(rec)} lr {lr:.3g}")
-        return history
-
-
 def set_epoch_plan(sizes, batch: int):
     """The steps of one epoch of a training set: a list of per-step lists [(start_k, count_k) for each model].  Model k walks
-    its sizes[k] samples in order in batches of `batch`, the last one partial, exactly as Trainer.fit does; once its epoch is
-    over it sits out the remaining steps with count 0.  The epoch has as many steps as the largest data set needs."""
+    its sizes[k] samples in order in batches of `batch`, the last one partial as in Keras; once its epoch is over it sits out
+    the remaining steps with count 0.  The epoch has as many steps as the largest data set needs."""
     if batch < 1:
         raise ValueError("batch must be at least 1")
     if not sizes or min(sizes) < 1:
@@ -687,11 +537,13 @@ class TrainerSet(_State):
     model in one launch of each kernel.  Model k is bit-identical to a Trainer made from the same weights and seed and fed
     model k's steps alone (include/covahip.h, "Training sets")."""
 
+    _tag_models = True      # fit's log lines name the model (a Trainer's set of one: they do not)
+
     def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, weights=None, n_models: int | None = None, seeds=None,
                  max_batch: int = 4, dropout: float = 0.2, lr: float = 1e-3, freeze=(), bn_inference=()):
         """weights: a list of flat weight arrays, one per model; or n_models with weights None: model k = init_weights(seeds[k]).
         seeds: the dropout seed per model (default 0, 1, ..).  freeze / bn_inference: the training plan (set_plan)."""
-        plan_bits(freeze, bn_inference)
+        plan_bits(freeze, bn_inference)             # a bad plan raises before anything is created
         if weights is None:
             if n_models is None:
                 raise ValueError("TrainerSet needs weights=[...] or n_models=K")
@@ -733,6 +585,23 @@ class TrainerSet(_State):
 
     __del__ = close
 
+    def _pack(self, pairs):
+        """(stack, gt, counts) of one (stacks u8 [n_k][4h][w][4], labels u8 [n_k][h][w]) pair per model, packed in model order;
+        a pair of None or of empty arrays counts 0."""
+        xs, ys, counts = [], [], []
+        for x, y in pairs:
+            n = 0 if x is None else len(x)
+            counts.append(n)
+            if n:
+                x = np.ascontiguousarray(x, dtype=np.uint8)
+                y = np.ascontiguousarray(y, dtype=np.uint8)
+                assert x.shape == (n, W.T * self.h, self.w, 4) and y.shape == (n, self.h, self.w), (x.shape, y.shape)
+                xs.append(x)
+                ys.append(y)
+        if len(xs) == 1:
+            return xs[0], ys[0], counts
+        return np.concatenate(xs or [np.empty(0, np.uint8)]), np.concatenate(ys or [np.empty(0, np.uint8)]), counts
+
     def _lrs(self, lrs):
         if lrs is None:
             lrs = self.cfg.lr
@@ -760,20 +629,9 @@ class TrainerSet(_State):
         the update (0 for a skipped model)."""
         if len(stacks_per_model) != self.n_models or len(labels_per_model) != self.n_models:
             raise ValueError(f"a step of this set takes {self.n_models} entries")
-        xs, ys, batches = [], [], []
-        for x, y in zip(stacks_per_model, labels_per_model):
-            b = 0 if x is None else len(x)
-            batches.append(b)
-            if b:
-                x = np.ascontiguousarray(x, dtype=np.uint8)
-                y = np.ascontiguousarray(y, dtype=np.uint8)
-                assert x.shape == (b, W.T * self.h, self.w, 4) and y.shape == (b, self.h, self.w), (x.shape, y.shape)
-                xs.append(x)
-                ys.append(y)
-        if not xs:
+        stack, gt, batches = self._pack(zip(stacks_per_model, labels_per_model))
+        if not any(batches):
             raise ValueError("a set step needs at least one model with samples")
-        stack = xs[0] if len(xs) == 1 else np.concatenate(xs)
-        gt = ys[0] if len(ys) == 1 else np.concatenate(ys)
         return self._step(stack.ctypes.data, gt.ctypes.data, batches, lrs, L.MEM_HOST)
 
     def step_device(self, d_stack: int, d_gt: int, batches, lrs=None):
@@ -787,6 +645,7 @@ class TrainerSet(_State):
         return int(v[0]), int(v[1]), int(v[2])
 
     def weights(self, k: int) -> np.ndarray:
+        """Model k's current weights (moving statistics in the BN mean / var slots), flat."""
         return W.from_bytes(self.weights_bytes(k))
 
     def weights_bytes(self, k: int) -> bytes:
@@ -800,6 +659,7 @@ class TrainerSet(_State):
         return buf.tobytes()
 
     def grads(self, k: int) -> np.ndarray:
+        """Model k's gradients of its last step, flat; BN mean / var slots = the batch mean / biased batch variance."""
         out = np.empty(W.N_PARAMS, np.float32)
         L.check(self._lib.covahip_train_grads_m(self.handle, k, out.ctypes.data, out.size), "covahip_train_grads_m", self.ctx.handle)
         return out
@@ -809,26 +669,17 @@ class TrainerSet(_State):
 
     def evaluate(self, records_per_model, want_sample_loss: bool = False, want_logits: bool = False):
         """Scores every model on its own samples in ONE call (one launch of each kernel per chunk of max_batch samples per
-        model): records_per_model[k] = (stacks, labels) of model k, any size; None or an empty entry = nothing for model k (its
-        dict holds zeros).  Returns one dict per model, as Trainer.evaluate's; model k's is bit-identical to Trainer.evaluate of
-        the same weights on the same samples."""
+        model), in inference mode (moving BN statistics, no dropout); training does not notice.  records_per_model[k] =
+        (stacks u8 [N_k][4h][w][4], labels u8 [N_k][h][w]) of model k, any size; None or an empty entry = nothing for model k
+        (its dict holds zeros).  Returns one dict per model, {"loss", "precision", "recall", "iou", "samples"}: the mean
+        per-sample Jaccard distance and the micro-averaged metrics at sigmoid > 0.5; plus "sample_loss" f32 [N_k] / "logits"
+        f32 [N_k][h][w] when asked for.  Model k's is bit-identical to its evaluation alone."""
         if len(records_per_model) != self.n_models:
             raise ValueError(f"{len(records_per_model)} data sets for {self.n_models} models")
-        xs, ys, counts = [], [], []
-        for r in records_per_model:
-            n = 0 if r is None else len(r[0])
-            counts.append(n)
-            if n:
-                x = np.ascontiguousarray(r[0], dtype=np.uint8)
-                y = np.ascontiguousarray(r[1], dtype=np.uint8)
-                assert x.shape == (n, W.T * self.h, self.w, 4) and y.shape == (n, self.h, self.w), (x.shape, y.shape)
-                xs.append(x)
-                ys.append(y)
-        if not xs:
-            raise ValueError("an evaluation needs at least one model with samples")
-        stack = xs[0] if len(xs) == 1 else np.concatenate(xs)
-        gt = ys[0] if len(ys) == 1 else np.concatenate(ys)
+        stack, gt, counts = self._pack((None, None) if r is None else r for r in records_per_model)
         total = sum(counts)
+        if not total:
+            raise ValueError("no samples to evaluate: an evaluation needs at least one model with samples")
         sl = np.empty(total, np.float32) if want_sample_loss else None
         lg = np.empty((total, self.h, self.w), np.float32) if want_logits else None
         cnt = np.ascontiguousarray(counts, dtype=np.int32)
@@ -838,7 +689,7 @@ class TrainerSet(_State):
                                                  L.MEM_HOST), "covahip_train_eval_set", self.ctx.handle)
         outs, at = [], 0
         for k, n in enumerate(counts):
-            outs.append(Trainer._eval_out(res[k], None if sl is None else sl[at:at + n], None if lg is None else lg[at:at + n]))
+            outs.append(_eval_out(res[k], None if sl is None else sl[at:at + n], None if lg is None else lg[at:at + n]))
             at += n
         return outs
 
@@ -861,10 +712,15 @@ class TrainerSet(_State):
 
     def fit(self, records_per_model, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None, val=None, keep: str = "last",
             checkpoint=None, start_epoch: int = 0):
-        """records_per_model[k] = (stacks, labels) of model k, as Trainer.fit takes them.  Every model walks its own data set in
-        order (set_epoch_plan); a model whose epoch is shorter sits out the rest of it.  Returns one history per model, each as
-        Trainer.fit's; model k's weights afterwards are those of Trainer.fit on records_per_model[k] alone, bit for bit.
-        val (one (stacks, labels) per model), keep, checkpoint and start_epoch as Trainer.fit; the best epoch is per model."""
+        """records_per_model[k] = (stacks u8 [N][4h][w][4], labels u8 [N][h][w]) of model k (slide's output).  Every model walks
+        its own data set in order (set_epoch_plan), the last batch partial as in Keras; a model whose epoch is shorter sits out
+        the rest of it.  Returns one history per model: per epoch the sample-weighted mean loss and precision / recall at 0.5 of
+        the training predictions.  Model k's weights afterwards are those of a fit on records_per_model[k] alone, bit for bit.
+        val = one (stacks, labels) per model: every epoch record gains val_loss / val_precision / val_recall / val_iou (evaluate
+        on val after the epoch).  keep="best": best_weights_bytes(k) returns model k's weights of its epoch with the lowest
+        val_loss (ties: the earliest).  checkpoint=PATH: the trainer state is written there after every epoch (and the best
+        epochs so far to PATH.best); load_state(PATH) returns the epoch to pass as start_epoch, which continues the schedule and
+        the numbering: the histories returned then start at that epoch."""
         _check_fit_args(val, keep)
         if len(records_per_model) != self.n_models:
             raise ValueError(f"{len(records_per_model)} data sets for {self.n_models} models")
@@ -902,12 +758,76 @@ class TrainerSet(_State):
                         self._best_update(k, rec["val_loss"], functools.partial(self.weights_bytes, k))
                 histories[k].append(rec)
                 if log:
-                    log(f"epoch {ep + 1}/{epochs} model {k}: loss {rec['loss']:.4f} precision {rec['precision']:.4f} "
-                        f"recall {rec['recall']:.4f}{_val_text(rec)} lr {lr:.3g}")
+                    log(_epoch_text(ep, epochs, rec, k if self._tag_models else None))
             if checkpoint is not None:
                 self.save_state(checkpoint, epoch=ep + 1)
                 self._best_save(checkpoint)
         return histories
+
+
+class Trainer(_State):
+    """One BlobNet trained on the GPU: a TrainerSet of one model, with its lists of one unwrapped.  `step_count` counts the
+    steps taken (the dropout hash's step)."""
+
+    def __init__(self, ctx, h_mb: int = 45, w_mb: int = 80, max_batch: int = 4, weights_flat: np.ndarray | None = None,
+                 seed: int = 0, dropout: float = 0.2, lr: float = 1e-3, freeze=(), bn_inference=()):
+        self._set = s = TrainerSet(ctx, h_mb, w_mb, [init_weights(seed) if weights_flat is None else weights_flat], seeds=[seed],
+                                   max_batch=max_batch, dropout=dropout, lr=lr, freeze=freeze, bn_inference=bn_inference)
+        s._tag_models = False
+        self.ctx, self.h, self.w, self.max_batch, self.cfg, self._lib = ctx, h_mb, w_mb, max_batch, s.cfg, s._lib
+
+    handle = property(lambda self: self._set.handle)
+    step_count = property(lambda self: self._set.step_counts[0])
+
+    def close(self):
+        if getattr(self, "_set", None):
+            self._set.close()
+
+    __del__ = close
+
+    def _set_step_counts(self, steps):
+        self._set._set_step_counts(steps)
+
+    def step(self, stack: np.ndarray, gt: np.ndarray, lr: float | None = None) -> float:
+        """One training step on stack u8 [B][4h][w][4] with labels u8 [B][h][w]; returns the loss before the update."""
+        stack, gt, batches = self._set._pack([(stack, gt)])
+        return self._set._step(stack.ctypes.data, gt.ctypes.data, batches, lr, L.MEM_HOST)[0]
+
+    def step_device(self, d_stack: int, d_gt: int, batch: int, lr: float | None = None) -> float:
+        """The same on device pointers (stack u8 [batch][4h][w][4], labels u8 [batch][h][w] on the ctx's GPU)."""
+        return self._set.step_device(d_stack, d_gt, [batch], lr)[0]
+
+    def metrics(self):
+        """(TP, FP, FN) of the last step at sigmoid > 0.5."""
+        return self._set.metrics(0)
+
+    def weights(self) -> np.ndarray:
+        """The current weights (moving statistics in the BN mean / var slots), flat."""
+        return self._set.weights(0)
+
+    def weights_bytes(self) -> bytes:
+        return self._set.weights_bytes(0)
+
+    def grads(self) -> np.ndarray:
+        """The last step's gradients, flat; BN mean / var slots = the batch mean / biased batch variance."""
+        return self._set.grads(0)
+
+    def evaluate(self, records, want_sample_loss: bool = False, want_logits: bool = False) -> dict:
+        """TrainerSet.evaluate of records = (stacks, labels), any N >= 1: the one dict."""
+        return self._set.evaluate([records], want_sample_loss, want_logits)[0]
+
+    def evaluate_device(self, d_stack: int, d_gt: int, n: int, d_sample_loss: int | None = None, d_logits: int | None = None) -> dict:
+        """The same on device pointers (the optional outputs are device buffers of n and n * h * w floats)."""
+        return self._set.evaluate_device(d_stack, d_gt, [n], d_sample_loss, d_logits)[0]
+
+    def best_weights_bytes(self) -> bytes:
+        """The weight file of the epoch with the lowest val_loss of the last fit(keep="best")."""
+        return self._set.best_weights_bytes(0)
+
+    def fit(self, records, epochs: int = 20, batch: int = 4, schedule=keras_lr, log=None, val=None, keep: str = "last",
+            checkpoint=None, start_epoch: int = 0):
+        """TrainerSet.fit of records = (stacks, labels) and val = (stacks, labels) or None: the one history."""
+        return self._set.fit([records], epochs, batch, schedule, log, None if val is None else [val], keep, checkpoint, start_epoch)[0]
 
 
 def parse_args(argv=None):

@@ -2,6 +2,7 @@
 in f64 over the case matrix of tests/torch_blobnet_train.py (bounds there, shown not vacuous by tests/test_train_bounds.py),
 partial batches bit for bit, a batch of 320 through the capped reduction plans, steps on device memory, optimiser state,
 determinism, learning on labelled synthetic streams, export into the fp16 inference path, and the record -> train -> infer loop."""
+import ctypes as C
 import os
 import subprocess
 import sys
@@ -9,7 +10,7 @@ import sys
 import numpy as np
 import pytest
 
-from cova_amd import synth, train as T, weights as W
+from cova_amd import _lib as L, synth, train as T, weights as W
 from cova_amd.elements import BlobNetInfer, Context, tfrecord_example
 from tests import torch_blobnet as TB
 from tests import torch_blobnet_train as TT
@@ -173,6 +174,45 @@ def test_device_memory_step_is_bit_identical(ctx):
     for (lh, mh, gh), (ld, md, gd) in zip(rh, rd):
         assert lh == ld and mh == md and (gh == gd).all()
     assert (wh == wd).all()
+
+
+def test_solo_abi_matches_trainer(ctx):
+    """covahip_train_create / _step / _metrics / _weights / _grads driven through ctypes (the Python Trainer is a set of one and
+    no longer calls them): loss, metrics, gradients and weights equal the Trainer's bit for bit after every step, the last one
+    a partial batch."""
+    h, w, mb, seed, lr = 16, 16, 2, 5, 1e-3
+    flat = T.init_weights(12)
+    lib = L.lib()
+    cfg = L.TrainCfg()
+    lib.covahip_train_default_cfg(C.byref(cfg))
+    cfg.h_mb, cfg.w_mb, cfg.max_batch, cfg.seed = h, w, mb, seed
+    blob = W.to_bytes(flat)
+    hd = C.c_void_p()
+    L.check(lib.covahip_train_create(ctx.handle, C.byref(cfg), blob, len(blob), C.byref(hd)), "covahip_train_create", ctx.handle)
+    tr = T.Trainer(ctx, h, w, max_batch=mb, weights_flat=flat, seed=seed)
+    try:
+        assert (tr.cfg.dropout, tr.cfg.lr) == (cfg.dropout, cfg.lr)
+        for k, b in enumerate((2, 2, 1)):
+            s, g = TT.sample_batch(h, w, b, 70 + k)
+            loss = C.c_float()
+            L.check(lib.covahip_train_step(hd, s.ctypes.data, g.ctypes.data, b, lr, C.byref(loss), L.MEM_HOST), "covahip_train_step",
+                    ctx.handle)
+            assert np.float32(loss.value).view(np.uint32) == np.float32(tr.step(s, g, lr=lr)).view(np.uint32), k
+            m = (C.c_int64 * 3)()
+            L.check(lib.covahip_train_metrics(hd, m), "covahip_train_metrics")
+            assert tuple(m) == tr.metrics(), k
+            gr = np.empty(W.N_PARAMS, np.float32)
+            L.check(lib.covahip_train_grads(hd, gr.ctypes.data, gr.size), "covahip_train_grads", ctx.handle)
+            assert (gr.view(np.uint32) == tr.grads().view(np.uint32)).all(), k
+            n = C.c_size_t()
+            assert lib.covahip_train_weights(hd, None, 0, C.byref(n)) == 7 and n.value == len(blob)   # the size query
+            buf = np.zeros(n.value, np.uint8)
+            L.check(lib.covahip_train_weights(hd, buf.ctypes.data, n.value, C.byref(n)), "covahip_train_weights", ctx.handle)
+            assert buf.tobytes() == tr.weights_bytes(), k
+        assert not (tr.weights().view(np.uint32) == flat.view(np.uint32)).all()       # (the weights moved)
+    finally:
+        tr.close()
+        lib.covahip_train_destroy(hd)
 
 
 def test_optimiser_state_after_three_steps(ctx):

@@ -1,7 +1,8 @@
 """Training sets (covahip_train_create_set / _step_set, cova_amd.train.TrainerSet): model k of a set is bit-identical to the
-same model trained alone.  Solo trainers made with covahip_train_create are the reference throughout and every comparison is
-np.array_equal on the float bits, never a tolerance -- but for one check of a non-zero model index against float64 autograd,
-so that the set does not rest on equality alone."""
+same model trained alone.  Solo trainers (cova_amd.train.Trainer: covahip_train_create_set with one model and the seed given,
+which is the trainer covahip_train_create makes -- K = 1, the kernels' solo instantiation; tests/test_gpu_train.py holds the
+two equal) are the reference throughout and every comparison is np.array_equal on the float bits, never a tolerance -- but for
+one check of a non-zero model index against float64 autograd, so that the set does not rest on equality alone."""
 import ctypes as C
 import os
 import subprocess
@@ -38,7 +39,7 @@ def _loss_bits(x):
 
 
 class _Solo:
-    """Model k's reference: a covahip_train_create trainer fed the steps in which k had a batch."""
+    """Model k's reference: a solo Trainer fed the steps in which k had a batch."""
 
     def __init__(self, ctx, h, w, flat, seed, max_batch, p):
         self.tr = T.Trainer(ctx, h, w, max_batch=max_batch, weights_flat=flat, seed=seed, dropout=p)
