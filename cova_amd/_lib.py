@@ -87,6 +87,20 @@ class BlobNetPost(C.Structure):
     _fields_ = [("logit_thresh", C.c_float), ("keep", C.c_void_p)]
 
 
+class SweepCfg(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_thresh", C.c_int32), ("logit_thresh", C.c_void_p), ("n_area", C.c_int32),
+                ("area_thresh", C.c_void_p), ("gt_area_thresh", C.c_int32), ("iou_num", C.c_int32), ("iou_den", C.c_int32),
+                ("max_boxes", C.c_int32), ("keep", C.c_void_p), ("chunk", C.c_int32)]
+
+
+class SweepCell(C.Structure):
+    _fields_ = [("pred", C.c_int64), ("pred_true", C.c_int64), ("gt_found", C.c_int64)]
+
+
+class SweepResult(C.Structure):
+    _fields_ = [("samples", C.c_int64), ("gt_objects", C.c_int64), ("gt_truncated", C.c_int64)]
+
+
 class MogCfg(C.Structure):
     _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
                 ("var_threshold", C.c_float)]
@@ -219,6 +233,7 @@ PROTOTYPES = {
     "covahip_train_set_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
     "covahip_train_get_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
     "covahip_train_destroy": (None, [_P]),
+    "covahip_post_sweep": (C.c_int, [_P, C.POINTER(SweepCfg), _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(SweepResult)]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),

@@ -101,6 +101,7 @@ void covahip_ctx_destroy(covahip_ctx *ctx) {
     }
     if (ctx->stage_in) hipFree(ctx->stage_in);
     if (ctx->stage_out) hipFree(ctx->stage_out);
+    if (ctx->sweep_buf) hipFree(ctx->sweep_buf);
     for (CtxLane &l : ctx->lanes) {
         if (l.cc_scratch) hipFree(l.cc_scratch);
         if (l.cc_ovf) hipFree(l.cc_ovf);

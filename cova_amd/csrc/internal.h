@@ -78,6 +78,8 @@ struct covahip_ctx {
     size_t stage_out_bytes = 0;
     void *pinned = nullptr;
     size_t pinned_bytes = 0;
+    void *sweep_buf = nullptr;   // covahip_post_sweep: accumulators, keep map, one chunk's mask frames, boxes and counts
+    size_t sweep_bytes = 0;
     int cc_wave_cap = 0;       // bboxcc wave kernel: developer override of its run capacity
     int tail_form = 0;         // which kernel ran the last decoder block of the last forward (covahip_dev_blobnet_tail_form)
     CtxLane &lane() { return lanes[cur_lane]; }

@@ -187,6 +187,55 @@ int covahip_blobnet_set_post(covahip_ctx *ctx, int model, const covahip_blobnet_
 /* The settings of a model.  logit_thresh, keep_or_null (u8 [h_mb][w_mb], written as 0 / 1; all 1 without a keep map)
  * and has_keep (1 when a keep map is set) may each be NULL.                                                         */
 int covahip_blobnet_get_post(covahip_ctx *ctx, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_keep);
+/* Calibration: which logit_thresh (covahip_blobnet_set_post) and which area threshold (the cc-threshold of bboxcc / cova) to
+ * set for a camera.  covahip_post_sweep scores logits against labels (the MoG labels of a held-out set) at n_thresh mask
+ * thresholds x n_area area thresholds in one pass on the GPU: pixel counts per threshold, and per cell the boxes serving would
+ * emit, how many of them hit a labelled object and how many labelled objects they find.  It has no model: it scores whatever
+ * forward produced the logits (python -m cova_amd.calibrate feeds it the deployed fp16 path).  Every quantity is an integer
+ * count, so the result is exact.  Rules:
+ *   keep'[y,x] = keep ? keep[y,x] != 0 : 1
+ *   mask_t     = (logit > logit_thresh[t]) & keep'     -- the expression of covahip_blobnet_set_post; NaN is background
+ *   gt'        = (gt != 0) & keep'                     -- a labelled object inside the ignore region is neither a miss nor a hit
+ *   pixel[t]   = tp |mask_t & gt'|, fp |mask_t & ~gt'|, fn |~mask_t & gt'|, over all samples
+ *   G          = regionprops(gt', gt_area_thresh), P[t][a] = regionprops(mask_t, area_thresh[a]): covahip_bboxcc semantics
+ *                (8-connected components in OpenCV label order, area_px >= the threshold).  regionprops(mask, a) is
+ *                regionprops(mask, area_thresh[0]) with the boxes of area_px < a dropped, order kept: one labelling per
+ *                (sample, threshold) serves every area.  Only the first max_boxes boxes of a frame take part -- of that
+ *                labelling at area_thresh[0] for predictions, of G for labels; a frame with more is counted in truncated[t] /
+ *                gt_truncated, and the boxes beyond are as if they did not exist (gt_objects counts the label boxes that take part).
+ *   hit(p, g)  = inter > 0 && inter * iou_den >= iou_num * (area_box(p) + area_box(g) - inter), in 64-bit integers, with
+ *                area_box = width * height of the box and inter the area of the boxes' intersection
+ *   cells[t][a]: pred = |P[t][a]|, pred_true = the p in P[t][a] that hit some g in G, gt_found = the g in G that hit some p in
+ *                P[t][a]; gt_objects = sum |G|.  There is no assignment, so there are no ties to break.
+ *   Additivity: the counts of n samples equal the sums of the counts of any partition of them into calls, and do not depend on
+ *   chunk.
+ * Errors, all checked on the host before the GPU is touched: COVAHIP_ERR_INVALID_ARG for a NULL pointer (keep may be NULL;
+ * logits / gt may be NULL when n == 0), a non-finite or not strictly ascending list, a count outside its range, iou_num < 1 or
+ * > iou_den, h or w < 1, n < 0, chunk < 0, another mem_kind; COVAHIP_ERR_UNSUPPORTED for w > 256 (covahip_bboxcc's limit) or
+ * h > 16384.  n == 0 is COVAHIP_OK with zeros.
+ * Runs on the primary stream behind all lanes, like stand-alone covahip_bboxcc; its scratch belongs to the ctx.  It changes no
+ * model, no setting and no result of any forward. */
+typedef struct covahip_sweep_cfg {
+    int32_t h, w;                    /* grid; the limits of covahip_bboxcc (w <= 256) */
+    int32_t n_thresh;                /* 1..64 */
+    const float *logit_thresh;       /* HOST [n_thresh], finite, strictly ascending */
+    int32_t n_area;                  /* 1..16 */
+    const int32_t *area_thresh;      /* HOST [n_area], >= 1, strictly ascending: cc-threshold candidates */
+    int32_t gt_area_thresh;          /* >= 1: a label component is an object when it has at least this many macroblocks */
+    int32_t iou_num, iou_den;        /* 1 <= iou_num <= iou_den: the hit rule's IoU as an exact fraction */
+    int32_t max_boxes;               /* 1..1024 boxes kept per frame (see "truncated") */
+    const uint8_t *keep;             /* HOST u8 [h][w], non-zero = scored; NULL = all (set_post's keep map) */
+    int32_t chunk;                   /* samples per internal pass; 0 = chosen by the library */
+} covahip_sweep_cfg;
+typedef struct covahip_sweep_cell { int64_t pred, pred_true, gt_found; } covahip_sweep_cell;
+typedef struct covahip_sweep_result {
+    int64_t samples, gt_objects, gt_truncated;   /* gt_truncated: samples whose label had more than max_boxes objects */
+} covahip_sweep_result;
+/* logits f32 [n][h][w], gt u8 [n][h][w] (mem_kind applies to both; outputs are HOST).  pixel: i64 [n_thresh][3] = tp, fp, fn;
+ * cells: [n_thresh][n_area]; truncated: i64 [n_thresh] = frames (sample, threshold) with more than max_boxes components.
+ * Synchronous.  Outputs are OVERWRITTEN with this call's counts; the caller adds calls up. */
+int covahip_post_sweep(covahip_ctx *ctx, const covahip_sweep_cfg *cfg, const float *logits, const uint8_t *gt, int n,
+                       int mem_kind, int64_t *pixel, covahip_sweep_cell *cells, int64_t *truncated, covahip_sweep_result *out);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc
