@@ -183,6 +183,9 @@ PROTOTYPES = {
     "covahip_blobnet_num_models": (C.c_int, [_P, _P]),
     "covahip_blobnet_set_post": (C.c_int, [_P, C.c_int, C.POINTER(BlobNetPost)]),
     "covahip_blobnet_get_post": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P, C.POINTER(C.c_int)]),
+    "covahip_blobnet_set_area": (C.c_int, [_P, C.c_int, C.c_int]),
+    "covahip_blobnet_get_area": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "covahip_bboxcc_v": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_int]),
     "covahip_pipe_model_ids": (C.c_int, [_P, C.c_int, _P]),
     "covahip_blobnet_forward_m": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_filter_forward_m": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, C.c_int, _P, _P, C.c_int]),

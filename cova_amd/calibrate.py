@@ -158,8 +158,9 @@ def save_post(path, choice: dict, ignore_rects=()) -> None:
 
 
 def load_post(path, h_mb: int, w_mb: int):
-    """-> (set_post_kwargs, cc_threshold): net.set_post(model, **set_post_kwargs), then filter(..., cc_threshold).  The keep map
-    is rebuilt from the sidecar's rectangles with keep_from_rects (None when it has none)."""
+    """-> (set_post_kwargs, cc_threshold): net.set_post(model, **set_post_kwargs) and net.set_area(model, cc_threshold) -- what
+    apply_post does -- or filter(..., cc_threshold) for a net that serves one camera.  The keep map is rebuilt from the sidecar's
+    rectangles with keep_from_rects (None when it has none)."""
     with open(path) as f:
         doc = json.load(f)
     if doc.get("format") != "covahip-post-1":
@@ -167,6 +168,23 @@ def load_post(path, h_mb: int, w_mb: int):
     rects = [tuple(r) for r in doc.get("ignore_rects", [])]
     kw = {"logit_thresh": float(np.float32(doc["logit_thresh"])), "keep": keep_from_rects(h_mb, w_mb, rects) if rects else None}
     return kw, int(doc["cc_threshold"])
+
+
+def apply_post(net, model: int, path_or_doc) -> int:
+    """Serves `model` of net (a BlobNetInfer) as calibrated: set_post(mask threshold, ignore region) and set_area(cc_threshold)
+    from a sidecar file, or from (set_post_kwargs, cc_threshold) as load_post returns it.  -> the cc_threshold applied."""
+    kw, cc = load_post(path_or_doc, net.h, net.w) if isinstance(path_or_doc, (str, bytes)) or hasattr(path_or_doc, "__fspath__") else path_or_doc
+    net.set_post(model, **kw)
+    net.set_area(model, int(cc))
+    return int(cc)
+
+
+def serving_hint(logit_thresh: float, cc_threshold: int, ignore_rects=()) -> str:
+    """The element properties that serve a calibrated camera: on a pad of a blobnetfilter model set, and as the whole element's."""
+    prob = 1.0 / (1.0 + float(np.exp(-np.float64(logit_thresh))))   # the element takes the threshold as a probability
+    rects = "+".join(",".join(str(v) for v in r) for r in ignore_rects)
+    return (f"blobnetfilter pad-mask-threshold=\"IDX={prob:.9g}\"" + (f" pad-ignore-rects=\"IDX={rects}\"" if rects else "") +
+            f" pad-cc-threshold=\"IDX={int(cc_threshold)}\"   cova / bboxcc cc-threshold={int(cc_threshold)}")
 
 
 def format_table(result: dict) -> str:
@@ -266,10 +284,8 @@ def main(argv=None) -> int:
           f"pred {ch['pred']} truncated {ch['truncated']}" + ("" if ch["met"] else f"  (no cell reaches recall {a.min_recall})"))
     rects = ";".join(",".join(str(v) for v in r) for r in a.ignore_rects)
     print(f"set_post(model, logit_thresh={ch['logit_thresh']!r}" + (f", keep=keep_from_rects({a.h_mb}, {a.w_mb}, {list(a.ignore_rects)!r})" if rects else "") + ")")
-    prob = 1.0 / (1.0 + float(np.exp(-np.float64(ch["logit_thresh"]))))   # the element takes the threshold as a probability
-    rects = "+".join(",".join(str(v) for v in r) for r in a.ignore_rects)
-    print(f"blobnetfilter pad-mask-threshold=\"IDX={prob:.9g}\"" + (f" pad-ignore-rects=\"IDX={rects}\"" if rects else "") +
-          f"   cova / bboxcc cc-threshold={ch['cc_threshold']}")
+    print(f"set_area(model, {ch['cc_threshold']})")
+    print(serving_hint(ch["logit_thresh"], ch["cc_threshold"], a.ignore_rects))
     if a.output:
         save_post(a.output, ch, a.ignore_rects)
         print(f"wrote {a.output}")

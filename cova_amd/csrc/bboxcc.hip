@@ -38,6 +38,12 @@ namespace {
 
 using namespace ccbody;
 
+// The area threshold of a frame: its own where the call has one per frame (area_v: covahip_bboxcc_v, per-model thresholds behind
+// a forward), else the call's.  Always indexed by the FRAME, also where a kernel takes its frames from a list.
+__device__ __forceinline__ int frame_area(const int32_t *__restrict__ area_v, int frame, int area_thresh) {
+    return area_v ? area_v[frame] : area_thresh;
+}
+
 // ---- one 1,024-thread workgroup per frame (any shape that fits LDS; also the overflow pass of the wave kernel)
 // list == nullptr: frame = blockIdx.x.  Otherwise the launch is persistent over the *n_list frame indices in list.
 // wg.cap > 0: the run-based body (bboxcc_wave.h, frame_wg) with worst-case capacity; else the block-based body.
@@ -47,7 +53,8 @@ __global__ __launch_bounds__(CC_THREADS) void bboxcc_kernel(const uint8_t *__res
                                                              const int32_t *__restrict__ list,
                                                              const int32_t *__restrict__ n_list,
                                                              const int32_t *__restrict__ stat_src, int32_t *__restrict__ stat_dst,
-                                                             int stat_batch, int stat_cap) {
+                                                             int stat_batch, int stat_cap,
+                                                             const int32_t *__restrict__ area_v) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     // last launch of a large-batch call: the call's overflow counters (final: the launches before this one are complete) go to
     // pinned host words that the NEXT call's plan reads -- no copy, no event, no host synchronisation
@@ -55,10 +62,11 @@ __global__ __launch_bounds__(CC_THREADS) void bboxcc_kernel(const uint8_t *__res
         stat_dst[threadIdx.x] = threadIdx.x < 5 ? stat_src[threadIdx.x] : threadIdx.x == 5 ? stat_batch : threadIdx.x == 6 ? stat_cap : 0;
     auto one = [&](int frame) {
         const uint8_t *m = masks + (size_t)frame * g.H * g.W;
+        const int area = frame_area(area_v, frame, area_thresh);
         if (wg.cap > 0)
-            ccwave::frame_wg<CC_THREADS>(m, smem, wg, area_thresh, boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, threadIdx.x);
+            ccwave::frame_wg<CC_THREADS>(m, smem, wg, area, boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, threadIdx.x);
         else
-            bboxcc_frame(m, smem, g, area_thresh, boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, threadIdx.x);
+            bboxcc_frame(m, smem, g, area, boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, threadIdx.x);
     };
     if (!list) {
         one(blockIdx.x);
@@ -76,10 +84,10 @@ __global__ __launch_bounds__(CC_THREADS) void bboxcc_kernel(const uint8_t *__res
 __global__ __launch_bounds__(CC_THREADS) void bboxcc_big_kernel(const uint8_t *__restrict__ masks, CcGeom g, uint8_t *slabs,
                                                                  size_t slab_bytes, int batch, int area_thresh,
                                                                  covahip_box *__restrict__ boxes, int32_t *__restrict__ counts,
-                                                                 int max_boxes) {
+                                                                 int max_boxes, const int32_t *__restrict__ area_v) {
     uint8_t *const slab = slabs + (size_t)blockIdx.x * slab_bytes;
     for (int frame = blockIdx.x; frame < batch; frame += gridDim.x) {
-        bboxcc_frame(masks + (size_t)frame * g.H * g.W, slab, g, area_thresh, boxes + (size_t)frame * max_boxes, counts + frame,
+        bboxcc_frame(masks + (size_t)frame * g.H * g.W, slab, g, frame_area(area_v, frame, area_thresh), boxes + (size_t)frame * max_boxes, counts + frame,
                      max_boxes, threadIdx.x);
         __syncthreads();   // the next frame reuses the slab
     }
@@ -100,7 +108,8 @@ __global__ __launch_bounds__(WV_WAVES * 64, LIST ? 1 : 8) void bboxcc_wave_kerne
                                                                     const int32_t *__restrict__ list, const int32_t *__restrict__ n_list,
                                                                     int32_t *__restrict__ ovf_list, int32_t *__restrict__ ovf_n,
                                                                     int base_cap, int32_t *__restrict__ n_big,
-                                                                    int32_t *__restrict__ zero_next) {
+                                                                    int32_t *__restrict__ zero_next,
+                                                                    const int32_t *__restrict__ area_v) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     uint8_t *const sm = smem + (size_t)wave * g.wave_bytes;
@@ -109,8 +118,8 @@ __global__ __launch_bounds__(WV_WAVES * 64, LIST ? 1 : 8) void bboxcc_wave_kerne
         if (zero_next && blockIdx.x == 0 && threadIdx.x < 8) zero_next[threadIdx.x] = 0;
         const int frame = blockIdx.x * WV_WAVES + wave;
         if (frame >= batch) return;
-        const int n = ccwave::frame_wave(masks + (size_t)frame * g.H * g.W, sm, g, area_thresh, boxes + (size_t)frame * max_boxes,
-                                         counts + frame, max_boxes, lane);
+        const int n = ccwave::frame_wave(masks + (size_t)frame * g.H * g.W, sm, g, frame_area(area_v, frame, area_thresh),
+                                         boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, lane);
         if (lane == 0) {
             if (n > g.cap) {   // more runs than the LDS region holds
                 // (the index is clamped to the list's capacity: a counter set that was NOT zero at the start of the call -- a failed
@@ -127,8 +136,8 @@ __global__ __launch_bounds__(WV_WAVES * 64, LIST ? 1 : 8) void bboxcc_wave_kerne
         const int nl = min(*n_list, batch);
         for (int k = blockIdx.x * WV_WAVES + wave; k < nl; k += gridDim.x * WV_WAVES) {
             const int frame = list[k];
-            const int n = ccwave::frame_wave(masks + (size_t)frame * g.H * g.W, sm, g, area_thresh, boxes + (size_t)frame * max_boxes,
-                                             counts + frame, max_boxes, lane);
+            const int n = ccwave::frame_wave(masks + (size_t)frame * g.H * g.W, sm, g, frame_area(area_v, frame, area_thresh),
+                                             boxes + (size_t)frame * max_boxes, counts + frame, max_boxes, lane);
             if (lane == 0 && n > g.cap) {
                 const int k2 = atomicAdd(ovf_n, 1);
                 if (k2 < batch) ovf_list[k2] = frame;
@@ -171,7 +180,7 @@ int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
 // Everything else runs the workgroup-per-frame kernel.
 constexpr int WAVE_CAP = 128;
 int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, int h, int w, int area_thresh,
-                          covahip_box *d_boxes, int32_t *d_counts, int max_boxes) {
+                          covahip_box *d_boxes, int32_t *d_counts, int max_boxes, const int32_t *d_area) {
     if (batch == 0) return COVAHIP_OK;
     CtxLane &ln = ctx->lane();             // scratch of the lane this call runs on (lane 0 on the primary stream)
     CcGeom g;
@@ -249,7 +258,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
             ProfScope ps(ctx, "bboxcc_wave_kernel");
             hipLaunchKernelGGL(bboxcc_wave_kernel<false>, dim3((batch + WV_WAVES - 1) / WV_WAVES), dim3(WV_WAVES * 64), wlds, ctx->stream,
                                d_mask, wg, batch, area_thresh, d_boxes, d_counts, max_boxes, (const int32_t *)nullptr,
-                               (const int32_t *)nullptr, list1, n1, WAVE_CAP, n_big, cnt_next);
+                               (const int32_t *)nullptr, list1, n1, WAVE_CAP, n_big, cnt_next, d_area);
             COVAHIP_CHECK_HIP(ctx, hipGetLastError());
             if (can_overflow) ln.cc_stat_turn++;
         }
@@ -260,7 +269,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
             ProfScope ps(ctx, "bboxcc_wave_kernel_2");
             hipLaunchKernelGGL(bboxcc_wave_kernel<true>, dim3(grid), dim3(WV_WAVES * 64), wlds2, ctx->stream, d_mask, wg2, batch, area_thresh,
                                d_boxes, d_counts, max_boxes, (const int32_t *)list1, (const int32_t *)n1, list2, n2, 0, (int32_t *)nullptr,
-                               (int32_t *)nullptr);
+                               (int32_t *)nullptr, d_area);
             COVAHIP_CHECK_HIP(ctx, hipGetLastError());
         }
         if (can_overflow) {
@@ -276,7 +285,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
             ProfScope ps(ctx, "bboxcc_kernel");
             hipLaunchKernelGGL(bboxcc_kernel, dim3(!have_list ? 1 : quiet ? 32 : std::min(batch, 2 * num_cu)), dim3(CC_THREADS), lds_wg, ctx->stream, d_mask, g, wfull,
                                area_thresh, d_boxes, d_counts, max_boxes, (const int32_t *)(second_now ? list2 : list1),
-                               (const int32_t *)(second_now ? n2 : n1), (const int32_t *)cnt, stat_dev, batch, cap);
+                               (const int32_t *)(second_now ? n2 : n1), (const int32_t *)cnt, stat_dev, batch, cap, d_area);
             COVAHIP_CHECK_HIP(ctx, hipGetLastError());
             ln.cc_stat_batch = batch;
             ln.cc_stat_cap = cap;
@@ -296,7 +305,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
         if (rc) return rc;
         ProfScope ps(ctx, "bboxcc_big_kernel");
         hipLaunchKernelGGL(bboxcc_big_kernel, dim3(grid), dim3(CC_THREADS), 0, ctx->stream, d_mask, gb, (uint8_t *)ln.cc_slab, slab,
-                           batch, area_thresh, d_boxes, d_counts, max_boxes);
+                           batch, area_thresh, d_boxes, d_counts, max_boxes, d_area);
         COVAHIP_CHECK_HIP(ctx, hipGetLastError());
         return COVAHIP_OK;
     }
@@ -305,7 +314,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
     ProfScope ps(ctx, "bboxcc_kernel");
     hipLaunchKernelGGL(bboxcc_kernel, dim3(batch), dim3(CC_THREADS), lds_wg, ctx->stream, d_mask, g, wfull, area_thresh,
                        d_boxes, d_counts, max_boxes, (const int32_t *)nullptr, (const int32_t *)nullptr, (const int32_t *)nullptr,
-                       (int32_t *)nullptr, 0, 0);
+                       (int32_t *)nullptr, 0, 0, d_area);
     COVAHIP_CHECK_HIP(ctx, hipGetLastError());
     return COVAHIP_OK;
 }
@@ -332,16 +341,38 @@ extern "C" int covahip_bboxcc_set_wave_cap(covahip_ctx *ctx, int cap) {
     return COVAHIP_OK;
 }
 
-extern "C" int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, int area_thresh,
-                              covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind) {
+// Shared body of covahip_bboxcc (area_v == nullptr) and covahip_bboxcc_v (area_v: HOST i32 [batch], a threshold per frame).
+static int bboxcc_any(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, int area_thresh, const int32_t *area_v,
+                      covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind) {
     if (!ctx || batch < 0 || h <= 0 || w <= 0 || max_boxes < 0) return COVAHIP_ERR_INVALID_ARG;
     if (batch == 0) return COVAHIP_OK;
     if (!mask || !counts || (!boxes && max_boxes > 0)) return COVAHIP_ERR_INVALID_ARG;
+    if (mem_kind != COVAHIP_MEM_DEVICE && mem_kind != COVAHIP_MEM_HOST) return COVAHIP_ERR_INVALID_ARG;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int prc = covahip_primary_op(ctx)) return prc;   // stand-alone bboxcc runs on the primary stream
+    // the thresholds are read during the call: into a pinned copy of the ctx (free again once the upload before it is done), from
+    // there to the device on the primary stream, in front of the kernels
+    const int32_t *d_area = nullptr;
+    if (area_v) {
+        const size_t bytes = (size_t)batch * sizeof(int32_t);
+        if (ctx->cc_area_ev) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ctx->cc_area_ev));
+        if (bytes > ctx->cc_area_bytes) {
+            COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // kernels of an earlier call may still read the device copy
+            if (ctx->cc_area_dev) hipFree(ctx->cc_area_dev);
+            if (ctx->cc_area_host) hipHostFree(ctx->cc_area_host);
+            ctx->cc_area_dev = nullptr; ctx->cc_area_host = nullptr; ctx->cc_area_bytes = 0;
+            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ctx->cc_area_dev, bytes));
+            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ctx->cc_area_host, bytes, hipHostMallocDefault));
+            ctx->cc_area_bytes = bytes;
+            if (!ctx->cc_area_ev) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ctx->cc_area_ev, hipEventDisableTiming));
+        }
+        std::copy(area_v, area_v + batch, ctx->cc_area_host);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->cc_area_dev, ctx->cc_area_host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ctx->cc_area_ev, ctx->stream));
+        d_area = ctx->cc_area_dev;
+    }
     if (mem_kind == COVAHIP_MEM_DEVICE)
-        return covahip_bboxcc_launch(ctx, mask, batch, h, w, area_thresh, boxes, counts, max_boxes);
-    if (mem_kind != COVAHIP_MEM_HOST) return COVAHIP_ERR_INVALID_ARG;
+        return covahip_bboxcc_launch(ctx, mask, batch, h, w, area_thresh, boxes, counts, max_boxes, d_area);
 
     const size_t mask_bytes = (size_t)batch * h * w;
     const size_t box_bytes = (size_t)batch * max_boxes * sizeof(covahip_box);
@@ -354,11 +385,22 @@ extern "C" int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, 
     covahip_box *d_boxes = (covahip_box *)ctx->stage_out;
     int32_t *d_counts = (int32_t *)((uint8_t *)ctx->stage_out + ((box_bytes + 15) & ~(size_t)15));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d_mask, mask, mask_bytes, hipMemcpyHostToDevice, ctx->stream));
-    rc = covahip_bboxcc_launch(ctx, d_mask, batch, h, w, area_thresh, d_boxes, d_counts, max_boxes);
+    rc = covahip_bboxcc_launch(ctx, d_mask, batch, h, w, area_thresh, d_boxes, d_counts, max_boxes, d_area);
     if (rc) return rc;
     if (box_bytes)
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(boxes, d_boxes, box_bytes, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(counts, d_counts, cnt_bytes, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return COVAHIP_OK;
+}
+
+extern "C" int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, int area_thresh,
+                              covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind) {
+    return bboxcc_any(ctx, mask, batch, h, w, area_thresh, nullptr, boxes, counts, max_boxes, mem_kind);
+}
+
+extern "C" int covahip_bboxcc_v(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, const int32_t *area_thresh,
+                                covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind) {
+    if (!area_thresh) return COVAHIP_ERR_INVALID_ARG;
+    return bboxcc_any(ctx, mask, batch, h, w, 0, area_thresh, boxes, counts, max_boxes, mem_kind);
 }

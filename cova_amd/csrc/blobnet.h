@@ -40,6 +40,13 @@ struct BnWorkspace {
     size_t models_cap = 0;            // capacity of both
     hipEvent_t ev_models = nullptr;   // upload of h_models done
     std::vector<uint8_t> last_models; // the ids resident in d_models (unchanged ids are not uploaded again)
+    // per-stack area thresholds of the stand-alone bboxcc behind a forward whose frame does not fit the fused tail
+    // (covahip_blobnet_set_area): i32 [batch], uploaded like the model ids
+    int32_t *d_areas = nullptr;
+    int32_t *h_areas = nullptr;       // pinned host copy it is uploaded from
+    size_t areas_cap = 0;             // capacity of both, in thresholds
+    hipEvent_t ev_areas = nullptr;    // upload of h_areas done
+    std::vector<int32_t> last_areas;  // the thresholds resident in d_areas (unchanged ones are not uploaded again)
 };
 
 struct covahip_blobnet {
@@ -64,14 +71,17 @@ struct covahip_blobnet {
                           // and the batch / geometry make it pay; 0: never, 2: whenever they fit
     int enc_rowtiles = 1; // MFMA path: levels 2 and 3 on row-aligned tiles (enc_mfma<.., TSZ>) where the geometry suits them
     int64_t macs_per_frame = 0;
-    // per-model post-processing (covahip_blobnet_set_post): host copies of the settings, and -- from the first non-default
-    // setting on -- their device tables, one allocation: fp32 threshold per model | keep bytes u8 [n_models][H][W] | the same
-    // as bboxcc's parity planes, u32 [n_models][H][E lo, E hi, O lo, O hi] (what dec3cc_rows_mfma ANDs into its ballots)
+    // per-model post-processing (covahip_blobnet_set_post, covahip_blobnet_set_area): host copies of the settings, and -- from
+    // the first non-default setting on -- their device tables, one allocation: fp32 threshold per model | i32 area threshold per
+    // model | keep bytes u8 [n_models][H][W] | the same as bboxcc's parity planes, u32 [n_models][H][E lo, E hi, O lo, O hi]
+    // (what dec3cc_rows_mfma ANDs into its ballots)
     std::vector<float> post_thr;                  // [n_models]
+    std::vector<int32_t> post_area;               // [n_models]: bboxcc's area threshold of the model, 0 = unset (the call's applies)
+    bool area_on = false;                         // some model has an area threshold of its own
     std::vector<std::vector<uint8_t>> post_keep;  // [n_models]: empty = keep everything, else H * W bytes of 0 / 1
     bool post_on = false;                         // some model has a non-default setting: the POST = true kernels run
     void *d_post = nullptr;
-    size_t post_keep_off = 0, post_planes_off = 0, post_keep_stride = 0, post_planes_stride = 0, post_bytes = 0;
+    size_t post_area_off = 0, post_keep_off = 0, post_planes_off = 0, post_keep_stride = 0, post_planes_stride = 0, post_bytes = 0;
 };
 
 // Whether encoder level 1 runs on enc1_mfma (16x16x32 tiles, fixed LDS row: grids of at most BN_E1_MAXW level-1 pixels) or on
@@ -111,6 +121,7 @@ struct BnInput {
     int model = 0;
     const uint8_t *model_ids = nullptr;
     const uint8_t *frame_models = nullptr;
+    const uint8_t *h_model_ids = nullptr;   // the same ids per stack on the HOST (the caller's array, alive during the call); null with model_ids
     bool mixed = false;    // dry: plan the mixed-batch kernels
 };
 int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const BnInput &in, int batch, float *d_logits,

@@ -37,6 +37,9 @@ static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
         if (ws.d_models) hipFree(ws.d_models);
         if (ws.h_models) hipHostFree(ws.h_models);
         if (ws.ev_models) hipEventDestroy(ws.ev_models);
+        if (ws.d_areas) hipFree(ws.d_areas);
+        if (ws.h_areas) hipHostFree(ws.h_areas);
+        if (ws.ev_areas) hipEventDestroy(ws.ev_areas);
     }
     delete m;
 }
@@ -74,6 +77,7 @@ static int resolve_models(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws,
     in.model = 0;
     in.model_ids = nullptr;
     in.frame_models = nullptr;
+    in.h_model_ids = nullptr;
     if (!model_ids) return COVAHIP_OK;
     if (int rc = check_model_ids(m, model_ids, batch)) return rc;
     bool uniform = true;
@@ -116,6 +120,44 @@ static int resolve_models(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws,
     }
     in.model_ids = ws.d_models;
     in.frame_models = ws.d_models + batch;
+    in.h_model_ids = model_ids;
+    return COVAHIP_OK;
+}
+
+// The stacks' area thresholds for the stand-alone bboxcc behind a forward (covahip_blobnet_set_area: the model's own when it has
+// one, else the call's), on the device: *d_out.  Null while no model has one: the scalar form runs.  Uploaded like the model ids:
+// from a pinned copy, on the lane's stream, and not at all when they equal the resident ones.
+static int resolve_areas(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, const BnInput &in, int batch, int area_thresh,
+                         const int32_t **d_out) {
+    *d_out = nullptr;
+    if (!m->area_on) return COVAHIP_OK;
+    std::vector<int32_t> eff((size_t)batch);
+    for (int b = 0; b < batch; b++) {
+        const int32_t a = m->post_area[in.h_model_ids ? in.h_model_ids[b] : in.model];
+        eff[b] = a >= 1 ? a : area_thresh;
+    }
+    if (!(ws.d_areas && eff == ws.last_areas)) {
+        if (ws.d_areas) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ws.ev_areas));   // the pinned copy is free again
+        if (eff.size() > ws.areas_cap) {
+            if (ws.d_areas) {
+                COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                hipFree(ws.d_areas);
+                hipHostFree(ws.h_areas);
+                ws.d_areas = nullptr; ws.h_areas = nullptr; ws.areas_cap = 0;
+                ws.last_areas.clear();
+            }
+            const size_t cap = std::max(eff.size(), (size_t)m->max_batch);
+            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.d_areas, cap * sizeof(int32_t)));
+            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ws.h_areas, cap * sizeof(int32_t), hipHostMallocDefault));
+            ws.areas_cap = cap;
+            if (!ws.ev_areas) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ws.ev_areas, hipEventDisableTiming));
+        }
+        std::copy(eff.begin(), eff.end(), ws.h_areas);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ws.d_areas, ws.h_areas, eff.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ws.ev_areas, ctx->stream));
+        ws.last_areas = std::move(eff);
+    }
+    *d_out = ws.d_areas;
     return COVAHIP_OK;
 }
 
@@ -139,9 +181,13 @@ static int filter_dev(covahip_ctx *ctx, BnInput &in, int batch, float *d_logits,
     int rc = blobnet_forward_mfma(ctx, m, m->ws[ctx->cur_lane], in, batch, d_logits, d_mask, with_cc ? &tail : nullptr, &cc_done);
     if (rc) return rc;
     // the fused decoder tail normally runs bboxcc itself; the separate kernel is the fallback for
-    // geometries whose frame does not fit its LDS plan
-    if (with_cc && !cc_done)
-        rc = covahip_bboxcc_launch(ctx, d_mask, batch, m->H, m->W, area_thresh, d_boxes, d_counts, max_boxes);
+    // geometries whose frame does not fit its LDS plan -- with the stacks' own area thresholds where models have them
+    if (with_cc && !cc_done) {
+        const int32_t *d_areas = nullptr;
+        rc = resolve_areas(ctx, m, m->ws[ctx->cur_lane], in, batch, area_thresh, &d_areas);
+        if (rc) return rc;
+        rc = covahip_bboxcc_launch(ctx, d_mask, batch, m->H, m->W, area_thresh, d_boxes, d_counts, max_boxes, d_areas);
+    }
     return rc;
 }
 
@@ -295,6 +341,7 @@ static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *const 
     if (rc) return rc;
     m->post_thr.assign(n_models, 0.f);   // per-model post-processing: the defaults
     m->post_keep.assign(n_models, {});
+    m->post_area.assign(n_models, 0);
     BnInput plan;   // planning only, both input forms, smallest and largest batch (a set: also the mixed-batch kernels)
     plan.dry = true;
     for (int pass = 0; pass < (n_models > 1 ? 8 : 4) && !rc; pass++) {
@@ -367,7 +414,8 @@ int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models) {
 
 // Per-model post-processing (covahip.h).  The device tables are one allocation, made at the first non-default setting and
 // rewritten whole by every later call: the ctx is drained first, so nothing in flight reads them.
-//   fp32 threshold [n_models] | keep bytes u8 [n_models][H][W] | keep planes u32 [n_models][H][E lo, E hi, O lo, O hi]
+//   fp32 threshold [n_models] | i32 area threshold [n_models] | keep bytes u8 [n_models][H][W] |
+//   keep planes u32 [n_models][H][E lo, E hi, O lo, O hi]
 // A plane holds the even (E) or odd (O) pixels of a row, pixel 2k (2k + 1) at bit k: bboxcc's planes (bboxcc_wave.h), which
 // dec3cc_rows_mfma ballots its logits into.  That kernel takes rows of at most 128 pixels; the planes of a wider grid are not read.
 static int upload_post(covahip_ctx *ctx, covahip_blobnet *m) {
@@ -376,13 +424,15 @@ static int upload_post(covahip_ctx *ctx, covahip_blobnet *m) {
     if (!m->d_post) {
         m->post_keep_stride = (hw + 15) & ~(size_t)15;
         m->post_planes_stride = (size_t)m->H * 16;
-        m->post_keep_off = al(n * sizeof(float));
+        m->post_area_off = n * sizeof(float);
+        m->post_keep_off = al(m->post_area_off + n * sizeof(int32_t));
         m->post_planes_off = al(m->post_keep_off + n * m->post_keep_stride);
         m->post_bytes = m->post_planes_off + n * m->post_planes_stride;
         COVAHIP_CHECK_HIP(ctx, hipMalloc(&m->d_post, m->post_bytes));
     }
     std::vector<uint8_t> host(m->post_bytes, 0);
     std::memcpy(host.data(), m->post_thr.data(), n * sizeof(float));
+    std::memcpy(host.data() + m->post_area_off, m->post_area.data(), n * sizeof(int32_t));
     for (size_t k = 0; k < n; k++) {
         uint8_t *kb = host.data() + m->post_keep_off + k * m->post_keep_stride;
         uint32_t *kp = reinterpret_cast<uint32_t *>(host.data() + m->post_planes_off + k * m->post_planes_stride);
@@ -395,6 +445,28 @@ static int upload_post(covahip_ctx *ctx, covahip_blobnet *m) {
             }
     }
     COVAHIP_CHECK_HIP(ctx, hipMemcpy(m->d_post, host.data(), host.size(), hipMemcpyHostToDevice));
+    return COVAHIP_OK;
+}
+
+// The host settings changed (the ctx is drained): the tables follow, and the forward runs the POST = true kernels while any model
+// has a setting that is not the default -- a threshold, a keep map or an area threshold.
+static int commit_post(covahip_ctx *ctx, covahip_blobnet *m) {
+    bool on = false, area = false;
+    for (int k = 0; k < m->n_models; k++) {
+        area = area || m->post_area[k] >= 1;
+        on = on || m->post_thr[k] != 0.f || !m->post_keep[k].empty() || m->post_area[k] >= 1;
+    }
+    if (on || m->d_post) {
+        if (int rc = upload_post(ctx, m)) {   // (an allocation or a copy failed: the model falls back to the defaults rather than to half a table)
+            m->post_thr.assign(m->n_models, 0.f);
+            m->post_keep.assign(m->n_models, {});
+            m->post_area.assign(m->n_models, 0);
+            m->post_on = m->area_on = false;
+            return rc;
+        }
+    }
+    m->post_on = on;
+    m->area_on = area;
     return COVAHIP_OK;
 }
 
@@ -413,17 +485,27 @@ int covahip_blobnet_set_post(covahip_ctx *ctx, int model, const covahip_blobnet_
         m->post_keep[model].resize(hw);
         for (size_t i = 0; i < hw; i++) m->post_keep[model][i] = post->keep[i] ? 1 : 0;
     }
-    bool on = false;
-    for (int k = 0; k < m->n_models; k++) on = on || m->post_thr[k] != 0.f || !m->post_keep[k].empty();
-    if (on || m->d_post) {
-        if (int rc = upload_post(ctx, m)) {   // (an allocation or a copy failed: the model falls back to the defaults rather than to half a table)
-            m->post_thr.assign(m->n_models, 0.f);
-            m->post_keep.assign(m->n_models, {});
-            m->post_on = false;
-            return rc;
-        }
-    }
-    m->post_on = on;
+    return commit_post(ctx, m);
+}
+
+// Per-model area threshold of bboxcc (covahip.h): the same tables, the same ordering rule, a setting of its own.
+int covahip_blobnet_set_area(covahip_ctx *ctx, int model, int area_thresh) {
+    if (!ctx) return COVAHIP_ERR_INVALID_ARG;
+    covahip_blobnet *m = ctx->blobnet;
+    if (!m) return COVAHIP_ERR_NOT_LOADED;
+    if (model < 0 || model >= m->n_models || area_thresh < 0) return COVAHIP_ERR_INVALID_ARG;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_sync_all(ctx)) return rc;   // batches in flight keep the settings they were submitted with
+    m->post_area[model] = area_thresh;
+    return commit_post(ctx, m);
+}
+
+int covahip_blobnet_get_area(covahip_ctx *ctx, int model, int *area_thresh) {
+    if (!ctx || !area_thresh) return COVAHIP_ERR_INVALID_ARG;
+    covahip_blobnet *m = ctx->blobnet;
+    if (!m) return COVAHIP_ERR_NOT_LOADED;
+    if (model < 0 || model >= m->n_models) return COVAHIP_ERR_INVALID_ARG;
+    *area_thresh = m->post_area[model];
     return COVAHIP_OK;
 }
 

@@ -324,6 +324,8 @@ struct DecMs {
 struct DecPost {
     float thr;                  // logit threshold of the batch's model
     const float *thr_tab;       // MS: threshold per model
+    int area;                   // bboxcc's area threshold of the batch's model, already resolved: the model's own when set, else the call's
+    const int32_t *area_tab;    // MS: area threshold per model, 0 = unset (the call's applies; covahip_blobnet_set_area)
     const uint8_t *keep;        // u8 [Hd][Wd], 1 = the macroblock may be foreground (always present: all ones without a keep map)
     const uint32_t *planes;     // the same as bboxcc's parity planes: u32 [Hd][E lo, E hi, O lo, O hi] (dec3cc_rows_mfma)
     uint32_t keep_stride, planes_stride;   // MS: bytes between two models' maps
@@ -348,6 +350,21 @@ __device__ __forceinline__ StackPost stack_post(const PostArg<POST> &pp, const u
     } else {
         const uint32_t id = __builtin_amdgcn_readfirstlane((uint32_t)mid[b]);
         return StackPost{pp.thr_tab[id], at_model(pp.keep, id * pp.keep_stride), at_model(pp.planes, id * pp.planes_stride)};
+    }
+}
+// bboxcc's area threshold of stack b, the last of its settings: the same three cases (area_call: the call's threshold, which a
+// model without one of its own takes; POST = false: nothing but that).  A function of its own, called where bboxcc starts: taken at
+// the top of the frame with the others, the scalar lived across the tile loop, whose scalar registers are all in use
+// (dec3cc_mfma<false, false, true, true> spilled it: 8 bytes of scratch).
+template <bool POST, bool MS>
+__device__ __forceinline__ int stack_area(const PostArg<POST> &pp, const uint8_t *mid, int b, int area_call) {
+    if constexpr (!POST) {
+        return area_call;
+    } else if constexpr (!MS) {
+        return pp.area;
+    } else {
+        const int a = pp.area_tab[__builtin_amdgcn_readfirstlane((uint32_t)mid[b])];
+        return a >= 1 ? a : area_call;
     }
 }
 
@@ -2323,11 +2340,12 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q, 
             }
         }
         PHASE_MARK(6);   // mask out
+        const int area = stack_area<POST, MS>(qp, q.ms.model_ids, b, q.area_thresh);
         if constexpr (WV)
-            ccwave::frame_wg<ccbody::CC_THREADS>(mfull, smem + q.cc_off, q.wg, q.area_thresh, q.boxes + (size_t)b * q.max_boxes,
+            ccwave::frame_wg<ccbody::CC_THREADS>(mfull, smem + q.cc_off, q.wg, area, q.boxes + (size_t)b * q.max_boxes,
                                                  q.counts + b, q.max_boxes, tid);
         else
-            ccbody::bboxcc_frame(mfull, smem + q.cc_off, q.g, q.area_thresh, q.boxes + (size_t)b * q.max_boxes, q.counts + b,
+            ccbody::bboxcc_frame(mfull, smem + q.cc_off, q.g, area, q.boxes + (size_t)b * q.max_boxes, q.counts + b,
                                  q.max_boxes, tid);
         PHASE_MARK(7);   // bboxcc
     }
@@ -2489,7 +2507,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
             }
         }
         PHASE_MARK(6);   // mask out
-        ccwave::frame_wg<ccbody::CC_THREADS, true>(nullptr, smem + q.cc_off, q.wg, q.area_thresh, q.boxes + (size_t)b * q.max_boxes,
+        ccwave::frame_wg<ccbody::CC_THREADS, true>(nullptr, smem + q.cc_off, q.wg, stack_area<POST, MS>(qp, q.ms.model_ids, b, q.area_thresh), q.boxes + (size_t)b * q.max_boxes,
                                                    q.counts + b, q.max_boxes, tid, planes);
         PHASE_MARK(7);   // bboxcc
     }
@@ -3396,6 +3414,9 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         const size_t k = ms ? 0 : (size_t)inp.model;
         f.pp.thr = m->post_thr[k];
         f.pp.thr_tab = (const float *)dp;
+        // the area threshold: a batch of one model gets it resolved here, a mixed batch per stack from the table behind the thresholds
+        f.pp.area = m->post_area[k] >= 1 ? m->post_area[k] : (cc ? cc->area_thresh : 0);
+        f.pp.area_tab = (const int32_t *)(dp + m->post_area_off);
         f.pp.keep = dp + m->post_keep_off + k * m->post_keep_stride;
         f.pp.planes = (const uint32_t *)(dp + m->post_planes_off + k * m->post_planes_stride);
         f.pp.keep_stride = (uint32_t)m->post_keep_stride;

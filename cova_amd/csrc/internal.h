@@ -80,6 +80,10 @@ struct covahip_ctx {
     size_t pinned_bytes = 0;
     void *sweep_buf = nullptr;   // covahip_post_sweep: accumulators, keep map, one chunk's mask frames, boxes and counts
     size_t sweep_bytes = 0;
+    // covahip_bboxcc_v: the call's per-frame area thresholds, pinned host copy -> device copy on the primary stream
+    int32_t *cc_area_host = nullptr, *cc_area_dev = nullptr;
+    size_t cc_area_bytes = 0;
+    hipEvent_t cc_area_ev = nullptr;   // upload done: the pinned copy is free again
     int cc_wave_cap = 0;       // bboxcc wave kernel: developer override of its run capacity
     int tail_form = 0;         // which kernel ran the last decoder block of the last forward (covahip_dev_blobnet_tail_form)
     CtxLane &lane() { return lanes[cur_lane]; }
@@ -124,8 +128,9 @@ int covahip_sync_all(covahip_ctx *ctx);
 uint32_t covahip_crc32c(const uint8_t *p, size_t n);
 
 // bboxcc.hip
+// d_area: optional device array i32 [batch], frame b's own area threshold (null: area_thresh for every frame)
 int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, int h, int w, int area_thresh,
-                          covahip_box *d_boxes, int32_t *d_counts, int max_boxes);
+                          covahip_box *d_boxes, int32_t *d_counts, int max_boxes, const int32_t *d_area = nullptr);
 
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);

@@ -246,6 +246,18 @@ class BlobNetInfer:
                 "covahip_blobnet_get_post", self.ctx.handle)
         return thr.value, (keep if has.value else None)
 
+    def set_area(self, model: int = 0, area: int = 0):
+        """Per-model area threshold (covahip_blobnet_set_area): the stacks of `model` keep components of at least `area`
+        macroblocks, whatever cc_threshold the call gives; 0 = unset, the call's applies again.  Independent of set_post /
+        reset_post.  Waits for everything the ctx has in flight first."""
+        L.check(self._lib.covahip_blobnet_set_area(self.ctx.handle, model, int(area)), "covahip_blobnet_set_area", self.ctx.handle)
+
+    def get_area(self, model: int = 0) -> int:
+        """The area threshold of `model` (0 = unset)."""
+        v = C.c_int()
+        L.check(self._lib.covahip_blobnet_get_area(self.ctx.handle, model, C.byref(v)), "covahip_blobnet_get_area", self.ctx.handle)
+        return v.value
+
     def set_enc_plan(self, level: int, nbands: int, nbuf: int = 1):
         """Developer switch (include/covahip_dev.h): band plan of encoder level 1..3; nbands = 0 -> automatic."""
         L.check(self._lib.covahip_blobnet_set_enc_plan(self.ctx.handle, level, nbands, nbuf), "covahip_blobnet_set_enc_plan")
@@ -617,6 +629,33 @@ class BboxCc:
     def regionprops_device(self, d_masks: int, b: int, h: int, w: int, d_boxes: int, d_counts: int):
         L.check(self._lib.covahip_bboxcc(self.ctx.handle, d_masks, b, h, w, self.cc_threshold, d_boxes, d_counts,
                                          self.max_boxes, L.MEM_DEVICE), "covahip_bboxcc", self.ctx.handle)
+
+    @staticmethod
+    def _thresholds(cc_thresholds, b: int) -> np.ndarray:
+        t = np.ascontiguousarray(cc_thresholds, dtype=np.int32)
+        if t.shape != (b,):
+            raise ValueError(f"cc_thresholds must be [{b}], got {t.shape}")
+        return t
+
+    def regionprops_v(self, masks: np.ndarray, cc_thresholds):
+        """regionprops with a threshold per frame (covahip_bboxcc_v): masks u8 [B][H][W] (host), cc_thresholds i32 [B]
+        -> (boxes [B][max_boxes], counts [B]); frame b keeps components of at least cc_thresholds[b] pixels."""
+        masks = np.ascontiguousarray(masks, dtype=np.uint8)
+        if masks.ndim == 2:
+            masks = masks[None]
+        b, h, w = masks.shape
+        t = self._thresholds(cc_thresholds, b)
+        boxes = np.zeros((b, self.max_boxes), dtype=L.BOX_DTYPE)
+        counts = np.zeros(b, dtype=np.int32)
+        L.check(self._lib.covahip_bboxcc_v(self.ctx.handle, _ptr(masks), b, h, w, _ptr(t), _ptr(boxes), _ptr(counts),
+                                           self.max_boxes, L.MEM_HOST), "covahip_bboxcc_v", self.ctx.handle)
+        return boxes, counts
+
+    def regionprops_v_device(self, d_masks: int, b: int, h: int, w: int, cc_thresholds, d_boxes: int, d_counts: int):
+        """The same on device pointers; cc_thresholds stays a HOST array, read during the call."""
+        t = self._thresholds(cc_thresholds, b)
+        L.check(self._lib.covahip_bboxcc_v(self.ctx.handle, d_masks, b, h, w, _ptr(t), d_boxes, d_counts, self.max_boxes,
+                                           L.MEM_DEVICE), "covahip_bboxcc_v", self.ctx.handle)
 
     def transform_ip(self, buf: bytes | np.ndarray, width: int, height: int) -> bytes:
         """GRAY8 mask buffer -> bincode Vec<Bbox> bytes (imp.rs:232-272)."""

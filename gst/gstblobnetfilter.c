@@ -78,6 +78,7 @@ struct _GstBlobNetFilter {
     gchar *pad_weights;   /* pad-model-weights: "IDX=PATH;IDX=PATH" (model sets: sink_IDX runs the model of PATH) */
     gchar *pad_rects;     /* pad-ignore-rects: "IDX=l,t,w,h+l,t,w,h;IDX=..." in pixels (macroblocks a rectangle overlaps never become foreground) */
     gchar *pad_thresh;    /* pad-mask-threshold: "IDX=P;IDX=P", the mask is where sigmoid(logit) > P */
+    gchar *pad_cc;        /* pad-cc-threshold: "IDX=N;IDX=N", sink_IDX keeps components of at least N macroblocks (N >= 1) */
     guint8 *pad_model;    /* model of sink pad idx [BF_MAX_PAD_MAP] when a pad-* property is set, else NULL */
     uint8_t *pm;          /* model ids of the slot being filled (covahip_pipe_model_ids) */
     guint gpu_id, batch_size, cc_threshold, max_boxes;
@@ -112,7 +113,7 @@ struct _GstBlobNetFilter {
 typedef struct { GstElementClass parent_class; } GstBlobNetFilterClass;
 G_DEFINE_TYPE(GstBlobNetFilter, gst_blobnetfilter, GST_TYPE_ELEMENT)
 enum { BF_PROP_0, BF_PROP_WEIGHTS, BF_PROP_GPU, BF_PROP_BATCH, BF_PROP_TIMEOUT, BF_PROP_CC, BF_PROP_MAXBOXES, BF_PROP_BATCHES, BF_PROP_TIMING,
-       BF_PROP_PAD_WEIGHTS, BF_PROP_PAD_RECTS, BF_PROP_PAD_THRESH };
+       BF_PROP_PAD_WEIGHTS, BF_PROP_PAD_RECTS, BF_PROP_PAD_THRESH, BF_PROP_PAD_CC };
 #define BF_MAX_PAD_MAP 1024   /* sink pads pad-model-weights can name: sink_0 .. sink_1023 */
 
 #define BF_ST_BITS 21
@@ -187,18 +188,29 @@ static gboolean bf_parse_threshold(const gchar *value, float *logit) {
     return TRUE;
 }
 
-/* Model sets.  pad-model-weights, pad-ignore-rects and pad-mask-threshold give a sink pad its weights file, its ignore region and
- * its mask threshold; every distinct (file, rects, threshold) triple becomes one model of the set (post-processing settings are
- * per model, so two cameras on one file with different ignore regions are two models of the same weights: 0.64 MB each).  Model 0
- * is model-weights-file with the default post-processing, and the model of every pad that no property names.  s->pad_model maps
- * each pad to its model.  Models are numbered in the order the properties first name them, pad-model-weights first: a value of
- * that property alone gives the ids it always gave.  Loads the set (or the one model when no property is set) and applies the settings. */
+/* pad-cc-threshold value: an integer N >= 1, the area threshold in macroblocks (covahip_blobnet_set_area).  FALSE: malformed. */
+static gboolean bf_parse_cc(const gchar *value, int *area) {
+    gchar *end = NULL;
+    const guint64 n = g_ascii_isdigit(*value) ? g_ascii_strtoull(value, &end, 10) : 0;
+    if (!end || end == value || *end || n < 1 || n > G_MAXINT32) return FALSE;
+    *area = (int)n;
+    return TRUE;
+}
+
+/* Model sets.  pad-model-weights, pad-ignore-rects, pad-mask-threshold and pad-cc-threshold give a sink pad its weights file, its
+ * ignore region, its mask threshold and its area threshold; every distinct (file, rects, threshold, cc) tuple becomes one model of
+ * the set (post-processing settings are per model, so two cameras on one file with different ignore regions are two models of the
+ * same weights: 0.64 MB each).  Model 0 is model-weights-file with the default post-processing and the element's cc-threshold, and
+ * the model of every pad that no property names.  s->pad_model maps each pad to its model.  Models are numbered in the order the
+ * properties first name them, pad-model-weights first and pad-cc-threshold last: pipelines that do not use a later property get the
+ * ids they always got.  Loads the set (or the one model when no property is set) and applies the settings. */
 static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
-    const gboolean any = (s->pad_weights && *s->pad_weights) || (s->pad_rects && *s->pad_rects) || (s->pad_thresh && *s->pad_thresh);
+    const gboolean any = (s->pad_weights && *s->pad_weights) || (s->pad_rects && *s->pad_rects) || (s->pad_thresh && *s->pad_thresh) ||
+                         (s->pad_cc && *s->pad_cc);
     if (!any) return covahip_blobnet_load(s->ctx, blob0, len0, s->h_mb, s->w_mb, BF_TIMESTEP, (int)s->batch_size);
-    typedef struct { gchar *path, *rects, *thr; guint file; } BfModel;
-    gchar **map[3];   /* per pad: weights file, rects, threshold */
-    for (int i = 0; i < 3; i++) map[i] = g_new0(gchar *, BF_MAX_PAD_MAP);
+    typedef struct { gchar *path, *rects, *thr, *cc; guint file; } BfModel;
+    gchar **map[4];   /* per pad: weights file, rects, threshold, cc */
+    for (int i = 0; i < 4; i++) map[i] = g_new0(gchar *, BF_MAX_PAD_MAP);
     GPtrArray *paths = g_ptr_array_new_with_free_func(g_free);   /* distinct files ... */
     GPtrArray *files = g_ptr_array_new_with_free_func(g_free);   /* ... and their bytes */
     GArray *fsizes = g_array_new(FALSE, FALSE, sizeof(size_t));
@@ -207,7 +219,7 @@ static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
     GArray *order = g_array_new(FALSE, FALSE, sizeof(guint));
     guint8 *seen = g_new0(guint8, BF_MAX_PAD_MAP);
     if (!bf_parse_pad_map(s->pad_weights, map[0], order, seen) || !bf_parse_pad_map(s->pad_rects, map[1], order, seen) ||
-        !bf_parse_pad_map(s->pad_thresh, map[2], order, seen))
+        !bf_parse_pad_map(s->pad_thresh, map[2], order, seen) || !bf_parse_pad_map(s->pad_cc, map[3], order, seen))
         rc = COVAHIP_ERR_INVALID_ARG;
     g_free(seen);
     s->pad_model = g_new0(guint8, BF_MAX_PAD_MAP);
@@ -217,15 +229,16 @@ static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
     g_ptr_array_add(files, copy0);
     size_t n0 = len0;
     g_array_append_val(fsizes, n0);
-    BfModel m0 = {g_strdup(s->weights), g_strdup(""), g_strdup(""), 0};
+    BfModel m0 = {g_strdup(s->weights), g_strdup(""), g_strdup(""), g_strdup(""), 0};
     g_array_append_val(models, m0);
     for (guint o = 0; o < order->len && rc == COVAHIP_OK; o++) {
         const guint idx = g_array_index(order, guint, o);
         const gchar *path = map[0][idx] ? map[0][idx] : s->weights, *rects = map[1][idx] ? map[1][idx] : "", *thr = map[2][idx] ? map[2][idx] : "";
+        const gchar *cc = map[3][idx] ? map[3][idx] : "";
         guint k = 0;
         for (; k < models->len; k++) {
             const BfModel *m = &g_array_index(models, BfModel, k);
-            if (!strcmp(m->path, path) && !strcmp(m->rects, rects) && !strcmp(m->thr, thr)) break;
+            if (!strcmp(m->path, path) && !strcmp(m->rects, rects) && !strcmp(m->thr, thr) && !strcmp(m->cc, cc)) break;
         }
         if (k == models->len) {
             if (k >= COVAHIP_MAX_MODELS) { rc = COVAHIP_ERR_BAD_WEIGHTS; break; }
@@ -240,7 +253,7 @@ static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
                 size_t nn = n;
                 g_array_append_val(fsizes, nn);
             }
-            BfModel m = {g_strdup(path), g_strdup(rects), g_strdup(thr), f};
+            BfModel m = {g_strdup(path), g_strdup(rects), g_strdup(thr), g_strdup(cc), f};
             g_array_append_val(models, m);
         }
         s->pad_model[idx] = (guint8)k;
@@ -249,10 +262,12 @@ static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
     const size_t hw = (size_t)s->h_mb * s->w_mb;
     guint8 *keeps = g_malloc(models->len * hw + 1);
     float *thrs = g_new0(float, models->len);
+    int *ccs = g_new0(int, models->len);
     for (guint k = 0; k < models->len && rc == COVAHIP_OK; k++) {
         const BfModel *m = &g_array_index(models, BfModel, k);
         if (*m->rects && !bf_parse_rects(m->rects, s->h_mb, s->w_mb, keeps + k * hw)) rc = COVAHIP_ERR_INVALID_ARG;
         if (*m->thr && !bf_parse_threshold(m->thr, &thrs[k])) rc = COVAHIP_ERR_INVALID_ARG;
+        if (*m->cc && !bf_parse_cc(m->cc, &ccs[k])) rc = COVAHIP_ERR_INVALID_ARG;
     }
     if (rc == COVAHIP_OK) {
         const void **blobs = g_new0(const void *, models->len);
@@ -268,22 +283,25 @@ static int bf_load_models(GstBlobNetFilter *s, const gchar *blob0, gsize len0) {
     }
     for (guint k = 0; k < models->len && rc == COVAHIP_OK; k++) {
         const BfModel *m = &g_array_index(models, BfModel, k);
-        if (!*m->rects && !*m->thr) continue;
-        covahip_blobnet_post post = {thrs[k], *m->rects ? keeps + k * hw : NULL};
-        rc = covahip_blobnet_set_post(s->ctx, (int)k, &post);
+        if (*m->rects || *m->thr) {
+            covahip_blobnet_post post = {thrs[k], *m->rects ? keeps + k * hw : NULL};
+            rc = covahip_blobnet_set_post(s->ctx, (int)k, &post);
+        }
+        if (rc == COVAHIP_OK && ccs[k]) rc = covahip_blobnet_set_area(s->ctx, (int)k, ccs[k]);
     }
     g_free(keeps);
     g_free(thrs);
+    g_free(ccs);
     for (guint k = 0; k < models->len; k++) {
         BfModel *m = &g_array_index(models, BfModel, k);
-        g_free(m->path); g_free(m->rects); g_free(m->thr);
+        g_free(m->path); g_free(m->rects); g_free(m->thr); g_free(m->cc);
     }
     g_array_free(models, TRUE);
     g_ptr_array_free(paths, TRUE);
     g_ptr_array_free(files, TRUE);
     g_array_free(fsizes, TRUE);
     g_array_free(order, TRUE);
-    for (int i = 0; i < 3; i++) {
+    for (int i = 0; i < 4; i++) {
         for (guint idx = 0; idx < BF_MAX_PAD_MAP; idx++) g_free(map[i][idx]);
         g_free(map[i]);
     }
@@ -880,6 +898,7 @@ static void bf_set_property(GObject *o, guint id, const GValue *v, GParamSpec *p
     case BF_PROP_PAD_WEIGHTS: if (!s->pipe) { g_free(s->pad_weights); s->pad_weights = g_value_dup_string(v); } break;
     case BF_PROP_PAD_RECTS: if (!s->pipe) { g_free(s->pad_rects); s->pad_rects = g_value_dup_string(v); } break;
     case BF_PROP_PAD_THRESH: if (!s->pipe) { g_free(s->pad_thresh); s->pad_thresh = g_value_dup_string(v); } break;
+    case BF_PROP_PAD_CC: if (!s->pipe) { g_free(s->pad_cc); s->pad_cc = g_value_dup_string(v); } break;
     case BF_PROP_GPU: s->gpu_id = g_value_get_uint(v); break;
     case BF_PROP_BATCH: if (!s->pipe) s->batch_size = g_value_get_uint(v); break;
     case BF_PROP_TIMEOUT: s->timeout_us = g_value_get_uint64(v); break;
@@ -896,6 +915,7 @@ static void bf_get_property(GObject *o, guint id, GValue *v, GParamSpec *ps) {
     case BF_PROP_PAD_WEIGHTS: g_value_set_string(v, s->pad_weights); break;
     case BF_PROP_PAD_RECTS: g_value_set_string(v, s->pad_rects); break;
     case BF_PROP_PAD_THRESH: g_value_set_string(v, s->pad_thresh); break;
+    case BF_PROP_PAD_CC: g_value_set_string(v, s->pad_cc); break;
     case BF_PROP_GPU: g_value_set_uint(v, s->gpu_id); break;
     case BF_PROP_BATCH: g_value_set_uint(v, s->batch_size); break;
     case BF_PROP_TIMEOUT: g_value_set_uint64(v, s->timeout_us); break;
@@ -932,6 +952,7 @@ static void bf_finalize(GObject *o) {
     g_free(s->pad_weights);
     g_free(s->pad_rects);
     g_free(s->pad_thresh);
+    g_free(s->pad_cc);
     g_free(s->pad_model);
     g_mutex_clear(&s->lock);
     g_cond_clear(&s->cond);
@@ -974,6 +995,9 @@ static void gst_blobnetfilter_class_init(GstBlobNetFilterClass *k) {
     g_object_class_install_property(g, BF_PROP_PAD_THRESH, g_param_spec_string("pad-mask-threshold", "Per-pad mask threshold",
         "\"IDX=P;IDX=P\": the mask of sink_IDX is where sigmoid(logit) > P, 0 < P < 1 (the reference's segmentation-threshold; default 0.5)",
         NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
+    g_object_class_install_property(g, BF_PROP_PAD_CC, g_param_spec_string("pad-cc-threshold", "Per-pad area threshold",
+        "\"IDX=N;IDX=N\": sink_IDX keeps components of at least N macroblocks, N >= 1 (the reference's cc-threshold per bboxcc element; "
+        "pads it does not name use cc-threshold)", NULL, G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_GPU, g_param_spec_uint("gpu-id", "GPU id", "HIP device to run on", 0, 15, 0,
         G_PARAM_READWRITE | GST_PARAM_MUTABLE_READY));
     g_object_class_install_property(g, BF_PROP_BATCH, g_param_spec_uint("batch-size", "Batch size",

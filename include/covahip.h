@@ -176,7 +176,8 @@ int covahip_blobnet_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const
  * affected.  covahip_blobnet_load and covahip_blobnet_load_set reset every model to the defaults.
  * covahip_blobnet_set_post waits for everything the ctx has in flight on all lanes, then updates the device tables:
  * batches submitted before the call have the old settings, batches submitted after it the new ones.  Call it under the
- * lock that guards acquire and submit.  post == NULL restores the defaults of that model.
+ * lock that guards acquire and submit.  post == NULL restores the defaults of that model.  Neither form touches the model's
+ * area threshold (covahip_blobnet_set_area below): the two settings are independent.
  *   COVAHIP_ERR_INVALID_ARG: NULL ctx, model outside the set, NaN or infinite threshold (nothing changes);
  *   COVAHIP_ERR_NOT_LOADED: no model loaded.                                                                        */
 typedef struct covahip_blobnet_post {
@@ -187,6 +188,27 @@ int covahip_blobnet_set_post(covahip_ctx *ctx, int model, const covahip_blobnet_
 /* The settings of a model.  logit_thresh, keep_or_null (u8 [h_mb][w_mb], written as 0 / 1; all 1 without a keep map)
  * and has_keep (1 when a keep map is set) may each be NULL.                                                         */
 int covahip_blobnet_get_post(covahip_ctx *ctx, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_keep);
+/* Per-model area threshold: the cc-threshold of bboxcc, which the reference carries per bboxcc element, i.e. per stream
+ * (cova-rs/gst-plugins/src/bboxcc, experiment/cova/config.yaml:59).  A model m of the loaded set has area[m]: 0 (the default)
+ * = unset, >= 1 = a threshold in macroblocks.  For a stack b that runs on model m
+ *     eff(b)    = area[m] >= 1 ? area[m] : the call's area_thresh
+ *     boxes[b]  = regionprops(mask[b], eff(b))     -- covahip_bboxcc semantics: 8-connected, OpenCV label order, area_px >= eff(b)
+ *     counts[b] = components that pass; the first min(count, max_boxes) are written
+ * byte for byte what the stack gives in a batch of its own with the scalar area_thresh = eff(b).  Logits and masks are not
+ * affected.  This is the P[t][a] of covahip_post_sweep: the number calibration prints is the number serving applies.
+ * It applies wherever a model produces boxes: covahip_filter_forward[_m], covahip_filter_forward_frames[_m],
+ * covahip_filter_forward_frames_packed[_m] and covahip_pipe_submit (the entries without _m run model 0 and use area[0]);
+ * covahip_blobnet_forward* makes no boxes and covahip_bboxcc has no model.  The threshold travels with the stack's other settings
+ * into the kernel that runs bboxcc: no launch, no copy and no synchronisation is added to a step, and while every model is unset
+ * (and has the defaults of covahip_blobnet_set_post) the forward runs the very kernels it ran before.
+ * Ordering and locking are those of covahip_blobnet_set_post: it waits for everything in flight on all lanes; batches
+ * submitted before the call see the old value, batches after it the new one.  covahip_blobnet_load[_set] reset every model to
+ * unset.  The two settings are independent: covahip_blobnet_set_post (post == NULL included) does not touch area[m], and
+ * covahip_blobnet_set_area does not touch the threshold or the keep map.
+ *   COVAHIP_ERR_INVALID_ARG: NULL ctx, model outside the set, negative value (nothing changes);
+ *   COVAHIP_ERR_NOT_LOADED: no model loaded.                                                                        */
+int covahip_blobnet_set_area(covahip_ctx *ctx, int model, int area_thresh /* 0 = unset */);
+int covahip_blobnet_get_area(covahip_ctx *ctx, int model, int *area_thresh);
 /* Calibration: which logit_thresh (covahip_blobnet_set_post) and which area threshold (the cc-threshold of bboxcc / cova) to
  * set for a camera.  covahip_post_sweep scores logits against labels (the MoG labels of a held-out set) at n_thresh mask
  * thresholds x n_area area thresholds in one pass on the GPU: pixel counts per threshold, and per cell the boxes serving would
@@ -255,6 +277,11 @@ typedef struct covahip_box {
  * same algorithm with that state in global memory -- same results, slower.        */
 int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, int area_thresh,
                    covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind);
+/* covahip_bboxcc with a threshold per frame.  area_thresh: HOST i32 [batch], frame b keeps pixel-count >= area_thresh[b]; read
+ * during the call (like model_ids), whatever mem_kind says about the other pointers; NULL is COVAHIP_ERR_INVALID_ARG.  Same
+ * limits, same kernel selection; frame b's result is covahip_bboxcc's of that frame alone at area_thresh[b], byte for byte. */
+int covahip_bboxcc_v(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, const int32_t *area_thresh,
+                     covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind);
 
 /* Fused hot path = nvinfer(BlobNet) -> maskcopy -> bboxcc for one batch: the mask
  * stays on the GPU.  logits/mask may be NULL.  bboxcc's limit (w <= 256) lies beyond the model's (w_mb <= 252):
