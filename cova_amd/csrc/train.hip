@@ -106,6 +106,19 @@ __device__ inline int64_t uniform64(int64_t v) {
 #define POFF (SET ? uniform64((int64_t)blockIdx.z * (int64_t)N_PARAMS) : (int64_t)0)
 __host__ __device__ inline int64_t red_stride(int maxB) { return 2 * (int64_t)(maxB > 128 ? maxB : 128); }
 
+// The posts of a trainer's models (include/covahip.h, "Training with a post"): device tables that only covahip_train_set_post
+// writes.  Model m's keep row starts at blockIdx.z * hw, so the row is workgroup-uniform.
+struct PostTab {
+    const uint8_t *keep;              // [K][hw], 0 / 1; all 1 for a model without a keep map or without a post
+    const float *thresh;              // [K] logit threshold of the counts
+    const uint8_t *flag;              // [K] 1: the model has a post; 0: its expressions are those of the form without
+};
+// The three kernels that read labels end in a parameter pack `Post... post`: empty, or one PostTab.  The empty pack is the
+// kernel of a trainer that never heard of posts, argument for argument and instruction for instruction; with a PostTab it is
+// the POST form, launched while any model of the trainer has a post.
+__device__ inline const PostTab *post_tab_of() { return nullptr; }
+__device__ inline const PostTab *post_tab_of(const PostTab &pt) { return &pt; }
+
 // slabs of a channel reduction over M = N*S elements per channel
 __host__ __device__ inline int red_slabs(int64_t M) {
     int64_t np = (M + RED_CHUNK - 1) / RED_CHUNK;
@@ -244,9 +257,13 @@ __global__ void k_sum_slabs(Mdl md, const float *__restrict__ slab, int64_t per,
 // Per-channel reductions of a [N][C][S] tensor: slab p of channel c covers elements [p*chunk, (p+1)*chunk) of its N*S.
 enum RedMode { R_SUM = 0, R_SQDEV = 1, R_BNBWD = 2, R_FINALW = 3, R_LOSS = 4 };
 // N = the model's batch and C = Cc, but for R_LOSS, where N = 1 and C = the model's batch (Cc: the grid's y extent).
-template <bool SET>
+// POST (R_LOSS only, S = hw): a macroblock outside the model's keep row enters I and S as y = p = 0, a select in front of the same
+// two statements, so a row of ones gives the sums of the form without, bit for bit, and its label byte reaches nothing.
+template <bool SET, class... Post>
 __global__ void k_reduce(Mdl md, int mode, int Cc, int64_t S, const float *__restrict__ x, const float *__restrict__ g, int Cg,
-                         const float *__restrict__ aux, const uint8_t *__restrict__ gt, float *__restrict__ part, int64_t solo_chunk) {
+                         const float *__restrict__ aux, const uint8_t *__restrict__ gt, float *__restrict__ part, int64_t solo_chunk,
+                         Post... post) {
+    constexpr bool POST = sizeof...(Post) != 0;
     __shared__ float sa[BLK], sb[BLK];
     const int Bm = model_b<SET>(md);
     const int N = mode == R_LOSS ? 1 : Bm, C = mode == R_LOSS ? Bm : Cc;
@@ -260,6 +277,7 @@ __global__ void k_reduce(Mdl md, int mode, int Cc, int64_t S, const float *__res
     if (aux) aux += blockIdx.z * STAT_STRIDE;
     if (gt) gt += (int64_t)model_first<SET>(md) * S;
     part += blockIdx.z * md.slab_stride;
+    const uint8_t *kp = POST ? post_tab_of(post...)->keep + (int64_t)blockIdx.z * S : nullptr;
     const int64_t e0 = (int64_t)p * chunk, e1 = e0 + chunk < M ? e0 + chunk : M;
     float a = 0.f, bsum = 0.f;
     for (int64_t e = e0 + threadIdx.x; e < e1; e += BLK) {
@@ -275,8 +293,9 @@ __global__ void k_reduce(Mdl md, int mode, int Cc, int64_t S, const float *__res
         } break;
         case R_FINALW: a += x[xi] * g[n * S + s]; break;
         case R_LOSS: {   // N = 1, C = batch: x = logits, gt = labels
-            const float pr = 1.f / (1.f + expf(-x[xi]));
-            const float yv = (float)gt[xi];
+            float pr = 1.f / (1.f + expf(-x[xi]));
+            float yv = (float)gt[xi];
+            if (POST && !kp[s]) pr = yv = 0.f;
             a += yv * pr;
             bsum += yv + pr;
         } break;
@@ -717,12 +736,21 @@ __global__ void k_final_fwd(Mdl md, const float *__restrict__ y, const float *__
 // A sample's loss: the Jaccard distance (1 - (I + sm) / (S - I + sm)) * sm of its I = sum y*p and S = sum y + p
 __device__ inline float jaccard_distance(float I, float S, float sm) { return (1.f - (I + sm) / (S - I + sm)) * sm; }
 
-// One position's share of the workgroup's TP / FP / FN counters (cnt[3] in LDS) at sigmoid > 0.5
-__device__ inline void count_confusion(unsigned *cnt, float pr, uint8_t label) {
-    const bool pos = pr > 0.5f, lab = label != 0;
+// One position's share of the workgroup's TP / FP / FN counters (cnt[3] in LDS)
+__device__ inline void count_pos(unsigned *cnt, bool pos, uint8_t label) {
+    const bool lab = label != 0;
     if (pos && lab) atomicAdd(&cnt[0], 1u);
     if (pos && !lab) atomicAdd(&cnt[1], 1u);
     if (!pos && lab) atomicAdd(&cnt[2], 1u);
+}
+// ... at sigmoid > 0.5
+__device__ inline void count_confusion(unsigned *cnt, float pr, uint8_t label) { count_pos(cnt, pr > 0.5f, label); }
+// ... of a trainer with a post: nothing outside the keep row; inside, a model with a post counts serving's logit > thresh (NaN is
+// background), a model without one sigmoid > 0.5 as above.  s = the position in its sample.
+__device__ inline void count_confusion_post(unsigned *cnt, const PostTab *pt, int64_t hw, int64_t s, float l, float pr,
+                                            const uint8_t *label) {
+    if (!pt->keep[(int64_t)blockIdx.z * hw + s]) return;
+    count_pos(cnt, pt->flag[blockIdx.z] ? l > pt->thresh[blockIdx.z] : pr > 0.5f, *label);
 }
 
 // loss = mean over samples of their Jaccard distance; red = [I per sample][S per sample]
@@ -737,11 +765,14 @@ __global__ void k_loss(Mdl md, const float *__restrict__ red, float sm, float *_
     loss[0] = acc / (float)B;
 }
 
-// d loss / d logit and d loss / d y3 (= dlogit * final kernel); TP / FP / FN counts at sigmoid > 0.5 (integer atomics)
-template <bool SET>
+// d loss / d logit and d loss / d y3 (= dlogit * final kernel); TP / FP / FN counts at sigmoid > 0.5 (integer atomics).
+// POST: d loss / d logit = 0 outside the keep row (a select behind the expression of the form without, whose I and S are the masked sums), the
+// counts by count_confusion_post.
+template <bool SET, class... Post>
 __global__ void k_final_bwd(Mdl md, const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
                             const float *__restrict__ fk, float *__restrict__ dlogit, float *__restrict__ dy, int64_t hw,
-                            float sm, unsigned long long *__restrict__ counts) {
+                            float sm, unsigned long long *__restrict__ counts, Post... post) {
+    constexpr bool POST = sizeof...(Post) != 0;
     __shared__ unsigned cnt[3];
     const int B = model_b<SET>(md);
     if ((int64_t)blockIdx.x * BLK >= (int64_t)B * hw) return;   // the whole workgroup: before the barrier
@@ -759,14 +790,16 @@ __global__ void k_final_bwd(Mdl md, const float *__restrict__ logit, const uint8
         const int64_t b = i / hw, s = i % hw;
         const float l = logit[i];
         const float pr = 1.f / (1.f + expf(-l));
-        const float yv = (float)gt[i];
+        const bool kept = !POST || post_tab_of(post...)->keep[(int64_t)blockIdx.z * hw + s];
+        const float yv = kept ? (float)gt[i] : 0.f;   // an ignored label byte is never looked at
         const float I = red[b], S = red[B + b];
         const float Nn = I + sm, D = S - I + sm;
         const float dp = -(sm / (float)B) * (yv * D - Nn * (1.f - yv)) / (D * D);
-        const float dl = dp * pr * (1.f - pr);
+        const float dl = kept ? dp * pr * (1.f - pr) : 0.f;
         dlogit[i] = dl;
         for (int c = 0; c < 16; c++) dy[(b * 16 + c) * hw + s] = dl * fk[c];
-        count_confusion(cnt, pr, gt[i]);
+        if (POST) count_confusion_post(cnt, post_tab_of(post...), hw, s, l, pr, gt + i);
+        else count_confusion(cnt, pr, gt[i]);
     }
     __syncthreads();
     if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
@@ -806,9 +839,12 @@ __global__ void k_bn_stat(Mdl md, const float *__restrict__ params, float *__res
 // TP / FP / FN at sigmoid > 0.5 as k_final_bwd counts them (integer atomics; the counters run on over the chunks of one
 // evaluation), and the per-sample Jaccard distance as k_loss forms it, to sample_loss[model][sample of the chunk].
 // red = [I per sample][S per sample] of the model's chunk.
-template <bool SET>
+// POST: the counts by count_confusion_post (red already holds the masked sums).
+template <bool SET, class... Post>
 __global__ void k_eval_tail(Mdl md, const float *__restrict__ logit, const uint8_t *__restrict__ gt, const float *__restrict__ red,
-                            int64_t hw, float sm, unsigned long long *__restrict__ counts, float *__restrict__ sample_loss) {
+                            int64_t hw, float sm, unsigned long long *__restrict__ counts, float *__restrict__ sample_loss,
+                            Post... post) {
+    constexpr bool POST = sizeof...(Post) != 0;
     __shared__ unsigned cnt[3];
     const int B = model_b<SET>(md);
     if ((int64_t)blockIdx.x * BLK >= (int64_t)B * hw) return;   // the whole workgroup: before the barrier
@@ -823,7 +859,11 @@ __global__ void k_eval_tail(Mdl md, const float *__restrict__ logit, const uint8
     if (threadIdx.x < 3) cnt[threadIdx.x] = 0;
     __syncthreads();
     const int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x;
-    if (i < (int64_t)B * hw) count_confusion(cnt, 1.f / (1.f + expf(-logit[i])), gt[i]);
+    if (i < (int64_t)B * hw) {
+        const float l = logit[i];
+        if (POST) count_confusion_post(cnt, post_tab_of(post...), hw, i % hw, l, 1.f / (1.f + expf(-l)), gt + i);
+        else count_confusion(cnt, 1.f / (1.f + expf(-l)), gt[i]);
+    }
     __syncthreads();
     if (threadIdx.x < 3 && cnt[threadIdx.x]) atomicAdd(&counts[threadIdx.x], (unsigned long long)cnt[threadIdx.x]);
 }
@@ -911,6 +951,13 @@ struct covahip_train {
     float *h_loss = nullptr;   // pinned [K]
     float *d_sample_loss = nullptr, *h_sample_loss = nullptr;   // evaluation: [K][max_batch] per-sample losses of a chunk (h_: pinned)
     unsigned long long *h_counts = nullptr;   // pinned [K][3]
+    // the models' posts: device tables (written by covahip_train_set_post only) and their host mirror
+    uint8_t *d_keep = nullptr, *d_post_flag = nullptr;   // [K][hw] 0 / 1, [K]
+    float *d_post_thresh = nullptr;                      // [K]
+    std::vector<uint8_t> post_keep, post_flag;           // [K][hw], [K] (a post without a keep map has a row of ones)
+    std::vector<float> post_thresh;                      // [K]
+    bool any_post = false;             // some model has a post: the passes launch the POST forms
+    PostTab post_tab() const { return PostTab{d_keep, d_post_thresh, d_post_flag}; }
 };
 
 namespace {
@@ -1015,7 +1062,11 @@ struct Run {
         const int Cmax = loss ? B : C;
         const int64_t M = (int64_t)(loss ? 1 : B) * S;
         const int NP = red_slabs(M);
-        KL(*this, k_reduce, (dim3(NP, Cmax, tr->K)), BLK, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP);
+        if (loss && tr->any_post)
+            KL(*this, k_reduce, (dim3(NP, Cmax, tr->K)), BLK, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP,
+                                                           tr->post_tab());
+        else
+            KL(*this, k_reduce, (dim3(NP, Cmax, tr->K)), BLK, mode, Cmax, S, x, g, Cg, aux, gt, tr->slab, (M + NP - 1) / NP);
         KL(*this, k_finalize, (g1(Cmax)), BLK, fmode, loss, Cmax, S, tr->slab, stat, stat_stride, g0, g1_, mov0, mov1,
                                                   tr->cfg.bn_momentum, tr->cfg.bn_eps);
     }
@@ -1130,8 +1181,12 @@ int run_step(covahip_train *tr, int B) {
     KL(r, k_loss, (dim3(1, 1, K)), 1, tr->red, sm, tr->d_loss);
 
     // ---------------------------------------------------------------- backward
-    KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
-                                            tr->d_counts);
+    if (tr->any_post)
+        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
+                                                     tr->d_counts, tr->post_tab());
+    else
+        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
+                                                tr->d_counts);
     if (!dec_fz(NL - 1)) {
         r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
         r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fb, nullptr, nullptr, nullptr);
@@ -1220,7 +1275,11 @@ int run_eval(covahip_train *tr, int B) {
     for (DropS &d : f.drop) d = DropS{0, 0u, 1.f, 0};   // the identity (see k_bn_stat)
     if (int rc = forward(r, f)) return rc;
     const int64_t hw = (int64_t)tr->H[0] * tr->W[0];
-    KL(r, k_eval_tail, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
+    if (tr->any_post)
+        KL(r, k_eval_tail, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts,
+                                                     tr->d_sample_loss, tr->post_tab());
+    else
+        KL(r, k_eval_tail, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, hw, tr->cfg.smooth, tr->d_counts, tr->d_sample_loss);
     r.ok();
     return r.rc;
 }
@@ -1337,7 +1396,13 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     TA(tr->d_stack, B * TT * hw0 * 4);
     TA(tr->d_gt, B * hw0);
     TA(tr->d_tab, K);
+    TA(tr->d_keep, (size_t)K * hw0);
+    TA(tr->d_post_flag, K);
+    TA(tr->d_post_thresh, K);
 #undef TA
+    tr->post_keep.assign((size_t)K * hw0, 1);
+    tr->post_flag.assign(K, 0);
+    tr->post_thresh.assign(K, 0.f);
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_tab, (size_t)K * sizeof(MStep), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_loss, (size_t)K * sizeof(float), hipHostMallocDefault));
     COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&tr->h_sample_loss, (size_t)B * sizeof(float), hipHostMallocDefault));
@@ -1351,6 +1416,9 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, (size_t)K * N_PARAMS * sizeof(float), s));
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_m, 0, (size_t)K * N_PARAMS * sizeof(float), s));
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->adam_v, 0, (size_t)K * N_PARAMS * sizeof(float), s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->d_keep, 1, (size_t)K * hw0, s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->d_post_flag, 0, (size_t)K, s));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->d_post_thresh, 0, (size_t)K * sizeof(float), s));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // tmask leaves scope
     return COVAHIP_OK;
 }
@@ -1631,6 +1699,43 @@ int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan) {
     if (!tr || !plan) return COVAHIP_ERR_INVALID_ARG;
     plan->frozen_groups = tr->frozen;
     plan->bn_inference = tr->bn_inf;
+    return COVAHIP_OK;
+}
+
+int covahip_train_set_post(covahip_train *tr, int model, const covahip_blobnet_post *post) {
+    if (!tr || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
+    const size_t hw = (size_t)tr->H[0] * tr->W[0];
+    std::vector<uint8_t> row(hw, 1);   // no post, or a post without a keep map: everything is kept
+    if (post) {
+        if (!std::isfinite(post->logit_thresh)) return COVAHIP_ERR_INVALID_ARG;
+        if (post->keep) {
+            size_t kept = 0;
+            for (size_t i = 0; i < hw; i++) kept += row[i] = post->keep[i] != 0;
+            if (!kept) return COVAHIP_ERR_INVALID_ARG;   // nothing to train on
+        }
+    }
+    const uint8_t flag = post ? 1 : 0;
+    const float thresh = post ? post->logit_thresh : 0.f;
+    covahip_ctx *ctx = tr->ctx;
+    if (int rc = enter(ctx)) return rc;
+    // every entry point of the trainer is synchronous: nothing of it is in flight that could read the tables
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_keep + (size_t)model * hw, row.data(), hw, hipMemcpyHostToDevice, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_post_thresh + model, &thresh, sizeof thresh, hipMemcpyHostToDevice, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_post_flag + model, &flag, 1, hipMemcpyHostToDevice, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // row, thresh and flag leave scope
+    std::copy(row.begin(), row.end(), tr->post_keep.begin() + (size_t)model * hw);
+    tr->post_flag[model] = flag;
+    tr->post_thresh[model] = thresh;
+    tr->any_post = std::find(tr->post_flag.begin(), tr->post_flag.end(), (uint8_t)1) != tr->post_flag.end();
+    return COVAHIP_OK;
+}
+
+int covahip_train_get_post(covahip_train *tr, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_post) {
+    if (!tr || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
+    const size_t hw = (size_t)tr->H[0] * tr->W[0];
+    if (logit_thresh) *logit_thresh = tr->post_thresh[model];
+    if (keep_or_null) std::memcpy(keep_or_null, tr->post_keep.data() + (size_t)model * hw, hw);
+    if (has_post) *has_post = tr->post_flag[model];
     return COVAHIP_OK;
 }
 

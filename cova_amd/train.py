@@ -38,6 +38,18 @@ per-model files named as --set -o writes them).  --freeze takes layer groups (en
 their weights are not trained and no gradient work is spent on them.  --freeze-bn keeps every BatchNorm layer on the moving
 statistics of the base model instead of the statistics of a batch of 4.  --resume with the same flags continues exactly; the
 plan is not part of the checkpoint.
+
+The camera's post (include/covahip.h, "Training with a post"): train and score a model with the ignore region and the mask
+threshold it is served with,
+
+    python -m cova_amd.calibrate --weights blobnet.cvhw -o post.json --ignore-rects 0,0,320,48 HELDOUT.tfrecord
+    python -m cova_amd.train NEWCAM.tfrecord -o adapted.cvhw --init blobnet.cvhw --post post.json
+    python -m cova_amd.train --eval-only adapted.cvhw TODAY.tfrecord --post post.json
+
+--post takes the sidecar calibrate wrote (with --set: one file for every model, or a directory of <stem>.json per model, named
+as --set -o names weight files); --ignore-rects L,T,W,H[+L,T,W,H...] and --mask-threshold P give the same for a camera without
+a sidecar.  Macroblocks in the ignore region take no part in the loss, its gradient or the metrics, and the metrics count
+logit > threshold as serving does.  The post is not part of the checkpoint either: --resume takes it from the command line again.
 """
 from __future__ import annotations
 
@@ -639,7 +651,7 @@ class TrainerSet(_State):
         return self._step(d_stack, d_gt, batches, lrs, L.MEM_DEVICE)
 
     def metrics(self, k: int):
-        """(TP, FP, FN) of model k's last step at sigmoid > 0.5."""
+        """(TP, FP, FN) of model k's last step at sigmoid > 0.5; with a post, at its threshold over its keep map."""
         v = (C.c_int64 * 3)()
         L.check(self._lib.covahip_train_metrics_m(self.handle, k, v), "covahip_train_metrics_m")
         return int(v[0]), int(v[1]), int(v[2])
@@ -666,6 +678,33 @@ class TrainerSet(_State):
 
     def _set_step_counts(self, steps):
         self.step_counts = list(steps)
+
+    def set_post(self, k: int, *, prob_thresh=None, logit_thresh=None, keep=None) -> None:
+        """Model k's post from the next step or evaluation on (covahip_train_set_post), with the keywords of
+        BlobNetInfer.set_post -- calibrate.load_post(path, h, w)[0] can be passed as **kw.  keep: u8 [h][w], non-zero = the
+        macroblock takes part in the loss, its gradient and the metrics (None: all; see keep_from_rects).  The threshold, a
+        probability or a logit (neither: 0), is where metrics() and evaluate() count a pixel as foreground: logit > threshold,
+        serving's expression; the loss does not depend on it.  The post is not part of the trainer state: set it again after
+        creating the trainer a state is loaded into."""
+        from .elements import BlobNetInfer
+        post = L.BlobNetPost(BlobNetInfer.post_logit_thresh(prob_thresh, logit_thresh), None)
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if keep.shape != (self.h, self.w):
+                raise ValueError(f"keep must be [{self.h}][{self.w}], got {keep.shape}")
+            post.keep = keep.ctypes.data
+        L.check(self._lib.covahip_train_set_post(self.handle, k, C.byref(post)), "covahip_train_set_post", self.ctx.handle)
+
+    def reset_post(self, k: int) -> None:
+        """Model k has no post again: the whole grid, and the metrics at sigmoid > 0.5."""
+        L.check(self._lib.covahip_train_set_post(self.handle, k, None), "covahip_train_set_post", self.ctx.handle)
+
+    def get_post(self, k: int):
+        """Model k's post: (logit_thresh, keep u8 [h][w] of 0 / 1 -- all 1 without a keep map), or None without a post."""
+        thr, has = C.c_float(), C.c_int()
+        keep = np.empty((self.h, self.w), dtype=np.uint8)
+        L.check(self._lib.covahip_train_get_post(self.handle, k, C.byref(thr), keep.ctypes.data, C.byref(has)), "covahip_train_get_post")
+        return (thr.value, keep) if has.value else None
 
     def evaluate(self, records_per_model, want_sample_loss: bool = False, want_logits: bool = False):
         """Scores every model on its own samples in ONE call (one launch of each kernel per chunk of max_batch samples per
@@ -788,6 +827,17 @@ class Trainer(_State):
     def _set_step_counts(self, steps):
         self._set._set_step_counts(steps)
 
+    def set_post(self, *, prob_thresh=None, logit_thresh=None, keep=None) -> None:
+        """TrainerSet.set_post of the one model."""
+        self._set.set_post(0, prob_thresh=prob_thresh, logit_thresh=logit_thresh, keep=keep)
+
+    def reset_post(self) -> None:
+        self._set.reset_post(0)
+
+    def get_post(self):
+        """(logit_thresh, keep u8 [h][w]) or None without a post."""
+        return self._set.get_post(0)
+
     def step(self, stack: np.ndarray, gt: np.ndarray, lr: float | None = None) -> float:
         """One training step on stack u8 [B][4h][w][4] with labels u8 [B][h][w]; returns the loss before the update."""
         stack, gt, batches = self._set._pack([(stack, gt)])
@@ -859,7 +909,24 @@ def parse_args(argv=None):
                                                        "commas, or encoder / decoder")
     ap.add_argument("--freeze-bn", action="store_true", help="every BatchNorm layer normalises with its moving statistics and "
                                                              "leaves them alone")
+    ap.add_argument("--post", metavar="FILE", help="the camera's calibration sidecar (python -m cova_amd.calibrate -o): train and "
+                                                   "score with its ignore region and mask threshold (with --set: one file for "
+                                                   "every model, or a directory of <stem>.json per model, named as --set -o names "
+                                                   "weight files)")
+    ap.add_argument("--ignore-rects", type=_rects, metavar="L,T,W,H[+...]", help="pixel rectangles of the camera's ignore region, "
+                                                                                 "for a camera without a sidecar")
+    ap.add_argument("--mask-threshold", type=float, metavar="P", help="the camera's mask threshold as a probability, for a camera "
+                                                                      "without a sidecar")
     a = ap.parse_args(argv)
+    if a.post and (a.ignore_rects is not None or a.mask_threshold is not None):
+        ap.error("--post carries the ignore region and the threshold: it excludes --ignore-rects and --mask-threshold")
+    if a.mask_threshold is not None and not 0.0 < a.mask_threshold < 1.0:
+        ap.error("--mask-threshold is a probability strictly between 0 and 1")
+    if a.post:
+        try:
+            post_paths(a.records if a.as_set else None, a.post)
+        except ValueError as e:
+            ap.error(str(e))
     if a.eval_only:
         if a.resume:
             ap.error("--resume continues a training; --eval-only trains nothing")
@@ -885,6 +952,57 @@ def parse_args(argv=None):
     except ValueError as e:
         ap.error(str(e))
     return a
+
+
+def _rects(text):
+    """--ignore-rects: L,T,W,H[+L,T,W,H...] in pixels, as blobnetfilter's pad-ignore-rects writes them."""
+    out = []
+    for part in text.split("+"):
+        try:
+            vals = [int(v) for v in part.split(",")]
+        except ValueError:
+            vals = []
+        if len(vals) != 4:
+            raise argparse.ArgumentTypeError(f"a rectangle is LEFT,TOP,WIDTH,HEIGHT in pixels, got {part!r}")
+        out.append(tuple(vals))
+    return out
+
+
+def post_paths(records, post: str):
+    """--post: the sidecar of every model, in argument order (records None: the one model of a run without --set).  A file
+    serves every model; a directory (--set only) holds <stem>.json per model, named as --set -o names weight files (set_jobs).
+    A missing file is a ValueError."""
+    if not os.path.isdir(post):
+        if not os.path.isfile(post):
+            raise ValueError(f"--post {post}: no such file")
+        return [post] * (1 if records is None else len(records))
+    if records is None:
+        raise ValueError(f"--post {post}: a directory of sidecars needs --set")
+    paths = [os.path.splitext(p)[0] + ".json" for _, p in set_jobs(records, post)]
+    missing = [p for p in paths if not os.path.isfile(p)]
+    if missing:
+        raise ValueError(f"--post {post}: no sidecar {', '.join(missing)}")
+    return paths
+
+
+def post_settings(a, n_models: int):
+    """The set_post keywords of every model from --post, or from --ignore-rects / --mask-threshold (the same for every model);
+    None when the command line names no post."""
+    if a.post:
+        from .calibrate import load_post
+        return [load_post(p, a.h_mb, a.w_mb)[0] for p in post_paths(a.records if a.as_set else None, a.post)]
+    if a.ignore_rects is None and a.mask_threshold is None:
+        return None
+    from .elements import keep_from_rects
+    kw = {"prob_thresh": a.mask_threshold, "keep": keep_from_rects(a.h_mb, a.w_mb, a.ignore_rects) if a.ignore_rects else None}
+    return [kw] * n_models
+
+
+def _apply_posts(trainer, posts) -> None:
+    """posts (post_settings) onto a TrainerSet, or onto a Trainer's one model."""
+    if posts is not None:
+        for k, kw in enumerate(posts):
+            getattr(trainer, "_set", trainer).set_post(k, **kw)
 
 
 def _plan_kw(a) -> dict:
@@ -941,14 +1059,20 @@ def main_eval(a) -> int:
         with open(path, "rb") as f:
             flats.append(W.from_bytes(f.read()))
         records.append(_load(files, a)[1])
+    posts = post_settings(a, len(jobs))
     ctx = Context(a.device)
     if a.as_set:
         ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=flats, max_batch=a.batch)
+        _apply_posts(ts, posts)
         evs = ts.evaluate(records)
     else:
         ts = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, weights_flat=flats[0])
+        _apply_posts(ts, posts)
         evs = [ts.evaluate(records[0])]
-    for (_, path), ev in zip(jobs, evs):
+    for k, ((_, path), ev) in enumerate(zip(jobs, evs)):
+        if posts is not None:
+            thr, keep = getattr(ts, "_set", ts).get_post(k)
+            ev["post"] = {"logit_thresh": thr, "ignored": int((keep == 0).sum())}
         print(json.dumps({"weights": path, **ev}))
     ts.close()
     ctx.close()
@@ -987,10 +1111,12 @@ def main_set(a) -> int:
         print(f"model {k}: {n_frames} frames -> {rec[0].shape[0]} samples of {a.h_mb}x{a.w_mb}"
               + (f", {val[k][0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
     os.makedirs(a.output, exist_ok=True)
+    posts = post_settings(a, len(jobs))
     ctx = Context(a.device)
     init = [_read_weights(p) for p in init_paths(a.records, a.init)] if a.init else None
     ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=init, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))],
                     max_batch=a.batch, **_plan_kw(a))
+    _apply_posts(ts, posts)
     start = _resume(ts, a, len(jobs))
     ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)
@@ -1018,9 +1144,11 @@ def main(argv=None) -> int:
         records, val = split_tail(*records, a.val_frac)
     print(f"{n_frames} frames -> {records[0].shape[0]} samples of {a.h_mb}x{a.w_mb}"
           + (f", {val[0].shape[0]} to validate" if val is not None else ""), file=sys.stderr)
+    posts = post_settings(a, 1)
     ctx = Context(a.device)
     tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed, weights_flat=_read_weights(a.init) if a.init else None,
                  **_plan_kw(a))
+    _apply_posts(tr, posts)
     start = _resume(tr, a, 1)
     tr.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)

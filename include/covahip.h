@@ -543,6 +543,40 @@ typedef struct covahip_train_plan {
 } covahip_train_plan;
 int covahip_train_set_plan(covahip_train *tr, const covahip_train_plan *plan);
 int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan);
+/* Training with a post: the camera's ignore region and mask threshold (covahip_blobnet_set_post, the sidecar of
+ * covahip_post_sweep) in the loss and the metrics, so that a model is trained on, and scored as, what serving lets through.
+ * Each model of a trainer (solo or set) has its own post: device tables of u8 [K][h_mb * w_mb] keep maps, a threshold and a
+ * flag per model, written by covahip_train_set_post only -- no launch is added to a step or an evaluation chunk and nothing is
+ * uploaded per step.  For a model WITH a post and keep'[y,x] = keep ? keep[y,x] != 0 : 1:
+ *   Loss (the step's, and sample_loss of an evaluation): I = sum over keep' of y*p, S = sum over keep' of (y + p); everything
+ *   else as without: (1 - (I + s) / (S - I + s)) * s per sample, the step's loss the mean over the model's batch.
+ *   Backward: d loss / d logit = 0 where !keep', elsewhere the expression of a step without a post with the masked I and S.
+ *   Nothing downstream changes: the weight-gradient reductions and all other layers run as they are.
+ *   Metrics (covahip_train_metrics[_m] and the evaluation result): TP / FP / FN over keep' pixels only, with
+ *   pos = logit > logit_thresh -- serving's expression, so NaN counts as background -- and lab = gt != 0.
+ *   The threshold affects the counts only, never the loss.
+ * A model WITHOUT a post: everything exactly as described above, pos = sigmoid(logit) > 0.5f included.
+ * covahip_train_set_post: takes effect from the next step or evaluation; may be set, changed or removed (post == NULL) between
+ * steps.  Like the training plan the post is NOT part of the state blob: covahip_train_load_state does not touch it, and a
+ * resumed run sets it again.  All errors are checked on the host and leave the trainer untouched: COVAHIP_ERR_INVALID_ARG for a
+ * NULL trainer, a model outside the set, a non-finite threshold, or a keep map without a single non-zero byte (there would be
+ * nothing to train on).
+ * covahip_train_get_post: logit_thresh (0 without a post), keep_or_null (u8 [h_mb][w_mb], written as 0 / 1; all 1 without a
+ * keep map or a post) and has_post may each be NULL.
+ *   Contract E -- no post is no post.  A trainer that never sets a post, or has removed every one, launches the kernels it
+ *   launched before posts existed: it is that trainer, bit for bit.
+ *   Contract F -- an all-ones keep map changes no float.  With a post whose keep map is all non-zero or NULL, at any threshold,
+ *   losses, gradients, weights, Adam moments, moving statistics, sample_loss and logits are BIT-IDENTICAL to the model without a
+ *   post; only the counts follow the threshold.  (An ignored pixel is skipped by a select inside the loops and slabs of the
+ *   reductions; their order is the same.)
+ *   Contract G -- what is ignored does not exist.  Changing the label bytes at ignored macroblocks to any values changes no
+ *   output bit: loss, gradients, weights, counts, sample_loss.
+ *   Sets: model k of a set with post k is bit-identical to the solo trainer with that post, and a post on model k changes
+ *   nothing of model j.  Models with and without a post share each launch: the masked kernel forms run while any model of the
+ *   trainer has a post, and a model without one keeps its expressions through its flag.
+ *   Contracts A - D hold with "the model" read as "the model and its post"; a post combines with any training plan. */
+int covahip_train_set_post(covahip_train *tr, int model, const covahip_blobnet_post *post /* NULL = no post */);
+int covahip_train_get_post(covahip_train *tr, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_post);
 void covahip_train_destroy(covahip_train *tr);
 
 /* ------------------------------------------------------------ MoG labels
