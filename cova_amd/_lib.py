@@ -101,6 +101,10 @@ class SweepResult(C.Structure):
     _fields_ = [("samples", C.c_int64), ("gt_objects", C.c_int64), ("gt_truncated", C.c_int64)]
 
 
+class HeatCfg(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_thresh", C.c_int32), ("logit_thresh", C.c_void_p)]
+
+
 class MogCfg(C.Structure):
     _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
                 ("var_threshold", C.c_float)]
@@ -239,6 +243,9 @@ PROTOTYPES = {
     "covahip_train_get_post": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P, C.POINTER(C.c_int)]),
     "covahip_train_destroy": (None, [_P]),
     "covahip_post_sweep": (C.c_int, [_P, C.POINTER(SweepCfg), _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(SweepResult)]),
+    "covahip_post_heat_begin": (C.c_int, [_P, C.POINTER(HeatCfg)]),
+    "covahip_post_heat_add": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
+    "covahip_post_heat_end": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),

@@ -102,6 +102,7 @@ void covahip_ctx_destroy(covahip_ctx *ctx) {
     if (ctx->stage_in) hipFree(ctx->stage_in);
     if (ctx->stage_out) hipFree(ctx->stage_out);
     if (ctx->sweep_buf) hipFree(ctx->sweep_buf);
+    if (ctx->heat_buf) hipFree(ctx->heat_buf);
     if (ctx->cc_area_dev) hipFree(ctx->cc_area_dev);
     if (ctx->cc_area_host) hipHostFree(ctx->cc_area_host);
     if (ctx->cc_area_ev) hipEventDestroy(ctx->cc_area_ev);

@@ -89,6 +89,13 @@ struct covahip_ctx {
     CtxLane &lane() { return lanes[cur_lane]; }
     struct { int nbands, nbuf; } enc_plan[4] = {};   // developer override of the encoder band plan per level (0 = automatic)
     covahip_blobnet *blobnet = nullptr;
+    // covahip_post_heat_*: the open heat's counters, u32 [2 T + 1][h][w] (fire planes, both planes, the label plane)
+    void *heat_buf = nullptr;
+    size_t heat_bytes = 0;
+    bool heat_open = false;
+    int heat_h = 0, heat_w = 0, heat_T = 0;
+    float heat_thresh[64] = {};
+    int64_t heat_samples = 0;
 };
 
 #define COVAHIP_CHECK_HIP(ctx, expr)                                                        \

@@ -258,6 +258,35 @@ typedef struct covahip_sweep_result {
  * Synchronous.  Outputs are OVERWRITTEN with this call's counts; the caller adds calls up. */
 int covahip_post_sweep(covahip_ctx *ctx, const covahip_sweep_cfg *cfg, const float *logits, const uint8_t *gt, int n,
                        int mem_kind, int64_t *pixel, covahip_sweep_cell *cells, int64_t *truncated, covahip_sweep_result *out);
+/* Ignore region from heat: how often each macroblock fires.  The sweep above cannot see a burned-in clock: MoG marks it in every
+ * frame, a model trained on those labels fires there, and its box hits the label box at every threshold.  What gives it away is
+ * persistence, so covahip_post_heat_* count per macroblock, per mask threshold and over all samples of a begin ... end bracket
+ *   fire[t][y][x]  = the samples with logit > logit_thresh[t]   -- covahip_post_sweep's expression WITHOUT a keep map (the heat
+ *                    must show what a keep map would hide); the compare is strict, NaN is background, +inf fires everywhere
+ *   both[t][y][x]  = the samples with logit > logit_thresh[t] and gt != 0
+ *   gt_fire[y][x]  = the samples with gt != 0
+ * so that per macroblock fp = fire - both and fn = gt_fire - both, and the sums over y, x of (both, fire - both, gt_fire - both)
+ * are pixel[t] of covahip_post_sweep without keep on the same inputs.  All values are integer counts and exact, and do not
+ * depend on how the samples are split over covahip_post_heat_add calls.  python -m cova_amd.calibrate --auto-ignore turns the
+ * table into the camera's ignore rectangles ("Ignore region from heat").
+ * The counters (u32) live in the ctx, on the device, between begin and end.  begin zeroes them; a begin while a heat is open
+ * starts over.  add runs on the primary stream behind all lanes and is synchronous, like the sweep: when it returns the
+ * caller's next forward may overwrite the logits.  end copies the counters out, widens them to i64 and closes the heat; every
+ * output pointer may be NULL.  The calls read no model state and write none.
+ * Errors, all checked on the host before the GPU is touched: COVAHIP_ERR_INVALID_ARG for a NULL ctx, cfg or list, a non-finite
+ * or not strictly ascending list, n_thresh outside 1..64, h or w < 1, n < 0, NULL logits or gt with n > 0, another mem_kind,
+ * add or end without begin, more than INT32_MAX samples in one heat; COVAHIP_ERR_UNSUPPORTED for h * w > 2^24.  A failed begin
+ * leaves an open heat as it was.  n == 0 is COVAHIP_OK and changes nothing. */
+typedef struct covahip_heat_cfg {
+    int32_t h, w;                    /* grid */
+    int32_t n_thresh;                /* 1..64 */
+    const float *logit_thresh;       /* HOST [n_thresh], finite, strictly ascending (copied by begin) */
+} covahip_heat_cfg;
+int covahip_post_heat_begin(covahip_ctx *ctx, const covahip_heat_cfg *cfg);
+/* logits f32 [n][h][w], gt u8 [n][h][w]; mem_kind applies to both. */
+int covahip_post_heat_add(covahip_ctx *ctx, const float *logits, const uint8_t *gt, int n, int mem_kind);
+/* HOST outputs: fire, both i64 [n_thresh][h][w]; gt_fire i64 [h][w]; samples: the number of samples added. */
+int covahip_post_heat_end(covahip_ctx *ctx, int64_t *fire, int64_t *both, int64_t *gt_fire, int64_t *samples);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc
