@@ -105,6 +105,14 @@ class HeatCfg(C.Structure):
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_thresh", C.c_int32), ("logit_thresh", C.c_void_p)]
 
 
+class MonitorCfg(C.Structure):
+    _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_models", C.c_int32), ("max_boxes", C.c_int32), ("attach", C.c_int32),
+                ("every", C.c_int32)]
+
+
+MONITOR_AREA_BINS = 16
+
+
 class MogCfg(C.Structure):
     _fields_ = [("src_w", C.c_int32), ("src_h", C.c_int32), ("n_streams", C.c_int32), ("history", C.c_int32),
                 ("var_threshold", C.c_float)]
@@ -246,6 +254,10 @@ PROTOTYPES = {
     "covahip_post_heat_begin": (C.c_int, [_P, C.POINTER(HeatCfg)]),
     "covahip_post_heat_add": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "covahip_post_heat_end": (C.c_int, [_P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "covahip_monitor_begin": (C.c_int, [_P, C.POINTER(MonitorCfg)]),
+    "covahip_monitor_add": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
+    "covahip_monitor_read": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "covahip_monitor_end": (C.c_int, [_P]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),
@@ -270,6 +282,7 @@ DEV_PROTOTYPES = {
     "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),
     "covahip_dev_mog_state": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "covahip_dev_mog_set_stage_budget": (C.c_int, [_P, _SZ]),
+    "covahip_dev_monitor_slice": (C.c_int, [_P, C.c_int]),
 }
 
 _lib = None

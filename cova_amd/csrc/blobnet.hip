@@ -48,6 +48,7 @@ void covahip_blobnet_destroy(covahip_ctx *ctx) {
     if (!ctx->blobnet) return;
     hipSetDevice(ctx->device);
     covahip_sync_all(ctx);
+    covahip_monitor_close(ctx, true);   // an attached monitor counts THIS model's batches: it goes with it
     free_model(ctx, ctx->blobnet);
     ctx->blobnet = nullptr;
 }
@@ -569,7 +570,11 @@ static int filter_placed(covahip_ctx *ctx, covahip_blobnet *m, const uint8_t *d_
     } else {
         in.stack = d_src;
     }
-    return filter_dev(ctx, in, batch, d_logits, d_mask, true, area_thresh, d_boxes, d_counts, max_boxes, n_frames > 0 ? nullptr : model_ids);
+    int rc = filter_dev(ctx, in, batch, d_logits, d_mask, true, area_thresh, d_boxes, d_counts, max_boxes, n_frames > 0 ? nullptr : model_ids);
+    // the serving monitor (monitor.hip): the batch's mask, counts and boxes are on the device and this is the stream that wrote them
+    if (rc == COVAHIP_OK && batch > 0 && ctx->mon && ctx->mon->attached && !ctx->mon_suspended)
+        rc = covahip_monitor_hook(ctx, d_mask, d_counts, d_boxes, max_boxes, model_ids, batch);
+    return rc;
 }
 
 // Shared body of covahip_filter_forward / covahip_filter_forward_frames: `src` is the stacked tensor (n_frames == 0)
@@ -747,6 +752,8 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
             rc = filter_placed(ctx, m, d_frames, n_frames, stack_index, batch, area_thresh, d_boxes, d_counts, max_boxes, nullptr, d_mask);
     };
     bool capturing = false;
+    const bool was_suspended = ctx->mon_suspended;
+    ctx->mon_suspended = true;   // the probe's steps are not served batches, and a counted launch must not be captured
     do {
         if (!hip_ok(hipEventCreate(&e0), "hipEventCreate") || !hip_ok(hipEventCreate(&e1), "hipEventCreate")) break;
         run(3);
@@ -769,6 +776,7 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
         if (rc || !hip_ok(hipEventRecord(e1, ctx->stream), "hipEventRecord") || !hip_ok(hipEventSynchronize(e1), "hipEventSynchronize")) break;
         hip_ok(hipEventElapsedTime(ms_graph, e0, e1), "hipEventElapsedTime");
     } while (false);
+    ctx->mon_suspended = was_suspended;
     if (capturing) (void)hipStreamEndCapture(ctx->stream, &graph);
     if (exec) (void)hipGraphExecDestroy(exec);
     if (graph) (void)hipGraphDestroy(graph);

@@ -87,6 +87,7 @@ void covahip_ctx_destroy(covahip_ctx *ctx) {
     hipSetDevice(ctx->device);
     covahip_sync_all(ctx);
     covahip_blobnet_destroy(ctx);
+    covahip_monitor_close(ctx, false);   // (a stand-alone monitor; the model took an attached one with it)
     for (int i = 0; i < 16; i++) {
         if (ctx->t_start[i]) hipEventDestroy(ctx->t_start[i]);
         if (ctx->t_stop[i]) hipEventDestroy(ctx->t_stop[i]);

@@ -47,6 +47,24 @@ struct CtxLane {
     int cc_first_cap = 0;                // first-pass capacity the statistics last decided on (0: none yet)
 };
 
+// covahip_monitor_* (monitor.hip): the open serving monitor of a ctx.  Everything a counted batch touches is allocated by begin.
+struct MonTable {                    // order / slice table of a mixed batch too large for the kernel arguments
+    int32_t *d_tab = nullptr;
+    int32_t *h_tab = nullptr;        // pinned host copy it is uploaded from
+    size_t cap = 0;                  // capacity of both, in ints
+    hipEvent_t ev = nullptr;         // upload of h_tab done (the next call may overwrite it)
+    std::vector<int32_t> last;       // the table resident in d_tab (an unchanged table is not uploaded again)
+};
+struct CovahipMonitor {
+    int h = 0, w = 0, n_models = 0, max_boxes = 0, every = 1;
+    bool attached = false;
+    // i64 counters on the device: frames [M] | boxes [M] | frames_with_boxes [M] | truncated [M] | area_hist [M][16] | fire [M][h][w]
+    unsigned long long *d_tab = nullptr;
+    size_t words = 0;
+    int64_t batches_seen = 0, batches_counted = 0;
+    MonTable lane[COVAHIP_MAX_LANES];   // attached: one per lane (lane 0's also serves the primary stream); stand-alone: [0] only
+};
+
 struct covahip_ctx {
     int device = 0;
     hipStream_t primary = nullptr;   // the ctx's own stream
@@ -96,6 +114,11 @@ struct covahip_ctx {
     int heat_h = 0, heat_w = 0, heat_T = 0;
     float heat_thresh[64] = {};
     int64_t heat_samples = 0;
+    // covahip_monitor_*: the open monitor (null: none), the developer override of its slice length (0 = automatic), and whether
+    // filter steps bypass it (covahip_dev_graph_probe: a captured step must not carry a counted launch into its replays)
+    CovahipMonitor *mon = nullptr;
+    int mon_slice = 0;
+    bool mon_suspended = false;
 };
 
 #define COVAHIP_CHECK_HIP(ctx, expr)                                                        \
@@ -138,6 +161,13 @@ uint32_t covahip_crc32c(const uint8_t *p, size_t n);
 // d_area: optional device array i32 [batch], frame b's own area threshold (null: area_thresh for every frame)
 int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, int h, int w, int area_thresh,
                           covahip_box *d_boxes, int32_t *d_counts, int max_boxes, const int32_t *d_area = nullptr);
+
+// monitor.hip
+// The hook at the end of a filter step that succeeded, on ctx->stream (the lane that ran the batch): sees the batch and, every
+// `every`-th time, counts it with one launch.  Only called while an attached monitor is open and not suspended.
+int covahip_monitor_hook(covahip_ctx *ctx, const uint8_t *d_mask, const int32_t *d_counts, const covahip_box *d_boxes, int max_boxes,
+                         const uint8_t *model_ids, int batch);
+void covahip_monitor_close(covahip_ctx *ctx, bool attached_only);   // drains the ctx and frees the monitor (if any)
 
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);

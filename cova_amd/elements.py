@@ -258,6 +258,25 @@ class BlobNetInfer:
         L.check(self._lib.covahip_blobnet_get_area(self.ctx.handle, model, C.byref(v)), "covahip_blobnet_get_area", self.ctx.handle)
         return v.value
 
+    def monitor_begin(self, every: int = 1):
+        """Opens the serving monitor on this model or set (covahip_monitor_begin, attached): from now on every `every`-th batch of
+        filter / filter_full / filter_frames / the _device forms / a FilterPipe is counted per model -- fire map, boxes per frame,
+        box areas -- behind the batch on its own lane.  An open monitor starts over; loading another model closes it."""
+        from . import monitor
+        monitor.begin(self.ctx, self.h, self.w, self.num_models, 0, attach=True, every=every)
+
+    def monitor_read(self, reset: bool = False) -> dict:
+        """The monitor's counters (covahip_monitor_read; cova_amd.monitor.read): frames, fire, boxes, frames_with_boxes,
+        truncated, area_hist as int64 arrays per model, batches_seen and batches_counted as ints.  Waits for everything the ctx
+        has in flight; reset zeroes the counters afterwards."""
+        from . import monitor
+        return monitor.read(self.ctx, reset)
+
+    def monitor_end(self):
+        """Closes the monitor (covahip_monitor_end)."""
+        from . import monitor
+        monitor.end(self.ctx)
+
     def set_enc_plan(self, level: int, nbands: int, nbuf: int = 1):
         """Developer switch (include/covahip_dev.h): band plan of encoder level 1..3; nbands = 0 -> automatic."""
         L.check(self._lib.covahip_blobnet_set_enc_plan(self.ctx.handle, level, nbands, nbuf), "covahip_blobnet_set_enc_plan")

@@ -287,6 +287,56 @@ int covahip_post_heat_begin(covahip_ctx *ctx, const covahip_heat_cfg *cfg);
 int covahip_post_heat_add(covahip_ctx *ctx, const float *logits, const uint8_t *gt, int n, int mem_kind);
 /* HOST outputs: fire, both i64 [n_thresh][h][w]; gt_fire i64 [h][w]; samples: the number of samples added. */
 int covahip_post_heat_end(covahip_ctx *ctx, int64_t *fire, int64_t *both, int64_t *gt_fire, int64_t *samples);
+/* Serving monitor: how a deployed model behaves, from what every filter step already has on the device -- no decode, no labels.
+ * Per model m of a set and over all COUNTED samples b (model m's) since begin or the last reset
+ *   frames[m]            += 1
+ *   fire[m][y][x]        += mask[b][y][x] != 0       -- the mask AS SERVED (the model's threshold and keep map applied); any
+ *                                                       non-zero byte counts once
+ *   boxes[m]             += counts[b]                -- the components that pass the stack's effective area threshold
+ *   frames_with_boxes[m] += counts[b] > 0
+ *   truncated[m]         += counts[b] > max_boxes
+ *   area_hist[m][k]      += the boxes i < min(counts[b], max_boxes) with min(15, floor(log2(boxes[b][i].area_px))) == k
+ *                           (an area below 2 is bin 0)
+ * All values are integer counts and exact; they are additive over batches and depend neither on the lanes nor on how the samples
+ * are split over calls.  The counters are 64-bit and live in the ctx, on the device, between begin and end ((20 + h * w) * 8
+ * bytes per model: 16.7 MB for 256 models of 68 x 120).  python -m cova_amd.monitor reports them per camera (DESIGN.md section
+ * 4, "Serving monitor").
+ * attach = 1: the monitor counts the filter batches of THIS ctx's loaded model or set -- every entry that produces boxes from a
+ * model: covahip_filter_forward[_m], the _frames[_m] / _frames_packed[_m] entries and covahip_pipe_submit, host or device
+ * pointers; covahip_blobnet_forward* makes no boxes and is not counted.  Batch i since begin or the last reset (0-based, in
+ * submission order) is counted iff i % every == 0, with one kernel launch behind the batch's own on the lane that ran it: no
+ * synchronisation, no allocation.  A failed or empty (batch == 0) call is neither seen nor counted.  max_boxes is the call's.
+ * begin needs a loaded model whose grid and number of models equal the cfg (COVAHIP_ERR_INVALID_ARG otherwise,
+ * COVAHIP_ERR_NOT_LOADED with nothing loaded); covahip_blobnet_load[_set] and destroying the model close an attached monitor.
+ * attach = 0: the monitor is fed by covahip_monitor_add alone (on an attached one add is COVAHIP_ERR_INVALID_ARG) and survives
+ * loads.  add runs on the primary stream behind all lanes and is synchronous, like covahip_post_heat_add.  With no monitor open,
+ * or one that is not attached, a filter step launches exactly the kernels it launches without this interface.
+ * read waits for everything the ctx has in flight on all lanes (like covahip_blobnet_set_post), copies the counters out and, with
+ * reset != 0, zeroes the tables and both batch counters; it does not close the monitor.  begin while a monitor is open starts
+ * over; a failed begin leaves an open monitor as it was.  end closes it.
+ * Errors, all checked on the host before the GPU is touched: COVAHIP_ERR_INVALID_ARG for a NULL ctx or cfg, h or w < 1, n_models
+ * outside 1..COVAHIP_MAX_MODELS, attach other than 0 / 1, every < 1 (attached), max_boxes < 0 (stand-alone), n < 0, NULL mask or
+ * counts with n > 0, NULL boxes while max_boxes > 0, an id >= n_models, another mem_kind, add, read or end without begin;
+ * COVAHIP_ERR_UNSUPPORTED for h * w > 2^24.  n == 0 is COVAHIP_OK and changes nothing. */
+typedef struct covahip_monitor_cfg {
+    int32_t h, w;        /* grid */
+    int32_t n_models;    /* 1..COVAHIP_MAX_MODELS */
+    int32_t max_boxes;   /* >= 0: row length of the boxes arrays that will be fed (stand-alone add); ignored when attached */
+    int32_t attach;      /* 1: count every `every`-th filter batch of THIS ctx's loaded model / set; 0: fed by covahip_monitor_add only */
+    int32_t every;       /* >= 1; attach only: filter batch i since begin (0-based, in submission order) is counted iff i % every == 0 */
+} covahip_monitor_cfg;
+#define COVAHIP_MONITOR_AREA_BINS 16
+struct covahip_box;   /* (bboxcc, below) */
+int covahip_monitor_begin(covahip_ctx *ctx, const covahip_monitor_cfg *cfg);
+/* mask u8 [n][h][w], counts i32 [n], boxes [n][max_boxes] (mem_kind applies to the three; boxes may be NULL with max_boxes == 0);
+ * model_ids: HOST u8 [n], read during the call, or NULL = model 0. */
+int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *counts, const struct covahip_box *boxes,
+                        const uint8_t *model_ids, int n, int mem_kind);
+/* HOST outputs, each may be NULL: frames, boxes, frames_with_boxes, truncated i64 [n_models]; fire i64 [n_models][h][w];
+ * area_hist i64 [n_models][16]; batches_seen / batches_counted: attached filter batches since begin or the last reset. */
+int covahip_monitor_read(covahip_ctx *ctx, int reset, int64_t *frames, int64_t *fire, int64_t *boxes, int64_t *frames_with_boxes,
+                         int64_t *truncated, int64_t *area_hist, int64_t *batches_seen, int64_t *batches_counted);
+int covahip_monitor_end(covahip_ctx *ctx);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc

@@ -84,6 +84,11 @@ int covahip_dev_mog_state(struct covahip_mog *m, int stream, float *W, float *V,
  * least one per launch; the results do not depend on it.  (tests/test_gpu_mog_branches.py) */
 int covahip_dev_mog_set_stage_budget(struct covahip_mog *m, size_t bytes);
 
+/* Serving monitor (covahip_monitor_*): samples per slice of its kernel; 0 restores the automatic choice (enough workgroups for
+ * every CU, at least 16 samples).  The counts do not depend on it; a slice longer than 255 samples makes the kernel's packed
+ * byte counters spill, which the automatic choice reaches only with batches of thousands.  (tests/test_gpu_monitor.py) */
+int covahip_dev_monitor_slice(covahip_ctx *ctx, int samples);
+
 #ifdef __cplusplus
 }
 #endif
