@@ -282,6 +282,9 @@ DEV_PROTOTYPES = {
     "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),
     "covahip_dev_mog_state": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "covahip_dev_mog_set_stage_budget": (C.c_int, [_P, _SZ]),
+    "covahip_dev_mog_post_masks": (C.c_int, [_P, _P, C.c_int, _P]),
+    "covahip_dev_mog_set_post_form": (C.c_int, [_P, C.c_int, C.c_int]),
+    "covahip_dev_mog_band_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "covahip_dev_monitor_slice": (C.c_int, [_P, C.c_int]),
 }
 

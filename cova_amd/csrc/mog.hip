@@ -2,7 +2,8 @@
 // close 4x4, open 6x6, hole fill and the ::8 subsample to the labels `tfrecordsink gt=` reads.  The arithmetic is stated in
 // include/covahip.h ("MoG labels"); tests/mog_ref.py is its numpy float32 restatement and the kernels match it bit for bit.
 // This file has the C-ABI and the kernels of the reference grid (every source resized to 640x360, 45x80 labels); the
-// macroblock grid's kernels (half-resolution working image) are mog_grid.hip, and both instantiate the device code of mog_dev.h.
+// macroblock grid's kernels (half-resolution working image) are mog_grid.hip and, for 1440p and 4K sources, mog_band.hip (the
+// post kernel in row bands); all three instantiate the device code of mog_dev.h.
 //
 //   k_mog_update  one lane per working-size pixel and stream.  The five modes (weight, variance, mean) are read once per call
 //                 into registers, every frame of the call is applied to them, and they are written back once.  The source is
@@ -96,15 +97,36 @@ int src_kind(int w, int h) {
     if (w == 640 && h == 360) return 0;
     if (w == 1280 && h == 720) return 1;
     if (w == 1920 && h == 1080) return 2;
+    if (w == 2560 && h == 1440) return 3;      // 3, 4: the macroblock grid only
+    if (w == 3840 && h == 2160) return 4;
     return -1;
 }
+
+// LDS of the banded post kernel beside its two planes: 16 bytes of flags and the column sweep's carries (256 bytes per word column)
+size_t band_lds_fixed(int mw) { return 16 + (size_t)256 * (mw / 64); }
+
+// the widest staged window of the banded post kernel: two planes of rows + 16 rows within a CU's LDS
+int band_max_rows(int mw) {
+    return (int)((COVAHIP_MOG_BAND_LDS_MAX - band_lds_fixed(mw)) / ((size_t)2 * (mw / 64) * 8)) - 16;
+}
+
+// the automatic band plan: as few bands as fit, of equal height
+void band_plan(int mw, int mh, int *rows, int *bands) {
+    const int mx = std::min(band_max_rows(mw), mh);
+    *bands = (mh + mx - 1) / mx;
+    *rows = (mh + *bands - 1) / *bands;
+}
+
+size_t band_lds_bytes(int mw, int mh, int rows) { return (size_t)2 * std::min(rows + 16, mh) * (mw / 64) * 8 + band_lds_fixed(mw); }
 
 }  // namespace
 
 struct covahip_mog {
     covahip_ctx *ctx = nullptr;
     covahip_mog_cfg cfg{};
-    int kind = 0;                  // reference-grid kernels: source kind (src_kind); -1 = the kernels of mog_grid.hip
+    int kind = 0;                  // reference-grid kernels: source kind (src_kind); -1 = the kernels of mog_grid.hip / mog_band.hip
+    bool banded = false;           // kind -1: the post kernel of mog_band.hip (always at working widths 1280 and 1920)
+    int band_rows = 0;             // its band height; 0 = the automatic plan
     int grid = COVAHIP_MOG_GRID_REFERENCE;
     int mw = MW, mh = MH, lw = LW, lh = LH;   // working size and labels
     size_t npix = NPIX, nword = NWORD, nlab = NLAB, state_bytes = G::STATE_BYTES;
@@ -112,7 +134,8 @@ struct covahip_mog {
     std::vector<int64_t> n;        // frames each stream has seen
     uint8_t *state = nullptr;      // [S][state_bytes]
     void *bits = nullptr, *filled = nullptr, *d_frames = nullptr, *d_labels = nullptr, *d_par = nullptr;
-    size_t bits_bytes = 0, filled_bytes = 0, frames_bytes = 0, labels_bytes = 0, par_bytes = 0;
+    void *plane = nullptr;         // banded post: the mask after the morphology, as bits
+    size_t bits_bytes = 0, filled_bytes = 0, frames_bytes = 0, labels_bytes = 0, par_bytes = 0, plane_bytes = 0;
     void *h_par = nullptr;         // pinned: (alphaT, prune) [F][S], then n_valid [S]
     size_t h_par_bytes = 0;
     int last_frames = 0;
@@ -122,7 +145,7 @@ struct covahip_mog {
 namespace {
 
 void free_mog(covahip_mog *m) {
-    for (void *p : {(void *)m->state, m->bits, m->filled, m->d_frames, m->d_labels, m->d_par})
+    for (void *p : {(void *)m->state, m->bits, m->filled, m->plane, m->d_frames, m->d_labels, m->d_par})
         if (p) hipFree(p);
     if (m->h_par) hipHostFree(m->h_par);
     delete m;
@@ -132,6 +155,8 @@ int launch_update(covahip_mog *m, const uint8_t *d_frames, int f0, int nf, int S
     covahip_ctx *ctx = m->ctx;
     const dim3 grid(NPIX / UPD_BLOCK, S);
     auto *bits = static_cast<unsigned long long *>(m->bits);
+    if (m->kind < 0 && m->mw > 960)
+        return covahip_mog_band_update(ctx, m->mw, d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold, bits);
     if (m->kind < 0)
         return covahip_mog_grid_update(ctx, m->mw, d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold, bits);
     {
@@ -145,6 +170,27 @@ int launch_update(covahip_mog *m, const uint8_t *d_frames, int f0, int nf, int S
         else
             k_mog_update<2><<<grid, UPD_BLOCK, 0, ctx->stream>>>(d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S,
                                                                  m->cfg.var_threshold, bits);
+    }
+    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+
+// the post launch on the call's raw planes (m->bits): filled planes and labels of FS (frame, stream) pairs
+int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, size_t FS) {
+    covahip_ctx *ctx = m->ctx;
+    auto *bits = static_cast<const unsigned long long *>(m->bits);
+    auto *filled = static_cast<unsigned long long *>(m->filled);
+    if (m->banded) {
+        if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->nword * 8)) return rc;
+        int rows = m->band_rows, bands = 0;
+        if (!rows) band_plan(m->mw, m->mh, &rows, &bands);
+        return covahip_mog_band_post(ctx, m->mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
+                                     rows);
+    }
+    if (m->kind < 0) return covahip_mog_grid_post(ctx, m->mw, bits, filled, d_labels, d_nv, S, FS);
+    {
+        ProfScope ps(ctx, "mog_post");
+        k_mog_post<<<dim3((unsigned)FS), POST_BLOCK, 0, ctx->stream>>>(bits, filled, d_labels, d_nv, S);
     }
     COVAHIP_CHECK_HIP(ctx, hipGetLastError());
     return COVAHIP_OK;
@@ -175,7 +221,7 @@ int covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int gr
         !(cfg->var_threshold > 0.f))
         return COVAHIP_ERR_INVALID_ARG;
     int kind = src_kind(cfg->src_w, cfg->src_h);
-    if (kind < 0) return COVAHIP_ERR_UNSUPPORTED;
+    if (kind < 0 || (kind > 2 && grid != COVAHIP_MOG_GRID_MACROBLOCK)) return COVAHIP_ERR_UNSUPPORTED;
     // the macroblock grid works at half the source: 1280x720 is then the reference grid itself (kind 1, the same kernels)
     const bool half = grid == COVAHIP_MOG_GRID_MACROBLOCK && kind != 1;
     if (half) kind = -1;
@@ -195,6 +241,7 @@ int covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int gr
         m->nword = m->npix / 64;
         m->nlab = (size_t)m->lw * m->lh;
         m->state_bytes = (size_t)5 * NMIX * m->npix * 4 + m->npix;
+        m->banded = m->mw > 960;
     }
     m->src_bytes = (size_t)cfg->src_w * cfg->src_h * 3;
     m->n.assign(cfg->n_streams, 0);
@@ -269,16 +316,7 @@ int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const
         // labels of frames past n_valid stay as the caller has them
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d_labels, labels, FS * NLAB, hipMemcpyHostToDevice, ctx->stream));
     }
-    if (m->kind < 0) {
-        if (int rc = covahip_mog_grid_post(ctx, m->mw, static_cast<const unsigned long long *>(m->bits),
-                                           static_cast<unsigned long long *>(m->filled), d_labels, d_nv, S, FS))
-            return rc;
-    } else {
-        ProfScope ps(ctx, "mog_post");
-        k_mog_post<<<dim3((unsigned)FS), POST_BLOCK, 0, ctx->stream>>>(static_cast<const unsigned long long *>(m->bits),
-                                                                       static_cast<unsigned long long *>(m->filled), d_labels, d_nv, S);
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    if (int rc = launch_post(m, d_labels, d_nv, S, FS)) return rc;
     if (mem_kind == COVAHIP_MEM_HOST)
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(labels, d_labels, FS * NLAB, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -338,6 +376,55 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
 int covahip_dev_mog_set_stage_budget(covahip_mog *m, size_t bytes) {
     if (!m) return COVAHIP_ERR_INVALID_ARG;
     m->stage_budget = bytes ? bytes : STAGE_BUDGET;
+    return COVAHIP_OK;
+}
+
+int covahip_dev_mog_post_masks(covahip_mog *m, const uint8_t *raw, int n_frames, uint8_t *labels) {
+    if (!m || !raw || !labels || n_frames < 1) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = m->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    const int S = m->cfg.n_streams;
+    const size_t FS = (size_t)n_frames * S, NWORD = m->nword, NLAB = m->nlab;
+    std::vector<unsigned long long> w(FS * NWORD);
+    for (size_t i = 0; i < FS * NWORD; i++) {
+        unsigned long long v = 0;
+        for (int b = 0; b < 64; b++) v |= (unsigned long long)(raw[i * 64 + b] != 0) << b;
+        w[i] = v;
+    }
+    const std::vector<int32_t> nv(S, n_frames);
+    if (int rc = covahip_ensure_buffer(ctx, &m->d_par, &m->par_bytes, S * sizeof(int32_t))) return rc;
+    if (int rc = covahip_ensure_buffer(ctx, &m->bits, &m->bits_bytes, FS * NWORD * 8)) return rc;
+    if (int rc = covahip_ensure_buffer(ctx, &m->filled, &m->filled_bytes, FS * NWORD * 8)) return rc;
+    if (int rc = covahip_ensure_buffer(ctx, &m->d_labels, &m->labels_bytes, FS * NLAB)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(m->d_par, nv.data(), S * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(m->bits, w.data(), FS * NWORD * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (int rc = launch_post(m, static_cast<uint8_t *>(m->d_labels), static_cast<const int32_t *>(m->d_par), S, FS)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(labels, m->d_labels, FS * NLAB, hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    m->last_frames = n_frames;
+    return COVAHIP_OK;
+}
+
+int covahip_dev_mog_set_post_form(covahip_mog *m, int banded, int band_rows) {
+    if (!m || (banded != 0 && banded != 1)) return COVAHIP_ERR_INVALID_ARG;
+    const bool has_banded = m->kind < 0 && m->mw >= 960, has_resident = !(m->kind < 0 && m->mw > 960);
+    if (banded ? !has_banded : !has_resident || band_rows != 0) return COVAHIP_ERR_INVALID_ARG;
+    if (banded && band_rows != 0 &&
+        (band_rows < 16 || band_rows > m->mh || band_lds_bytes(m->mw, m->mh, band_rows) > COVAHIP_MOG_BAND_LDS_MAX))
+        return COVAHIP_ERR_INVALID_ARG;
+    m->banded = banded != 0;
+    m->band_rows = band_rows;
+    return COVAHIP_OK;
+}
+
+int covahip_dev_mog_band_plan(int work_w, int work_h, int *rows, int *bands, size_t *lds_bytes) {
+    if (work_w < 64 || work_w % 64 || work_h < 16 || band_max_rows(work_w) < 16) return COVAHIP_ERR_INVALID_ARG;
+    int r = 0, b = 0;
+    band_plan(work_w, work_h, &r, &b);
+    if (rows) *rows = r;
+    if (bands) *bands = b;
+    if (lds_bytes) *lds_bytes = band_lds_bytes(work_w, work_h, r);
     return COVAHIP_OK;
 }
 

@@ -1,5 +1,6 @@
-// Device code shared by the MoG label kernels of mog.hip (the reference grid: 640x360 working frames) and mog_grid.hip (the
-// macroblock grid: half-resolution working frames): the MOG2 pixel update, the update kernel's body, and the morphology and
+// Device code shared by the MoG label kernels of mog.hip (the reference grid: 640x360 working frames), mog_grid.hip (the
+// macroblock grid: half-resolution working frames) and mog_band.hip (the macroblock grid of 1440p and 4K sources, whose planes
+// are worked on in row bands): the MOG2 pixel update, the update kernel's body, and the morphology and
 // hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
 // include/covahip.h ("MoG labels").
 //
@@ -198,6 +199,19 @@ __device__ __forceinline__ void update_body(Load load, const uint8_t *__restrict
     st[G::OFF_N + p] = (uint8_t)nm;
 }
 
+// working pixel (x, y) of a frame of 2 MW x 2 MH: the rounded mean of its 2x2 block (the macroblock grid's load)
+template <int MW>
+struct LoadHalf {
+    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
+        const uint8_t *a = fr + ((size_t)(2 * y) * (2 * MW) + 2 * x) * 3;
+        const uint8_t *b = a + 2 * MW * 3;
+        unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
+        unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
+        unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
+        return {(float)s0, (float)s1, (float)s2};
+    }
+};
+
 // ------------------------------------------------------------------------------------------------ post passes
 // Bit x of word w of a row is pixel 64 w + x.  A k x k window at x covers x - k/2 .. x + k - 1 - k/2 (OpenCV's anchor, the same
 // offsets for dilate and erode); outside the image is 0 for dilate and 1 for erode.  BLOCK = threads of the workgroup.
@@ -339,6 +353,185 @@ __device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long
     }
 }
 
+// ------------------------------------------------------------------------------------------------ post passes on a row band
+// The same passes on a window of `nrows` whole rows of a frame ROWW words wide (mog_band.hip: frames whose planes do not fit
+// LDS).  The window is clipped to the frame, so a row beyond it is either outside the frame, where the neutral element is
+// what the pass wants, or a row of the frame that was not staged: then the neutral element is a stand-in, and the rows it
+// reaches (K/2 rows at the top, K - 1 - K/2 at the bottom of the window, per vertical pass) are not valid any more.  The
+// caller stages enough rows around its band for the valid region to end on the band.
+template <int ROWW, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void hpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
+    constexpr int A = K / 2, B = K - 1 - K / 2;
+    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
+    const int nword = nrows * ROWW;
+    for (int i = threadIdx.x; i < nword; i += BLOCK) {
+        const int w = i % ROWW;
+        const unsigned long long c = in[i];
+        const unsigned long long pv = w > 0 ? in[i - 1] : NEU;
+        const unsigned long long nx = w < ROWW - 1 ? in[i + 1] : NEU;
+        unsigned long long r = c;
+#pragma unroll
+        for (int d = -A; d <= B; d++) {
+            if (d == 0) continue;
+            const unsigned long long v = d > 0 ? (c >> d) | (nx << (64 - d)) : (c << -d) | (pv >> (64 + d));
+            r = DIL ? (r | v) : (r & v);
+        }
+        out[i] = r;
+    }
+}
+
+template <int ROWW, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void vpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
+    constexpr int A = K / 2, B = K - 1 - K / 2;
+    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
+    const int nword = nrows * ROWW;
+    for (int i = threadIdx.x; i < nword; i += BLOCK) {
+        const int y = i / ROWW;
+        unsigned long long r = in[i];
+#pragma unroll
+        for (int d = -A; d <= B; d++) {
+            if (d == 0) continue;
+            const unsigned long long v = (y + d >= 0 && y + d < nrows) ? in[i + d * ROWW] : NEU;
+            r = DIL ? (r | v) : (r & v);
+        }
+        out[i] = r;
+    }
+}
+
+// close 4x4 and open 6x6 of the window in X (LDS, nrows x ROWW words, behind a barrier), with Y (the same size) as the other
+// plane of the ping-pong.  The result is in X, behind a barrier; of its rows, 10 at the top and 6 at the bottom are valid only
+// where the window ends on the frame edge.
+template <int ROWW, int BLOCK>
+__device__ __forceinline__ void morph_band(unsigned long long *X, unsigned long long *Y, int nrows) {
+    hpass_band<ROWW, BLOCK, true, 4>(X, Y, nrows);
+    __syncthreads();
+    vpass_band<ROWW, BLOCK, true, 4>(Y, X, nrows);
+    __syncthreads();
+    hpass_band<ROWW, BLOCK, false, 4>(X, Y, nrows);
+    __syncthreads();
+    vpass_band<ROWW, BLOCK, false, 4>(Y, X, nrows);
+    __syncthreads();
+    hpass_band<ROWW, BLOCK, false, 6>(X, Y, nrows);
+    __syncthreads();
+    vpass_band<ROWW, BLOCK, false, 6>(Y, X, nrows);
+    __syncthreads();
+    hpass_band<ROWW, BLOCK, true, 6>(X, Y, nrows);
+    __syncthreads();
+    vpass_band<ROWW, BLOCK, true, 6>(Y, X, nrows);
+    __syncthreads();
+}
+
+// One direction of the band's column sweep on FILL_SEG row segments per word column: r(y) = T(y) | (~A(y) & r(y - 1)) is linear in
+// OR, so every lane first sweeps its own segment with nothing carried in and notes what leaves the segment (`out`) and which
+// columns are background in all of its rows (`pass`: what a carry would cross the segment through); the carry into a segment
+// then follows from the segments before it, and a second walk ORs in what the carry reaches, ending where it is blocked.  The
+// result is that of one lane walking the whole column.  carry: LDS, 2 x FILL_SEG x ROWW words; all threads call this.
+constexpr int FILL_SEG = 16;
+template <int ROWW, bool DOWN>
+__device__ __forceinline__ bool col_sweep_band(const unsigned long long *A, unsigned long long *T, int nrows,
+                                               unsigned long long *carry) {
+    const int tid = threadIdx.x;
+    const bool active = tid < ROWW * FILL_SEG;
+    const int w = tid % ROWW, sg = tid / ROWW;
+    const int len = (nrows + FILL_SEG - 1) / FILL_SEG;
+    const int ya = sg * len < nrows ? sg * len : nrows, yb = ya + len < nrows ? ya + len : nrows;   // this lane's rows (may be none)
+    unsigned long long *out = carry, *pass = carry + FILL_SEG * ROWW;
+    bool ch = false;
+    if (active) {
+        unsigned long long r = 0, p = ~0ull;
+        for (int k = 0; k < yb - ya; k++) {
+            const int i = (DOWN ? ya + k : yb - 1 - k) * ROWW + w;
+            const unsigned long long na = ~A[i], old = T[i], nw = old | (na & r);
+            if (nw != old) {
+                T[i] = nw;
+                ch = true;
+            }
+            r = nw;
+            p &= na;
+        }
+        out[tid] = r;
+        pass[tid] = p;
+    }
+    __syncthreads();
+    if (active) {
+        unsigned long long d = 0;                      // what the segments walked before this one carry into it
+        if (DOWN)
+            for (int k = 0; k < sg; k++) d = out[k * ROWW + w] | (pass[k * ROWW + w] & d);
+        else
+            for (int k = FILL_SEG - 1; k > sg; k--) d = out[k * ROWW + w] | (pass[k * ROWW + w] & d);
+        for (int k = 0; k < yb - ya && d; k++) {
+            const int i = (DOWN ? ya + k : yb - 1 - k) * ROWW + w;
+            d &= ~A[i];
+            const unsigned long long old = T[i], nw = old | d;
+            if (nw != old) {
+                T[i] = nw;
+                ch = true;
+            }
+        }
+    }
+    __syncthreads();
+    return ch;
+}
+
+// The two-phase loop of post_planes on a band: T (LDS, nrows x ROWW words, seeded by the caller, behind a barrier) grows
+// through the background ~A (LDS, the same size) until nothing changes.  Returns whether T changed at all (the same value in
+// every thread); ends behind a barrier.  The column sweep runs on FILL_SEG row segments per column (above).  The row fill keeps
+// the row in 2 x ROWW words per lane: the pass towards higher x adds what it reaches to the seeds of the pass towards lower x,
+// which fills the same runs as two passes from the same seeds.
+template <int ROWW, int BLOCK>
+__device__ __forceinline__ bool fill_band(const unsigned long long *A, unsigned long long *T, int nrows, int *changed,
+                                          unsigned long long *carry) {
+    static_assert(ROWW * FILL_SEG <= BLOCK, "one lane per word column and row segment");
+    const int tid = threadIdx.x;
+    bool any = false;
+    for (;;) {
+        if (tid == 0) *changed = 0;
+        __syncthreads();
+        // vertical: down, then up (each ends behind a barrier)
+        const bool chd = col_sweep_band<ROWW, true>(A, T, nrows, carry);
+        const bool chu = col_sweep_band<ROWW, false>(A, T, nrows, carry);
+        if (chd || chu) *changed = 1;
+        // horizontal: one lane per row fills every background run that holds a reached pixel, carrying across words
+        for (int y = tid; y < nrows; y += BLOCK) {
+            unsigned long long m[ROWW], sd[ROWW];
+#pragma unroll
+            for (int w = 0; w < ROWW; w++) {
+                m[w] = ~A[y * ROWW + w];
+                sd[w] = T[y * ROWW + w];
+            }
+            unsigned long long c = 0;
+#pragma unroll
+            for (int w = 0; w < ROWW; w++) {           // towards higher x: m + seeds ripples through each seeded run
+                const unsigned long long s1 = sd[w] | (c & m[w] & 1ull);
+                const unsigned long long t = m[w] + s1;
+                sd[w] = ((t ^ m[w]) | s1) & m[w];       // the seeds and what they reached: a superset of sd[w]
+                c = t < m[w] ? 1ull : 0ull;           // carried out of bit 63: the run goes on in the next word
+            }
+            c = 0;
+            bool ch = false;
+#pragma unroll
+            for (int w = ROWW - 1; w >= 0; w--) {      // towards lower x: the same on bit-reversed words
+                const unsigned long long rm = __builtin_bitreverse64(m[w]);
+                const unsigned long long s1 = __builtin_bitreverse64(sd[w]) | (c & rm & 1ull);
+                const unsigned long long t = rm + s1;
+                const unsigned long long nw = __builtin_bitreverse64(((t ^ rm) | s1) & rm);
+                c = t < rm ? 1ull : 0ull;
+                if (nw != T[y * ROWW + w]) {
+                    T[y * ROWW + w] = nw;
+                    ch = true;
+                }
+            }
+            if (ch) *changed = 1;
+        }
+        __syncthreads();
+        const int again = *changed;
+        __syncthreads();
+        if (!again) break;
+        any = true;
+    }
+    return any;
+}
+
 }  // namespace mogdev
 
 // ------------------------------------------------------------------------------------------------ host side (mog_grid.hip)
@@ -349,3 +542,12 @@ int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, siz
                             const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           uint8_t *labels, const int32_t *nvalid, int S, size_t FS);
+// The banded kernels (mog_band.hip) at working width `mw`: 1280 and 1920, whose planes do not fit LDS, and 960 (the post
+// kernel only, for comparison with the resident one).  plane: one more plane per (frame, stream), FS * NWORD words, for the
+// mask after the morphology; rows: the band height, 16 .. working height, with 2 x min(rows + 16, height) staged rows, the
+// flags and the column sweep's carries within COVAHIP_MOG_BAND_LDS_MAX (else COVAHIP_ERR_UNSUPPORTED).
+constexpr size_t COVAHIP_MOG_BAND_LDS_MAX = 160 * 1024 - 64;
+int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
+                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
+int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
+                          unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);

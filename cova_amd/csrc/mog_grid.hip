@@ -29,19 +29,6 @@ namespace {
 
 using namespace mogdev;
 
-// working pixel (x, y) of a frame of 2 MW x 2 MH: the rounded mean of its 2x2 block
-template <int MW>
-struct LoadHalf {
-    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
-        const uint8_t *a = fr + ((size_t)(2 * y) * (2 * MW) + 2 * x) * 3;
-        const uint8_t *b = a + 2 * MW * 3;
-        unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
-        unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
-        unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
-        return {(float)s0, (float)s1, (float)s2};
-    }
-};
-
 // frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
 template <int MW, int MH>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__restrict__ frames, size_t src_bytes,

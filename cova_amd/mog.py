@@ -2,13 +2,15 @@
 
   MogLabeler   covahip_mog_*: per-pixel MOG2 at 640x360, close 4x4, open 6x6, hole fill and the ::8 subsample to the 45x80
                labels `tfrecordsink gt=` reads, for several independent videos (streams) per call.  grid="macroblock" works
-               at half the source instead and labels the source's own macroblocks: 68x120 for 1920x1080
+               at half the source instead and labels the source's own macroblocks: 68x120 for 1920x1080, and it alone
+               takes 2560x1440 (90x160 labels) and 3840x2160 (135x240)
   label_dims   (label_h, label_w) of a source size on either grid, without a GPU
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
 
     ffmpeg -i VIDEO -f rawvideo -pix_fmt bgr24 - | python -m cova_amd.mog --size 1280x720 -:VIDEO_gt.dump
     python -m cova_amd.mog --size 1280x720 a.bgr b.bgr:labels_b.dump ... [--streams S] [--chunk F]
     python -m cova_amd.mog --size 1920x1080 --grid macroblock IN.bgr ...      (68x120 labels: what 1080p records need)
+    python -m cova_amd.mog --size 3840x2160 --grid macroblock IN.bgr ...      (135x240 labels; 2560x1440 gives 90x160)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
 to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Pixel decoding is not done here:
@@ -32,14 +34,15 @@ NMIX = 5
 SIZES = ((640, 360), (1280, 720), (1920, 1080))
 MAX_STREAMS = 1024
 GRIDS = {"reference": 0, "macroblock": 1}       # COVAHIP_MOG_GRID_*
+GRID_SIZES = {"reference": SIZES, "macroblock": SIZES + ((2560, 1440), (3840, 2160))}   # the source sizes each grid takes
 
 
 def work_dims(w: int, h: int, grid: str = "reference"):
     """(work_w, work_h) of a w x h source: 640x360 on the reference grid, half the source on the macroblock grid."""
     if grid not in GRIDS:
         raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
-    if (w, h) not in SIZES:
-        raise ValueError(f"unsupported size {w}x{h}: one of " + ", ".join(f"{a}x{b}" for a, b in SIZES))
+    if (w, h) not in GRID_SIZES[grid]:
+        raise ValueError(f"unsupported size {w}x{h} on the {grid} grid: one of " + ", ".join(f"{a}x{b}" for a, b in GRID_SIZES[grid]))
     return (WORK_W, WORK_H) if grid == "reference" else (w // 2, h // 2)
 
 
@@ -56,12 +59,15 @@ def _ptr(a: np.ndarray) -> int:
 class MogLabeler:
     """covahip_mog_* over one ctx: `streams` videos of src_w x src_h BGR24 frames advance per `apply` call.  `grid` is
     "reference" (640x360 working frames, 45x80 labels) or "macroblock" (half the source, one label per macroblock of the
-    source); work_w, work_h, label_h and label_w say which shapes the labeller takes and gives."""
+    source; 2560x1440 and 3840x2160 sources are this grid's alone); work_w, work_h, label_h and label_w say which shapes the
+    labeller takes and gives."""
 
     def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0,
                  grid: str = "reference"):
         if grid not in GRIDS:
             raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
+        if (src_w, src_h) in GRID_SIZES["macroblock"] and (src_w, src_h) not in GRID_SIZES[grid]:
+            raise ValueError(f"{src_w}x{src_h} needs grid='macroblock'")     # (any other size is the library's to refuse)
         self.ctx = ctx
         self._lib = L.lib()
         cfg = L.MogCfg()
@@ -123,6 +129,22 @@ class MogLabeler:
     def set_stage_budget(self, nbytes: int):
         """Developer switch: device bytes of host frames staged per update launch of `apply` (0 = the default, 1 GiB)."""
         L.check(self._lib.covahip_dev_mog_set_stage_budget(self.handle, nbytes), "covahip_dev_mog_set_stage_budget")
+
+    def set_post_form(self, banded: bool, band_rows: int = 0):
+        """Developer switch: the post kernel of a macroblock-grid labeller, banded (band_rows rows per band, 0 = the automatic
+        plan) or resident; the results do not depend on it."""
+        L.check(self._lib.covahip_dev_mog_set_post_form(self.handle, int(bool(banded)), band_rows), "covahip_dev_mog_set_post_form")
+
+    def post_masks(self, raw: np.ndarray) -> np.ndarray:
+        """Developer entry: the post launch alone on raw u8 [F][S][work_h][work_w] (non-zero = foreground) -> labels; debug_masks
+        then gives the raw / filled masks of this call.  The model is untouched."""
+        raw = np.ascontiguousarray(raw, dtype=np.uint8)
+        if raw.ndim != 4 or raw.shape[1:] != (self.streams, self.work_h, self.work_w):
+            raise ValueError(f"raw of shape {raw.shape}, expected [F]{[self.streams, self.work_h, self.work_w]}")
+        labels = np.zeros((raw.shape[0], self.streams, self.label_h, self.label_w), np.uint8)
+        L.check(self._lib.covahip_dev_mog_post_masks(self.handle, _ptr(raw), raw.shape[0], _ptr(labels)), "covahip_dev_mog_post_masks",
+                self.ctx.handle)
+        return labels
 
     def state(self, s: int) -> dict:
         """Stream s's model: W f32 [5][work_h][work_w], V the same, M f32 [5][3][work_h][work_w], nmodes u8 [work_h][work_w], n."""
@@ -211,8 +233,10 @@ def parse_size(text: str):
         w, h = (int(v) for v in text.lower().split("x"))
     except ValueError:
         raise argparse.ArgumentTypeError(f"size {text!r} is not WxH") from None
-    if (w, h) not in SIZES:
-        raise argparse.ArgumentTypeError(f"unsupported size {w}x{h}: one of " + ", ".join(f"{a}x{b}" for a, b in SIZES))
+    if not any((w, h) in sizes for sizes in GRID_SIZES.values()):
+        raise argparse.ArgumentTypeError(f"unsupported size {w}x{h}: one of " + ", ".join(f"{a}x{b}" for a, b in SIZES)
+                                         + ", and with --grid macroblock "
+                                         + ", ".join(f"{a}x{b}" for a, b in GRID_SIZES["macroblock"] if (a, b) not in SIZES))
     return w, h
 
 
@@ -234,16 +258,20 @@ def _args(argv):
     ap = argparse.ArgumentParser(prog="python -m cova_amd.mog", description=__doc__.split("\n")[0])
     ap.add_argument("inputs", nargs="+", type=parse_io, metavar="IN[:OUT]",
                     help="raw BGR24 video ('-' = stdin); OUT defaults to IN's name with _gt.dump")
-    ap.add_argument("--size", type=parse_size, required=True, help="source size: 640x360, 1280x720 or 1920x1080")
+    ap.add_argument("--size", type=parse_size, required=True,
+                    help="source size: 640x360, 1280x720 or 1920x1080; with --grid macroblock also 2560x1440 and 3840x2160")
     ap.add_argument("--grid", choices=sorted(GRIDS), default="reference",
                     help="reference: 45x80 labels whatever the source (the 1280x720 macroblock grid); macroblock: one label per "
-                         "macroblock of the source, which 1080p records need (1920x1080 -> 68x120)")
+                         "macroblock of the source, which 1080p records need (1920x1080 -> 68x120, 2560x1440 -> 90x160, "
+                         "3840x2160 -> 135x240)")
     ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
     ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
     ap.add_argument("--history", type=int, default=9000)
     ap.add_argument("--var-threshold", type=float, default=32.0)
     ap.add_argument("--device", type=int, default=0)
     a = ap.parse_args(argv)
+    if a.size not in GRID_SIZES[a.grid]:
+        ap.error(f"--size {a.size[0]}x{a.size[1]} needs --grid macroblock")
     if a.streams is None:
         a.streams = min(len(a.inputs), 8)
     if not 1 <= a.streams <= MAX_STREAMS:

@@ -678,9 +678,11 @@ void covahip_train_destroy(covahip_train *tr);
  * source.  The macroblock grid (COVAHIP_MOG_GRID_MACROBLOCK) labels the source's own 16x16 macroblocks; it differs in two steps:
  *   1. the working image is half the source in both axes, by the exact-2x rule above ((a + b + c + d + 2) >> 2 per channel over
  *      the 2x2 block): 1920x1080 -> 960x540, 1280x720 -> 640x360 (the reference grid itself: the same labels, masks and model,
- *      byte for byte), 640x360 -> 320x180; any other size is COVAHIP_ERR_UNSUPPORTED;
+ *      byte for byte), 640x360 -> 320x180, and two sizes that only this grid takes (the reference grid answers
+ *      COVAHIP_ERR_UNSUPPORTED): 2560x1440 -> 1280x720 and 3840x2160 -> 1920x1080; any other size is COVAHIP_ERR_UNSUPPORTED;
  *   6. label[i][j] = filled[8i][8j] for every i, j with 8i < working height and 8j < working width, the pixel at the top-left
- *      corner of macroblock (i, j): 68x120 (the last row reads working row 536), 45x80 and 23x40 (row 176) bytes per frame.
+ *      corner of macroblock (i, j): 68x120 (the last row reads working row 536), 45x80, 23x40 (row 176), 90x160 and 135x240
+ *      (a 4K grid; row 1072) bytes per frame.
  * Steps 2 - 5 are the same: the 4x4 / 6x6 kernels stay in working pixels, the same size relative to a macroblock.
  * MOG2 (the CPU path of OpenCV 4.x MOG2Invoker, nmixtures 5).  All values f32 unless noted, every product and sum rounded on
  * its own (no fused multiply-add), divisions correctly rounded:
@@ -704,11 +706,12 @@ void covahip_train_destroy(covahip_train *tr);
  *        i < nmodes - 1; M[m] = data; V[m] = varInit; for i = nmodes - 1 down to 1: stop if alphaT < W[i-1], else swap;
  *     5. mask = bg ? 0 : 255.
  * Streams: n_streams independent videos advance in one call, each with its own model and frame count.  Memory: about 23 MB of
- * model per stream (101 bytes per working pixel: 52 MB at 960x540).  Every call is synchronous. */
+ * model per stream (101 bytes per working pixel: 52 MB at 960x540, 93 MB at 1280x720, 209 MB at 1920x1080; many 4K streams can
+ * exhaust device memory, and create then answers COVAHIP_ERR_HIP).  Every call is synchronous. */
 enum { COVAHIP_MOG_MAX_STREAMS = 1024, COVAHIP_MOG_LABEL_H = 45, COVAHIP_MOG_LABEL_W = 80 };
 typedef struct covahip_mog covahip_mog;
 typedef struct covahip_mog_cfg {
-    int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 BGR24 */
+    int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 BGR24; on the macroblock grid also 2560x1440 and 3840x2160 */
     int32_t n_streams;          /* independent videos advanced per call, 1 .. COVAHIP_MOG_MAX_STREAMS */
     int32_t history;            /* 9000 (generate-mog.py); >= 1 */
     float   var_threshold;      /* 32; finite and > 0 */
@@ -717,7 +720,8 @@ typedef struct covahip_mog_cfg {
 void covahip_mog_default_cfg(covahip_mog_cfg *cfg);
 /* COVAHIP_ERR_UNSUPPORTED for another source size, COVAHIP_ERR_INVALID_ARG for streams, history or var_threshold out of range. */
 int  covahip_mog_create(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out);
-/* The same on either label grid; covahip_mog_create is the reference grid.  COVAHIP_ERR_INVALID_ARG for another `grid`.  apply,
+/* The same on either label grid; covahip_mog_create is the reference grid.  COVAHIP_ERR_INVALID_ARG for another `grid`,
+ * COVAHIP_ERR_UNSUPPORTED for a size the grid does not take (2560x1440 and 3840x2160 are the macroblock grid's alone).  apply,
  * reset and destroy take either kind of labeller; in the comments below 45x80 stands for the labeller's label_h x label_w. */
 enum { COVAHIP_MOG_GRID_REFERENCE = 0, COVAHIP_MOG_GRID_MACROBLOCK = 1 };
 int  covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int grid, covahip_mog **out);

@@ -83,6 +83,23 @@ int covahip_dev_mog_state(struct covahip_mog *m, int stream, float *W, float *V,
  * 1 GiB.  A call whose frames exceed it runs as several update launches of whole frame-steps (one frame of every stream), at
  * least one per launch; the results do not depend on it.  (tests/test_gpu_mog_branches.py) */
 int covahip_dev_mog_set_stage_budget(struct covahip_mog *m, size_t bytes);
+/* The labeller's post launch (close, open, hole fill, labels) on given masks instead of MOG2's: raw u8
+ * [n_frames][n_streams][work_h][work_w], non-zero = foreground, is packed into bit planes on the host and uploaded as the call's
+ * raw planes; labels u8 [n_frames][n_streams][label_h][label_w] (host memory) come back, and covahip_dev_mog_masks then reads the
+ * raw / filled masks of this call.  The model and the frame counts are untouched.  Works for every labeller.
+ * (tests/test_gpu_mog_band.py) */
+int covahip_dev_mog_post_masks(struct covahip_mog *m, const uint8_t *raw, int n_frames, uint8_t *labels);
+/* Which post kernel a macroblock-grid labeller runs.  banded = 1: the banded kernel of mog_band.hip, which labellers of
+ * 2560x1440 and 3840x2160 sources always run and a 1920x1080 one (960x540 working) runs only through this switch, to be compared
+ * with its resident kernel on the same planes; band_rows = 0 is the automatic plan (covahip_dev_mog_band_plan), otherwise the band
+ * height, 16 .. work_h, whose staged window must fit LDS.  banded = 0 (band_rows = 0): the resident kernel.
+ * COVAHIP_ERR_INVALID_ARG outside those ranges, for banded = 0 on a labeller that has no resident kernel and for banded = 1 on
+ * one that has no banded kernel (the reference grid, 320x180).  The results do not depend on it. */
+int covahip_dev_mog_set_post_form(struct covahip_mog *m, int banded, int band_rows);
+/* The automatic band plan of a working size (a multiple of 64 wide): `bands` bands of `rows` rows (the last may be shorter), as
+ * few as fit, and the dynamic LDS of the launch: two planes of min(rows + 16, work_h) rows, 16 bytes of flags and 256 bytes per 64 columns for the column sweep, at most
+ * 160 KiB - 64 B.  Any pointer may be NULL.  Pure host code: no GPU call. */
+int covahip_dev_mog_band_plan(int work_w, int work_h, int *rows, int *bands, size_t *lds_bytes);
 
 /* Serving monitor (covahip_monitor_*): samples per slice of its kernel; 0 restores the automatic choice (enough workgroups for
  * every CU, at least 16 samples).  The counts do not depend on it; a slice longer than 255 samples makes the kernel's packed

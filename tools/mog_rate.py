@@ -3,6 +3,7 @@
 
     python tools/mog_rate.py [--streams 1,8,64 --sizes 1280x720,640x360 --frames 1024 --reps 3] [--oracle-frames 3]
     python tools/mog_rate.py --grid macroblock --sizes 1920x1080 --frames 256      (960x540 working frames, 68x120 labels)
+    python tools/mog_rate.py --grid macroblock --sizes 3840x2160,2560x1440 --frames 64 --min-frames 2   (the banded kernels)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -45,16 +46,20 @@ def main():
     ap.add_argument("--sizes", default="1280x720,640x360")
     ap.add_argument("--grid", choices=sorted(mog.GRIDS), default="reference")
     ap.add_argument("--frames", type=int, default=1024, help="working frames per call (all streams)")
+    ap.add_argument("--min-frames", type=int, default=8, help="frames per stream and call at least (4K frames are 24.9 MB each)")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--oracle-frames", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
     a = ap.parse_args()
+    for size in a.sizes.split(","):
+        if mog.parse_size(size) not in mog.GRID_SIZES[a.grid]:
+            ap.error(f"--sizes {size} needs --grid macroblock")
     ctx = Context(0)
     for size in a.sizes.split(","):
         w, h = mog.parse_size(size)
         pool = clip(8, w, h)
         for S in (int(s) for s in a.streams.split(",")):
-            F = max(8, a.frames // S)
+            F = max(a.min_frames, a.frames // S)
             frames = np.empty((F, S, h, w, 3), np.uint8)
             for f in range(F):
                 frames[f] = pool[(f + np.arange(S)) % len(pool)]
