@@ -58,6 +58,10 @@ H264_SLICE_DTYPE = np.dtype([("nal_offset", "<u8"), ("nal_bytes", "<u4"), ("data
 
 KERNEL_TIME_DTYPE = np.dtype([("name", "S48"), ("total_ms", "<f8"), ("launches", "<i8")])
 
+# covahip_train_sample: the frames of the T = 0 .. 3 slices, the frame whose gt labels the sample, bit 0 mirror x / bit 1 mirror y
+TRAIN_SAMPLE_DTYPE = np.dtype([("frame", "<i4", (4,)), ("label", "<i4"), ("flags", "<u4")])
+assert TRAIN_SAMPLE_DTYPE.itemsize == 24
+
 
 class GopFilterCfg(C.Structure):
     _fields_ = [("sort_iou", C.c_float), ("sort_maxage", C.c_uint32), ("sort_minhits", C.c_uint32),
@@ -250,6 +254,15 @@ PROTOTYPES = {
     "covahip_train_set_post": (C.c_int, [_P, C.c_int, C.POINTER(BlobNetPost)]),
     "covahip_train_get_post": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P, C.POINTER(C.c_int)]),
     "covahip_train_destroy": (None, [_P]),
+    "covahip_train_data_create": (C.c_int, [_P, C.c_int, C.c_int, C.c_int64, C.POINTER(_P)]),
+    "covahip_train_data_append": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
+    "covahip_train_data_frames": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "covahip_train_data_gather": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_train_data_destroy": (None, [_P]),
+    "covahip_train_step_data": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(C.c_float)]),
+    "covahip_train_step_set_data": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "covahip_train_eval_data": (C.c_int, [_P, _P, _P, C.c_int, _P, _P, C.POINTER(TrainEvalResult), C.c_int]),
+    "covahip_train_eval_set_data": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(TrainEvalResult), C.c_int]),
     "covahip_post_sweep": (C.c_int, [_P, C.POINTER(SweepCfg), _P, _P, C.c_int, C.c_int, _P, _P, _P, C.POINTER(SweepResult)]),
     "covahip_post_heat_begin": (C.c_int, [_P, C.POINTER(HeatCfg)]),
     "covahip_post_heat_add": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),

@@ -169,6 +169,16 @@ int covahip_monitor_hook(covahip_ctx *ctx, const uint8_t *d_mask, const int32_t 
                          const uint8_t *model_ids, int batch);
 void covahip_monitor_close(covahip_ctx *ctx, bool attached_only);   // drains the ctx and frees the monitor (if any)
 
+// train_data.hip: what the trainer's data entry points (train.hip) need of a covahip_train_data
+// Host check of n samples against the data set, the caller's ctx (null: any) and geometry: COVAHIP_OK or COVAHIP_ERR_INVALID_ARG.
+int covahip_train_data_check(const covahip_train_data *d, const covahip_ctx *ctx, int h, int w, const covahip_train_sample *s,
+                             int64_t n);
+// The data set's pinned sample table, grown to n entries: the caller writes the samples of one launch there, in output order ...
+int covahip_train_data_table(covahip_train_data *d, int n, covahip_train_sample **tab);
+// ... and this uploads the first n and builds their stacks u8 [n][4h][w][4] and labels u8 [n][h][w] in device memory, on the ctx's
+// stream.  The table is free again once the stream has passed the launch.
+int covahip_train_data_launch(covahip_train_data *d, int n, uint8_t *d_stack, uint8_t *d_gt);
+
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);
 int covahip_blobnet_forward_dev(covahip_ctx *ctx, const uint8_t *d_stack, int batch, float *d_logits,

@@ -1443,9 +1443,24 @@ int set_tab(covahip_train *tr, const int32_t *b, const float *lrs) {
     return COVAHIP_OK;
 }
 
-// The step of a set: batches / lrs / losses have K entries, the samples are packed in model order.
+// The samples of a pass written into the trainer's staging by the data set's gather launch instead of a copy: `first`[k] is
+// model k's first entry of `samples`, of which the pass takes h_tab[k].b to the model's place in the packing.
+int fill_from_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, const int64_t *first) {
+    int total = 0;
+    for (int k = 0; k < tr->K; k++) total += tr->h_tab[k].b;
+    covahip_train_sample *tab = nullptr;
+    if (int rc = covahip_train_data_table(d, total, &tab)) return rc;
+    for (int k = 0; k < tr->K; k++) {
+        const MStep &ms = tr->h_tab[k];
+        if (ms.b) std::memcpy(tab + ms.first, samples + first[k], (size_t)ms.b * sizeof(covahip_train_sample));
+    }
+    return covahip_train_data_launch(d, total, tr->d_stack, tr->d_gt);
+}
+
+// The step of a set: batches / lrs / losses have K entries, the samples are packed in model order.  With a data set `d` they are
+// `samples` of it (a host table, checked here before anything is launched) and stack / gt / mem_kind are unused.
 int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int *batches, const float *lrs, float *losses,
-              int mem_kind) {
+              int mem_kind, covahip_train_data *d = nullptr, const covahip_train_sample *samples = nullptr) {
     const int K = tr->K;
     int64_t total = 0;
     int bmax = 0;
@@ -1455,14 +1470,24 @@ int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
         bmax = std::max(bmax, batches[k]);
     }
     if (total == 0) return COVAHIP_ERR_INVALID_ARG;
-    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    if (d) {
+        if (int rc = covahip_train_data_check(d, tr->ctx, tr->H[0], tr->W[0], samples, total)) return rc;
+    } else if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) {
+        return COVAHIP_ERR_INVALID_ARG;
+    }
     covahip_ctx *ctx = tr->ctx;
     if (int rc = enter(ctx)) return rc;
     if (int rc = set_tab(tr, batches, lrs)) return rc;
-    const size_t hw = (size_t)tr->H[0] * tr->W[0];
-    const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * TT * hw * 4, kind, ctx->stream));
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, kind, ctx->stream));
+    if (d) {
+        std::vector<int64_t> first(K);
+        for (int k = 0; k < K; k++) first[k] = tr->h_tab[k].first;
+        if (int rc = fill_from_data(tr, d, samples, first.data())) return rc;
+    } else {
+        const size_t hw = (size_t)tr->H[0] * tr->W[0];
+        const hipMemcpyKind kind = mem_kind == COVAHIP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * TT * hw * 4, kind, ctx->stream));
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, kind, ctx->stream));
+    }
     if (int rc = run_step(tr, bmax)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_loss, tr->d_loss, (size_t)K * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->h_counts, tr->d_counts, (size_t)K * 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost,
@@ -1480,9 +1505,11 @@ int step_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     return COVAHIP_OK;
 }
 
-// Evaluation of counts[k] samples of model k (packed in model order), in chunks of max_batch per model.
+// Evaluation of counts[k] samples of model k (packed in model order), in chunks of max_batch per model.  With a data set `d` the
+// samples are `samples` of it (step_body); mem_kind then applies to sample_loss and logits alone.
 int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const int32_t *counts, float *sample_loss, float *logits,
-              covahip_train_eval_result *out, int mem_kind) {
+              covahip_train_eval_result *out, int mem_kind, covahip_train_data *d = nullptr,
+              const covahip_train_sample *samples = nullptr) {
     const int K = tr->K, mb = tr->cfg.max_batch;
     std::vector<int64_t> base(K);
     int64_t total = 0;
@@ -1495,6 +1522,8 @@ int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     }
     if (total == 0 || total > INT32_MAX) return COVAHIP_ERR_INVALID_ARG;
     if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    if (d)
+        if (int rc = covahip_train_data_check(d, tr->ctx, tr->H[0], tr->W[0], samples, total)) return rc;
     covahip_ctx *ctx = tr->ctx;
     if (int rc = enter(ctx)) return rc;
     const hipStream_t s = ctx->stream;
@@ -1509,7 +1538,11 @@ int eval_body(covahip_train *tr, const uint8_t *stack, const uint8_t *gt, const 
     for (int c = 0; c < nchunks; c++) {
         for (int k = 0; k < K; k++) cb[k] = (int32_t)std::min<int64_t>(mb, std::max<int64_t>(0, (int64_t)counts[k] - (int64_t)c * mb));
         if (int rc = set_tab(tr, cb.data(), nullptr)) return rc;   // keys and lr_t: unused
-        if (nchunks == 1) {   // the caller's packing is the chunk's
+        if (d) {
+            std::vector<int64_t> first(K);
+            for (int k = 0; k < K; k++) first[k] = base[k] + (int64_t)c * mb;
+            if (int rc = fill_from_data(tr, d, samples, first.data())) return rc;
+        } else if (nchunks == 1) {   // the caller's packing is the chunk's
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_stack, stack, (size_t)total * stack_b, in_kind, s));
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->d_gt, gt, (size_t)total * hw, in_kind, s));
         } else {
@@ -1644,6 +1677,18 @@ int covahip_train_step(covahip_train *tr, const uint8_t *stack, const uint8_t *g
     return step_body(tr, stack, gt, &batch, &lr, loss, mem_kind);
 }
 
+int covahip_train_step_set_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, const int32_t *batches,
+                                const float *lrs, float *losses) {
+    if (!tr || !d || !samples || !batches || !lrs || !losses) return COVAHIP_ERR_INVALID_ARG;
+    return step_body(tr, nullptr, nullptr, batches, lrs, losses, COVAHIP_MEM_DEVICE, d, samples);
+}
+
+int covahip_train_step_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, int batch, float lr,
+                            float *loss) {
+    if (!tr || !d || !samples || !loss || batch <= 0 || tr->K != 1) return COVAHIP_ERR_INVALID_ARG;
+    return step_body(tr, nullptr, nullptr, &batch, &lr, loss, COVAHIP_MEM_DEVICE, d, samples);
+}
+
 int covahip_train_metrics_m(covahip_train *tr, int model, int64_t tp_fp_fn[3]) {
     if (!tr || !tp_fp_fn || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
     for (int k = 0; k < 3; k++) tp_fp_fn[k] = tr->last_counts[(size_t)model * 3 + k];
@@ -1750,6 +1795,19 @@ int covahip_train_eval(covahip_train *tr, const uint8_t *stack, const uint8_t *g
     if (!tr || !stack || !gt || !out || n < 1 || tr->K != 1) return COVAHIP_ERR_INVALID_ARG;
     const int32_t count = n;
     return eval_body(tr, stack, gt, &count, sample_loss, logits, out, mem_kind);
+}
+
+int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, const int32_t *counts,
+                                float *sample_loss, float *logits, covahip_train_eval_result *out, int mem_kind) {
+    if (!tr || !d || !samples || !counts || !out) return COVAHIP_ERR_INVALID_ARG;
+    return eval_body(tr, nullptr, nullptr, counts, sample_loss, logits, out, mem_kind, d, samples);
+}
+
+int covahip_train_eval_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, int n, float *sample_loss,
+                            float *logits, covahip_train_eval_result *out, int mem_kind) {
+    if (!tr || !d || !samples || !out || n < 1 || tr->K != 1) return COVAHIP_ERR_INVALID_ARG;
+    const int32_t count = n;
+    return eval_body(tr, nullptr, nullptr, &count, sample_loss, logits, out, mem_kind, d, samples);
 }
 
 int covahip_train_state_size(covahip_train *tr, size_t *n) {

@@ -1,0 +1,240 @@
+// Device-resident training data (include/covahip.h, "Training data"): the frames of any number of recordings as two-byte
+// records (covahip_carrier_pack's packing) with their label bytes, and the launch that builds a training step's stacks and labels
+// from a table of frame indices, mirrored where a sample asks for it, straight into the trainer's staging.
+//
+// Storage: rec u16 [capacity][h][w], gt u8 [capacity][h][w]; every element offset is 64-bit (a 16x16 set of 8.5 M frames is 4.4 GB
+// of records).  A frame of an odd h * w starts on an odd element, so the read side relies on 2-byte alignment only.
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
+#include "internal.h"
+
+namespace {
+
+constexpr int TT = 4;                         // slices of a stack
+constexpr int BLK = 256;
+constexpr int GATHER_MAX = 65535;             // samples per launch: the grid's y extent
+constexpr size_t STAGE_BYTES = 32u << 20;     // host appends and host-bound gathers move through a staging area of this size
+constexpr unsigned PACK_BLOCKS_MAX = 1u << 18;
+
+// u8 [n_mb][4] -> min(type, 6) | min(mv_x, 6) << 3 | min(mv_y, 6) << 6, one macroblock per thread and round of the grid.
+// WORDS: the source is 4-byte aligned and read a record at a time; otherwise byte by byte.
+template <bool WORDS>
+__global__ void k_pack_records(const uint8_t *__restrict__ frames, uint16_t *__restrict__ rec, int64_t n_mb) {
+    const int64_t stride = (int64_t)gridDim.x * BLK;
+    for (int64_t i = (int64_t)blockIdx.x * BLK + threadIdx.x; i < n_mb; i += stride) {
+        uint32_t t, x, y;
+        if (WORDS) {
+            const uint32_t v = reinterpret_cast<const uint32_t *>(frames)[i];
+            t = v & 0xFFu, x = (v >> 8) & 0xFFu, y = (v >> 16) & 0xFFu;
+        } else {
+            t = frames[4 * i], x = frames[4 * i + 1], y = frames[4 * i + 2];
+        }
+        rec[i] = (uint16_t)(min(t, 6u) | (min(x, 6u) << 3) | (min(y, 6u) << 6));
+    }
+}
+
+// One workgroup row per output sample (blockIdx.y), one thread per macroblock of the grid: the thread at (y, x) reads the four
+// records and the label at (y', x') and stores four bytes per slice at (y, x), so a wave's stores are contiguous whatever the
+// mirror; a mirrored row is read back to front inside the same cache lines.
+__global__ void k_gather(const uint16_t *__restrict__ rec, const uint8_t *__restrict__ gt, const covahip_train_sample *__restrict__ tab,
+                         uint32_t *__restrict__ stack, uint8_t *__restrict__ lab, int h, int w) {
+    const int hw = h * w;
+    const int pos = (int)(blockIdx.x * BLK + threadIdx.x);
+    if (pos >= hw) return;
+    const covahip_train_sample s = tab[blockIdx.y];
+    const int y = pos / w, x = pos - y * w;
+    const int ys = (s.flags & 2u) ? h - 1 - y : y, xs = (s.flags & 1u) ? w - 1 - x : x;
+    const int src = ys * w + xs;
+    uint32_t *out = stack + (int64_t)blockIdx.y * TT * hw + pos;
+#pragma unroll
+    for (int t = 0; t < TT; t++) {
+        const uint32_t r = rec[(int64_t)s.frame[t] * hw + src];
+        out[(int64_t)t * hw] = (r & 7u) | ((r >> 3) & 7u) << 8 | ((r >> 6) & 7u) << 16;
+    }
+    lab[(int64_t)blockIdx.y * hw + pos] = gt[(int64_t)s.label * hw + src];
+}
+
+}  // namespace
+
+struct covahip_train_data {
+    covahip_ctx *ctx = nullptr;
+    int h = 0, w = 0;
+    int64_t capacity = 0, frames = 0;
+    uint16_t *rec = nullptr;
+    uint8_t *gt = nullptr;
+    covahip_train_sample *d_tab = nullptr, *h_tab = nullptr;   // the table of one launch sequence; h_: pinned
+    int tab_cap = 0;
+    void *stage = nullptr;                                      // device staging of a host-bound gather
+    size_t stage_bytes = 0;
+    std::vector<uint16_t> pack;                                 // host staging of a host append
+};
+
+namespace {
+
+int enter(covahip_ctx *ctx) {
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    return covahip_primary_op(ctx);
+}
+
+void free_data(covahip_train_data *d) {
+    if (d->rec) hipFree(d->rec);
+    if (d->gt) hipFree(d->gt);
+    if (d->d_tab) hipFree(d->d_tab);
+    if (d->h_tab) hipHostFree(d->h_tab);
+    if (d->stage) hipFree(d->stage);
+    delete d;
+}
+
+}  // namespace
+
+int covahip_train_data_check(const covahip_train_data *d, const covahip_ctx *ctx, int h, int w, const covahip_train_sample *s,
+                             int64_t n) {
+    if (!d || !s || n < 0 || (ctx && d->ctx != ctx) || d->h != h || d->w != w) return COVAHIP_ERR_INVALID_ARG;
+    for (int64_t i = 0; i < n; i++) {
+        if (s[i].flags & ~3u) return COVAHIP_ERR_INVALID_ARG;
+        if (s[i].label < 0 || s[i].label >= d->frames) return COVAHIP_ERR_INVALID_ARG;
+        for (int t = 0; t < TT; t++)
+            if (s[i].frame[t] < 0 || s[i].frame[t] >= d->frames) return COVAHIP_ERR_INVALID_ARG;
+    }
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_table(covahip_train_data *d, int n, covahip_train_sample **tab) {
+    covahip_ctx *ctx = d->ctx;
+    if (n > d->tab_cap) {
+        COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // nothing in flight reads the old table
+        if (d->d_tab) hipFree(d->d_tab);
+        if (d->h_tab) hipHostFree(d->h_tab);
+        d->d_tab = d->h_tab = nullptr;
+        d->tab_cap = 0;
+        const int cap = std::max(n, 256);
+        COVAHIP_CHECK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d->d_tab), (size_t)cap * sizeof(covahip_train_sample)));
+        COVAHIP_CHECK_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&d->h_tab), (size_t)cap * sizeof(covahip_train_sample)));
+        d->tab_cap = cap;
+    }
+    *tab = d->h_tab;
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_launch(covahip_train_data *d, int n, uint8_t *d_stack, uint8_t *d_gt) {
+    covahip_ctx *ctx = d->ctx;
+    if (n <= 0 || n > d->tab_cap) return COVAHIP_ERR_INVALID_ARG;
+    const hipStream_t s = ctx->stream;
+    const size_t hw = (size_t)d->h * d->w;
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d->d_tab, d->h_tab, (size_t)n * sizeof(covahip_train_sample), hipMemcpyHostToDevice, s));
+    for (int at = 0; at < n; at += GATHER_MAX) {
+        const int m = std::min(GATHER_MAX, n - at);
+        ProfScope prof(ctx, "train_data_gather");
+        k_gather<<<dim3((unsigned)((hw + BLK - 1) / BLK), (unsigned)m), BLK, 0, s>>>(
+            d->rec, d->gt, d->d_tab + at, reinterpret_cast<uint32_t *>(d_stack + (size_t)at * TT * hw * 4), d_gt + (size_t)at * hw, d->h, d->w);
+        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    }
+    return COVAHIP_OK;
+}
+
+extern "C" {
+
+int covahip_train_data_create(covahip_ctx *ctx, int h_mb, int w_mb, int64_t capacity_frames, covahip_train_data **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !out || h_mb < 16 || w_mb < 16 || h_mb > 1024 || w_mb > 1024 || capacity_frames < 1 || capacity_frames > INT32_MAX)
+        return COVAHIP_ERR_INVALID_ARG;
+    if (int rc = enter(ctx)) return rc;
+    covahip_train_data *d = new covahip_train_data();
+    d->ctx = ctx;
+    d->h = h_mb;
+    d->w = w_mb;
+    d->capacity = capacity_frames;
+    const size_t n_mb = (size_t)capacity_frames * h_mb * w_mb;
+    hipError_t e = hipMalloc(reinterpret_cast<void **>(&d->rec), n_mb * sizeof(uint16_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void **>(&d->gt), n_mb);
+    if (e != hipSuccess) {
+        ctx->last_hip_error = std::string("covahip_train_data_create: ") + hipGetErrorString(e);
+        (void)hipGetLastError();
+        free_data(d);
+        return COVAHIP_ERR_HIP;
+    }
+    *out = d;
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_append(covahip_train_data *d, const uint8_t *frames, const uint8_t *gt, int n, int mem_kind, int64_t *first_index) {
+    if (!d || !frames || !gt || n < 1 || (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE)) return COVAHIP_ERR_INVALID_ARG;
+    if ((int64_t)n > d->capacity - d->frames) return COVAHIP_ERR_OVERFLOW;
+    covahip_ctx *ctx = d->ctx;
+    if (int rc = enter(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const size_t hw = (size_t)d->h * d->w, at = (size_t)d->frames * hw, n_mb = (size_t)n * hw;
+    if (mem_kind == COVAHIP_MEM_DEVICE) {
+        const unsigned blocks = (unsigned)std::min<size_t>((n_mb + BLK - 1) / BLK, PACK_BLOCKS_MAX);
+        ProfScope prof(ctx, "train_data_pack");
+        if ((reinterpret_cast<uintptr_t>(frames) & 3u) == 0)
+            k_pack_records<true><<<blocks, BLK, 0, s>>>(frames, d->rec + at, (int64_t)n_mb);
+        else
+            k_pack_records<false><<<blocks, BLK, 0, s>>>(frames, d->rec + at, (int64_t)n_mb);
+        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d->gt + at, gt, n_mb, hipMemcpyDeviceToDevice, s));
+    } else {   // packed on the host: two bytes per macroblock cross the bus
+        const size_t chunk = std::min(n_mb, STAGE_BYTES / sizeof(uint16_t));
+        if (d->pack.size() < chunk) d->pack.resize(chunk);
+        for (size_t o = 0; o < n_mb; o += chunk) {
+            const size_t m = std::min(chunk, n_mb - o);
+            covahip_carrier_pack(frames + 4 * o, m, d->pack.data());
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d->rec + at + o, d->pack.data(), m * sizeof(uint16_t), hipMemcpyHostToDevice, s));
+            COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the staging is packed again by the next round
+        }
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d->gt + at, gt, n_mb, hipMemcpyHostToDevice, s));
+    }
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    if (first_index) *first_index = d->frames;
+    d->frames += n;
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_frames(const covahip_train_data *d, int64_t *n) {
+    if (!d || !n) return COVAHIP_ERR_INVALID_ARG;
+    *n = d->frames;
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample *samples, int n, uint8_t *stack, uint8_t *gt, int mem_kind) {
+    if (!d || !samples || !stack || !gt || n < 1 || (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE))
+        return COVAHIP_ERR_INVALID_ARG;
+    const bool host = mem_kind == COVAHIP_MEM_HOST;
+    if (!host && (reinterpret_cast<uintptr_t>(stack) & 3u)) return COVAHIP_ERR_INVALID_ARG;   // the launch stores whole records
+    if (int rc = covahip_train_data_check(d, nullptr, d->h, d->w, samples, n)) return rc;
+    covahip_ctx *ctx = d->ctx;
+    if (int rc = enter(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const size_t hw = (size_t)d->h * d->w, stack_b = TT * hw * 4, per = stack_b + hw;
+    // a launch's samples: what the grid takes, and for host output what the staging holds
+    const size_t fit = host ? std::max<size_t>(1, std::min<size_t>(STAGE_BYTES / per, GATHER_MAX)) : (size_t)GATHER_MAX;
+    const int chunk = (int)std::min<size_t>((size_t)n, fit);
+    if (host)
+        if (int rc = covahip_ensure_buffer(ctx, &d->stage, &d->stage_bytes, (size_t)chunk * per)) return rc;
+    for (int at = 0; at < n; at += chunk) {
+        const int m = std::min(chunk, n - at);
+        covahip_train_sample *tab = nullptr;
+        if (int rc = covahip_train_data_table(d, m, &tab)) return rc;
+        std::memcpy(tab, samples + at, (size_t)m * sizeof(covahip_train_sample));
+        uint8_t *o_stack = host ? static_cast<uint8_t *>(d->stage) : stack + (size_t)at * stack_b;
+        uint8_t *o_gt = host ? static_cast<uint8_t *>(d->stage) + (size_t)chunk * stack_b : gt + (size_t)at * hw;
+        if (int rc = covahip_train_data_launch(d, m, o_stack, o_gt)) return rc;
+        if (host) {
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(stack + (size_t)at * stack_b, o_stack, (size_t)m * stack_b, hipMemcpyDeviceToHost, s));
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(gt + (size_t)at * hw, o_gt, (size_t)m * hw, hipMemcpyDeviceToHost, s));
+        }
+        COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the table and the staging are reused by the next chunk
+    }
+    return COVAHIP_OK;
+}
+
+void covahip_train_data_destroy(covahip_train_data *d) {
+    if (!d) return;
+    hipSetDevice(d->ctx->device);
+    covahip_sync_all(d->ctx);
+    free_data(d);
+}
+
+}  // extern "C"

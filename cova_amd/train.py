@@ -6,6 +6,11 @@
   TrainerSet      K models of one geometry in one trainer (covahip_train_*: forward, backward and Adam in HIP, one launch of each
                   kernel per step of all models) and the epoch loop
   Trainer         one model: a TrainerSet of one
+  TrainData       frames and labels resident on the device (.append / .append_device from host / device memory, .gather /
+                  .gather_device: the batch a sample array describes, to host / device memory)
+  windows         the windows of a model's recordings as a table; epoch_samples: the table as one epoch's sample array, reordered,
+                  mirrored, reversed; plain_samples: the table's windows as they are (validation, scoring); split_frames_tail
+                  TrainerSet / Trainer .step_data, .evaluate_data, .fit_data take their batches from a TrainData by such arrays
 
     python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
 
@@ -50,6 +55,16 @@ threshold it is served with,
 as --set -o names weight files); --ignore-rects L,T,W,H[+L,T,W,H...] and --mask-threshold P give the same for a camera without
 a sidecar.  Macroblocks in the ignore region take no part in the loss, its gradient or the metrics, and the metrics count
 logit > threshold as serving does.  The post is not part of the checkpoint either: --resume takes it from the command line again.
+
+Training from resident frames (include/covahip.h, "Training data"): every window of a recording, mirrored, reversed, reshuffled,
+
+    python -m cova_amd.train CAM.tfrecord -o blobnet.cvhw --windows overlap --stride 1,2 --flip xy --reverse --shuffle --data-seed 1
+
+Any of these six flags keeps the frames on the device as two-byte records (TrainData) and builds each step's batch there from a
+table of frame indices (windows, epoch_samples; TrainerSet.fit_data / evaluate_data).  Every file is one segment that no window
+crosses; --windows overlap takes all F - 3 windows of F frames instead of F / 4; --stride, --flip and --reverse are drawn per
+sample and epoch and --shuffle reorders every epoch, all as pure functions of (--data-seed, epoch, model), so --resume with the
+same flags continues exactly.  Validation windows are never augmented.  Without these flags the program runs as it always has.
 """
 from __future__ import annotations
 
@@ -531,6 +546,200 @@ def _epoch_text(ep: int, epochs: int, rec: dict, model=None) -> str:
             f"precision {rec['precision']:.4f} recall {rec['recall']:.4f}{val} lr {rec['lr']:.3g}")
 
 
+# ------------------------------------------------------------------------------------------------ resident training data
+SAMPLE = L.TRAIN_SAMPLE_DTYPE
+_M64 = (1 << 64) - 1
+
+
+def splitmix64(z):
+    """The header's splitmix64 (include/covahip.h, "BlobNet training") on a u64 array, all arithmetic mod 2^64."""
+    z = np.atleast_1d(np.asarray(z, dtype=np.uint64)) + np.uint64(0x9E3779B97F4A7C15)
+    z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def _segments(segments) -> list:
+    out = [(int(a), int(b)) for a, b in segments]
+    if any(a < 0 or b < a for a, b in out):
+        raise ValueError(f"a segment is a half-open range of frame indices [a, b), got {out}")
+    return out
+
+
+def _strides(strides) -> tuple:
+    strides = tuple(int(s) for s in ((strides,) if np.isscalar(strides) else strides))
+    if not strides or min(strides) < 1:
+        raise ValueError(f"strides = {strides}: at least one, each at least 1")
+    return strides
+
+
+def windows(segments, mode: str = "skip", strides=(1,)) -> np.ndarray:
+    """The windows of a model's segments (half-open ranges of frame indices of a TrainData, one contiguous recording each) as a
+    table i64 [N][2] of (segment start, newest frame k) in canonical order: segment by segment, k ascending.  mode "skip": slide's
+    groups, frames 4j .. 4j + 3 of the segment (k = start + 4j + 3); "overlap": every k of the segment.  Either way only k with
+    k - 3 * min(strides) >= start: a window never crosses a segment boundary, and every window of the table fits at least one of
+    the strides (epoch_samples picks among those that fit)."""
+    if mode not in ("skip", "overlap"):
+        raise ValueError(f"mode = {mode!r}: 'skip' or 'overlap'")
+    reach = (W.T - 1) * min(_strides(strides))
+    rows = []
+    for a, b in _segments(segments):
+        k = np.arange(a + W.T - 1, a + (b - a) // W.T * W.T, W.T) if mode == "skip" else np.arange(a, b)
+        k = k[k - reach >= a].astype(np.int64)
+        rows.append(np.stack([np.full(k.size, a, np.int64), k], axis=1))
+    return np.concatenate(rows) if rows else np.zeros((0, 2), np.int64)
+
+
+def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model: int = 0, shuffle: bool = False, flip=(),
+                  reverse: bool = False) -> np.ndarray:
+    """The covahip_train_sample array (dtype SAMPLE) of one epoch of one model over a windows() table: a pure function of its
+    arguments, built on the header's splitmix64 (numpy's generators are not pinned across versions, and resume must be exact).
+        key(site) = splitmix64(data_seed ^ splitmix64(epoch << 20 | model << 4 | site))
+        r(site, i) = splitmix64(key(site) + i),   i = the window's canonical index (its row of the table)
+    order: a stable argsort of r(0, i) when `shuffle`, else canonical; mirror x: r(1, i) >> 63 when "x" is in `flip`; mirror y:
+    r(2, i) >> 63 when "y" is in it; time reversal: r(3, i) >> 63 when `reverse` -- the frames are then listed oldest first and
+    the OLDEST frame labels the sample; stride: the (r(4, i) mod m)-th, in the order given, of the m strides s with
+    k - 3 s >= segment start.  A forward window at stride s is frames (k, k - s, k - 2s, k - 3s) labelled by frame k.
+    The key's word keeps its three fields apart for 0 <= site < 16, 0 <= model < 2^16 and 0 <= epoch < 2^44; anything outside is
+    a ValueError."""
+    table = np.asarray(table, dtype=np.int64).reshape(-1, 2)
+    strides = _strides(strides)
+    if not (0 <= int(model) < 1 << 16 and 0 <= int(epoch) < 1 << 44):
+        raise ValueError(f"model = {model}, epoch = {epoch}: 0 <= model < 2^16 and 0 <= epoch < 2^44")
+    if any(c not in ("x", "y") for c in flip):
+        raise ValueError(f"flip = {flip!r}: 'x', 'y', both or neither")
+    n = table.shape[0]
+    idx = np.arange(n, dtype=np.uint64)
+    word = ((int(epoch) << 20) | (int(model) << 4)) & _M64
+
+    def r(site):
+        key = splitmix64(np.uint64(int(data_seed) & _M64) ^ splitmix64(np.uint64(word | site)))
+        return splitmix64(key + idx)
+
+    start, k = table[:, 0], table[:, 1]
+    fits = np.stack([k - (W.T - 1) * s >= start for s in strides], axis=1) if n else np.zeros((0, len(strides)), bool)
+    m = fits.sum(axis=1)
+    if (m == 0).any():
+        raise ValueError(f"none of the strides {strides} fits window {table[int(np.argmin(m))].tolist()} in its segment")
+    pick = (r(4) % m.astype(np.uint64)).astype(np.int64)
+    which = np.argmax(fits & (np.cumsum(fits, axis=1) - 1 == pick[:, None]), axis=1) if n else np.zeros(0, np.int64)
+    step = np.asarray(strides, dtype=np.int64)[which]
+    out = np.zeros(n, SAMPLE)
+    frames = k[:, None] - step[:, None] * np.arange(W.T, dtype=np.int64)[None, :]      # newest first
+    if reverse:
+        rev = (r(3) >> np.uint64(63)).astype(bool)
+        frames = np.where(rev[:, None], frames[:, ::-1], frames)
+    out["frame"] = frames
+    out["label"] = frames[:, 0]
+    if "x" in flip:
+        out["flags"] |= (r(1) >> np.uint64(63)).astype(np.uint32)
+    if "y" in flip:
+        out["flags"] |= (r(2) >> np.uint64(63)).astype(np.uint32) << np.uint32(1)
+    if shuffle:
+        out = out[np.argsort(r(0), kind="stable")]
+    return np.ascontiguousarray(out)
+
+
+def plain_samples(table, stride: int = 1) -> np.ndarray:
+    """The table's windows as they are: canonical order, forward, unmirrored, at `stride` (validation and scoring)."""
+    return epoch_samples(table, (stride,))
+
+
+def split_frames_tail(segments, frac: float):
+    """(training segments, validation segments) of one model: the LAST ceil(frac * F) of its F frames validate.  The cut splits
+    a segment in two, so no window straddles it (split_tail's rule, in frames).  A frac that leaves either part empty is a
+    ValueError."""
+    segments = _segments(segments)
+    total = sum(b - a for a, b in segments)
+    n_val = int(math.ceil(frac * total - 1e-9))
+    if not 0 < n_val < total:
+        raise ValueError(f"validation fraction {frac} of {total} frames leaves {n_val} to validate and {total - n_val} to train")
+    train, val, left = [], [], total - n_val
+    for a, b in segments:
+        cut = min(b, a + left)
+        left -= cut - a
+        if cut > a:
+            train.append((a, cut))
+        if b > cut:
+            val.append((cut, b))
+    return train, val
+
+
+class TrainData:
+    """A device-resident training data set (include/covahip.h, "Training data"): frames as two-byte records with their label
+    bytes, 3 bytes per macroblock.  The trainers take their batches from it by tables of frame indices (epoch_samples)."""
+
+    def __init__(self, ctx, h_mb: int, w_mb: int, capacity: int):
+        self.ctx, self.h, self.w, self.capacity = ctx, h_mb, w_mb, int(capacity)
+        self._lib = L.lib()
+        h = C.c_void_p()
+        L.check(self._lib.covahip_train_data_create(ctx.handle, h_mb, w_mb, self.capacity, C.byref(h)), "covahip_train_data_create",
+                ctx.handle)
+        self.handle = h
+
+    def close(self):
+        if getattr(self, "handle", None):
+            if getattr(self.ctx, "handle", None):
+                self._lib.covahip_train_data_destroy(self.handle)
+            self.handle = None
+
+    __del__ = close
+
+    @property
+    def frames(self) -> int:
+        n = C.c_int64()
+        L.check(self._lib.covahip_train_data_frames(self.handle, C.byref(n)), "covahip_train_data_frames")
+        return int(n.value)
+
+    def _append(self, p_frames, p_gt, n, kind):
+        first = C.c_int64()
+        L.check(self._lib.covahip_train_data_append(self.handle, p_frames, p_gt, n, kind, C.byref(first)), "covahip_train_data_append",
+                self.ctx.handle)
+        return int(first.value), int(first.value) + n
+
+    def append(self, frames: np.ndarray, gt: np.ndarray):
+        """frames u8 [n][h][w][4] and gt u8 [n][h][w] of ONE contiguous recording; returns the half-open range of frame indices it
+        filled: a segment (windows)."""
+        frames = np.ascontiguousarray(frames, dtype=np.uint8)
+        gt = np.ascontiguousarray(gt, dtype=np.uint8)
+        n = frames.shape[0]
+        if frames.shape != (n, self.h, self.w, 4) or gt.shape != (n, self.h, self.w):
+            raise ValueError(f"frames {frames.shape} / gt {gt.shape}: expected [n][{self.h}][{self.w}][4] and [n][{self.h}][{self.w}]")
+        return self._append(frames.ctypes.data, gt.ctypes.data, n, L.MEM_HOST)
+
+    def append_device(self, d_frames: int, d_gt: int, n: int):
+        """The same from device pointers (packed by a kernel)."""
+        return self._append(d_frames, d_gt, n, L.MEM_DEVICE)
+
+    def gather(self, samples):
+        """(stacks u8 [n][4h][w][4], labels u8 [n][h][w]) of a SAMPLE array: the batch a step on these samples sees."""
+        samples = _samples(samples)
+        n = samples.shape[0]
+        stack = np.empty((n, W.T * self.h, self.w, 4), np.uint8)
+        gt = np.empty((n, self.h, self.w), np.uint8)
+        L.check(self._lib.covahip_train_data_gather(self.handle, samples.ctypes.data, n, stack.ctypes.data, gt.ctypes.data, L.MEM_HOST),
+                "covahip_train_data_gather", self.ctx.handle)
+        return stack, gt
+
+    def gather_device(self, samples, d_stack: int, d_gt: int) -> None:
+        samples = _samples(samples)
+        L.check(self._lib.covahip_train_data_gather(self.handle, samples.ctypes.data, samples.shape[0], d_stack, d_gt, L.MEM_DEVICE),
+                "covahip_train_data_gather", self.ctx.handle)
+
+
+def _samples(samples) -> np.ndarray:
+    samples = np.asarray(samples)
+    if samples.dtype != SAMPLE or samples.ndim != 1:
+        raise ValueError("samples: a one-dimensional array of dtype train.SAMPLE (epoch_samples, plain_samples)")
+    return np.ascontiguousarray(samples)
+
+
+def _pack_samples(per_model):
+    """(SAMPLE array packed in model order, counts) of one SAMPLE array (or None) per model."""
+    parts = [np.zeros(0, SAMPLE) if s is None else _samples(s) for s in per_model]
+    return np.ascontiguousarray(np.concatenate(parts)), [int(p.shape[0]) for p in parts]
+
+
 # ------------------------------------------------------------------------------------------------ GPU trainer
 def set_epoch_plan(sizes, batch: int):
     """The steps of one epoch of a training set: a list of per-step lists [(start_k, count_k) for each model].  Model k walks
@@ -770,6 +979,18 @@ class TrainerSet(_State):
         sizes = [int(r[0].shape[0]) for r in records_per_model]
         if min(sizes) == 0:
             raise ValueError("no training samples")
+
+        def take_step(ep, st, lr):
+            xs = [records_per_model[k][0][a:a + n] for k, (a, n) in enumerate(st)]
+            ys = [records_per_model[k][1][a:a + n] for k, (a, n) in enumerate(st)]
+            return self.step(xs, ys, lr)
+
+        return self._epochs(sizes, epochs, batch, schedule, log, keep, checkpoint, start_epoch, take_step,
+                            None if val is None else lambda: self.evaluate(val))
+
+    def _epochs(self, sizes, epochs, batch, schedule, log, keep, checkpoint, start_epoch, take_step, evaluate_val, note=""):
+        """The epoch loop of fit and fit_data: take_step(epoch, step of set_epoch_plan, lr) -> losses; evaluate_val() -> one dict
+        per model, or None for a run without validation; `note` ends every log line."""
         plan = set_epoch_plan(sizes, batch)
         self._best_start(self.n_models, keep, checkpoint, start_epoch)
         histories = [[] for _ in range(self.n_models)]
@@ -778,15 +999,13 @@ class TrainerSet(_State):
             tot = [0.0] * self.n_models
             cnt = [[0, 0, 0] for _ in range(self.n_models)]
             for st in plan:
-                xs = [records_per_model[k][0][a:a + n] for k, (a, n) in enumerate(st)]
-                ys = [records_per_model[k][1][a:a + n] for k, (a, n) in enumerate(st)]
-                losses = self.step(xs, ys, lr)
+                losses = take_step(ep, st, lr)
                 for k, (_, n) in enumerate(st):
                     if n:
                         tot[k] += losses[k] * n
                         for q, v in enumerate(self.metrics(k)):
                             cnt[k][q] += v
-            evs = self.evaluate(val) if val is not None else None
+            evs = evaluate_val() if evaluate_val is not None else None
             for k in range(self.n_models):
                 tp, fp, fn = cnt[k]
                 rec = {"epoch": ep, "lr": lr, "loss": tot[k] / sizes[k], "precision": tp / max(1, tp + fp),
@@ -797,11 +1016,94 @@ class TrainerSet(_State):
                         self._best_update(k, rec["val_loss"], functools.partial(self.weights_bytes, k))
                 histories[k].append(rec)
                 if log:
-                    log(_epoch_text(ep, epochs, rec, k if self._tag_models else None))
+                    log(_epoch_text(ep, epochs, rec, k if self._tag_models else None) + (note and note.format(windows=sizes[k])))
             if checkpoint is not None:
                 self.save_state(checkpoint, epoch=ep + 1)
                 self._best_save(checkpoint)
         return histories
+
+    # ---- the same from a resident data set (include/covahip.h, "Training data")
+    def _check_data(self, data):
+        if (data.h, data.w) != (self.h, self.w):
+            raise ValueError(f"a {data.h}x{data.w} data set for a {self.h}x{self.w} trainer")
+
+    def step_data(self, data, samples_per_model, lrs=None):
+        """step() on samples of a TrainData: samples_per_model[k] = a SAMPLE array of b_k entries (None or empty: model k sits the
+        step out).  Bit-identical to step() on data.gather() of the same samples."""
+        if len(samples_per_model) != self.n_models:
+            raise ValueError(f"a step of this set takes {self.n_models} entries")
+        self._check_data(data)
+        samples, batches = _pack_samples(samples_per_model)
+        if not any(batches):
+            raise ValueError("a set step needs at least one model with samples")
+        bt = np.ascontiguousarray(batches, dtype=np.int32)
+        lrs = self._lrs(lrs)
+        losses = np.zeros(self.n_models, np.float32)
+        L.check(self._lib.covahip_train_step_set_data(self.handle, data.handle, samples.ctypes.data, bt.ctypes.data, lrs.ctypes.data,
+                                                      losses.ctypes.data), "covahip_train_step_set_data", self.ctx.handle)
+        for k in range(self.n_models):
+            self.step_counts[k] += int(batches[k] > 0)
+        return [float(v) for v in losses]
+
+    def evaluate_data(self, data, tables_per_model, stride: int = 1, want_sample_loss: bool = False, want_logits: bool = False):
+        """evaluate() on windows of a TrainData: tables_per_model[k] = model k's windows() table, scored as they are (canonical
+        order, forward, unmirrored, at `stride`), or a SAMPLE array to score exactly those samples; None or empty = nothing for
+        model k.  Returns evaluate()'s dicts."""
+        if len(tables_per_model) != self.n_models:
+            raise ValueError(f"{len(tables_per_model)} tables for {self.n_models} models")
+        self._check_data(data)
+        per = [None if t is None else t if getattr(t, "dtype", None) == SAMPLE else plain_samples(t, stride) for t in tables_per_model]
+        samples, counts = _pack_samples(per)
+        total = sum(counts)
+        if not total:
+            raise ValueError("no samples to evaluate: an evaluation needs at least one model with samples")
+        sl = np.empty(total, np.float32) if want_sample_loss else None
+        lg = np.empty((total, self.h, self.w), np.float32) if want_logits else None
+        cnt = np.ascontiguousarray(counts, dtype=np.int32)
+        res = (L.TrainEvalResult * self.n_models)()
+        L.check(self._lib.covahip_train_eval_set_data(self.handle, data.handle, samples.ctypes.data, cnt.ctypes.data,
+                                                      None if sl is None else sl.ctypes.data, None if lg is None else lg.ctypes.data,
+                                                      res, L.MEM_HOST), "covahip_train_eval_set_data", self.ctx.handle)
+        outs, at = [], 0
+        for k, n in enumerate(counts):
+            outs.append(_eval_out(res[k], None if sl is None else sl[at:at + n], None if lg is None else lg[at:at + n]))
+            at += n
+        return outs
+
+    def fit_data(self, data, tables_per_model, epochs: int = 20, batch: int = 4, *, strides=(1,), shuffle: bool = False, flip=(),
+                 reverse: bool = False, data_seed: int = 0, val_tables=None, schedule=keras_lr, log=None, keep: str = "last",
+                 checkpoint=None, start_epoch: int = 0):
+        """fit() from a resident TrainData: tables_per_model[k] = model k's windows() table, and every epoch walks
+        epoch_samples(table, strides, data_seed, epoch, model = k, shuffle, flip, reverse) of it -- a new order and new mirrors
+        every epoch, a pure function of (data_seed, epoch, k), so a resumed run continues exactly.  Everything else is fit's:
+        set_epoch_plan, the partial last batch, the histories, keep="best", the checkpoints.  val_tables = one table per model,
+        scored after every epoch as they are, at min(strides), never shuffled or augmented.  With windows(mode="skip") and no
+        augmentation this is fit(slide(...)), bit for bit.  The augmentation settings are not part of the checkpoint: a resumed
+        run passes them again, like the plan and the post."""
+        _check_fit_args(val_tables, keep)
+        if len(tables_per_model) != self.n_models:
+            raise ValueError(f"{len(tables_per_model)} tables for {self.n_models} models")
+        if val_tables is not None and len(val_tables) != self.n_models:
+            raise ValueError(f"{len(val_tables)} validation tables for {self.n_models} models")
+        if not 1 <= batch <= self.max_batch:
+            raise ValueError(f"batch {batch} outside [1, max_batch = {self.max_batch}] of this trainer")
+        self._check_data(data)
+        strides = _strides(strides)
+        tables = [np.asarray(t, dtype=np.int64).reshape(-1, 2) for t in tables_per_model]
+        sizes = [int(t.shape[0]) for t in tables]
+        if min(sizes) == 0:
+            raise ValueError("no training samples")
+        current = {}
+
+        def take_step(ep, st, lr):
+            if current.get("epoch") != ep:
+                current["epoch"] = ep
+                current["samples"] = [epoch_samples(t, strides, data_seed, ep, k, shuffle, flip, reverse) for k, t in enumerate(tables)]
+            return self.step_data(data, [current["samples"][k][a:a + n] for k, (a, n) in enumerate(st)], lr)
+
+        return self._epochs(sizes, epochs, batch, schedule, log, keep, checkpoint, start_epoch, take_step,
+                            None if val_tables is None else lambda: self.evaluate_data(data, val_tables, min(strides)),
+                            note=" windows {windows}")
 
 
 class Trainer(_State):
@@ -879,6 +1181,18 @@ class Trainer(_State):
         """TrainerSet.fit of records = (stacks, labels) and val = (stacks, labels) or None: the one history."""
         return self._set.fit([records], epochs, batch, schedule, log, None if val is None else [val], keep, checkpoint, start_epoch)[0]
 
+    def step_data(self, data, samples, lr: float | None = None) -> float:
+        """TrainerSet.step_data of the one model: a SAMPLE array of the batch."""
+        return self._set.step_data(data, [samples], lr)[0]
+
+    def evaluate_data(self, data, table, stride: int = 1, want_sample_loss: bool = False, want_logits: bool = False) -> dict:
+        """TrainerSet.evaluate_data of the one table (or SAMPLE array): the one dict."""
+        return self._set.evaluate_data(data, [table], stride, want_sample_loss, want_logits)[0]
+
+    def fit_data(self, data, table, epochs: int = 20, batch: int = 4, *, val_table=None, **kw):
+        """TrainerSet.fit_data of the one table and val_table (or None), with its keywords: the one history."""
+        return self._set.fit_data(data, [table], epochs, batch, val_tables=None if val_table is None else [val_table], **kw)[0]
+
 
 def parse_args(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cova_amd.train", description=__doc__.split("\n")[0])
@@ -917,7 +1231,23 @@ def parse_args(argv=None):
                                                                                  "for a camera without a sidecar")
     ap.add_argument("--mask-threshold", type=float, metavar="P", help="the camera's mask threshold as a probability, for a camera "
                                                                       "without a sidecar")
+    ap.add_argument("--windows", choices=("skip", "overlap"), help="which windows of a recording are samples: 'skip', frames "
+                                                                   "4j..4j+3 (what runs without these flags), or 'overlap', "
+                                                                   "every window: F - 3 of F frames.  This and the five flags "
+                                                                   "below train from a device-resident data set, each file one "
+                                                                   "segment that no window crosses")
+    ap.add_argument("--stride", type=_stride_list, metavar="S[,S...]", help="frame strides of a window, one drawn per sample and epoch")
+    ap.add_argument("--flip", choices=("x", "y", "xy"), help="mirror samples in x, y or both, drawn per sample and epoch")
+    ap.add_argument("--reverse", action="store_true", help="reverse samples in time, drawn per sample and epoch")
+    ap.add_argument("--shuffle", action="store_true", help="a new sample order every epoch")
+    ap.add_argument("--data-seed", type=int, metavar="N", help="seed of the order and the augmentation draws (default 0)")
     a = ap.parse_args(argv)
+    a.resident = (a.windows is not None or a.stride is not None or a.flip is not None or a.reverse or a.shuffle
+                  or a.data_seed is not None)
+    if a.eval_only and (a.flip or a.reverse or a.shuffle or a.data_seed is not None):
+        ap.error("--flip / --reverse / --shuffle / --data-seed shape a training; --eval-only trains nothing")
+    if a.eval_only and a.stride is not None and len(a.stride) != 1:
+        ap.error("--eval-only scores every window at ONE stride: --stride S")
     if a.post and (a.ignore_rects is not None or a.mask_threshold is not None):
         ap.error("--post carries the ignore region and the threshold: it excludes --ignore-rects and --mask-threshold")
     if a.mask_threshold is not None and not 0.0 < a.mask_threshold < 1.0:
@@ -952,6 +1282,14 @@ def parse_args(argv=None):
     except ValueError as e:
         ap.error(str(e))
     return a
+
+
+def _stride_list(text):
+    """--stride: S[,S...], each at least 1."""
+    try:
+        return _strides([int(v) for v in text.split(",")])
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"strides are positive integers joined with commas, got {text!r}")
 
 
 def _rects(text):
@@ -1128,8 +1466,73 @@ def main_set(a) -> int:
     return 0
 
 
+def main_resident(a) -> int:
+    """Training or scoring from a device-resident data set (--windows / --stride / --flip / --reverse / --shuffle / --data-seed):
+    every file is one segment, one data set serves all models of a --set, and the samples of an epoch are epoch_samples of the
+    model's windows."""
+    from .elements import Context
+
+    where = a.eval_only or a.output
+    jobs = set_jobs(a.records, where) if a.as_set else [(list(a.records), where)]
+    mode, strides = a.windows or "skip", a.stride or (1,)
+    files, val_files = [], []
+    for k, (fl, _) in enumerate(jobs):
+        files.append([read_tfrecords(f, a.h_mb, a.w_mb) for f in fl])
+        names = [] if not a.val else [f for f in a.val[k].split(",") if f] if a.as_set else list(a.val)
+        val_files.append([read_tfrecords(f, a.h_mb, a.w_mb) for f in names])
+    capacity = sum(fr.shape[0] for group in files + val_files for fr, _ in group)
+    if not capacity:
+        raise ValueError("the records hold no frames")
+    posts = post_settings(a, len(jobs))
+    ctx = Context(a.device)
+    data = TrainData(ctx, a.h_mb, a.w_mb, capacity)
+    tables, val_tables = [], ([] if a.val or a.val_frac is not None else None)
+    for k in range(len(jobs)):
+        segs = [data.append(fr, gt) for fr, gt in files[k] if fr.shape[0]]
+        vsegs = [data.append(fr, gt) for fr, gt in val_files[k] if fr.shape[0]]
+        if a.val_frac is not None:
+            segs, vsegs = split_frames_tail(segs, a.val_frac)
+        tables.append(windows(segs, mode, strides))
+        if val_tables is not None:
+            val_tables.append(windows(vsegs, mode, strides))
+        print((f"model {k}: " if a.as_set else "") + f"{sum(b - s for s, b in segs)} frames -> {tables[k].shape[0]} windows of "
+              f"{a.h_mb}x{a.w_mb}" + (f", {val_tables[k].shape[0]} to validate" if val_tables is not None else ""), file=sys.stderr)
+    del files, val_files
+    if a.eval_only:
+        ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=[_read_weights(p) for _, p in jobs], max_batch=a.batch)
+        _apply_posts(ts, posts)
+        for k, ((_, path), ev) in enumerate(zip(jobs, ts.evaluate_data(data, tables, min(strides)))):
+            if posts is not None:
+                thr, keep = ts.get_post(k)
+                ev["post"] = {"logit_thresh": thr, "ignored": int((keep == 0).sum())}
+            print(json.dumps({"weights": path, **ev}))
+    else:
+        if a.as_set:
+            os.makedirs(a.output, exist_ok=True)
+            init = [_read_weights(p) for p in init_paths(a.records, a.init)] if a.init else None
+        else:
+            init = [_read_weights(a.init)] if a.init else None
+        ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=init, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))],
+                        max_batch=a.batch, **_plan_kw(a))
+        ts._tag_models = a.as_set
+        _apply_posts(ts, posts)
+        start = _resume(ts, a, len(jobs))
+        ts.fit_data(data, tables, epochs=a.epochs, batch=a.batch, strides=strides, shuffle=a.shuffle, flip=a.flip or (),
+                    reverse=a.reverse, data_seed=a.data_seed or 0, val_tables=val_tables, log=lambda s: print(s, file=sys.stderr),
+                    keep=a.keep, checkpoint=a.checkpoint, start_epoch=start)
+        for k, (_, out) in enumerate(jobs):
+            with open(out, "wb") as f:
+                f.write(ts.best_weights_bytes(k) if a.keep == "best" else ts.weights_bytes(k))
+    ts.close()
+    data.close()
+    ctx.close()
+    return 0
+
+
 def main(argv=None) -> int:
     a = parse_args(argv)
+    if a.resident:
+        return main_resident(a)
     if a.eval_only:
         return main_eval(a)
     if a.as_set:

@@ -658,6 +658,64 @@ int covahip_train_set_post(covahip_train *tr, int model, const covahip_blobnet_p
 int covahip_train_get_post(covahip_train *tr, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_post);
 void covahip_train_destroy(covahip_train *tr);
 
+/* ------------------------------------------------------------ Training data
+ * A device-resident training data set: the frames of any number of recordings (of any mix of cameras, of ONE geometry) with their
+ * labels, and a trainer that takes its batches from it by a table of frame indices.  A stack is four frame indices, as the
+ * stack_index of covahip_filter_forward_frames has it, so a recording of F frames holds F - 3 windows (metapreprocess at
+ * gamma = 4 emits F / 4 of them), and since bytes 1 and 2 of a record are motion-vector MAGNITUDES a mirrored frame and a
+ * time-reversed window are valid records too: no field changes sign.
+ *   Storage: records u16 [capacity][h_mb][w_mb], packed exactly as covahip_carrier_pack packs them (everything BlobNet keeps of a
+ *   record: the step's first operation is clip(x, 0, 6)), and labels u8 [capacity][h_mb][w_mb], the bytes AS GIVEN -- not reduced
+ *   to 0 / 1, the loss reads the byte as a float.  3 bytes per macroblock against 5 of the frames appended; the capacity is fixed at
+ *   creation (16 <= h_mb, w_mb <= 1024, 1 <= capacity_frames < 2^31) and all element offsets are 64-bit.
+ *   A sample names GLOBAL frame indices of the data set: */
+typedef struct covahip_train_data covahip_train_data;
+typedef struct covahip_train_sample {   /* 24 bytes */
+    int32_t  frame[4];   /* the frames of the T = 0 (current) .. 3 (oldest) slices, as stack_index names them */
+    int32_t  label;      /* the frame whose gt labels the sample (frame[0] for a forward window)            */
+    uint32_t flags;      /* bit 0 mirror x, bit 1 mirror y; any other bit: COVAHIP_ERR_INVALID_ARG           */
+} covahip_train_sample;
+/*   The batch a table of n samples describes: stack u8 [n][4 * h_mb][w_mb][4] and labels u8 [n][h_mb][w_mb] with
+ *       stack[b][t * h_mb + y][x] = (min(class, 6), min(mv_x, 6), min(mv_y, 6), 0) of frame[t] at (y', x'),
+ *       label[b][y][x]           = the gt byte of frame `label` at (y', x'),
+ *       x' = w_mb - 1 - x when bit 0 of flags is set, else x;  y' = h_mb - 1 - y when bit 1 is set, else y.
+ *   ONE launch builds the stacks and the labels of all n samples (of all models of a set step).
+ * Calling rules.  `samples` is always a HOST array.  Every call is synchronous, on the ctx's primary stream, ordered as
+ * covahip_train_step is.  Every check runs on the host before anything is launched and a refused call changes nothing:
+ * COVAHIP_ERR_INVALID_ARG for a NULL array, an index outside [0, frames), an unknown flag bit, a data set whose geometry (or
+ * ctx) is not the trainer's, and what the pointer form of the call refuses (a batch above max_batch among it);
+ * COVAHIP_ERR_OVERFLOW for an append past the capacity.
+ * covahip_train_data_append: n >= 1 frames u8 [n][h_mb][w_mb][4] (byte 3 is ignored) and gt u8 [n][h_mb][w_mb]; mem_kind applies
+ * to both.  Device frames are packed by a kernel; host frames with covahip_carrier_pack, and two bytes per macroblock are
+ * uploaded.  *first_index (may be NULL) = the index of the first frame appended: the n frames are [first, first + n).
+ * covahip_train_data_gather: the batch itself, for a caller that wants to see it (mem_kind applies to stack and gt).  A DEVICE
+ * stack must be 4-byte aligned (the launch stores a record's four bytes at once): COVAHIP_ERR_INVALID_ARG otherwise. */
+int  covahip_train_data_create(covahip_ctx *ctx, int h_mb, int w_mb, int64_t capacity_frames, covahip_train_data **out);
+int  covahip_train_data_append(covahip_train_data *d, const uint8_t *frames, const uint8_t *gt, int n, int mem_kind,
+                               int64_t *first_index);
+int  covahip_train_data_frames(const covahip_train_data *d, int64_t *n);
+int  covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample *samples, int n, uint8_t *stack, uint8_t *gt,
+                               int mem_kind);
+void covahip_train_data_destroy(covahip_train_data *d);
+/* covahip_train_step / _step_set / _eval / _eval_set on samples of a data set: the gather launch writes the batch straight into
+ * the trainer's own staging, in the packing the step expects; nothing is copied from the host but the table.  samples: packed in
+ * model order (sum of batches / counts entries); eval takes any n, in chunks of max_batch, as covahip_train_eval does; mem_kind
+ * of the eval forms applies to sample_loss and logits.
+ *   Contract D (data) -- the data forms are BIT-IDENTICAL to their pointer forms on the stacks and labels the samples describe,
+ *   the comparison stacks built from the frames AS THEY WERE APPENDED, field values above 6 included (the step clips them as the
+ *   packing does): loss, gradients and metrics; weights, moving statistics, Adam state and step counter; logits and sample
+ *   losses.  The step itself is unchanged, only the way its staging gets filled is new: contracts A, B and C, the bit-identity
+ *   of a set's models, the training plan and the post hold as written. */
+int covahip_train_step_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, int batch, float lr,
+                            float *loss);
+int covahip_train_step_set_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples,
+                                const int32_t *batches, const float *lrs, float *losses);
+int covahip_train_eval_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples, int n,
+                            float *sample_loss, float *logits, covahip_train_eval_result *out, int mem_kind);
+int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const covahip_train_sample *samples,
+                                const int32_t *counts, float *sample_loss, float *logits, covahip_train_eval_result *out,
+                                int mem_kind);
+
 /* ------------------------------------------------------------ MoG labels
  * The training labels of the reference's "train from scratch" flow, made on the GPU: what utils/generate-mog.py does with
  * OpenCV to a decoded video, per frame in decode-output order, per video:
