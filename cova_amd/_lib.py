@@ -299,6 +299,8 @@ DEV_PROTOTYPES = {
     "covahip_dev_mog_set_post_form": (C.c_int, [_P, C.c_int, C.c_int]),
     "covahip_dev_mog_band_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "covahip_dev_monitor_slice": (C.c_int, [_P, C.c_int]),
+    "covahip_dev_heat_set_stage": (C.c_int, [_P, _SZ]),
+    "covahip_dev_train_data_set_stage": (C.c_int, [_P, _SZ]),
 }
 
 _lib = None

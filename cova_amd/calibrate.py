@@ -112,6 +112,11 @@ def heat_add_device(ctx, d_logits, d_gt, n, mem_kind=L.MEM_DEVICE) -> None:
     L.check(L.lib().covahip_post_heat_add(ctx.handle, d_logits, d_gt, int(n), mem_kind), "covahip_post_heat_add", ctx.handle)
 
 
+def heat_set_stage(ctx, nbytes: int = 0) -> None:
+    """Developer switch (include/covahip_dev.h): device bytes of host samples staged per piece of a heat_add, 0 = the default."""
+    L.check(L.lib().covahip_dev_heat_set_stage(ctx.handle, int(nbytes)), "covahip_dev_heat_set_stage")
+
+
 def heat_end(ctx, h, w, th) -> dict:
     """covahip_post_heat_end: reads the open heat of grid [h][w] with thresholds th out and closes it.  -> fire, both i64
     [T][h][w], gt i64 [h][w], samples, logit_thresh."""

@@ -147,7 +147,8 @@ extern "C" int covahip_post_heat_add(covahip_ctx *ctx, const float *logits, cons
         for (int s0 = 0; s0 < n; s0 += HT_LAUNCH_MAX)   // (a launch's slices fit a grid dimension)
             if (int rc = heat_launch(ctx, logits + (size_t)s0 * hw, gt + (size_t)s0 * hw, std::min(HT_LAUNCH_MAX, n - s0))) return rc;
     } else {   // staged in pieces: [logits f32][labels u8]
-        const int piece = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, HT_STAGE / (hw * 5)));
+        const size_t stage = ctx->heat_stage ? ctx->heat_stage : HT_STAGE;
+        const int piece = (int)std::min<size_t>((size_t)n, std::max<size_t>(1, stage / (hw * 5)));
         if (int rc = covahip_ensure_buffer(ctx, &ctx->stage_in, &ctx->stage_in_bytes, (size_t)piece * hw * 5)) return rc;
         float *sl = (float *)ctx->stage_in;
         uint8_t *sg = (uint8_t *)ctx->stage_in + (size_t)piece * hw * 4;
@@ -177,5 +178,11 @@ extern "C" int covahip_post_heat_end(covahip_ctx *ctx, int64_t *fire, int64_t *b
     if (fire) std::copy(host.begin(), host.begin() + T * hw, fire);
     if (both) std::copy(host.begin() + T * hw, host.begin() + 2 * T * hw, both);
     if (gt_fire) std::copy(host.begin() + 2 * T * hw, host.end(), gt_fire);
+    return COVAHIP_OK;
+}
+
+extern "C" int covahip_dev_heat_set_stage(covahip_ctx *ctx, size_t bytes) {
+    if (!ctx) return COVAHIP_ERR_INVALID_ARG;
+    ctx->heat_stage = bytes;
     return COVAHIP_OK;
 }

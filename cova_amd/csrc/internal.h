@@ -114,6 +114,7 @@ struct covahip_ctx {
     int heat_h = 0, heat_w = 0, heat_T = 0;
     float heat_thresh[64] = {};
     int64_t heat_samples = 0;
+    size_t heat_stage = 0;   // bytes of host samples staged per piece; 0: heat.hip's default (covahip_dev_heat_set_stage)
     // covahip_monitor_*: the open monitor (null: none), the developer override of its slice length (0 = automatic), and whether
     // filter steps bypass it (covahip_dev_graph_probe: a captured step must not carry a counted launch into its replays)
     CovahipMonitor *mon = nullptr;

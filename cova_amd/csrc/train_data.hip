@@ -69,6 +69,7 @@ struct covahip_train_data {
     void *stage = nullptr;                                      // device staging of a host-bound gather
     size_t stage_bytes = 0;
     std::vector<uint16_t> pack;                                 // host staging of a host append
+    size_t stage_budget = STAGE_BYTES;                          // covahip_dev_train_data_set_stage changes it per set
 };
 
 namespace {
@@ -176,7 +177,7 @@ int covahip_train_data_append(covahip_train_data *d, const uint8_t *frames, cons
         COVAHIP_CHECK_HIP(ctx, hipGetLastError());
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d->gt + at, gt, n_mb, hipMemcpyDeviceToDevice, s));
     } else {   // packed on the host: two bytes per macroblock cross the bus
-        const size_t chunk = std::min(n_mb, STAGE_BYTES / sizeof(uint16_t));
+        const size_t chunk = std::min(n_mb, std::max<size_t>(1, d->stage_budget / sizeof(uint16_t)));
         if (d->pack.size() < chunk) d->pack.resize(chunk);
         for (size_t o = 0; o < n_mb; o += chunk) {
             const size_t m = std::min(chunk, n_mb - o);
@@ -209,7 +210,7 @@ int covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample 
     const hipStream_t s = ctx->stream;
     const size_t hw = (size_t)d->h * d->w, stack_b = TT * hw * 4, per = stack_b + hw;
     // a launch's samples: what the grid takes, and for host output what the staging holds
-    const size_t fit = host ? std::max<size_t>(1, std::min<size_t>(STAGE_BYTES / per, GATHER_MAX)) : (size_t)GATHER_MAX;
+    const size_t fit = host ? std::max<size_t>(1, std::min<size_t>(d->stage_budget / per, GATHER_MAX)) : (size_t)GATHER_MAX;
     const int chunk = (int)std::min<size_t>((size_t)n, fit);
     if (host)
         if (int rc = covahip_ensure_buffer(ctx, &d->stage, &d->stage_bytes, (size_t)chunk * per)) return rc;
@@ -235,6 +236,12 @@ void covahip_train_data_destroy(covahip_train_data *d) {
     hipSetDevice(d->ctx->device);
     covahip_sync_all(d->ctx);
     free_data(d);
+}
+
+int covahip_dev_train_data_set_stage(covahip_train_data *d, size_t bytes) {
+    if (!d) return COVAHIP_ERR_INVALID_ARG;
+    d->stage_budget = bytes ? bytes : STAGE_BYTES;
+    return COVAHIP_OK;
 }
 
 }  // extern "C"

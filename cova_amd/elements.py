@@ -444,7 +444,9 @@ class FilterPipe:
 
     def close(self):
         if getattr(self, "_h", None):
-            self._lib.covahip_pipe_destroy(self._h)
+            # (a pipe outliving its closed ctx is not freed: covahip_pipe_destroy synchronises that ctx, which is gone)
+            if getattr(self.net.ctx, "handle", None):
+                self._lib.covahip_pipe_destroy(self._h)
             self._h = None
 
     __del__ = close

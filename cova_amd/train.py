@@ -711,6 +711,10 @@ class TrainData:
         """The same from device pointers (packed by a kernel)."""
         return self._append(d_frames, d_gt, n, L.MEM_DEVICE)
 
+    def set_stage(self, nbytes: int = 0) -> None:
+        """Developer switch (include/covahip_dev.h): bytes of the staging of host appends and host-bound gathers, 0 = the default."""
+        L.check(self._lib.covahip_dev_train_data_set_stage(self.handle, int(nbytes)), "covahip_dev_train_data_set_stage")
+
     def gather(self, samples):
         """(stacks u8 [n][4h][w][4], labels u8 [n][h][w]) of a SAMPLE array: the batch a step on these samples sees."""
         samples = _samples(samples)

@@ -47,6 +47,15 @@ const char *covahip_strerror(int status);
 const char *covahip_version(void);
 
 enum { COVAHIP_MEM_HOST = 0, COVAHIP_MEM_DEVICE = 1 };
+/* Alignment of DEVICE pointers (host pointers are copied into the library's own staging and may have any alignment).  Every
+ * entry below says which of two things holds for each of its device pointers:
+ *   "any alignment": the library looks at the address, runs a narrower kernel form where the wide one does not apply, and
+ *       gives the same results (tests offset each such pointer by single bytes);
+ *   "aligned to N": the kernels load or store N bytes at a time through the pointer and there is NO check and no other form;
+ *       what covahip_malloc returns (256-byte aligned) always qualifies, an address inside such an allocation must be a
+ *       multiple of N.
+ * Pointers to f32, i32 and covahip_box always need their natural 4-byte alignment; that is not repeated per entry.
+ * ("Host-side choices of kernel form and chunking", lists the branches and the tests that run them.) */
 
 /* ------------------------------------------------------------ GPU context */
 typedef struct covahip_ctx covahip_ctx;
@@ -157,7 +166,9 @@ int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models);
  * logits (may be NULL): f32 [batch][h_mb][w_mb] pre-sigmoid output.
  * mask   (may be NULL): u8  [batch][h_mb][w_mb], 1 where sigmoid(logit) > 0.5.
  * mem_kind applies to all three pointers.  Asynchronous for device pointers (use
- * covahip_ctx_sync); synchronous for host pointers.                               */
+ * covahip_ctx_sync); synchronous for host pointers.
+ * Device pointers: rgba_stack aligned to 16 (four macroblocks a load; w_mb is a multiple of 4, so every row is); mask any
+ * alignment (off a 4-byte boundary it is stored byte by byte); logits natural.        */
 int covahip_blobnet_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, float *logits,
                             uint8_t *mask, int mem_kind);
 /* covahip_blobnet_forward with a model per stack (model_ids: see covahip_blobnet_load_set). */
@@ -253,7 +264,9 @@ typedef struct covahip_sweep_cell { int64_t pred, pred_true, gt_found; } covahip
 typedef struct covahip_sweep_result {
     int64_t samples, gt_objects, gt_truncated;   /* gt_truncated: samples whose label had more than max_boxes objects */
 } covahip_sweep_result;
-/* logits f32 [n][h][w], gt u8 [n][h][w] (mem_kind applies to both; outputs are HOST).  pixel: i64 [n_thresh][3] = tp, fp, fn;
+/* logits f32 [n][h][w], gt u8 [n][h][w] (mem_kind applies to both; outputs are HOST).  Device pointers: gt any alignment, logits
+ * natural (with h * w a multiple of 4, logits on a 16-byte and gt on a 4-byte boundary the masks are made four macroblocks per
+ * work item, otherwise one: same counts).  pixel: i64 [n_thresh][3] = tp, fp, fn;
  * cells: [n_thresh][n_area]; truncated: i64 [n_thresh] = frames (sample, threshold) with more than max_boxes components.
  * Synchronous.  Outputs are OVERWRITTEN with this call's counts; the caller adds calls up. */
 int covahip_post_sweep(covahip_ctx *ctx, const covahip_sweep_cfg *cfg, const float *logits, const uint8_t *gt, int n,
@@ -283,7 +296,8 @@ typedef struct covahip_heat_cfg {
     const float *logit_thresh;       /* HOST [n_thresh], finite, strictly ascending (copied by begin) */
 } covahip_heat_cfg;
 int covahip_post_heat_begin(covahip_ctx *ctx, const covahip_heat_cfg *cfg);
-/* logits f32 [n][h][w], gt u8 [n][h][w]; mem_kind applies to both. */
+/* logits f32 [n][h][w], gt u8 [n][h][w]; mem_kind applies to both.  Device pointers: gt any alignment, logits natural (the kernel
+ * loads single values). */
 int covahip_post_heat_add(covahip_ctx *ctx, const float *logits, const uint8_t *gt, int n, int mem_kind);
 /* HOST outputs: fire, both i64 [n_thresh][h][w]; gt_fire i64 [h][w]; samples: the number of samples added. */
 int covahip_post_heat_end(covahip_ctx *ctx, int64_t *fire, int64_t *both, int64_t *gt_fire, int64_t *samples);
@@ -329,7 +343,8 @@ typedef struct covahip_monitor_cfg {
 struct covahip_box;   /* (bboxcc, below) */
 int covahip_monitor_begin(covahip_ctx *ctx, const covahip_monitor_cfg *cfg);
 /* mask u8 [n][h][w], counts i32 [n], boxes [n][max_boxes] (mem_kind applies to the three; boxes may be NULL with max_boxes == 0);
- * model_ids: HOST u8 [n], read during the call, or NULL = model 0. */
+ * model_ids: HOST u8 [n], read during the call, or NULL = model 0.  Device pointers: mask any alignment (read a word at a time
+ * only when h * w is a multiple of 4 and the pointer is on a 4-byte boundary); counts and boxes natural. */
 int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *counts, const struct covahip_box *boxes,
                         const uint8_t *model_ids, int n, int mem_kind);
 /* HOST outputs, each may be NULL: frames, boxes, frames_with_boxes, truncated i64 [n_models]; fire i64 [n_models][h][w];
@@ -353,7 +368,10 @@ typedef struct covahip_box {
  * written).  mem_kind applies to mask, boxes and counts.
  * Limit (COVAHIP_ERR_UNSUPPORTED): w <= 256.  Frames of up to about 6,400 2x2 blocks (1080p = 68x120, 1440p =
  * 90x160 macroblock grids) keep their union-find in the LDS of one CU; larger ones (a 4K grid is 135x240) run the
- * same algorithm with that state in global memory -- same results, slower.        */
+ * same algorithm with that state in global memory -- same results, slower.
+ * Device pointers: mask any alignment.  The wave-per-frame kernel and the run-based body load 8 mask bytes at a time and are
+ * chosen only when the pointer is on an 8-byte boundary and h * w and w are multiples of 8; otherwise the workgroup kernel reads
+ * the frame byte by byte -- same boxes, slower.  boxes and counts natural.        */
 int covahip_bboxcc(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, int w, int area_thresh,
                    covahip_box *boxes, int32_t *counts, int max_boxes, int mem_kind);
 /* covahip_bboxcc with a threshold per frame.  area_thresh: HOST i32 [batch], frame b keeps pixel-count >= area_thresh[b]; read
@@ -364,7 +382,10 @@ int covahip_bboxcc_v(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, in
 
 /* Fused hot path = nvinfer(BlobNet) -> maskcopy -> bboxcc for one batch: the mask
  * stays on the GPU.  logits/mask may be NULL.  bboxcc's limit (w <= 256) lies beyond the model's (w_mb <= 252):
- * every grid that loads runs here.                                                                  */
+ * every grid that loads runs here.
+ * Device pointers: rgba_stack aligned to 16, as for covahip_blobnet_forward; mask any alignment (off a 4-byte boundary the fused
+ * tail runs its band form, which stores the mask byte by byte, instead of its row form -- same mask, counts and boxes); logits,
+ * boxes and counts natural.                                                                         */
 int covahip_filter_forward(covahip_ctx *ctx, const uint8_t *rgba_stack, int batch, int area_thresh,
                            covahip_box *boxes, int32_t *counts, int max_boxes, float *logits,
                            uint8_t *mask, int mem_kind);
@@ -381,7 +402,8 @@ int covahip_filter_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const 
  *   frames:      u8 [n_frames][h_mb][w_mb][4], any mix of streams (mem_kind as for the other pointers)
  *   stack_index: HOST i32 [batch][4]: for output b the indices into `frames` of its T = 0 (current), 1, 2, 3
  *                (oldest) slices; NULL = one stream in order (batch == n_frames - 3, output b = frames b+3 .. b)
- *   4 <= n_frames <= 4 * max_batch; an index outside [0, n_frames) is COVAHIP_ERR_INVALID_ARG.               */
+ *   4 <= n_frames <= 4 * max_batch; an index outside [0, n_frames) is COVAHIP_ERR_INVALID_ARG.
+ * Device pointers: frames aligned to 16 (four macroblocks a load); the others as for covahip_filter_forward.     */
 int covahip_filter_forward_frames(covahip_ctx *ctx, const uint8_t *frames, int n_frames, const int32_t *stack_index,
                                   int batch, int area_thresh, covahip_box *boxes, int32_t *counts, int max_boxes,
                                   float *logits, uint8_t *mask, int mem_kind);
@@ -688,8 +710,10 @@ typedef struct covahip_train_sample {   /* 24 bytes */
  * covahip_train_data_append: n >= 1 frames u8 [n][h_mb][w_mb][4] (byte 3 is ignored) and gt u8 [n][h_mb][w_mb]; mem_kind applies
  * to both.  Device frames are packed by a kernel; host frames with covahip_carrier_pack, and two bytes per macroblock are
  * uploaded.  *first_index (may be NULL) = the index of the first frame appended: the n frames are [first, first + n).
+ * Device pointers: frames and gt any alignment (frames off a 4-byte boundary are read byte by byte).
  * covahip_train_data_gather: the batch itself, for a caller that wants to see it (mem_kind applies to stack and gt).  A DEVICE
- * stack must be 4-byte aligned (the launch stores a record's four bytes at once): COVAHIP_ERR_INVALID_ARG otherwise. */
+ * stack must be 4-byte aligned (the launch stores a record's four bytes at once): COVAHIP_ERR_INVALID_ARG otherwise; a device
+ * gt may have any alignment (label bytes are stored one at a time). */
 int  covahip_train_data_create(covahip_ctx *ctx, int h_mb, int w_mb, int64_t capacity_frames, covahip_train_data **out);
 int  covahip_train_data_append(covahip_train_data *d, const uint8_t *frames, const uint8_t *gt, int n, int mem_kind,
                                int64_t *first_index);
@@ -903,7 +927,8 @@ int covahip_carrier_write_records(const uint8_t *mb_type, const uint8_t *mv_x, c
  * bytes: the host-to-device copy is what bounds the element path (9.1 MB per 256-frame batch over PCIe).  The pinned host
  * pipeline takes its frames in this form when asked to (covahip_pipe_set_packed); results are bit-identical. */
 void covahip_carrier_pack(const uint8_t *frame, size_t n_mb, uint16_t *records);
-/* covahip_filter_forward_frames on packed records [n_frames][H][W] (device pointers only). */
+/* covahip_filter_forward_frames on packed records [n_frames][H][W] (device pointers only): d_records aligned to 8 (four records a
+ * load), the others as for covahip_filter_forward. */
 int covahip_filter_forward_frames_packed(covahip_ctx *ctx, const uint16_t *d_records, int n_frames, const int32_t *stack_index,
                                          int batch, int area_thresh, covahip_box *d_boxes, int32_t *d_counts, int max_boxes,
                                          float *d_logits, uint8_t *d_mask);

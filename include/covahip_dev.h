@@ -106,6 +106,19 @@ int covahip_dev_mog_band_plan(int work_w, int work_h, int *rows, int *bands, siz
  * byte counters spill, which the automatic choice reaches only with batches of thousands.  (tests/test_gpu_monitor.py) */
 int covahip_dev_monitor_slice(covahip_ctx *ctx, int samples);
 
+/* Device bytes of host samples (4 bytes of logit and 1 label byte per macroblock) that covahip_post_heat_add (COVAHIP_MEM_HOST)
+ * stages per piece; 0 restores the default of 64 MiB.  A call whose samples exceed it is uploaded and counted in several pieces
+ * of whole samples, at least one per piece.  Host-only: no kernel changes and the tables do not depend on it; device-memory calls
+ * ignore it.  (tests/test_gpu_heat.py) */
+int covahip_dev_heat_set_stage(covahip_ctx *ctx, size_t bytes);
+/* Bytes of the staging that a training-data set's host traffic moves through; 0 restores the default of 32 MiB.  A host
+ * covahip_train_data_append packs and uploads its frames in rounds of bytes / 2 macroblocks (at least one; a round may end in the
+ * middle of a frame), and a host-bound covahip_train_data_gather runs one launch per as many samples as fit (at least one).
+ * Host-only: no kernel changes and the results do not depend on it; device-memory calls ignore it.
+ * (tests/test_gpu_train_data.py) */
+struct covahip_train_data;
+int covahip_dev_train_data_set_stage(struct covahip_train_data *data, size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

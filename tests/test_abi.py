@@ -76,3 +76,5 @@ def test_null_and_invalid_arguments_do_not_need_a_gpu():
     assert lib.covahip_stack_new(16, 0, 1, C.byref(C.c_void_p())) == 1
     n = C.c_size_t()
     assert lib.covahip_bbox_deserialize_vec(None, 0, None, 0, C.byref(n)) == 1
+    assert lib.covahip_dev_heat_set_stage(None, C.c_size_t(0)) == 1          # the developer switches check their handle too
+    assert lib.covahip_dev_train_data_set_stage(None, C.c_size_t(0)) == 1

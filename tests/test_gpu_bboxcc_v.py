@@ -54,11 +54,14 @@ def _thresholds_matter(table, frames):
         assert all(a > b for a, b in zip(c, c[1:])) and c[-1] > 0, (u, c)
 
 
-def _device_call(ctx, cc, masks, thr, fn=None):
+def _device_call(ctx, cc, masks, thr, fn=None, shift=0):
+    """shift: the mask starts that many bytes past its (longer) allocation."""
     b, h, w = masks.shape
-    d_m, d_b, d_c = ctx.malloc(masks.nbytes), ctx.malloc(max(1, b * cc.max_boxes) * 20), ctx.malloc(b * 4)
+    d_m0, d_b, d_c = ctx.malloc(masks.nbytes + 8), ctx.malloc(max(1, b * cc.max_boxes) * 20), ctx.malloc(b * 4)
+    d_m = d_m0 + shift
     lib = L.lib()
     try:
+        assert d_m0 % 8 == 0
         ctx.h2d(d_m, masks)
         L.check(lib.covahip_memset(ctx.handle, d_c, 0xA5, b * 4), "memset")          # poisoned: a frame no pass labels cannot pass
         L.check(lib.covahip_memset(ctx.handle, d_b, 0x5A, b * cc.max_boxes * 20), "memset")
@@ -72,7 +75,7 @@ def _device_call(ctx, cc, masks, thr, fn=None):
         ctx.d2h(counts, d_c)
         return boxes, counts, stats
     finally:
-        for p in (d_m, d_b, d_c):
+        for p in (d_m0, d_b, d_c):
             ctx.free(p)
 
 
@@ -120,6 +123,60 @@ def test_every_kernel_choice(own_ctx, h, w, cap, kernels):
     finally:
         ctx.profile(False)
         cc.set_wave_cap(0)
+
+
+@pytest.mark.parametrize("density", [0.05, 0.5])
+@pytest.mark.parametrize("cap", [0, 24, -1])
+@pytest.mark.parametrize("h,w", [(68, 120), (16, 64)])
+def test_mask_pointer_off_an_8_byte_boundary(own_ctx, h, w, cap, density):
+    """h * w and W are multiples of 8 here, so only the caller's pointer keeps the frames off 8-byte boundaries: the wave kernel
+    and the run-based body are turned away (both load 8 mask bytes at a time) and the block-based body reads byte by byte.  Both
+    device entries, against the oracle."""
+    ctx = own_ctx
+    b, max_boxes = 11, 2048
+    masks = _noise(np.random.default_rng(h + w + cap), b, h, w, density)
+    thr = np.array([THRS[(3 * i + 1) % 5] for i in range(b)], np.int32)
+    table = _oracle(masks, max_boxes)
+    assert all(table[1][1][u] > table[8][1][u] for u in range(b))      # from the oracle alone: the thresholds matter
+    idx = np.arange(b)
+    cc, one = BboxCc(ctx, 99, max_boxes), BboxCc(ctx, 2, max_boxes)
+    cc.set_wave_cap(cap)
+    ctx.profile(True)
+    try:
+        for shift in (1, 4, 7):
+            boxes, counts, _ = _device_call(ctx, cc, masks, thr, shift=shift)
+            _check(boxes, counts, table, idx, thr, max_boxes, f"bboxcc_v, mask + {shift}")
+            boxes, counts, _ = _device_call(ctx, one, masks, None, fn=one.regionprops_device, shift=shift)
+            _check(boxes, counts, table, idx, np.full(b, 2), max_boxes, f"bboxcc, mask + {shift}")
+        assert set(ctx.profile_read()) == {"bboxcc_kernel"}
+    finally:
+        ctx.profile(False)
+        cc.set_wave_cap(0)
+
+
+def test_large_batch_plan_declines_an_unaligned_mask(own_ctx):
+    """More than 3 x num_cu frames ask for the wave kernel's large-batch plan; a mask 4 bytes off has to be declined by it."""
+    ctx = own_ctx
+    h, w, max_boxes = 16, 64, 512
+    rng = np.random.default_rng(21)
+    uniq = np.concatenate([_noise(rng, 6, h, w, 0.05), _noise(rng, 6, h, w, 0.5)])
+    table = _oracle(uniq, max_boxes)
+    assert all(table[1][1][u] > table[8][1][u] for u in range(12))
+    b = 3 * ctx.info()["num_cu"] + 8
+    idx = rng.integers(0, 12, b)
+    thr = rng.choice(THRS, b).astype(np.int32)
+    cc = BboxCc(ctx, 99, max_boxes)
+    masks = np.ascontiguousarray(uniq[idx])
+    ctx.profile(True)
+    try:
+        boxes, counts, stats = _device_call(ctx, cc, masks, thr, shift=4)
+        assert set(ctx.profile_read()) == {"bboxcc_kernel"} and stats["batch"] == 0
+        _check(boxes, counts, table, idx, thr, max_boxes, "large batch, mask + 4")
+        boxes, counts, stats = _device_call(ctx, cc, masks, thr)           # aligned: the plan it declined
+        assert "bboxcc_wave_kernel" in set(ctx.profile_read())
+        _check(boxes, counts, table, idx, thr, max_boxes, "large batch, aligned")
+    finally:
+        ctx.profile(False)
 
 
 def test_truncation_per_frame(own_ctx):

@@ -22,6 +22,8 @@ GRIDS = [(1, 1), (5, 7), (9, 20), (17, 16), (45, 80), (67, 120)]
 NS = [1, 2, 37, 257]                                      # 37 and 257: uneven sample slices
 N_MAX = 257
 T_SEL = {1: [32], 3: [10, 32, 50], 64: list(range(64))}
+# the edges of the kernel's 16 / 32 / 64-threshold instantiations: evenly spread planes of the 64, the last one included
+T_SEL.update({k: np.linspace(0, 63, k).astype(int).tolist() for k in (16, 17, 32, 33)})
 TABLES = ("fire", "both", "gt")
 INVALID = 1
 
@@ -101,6 +103,64 @@ def test_tables_equal_the_restatement(ctx, cases, h, w, n, n_thresh, device):
     got = _heat_device(ctx, lg, gt, th) if device else cal.heat(ctx, lg, gt, th)
     _same(got, want)
     assert np.array_equal(got["logit_thresh"], th)
+
+
+@pytest.mark.parametrize("device", [False, True])
+@pytest.mark.parametrize("n_thresh", [16, 17, 32, 33])
+@pytest.mark.parametrize("h,w", [(5, 7), (17, 16)])
+def test_threshold_count_edges(ctx, cases, h, w, n_thresh, device):
+    """16 | 17 and 32 | 33 thresholds: either side of the choice between the kernel's 16-, 32- and 64-threshold forms."""
+    n = 37
+    d, ref = cases(h, w, n)
+    t_idx = T_SEL[n_thresh]
+    assert len(set(t_idx)) == n_thresh and t_idx[-1] == 63
+    want = _select(ref, t_idx)
+    assert want["fire"][0].any() and ((want["both"] > 0) & (want["both"] < want["fire"])).any()
+    assert (want["fire"][-1] != want["fire"][-2]).any()                 # the last plane is not a copy of the one below it
+    lg, gt, th = d["logits"][:n], d["gt"][:n], d["th"][t_idx]
+    got = _heat_device(ctx, lg, gt, th) if device else cal.heat(ctx, lg, gt, th)
+    _same(got, want)
+
+
+def test_slices_clamped_to_their_counter_width(ctx):
+    """One macroblock, num_cu * 32768 + 5 samples: one slice per CU would be longer than the 32768 samples a bin's two 16-bit
+    halves are sized for, so the slice count is raised.  The first three quarters are one logit above every threshold with the
+    label set: whole slices land in ONE bin, in both halves of the packed word.  The reference is three counts per threshold."""
+    n = ctx.info()["num_cu"] * 32768 + 5
+    rng = np.random.default_rng(41)
+    lg = rng.standard_normal(n).astype(np.float32)
+    gt = (rng.random(n) < 0.3).astype(np.uint8) * 255
+    const = 3 * n // 4
+    th = np.array([-0.5, 0.0, 0.7], np.float32)
+    lg[:const], gt[:const] = 5.0, 1
+    fire = np.array([int((lg > t).sum()) for t in th])
+    both = np.array([int(((lg > t) & (gt != 0)).sum()) for t in th])
+    assert fire[2] > const and (np.diff(fire) < 0).all() and (both < fire).all() and both[2] > const
+    got = _heat_device(ctx, lg.reshape(n, 1, 1), gt.reshape(n, 1, 1), th)
+    assert got["samples"] == n
+    assert got["fire"].reshape(-1).tolist() == fire.tolist() and got["both"].reshape(-1).tolist() == both.tolist()
+    assert got["gt"].reshape(-1).tolist() == [int((gt != 0).sum())]
+
+
+@pytest.mark.parametrize("per_piece", [10, 1])
+@pytest.mark.parametrize("h,w", [(5, 7), (45, 80)])
+def test_host_samples_staged_in_pieces(ctx, cases, h, w, per_piece):
+    """The developer's staging budget: 37 host samples go up in pieces of 10, 10, 10 and 7, and -- with a budget below one
+    sample -- one at a time.  The tables are the unstaged call's."""
+    n = 37
+    d, ref = cases(h, w, n)
+    want = _select(ref, T_SEL[3])
+    lg, gt, th = d["logits"][:n], d["gt"][:n], d["th"][T_SEL[3]]
+    sample = h * w * 5                                                   # four bytes of logit and a label byte per macroblock
+    budget = 10 * sample + sample // 2 if per_piece == 10 else sample - 1
+    assert budget // sample == (10 if per_piece == 10 else 0) and n % 10 == 7
+    try:
+        cal.heat_set_stage(ctx, budget)
+        got = cal.heat(ctx, lg, gt, th)
+    finally:
+        cal.heat_set_stage(ctx, 0)
+    _same(got, want)
+    _same(cal.heat(ctx, lg, gt, th), want)                               # and with the default restored
 
 
 def test_specials(ctx):

@@ -153,6 +153,30 @@ def test_a_slice_longer_than_255_samples_is_exact(ctx, cases, h, w):
             d.free()
 
 
+def test_an_add_longer_than_one_launch(ctx, cases):
+    """A stand-alone add takes 16384 samples per launch: 16384 + 5 samples are two launches from device memory, and from host
+    memory two staged pieces, the second from the arrays' offsets (model ids included)."""
+    h, w, n = 5, 7, 16384 + 5
+    m300, c300, b300 = cases(h, w, N_MAX, "one")[:3]
+    pick = np.random.default_rng(3).integers(0, N_MAX, n)
+    mask, counts, boxes = np.ascontiguousarray(m300[pick]), np.ascontiguousarray(c300[pick]), np.ascontiguousarray(b300[pick])
+    dev = _OnDevice(ctx, mask, counts, boxes)
+    try:
+        for kind in ("one", "robin3"):
+            ids, n_models = _ids(kind, n)
+            want = monitor_ref(mask, counts, boxes, ids, MAX_BOXES, n_models)
+            tail = monitor_ref(mask[16384:], counts[16384:], boxes[16384:], None if ids is None else ids[16384:], MAX_BOXES, n_models)
+            assert tail["fire"].any() and tail["area_hist"].any()          # the second launch's share is visible in the tables
+            mon.begin(ctx, h, w, n_models, MAX_BOXES)
+            mon.add_device(ctx, *dev.at(0), n, ids)
+            same(mon.read(ctx, reset=True), want)
+            mon.add(ctx, mask, counts, boxes, ids)
+            same(mon.read(ctx, reset=True), want)
+            mon.end(ctx)
+    finally:
+        dev.free()
+
+
 # ------------------------------------------------------------------------------------------------------------------ 2. additivity, state
 def test_additivity_and_state(ctx, cases):
     h, w, n = 17, 16, 257

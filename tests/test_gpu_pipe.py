@@ -5,6 +5,7 @@ import pytest
 
 from cova_amd import _lib as L
 from cova_amd import synth
+from cova_amd import weights as W
 from cova_amd.elements import BlobNetInfer, FilterPipe
 
 pytestmark = pytest.mark.gpu
@@ -231,3 +232,87 @@ def test_blocking_wait_only_with_idle_slots_and_device_pci_address(ctx, weights_
     assert lib.covahip_device_pci_bus_id(0, buf, 4) != 0 and lib.covahip_device_pci_bus_id(9999, buf, len(buf)) != 0
     if os.path.isdir("/sys/bus/pci/devices"):
         assert os.path.exists(os.path.join("/sys/bus/pci/devices", addr))
+
+
+# ---- the edges of the offset scan and the growth of the speculative copy (last in the module: the fixture's pipe closes right after)
+def _submit_and_compare(pipe, net, frames, index, cc, max_boxes):
+    """One batch through the pipe against the synchronous call on the same batch: counts, offsets (offsets[batch] included) and
+    every frame's boxes.  -> the synchronous counts."""
+    b = index.shape[0]
+    boxes, counts, _, _ = net.filter_frames(frames, index, cc, max_boxes=max_boxes)
+    slot, pf, pi = pipe.acquire()
+    pf[:frames.shape[0]] = frames
+    pi[:b] = index
+    pipe.submit(slot, frames.shape[0], b, cc)
+    c, o, bx, _m = pipe.collect(slot)
+    kept = np.minimum(counts, max_boxes)
+    np.testing.assert_array_equal(c, counts)
+    np.testing.assert_array_equal(o, np.concatenate([[0], np.cumsum(kept)]))
+    assert o.shape == (b + 1,) and bx.shape == (int(kept.sum()),)
+    # frame i's boxes are bx[o[i]:o[i + 1]]: the first min(count, max_boxes) slots of every frame's row, in frame order
+    want = boxes[np.arange(max_boxes)[None, :] < kept[:, None]]
+    assert bx.tobytes() == want.tobytes()
+    return counts
+
+
+@pytest.fixture(scope="module")
+def scan_edges(ctx):
+    """One model at 16x24, one pipe and one set of carrier frames for all the batch sizes; max_boxes = 2."""
+    h, w, b_max, max_boxes = 16, 24, 2049, 2
+    net = BlobNetInfer(ctx, W.blob_like(), h, w, max_batch=b_max)
+    frames, index = synth.carrier_batch(b_max, h, w, seed=4000, streams=256)   # short streams: the objects are still in view
+    pipe = FilterPipe(net, max_batch=b_max, max_frames=frames.shape[0], max_boxes=max_boxes, n_slots=2)
+    try:
+        yield net, pipe, frames, index, max_boxes
+    finally:
+        pipe.close()
+
+
+@pytest.mark.parametrize("b", [1024, 1025, 2048, 2049])
+def test_the_edges_of_the_offset_scan(ctx, scan_edges, b):
+    """1024 | 1025: either side of the choice between the pack kernel summing the counts itself and the scan kernel; 2048 | 2049: a
+    last round of the scan that is full (its thread 1023 holds a real frame) and one that holds a single frame.  The batches are
+    prefixes of one set of stacks.  max_boxes = 2 cuts frames short beside frames that have nothing, so the offsets follow
+    min(count, max_boxes) and stay put across empty frames."""
+    net, pipe, frames, index, max_boxes = scan_edges
+    for _ in range(2):                                    # twice: the slots' buffers are reused
+        counts = _submit_and_compare(pipe, net, frames, index[:b], 1, max_boxes)
+    kept = int(np.minimum(counts, max_boxes).sum())
+    print(f"batch {b}: {int((counts == 0).sum())} empty, {int((counts > max_boxes).sum())} truncated, {kept} boxes kept")
+    assert (counts == 0).sum() >= 16 and (counts > max_boxes).sum() >= 8
+    assert kept > b                                       # more than a box per frame: the offsets are not trivial
+    assert counts[b - 1] > 0                              # the last frame, which decides offsets[batch], has boxes
+
+
+def test_speculative_copy_grows_and_later_batches_stay_exact(ctx, weights_flat):
+    """A collect that found more boxes than the pipelined copy carried fetches the rest and enlarges the copy for later batches.
+    The two submits after it -- one with more boxes still, one with far fewer -- are exact as well."""
+    h, w, b, max_boxes = 68, 120, 16, 2048
+    net = BlobNetInfer(ctx, weights_flat, h, w, max_batch=b)
+    frames, index = synth.carrier_batch(b, h, w, seed=77, streams=2)
+    pipe = FilterPipe(net, max_batch=b, max_frames=frames.shape[0], max_boxes=max_boxes, n_slots=2)
+    try:
+        totals = []
+        for batch, cc in ((8, 1), (16, 1), (16, 40), (16, 1)):
+            counts = _submit_and_compare(pipe, net, frames, index[:batch], cc, max_boxes)
+            totals.append(int(counts.sum()))
+        print("boxes per submit:", totals)
+        spec0 = max(1024, 16 * b)                     # what the first pipelined copy carries (pipe.hip, covahip_pipe_create)
+        assert totals[0] > spec0                      # the first collect had to fetch
+        assert totals[1] > totals[0] + totals[0] // 4 # more than the enlarged copy: fetched again
+        assert totals[2] < totals[0] // 8             # far fewer
+    finally:
+        pipe.close()
+
+
+def test_a_pipe_that_outlives_its_context_is_not_destroyed(ctx, weights_flat):
+    """A pipe lost to an exception is collected when the interpreter gets to it, possibly after its Context was closed:
+    close() must then leave the handle alone (covahip_pipe_destroy synchronises the ctx the pipe was created on)."""
+    from cova_amd.elements import Context
+    own = Context(0)
+    net = BlobNetInfer(own, weights_flat, 45, 80, max_batch=4)
+    pipe = FilterPipe(net, max_batch=4, max_frames=16, max_boxes=16, n_slots=1)
+    own.close()
+    pipe.close()
+    assert pipe._h is None
+    pipe.close()                                       # and again: nothing left to do

@@ -453,3 +453,75 @@ def test_errors_leave_the_settings_alone(ctx, models):
     post = L.BlobNetPost(0.5, None)
     assert lib.covahip_blobnet_set_post(ctx.handle, 0, C.byref(post)) == 4
     assert lib.covahip_blobnet_get_post(ctx.handle, 0, C.byref(t), None, None) == 4
+
+
+# ------------------------------------------------------------------------------------------------------------------ 7. the caller's mask pointer
+PAD, FILL = 64, 0xAA
+MASK_CASES = ["frames_68x120", "frames_45x80_post", "frames_68x120_two_models_post", "stack_45x80", "stack_68x120_post", "infer_20x28"]
+
+
+@pytest.mark.parametrize("case", MASK_CASES)
+def test_mask_pointer_of_any_alignment(ctx, models, case):
+    """d_mask 0, 1, 2 and 3 bytes into a buffer of 0xAA.  Off a 4-byte boundary the row form of the fused tail (whose ballots leave
+    as words) is turned away for the band form, and the band form and the unfused last block store the mask byte by byte.  Mask,
+    counts and boxes are the aligned call's, and no byte outside [d_mask, d_mask + batch * h * w) is written."""
+    kind, geom = case.split("_")[:2]
+    h, w = (int(v) for v in geom.split("x"))
+    b = 5
+    rng = np.random.default_rng(len(case) + h)
+    frames, table = _frames(rng, 4 * b, h, w), _own_frames_table(b)
+    src = frames if kind == "frames" else _stack_of(frames, table)
+    two = "two_models" in case
+    ids = np.array([0, 1, 1, 0, 1], np.uint8) if two else None
+    net = BlobNetInfer(ctx, [models[1], models[3]] if two else models[1], h, w, max_batch=b)
+    if "post" in case:
+        net.set_post(1 if two else 0, logit_thresh=0.25, keep=_keeps(h, w, 6)["stripes3"])
+    nbytes = b * h * w
+    d_src, d_boxes, d_counts = ctx.malloc(src.nbytes), ctx.malloc(b * MAXB * L.BOX_DTYPE.itemsize), ctx.malloc(b * 4)
+    d_buf = ctx.malloc(PAD + nbytes + PAD)
+    runs = []
+    try:
+        assert d_buf % 16 == 0
+        ctx.h2d(d_src, src)
+        for shift in (0, 1, 2, 3):
+            ctx.h2d(d_buf, np.full(PAD + nbytes + PAD, FILL, np.uint8))
+            ctx.h2d(d_boxes, np.zeros(b * MAXB, L.BOX_DTYPE))
+            ctx.h2d(d_counts, np.full(b, -1, np.int32))
+            d_mask = d_buf + PAD + shift
+            if kind == "frames":
+                net.filter_frames_device(d_src, 4 * b, table, b, 1, d_boxes, d_counts, MAXB, d_mask=d_mask, model_ids=ids)
+            elif kind == "stack":
+                net.filter_device(d_src, b, 1, d_boxes, d_counts, MAXB, d_mask=d_mask, model_ids=ids)
+            else:
+                net.infer_device(d_src, b, None, d_mask, model_ids=ids)
+            ctx.sync()
+            form = net.tail_form()
+            buf, boxes, counts = np.empty(PAD + nbytes + PAD, np.uint8), np.empty((b, MAXB), L.BOX_DTYPE), np.empty(b, np.int32)
+            ctx.d2h(buf, d_buf)
+            ctx.d2h(boxes, d_boxes)
+            ctx.d2h(counts, d_counts)
+            runs.append((shift, form, buf, boxes, counts))
+    finally:
+        ctx.sync()
+        for d in (d_src, d_boxes, d_counts, d_buf):
+            ctx.free(d)
+    _, form0, buf0, boxes0, counts0 = runs[0]
+    mask0 = buf0[PAD:PAD + nbytes].reshape(b, h, w)
+    assert set(np.unique(mask0)) == {0, 1}                              # both classes, and every byte of the region was written
+    if kind == "infer":
+        assert form0 == ALONE
+    else:
+        assert form0 == ROWS and counts0.min() >= 0 and counts0.sum() > 0
+        _eq_boxes(boxes0, counts0, mask0)
+    for shift, form, buf, boxes, counts in runs:
+        lo = PAD + shift
+        assert (buf[:lo] == FILL).all() and (buf[lo + nbytes:] == FILL).all(), (shift, "a store outside the caller's mask")
+        assert buf[lo:lo + nbytes].tobytes() == mask0.tobytes(), shift
+        if kind == "infer":
+            assert form == ALONE
+            continue
+        assert form == (ROWS if shift == 0 else BANDS + 3), (shift, form)   # dec3cc_mfma<WV = 1, PART = 1> where rows are turned away
+        assert np.array_equal(counts, counts0), shift
+        for i in range(b):
+            n = min(int(counts0[i]), MAXB)
+            assert boxes[i, :n].tobytes() == boxes0[i, :n].tobytes(), (shift, i)

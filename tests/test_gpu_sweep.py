@@ -17,6 +17,7 @@ from tests.sweep_ref import smooth_field, sweep_ref
 pytestmark = pytest.mark.gpu
 
 GRIDS = [(16, 16), (9, 20), (45, 80), (67, 120)]          # 9 x 20: width no multiple of 8; 45 x 80: odd height
+ODD_GRIDS = [(5, 7), (17, 33)]                            # h * w = 35, 561: no multiple of 4, one macroblock per work item
 AREAS16 = [1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20, 24, 30, 40, 60, 100]
 N_ALL, N_FULL = 37, 5                                     # samples at three thresholds / at all 64
 T3 = [10, 32, 50]                                         # the three thresholds, as indices into the 64
@@ -54,7 +55,9 @@ def cases():
 
     def get(h, w):
         if (h, w) not in made:
-            rng = np.random.default_rng(1000 * h + w)
+            # (5 x 7's own seed: 35 macroblocks are few, and the first sample must hold a labelled object that is hit and a prediction
+            # that is not, which test_samples_and_chunks asserts on the reference at n = 1)
+            rng = np.random.default_rng(5008 if (h, w) == (5, 7) else 1000 * h + w)
             k = 3 if h * w <= 256 else 7
             logits = smooth_field(rng, N_ALL, h, w, k)
             gt = (smooth_field(rng, N_ALL, h, w, k) > 1.0).astype(np.uint8) * 255
@@ -91,7 +94,7 @@ def _on_device(ctx, logits, gt, fn):
 # ------------------------------------------------------------------------------------------------------------------ exact agreement
 @pytest.mark.parametrize("chunk", [0, 4])
 @pytest.mark.parametrize("n", [1, 5, N_ALL])
-@pytest.mark.parametrize("h,w", GRIDS)
+@pytest.mark.parametrize("h,w", GRIDS + ODD_GRIDS)
 def test_samples_and_chunks(ctx, cases, h, w, n, chunk):
     c = cases(h, w)
     want = _sum(c["ref3"][:n])
@@ -115,7 +118,7 @@ def test_thresholds_and_areas(ctx, cases, h, w, n_thresh, n_area):
 
 @pytest.mark.parametrize("device", [False, True])
 @pytest.mark.parametrize("with_keep", [False, True])
-@pytest.mark.parametrize("h,w", GRIDS)
+@pytest.mark.parametrize("h,w", GRIDS + ODD_GRIDS)
 def test_keep_map_and_mem_kind(ctx, cases, h, w, with_keep, device):
     c = cases(h, w)
     keep = c["keep"] if with_keep else None
@@ -128,6 +131,28 @@ def test_keep_map_and_mem_kind(ctx, cases, h, w, with_keep, device):
         got = _on_device(ctx, lg, gt, lambda d_l, d_g: cal.sweep_device(ctx, d_l, d_g, N_FULL, h, w, c["th"], AREAS16, keep=keep))
     else:
         got = cal.sweep(ctx, lg, gt, c["th"], AREAS16, keep=keep)
+    _same(got, want)
+
+
+@pytest.mark.parametrize("chunk", [0, 2])
+@pytest.mark.parametrize("which", ["logits+4", "labels+1"])
+@pytest.mark.parametrize("h,w", [(16, 16), (45, 80)])
+def test_offset_device_pointers(ctx, cases, h, w, which, chunk):
+    """h * w is a multiple of 4 here, so only the caller's pointers decide: logits that are float-aligned but not 16-byte
+    aligned, or labels on an odd address, take the one-macroblock kernel and must give the aligned call's tables."""
+    c = cases(h, w)
+    want = _sum(c["ref64k"])
+    lg, gt = c["logits"][:N_FULL], c["gt"][:N_FULL]
+    off_l, off_g = (4, 0) if which == "logits+4" else (0, 1)
+    d_l, d_g = ctx.malloc(lg.nbytes + 16), ctx.malloc(gt.nbytes + 16)
+    try:
+        assert d_l % 16 == 0 and d_g % 16 == 0             # the allocation is aligned, so the offset is what the kernel sees
+        ctx.h2d(d_l + off_l, lg)
+        ctx.h2d(d_g + off_g, gt)
+        got = cal.sweep_device(ctx, d_l + off_l, d_g + off_g, N_FULL, h, w, c["th"], AREAS16, keep=c["keep"], chunk=chunk)
+    finally:
+        ctx.free(d_l)
+        ctx.free(d_g)
     _same(got, want)
 
 

@@ -125,6 +125,127 @@ def test_gather_against_numpy(ctx, h, w):
         d.close()
 
 
+# ------------------------------------------------------------------------------------------------ 1b. the host's choices
+def _every_frame_mirrored(n_frames):
+    """Every frame in slot 0 and as the label, under each of the four mirror settings; the other slots walk on."""
+    return _samples([([f, (f + 1) % n_frames, (f + 2) % n_frames, (f + 3) % n_frames], f, m) for f in range(n_frames) for m in range(4)])
+
+
+@pytest.mark.parametrize("shift", [1, 2, 3])
+@pytest.mark.parametrize("h,w", [(16, 16), (17, 33)])
+def test_append_device_from_an_unaligned_source(ctx, h, w, shift):
+    """A device source off a 4-byte boundary is packed byte by byte instead of a record at a time."""
+    f = 6
+    frames, gt = _frames(20 + shift, f, h, w)
+    assert frames[..., :3].min() == 0 and frames[..., :3].max() == 255 and len(np.unique(frames[..., 3])) > 200
+    d = T.TrainData(ctx, h, w, f)
+    d_fr, d_gt = ctx.malloc(frames.nbytes + 4), ctx.malloc(gt.nbytes + 4)
+    try:
+        assert d_fr % 4 == 0
+        ctx.h2d(d_fr + shift, frames)
+        ctx.h2d(d_gt + shift, gt)
+        assert d.append_device(d_fr + shift, d_gt + shift, f) == (0, f)
+        samples = _every_frame_mirrored(f)
+        want_stack, want_gt = _batch(frames, gt, samples, packed=True)
+        stack, lab = d.gather(samples)
+        assert (stack == want_stack).all() and (lab == want_gt).all()
+    finally:
+        ctx.free(d_fr)
+        ctx.free(d_gt)
+        d.close()
+
+
+def test_append_device_past_one_round_of_the_pack_grid(ctx):
+    """One device append of 2^18 + 3 frames of 16x16: the pack kernel's grid stops at 2^18 workgroups of 256 macroblocks, so the
+    macroblocks from index 2^26 on -- the last three frames -- are packed in the second round of its loop."""
+    h = w = 16
+    block_n = 1024                                                         # 1 MiB of frames
+    total = (1 << 18) + 3
+    assert total * h * w > (1 << 18) * 256 and (1 << 26) == (1 << 18) * h * w
+    rng = np.random.default_rng(12)
+    block = rng.integers(0, 256, (block_n, h, w, 4), dtype=np.uint8)
+    block[::2, ..., :3] = rng.integers(0, 9, (block_n // 2, h, w, 3), dtype=np.uint8)    # every other frame around the clip at 6
+    block_gt = rng.integers(0, 256, (block_n, h, w), dtype=np.uint8)
+    d = T.TrainData(ctx, h, w, total)
+    d_fr, d_gt = ctx.malloc(total * h * w * 4), ctx.malloc(total * h * w)
+    try:
+        for at in range(0, total, block_n):
+            m = min(block_n, total - at)
+            ctx.h2d(d_fr + at * h * w * 4, block[:m])
+            ctx.h2d(d_gt + at * h * w, block_gt[:m])
+        assert d.append_device(d_fr, d_gt, total) == (0, total) and d.frames == total
+        edge = 1 << 18                                                     # the frame whose first macroblock is index 2^26
+        samples = _samples([([0, 1, 2, 3], 0, 0), ([4, 5, 6, 7], 4, 3),
+                            ([total - 1, total - 2, total - 3, total - 4], total - 1, 1),
+                            ([edge - 1, edge, edge + 1, edge + 2], edge, 2), ([edge, edge - 1, edge - 2, edge - 3], edge - 1, 0),
+                            ([edge - 1, edge - 1, edge, edge], total - 2, 3)])
+        stack, lab = d.gather(samples)
+        for b, smp in enumerate(samples):
+            sx = slice(None, None, -1) if smp["flags"] & 1 else slice(None)
+            sy = slice(None, None, -1) if smp["flags"] & 2 else slice(None)
+            for t in range(4):
+                want = np.minimum(block[int(smp["frame"][t]) % block_n][sy, sx], 6)
+                want[..., 3] = 0
+                assert (stack[b, t * h:(t + 1) * h] == want).all(), (b, t)
+            assert (lab[b] == block_gt[int(smp["label"]) % block_n][sy, sx]).all(), b
+    finally:
+        ctx.free(d_fr)
+        ctx.free(d_gt)
+        d.close()
+
+
+def test_host_append_and_gather_in_staging_rounds(ctx):
+    """The developer's staging budget: a host append whose rounds end in the middle of a frame, the last one ragged, and a
+    host-bound gather of 23 samples through a staging that holds 5.  Both equal numpy, as with the default budget."""
+    h, w, f = 17, 33, 7
+    frames, gt = _frames(13, f, h, w)
+    hw = h * w
+    d = T.TrainData(ctx, h, w, 2 * f)
+    try:
+        d.set_stage(2 * 1000)                                              # 1000 macroblocks a round: 3927 = 3 * 1000 + 927
+        assert 1000 % hw != 0 and (f * hw) % 1000 not in (0, hw)
+        assert d.append(frames, gt) == (0, f)
+        d.set_stage(0)
+        assert d.append(frames[::-1], gt[::-1]) == (f, 2 * f)              # the default budget: one round
+        both, both_gt = np.concatenate([frames, frames[::-1]]), np.concatenate([gt, gt[::-1]])
+        samples = np.concatenate([_every_frame_mirrored(2 * f)[::3], _mixed(2 * f, 4, 5)])
+        assert len(samples) == 23
+        want_stack, want_gt = _batch(both, both_gt, samples, packed=True)
+        per = 17 * hw                                                      # a sample's staging: four slices of four bytes and a label byte
+        for budget in (5 * per + per // 2, per - 1, 0):                    # 5 + 5 + 5 + 5 + 3 samples; one at a time; the default
+            d.set_stage(budget)
+            stack, lab = d.gather(samples)
+            assert (stack == want_stack).all() and (lab == want_gt).all(), budget
+    finally:
+        d.close()
+
+
+def test_device_gather_past_one_grid(ctx):
+    """65535 + 9 samples to device memory: a launch's grid holds 65535, so the gather runs twice, the second time from the
+    table's and the outputs' offsets.  285 MB of output, checked where the launches meet, at both ends and on every 4099th."""
+    h = w = 16
+    hw = h * w
+    frames, gt = _frames(14, 15, h, w)
+    n = 65535 + 9
+    samples = np.tile(_mixed(15, 997, 15), n // 997 + 1)[:n]               # 997: a prime period, so the meeting point is mid-pattern
+    assert {int(f) for f in samples["flags"]} == {0, 1, 2, 3}
+    d = _data(ctx, frames, gt)
+    o_stack, o_gt = ctx.malloc(n * 16 * hw), ctx.malloc(n * hw)
+    try:
+        d.gather_device(samples, o_stack, o_gt)
+        runs = [(0, 4), (65535 - 8, 65535 + 8), (n - 4, n)] + [(i, i + 1) for i in range(4099, n, 4099)]
+        for a, b in runs:
+            want_stack, want_gt = _batch(frames, gt, samples[a:b], packed=True)
+            stack, lab = np.full_like(want_stack, 0xAA), np.full_like(want_gt, 0xAA)
+            ctx.d2h(stack, o_stack + a * 16 * hw)
+            ctx.d2h(lab, o_gt + a * hw)
+            assert (stack == want_stack).all() and (lab == want_gt).all(), (a, b)
+    finally:
+        ctx.free(o_stack)
+        ctx.free(o_gt)
+        d.close()
+
+
 # ------------------------------------------------------------------------------------------------ 2. Contract D, step
 @pytest.mark.parametrize("h,w,batch", [(17, 33, 4), (16, 16, 3)])
 def test_contract_d_step(ctx, h, w, batch):
