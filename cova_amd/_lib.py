@@ -122,6 +122,12 @@ class MogCfg(C.Structure):
                 ("var_threshold", C.c_float)]
 
 
+class MogYuv(C.Structure):
+    """covahip_mog_yuv: an NV12 / I420 surface layout (72 bytes)."""
+    _fields_ = [("format", C.c_int32), ("range", C.c_int32), ("offset", C.c_int64 * 3), ("pitch", C.c_int64 * 3),
+                ("frame_stride", C.c_int64), ("stream_stride", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/covahip.h declares
 _P = C.c_void_p
 _SZ = C.c_size_t
@@ -276,6 +282,8 @@ PROTOTYPES = {
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),
     "covahip_mog_dims": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "covahip_mog_apply": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_mog_yuv_tight": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MogYuv)]),
+    "covahip_mog_apply_yuv": (C.c_int, [_P, C.POINTER(MogYuv), _P, C.c_int, _P, _P, C.c_int]),
     "covahip_mog_reset": (C.c_int, [_P, C.c_int]),
     "covahip_mog_destroy": (None, [_P]),
 }

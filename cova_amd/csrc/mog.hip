@@ -3,7 +3,8 @@
 // include/covahip.h ("MoG labels"); tests/mog_ref.py is its numpy float32 restatement and the kernels match it bit for bit.
 // This file has the C-ABI and the kernels of the reference grid (every source resized to 640x360, 45x80 labels); the
 // macroblock grid's kernels (half-resolution working image) are mog_grid.hip and, for 1440p and 4K sources, mog_band.hip (the
-// post kernel in row bands); all three instantiate the device code of mog_dev.h.
+// post kernel in row bands); all three instantiate the device code of mog_dev.h.  covahip_mog_apply_yuv (NV12 / I420 surfaces at
+// the caller's pitch, offsets and strides) is checked and staged here and runs the update kernels of mog_yuv.hip.
 //
 //   k_mog_update  one lane per working-size pixel and stream.  The five modes (weight, variance, mean) are read once per call
 //                 into registers, every frame of the call is applied to them, and they are written back once.  The source is
@@ -175,6 +176,20 @@ int launch_update(covahip_mog *m, const uint8_t *d_frames, int f0, int nf, int S
     return COVAHIP_OK;
 }
 
+// A checked covahip_mog_yuv: the surface as the kernels of mog_yuv.hip take it, and the bytes lo .. lo + ext of a frame that
+// hold its planes' rows (what a call from host memory stages per frame and stream).
+struct YuvPlan {
+    int format = 0;
+    covahip_mog_yuv_src src{};
+    size_t lo = 0, ext = 0;
+};
+
+int launch_update_yuv(covahip_mog *m, int format, const uint8_t *d_frames, const covahip_mog_yuv_src &src, int f0, int nf, int S,
+                      const float2 *d_par, const int32_t *d_nv) {
+    return covahip_mog_yuv_update(m->ctx, format, m->kind, m->mw, d_frames, src, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold,
+                                  static_cast<unsigned long long *>(m->bits));
+}
+
 // the post launch on the call's raw planes (m->bits): filled planes and labels of FS (frame, stream) pairs
 int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, size_t FS) {
     covahip_ctx *ctx = m->ctx;
@@ -258,7 +273,13 @@ int covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int gr
     return COVAHIP_OK;
 }
 
-int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const int32_t *n_valid, uint8_t *labels, int mem_kind) {
+}  // extern "C"
+
+namespace {
+
+// One call of either entry: frames are BGR24 [n_frames][S][src] (yuv == nullptr) or the surfaces `yuv` describes from `frames`.
+int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int n_frames, const int32_t *n_valid, uint8_t *labels,
+                 int mem_kind) {
     if (!m || !frames || !labels || n_frames < 1) return COVAHIP_ERR_INVALID_ARG;
     if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
     const int S = m->cfg.n_streams;
@@ -299,7 +320,40 @@ int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const
     const int32_t *d_nv = reinterpret_cast<const int32_t *>(d_par + FS);
     uint8_t *d_labels = labels;
     if (mem_kind == COVAHIP_MEM_DEVICE) {
-        if (int rc = launch_update(m, frames, 0, n_frames, S, d_par, d_nv)) return rc;
+        if (int rc = yuv ? launch_update_yuv(m, yuv->format, frames, yuv->src, 0, n_frames, S, d_par, d_nv)
+                         : launch_update(m, frames, 0, n_frames, S, d_par, d_nv))
+            return rc;
+    } else if (yuv) {
+        // host surfaces: per (frame, stream) the extent lo .. lo + ext of the frame is staged, densely and frame-major, so the
+        // kernel sees the caller's plane offsets less lo and the caller's pitches; nothing outside an extent is read
+        const size_t slot = (yuv->ext + 15) & ~(size_t)15, step = (size_t)S * slot;
+        const bool dense = (size_t)yuv->src.stream_stride == yuv->ext && (size_t)yuv->src.frame_stride == (size_t)S * yuv->ext;
+        const size_t dstep = dense ? (size_t)S * yuv->ext : step;
+        const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, m->stage_budget / dstep));
+        if (int rc = covahip_ensure_buffer(ctx, &m->d_frames, &m->frames_bytes, (size_t)per * dstep)) return rc;
+        covahip_mog_yuv_src st = yuv->src;
+        for (int p = 0; p < 3; p++) st.off[p] -= (long long)yuv->lo;
+        if (!dense) st.stream_stride = (long long)slot, st.frame_stride = (long long)step;
+        uint8_t *d = static_cast<uint8_t *>(m->d_frames);
+        for (int f0 = 0; f0 < n_frames; f0 += per) {
+            const int nf = std::min(per, n_frames - f0);
+            const uint8_t *h0 = frames + yuv->lo + (long long)f0 * yuv->src.frame_stride;
+            if (dense) {
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d, h0, (size_t)nf * dstep, hipMemcpyHostToDevice, ctx->stream));
+            } else {
+                for (int f = 0; f < nf; f++)
+                    for (int s = 0; s < S; s++) {
+                        if (f0 + f >= nv[s]) continue;     // frames past n_valid are not read at all
+                        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d + (size_t)f * step + (size_t)s * slot,
+                                                              h0 + (long long)f * yuv->src.frame_stride + (long long)s * yuv->src.stream_stride,
+                                                              yuv->ext, hipMemcpyHostToDevice, ctx->stream));
+                    }
+            }
+            if (int rc = launch_update_yuv(m, yuv->format, d, st, f0, nf, S, d_par, d_nv)) return rc;
+        }
+        if (int rc = covahip_ensure_buffer(ctx, &m->d_labels, &m->labels_bytes, FS * NLAB)) return rc;
+        d_labels = static_cast<uint8_t *>(m->d_labels);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d_labels, labels, FS * NLAB, hipMemcpyHostToDevice, ctx->stream));
     } else {
         // host frames: staged in launches of as many frames as fit the budget (the model is read and written once per launch)
         const size_t step = (size_t)S * m->src_bytes;
@@ -323,6 +377,71 @@ int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const
     for (int s = 0; s < S; s++) m->n[s] += nv[s];
     m->last_frames = n_frames;
     return COVAHIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const int32_t *n_valid, uint8_t *labels, int mem_kind) {
+    return apply_frames(m, frames, nullptr, n_frames, n_valid, labels, mem_kind);
+}
+
+int covahip_mog_yuv_tight(const covahip_mog *m, int format, int range, covahip_mog_yuv *out) {
+    if (!m || !out) return COVAHIP_ERR_INVALID_ARG;
+    if (format != COVAHIP_MOG_FMT_NV12 && format != COVAHIP_MOG_FMT_I420) return COVAHIP_ERR_INVALID_ARG;
+    if (range != COVAHIP_MOG_RANGE_LIMITED && range != COVAHIP_MOG_RANGE_FULL) return COVAHIP_ERR_INVALID_ARG;
+    const int64_t w = m->cfg.src_w, h = m->cfg.src_h;
+    std::memset(out, 0, sizeof(*out));
+    out->format = format;
+    out->range = range;
+    out->offset[1] = w * h;
+    out->pitch[0] = w;
+    if (format == COVAHIP_MOG_FMT_NV12) {
+        out->pitch[1] = w;
+    } else {
+        out->offset[2] = w * h + w * h / 4;
+        out->pitch[1] = out->pitch[2] = w / 2;
+    }
+    out->stream_stride = w * h * 3 / 2;
+    out->frame_stride = out->stream_stride * m->cfg.n_streams;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_apply_yuv(covahip_mog *m, const covahip_mog_yuv *lay, const uint8_t *base, int n_frames, const int32_t *n_valid,
+                          uint8_t *labels, int mem_kind) {
+    if (!m || !lay || !base || !labels) return COVAHIP_ERR_INVALID_ARG;
+    const bool nv12 = lay->format == COVAHIP_MOG_FMT_NV12;
+    if (!nv12 && lay->format != COVAHIP_MOG_FMT_I420) return COVAHIP_ERR_INVALID_ARG;
+    if (lay->range != COVAHIP_MOG_RANGE_LIMITED && lay->range != COVAHIP_MOG_RANGE_FULL) return COVAHIP_ERR_INVALID_ARG;
+    const int64_t w = m->cfg.src_w, h = m->cfg.src_h;
+    const int planes = nv12 ? 2 : 3;
+    const int64_t row_bytes[3] = {w, nv12 ? w : w / 2, w / 2}, rows[3] = {h, h / 2, h / 2};
+    if ((reinterpret_cast<uintptr_t>(base) & 1) || lay->frame_stride < 0 || lay->stream_stride < 0 ||
+        ((lay->frame_stride | lay->stream_stride) & 1))
+        return COVAHIP_ERR_INVALID_ARG;
+    YuvPlan plan{};
+    int64_t lo = INT64_MAX, hi = 0;
+    for (int p = 0; p < planes; p++) {
+        if (lay->offset[p] < 0 || lay->pitch[p] < row_bytes[p] || ((lay->offset[p] | lay->pitch[p]) & 1)) return COVAHIP_ERR_INVALID_ARG;
+        lo = std::min(lo, lay->offset[p]);
+        hi = std::max(hi, lay->offset[p] + (rows[p] - 1) * lay->pitch[p] + row_bytes[p]);
+        plan.src.off[p] = lay->offset[p];
+        plan.src.pitch[p] = lay->pitch[p];
+    }
+    plan.format = lay->format;
+    plan.lo = (size_t)lo;
+    plan.ext = (size_t)(hi - lo);
+    plan.src.frame_stride = lay->frame_stride;
+    plan.src.stream_stride = lay->stream_stride;
+    const bool full = lay->range == COVAHIP_MOG_RANGE_FULL;
+    plan.src.ysub = full ? 0 : 16;
+    plan.src.ymul = full ? 1 << 20 : 1220542;
+    plan.src.bu = full ? 1858077 : 2116026;
+    plan.src.gv = full ? 748826 : 852492;
+    plan.src.gu = full ? 360853 : 409993;
+    plan.src.rv = full ? 1470104 : 1673527;
+    return apply_frames(m, base, &plan, n_frames, n_valid, labels, mem_kind);
 }
 
 int covahip_mog_reset(covahip_mog *m, int stream) {

@@ -2,7 +2,8 @@
 // macroblock grid: half-resolution working frames) and mog_band.hip (the macroblock grid of 1440p and 4K sources, whose planes
 // are worked on in row bands): the MOG2 pixel update, the update kernel's body, and the morphology and
 // hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
-// include/covahip.h ("MoG labels").
+// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces; they
+// run update_body_strided, the body's sibling for frames at strides of the caller's.
 //
 // No contraction in this code: every product and sum is rounded on its own, as the x86 builds of OpenCV compute it (both
 // translation units are also built with -ffp-contract=off).  The f32 divisions go through double: the f64 quotient is
@@ -182,6 +183,64 @@ __device__ __forceinline__ void update_body(Load load, const uint8_t *__restrict
         if (f + 1 < fend) nxt = load(fr + (size_t)(f + 1) * fstride, x, y);   // next frame's pixel in flight
         const float2 pr = par[(size_t)(f0 + f) * S + s];
         const bool fg = mog2_pixel(W, V, M, nm, cur, pr.x, pr.y, Tb);
+        const unsigned long long word = __ballot(fg);
+        if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+        cur = nxt;
+    }
+    float *oW = reinterpret_cast<float *>(st + G::OFF_W);
+    float *oV = reinterpret_cast<float *>(st + G::OFF_V);
+    float *oM = reinterpret_cast<float *>(st + G::OFF_M);
+#pragma unroll
+    for (int k = 0; k < NMIX; k++) {
+        oW[(size_t)k * NPIX + p] = W[k];
+        oV[(size_t)k * NPIX + p] = V[k];
+#pragma unroll
+        for (int c = 0; c < 3; c++) oM[(size_t)(k * 3 + c) * NPIX + p] = M[k][c];
+    }
+    st[G::OFF_N + p] = (uint8_t)nm;
+}
+
+// The same body for sources whose frames and streams lie at byte strides of their own and whose working pixel needs arithmetic
+// after the load (decoder surfaces, mog_yuv.hip).  frames: the launch's first frame of stream 0.  `load.at(x, y)` gives the lane's
+// byte offsets within a frame, once; `load(frame, at)` gives the raw words of working pixel (x, y) and `load.px(raw)` makes the
+// pixel of them where it is consumed, so that the next frame's words stay in flight across this frame's mog2_pixel.
+template <class G, class Load>
+__device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__restrict__ frames, long long frame_stride,
+                                                    long long stream_stride, uint8_t *__restrict__ state,
+                                                    const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf,
+                                                    int S, float Tb, unsigned long long *__restrict__ bits) {
+    constexpr int NPIX = G::NPIX;
+    const int s = blockIdx.y;
+    int fend = nvalid[s] - f0;
+    fend = fend < nf ? fend : nf;
+    if (fend <= 0) return;                     // the same for the whole block
+    const int p = blockIdx.x * UPD_BLOCK + threadIdx.x;
+    const int x = p % G::MW, y = p / G::MW;
+    uint8_t *st = state + (size_t)s * G::STATE_BYTES;
+    const float *gW = reinterpret_cast<const float *>(st + G::OFF_W);
+    const float *gV = reinterpret_cast<const float *>(st + G::OFF_V);
+    const float *gM = reinterpret_cast<const float *>(st + G::OFF_M);
+    float W[NMIX], V[NMIX], M[NMIX][3];
+#pragma unroll
+    for (int k = 0; k < NMIX; k++) {
+        W[k] = gW[(size_t)k * NPIX + p];
+        V[k] = gV[(size_t)k * NPIX + p];
+#pragma unroll
+        for (int c = 0; c < 3; c++) M[k][c] = gM[(size_t)(k * 3 + c) * NPIX + p];
+    }
+    int nm = st[G::OFF_N + p];
+    const uint8_t *fr = frames + (long long)s * stream_stride;
+    const typename Load::At at = load.at(x, y);
+    typename Load::Raw cur = load(fr, at);
+    // The model and the first frame's words land here, once (s_waitcnt vmcnt(0), gfx9 encoding).  Left to the compiler, the one
+    // wait for them sits at the head of the loop body, where it also waits for the next frame's words in every later iteration.
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    for (int f = 0; f < fend; f++) {
+        typename Load::Raw nxt = cur;
+        if (f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
+        const float2 pr = par[(size_t)(f0 + f) * S + s];
+        const Px px = load.px(cur);
+        const bool fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
         const unsigned long long word = __ballot(fg);
         if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
         cur = nxt;
@@ -551,3 +610,14 @@ int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, siz
                             const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);
+// The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries.  A surface as a kernel sees it: plane
+// offsets from a frame's first byte, pitches and the two strides in bytes (all even), and the range's constants of
+// include/covahip.h ("MoG labels", conversion): yy = max(0, Y - ysub) * ymul, B += bu * uu, G -= gv * vv + gu * uu, R += rv * vv.
+struct covahip_mog_yuv_src {
+    long long off[3], pitch[3], frame_stride, stream_stride;
+    int ysub, ymul, bu, gv, gu, rv;
+};
+// kind: the reference grid's source kind (0 copy, 1 the 2x2 mean, 2 centre pick) or -1 = the half-size load at working width mw
+int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int kind, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
+                           uint8_t *state, const float2 *par, const int32_t *nvalid, int f0, int nf, int S, float Tb,
+                           unsigned long long *bits);

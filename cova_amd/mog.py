@@ -6,15 +6,21 @@
                takes 2560x1440 (90x160 labels) and 3840x2160 (135x240)
   label_dims   (label_h, label_w) of a source size on either grid, without a GPU
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
+  apply_yuv    the same labels from 8-bit 4:2:0 frames as decoders give them, NV12 or I420, at a row pitch, plane offsets and
+               frame / stream strides of the caller's (a MogYuv layout; yuv_tight makes the dense one), 1.5 bytes per pixel
+               and no BGR copy; limited (video) or full (JPEG) range, the BT.601 constants of cv.cvtColor
+  read_yuv420  raw NV12 / I420 frames (ffmpeg -f rawvideo -pix_fmt nv12 | yuv420p); read_y4m: YUV4MPEG2, which carries its size
 
     ffmpeg -i VIDEO -f rawvideo -pix_fmt bgr24 - | python -m cova_amd.mog --size 1280x720 -:VIDEO_gt.dump
     python -m cova_amd.mog --size 1280x720 a.bgr b.bgr:labels_b.dump ... [--streams S] [--chunk F]
     python -m cova_amd.mog --size 1920x1080 --grid macroblock IN.bgr ...      (68x120 labels: what 1080p records need)
     python -m cova_amd.mog --size 3840x2160 --grid macroblock IN.bgr ...      (135x240 labels; 2560x1440 gives 90x160)
+    ffmpeg -i VIDEO -f yuv4mpegpipe -pix_fmt yuv420p - | python -m cova_amd.mog --format y4m -:VIDEO_gt.dump
+    python -m cova_amd.mog --format nv12 --size 1920x1080 [--range full] IN.nv12 ...     (also --format i420)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
-to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Pixel decoding is not done here:
-the labeller takes decoded BGR frames, which is what cv.VideoCapture hands generate-mog.py.
+to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Bitstream decoding is not done here:
+the labeller takes decoded frames, BGR24 (what cv.VideoCapture hands generate-mog.py) or the decoder's own NV12 / I420.
 """
 from __future__ import annotations
 
@@ -35,6 +41,8 @@ SIZES = ((640, 360), (1280, 720), (1920, 1080))
 MAX_STREAMS = 1024
 GRIDS = {"reference": 0, "macroblock": 1}       # COVAHIP_MOG_GRID_*
 GRID_SIZES = {"reference": SIZES, "macroblock": SIZES + ((2560, 1440), (3840, 2160))}   # the source sizes each grid takes
+FORMATS = {"nv12": 1, "i420": 2}                # COVAHIP_MOG_FMT_*
+RANGES = {"limited": 0, "full": 1}              # COVAHIP_MOG_RANGE_*
 
 
 def work_dims(w: int, h: int, grid: str = "reference"):
@@ -54,6 +62,35 @@ def label_dims(w: int, h: int, grid: str = "reference"):
 
 def _ptr(a: np.ndarray) -> int:
     return a.ctypes.data
+
+
+def yuv_tight(w: int, h: int, fmt: str, range: str = "limited", streams: int = 1, stream_major: bool = False,
+              frames: int | None = None) -> L.MogYuv:
+    """The dense layout of w x h 4:2:0 frames, w * h * 3 / 2 bytes each (the Y plane, then the UV plane of NV12 or the U and V
+    planes of I420): frame-major [F][S][frame] as covahip_mog_yuv_tight gives it, or with stream_major [S][F][frame], which needs
+    `frames` = F, the frames each stream has in the buffer."""
+    if fmt not in FORMATS:
+        raise ValueError(f"unknown format {fmt!r}: one of " + ", ".join(FORMATS))
+    if range not in RANGES:
+        raise ValueError(f"unknown range {range!r}: one of " + ", ".join(RANGES))
+    if w < 2 or h < 2 or w % 2 or h % 2 or streams < 1:
+        raise ValueError(f"4:2:0 frames need even sizes, got {w}x{h}")
+    fb = w * h * 3 // 2
+    lay = L.MogYuv()
+    lay.format, lay.range = FORMATS[fmt], RANGES[range]
+    if fmt == "nv12":
+        lay.offset[:] = (0, w * h, 0)
+        lay.pitch[:] = (w, w, 0)
+    else:
+        lay.offset[:] = (0, w * h, w * h + w * h // 4)
+        lay.pitch[:] = (w, w // 2, w // 2)
+    if stream_major:
+        if frames is None or frames < 1:
+            raise ValueError("a stream-major layout needs frames >= 1")
+        lay.frame_stride, lay.stream_stride = fb, frames * fb
+    else:
+        lay.frame_stride, lay.stream_stride = streams * fb, fb
+    return lay
 
 
 class MogLabeler:
@@ -122,6 +159,41 @@ class MogLabeler:
         L.check(self._lib.covahip_mog_apply(self.handle, d_frames, n_frames, None if nv is None else _ptr(nv), d_labels,
                                             L.MEM_DEVICE), "covahip_mog_apply", self.ctx.handle)
 
+    def yuv_span(self, layout: L.MogYuv, n_frames: int) -> int:
+        """Bytes from `base` to the last byte of the last row that an apply_yuv call of n_frames frames reads."""
+        nv12 = layout.format == FORMATS["nv12"]
+        rows = (self.src_h, self.src_h // 2, self.src_h // 2)
+        rowb = (self.src_w, self.src_w if nv12 else self.src_w // 2, self.src_w // 2)
+        hi = max(layout.offset[p] + (rows[p] - 1) * layout.pitch[p] + rowb[p] for p in range(2 if nv12 else 3))
+        return (n_frames - 1) * layout.frame_stride + (self.streams - 1) * layout.stream_stride + hi
+
+    def apply_yuv(self, buf: np.ndarray, layout: L.MogYuv, n_frames: int, n_valid=None, labels: np.ndarray | None = None) -> np.ndarray:
+        """The labels of n_frames NV12 / I420 frames per stream in `buf` (u8, C-contiguous; byte 0 is the layout's base) ->
+        u8 [F][S][label_h][label_w]: the working pixel is the converted one, as if `apply` had been given the BGR frames.  n_valid
+        and labels as for `apply`.  The layout is the library's to refuse (CovahipError, status 1); a buffer shorter than what
+        the layout reaches raises ValueError."""
+        if not isinstance(buf, np.ndarray) or buf.dtype != np.uint8 or not buf.flags.c_contiguous:
+            raise ValueError("buf must be a C-contiguous u8 array")
+        n = int(n_frames)
+        vals = list(layout.offset) + list(layout.pitch) + [layout.frame_stride, layout.stream_stride]
+        if n >= 1 and min(vals) >= 0 and layout.format in FORMATS.values() and buf.nbytes < self.yuv_span(layout, n):
+            raise ValueError(f"buf has {buf.nbytes} bytes, the layout reaches {self.yuv_span(layout, n)}")
+        if labels is None:
+            labels = np.zeros((max(n, 0), self.streams, self.label_h, self.label_w), np.uint8)
+        elif (labels.shape != (n, self.streams, self.label_h, self.label_w) or labels.dtype != np.uint8
+              or not labels.flags.c_contiguous):
+            raise ValueError(f"labels must be a C-contiguous u8 array [F][S][{self.label_h}][{self.label_w}]")
+        nv = self._n_valid(n_valid, n)
+        L.check(self._lib.covahip_mog_apply_yuv(self.handle, C.byref(layout), _ptr(buf), n, None if nv is None else _ptr(nv),
+                                                _ptr(labels), L.MEM_HOST), "covahip_mog_apply_yuv", self.ctx.handle)
+        return labels
+
+    def apply_yuv_device(self, d_base: int, layout: L.MogYuv, n_frames: int, d_labels: int, n_valid=None):
+        """The same on device pointers: surfaces on the ctx's GPU from d_base, labels u8 [F][S][label_h][label_w] at d_labels."""
+        nv = self._n_valid(n_valid, n_frames)
+        L.check(self._lib.covahip_mog_apply_yuv(self.handle, C.byref(layout), d_base, n_frames, None if nv is None else _ptr(nv),
+                                                d_labels, L.MEM_DEVICE), "covahip_mog_apply_yuv", self.ctx.handle)
+
     def reset(self, s: int):
         """Stream slot s starts a new video: model zeroed, frame count 0."""
         L.check(self._lib.covahip_mog_reset(self.handle, s), "covahip_mog_reset", self.ctx.handle)
@@ -171,10 +243,10 @@ class MogLabeler:
 
 
 # ------------------------------------------------------------------------------------------------ raw BGR24 input
-class _Bgr24Source:
-    """Whole frames of a raw BGR24 stream; a trailing partial frame raises ValueError."""
+class _RawSource:
+    """Whole frames of frame_bytes bytes of a raw stream; a trailing partial frame raises ValueError."""
 
-    def __init__(self, src, w: int, h: int):
+    def __init__(self, src, frame_bytes: int):
         self.name = src if isinstance(src, str) else getattr(src, "name", "<stream>")
         if src == "-":
             self.f, self.own = sys.stdin.buffer, False
@@ -182,7 +254,7 @@ class _Bgr24Source:
             self.f, self.own = open(src, "rb"), True
         else:
             self.f, self.own = src, False
-        self.frame_bytes = w * h * 3
+        self.frame_bytes = frame_bytes
         self.frames = 0
 
     def read_into(self, out: np.ndarray) -> bool:
@@ -206,14 +278,82 @@ class _Bgr24Source:
             self.f.close()
 
 
+class _Bgr24Source(_RawSource):
+    """Whole frames of a raw BGR24 stream."""
+
+    def __init__(self, src, w: int, h: int):
+        super().__init__(src, w * h * 3)
+
+
+Y4M_CHROMA = ("420", "420jpeg", "420mpeg2", "420paldv")     # the 8-bit 4:2:0 tags: the same bytes, as tight I420
+
+
+class _Y4mSource(_RawSource):
+    """Whole frames of a YUV4MPEG2 stream: `YUV4MPEG2 W.. H.. [C420..] [XCOLORRANGE=FULL|LIMITED] ..\\n`, then per frame
+    `FRAME..\\n` and tight I420.  w, h and range (None where the header has no XCOLORRANGE) come from the header; another
+    chroma tag, a malformed header or a truncated frame raises ValueError."""
+
+    def __init__(self, src):
+        super().__init__(src, 0)
+        try:
+            tags = self._line(b"YUV4MPEG2", "a YUV4MPEG2 header").split()
+            self.w = self.h = 0
+            self.range = None
+            for t in tags:
+                if t[:1] == b"W":
+                    self.w = int(t[1:])
+                elif t[:1] == b"H":
+                    self.h = int(t[1:])
+                elif t[:1] == b"C" and t[1:].decode("ascii", "replace") not in Y4M_CHROMA:
+                    raise ValueError(f"{self.name}: chroma {t[1:].decode('ascii', 'replace')!r} is not 8-bit 4:2:0 (one of "
+                                     + ", ".join("C" + c for c in Y4M_CHROMA) + ")")
+                elif t.startswith(b"XCOLORRANGE="):
+                    v = t[12:].decode("ascii", "replace").lower()
+                    if v not in RANGES:
+                        raise ValueError(f"{self.name}: XCOLORRANGE={v!r} is neither FULL nor LIMITED")
+                    self.range = v
+            if self.w < 2 or self.h < 2 or self.w % 2 or self.h % 2:
+                raise ValueError(f"{self.name}: no even W and H in the YUV4MPEG2 header")
+        except ValueError:
+            self.close()
+            raise
+        self.frame_bytes = self.w * self.h * 3 // 2
+
+    def _line(self, magic: bytes, what: str, at_end_ok: bool = False):
+        """The rest of a line that starts with `magic`; None at the end of the stream where that is allowed."""
+        line = bytearray()
+        while len(line) < 4096:
+            c = self.f.read(1)
+            if not c:
+                break
+            if c == b"\n":
+                if not line.startswith(magic):
+                    break
+                return bytes(line[len(magic):])
+            line += c
+        if at_end_ok and not line:
+            return None
+        raise ValueError(f"{self.name}: expected {what} after {self.frames} frames, got {bytes(line[:16])!r}")
+
+    def read_into(self, out: np.ndarray) -> bool:
+        if self._line(b"FRAME", "a FRAME header", at_end_ok=True) is None:
+            return False
+        if not super().read_into(out):
+            raise ValueError(f"{self.name}: truncated input, a FRAME header and no frame after {self.frames} frames")
+        return True
+
+
 def read_bgr24(path_or_stdin, w: int, h: int, chunk: int):
     """Yields u8 [k][h][w][3] chunks, 1 <= k <= chunk, of a raw BGR24 stream (a path, "-" for stdin, or a binary file
     object), to its end.  A trailing partial frame raises ValueError."""
     if chunk < 1:
         raise ValueError("chunk must be >= 1")
-    src = _Bgr24Source(path_or_stdin, w, h)
+    yield from _chunks(_Bgr24Source(path_or_stdin, w, h), (h, w, 3), chunk)
+
+
+def _chunks(src, frame_shape, chunk: int):
     try:
-        buf = np.empty((chunk, h, w, 3), np.uint8)
+        buf = np.empty((chunk,) + tuple(frame_shape), np.uint8)
         while True:
             k = 0
             while k < chunk and src.read_into(buf[k]):
@@ -225,6 +365,46 @@ def read_bgr24(path_or_stdin, w: int, h: int, chunk: int):
                 return
     finally:
         src.close()
+
+
+def read_yuv420(path_or_stdin, w: int, h: int, chunk: int, fmt: str = "i420"):
+    """Yields u8 [k][w * h * 3 / 2] chunks, 1 <= k <= chunk, of a raw NV12 or I420 stream of tight frames (yuv_tight(w, h, fmt)
+    is a chunk's layout), with the contract of read_bgr24: a path, "-" or a binary file object, to its end; a trailing partial
+    frame raises ValueError."""
+    if chunk < 1:
+        raise ValueError("chunk must be >= 1")
+    if fmt not in FORMATS:
+        raise ValueError(f"unknown format {fmt!r}: one of " + ", ".join(FORMATS))
+    if w < 2 or h < 2 or w % 2 or h % 2:
+        raise ValueError(f"4:2:0 frames need even sizes, got {w}x{h}")
+    yield from _chunks(_RawSource(path_or_stdin, w * h * 3 // 2), (w * h * 3 // 2,), chunk)
+
+
+class Y4mReader:
+    """read_y4m's result: w, h, fmt ("i420") and range ("full" / "limited", or None where the header does not say) from the
+    header; iterating yields u8 [k][w * h * 3 / 2] chunks of tight I420 frames, 1 <= k <= chunk, to the stream's end."""
+
+    fmt = "i420"
+
+    def __init__(self, path_or_stdin, chunk: int):
+        if chunk < 1:
+            raise ValueError("chunk must be >= 1")
+        self._src = _Y4mSource(path_or_stdin)
+        self._chunk = chunk
+        self.w, self.h, self.range = self._src.w, self._src.h, self._src.range
+
+    def __iter__(self):
+        return _chunks(self._src, (self._src.frame_bytes,), self._chunk)
+
+    def close(self):
+        self._src.close()
+
+
+def read_y4m(path_or_stdin, chunk: int) -> Y4mReader:
+    """A YUV4MPEG2 stream (ffmpeg -f yuv4mpegpipe -pix_fmt yuv420p) from a path, "-" or a binary file object: the header is read
+    at once (ValueError for a chroma tag other than C420 / C420jpeg / C420mpeg2 / C420paldv), the frames in chunks while
+    iterating; a truncated frame raises ValueError."""
+    return Y4mReader(path_or_stdin, chunk)
 
 
 # ------------------------------------------------------------------------------------------------ command line
@@ -256,10 +436,17 @@ def parse_io(arg: str):
 
 def _args(argv):
     ap = argparse.ArgumentParser(prog="python -m cova_amd.mog", description=__doc__.split("\n")[0])
-    ap.add_argument("inputs", nargs="+", type=parse_io, metavar="IN[:OUT]",
-                    help="raw BGR24 video ('-' = stdin); OUT defaults to IN's name with _gt.dump")
-    ap.add_argument("--size", type=parse_size, required=True,
-                    help="source size: 640x360, 1280x720 or 1920x1080; with --grid macroblock also 2560x1440 and 3840x2160")
+    ap.add_argument("inputs", nargs="*", type=parse_io, metavar="IN[:OUT]",
+                    help="raw video in --format ('-' = stdin); OUT defaults to IN's name with _gt.dump")
+    ap.add_argument("--size", type=parse_size, default=None,
+                    help="source size: 640x360, 1280x720 or 1920x1080; with --grid macroblock also 2560x1440 and 3840x2160 "
+                         "(optional with --format y4m, whose header has it)")
+    ap.add_argument("--format", choices=("bgr24", "nv12", "i420", "y4m"), default="bgr24",
+                    help="bgr24: packed BGR, 3 bytes per pixel; nv12, i420: tight 4:2:0 frames, 1.5 bytes per pixel; y4m: "
+                         "YUV4MPEG2 (ffmpeg -f yuv4mpegpipe -pix_fmt yuv420p)")
+    ap.add_argument("--range", choices=sorted(RANGES), default=None,
+                    help="of the YUV formats: limited (video, Y 16..235; the default) or full (JPEG, yuvj420p); a y4m header's XCOLORRANGE "
+                         "must agree with it where one is given")
     ap.add_argument("--grid", choices=sorted(GRIDS), default="reference",
                     help="reference: 45x80 labels whatever the source (the 1280x720 macroblock grid); macroblock: one label per "
                          "macroblock of the source, which 1080p records need (1920x1080 -> 68x120, 2560x1440 -> 90x160, "
@@ -269,8 +456,22 @@ def _args(argv):
     ap.add_argument("--history", type=int, default=9000)
     ap.add_argument("--var-threshold", type=float, default=32.0)
     ap.add_argument("--device", type=int, default=0)
-    a = ap.parse_args(argv)
-    if a.size not in GRID_SIZES[a.grid]:
+    # `-:OUT` (stdin) starts with a dash, so argparse takes it for an option it does not know: such arguments are inputs
+    a, rest = ap.parse_known_args(argv)
+    for r in rest:
+        if not r.startswith("-:"):
+            ap.error(f"unrecognized arguments: {r}")
+        try:
+            a.inputs.append(parse_io(r))
+        except argparse.ArgumentTypeError as e:
+            ap.error(str(e))
+    if not a.inputs:
+        ap.error("the following arguments are required: IN[:OUT]")
+    a.range_given = a.range is not None
+    a.range = a.range or "limited"
+    if a.size is None and a.format != "y4m":
+        ap.error(f"--format {a.format} needs --size")
+    if a.size is not None and a.size not in GRID_SIZES[a.grid]:
         ap.error(f"--size {a.size[0]}x{a.size[1]} needs --grid macroblock")
     if a.streams is None:
         a.streams = min(len(a.inputs), 8)
@@ -294,12 +495,56 @@ def main(argv=None) -> int:
     a = _args(argv)
     from .elements import Context
 
+    def fail(msg):                # as argparse's error(): a usage mistake is exit status 2
+        print(f"python -m cova_amd.mog: error: {msg}", file=sys.stderr)
+        raise SystemExit(2)
+
+    # y4m: every header must agree with --size, --range and the other headers.  Files are looked at before anything is set up;
+    # stdin can be read once, so its source is opened here (and kept) only where nothing else gives the size.
+    opened = {}
+    y4m_range = [a.range if a.range_given else None]
+
+    def y4m_open(src):
+        try:
+            y = opened.pop(src, None) or _Y4mSource(src)
+        except (OSError, ValueError) as e:
+            fail(str(e))
+        if a.size is None:
+            try:
+                a.size = parse_size(f"{y.w}x{y.h}")
+            except argparse.ArgumentTypeError as e:
+                y.close()
+                fail(f"{y.name}: {e}")
+            if a.size not in GRID_SIZES[a.grid]:
+                y.close()
+                fail(f"{y.name}: {y.w}x{y.h} needs --grid macroblock")
+        if (y.w, y.h) != a.size:
+            y.close()
+            fail(f"{y.name}: the header says {y.w}x{y.h}, expected {a.size[0]}x{a.size[1]}")
+        if y.range is not None:
+            if y4m_range[0] is not None and y.range != y4m_range[0]:
+                y.close()
+                fail(f"{y.name}: the header says XCOLORRANGE={y.range.upper()}, expected {y4m_range[0]}")
+            y4m_range[0] = y.range
+        return y
+
+    if a.format == "y4m":
+        for src, _ in a.inputs:
+            if src != "-":
+                y4m_open(src).close()
+        if a.size is None:
+            opened["-"] = y4m_open("-")
+        if y4m_range[0] is not None:
+            a.range = y4m_range[0]
+        y4m_range[0] = a.range          # from here on a header that names a range names this one
     w, h = a.size
     S = min(a.streams, len(a.inputs))
     pending = list(a.inputs)
+    yuv = a.format != "bgr24"
     ctx = Context(a.device)
     mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid)
-    frames = np.empty((a.chunk, S, h, w, 3), np.uint8)
+    layout = yuv_tight(w, h, "nv12" if a.format == "nv12" else "i420", a.range, streams=S) if yuv else None
+    frames = np.empty((a.chunk, S, w * h * 3 // 2) if yuv else (a.chunk, S, h, w, 3), np.uint8)
     labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)
     slots = [None] * S           # (source, output file, output name, start time) per stream slot
 
@@ -308,7 +553,8 @@ def main(argv=None) -> int:
             slots[s] = None
             return
         src, out = pending.pop(0)
-        slots[s] = (_Bgr24Source(src, w, h), open(out, "wb"), out, time.perf_counter())
+        source = (y4m_open(src) if a.format == "y4m" else _RawSource(src, w * h * 3 // 2) if yuv else _Bgr24Source(src, w, h))
+        slots[s] = (source, open(out, "wb"), out, time.perf_counter())
         mog.reset(s)
 
     def finish(s):
@@ -335,7 +581,10 @@ def main(argv=None) -> int:
                     open_next(s)
             if not nv.any():
                 break
-            mog.apply(frames[:int(nv.max())], n_valid=nv, labels=labels[:int(nv.max())])
+            if yuv:
+                mog.apply_yuv(frames, layout, int(nv.max()), n_valid=nv, labels=labels[:int(nv.max())])
+            else:
+                mog.apply(frames[:int(nv.max())], n_valid=nv, labels=labels[:int(nv.max())])
             for s in range(S):
                 if nv[s]:
                     slots[s][1].write(np.ascontiguousarray(labels[:nv[s], s]).tobytes())

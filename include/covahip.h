@@ -793,7 +793,8 @@ int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const 
 enum { COVAHIP_MOG_MAX_STREAMS = 1024, COVAHIP_MOG_LABEL_H = 45, COVAHIP_MOG_LABEL_W = 80 };
 typedef struct covahip_mog covahip_mog;
 typedef struct covahip_mog_cfg {
-    int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 BGR24; on the macroblock grid also 2560x1440 and 3840x2160 */
+    int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 (BGR24, or NV12 / I420 through covahip_mog_apply_yuv); on the
+                                 * macroblock grid also 2560x1440 and 3840x2160 */
     int32_t n_streams;          /* independent videos advanced per call, 1 .. COVAHIP_MOG_MAX_STREAMS */
     int32_t history;            /* 9000 (generate-mog.py); >= 1 */
     float   var_threshold;      /* 32; finite and > 0 */
@@ -814,6 +815,44 @@ int  covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, in
  * n_frames >= 1.  Host frames are staged in launches of up to 1 GiB of frames. */
 int  covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, const int32_t *n_valid,
                        uint8_t *labels, int mem_kind);
+/* The same from decoder surfaces: 8-bit 4:2:0 frames as NV12 (VCN through VA-API or rocDecode) or I420 (avdec_h264), at the
+ * caller's row pitch, plane offsets and strides, without a BGR24 copy.  Row r of plane p of (frame f, stream s) starts at
+ *   base + f * frame_stride + s * stream_stride + offset[p] + r * pitch[p]       (64-bit arithmetic).
+ * The Y plane is src_h rows of src_w bytes; NV12 chroma is src_h/2 rows of src_w bytes (U, V pairs); I420 has U and V planes of
+ * src_h/2 rows of src_w/2 bytes.  The kernels read nothing outside those rows: not the padding behind a row, not the coded rows
+ * behind the picture (1080 rows sit in 1088), not the gaps between frames.  From host memory the call copies, per (frame,
+ * stream), the extent from the lowest plane start to the last byte of the last row (the row padding inside that extent
+ * included) and nothing else, in launches within the stage budget; where the layout is frame-major and dense (stream_stride =
+ * that extent, frame_stride = n_streams * stream_stride) a launch's frames are one copy.
+ * Conversion, then the resize of step 1 above.  All values int32, >> arithmetic, sat clamps to 0 .. 255, h = 1 << 19,
+ * uu = U - 128, vv = V - 128:
+ *   limited range (the constants of OpenCV's cvtColor(.., COLOR_YUV2BGR_NV12 / _I420): round(c * 2^20) of 1.164, 2.018, 0.391,
+ *   0.813, 1.596):              yy = max(0, Y - 16) * 1220542;
+ *     B = sat((yy + h + 2116026 * uu) >> 20); G = sat((yy + h - 852492 * vv - 409993 * uu) >> 20); R = sat((yy + h + 1673527 * vv) >> 20);
+ *   full range (JPEG, yuvj420p; round(c * 2^20) of 1.772, 0.714136, 0.344136, 1.402):      yy = Y << 20;
+ *     B = sat((yy + h + 1858077 * uu) >> 20); G = sat((yy + h - 748826 * vv - 360853 * uu) >> 20); R = sat((yy + h + 1470104 * vv) >> 20).
+ * Source pixel (X, Y) takes the chroma sample (X >> 1, Y >> 1), no interpolation, as cvtColor does.  Then: 640x360 copy; the 2x2
+ * mean converts the block's four pixels (they share one chroma sample) and takes (a + b + c + d + 2) >> 2 per channel
+ * (converting the mean of Y is not the same, because of sat); 1920x1080 on the reference grid converts the pixel at
+ * (3x + 1, 3y + 1).  The working pixel is then (B, G, R) as floats, exactly as if covahip_mog_apply had been given the
+ * converted frame: the same stream slots and model, so apply and apply_yuv calls may be mixed at will, on every source size
+ * and grid.  n_valid, labels and mem_kind (which applies to base and labels) as for covahip_mog_apply; synchronous.
+ * COVAHIP_ERR_INVALID_ARG, before anything is launched and with the model untouched: a NULL argument; an unknown format or
+ * range; a negative offset, pitch or stride; pitch[0] < src_w; NV12 pitch[1] < src_w; I420 pitch[1] or pitch[2] < src_w/2; an
+ * odd base, offset, pitch or stride (Y pairs and UV pairs are loaded as 16-bit words); whatever covahip_mog_apply refuses. */
+enum { COVAHIP_MOG_FMT_NV12 = 1, COVAHIP_MOG_FMT_I420 = 2 };
+enum { COVAHIP_MOG_RANGE_LIMITED = 0, COVAHIP_MOG_RANGE_FULL = 1 };
+typedef struct covahip_mog_yuv {   /* 72 bytes */
+    int32_t format, range;
+    int64_t offset[3];      /* bytes from a frame's first byte to plane p: Y, UV (NV12) | Y, U, V (I420); NV12 ignores [2] */
+    int64_t pitch[3];       /* bytes per row of plane p */
+    int64_t frame_stride;   /* frame f -> f + 1 of one stream */
+    int64_t stream_stride;  /* stream s -> s + 1 at one frame index */
+} covahip_mog_yuv;
+/* the tight frame-major layout [F][S][Y plane, chroma] for this labeller's source size */
+int  covahip_mog_yuv_tight(const covahip_mog *m, int format, int range, covahip_mog_yuv *out);
+int  covahip_mog_apply_yuv(covahip_mog *m, const covahip_mog_yuv *lay, const uint8_t *base, int n_frames,
+                           const int32_t *n_valid, uint8_t *labels, int mem_kind);
 /* Next video in that slot: model zeroed, n = 0. */
 int  covahip_mog_reset(covahip_mog *m, int stream);
 void covahip_mog_destroy(covahip_mog *m);

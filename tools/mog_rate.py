@@ -4,13 +4,15 @@
     python tools/mog_rate.py [--streams 1,8,64 --sizes 1280x720,640x360 --frames 1024 --reps 3] [--oracle-frames 3]
     python tools/mog_rate.py --grid macroblock --sizes 1920x1080 --frames 256      (960x540 working frames, 68x120 labels)
     python tools/mog_rate.py --grid macroblock --sizes 3840x2160,2560x1440 --frames 64 --min-frames 2   (the banded kernels)
+    python tools/mog_rate.py --format nv12 --sizes 1280x720      (covahip_mog_apply_yuv on tight NV12 frames; also i420)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
   host     frames from (pageable) host memory, wall clock of the call: the H2D copy and the label read-back included.
 Each call advances every stream by frames / streams frames, so the model is read and written once per call.  The line also has
 each kernel's share of the device call (HIP-event brackets, covahip_profile_*).  --oracle-frames > 0 adds a line with the numpy
-oracle's (tests/mog_ref.py) frames/s on this machine's CPU.
+oracle's (tests/mog_ref.py) frames/s on this machine's CPU.  --format nv12 | i420 labels the same clip, converted once with a
+numpy forward transform (BT.601, limited range), from tight 4:2:0 frames of 1.5 bytes per pixel; every line says its format.
 """
 import argparse
 import json
@@ -40,11 +42,32 @@ def clip(n, w, h, seed=0):
     return out
 
 
+def to_yuv420(bgr, fmt):
+    """u8 [n][h][w][3] -> u8 [n][h * w * 3 / 2]: tight NV12 or I420 frames of the same scene (BT.601, limited range, chroma as the
+    mean of the 2x2 block)."""
+    f = bgr.astype(np.float32)
+    b, g, r = f[..., 0], f[..., 1], f[..., 2]
+    y = 0.299 * r + 0.587 * g + 0.114 * b
+    cb, cr = (b - y) * (0.564 * 224 / 255), (r - y) * (0.713 * 224 / 255)
+    y = 16 + y * (219 / 255)
+
+    def sub(c):
+        return 128 + (c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2]) / 4
+
+    q = lambda a: np.clip(np.rint(a), 0, 255).astype(np.uint8)   # noqa: E731
+    n = bgr.shape[0]
+    yq, uq, vq = q(y).reshape(n, -1), q(sub(cb)), q(sub(cr))
+    chroma = np.stack([uq, vq], -1).reshape(n, -1) if fmt == "nv12" else np.concatenate([uq.reshape(n, -1), vq.reshape(n, -1)], 1)
+    return np.concatenate([yq, chroma], 1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", default="1,8,64")
     ap.add_argument("--sizes", default="1280x720,640x360")
     ap.add_argument("--grid", choices=sorted(mog.GRIDS), default="reference")
+    ap.add_argument("--format", choices=("bgr24",) + tuple(mog.FORMATS), default="bgr24",
+                    help="bgr24: covahip_mog_apply; nv12, i420: covahip_mog_apply_yuv on the same clip as tight 4:2:0 frames")
     ap.add_argument("--frames", type=int, default=1024, help="working frames per call (all streams)")
     ap.add_argument("--min-frames", type=int, default=8, help="frames per stream and call at least (4K frames are 24.9 MB each)")
     ap.add_argument("--reps", type=int, default=3)
@@ -58,29 +81,46 @@ def main():
     for size in a.sizes.split(","):
         w, h = mog.parse_size(size)
         pool = clip(8, w, h)
+        yuv = a.format != "bgr24"
+        if yuv:
+            pool = to_yuv420(pool, a.format)
         for S in (int(s) for s in a.streams.split(",")):
             F = max(a.min_frames, a.frames // S)
-            frames = np.empty((F, S, h, w, 3), np.uint8)
+            frames = np.empty((F, S, w * h * 3 // 2) if yuv else (F, S, h, w, 3), np.uint8)
+            lay = mog.yuv_tight(w, h, a.format, streams=S) if yuv else None
             for f in range(F):
                 frames[f] = pool[(f + np.arange(S)) % len(pool)]
             labels = np.zeros((F, S) + mog.label_dims(w, h, a.grid), np.uint8)
             m = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
-            m.apply_device(d_f, F, d_l)                      # warm-up (buffers, code objects)
+
+            def apply_device():
+                if yuv:
+                    m.apply_yuv_device(d_f, lay, F, d_l)
+                else:
+                    m.apply_device(d_f, F, d_l)
+
+            def apply_host():
+                if yuv:
+                    m.apply_yuv(frames, lay, F, labels=labels)
+                else:
+                    m.apply(frames, labels=labels)
+
+            apply_device()                                   # warm-up (buffers, code objects)
             ms = []
             for _ in range(a.reps):
                 ctx.timer_start(0)
-                m.apply_device(d_f, F, d_l)
+                apply_device()
                 ctx.timer_stop(0)
                 ms.append(ctx.timer_ms(0))
             ctx.profile(True)
-            m.apply_device(d_f, F, d_l)
+            apply_device()
             prof = ctx.profile_read()
             ctx.profile(False)
             tot = sum(v[0] for k, v in prof.items() if k.startswith("mog_"))
             med = statistics.median(ms)
-            rec = {"case": "device", "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+            rec = {"case": "device", "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
                    "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms],
                    "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
                    "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
@@ -88,14 +128,14 @@ def main():
             ctx.free(d_f)
             ctx.free(d_l)
             if not a.no_host:
-                m.apply(frames, labels=labels)
+                apply_host()
                 wall = []
                 for _ in range(a.reps):
                     t0 = time.perf_counter()
-                    m.apply(frames, labels=labels)
+                    apply_host()
                     wall.append((time.perf_counter() - t0) * 1e3)
                 med = statistics.median(wall)
-                print(json.dumps({"case": "host", "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+                print(json.dumps({"case": "host", "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
                                   "frames_per_s": round(F * S / med * 1e3, 1), "in_gb_per_s": round(frames.nbytes / med / 1e6, 2),
                                   "ms_all": [round(x, 3) for x in wall]}), flush=True)
             m.close()
