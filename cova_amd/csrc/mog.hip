@@ -34,36 +34,27 @@
 namespace {
 
 using namespace mogdev;
-using G = Geom<640, 360>;                      // working size of the reference grid
-constexpr int MW = G::MW, MH = G::MH, NPIX = G::NPIX, ROWW = G::ROWW, NWORD = G::NWORD;
+using G = G640;                                // working size of the reference grid
+constexpr int MW = G::MW, ROWW = G::ROWW, NWORD = G::NWORD;
 constexpr int LW = G::LW, LH = G::LH, NLAB = G::NLAB;
 constexpr int POST_BLOCK = 256;
 static_assert(LW == COVAHIP_MOG_LABEL_W && LH == COVAHIP_MOG_LABEL_H && NLAB == NWORD, "geometry");
 // device budget for host frames staged per update launch (covahip_dev_mog_set_stage_budget changes it per labeller)
 constexpr size_t STAGE_BUDGET = (size_t)1 << 30;
 
-// source pixel(s) of working pixel (x, y) of one frame, resized as cv.resize INTER_LINEAR does for the three sizes
+// source pixel(s) of working pixel (x, y) of one frame, resized as cv.resize INTER_LINEAR does for the three sizes: the copy
+// (640x360 sources), the 2x2 mean (1280x720) and the centre pick (1920x1080)
 template <int SRC>
 struct LoadPx {
     __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
-        if constexpr (SRC == 0) {
-            const uint8_t *q = fr + ((size_t)y * 640 + x) * 3;
-            return {(float)q[0], (float)q[1], (float)q[2]};
-        } else if constexpr (SRC == 1) {
-            const uint8_t *a = fr + ((size_t)(2 * y) * 1280 + 2 * x) * 3;
-            const uint8_t *b = a + 1280 * 3;
-            unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
-            unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
-            unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
-            return {(float)s0, (float)s1, (float)s2};
-        } else {
-            const uint8_t *q = fr + ((size_t)(3 * y + 1) * 1920 + 3 * x + 1) * 3;
-            return {(float)q[0], (float)q[1], (float)q[2]};
-        }
+        if constexpr (SRC == MOG_LOAD_HALF) return LoadHalf<MW>()(fr, x, y);
+        const uint8_t *q = SRC == MOG_LOAD_COPY ? fr + ((size_t)y * 640 + x) * 3 : fr + ((size_t)(3 * y + 1) * 1920 + 3 * x + 1) * 3;
+        return {(float)q[0], (float)q[1], (float)q[2]};
     }
 };
 
-// frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of the call; bits: raw masks [F][S][3600]
+// SRC: MOG_LOAD_*.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of the call; bits: raw masks
+// [F][S][3600]
 template <int SRC>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
                                                           const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
@@ -89,26 +80,15 @@ __global__ __launch_bounds__(POST_BLOCK) void k_mog_post(const unsigned long lon
     uint8_t *lab = labels + (size_t)fs * NLAB;
     for (int i = tid; i < NWORD; i += POST_BLOCK) {
         dst[i] = ~T[i];
-        const int r = i / LW, c = i % LW;              // label (r, c) = filled pixel (8 c, 8 r); NLAB == NWORD here
-        lab[i] = (uint8_t)((~T[8 * r * ROWW + c / 8] >> (8 * (c % 8))) & 1ull);
+        lab[i] = label_bit(T, i / LW, i % LW, ROWW);   // NLAB == NWORD here
     }
 }
 
-int src_kind(int w, int h) {
-    if (w == 640 && h == 360) return 0;
-    if (w == 1280 && h == 720) return 1;
-    if (w == 1920 && h == 1080) return 2;
-    if (w == 2560 && h == 1440) return 3;      // 3, 4: the macroblock grid only
-    if (w == 3840 && h == 2160) return 4;
-    return -1;
-}
-
-// LDS of the banded post kernel beside its two planes: 16 bytes of flags and the column sweep's carries (256 bytes per word column)
-size_t band_lds_fixed(int mw) { return 16 + (size_t)256 * (mw / 64); }
-
-// the widest staged window of the banded post kernel: two planes of rows + 16 rows within a CU's LDS
+// the highest band of the banded post kernel at working width mw: band_lds_bytes is linear in the staged rows (a window of 0
+// rows is its fixed part, of 1 row one row more), and a band stages HALO_UP + HALO_DOWN rows beside its own
 int band_max_rows(int mw) {
-    return (int)((COVAHIP_MOG_BAND_LDS_MAX - band_lds_fixed(mw)) / ((size_t)2 * (mw / 64) * 8)) - 16;
+    const size_t fixed = band_lds_bytes(mw, 0, 0), per_row = band_lds_bytes(mw, 1, 1) - fixed;
+    return (int)((COVAHIP_MOG_BAND_LDS_MAX - fixed) / per_row) - (HALO_UP + HALO_DOWN);
 }
 
 // the automatic band plan: as few bands as fit, of equal height
@@ -118,19 +98,14 @@ void band_plan(int mw, int mh, int *rows, int *bands) {
     *rows = (mh + *bands - 1) / *bands;
 }
 
-size_t band_lds_bytes(int mw, int mh, int rows) { return (size_t)2 * std::min(rows + 16, mh) * (mw / 64) * 8 + band_lds_fixed(mw); }
-
 }  // namespace
 
 struct covahip_mog {
     covahip_ctx *ctx = nullptr;
     covahip_mog_cfg cfg{};
-    int kind = 0;                  // reference-grid kernels: source kind (src_kind); -1 = the kernels of mog_grid.hip / mog_band.hip
-    bool banded = false;           // kind -1: the post kernel of mog_band.hip (always at working widths 1280 and 1920)
+    const MogGeomRow *row = nullptr;   // the (source size, grid) row of MOG_GEOMS
+    bool banded = false;           // the post kernel of mog_band.hip, where the row has it
     int band_rows = 0;             // its band height; 0 = the automatic plan
-    int grid = COVAHIP_MOG_GRID_REFERENCE;
-    int mw = MW, mh = MH, lw = LW, lh = LH;   // working size and labels
-    size_t npix = NPIX, nword = NWORD, nlab = NLAB, state_bytes = G::STATE_BYTES;
     size_t src_bytes = 0;
     std::vector<int64_t> n;        // frames each stream has seen
     uint8_t *state = nullptr;      // [S][state_bytes]
@@ -152,30 +127,6 @@ void free_mog(covahip_mog *m) {
     delete m;
 }
 
-int launch_update(covahip_mog *m, const uint8_t *d_frames, int f0, int nf, int S, const float2 *d_par, const int32_t *d_nv) {
-    covahip_ctx *ctx = m->ctx;
-    const dim3 grid(NPIX / UPD_BLOCK, S);
-    auto *bits = static_cast<unsigned long long *>(m->bits);
-    if (m->kind < 0 && m->mw > 960)
-        return covahip_mog_band_update(ctx, m->mw, d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold, bits);
-    if (m->kind < 0)
-        return covahip_mog_grid_update(ctx, m->mw, d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold, bits);
-    {
-        ProfScope ps(ctx, "mog_update");
-        if (m->kind == 0)
-            k_mog_update<0><<<grid, UPD_BLOCK, 0, ctx->stream>>>(d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S,
-                                                                 m->cfg.var_threshold, bits);
-        else if (m->kind == 1)
-            k_mog_update<1><<<grid, UPD_BLOCK, 0, ctx->stream>>>(d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S,
-                                                                 m->cfg.var_threshold, bits);
-        else
-            k_mog_update<2><<<grid, UPD_BLOCK, 0, ctx->stream>>>(d_frames, m->src_bytes, m->state, d_par, d_nv, f0, nf, S,
-                                                                 m->cfg.var_threshold, bits);
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
-}
-
 // A checked covahip_mog_yuv: the surface as the kernels of mog_yuv.hip take it, and the bytes lo .. lo + ext of a frame that
 // hold its planes' rows (what a call from host memory stages per frame and stream).
 struct YuvPlan {
@@ -184,10 +135,16 @@ struct YuvPlan {
     size_t lo = 0, ext = 0;
 };
 
-int launch_update_yuv(covahip_mog *m, int format, const uint8_t *d_frames, const covahip_mog_yuv_src &src, int f0, int nf, int S,
-                      const float2 *d_par, const int32_t *d_nv) {
-    return covahip_mog_yuv_update(m->ctx, format, m->kind, m->mw, d_frames, src, m->state, d_par, d_nv, f0, nf, S, m->cfg.var_threshold,
-                                  static_cast<unsigned long long *>(m->bits));
+// one update launch on device frames: BGR24 (yuv == nullptr) or the surfaces of `yuv`'s format as `src` describes them
+int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
+    covahip_ctx *ctx = m->ctx;
+    const int load = m->row->load;
+    if (yuv) return covahip_mog_yuv_update(ctx, yuv->format, load, m->row->work.mw, d_frames, src, a);
+    if (m->row->work.mw != MW)             // the macroblock grid's other working sizes: the kernels beside the row's post kernels
+        return (m->row->resident ? covahip_mog_grid_update : covahip_mog_band_update)(ctx, m->row->work.mw, d_frames, m->src_bytes, a);
+    const auto kernel = load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY>
+                                              : (load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF> : k_mog_update<MOG_LOAD_PICK>);
+    return mog_launch_update<G>(ctx, "mog_update", kernel, d_frames, m->src_bytes, a);
 }
 
 // the post launch on the call's raw planes (m->bits): filled planes and labels of FS (frame, stream) pairs
@@ -196,19 +153,14 @@ int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, s
     auto *bits = static_cast<const unsigned long long *>(m->bits);
     auto *filled = static_cast<unsigned long long *>(m->filled);
     if (m->banded) {
-        if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->nword * 8)) return rc;
+        if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->row->work.nword() * 8)) return rc;
         int rows = m->band_rows, bands = 0;
-        if (!rows) band_plan(m->mw, m->mh, &rows, &bands);
-        return covahip_mog_band_post(ctx, m->mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
+        if (!rows) band_plan(m->row->work.mw, m->row->work.mh, &rows, &bands);
+        return covahip_mog_band_post(ctx, m->row->work.mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
                                      rows);
     }
-    if (m->kind < 0) return covahip_mog_grid_post(ctx, m->mw, bits, filled, d_labels, d_nv, S, FS);
-    {
-        ProfScope ps(ctx, "mog_post");
-        k_mog_post<<<dim3((unsigned)FS), POST_BLOCK, 0, ctx->stream>>>(bits, filled, d_labels, d_nv, S);
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
+    if (m->row->work.mw != MW) return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS);
+    return mog_launch(ctx, "mog_post", k_mog_post, dim3((unsigned)FS), POST_BLOCK, 0, bits, filled, d_labels, d_nv, S);
 }
 
 }  // namespace
@@ -235,32 +187,18 @@ int covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int gr
     if (cfg->n_streams < 1 || cfg->n_streams > COVAHIP_MOG_MAX_STREAMS || cfg->history < 1 || !std::isfinite(cfg->var_threshold) ||
         !(cfg->var_threshold > 0.f))
         return COVAHIP_ERR_INVALID_ARG;
-    int kind = src_kind(cfg->src_w, cfg->src_h);
-    if (kind < 0 || (kind > 2 && grid != COVAHIP_MOG_GRID_MACROBLOCK)) return COVAHIP_ERR_UNSUPPORTED;
-    // the macroblock grid works at half the source: 1280x720 is then the reference grid itself (kind 1, the same kernels)
-    const bool half = grid == COVAHIP_MOG_GRID_MACROBLOCK && kind != 1;
-    if (half) kind = -1;
+    const MogGeomRow *row = mog_geom_row(cfg->src_w, cfg->src_h, grid);
+    if (!row) return COVAHIP_ERR_UNSUPPORTED;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     covahip_mog *m = new covahip_mog();
     m->ctx = ctx;
     m->cfg = *cfg;
-    m->kind = kind;
-    m->grid = grid;
-    if (half) {
-        m->mw = cfg->src_w / 2;
-        m->mh = cfg->src_h / 2;
-        m->lw = (m->mw + 7) / 8;
-        m->lh = (m->mh + 7) / 8;
-        m->npix = (size_t)m->mw * m->mh;
-        m->nword = m->npix / 64;
-        m->nlab = (size_t)m->lw * m->lh;
-        m->state_bytes = (size_t)5 * NMIX * m->npix * 4 + m->npix;
-        m->banded = m->mw > 960;
-    }
+    m->row = row;
+    m->banded = row->starts_banded;
     m->src_bytes = (size_t)cfg->src_w * cfg->src_h * 3;
     m->n.assign(cfg->n_streams, 0);
-    const size_t sb = m->state_bytes * cfg->n_streams;
+    const size_t sb = m->row->work.state_bytes() * cfg->n_streams;
     hipError_t e = hipMalloc(&m->state, sb);
     if (e == hipSuccess) e = hipMemsetAsync(m->state, 0, sb, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
@@ -293,7 +231,7 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     const size_t FS = (size_t)n_frames * S;
-    const size_t NWORD = m->nword, NLAB = m->nlab;   // this labeller's geometry
+    const size_t NWORD = m->row->work.nword(), NLAB = m->row->work.nlab();   // this labeller's geometry
     // per-stream, per-frame learning rates, in double as generate-mog.py's OpenCV computes them
     const size_t par_bytes = FS * sizeof(float2) + S * sizeof(int32_t);
     if (m->h_par_bytes < par_bytes) {
@@ -318,52 +256,39 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(m->d_par, hp, par_bytes, hipMemcpyHostToDevice, ctx->stream));
     const float2 *d_par = static_cast<const float2 *>(m->d_par);
     const int32_t *d_nv = reinterpret_cast<const int32_t *>(d_par + FS);
+    MogUpdateArgs a{m->state, d_par, d_nv, 0, n_frames, S, m->cfg.var_threshold, static_cast<unsigned long long *>(m->bits)};
+    covahip_mog_yuv_src src = yuv ? yuv->src : covahip_mog_yuv_src{};
     uint8_t *d_labels = labels;
     if (mem_kind == COVAHIP_MEM_DEVICE) {
-        if (int rc = yuv ? launch_update_yuv(m, yuv->format, frames, yuv->src, 0, n_frames, S, d_par, d_nv)
-                         : launch_update(m, frames, 0, n_frames, S, d_par, d_nv))
-            return rc;
-    } else if (yuv) {
-        // host surfaces: per (frame, stream) the extent lo .. lo + ext of the frame is staged, densely and frame-major, so the
-        // kernel sees the caller's plane offsets less lo and the caller's pitches; nothing outside an extent is read
-        const size_t slot = (yuv->ext + 15) & ~(size_t)15, step = (size_t)S * slot;
-        const bool dense = (size_t)yuv->src.stream_stride == yuv->ext && (size_t)yuv->src.frame_stride == (size_t)S * yuv->ext;
-        const size_t dstep = dense ? (size_t)S * yuv->ext : step;
-        const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, m->stage_budget / dstep));
-        if (int rc = covahip_ensure_buffer(ctx, &m->d_frames, &m->frames_bytes, (size_t)per * dstep)) return rc;
-        covahip_mog_yuv_src st = yuv->src;
-        for (int p = 0; p < 3; p++) st.off[p] -= (long long)yuv->lo;
-        if (!dense) st.stream_stride = (long long)slot, st.frame_stride = (long long)step;
-        uint8_t *d = static_cast<uint8_t *>(m->d_frames);
-        for (int f0 = 0; f0 < n_frames; f0 += per) {
-            const int nf = std::min(per, n_frames - f0);
-            const uint8_t *h0 = frames + yuv->lo + (long long)f0 * yuv->src.frame_stride;
-            if (dense) {
-                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d, h0, (size_t)nf * dstep, hipMemcpyHostToDevice, ctx->stream));
-            } else {
-                for (int f = 0; f < nf; f++)
-                    for (int s = 0; s < S; s++) {
-                        if (f0 + f >= nv[s]) continue;     // frames past n_valid are not read at all
-                        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d + (size_t)f * step + (size_t)s * slot,
-                                                              h0 + (long long)f * yuv->src.frame_stride + (long long)s * yuv->src.stream_stride,
-                                                              yuv->ext, hipMemcpyHostToDevice, ctx->stream));
-                    }
-            }
-            if (int rc = launch_update_yuv(m, yuv->format, d, st, f0, nf, S, d_par, d_nv)) return rc;
-        }
-        if (int rc = covahip_ensure_buffer(ctx, &m->d_labels, &m->labels_bytes, FS * NLAB)) return rc;
-        d_labels = static_cast<uint8_t *>(m->d_labels);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d_labels, labels, FS * NLAB, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = launch_update(m, yuv, frames, src, a)) return rc;
     } else {
-        // host frames: staged in launches of as many frames as fit the budget (the model is read and written once per launch)
-        const size_t step = (size_t)S * m->src_bytes;
+        // host memory: staged in launches of as many frames as fit the budget (the model is read and written once per launch).
+        // Per (frame, stream) the extent lo .. lo + ext of the frame (a BGR24 frame: all of it) is staged, densely and
+        // frame-major, so a kernel on surfaces sees the caller's plane offsets less lo and the caller's pitches; nothing outside
+        // an extent is read.  Frames that lie so already (BGR24; covahip_mog_yuv_tight's layout) are one copy per launch.
+        const size_t lo = yuv ? yuv->lo : 0, ext = yuv ? yuv->ext : m->src_bytes, slot = yuv ? (ext + 15) & ~(size_t)15 : ext;
+        const bool dense = !yuv || ((size_t)src.stream_stride == ext && (size_t)src.frame_stride == (size_t)S * ext);
+        const size_t step = (size_t)S * (dense ? ext : slot);   // staged bytes per frame of the call
+        const long long h_frame = dense ? (long long)step : src.frame_stride, h_stream = src.stream_stride;
         const int per = (int)std::max<size_t>(1, std::min<size_t>((size_t)n_frames, m->stage_budget / step));
         if (int rc = covahip_ensure_buffer(ctx, &m->d_frames, &m->frames_bytes, (size_t)per * step)) return rc;
-        for (int f0 = 0; f0 < n_frames; f0 += per) {
-            const int nf = std::min(per, n_frames - f0);
-            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(m->d_frames, frames + (size_t)f0 * step, (size_t)nf * step, hipMemcpyHostToDevice,
-                                                  ctx->stream));
-            if (int rc = launch_update(m, static_cast<const uint8_t *>(m->d_frames), f0, nf, S, d_par, d_nv)) return rc;
+        uint8_t *d = static_cast<uint8_t *>(m->d_frames);
+        for (int p = 0; p < 3; p++) src.off[p] -= (long long)lo;
+        if (!dense) src.stream_stride = (long long)slot, src.frame_stride = (long long)step;
+        for (a.f0 = 0; a.f0 < n_frames; a.f0 += per) {
+            a.nf = std::min(per, n_frames - a.f0);
+            const uint8_t *h0 = frames + lo + (long long)a.f0 * h_frame;
+            if (dense) {
+                COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d, h0, (size_t)a.nf * step, hipMemcpyHostToDevice, ctx->stream));
+            } else {
+                for (int f = 0; f < a.nf; f++)
+                    for (int s = 0; s < S; s++) {
+                        if (a.f0 + f >= nv[s]) continue;   // frames past n_valid are not read at all
+                        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(d + (size_t)f * step + (size_t)s * slot, h0 + f * h_frame + s * h_stream, ext,
+                                                              hipMemcpyHostToDevice, ctx->stream));
+                    }
+            }
+            if (int rc = launch_update(m, yuv, d, src, a)) return rc;
         }
         if (int rc = covahip_ensure_buffer(ctx, &m->d_labels, &m->labels_bytes, FS * NLAB)) return rc;
         d_labels = static_cast<uint8_t *>(m->d_labels);
@@ -449,17 +374,17 @@ int covahip_mog_reset(covahip_mog *m, int stream) {
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(m->state + (size_t)stream * m->state_bytes, 0, m->state_bytes, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(m->state + (size_t)stream * m->row->work.state_bytes(), 0, m->row->work.state_bytes(), ctx->stream));
     m->n[stream] = 0;
     return COVAHIP_OK;
 }
 
 int covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h) {
     if (!m) return COVAHIP_ERR_INVALID_ARG;
-    if (work_w) *work_w = m->mw;
-    if (work_h) *work_h = m->mh;
-    if (label_w) *label_w = m->lw;
-    if (label_h) *label_h = m->lh;
+    if (work_w) *work_w = m->row->work.mw;
+    if (work_h) *work_h = m->row->work.mh;
+    if (label_w) *label_w = m->row->work.lw();
+    if (label_h) *label_h = m->row->work.lh();
     return COVAHIP_OK;
 }
 
@@ -474,7 +399,7 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
     if (!m || !n_frames) return COVAHIP_ERR_INVALID_ARG;
     *n_frames = m->last_frames;
     const size_t FS = (size_t)m->last_frames * m->cfg.n_streams;
-    const size_t NPIX = m->npix, NWORD = m->nword;
+    const size_t NPIX = m->row->work.npix(), NWORD = m->row->work.nword();
     if ((raw || filled) && cap < FS * NPIX) return COVAHIP_ERR_OVERFLOW;
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -504,7 +429,7 @@ int covahip_dev_mog_post_masks(covahip_mog *m, const uint8_t *raw, int n_frames,
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     const int S = m->cfg.n_streams;
-    const size_t FS = (size_t)n_frames * S, NWORD = m->nword, NLAB = m->nlab;
+    const size_t FS = (size_t)n_frames * S, NWORD = m->row->work.nword(), NLAB = m->row->work.nlab();
     std::vector<unsigned long long> w(FS * NWORD);
     for (size_t i = 0; i < FS * NWORD; i++) {
         unsigned long long v = 0;
@@ -527,10 +452,9 @@ int covahip_dev_mog_post_masks(covahip_mog *m, const uint8_t *raw, int n_frames,
 
 int covahip_dev_mog_set_post_form(covahip_mog *m, int banded, int band_rows) {
     if (!m || (banded != 0 && banded != 1)) return COVAHIP_ERR_INVALID_ARG;
-    const bool has_banded = m->kind < 0 && m->mw >= 960, has_resident = !(m->kind < 0 && m->mw > 960);
-    if (banded ? !has_banded : !has_resident || band_rows != 0) return COVAHIP_ERR_INVALID_ARG;
+    if (banded ? !m->row->banded : !m->row->resident || band_rows != 0) return COVAHIP_ERR_INVALID_ARG;
     if (banded && band_rows != 0 &&
-        (band_rows < 16 || band_rows > m->mh || band_lds_bytes(m->mw, m->mh, band_rows) > COVAHIP_MOG_BAND_LDS_MAX))
+        (band_rows < 16 || band_rows > m->row->work.mh || band_lds_bytes(m->row->work.mw, m->row->work.mh, band_rows) > COVAHIP_MOG_BAND_LDS_MAX))
         return COVAHIP_ERR_INVALID_ARG;
     m->banded = banded != 0;
     m->band_rows = band_rows;
@@ -552,14 +476,14 @@ int covahip_dev_mog_state(covahip_mog *m, int stream, float *W, float *V, float 
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    const size_t NPIX = m->npix;
-    const uint8_t *st = m->state + (size_t)stream * m->state_bytes;
-    const struct { void *dst; size_t off, bytes; } parts[] = {{W, 0, (size_t)NMIX * NPIX * 4},
-                                                              {V, (size_t)NMIX * NPIX * 4, (size_t)NMIX * NPIX * 4},
-                                                              {M, (size_t)2 * NMIX * NPIX * 4, (size_t)NMIX * 3 * NPIX * 4},
-                                                              {nmodes, (size_t)5 * NMIX * NPIX * 4, (size_t)NPIX}};
+    const MogDims &d = m->row->work;
+    const uint8_t *st = m->state + (size_t)stream * d.state_bytes();
+    const struct { void *dst; size_t off, end; } parts[] = {{W, 0, d.off_v()},
+                                                            {V, d.off_v(), d.off_m()},
+                                                            {M, d.off_m(), d.off_n()},
+                                                            {nmodes, d.off_n(), d.state_bytes()}};
     for (const auto &pt : parts)
-        if (pt.dst) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(pt.dst, st + pt.off, pt.bytes, hipMemcpyDeviceToHost, ctx->stream));
+        if (pt.dst) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(pt.dst, st + pt.off, pt.end - pt.off, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n) *n = m->n[stream];
     return COVAHIP_OK;

@@ -31,10 +31,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <utility>
-#include <vector>
-
 #include "covahip.h"
 #include "internal.h"
 #include "mog_dev.h"
@@ -52,16 +48,6 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_band_update(const uint8_t *__
     update_body<Geom<MW, MH>>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
 }
 
-constexpr int HALO_UP = 10, HALO_DOWN = 6;     // rows of input above / below an output row of close 4x4 + open 6x6
-constexpr int FLAG_BYTES = 16;                 // LDS ints in front of the planes: fill loop, seeds of a visit, sweep
-constexpr int carry_bytes(int roww) { return 2 * FILL_SEG * roww * 8; }   // then the column sweep's carries
-
-// bytes of dynamic LDS at band height `rows`: the morphology stage (two windows) is the larger of the two stages
-inline size_t band_lds(int roww, int mh, int rows) {
-    const int win = rows + HALO_UP + HALO_DOWN < mh ? rows + HALO_UP + HALO_DOWN : mh;
-    return (size_t)2 * win * roww * 8 + FLAG_BYTES + carry_bytes(roww);
-}
-
 // bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout (T while the fill runs); plane: the mask after the
 // morphology, same layout; labels [F][S][LH][LW]; rows: band height, >= 1
 template <int MW, int MH, int BLOCK>
@@ -71,9 +57,10 @@ __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long lon
     using G = Geom<MW, MH>;
     constexpr int NWORD = G::NWORD, NLAB = G::NLAB, LW = G::LW, ROWW = G::ROWW;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int *flags = reinterpret_cast<int *>(smem);            // [0] fill loop, [1] a visit's seeds, [2] the sweep
-    unsigned long long *carry = reinterpret_cast<unsigned long long *>(smem + FLAG_BYTES);
-    unsigned long long *P = reinterpret_cast<unsigned long long *>(smem + FLAG_BYTES + carry_bytes(ROWW));
+    // the layout band_lds_bytes sizes: flags ([0] fill loop, [1] a visit's seeds, [2] the sweep), carries, two windows
+    int *flags = reinterpret_cast<int *>(smem);
+    unsigned long long *carry = reinterpret_cast<unsigned long long *>(smem + BAND_FLAG_BYTES);
+    unsigned long long *P = reinterpret_cast<unsigned long long *>(smem + BAND_FLAG_BYTES + band_carry_bytes(ROWW));
     const int fs = blockIdx.x;
     const int f = fs / S, s = fs % S;
     if (f >= nvalid[s]) return;
@@ -93,13 +80,9 @@ __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long lon
         morph_band<ROWW, BLOCK>(X, Y, n);
         for (int i = tid; i < (y1 - y0) * ROWW; i += BLOCK) {
             const int gi = y0 * ROWW + i;
-            const int y = gi / ROWW, w = gi % ROWW;
             const unsigned long long a = X[(y0 - lo) * ROWW + i];
-            unsigned long long edge = (y == 0 || y == MH - 1) ? ~0ull : 0ull;
-            if (w == 0) edge |= 1ull;
-            if (w == ROWW - 1) edge |= 1ull << 63;
             Ag[gi] = a;
-            Tg[gi] = ~a & edge;
+            Tg[gi] = ~a & edge_seed<ROWW>(gi / ROWW, gi % ROWW, MH);
         }
         __syncthreads();                                   // X is free for the next band; A and T are visible
     }
@@ -149,10 +132,7 @@ __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long lon
 
     // 3. labels from T, then filled = ~T in place
     uint8_t *lab = labels + (size_t)fs * NLAB;
-    for (int i = tid; i < NLAB; i += BLOCK) {
-        const int r = i / LW, c = i % LW;                  // label (r, c) = filled pixel (8 c, 8 r); 8 r < MH by Geom's assert
-        lab[i] = (uint8_t)((~Tg[8 * r * ROWW + c / 8] >> (8 * (c % 8))) & 1ull);
-    }
+    for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(Tg, i / LW, i % LW, ROWW);
     __syncthreads();
     for (int i = tid; i < NWORD; i += BLOCK) Tg[i] = ~Tg[i];
 }
@@ -160,58 +140,25 @@ __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long lon
 // 512 lanes: the row fill holds 2 x ROWW 64-bit words per lane (120 VGPRs at 1920 wide) and 512 lanes leave 256 VGPRs each
 constexpr int POST_BLOCK = 512;
 
-template <typename K>
-int open_lds(covahip_ctx *ctx, K kernel) {
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> opened;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto &o : opened)
-        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
-    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)COVAHIP_MOG_BAND_LDS_MAX));
-    opened.emplace_back(ctx->device, fn);
-    return COVAHIP_OK;
-}
-
-template <int MW, int MH>
-int launch_post(covahip_ctx *ctx, const unsigned long long *bits, unsigned long long *filled_bits, unsigned long long *plane,
-                uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows) {
-    if (rows < 16 || rows > MH) return COVAHIP_ERR_UNSUPPORTED;
-    const size_t lds = band_lds(Geom<MW, MH>::ROWW, MH, rows);
-    if (lds > COVAHIP_MOG_BAND_LDS_MAX) return COVAHIP_ERR_UNSUPPORTED;
-    if (int rc = open_lds(ctx, k_mog_band_post<MW, MH, POST_BLOCK>)) return rc;
-    {
-        ProfScope ps(ctx, "mog_band_post");
-        k_mog_band_post<MW, MH, POST_BLOCK><<<dim3((unsigned)FS), POST_BLOCK, lds, ctx->stream>>>(bits, filled_bits, plane, labels,
-                                                                                                  nvalid, S, rows);
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
-}
-
 }  // namespace
 
-int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
-                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits) {
-    {
-        ProfScope ps(ctx, "mog_band_update");
-        if (mw == 1920)
-            k_mog_band_update<1920, 1080><<<dim3(Geom<1920, 1080>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
-                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (mw == 1280)
-            k_mog_band_update<1280, 720><<<dim3(Geom<1280, 720>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
-                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-        else
-            return COVAHIP_ERR_UNSUPPORTED;
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
+int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a) {
+    return with_geom<G1920, G1280>(mw, [&](auto g) {
+        using G = decltype(g);
+        return mog_launch_update<G>(ctx, "mog_band_update", k_mog_band_update<G::MW, G::MH>, frames, src_bytes, a);
+    });
 }
 
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows) {
-    if (mw == 1920) return launch_post<1920, 1080>(ctx, bits, filled_bits, plane, labels, nvalid, S, FS, rows);
-    if (mw == 1280) return launch_post<1280, 720>(ctx, bits, filled_bits, plane, labels, nvalid, S, FS, rows);
-    if (mw == 960) return launch_post<960, 540>(ctx, bits, filled_bits, plane, labels, nvalid, S, FS, rows);
-    return COVAHIP_ERR_UNSUPPORTED;
+    return with_geom<G1920, G1280, G960>(mw, [&](auto g) -> int {
+        using G = decltype(g);
+        if (rows < 16 || rows > G::MH) return COVAHIP_ERR_UNSUPPORTED;
+        const size_t lds = band_lds_bytes(G::MW, G::MH, rows);
+        if (lds > COVAHIP_MOG_BAND_LDS_MAX) return COVAHIP_ERR_UNSUPPORTED;
+        // opened to the maximum, once: `rows` differs between launches
+        if (int rc = open_lds(ctx, k_mog_band_post<G::MW, G::MH, POST_BLOCK>, COVAHIP_MOG_BAND_LDS_MAX)) return rc;
+        return mog_launch(ctx, "mog_band_post", k_mog_band_post<G::MW, G::MH, POST_BLOCK>, dim3((unsigned)FS), POST_BLOCK, lds, bits,
+                          filled_bits, plane, labels, nvalid, S, rows);
+    });
 }

@@ -2,8 +2,10 @@
 // macroblock grid: half-resolution working frames) and mog_band.hip (the macroblock grid of 1440p and 4K sources, whose planes
 // are worked on in row bands): the MOG2 pixel update, the update kernel's body, and the morphology and
 // hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
-// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces; they
-// run update_body_strided, the body's sibling for frames at strides of the caller's.
+// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces.  There
+// is one update body (update_body_strided; update_body adapts a BGR24 load to it) and one set of morphology passes (the band
+// passes; the resident kernels run them on the whole frame).  Below the namespace is the host side the four files share: the
+// table of admitted geometries, Geom's runtime twin, the dispatch on the working width and the banded kernel's LDS formula.
 //
 // No contraction in this code: every product and sum is rounded on its own, as the x86 builds of OpenCV compute it (both
 // translation units are also built with -ffp-contract=off).  The f32 divisions go through double: the f64 quotient is
@@ -18,8 +20,12 @@
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
+#include <mutex>
+#include <utility>
+#include <vector>
 
 #include "covahip.h"
+#include "internal.h"
 
 namespace mogdev {
 
@@ -42,6 +48,11 @@ struct Geom {
     static constexpr size_t STATE_BYTES = OFF_N + NPIX;
     static_assert(NPIX % UPD_BLOCK == 0 && MW % 64 == 0 && 8 * (LH - 1) < MH && (LW - 1) / 8 < ROWW, "geometry");
 };
+using G320 = Geom<320, 180>;                   // the five working geometries
+using G640 = Geom<640, 360>;
+using G960 = Geom<960, 540>;
+using G1280 = Geom<1280, 720>;
+using G1920 = Geom<1920, 1080>;
 
 // correctly rounded a / b through an f64 quotient (see the head of the file).  The empty asm keeps the optimiser from folding
 // the widened division back into the f32 one, whose expansion uses f32 fused multiply-adds.
@@ -148,62 +159,12 @@ __device__ __forceinline__ bool mog2_pixel(float (&W)[NMIX], float (&V)[NMIX], f
     return !bg;
 }
 
-// The update kernel's body: one lane per working pixel and stream, grid (G::NPIX / UPD_BLOCK, S).  `load(frame, x, y)` gives
-// working pixel (x, y) of one source frame.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of
-// the call; bits: raw masks [F][S][G::NWORD].  A wave's 64 pixels lie in one row, so its ballot is one word of the plane.
-template <class G, class Load>
-__device__ __forceinline__ void update_body(Load load, const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
-                                            const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf, int S,
-                                            float Tb, unsigned long long *__restrict__ bits) {
-    constexpr int NPIX = G::NPIX;
-    const int s = blockIdx.y;
-    int fend = nvalid[s] - f0;
-    fend = fend < nf ? fend : nf;
-    if (fend <= 0) return;                     // the same for the whole block
-    const int p = blockIdx.x * UPD_BLOCK + threadIdx.x;
-    const int x = p % G::MW, y = p / G::MW;
-    uint8_t *st = state + (size_t)s * G::STATE_BYTES;
-    const float *gW = reinterpret_cast<const float *>(st + G::OFF_W);
-    const float *gV = reinterpret_cast<const float *>(st + G::OFF_V);
-    const float *gM = reinterpret_cast<const float *>(st + G::OFF_M);
-    float W[NMIX], V[NMIX], M[NMIX][3];
-#pragma unroll
-    for (int k = 0; k < NMIX; k++) {
-        W[k] = gW[(size_t)k * NPIX + p];
-        V[k] = gV[(size_t)k * NPIX + p];
-#pragma unroll
-        for (int c = 0; c < 3; c++) M[k][c] = gM[(size_t)(k * 3 + c) * NPIX + p];
-    }
-    int nm = st[G::OFF_N + p];
-    const size_t fstride = (size_t)S * src_bytes;
-    const uint8_t *fr = frames + (size_t)s * src_bytes;
-    Px cur = load(fr, x, y);
-    for (int f = 0; f < fend; f++) {
-        Px nxt = cur;
-        if (f + 1 < fend) nxt = load(fr + (size_t)(f + 1) * fstride, x, y);   // next frame's pixel in flight
-        const float2 pr = par[(size_t)(f0 + f) * S + s];
-        const bool fg = mog2_pixel(W, V, M, nm, cur, pr.x, pr.y, Tb);
-        const unsigned long long word = __ballot(fg);
-        if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
-        cur = nxt;
-    }
-    float *oW = reinterpret_cast<float *>(st + G::OFF_W);
-    float *oV = reinterpret_cast<float *>(st + G::OFF_V);
-    float *oM = reinterpret_cast<float *>(st + G::OFF_M);
-#pragma unroll
-    for (int k = 0; k < NMIX; k++) {
-        oW[(size_t)k * NPIX + p] = W[k];
-        oV[(size_t)k * NPIX + p] = V[k];
-#pragma unroll
-        for (int c = 0; c < 3; c++) oM[(size_t)(k * 3 + c) * NPIX + p] = M[k][c];
-    }
-    st[G::OFF_N + p] = (uint8_t)nm;
-}
-
-// The same body for sources whose frames and streams lie at byte strides of their own and whose working pixel needs arithmetic
-// after the load (decoder surfaces, mog_yuv.hip).  frames: the launch's first frame of stream 0.  `load.at(x, y)` gives the lane's
-// byte offsets within a frame, once; `load(frame, at)` gives the raw words of working pixel (x, y) and `load.px(raw)` makes the
-// pixel of them where it is consumed, so that the next frame's words stay in flight across this frame's mog2_pixel.
+// The update kernel's body: one lane per working pixel and stream, grid (G::NPIX / UPD_BLOCK, S).  frames: the launch's first
+// frame of stream 0, with frames and streams at byte strides of the caller's; par: (alphaT, prune) [F][S] of the call; bits: raw
+// masks [F][S][G::NWORD].  A wave's 64 pixels lie in one row, so its ballot is one word of the plane.  `load.at(x, y)` gives
+// what the lane needs to address its pixel within a frame (Load::At), once; `load(frame, at)` gives the raw words of working
+// pixel (x, y) (Load::Raw) and `load.px(raw)` makes the pixel of them where it is consumed, so that the next frame's words stay
+// in flight across this frame's mog2_pixel.  Load::WAIT says whether the body waits once before its loop (below).
 template <class G, class Load>
 __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__restrict__ frames, long long frame_stride,
                                                     long long stream_stride, uint8_t *__restrict__ state,
@@ -217,9 +178,8 @@ __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__
     const int p = blockIdx.x * UPD_BLOCK + threadIdx.x;
     const int x = p % G::MW, y = p / G::MW;
     uint8_t *st = state + (size_t)s * G::STATE_BYTES;
-    const float *gW = reinterpret_cast<const float *>(st + G::OFF_W);
-    const float *gV = reinterpret_cast<const float *>(st + G::OFF_V);
-    const float *gM = reinterpret_cast<const float *>(st + G::OFF_M);
+    float *gW = reinterpret_cast<float *>(st + G::OFF_W), *gV = reinterpret_cast<float *>(st + G::OFF_V);
+    float *gM = reinterpret_cast<float *>(st + G::OFF_M);
     float W[NMIX], V[NMIX], M[NMIX][3];
 #pragma unroll
     for (int k = 0; k < NMIX; k++) {
@@ -233,8 +193,9 @@ __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__
     const typename Load::At at = load.at(x, y);
     typename Load::Raw cur = load(fr, at);
     // The model and the first frame's words land here, once (s_waitcnt vmcnt(0), gfx9 encoding).  Left to the compiler, the one
-    // wait for them sits at the head of the loop body, where it also waits for the next frame's words in every later iteration.
-    __builtin_amdgcn_s_waitcnt(0x0F70);
+    // wait for them sits at the head of the loop body, where it also waits for the next frame's words in every later iteration:
+    // that is where the BGR24 kernels have it (WAIT = false), and moving it is a change of speed that wants a measurement.
+    if constexpr (Load::WAIT) __builtin_amdgcn_s_waitcnt(0x0F70);
     for (int f = 0; f < fend; f++) {
         typename Load::Raw nxt = cur;
         if (f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
@@ -245,17 +206,33 @@ __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__
         if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
         cur = nxt;
     }
-    float *oW = reinterpret_cast<float *>(st + G::OFF_W);
-    float *oV = reinterpret_cast<float *>(st + G::OFF_V);
-    float *oM = reinterpret_cast<float *>(st + G::OFF_M);
 #pragma unroll
     for (int k = 0; k < NMIX; k++) {
-        oW[(size_t)k * NPIX + p] = W[k];
-        oV[(size_t)k * NPIX + p] = V[k];
+        gW[(size_t)k * NPIX + p] = W[k];
+        gV[(size_t)k * NPIX + p] = V[k];
 #pragma unroll
-        for (int c = 0; c < 3; c++) oM[(size_t)(k * 3 + c) * NPIX + p] = M[k][c];
+        for (int c = 0; c < 3; c++) gM[(size_t)(k * 3 + c) * NPIX + p] = M[k][c];
     }
     st[G::OFF_N + p] = (uint8_t)nm;
+}
+
+// The body on dense BGR24 frames [nf][S][src_bytes]: `load(frame, x, y)` gives working pixel (x, y) of one source frame.
+template <class L>
+struct PlainLoad {
+    static constexpr bool WAIT = false;
+    L load;
+    struct At { int x, y; };
+    using Raw = Px;
+    __device__ __forceinline__ At at(int x, int y) const { return {x, y}; }
+    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, const At &t) const { return load(fr, t.x, t.y); }
+    __device__ __forceinline__ Px px(const Px &r) const { return r; }
+};
+template <class G, class L>
+__device__ __forceinline__ void update_body(L load, const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
+                                            const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf, int S,
+                                            float Tb, unsigned long long *__restrict__ bits) {
+    update_body_strided<G>(PlainLoad<L>{load}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par, nvalid,
+                           f0, nf, S, Tb, bits);
 }
 
 // working pixel (x, y) of a frame of 2 MW x 2 MH: the rounded mean of its 2x2 block (the macroblock grid's load)
@@ -274,15 +251,22 @@ struct LoadHalf {
 // ------------------------------------------------------------------------------------------------ post passes
 // Bit x of word w of a row is pixel 64 w + x.  A k x k window at x covers x - k/2 .. x + k - 1 - k/2 (OpenCV's anchor, the same
 // offsets for dilate and erode); outside the image is 0 for dilate and 1 for erode.  BLOCK = threads of the workgroup.
-template <class G, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void hpass(const unsigned long long *in, unsigned long long *out) {
+// The passes work on a window of `nrows` whole rows of a frame ROWW words wide: the whole frame in the resident kernels (nrows
+// is G::MH there and folds away), a band and its halo in mog_band.hip (frames whose planes do not fit LDS).  That window is
+// clipped to the frame, so a row beyond it is either outside the frame, where the neutral element is
+// what the pass wants, or a row of the frame that was not staged: then the neutral element is a stand-in, and the rows it
+// reaches (K/2 rows at the top, K - 1 - K/2 at the bottom of the window, per vertical pass) are not valid any more.  The
+// caller stages enough rows around its band for the valid region to end on the band.
+template <int ROWW, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void hpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
     constexpr int A = K / 2, B = K - 1 - K / 2;
     constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    for (int i = threadIdx.x; i < G::NWORD; i += BLOCK) {
-        const int w = i % G::ROWW;
+    const int nword = nrows * ROWW;
+    for (int i = threadIdx.x; i < nword; i += BLOCK) {
+        const int w = i % ROWW;
         const unsigned long long c = in[i];
         const unsigned long long pv = w > 0 ? in[i - 1] : NEU;
-        const unsigned long long nx = w < G::ROWW - 1 ? in[i + 1] : NEU;
+        const unsigned long long nx = w < ROWW - 1 ? in[i + 1] : NEU;
         unsigned long long r = c;
 #pragma unroll
         for (int d = -A; d <= B; d++) {
@@ -294,21 +278,56 @@ __device__ __forceinline__ void hpass(const unsigned long long *in, unsigned lon
     }
 }
 
-template <class G, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void vpass(const unsigned long long *in, unsigned long long *out) {
+template <int ROWW, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void vpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
     constexpr int A = K / 2, B = K - 1 - K / 2;
     constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    for (int i = threadIdx.x; i < G::NWORD; i += BLOCK) {
-        const int y = i / G::ROWW;
+    const int nword = nrows * ROWW;
+    for (int i = threadIdx.x; i < nword; i += BLOCK) {
+        const int y = i / ROWW;
         unsigned long long r = in[i];
 #pragma unroll
         for (int d = -A; d <= B; d++) {
             if (d == 0) continue;
-            const unsigned long long v = (y + d >= 0 && y + d < G::MH) ? in[i + d * G::ROWW] : NEU;
+            const unsigned long long v = (y + d >= 0 && y + d < nrows) ? in[i + d * ROWW] : NEU;
             r = DIL ? (r | v) : (r & v);
         }
         out[i] = r;
     }
+}
+
+// one separable dilate (DIL) or erode K x K of the window in X (LDS, nrows x ROWW words, behind a barrier) through Y (the same
+// size); the result is in X, behind a barrier
+template <int ROWW, int BLOCK, bool DIL, int K>
+__device__ __forceinline__ void morph_pass(unsigned long long *X, unsigned long long *Y, int nrows) {
+    hpass_band<ROWW, BLOCK, DIL, K>(X, Y, nrows);
+    __syncthreads();
+    vpass_band<ROWW, BLOCK, DIL, K>(Y, X, nrows);
+    __syncthreads();
+}
+
+// close 4x4 and open 6x6 of the window in X, with Y as the other plane of the ping-pong.  Of the result's rows, 10 at the top
+// and 6 at the bottom are valid only where the window ends on the frame edge.
+template <int ROWW, int BLOCK>
+__device__ __forceinline__ void morph_band(unsigned long long *X, unsigned long long *Y, int nrows) {
+    morph_pass<ROWW, BLOCK, true, 4>(X, Y, nrows);
+    morph_pass<ROWW, BLOCK, false, 4>(X, Y, nrows);
+    morph_pass<ROWW, BLOCK, false, 6>(X, Y, nrows);
+    morph_pass<ROWW, BLOCK, true, 6>(X, Y, nrows);
+}
+
+// the hole fill's seed in word w of row y of a frame mh rows high: the frame's edge pixels
+template <int ROWW>
+__device__ __forceinline__ unsigned long long edge_seed(int y, int w, int mh) {
+    unsigned long long edge = (y == 0 || y == mh - 1) ? ~0ull : 0ull;
+    if (w == 0) edge |= 1ull;
+    if (w == ROWW - 1) edge |= 1ull << 63;
+    return edge;
+}
+
+// label (r, c) = filled pixel (8 c, 8 r) of the plane whose reached background is T (rows of roww words): 8 r < MH by Geom's assert
+__device__ __forceinline__ uint8_t label_bit(const unsigned long long *T, unsigned r, unsigned c, unsigned roww) {
+    return (uint8_t)((~T[8 * r * roww + c / 8] >> (8 * (c % 8))) & 1ull);
 }
 
 // A (LDS, G::NWORD words, the raw mask; all threads have passed a barrier after writing it) becomes the mask after close 4x4
@@ -318,31 +337,9 @@ template <class G, int BLOCK>
 __device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long long *T, int *changed) {
     constexpr int ROWW = G::ROWW, NWORD = G::NWORD, MH = G::MH;
     const int tid = threadIdx.x;
-    // close 4x4, open 6x6 (separable)
-    hpass<G, BLOCK, true, 4>(A, T);
-    __syncthreads();
-    vpass<G, BLOCK, true, 4>(T, A);
-    __syncthreads();
-    hpass<G, BLOCK, false, 4>(A, T);
-    __syncthreads();
-    vpass<G, BLOCK, false, 4>(T, A);
-    __syncthreads();
-    hpass<G, BLOCK, false, 6>(A, T);
-    __syncthreads();
-    vpass<G, BLOCK, false, 6>(T, A);
-    __syncthreads();
-    hpass<G, BLOCK, true, 6>(A, T);
-    __syncthreads();
-    vpass<G, BLOCK, true, 6>(T, A);
-    __syncthreads();
+    morph_band<ROWW, BLOCK>(A, T, MH);         // close 4x4, open 6x6 (separable) on the whole frame
     // hole fill: T = background reached from the frame edge through 4-connected background (~A)
-    for (int i = tid; i < NWORD; i += BLOCK) {
-        const int y = i / ROWW, w = i % ROWW;
-        unsigned long long edge = (y == 0 || y == MH - 1) ? ~0ull : 0ull;
-        if (w == 0) edge |= 1ull;
-        if (w == ROWW - 1) edge |= 1ull << 63;
-        T[i] = ~A[i] & edge;
-    }
+    for (int i = tid; i < NWORD; i += BLOCK) T[i] = ~A[i] & edge_seed<ROWW>(i / ROWW, i % ROWW, MH);
     for (;;) {
         if (tid == 0) *changed = 0;
         __syncthreads();
@@ -412,74 +409,7 @@ __device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long
     }
 }
 
-// ------------------------------------------------------------------------------------------------ post passes on a row band
-// The same passes on a window of `nrows` whole rows of a frame ROWW words wide (mog_band.hip: frames whose planes do not fit
-// LDS).  The window is clipped to the frame, so a row beyond it is either outside the frame, where the neutral element is
-// what the pass wants, or a row of the frame that was not staged: then the neutral element is a stand-in, and the rows it
-// reaches (K/2 rows at the top, K - 1 - K/2 at the bottom of the window, per vertical pass) are not valid any more.  The
-// caller stages enough rows around its band for the valid region to end on the band.
-template <int ROWW, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void hpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
-    constexpr int A = K / 2, B = K - 1 - K / 2;
-    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    const int nword = nrows * ROWW;
-    for (int i = threadIdx.x; i < nword; i += BLOCK) {
-        const int w = i % ROWW;
-        const unsigned long long c = in[i];
-        const unsigned long long pv = w > 0 ? in[i - 1] : NEU;
-        const unsigned long long nx = w < ROWW - 1 ? in[i + 1] : NEU;
-        unsigned long long r = c;
-#pragma unroll
-        for (int d = -A; d <= B; d++) {
-            if (d == 0) continue;
-            const unsigned long long v = d > 0 ? (c >> d) | (nx << (64 - d)) : (c << -d) | (pv >> (64 + d));
-            r = DIL ? (r | v) : (r & v);
-        }
-        out[i] = r;
-    }
-}
-
-template <int ROWW, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void vpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
-    constexpr int A = K / 2, B = K - 1 - K / 2;
-    constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    const int nword = nrows * ROWW;
-    for (int i = threadIdx.x; i < nword; i += BLOCK) {
-        const int y = i / ROWW;
-        unsigned long long r = in[i];
-#pragma unroll
-        for (int d = -A; d <= B; d++) {
-            if (d == 0) continue;
-            const unsigned long long v = (y + d >= 0 && y + d < nrows) ? in[i + d * ROWW] : NEU;
-            r = DIL ? (r | v) : (r & v);
-        }
-        out[i] = r;
-    }
-}
-
-// close 4x4 and open 6x6 of the window in X (LDS, nrows x ROWW words, behind a barrier), with Y (the same size) as the other
-// plane of the ping-pong.  The result is in X, behind a barrier; of its rows, 10 at the top and 6 at the bottom are valid only
-// where the window ends on the frame edge.
-template <int ROWW, int BLOCK>
-__device__ __forceinline__ void morph_band(unsigned long long *X, unsigned long long *Y, int nrows) {
-    hpass_band<ROWW, BLOCK, true, 4>(X, Y, nrows);
-    __syncthreads();
-    vpass_band<ROWW, BLOCK, true, 4>(Y, X, nrows);
-    __syncthreads();
-    hpass_band<ROWW, BLOCK, false, 4>(X, Y, nrows);
-    __syncthreads();
-    vpass_band<ROWW, BLOCK, false, 4>(Y, X, nrows);
-    __syncthreads();
-    hpass_band<ROWW, BLOCK, false, 6>(X, Y, nrows);
-    __syncthreads();
-    vpass_band<ROWW, BLOCK, false, 6>(Y, X, nrows);
-    __syncthreads();
-    hpass_band<ROWW, BLOCK, true, 6>(X, Y, nrows);
-    __syncthreads();
-    vpass_band<ROWW, BLOCK, true, 6>(Y, X, nrows);
-    __syncthreads();
-}
-
+// ------------------------------------------------------------------------------------------------ hole fill on a row band
 // One direction of the band's column sweep on FILL_SEG row segments per word column: r(y) = T(y) | (~A(y) & r(y - 1)) is linear in
 // OR, so every lane first sweeps its own segment with nothing carried in and notes what leaves the segment (`out`) and which
 // columns are background in all of its rows (`pass`: what a carry would cross the segment through); the carry into a segment
@@ -591,23 +521,135 @@ __device__ __forceinline__ bool fill_band(const unsigned long long *A, unsigned 
     return any;
 }
 
+// The banded post kernel's dynamic LDS at band height `rows` (mog_band.hip lays it out and sizes its launch with this, mog.hip
+// plans and validates band heights with it): the flags (fill loop, seeds of a visit, sweep), the column sweep's carries, then
+// two windows of a band and its halo, clipped to the frame.  The morphology stage is the larger of the two stages; the fill
+// needs only 2 x rows.
+constexpr int HALO_UP = 10, HALO_DOWN = 6;     // rows of input above / below an output row of close 4x4 + open 6x6
+constexpr size_t BAND_FLAG_BYTES = 16;
+constexpr size_t band_carry_bytes(int roww) { return (size_t)2 * FILL_SEG * roww * 8; }
+constexpr size_t band_lds_bytes(int mw, int mh, int rows) {
+    const int win = rows + HALO_UP + HALO_DOWN < mh ? rows + HALO_UP + HALO_DOWN : mh;
+    return BAND_FLAG_BYTES + band_carry_bytes(mw / 64) + (size_t)2 * win * (mw / 64) * 8;
+}
+
 }  // namespace mogdev
 
-// ------------------------------------------------------------------------------------------------ host side (mog_grid.hip)
+// ------------------------------------------------------------------------------------------------ host side
+// Geom at run time: what the host derives from a labeller's working size.
+struct MogDims {
+    int mw, mh;
+    constexpr size_t npix() const { return (size_t)mw * mh; }
+    constexpr size_t nword() const { return npix() / 64; }
+    constexpr int lw() const { return (mw + 7) / 8; }
+    constexpr int lh() const { return (mh + 7) / 8; }
+    constexpr size_t nlab() const { return (size_t)lw() * lh(); }
+    constexpr size_t off_v() const { return (size_t)mogdev::NMIX * npix() * 4; }
+    constexpr size_t off_m() const { return 2 * off_v(); }
+    constexpr size_t off_n() const { return 5 * off_v(); }
+    constexpr size_t state_bytes() const { return off_n() + npix(); }
+};
+template <class G>
+constexpr bool mog_dims_match() {
+    constexpr MogDims d{G::MW, G::MH};
+    return d.npix() == G::NPIX && d.nword() == G::NWORD && d.lw() == G::LW && d.lh() == G::LH && d.nlab() == G::NLAB &&
+           G::OFF_W == 0 && d.off_v() == G::OFF_V && d.off_m() == G::OFF_M && d.off_n() == G::OFF_N &&
+           d.state_bytes() == G::STATE_BYTES;
+}
+static_assert(mog_dims_match<mogdev::G320>() && mog_dims_match<mogdev::G640>() && mog_dims_match<mogdev::G960>() &&
+                  mog_dims_match<mogdev::G1280>() && mog_dims_match<mogdev::G1920>(),
+              "MogDims restates Geom");
+
+// The admitted (source size, grid) pairs: the working size, how the update kernel loads a working pixel, and which forms of
+// the post kernel exist there (resident: both planes in LDS, mog.hip at 640 wide and mog_grid.hip; banded: mog_band.hip) with
+// the one a new labeller starts in.  Where the resident form does not exist the update kernel is mog_band.hip's too.  The
+// macroblock grid works at half the source, so 1280x720 is the reference grid's row there and runs the same kernels.
+enum { MOG_LOAD_COPY = 0, MOG_LOAD_HALF = 1, MOG_LOAD_PICK = 2 };
+struct MogGeomRow {
+    int src_w, src_h;
+    unsigned grids;                // bit COVAHIP_MOG_GRID_*
+    MogDims work;
+    int load;
+    bool resident, banded, starts_banded;
+};
+constexpr unsigned MOG_ON_REF = 1u << COVAHIP_MOG_GRID_REFERENCE, MOG_ON_MB = 1u << COVAHIP_MOG_GRID_MACROBLOCK;
+constexpr MogGeomRow MOG_GEOMS[] = {
+    {640, 360, MOG_ON_REF, {640, 360}, MOG_LOAD_COPY, true, false, false},
+    {1280, 720, MOG_ON_REF | MOG_ON_MB, {640, 360}, MOG_LOAD_HALF, true, false, false},
+    {1920, 1080, MOG_ON_REF, {640, 360}, MOG_LOAD_PICK, true, false, false},
+    {640, 360, MOG_ON_MB, {320, 180}, MOG_LOAD_HALF, true, false, false},
+    {1920, 1080, MOG_ON_MB, {960, 540}, MOG_LOAD_HALF, true, true, false},
+    {2560, 1440, MOG_ON_MB, {1280, 720}, MOG_LOAD_HALF, false, true, true},
+    {3840, 2160, MOG_ON_MB, {1920, 1080}, MOG_LOAD_HALF, false, true, true},
+};
+inline const MogGeomRow *mog_geom_row(int src_w, int src_h, int grid) {
+    for (const MogGeomRow &r : MOG_GEOMS)
+        if (r.src_w == src_w && r.src_h == src_h && (r.grids >> grid & 1u)) return &r;
+    return nullptr;
+}
+
+// f(Geom<MW, MH>{}) for the one of the listed working geometries that is `mw` wide, else COVAHIP_ERR_UNSUPPORTED
+template <class... Gs, class F>
+int with_geom(int mw, F &&f) {
+    int rc = COVAHIP_ERR_UNSUPPORTED;
+    (void)((mw == Gs::MW && ((rc = f(Gs{})), true)) || ...);
+    return rc;
+}
+
+// Opens a kernel's dynamic LDS to `lds` bytes, once per (device, function); up to 64 KiB needs no call.
+template <typename K>
+int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
+    if (lds <= 64 * 1024) return COVAHIP_OK;
+    static std::mutex mu;
+    static std::vector<std::pair<int, const void *>> opened;
+    const void *fn = reinterpret_cast<const void *>(kernel);
+    std::lock_guard<std::mutex> lock(mu);
+    for (auto &o : opened)
+        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
+    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    opened.emplace_back(ctx->device, fn);
+    return COVAHIP_OK;
+}
+
+// What an update launch takes behind its frames: the model, the call's tables (par: (alphaT, prune) [F][S]; nvalid [S]), the
+// launch's frames f0 .. f0 + nf of the call, and the call's raw planes.  All device memory.
+struct MogUpdateArgs {
+    uint8_t *state;
+    const float2 *par;
+    const int32_t *nvalid;
+    int f0, nf, S;
+    float Tb;
+    unsigned long long *bits;
+};
+// One kernel launch on ctx->stream under a profile scope
+template <class K, class... Args>
+int mog_launch(covahip_ctx *ctx, const char *scope, K kernel, dim3 grid, int block, size_t lds, Args... args) {
+    {
+        ProfScope ps(ctx, scope);
+        kernel<<<grid, block, lds, ctx->stream>>>(args...);
+    }
+    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+// One update launch of geometry G: every update kernel takes (frames, src, the fields of MogUpdateArgs), where src is a BGR24
+// frame's bytes or a covahip_mog_yuv_src
+template <class G, class K, class Src>
+int mog_launch_update(covahip_ctx *ctx, const char *scope, K kernel, const uint8_t *frames, const Src &src, const MogUpdateArgs &a) {
+    return mog_launch(ctx, scope, kernel, dim3(G::NPIX / mogdev::UPD_BLOCK, a.S), mogdev::UPD_BLOCK, 0, frames, src, a.state, a.par,
+                      a.nvalid, a.f0, a.nf, a.S, a.Tb, a.bits);
+}
+
 // The macroblock grid's kernels at working width `mw` (960 or 320; 640 runs mog.hip's own).  Pointers are device memory, the
 // layouts those of the kernels above; the launches go to ctx->stream and return without waiting.
-struct covahip_ctx;
-int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
-                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
+int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           uint8_t *labels, const int32_t *nvalid, int S, size_t FS);
 // The banded kernels (mog_band.hip) at working width `mw`: 1280 and 1920, whose planes do not fit LDS, and 960 (the post
 // kernel only, for comparison with the resident one).  plane: one more plane per (frame, stream), FS * NWORD words, for the
-// mask after the morphology; rows: the band height, 16 .. working height, with 2 x min(rows + 16, height) staged rows, the
-// flags and the column sweep's carries within COVAHIP_MOG_BAND_LDS_MAX (else COVAHIP_ERR_UNSUPPORTED).
+// mask after the morphology; rows: the band height, 16 .. working height, with mogdev::band_lds_bytes within
+// COVAHIP_MOG_BAND_LDS_MAX (else COVAHIP_ERR_UNSUPPORTED).
 constexpr size_t COVAHIP_MOG_BAND_LDS_MAX = 160 * 1024 - 64;
-int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
-                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits);
+int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);
 // The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries.  A surface as a kernel sees it: plane
@@ -617,7 +659,6 @@ struct covahip_mog_yuv_src {
     long long off[3], pitch[3], frame_stride, stream_stride;
     int ysub, ymul, bu, gv, gu, rv;
 };
-// kind: the reference grid's source kind (0 copy, 1 the 2x2 mean, 2 centre pick) or -1 = the half-size load at working width mw
-int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int kind, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
-                           uint8_t *state, const float2 *par, const int32_t *nvalid, int f0, int nf, int S, float Tb,
-                           unsigned long long *bits);
+// load: MOG_LOAD_* of the labeller's row (copy and centre pick exist at working width 640 only)
+int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int load, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
+                           const MogUpdateArgs &a);

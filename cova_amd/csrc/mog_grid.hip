@@ -17,10 +17,6 @@
 
 #include <hip/hip_runtime.h>
 
-#include <mutex>
-#include <utility>
-#include <vector>
-
 #include "covahip.h"
 #include "internal.h"
 #include "mog_dev.h"
@@ -36,11 +32,6 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__
                                                                const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
                                                                unsigned long long *__restrict__ bits) {
     update_body<Geom<MW, MH>>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-}
-
-template <class G>
-constexpr size_t post_lds() {
-    return (size_t)2 * G::NWORD * 8 + 16;      // the two planes and the `changed` word
 }
 
 // bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout; labels [F][S][LH][LW]
@@ -64,65 +55,28 @@ __global__ __launch_bounds__(BLOCK) void k_mog_grid_post(const unsigned long lon
     unsigned long long *dst = filled_bits + (size_t)fs * NWORD;
     uint8_t *lab = labels + (size_t)fs * NLAB;
     for (int i = tid; i < NWORD; i += BLOCK) dst[i] = ~T[i];
-    for (int i = tid; i < NLAB; i += BLOCK) {
-        const int r = i / LW, c = i % LW;              // label (r, c) = filled pixel (8 c, 8 r); 8 r < MH by Geom's assert
-        lab[i] = (uint8_t)((~T[8 * r * ROWW + c / 8] >> (8 * (c % 8))) & 1ull);
-    }
-}
-
-// workgroup sizes of the post kernel (the results do not depend on them): at 960x540 one workgroup owns the CU
-constexpr int POST_BLOCK_960 = 512, POST_BLOCK_320 = 256;
-
-template <typename K>
-int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return COVAHIP_OK;
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> opened;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto &o : opened)
-        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
-    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    opened.emplace_back(ctx->device, fn);
-    return COVAHIP_OK;
-}
-
-template <int MW, int MH, int BLOCK>
-int launch_post(covahip_ctx *ctx, const unsigned long long *bits, unsigned long long *filled_bits, uint8_t *labels,
-                const int32_t *nvalid, int S, size_t FS) {
-    constexpr size_t lds = post_lds<Geom<MW, MH>>();
-    static_assert(lds <= 160 * 1024 - 64, "the two planes must fit a CU's LDS");
-    if (int rc = open_lds(ctx, k_mog_grid_post<MW, MH, BLOCK>, lds)) return rc;
-    {
-        ProfScope ps(ctx, "mog_post");
-        k_mog_grid_post<MW, MH, BLOCK><<<dim3((unsigned)FS), BLOCK, lds, ctx->stream>>>(bits, filled_bits, labels, nvalid, S);
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
+    for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(T, i / LW, i % LW, ROWW);
 }
 
 }  // namespace
 
-int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, uint8_t *state, const float2 *par,
-                            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits) {
-    {
-        ProfScope ps(ctx, "mog_update");
-        if (mw == 960)
-            k_mog_grid_update<960, 540><<<dim3(Geom<960, 540>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
-                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (mw == 320)
-            k_mog_grid_update<320, 180><<<dim3(Geom<320, 180>::NPIX / UPD_BLOCK, S), UPD_BLOCK, 0, ctx->stream>>>(
-                frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-        else
-            return COVAHIP_ERR_UNSUPPORTED;
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
+int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a) {
+    return with_geom<G960, G320>(mw, [&](auto g) {
+        using G = decltype(g);
+        return mog_launch_update<G>(ctx, "mog_update", k_mog_grid_update<G::MW, G::MH>, frames, src_bytes, a);
+    });
 }
 
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           uint8_t *labels, const int32_t *nvalid, int S, size_t FS) {
-    if (mw == 960) return launch_post<960, 540, POST_BLOCK_960>(ctx, bits, filled_bits, labels, nvalid, S, FS);
-    if (mw == 320) return launch_post<320, 180, POST_BLOCK_320>(ctx, bits, filled_bits, labels, nvalid, S, FS);
-    return COVAHIP_ERR_UNSUPPORTED;
+    return with_geom<G960, G320>(mw, [&](auto g) -> int {
+        using G = decltype(g);
+        constexpr int BLOCK = G::MW == 960 ? 512 : 256;    // (the results do not depend on it) at 960x540 one workgroup owns the CU
+        constexpr size_t lds = (size_t)2 * G::NWORD * 8 + 16;   // the two planes and the `changed` word
+        static_assert(lds <= 160 * 1024 - 64, "the two planes must fit a CU's LDS");
+        if (int rc = open_lds(ctx, k_mog_grid_post<G::MW, G::MH, BLOCK>, lds)) return rc;
+        return mog_launch(ctx, "mog_post", k_mog_grid_post<G::MW, G::MH, BLOCK>, dim3((unsigned)FS), BLOCK, lds, bits, filled_bits, labels,
+                          nvalid, S);
+    });
 }
+

@@ -3,8 +3,9 @@
 // states the conversion).  Everything behind the working pixel is the device code of mog_dev.h, the same as for BGR24 frames:
 // mog2_pixel, the ballot word, the model's layout; the post kernels are those of mog.hip, mog_grid.hip and mog_band.hip.
 //
-//   k_mog_yuv_update<G, FMT, KIND>  update_body_strided with LoadYuv: one lane per working pixel and stream, a wave owns 64
-//                                   consecutive x of one row.  KIND is how the working pixel comes from the source:
+//   k_mog_yuv_update<G, FMT, KIND>  update_body_strided (the one update body; LoadYuv::WAIT makes it wait once before its
+//                                   loop) with LoadYuv: one lane per working pixel and stream, a wave owns 64 consecutive x
+//                                   of one row.  KIND is how the working pixel comes from the source:
 //     HALF  (the macroblock grid's half sizes and 1280x720 on either grid) a 16-bit word at byte 2x of Y rows 2y and 2y + 1 and,
 //           NV12, a 16-bit word at byte 2x of UV row y: three loads of 128 contiguous bytes per wave.  I420 loads one byte each
 //           of U and V at x of row y.  The four pixels of the 2x2 block share the chroma sample; each is converted, then the
@@ -34,6 +35,7 @@ __device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 :
 
 template <int FMT, int KIND>
 struct LoadYuv {
+    static constexpr bool WAIT = true;         // the body waits for the model and the first frame once, before its loop
     covahip_mog_yuv_src a;
     struct At { long long y, u, v; };          // bytes from the plane's first byte: Y sample(s), U (NV12: the UV pair), V
     struct Raw { unsigned y0, y1, u, v; };     // HALF: two Y pairs; else y0 = Y.  NV12: u = the UV pair as loaded
@@ -116,41 +118,24 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_yuv_update(const uint8_t *__r
                                       nf, S, Tb, bits);
 }
 
-template <int MW, int MH, int KIND>
-void launch(covahip_ctx *ctx, int format, const uint8_t *frames, const covahip_mog_yuv_src &src, uint8_t *state, const float2 *par,
-            const int32_t *nvalid, int f0, int nf, int S, float Tb, unsigned long long *bits) {
-    const dim3 grid(Geom<MW, MH>::NPIX / UPD_BLOCK, S);
-    if (format == NV12)
-        k_mog_yuv_update<MW, MH, NV12, KIND><<<grid, UPD_BLOCK, 0, ctx->stream>>>(frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-    else
-        k_mog_yuv_update<MW, MH, I420, KIND><<<grid, UPD_BLOCK, 0, ctx->stream>>>(frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
+template <class G, int KIND>
+int launch(covahip_ctx *ctx, int format, const uint8_t *frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
+    const auto kernel = format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND> : k_mog_yuv_update<G::MW, G::MH, I420, KIND>;
+    return mog_launch_update<G>(ctx, "mog_yuv_update", kernel, frames, src, a);
 }
 
 }  // namespace
 
-int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int kind, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
-                           uint8_t *state, const float2 *par, const int32_t *nvalid, int f0, int nf, int S, float Tb,
-                           unsigned long long *bits) {
+int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int load, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
+                           const MogUpdateArgs &a) {
     if (format != NV12 && format != I420) return COVAHIP_ERR_INVALID_ARG;
-    {
-        ProfScope ps(ctx, "mog_yuv_update");
-        if (kind == 0)
-            launch<640, 360, COPY>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == 1)
-            launch<640, 360, HALF>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == 2)
-            launch<640, 360, PICK>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == -1 && mw == 320)
-            launch<320, 180, HALF>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == -1 && mw == 960)
-            launch<960, 540, HALF>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == -1 && mw == 1280)
-            launch<1280, 720, HALF>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else if (kind == -1 && mw == 1920)
-            launch<1920, 1080, HALF>(ctx, format, frames, src, state, par, nvalid, f0, nf, S, Tb, bits);
-        else
-            return COVAHIP_ERR_UNSUPPORTED;
-    }
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
-    return COVAHIP_OK;
+    return with_geom<G640, G320, G960, G1280, G1920>(mw, [&](auto g) -> int {
+        using G = decltype(g);
+        if (load == MOG_LOAD_HALF) return launch<G, HALF>(ctx, format, frames, src, a);
+        if constexpr (G::MW == 640) {          // copy and centre pick exist at the reference grid's working size only
+            if (load == MOG_LOAD_COPY) return launch<G, COPY>(ctx, format, frames, src, a);
+            if (load == MOG_LOAD_PICK) return launch<G, PICK>(ctx, format, frames, src, a);
+        }
+        return COVAHIP_ERR_UNSUPPORTED;
+    });
 }
