@@ -26,7 +26,6 @@
 //     roots are compacted in ascending id order with a workgroup prefix sum.
 #include <algorithm>
 #include <cstdint>
-#include <mutex>
 #include <vector>
 
 #include "bboxcc_body.h"
@@ -147,19 +146,8 @@ __global__ __launch_bounds__(WV_WAVES * 64, LIST ? 1 : 8) void bboxcc_wave_kerne
     }
 }
 
-template <typename K>
-int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return COVAHIP_OK;
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> opened;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto &o : opened)
-        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
-    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64));
-    opened.emplace_back(ctx->device, fn);
-    return COVAHIP_OK;
-}
+// what these kernels' dynamic LDS is opened to when a launch needs more than the default 64 KB (covahip_open_lds)
+constexpr size_t CC_LDS_LIMIT = 160 * 1024 - 64;
 
 }  // namespace
 
@@ -250,9 +238,9 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
         // (nothing known yet: it runs); whatever overflows is picked up by the workgroup kernel below either way
         const bool second_now = second && !(ln.cc_stat && ln.cc_stat[5] > 0 && ln.cc_stat[0] == 0);
         const size_t wlds = (size_t)WV_WAVES * wg.wave_bytes;
-        int rc = open_lds(ctx, bboxcc_wave_kernel<false>, wlds);
+        int rc = covahip_open_lds(ctx, bboxcc_wave_kernel<false>, wlds, CC_LDS_LIMIT);
         if (rc) return rc;
-        if (second) rc = open_lds(ctx, bboxcc_wave_kernel<true>, (size_t)WV_WAVES * wg2.wave_bytes);
+        if (second) rc = covahip_open_lds(ctx, bboxcc_wave_kernel<true>, (size_t)WV_WAVES * wg2.wave_bytes, CC_LDS_LIMIT);
         if (rc) return rc;
         {
             ProfScope ps(ctx, "bboxcc_wave_kernel");
@@ -274,7 +262,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
         }
         if (can_overflow) {
             // the workgroup kernel over what is left (exits at once when the list is empty); it also exports the call's counters
-            rc = open_lds(ctx, bboxcc_kernel, lds_wg);
+            rc = covahip_open_lds(ctx, bboxcc_kernel, lds_wg, CC_LDS_LIMIT);
             if (rc) return rc;
             int32_t *stat_dev = nullptr;
             COVAHIP_CHECK_HIP(ctx, hipHostGetDevicePointer((void **)&stat_dev, ln.cc_stat_ring, 0));
@@ -309,7 +297,7 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
         COVAHIP_CHECK_HIP(ctx, hipGetLastError());
         return COVAHIP_OK;
     }
-    int rc = open_lds(ctx, bboxcc_kernel, lds_wg);
+    int rc = covahip_open_lds(ctx, bboxcc_kernel, lds_wg, CC_LDS_LIMIT);
     if (rc) return rc;
     ProfScope ps(ctx, "bboxcc_kernel");
     hipLaunchKernelGGL(bboxcc_kernel, dim3(batch), dim3(CC_THREADS), lds_wg, ctx->stream, d_mask, g, wfull, area_thresh,
@@ -353,23 +341,9 @@ static int bboxcc_any(covahip_ctx *ctx, const uint8_t *mask, int batch, int h, i
     // the thresholds are read during the call: into a pinned copy of the ctx (free again once the upload before it is done), from
     // there to the device on the primary stream, in front of the kernels
     const int32_t *d_area = nullptr;
-    if (area_v) {
-        const size_t bytes = (size_t)batch * sizeof(int32_t);
-        if (ctx->cc_area_ev) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ctx->cc_area_ev));
-        if (bytes > ctx->cc_area_bytes) {
-            COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // kernels of an earlier call may still read the device copy
-            if (ctx->cc_area_dev) hipFree(ctx->cc_area_dev);
-            if (ctx->cc_area_host) hipHostFree(ctx->cc_area_host);
-            ctx->cc_area_dev = nullptr; ctx->cc_area_host = nullptr; ctx->cc_area_bytes = 0;
-            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ctx->cc_area_dev, bytes));
-            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ctx->cc_area_host, bytes, hipHostMallocDefault));
-            ctx->cc_area_bytes = bytes;
-            if (!ctx->cc_area_ev) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ctx->cc_area_ev, hipEventDisableTiming));
-        }
-        std::copy(area_v, area_v + batch, ctx->cc_area_host);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->cc_area_dev, ctx->cc_area_host, bytes, hipMemcpyHostToDevice, ctx->stream));
-        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ctx->cc_area_ev, ctx->stream));
-        d_area = ctx->cc_area_dev;
+    if (area_v) {   // (the one table that grows: a stand-alone call has no max_batch)
+        if (int rc = ctx->cc_area.reserve(ctx, (size_t)batch)) return rc;
+        if (int rc = ctx->cc_area.upload(ctx, area_v, (size_t)batch, &d_area)) return rc;
     }
     if (mem_kind == COVAHIP_MEM_DEVICE)
         return covahip_bboxcc_launch(ctx, mask, batch, h, w, area_thresh, boxes, counts, max_boxes, d_area);

@@ -70,7 +70,7 @@ inline size_t cc_plan_global(int h, int w, CcGeom &g) {
     const size_t fits = cc_plan(h, w, g);
     if (fits) return fits;
     if (g.BW > 128) return 0;
-    return (((size_t)g.wt_off + 64) + 255) & ~(size_t)255;
+    return align256((size_t)g.wt_off + 64);
 }
 
 // m: the frame's H x W mask bytes (HBM or LDS); smem: this frame's LDS region of cc_plan() bytes;

@@ -4,10 +4,9 @@
 
 #include <vector>
 
+#include "blobnet_params.h"
 #include "internal.h"
 
-constexpr int BN_T = 4;       // timestep the network is built for (utils/train-blobnet.py:58)
-constexpr int BN_LEVELS = 4;
 constexpr int BN_KTAB_STACKS = 256;   // stacks whose table (16-bit frame indices, 2 KB) travels in enc1_mfma's kernel arguments
 
 struct BnLevelGeom {
@@ -27,35 +26,21 @@ struct BnWorkspace {
     // the level-0 skip connection's share of the logits (round 5): fp32 [B][H_1 + 1][W_1 + 1][4], written by the level-1 kernel, added by the last
     // decoder block -- the skip tensor itself (act[1]) is then neither written nor read
     float *part = nullptr;
-    // stack -> frame index table of the call in flight
-    int32_t *d_index = nullptr;
-    int32_t *h_index = nullptr;       // pinned host copy it is uploaded from
-    size_t index_ints = 0;            // capacity of both
-    hipEvent_t ev_index = nullptr;    // upload of h_index done (the next call may overwrite it)
-    std::vector<int32_t> last_table;  // the table that is resident in d_index (an unchanged table is not uploaded again)
-    int last_n_frames = 0;
-    // model ids of a mixed batch (model sets): u8 [batch] per stack, then u8 [n_frames] per carrier frame
-    uint8_t *d_models = nullptr;
-    uint8_t *h_models = nullptr;      // pinned host copy it is uploaded from
-    size_t models_cap = 0;            // capacity of both
-    hipEvent_t ev_models = nullptr;   // upload of h_models done
-    std::vector<uint8_t> last_models; // the ids resident in d_models (unchanged ids are not uploaded again)
+    // The lane's small tables (internal.h, ResidentTable), each reserved once, on first use, for max_batch:
+    ResidentTable<int32_t> index;     // stack -> frame table of a carrier-frame call, i32 [batch][4]; 4 * max_batch ints
+    int index_frames = 0;             // n_frames of the call `index` was uploaded for: part of what "resident" means there
+    std::vector<int32_t> kept_table;  // a table that travels BY VALUE (BnInput::h_index), alive until the launch has copied it
+    ResidentTable<uint8_t> models;    // model ids of a mixed batch: u8 [batch] per stack, then u8 [n_frames] per carrier frame; 5 * max_batch bytes
     // per-stack area thresholds of the stand-alone bboxcc behind a forward whose frame does not fit the fused tail
-    // (covahip_blobnet_set_area): i32 [batch], uploaded like the model ids
-    int32_t *d_areas = nullptr;
-    int32_t *h_areas = nullptr;       // pinned host copy it is uploaded from
-    size_t areas_cap = 0;             // capacity of both, in thresholds
-    hipEvent_t ev_areas = nullptr;    // upload of h_areas done
-    std::vector<int32_t> last_areas;  // the thresholds resident in d_areas (unchanged ones are not uploaded again)
+    // (covahip_blobnet_set_area): i32 [batch]; max_batch ints
+    ResidentTable<int32_t> areas;
 };
 
 struct covahip_blobnet {
     int H = 0, W = 0, max_batch = 0;
     int n_models = 1;   // models of the set; their prepared weights lie Prepared::total bytes apart from d_prepared on
     BnLevelGeom lv[BN_LEVELS + 1];
-    int enc_c[BN_LEVELS + 1] = {3, 16, 32, 64, 128};
-    int dec_ci[BN_LEVELS] = {128, 128, 64, 32};
-    int dec_co[BN_LEVELS] = {64, 32, 16, 16};
+    int enc_c[BN_LEVELS + 1], dec_ci[BN_LEVELS], dec_co[BN_LEVELS];   // blobnet_params.h's, copied by the constructor
     int dec_cy[BN_LEVELS], dec_cx[BN_LEVELS];  // crop offsets (top/left) per decoder block
     BnWorkspace ws[COVAHIP_MAX_LANES];
     // prepared (MFMA path) weights
@@ -82,6 +67,11 @@ struct covahip_blobnet {
     bool post_on = false;                         // some model has a non-default setting: the POST = true kernels run
     void *d_post = nullptr;
     size_t post_area_off = 0, post_keep_off = 0, post_planes_off = 0, post_keep_stride = 0, post_planes_stride = 0, post_bytes = 0;
+    covahip_blobnet() {
+        std::copy(BN_ENC_C, BN_ENC_C + BN_LEVELS + 1, enc_c);
+        std::copy(BN_DEC_CI, BN_DEC_CI + BN_LEVELS, dec_ci);
+        std::copy(BN_DEC_CO, BN_DEC_CO + BN_LEVELS, dec_co);
+    }
 };
 
 // Whether encoder level 1 runs on enc1_mfma (16x16x32 tiles, fixed LDS row: grids of at most BN_E1_MAXW level-1 pixels) or on

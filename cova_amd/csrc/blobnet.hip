@@ -13,13 +13,6 @@
 #include "blobnet.h"
 #include "covahip_dev.h"
 
-namespace {
-
-constexpr uint32_t W_MAGIC = 0x57485643;  // "CVHW"
-constexpr size_t N_PARAMS = 320305;
-
-}  // namespace
-
 static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
     if (!m) return;
     blobnet_release_mfma(ctx, m);
@@ -31,15 +24,9 @@ static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
             if (ws.dact[j]) hipFree(ws.dact[j]);
         if (ws.pbuf) hipFree(ws.pbuf);
         if (ws.part) hipFree(ws.part);
-        if (ws.d_index) hipFree(ws.d_index);
-        if (ws.h_index) hipHostFree(ws.h_index);
-        if (ws.ev_index) hipEventDestroy(ws.ev_index);
-        if (ws.d_models) hipFree(ws.d_models);
-        if (ws.h_models) hipHostFree(ws.h_models);
-        if (ws.ev_models) hipEventDestroy(ws.ev_models);
-        if (ws.d_areas) hipFree(ws.d_areas);
-        if (ws.h_areas) hipHostFree(ws.h_areas);
-        if (ws.ev_areas) hipEventDestroy(ws.ev_areas);
+        ws.index.release();
+        ws.models.release();
+        ws.areas.release();
     }
     delete m;
 }
@@ -98,29 +85,9 @@ static int resolve_models(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws,
             seen[f] = 1;
             fm = model_ids[b];
         }
-    if (!(ws.d_models && ids == ws.last_models)) {
-        if (ws.d_models) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ws.ev_models));   // the pinned copy is free again
-        if (ids.size() > ws.models_cap) {
-            if (ws.d_models) {
-                COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                hipFree(ws.d_models);
-                hipHostFree(ws.h_models);
-                ws.d_models = nullptr; ws.h_models = nullptr; ws.models_cap = 0;
-                ws.last_models.clear();
-            }
-            const size_t cap = std::max(ids.size(), (size_t)m->max_batch * (1 + BN_T));
-            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.d_models, cap));
-            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ws.h_models, cap, hipHostMallocDefault));
-            ws.models_cap = cap;
-            if (!ws.ev_models) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ws.ev_models, hipEventDisableTiming));
-        }
-        std::copy(ids.begin(), ids.end(), ws.h_models);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ws.d_models, ws.h_models, ids.size(), hipMemcpyHostToDevice, ctx->stream));
-        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ws.ev_models, ctx->stream));
-        ws.last_models = std::move(ids);
-    }
-    in.model_ids = ws.d_models;
-    in.frame_models = ws.d_models + batch;
+    if (int rc = ws.models.reserve(ctx, (size_t)m->max_batch * (1 + BN_T))) return rc;
+    if (int rc = ws.models.upload(ctx, ids.data(), ids.size(), &in.model_ids)) return rc;
+    in.frame_models = in.model_ids + batch;
     in.h_model_ids = model_ids;
     return COVAHIP_OK;
 }
@@ -137,29 +104,8 @@ static int resolve_areas(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         const int32_t a = m->post_area[in.h_model_ids ? in.h_model_ids[b] : in.model];
         eff[b] = a >= 1 ? a : area_thresh;
     }
-    if (!(ws.d_areas && eff == ws.last_areas)) {
-        if (ws.d_areas) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ws.ev_areas));   // the pinned copy is free again
-        if (eff.size() > ws.areas_cap) {
-            if (ws.d_areas) {
-                COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                hipFree(ws.d_areas);
-                hipHostFree(ws.h_areas);
-                ws.d_areas = nullptr; ws.h_areas = nullptr; ws.areas_cap = 0;
-                ws.last_areas.clear();
-            }
-            const size_t cap = std::max(eff.size(), (size_t)m->max_batch);
-            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.d_areas, cap * sizeof(int32_t)));
-            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ws.h_areas, cap * sizeof(int32_t), hipHostMallocDefault));
-            ws.areas_cap = cap;
-            if (!ws.ev_areas) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ws.ev_areas, hipEventDisableTiming));
-        }
-        std::copy(eff.begin(), eff.end(), ws.h_areas);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ws.d_areas, ws.h_areas, eff.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ws.ev_areas, ctx->stream));
-        ws.last_areas = std::move(eff);
-    }
-    *d_out = ws.d_areas;
-    return COVAHIP_OK;
+    if (int rc = ws.areas.reserve(ctx, (size_t)m->max_batch)) return rc;
+    return ws.areas.upload(ctx, eff.data(), eff.size(), d_out);
 }
 
 // BlobNet forward (+ optionally bboxcc) on device pointers, asynchronous on the ctx stream.
@@ -211,41 +157,17 @@ static int prepare_frames(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws,
     // small batches: the table travels in the level-1 kernel's arguments (blobnet_mfma.hip); the device copy below is for
     // larger ones and for the round-1..3 level-1 kernel
     const bool by_value = batch <= BN_KTAB_STACKS && n_frames <= 65535 && bn_level1_on_enc1(ctx, m);
-    if (by_value) {
-        ws.last_table = std::move(table);      // (kept alive until the launch has copied it)
-        ws.last_n_frames = -1;                 // the device table, if any, is stale
-        in.h_index = ws.last_table.data();
-        in.frames = d_frames;
-        in.n_frames = n_frames;
-        return ensure_pbuf(ctx, m, ws, n_frames);
-    }
-    const bool same = ws.d_index && table == ws.last_table && n_frames == ws.last_n_frames;
-    if (!same) {
-        const size_t need = table.size();
-        if (ws.d_index) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ws.ev_index));   // the pinned copy is free again
-        if (need > ws.index_ints) {
-            if (ws.d_index) {
-                COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                hipFree(ws.d_index);
-                hipHostFree(ws.h_index);
-                ws.d_index = nullptr; ws.h_index = nullptr; ws.index_ints = 0;
-                ws.last_table.clear();
-            }
-            const size_t cap = std::max(need, (size_t)m->max_batch * BN_T);
-            COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.d_index, cap * sizeof(int32_t)));
-            COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&ws.h_index, cap * sizeof(int32_t), hipHostMallocDefault));
-            ws.index_ints = cap;
-            if (!ws.ev_index) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ws.ev_index, hipEventDisableTiming));
-        }
-        std::copy(table.begin(), table.end(), ws.h_index);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ws.d_index, ws.h_index, need * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        COVAHIP_CHECK_HIP(ctx, hipEventRecord(ws.ev_index, ctx->stream));
-        ws.last_table = std::move(table);
-        ws.last_n_frames = n_frames;
-    }
     in.frames = d_frames;
     in.n_frames = n_frames;
-    in.index = ws.d_index;
+    if (by_value) {
+        ws.kept_table = std::move(table);
+        in.h_index = ws.kept_table.data();
+    } else {
+        if (n_frames != ws.index_frames) ws.index.invalidate();
+        if (int rc = ws.index.reserve(ctx, (size_t)m->max_batch * BN_T)) return rc;
+        if (int rc = ws.index.upload(ctx, table.data(), table.size(), &in.index)) return rc;
+        ws.index_frames = n_frames;
+    }
     return ensure_pbuf(ctx, m, ws, n_frames);
 }
 
@@ -356,22 +278,10 @@ static int build_model(covahip_ctx *ctx, covahip_blobnet *m, const float *const 
 
 extern "C" {
 
-// A CVHW blob's header and size; the parameters behind the 64-byte header.
-static const float *check_blob(const void *weights, size_t weights_bytes) {
-    if (!weights || weights_bytes < 64) return nullptr;
-    uint32_t hdr[16];
-    std::memcpy(hdr, weights, 64);
-    static const uint32_t want[] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS};
-    for (int i = 0; i < 13; i++)
-        if (hdr[i] != want[i]) return nullptr;
-    if (weights_bytes != 64 + N_PARAMS * sizeof(float)) return nullptr;
-    return reinterpret_cast<const float *>(static_cast<const uint8_t *>(weights) + 64);
-}
-
 int covahip_blobnet_load(covahip_ctx *ctx, const void *weights, size_t weights_bytes, int h_mb, int w_mb, int t,
                          int max_batch) {
     if (!ctx || !weights) return COVAHIP_ERR_INVALID_ARG;
-    if (t == BN_T && h_mb >= 16 && w_mb >= 16 && h_mb <= 1024 && w_mb <= 1024 && max_batch > 0 && !check_blob(weights, weights_bytes))
+    if (t == BN_T && h_mb >= 16 && w_mb >= 16 && h_mb <= 1024 && w_mb <= 1024 && max_batch > 0 && !bn_check_blob(weights, weights_bytes))
         return COVAHIP_ERR_BAD_WEIGHTS;   // a bad blob alone leaves the model loaded before in place
     return covahip_blobnet_load_set(ctx, 1, &weights, &weights_bytes, h_mb, w_mb, t, max_batch);
 }
@@ -386,7 +296,7 @@ int covahip_blobnet_load_set(covahip_ctx *ctx, int n_models, const void *const *
     if (h_mb < 16 || w_mb < 16 || h_mb > 1024 || w_mb > 1024) return COVAHIP_ERR_UNSUPPORTED;
     std::vector<const float *> h_w(n_models);
     bool bad = false;
-    for (int k = 0; k < n_models; k++) bad = bad || !(h_w[k] = check_blob(weights[k], weights_bytes[k]));
+    for (int k = 0; k < n_models; k++) bad = bad || !(h_w[k] = bn_check_blob(weights[k], weights_bytes[k]));
 
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     covahip_blobnet_destroy(ctx);
@@ -421,13 +331,12 @@ int covahip_blobnet_num_models(covahip_ctx *ctx, int *n_models) {
 // dec3cc_rows_mfma ballots its logits into.  That kernel takes rows of at most 128 pixels; the planes of a wider grid are not read.
 static int upload_post(covahip_ctx *ctx, covahip_blobnet *m) {
     const size_t hw = (size_t)m->H * m->W, n = (size_t)m->n_models;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (!m->d_post) {
         m->post_keep_stride = (hw + 15) & ~(size_t)15;
         m->post_planes_stride = (size_t)m->H * 16;
         m->post_area_off = n * sizeof(float);
-        m->post_keep_off = al(m->post_area_off + n * sizeof(int32_t));
-        m->post_planes_off = al(m->post_keep_off + n * m->post_keep_stride);
+        m->post_keep_off = align256(m->post_area_off + n * sizeof(int32_t));
+        m->post_planes_off = align256(m->post_keep_off + n * m->post_keep_stride);
         m->post_bytes = m->post_planes_off + n * m->post_planes_stride;
         COVAHIP_CHECK_HIP(ctx, hipMalloc(&m->d_post, m->post_bytes));
     }
@@ -596,7 +505,6 @@ static int filter_any(covahip_ctx *ctx, const uint8_t *src, int n_frames, const 
     const size_t logit_bytes = mask_bytes * sizeof(float);
     const size_t box_bytes = (size_t)batch * max_boxes * sizeof(covahip_box);
     const size_t cnt_bytes = (size_t)batch * sizeof(int32_t);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (mem_kind != COVAHIP_MEM_DEVICE && mem_kind != COVAHIP_MEM_HOST) return COVAHIP_ERR_INVALID_ARG;
 
     // device pointers: the call goes to the next lane (internal.h, CtxLane) and overlaps the calls before it; host pointers:
@@ -611,13 +519,13 @@ static int filter_any(covahip_ctx *ctx, const uint8_t *src, int n_frames, const 
     int rc = covahip_ensure_buffer(ctx, &ctx->stage_in, &ctx->stage_in_bytes, in_bytes);
     if (rc) return rc;
     rc = covahip_ensure_buffer(ctx, &ctx->stage_out, &ctx->stage_out_bytes,
-                               al(mask_bytes) + al(logit_bytes) + al(box_bytes) + al(cnt_bytes));
+                               align256(mask_bytes) + align256(logit_bytes) + align256(box_bytes) + align256(cnt_bytes));
     if (rc) return rc;
     uint8_t *base = (uint8_t *)ctx->stage_out;
     uint8_t *d_mask = base;
-    float *d_logits = logits ? (float *)(base + al(mask_bytes)) : nullptr;
-    covahip_box *d_boxes = (covahip_box *)(base + al(mask_bytes) + al(logit_bytes));
-    int32_t *d_counts = (int32_t *)(base + al(mask_bytes) + al(logit_bytes) + al(box_bytes));
+    float *d_logits = logits ? (float *)(base + align256(mask_bytes)) : nullptr;
+    covahip_box *d_boxes = (covahip_box *)(base + align256(mask_bytes) + align256(logit_bytes));
+    int32_t *d_counts = (int32_t *)(base + align256(mask_bytes) + align256(logit_bytes) + align256(box_bytes));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->stage_in, src, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     d_src = (const uint8_t *)ctx->stage_in;
     rc = filter_placed(ctx, m, d_src, n_frames, stack_index, batch, area_thresh, d_boxes, d_counts, max_boxes, d_logits, d_mask, false,
@@ -806,13 +714,12 @@ int covahip_blobnet_forward_m(covahip_ctx *ctx, const uint8_t *rgba_stack, const
     const size_t in_bytes = (size_t)batch * BN_T * hw * 4;
     const size_t mask_bytes = (size_t)batch * hw;
     const size_t logit_bytes = mask_bytes * sizeof(float);
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     int rc = covahip_ensure_buffer(ctx, &ctx->stage_in, &ctx->stage_in_bytes, in_bytes);
     if (rc) return rc;
-    rc = covahip_ensure_buffer(ctx, &ctx->stage_out, &ctx->stage_out_bytes, al(mask_bytes) + al(logit_bytes));
+    rc = covahip_ensure_buffer(ctx, &ctx->stage_out, &ctx->stage_out_bytes, align256(mask_bytes) + align256(logit_bytes));
     if (rc) return rc;
     uint8_t *d_mask = (uint8_t *)ctx->stage_out;
-    float *d_logits = (float *)((uint8_t *)ctx->stage_out + al(mask_bytes));
+    float *d_logits = (float *)((uint8_t *)ctx->stage_out + align256(mask_bytes));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(ctx->stage_in, rgba_stack, in_bytes, hipMemcpyHostToDevice, ctx->stream));
     rc = covahip_blobnet_forward_dev(ctx, (const uint8_t *)ctx->stage_in, batch, logits ? d_logits : nullptr,
                                      mask ? d_mask : nullptr, model_ids);

@@ -2817,24 +2817,10 @@ ItemPlan make_plan(int grid, int num_cu, int wgs_per_cu, int batch, int nbands, 
     return pl;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// Raises a kernel's dynamic-LDS limit once per (device, kernel): the attribute is sticky, so every kernel
-// is opened up to the 160 KB a CU has (minus the 256 B the runtime keeps) the first time it needs more
-// than the default 64 KB.
-std::mutex g_host_mutex;   // guards the cache below
-template <typename K>
-int set_lds(covahip_ctx *ctx, K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return COVAHIP_OK;
-    static std::vector<std::pair<int, const void *>> opened;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(g_host_mutex);
-    for (auto &o : opened)
-        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
-    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 256));
-    opened.emplace_back(ctx->device, fn);
-    return COVAHIP_OK;
-}
+// What every kernel here that needs more than the default 64 KB of dynamic LDS is opened to (covahip_open_lds): the 160 KB a CU
+// has, minus the 256 B the runtime keeps.
+constexpr size_t LDS_LIMIT = 160 * 1024 - 256;
 
 // Run-time bools as template arguments: with_bools(f, b0, b1, ..) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ..)
 // and returns its code, so that a generic lambda names a kernel family once and instantiates one kernel per combination of
@@ -2870,36 +2856,8 @@ int plan_bands(int Hp, int batch, long long slots, Fit fits) {
 }  // namespace
 
 int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *const *ws, int n_models) {
-    // host view of the parameter blob (same order as bind_params in blobnet.hip)
-    struct HE { const float *k, *b, *gamma, *beta, *mean, *var, *w1, *w2; } he[BN_LEVELS];
-    struct HD { const float *k, *b, *gamma, *beta, *mean, *var; } hd[BN_LEVELS];
-    const float *fk = nullptr, *fb = nullptr;
-    auto view = [&](const float *w) {
-        const float *p = w;
-        for (int i = 0; i < BN_LEVELS; i++) {
-            const int ci = m->enc_c[i], co = m->enc_c[i + 1];
-            he[i].k = p; p += 9 * ci * co;
-            he[i].b = p; p += co;
-            he[i].gamma = p; p += co;
-            he[i].beta = p; p += co;
-            he[i].mean = p; p += co;
-            he[i].var = p; p += co;
-            he[i].w1 = p; p += 16;
-            he[i].w2 = p; p += 16;
-        }
-        for (int j = 0; j < BN_LEVELS; j++) {
-            const int ci = m->dec_ci[j], co = m->dec_co[j];
-            hd[j].k = p; p += 16 * ci * co;
-            hd[j].b = p; p += co;
-            if (j < BN_LEVELS - 1) {
-                hd[j].gamma = p; p += co;
-                hd[j].beta = p; p += co;
-                hd[j].mean = p; p += co;
-                hd[j].var = p; p += co;
-            }
-        }
-        fk = p; fb = p + 16;
-    };
+    const BnEncOff *const he = BN_LAYOUT.enc;   // where the tensors lie in a model's parameters (blobnet_params.h)
+    const BnDecOff *const hd = BN_LAYOUT.dec;
 
     Prepared *pr = new Prepared();
     size_t off = 0;
@@ -2926,31 +2884,29 @@ int blobnet_prepare_mfma(covahip_ctx *ctx, covahip_blobnet *m, const float *cons
     // the K models lie `off` bytes apart; allpos (which kernel template and which epilogue form) is shared by the set
     std::vector<uint8_t> host_all(off * (size_t)n_models, 0);
     for (int i = 0; i < BN_LEVELS; i++) pr->allpos[i] = true;
-    for (int k = 0; k < n_models; k++) {
-        view(ws[k]);
+    for (int k = 0; k < n_models; k++)
         for (int i = 0; i < BN_LEVELS; i++)
-            for (int c = 0; c < m->enc_c[i + 1]; c++) pr->allpos[i] = pr->allpos[i] && he[i].gamma[c] >= 0.f;
-    }
+            for (int c = 0; c < m->enc_c[i + 1]; c++) pr->allpos[i] = pr->allpos[i] && ws[k][he[i].gamma + c] >= 0.f;
     for (int k = 0; k < n_models; k++) {
-        view(ws[k]);
+        const float *const w = ws[k], *const fk = w + BN_LAYOUT.fk, *const fb = w + BN_LAYOUT.fb;
         uint8_t *const host = host_all.data() + (size_t)k * off;
-        prep_enc0(pr->allpos[0], he[0].k, he[0].b, he[0].gamma, he[0].beta, he[0].mean, he[0].var, he[0].w1, he[0].w2,
-                  (_Float16 *)(host + pr->enc[0].wfrag), (float *)(host + pr->enc[0].epi));
+        prep_enc0(pr->allpos[0], w + he[0].k, w + he[0].b, w + he[0].gamma, w + he[0].beta, w + he[0].mean, w + he[0].var, w + he[0].w1,
+                  w + he[0].w2, (_Float16 *)(host + pr->enc[0].wfrag), (float *)(host + pr->enc[0].epi));
         for (int i = 1; i < BN_LEVELS; i++)
-            prep_enc(pr->allpos[i], m->enc_c[i], m->enc_c[i + 1], he[i].k, he[i].b, he[i].gamma, he[i].beta, he[i].mean, he[i].var,
-                     he[i].w1, he[i].w2, (_Float16 *)(host + pr->enc[i].wfrag),
+            prep_enc(pr->allpos[i], m->enc_c[i], m->enc_c[i + 1], w + he[i].k, w + he[i].b, w + he[i].gamma, w + he[i].beta, w + he[i].mean,
+                     w + he[i].var, w + he[i].w1, w + he[i].w2, (_Float16 *)(host + pr->enc[i].wfrag),
                      (float *)(host + pr->enc[i].epi));
         if (m->enc_c[1] == 16 && m->enc_c[2] == 32)
-            prep_enc1w(pr->allpos[1], he[1].k, he[1].b, he[1].gamma, he[1].beta, he[1].mean, he[1].var,
+            prep_enc1w(pr->allpos[1], w + he[1].k, w + he[1].b, w + he[1].gamma, w + he[1].beta, w + he[1].mean, w + he[1].var,
                        (_Float16 *)(host + pr->enc1w));
         for (int j = 0; j < BN_LEVELS - 1; j++)
-            prep_dec(m->dec_ci[j], m->dec_co[j], hd[j].k, hd[j].b, hd[j].gamma, hd[j].beta, hd[j].mean, hd[j].var,
+            prep_dec(m->dec_ci[j], m->dec_co[j], w + hd[j].k, w + hd[j].b, w + hd[j].gamma, w + hd[j].beta, w + hd[j].mean, w + hd[j].var,
                      (_Float16 *)(host + pr->dec[j].wfrag), (float *)(host + pr->dec[j].epi));
-        prep_final(m->dec_ci[3], m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w),
+        prep_final(m->dec_ci[3], m->dec_co[3], w + hd[3].k, w + hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w),
                    (float *)(host + pr->final_epi));
         if (m->dec_ci[3] == 32) {   // the last block's input = concat(up 16, skip 16): decoder.py:122-134
-            prep_final(32, m->dec_co[3], hd[3].k, hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w_up), nullptr, 0, 16);
-            prep_tail(32, m->dec_co[3], hd[3].k, fk, 16, (_Float16 *)(host + pr->tail_w));
+            prep_final(32, m->dec_co[3], w + hd[3].k, w + hd[3].b, fk, fb, (_Float16 *)(host + pr->final_w_up), nullptr, 0, 16);
+            prep_tail(32, m->dec_co[3], w + hd[3].k, fk, 16, (_Float16 *)(host + pr->tail_w));
         }
     }
     m->prep = pr;   // (released with the model whatever happens below)
@@ -3002,13 +2958,13 @@ PostArg<POST> post_arg(const Fwd &f) {
     else return DecNoPost{};
 }
 
-// One launch: opens the kernel's dynamic-LDS limit (set_lds: nothing to do up to 64 KB), brackets the launch for the profile
-// as `name` and launches -- unless the pass is planning only, which goes through every check and still opens the limit (this
-// is how covahip_blobnet_load opens the kernels before the first forward).  Returns set_lds's code; the launch's own error
-// is launched()'s.
+// One launch: opens the kernel's dynamic-LDS limit (covahip_open_lds: nothing to do up to 64 KB), brackets the launch for the
+// profile as `name` and launches -- unless the pass is planning only, which goes through every check and still opens the limit
+// (this is how covahip_blobnet_load opens the kernels before the first forward).  Returns the opener's code; the launch's own
+// error is launched()'s.
 template <typename K, typename... A>
 int launch(const Fwd &f, const char *name, K kernel, int grid, int block, size_t lds, const A &...args) {
-    if (int rc = set_lds(f.ctx, kernel, lds)) return rc;
+    if (int rc = covahip_open_lds(f.ctx, kernel, lds, LDS_LIMIT)) return rc;
     ProfScope ps(f.ctx, name);
     if (!f.dry) hipLaunchKernelGGL(kernel, dim3(grid), dim3(block), lds, f.ctx->stream, args...);
     return COVAHIP_OK;
@@ -3232,7 +3188,7 @@ bool run_dec012(const Fwd &f, int &rc) {
         g.mRC = magic((in.W + 2) * (m->dec_ci[j] / 8));
         g.swz = choose_swz(false, m->dec_ci[j], in.W, 0, in.H + 1);
         g.tile_off = (int)off;
-        off += (((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2) + 255) & ~(size_t)255;   // 256: dec012_block's xor addressing
+        off += align256((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2);   // 256: dec012_block's xor addressing
         a.skip[j] = f.ws.act[BN_LEVELS - j];
         a.Ts[j] = j == 0 ? 1 : BN_T;
         a.wf[j] = (const half8 *)(f.prep + pr->dec[j].wfrag);

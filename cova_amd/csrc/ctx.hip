@@ -2,6 +2,7 @@
 // libcovahip.so (see include/covahip.h).
 #include <cstdio>
 #include <cstring>
+#include <mutex>
 
 #include "internal.h"
 
@@ -104,9 +105,7 @@ void covahip_ctx_destroy(covahip_ctx *ctx) {
     if (ctx->stage_out) hipFree(ctx->stage_out);
     if (ctx->sweep_buf) hipFree(ctx->sweep_buf);
     if (ctx->heat_buf) hipFree(ctx->heat_buf);
-    if (ctx->cc_area_dev) hipFree(ctx->cc_area_dev);
-    if (ctx->cc_area_host) hipHostFree(ctx->cc_area_host);
-    if (ctx->cc_area_ev) hipEventDestroy(ctx->cc_area_ev);
+    ctx->cc_area.release();
     for (CtxLane &l : ctx->lanes) {
         if (l.cc_scratch) hipFree(l.cc_scratch);
         if (l.cc_ovf) hipFree(l.cc_ovf);
@@ -418,5 +417,24 @@ int covahip_ensure_buffer(covahip_ctx *ctx, void **buf, size_t *cur, size_t need
     }
     COVAHIP_CHECK_HIP(ctx, hipMalloc(buf, need));
     *cur = need;
+    return COVAHIP_OK;
+}
+
+int covahip_open_lds(covahip_ctx *ctx, const void *fn, size_t lds, size_t limit) {
+    struct Opened {
+        int device;
+        const void *fn;
+        size_t limit;
+    };
+    static std::mutex mu;
+    static std::vector<Opened> opened;
+    std::lock_guard<std::mutex> lock(mu);
+    Opened *o = nullptr;
+    for (Opened &q : opened)
+        if (q.device == ctx->device && q.fn == fn) o = &q;
+    if (o && lds <= o->limit) return COVAHIP_OK;
+    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)limit));
+    if (o) o->limit = limit;
+    else opened.push_back({ctx->device, fn, limit});
     return COVAHIP_OK;
 }

@@ -113,8 +113,7 @@ int heat_launch(covahip_ctx *ctx, const float *d_logits, const uint8_t *d_gt, in
 extern "C" int covahip_post_heat_begin(covahip_ctx *ctx, const covahip_heat_cfg *cfg) {
     if (!ctx || !cfg || !cfg->logit_thresh) return COVAHIP_ERR_INVALID_ARG;
     if (cfg->h < 1 || cfg->w < 1 || cfg->n_thresh < 1 || cfg->n_thresh > HT_MAX_T) return COVAHIP_ERR_INVALID_ARG;
-    for (int t = 0; t < cfg->n_thresh; t++)
-        if (!std::isfinite(cfg->logit_thresh[t]) || (t && !(cfg->logit_thresh[t] > cfg->logit_thresh[t - 1]))) return COVAHIP_ERR_INVALID_ARG;
+    if (!covahip_thresholds_ok(cfg->logit_thresh, cfg->n_thresh)) return COVAHIP_ERR_INVALID_ARG;
     // a launch indexes macroblocks and tiles with 32 bits, and a grid's second dimension is at most 65,535 slices
     if ((int64_t)cfg->h * cfg->w > (int64_t)1 << 24) return COVAHIP_ERR_UNSUPPORTED;
 

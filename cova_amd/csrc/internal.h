@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
 #include <cstdint>
 #include <map>
 #include <string>
@@ -10,6 +12,38 @@
 #include "covahip.h"
 
 struct covahip_blobnet;  // blobnet.hip
+struct covahip_ctx;
+
+// x rounded up to the 256-byte step of sub-buffers carved from one allocation
+constexpr size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+// A list of mask thresholds as covahip_post_sweep and covahip_post_heat_begin take it: finite and strictly ascending.
+inline bool covahip_thresholds_ok(const float *v, int n) {
+    for (int t = 0; t < n; t++)
+        if (!std::isfinite(v[t]) || (t && !(v[t] > v[t - 1]))) return false;
+    return true;
+}
+
+// A small host table that kernels read from device memory: uploaded from a pinned copy on ctx->stream, and not at all while the
+// contents a call asks for are the resident ones.  One stream per table (a lane's, or the primary one).  The owner states the
+// capacity policy: reserve() is the only member that allocates, upload() refuses what does not fit.  (Members: below the ctx.)
+template <typename T>
+struct ResidentTable {
+    T *dev = nullptr;
+    T *pinned = nullptr;         // host copy the device copy is uploaded from
+    size_t cap = 0;              // capacity of both, in elements
+    hipEvent_t ev = nullptr;     // behind the last upload: once it has passed, the pinned copy is free again
+    bool recorded = false;       // `ev` was ever recorded
+    std::vector<T> resident;     // what `dev` holds; empty: nothing a call could ask for
+
+    // Room for n elements.  Storage that is replaced may still be read by kernels on ctx->stream: that stream is drained first,
+    // and nothing is resident afterwards.
+    int reserve(covahip_ctx *ctx, size_t n);
+    // src[0 .. n) on the device: *d_out = dev.  Resident contents cost no HIP call; n > cap is COVAHIP_ERR_INVALID_ARG.
+    int upload(covahip_ctx *ctx, const T *src, size_t n, const T **d_out);
+    void invalidate() { resident.clear(); }   // the next upload copies whatever it is given
+    void release();                           // frees everything (nothing in flight reads the device copy any more)
+};
 
 // Lanes: batches in flight on one GPU.  Every launch of the hot path has a fixed cost (weights into registers, the first
 // band's DMA, the slowest workgroup's tail) during which most of the chip idles; at b = 256 that is a third of a step.
@@ -48,13 +82,7 @@ struct CtxLane {
 };
 
 // covahip_monitor_* (monitor.hip): the open serving monitor of a ctx.  Everything a counted batch touches is allocated by begin.
-struct MonTable {                    // order / slice table of a mixed batch too large for the kernel arguments
-    int32_t *d_tab = nullptr;
-    int32_t *h_tab = nullptr;        // pinned host copy it is uploaded from
-    size_t cap = 0;                  // capacity of both, in ints
-    hipEvent_t ev = nullptr;         // upload of h_tab done (the next call may overwrite it)
-    std::vector<int32_t> last;       // the table resident in d_tab (an unchanged table is not uploaded again)
-};
+using MonTable = ResidentTable<int32_t>;   // order / slice table of a mixed batch too large for the kernel arguments; reserved by begin
 struct CovahipMonitor {
     int h = 0, w = 0, n_models = 0, max_boxes = 0, every = 1;
     bool attached = false;
@@ -98,10 +126,7 @@ struct covahip_ctx {
     size_t pinned_bytes = 0;
     void *sweep_buf = nullptr;   // covahip_post_sweep: accumulators, keep map, one chunk's mask frames, boxes and counts
     size_t sweep_bytes = 0;
-    // covahip_bboxcc_v: the call's per-frame area thresholds, pinned host copy -> device copy on the primary stream
-    int32_t *cc_area_host = nullptr, *cc_area_dev = nullptr;
-    size_t cc_area_bytes = 0;
-    hipEvent_t cc_area_ev = nullptr;   // upload done: the pinned copy is free again
+    ResidentTable<int32_t> cc_area;   // covahip_bboxcc_v: the call's per-frame area thresholds, on the primary stream; grows to the batch
     int cc_wave_cap = 0;       // bboxcc wave kernel: developer override of its run capacity
     int tail_form = 0;         // which kernel ran the last decoder block of the last forward (covahip_dev_blobnet_tail_form)
     CtxLane &lane() { return lanes[cur_lane]; }
@@ -130,6 +155,56 @@ struct covahip_ctx {
             return COVAHIP_ERR_HIP;                                                         \
         }                                                                                   \
     } while (0)
+
+template <typename T>
+int ResidentTable<T>::reserve(covahip_ctx *ctx, size_t n) {
+    if (n <= cap) return COVAHIP_OK;
+    if (dev || pinned) {
+        COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        hipFree(dev);
+        hipHostFree(pinned);
+        dev = pinned = nullptr;
+        cap = 0;
+        resident.clear();
+    }
+    if (!ev) COVAHIP_CHECK_HIP(ctx, hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+    COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&dev, n * sizeof(T)));
+    COVAHIP_CHECK_HIP(ctx, hipHostMalloc((void **)&pinned, n * sizeof(T), hipHostMallocDefault));
+    cap = n;
+    return COVAHIP_OK;
+}
+
+template <typename T>
+int ResidentTable<T>::upload(covahip_ctx *ctx, const T *src, size_t n, const T **d_out) {
+    *d_out = dev;
+    if (n > cap) return COVAHIP_ERR_INVALID_ARG;
+    if (n && resident.size() == n && std::equal(src, src + n, resident.begin())) return COVAHIP_OK;
+    if (recorded) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(ev));   // the pinned copy is free again
+    std::copy(src, src + n, pinned);
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(dev, pinned, n * sizeof(T), hipMemcpyHostToDevice, ctx->stream));
+    resident.clear();   // (should the record fail, the device copy is no longer what it was)
+    COVAHIP_CHECK_HIP(ctx, hipEventRecord(ev, ctx->stream));
+    recorded = true;
+    resident.assign(src, src + n);
+    return COVAHIP_OK;
+}
+
+template <typename T>
+void ResidentTable<T>::release() {
+    if (dev) hipFree(dev);
+    if (pinned) hipHostFree(pinned);
+    if (ev) hipEventDestroy(ev);
+    *this = ResidentTable<T>();
+}
+
+// Opens a kernel's dynamic LDS above the 64 KiB every kernel has (ctx.hip): sets the function's limit to `limit` bytes unless a
+// limit of at least `lds` was set for this (device, function) before.  The attribute is sticky, so a launch path calls this
+// with the launch's `lds` every time and pays a cache look-up.
+int covahip_open_lds(covahip_ctx *ctx, const void *fn, size_t lds, size_t limit);
+template <typename K>
+int covahip_open_lds(covahip_ctx *ctx, K kernel, size_t lds, size_t limit) {
+    return lds <= 64 * 1024 ? COVAHIP_OK : covahip_open_lds(ctx, reinterpret_cast<const void *>(kernel), lds, limit);
+}
 
 // RAII-less helpers: bracket a kernel launch with events when profiling is on.
 struct ProfScope {

@@ -156,8 +156,8 @@ int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bi
         if (rows < 16 || rows > G::MH) return COVAHIP_ERR_UNSUPPORTED;
         const size_t lds = band_lds_bytes(G::MW, G::MH, rows);
         if (lds > COVAHIP_MOG_BAND_LDS_MAX) return COVAHIP_ERR_UNSUPPORTED;
-        // opened to the maximum, once: `rows` differs between launches
-        if (int rc = open_lds(ctx, k_mog_band_post<G::MW, G::MH, POST_BLOCK>, COVAHIP_MOG_BAND_LDS_MAX)) return rc;
+        // opened to the maximum: `rows` differs between launches
+        if (int rc = covahip_open_lds(ctx, k_mog_band_post<G::MW, G::MH, POST_BLOCK>, lds, COVAHIP_MOG_BAND_LDS_MAX)) return rc;
         return mog_launch(ctx, "mog_band_post", k_mog_band_post<G::MW, G::MH, POST_BLOCK>, dim3((unsigned)FS), POST_BLOCK, lds, bits,
                           filled_bits, plane, labels, nvalid, S, rows);
     });

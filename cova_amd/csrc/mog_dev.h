@@ -20,7 +20,6 @@
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
-#include <mutex>
 #include <utility>
 #include <vector>
 
@@ -594,21 +593,6 @@ int with_geom(int mw, F &&f) {
     int rc = COVAHIP_ERR_UNSUPPORTED;
     (void)((mw == Gs::MW && ((rc = f(Gs{})), true)) || ...);
     return rc;
-}
-
-// Opens a kernel's dynamic LDS to `lds` bytes, once per (device, function); up to 64 KiB needs no call.
-template <typename K>
-int open_lds(covahip_ctx *ctx, K kernel, size_t lds) {
-    if (lds <= 64 * 1024) return COVAHIP_OK;
-    static std::mutex mu;
-    static std::vector<std::pair<int, const void *>> opened;
-    const void *fn = reinterpret_cast<const void *>(kernel);
-    std::lock_guard<std::mutex> lock(mu);
-    for (auto &o : opened)
-        if (o.first == ctx->device && o.second == fn) return COVAHIP_OK;
-    COVAHIP_CHECK_HIP(ctx, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    opened.emplace_back(ctx->device, fn);
-    return COVAHIP_OK;
 }
 
 // What an update launch takes behind its frames: the model, the call's tables (par: (alphaT, prune) [F][S]; nvalid [S]), the

@@ -74,7 +74,7 @@ int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bi
         constexpr int BLOCK = G::MW == 960 ? 512 : 256;    // (the results do not depend on it) at 960x540 one workgroup owns the CU
         constexpr size_t lds = (size_t)2 * G::NWORD * 8 + 16;   // the two planes and the `changed` word
         static_assert(lds <= 160 * 1024 - 64, "the two planes must fit a CU's LDS");
-        if (int rc = open_lds(ctx, k_mog_grid_post<G::MW, G::MH, BLOCK>, lds)) return rc;
+        if (int rc = covahip_open_lds(ctx, k_mog_grid_post<G::MW, G::MH, BLOCK>, lds, lds)) return rc;   // (a constant of the kernel)
         return mog_launch(ctx, "mog_post", k_mog_grid_post<G::MW, G::MH, BLOCK>, dim3((unsigned)FS), BLOCK, lds, bits, filled_bits, labels,
                           nvalid, S);
     });

@@ -261,15 +261,9 @@ int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, MonTable &tb, const uint8
         std::copy(seg, seg + COVAHIP_MAX_MODELS, at);
         for (int b = 0; b < n; b++) table[(size_t)2 * S + at[model_ids[b]]++] = b;
     }
-    if (table.size() > tb.cap) return COVAHIP_ERR_INVALID_ARG;
-    if (table != tb.last) {
-        if (!tb.last.empty()) COVAHIP_CHECK_HIP(ctx, hipEventSynchronize(tb.ev));   // the pinned copy is free again
-        std::copy(table.begin(), table.end(), tb.h_tab);
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tb.d_tab, tb.h_tab, table.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-        COVAHIP_CHECK_HIP(ctx, hipEventRecord(tb.ev, ctx->stream));
-        tb.last = std::move(table);
-    }
-    launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, S, MonByPtr{tb.d_tab});
+    const int32_t *d_table = nullptr;   // (a counted batch never allocates: a table beyond what begin reserved is refused)
+    if (int rc = tb.upload(ctx, table.data(), table.size(), &d_table)) return rc;
+    launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, S, MonByPtr{d_table});
     COVAHIP_CHECK_HIP(ctx, hipGetLastError());
     return COVAHIP_OK;
 }
@@ -277,11 +271,7 @@ int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, MonTable &tb, const uint8
 void free_monitor(CovahipMonitor *mon) {
     if (!mon) return;
     if (mon->d_tab) hipFree(mon->d_tab);
-    for (MonTable &tb : mon->lane) {
-        if (tb.d_tab) hipFree(tb.d_tab);
-        if (tb.h_tab) hipHostFree(tb.h_tab);
-        if (tb.ev) hipEventDestroy(tb.ev);
-    }
+    for (MonTable &tb : mon->lane) tb.release();
     delete mon;
 }
 
@@ -335,13 +325,7 @@ int covahip_monitor_begin(covahip_ctx *ctx, const covahip_monitor_cfg *cfg) {
     bool ok = hipMalloc((void **)&mon->d_tab, mon->words * sizeof(unsigned long long)) == hipSuccess &&
               hipMemsetAsync(mon->d_tab, 0, mon->words * sizeof(unsigned long long), ctx->primary) == hipSuccess &&
               hipStreamSynchronize(ctx->primary) == hipSuccess;
-    for (int k = 0; k < (cfg->attach ? COVAHIP_MAX_LANES : 1) && ok; k++) {
-        MonTable &tb = mon->lane[k];
-        ok = hipMalloc((void **)&tb.d_tab, tab_ints * sizeof(int32_t)) == hipSuccess &&
-             hipHostMalloc((void **)&tb.h_tab, tab_ints * sizeof(int32_t), hipHostMallocDefault) == hipSuccess &&
-             hipEventCreateWithFlags(&tb.ev, hipEventDisableTiming) == hipSuccess;
-        tb.cap = ok ? tab_ints : 0;
-    }
+    for (int k = 0; k < (cfg->attach ? COVAHIP_MAX_LANES : 1) && ok; k++) ok = mon->lane[k].reserve(ctx, tab_ints) == COVAHIP_OK;
     if (!ok) {
         ctx->last_hip_error = "covahip_monitor_begin: allocation failed";
         (void)hipGetLastError();
@@ -367,7 +351,6 @@ int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *co
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int prc = covahip_primary_op(ctx)) return prc;   // on the primary stream, behind all lanes
     const size_t hw = (size_t)mon->h * mon->w, mb = (size_t)mon->max_boxes;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (mem_kind == COVAHIP_MEM_DEVICE) {
         for (int s0 = 0; s0 < n; s0 += MON_CHUNK)
             if (int rc = count_batch(ctx, mon, mon->lane[0], mask + (size_t)s0 * hw, counts + s0, boxes ? boxes + (size_t)s0 * mb : nullptr,
@@ -376,8 +359,8 @@ int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *co
     } else {   // staged in pieces: [mask][counts][boxes]
         const size_t per_sample = hw + sizeof(int32_t) + mb * sizeof(covahip_box);
         const int piece = (int)std::min<size_t>(std::min(n, MON_CHUNK), std::max<size_t>(1, MON_STAGE / per_sample));
-        const size_t o_cnt = al((size_t)piece * hw), o_box = o_cnt + al((size_t)piece * sizeof(int32_t));
-        if (int rc = covahip_ensure_buffer(ctx, &ctx->stage_in, &ctx->stage_in_bytes, o_box + al((size_t)piece * mb * sizeof(covahip_box))))
+        const size_t o_cnt = align256((size_t)piece * hw), o_box = o_cnt + align256((size_t)piece * sizeof(int32_t));
+        if (int rc = covahip_ensure_buffer(ctx, &ctx->stage_in, &ctx->stage_in_bytes, o_box + align256((size_t)piece * mb * sizeof(covahip_box))))
             return rc;
         uint8_t *sm = (uint8_t *)ctx->stage_in;
         int32_t *sc = (int32_t *)(sm + o_cnt);

@@ -197,7 +197,6 @@ __global__ __launch_bounds__(SM_WAVES * 64) void sweep_match(const covahip_box *
     }
 }
 
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 }  // namespace
 
@@ -211,8 +210,7 @@ extern "C" int covahip_post_sweep(covahip_ctx *ctx, const covahip_sweep_cfg *cfg
     if (cfg->h <= 0 || cfg->w <= 0) return COVAHIP_ERR_INVALID_ARG;
     if (cfg->n_thresh < 1 || cfg->n_thresh > SW_MAX_T || !cfg->logit_thresh) return COVAHIP_ERR_INVALID_ARG;
     if (cfg->n_area < 1 || cfg->n_area > SW_MAX_A || !cfg->area_thresh) return COVAHIP_ERR_INVALID_ARG;
-    for (int t = 0; t < cfg->n_thresh; t++)
-        if (!std::isfinite(cfg->logit_thresh[t]) || (t && !(cfg->logit_thresh[t] > cfg->logit_thresh[t - 1]))) return COVAHIP_ERR_INVALID_ARG;
+    if (!covahip_thresholds_ok(cfg->logit_thresh, cfg->n_thresh)) return COVAHIP_ERR_INVALID_ARG;
     for (int a = 0; a < cfg->n_area; a++)
         if (cfg->area_thresh[a] < 1 || (a && cfg->area_thresh[a] <= cfg->area_thresh[a - 1])) return COVAHIP_ERR_INVALID_ARG;
     if (cfg->gt_area_thresh < 1 || cfg->iou_num < 1 || cfg->iou_num > cfg->iou_den) return COVAHIP_ERR_INVALID_ARG;
@@ -239,14 +237,14 @@ extern "C" int covahip_post_sweep(covahip_ctx *ctx, const covahip_sweep_cfg *cfg
     if (int prc = covahip_primary_op(ctx)) return prc;   // on the primary stream, behind all lanes
 
     // scratch: [accumulators][keep map][prediction frames][label frames][prediction boxes][label boxes][counts]
-    const size_t off_keep = align_up(ACC_WORDS * sizeof(uint64_t), 256);
-    const size_t off_pred = off_keep + align_up(hw, 256);
-    const size_t off_gtm = off_pred + align_up((size_t)chunk * T * hw, 256);
-    const size_t off_pbox = off_gtm + align_up((size_t)chunk * hw, 256);
-    const size_t off_gbox = off_pbox + align_up((size_t)chunk * T * max_boxes * sizeof(covahip_box), 256);
-    const size_t off_pcnt = off_gbox + align_up((size_t)chunk * max_boxes * sizeof(covahip_box), 256);
-    const size_t off_gcnt = off_pcnt + align_up((size_t)chunk * T * sizeof(int32_t), 256);
-    const size_t total = off_gcnt + align_up((size_t)chunk * sizeof(int32_t), 256);
+    const size_t off_keep = align256(ACC_WORDS * sizeof(uint64_t));
+    const size_t off_pred = off_keep + align256(hw);
+    const size_t off_gtm = off_pred + align256((size_t)chunk * T * hw);
+    const size_t off_pbox = off_gtm + align256((size_t)chunk * hw);
+    const size_t off_gbox = off_pbox + align256((size_t)chunk * T * max_boxes * sizeof(covahip_box));
+    const size_t off_pcnt = off_gbox + align256((size_t)chunk * max_boxes * sizeof(covahip_box));
+    const size_t off_gcnt = off_pcnt + align256((size_t)chunk * T * sizeof(int32_t));
+    const size_t total = off_gcnt + align256((size_t)chunk * sizeof(int32_t));
     int rc = covahip_ensure_buffer(ctx, &ctx->sweep_buf, &ctx->sweep_bytes, total);
     if (rc) return rc;
     uint8_t *const base = (uint8_t *)ctx->sweep_buf;

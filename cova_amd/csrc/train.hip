@@ -22,19 +22,16 @@
 #include <cstring>
 #include <vector>
 
+#include "blobnet_params.h"
 #include "internal.h"
 
 namespace {
 
-constexpr int TT = 4;                 // timestep
-constexpr int NL = 4;                 // encoder levels / decoder blocks
-constexpr size_t N_PARAMS = 320305;
-constexpr uint32_t W_MAGIC = 0x57485643;  // "CVHW"
-constexpr int ENC_C[NL + 1] = {3, 16, 32, 64, 128};
-constexpr int DEC_CI[NL] = {128, 128, 64, 32};
-constexpr int DEC_CO[NL] = {64, 32, 16, 16};
-// the 64-byte header of a weight file of the trained architecture; a reader checks the first 13 words
-constexpr uint32_t W_HEADER[16] = {W_MAGIC, 1, 4, 3, 16, 32, 64, 128, 64, 32, 16, 16, (uint32_t)N_PARAMS, 0, 0, 0};
+// the architecture and the parameter layout are blobnet_params.h's; these are the short names this file uses for them
+constexpr int TT = BN_T;              // timestep
+constexpr int NL = BN_LEVELS;         // encoder levels / decoder blocks
+constexpr size_t N_PARAMS = BN_N_PARAMS;
+constexpr const int (&ENC_C)[NL + 1] = BN_ENC_C, (&DEC_CI)[NL] = BN_DEC_CI, (&DEC_CO)[NL] = BN_DEC_CO;
 constexpr int BLK = 256;
 constexpr int RED_CHUNK = 4096;       // elements per slab of a channel reduction
 constexpr int WG_CHUNK = 1024;        // positions per slab of a weight gradient
@@ -910,11 +907,9 @@ __global__ void k_adam_plan(Mdl md, float *__restrict__ w, float *__restrict__ g
     w[i] -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
-// ------------------------------------------------------------------------------------------------ host state
-struct EncOff { size_t k, b, gamma, beta, mean, var, w1, w2; };
-struct DecOff { size_t k, b, gamma, beta, mean, var; };
-
 }  // namespace
+
+// ------------------------------------------------------------------------------------------------ host state
 
 struct covahip_train {
     covahip_ctx *ctx = nullptr;
@@ -923,9 +918,6 @@ struct covahip_train {
                                // params / grads / adam_*) behind model 0's
     int H[NL + 1], W[NL + 1];
     int cy[NL], cx[NL];
-    EncOff eo[NL];
-    DecOff dof[NL];
-    size_t fk = 0, fb = 0;
     std::vector<int64_t> step;         // per model: steps taken (Adam's t - 1, the dropout hash's step)
     std::vector<uint64_t> seed;        // per model: dropout seed
     std::vector<long long> last_counts;   // per model: TP, FP, FN of its last step
@@ -984,36 +976,6 @@ void free_train(covahip_train *tr) {
     if (tr->h_sample_loss) hipHostFree(tr->h_sample_loss);
     if (tr->h_counts) hipHostFree(tr->h_counts);
     delete tr;
-}
-
-void layout(covahip_train *tr) {
-    size_t off = 0;
-    for (int i = 0; i < NL; i++) {
-        const size_t ci = ENC_C[i], co = ENC_C[i + 1];
-        EncOff &o = tr->eo[i];
-        o.k = off; off += 9 * ci * co;
-        o.b = off; off += co;
-        o.gamma = off; off += co;
-        o.beta = off; off += co;
-        o.mean = off; off += co;
-        o.var = off; off += co;
-        o.w1 = off; off += TT * TT;
-        o.w2 = off; off += TT * TT;
-    }
-    for (int j = 0; j < NL; j++) {
-        const size_t ci = DEC_CI[j], co = DEC_CO[j];
-        DecOff &o = tr->dof[j];
-        o.k = off; off += 16 * co * ci;
-        o.b = off; off += co;
-        if (j < NL - 1) {
-            o.gamma = off; off += co;
-            o.beta = off; off += co;
-            o.mean = off; off += co;
-            o.var = off; off += co;
-        }
-    }
-    tr->fk = off; off += 16;
-    tr->fb = off; off += 1;
 }
 
 DropS make_drop(const covahip_train *tr, int site) {
@@ -1075,13 +1037,13 @@ struct Run {
 BNTab bn_table(const covahip_train *tr) {
     BNTab bn;
     for (int i = 0; i < NL; i++) {
-        bn.mean[i] = (int32_t)tr->eo[i].mean;
-        bn.var[i] = (int32_t)tr->eo[i].var;
+        bn.mean[i] = (int32_t)BN_LAYOUT.enc[i].mean;
+        bn.var[i] = (int32_t)BN_LAYOUT.enc[i].var;
         bn.C[i] = ENC_C[i + 1];
     }
     for (int j = 0; j < NL - 1; j++) {
-        bn.mean[NL + j] = (int32_t)tr->dof[j].mean;
-        bn.var[NL + j] = (int32_t)tr->dof[j].var;
+        bn.mean[NL + j] = (int32_t)BN_LAYOUT.dec[j].mean;
+        bn.var[NL + j] = (int32_t)BN_LAYOUT.dec[j].var;
         bn.C[NL + j] = DEC_CO[j];
     }
     return bn;
@@ -1108,7 +1070,7 @@ int forward(Run &r, const Fwd &f) {
     KL(r, k_input, (r.g1((int64_t)B * 3 * TT * H0 * W0)), BLK, tr->d_stack, tr->x0, H0, W0);
     for (int i = 0; i < NL; i++) {
         const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
-        const EncOff &o = tr->eo[i];
+        const BnEncOff &o = BN_LAYOUT.enc[i];
         const float *xin = i ? tr->e[i - 1] : tr->x0;
         const int64_t S = (int64_t)TT * H * W;
         KL(r, k_conv3_fwd, (r.g1(B * Co * S)), BLK, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
@@ -1128,7 +1090,7 @@ int forward(Run &r, const Fwd &f) {
     for (int j = 0; j < NL; j++) {
         const int Ci = DEC_CI[j], Co = DEC_CO[j];
         const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
-        const DecOff &o = tr->dof[j];
+        const BnDecOff &o = BN_LAYOUT.dec[j];
         const int64_t per = (int64_t)Ci * Hi * Wi, So = (int64_t)Ho * Wo;
         KL(r, k_drop_relu, (r.g1(B * per)), BLK, tr->z[j], tr->zd[j], per, f.drop[2 * NL + j]);
         KL(r, k_convT_fwd, (r.g1(B * Co * So)), BLK, tr->zd[j], P + o.k, P + o.b, tr->y[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j]);
@@ -1144,7 +1106,7 @@ int forward(Run &r, const Fwd &f) {
         if (!r.ok()) return r.rc;
     }
     const int64_t hw = (int64_t)H0 * W0;
-    KL(r, k_final_fwd, (r.g1(B * hw)), BLK, tr->y[NL - 1], P + tr->fk, P + tr->fb, tr->logit, hw);
+    KL(r, k_final_fwd, (r.g1(B * hw)), BLK, tr->y[NL - 1], P + BN_LAYOUT.fk, P + BN_LAYOUT.fb, tr->logit, hw);
     r.reduce(R_LOSS, B, hw, tr->logit, nullptr, 0, nullptr, tr->d_gt, F_SUM2, tr->red, red_stride(tr->cfg.max_batch), nullptr, nullptr,
              nullptr, nullptr);
     return r.rc;
@@ -1182,20 +1144,20 @@ int run_step(covahip_train *tr, int B) {
 
     // ---------------------------------------------------------------- backward
     if (tr->any_post)
-        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
+        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + BN_LAYOUT.fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
                                                      tr->d_counts, tr->post_tab());
     else
-        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + tr->fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
+        KL(r, k_final_bwd, (r.g1(B * hw)), BLK, tr->logit, tr->d_gt, tr->red, P + BN_LAYOUT.fk, tr->dlogit, tr->dy[NL - 1], hw, sm,
                                                 tr->d_counts);
     if (!dec_fz(NL - 1)) {
-        r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fk, nullptr, nullptr, nullptr);
-        r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + tr->fb, nullptr, nullptr, nullptr);
+        r.reduce(R_FINALW, 16, hw, tr->y[NL - 1], tr->dlogit, 1, nullptr, nullptr, F_SUM, nullptr, 0, G + BN_LAYOUT.fk, nullptr, nullptr, nullptr);
+        r.reduce(R_SUM, 1, hw, tr->dlogit, nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + BN_LAYOUT.fb, nullptr, nullptr, nullptr);
     }
     if (!r.ok()) return r.rc;
     for (int j = NL - 1; j >= 0 && need_dy[j]; j--) {
         const int Ci = DEC_CI[j], Co = DEC_CO[j];
         const int Hi = tr->H[NL - j], Wi = tr->W[NL - j], Ho = tr->H[NL - 1 - j], Wo = tr->W[NL - 1 - j];
-        const DecOff &o = tr->dof[j];
+        const BnDecOff &o = BN_LAYOUT.dec[j];
         const int64_t So = (int64_t)Ho * Wo;
         if (j < NL - 1) {   // BN of this block: its output gradient is channel range [0, Co) of the next block's dz
             // the sums are gamma's and beta's gradients in either mode, and the batch-mean terms of a batch-mode layer
@@ -1225,7 +1187,7 @@ int run_step(covahip_train *tr, int B) {
     }
     for (int i = NL - 1; i >= 0 && enc_live(i); i--) {
         const int Ci = ENC_C[i], Co = ENC_C[i + 1], H = tr->H[i], W = tr->W[i], Hp = tr->H[i + 1], Wp = tr->W[i + 1];
-        const EncOff &o = tr->eo[i];
+        const BnEncOff &o = BN_LAYOUT.enc[i];
         const int zj = NL - 1 - i;
         const int c_off = i == NL - 1 ? 0 : DEC_CO[zj - 1];
         const int64_t tper = (int64_t)Co * Hp * Wp;
@@ -1288,13 +1250,13 @@ int run_eval(covahip_train *tr, int B) {
 std::vector<uint8_t> plan_mask(const covahip_train *tr, uint32_t frozen) {
     std::vector<uint8_t> m(N_PARAMS, 1);
     for (int i = 0; i < NL; i++) {
-        const EncOff &o = tr->eo[i];
+        const BnEncOff &o = BN_LAYOUT.enc[i];
         if (frozen >> i & 1u) std::fill(m.begin() + o.k, m.begin() + o.w2 + TT * TT, 2);
         std::fill(m.begin() + o.mean, m.begin() + o.w1, 0);
     }
     for (int j = 0; j < NL; j++) {
-        const DecOff &o = tr->dof[j];
-        const size_t end = j < NL - 1 ? tr->dof[j + 1].k : N_PARAMS;   // block 3's group ends with final.kernel / final.bias
+        const BnDecOff &o = BN_LAYOUT.dec[j];
+        const size_t end = j < NL - 1 ? BN_LAYOUT.dec[j + 1].k : N_PARAMS;   // block 3's group ends with final.kernel / final.bias
         if (frozen >> (NL + j) & 1u) std::fill(m.begin() + o.k, m.begin() + end, 2);
         if (j < NL - 1) std::fill(m.begin() + o.mean, m.begin() + o.var + DEC_CO[j], 0);
     }
@@ -1309,17 +1271,6 @@ int validate_cfg(const covahip_train_cfg *c) {
     if (!(c->beta1 >= 0.f && c->beta1 < 1.f) || !(c->beta2 >= 0.f && c->beta2 < 1.f) || !finite_pos(c->eps)) return COVAHIP_ERR_INVALID_ARG;
     if (!(c->bn_momentum >= 0.f && c->bn_momentum <= 1.f) || !finite_pos(c->bn_eps)) return COVAHIP_ERR_INVALID_ARG;
     if (!(c->dropout >= 0.f && c->dropout < 1.f) || !finite_pos(c->smooth)) return COVAHIP_ERR_INVALID_ARG;
-    return COVAHIP_OK;
-}
-
-// COVAHIP_OK if `cvhw` is a weight file of the trained architecture
-int check_blob(const void *cvhw, size_t cvhw_bytes) {
-    if (cvhw_bytes < 64) return COVAHIP_ERR_BAD_WEIGHTS;
-    uint32_t hdr[16];
-    std::memcpy(hdr, cvhw, 64);
-    for (int i = 0; i < 13; i++)
-        if (hdr[i] != W_HEADER[i]) return COVAHIP_ERR_BAD_WEIGHTS;
-    if (cvhw_bytes != 64 + N_PARAMS * sizeof(float)) return COVAHIP_ERR_BAD_WEIGHTS;
     return COVAHIP_OK;
 }
 
@@ -1346,7 +1297,6 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     // output) and the y extent of the per-sample loss reduction (one row per sample of a model).
     if (B > INT32_MAX / 2 || ((int64_t)cf.max_batch * 16 * TT * hw0 + BLK - 1) / BLK > INT32_MAX || (K > 1 && cf.max_batch > 65535))
         return COVAHIP_ERR_UNSUPPORTED;
-    layout(tr);
     tr->step.assign(K, 0);
     tr->last_counts.assign((size_t)K * 3, 0);
     int rc;
@@ -1410,7 +1360,7 @@ int create_body(covahip_train *tr, const void *const *blobs) {
     const std::vector<uint8_t> tmask = plan_mask(tr, 0);
     const hipStream_t s = ctx->stream;
     for (int k = 0; k < K; k++)
-        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params + (size_t)k * N_PARAMS, static_cast<const uint8_t *>(blobs[k]) + 64,
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->params + (size_t)k * N_PARAMS, static_cast<const uint8_t *>(blobs[k]) + BN_HEADER_BYTES,
                                               N_PARAMS * sizeof(float), hipMemcpyHostToDevice, s));
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(tr->trainable, tmask.data(), N_PARAMS, hipMemcpyHostToDevice, s));
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(tr->grads, 0, (size_t)K * N_PARAMS * sizeof(float), s));
@@ -1635,7 +1585,7 @@ int covahip_train_create_set(covahip_ctx *ctx, const covahip_train_cfg *cfg, int
         if (!weights[k]) return COVAHIP_ERR_INVALID_ARG;
     if (int rc = validate_cfg(cfg)) return rc;
     for (int k = 0; k < n_models; k++)
-        if (int rc = check_blob(weights[k], weights_bytes[k])) return rc;
+        if (!bn_check_blob(weights[k], weights_bytes[k])) return COVAHIP_ERR_BAD_WEIGHTS;
     if (int rc = enter(ctx)) return rc;
     covahip_train *tr = new covahip_train();
     tr->ctx = ctx;
@@ -1699,13 +1649,13 @@ int covahip_train_metrics(covahip_train *tr, int64_t tp_fp_fn[3]) { return covah
 
 int covahip_train_weights_m(covahip_train *tr, int model, void *cvhw, size_t cap, size_t *n) {
     if (!tr || !n || model < 0 || model >= tr->K) return COVAHIP_ERR_INVALID_ARG;
-    const size_t need = 64 + N_PARAMS * sizeof(float);
+    const size_t need = BN_BLOB_BYTES;
     *n = need;
     if (!cvhw || cap < need) return COVAHIP_ERR_OVERFLOW;
     covahip_ctx *ctx = tr->ctx;
     if (int rc = enter(ctx)) return rc;
-    std::memcpy(cvhw, W_HEADER, 64);
-    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + 64, tr->params + (size_t)model * N_PARAMS,
+    std::memcpy(cvhw, BN_HEADER, BN_HEADER_BYTES);
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(static_cast<uint8_t *>(cvhw) + BN_HEADER_BYTES, tr->params + (size_t)model * N_PARAMS,
                                           N_PARAMS * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return COVAHIP_OK;

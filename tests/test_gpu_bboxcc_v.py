@@ -224,6 +224,29 @@ def test_large_batch_overflow_lists(own_ctx):
     _check(boxes, counts, table, idx, thr, max_boxes, "large batch, host")
 
 
+def test_threshold_table_grows_repeats_changes_and_shrinks(own_ctx):
+    """One ctx, calls of 3, 8, 8, 8 and 5 frames: the ctx's threshold table is made, grows, is asked for the thresholds it holds,
+    for others of the same length, and for a shorter list.  Device pointers (the kernels read the table while the host goes on)
+    and host pointers, each call against the oracle."""
+    ctx = own_ctx
+    h, w, max_boxes = 16, 16, 64
+    rng = np.random.default_rng(33)
+    uniq = _noise(rng, 8, h, w)
+    table = _oracle(uniq, max_boxes)
+    assert all(table[1][1][u] > table[8][1][u] for u in range(8))          # from the oracle alone: the thresholds matter
+    cc = BboxCc(ctx, 99, max_boxes)
+    thr8 = np.array([THRS[(3 * i + 1) % 5] for i in range(8)], np.int32)
+    other8 = np.array([THRS[(3 * i + 2) % 5] for i in range(8)], np.int32)
+    assert (thr8 != other8).all()
+    for b, thr, what in ((3, thr8[:3], "first"), (8, thr8, "grown"), (8, thr8, "repeated"), (8, other8, "changed"), (5, thr8[3:], "shrunk")):
+        idx = np.arange(8 - b, 8) if what == "shrunk" else np.arange(b)
+        masks = np.ascontiguousarray(uniq[idx])
+        boxes, counts, _ = _device_call(ctx, cc, masks, thr)
+        _check(boxes, counts, table, idx, thr, max_boxes, f"{what}, device")
+        boxes, counts = cc.regionprops_v(masks, thr)
+        _check(boxes, counts, table, idx, thr, max_boxes, f"{what}, host")
+
+
 def test_errors(own_ctx):
     lib = L.lib()
     masks = _noise(np.random.default_rng(1), 2, 16, 16)
