@@ -3,6 +3,7 @@
 // in LDS).  See bboxcc.hip for the algorithm.
 #pragma once
 #include <cstdint>
+#include <type_traits>
 
 #include "internal.h"
 
@@ -11,7 +12,13 @@ namespace ccbody {
 constexpr int CC_THREADS = 1024;  // 16 waves: the union-find phases are LDS-latency bound, so run 4 waves per SIMD
 constexpr uint32_t NONE = 0xFFFFFFFFu;
 
-__device__ __forceinline__ uint32_t uf_find(const volatile uint32_t *lab, uint32_t i) {
+// LDS = true: the caller's labels are in LDS (the run-based body, bboxcc_wave.h; this body also runs on a slab in global memory) and
+// the pointer says so.  A volatile read through a generic pointer stays a flat_load -- address-space inference leaves volatile
+// accesses alone --, which takes the long way to LDS and counts on both memory counters, for every hop of a chain.
+template <bool LDS = false>
+__device__ __forceinline__ uint32_t uf_find(const uint32_t *lab_generic, uint32_t i) {
+    using lab_ptr = std::conditional_t<LDS, const volatile __attribute__((address_space(3))) uint32_t *, const volatile uint32_t *>;
+    const lab_ptr lab = (lab_ptr)lab_generic;
     uint32_t p = lab[i];
     while (p != i) {
         i = p;
@@ -21,10 +28,11 @@ __device__ __forceinline__ uint32_t uf_find(const volatile uint32_t *lab, uint32
 }
 
 // min-root union; safe under concurrent unions from other lanes/waves.
+template <bool LDS = false>
 __device__ __forceinline__ void uf_union(uint32_t *lab, uint32_t a, uint32_t b) {
     while (true) {
-        a = uf_find(lab, a);
-        b = uf_find(lab, b);
+        a = uf_find<LDS>(lab, a);
+        b = uf_find<LDS>(lab, b);
         if (a == b) return;
         if (a < b) {
             uint32_t t = a;

@@ -211,7 +211,7 @@ __device__ __forceinline__ int frame_wave(const uint8_t *m, uint8_t *sm, const W
                     const uint64_t jr = (hJu >> p) >> 1;
                     const int e_up = p + (~jr ? ctz64(~jr) : 0);
                     Tu &= ~mask_upto(e_up);
-                    ccbody::uf_union(lab, (uint32_t)idx, (uint32_t)(hbase_up + rank));
+                    ccbody::uf_union<true>(lab, (uint32_t)idx, (uint32_t)(hbase_up + rank));
                 }
             }
         }
@@ -220,7 +220,7 @@ __device__ __forceinline__ int frame_wave(const uint8_t *m, uint8_t *sm, const W
     wave_fence();
     // ---- D: statistics to the roots
     for (int i = lane; i < n; i += 64) {
-        const uint32_t root = ccbody::uf_find(lab, (uint32_t)i);
+        const uint32_t root = ccbody::uf_find<true>(lab, (uint32_t)i);
         if (root != (uint32_t)i) {
             lab[i] = root;
             atomicAdd(&s_area[root], s_area[i]);
@@ -351,7 +351,7 @@ __device__ __forceinline__ void frame_wg(const uint8_t *m, uint8_t *sm, const Wv
                 const uint64_t jr = (J_up >> p) >> 1;
                 const int e_up = p + (~jr ? ctz64(~jr) : 0);
                 Tu &= ~mask_upto(e_up);
-                ccbody::uf_union(lab, (uint32_t)idx, (uint32_t)(base_up + rank));
+                ccbody::uf_union<true>(lab, (uint32_t)idx, (uint32_t)(base_up + rank));
             }
         }
     }
@@ -359,7 +359,7 @@ __device__ __forceinline__ void frame_wg(const uint8_t *m, uint8_t *sm, const Wv
     CCWG_MARK(2);   // C: runs, unions
     // ---- D
     for (int i = tid; i < n; i += NTH) {
-        const uint32_t root = ccbody::uf_find(lab, (uint32_t)i);
+        const uint32_t root = ccbody::uf_find<true>(lab, (uint32_t)i);
         if (root != (uint32_t)i) {
             lab[i] = root;
             atomicAdd(&s_area[root], s_area[i]);

@@ -97,6 +97,17 @@ template <typename T>
 __device__ __forceinline__ const T *at_model(const T *ptr, uint32_t off) {
     return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(ptr) + off);
 }
+// Weight loads are GLOBAL loads ("Weight loads are global loads").  A pointer that went through an opaque
+// `asm` (the hoisting barriers below) or came out of at_model's byte arithmetic has lost its address space, and a load through it
+// becomes flat_load: that counts on lgkmcnt as well as vmcnt, so every LDS wait -- lds_barrier() ends in one -- also waits for
+// the weights in flight.  Everything the kernels read through these pointers lies in device memory; saying so gives
+// global_load (vmcnt alone, returned in order, waited for with a counted vmcnt where the value is used).
+template <typename T>
+using gptr = const __attribute__((address_space(1))) T *;
+template <typename T>
+__device__ __forceinline__ gptr<T> as_global(const T *ptr) {
+    return (gptr<T>)ptr;
+}
 
 // relu -> BN affine -> 2x2 max-pool of the four conv outputs of one window.  BN runs between ReLU and the pool
 // (encoder.py:61-66) and gamma may be negative.  The BN scale s of a channel is folded into its weights and bias on the host
@@ -208,6 +219,19 @@ __device__ __forceinline__ void lds_barrier() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup", "local");
 }
 __device__ __forceinline__ void wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // vmcnt(0), nothing else
+// vmcnt(N), nothing else: everything but the N youngest vector-memory operations has completed (gfx9 encoding: the count's low four
+// bits at [3:0], its high two at [15:14])
+// lds_barrier() behind LDS-DMA requests, with the N youngest vector-memory operations (plain loads issued behind the requests)
+// left in flight.  Written out -- wait, barrier, and the compiler kept from moving memory accesses across either -- because a
+// release fence behind LDS-DMA makes hipcc wait for vmcnt(0) whatever wait stands in front of it.
+template <int N>
+__device__ __forceinline__ void lds_barrier_vmem_but() {
+    static_assert(N >= 0 && N < 64, "vmcnt is a six-bit counter");
+    asm volatile("" ::: "memory");
+    __builtin_amdgcn_s_waitcnt(0x0070 | (N & 15) | ((N >> 4) << 14));   // vmcnt(N) lgkmcnt(0)
+    __builtin_amdgcn_s_barrier();
+    asm volatile("" ::: "memory");
+}
 
 // LDS pixel swizzle: the 16-byte chunk c of tile pixel (xx, yy) sits at chunk c ^ s(xx, yy).  s comes
 // from a small linear family whose parameters the host picks per level and band geometry with a
@@ -1249,10 +1273,11 @@ __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
         {
             const half8 *wp = (MS ? at_model(p.wfrag, moff) : p.wfrag) + ll;
             asm volatile("" : "+v"(wp));
+            const gptr<half8> wg = as_global(wp);
 #pragma unroll
             for (int nt = 0; nt < 2; nt++)
 #pragma unroll
-                for (int s = 0; s < 5; s++) bf[nt][s] = wp[(nt * 5 + s) * 64];
+                for (int s = 0; s < 5; s++) bf[nt][s] = wg[(nt * 5 + s) * 64];
         }
         lds_barrier();   // the band is complete
         PHASE_MARK(4);   // barrier: the band complete
@@ -1537,8 +1562,9 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
             {
                 const half8 *wp = at_model(p.wf2, moff) + nt2 * 18 * 64 + ll;
                 asm volatile("" : "+v"(wp));
+                const gptr<half8> wg = as_global(wp);
 #pragma unroll
-                for (int ks = 0; ks < 18; ks++) bf[ks] = wp[ks * 64];
+                for (int ks = 0; ks < 18; ks++) bf[ks] = wg[ks * 64];
             }
             const int co = nt2 * 32 + (ll & 31);
             const float *const epi2 = at_model(p.epi2, moff);
@@ -1634,12 +1660,15 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
             asm volatile("" : "+v"(l3));
             const int m0 = l3 & 31, kh = l3 >> 5;
             const int yl = (m0 >> 1) & 1, xl = 2 * (m0 >> 2) + (m0 & 1);
-            half8 bf[36];   // requested in front of the barrier that completes the band
+            // Requested in front of the barrier that completes the band and in flight across it and the T = 0 copy-out: global loads,
+            // so neither the barrier's LDS wait nor the copy-out's LDS reads wait for them; the tile loop's preheader does (vmcnt(0))
+            half8 bf[36];
             {
                 const half8 *wp = at_model(p.wf3, moff) + nt3 * 36 * 64 + ll;
                 asm volatile("" : "+v"(wp));
+                const gptr<half8> wg = as_global(wp);
 #pragma unroll
-                for (int ks = 0; ks < 36; ks++) bf[ks] = wp[ks * 64];
+                for (int ks = 0; ks < 36; ks++) bf[ks] = wg[ks * 64];
             }
             lds_barrier();   // level 3's band is complete
             // T = 0 slice of level 2's output -> act[3] (rows / columns of the pad are zero in HBM and never written)
@@ -1996,6 +2025,7 @@ struct Dec012W {   // a wave's weight fragments and epilogue constants of one bl
     half8 wf[4 * (C / 16)];
     float es[16], eb[16];
 };
+constexpr int DEC012_W0_KEPT = 4 * (128 / 16);   // block 0's fragment loads: what dec012_mfma leaves in flight across its first barrier
 template <int C, int COUT>
 __device__ __forceinline__ void dec012_load(Dec012W<C, COUT> &w, const half8 *wfrag, const float *epi, int wave, int lane) {
     constexpr int MT = 4 * COUT / 32, KSTEPS = 4 * (C / 16);
@@ -2003,15 +2033,17 @@ __device__ __forceinline__ void dec012_load(Dec012W<C, COUT> &w, const half8 *wf
     // opaque pointers: the fragments are loaded here, per frame and per block -- hoisted out of the frame loop the three
     // blocks' weights (320 registers) would be live together and spill
     asm volatile("" : "+s"(wfrag), "+s"(epi));
+    const gptr<half8> wg = as_global(wfrag);
+    const gptr<float> eg = as_global(epi);
 #pragma unroll
-    for (int ks = 0; ks < KSTEPS; ks++) w.wf[ks] = wfrag[(mtile * KSTEPS + ks) * 64 + lane];
+    for (int ks = 0; ks < KSTEPS; ks++) w.wf[ks] = wg[(mtile * KSTEPS + ks) * 64 + lane];
     // registers 4g .. 4g+3 <-> rows n0 .. n0+3, n0 = mtile*32 + 8g + 4kh: four consecutive channels, one 16-byte load
 #pragma unroll
     for (int gq = 0; gq < 4; gq++) {
         const int c0 = (mtile * 32 + 8 * gq + 4 * kh) % COUT;
-        const float4 sc = *reinterpret_cast<const float4 *>(epi + c0), sh = *reinterpret_cast<const float4 *>(epi + COUT + c0);
-        w.es[4 * gq] = sc.x; w.es[4 * gq + 1] = sc.y; w.es[4 * gq + 2] = sc.z; w.es[4 * gq + 3] = sc.w;
-        w.eb[4 * gq] = sh.x; w.eb[4 * gq + 1] = sh.y; w.eb[4 * gq + 2] = sh.z; w.eb[4 * gq + 3] = sh.w;
+        const f32x4 sc = *(gptr<f32x4>)(eg + c0), sh = *(gptr<f32x4>)(eg + COUT + c0);
+#pragma unroll
+        for (int j = 0; j < 4; j++) { w.es[4 * gq + j] = sc[j]; w.eb[4 * gq + j] = sh[j]; }
     }
 }
 template <int C1, int C2, int COUT, int CN>
@@ -2145,16 +2177,23 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
         if (b != (int)blockIdx.x) lds_barrier();
         PHASE_MARK(0);
         {
-            Dec012W<128, 64> w0;
-            dec012_load(w0, at_model(p.wf[0], moff), at_model(p.epi[0], moff), wave, lane);   // in flight together with the tiles
+            // The three tiles are requested FIRST, block 0's weights behind them, and the barrier waits for the tiles alone: the
+            // vector-memory counter returns in order, so "at most DEC012_W0_KEPT operations outstanding" says that everything
+            // older than the youngest DEC012_W0_KEPT has landed -- the tile requests are older than all of block 0's loads (32
+            // fragments, then its constants; the fragments cannot merge, so there are never fewer).  The weights stay in flight
+            // across the barrier and the first tile takes them fragment by fragment.  The scheduling barriers keep the three
+            // groups -- requests, loads, wait -- in this order.
             // (the rows of the three tiles start at different waves so that the requests spread evenly)
             dec012_stage<0, 128>(t0, p.skip[0] + (size_t)b * p.Ts[0] * p.lv[0].Hi * p.lv[0].Wi * 128, p.lv[0], wave, lane, 0);
             dec012_stage<64, 64>(t1, p.skip[1] + (size_t)b * p.Ts[1] * p.lv[1].Hi * p.lv[1].Wi * 64, p.lv[1], wave, lane, p.lv[0].Hi & 7);
             dec012_stage<32, 32>(t2, p.skip[2] + (size_t)b * p.Ts[2] * p.lv[2].Hi * p.lv[2].Wi * 32, p.lv[2], wave, lane,
                                  (p.lv[0].Hi + p.lv[1].Hi) & 7);
-            PHASE_MARK(1);   // requesting the three tiles (and block 0's weights)
-            wait_vmem();
-            lds_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+            Dec012W<128, 64> w0;
+            dec012_load(w0, at_model(p.wf[0], moff), at_model(p.epi[0], moff), wave, lane);
+            __builtin_amdgcn_sched_barrier(0);
+            PHASE_MARK(1);   // requesting the three tiles and block 0's weights
+            lds_barrier_vmem_but<DEC012_W0_KEPT>();
             PHASE_MARK(2);   // tiles landing
             dec012_block<0, 128, 64, 128>(smem, t0, t1, nullptr, nullptr, w0, p.lv[0], p.lv[1], wave, lane);
         }
