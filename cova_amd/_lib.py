@@ -264,6 +264,7 @@ PROTOTYPES = {
     "covahip_train_data_append": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.POINTER(C.c_int64)]),
     "covahip_train_data_frames": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "covahip_train_data_gather": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
+    "covahip_train_data_label_mass": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int]),
     "covahip_train_data_destroy": (None, [_P]),
     "covahip_train_step_data": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(C.c_float)]),
     "covahip_train_step_set_data": (C.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -255,6 +255,12 @@ int covahip_train_data_table(covahip_train_data *d, int n, covahip_train_sample 
 // stream.  The table is free again once the stream has passed the launch.
 int covahip_train_data_launch(covahip_train_data *d, int n, uint8_t *d_stack, uint8_t *d_gt);
 
+// label_mass.hip: d_mass[i] = the label mass of frame first + i of d_gt u8 [..][hw] for i in [0, n), n >= 1, in one launch on the
+// ctx's stream.  d_bits: the keep map as a bit per macroblock, u32 [(hw + 31) / 32] (bit p & 31 of word p >> 5), or null: the
+// form that reads none.
+int covahip_label_mass_launch(covahip_ctx *ctx, const uint8_t *d_gt, const uint32_t *d_bits, uint32_t *d_mass, int64_t first,
+                              int64_t n, int hw);
+
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);
 int covahip_blobnet_forward_dev(covahip_ctx *ctx, const uint8_t *d_stack, int batch, float *d_logits,

@@ -1,6 +1,7 @@
 // Device-resident training data (include/covahip.h, "Training data"): the frames of any number of recordings as two-byte
 // records (covahip_carrier_pack's packing) with their label bytes, and the launch that builds a training step's stacks and labels
-// from a table of frame indices, mirrored where a sample asks for it, straight into the trainer's staging.
+// from a table of frame indices, mirrored where a sample asks for it, straight into the trainer's staging.  The label mass of
+// the resident frames is served from here too (covahip_train_data_label_mass); its kernel lives in label_mass.hip.
 //
 // Storage: rec u16 [capacity][h][w], gt u8 [capacity][h][w]; every element offset is 64-bit (a 16x16 set of 8.5 M frames is 4.4 GB
 // of records).  A frame of an odd h * w starts on an odd element, so the read side relies on 2-byte alignment only.
@@ -70,6 +71,7 @@ struct covahip_train_data {
     size_t stage_bytes = 0;
     std::vector<uint16_t> pack;                                 // host staging of a host append
     size_t stage_budget = STAGE_BYTES;                          // covahip_dev_train_data_set_stage changes it per set
+    ResidentTable<uint32_t> keep_bits;                          // label mass: the call's keep map, a bit per macroblock; reserved on first use
 };
 
 namespace {
@@ -85,6 +87,7 @@ void free_data(covahip_train_data *d) {
     if (d->d_tab) hipFree(d->d_tab);
     if (d->h_tab) hipHostFree(d->h_tab);
     if (d->stage) hipFree(d->stage);
+    d->keep_bits.release();
     delete d;
 }
 
@@ -228,6 +231,48 @@ int covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample 
         }
         COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the table and the staging are reused by the next chunk
     }
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t n, const uint8_t *keep_or_null, uint32_t *mass,
+                                  int mem_kind) {
+    if (!d || !mass || n < 1 || first < 0 || (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE))
+        return COVAHIP_ERR_INVALID_ARG;
+    if (n > d->frames || first > d->frames - n) return COVAHIP_ERR_INVALID_ARG;
+    const bool host = mem_kind == COVAHIP_MEM_HOST;
+    if (!host && (reinterpret_cast<uintptr_t>(mass) & 3u)) return COVAHIP_ERR_INVALID_ARG;   // the launch stores whole counts
+    const int hw = d->h * d->w;
+    const size_t nw = ((size_t)hw + 31) / 32;
+    std::vector<uint32_t> bits;
+    if (keep_or_null) {
+        bits.assign(nw, 0u);
+        bool any = false;
+        for (int i = 0; i < hw; i++)
+            if (keep_or_null[i]) bits[(size_t)i >> 5] |= 1u << (i & 31), any = true;
+        if (!any) return COVAHIP_ERR_INVALID_ARG;   // nothing would count
+    }
+    covahip_ctx *ctx = d->ctx;
+    if (int rc = enter(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const uint32_t *d_bits = nullptr;
+    if (keep_or_null) {
+        if (int rc = d->keep_bits.reserve(ctx, nw)) return rc;
+        if (int rc = d->keep_bits.upload(ctx, bits.data(), nw, &d_bits)) return rc;
+    }
+    // a launch sequence's frames: all of them, or for host output what the staging holds
+    const int64_t chunk = host ? std::min<int64_t>(n, (int64_t)std::max<size_t>(1, d->stage_budget / sizeof(uint32_t))) : n;
+    if (host)
+        if (int rc = covahip_ensure_buffer(ctx, &d->stage, &d->stage_bytes, (size_t)chunk * sizeof(uint32_t))) return rc;
+    for (int64_t at = 0; at < n; at += chunk) {
+        const int64_t m = std::min(chunk, n - at);
+        uint32_t *out = host ? static_cast<uint32_t *>(d->stage) : mass + at;
+        if (int rc = covahip_label_mass_launch(ctx, d->gt, d_bits, out, first + at, m, hw)) return rc;
+        if (host) {
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(mass + at, out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the staging is written again by the next chunk
+        }
+    }
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
     return COVAHIP_OK;
 }
 

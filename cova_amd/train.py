@@ -9,7 +9,8 @@
   TrainData       frames and labels resident on the device (.append / .append_device from host / device memory, .gather /
                   .gather_device: the batch a sample array describes, to host / device memory)
   windows         the windows of a model's recordings as a table; epoch_samples: the table as one epoch's sample array, reordered,
-                  mirrored, reversed; plain_samples: the table's windows as they are (validation, scoring); split_frames_tail
+                  mirrored, reversed; plain_samples: the table's windows as they are (validation, scoring); split_frames_tail;
+                  balanced_samples: an epoch redrawn half from busy, half from quiet samples (TrainData.label_mass)
                   TrainerSet / Trainer .step_data, .evaluate_data, .fit_data take their batches from a TrainData by such arrays
 
     python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
@@ -65,6 +66,16 @@ table of frame indices (windows, epoch_samples; TrainerSet.fit_data / evaluate_d
 crosses; --windows overlap takes all F - 3 windows of F frames instead of F / 4; --stride, --flip and --reverse are drawn per
 sample and epoch and --shuffle reorders every epoch, all as pure functions of (--data-seed, epoch, model), so --resume with the
 same flags continues exactly.  Validation windows are never augmented.  Without these flags the program runs as it always has.
+
+Balanced epochs (utils/data/balance.py of the reference): most windows of a surveillance recording are empty road,
+
+    python -m cova_amd.train CAM.tfrecord -o blobnet.cvhw --windows overlap --shuffle --balance 100
+
+--balance N also trains from the resident data set.  A window is busy when the frame that labels it carries at least N labelled
+macroblocks outside the camera's ignore region (counted on the device, TrainData.label_mass; the reference uses 100 at 45x80);
+every epoch keeps its length and draws each sample from the busy or the quiet windows with probability 1/2, each half walked in
+the epoch's order (balanced_samples).  The draws are a pure function of (--data-seed, epoch, model) too, and --resume takes
+--balance from the command line again.  Validation windows are never balanced, and --eval-only refuses the flag.
 """
 from __future__ import annotations
 
@@ -590,6 +601,13 @@ def windows(segments, mode: str = "skip", strides=(1,)) -> np.ndarray:
     return np.concatenate(rows) if rows else np.zeros((0, 2), np.int64)
 
 
+def _draws(data_seed: int, epoch: int, model: int, site: int, n: int) -> np.ndarray:
+    """r(site, i) for i in [0, n) of epoch_samples' docstring, u64 [n]."""
+    word = ((int(epoch) << 20) | (int(model) << 4)) & _M64
+    key = splitmix64(np.uint64(int(data_seed) & _M64) ^ splitmix64(np.uint64(word | site)))
+    return splitmix64(key + np.arange(n, dtype=np.uint64))
+
+
 def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model: int = 0, shuffle: bool = False, flip=(),
                   reverse: bool = False) -> np.ndarray:
     """The covahip_train_sample array (dtype SAMPLE) of one epoch of one model over a windows() table: a pure function of its
@@ -609,12 +627,9 @@ def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model
     if any(c not in ("x", "y") for c in flip):
         raise ValueError(f"flip = {flip!r}: 'x', 'y', both or neither")
     n = table.shape[0]
-    idx = np.arange(n, dtype=np.uint64)
-    word = ((int(epoch) << 20) | (int(model) << 4)) & _M64
 
     def r(site):
-        key = splitmix64(np.uint64(int(data_seed) & _M64) ^ splitmix64(np.uint64(word | site)))
-        return splitmix64(key + idx)
+        return _draws(data_seed, epoch, model, site, n)
 
     start, k = table[:, 0], table[:, 1]
     fits = np.stack([k - (W.T - 1) * s >= start for s in strides], axis=1) if n else np.zeros((0, len(strides)), bool)
@@ -643,6 +658,37 @@ def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model
 def plain_samples(table, stride: int = 1) -> np.ndarray:
     """The table's windows as they are: canonical order, forward, unmirrored, at `stride` (validation and scoring)."""
     return epoch_samples(table, (stride,))
+
+
+def balanced_samples(samples, mass, threshold: int, *, mass_first: int = 0, data_seed: int = 0, epoch: int = 0,
+                     model: int = 0) -> np.ndarray:
+    """An epoch's SAMPLE array redrawn so that busy and quiet samples come up with probability 1/2 each (the reference's
+    utils/data/balance.py, threshold 100 at 45x80): as many samples as given, a pure function of its arguments.
+    mass[i] = the label mass of frame mass_first + i (TrainData.label_mass).  A sample is busy when the mass of the frame that
+    LABELS it -- the oldest frame of a reversed window -- is at least `threshold`.  B = the busy samples and Q = the quiet ones,
+    each in the order given; either one empty is a ValueError (the reference would run an empty epoch).  With epoch_samples' key
+    at site 5 and i the DRAW POSITION, c[j] = r(5, j) >> 63; nb[j] = the busy draws before j and nq[j] = j - nb[j]:
+        out[j] = B[nb[j] mod len(B)] if c[j] else Q[nq[j] mod len(Q)]
+    so each half is walked in order and wraps, as the reference's .repeat() does.  A sample drawn twice in an epoch carries the
+    same stride, mirrors and direction both times: epoch_samples keys those draws by the window's canonical index, not by where
+    the sample stands in the epoch."""
+    samples = _samples(samples)
+    mass = np.asarray(mass).reshape(-1)
+    if not (0 <= int(model) < 1 << 16 and 0 <= int(epoch) < 1 << 44):
+        raise ValueError(f"model = {model}, epoch = {epoch}: 0 <= model < 2^16 and 0 <= epoch < 2^44")
+    at = samples["label"].astype(np.int64) - int(mass_first)
+    if at.size and (at.min() < 0 or at.max() >= mass.size):
+        raise ValueError(f"mass covers frames [{mass_first}, {int(mass_first) + mass.size}), the samples are labelled by frames "
+                         f"{int(at.min()) + int(mass_first)} .. {int(at.max()) + int(mass_first)}")
+    busy = mass[at] >= threshold
+    b, q = np.flatnonzero(busy), np.flatnonzero(~busy)
+    if not b.size or not q.size:
+        raise ValueError(f"balance: {b.size} busy and {q.size} quiet samples at threshold {threshold}: both halves need at least one")
+    n = samples.shape[0]
+    c = (_draws(data_seed, epoch, model, 5, n) >> np.uint64(63)).astype(np.int64)
+    nb = np.cumsum(c) - c
+    nq = np.arange(n, dtype=np.int64) - nb
+    return np.ascontiguousarray(samples[np.where(c != 0, b[nb % b.size], q[nq % q.size])])
 
 
 def split_frames_tail(segments, frac: float):
@@ -729,6 +775,29 @@ class TrainData:
         samples = _samples(samples)
         L.check(self._lib.covahip_train_data_gather(self.handle, samples.ctypes.data, samples.shape[0], d_stack, d_gt, L.MEM_DEVICE),
                 "covahip_train_data_gather", self.ctx.handle)
+
+    def _label_mass(self, first, n, keep, p_mass, kind):
+        first = int(first)
+        n = self.frames - first if n is None else int(n)
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if keep.shape != (self.h, self.w):
+                raise ValueError(f"keep must be [{self.h}][{self.w}], got {keep.shape}")
+        mass = np.empty(max(n, 0), np.uint32) if p_mass is None else None
+        L.check(self._lib.covahip_train_data_label_mass(self.handle, first, n, None if keep is None else keep.ctypes.data,
+                                                        mass.ctypes.data if p_mass is None else p_mass, kind),
+                "covahip_train_data_label_mass", self.ctx.handle)
+        return mass
+
+    def label_mass(self, first: int = 0, n: int | None = None, keep=None) -> np.ndarray:
+        """u32 [n]: per frame of [first, first + n) (n None: up to `frames`) the number of macroblocks with a non-zero label
+        byte, among those `keep` (u8 [h][w], non-zero = kept; None: all) keeps -- the label sum the loss of a camera with that
+        ignore region sees, counted on the device (balanced_samples)."""
+        return self._label_mass(first, n, keep, None, L.MEM_HOST)
+
+    def label_mass_device(self, d_mass: int, first: int = 0, n: int | None = None, keep=None) -> None:
+        """The same into device memory: u32 [n] at d_mass, 4-byte aligned."""
+        self._label_mass(first, n, keep, d_mass, L.MEM_DEVICE)
 
 
 def _samples(samples) -> np.ndarray:
@@ -1074,16 +1143,36 @@ class TrainerSet(_State):
             at += n
         return outs
 
+    def _masses(self, data, tables, balance, log):
+        """fit_data(balance=...): per model (first frame, label mass of the frames its table spans, under its post's keep map)."""
+        out = []
+        for k, t in enumerate(tables):
+            lo, hi = int(t[:, 0].min()), int(t[:, 1].max()) + 1
+            post = self.get_post(k)
+            keep = None if post is None or post[1].all() else post[1]
+            mass = data.label_mass(lo, hi - lo, keep)
+            busy = int((mass[t[:, 1] - lo] >= balance).sum())
+            if log:
+                log(f"{f'model {k}: ' if self._tag_models else ''}balance {balance}: {busy} busy / {t.shape[0] - busy} quiet windows")
+            out.append((lo, mass))
+        return out
+
     def fit_data(self, data, tables_per_model, epochs: int = 20, batch: int = 4, *, strides=(1,), shuffle: bool = False, flip=(),
                  reverse: bool = False, data_seed: int = 0, val_tables=None, schedule=keras_lr, log=None, keep: str = "last",
-                 checkpoint=None, start_epoch: int = 0):
+                 checkpoint=None, start_epoch: int = 0, balance: int | None = None):
         """fit() from a resident TrainData: tables_per_model[k] = model k's windows() table, and every epoch walks
         epoch_samples(table, strides, data_seed, epoch, model = k, shuffle, flip, reverse) of it -- a new order and new mirrors
         every epoch, a pure function of (data_seed, epoch, k), so a resumed run continues exactly.  Everything else is fit's:
         set_epoch_plan, the partial last batch, the histories, keep="best", the checkpoints.  val_tables = one table per model,
         scored after every epoch as they are, at min(strides), never shuffled or augmented.  With windows(mode="skip") and no
         augmentation this is fit(slide(...)), bit for bit.  The augmentation settings are not part of the checkpoint: a resumed
-        run passes them again, like the plan and the post."""
+        run passes them again, like the plan and the post.
+        balance = a label-mass threshold (the reference's 100 at 45x80): every epoch becomes balanced_samples(epoch_samples(...),
+        mass, balance, ...) with the same data_seed, epoch and model -- as many samples, half of the draws busy.  Model k's masses
+        are taken once, before the first epoch, under the keep map of ITS post if it has one (TrainData.label_mass), and the
+        log gains one line per model with the busy / quiet windows of its table (each classed by its newest frame, the label of
+        the forward window).  Validation tables are never balanced.  Like the augmentation settings `balance` is not in the
+        checkpoint; None runs exactly what ran before the keyword existed."""
         _check_fit_args(val_tables, keep)
         if len(tables_per_model) != self.n_models:
             raise ValueError(f"{len(tables_per_model)} tables for {self.n_models} models")
@@ -1098,11 +1187,15 @@ class TrainerSet(_State):
         if min(sizes) == 0:
             raise ValueError("no training samples")
         current = {}
+        masses = None if balance is None else self._masses(data, tables, balance, log)
 
         def take_step(ep, st, lr):
             if current.get("epoch") != ep:
                 current["epoch"] = ep
                 current["samples"] = [epoch_samples(t, strides, data_seed, ep, k, shuffle, flip, reverse) for k, t in enumerate(tables)]
+                if masses is not None:
+                    current["samples"] = [balanced_samples(s, mass, balance, mass_first=lo, data_seed=data_seed, epoch=ep, model=k)
+                                          for k, (s, (lo, mass)) in enumerate(zip(current["samples"], masses))]
             return self.step_data(data, [current["samples"][k][a:a + n] for k, (a, n) in enumerate(st)], lr)
 
         return self._epochs(sizes, epochs, batch, schedule, log, keep, checkpoint, start_epoch, take_step,
@@ -1245,9 +1338,17 @@ def parse_args(argv=None):
     ap.add_argument("--reverse", action="store_true", help="reverse samples in time, drawn per sample and epoch")
     ap.add_argument("--shuffle", action="store_true", help="a new sample order every epoch")
     ap.add_argument("--data-seed", type=int, metavar="N", help="seed of the order and the augmentation draws (default 0)")
+    ap.add_argument("--balance", type=int, metavar="N", help="draw every epoch half from the busy windows, whose labelling frame "
+                                                             "carries at least N labelled macroblocks the camera keeps, and half "
+                                                             "from the quiet ones (the reference's utils/data/balance.py: 100 at "
+                                                             "45x80); trains from the device-resident data set")
     a = ap.parse_args(argv)
     a.resident = (a.windows is not None or a.stride is not None or a.flip is not None or a.reverse or a.shuffle
-                  or a.data_seed is not None)
+                  or a.data_seed is not None or a.balance is not None)
+    if a.eval_only and a.balance is not None:
+        ap.error("--balance shapes a training's epochs; --eval-only scores every window once")
+    if a.balance is not None and a.balance < 1:
+        ap.error("--balance is a count of macroblocks, at least 1")
     if a.eval_only and (a.flip or a.reverse or a.shuffle or a.data_seed is not None):
         ap.error("--flip / --reverse / --shuffle / --data-seed shape a training; --eval-only trains nothing")
     if a.eval_only and a.stride is not None and len(a.stride) != 1:
@@ -1471,7 +1572,7 @@ def main_set(a) -> int:
 
 
 def main_resident(a) -> int:
-    """Training or scoring from a device-resident data set (--windows / --stride / --flip / --reverse / --shuffle / --data-seed):
+    """Training or scoring from a device-resident data set (--windows / --stride / --flip / --reverse / --shuffle / --data-seed / --balance):
     every file is one segment, one data set serves all models of a --set, and the samples of an epoch are epoch_samples of the
     model's windows."""
     from .elements import Context
@@ -1523,7 +1624,7 @@ def main_resident(a) -> int:
         start = _resume(ts, a, len(jobs))
         ts.fit_data(data, tables, epochs=a.epochs, batch=a.batch, strides=strides, shuffle=a.shuffle, flip=a.flip or (),
                     reverse=a.reverse, data_seed=a.data_seed or 0, val_tables=val_tables, log=lambda s: print(s, file=sys.stderr),
-                    keep=a.keep, checkpoint=a.checkpoint, start_epoch=start)
+                    keep=a.keep, checkpoint=a.checkpoint, start_epoch=start, balance=a.balance)
         for k, (_, out) in enumerate(jobs):
             with open(out, "wb") as f:
                 f.write(ts.best_weights_bytes(k) if a.keep == "best" else ts.weights_bytes(k))

@@ -713,13 +713,26 @@ typedef struct covahip_train_sample {   /* 24 bytes */
  * Device pointers: frames and gt any alignment (frames off a 4-byte boundary are read byte by byte).
  * covahip_train_data_gather: the batch itself, for a caller that wants to see it (mem_kind applies to stack and gt).  A DEVICE
  * stack must be 4-byte aligned (the launch stores a record's four bytes at once): COVAHIP_ERR_INVALID_ARG otherwise; a device
- * gt may have any alignment (label bytes are stored one at a time). */
+ * gt may have any alignment (label bytes are stored one at a time).
+ * covahip_train_data_label_mass: how much label each of the frames [first, first + n) carries AS A CAMERA IS SERVED, for a
+ * sampler that wants to tell busy frames from quiet ones (utils/data/balance.py's reduce_sum(y) >= threshold) without taking
+ * the labels off the device:
+ *       mass[i] = the number of macroblocks (y, x) of frame first + i with gt != 0 (the trainer's `lab`) and keep'[y,x],
+ *       keep'[y,x] = keep ? keep[y,x] != 0 : 1 (covahip_train_set_post's definition; keep_or_null is a HOST array u8 [h_mb * w_mb]).
+ *   Integer counts, exact; for 0 / 1 labels without a keep map the reference's label sum.  A label byte at an ignored macroblock
+ *   counts nothing whatever its value (Contract G).  mem_kind applies to `mass` (a DEVICE mass must be 4-byte aligned); one launch
+ *   sequence serves any n up to the capacity, and a host mass moves through the data set's staging.
+ *   COVAHIP_ERR_INVALID_ARG, checked on the host before anything is launched and with nothing written: a NULL d or mass, n < 1,
+ *   first < 0, first + n > frames, an unknown mem_kind, a misaligned device mass, or a keep map without a single non-zero byte
+ *   (as covahip_train_set_post refuses it). */
 int  covahip_train_data_create(covahip_ctx *ctx, int h_mb, int w_mb, int64_t capacity_frames, covahip_train_data **out);
 int  covahip_train_data_append(covahip_train_data *d, const uint8_t *frames, const uint8_t *gt, int n, int mem_kind,
                                int64_t *first_index);
 int  covahip_train_data_frames(const covahip_train_data *d, int64_t *n);
 int  covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample *samples, int n, uint8_t *stack, uint8_t *gt,
                                int mem_kind);
+int  covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t n, const uint8_t *keep_or_null, uint32_t *mass,
+                                   int mem_kind);
 void covahip_train_data_destroy(covahip_train_data *d);
 /* covahip_train_step / _step_set / _eval / _eval_set on samples of a data set: the gather launch writes the batch straight into
  * the trainer's own staging, in the packing the step expects; nothing is copied from the host but the table.  samples: packed in
