@@ -299,6 +299,7 @@ DEV_PROTOTYPES = {
                                           C.POINTER(C.c_float)]),
     "covahip_dev_bboxcc_overflow": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "covahip_dev_blobnet_tail_form": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "covahip_dev_blobnet_tail_in_dec012": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "covahip_dev_pipe_queue_plan": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "covahip_dev_blobnet_buffer": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_int32)]),
     "covahip_dev_mog_masks": (C.c_int, [_P, _P, _P, _SZ, C.POINTER(C.c_int)]),

@@ -26,6 +26,9 @@ struct BnWorkspace {
     // the level-0 skip connection's share of the logits (round 5): fp32 [B][H_1 + 1][W_1 + 1][4], written by the level-1 kernel, added by the last
     // decoder block -- the skip tensor itself (act[1]) is then neither written nor read
     float *part = nullptr;
+    // bboxcc's parity planes per frame, u32 [B][2 * ceil(H / 2) + 2][E lo, E hi, O lo, O hi]: written by dec012_mfma<.., TAILF>, read by
+    // cc_planes (the form in which the last decoder block runs inside the decoder launch)
+    uint32_t *planes = nullptr;
     // The lane's small tables (internal.h, ResidentTable), each reserved once, on first use, for max_batch:
     ResidentTable<int32_t> index;     // stack -> frame table of a carrier-frame call, i32 [batch][4]; 4 * max_batch ints
     int index_frames = 0;             // n_frames of the call `index` was uploaded for: part of what "resident" means there
@@ -51,6 +54,8 @@ struct covahip_blobnet {
     int fuse_dec = 1;  // MFMA path: decoder blocks 0..2 as one launch (a frame's three input tiles side by side in LDS) when they fit
     int enc1_tile16 = 1;  // MFMA path: level 1 on 16-position tiles (enc1_mfma) where the row fits its fixed LDS stride
     int tail_rows = 1;    // MFMA path: the fused tail on row tiles with ballots straight into bboxcc's planes (dec3cc_rows_mfma, round 6)
+    int tail_in_dec012 = 1;   // MFMA path: the last block inside dec012_mfma, bboxcc alone behind it (cc_planes) -- 1: where it applies and
+                              // the batch fills the chip, 2: wherever it applies, 0: never
     int tail_part = 1;    // MFMA path: the last decoder block's skip half computed by the level-1 kernel as partial logits (enc1_mfma only)
     int fuse_enc23 = 1;   // MFMA path: encoder levels 2 + 3 in one launch (enc23_mfma: level 2's output stays in LDS as level 3's band) when they fit
                           // and the batch / geometry make it pay; 0: never, 2: whenever they fit

@@ -24,6 +24,7 @@ static void free_model(covahip_ctx *ctx, covahip_blobnet *m) {
             if (ws.dact[j]) hipFree(ws.dact[j]);
         if (ws.pbuf) hipFree(ws.pbuf);
         if (ws.part) hipFree(ws.part);
+        if (ws.planes) hipFree(ws.planes);
         ws.index.release();
         ws.models.release();
         ws.areas.release();
@@ -213,6 +214,7 @@ static int alloc_workspace(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws
         COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.dact[j], n * sizeof(__half)));
     }
     COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.part, (size_t)m->max_batch * (m->lv[1].H + 1) * (m->lv[1].W + 1) * 4 * sizeof(float)));
+    COVAHIP_CHECK_HIP(ctx, hipMalloc((void **)&ws.planes, (size_t)m->max_batch * (2 * ((m->H + 1) / 2) + 2) * 16));
     ws.ready = true;
     return COVAHIP_OK;
 }
@@ -451,13 +453,14 @@ int covahip_blobnet_set_enc_plan(covahip_ctx *ctx, int level, int nbands, int nb
 
 int covahip_blobnet_set_impl(covahip_ctx *ctx, int impl) {
     if (!ctx || !ctx->blobnet) return COVAHIP_ERR_NOT_LOADED;
-    if (impl != 1 && (impl < 4 || impl > 10)) return COVAHIP_ERR_INVALID_ARG;
+    if (impl != 1 && (impl < 4 || impl > 12)) return COVAHIP_ERR_INVALID_ARG;
     ctx->blobnet->fuse_dec = impl != 4;
     ctx->blobnet->enc1_tile16 = impl != 5;
     ctx->blobnet->enc_rowtiles = impl != 6;
     ctx->blobnet->fuse_enc23 = impl == 7 ? 0 : impl == 8 ? 2 : 1;
     ctx->blobnet->tail_part = impl != 9;
     ctx->blobnet->tail_rows = impl != 10;
+    ctx->blobnet->tail_in_dec012 = impl == 11 ? 2 : impl == 12 ? 0 : 1;
     return COVAHIP_OK;
 }
 
@@ -591,6 +594,12 @@ int covahip_filter_forward_frames_packed_m(covahip_ctx *ctx, const uint16_t *d_r
 int covahip_dev_blobnet_tail_form(covahip_ctx *ctx, int *form) {
     if (!ctx || !form) return COVAHIP_ERR_INVALID_ARG;
     *form = ctx->tail_form;
+    return COVAHIP_OK;
+}
+
+int covahip_dev_blobnet_tail_in_dec012(covahip_ctx *ctx, int *in_dec012) {
+    if (!ctx || !in_dec012) return COVAHIP_ERR_INVALID_ARG;
+    *in_dec012 = ctx->tail_in_dec012;
     return COVAHIP_OK;
 }
 

@@ -93,6 +93,11 @@ __device__ __forceinline__ uint32_t model_off(const uint8_t *mid, uint32_t strid
     if constexpr (!MS) return 0u;
     else return __builtin_amdgcn_readfirstlane((uint32_t)mid[idx] * stride);
 }
+// A vector value the compiler cannot see through: what is computed from it stays where it is written (is not hoisted out of a loop)
+__device__ __forceinline__ int opaque_v(int v) {
+    asm volatile("" : "+v"(v));
+    return v;
+}
 template <typename T>
 __device__ __forceinline__ const T *at_model(const T *ptr, uint32_t off) {
     return reinterpret_cast<const T *>(reinterpret_cast<const uint8_t *>(ptr) + off);
@@ -1979,6 +1984,23 @@ struct Dec012Args {
     const uint8_t *model_ids;   // MS: model id per stack [B]
     uint32_t mstride;           // MS: bytes between two models' prepared weights
 };
+// dec012_mfma<.., TAILF>: the folded last block runs behind block 2, on block 2's output in LDS, and the launch ends in bboxcc's
+// parity planes (cc_planes takes them from there).  The kernel's own argument behind Dec012Args, so that the form without it keeps
+// its argument layout (it gets the empty Dec012NoTail).
+struct Dec012Tail {
+    DecLvl lv;                  // the last block: Hi x Wi = block 2's output, Hd x Wd = the frame; tile_off: the tile t3
+    const half8 *wfrag;         // the four folded fragments of the "up" half (Prepared::final_w_up)
+    const float *epi;           // the folded bias
+    const float *part;          // partial logits, fp32 [B][Hi + 1][Wi + 1][4]
+    float *logits;              // [B][Hd][Wd] or null
+    uint8_t *mask;              // [B][Hd][Wd] or null
+    uint32_t *planes_out;       // [B][rows_bytes / 4]: the frames' parity planes (BnWorkspace::planes)
+    int planes_off, rows_bytes; // the planes in LDS (ccwave::WvGeom::rows_bytes)
+    uint32_t mW4;               // magic(Wd / 4): the mask expansion's division
+};
+struct Dec012NoTail {};
+template <bool TAILF>
+using Dec012TailArg = std::conditional_t<TAILF, Dec012Tail, Dec012NoTail>;
 
 // The border of a block's tile (the zero padding of the transposed convolution's input) is written once per launch:
 // nothing ever overwrites it, interior pixels are refilled for every frame (skip half by DMA, "up" half by the block
@@ -2097,7 +2119,35 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
             if (ks + AD < KSTEPS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
         }
-        if constexpr (CN > 0) {
+        if constexpr (CN > 0 && COUT == 16) {
+            // Block 2 into the row tail's tile (dec012_mfma<.., TAILF>; CN = 16 channels of 32 bytes per pixel, the 16-byte halves
+            // swizzled by (xx >> 3) & 1).  Rows n0 + j, n0 = mtile*32 + 8 gq + 4 kh, with COUT = 16: parity 2 mtile + (gq >> 1), channels
+            // 8 (gq & 1) + 4 kh + j -- a lane's four register groups are TWO output pixels (px = 0, 1 of output row 2u + mtile) x two
+            // 8-channel chunks, of which it holds four channels each: two bounds tests, four 8-byte writes
+            static_assert(CN == 16 && MT == 2, "the row tail's tile");
+            const int TCN = gn.Wi + 2;
+            const int Y = 2 * u + mtile - g.cy;
+            if (q < npos && Y >= 0 && Y < g.Hd) {
+#pragma unroll
+                for (int px = 0; px < 2; px++) {
+                    const int X = 2 * v + px - g.cx;
+                    if (X >= 0 && X < g.Wd) {
+                        const int yy = Y + 1, xx = X + 1;
+                        uint8_t *const pix = next_tile + (yy * TCN + xx) * 32 + kh * 8;
+                        const int sw = (xx >> 3) & 1;
+#pragma unroll
+                        for (int c = 0; c < 2; c++) {
+                            const int gq = 2 * px + c;
+                            half4 o;
+#pragma unroll
+                            for (int j = 0; j < 4; j++)
+                                o[j] = (_Float16)fmaxf(acc[4 * gq + j] * es[4 * gq + j] + eb[4 * gq + j], 0.f);
+                            *reinterpret_cast<half4 *>(pix + ((c ^ sw) * 16)) = o;
+                        }
+                    }
+                }
+            }
+        } else if constexpr (CN > 0) {
             // reg 4g+j <-> row n0 + j, n0 = mtile*32 + 8g + 4kh: one parity, four consecutive channels
             constexpr int CPPN = CN / 8, PSN = CN * 2;
             const int TCN = gn.Wi + 2;
@@ -2156,26 +2206,142 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
     }
 }
 
-template <bool MS = false>
-__global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
+// ---- the row tail's pieces that dec3cc_rows_mfma and dec012_mfma<.., TAILF> share (the kernels' comments say what they are)
+// lane constants of the two tile halves x two tap columns: pixel column xx = 32 h + pos + 1 - bb (clamped to the grid's last
+// position: lanes past the row's end compute on that pixel and are masked out of the ballots)
+__device__ __forceinline__ void tail_row_lanes(uint32_t (&lc)[2][2], int GW, int lane) {
+    const int kh = lane >> 5, pos = lane & 31;
+#pragma unroll
+    for (int h = 0; h < 2; h++)
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) {
+            const int xx = min(32 * h + pos, GW - 1) + 1 - bb;
+            lc[h][bb] = (uint32_t)(xx * 32 + ((kh ^ ((xx >> 3) & 1)) << 4));
+        }
+}
+// One row tile: half h of grid row u of frame b.  tile: the frame's [Hi + 2][Wi + 2] pixels of 16 channels (row_b bytes per row);
+// pl: the tile's partial logits (position u * GW + min(32 h + pos, GW - 1)); planes: [2 BH + 2][E lo, E hi, O lo, O hi] in LDS.
+// tail_row_acc: the tile's four products; tail_row_out: logits, ballots, planes; tail_row_tile: both.
+__device__ __forceinline__ f32x16 tail_row_acc(const uint8_t *tile, uint32_t row_b, const uint32_t (&lc)[2][2], const half8 (&wf)[4], int u, int h) {
+    const uint32_t rb = (uint32_t)(u * row_b);   // tile row u holds input row u - 1 (tap a = 1); tap a = 0 one row further
+    const uint32_t a00 = rb + row_b + (h ? lc[1][0] : lc[0][0]), a01 = rb + row_b + (h ? lc[1][1] : lc[0][1]);
+    const uint32_t a10 = rb + (h ? lc[1][0] : lc[0][0]), a11 = rb + (h ? lc[1][1] : lc[0][1]);
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[0], *reinterpret_cast<const half8 *>(tile + a00), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[1], *reinterpret_cast<const half8 *>(tile + a01), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[2], *reinterpret_cast<const half8 *>(tile + a10), acc, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[3], *reinterpret_cast<const half8 *>(tile + a11), acc, 0, 0, 0);
+    return acc;
+}
+__device__ __forceinline__ void tail_row_out(const f32x16 acc, const f32x4 pl, float fbias, float thr, float *logits, int Hd, int Wd, int cy, int cx,
+                                             int GW, int b, int u, int h, int lane, uint32_t *planes) {
+    const int kh = lane >> 5, pos = lane & 31;
+    const int v = 32 * h + pos;
+    const bool live = kh == 0 && v < GW;
+    float l[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) l[r] = (acc[r] + fbias) + pl[r];
+    if (logits && live) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int Y = 2 * u + (r >> 1) - cy, X = 2 * v + (r & 1) - cx;
+            if (Y >= 0 && Y < Hd && X >= 0 && X < Wd) logits[((size_t)b * Hd + Y) * Wd + X] = l[r];
+        }
+    }
+    // bit v - 32 h of parity r's ballot = output pixel (Y, 2 v + X0): plane X0 & 1, plane bit v + (X0 >> 1).  Lane r < 4 takes parity
+    // r's ballot, shifts it by the crop offset and ORs it into the row's 64-bit plane word: one masked ds_or_b64 per tile
+    uint32_t bal[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) bal[r] = (uint32_t)__ballot(live && l[r] > thr);
+    {
+        const int r = lane & 3;
+        const uint64_t bits = (uint64_t)(r == 0 ? bal[0] : r == 1 ? bal[1] : r == 2 ? bal[2] : bal[3]) << (32 * h);
+        const int Y = 2 * u + (r >> 1) - cy, X0 = (r & 1) - cx;
+        const int pln = X0 & 1, sh = X0 >> 1;                         // (arithmetic shift: floor)
+        const int nb = (Wd - pln + 1) >> 1;                            // pixels of this plane in a row
+        uint64_t w = sh >= 0 ? bits << sh : bits >> (-sh);
+        w &= nb >= 64 ? ~0ull : ((1ull << nb) - 1);
+        if (lane < 4 && Y >= 0 && Y < Hd && w)
+            atomicOr(reinterpret_cast<unsigned long long *>(planes + (Y + 1) * 4 + 2 * pln), (unsigned long long)w);
+    }
+}
+__device__ __forceinline__ void tail_row_tile(const uint8_t *tile, uint32_t row_b, const uint32_t (&lc)[2][2], const half8 (&wf)[4], const f32x4 pl,
+                                              float fbias, float thr, float *logits, int Hd, int Wd, int cy, int cx, int GW, int b, int u,
+                                              int h, int lane, uint32_t *planes) {
+    tail_row_out(tail_row_acc(tile, row_b, lc, wf, u, h), pl, fbias, thr, logits, Hd, Wd, cy, cx, GW, b, u, h, lane, planes);
+}
+// the frame's mask bytes out of its planes: four bytes per thread and store (W is a multiple of 8: ccwave::wv_plan; dst 4-byte aligned)
+template <int NTH>
+__device__ __forceinline__ void tail_mask_from_planes(const uint32_t *planes, uint8_t *mask_frame, int Hd, int Wd, uint32_t mW4, int tid) {
+    uint32_t *dst = reinterpret_cast<uint32_t *>(mask_frame);
+    const int wq = Wd >> 2, nq = Hd * wq;
+    for (int i = tid; i < nq; i += NTH) {
+        const int y = fdiv(i, mW4), xq = i - y * wq;   // (mW4 = magic(Wd / 4))
+        const int bx = 2 * xq;
+        const uint32_t *rw = planes + (y + 1) * 4 + (bx >> 5);
+        const uint32_t e2 = (rw[0] >> (bx & 31)) & 3u, o2 = (rw[2] >> (bx & 31)) & 3u;
+        dst[i] = (e2 & 1u) | ((o2 & 1u) << 8) | ((e2 >> 1) << 16) | ((o2 >> 1) << 24);
+    }
+}
+
+// What dec012_mfma<.., TAILF>'s fold holds in registers from in front of block 2 on, so that their loads land under block 2's tiles
+// (block 2 leaves a third of the kernel's registers free): the four folded fragments, the bias, and the partial logits of the
+// wave's first DEC012_PF tiles.  A wave takes DEC012_TI tiles per iteration -- a tile is ONE dependent chain (read, four products,
+// compare, ballot, ds_or), and the fold has two waves per SIMD to hide it with -- and keeps the partial logits of two iterations.
+constexpr int DEC012_TI = 3, DEC012_PF = 2 * DEC012_TI;
+struct Dec012Fold {
+    half8 wf[4];
+    f32x4 ring[DEC012_PF];
+    float fbias;
+};
+struct Dec012NoFold {};
+// the partial logits of the wave's tile t of frame b, one 16-byte load per position (the kh == 0 lanes hold the four parities'
+// accumulator rows; the others load the same addresses).  No branch around the load -- past the frame's last tile it reads that
+// tile's again, for nothing: behind a divergent branch the compiler loses count of the loads in flight and waits for ALL of them,
+// the ones just issued for two iterations ahead included
+__device__ __forceinline__ f32x4 dec012_part(const Dec012Tail &pt, int b, int t, int lane) {
+    const int GW = pt.lv.Wi + 1, GH = pt.lv.Hi + 1, tpr = GW > 32 ? 2 : 1;
+    const int tc = min(t, tpr * GH - 1);
+    const int u = tpr == 2 ? tc >> 1 : tc, h = tpr == 2 ? tc & 1 : 0;
+    return as_global(reinterpret_cast<const f32x4 *>(pt.part) + (size_t)b * GH * GW)[u * GW + min(32 * h + (lane & 31), GW - 1)];
+}
+
+// TAILF: the launch ends in bboxcc's parity planes instead of dact[2].  Block 2 scatters its output into the row tail's tile t3
+// in LDS (over t0 + t1, dead once block 1 has finished), the folded last block runs on it behind a barrier -- tail_row_tile, the
+// text dec3cc_rows_mfma runs, on eight waves, the partial logits straight from global memory a few tiles ahead of their use -- and
+// behind a second barrier the planes leave for the workspace (cc_planes reads them), with the mask bytes and logits the caller asked
+// for.  Same products in the same order, same logit expression, same ballots: bit-identical to the two launches
+// (tests/test_gpu_tail_in_dec012.py).  t3 overwrites the borders of t0 and t1, so this form writes them per frame.
+template <bool MS = false, bool TAILF = false>
+__global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p, Dec012TailArg<TAILF> pt) {
+    static_assert(!(MS && TAILF), "the form that ends in planes is the single-model kernel's");
     extern __shared__ __attribute__((aligned(256))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     uint8_t *const t0 = smem + p.lv[0].tile_off, *const t1 = smem + p.lv[1].tile_off, *const t2 = smem + p.lv[2].tile_off;
     WGSPAN_BEGIN();
 #ifdef PHASE_TIMING
-    unsigned long long ph_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
+    unsigned long long ph_[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
 #endif
     // border pieces only: disjoint from what the tile requests fill, and ordered in front of the first tile reads by the barrier
     // behind the landing
-    dec012_zero_border<128>(t0, p.lv[0], tid);
-    dec012_zero_border<128>(t1, p.lv[1], tid);
+    if constexpr (!TAILF) {
+        dec012_zero_border<128>(t0, p.lv[0], tid);
+        dec012_zero_border<128>(t1, p.lv[1], tid);
+    }
     dec012_zero_border<64>(t2, p.lv[2], tid);
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
         [[maybe_unused]] const uint32_t moff = model_off<MS>(p.model_ids, p.mstride, b);
-        // the previous frame's last block has left its tiles.  The FIRST frame of a workgroup (at b <= CUs the only one) has nothing
-        // to wait for: its weights and tile requests go out at once (round 6)
+        // the previous frame's last block has left its tiles (TAILF: its fold has left t3, and its planes are out).  The FIRST frame
+        // of a workgroup (at b <= CUs the only one) has nothing to wait for: its weights and tile requests go out at once (round 6)
         if (b != (int)blockIdx.x) lds_barrier();
         PHASE_MARK(0);
+        if constexpr (TAILF) {   // (behind the barrier: the previous frame's t3 lay over them)
+            const int tid_f = opaque_v(tid);
+            dec012_zero_border<128>(t0, p.lv[0], tid_f);
+            dec012_zero_border<128>(t1, p.lv[1], tid_f);
+        }
         {
             // The three tiles are requested FIRST, block 0's weights behind them, and the barrier waits for the tiles alone: the
             // vector-memory counter returns in order, so "at most DEC012_W0_KEPT operations outstanding" says that everything
@@ -2209,6 +2375,7 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
             dec012_block<64, 64, 32, 64>(smem, t1, t2, nullptr, nullptr, w1, p.lv[1], p.lv[2], wave, lane);
         }
         PHASE_MARK(5);       // block 1: tiles
+        [[maybe_unused]] std::conditional_t<TAILF, Dec012Fold, Dec012NoFold> fold;
         {
             Dec012W<64, 16> w2;
             dec012_load(w2, at_model(p.wf[2], moff), at_model(p.epi[2], moff), wave, lane);
@@ -2217,14 +2384,81 @@ __global__ __launch_bounds__(512, 2) void dec012_mfma(Dec012Args p) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 #endif
             PHASE_MARK(6);   // block 2: weights + barrier
-            dec012_block<32, 32, 16, 0>(smem, t2, nullptr, p.out + (size_t)b * p.lv[2].Hd * p.lv[2].Wd * 16, smem + p.scr_off, w2,
-                                        p.lv[2], p.lv[2], wave, lane);
+            if constexpr (!TAILF) {
+                dec012_block<32, 32, 16, 0>(smem, t2, nullptr, p.out + (size_t)b * p.lv[2].Hd * p.lv[2].Wd * 16, smem + p.scr_off, w2,
+                                            p.lv[2], p.lv[2], wave, lane);
+            } else {
+                // t0 and t1 are dead from the barrier above on: t3's border and the planes as zeros (disjoint from what block 2
+                // scatters), ordered in front of the fold by the barrier behind block 2
+                uint8_t *const t3 = smem + pt.lv.tile_off;
+                const int tid_f = opaque_v(tid);
+                dec012_zero_border<16>(t3, pt.lv, tid_f);
+                for (int i = tid_f; i < pt.rows_bytes / 4; i += 512) reinterpret_cast<uint32_t *>(smem + pt.planes_off)[i] = 0;
+                // the fold's loads (Dec012Fold)
+                const gptr<half8> wg = as_global(pt.wfrag);
+#pragma unroll
+                for (int ks = 0; ks < 4; ks++) fold.wf[ks] = wg[ks * 64 + (tid_f & 63)];
+                fold.fbias = pt.epi[0];
+#pragma unroll
+                for (int k = 0; k < DEC012_PF; k++) fold.ring[k] = dec012_part(pt, b, (tid_f >> 6) + 8 * k, tid_f & 63);
+                dec012_block<32, 32, 16, 16>(smem, t2, t3, nullptr, nullptr, w2, p.lv[2], pt.lv, wave, lane);
+            }
         }
         PHASE_MARK(7);       // block 2: tiles + stores
+        if constexpr (TAILF) {
+            // (the fold's lane values are made per frame, in this scope: hoisted out of the frame loop they would live across blocks
+            // 0 and 1, which use every register the kernel has)
+            const int tid = opaque_v((int)threadIdx.x), lane = tid & 63, wave = tid >> 6;
+            const DecLvl &g = pt.lv;
+            const int GW = g.Wi + 1, GH = g.Hi + 1;
+            const uint32_t row_b = (uint32_t)((g.Wi + 2) * 32);
+            const uint8_t *const t3 = smem + g.tile_off;
+            uint32_t *const planes = reinterpret_cast<uint32_t *>(smem + pt.planes_off);
+            // a row of up to 32 positions is one tile, a longer one two: tile t of the frame is half t % tpr of grid row t / tpr
+            const int tpr = GW > 32 ? 2 : 1, ntl = tpr * GH;
+            uint32_t lc[2][2];
+            tail_row_lanes(lc, GW, lane);
+            lds_barrier();   // block 2's output is in t3, its border and the planes are zero
+            PHASE_MARK(8);   // the fold: barrier
+            for (int t0 = wave; t0 < ntl; t0 += 8 * DEC012_TI) {
+                f32x4 pl[DEC012_TI];
+                f32x16 acc[DEC012_TI];
+#pragma unroll
+                for (int j = 0; j < DEC012_TI; j++) pl[j] = fold.ring[j];
+#pragma unroll
+                for (int k = 0; k + DEC012_TI < DEC012_PF; k++) fold.ring[k] = fold.ring[k + DEC012_TI];
+#pragma unroll
+                for (int j = 0; j < DEC012_TI; j++) fold.ring[DEC012_PF - DEC012_TI + j] = dec012_part(pt, b, t0 + 8 * (DEC012_PF + j), lane);
+                // the products of the iteration's tiles first: independent chains side by side (a tile past the wave's last computes
+                // the iteration's first again and leaves nothing)
+#pragma unroll
+                for (int j = 0; j < DEC012_TI; j++) {
+                    const int t = t0 + 8 * j < ntl ? t0 + 8 * j : t0;
+                    acc[j] = tail_row_acc(t3, row_b, lc, fold.wf, tpr == 2 ? t >> 1 : t, tpr == 2 ? t & 1 : 0);
+                }
+#pragma unroll
+                for (int j = 0; j < DEC012_TI; j++) {
+                    const int t = t0 + 8 * j;
+                    if (t < ntl)
+                        tail_row_out(acc[j], pl[j], fold.fbias, 0.f, pt.logits, g.Hd, g.Wd, g.cy, g.cx, GW, b, tpr == 2 ? t >> 1 : t, tpr == 2 ? t & 1 : 0,
+                                     lane, planes);
+                }
+            }
+            PHASE_MARK(9);   // the fold: tiles
+            lds_barrier();   // the frame's planes are complete
+            PHASE_MARK(10);  // the fold: barrier
+            {
+                const uint4 *const src = reinterpret_cast<const uint4 *>(planes);
+                uint4 *const dst = reinterpret_cast<uint4 *>(pt.planes_out) + (size_t)b * (pt.rows_bytes / 16);
+                for (int i = tid; i < pt.rows_bytes / 16; i += 512) dst[i] = src[i];
+            }
+            if (pt.mask) tail_mask_from_planes<512>(planes, pt.mask + (size_t)b * g.Hd * g.Wd, g.Hd, g.Wd, pt.mW4, tid);
+            PHASE_MARK(11);  // planes + mask out
+        }
     }
 #ifdef PHASE_TIMING
     if (tid == 0)
-        for (int i = 0; i < 9; i++) atomicAdd(&g_phase[48 + i], ph_[i]);
+        for (int i = 0; i < 12; i++) atomicAdd(&g_phase[48 + i], ph_[i]);
 #endif
     WGSPAN_END(3);
 }
@@ -2422,7 +2656,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
     const DecArgs &p = q.d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int TC = p.Wi + 2, GW = p.Wi + 1, GH = p.Hi + 1;
-    const int kh = lane >> 5, pos = lane & 31;
+    const int pos = lane & 31;
     const float fbias0 = p.epi[0];
     uint32_t *const planes = reinterpret_cast<uint32_t *>(smem + q.mfull_off);   // [2 BH + 2][E lo, E hi, O lo, O hi], pixel row y at y + 1
     const f32x4 *const part = reinterpret_cast<const f32x4 *>(smem + q.part_off);
@@ -2430,16 +2664,8 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
 #ifdef PHASE_TIMING
     unsigned long long ph_[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}, last_ = __builtin_amdgcn_s_memrealtime();
 #endif
-    // lane constants of the two tile halves x two tap columns: pixel column xx = 32 h + pos + 1 - bb (clamped to the grid's last
-    // position: lanes past the row's end compute on that pixel and are masked out of the ballots)
     uint32_t lc[2][2];
-#pragma unroll
-    for (int h = 0; h < 2; h++)
-#pragma unroll
-        for (int bb = 0; bb < 2; bb++) {
-            const int xx = min(32 * h + pos, GW - 1) + 1 - bb;
-            lc[h][bb] = (uint32_t)(xx * PS + ((kh ^ ((xx >> 3) & 1)) << 4));
-        }
+    tail_row_lanes(lc, GW, lane);
     const int row_b = TC * PS;
     for (int b = blockIdx.x; b < p.B; b += gridDim.x) {
         const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
@@ -2488,44 +2714,9 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
         for (int t = wave; t < 2 * GH; t += NW) {
             const int u = t >> 1, h = t & 1;
             if (32 * h >= GW) continue;   // rows of at most 32 positions have one tile
-            const uint32_t rb = (uint32_t)(u * row_b);   // tile row u holds input row u - 1 (tap a = 1); tap a = 0 one row further
-            const uint32_t a00 = rb + row_b + (h ? lc[1][0] : lc[0][0]), a01 = rb + row_b + (h ? lc[1][1] : lc[0][1]);
-            const uint32_t a10 = rb + (h ? lc[1][0] : lc[0][0]), a11 = rb + (h ? lc[1][1] : lc[0][1]);
-            f32x16 acc;
-#pragma unroll
-            for (int r = 0; r < 16; r++) acc[r] = 0.f;
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[0], *reinterpret_cast<const half8 *>(smem + a00), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[1], *reinterpret_cast<const half8 *>(smem + a01), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[2], *reinterpret_cast<const half8 *>(smem + a10), acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[3], *reinterpret_cast<const half8 *>(smem + a11), acc, 0, 0, 0);
             const int v = 32 * h + pos;
-            const bool live = kh == 0 && v < GW;
-            const f32x4 pl = part[u * GW + min(v, GW - 1)];
-            float l[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) l[r] = (acc[r] + fbias) + pl[r];
-            if (p.logits && live) {
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const int Y = 2 * u + (r >> 1) - p.cy, X = 2 * v + (r & 1) - p.cx;
-                    if (Y >= 0 && Y < p.Hd && X >= 0 && X < p.Wd) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l[r];
-                }
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                // bit v - 32 h of the ballot = output pixel (Y, 2 v + X0): plane X0 & 1, plane bit v + (X0 >> 1)
-                const uint64_t bits = (uint64_t)(uint32_t)__ballot(live && l[r] > sp.thr) << (32 * h);
-                const int Y = 2 * u + (r >> 1) - p.cy, X0 = (r & 1) - p.cx;
-                const int pln = X0 & 1, sh = X0 >> 1;                         // (arithmetic shift: floor)
-                const int nb = (p.Wd - pln + 1) >> 1;                          // pixels of this plane in a row
-                uint64_t w = sh >= 0 ? bits << sh : bits >> (-sh);
-                w &= nb >= 64 ? ~0ull : ((1ull << nb) - 1);
-                if (Y >= 0 && Y < p.Hd && lane == 0) {
-                    uint32_t *rw = planes + (Y + 1) * 4 + 2 * pln;
-                    if ((uint32_t)w) atomicOr(rw, (uint32_t)w);
-                    if ((uint32_t)(w >> 32)) atomicOr(rw + 1, (uint32_t)(w >> 32));
-                }
-            }
+            tail_row_tile(smem, (uint32_t)row_b, lc, wf, part[u * GW + min(v, GW - 1)], fbias, sp.thr, p.logits, p.Hd, p.Wd, p.cy, p.cx, GW, b, u, h,
+                          lane, planes);
         }
         PHASE_MARK(4);   // tiles
         lds_barrier();   // the frame's planes are complete; the tile buffer is free
@@ -2534,17 +2725,8 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
             lds_barrier();
         }
         PHASE_MARK(5);   // barrier
-        if (p.mask) {    // four mask bytes per thread and store, out of the planes (W is a multiple of 8: ccwave::wv_plan)
-            uint32_t *dst = reinterpret_cast<uint32_t *>(p.mask + (size_t)b * p.Hd * p.Wd);
-            const int wq = p.Wd >> 2, nq = p.Hd * wq;
-            for (int i = tid; i < nq; i += NW * 64) {
-                const int y = fdiv(i, p.mRC), xq = i - y * wq;   // (mRC = magic(Wd / 4) for this kernel)
-                const int bx = 2 * xq;
-                const uint32_t *rw = planes + (y + 1) * 4 + (bx >> 5);
-                const uint32_t e2 = (rw[0] >> (bx & 31)) & 3u, o2 = (rw[2] >> (bx & 31)) & 3u;
-                dst[i] = (e2 & 1u) | ((o2 & 1u) << 8) | ((e2 >> 1) << 16) | ((o2 >> 1) << 24);
-            }
-        }
+        // four mask bytes per thread and store, out of the planes (W is a multiple of 8: ccwave::wv_plan; mRC = magic(Wd / 4) for this kernel)
+        if (p.mask) tail_mask_from_planes<NW * 64>(planes, p.mask + (size_t)b * p.Hd * p.Wd, p.Hd, p.Wd, p.mRC, tid);
         PHASE_MARK(6);   // mask out
         ccwave::frame_wg<ccbody::CC_THREADS, true>(nullptr, smem + q.cc_off, q.wg, stack_area<POST, MS>(qp, q.ms.model_ids, b, q.area_thresh), q.boxes + (size_t)b * q.max_boxes,
                                                    q.counts + b, q.max_boxes, tid, planes);
@@ -2554,6 +2736,33 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
     if (tid == 0)
         for (int i = 0; i < 9; i++) atomicAdd(&g_phase[64 + i], ph_[i]);
 #endif
+    WGSPAN_END(4);
+}
+
+// ------------------------------------------------------------------ bboxcc on the planes of dec012_mfma<.., TAILF>
+// What is left of the tail when the last block has run in dec012_mfma: one 16-wave workgroup per frame copies the frame's parity
+// planes ((2 BH + 2) x 16 bytes) from the workspace into LDS and runs the run-based bboxcc on them, the call dec3cc_rows_mfma makes.
+struct CcPlanesArgs {
+    const uint32_t *planes;    // [B][rows_bytes / 4] (BnWorkspace::planes)
+    ccwave::WvGeom wg;
+    covahip_box *boxes;        // [B][max_boxes]
+    int32_t *counts;           // [B]
+    int B, area_thresh, max_boxes;
+    int cc_off, planes_off;    // LDS offsets of bboxcc's region (wg.wave_bytes) and of the planes (wg.rows_bytes)
+};
+__global__ __launch_bounds__(ccbody::CC_THREADS) void cc_planes(CcPlanesArgs q) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int tid = threadIdx.x;
+    uint32_t *const planes = reinterpret_cast<uint32_t *>(smem + q.planes_off);
+    WGSPAN_BEGIN();
+    for (int b = blockIdx.x; b < q.B; b += gridDim.x) {
+        if (b != (int)blockIdx.x) lds_barrier();   // the previous frame's bboxcc is done with its planes
+        const uint4 *const src = reinterpret_cast<const uint4 *>(q.planes) + (size_t)b * (q.wg.rows_bytes / 16);
+        for (int i = tid; i < q.wg.rows_bytes / 16; i += ccbody::CC_THREADS) reinterpret_cast<uint4 *>(planes)[i] = src[i];
+        lds_barrier();
+        ccwave::frame_wg<ccbody::CC_THREADS, true>(nullptr, smem + q.cc_off, q.wg, q.area_thresh, q.boxes + (size_t)b * q.max_boxes, q.counts + b,
+                                                   q.max_boxes, tid, planes);
+    }
     WGSPAN_END(4);
 }
 
@@ -2860,6 +3069,9 @@ ItemPlan make_plan(int grid, int num_cu, int wgs_per_cu, int batch, int nbands, 
 // What every kernel here that needs more than the default 64 KB of dynamic LDS is opened to (covahip_open_lds): the 160 KB a CU
 // has, minus the 256 B the runtime keeps.
 constexpr size_t LDS_LIMIT = 160 * 1024 - 256;
+// Whether run_dec012 takes the form that ends in planes (dec012_mfma<.., TAILF> + cc_planes) on its own where it applies; the
+// developer switches reach it either way (DESIGN.md section 6 has the measurement that decides this).
+constexpr bool TAIL_IN_DEC012_AUTO = true;
 
 // Run-time bools as template arguments: with_bools(f, b0, b1, ..) calls f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ..)
 // and returns its code, so that a generic lambda names a kernel family once and instantiates one kernel per combination of
@@ -3209,16 +3421,32 @@ int run_enc_level(const Fwd &f, int i) {
     }, ap, rowtiles, f.ms));
 }
 
+// The fused tail's plan (plan_tail_fused): the arguments of its launch, its LDS, and whether it is the row form.
+struct TailPlan {
+    Dec3ccArgs t;
+    size_t lds;
+    bool rows;
+    bool in_dec012;   // the row tiles take the frame's geometry (run_dec012's form that ends in planes asks no more of it)
+};
+
 // Decoder blocks 0..2 in one launch when a frame's three input tiles fit in LDS together.
 // False: the blocks are run_dec_block's.  True: they ran, or failed with rc set.
-bool run_dec012(const Fwd &f, int &rc) {
+// tail: the fused tail's plan when row tiles take the frame's geometry (TailPlan::in_dec012), else null.  tail_in: the last block
+// ran here as well (dec012_mfma<.., TAILF>) and left the frames' planes in the workspace: run_cc_planes is what remains.  That form
+// is taken when the row tail would run behind this launch, for a single model without per-model post-processing, when its LDS
+// plan fits -- t3 over t0 + t1, then t2, then the planes -- and when the batch fills the chip by enc23_mfma's rule (at small
+// batches the existing tests pin the two launches and their intermediate dact[2]); a call that asks for the logits keeps the two
+// launches and every intermediate of theirs in the workspace.  tail_in_dec012 == 2 (developer switch "tail_in_dec012") takes it
+// wherever the geometry and the LDS plan allow it, whatever the batch and the outputs; 0 ("tail_separate") never.
+bool run_dec012(const Fwd &f, int &rc, const TailPlan *tail, bool &tail_in) {
     const covahip_blobnet *m = f.m;
     const Prepared *pr = f.pr;
+    tail_in = false;
     if (!(m->fuse_dec && m->dec_ci[0] == 128 && m->dec_ci[1] == 128 && m->dec_ci[2] == 64 && m->dec_co[0] == 64 &&
           m->dec_co[1] == 32 && m->dec_co[2] == 16))
         return false;
     Dec012Args a;
-    size_t off = 0;
+    size_t off = 0, tile_bytes[3];
     for (int j = 0; j < 3; j++) {
         const BnLevelGeom in = m->lv[BN_LEVELS - j], out = m->lv[BN_LEVELS - 1 - j];
         DecLvl &g = a.lv[j];
@@ -3227,7 +3455,8 @@ bool run_dec012(const Fwd &f, int &rc) {
         g.mRC = magic((in.W + 2) * (m->dec_ci[j] / 8));
         g.swz = choose_swz(false, m->dec_ci[j], in.W, 0, in.H + 1);
         g.tile_off = (int)off;
-        off += align256((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2);   // 256: dec012_block's xor addressing
+        tile_bytes[j] = align256((size_t)(in.H + 2) * (in.W + 2) * m->dec_ci[j] * 2);   // 256: dec012_block's xor addressing
+        off += tile_bytes[j];
         a.skip[j] = f.ws.act[BN_LEVELS - j];
         a.Ts[j] = j == 0 ? 1 : BN_T;
         a.wf[j] = (const half8 *)(f.prep + pr->dec[j].wfrag);
@@ -3238,10 +3467,42 @@ bool run_dec012(const Fwd &f, int &rc) {
     if (lds > 160 * 1024 - 256) return false;
     a.out = f.ws.dact[2]; a.B = f.batch; a.zero = f.prep + pr->zero;
     a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
+    const int grid = std::min(f.batch, f.num_cu);
+    if (tail && m->tail_in_dec012 && !f.ms && !f.post && f.ws.planes &&
+        (m->tail_in_dec012 == 2 || (TAIL_IN_DEC012_AUTO && tail->rows && 4 * f.batch >= 3 * f.num_cu && !f.d_logits))) {
+        const DecArgs &d = tail->t.d;
+        Dec012Tail t;
+        t.lv = DecLvl{d.Hi, d.Wi, d.Hd, d.Wd, d.cy, d.cx, 0u, 0u, Swz{3, 1, 0, 0, 0}, 0};
+        const size_t t3 = align256((size_t)(d.Hi + 2) * (d.Wi + 2) * 32);
+        const size_t t2_off = std::max(tile_bytes[0] + tile_bytes[1], t3);
+        const size_t planes_off = t2_off + tile_bytes[2];
+        const size_t lds_t = planes_off + (size_t)tail->t.wg.rows_bytes;
+        if (lds_t <= LDS_LIMIT) {
+            a.lv[2].tile_off = (int)t2_off;
+            a.scr_off = 0; a.out = nullptr;   // (neither exists in this form)
+            t.wfrag = d.wfrag; t.epi = d.epi; t.part = d.part; t.logits = d.logits; t.mask = d.mask;
+            t.planes_out = f.ws.planes;
+            t.planes_off = (int)planes_off; t.rows_bytes = tail->t.wg.rows_bytes;
+            t.mW4 = magic(d.Wd / 4);
+            tail_in = true;
+            rc = launched(f, launch(f, "dec012_mfma", dec012_mfma<false, true>, grid, 512, lds_t, a, t));
+            return true;
+        }
+    }
     rc = launched(f, with_bools([&](auto MS) {
-        return launch(f, "dec012_mfma", dec012_mfma<MS.value>, std::min(f.batch, f.num_cu), 512, lds, a);
+        return launch(f, "dec012_mfma", dec012_mfma<MS.value, false>, grid, 512, lds, a, Dec012NoTail{});
     }, f.ms));
     return true;
+}
+// bboxcc on the planes that dec012_mfma<.., TAILF> left in the workspace
+int run_cc_planes(const Fwd &f, const TailPlan &tp) {
+    CcPlanesArgs q;
+    q.planes = f.ws.planes; q.wg = tp.t.wg;
+    q.boxes = f.cc->boxes; q.counts = f.cc->counts;
+    q.B = f.batch; q.area_thresh = f.cc->area_thresh; q.max_boxes = f.cc->max_boxes;
+    q.cc_off = 0; q.planes_off = tp.t.wg.wave_bytes;
+    const size_t lds = (size_t)tp.t.wg.wave_bytes + (size_t)tp.t.wg.rows_bytes;
+    return launch(f, "dec3_bboxcc_fused", cc_planes, std::min(f.batch, 2 * f.num_cu), ccbody::CC_THREADS, lds, q);
 }
 
 // Decoder block j on dec_mfma (the last one carries the folded final conv + threshold): its plan, which the fused tail
@@ -3327,11 +3588,12 @@ int run_dec_block(const Fwd &f, int j) {
 
 // Last block + bboxcc in one launch when the frame's LDS plan fits: two band buffers (which bboxcc's region reuses) + the
 // frame's mask bytes.  p: the last block's own plan.  False: it does not fit -- a kernel whose LDS limit cannot be opened
-// counts as that -- and the block runs alone.
-bool run_tail_fused(const Fwd &f, const DecPlan &p) {
+// counts as that -- and the block runs alone.  The plan first (the decoder launch in front of it looks at it: run_dec012), then
+// the launch.
+bool plan_tail_fused(const Fwd &f, const DecPlan &p, TailPlan &tp) {
     const BnLevelGeom in = p.in, out = p.out;
     const int GH = p.GH;
-    Dec3ccArgs t;
+    Dec3ccArgs &t = tp.t;
     size_t cc_bytes = ccbody::cc_plan(out.H, out.W, t.g);
     // the run-based body (bboxcc_wave.h) when the shape allows it: worst-case run capacity, nothing overflows
     t.use_wv = f.ctx->cc_wave_cap >= 0 && ccwave::wv_plan(out.H, out.W, ((out.H + 1) / 2) * ((out.W + 1) / 2), t.wg) ? 1 : 0;
@@ -3364,13 +3626,23 @@ bool run_tail_fused(const Fwd &f, const DecPlan &p) {
     t.tile_bytes = (int)tb; t.cc_off = 0;
     t.mfull_off = (int)std::max((best_nb == 1 ? 1 : 2) * tb, cc_bytes);
     t.part_off = (int)((size_t)t.mfull_off + mfull);
-    const size_t tl = (size_t)t.part_off + partb;
-    const int grid = std::min(f.batch, 2 * f.num_cu);
+    tp.lds = (size_t)t.part_off + partb;
     // row tiles + ballots straight into bboxcc's planes (dec3cc_rows_mfma) when the shape allows it
-    if (p.half && t.use_wv && best_nb == 1 && in.W + 1 <= 64 && f.m->tail_rows && (out.W & 7) == 0 &&
-        (size_t)t.wg.rows_bytes <= mfull && (!f.d_mask || (reinterpret_cast<uintptr_t>(f.d_mask) & 3) == 0)) {
+    // (in_dec012: what of this is geometry of the row tiles themselves, and not of this launch's LDS plan)
+    tp.in_dec012 = p.half && t.use_wv && in.W + 1 <= 64 && f.m->tail_rows && (out.W & 7) == 0 &&
+                   (!f.d_mask || (reinterpret_cast<uintptr_t>(f.d_mask) & 3) == 0);
+    tp.rows = tp.in_dec012 && best_nb == 1 && (size_t)t.wg.rows_bytes <= mfull;
+    if (tp.rows) {
         t.d.swz = Swz{3, 1, 0, 0, 0};            // s = (xx >> 3) & 1 (what the staging of both forms evaluates)
         t.d.mRC = magic(out.W / 4);               // the mask expansion's division
+    }
+    return true;
+}
+bool launch_tail_fused(const Fwd &f, const DecPlan &p, const TailPlan &tp) {
+    const Dec3ccArgs &t = tp.t;
+    const size_t tl = tp.lds;
+    const int grid = std::min(f.batch, 2 * f.num_cu);
+    if (tp.rows) {
         if (!f.dry) f.ctx->tail_form = COVAHIP_DEV_TAIL_ROWS;
         return !with_bools([&](auto MS, auto POST) {
             return launch(f, "dec3_bboxcc_fused", dec3cc_rows_mfma<MS.value, POST.value>, grid, ccbody::CC_THREADS, tl, t, post_arg<POST.value>(f));
@@ -3427,13 +3699,23 @@ int blobnet_forward_mfma(covahip_ctx *ctx, covahip_blobnet *m, BnWorkspace &ws, 
         if (!rc) rc = run_enc_level(f, 3);
     }
     if (rc) return rc;
-    if (!run_dec012(f, rc))
-        for (int j = 0; j < BN_LEVELS - 1 && !rc; j++) rc = run_dec_block(f, j);
-    if (rc) return rc;
+    // the tail's plan first: the decoder launch takes the last block in when the row tail would run behind it (run_dec012)
     DecPlan last;
     rc = plan_dec_block(f, BN_LEVELS - 1, last);
     if (rc) return rc;
-    if (!(cc && m->fuse_tail && run_tail_fused(f, last))) {
+    TailPlan tp;
+    const bool fused = cc && m->fuse_tail && plan_tail_fused(f, last, tp);
+    bool tail_in = false;
+    if (!run_dec012(f, rc, fused && tp.in_dec012 ? &tp : nullptr, tail_in))
+        for (int j = 0; j < BN_LEVELS - 1 && !rc; j++) rc = run_dec_block(f, j);
+    if (rc) return rc;
+    if (!dry) ctx->tail_in_dec012 = tail_in;
+    if (tail_in) {
+        if (!dry) ctx->tail_form = COVAHIP_DEV_TAIL_ROWS;   // (the row tail's text, in the decoder launch)
+        if (cc_done) *cc_done = true;
+        return launched(f, run_cc_planes(f, tp));
+    }
+    if (!(fused && launch_tail_fused(f, last, tp))) {
         if (!dry) ctx->tail_form = COVAHIP_DEV_TAIL_ALONE;
         return launch_dec_block(f, BN_LEVELS - 1, last);
     }

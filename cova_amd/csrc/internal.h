@@ -128,6 +128,7 @@ struct covahip_ctx {
     size_t sweep_bytes = 0;
     ResidentTable<int32_t> cc_area;   // covahip_bboxcc_v: the call's per-frame area thresholds, on the primary stream; grows to the batch
     int cc_wave_cap = 0;       // bboxcc wave kernel: developer override of its run capacity
+    int tail_in_dec012 = 0;    // the last forward ran the last decoder block inside dec012_mfma (covahip_dev_blobnet_tail_in_dec012)
     int tail_form = 0;         // which kernel ran the last decoder block of the last forward (covahip_dev_blobnet_tail_form)
     CtxLane &lane() { return lanes[cur_lane]; }
     struct { int nbands, nbuf; } enc_plan[4] = {};   // developer override of the encoder band plan per level (0 = automatic)

@@ -288,8 +288,10 @@ class BlobNetInfer:
         "enc23_separate" / "enc23_force": encoder levels 2 + 3 always as two launches / as one launch (enc23_mfma) whenever it
         fits (the default takes the single launch when the batch fills the chip and the rows fill their tile columns);
         "tail_skip_tensor": the last decoder block reads the level-0 skip tensor (rounds 1-4) instead of the partial logits the
-        level-1 kernel computes from it (round 5 default; another summation order, not another value)."""
-        L.check(self._lib.covahip_blobnet_set_impl(self.ctx.handle, {"mfma": 1, "dec_separate": 4, "enc1_legacy": 5, "enc_general_tiles": 6, "enc23_separate": 7, "enc23_force": 8, "tail_skip_tensor": 9, "tail_band_tiles": 10}[impl]), "set_impl")
+        level-1 kernel computes from it (round 5 default; another summation order, not another value);
+        "tail_in_dec012" / "tail_separate": the last decoder block inside the decoder launch, bboxcc alone behind it, wherever the
+        geometry allows it / never (the default takes it when the batch fills the chip and no logits are asked for)."""
+        L.check(self._lib.covahip_blobnet_set_impl(self.ctx.handle, {"mfma": 1, "dec_separate": 4, "enc1_legacy": 5, "enc_general_tiles": 6, "enc23_separate": 7, "enc23_force": 8, "tail_skip_tensor": 9, "tail_band_tiles": 10, "tail_in_dec012": 11, "tail_separate": 12}[impl]), "set_impl")
 
     TAIL_ALONE, TAIL_ROWS, TAIL_BANDS = 1, 2, 4
 
@@ -299,6 +301,12 @@ class BlobNetInfer:
         v = C.c_int()
         L.check(self._lib.covahip_dev_blobnet_tail_form(self.ctx.handle, C.byref(v)), "covahip_dev_blobnet_tail_form")
         return v.value
+
+    def tail_in_dec012(self) -> bool:
+        """Developer read-back (include/covahip_dev.h): whether the last forward ran the last decoder block inside dec012_mfma."""
+        v = C.c_int()
+        L.check(self._lib.covahip_dev_blobnet_tail_in_dec012(self.ctx.handle, C.byref(v)), "covahip_dev_blobnet_tail_in_dec012")
+        return bool(v.value)
 
     def read_buffer(self, which: int, index: int = 0) -> np.ndarray:
         """Developer read-back (include/covahip_dev.h): a copy of one buffer of lane 0's workspace -- which = 0 P, 1 act[index],

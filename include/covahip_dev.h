@@ -64,6 +64,12 @@ int covahip_dev_graph_probe(covahip_ctx *ctx, const uint8_t *d_frames, int n_fra
 #define COVAHIP_DEV_TAIL_ROWS 2
 #define COVAHIP_DEV_TAIL_BANDS 4
 int covahip_dev_blobnet_tail_form(covahip_ctx *ctx, int *form);
+/* Whether the ctx's last BlobNet forward ran the last decoder block INSIDE the decoder launch (dec012_mfma ending in bboxcc's
+ * parity planes, "dec3_bboxcc_fused" then being bboxcc alone on those planes: cc_planes) -- 1 -- or as a launch of its own -- 0.
+ * tail_form reads ROWS in both cases: it is the row tail's text that runs.  covahip_blobnet_set_impl 11 takes that form wherever
+ * its geometry allows it (single model, no per-model post-processing), 12 never; the default takes it when the batch fills the
+ * chip and the call does not ask for the logits. */
+int covahip_dev_blobnet_tail_in_dec012(covahip_ctx *ctx, int *in_dec012);
 
 /* What covahip_pipe_create's hardware-queue probe decided (pipe.hip, round 6): how many of the ctx's ACTIVE lanes share a hardware
  * queue with the pipe's upload stream / with its result stream.  0 / <= 1 with up to three lanes on the default four queues. */

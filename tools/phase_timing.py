@@ -21,7 +21,9 @@ for spec in filter(None, os.environ.get("QB_PLAN", "").split(",")):      # level
 NWG = {0: int(os.environ.get("NWG1", 512)), 16: 512, 32: 256, 48: 256, 64: 256}
 TAIL_NAMES = ["barrier (previous frame)", "requesting band 0 + weights", "bands landing", "requesting the next band", "tiles", "barrier", "mask out", "bboxcc", "-"]
 DEC_NAMES = ["barrier (previous frame)", "requesting the three tiles + block 0 weights", "tiles landing", "block 0: tiles",
-             "block 1: weights + barrier", "block 1: tiles", "block 2: weights + barrier", "block 2: tiles + stores", "-"]
+             "block 1: weights + barrier", "block 1: tiles", "block 2: weights + barrier", "block 2: tiles + stores",
+             # the form that ends in planes (dec012_mfma<.., TAILF>: the default at this batch, QB_IMPL=tail_separate for the other)
+             "the fold: barrier", "the fold: tiles", "the fold: barrier (planes complete)", "planes + mask out"]
 frames, index = synth.carrier_batch(B, H, Wd, seed=1, streams=8)
 d_frames = ctx.malloc(frames.nbytes)
 ctx.h2d(d_frames, frames)
@@ -46,9 +48,10 @@ v = np.array(list(out), dtype=np.float64)
 FUSED23 = os.environ.get("QB_IMPL") not in ("enc23_separate", "enc_general_tiles")
 NWG[16] = 256 if FUSED23 else 512
 for base, label in ((0, "enc1t (PRE)"), (16, "enc23" if FUSED23 else "enc2"), (32, "enc3"), (48, "dec012"), (64, "dec3cc")):
-    if v[base:base + 9].sum() == 0:
+    np_ = 12 if base == 48 else 9   # phases of the kernel
+    if v[base:base + np_].sum() == 0:
         continue
-    tot = v[base:base + 9].sum()
+    tot = v[base:base + np_].sum()
     print(f"{label}: {tot / steps / 100:.0f} us of workgroup time per launch (all workgroups)")
     for i, n in enumerate(E23_NAMES if base == 16 and FUSED23 else DEC_NAMES if base == 48 else TAIL_NAMES if base == 64 else E1V_NAMES if base == 0 and not os.environ.get('QB_IMPL') else names):
         print(f"   {n:40s} {100 * v[base + i] / tot:5.1f} %   {v[base + i] / steps / 100 / NWG[base]:7.2f} us per workgroup ({NWG[base]} of them)")
