@@ -5,6 +5,7 @@
 // macroblock grid's kernels (half-resolution working image) are mog_grid.hip and, for 1440p and 4K sources, mog_band.hip (the
 // post kernel in row bands); all three instantiate the device code of mog_dev.h.  covahip_mog_apply_yuv (NV12 / I420 surfaces at
 // the caller's pitch, offsets and strides) is checked and staged here and runs the update kernels of mog_yuv.hip.
+// covahip_mog_create_any (the macroblock grid at any even source size) makes a labeller that runs the kernels of mog_any.hip.
 //
 //   k_mog_update  one lane per working-size pixel and stream.  The five modes (weight, variance, mean) are read once per call
 //                 into registers, every frame of the call is applied to them, and they are written back once.  The source is
@@ -103,7 +104,11 @@ void band_plan(int mw, int mh, int *rows, int *bands) {
 struct covahip_mog {
     covahip_ctx *ctx = nullptr;
     covahip_mog_cfg cfg{};
-    const MogGeomRow *row = nullptr;   // the (source size, grid) row of MOG_GEOMS
+    const MogGeomRow *row = nullptr;   // the (source size, grid) row of MOG_GEOMS, or &own
+    MogGeomRow own{};              // covahip_mog_create_any: this labeller's geometry, banded only, run by mog_any.hip
+    bool any = false;
+    MogDims alloc{};               // what the planes and the model are sized and laid out by: row->work, or with `any` its rows at
+                                   // the pitch of mog_any_pitch
     bool banded = false;           // the post kernel of mog_band.hip, where the row has it
     int band_rows = 0;             // its band height; 0 = the automatic plan
     size_t src_bytes = 0;
@@ -139,6 +144,11 @@ struct YuvPlan {
 int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
     covahip_ctx *ctx = m->ctx;
     const int load = m->row->load;
+    if (m->any) {
+        const MogDims &w = m->row->work;
+        return yuv ? covahip_mog_any_yuv_update(ctx, yuv->format, w.mw, w.mh, d_frames, src, a)
+                   : covahip_mog_any_update(ctx, w.mw, w.mh, d_frames, m->src_bytes, a);
+    }
     if (yuv) return covahip_mog_yuv_update(ctx, yuv->format, load, m->row->work.mw, d_frames, src, a);
     if (m->row->work.mw != MW)             // the macroblock grid's other working sizes: the kernels beside the row's post kernels
         return (m->row->resident ? covahip_mog_grid_update : covahip_mog_band_update)(ctx, m->row->work.mw, d_frames, m->src_bytes, a);
@@ -153,14 +163,55 @@ int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, s
     auto *bits = static_cast<const unsigned long long *>(m->bits);
     auto *filled = static_cast<unsigned long long *>(m->filled);
     if (m->banded) {
-        if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->row->work.nword() * 8)) return rc;
+        if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->alloc.nword() * 8)) return rc;
         int rows = m->band_rows, bands = 0;
-        if (!rows) band_plan(m->row->work.mw, m->row->work.mh, &rows, &bands);
+        if (!rows) band_plan(m->alloc.mw, m->alloc.mh, &rows, &bands);
+        if (m->any)
+            return covahip_mog_any_post(ctx, m->row->work.mw, m->row->work.mh, bits, filled, static_cast<unsigned long long *>(m->plane),
+                                        d_labels, d_nv, S, FS, rows);
         return covahip_mog_band_post(ctx, m->row->work.mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
                                      rows);
     }
     if (m->row->work.mw != MW) return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS);
     return mog_launch(ctx, "mog_post", k_mog_post, dim3((unsigned)FS), POST_BLOCK, 0, bits, filled, d_labels, d_nv, S);
+}
+
+bool cfg_ok(const covahip_mog_cfg *cfg) {
+    return cfg->n_streams >= 1 && cfg->n_streams <= COVAHIP_MOG_MAX_STREAMS && cfg->history >= 1 && std::isfinite(cfg->var_threshold) &&
+           cfg->var_threshold > 0.f;
+}
+
+// the labeller of a checked cfg: on `row` of MOG_GEOMS, or (row == nullptr) the general kernels at half the source
+int create_mog(covahip_ctx *ctx, const covahip_mog_cfg *cfg, const MogGeomRow *row, covahip_mog **out) {
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    covahip_mog *m = new covahip_mog();
+    m->ctx = ctx;
+    m->cfg = *cfg;
+    if (row) {
+        m->row = row;
+        m->alloc = row->work;
+    } else {
+        const MogDims work{cfg->src_w / 2, cfg->src_h / 2};
+        m->own = MogGeomRow{cfg->src_w, cfg->src_h, MOG_ON_MB, work, MOG_LOAD_HALF, false, true, true};
+        m->row = &m->own;
+        m->any = true;
+        m->alloc = MogDims{mog_any_pitch(work.mw), work.mh};
+    }
+    m->banded = m->row->starts_banded;
+    m->src_bytes = (size_t)cfg->src_w * cfg->src_h * 3;
+    m->n.assign(cfg->n_streams, 0);
+    const size_t sb = m->alloc.state_bytes() * cfg->n_streams;
+    hipError_t e = hipMalloc(&m->state, sb);
+    if (e == hipSuccess) e = hipMemsetAsync(m->state, 0, sb, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) {
+        ctx->last_hip_error = std::string("covahip_mog_create: ") + hipGetErrorString(e);
+        free_mog(m);
+        return COVAHIP_ERR_HIP;
+    }
+    *out = m;
+    return COVAHIP_OK;
 }
 
 }  // namespace
@@ -184,31 +235,19 @@ int covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int gr
     if (out) *out = nullptr;
     if (!ctx || !cfg || !out) return COVAHIP_ERR_INVALID_ARG;
     if (grid != COVAHIP_MOG_GRID_REFERENCE && grid != COVAHIP_MOG_GRID_MACROBLOCK) return COVAHIP_ERR_INVALID_ARG;
-    if (cfg->n_streams < 1 || cfg->n_streams > COVAHIP_MOG_MAX_STREAMS || cfg->history < 1 || !std::isfinite(cfg->var_threshold) ||
-        !(cfg->var_threshold > 0.f))
-        return COVAHIP_ERR_INVALID_ARG;
+    if (!cfg_ok(cfg)) return COVAHIP_ERR_INVALID_ARG;
     const MogGeomRow *row = mog_geom_row(cfg->src_w, cfg->src_h, grid);
     if (!row) return COVAHIP_ERR_UNSUPPORTED;
-    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
-    if (int rc = covahip_primary_op(ctx)) return rc;
-    covahip_mog *m = new covahip_mog();
-    m->ctx = ctx;
-    m->cfg = *cfg;
-    m->row = row;
-    m->banded = row->starts_banded;
-    m->src_bytes = (size_t)cfg->src_w * cfg->src_h * 3;
-    m->n.assign(cfg->n_streams, 0);
-    const size_t sb = m->row->work.state_bytes() * cfg->n_streams;
-    hipError_t e = hipMalloc(&m->state, sb);
-    if (e == hipSuccess) e = hipMemsetAsync(m->state, 0, sb, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) {
-        ctx->last_hip_error = std::string("covahip_mog_create: ") + hipGetErrorString(e);
-        free_mog(m);
-        return COVAHIP_ERR_HIP;
-    }
-    *out = m;
-    return COVAHIP_OK;
+    return create_mog(ctx, cfg, row, out);
+}
+
+int covahip_mog_create_any(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out) {
+    if (out) *out = nullptr;
+    if (!ctx || !cfg || !out) return COVAHIP_ERR_INVALID_ARG;
+    if (!cfg_ok(cfg)) return COVAHIP_ERR_INVALID_ARG;
+    for (const int v : {cfg->src_w, cfg->src_h})
+        if (v % 2 || v < COVAHIP_MOG_ANY_MIN || v > COVAHIP_MOG_ANY_MAX) return COVAHIP_ERR_UNSUPPORTED;
+    return create_mog(ctx, cfg, nullptr, out);
 }
 
 }  // extern "C"
@@ -231,7 +270,7 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     const size_t FS = (size_t)n_frames * S;
-    const size_t NWORD = m->row->work.nword(), NLAB = m->row->work.nlab();   // this labeller's geometry
+    const size_t NWORD = m->alloc.nword(), NLAB = m->row->work.nlab();   // this labeller's geometry
     // per-stream, per-frame learning rates, in double as generate-mog.py's OpenCV computes them
     const size_t par_bytes = FS * sizeof(float2) + S * sizeof(int32_t);
     if (m->h_par_bytes < par_bytes) {
@@ -348,13 +387,18 @@ int covahip_mog_apply_yuv(covahip_mog *m, const covahip_mog_yuv *lay, const uint
     YuvPlan plan{};
     int64_t lo = INT64_MAX, hi = 0;
     for (int p = 0; p < planes; p++) {
-        if (lay->offset[p] < 0 || lay->pitch[p] < row_bytes[p] || ((lay->offset[p] | lay->pitch[p]) & 1)) return COVAHIP_ERR_INVALID_ARG;
+        // (an any-size labeller takes I420's U and V at odd offsets and pitches: they are loaded byte by byte, and where
+        // src_w / 2 is odd a tight frame has them so)
+        const bool odd_ok = m->any && !nv12 && p > 0;
+        if (lay->offset[p] < 0 || lay->pitch[p] < row_bytes[p] || (!odd_ok && ((lay->offset[p] | lay->pitch[p]) & 1)))
+            return COVAHIP_ERR_INVALID_ARG;
         lo = std::min(lo, lay->offset[p]);
         hi = std::max(hi, lay->offset[p] + (rows[p] - 1) * lay->pitch[p] + row_bytes[p]);
         plan.src.off[p] = lay->offset[p];
         plan.src.pitch[p] = lay->pitch[p];
     }
     plan.format = lay->format;
+    lo -= lo & 1;                  // (staged Y rows keep their even addresses where an odd chroma offset is the lowest)
     plan.lo = (size_t)lo;
     plan.ext = (size_t)(hi - lo);
     plan.src.frame_stride = lay->frame_stride;
@@ -374,7 +418,7 @@ int covahip_mog_reset(covahip_mog *m, int stream) {
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(m->state + (size_t)stream * m->row->work.state_bytes(), 0, m->row->work.state_bytes(), ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(m->state + (size_t)stream * m->alloc.state_bytes(), 0, m->alloc.state_bytes(), ctx->stream));
     m->n[stream] = 0;
     return COVAHIP_OK;
 }
@@ -399,7 +443,8 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
     if (!m || !n_frames) return COVAHIP_ERR_INVALID_ARG;
     *n_frames = m->last_frames;
     const size_t FS = (size_t)m->last_frames * m->cfg.n_streams;
-    const size_t NPIX = m->row->work.npix(), NWORD = m->row->work.nword();
+    const size_t NPIX = m->row->work.npix(), NWORD = m->alloc.nword();
+    const size_t mw = m->row->work.mw, roww = m->alloc.mw / 64, NROW = FS * m->alloc.mh;   // a plane row: mw pixels of roww words
     if ((raw || filled) && cap < FS * NPIX) return COVAHIP_ERR_OVERFLOW;
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
@@ -411,8 +456,8 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(w.data(), which ? m->filled : m->bits, FS * NWORD * 8, hipMemcpyDeviceToHost, ctx->stream));
         COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         const uint8_t one = which ? 1 : 255;
-        for (size_t i = 0; i < FS * NWORD; i++)
-            for (int b = 0; b < 64; b++) out[i * 64 + b] = (w[i] >> b) & 1ull ? one : 0;
+        for (size_t r = 0; r < NROW; r++)
+            for (size_t x = 0; x < mw; x++) out[r * mw + x] = (w[r * roww + x / 64] >> (x % 64)) & 1ull ? one : 0;
     }
     return COVAHIP_OK;
 }
@@ -429,13 +474,11 @@ int covahip_dev_mog_post_masks(covahip_mog *m, const uint8_t *raw, int n_frames,
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
     const int S = m->cfg.n_streams;
-    const size_t FS = (size_t)n_frames * S, NWORD = m->row->work.nword(), NLAB = m->row->work.nlab();
-    std::vector<unsigned long long> w(FS * NWORD);
-    for (size_t i = 0; i < FS * NWORD; i++) {
-        unsigned long long v = 0;
-        for (int b = 0; b < 64; b++) v |= (unsigned long long)(raw[i * 64 + b] != 0) << b;
-        w[i] = v;
-    }
+    const size_t FS = (size_t)n_frames * S, NWORD = m->alloc.nword(), NLAB = m->row->work.nlab();
+    const size_t mw = m->row->work.mw, roww = m->alloc.mw / 64, NROW = FS * m->alloc.mh;
+    std::vector<unsigned long long> w(FS * NWORD, 0ull);       // (the bits beyond a row's mw pixels stay 0)
+    for (size_t r = 0; r < NROW; r++)
+        for (size_t x = 0; x < mw; x++) w[r * roww + x / 64] |= (unsigned long long)(raw[r * mw + x] != 0) << (x % 64);
     const std::vector<int32_t> nv(S, n_frames);
     if (int rc = covahip_ensure_buffer(ctx, &m->d_par, &m->par_bytes, S * sizeof(int32_t))) return rc;
     if (int rc = covahip_ensure_buffer(ctx, &m->bits, &m->bits_bytes, FS * NWORD * 8)) return rc;
@@ -454,7 +497,7 @@ int covahip_dev_mog_set_post_form(covahip_mog *m, int banded, int band_rows) {
     if (!m || (banded != 0 && banded != 1)) return COVAHIP_ERR_INVALID_ARG;
     if (banded ? !m->row->banded : !m->row->resident || band_rows != 0) return COVAHIP_ERR_INVALID_ARG;
     if (banded && band_rows != 0 &&
-        (band_rows < 16 || band_rows > m->row->work.mh || band_lds_bytes(m->row->work.mw, m->row->work.mh, band_rows) > COVAHIP_MOG_BAND_LDS_MAX))
+        (band_rows < 16 || band_rows > m->alloc.mh || band_lds_bytes(m->alloc.mw, m->alloc.mh, band_rows) > COVAHIP_MOG_BAND_LDS_MAX))
         return COVAHIP_ERR_INVALID_ARG;
     m->banded = banded != 0;
     m->band_rows = band_rows;
@@ -476,14 +519,20 @@ int covahip_dev_mog_state(covahip_mog *m, int stream, float *W, float *V, float 
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    const MogDims &d = m->row->work;
+    const MogDims &d = m->alloc;
     const uint8_t *st = m->state + (size_t)stream * d.state_bytes();
-    const struct { void *dst; size_t off, end; } parts[] = {{W, 0, d.off_v()},
-                                                            {V, d.off_v(), d.off_m()},
-                                                            {M, d.off_m(), d.off_n()},
-                                                            {nmodes, d.off_n(), d.state_bytes()}};
+    // elem: bytes per pixel and array; the rows come back dense, [work_h][work_w], whatever the device's pitch (d.mw)
+    const struct { void *dst; size_t off, end, elem; } parts[] = {{W, 0, d.off_v(), 4},
+                                                                  {V, d.off_v(), d.off_m(), 4},
+                                                                  {M, d.off_m(), d.off_n(), 4},
+                                                                  {nmodes, d.off_n(), d.state_bytes(), 1}};
+    const size_t mw = m->row->work.mw;
     for (const auto &pt : parts)
-        if (pt.dst) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(pt.dst, st + pt.off, pt.end - pt.off, hipMemcpyDeviceToHost, ctx->stream));
+        if (pt.dst && d.mw == (int)mw)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(pt.dst, st + pt.off, pt.end - pt.off, hipMemcpyDeviceToHost, ctx->stream));
+        else if (pt.dst)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(pt.dst, mw * pt.elem, st + pt.off, d.mw * pt.elem, mw * pt.elem,
+                                                    (pt.end - pt.off) / (d.mw * pt.elem), hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n) *n = m->n[stream];
     return COVAHIP_OK;

@@ -2,7 +2,9 @@
 // macroblock grid: half-resolution working frames) and mog_band.hip (the macroblock grid of 1440p and 4K sources, whose planes
 // are worked on in row bands): the MOG2 pixel update, the update kernel's body, and the morphology and
 // hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
-// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces.  There
+// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces, and
+// mog_any.hip the kernels of covahip_mog_create_any, whose geometry is an argument (it uses mog2_pixel and the loads of this
+// file and has runtime-width twins of the post passes).  There
 // is one update body (update_body_strided; update_body adapts a BGR24 load to it) and one set of morphology passes (the band
 // passes; the resident kernels run them on the whole frame).  Below the namespace is the host side the four files share: the
 // table of admitted geometries, Geom's runtime twin, the dispatch on the working width and the banded kernel's LDS formula.
@@ -25,6 +27,14 @@
 
 #include "covahip.h"
 #include "internal.h"
+
+// An NV12 / I420 surface as a kernel sees it: plane offsets from a frame's first byte, pitches and the two strides in bytes (all
+// even), and the range's constants of include/covahip.h ("MoG labels", conversion): yy = max(0, Y - ysub) * ymul,
+// B += bu * uu, G -= gv * vv + gu * uu, R += rv * vv.
+struct covahip_mog_yuv_src {
+    long long off[3], pitch[3], frame_stride, stream_stride;
+    int ysub, ymul, bu, gv, gu, rv;
+};
 
 namespace mogdev {
 
@@ -244,6 +254,88 @@ struct LoadHalf {
         unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
         unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
         return {(float)s0, (float)s1, (float)s2};
+    }
+};
+
+// Working pixel (x, y) of an NV12 / I420 surface (mog_yuv.hip states the loads; mog_any.hip uses the HALF kind too).  KIND is how
+// the working pixel comes from the source: YUV_HALF the 2x2 mean, YUV_COPY the pixel itself, YUV_PICK source pixel (3x + 1, 3y + 1).
+enum { YUV_HALF = 0, YUV_COPY = 1, YUV_PICK = 2 };
+
+__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
+
+template <int FMT, int KIND>
+struct LoadYuv {
+    static constexpr bool WAIT = true;         // the body waits for the model and the first frame once, before its loop
+    static constexpr int NV12 = COVAHIP_MOG_FMT_NV12, HALF = YUV_HALF, COPY = YUV_COPY;
+    covahip_mog_yuv_src a;
+    struct At { long long y, u, v; };          // bytes from the plane's first byte: Y sample(s), U (NV12: the UV pair), V
+    struct Raw { unsigned y0, y1, u, v; };     // HALF: two Y pairs; else y0 = Y.  NV12: u = the UV pair as loaded
+
+    __device__ __forceinline__ At at(int x, int y) const {
+        int yr, yb, cr, cc;                        // Y row and byte, chroma row and sample
+        if constexpr (KIND == HALF) {
+            yr = 2 * y, yb = 2 * x, cr = y, cc = x;
+        } else if constexpr (KIND == COPY) {
+            yr = y, yb = x, cr = y >> 1, cc = x >> 1;
+        } else {
+            yr = 3 * y + 1, yb = 3 * x + 1, cr = yr >> 1, cc = yb >> 1;
+        }
+        At t;
+        t.y = (long long)yr * a.pitch[0] + yb;
+        if constexpr (FMT == NV12) {
+            t.u = (long long)cr * a.pitch[1] + 2 * cc;
+            t.v = 0;
+        } else {
+            t.u = (long long)cr * a.pitch[1] + cc;
+            t.v = (long long)cr * a.pitch[2] + cc;
+        }
+        return t;
+    }
+
+    __device__ __forceinline__ Raw operator()(const uint8_t *__restrict__ fr, const At &t) const {
+        Raw r;
+        const uint8_t *py = fr + a.off[0] + t.y, *pu = fr + a.off[1] + t.u;
+        if constexpr (KIND == HALF) {
+            r.y0 = *reinterpret_cast<const uint16_t *>(py);
+            r.y1 = *reinterpret_cast<const uint16_t *>(py + a.pitch[0]);
+        } else {
+            r.y0 = *py;
+            r.y1 = 0;
+        }
+        if constexpr (FMT == NV12) {
+            r.u = *reinterpret_cast<const uint16_t *>(pu);
+            r.v = 0;
+        } else {
+            r.u = *pu;
+            r.v = *(fr + a.off[2] + t.v);
+        }
+        return r;
+    }
+
+    __device__ __forceinline__ Px px(const Raw &r) const {
+        const int U = FMT == NV12 ? (int)(r.u & 255u) : (int)r.u, V = FMT == NV12 ? (int)(r.u >> 8) : (int)r.v;
+        // every factor fits 24 bits (|uu|, |vv| <= 128, Y <= 255, the constants < 2^22) and every product 32, so the full-rate
+        // 24-bit multiply gives the int32 product of the header exactly
+        const int uu = U - 128, vv = V - 128, h = 1 << 19;
+        const int cb = h + __mul24(a.bu, uu), cg = h - __mul24(a.gv, vv) - __mul24(a.gu, uu), cr = h + __mul24(a.rv, vv);
+        auto yy = [&](unsigned Y) {
+            const int d = (int)Y - a.ysub;
+            return __mul24(d < 0 ? 0 : d, a.ymul);
+        };
+        if constexpr (KIND == HALF) {
+            const int q[4] = {yy(r.y0 & 255u), yy(r.y0 >> 8), yy(r.y1 & 255u), yy(r.y1 >> 8)};
+            int b = 2, g = 2, c = 2;
+#pragma unroll
+            for (int i = 0; i < 4; i++) {
+                b += sat8((q[i] + cb) >> 20);
+                g += sat8((q[i] + cg) >> 20);
+                c += sat8((q[i] + cr) >> 20);
+            }
+            return {(float)(b >> 2), (float)(g >> 2), (float)(c >> 2)};
+        } else {
+            const int q = yy(r.y0);
+            return {(float)sat8((q + cb) >> 20), (float)sat8((q + cg) >> 20), (float)sat8((q + cr) >> 20)};
+        }
     }
 };
 
@@ -636,13 +728,16 @@ constexpr size_t COVAHIP_MOG_BAND_LDS_MAX = 160 * 1024 - 64;
 int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);
-// The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries.  A surface as a kernel sees it: plane
-// offsets from a frame's first byte, pitches and the two strides in bytes (all even), and the range's constants of
-// include/covahip.h ("MoG labels", conversion): yy = max(0, Y - ysub) * ymul, B += bu * uu, G -= gv * vv + gu * uu, R += rv * vv.
-struct covahip_mog_yuv_src {
-    long long off[3], pitch[3], frame_stride, stream_stride;
-    int ysub, ymul, bu, gv, gu, rv;
-};
+// The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries, on a covahip_mog_yuv_src (above).
 // load: MOG_LOAD_* of the labeller's row (copy and centre pick exist at working width 640 only)
 int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int load, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
                            const MogUpdateArgs &a);
+// The general kernels (mog_any.hip): the macroblock grid at any working size mw x mh, 128 <= mw, mh <= 2048, as arguments of the
+// kernels.  Rows of the planes and of the model lie at a pitch of mog_any_pitch(mw) pixels, so the sizes of a labeller's buffers
+// are those of MogDims{mog_any_pitch(mw), mh}.  plane and rows as for covahip_mog_band_post, with band_lds_bytes at the pitch.
+constexpr int mog_any_pitch(int mw) { return (mw + 63) / 64 * 64; }
+int covahip_mog_any_update(covahip_ctx *ctx, int mw, int mh, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
+int covahip_mog_any_yuv_update(covahip_ctx *ctx, int format, int mw, int mh, const uint8_t *frames, const covahip_mog_yuv_src &src,
+                               const MogUpdateArgs &a);
+int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,
+                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);

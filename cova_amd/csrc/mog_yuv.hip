@@ -4,7 +4,7 @@
 // mog2_pixel, the ballot word, the model's layout; the post kernels are those of mog.hip, mog_grid.hip and mog_band.hip.
 //
 //   k_mog_yuv_update<G, FMT, KIND>  update_body_strided (the one update body; LoadYuv::WAIT makes it wait once before its
-//                                   loop) with LoadYuv: one lane per working pixel and stream, a wave owns 64 consecutive x
+//                                   loop) with LoadYuv (mog_dev.h): one lane per working pixel and stream, a wave owns 64 consecutive x
 //                                   of one row.  KIND is how the working pixel comes from the source:
 //     HALF  (the macroblock grid's half sizes and 1280x720 on either grid) a 16-bit word at byte 2x of Y rows 2y and 2y + 1 and,
 //           NV12, a 16-bit word at byte 2x of UV row y: three loads of 128 contiguous bytes per wave.  I420 loads one byte each
@@ -28,85 +28,8 @@ namespace {
 
 using namespace mogdev;
 
-enum { HALF = 0, COPY = 1, PICK = 2 };
+constexpr int HALF = YUV_HALF, COPY = YUV_COPY, PICK = YUV_PICK;   // LoadYuv's kinds (mog_dev.h)
 constexpr int NV12 = COVAHIP_MOG_FMT_NV12, I420 = COVAHIP_MOG_FMT_I420;
-
-__device__ __forceinline__ int sat8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
-
-template <int FMT, int KIND>
-struct LoadYuv {
-    static constexpr bool WAIT = true;         // the body waits for the model and the first frame once, before its loop
-    covahip_mog_yuv_src a;
-    struct At { long long y, u, v; };          // bytes from the plane's first byte: Y sample(s), U (NV12: the UV pair), V
-    struct Raw { unsigned y0, y1, u, v; };     // HALF: two Y pairs; else y0 = Y.  NV12: u = the UV pair as loaded
-
-    __device__ __forceinline__ At at(int x, int y) const {
-        int yr, yb, cr, cc;                        // Y row and byte, chroma row and sample
-        if constexpr (KIND == HALF) {
-            yr = 2 * y, yb = 2 * x, cr = y, cc = x;
-        } else if constexpr (KIND == COPY) {
-            yr = y, yb = x, cr = y >> 1, cc = x >> 1;
-        } else {
-            yr = 3 * y + 1, yb = 3 * x + 1, cr = yr >> 1, cc = yb >> 1;
-        }
-        At t;
-        t.y = (long long)yr * a.pitch[0] + yb;
-        if constexpr (FMT == NV12) {
-            t.u = (long long)cr * a.pitch[1] + 2 * cc;
-            t.v = 0;
-        } else {
-            t.u = (long long)cr * a.pitch[1] + cc;
-            t.v = (long long)cr * a.pitch[2] + cc;
-        }
-        return t;
-    }
-
-    __device__ __forceinline__ Raw operator()(const uint8_t *__restrict__ fr, const At &t) const {
-        Raw r;
-        const uint8_t *py = fr + a.off[0] + t.y, *pu = fr + a.off[1] + t.u;
-        if constexpr (KIND == HALF) {
-            r.y0 = *reinterpret_cast<const uint16_t *>(py);
-            r.y1 = *reinterpret_cast<const uint16_t *>(py + a.pitch[0]);
-        } else {
-            r.y0 = *py;
-            r.y1 = 0;
-        }
-        if constexpr (FMT == NV12) {
-            r.u = *reinterpret_cast<const uint16_t *>(pu);
-            r.v = 0;
-        } else {
-            r.u = *pu;
-            r.v = *(fr + a.off[2] + t.v);
-        }
-        return r;
-    }
-
-    __device__ __forceinline__ Px px(const Raw &r) const {
-        const int U = FMT == NV12 ? (int)(r.u & 255u) : (int)r.u, V = FMT == NV12 ? (int)(r.u >> 8) : (int)r.v;
-        // every factor fits 24 bits (|uu|, |vv| <= 128, Y <= 255, the constants < 2^22) and every product 32, so the full-rate
-        // 24-bit multiply gives the int32 product of the header exactly
-        const int uu = U - 128, vv = V - 128, h = 1 << 19;
-        const int cb = h + __mul24(a.bu, uu), cg = h - __mul24(a.gv, vv) - __mul24(a.gu, uu), cr = h + __mul24(a.rv, vv);
-        auto yy = [&](unsigned Y) {
-            const int d = (int)Y - a.ysub;
-            return __mul24(d < 0 ? 0 : d, a.ymul);
-        };
-        if constexpr (KIND == HALF) {
-            const int q[4] = {yy(r.y0 & 255u), yy(r.y0 >> 8), yy(r.y1 & 255u), yy(r.y1 >> 8)};
-            int b = 2, g = 2, c = 2;
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                b += sat8((q[i] + cb) >> 20);
-                g += sat8((q[i] + cg) >> 20);
-                c += sat8((q[i] + cr) >> 20);
-            }
-            return {(float)(b >> 2), (float)(g >> 2), (float)(c >> 2)};
-        } else {
-            const int q = yy(r.y0);
-            return {(float)sat8((q + cb) >> 20), (float)sat8((q + cg) >> 20), (float)sat8((q + cr) >> 20)};
-        }
-    }
-};
 
 // frames: the launch's first frame of stream 0; par: (alphaT, prune) [F][S] of the call; bits: raw masks [F][S][G::NWORD]
 template <int MW, int MH, int FMT, int KIND>

@@ -3,8 +3,9 @@
   MogLabeler   covahip_mog_*: per-pixel MOG2 at 640x360, close 4x4, open 6x6, hole fill and the ::8 subsample to the 45x80
                labels `tfrecordsink gt=` reads, for several independent videos (streams) per call.  grid="macroblock" works
                at half the source instead and labels the source's own macroblocks: 68x120 for 1920x1080, and it alone
-               takes 2560x1440 (90x160 labels) and 3840x2160 (135x240)
-  label_dims   (label_h, label_w) of a source size on either grid, without a GPU
+               takes 2560x1440 (90x160 labels) and 3840x2160 (135x240).  any_size=True (macroblock grid) takes every even
+               source size from 256 to 4096 in both axes: 1280x960 gives 60x80 labels, 704x576 36x44
+  label_dims   (label_h, label_w) of a source size on either grid, without a GPU; label_dims_any / work_dims_any: of any_size
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
   apply_yuv    the same labels from 8-bit 4:2:0 frames as decoders give them, NV12 or I420, at a row pitch, plane offsets and
                frame / stream strides of the caller's (a MogYuv layout; yuv_tight makes the dense one), 1.5 bytes per pixel
@@ -15,6 +16,7 @@
     python -m cova_amd.mog --size 1280x720 a.bgr b.bgr:labels_b.dump ... [--streams S] [--chunk F]
     python -m cova_amd.mog --size 1920x1080 --grid macroblock IN.bgr ...      (68x120 labels: what 1080p records need)
     python -m cova_amd.mog --size 3840x2160 --grid macroblock IN.bgr ...      (135x240 labels; 2560x1440 gives 90x160)
+    python -m cova_amd.mog --any-size 1280x960 IN.bgr ...                     (60x80 labels; any even size, 256 .. 4096)
     ffmpeg -i VIDEO -f yuv4mpegpipe -pix_fmt yuv420p - | python -m cova_amd.mog --format y4m -:VIDEO_gt.dump
     python -m cova_amd.mog --format nv12 --size 1920x1080 [--range full] IN.nv12 ...     (also --format i420)
 
@@ -43,6 +45,7 @@ GRIDS = {"reference": 0, "macroblock": 1}       # COVAHIP_MOG_GRID_*
 GRID_SIZES = {"reference": SIZES, "macroblock": SIZES + ((2560, 1440), (3840, 2160))}   # the source sizes each grid takes
 FORMATS = {"nv12": 1, "i420": 2}                # COVAHIP_MOG_FMT_*
 RANGES = {"limited": 0, "full": 1}              # COVAHIP_MOG_RANGE_*
+ANY_MIN, ANY_MAX = 256, 4096                    # COVAHIP_MOG_ANY_*: what any_size admits, per axis and even
 
 
 def work_dims(w: int, h: int, grid: str = "reference"):
@@ -57,6 +60,19 @@ def work_dims(w: int, h: int, grid: str = "reference"):
 def label_dims(w: int, h: int, grid: str = "reference"):
     """(label_h, label_w) of a w x h source: one label per 8x8 block of the working image (its top-left pixel)."""
     ww, wh = work_dims(w, h, grid)
+    return (wh + 7) // 8, (ww + 7) // 8
+
+
+def work_dims_any(w: int, h: int):
+    """(work_w, work_h) of a w x h source with any_size=True: half the source, for every even size of ANY_MIN .. ANY_MAX."""
+    if w % 2 or h % 2 or not (ANY_MIN <= w <= ANY_MAX and ANY_MIN <= h <= ANY_MAX):
+        raise ValueError(f"unsupported size {w}x{h} for any_size: even, {ANY_MIN} .. {ANY_MAX} in both axes")
+    return w // 2, h // 2
+
+
+def label_dims_any(w: int, h: int):
+    """(label_h, label_w) of a w x h source with any_size=True: one label per macroblock, (ceil(h / 16), ceil(w / 16))."""
+    ww, wh = work_dims_any(w, h)
     return (wh + 7) // 8, (ww + 7) // 8
 
 
@@ -97,13 +113,20 @@ class MogLabeler:
     """covahip_mog_* over one ctx: `streams` videos of src_w x src_h BGR24 frames advance per `apply` call.  `grid` is
     "reference" (640x360 working frames, 45x80 labels) or "macroblock" (half the source, one label per macroblock of the
     source; 2560x1440 and 3840x2160 sources are this grid's alone); work_w, work_h, label_h and label_w say which shapes the
-    labeller takes and gives."""
+    labeller takes and gives.  any_size=True (macroblock grid only) admits every size of work_dims_any: a size of
+    GRID_SIZES["macroblock"] runs that grid's own kernels, any other the general ones (covahip_mog_create_any), which
+    force_general=True (tests, measurements) takes at every size; the results do not depend on which."""
 
     def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0,
-                 grid: str = "reference"):
+                 grid: str = "reference", any_size: bool = False, force_general: bool = False):
         if grid not in GRIDS:
             raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
-        if (src_w, src_h) in GRID_SIZES["macroblock"] and (src_w, src_h) not in GRID_SIZES[grid]:
+        any_size = any_size or force_general
+        if any_size:
+            if grid != "macroblock":
+                raise ValueError("any_size needs grid='macroblock'")
+            work_dims_any(src_w, src_h)                                      # ValueError before the ctx is touched
+        elif (src_w, src_h) in GRID_SIZES["macroblock"] and (src_w, src_h) not in GRID_SIZES[grid]:
             raise ValueError(f"{src_w}x{src_h} needs grid='macroblock'")     # (any other size is the library's to refuse)
         self.ctx = ctx
         self._lib = L.lib()
@@ -111,8 +134,12 @@ class MogLabeler:
         self._lib.covahip_mog_default_cfg(C.byref(cfg))
         cfg.src_w, cfg.src_h, cfg.n_streams, cfg.history, cfg.var_threshold = src_w, src_h, streams, history, var_threshold
         h = C.c_void_p()
-        L.check(self._lib.covahip_mog_create_grid(ctx.handle, C.byref(cfg), GRIDS[grid], C.byref(h)), "covahip_mog_create_grid",
-                ctx.handle)
+        self.general = force_general or (any_size and (src_w, src_h) not in GRID_SIZES["macroblock"])
+        if self.general:
+            L.check(self._lib.covahip_mog_create_any(ctx.handle, C.byref(cfg), C.byref(h)), "covahip_mog_create_any", ctx.handle)
+        else:
+            L.check(self._lib.covahip_mog_create_grid(ctx.handle, C.byref(cfg), GRIDS[grid], C.byref(h)), "covahip_mog_create_grid",
+                    ctx.handle)
         self.handle = h
         self.src_w, self.src_h, self.streams, self.grid = src_w, src_h, streams, grid
         d = [C.c_int32() for _ in range(4)]
@@ -420,6 +447,18 @@ def parse_size(text: str):
     return w, h
 
 
+def parse_any_size(text: str):
+    try:
+        w, h = (int(v) for v in text.lower().split("x"))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"size {text!r} is not WxH") from None
+    try:
+        work_dims_any(w, h)
+    except ValueError as e:
+        raise argparse.ArgumentTypeError(str(e)) from None
+    return w, h
+
+
 def parse_io(arg: str):
     """IN[:OUT] -> (IN, OUT); OUT defaults to IN's name with `_gt.dump`."""
     src, sep, out = arg.rpartition(":")
@@ -441,13 +480,16 @@ def _args(argv):
     ap.add_argument("--size", type=parse_size, default=None,
                     help="source size: 640x360, 1280x720 or 1920x1080; with --grid macroblock also 2560x1440 and 3840x2160 "
                          "(optional with --format y4m, whose header has it)")
+    ap.add_argument("--any-size", type=parse_any_size, default=None, metavar="WxH",
+                    help=f"instead of --size: any even source size, {ANY_MIN} .. {ANY_MAX} in both axes, on the macroblock grid "
+                         "(1280x960 -> 60x80 labels); a y4m header must state the same size")
     ap.add_argument("--format", choices=("bgr24", "nv12", "i420", "y4m"), default="bgr24",
                     help="bgr24: packed BGR, 3 bytes per pixel; nv12, i420: tight 4:2:0 frames, 1.5 bytes per pixel; y4m: "
                          "YUV4MPEG2 (ffmpeg -f yuv4mpegpipe -pix_fmt yuv420p)")
     ap.add_argument("--range", choices=sorted(RANGES), default=None,
                     help="of the YUV formats: limited (video, Y 16..235; the default) or full (JPEG, yuvj420p); a y4m header's XCOLORRANGE "
                          "must agree with it where one is given")
-    ap.add_argument("--grid", choices=sorted(GRIDS), default="reference",
+    ap.add_argument("--grid", choices=sorted(GRIDS), default=None,
                     help="reference: 45x80 labels whatever the source (the 1280x720 macroblock grid); macroblock: one label per "
                          "macroblock of the source, which 1080p records need (1920x1080 -> 68x120, 2560x1440 -> 90x160, "
                          "3840x2160 -> 135x240)")
@@ -467,11 +509,18 @@ def _args(argv):
             ap.error(str(e))
     if not a.inputs:
         ap.error("the following arguments are required: IN[:OUT]")
+    if a.any_size is not None:
+        if a.size is not None:
+            ap.error("--any-size stands instead of --size: give one of them")
+        if a.grid == "reference":
+            ap.error("--any-size is on the macroblock grid: it cannot go with --grid reference")
+        a.size, a.grid = a.any_size, "macroblock"
+    a.grid = a.grid or "reference"
     a.range_given = a.range is not None
     a.range = a.range or "limited"
     if a.size is None and a.format != "y4m":
         ap.error(f"--format {a.format} needs --size")
-    if a.size is not None and a.size not in GRID_SIZES[a.grid]:
+    if a.size is not None and a.any_size is None and a.size not in GRID_SIZES[a.grid]:
         ap.error(f"--size {a.size[0]}x{a.size[1]} needs --grid macroblock")
     if a.streams is None:
         a.streams = min(len(a.inputs), 8)
@@ -542,7 +591,7 @@ def main(argv=None) -> int:
     pending = list(a.inputs)
     yuv = a.format != "bgr24"
     ctx = Context(a.device)
-    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid)
+    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid, any_size=a.any_size is not None)
     layout = yuv_tight(w, h, "nv12" if a.format == "nv12" else "i420", a.range, streams=S) if yuv else None
     frames = np.empty((a.chunk, S, w * h * 3 // 2) if yuv else (a.chunk, S, h, w, 3), np.uint8)
     labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)

@@ -807,7 +807,8 @@ enum { COVAHIP_MOG_MAX_STREAMS = 1024, COVAHIP_MOG_LABEL_H = 45, COVAHIP_MOG_LAB
 typedef struct covahip_mog covahip_mog;
 typedef struct covahip_mog_cfg {
     int32_t src_w, src_h;       /* 640x360, 1280x720 or 1920x1080 (BGR24, or NV12 / I420 through covahip_mog_apply_yuv); on the
-                                 * macroblock grid also 2560x1440 and 3840x2160 */
+                                 * macroblock grid also 2560x1440 and 3840x2160; covahip_mog_create_any: any even size of
+                                 * COVAHIP_MOG_ANY_MIN .. COVAHIP_MOG_ANY_MAX */
     int32_t n_streams;          /* independent videos advanced per call, 1 .. COVAHIP_MOG_MAX_STREAMS */
     int32_t history;            /* 9000 (generate-mog.py); >= 1 */
     float   var_threshold;      /* 32; finite and > 0 */
@@ -821,6 +822,22 @@ int  covahip_mog_create(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mo
  * reset and destroy take either kind of labeller; in the comments below 45x80 stands for the labeller's label_h x label_w. */
 enum { COVAHIP_MOG_GRID_REFERENCE = 0, COVAHIP_MOG_GRID_MACROBLOCK = 1 };
 int  covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int grid, covahip_mog **out);
+/* The macroblock grid at any source size: src_w and src_h even and within COVAHIP_MOG_ANY_MIN .. COVAHIP_MOG_ANY_MAX (16
+ * macroblocks, the least a BlobNet is trained on; a plane row of at most 32 words), else COVAHIP_ERR_UNSUPPORTED, checked before
+ * the ctx is touched as covahip_mog_create_grid does; streams, history and var_threshold as there.  The steps are exactly the
+ * macroblock grid's: the working image is src/2 by the 2x2 rounded mean (work_w = src_w/2, work_h = src_h/2; either may be odd
+ * and neither need be a multiple of 8 or 64), MOG2, close 4x4, open 6x6 and the hole fill in working pixels, and
+ * label[i][j] = filled[8i][8j] for 8i < work_h, 8j < work_w: ceil(src_h/16) x ceil(src_w/16) labels, whose last row and column
+ * read a started macroblock.  The image ends at column work_w - 1 and row work_h - 1: those are the edge the hole fill starts
+ * from, and beyond them is 0 for dilate and 1 for erode.  1280x960 gives 60x80 labels, 704x576 36x44, 2592x1944 122x162.
+ * Every entry below takes such a labeller: dims, apply, apply_yuv (NV12 and I420, both ranges, any admitted layout; a picture of
+ * 960 rows in a taller coded surface is fine, nothing outside its rows is read), yuv_tight, reset and destroy, with n_valid,
+ * ragged streams and mixed apply / apply_yuv calls as for the others.  This entry always runs the general kernels (geometry
+ * as kernel arguments, the post kernel in row bands), also at a size covahip_mog_create_grid takes, where both give the same
+ * labels, masks and model bit for bit (DESIGN.md section 4 has the rates of both).  Model memory is 101 bytes per pixel of the
+ * working image at a row pitch of work_w rounded up to 64. */
+enum { COVAHIP_MOG_ANY_MIN = 256, COVAHIP_MOG_ANY_MAX = 4096 };
+int  covahip_mog_create_any(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out);
 /* The labeller's working size and label grid; any pointer may be NULL. */
 int  covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h);
 /* frames u8 [n_frames][n_streams][src_h][src_w][3]; labels u8 [n_frames][n_streams][45][80] (mem_kind applies to both; n_valid is
@@ -852,7 +869,9 @@ int  covahip_mog_apply(covahip_mog *m, const uint8_t *frames, int n_frames, cons
  * and grid.  n_valid, labels and mem_kind (which applies to base and labels) as for covahip_mog_apply; synchronous.
  * COVAHIP_ERR_INVALID_ARG, before anything is launched and with the model untouched: a NULL argument; an unknown format or
  * range; a negative offset, pitch or stride; pitch[0] < src_w; NV12 pitch[1] < src_w; I420 pitch[1] or pitch[2] < src_w/2; an
- * odd base, offset, pitch or stride (Y pairs and UV pairs are loaded as 16-bit words); whatever covahip_mog_apply refuses. */
+ * odd base, offset, pitch or stride (Y pairs and UV pairs are loaded as 16-bit words; a labeller of covahip_mog_create_any takes
+ * I420's U and V planes at odd offsets and pitches, as a tight frame has them where src_w/2 is odd: those samples are loaded
+ * one by one); whatever covahip_mog_apply refuses. */
 enum { COVAHIP_MOG_FMT_NV12 = 1, COVAHIP_MOG_FMT_I420 = 2 };
 enum { COVAHIP_MOG_RANGE_LIMITED = 0, COVAHIP_MOG_RANGE_FULL = 1 };
 typedef struct covahip_mog_yuv {   /* 72 bytes */

@@ -100,7 +100,10 @@ int covahip_dev_mog_post_masks(struct covahip_mog *m, const uint8_t *raw, int n_
  * with its resident kernel on the same planes; band_rows = 0 is the automatic plan (covahip_dev_mog_band_plan), otherwise the band
  * height, 16 .. work_h, whose staged window must fit LDS.  banded = 0 (band_rows = 0): the resident kernel.
  * COVAHIP_ERR_INVALID_ARG outside those ranges, for banded = 0 on a labeller that has no resident kernel and for banded = 1 on
- * one that has no banded kernel (the reference grid, 320x180).  The results do not depend on it. */
+ * one that has no banded kernel (the reference grid, 320x180).  The results do not depend on it.  A labeller of
+ * covahip_mog_create_any has the banded form only (mog_any.hip), with the window's rows at work_w rounded up to 64.  These
+ * entries, covahip_dev_mog_masks and covahip_dev_mog_state take such a labeller too, and give and take masks and model in the
+ * working image's own [work_h][work_w] order whatever pitch the device uses. */
 int covahip_dev_mog_set_post_form(struct covahip_mog *m, int banded, int band_rows);
 /* The automatic band plan of a working size (a multiple of 64 wide): `bands` bands of `rows` rows (the last may be shorter), as
  * few as fit, and the dynamic LDS of the launch: two planes of min(rows + 16, work_h) rows, 16 bytes of flags and 256 bytes per 64 columns for the column sweep, at most

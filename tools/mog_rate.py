@@ -5,6 +5,8 @@
     python tools/mog_rate.py --grid macroblock --sizes 1920x1080 --frames 256      (960x540 working frames, 68x120 labels)
     python tools/mog_rate.py --grid macroblock --sizes 3840x2160,2560x1440 --frames 64 --min-frames 2   (the banded kernels)
     python tools/mog_rate.py --format nv12 --sizes 1280x720      (covahip_mog_apply_yuv on tight NV12 frames; also i420)
+    python tools/mog_rate.py --general --sizes 1920x1080,1280x960 --frames 64 --min-frames 2 --reps 5
+                                 (covahip_mog_create_any's kernels: any even size, beside the table's kernels where a size has both)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -13,6 +15,9 @@ Each call advances every stream by frames / streams frames, so the model is read
 each kernel's share of the device call (HIP-event brackets, covahip_profile_*).  --oracle-frames > 0 adds a line with the numpy
 oracle's (tests/mog_ref.py) frames/s on this machine's CPU.  --format nv12 | i420 labels the same clip, converted once with a
 numpy forward transform (BT.601, limited range), from tight 4:2:0 frames of 1.5 bytes per pixel; every line says its format.
+--general (macroblock grid) times the general kernels ("device_general": MogLabeler(force_general=True)) at any admitted size;
+at a size the table has too, the table's labeller ("device") is timed in the same process on the same frames, call by call in
+turn, so the two lines compare.
 """
 import argparse
 import json
@@ -73,13 +78,17 @@ def main():
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--oracle-frames", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
+    ap.add_argument("--general", action="store_true", help="the general kernels (any even size of 256 .. 4096; implies --grid macroblock)")
     a = ap.parse_args()
+    if a.general:
+        a.grid = "macroblock"
+    parse_size = mog.parse_any_size if a.general else mog.parse_size
     for size in a.sizes.split(","):
-        if mog.parse_size(size) not in mog.GRID_SIZES[a.grid]:
+        if not a.general and parse_size(size) not in mog.GRID_SIZES[a.grid]:
             ap.error(f"--sizes {size} needs --grid macroblock")
     ctx = Context(0)
     for size in a.sizes.split(","):
-        w, h = mog.parse_size(size)
+        w, h = parse_size(size)
         pool = clip(8, w, h)
         yuv = a.format != "bgr24"
         if yuv:
@@ -90,12 +99,17 @@ def main():
             lay = mog.yuv_tight(w, h, a.format, streams=S) if yuv else None
             for f in range(F):
                 frames[f] = pool[(f + np.arange(S)) % len(pool)]
-            labels = np.zeros((F, S) + mog.label_dims(w, h, a.grid), np.uint8)
-            m = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid)
+            labels = np.zeros((F, S) + (mog.label_dims_any(w, h) if a.general else mog.label_dims(w, h, a.grid)), np.uint8)
+            # the labellers timed on the device, call by call in turn; the host case is the last one's
+            cases = {}
+            if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
+                cases["device"] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid)
+            if a.general:
+                cases["device_general"] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
 
-            def apply_device():
+            def apply_device(m):
                 if yuv:
                     m.apply_yuv_device(d_f, lay, F, d_l)
                 else:
@@ -107,26 +121,30 @@ def main():
                 else:
                     m.apply(frames, labels=labels)
 
-            apply_device()                                   # warm-up (buffers, code objects)
-            ms = []
+            for m in cases.values():
+                apply_device(m)                              # warm-up (buffers, code objects)
+            ms = {case: [] for case in cases}
             for _ in range(a.reps):
-                ctx.timer_start(0)
-                apply_device()
-                ctx.timer_stop(0)
-                ms.append(ctx.timer_ms(0))
-            ctx.profile(True)
-            apply_device()
-            prof = ctx.profile_read()
-            ctx.profile(False)
-            tot = sum(v[0] for k, v in prof.items() if k.startswith("mog_"))
-            med = statistics.median(ms)
-            rec = {"case": "device", "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
-                   "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms],
-                   "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
-                   "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
-            print(json.dumps(rec), flush=True)
+                for case, m in cases.items():
+                    ctx.timer_start(0)
+                    apply_device(m)
+                    ctx.timer_stop(0)
+                    ms[case].append(ctx.timer_ms(0))
+            for case, m in cases.items():
+                ctx.profile(True)
+                apply_device(m)
+                prof = ctx.profile_read()
+                ctx.profile(False)
+                tot = sum(v[0] for k, v in prof.items() if k.startswith("mog_"))
+                med = statistics.median(ms[case])
+                rec = {"case": case, "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F,
+                       "ms_per_call": round(med, 3), "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms[case]],
+                       "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
+                       "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
+                print(json.dumps(rec), flush=True)
             ctx.free(d_f)
             ctx.free(d_l)
+            m = list(cases.values())[-1]
             if not a.no_host:
                 apply_host()
                 wall = []
@@ -135,10 +153,11 @@ def main():
                     apply_host()
                     wall.append((time.perf_counter() - t0) * 1e3)
                 med = statistics.median(wall)
-                print(json.dumps({"case": "host", "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
+                print(json.dumps({"case": "host_general" if m.general else "host", "format": a.format, "src": size, "grid": a.grid, "streams": S, "frames_per_stream": F, "ms_per_call": round(med, 3),
                                   "frames_per_s": round(F * S / med * 1e3, 1), "in_gb_per_s": round(frames.nbytes / med / 1e6, 2),
                                   "ms_all": [round(x, 3) for x in wall]}), flush=True)
-            m.close()
+            for m in cases.values():
+                m.close()
             del frames
     ctx.close()
     if a.oracle_frames > 0:
