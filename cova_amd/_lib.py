@@ -257,6 +257,8 @@ PROTOTYPES = {
     "covahip_train_load_state": (C.c_int, [_P, _P, _SZ, C.POINTER(C.c_uint64)]),
     "covahip_train_set_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
     "covahip_train_get_plan": (C.c_int, [_P, C.POINTER(TrainPlan)]),
+    "covahip_train_set_math": (C.c_int, [_P, C.c_int]),
+    "covahip_train_get_math": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "covahip_train_set_post": (C.c_int, [_P, C.c_int, C.POINTER(BlobNetPost)]),
     "covahip_train_get_post": (C.c_int, [_P, C.c_int, C.POINTER(C.c_float), _P, C.POINTER(C.c_int)]),
     "covahip_train_destroy": (None, [_P]),

@@ -907,6 +907,309 @@ __global__ void k_adam_plan(Mdl md, float *__restrict__ w, float *__restrict__ g
     w[i] -= lr_t * mi / (sqrtf(vi) + eps);
 }
 
+// ------------------------------------------------------------------------------------------------ matrix-core convolutions
+// COVAHIP_TRAIN_MATH_MATRIX (include/covahip.h, "Training arithmetic"): the 3x3 convolution's forward, data gradient and weight
+// gradient and the transposed convolution's weight gradient as implicit GEMMs on v_mfma_f32_16x16x4_f32.  The instruction is an
+// fp32 fmaf chain in k order with one rounding per product, so the arithmetic is the plain kernels' precision class; the order
+// of the sums differs from theirs, which is why the mode is a choice and not a replacement.  Operands: lane l holds
+// A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15]; register r of the result is D[m = 4 * (l >> 4) + r][n = l & 15].
+//
+// The same guarantees as above: no float atomics; a weight gradient is split over the slabs wg_slabs gives for the model's own
+// batch, each slab is one workgroup's fixed-order sum and k_sum_slabs adds the slabs in order; the model is the grid's z index.
+// Every kernel walks tiles of consecutive positions in the tensors' own flattened order, so a row of any width is a sequence
+// of tiles and a narrow level packs several rows into one.  A tap's neighbour is staged by the row it belongs to (a row outside
+// the image stages zeros) and masked by the column of the position that reads it.
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+constexpr int MM_PT = 64;             // positions per tile: conv forward / data gradient / weight gradient
+constexpr int MM_KC = 8;              // summed channels staged at a time by the forward / data gradient
+constexpr int MM_XS = 80;             // floats per staged row there: 66 used; 80 = 16 mod 64 keeps the four k rows of a read on distinct banks
+constexpr int MM_WS = 68;             // floats per staged row of the weight gradients: = 4 mod 64, the 16 channels of a read on distinct banks
+constexpr int MM_TPT = 32;            // positions per tile: transposed-conv weight gradient
+constexpr int MM_TS = 36;             // floats per staged row there (= 4 mod 64)
+
+// FWD:   out[b][co][s] = relu(bias[co] + sum_{tap, ci} in[b][ci][s + tap] * k[tap][ci][co])        (in = x, Cin = Ci, Cout = Co)
+// DGRAD: out[b][ci][s] =                sum_{tap, co} in[b][co][s + tap] * k[8 - tap][ci][co]      (in = dA, Cin = Co, Cout = Ci)
+// s: a position of the sample's T*H*W block, tap = (dy, dx) in -1..1.  A workgroup: 64 positions of one sample, 16 * NACC output
+// channels (blockIdx.y); wave w: positions 16 w .. 16 w + 15.  M = output channel (A = weights), N = position (B = input),
+// K = (tap, summed channel), MM_KC channels at a time through LDS.  grid.x = largest batch * tiles per sample.
+template <bool SET, bool DGRAD, int NACC>
+__global__ void __launch_bounds__(BLK) k_conv3_mm(Mdl md, const float *__restrict__ in, const float *__restrict__ k,
+                                                  const float *__restrict__ bias, float *__restrict__ out, int Ci, int Co, int H, int W) {
+    constexpr int NB = 16 * NACC, WST = NB + 16;
+    __shared__ float xs[3 * MM_KC * MM_XS];
+    __shared__ float ws[9 * MM_KC * WST];
+    __shared__ int sy[MM_PT + 2];
+    const int B = model_b<SET>(md);
+    const int hw = H * W, S = TT * hw;
+    const int ntile = (S + MM_PT - 1) / MM_PT;
+    const int b = blockIdx.x / ntile, s0 = (blockIdx.x % ntile) * MM_PT;
+    if (b >= B) return;   // the whole workgroup: before the barriers
+    const int Cin = DGRAD ? Co : Ci, Cout = DGRAD ? Ci : Co, ob = blockIdx.y * NB;
+    in += MOFF(Cin * S) + (int64_t)b * Cin * S;
+    out += MOFF(Cout * S) + (int64_t)b * Cout * S;
+    k += POFF;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
+    const int s = s0 + wave * 16 + n;
+    const bool valid = s < S;
+    const int xq = s % W;
+    const bool okx[3] = {valid && xq > 0, valid, valid && xq < W - 1};
+    if (tid < MM_PT + 2) {   // the row of slot tid's position, or far outside
+        const int pj = s0 + tid - 1;
+        sy[tid] = pj >= 0 && pj < S ? (pj % hw) / W : -4;
+    }
+    f32x4 acc[NACC];
+    for (int a = 0; a < NACC; a++)
+        for (int r = 0; r < 4; r++) acc[a][r] = DGRAD ? 0.f : bias[POFF + ob + a * 16 + kq * 4 + r];
+    // A chunk's operands go global -> registers -> LDS: all loads of a chunk are in flight together, and the next chunk's are
+    // issued before this chunk's products, which hide them.
+    // Thread tid stages slot 1 + tid % 64 of the 24 input rows tid / 64 + 4 it; threads 0 .. 47 also slots 0 and 65 of a row.
+    constexpr int XI = 3 * MM_KC / 4, NWE = 9 * MM_KC * NB, WI = (NWE + BLK - 1) / BLK;
+    float xv[XI + 1], wv[WI];
+    const int er = tid >> 1, ej = (tid & 1) * (MM_PT + 1);
+    auto load = [&](int c0) {
+        const int yj = sy[lane + 1];
+#pragma unroll
+        for (int it = 0; it < XI; it++) {
+            const int dyi = it >> 1, c = c0 + 4 * (it & 1) + wave, yy = yj + dyi - 1;
+            xv[it] = c < Cin && yy >= 0 && yy < H ? in[(int64_t)c * S + (s0 + lane + (dyi - 1) * W)] : 0.f;
+        }
+        {
+            const int dyi = er >> 3, c = c0 + (er & 7), yy = tid < 6 * MM_KC ? sy[ej] + dyi - 1 : -1;
+            xv[XI] = c < Cin && yy >= 0 && yy < H ? in[(int64_t)c * S + (s0 + ej - 1 + (dyi - 1) * W)] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < WI; it++) {
+            const int e = tid + it * BLK;
+            int o, kc, tp;
+            if (DGRAD) { kc = e % MM_KC; o = (e / MM_KC) % NB; tp = e / (MM_KC * NB); }
+            else { o = e % NB; kc = (e / NB) % MM_KC; tp = e / (NB * MM_KC); }
+            const int c = c0 + kc;
+            wv[it] = e < NWE && c < Cin ? (DGRAD ? k[((8 - tp) * Ci + ob + o) * Co + c] : k[(tp * Ci + c) * Co + ob + o]) : 0.f;
+        }
+    };
+    __syncthreads();   // sy written
+    load(0);
+    for (int c0 = 0; c0 < Cin; c0 += MM_KC) {
+        __syncthreads();   // the previous chunk read
+#pragma unroll
+        for (int it = 0; it < XI; it++) xs[((it >> 1) * MM_KC + 4 * (it & 1) + wave) * MM_XS + lane + 1] = xv[it];
+        if (tid < 6 * MM_KC) xs[er * MM_XS + ej] = xv[XI];
+#pragma unroll
+        for (int it = 0; it < WI; it++) {
+            const int e = tid + it * BLK;
+            int o, kc, tp;
+            if (DGRAD) { kc = e % MM_KC; o = (e / MM_KC) % NB; tp = e / (MM_KC * NB); }
+            else { o = e % NB; kc = (e / NB) % MM_KC; tp = e / (NB * MM_KC); }
+            if (e < NWE) ws[(tp * MM_KC + kc) * WST + o] = wv[it];
+        }
+        __syncthreads();
+        if (c0 + MM_KC < Cin) load(c0 + MM_KC);
+        const int ksteps = Cin - c0 > 4 ? 2 : 1;
+        for (int tp = 0; tp < 9; tp++) {
+            const int dyi = tp / 3, dxi = tp % 3;
+            for (int ks = 0; ks < ksteps; ks++) {
+                const int kc = ks * 4 + kq;
+                const float xn = xs[(dyi * MM_KC + kc) * MM_XS + wave * 16 + n + dxi];
+                const float bv = okx[dxi] ? xn : 0.f;
+                for (int a = 0; a < NACC; a++)
+                    acc[a] = __builtin_amdgcn_mfma_f32_16x16x4f32(ws[(tp * MM_KC + kc) * WST + a * 16 + n], bv, acc[a], 0, 0, 0);
+            }
+        }
+    }
+    if (!valid) return;
+    for (int a = 0; a < NACC; a++)
+        for (int r = 0; r < 4; r++) {
+            const int ch = ob + a * 16 + kq * 4 + r;
+            out[(int64_t)ch * S + s] = DGRAD ? acc[a][r] : fmaxf(acc[a][r], 0.f);
+        }
+}
+
+// dK slabs of the conv on the matrix cores: the slab split of k_conv3_wgrad (wg_slabs of the model's positions, the same
+// chunk), slab[s][tap][ci][co].  Per tap a GEMM with M = ci (A = x at the tap's neighbour), N = co (B = dA), K = the slab's
+// positions, 64 at a time through LDS.  A workgroup: one 16-channel tile of ci, up to 64 of co (blockIdx.x), all nine taps;
+// its 9 * (co tiles) output tiles go round the four waves.  Ci = 3 is a tile whose other 13 rows are zero.
+template <bool SET>
+__global__ void __launch_bounds__(BLK) k_conv3_wgrad_mm(Mdl md, const float *__restrict__ dA, const float *__restrict__ x,
+                                                        float *__restrict__ slab, int Ci, int Co, int H, int W, int64_t solo_chunk) {
+    __shared__ float xs[3 * 16 * MM_WS];
+    __shared__ float ds[64 * MM_WS];
+    __shared__ int sb[MM_PT + 2], srem[MM_PT + 2], sy[MM_PT + 2], fl[MM_PT];
+    const int B = model_b<SET>(md);
+    const int hw = H * W, S = TT * hw;
+    const int64_t P = (int64_t)B * S;
+    const int ns = wg_slabs(P);
+    if (B == 0 || (int)blockIdx.y >= ns) return;   // the whole workgroup: before the barriers
+    const int64_t chunk = SET ? uniform64((P + ns - 1) / ns) : solo_chunk;
+    const int CT = Co < 64 ? Co : 64, nct = CT / 16, ncb = Co / CT;
+    const int ci0 = (blockIdx.x / ncb) * 16, cob = (blockIdx.x % ncb) * CT;
+    const int ntiles = 9 * nct, nw = 9 * Ci * Co;
+    dA += MOFF(Co * S);
+    x += MOFF(Ci * S);
+    slab += blockIdx.z * md.slab_stride;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+    f32x4 acc[9];
+    int xo[9], dof[9], xm[9];   // tile q of this wave: where its lane reads x and dA in LDS, and its column's bit (1 left, 2 right, 4 centre)
+#pragma unroll
+    for (int q = 0; q < 9; q++) {
+        acc[q] = f32x4{0.f, 0.f, 0.f, 0.f};
+        const int id = wave + 4 * q, tp = id / nct, cot = id % nct, dyi = tp / 3, dxi = tp % 3;
+        xo[q] = (dyi * 16 + n) * MM_WS + dxi;
+        dof[q] = (cot * 16 + n) * MM_WS;
+        xm[q] = dxi == 0 ? 1 : dxi == 2 ? 2 : 4;
+    }
+    for (int64_t pt = p0; pt < p1; pt += MM_PT) {
+        __syncthreads();   // the previous tile read
+        if (tid < MM_PT + 2) {   // slot tid: position pt + tid - 1
+            const int64_t pj = pt + tid - 1;
+            int bb = 0, rem = 0, yy = -4;
+            if (pj >= 0 && pj < P) {
+                bb = (int)(pj / S);
+                rem = (int)(pj % S);
+                const int sp = rem % hw, xq = sp % W;
+                yy = sp / W;
+                if (tid >= 1 && tid <= MM_PT) fl[tid - 1] = (xq > 0 ? 1 : 0) | (xq < W - 1 ? 2 : 0);
+            } else if (tid >= 1 && tid <= MM_PT) {
+                fl[tid - 1] = 0;
+            }
+            sb[tid] = bb;
+            srem[tid] = rem;
+            sy[tid] = yy;
+        }
+        __syncthreads();
+        // global -> registers -> LDS: all loads of the tile are in flight together.  Thread tid stages position tid % 64 of rows
+        // tid / 64 + 4 it; threads 0 .. 95 also slots 0 and 65 (the positions in front of and behind the tile) of a row of x.
+        constexpr int XI = 3 * 16 / 4, DI = 64 / 4;
+        float xv[XI + 1], dv[DI];
+        const int j = lane + 1;   // the slot of position tid % 64 (slot 0: the position in front of the tile)
+        const int64_t xb = (int64_t)sb[j] * Ci * S + srem[j], db = ((int64_t)sb[j] * Co + cob) * S + srem[j];
+        const int yj = sy[j];
+        const bool din = pt + lane < p1;
+#pragma unroll
+        for (int it = 0; it < XI; it++) {
+            const int dyi = it >> 2, ci = ci0 + 4 * (it & 3) + wave, yy = yj + dyi - 1;
+            xv[it] = ci < Ci && yy >= 0 && yy < H ? x[xb + (int64_t)ci * S + (dyi - 1) * W] : 0.f;
+        }
+        const int er = tid >> 1, ej = (tid & 1) * (MM_PT + 1);   // row er < 48, slot 0 or 65
+        {
+            const int dyi = er >> 4, ci = ci0 + (er & 15), yy = tid < 96 ? sy[ej] + dyi - 1 : -1;
+            xv[XI] = ci < Ci && yy >= 0 && yy < H ? x[((int64_t)sb[ej] * Ci + ci) * S + (srem[ej] + (dyi - 1) * W)] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < DI; it++) {
+            const int co = 4 * it + wave;
+            dv[it] = co < CT && din ? dA[db + (int64_t)co * S] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < XI; it++) xs[((it >> 2) * 16 + 4 * (it & 3) + wave) * MM_WS + j] = xv[it];
+        if (tid < 96) xs[er * MM_WS + ej] = xv[XI];
+#pragma unroll
+        for (int it = 0; it < DI; it++)
+            if (4 * it + wave < CT) ds[(4 * it + wave) * MM_WS + lane] = dv[it];
+        __syncthreads();
+#pragma unroll 2
+        for (int ks = 0; ks < MM_PT / 4; ks++) {
+            const int i = ks * 4 + kq, f = fl[i] | 4;
+#pragma unroll
+            for (int q = 0; q < 9; q++) {
+                if (wave + 4 * q < ntiles) {
+                    const float xn = xs[xo[q] + i];
+                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(f & xm[q] ? xn : 0.f, ds[dof[q] + i], acc[q], 0, 0, 0);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < 9; q++) {
+        const int id = wave + 4 * q;
+        if (id >= ntiles) continue;
+        const int tp = id / nct, cot = id % nct;
+        for (int r = 0; r < 4; r++) {
+            const int ci = ci0 + kq * 4 + r;
+            if (ci < Ci) slab[(int64_t)blockIdx.y * nw + (tp * Ci + ci) * Co + cob + cot * 16 + n] = acc[q][r];
+        }
+    }
+}
+
+// dK slabs of the convT on the matrix cores: the slab split of k_convT_wgrad, slab[s][ky][kx][co][ci].  Per tap a GEMM with
+// M = co (A = dy at the tap's output position, zero outside the crop), N = ci (B = zd), K = the slab's input positions, 32 at a
+// time through LDS.  A workgroup: 16 of co, 16 * NCI of ci (blockIdx.x), all sixteen taps; wave w: the four taps of ky = w.
+template <bool SET, int NCI>
+__global__ void __launch_bounds__(BLK) k_convT_wgrad_mm(Mdl md, const float *__restrict__ zd, const float *__restrict__ dy,
+                                                        float *__restrict__ slab, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy,
+                                                        int cx, int64_t solo_chunk) {
+    constexpr int CIB = 16 * NCI;
+    __shared__ float dys[16 * 16 * MM_TS];
+    __shared__ float zs[CIB * MM_TS];
+    __shared__ int pb[MM_TPT], ps[MM_TPT], piy[MM_TPT], pix[MM_TPT];
+    const int B = model_b<SET>(md);
+    const int hwi = Hi * Wi, hwo = Ho * Wo;
+    const int64_t P = (int64_t)B * hwi;
+    const int ns = wg_slabs(P);
+    if (B == 0 || (int)blockIdx.y >= ns) return;   // the whole workgroup: before the barriers
+    const int64_t chunk = SET ? uniform64((P + ns - 1) / ns) : solo_chunk;
+    const int ncib = Ci / CIB;
+    const int cob = (blockIdx.x / ncib) * 16, cib = (blockIdx.x % ncib) * CIB;
+    const int nw = 16 * Co * Ci;
+    zd += MOFF(Ci * hwi);
+    dy += MOFF(Co * hwo);
+    slab += blockIdx.z * md.slab_stride;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, n = lane & 15, kq = lane >> 4;
+    const int64_t p0 = (int64_t)blockIdx.y * chunk, p1 = p0 + chunk < P ? p0 + chunk : P;
+    f32x4 acc[4][NCI];
+    for (int kx = 0; kx < 4; kx++)
+        for (int c = 0; c < NCI; c++) acc[kx][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int64_t pt = p0; pt < p1; pt += MM_TPT) {
+        __syncthreads();   // the previous tile read
+        if (tid < MM_TPT) {
+            const int64_t p = pt + tid;
+            int bb = -1, sp = 0;
+            if (p < p1) {
+                bb = (int)(p / hwi);
+                sp = (int)(p % hwi);
+            }
+            pb[tid] = bb;
+            ps[tid] = sp;
+            piy[tid] = sp / Wi;
+            pix[tid] = sp % Wi;
+        }
+        __syncthreads();
+        // global -> registers -> LDS: all loads of the tile are in flight together.  Thread tid stages position tid % 32 throughout.
+        constexpr int YI = 16 * 16 * MM_TPT / BLK, ZI = CIB * MM_TPT / BLK;
+        float yv[YI], zv[ZI];
+        const int i = tid % MM_TPT, bi = pb[i], iy2 = 2 * piy[i] - cy, ix2 = 2 * pix[i] - cx, si = ps[i];
+#pragma unroll
+        for (int it = 0; it < YI; it++) {
+            const int r = tid / MM_TPT + it * (BLK / MM_TPT), co = r % 16, tap = r / 16;
+            const int yy = iy2 + (tap >> 2), xx = ix2 + (tap & 3);
+            yv[it] = bi >= 0 && yy >= 0 && yy < Ho && xx >= 0 && xx < Wo ? dy[((int64_t)bi * Co + cob + co) * hwo + (yy * Wo + xx)] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < ZI; it++) {
+            const int ci = tid / MM_TPT + it * (BLK / MM_TPT);
+            zv[it] = bi >= 0 ? zd[((int64_t)bi * Ci + cib + ci) * hwi + si] : 0.f;
+        }
+#pragma unroll
+        for (int it = 0; it < YI; it++) dys[(tid / MM_TPT + it * (BLK / MM_TPT)) * MM_TS + i] = yv[it];
+#pragma unroll
+        for (int it = 0; it < ZI; it++) zs[(tid / MM_TPT + it * (BLK / MM_TPT)) * MM_TS + i] = zv[it];
+        __syncthreads();
+        for (int ks = 0; ks < MM_TPT / 4; ks++) {
+            const int i = ks * 4 + kq;
+            float bv[NCI];
+            for (int c = 0; c < NCI; c++) bv[c] = zs[(c * 16 + n) * MM_TS + i];
+            for (int kx = 0; kx < 4; kx++) {
+                const float av = dys[((wave * 4 + kx) * 16 + n) * MM_TS + i];
+                for (int c = 0; c < NCI; c++) acc[kx][c] = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv[c], acc[kx][c], 0, 0, 0);
+            }
+        }
+    }
+    for (int kx = 0; kx < 4; kx++)
+        for (int c = 0; c < NCI; c++)
+            for (int r = 0; r < 4; r++)
+                slab[(int64_t)blockIdx.y * nw + ((wave * 4 + kx) * Co + cob + kq * 4 + r) * Ci + cib + c * 16 + n] = acc[kx][c][r];
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------------ host state
@@ -949,6 +1252,7 @@ struct covahip_train {
     std::vector<uint8_t> post_keep, post_flag;           // [K][hw], [K] (a post without a keep map has a row of ones)
     std::vector<float> post_thresh;                      // [K]
     bool any_post = false;             // some model has a post: the passes launch the POST forms
+    int math = COVAHIP_TRAIN_MATH_EXACT;   // covahip_train_set_math: which convolution kernels the passes launch
     PostTab post_tab() const { return PostTab{d_keep, d_post_thresh, d_post_flag}; }
 };
 
@@ -988,12 +1292,21 @@ DropS make_drop(const covahip_train *tr, int site) {
     return d;
 }
 
-// launch the set or the solo instantiation of kernel k on Run r's stream, for r's models
+// launch the set or the solo instantiation of kernel k on Run r's stream, for r's models, under the ctx profile's scope `k`
 #define KL(r, k, grid, block, ...)                                                     \
     do {                                                                               \
+        ProfScope ps_((r).tr->ctx, #k);                                                \
         if ((r).tr->K > 1) k<true><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__);    \
         else k<false><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__);                 \
     } while (0)
+// ... of a kernel with template arguments behind SET, under the scope `name`
+#define KLT(r, name, k, targs, grid, block, ...)                                                          \
+    do {                                                                                                  \
+        ProfScope ps_((r).tr->ctx, name);                                                                 \
+        if ((r).tr->K > 1) k<true, COVAHIP_UNPAREN targs><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__); \
+        else k<false, COVAHIP_UNPAREN targs><<<grid, block, 0, (r).s>>>((r).md, __VA_ARGS__);             \
+    } while (0)
+#define COVAHIP_UNPAREN(...) __VA_ARGS__
 
 // One pass (a step, or an evaluation chunk) over every model with a non-zero batch in tr->h_tab (K > 1: already uploaded to
 // d_tab); B = the largest batch.
@@ -1034,6 +1347,73 @@ struct Run {
     }
 };
 
+// ---------------------------------------------------------------- the matrix-core launches (COVAHIP_TRAIN_MATH_MATRIX)
+// The grid of each, as 64-bit extents for a largest batch B: the launches size their grids with these, and the planning pass of
+// covahip_train_set_math (mm_plan) holds them against the launch limits at max_batch before the mode is taken.
+struct Grid64 {
+    int64_t x, y;
+    bool fits() const { return x >= 1 && x <= INT32_MAX && y >= 1 && y <= 65535; }
+    dim3 dim(int K) const { return dim3((unsigned)x, (unsigned)y, (unsigned)K); }
+};
+inline int conv3_mm_nacc(int Cout) { return Cout >= 64 ? 4 : Cout / 16; }   // 16 * NACC output channels per workgroup
+Grid64 conv3_mm_grid(int64_t B, int64_t S, int Cout) { return Grid64{B * ((S + MM_PT - 1) / MM_PT), Cout / (16 * conv3_mm_nacc(Cout))}; }
+Grid64 conv3_wgrad_mm_grid(int64_t P, int Ci, int Co) { return Grid64{(int64_t)((Ci + 15) / 16) * (Co / std::min(Co, 64)), wg_slabs(P)}; }
+Grid64 convT_wgrad_mm_grid(int64_t P, int Ci, int Co) { return Grid64{(int64_t)(Co / 16) * (Ci / std::min(Ci, 64)), wg_slabs(P)}; }
+
+// conv forward (dgrad = false: in = x, bias, out = relu) or data gradient (in = dA, out = dx) of a level with Ci -> Co channels
+void launch_conv3_mm(Run &r, bool dgrad, const float *in, const float *k, const float *bias, float *out, int Ci, int Co, int H, int W) {
+    const int Cout = dgrad ? Ci : Co;
+    const dim3 g = conv3_mm_grid(r.B, (int64_t)TT * H * W, Cout).dim(r.tr->K);
+#define MM_CASE(D, N)                                                                                                    \
+    if (dgrad == D && conv3_mm_nacc(Cout) == N) {                                                                        \
+        KLT(r, D ? "k_conv3_mm_dgrad" : "k_conv3_mm_fwd", k_conv3_mm, (D, N), g, BLK, in, k, bias, out, Ci, Co, H, W);  \
+        return;                                                                                                          \
+    }
+    MM_CASE(false, 1) MM_CASE(false, 2) MM_CASE(false, 4) MM_CASE(true, 1) MM_CASE(true, 2) MM_CASE(true, 4)
+#undef MM_CASE
+    r.rc = COVAHIP_ERR_UNSUPPORTED;   // a channel count mm_plan does not admit
+}
+void launch_conv3_wgrad_mm(Run &r, const float *dA, const float *x, int Ci, int Co, int H, int W) {
+    const int64_t P = (int64_t)r.B * TT * H * W;
+    const Grid64 g = conv3_wgrad_mm_grid(P, Ci, Co);
+    KL(r, k_conv3_wgrad_mm, (g.dim(r.tr->K)), BLK, dA, x, r.tr->slab, Ci, Co, H, W, (P + g.y - 1) / g.y);
+}
+void launch_convT_wgrad_mm(Run &r, const float *zd, const float *dy, int Ci, int Co, int Hi, int Wi, int Ho, int Wo, int cy, int cx) {
+    const int64_t P = (int64_t)r.B * Hi * Wi;
+    const Grid64 g = convT_wgrad_mm_grid(P, Ci, Co);
+    if (Ci >= 64)
+        KLT(r, "k_convT_wgrad_mm", k_convT_wgrad_mm, (4), (g.dim(r.tr->K)), BLK, zd, dy, r.tr->slab, Ci, Co, Hi, Wi, Ho, Wo, cy, cx, (P + g.y - 1) / g.y);
+    else
+        KLT(r, "k_convT_wgrad_mm", k_convT_wgrad_mm, (2), (g.dim(r.tr->K)), BLK, zd, dy, r.tr->slab, Ci, Co, Hi, Wi, Ho, Wo, cy, cx, (P + g.y - 1) / g.y);
+}
+
+// The planning pass of the matrix mode: every launch of a full step at max_batch, none made.  The kernels' own limits: channel
+// counts in whole 16-channel tiles (Ci = 3 of level 0 is padded inside the kernels), a sample's block and a slab's position
+// within a sample in 32 bits, the grids within the launch limits, the slab workspace as the plain kernels size it (the same
+// slab counts, the same floats per slab).  None of it depends on the row width: the kernels tile positions, not rows.
+// For the geometry covahip_train_create_set admits (16 <= h_mb, w_mb <= 1024, a level-0 elementwise grid within 2^31) every
+// check passes: the widest grid below, level 0's B * ceil(4 hw / 64), is a quarter of that elementwise grid (B * 64 hw / 256).
+int mm_plan(const covahip_train *tr) {
+    const int64_t mb = tr->cfg.max_batch;
+    if (tr->K > 65535) return COVAHIP_ERR_UNSUPPORTED;
+    for (int i = 0; i < NL; i++) {
+        const int Ci = ENC_C[i], Co = ENC_C[i + 1];
+        const int64_t S = (int64_t)TT * tr->H[i] * tr->W[i];
+        if (Co % 16 || (i > 0 && Ci % 16) || (Co > 64 && Co % 64) || S * std::max(Ci, Co) > INT32_MAX) return COVAHIP_ERR_UNSUPPORTED;
+        if (!conv3_mm_grid(mb, S, Co).fits() || (i > 0 && !conv3_mm_grid(mb, S, Ci).fits())) return COVAHIP_ERR_UNSUPPORTED;
+        const Grid64 g = conv3_wgrad_mm_grid(mb * S, Ci, Co);
+        if (!g.fits() || (size_t)9 * Ci * Co * g.y > tr->slab_floats) return COVAHIP_ERR_UNSUPPORTED;
+    }
+    for (int j = 0; j < NL; j++) {
+        const int Ci = DEC_CI[j], Co = DEC_CO[j];
+        const int64_t Si = (int64_t)tr->H[NL - j] * tr->W[NL - j], So = (int64_t)tr->H[NL - 1 - j] * tr->W[NL - 1 - j];
+        if (Co % 16 || Ci % 32 || (Ci > 64 && Ci % 64) || Si * Ci > INT32_MAX || So * Co > INT32_MAX) return COVAHIP_ERR_UNSUPPORTED;
+        const Grid64 g = convT_wgrad_mm_grid(mb * Si, Ci, Co);
+        if (!g.fits() || (size_t)16 * Ci * Co * g.y > tr->slab_floats) return COVAHIP_ERR_UNSUPPORTED;
+    }
+    return COVAHIP_OK;
+}
+
 BNTab bn_table(const covahip_train *tr) {
     BNTab bn;
     for (int i = 0; i < NL; i++) {
@@ -1064,6 +1444,7 @@ int forward(Run &r, const Fwd &f) {
     float *P = tr->params, *G = tr->grads;
     const int H0 = tr->H[0], W0 = tr->W[0];
     auto inf = [&](int layer) { return (f.bn_inf >> layer & 1u) != 0; };
+    const bool mm = tr->math == COVAHIP_TRAIN_MATH_MATRIX;
     if (f.bn_inf)
         KL(r, k_bn_stat, (dim3(2 * NL - 1, 1, tr->K)), 128, P, f.stat_to_grads ? G : nullptr, tr->stat, bn_table(tr), f.bn_inf,
                                                           tr->cfg.bn_eps);
@@ -1073,7 +1454,8 @@ int forward(Run &r, const Fwd &f) {
         const BnEncOff &o = BN_LAYOUT.enc[i];
         const float *xin = i ? tr->e[i - 1] : tr->x0;
         const int64_t S = (int64_t)TT * H * W;
-        KL(r, k_conv3_fwd, (r.g1(B * Co * S)), BLK, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
+        if (mm) launch_conv3_mm(r, false, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
+        else KL(r, k_conv3_fwd, (r.g1(B * Co * S)), BLK, xin, P + o.k, P + o.b, tr->c[i], Ci, Co, H, W);
         if (!inf(i)) {
             r.reduce(R_SUM, Co, S, tr->c[i], nullptr, 0, nullptr, nullptr, F_MEAN, r.stat(i), STAT_STRIDE, nullptr, nullptr, nullptr, nullptr);
             r.reduce(R_SQDEV, Co, S, tr->c[i], nullptr, 0, r.stat(i), nullptr, F_VAR, r.stat(i), STAT_STRIDE, G + o.mean, G + o.var, P + o.mean,
@@ -1125,6 +1507,7 @@ int run_step(covahip_train *tr, int B) {
     // decoder blocks 0..j.  need_dz[j]: block j's input gradient has a reader (the BN of block j - 1, or the encoder through
     // the skip channels); need_dy[j]: block j's output gradient has one (its own weights, or need_dz[j]).
     const uint32_t fz = tr->frozen, bninf = tr->bn_inf;
+    const bool mm = tr->math == COVAHIP_TRAIN_MATH_MATRIX;
     auto enc_fz = [&](int i) { return (fz >> i & 1u) != 0; };
     auto dec_fz = [&](int j) { return (fz >> (NL + j) & 1u) != 0; };
     auto inf = [&](int layer) { return (bninf >> layer & 1u) != 0; };
@@ -1176,8 +1559,10 @@ int run_step(covahip_train *tr, int B) {
             r.reduce(R_SUM, Co, So, tr->dy[j], nullptr, 0, nullptr, nullptr, F_SUM, nullptr, 0, G + o.b, nullptr, nullptr, nullptr);
             const int ns = wg_slabs(Pp);
             const int nw = 16 * Co * Ci;
-            KL(r, k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
-                                                               tr->cx[j], (Pp + ns - 1) / ns);
+            if (mm) launch_convT_wgrad_mm(r, tr->zd[j], tr->dy[j], Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j], tr->cx[j]);
+            else
+                KL(r, k_convT_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->zd[j], tr->dy[j], tr->slab, Ci, Co, Hi, Wi, Ho, Wo, tr->cy[j],
+                                                                   tr->cx[j], (Pp + ns - 1) / ns);
             KL(r, k_sum_slabs, (r.g1(nw)), BLK, tr->slab, per, 0, nw, G + o.k);
         }
         if (need_dz[j])
@@ -1210,10 +1595,14 @@ int run_step(covahip_train *tr, int B) {
             const int64_t Pp = (int64_t)B * S;
             const int ns = wg_slabs(Pp);
             const int nw = 9 * Ci * Co;
-            KL(r, k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
+            if (mm) launch_conv3_wgrad_mm(r, tr->dc[i], xin, Ci, Co, H, W);
+            else KL(r, k_conv3_wgrad, (dim3(nblk(nw), ns, K)), BLK, tr->dc[i], xin, tr->slab, Ci, Co, H, W, (Pp + ns - 1) / ns);
             KL(r, k_sum_slabs, (r.g1(nw)), BLK, tr->slab, S, 0, nw, G + o.k);
         }
-        if (i > 0 && enc_live(i - 1)) KL(r, k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
+        if (i > 0 && enc_live(i - 1)) {
+            if (mm) launch_conv3_mm(r, true, tr->dc[i], P + o.k, nullptr, tr->de[i - 1], Ci, Co, H, W);
+            else KL(r, k_conv3_dgrad, (r.g1((int64_t)B * Ci * S)), BLK, tr->dc[i], P + o.k, tr->de[i - 1], Ci, Co, H, W);
+        }
         if (!r.ok()) return r.rc;
     }
 
@@ -1694,6 +2083,21 @@ int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan) {
     if (!tr || !plan) return COVAHIP_ERR_INVALID_ARG;
     plan->frozen_groups = tr->frozen;
     plan->bn_inference = tr->bn_inf;
+    return COVAHIP_OK;
+}
+
+int covahip_train_set_math(covahip_train *tr, int math) {
+    if (!tr || (math != COVAHIP_TRAIN_MATH_EXACT && math != COVAHIP_TRAIN_MATH_MATRIX)) return COVAHIP_ERR_INVALID_ARG;
+    if (math == COVAHIP_TRAIN_MATH_MATRIX)
+        if (int rc = mm_plan(tr)) return rc;   // before anything changes
+    // every entry point of the trainer is synchronous: no step is in flight that the switch could divide
+    tr->math = math;
+    return COVAHIP_OK;
+}
+
+int covahip_train_get_math(covahip_train *tr, int *math) {
+    if (!tr || !math) return COVAHIP_ERR_INVALID_ARG;
+    *math = tr->math;
     return COVAHIP_OK;
 }
 

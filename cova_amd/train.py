@@ -57,6 +57,11 @@ as --set -o names weight files); --ignore-rects L,T,W,H[+L,T,W,H...] and --mask-
 a sidecar.  Macroblocks in the ignore region take no part in the loss, its gradient or the metrics, and the metrics count
 logit > threshold as serving does.  The post is not part of the checkpoint either: --resume takes it from the command line again.
 
+Matrix-core arithmetic (include/covahip.h, "Training arithmetic"): --math matrix runs the convolutions of every step and
+evaluation as fp32 implicit GEMMs on the matrix cores, two to five times faster per step; --math exact (the default) is the
+trainer as it always was.  A run is bit-reproducible within its mode; the mode is not part of the checkpoint, and a checkpoint
+of one mode resumes in the other.  It combines with every other flag.
+
 Training from resident frames (include/covahip.h, "Training data"): every window of a recording, mirrored, reversed, reshuffled,
 
     python -m cova_amd.train CAM.tfrecord -o blobnet.cvhw --windows overlap --stride 1,2 --flip xy --reverse --shuffle --data-seed 1
@@ -467,6 +472,9 @@ WEIGHT_FILE_BYTES = 64 + 4 * W.N_PARAMS
 _BEST_HEAD = struct.Struct("<4sI")
 
 
+MATH_MODES = ("exact", "matrix")    # COVAHIP_TRAIN_MATH_EXACT, COVAHIP_TRAIN_MATH_MATRIX
+
+
 class _State:
     """Trainer state and best-epoch bookkeeping of TrainerSet and Trainer (both hold .handle, .ctx, ._lib)."""
 
@@ -506,6 +514,21 @@ class _State:
         p = L.TrainPlan()
         L.check(self._lib.covahip_train_get_plan(self.handle, C.byref(p)), "covahip_train_get_plan")
         return plan_names(p.frozen_groups, p.bn_inference)
+
+    def set_math(self, math: str) -> None:
+        """The arithmetic of the convolutions from the next step or evaluation on (for every model of a set): "exact", the plain
+        kernels (the default), or "matrix", the matrix-core implicit GEMMs (covahip_train_set_math).  Both are fp32 throughout;
+        a run is bit-reproducible within its mode, not across the two.  Like the plan the mode is not part of the trainer
+        state: a state saved in one mode loads in the other."""
+        if math not in MATH_MODES:
+            raise ValueError(f"math must be one of {', '.join(MATH_MODES)}, not {math!r}")
+        L.check(self._lib.covahip_train_set_math(self.handle, MATH_MODES.index(math)), "covahip_train_set_math", self.ctx.handle)
+
+    @property
+    def math(self) -> str:
+        m = C.c_int()
+        L.check(self._lib.covahip_train_get_math(self.handle, C.byref(m)), "covahip_train_get_math")
+        return MATH_MODES[m.value]
 
     def load_state(self, path) -> int:
         with open(path, "rb") as f:
@@ -1324,6 +1347,10 @@ def parse_args(argv=None):
                                                    "score with its ignore region and mask threshold (with --set: one file for "
                                                    "every model, or a directory of <stem>.json per model, named as --set -o names "
                                                    "weight files)")
+    ap.add_argument("--math", choices=MATH_MODES, default="exact", help="the arithmetic of the convolutions: 'exact', the plain "
+                                                                        "kernels, or 'matrix', fp32 implicit GEMMs on the "
+                                                                        "matrix cores (faster; bit-reproducible within the "
+                                                                        "mode, not against 'exact')")
     ap.add_argument("--ignore-rects", type=_rects, metavar="L,T,W,H[+...]", help="pixel rectangles of the camera's ignore region, "
                                                                                  "for a camera without a sidecar")
     ap.add_argument("--mask-threshold", type=float, metavar="P", help="the camera's mask threshold as a probability, for a camera "
@@ -1507,10 +1534,12 @@ def main_eval(a) -> int:
     if a.as_set:
         ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=flats, max_batch=a.batch)
         _apply_posts(ts, posts)
+        ts.set_math(a.math)
         evs = ts.evaluate(records)
     else:
         ts = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, weights_flat=flats[0])
         _apply_posts(ts, posts)
+        ts.set_math(a.math)
         evs = [ts.evaluate(records[0])]
     for k, ((_, path), ev) in enumerate(zip(jobs, evs)):
         if posts is not None:
@@ -1560,6 +1589,7 @@ def main_set(a) -> int:
     ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=init, n_models=len(jobs), seeds=[a.seed + k for k in range(len(jobs))],
                     max_batch=a.batch, **_plan_kw(a))
     _apply_posts(ts, posts)
+    ts.set_math(a.math)
     start = _resume(ts, a, len(jobs))
     ts.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)
@@ -1606,6 +1636,7 @@ def main_resident(a) -> int:
     if a.eval_only:
         ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=[_read_weights(p) for _, p in jobs], max_batch=a.batch)
         _apply_posts(ts, posts)
+        ts.set_math(a.math)
         for k, ((_, path), ev) in enumerate(zip(jobs, ts.evaluate_data(data, tables, min(strides)))):
             if posts is not None:
                 thr, keep = ts.get_post(k)
@@ -1621,6 +1652,7 @@ def main_resident(a) -> int:
                         max_batch=a.batch, **_plan_kw(a))
         ts._tag_models = a.as_set
         _apply_posts(ts, posts)
+        ts.set_math(a.math)
         start = _resume(ts, a, len(jobs))
         ts.fit_data(data, tables, epochs=a.epochs, batch=a.batch, strides=strides, shuffle=a.shuffle, flip=a.flip or (),
                     reverse=a.reverse, data_seed=a.data_seed or 0, val_tables=val_tables, log=lambda s: print(s, file=sys.stderr),
@@ -1657,6 +1689,7 @@ def main(argv=None) -> int:
     tr = Trainer(ctx, a.h_mb, a.w_mb, max_batch=a.batch, seed=a.seed, weights_flat=_read_weights(a.init) if a.init else None,
                  **_plan_kw(a))
     _apply_posts(tr, posts)
+    tr.set_math(a.math)
     start = _resume(tr, a, 1)
     tr.fit(records, epochs=a.epochs, batch=a.batch, log=lambda s: print(s, file=sys.stderr), val=val, keep=a.keep,
            checkpoint=a.checkpoint, start_epoch=start)

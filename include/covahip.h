@@ -678,6 +678,31 @@ int covahip_train_get_plan(covahip_train *tr, covahip_train_plan *plan);
  *   Contracts A - D hold with "the model" read as "the model and its post"; a post combines with any training plan. */
 int covahip_train_set_post(covahip_train *tr, int model, const covahip_blobnet_post *post /* NULL = no post */);
 int covahip_train_get_post(covahip_train *tr, int model, float *logit_thresh, uint8_t *keep_or_null, int *has_post);
+/* Training arithmetic: which kernels compute the convolutions of a step and of an evaluation.  Both are fp32 throughout and
+ * compute the same sums; they differ in the ORDER of the additions inside a sum, so their results differ in the last bits.
+ *   COVAHIP_TRAIN_MATH_EXACT (the default): the plain kernels described above, one thread per output element or per weight.
+ *   They are the path pinned against f64 autograd and bit-reproducible against every earlier checkpoint.
+ *   COVAHIP_TRAIN_MATH_MATRIX: the 3x3 convolution's forward, data gradient and weight gradient and the transposed
+ *   convolution's weight gradient run as implicit GEMMs on the fp32-input matrix instruction (v_mfma_f32_16x16x4_f32: an fmaf
+ *   chain in k order, one rounding per product).  Everything else -- the transposed convolution's forward and data gradient,
+ *   BatchNorm, pooling, the temporal MLP, dropout, the loss, Adam -- runs the kernels of the exact mode.  No loss scaling, no
+ *   other tolerance, no change to the weight file.
+ * The guarantees of the trainer hold in either mode, each within its mode: no float atomics, a step is bit-reproducible, batch
+ * b of max_batch equals batch b of b, model k of a set equals the solo trainer, a skipped model is not touched, exact resume,
+ * frozen groups launch no weight-gradient work.  A matrix-mode run is NOT bit-identical to an exact-mode run.
+ * covahip_train_set_math: may be called between steps; applies to all models of a set; synchronous.  Every kernel limit of the
+ * matrix mode is checked here by a planning pass over the trainer's geometry at max_batch (COVAHIP_ERR_UNSUPPORTED, the mode
+ * unchanged; none of the geometries covahip_train_create admits is refused).  An unknown value is COVAHIP_ERR_INVALID_ARG
+ * and changes nothing.  Like the plan and the post the mode is NOT part of the state blob: a checkpoint written in one mode
+ * loads in the other, and a resumed run sets the mode again.
+ *   Contract H -- exact is what was.  A trainer that never calls covahip_train_set_math, or calls it with
+ *   COVAHIP_TRAIN_MATH_EXACT, launches the kernels it launched before the mode existed, with the same arguments. */
+enum {
+    COVAHIP_TRAIN_MATH_EXACT = 0,
+    COVAHIP_TRAIN_MATH_MATRIX = 1
+};
+int covahip_train_set_math(covahip_train *tr, int math);
+int covahip_train_get_math(covahip_train *tr, int *math);
 void covahip_train_destroy(covahip_train *tr);
 
 /* ------------------------------------------------------------ Training data

@@ -6,7 +6,8 @@ covahip_train_step calls on K solo trainers, one after the other in the same pro
 
 Device-pointer steps (the loss read-back included).  The two sides alternate, `--repeats` times per K: the spread of a side's
 rows is the box's noise.  One JSON line per K.  `--only set|solo` runs one side alone (a profiling run).  `--freeze GROUPS` /
-`--freeze-bn` put both sides under a training plan (cova_amd.train's flags of the same names)."""
+`--freeze-bn` put both sides under a training plan, `--math exact|matrix` in that arithmetic (cova_amd.train's flags of the same
+names)."""
 import argparse
 import json
 import os
@@ -42,6 +43,7 @@ def main():
     ap.add_argument("--only", choices=("set", "solo"))
     ap.add_argument("--freeze", default="")
     ap.add_argument("--freeze-bn", action="store_true")
+    ap.add_argument("--math", choices=T.MATH_MODES, default="exact")
     a = ap.parse_args()
     h, w, b = a.h_mb, a.w_mb, a.batch
     plan = {"freeze": a.freeze, "bn_inference": "all" if a.freeze_bn else ()}
@@ -55,6 +57,8 @@ def main():
         flats = [T.init_weights(m) for m in range(k)]
         ts = T.TrainerSet(ctx, h, w, weights=flats, seeds=list(range(k)), max_batch=b, **plan) if a.only != "solo" else None
         solos = [T.Trainer(ctx, h, w, max_batch=b, weights_flat=flats[m], seed=m, **plan) for m in range(k)] if a.only != "set" else []
+        for tr in ([ts] if ts else []) + solos:
+            tr.set_math(a.math)
         per_stack, per_gt = stack.nbytes // (k * b), gt.nbytes // (k * b)
 
         def solo_step():
@@ -67,7 +71,7 @@ def main():
                 set_ms.append(timed(lambda: ts.step_device(d_stack, d_gt, [b] * k), a.warmup, a.steps))
             if solos:
                 solo_ms.append(timed(solo_step, a.warmup, a.steps))
-        rec = {"h_mb": h, "w_mb": w, "batch": b, "models": k, "steps": a.steps, **T.plan_names(*T.plan_bits(**plan))}
+        rec = {"h_mb": h, "w_mb": w, "batch": b, "models": k, "steps": a.steps, "math": a.math, **T.plan_names(*T.plan_bits(**plan))}
         if set_ms:
             rec.update(set_ms_per_step=[round(v, 3) for v in set_ms], set_samples_per_s=round(1e3 * k * b / min(set_ms)))
         if solo_ms:
