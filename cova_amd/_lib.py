@@ -284,6 +284,8 @@ PROTOTYPES = {
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),
     "covahip_mog_create_any": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
+    "covahip_mog_set_labels": (C.c_int, [_P, C.c_int, C.c_int]),
+    "covahip_mog_get_labels": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "covahip_mog_dims": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "covahip_mog_apply": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_mog_yuv_tight": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MogYuv)]),

@@ -13,7 +13,8 @@
 //                 exactly ten waves wide) is one __ballot word: a frame's raw mask is 3,600 words, 28.8 KB.
 //   k_mog_post    one workgroup per (stream, frame): the bit plane in LDS, separable morphology on 64-bit words with shifts,
 //                 hole fill by seeding the background on the frame edge and propagating it (column sweeps + word-carry run
-//                 fill along rows) until a pass changes nothing, then the subsample.
+//                 fill along rows) until a pass changes nothing, then the subsample (label_bit) or, in the label modes
+//                 COVAHIP_MOG_LABELS_COVER / _COUNT of covahip_mog_set_labels, the blocks' coverage (cover_labels).
 //
 // No contraction in this file (see mog_dev.h): every product and sum is rounded on its own, as the x86 builds of OpenCV
 // compute it, and the update kernel's ISA has no f32 fused multiply-add at all (DESIGN.md checks it).
@@ -63,10 +64,10 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restr
     update_body<G>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
 }
 
-// bits: raw masks [F][S][3600]; filled_bits: the filled masks, same layout; labels [F][S][45][80]
+// bits: raw masks [F][S][3600]; filled_bits: the filled masks, same layout; labels [F][S][45][80]; mode, ncover: MogLabelArgs
 __global__ __launch_bounds__(POST_BLOCK) void k_mog_post(const unsigned long long *__restrict__ bits,
                                                          unsigned long long *__restrict__ filled_bits, uint8_t *__restrict__ labels,
-                                                         const int32_t *__restrict__ nvalid, int S) {
+                                                         const int32_t *__restrict__ nvalid, int S, int mode, int ncover) {
     __shared__ unsigned long long A[NWORD], T[NWORD];
     __shared__ int changed;
     const int fs = blockIdx.x;
@@ -79,9 +80,14 @@ __global__ __launch_bounds__(POST_BLOCK) void k_mog_post(const unsigned long lon
     post_planes<G, POST_BLOCK>(A, T, &changed);
     unsigned long long *dst = filled_bits + (size_t)fs * NWORD;
     uint8_t *lab = labels + (size_t)fs * NLAB;
-    for (int i = tid; i < NWORD; i += POST_BLOCK) {
-        dst[i] = ~T[i];
-        lab[i] = label_bit(T, i / LW, i % LW, ROWW);   // NLAB == NWORD here
+    if (mode == COVAHIP_MOG_LABELS_CORNER) {
+        for (int i = tid; i < NWORD; i += POST_BLOCK) {
+            dst[i] = ~T[i];
+            lab[i] = label_bit(T, i / LW, i % LW, ROWW);   // NLAB == NWORD here
+        }
+    } else {
+        for (int i = tid; i < NWORD; i += POST_BLOCK) dst[i] = ~T[i];
+        cover_labels<POST_BLOCK>(T, lab, MW, G::MH, ROWW, mode, ncover);
     }
 }
 
@@ -111,6 +117,7 @@ struct covahip_mog {
                                    // the pitch of mog_any_pitch
     bool banded = false;           // the post kernel of mog_band.hip, where the row has it
     int band_rows = 0;             // its band height; 0 = the automatic plan
+    MogLabelArgs labels;           // covahip_mog_set_labels: how every post launch takes its labels
     size_t src_bytes = 0;
     std::vector<int64_t> n;        // frames each stream has seen
     uint8_t *state = nullptr;      // [S][state_bytes]
@@ -168,12 +175,13 @@ int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, s
         if (!rows) band_plan(m->alloc.mw, m->alloc.mh, &rows, &bands);
         if (m->any)
             return covahip_mog_any_post(ctx, m->row->work.mw, m->row->work.mh, bits, filled, static_cast<unsigned long long *>(m->plane),
-                                        d_labels, d_nv, S, FS, rows);
+                                        d_labels, d_nv, S, FS, rows, m->labels);
         return covahip_mog_band_post(ctx, m->row->work.mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
-                                     rows);
+                                     rows, m->labels);
     }
-    if (m->row->work.mw != MW) return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS);
-    return mog_launch(ctx, "mog_post", k_mog_post, dim3((unsigned)FS), POST_BLOCK, 0, bits, filled, d_labels, d_nv, S);
+    if (m->row->work.mw != MW) return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS, m->labels);
+    return mog_launch(ctx, "mog_post", k_mog_post, dim3((unsigned)FS), POST_BLOCK, 0, bits, filled, d_labels, d_nv, S, m->labels.mode,
+                      m->labels.ncover);
 }
 
 bool cfg_ok(const covahip_mog_cfg *cfg) {
@@ -420,6 +428,25 @@ int covahip_mog_reset(covahip_mog *m, int stream) {
     if (int rc = covahip_primary_op(ctx)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(m->state + (size_t)stream * m->alloc.state_bytes(), 0, m->alloc.state_bytes(), ctx->stream));
     m->n[stream] = 0;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_set_labels(covahip_mog *m, int mode, int min_cover) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    if (mode != COVAHIP_MOG_LABELS_CORNER && mode != COVAHIP_MOG_LABELS_COVER && mode != COVAHIP_MOG_LABELS_COUNT)
+        return COVAHIP_ERR_INVALID_ARG;
+    if (mode == COVAHIP_MOG_LABELS_COVER) {
+        if (min_cover < 1 || min_cover > 64) return COVAHIP_ERR_INVALID_ARG;
+        m->labels.ncover = min_cover;          // (read in COVER mode only: the other modes keep the last one)
+    }
+    m->labels.mode = mode;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_get_labels(const covahip_mog *m, int *mode, int *min_cover) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    if (mode) *mode = m->labels.mode;
+    if (min_cover) *min_cover = m->labels.ncover;
     return COVAHIP_OK;
 }
 

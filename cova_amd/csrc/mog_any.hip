@@ -278,10 +278,11 @@ __device__ __forceinline__ bool fill_any(const u64 *A, u64 *T, int nrows, int ro
 }
 
 // bits: raw masks [F][S][roww mh]; filled_bits: the filled masks, same layout (T while the fill runs); plane: the mask after
-// the morphology, same layout; labels [F][S][lh][lw]; rows: band height, >= 1.  Dynamic LDS: band_lds_bytes(64 roww, mh, rows).
+// the morphology, same layout; labels [F][S][lh][lw]; rows: band height, >= 1; mode, ncover: MogLabelArgs.
+// Dynamic LDS: band_lds_bytes(64 roww, mh, rows).
 __global__ __launch_bounds__(POST_BLOCK) void k_mog_any_post(const u64 *__restrict__ bits, u64 *filled_bits, u64 *plane,
                                                              uint8_t *__restrict__ labels, const int32_t *__restrict__ nvalid, int S,
-                                                             int rows, int mw, int mh) {
+                                                             int rows, int mw, int mh, int mode, int ncover) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int roww = (mw + 63) / 64, nword = roww * mh, lw = (mw + 7) / 8, nlab = lw * ((mh + 7) / 8);
     const u64 tail = (mw & 63) ? (1ull << (mw & 63)) - 1 : ~0ull;
@@ -361,9 +362,14 @@ __global__ __launch_bounds__(POST_BLOCK) void k_mog_any_post(const u64 *__restri
         if (!again) break;
     }
 
-    // 3. labels from T, then filled = ~T inside the image, in place
+    // 3. labels from T (the bits beyond the image are still clear in it: cover_labels masks them itself), then filled = ~T
+    // inside the image, in place
     uint8_t *lab = labels + (size_t)fs * nlab;
-    for (int i = tid; i < nlab; i += POST_BLOCK) lab[i] = label_bit(Tg, i / lw, i % lw, roww);
+    if (mode == COVAHIP_MOG_LABELS_CORNER) {
+        for (int i = tid; i < nlab; i += POST_BLOCK) lab[i] = label_bit(Tg, i / lw, i % lw, roww);
+    } else {
+        cover_labels<POST_BLOCK>(Tg, lab, mw, mh, roww, mode, ncover);
+    }
     __syncthreads();
     for (int i = tid; i < nword; i += POST_BLOCK) Tg[i] = ~Tg[i] & (i % roww == roww - 1 ? tail : ~0ull);
 }
@@ -390,7 +396,8 @@ int covahip_mog_any_yuv_update(covahip_ctx *ctx, int format, int mw, int mh, con
 }
 
 int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,
-                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows) {
+                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
+                         MogLabelArgs la) {
     const int pitch = mog_any_pitch(mw);
     if (pitch / 64 * FILL_SEG > POST_BLOCK || rows < 16 || rows > mh) return COVAHIP_ERR_UNSUPPORTED;
     const size_t lds = band_lds_bytes(pitch, mh, rows);
@@ -398,5 +405,5 @@ int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long l
     // opened to the maximum: `rows` differs between launches
     if (int rc = covahip_open_lds(ctx, k_mog_any_post, lds, COVAHIP_MOG_BAND_LDS_MAX)) return rc;
     return mog_launch(ctx, "mog_any_post", k_mog_any_post, dim3((unsigned)FS), POST_BLOCK, lds, bits, filled_bits, plane, labels, nvalid, S,
-                      rows, mw, mh);
+                      rows, mw, mh, la.mode, la.ncover);
 }

@@ -19,7 +19,7 @@
 //        bands are visited downwards, then upwards, until a whole such sweep changed nothing.  The fixed point is the
 //        background 4-connected to the edge whatever the band plan, so the result equals the resident kernel's bit for bit.
 //        Termination is a flag in LDS; there is no iteration cap.
-//     3. filled = ~T and the labels, label (r, c) = filled pixel (8 c, 8 r).
+//     3. filled = ~T and the labels, label (r, c) = filled pixel (8 c, 8 r), or by block coverage (cover_labels of mog_dev.h).
 //   One workgroup reads what another of its threads wrote to global memory only across __syncthreads(), whose fences order
 //   global memory within the workgroup; the planes are not __restrict__.
 //
@@ -49,11 +49,12 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_band_update(const uint8_t *__
 }
 
 // bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout (T while the fill runs); plane: the mask after the
-// morphology, same layout; labels [F][S][LH][LW]; rows: band height, >= 1
+// morphology, same layout; labels [F][S][LH][LW]; rows: band height, >= 1; mode, ncover: MogLabelArgs
 template <int MW, int MH, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long long *__restrict__ bits, unsigned long long *filled_bits,
                                                          unsigned long long *plane, uint8_t *__restrict__ labels,
-                                                         const int32_t *__restrict__ nvalid, int S, int rows) {
+                                                         const int32_t *__restrict__ nvalid, int S, int rows, int mode,
+                                                         int ncover) {
     using G = Geom<MW, MH>;
     constexpr int NWORD = G::NWORD, NLAB = G::NLAB, LW = G::LW, ROWW = G::ROWW;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -132,7 +133,11 @@ __global__ __launch_bounds__(BLOCK) void k_mog_band_post(const unsigned long lon
 
     // 3. labels from T, then filled = ~T in place
     uint8_t *lab = labels + (size_t)fs * NLAB;
-    for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(Tg, i / LW, i % LW, ROWW);
+    if (mode == COVAHIP_MOG_LABELS_CORNER) {
+        for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(Tg, i / LW, i % LW, ROWW);
+    } else {
+        cover_labels<BLOCK>(Tg, lab, MW, MH, ROWW, mode, ncover);
+    }
     __syncthreads();
     for (int i = tid; i < NWORD; i += BLOCK) Tg[i] = ~Tg[i];
 }
@@ -150,7 +155,8 @@ int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, siz
 }
 
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
-                          unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows) {
+                          unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
+                          MogLabelArgs la) {
     return with_geom<G1920, G1280, G960>(mw, [&](auto g) -> int {
         using G = decltype(g);
         if (rows < 16 || rows > G::MH) return COVAHIP_ERR_UNSUPPORTED;
@@ -159,6 +165,6 @@ int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bi
         // opened to the maximum: `rows` differs between launches
         if (int rc = covahip_open_lds(ctx, k_mog_band_post<G::MW, G::MH, POST_BLOCK>, lds, COVAHIP_MOG_BAND_LDS_MAX)) return rc;
         return mog_launch(ctx, "mog_band_post", k_mog_band_post<G::MW, G::MH, POST_BLOCK>, dim3((unsigned)FS), POST_BLOCK, lds, bits,
-                          filled_bits, plane, labels, nvalid, S, rows);
+                          filled_bits, plane, labels, nvalid, S, rows, la.mode, la.ncover);
     });
 }

@@ -43,7 +43,8 @@ constexpr int UPD_BLOCK = 256;
 constexpr float TB = 0.9f, TG = 9.0f, VAR_INIT = 15.0f, VAR_MIN = 4.0f, VAR_MAX = 75.0f, FCT = 0.05f;
 
 // A working geometry: W x H pixels, a row is W / 64 ballot words of the bit plane, one label per 8x8 block (the block's
-// top-left pixel; the last label row of a height that is no multiple of 8 reads the last started block).
+// top-left pixel, or its coverage: label_bit and cover_labels below; the last label row of a height that is no multiple of 8
+// reads the last started block).
 template <int W, int H>
 struct Geom {
     static constexpr int MW = W, MH = H;
@@ -421,6 +422,45 @@ __device__ __forceinline__ uint8_t label_bit(const unsigned long long *T, unsign
     return (uint8_t)((~T[8 * r * roww + c / 8] >> (8 * (c % 8))) & 1ull);
 }
 
+// The labels by block coverage (COVAHIP_MOG_LABELS_COVER and _COUNT; include/covahip.h, "MoG labels", step 6) of one frame
+// mw x mh whose reached background is T (rows of roww words, LDS or global memory), by all BLOCK threads of the workgroup; lab
+// is the frame's [lh][lw].  One thread per (label row, plane word): the word's eight bytes are the rows of eight blocks, so
+// the block's up-to-8 rows are each reduced to per-byte popcounts (the 64-bit SWAR steps) and added -- a byte reaches at most
+// 8 x 8 = 64, so nothing carries -- and the eight bytes of the sum are the counts of the word's eight labels.  Consecutive
+// threads read consecutive 64-bit words of a row.  `live` masks the bits at x >= mw of a row's last word (T has them clear, so ~T
+// has them set): they are neither counted nor inside, nor are the rows at y >= mh, which are not read.
+template <int BLOCK>
+__device__ __forceinline__ void cover_labels(const unsigned long long *T, uint8_t *lab, unsigned mw, unsigned mh, unsigned roww,
+                                             int mode, unsigned ncover) {
+    constexpr unsigned long long M1 = 0x5555555555555555ull, M2 = 0x3333333333333333ull, M4 = 0x0f0f0f0f0f0f0f0full;
+    const unsigned lw = (mw + 7) / 8, lh = (mh + 7) / 8;
+    const unsigned long long tail = (mw & 63) ? (1ull << (mw & 63)) - 1 : ~0ull;
+    for (unsigned i = threadIdx.x; i < lh * roww; i += BLOCK) {
+        const unsigned r = i / roww, wc = i % roww;
+        const unsigned long long live = wc == roww - 1 ? tail : ~0ull;
+        const unsigned rows_in = mh - 8 * r < 8 ? mh - 8 * r : 8;
+        unsigned long long sum = 0;
+#pragma unroll
+        for (unsigned k = 0; k < 8; k++) {
+            if (k < rows_in) {
+                unsigned long long v = ~T[(8 * r + k) * roww + wc] & live;
+                v = v - ((v >> 1) & M1);
+                v = (v & M2) + ((v >> 2) & M2);
+                sum += (v + (v >> 4)) & M4;
+            }
+        }
+#pragma unroll
+        for (unsigned j = 0; j < 8; j++) {
+            const unsigned c = 8 * wc + j;
+            if (c < lw) {
+                const unsigned count = (unsigned)(sum >> (8 * j)) & 255u;
+                const unsigned inside = rows_in * (mw - 8 * c < 8 ? mw - 8 * c : 8);
+                lab[r * lw + c] = mode == COVAHIP_MOG_LABELS_COUNT ? (uint8_t)count : (uint8_t)(64u * count >= ncover * inside);
+            }
+        }
+    }
+}
+
 // A (LDS, G::NWORD words, the raw mask; all threads have passed a barrier after writing it) becomes the mask after close 4x4
 // and open 6x6; T (LDS, the same size) becomes the background reached from the frame edge through 4-connected background,
 // so ~T is the filled mask.  Ends behind a barrier.  `changed` is one LDS int.
@@ -697,6 +737,11 @@ struct MogUpdateArgs {
     float Tb;
     unsigned long long *bits;
 };
+// How a post launch takes its labels (include/covahip.h, "MoG labels", step 6): mode COVAHIP_MOG_LABELS_*, and with _COVER
+// ncover in 1 .. 64.  Arguments of the post kernels, the same for the whole launch.
+struct MogLabelArgs {
+    int mode = COVAHIP_MOG_LABELS_CORNER, ncover = 1;
+};
 // One kernel launch on ctx->stream under a profile scope
 template <class K, class... Args>
 int mog_launch(covahip_ctx *ctx, const char *scope, K kernel, dim3 grid, int block, size_t lds, Args... args) {
@@ -719,7 +764,7 @@ int mog_launch_update(covahip_ctx *ctx, const char *scope, K kernel, const uint8
 // layouts those of the kernels above; the launches go to ctx->stream and return without waiting.
 int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
-                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS);
+                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS, MogLabelArgs la);
 // The banded kernels (mog_band.hip) at working width `mw`: 1280 and 1920, whose planes do not fit LDS, and 960 (the post
 // kernel only, for comparison with the resident one).  plane: one more plane per (frame, stream), FS * NWORD words, for the
 // mask after the morphology; rows: the band height, 16 .. working height, with mogdev::band_lds_bytes within
@@ -727,7 +772,8 @@ int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bi
 constexpr size_t COVAHIP_MOG_BAND_LDS_MAX = 160 * 1024 - 64;
 int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
 int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
-                          unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);
+                          unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
+                          MogLabelArgs la);
 // The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries, on a covahip_mog_yuv_src (above).
 // load: MOG_LOAD_* of the labeller's row (copy and centre pick exist at working width 640 only)
 int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int load, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
@@ -740,4 +786,5 @@ int covahip_mog_any_update(covahip_ctx *ctx, int mw, int mh, const uint8_t *fram
 int covahip_mog_any_yuv_update(covahip_ctx *ctx, int format, int mw, int mh, const uint8_t *frames, const covahip_mog_yuv_src &src,
                                const MogUpdateArgs &a);
 int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,
-                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows);
+                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
+                         MogLabelArgs la);

@@ -34,11 +34,11 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__
     update_body<Geom<MW, MH>>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
 }
 
-// bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout; labels [F][S][LH][LW]
+// bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout; labels [F][S][LH][LW]; mode, ncover: MogLabelArgs
 template <int MW, int MH, int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_mog_grid_post(const unsigned long long *__restrict__ bits,
                                                          unsigned long long *__restrict__ filled_bits, uint8_t *__restrict__ labels,
-                                                         const int32_t *__restrict__ nvalid, int S) {
+                                                         const int32_t *__restrict__ nvalid, int S, int mode, int ncover) {
     using G = Geom<MW, MH>;
     constexpr int NWORD = G::NWORD, NLAB = G::NLAB, LW = G::LW, ROWW = G::ROWW;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
@@ -55,7 +55,11 @@ __global__ __launch_bounds__(BLOCK) void k_mog_grid_post(const unsigned long lon
     unsigned long long *dst = filled_bits + (size_t)fs * NWORD;
     uint8_t *lab = labels + (size_t)fs * NLAB;
     for (int i = tid; i < NWORD; i += BLOCK) dst[i] = ~T[i];
-    for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(T, i / LW, i % LW, ROWW);
+    if (mode == COVAHIP_MOG_LABELS_CORNER) {
+        for (int i = tid; i < NLAB; i += BLOCK) lab[i] = label_bit(T, i / LW, i % LW, ROWW);
+    } else {
+        cover_labels<BLOCK>(T, lab, MW, MH, ROWW, mode, ncover);
+    }
 }
 
 }  // namespace
@@ -68,7 +72,7 @@ int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, siz
 }
 
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
-                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS) {
+                          uint8_t *labels, const int32_t *nvalid, int S, size_t FS, MogLabelArgs la) {
     return with_geom<G960, G320>(mw, [&](auto g) -> int {
         using G = decltype(g);
         constexpr int BLOCK = G::MW == 960 ? 512 : 256;    // (the results do not depend on it) at 960x540 one workgroup owns the CU
@@ -76,7 +80,7 @@ int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bi
         static_assert(lds <= 160 * 1024 - 64, "the two planes must fit a CU's LDS");
         if (int rc = covahip_open_lds(ctx, k_mog_grid_post<G::MW, G::MH, BLOCK>, lds, lds)) return rc;   // (a constant of the kernel)
         return mog_launch(ctx, "mog_post", k_mog_grid_post<G::MW, G::MH, BLOCK>, dim3((unsigned)FS), BLOCK, lds, bits, filled_bits, labels,
-                          nvalid, S);
+                          nvalid, S, la.mode, la.ncover);
     });
 }
 

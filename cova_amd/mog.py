@@ -5,6 +5,8 @@
                at half the source instead and labels the source's own macroblocks: 68x120 for 1920x1080, and it alone
                takes 2560x1440 (90x160 labels) and 3840x2160 (135x240).  any_size=True (macroblock grid) takes every even
                source size from 256 to 4096 in both axes: 1280x960 gives 60x80 labels, 704x576 36x44
+               labels="corner" (the default: the block's top-left pixel, the reference's ::8 subsample), ("cover", N) (1 where
+               at least N / 64 of the block is foreground: small objects keep their labels) or "count" (0 .. 64, for inspection)
   label_dims   (label_h, label_w) of a source size on either grid, without a GPU; label_dims_any / work_dims_any: of any_size
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
   apply_yuv    the same labels from 8-bit 4:2:0 frames as decoders give them, NV12 or I420, at a row pitch, plane offsets and
@@ -19,6 +21,8 @@
     python -m cova_amd.mog --any-size 1280x960 IN.bgr ...                     (60x80 labels; any even size, 256 .. 4096)
     ffmpeg -i VIDEO -f yuv4mpegpipe -pix_fmt yuv420p - | python -m cova_amd.mog --format y4m -:VIDEO_gt.dump
     python -m cova_amd.mog --format nv12 --size 1920x1080 [--range full] IN.nv12 ...     (also --format i420)
+    python -m cova_amd.mog --size 1280x720 --labels cover:32 IN.bgr ...       (a label where half the block is foreground)
+    python -m cova_amd.mog --size 1280x720 --labels count IN.bgr:IN_count.dump           (then tools/label_cover.py picks N)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
 to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Bitstream decoding is not done here:
@@ -46,6 +50,26 @@ GRID_SIZES = {"reference": SIZES, "macroblock": SIZES + ((2560, 1440), (3840, 21
 FORMATS = {"nv12": 1, "i420": 2}                # COVAHIP_MOG_FMT_*
 RANGES = {"limited": 0, "full": 1}              # COVAHIP_MOG_RANGE_*
 ANY_MIN, ANY_MAX = 256, 4096                    # COVAHIP_MOG_ANY_*: what any_size admits, per axis and even
+LABEL_MODES = {"corner": 0, "cover": 1, "count": 2}     # COVAHIP_MOG_LABELS_*
+
+
+def label_mode(labels):
+    """(mode name, N) of a `labels` value: "corner", "count", ("cover", N) with N in 1 .. 64, or "cover" for ("cover", 1).  N is 1
+    where the mode does not read it.  Anything else raises ValueError."""
+    if isinstance(labels, str):
+        name, n = labels, 1
+    else:
+        try:
+            name, n = labels
+        except (TypeError, ValueError):
+            raise ValueError(f"labels {labels!r}: 'corner', 'count' or ('cover', N)") from None
+        if name != "cover":
+            raise ValueError(f"labels {labels!r}: only 'cover' takes a number")
+    if name not in LABEL_MODES:
+        raise ValueError(f"unknown label mode {name!r}: one of " + ", ".join(LABEL_MODES))
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 1 <= n <= 64:
+        raise ValueError(f"labels {labels!r}: N must be an integer in 1 .. 64")
+    return name, int(n)
 
 
 def work_dims(w: int, h: int, grid: str = "reference"):
@@ -115,10 +139,14 @@ class MogLabeler:
     source; 2560x1440 and 3840x2160 sources are this grid's alone); work_w, work_h, label_h and label_w say which shapes the
     labeller takes and gives.  any_size=True (macroblock grid only) admits every size of work_dims_any: a size of
     GRID_SIZES["macroblock"] runs that grid's own kernels, any other the general ones (covahip_mog_create_any), which
-    force_general=True (tests, measurements) takes at every size; the results do not depend on which."""
+    force_general=True (tests, measurements) takes at every size; the results do not depend on which.  `labels` is the label
+    mode (label_mode; set_labels changes it later): "corner", the default, is the block's top-left pixel; ("cover", N) is 1 where
+    64 * count >= N * inside for the block's foreground count and its pixels inside the image; "count" is that count, 0 .. 64,
+    which is for inspection and no trainer input."""
 
     def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0,
-                 grid: str = "reference", any_size: bool = False, force_general: bool = False):
+                 grid: str = "reference", any_size: bool = False, force_general: bool = False, labels="corner"):
+        label_mode(labels)                                                   # ValueError before the ctx is touched
         if grid not in GRIDS:
             raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
         any_size = any_size or force_general
@@ -145,6 +173,22 @@ class MogLabeler:
         d = [C.c_int32() for _ in range(4)]
         L.check(self._lib.covahip_mog_dims(h, *(C.byref(v) for v in d)), "covahip_mog_dims")
         self.work_w, self.work_h, self.label_w, self.label_h = (int(v.value) for v in d)
+        if label_mode(labels)[0] != "corner":
+            self.set_labels(labels)
+
+    def set_labels(self, labels):
+        """The label mode of every later call (apply, apply_yuv, post_masks), for all streams: "corner", "count" or ("cover", N),
+        N in 1 .. 64 ("cover" alone is N = 1).  The model and the masks do not depend on it, and reset keeps it."""
+        name, n = label_mode(labels)
+        L.check(self._lib.covahip_mog_set_labels(self.handle, LABEL_MODES[name], n), "covahip_mog_set_labels")
+
+    @property
+    def labels(self):
+        """The label mode in force: "corner", "count" or ("cover", N)."""
+        mode, n = C.c_int(), C.c_int()
+        L.check(self._lib.covahip_mog_get_labels(self.handle, C.byref(mode), C.byref(n)), "covahip_mog_get_labels")
+        name = {v: k for k, v in LABEL_MODES.items()}[mode.value]
+        return (name, int(n.value)) if name == "cover" else name
 
     def close(self):
         if getattr(self, "handle", None):
@@ -459,6 +503,20 @@ def parse_any_size(text: str):
     return w, h
 
 
+def parse_labels(text: str):
+    """corner | cover[:N] | count -> a `labels` value of MogLabeler; cover alone is N = 1."""
+    name, sep, num = text.partition(":")
+    if name not in LABEL_MODES or (sep and name != "cover"):
+        raise argparse.ArgumentTypeError(f"labels {text!r}: corner, cover[:N] or count")
+    if name != "cover":
+        return name
+    if not sep:
+        return "cover", 1
+    if not (num.isascii() and num.isdigit()) or not 1 <= int(num) <= 64:
+        raise argparse.ArgumentTypeError(f"labels {text!r}: N must be an integer in 1 .. 64")
+    return "cover", int(num)
+
+
 def parse_io(arg: str):
     """IN[:OUT] -> (IN, OUT); OUT defaults to IN's name with `_gt.dump`."""
     src, sep, out = arg.rpartition(":")
@@ -493,6 +551,11 @@ def _args(argv):
                     help="reference: 45x80 labels whatever the source (the 1280x720 macroblock grid); macroblock: one label per "
                          "macroblock of the source, which 1080p records need (1920x1080 -> 68x120, 2560x1440 -> 90x160, "
                          "3840x2160 -> 135x240)")
+    ap.add_argument("--labels", type=parse_labels, default="corner", metavar="corner|cover[:N]|count",
+                    help="how a block becomes a label.  corner (the default): its top-left pixel, the reference's ::8 subsample; "
+                         "cover[:N], N in 1 .. 64 (default 1): 1 where at least N / 64 of the block's pixels inside the image are "
+                         "foreground, so an object narrower than a block keeps its label; count: that number of pixels, a byte "
+                         "0 .. 64 -- for inspection and for choosing N (tools/label_cover.py), not a trainer input")
     ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
     ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
     ap.add_argument("--history", type=int, default=9000)
@@ -591,7 +654,8 @@ def main(argv=None) -> int:
     pending = list(a.inputs)
     yuv = a.format != "bgr24"
     ctx = Context(a.device)
-    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid, any_size=a.any_size is not None)
+    mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid, any_size=a.any_size is not None,
+                     labels=a.labels)
     layout = yuv_tight(w, h, "nv12" if a.format == "nv12" else "i420", a.range, streams=S) if yuv else None
     frames = np.empty((a.chunk, S, w * h * 3 // 2) if yuv else (a.chunk, S, h, w, 3), np.uint8)
     labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)

@@ -793,15 +793,27 @@ int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const 
  *   5. contour fill (findContours RETR_EXTERNAL + drawContours FILLED) as hole filling: foreground 8-connected, background
  *      4-connected, every background 4-component that does not touch the image edge becomes 1;
  *   6. label[i][j] = filled[8i][8j]: 45x80 bytes of 0 / 1 per frame, the file `tfrecordsink gt=` reads (frames one after the
- *      other, as ndarray.tofile writes them).
+ *      other, as ndarray.tofile writes them).  That is the label mode COVAHIP_MOG_LABELS_CORNER, the default and the
+ *      reference's cl_op_fill[::8, ::8]; covahip_mog_set_labels (below) chooses another per labeller.  With F the filled mask
+ *      of step 5, mw x mh working pixels, block (i, j) is the pixels y in [8i, min(8i + 8, mh)), x in [8j, min(8j + 8, mw));
+ *      `inside` is their number (64, except in a last label row or column that is only started) and `count` how many of them
+ *      are 1 in F.  Nothing at x >= mw or y >= mh is counted or inside.
+ *        COVAHIP_MOG_LABELS_CORNER  label = F[8i][8j];
+ *        COVAHIP_MOG_LABELS_COVER   with min_cover N in 1 .. 64: label = 1 iff 64 * count >= N * inside, else 0.  N = 1: any
+ *                                   foreground pixel in the block; N = 32: at least half of what the image holds of the block;
+ *                                   N = 64: all of it.  COVER(1) holds every CORNER label, and COVER(N) shrinks as N grows;
+ *        COVAHIP_MOG_LABELS_COUNT   label = count, a byte 0 .. 64, > 0 exactly where COVER(1) is 1.  For inspection and for
+ *                                   choosing N (tools/label_cover.py): it is not a trainer input.
+ *      The opening guarantees an object only a 6x6 square and a corner sits every 8 pixels, so CORNER gives an object narrower
+ *      than 8 working pixels a label only where it straddles a corner ("MoG labels by coverage").
  * That is the reference grid (COVAHIP_MOG_GRID_REFERENCE): 45x80 is the macroblock grid of a 1280x720 stream, whatever the
  * source.  The macroblock grid (COVAHIP_MOG_GRID_MACROBLOCK) labels the source's own 16x16 macroblocks; it differs in two steps:
  *   1. the working image is half the source in both axes, by the exact-2x rule above ((a + b + c + d + 2) >> 2 per channel over
  *      the 2x2 block): 1920x1080 -> 960x540, 1280x720 -> 640x360 (the reference grid itself: the same labels, masks and model,
  *      byte for byte), 640x360 -> 320x180, and two sizes that only this grid takes (the reference grid answers
  *      COVAHIP_ERR_UNSUPPORTED): 2560x1440 -> 1280x720 and 3840x2160 -> 1920x1080; any other size is COVAHIP_ERR_UNSUPPORTED;
- *   6. label[i][j] = filled[8i][8j] for every i, j with 8i < working height and 8j < working width, the pixel at the top-left
- *      corner of macroblock (i, j): 68x120 (the last row reads working row 536), 45x80, 23x40 (row 176), 90x160 and 135x240
+ *   6. one label for every i, j with 8i < working height and 8j < working width, in the default mode filled[8i][8j], the pixel
+ *      at the top-left corner of macroblock (i, j): 68x120 (the last row reads working row 536), 45x80, 23x40 (row 176), 90x160 and 135x240
  *      (a 4K grid; row 1072) bytes per frame.
  * Steps 2 - 5 are the same: the 4x4 / 6x6 kernels stay in working pixels, the same size relative to a macroblock.
  * MOG2 (the CPU path of OpenCV 4.x MOG2Invoker, nmixtures 5).  All values f32 unless noted, every product and sum rounded on
@@ -863,6 +875,16 @@ int  covahip_mog_create_grid(covahip_ctx *ctx, const covahip_mog_cfg *cfg, int g
  * working image at a row pitch of work_w rounded up to 64. */
 enum { COVAHIP_MOG_ANY_MIN = 256, COVAHIP_MOG_ANY_MAX = 4096 };
 int  covahip_mog_create_any(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahip_mog **out);
+/* The label mode of step 6 and, for COVAHIP_MOG_LABELS_COVER, its min_cover N in 1 .. 64 (min_cover is read in that mode only).
+ * A new labeller is in COVAHIP_MOG_LABELS_CORNER.  The setting holds for every later covahip_mog_apply and covahip_mog_apply_yuv
+ * of the labeller, for all its streams, and covahip_mog_reset keeps it.  The model and the masks do not depend on it: a
+ * labeller that switches modes between calls has, bit for bit, the state of one that never did.  COVAHIP_MOG_LABELS_COUNT
+ * writes bytes 0 .. 64 and is not a trainer input.  COVAHIP_ERR_INVALID_ARG, with nothing changed: a NULL labeller, an unknown
+ * mode, N outside 1 .. 64 in COVER mode.  covahip_mog_get_labels gives the setting back (min_cover: the last one set, 1 at
+ * first); either pointer may be NULL. */
+enum { COVAHIP_MOG_LABELS_CORNER = 0, COVAHIP_MOG_LABELS_COVER = 1, COVAHIP_MOG_LABELS_COUNT = 2 };
+int  covahip_mog_set_labels(covahip_mog *m, int mode, int min_cover);
+int  covahip_mog_get_labels(const covahip_mog *m, int *mode, int *min_cover);
 /* The labeller's working size and label grid; any pointer may be NULL. */
 int  covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h);
 /* frames u8 [n_frames][n_streams][src_h][src_w][3]; labels u8 [n_frames][n_streams][45][80] (mem_kind applies to both; n_valid is

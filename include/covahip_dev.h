@@ -92,8 +92,8 @@ int covahip_dev_mog_set_stage_budget(struct covahip_mog *m, size_t bytes);
 /* The labeller's post launch (close, open, hole fill, labels) on given masks instead of MOG2's: raw u8
  * [n_frames][n_streams][work_h][work_w], non-zero = foreground, is packed into bit planes on the host and uploaded as the call's
  * raw planes; labels u8 [n_frames][n_streams][label_h][label_w] (host memory) come back, and covahip_dev_mog_masks then reads the
- * raw / filled masks of this call.  The model and the frame counts are untouched.  Works for every labeller.
- * (tests/test_gpu_mog_band.py) */
+ * raw / filled masks of this call.  The model and the frame counts are untouched.  Works for every labeller, in the label mode
+ * of covahip_mog_set_labels.  (tests/test_gpu_mog_band.py, tests/test_gpu_mog_cover.py) */
 int covahip_dev_mog_post_masks(struct covahip_mog *m, const uint8_t *raw, int n_frames, uint8_t *labels);
 /* Which post kernel a macroblock-grid labeller runs.  banded = 1: the banded kernel of mog_band.hip, which labellers of
  * 2560x1440 and 3840x2160 sources always run and a 1920x1080 one (960x540 working) runs only through this switch, to be compared

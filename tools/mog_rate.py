@@ -7,6 +7,8 @@
     python tools/mog_rate.py --format nv12 --sizes 1280x720      (covahip_mog_apply_yuv on tight NV12 frames; also i420)
     python tools/mog_rate.py --general --sizes 1920x1080,1280x960 --frames 64 --min-frames 2 --reps 5
                                  (covahip_mog_create_any's kernels: any even size, beside the table's kernels where a size has both)
+    python tools/mog_rate.py --grid macroblock --sizes 2560x1440 --labels corner,cover:1,count --no-host
+                                 (the label modes side by side: one labeller each, timed call by call in turn)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -17,7 +19,8 @@ oracle's (tests/mog_ref.py) frames/s on this machine's CPU.  --format nv12 | i42
 numpy forward transform (BT.601, limited range), from tight 4:2:0 frames of 1.5 bytes per pixel; every line says its format.
 --general (macroblock grid) times the general kernels ("device_general": MogLabeler(force_general=True)) at any admitted size;
 at a size the table has too, the table's labeller ("device") is timed in the same process on the same frames, call by call in
-turn, so the two lines compare.
+turn, so the two lines compare.  --labels lists label modes (corner, cover[:N], count): every device case is timed once per mode
+("device[cover:1]"), in the same turn-by-turn loop.
 """
 import argparse
 import json
@@ -79,7 +82,12 @@ def main():
     ap.add_argument("--oracle-frames", type=int, default=3)
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--general", action="store_true", help="the general kernels (any even size of 256 .. 4096; implies --grid macroblock)")
+    ap.add_argument("--labels", default="corner", help="label modes to time, comma-separated: corner, cover[:N], count")
     a = ap.parse_args()
+    try:
+        label_modes = [(t, mog.parse_labels(t)) for t in a.labels.split(",")]
+    except argparse.ArgumentTypeError as e:
+        ap.error(str(e))
     if a.general:
         a.grid = "macroblock"
     parse_size = mog.parse_any_size if a.general else mog.parse_size
@@ -102,10 +110,12 @@ def main():
             labels = np.zeros((F, S) + (mog.label_dims_any(w, h) if a.general else mog.label_dims(w, h, a.grid)), np.uint8)
             # the labellers timed on the device, call by call in turn; the host case is the last one's
             cases = {}
-            if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
-                cases["device"] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid)
-            if a.general:
-                cases["device_general"] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True)
+            for text, mode in label_modes:
+                tag = "" if text == "corner" else f"[{text}]"
+                if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
+                    cases["device" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, labels=mode)
+                if a.general:
+                    cases["device_general" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True, labels=mode)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
 
