@@ -286,6 +286,9 @@ PROTOTYPES = {
     "covahip_mog_create_any": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_set_labels": (C.c_int, [_P, C.c_int, C.c_int]),
     "covahip_mog_get_labels": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "covahip_mog_set_shadows": (C.c_int, [_P, C.c_int, C.c_float]),
+    "covahip_mog_get_shadows": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_float)]),
+    "covahip_mog_shadow_counts": (C.c_int, [_P, _P, _P, C.c_size_t, C.POINTER(C.c_int)]),
     "covahip_mog_dims": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "covahip_mog_apply": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_mog_yuv_tight": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MogYuv)]),

@@ -6,6 +6,8 @@
 // post kernel in row bands); all three instantiate the device code of mog_dev.h.  covahip_mog_apply_yuv (NV12 / I420 surfaces at
 // the caller's pitch, offsets and strides) is checked and staged here and runs the update kernels of mog_yuv.hip.
 // covahip_mog_create_any (the macroblock grid at any even source size) makes a labeller that runs the kernels of mog_any.hip.
+// The update kernels themselves are templates of mog_update.h; with shadow detection on (covahip_mog_set_shadows) a call's update
+// launches go to their SHADOW instances in mog_shadow.hip, which also has the kernel behind covahip_mog_shadow_counts.
 //
 //   k_mog_update  one lane per working-size pixel and stream.  The five modes (weight, variance, mean) are read once per call
 //                 into registers, every frame of the call is applied to them, and they are written back once.  The source is
@@ -32,6 +34,7 @@
 #include "covahip_dev.h"
 #include "internal.h"
 #include "mog_dev.h"
+#include "mog_update.h"
 
 namespace {
 
@@ -43,26 +46,6 @@ constexpr int POST_BLOCK = 256;
 static_assert(LW == COVAHIP_MOG_LABEL_W && LH == COVAHIP_MOG_LABEL_H && NLAB == NWORD, "geometry");
 // device budget for host frames staged per update launch (covahip_dev_mog_set_stage_budget changes it per labeller)
 constexpr size_t STAGE_BUDGET = (size_t)1 << 30;
-
-// source pixel(s) of working pixel (x, y) of one frame, resized as cv.resize INTER_LINEAR does for the three sizes: the copy
-// (640x360 sources), the 2x2 mean (1280x720) and the centre pick (1920x1080)
-template <int SRC>
-struct LoadPx {
-    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
-        if constexpr (SRC == MOG_LOAD_HALF) return LoadHalf<MW>()(fr, x, y);
-        const uint8_t *q = SRC == MOG_LOAD_COPY ? fr + ((size_t)y * 640 + x) * 3 : fr + ((size_t)(3 * y + 1) * 1920 + 3 * x + 1) * 3;
-        return {(float)q[0], (float)q[1], (float)q[2]};
-    }
-};
-
-// SRC: MOG_LOAD_*.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of the call; bits: raw masks
-// [F][S][3600]
-template <int SRC>
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
-                                                          const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
-                                                          int nf, int S, float Tb, unsigned long long *__restrict__ bits) {
-    update_body<G>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-}
 
 // bits: raw masks [F][S][3600]; filled_bits: the filled masks, same layout; labels [F][S][45][80]; mode, ncover: MogLabelArgs
 __global__ __launch_bounds__(POST_BLOCK) void k_mog_post(const unsigned long long *__restrict__ bits,
@@ -118,6 +101,13 @@ struct covahip_mog {
     bool banded = false;           // the post kernel of mog_band.hip, where the row has it
     int band_rows = 0;             // its band height; 0 = the automatic plan
     MogLabelArgs labels;           // covahip_mog_set_labels: how every post launch takes its labels
+    int shadows = COVAHIP_MOG_SHADOWS_OFF;     // covahip_mog_set_shadows: every later apply call runs in this mode, with this tau
+    float tau = 0.5f;
+    int last_shadows = COVAHIP_MOG_SHADOWS_OFF;    // the mode the call behind m->bits ran in: whether m->shadow belongs to it
+    std::vector<int32_t> last_nv;  // and its n_valid
+    void *shadow = nullptr;        // the call's shadow planes, as bits; allocated by the first call that leaves OFF
+    void *d_counts = nullptr;      // covahip_mog_shadow_counts: (shadow, foreground) u32 [F][S][2]
+    size_t shadow_bytes = 0, counts_bytes = 0;
     size_t src_bytes = 0;
     std::vector<int64_t> n;        // frames each stream has seen
     uint8_t *state = nullptr;      // [S][state_bytes]
@@ -133,7 +123,7 @@ struct covahip_mog {
 namespace {
 
 void free_mog(covahip_mog *m) {
-    for (void *p : {(void *)m->state, m->bits, m->filled, m->plane, m->d_frames, m->d_labels, m->d_par})
+    for (void *p : {(void *)m->state, m->bits, m->filled, m->plane, m->d_frames, m->d_labels, m->d_par, m->shadow, m->d_counts})
         if (p) hipFree(p);
     if (m->h_par) hipHostFree(m->h_par);
     delete m;
@@ -151,6 +141,9 @@ struct YuvPlan {
 int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
     covahip_ctx *ctx = m->ctx;
     const int load = m->row->load;
+    if (a.shadows != COVAHIP_MOG_SHADOWS_OFF)  // the kernels' SHADOW instances, all of them in mog_shadow.hip
+        return covahip_mog_shadow_update(ctx, MogShadowRoute{m->any, yuv ? yuv->format : 0, load, m->row->work.mw, m->row->work.mh, m->row->resident},
+                                         d_frames, m->src_bytes, src, a);
     if (m->any) {
         const MogDims &w = m->row->work;
         return yuv ? covahip_mog_any_yuv_update(ctx, yuv->format, w.mw, w.mh, d_frames, src, a)
@@ -159,8 +152,8 @@ int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, c
     if (yuv) return covahip_mog_yuv_update(ctx, yuv->format, load, m->row->work.mw, d_frames, src, a);
     if (m->row->work.mw != MW)             // the macroblock grid's other working sizes: the kernels beside the row's post kernels
         return (m->row->resident ? covahip_mog_grid_update : covahip_mog_band_update)(ctx, m->row->work.mw, d_frames, m->src_bytes, a);
-    const auto kernel = load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY>
-                                              : (load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF> : k_mog_update<MOG_LOAD_PICK>);
+    const auto kernel = load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY, false>
+                                              : (load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF, false> : k_mog_update<MOG_LOAD_PICK, false>);
     return mog_launch_update<G>(ctx, "mog_update", kernel, d_frames, m->src_bytes, a);
 }
 
@@ -304,6 +297,12 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     const float2 *d_par = static_cast<const float2 *>(m->d_par);
     const int32_t *d_nv = reinterpret_cast<const int32_t *>(d_par + FS);
     MogUpdateArgs a{m->state, d_par, d_nv, 0, n_frames, S, m->cfg.var_threshold, static_cast<unsigned long long *>(m->bits)};
+    if (m->shadows != COVAHIP_MOG_SHADOWS_OFF) {
+        if (int rc = covahip_ensure_buffer(ctx, &m->shadow, &m->shadow_bytes, FS * NWORD * 8)) return rc;
+        a.shadows = m->shadows;
+        a.tau = m->tau;
+        a.shadow = static_cast<unsigned long long *>(m->shadow);
+    }
     covahip_mog_yuv_src src = yuv ? yuv->src : covahip_mog_yuv_src{};
     uint8_t *d_labels = labels;
     if (mem_kind == COVAHIP_MEM_DEVICE) {
@@ -348,6 +347,8 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int s = 0; s < S; s++) m->n[s] += nv[s];
     m->last_frames = n_frames;
+    m->last_shadows = a.shadows;
+    m->last_nv = nv;
     return COVAHIP_OK;
 }
 
@@ -450,6 +451,52 @@ int covahip_mog_get_labels(const covahip_mog *m, int *mode, int *min_cover) {
     return COVAHIP_OK;
 }
 
+int covahip_mog_set_shadows(covahip_mog *m, int mode, float tau) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    if (mode != COVAHIP_MOG_SHADOWS_OFF && mode != COVAHIP_MOG_SHADOWS_DROP && mode != COVAHIP_MOG_SHADOWS_KEEP)
+        return COVAHIP_ERR_INVALID_ARG;
+    if (mode != COVAHIP_MOG_SHADOWS_OFF) {
+        if (!std::isfinite(tau) || !(tau > 0.f) || tau > 1.f) return COVAHIP_ERR_INVALID_ARG;
+        m->tau = tau;                          // (read when the test runs: OFF keeps the last one)
+    }
+    m->shadows = mode;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_get_shadows(const covahip_mog *m, int *mode, float *tau) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    if (mode) *mode = m->shadows;
+    if (tau) *tau = m->tau;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_shadow_counts(covahip_mog *m, uint32_t *shadow, uint32_t *foreground, size_t cap, int *n_frames) {
+    if (!m) return COVAHIP_ERR_INVALID_ARG;
+    if (n_frames) *n_frames = m->last_frames;
+    const int S = m->cfg.n_streams;
+    const size_t FS = (size_t)m->last_frames * S;
+    if ((shadow || foreground) && cap < FS) return COVAHIP_ERR_OVERFLOW;
+    if (!(shadow || foreground) || !FS) return COVAHIP_OK;
+    covahip_ctx *ctx = m->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    if (int rc = covahip_ensure_buffer(ctx, &m->d_counts, &m->counts_bytes, FS * 2 * sizeof(uint32_t))) return rc;
+    const bool on = m->last_shadows != COVAHIP_MOG_SHADOWS_OFF;
+    if (int rc = covahip_mog_counts(ctx, static_cast<const unsigned long long *>(m->bits),
+                                    on ? static_cast<const unsigned long long *>(m->shadow) : nullptr, m->alloc.nword(), FS,
+                                    static_cast<uint32_t *>(m->d_counts)))
+        return rc;
+    std::vector<uint32_t> c(FS * 2);
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(c.data(), m->d_counts, FS * 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < FS; i++) {
+        const bool valid = (int)(i / S) < m->last_nv[i % S];   // (the planes of frames past n_valid were never written)
+        if (shadow) shadow[i] = valid ? c[2 * i] : 0;
+        if (foreground) foreground[i] = valid ? c[2 * i + 1] : 0;
+    }
+    return COVAHIP_OK;
+}
+
 int covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h) {
     if (!m) return COVAHIP_ERR_INVALID_ARG;
     if (work_w) *work_w = m->row->work.mw;
@@ -476,7 +523,11 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    std::vector<unsigned long long> w(FS * NWORD);
+    std::vector<unsigned long long> w(FS * NWORD), sh;
+    if (raw && FS && m->last_shadows != COVAHIP_MOG_SHADOWS_OFF) {     // the call's shadow planes: 127 wherever a bit is set
+        sh.resize(FS * NWORD);
+        COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(sh.data(), m->shadow, FS * NWORD * 8, hipMemcpyDeviceToHost, ctx->stream));
+    }
     for (int which = 0; which < 2; which++) {
         uint8_t *out = which ? filled : raw;
         if (!out || !FS) continue;
@@ -485,6 +536,10 @@ int covahip_dev_mog_masks(covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t 
         const uint8_t one = which ? 1 : 255;
         for (size_t r = 0; r < NROW; r++)
             for (size_t x = 0; x < mw; x++) out[r * mw + x] = (w[r * roww + x / 64] >> (x % 64)) & 1ull ? one : 0;
+        if (!which && !sh.empty())
+            for (size_t r = 0; r < NROW; r++)
+                for (size_t x = 0; x < mw; x++)
+                    if ((sh[r * roww + x / 64] >> (x % 64)) & 1ull) out[r * mw + x] = 127;
     }
     return COVAHIP_OK;
 }
@@ -517,6 +572,8 @@ int covahip_dev_mog_post_masks(covahip_mog *m, const uint8_t *raw, int n_frames,
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(labels, m->d_labels, FS * NLAB, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     m->last_frames = n_frames;
+    m->last_shadows = COVAHIP_MOG_SHADOWS_OFF;     // these planes are the caller's: no shadow plane goes with them
+    m->last_nv = nv;
     return COVAHIP_OK;
 }
 

@@ -4,9 +4,10 @@
 // p = y * 64 roww + x of the update grid and entry p of the model's arrays (W[5][P], V[5][P], M[5][3][P] f32, nmodes[P] u8 with
 // P = 64 roww mh, as Geom lays them out at its NPIX).  The entries at x >= mw are never read or written.
 //
-//   k_mog_any_update  the update body of mog_dev.h with runtime sizes: a wave is 64 consecutive x of one padded row, so its
-//                     ballot is one plane word.  Lanes at x >= mw load nothing, keep no model and ballot 0; the last block
-//                     may be partial (P is a multiple of 64, not of 256).  BGR24 (the 2x2 mean of LoadHalf) and, with
+//   k_mog_any_update  the update body of mog_dev.h with runtime sizes (update_any, in mog_update.h with the kernel): a wave
+//                     is 64 consecutive x of one padded row, so its ballot is one plane word.  Lanes at x >= mw load nothing,
+//                     keep no model and ballot 0; the last block may be partial (P is a multiple of 64, not of 256).  BGR24
+//                     (the 2x2 mean of LoadHalf) and, with
 //                     LoadYuv<.., HALF> of mog_dev.h, NV12 / I420.  mog2_pixel is the one of mog_dev.h.
 //   k_mog_any_post    k_mog_band_post (mog_band.hip) with runtime sizes: planes in global memory, the morphology band by band
 //                     with the 10-row-up / 6-row-down halo, the hole fill swept over the bands to its fixed point, then the
@@ -27,6 +28,7 @@
 #include "covahip.h"
 #include "internal.h"
 #include "mog_dev.h"
+#include "mog_update.h"
 
 namespace {
 
@@ -34,94 +36,6 @@ using namespace mogdev;
 using u64 = unsigned long long;
 
 constexpr int POST_BLOCK = 512;                // one lane per word column and row segment of the column sweep at 32 words
-
-// working pixel (x, y) of a BGR24 frame src_w wide: LoadHalf with the width as a member
-struct LoadHalfAny {
-    int src_w;
-    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
-        const uint8_t *a = fr + ((size_t)(2 * y) * src_w + 2 * x) * 3;
-        const uint8_t *b = a + (size_t)src_w * 3;
-        unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
-        unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
-        unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
-        return {(float)s0, (float)s1, (float)s2};
-    }
-};
-
-// update_body_strided of mog_dev.h on the padded pitch: grid (ceil(P / UPD_BLOCK), S), bits [F][S][roww mh]
-template <class Load>
-__device__ __forceinline__ void update_any(Load load, const uint8_t *__restrict__ frames, long long frame_stride, long long stream_stride,
-                                           uint8_t *__restrict__ state, const float2 *__restrict__ par,
-                                           const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
-                                           u64 *__restrict__ bits, int mw, int mh) {
-    const int s = blockIdx.y;
-    int fend = nvalid[s] - f0;
-    fend = fend < nf ? fend : nf;
-    if (fend <= 0) return;                     // the same for the whole block
-    const int pitch = (mw + 63) / 64 * 64;
-    const size_t P = (size_t)pitch * mh;
-    const size_t p = (size_t)blockIdx.x * UPD_BLOCK + threadIdx.x;
-    if (p >= P) return;                        // whole waves: P is a multiple of 64
-    const int x = (int)(p % pitch), y = (int)(p / pitch);
-    const bool live = x < mw;                  // lane 0 of a wave always is
-    uint8_t *st = state + (size_t)s * (P * (5 * NMIX * 4 + 1));
-    float *gW = reinterpret_cast<float *>(st), *gV = gW + NMIX * P, *gM = gW + 2 * NMIX * P;
-    uint8_t *gN = st + (size_t)5 * NMIX * 4 * P;
-    float W[NMIX] = {}, V[NMIX] = {}, M[NMIX][3] = {};
-    int nm = 0;
-    const uint8_t *fr = frames + (long long)s * stream_stride;
-    typename Load::At at{};
-    typename Load::Raw cur{};
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < NMIX; k++) {
-            W[k] = gW[(size_t)k * P + p];
-            V[k] = gV[(size_t)k * P + p];
-#pragma unroll
-            for (int c = 0; c < 3; c++) M[k][c] = gM[(size_t)(k * 3 + c) * P + p];
-        }
-        nm = gN[p];
-        at = load.at(x, y);
-        cur = load(fr, at);
-    }
-    for (int f = 0; f < fend; f++) {
-        typename Load::Raw nxt = cur;
-        if (live && f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
-        const float2 pr = par[(size_t)(f0 + f) * S + s];
-        bool fg = false;
-        if (live) fg = mog2_pixel(W, V, M, nm, load.px(cur), pr.x, pr.y, Tb);
-        const u64 word = __ballot(fg);
-        if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * (P / 64) + p / 64] = word;
-        cur = nxt;
-    }
-    if (live) {
-#pragma unroll
-        for (int k = 0; k < NMIX; k++) {
-            gW[(size_t)k * P + p] = W[k];
-            gV[(size_t)k * P + p] = V[k];
-#pragma unroll
-            for (int c = 0; c < 3; c++) gM[(size_t)(k * 3 + c) * P + p] = M[k][c];
-        }
-        gN[p] = (uint8_t)nm;
-    }
-}
-
-// frames: this launch's first frame, [nf][S][2 mh][2 mw][3]
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
-                                                              const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
-                                                              int nf, int S, float Tb, u64 *__restrict__ bits, int mw, int mh) {
-    update_any(PlainLoad<LoadHalfAny>{LoadHalfAny{2 * mw}}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par,
-               nvalid, f0, nf, S, Tb, bits, mw, mh);
-}
-
-// frames: the launch's first frame of stream 0, surfaces as `src` describes them
-template <int FMT>
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
-                                                                  uint8_t *__restrict__ state, const float2 *__restrict__ par,
-                                                                  const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
-                                                                  u64 *__restrict__ bits, int mw, int mh) {
-    update_any(LoadYuv<FMT, YUV_HALF>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid, f0, nf, S, Tb, bits, mw, mh);
-}
 
 // ------------------------------------------------------------------------------------------------ post passes, runtime width
 // hpass_band / vpass_band of mog_dev.h on rows of `roww` words whose last word holds the image in the bits of `tail`
@@ -374,25 +288,18 @@ __global__ __launch_bounds__(POST_BLOCK) void k_mog_any_post(const u64 *__restri
     for (int i = tid; i < nword; i += POST_BLOCK) Tg[i] = ~Tg[i] & (i % roww == roww - 1 ? tail : ~0ull);
 }
 
-template <class K, class Src>
-int launch_update(covahip_ctx *ctx, const char *scope, K kernel, int mw, int mh, const uint8_t *frames, const Src &src,
-                  const MogUpdateArgs &a) {
-    const size_t P = (size_t)mog_any_pitch(mw) * mh;
-    return mog_launch(ctx, scope, kernel, dim3((unsigned)((P + UPD_BLOCK - 1) / UPD_BLOCK), a.S), UPD_BLOCK, 0, frames, src, a.state, a.par,
-                      a.nvalid, a.f0, a.nf, a.S, a.Tb, a.bits, mw, mh);
-}
-
 }  // namespace
 
 int covahip_mog_any_update(covahip_ctx *ctx, int mw, int mh, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a) {
-    return launch_update(ctx, "mog_any_update", k_mog_any_update, mw, mh, frames, src_bytes, a);
+    return mog_launch_update_any(ctx, "mog_any_update", k_mog_any_update<false>, mw, mh, frames, src_bytes, a);
 }
 
 int covahip_mog_any_yuv_update(covahip_ctx *ctx, int format, int mw, int mh, const uint8_t *frames, const covahip_mog_yuv_src &src,
                                const MogUpdateArgs &a) {
     if (format != COVAHIP_MOG_FMT_NV12 && format != COVAHIP_MOG_FMT_I420) return COVAHIP_ERR_INVALID_ARG;
-    const auto kernel = format == COVAHIP_MOG_FMT_NV12 ? k_mog_any_yuv_update<COVAHIP_MOG_FMT_NV12> : k_mog_any_yuv_update<COVAHIP_MOG_FMT_I420>;
-    return launch_update(ctx, "mog_any_yuv_update", kernel, mw, mh, frames, src, a);
+    const auto kernel = format == COVAHIP_MOG_FMT_NV12 ? k_mog_any_yuv_update<COVAHIP_MOG_FMT_NV12, false>
+                                                       : k_mog_any_yuv_update<COVAHIP_MOG_FMT_I420, false>;
+    return mog_launch_update_any(ctx, "mog_any_yuv_update", kernel, mw, mh, frames, src, a);
 }
 
 int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,

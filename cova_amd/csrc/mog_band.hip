@@ -34,19 +34,11 @@
 #include "covahip.h"
 #include "internal.h"
 #include "mog_dev.h"
+#include "mog_update.h"
 
 namespace {
 
 using namespace mogdev;
-
-// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
-template <int MW, int MH>
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_band_update(const uint8_t *__restrict__ frames, size_t src_bytes,
-                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
-                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
-                                                               unsigned long long *__restrict__ bits) {
-    update_body<Geom<MW, MH>>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits);
-}
 
 // bits: raw masks [F][S][NWORD]; filled_bits: the filled masks, same layout (T while the fill runs); plane: the mask after the
 // morphology, same layout; labels [F][S][LH][LW]; rows: band height, >= 1; mode, ncover: MogLabelArgs
@@ -150,7 +142,7 @@ constexpr int POST_BLOCK = 512;
 int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a) {
     return with_geom<G1920, G1280>(mw, [&](auto g) {
         using G = decltype(g);
-        return mog_launch_update<G>(ctx, "mog_band_update", k_mog_band_update<G::MW, G::MH>, frames, src_bytes, a);
+        return mog_launch_update<G>(ctx, "mog_band_update", k_mog_band_update<G::MW, G::MH, false>, frames, src_bytes, a);
     });
 }
 

@@ -169,17 +169,74 @@ __device__ __forceinline__ bool mog2_pixel(float (&W)[NMIX], float (&V)[NMIX], f
     return !bg;
 }
 
+// The shadow test of one foreground pixel on the model mog2_pixel has just left (include/covahip.h, "MoG labels", step 2a;
+// detectShadowGMM of OpenCV's MOG2): true when the pixel is a darker copy, by a factor a in [tau, 1], of a background mode's
+// mean.  The model is only read.  The returns of the statement are the `done` flag here, so the unrolled loop keeps W, V and M
+// in registers; a mode past `done` costs nothing but the test of the flag.
+__device__ __forceinline__ bool shadow_pixel(const float (&W)[NMIX], const float (&V)[NMIX], const float (&M)[NMIX][3], int nm,
+                                             const Px &px, float Tb, float tau) {
+    bool done = false, shadow = false;
+    float tw = 0.f;
+#pragma unroll
+    for (int mode = 0; mode < NMIX; mode++) {
+        if (mode < nm && !done) {
+            const float m0 = M[mode][0], m1 = M[mode][1], m2 = M[mode][2];
+            const float num = ((0.f + px.c0 * m0) + px.c1 * m1) + px.c2 * m2;
+            const float den = ((0.f + m0 * m0) + m1 * m1) + m2 * m2;
+            if (den == 0.f) {
+                done = true;
+            } else {
+                if (num <= den && num >= tau * den) {
+                    const float a = div_rn(num, den);
+                    const float d0 = a * m0 - px.c0, d1 = a * m1 - px.c1, d2 = a * m2 - px.c2;
+                    const float dist2a = ((0.f + d0 * d0) + d1 * d1) + d2 * d2;
+                    if (dist2a < ((Tb * V[mode]) * a) * a) shadow = done = true;
+                }
+                if (!done) {
+                    tw = tw + W[mode];
+                    if (tw > TB) done = true;
+                }
+            }
+        }
+    }
+    return shadow;
+}
+
+// What the update kernels take for the shadow test (covahip_mog_set_shadows), behind their other arguments; the instances
+// without the test (SHADOW = false) take it too and read none of it.  plane: the shadow planes [F][S][NWORD], laid out as the raw
+// planes; drop: COVAHIP_MOG_SHADOWS_DROP (the raw plane is fg && !shadow) or _KEEP (it is fg), the same for the whole launch.
+struct MogShadowDev {
+    unsigned long long *plane;
+    float tau;
+    int drop;
+};
+
+// The two words a wave stores for a frame when the shadow test is on: `fg` is mog2_pixel's answer (false in a lane without a
+// pixel), and the test runs on the model as that call left it.  word: where the wave's word lies in either plane.
+__device__ __forceinline__ void shadow_ballots(bool fg, const float (&W)[NMIX], const float (&V)[NMIX], const float (&M)[NMIX][3],
+                                               int nm, const Px &px, float Tb, const MogShadowDev &sh, size_t word,
+                                               unsigned long long *__restrict__ bits) {
+    const bool shd = fg && shadow_pixel(W, V, M, nm, px, Tb, sh.tau);
+    const unsigned long long sw = __ballot(shd), fw = __ballot(fg);
+    if ((threadIdx.x & 63) == 0) {
+        bits[word] = sh.drop ? fw & ~sw : fw;      // wave-uniform select
+        sh.plane[word] = sw;
+    }
+}
+
 // The update kernel's body: one lane per working pixel and stream, grid (G::NPIX / UPD_BLOCK, S).  frames: the launch's first
 // frame of stream 0, with frames and streams at byte strides of the caller's; par: (alphaT, prune) [F][S] of the call; bits: raw
 // masks [F][S][G::NWORD].  A wave's 64 pixels lie in one row, so its ballot is one word of the plane.  `load.at(x, y)` gives
 // what the lane needs to address its pixel within a frame (Load::At), once; `load(frame, at)` gives the raw words of working
 // pixel (x, y) (Load::Raw) and `load.px(raw)` makes the pixel of them where it is consumed, so that the next frame's words stay
-// in flight across this frame's mog2_pixel.  Load::WAIT says whether the body waits once before its loop (below).
-template <class G, class Load>
+// in flight across this frame's mog2_pixel.  Load::WAIT says whether the body waits once before its loop (below).  SHADOW: the
+// shadow test runs on every foreground pixel and the wave stores two words per frame (shadow_ballots); without it `sh` is not
+// read and the body is the one it was before the test existed.
+template <class G, bool SHADOW, class Load>
 __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__restrict__ frames, long long frame_stride,
                                                     long long stream_stride, uint8_t *__restrict__ state,
                                                     const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf,
-                                                    int S, float Tb, unsigned long long *__restrict__ bits) {
+                                                    int S, float Tb, unsigned long long *__restrict__ bits, const MogShadowDev &sh) {
     constexpr int NPIX = G::NPIX;
     const int s = blockIdx.y;
     int fend = nvalid[s] - f0;
@@ -212,8 +269,12 @@ __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__
         const float2 pr = par[(size_t)(f0 + f) * S + s];
         const Px px = load.px(cur);
         const bool fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
-        const unsigned long long word = __ballot(fg);
-        if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+        if constexpr (SHADOW) {
+            shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * G::NWORD + p / 64, bits);
+        } else {
+            const unsigned long long word = __ballot(fg);
+            if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+        }
         cur = nxt;
     }
 #pragma unroll
@@ -237,12 +298,12 @@ struct PlainLoad {
     __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, const At &t) const { return load(fr, t.x, t.y); }
     __device__ __forceinline__ Px px(const Px &r) const { return r; }
 };
-template <class G, class L>
+template <class G, bool SHADOW, class L>
 __device__ __forceinline__ void update_body(L load, const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
                                             const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf, int S,
-                                            float Tb, unsigned long long *__restrict__ bits) {
-    update_body_strided<G>(PlainLoad<L>{load}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par, nvalid,
-                           f0, nf, S, Tb, bits);
+                                            float Tb, unsigned long long *__restrict__ bits, const MogShadowDev &sh) {
+    update_body_strided<G, SHADOW>(PlainLoad<L>{load}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par,
+                                   nvalid, f0, nf, S, Tb, bits, sh);
 }
 
 // working pixel (x, y) of a frame of 2 MW x 2 MH: the rounded mean of its 2x2 block (the macroblock grid's load)
@@ -728,7 +789,9 @@ int with_geom(int mw, F &&f) {
 }
 
 // What an update launch takes behind its frames: the model, the call's tables (par: (alphaT, prune) [F][S]; nvalid [S]), the
-// launch's frames f0 .. f0 + nf of the call, and the call's raw planes.  All device memory.
+// launch's frames f0 .. f0 + nf of the call, and the call's raw planes.  All device memory.  shadows: COVAHIP_MOG_SHADOWS_* of
+// the call; other than _OFF the launch goes to the kernels' SHADOW instances (mog_shadow.hip), which read tau and write
+// `shadow`, the call's shadow planes.
 struct MogUpdateArgs {
     uint8_t *state;
     const float2 *par;
@@ -736,12 +799,18 @@ struct MogUpdateArgs {
     int f0, nf, S;
     float Tb;
     unsigned long long *bits;
+    int shadows = COVAHIP_MOG_SHADOWS_OFF;
+    float tau = 0.5f;
+    unsigned long long *shadow = nullptr;
 };
 // How a post launch takes its labels (include/covahip.h, "MoG labels", step 6): mode COVAHIP_MOG_LABELS_*, and with _COVER
 // ncover in 1 .. 64.  Arguments of the post kernels, the same for the whole launch.
 struct MogLabelArgs {
     int mode = COVAHIP_MOG_LABELS_CORNER, ncover = 1;
 };
+inline mogdev::MogShadowDev mog_shadow_dev(const MogUpdateArgs &a) {
+    return {a.shadow, a.tau, a.shadows == COVAHIP_MOG_SHADOWS_DROP};
+}
 // One kernel launch on ctx->stream under a profile scope
 template <class K, class... Args>
 int mog_launch(covahip_ctx *ctx, const char *scope, K kernel, dim3 grid, int block, size_t lds, Args... args) {
@@ -752,12 +821,12 @@ int mog_launch(covahip_ctx *ctx, const char *scope, K kernel, dim3 grid, int blo
     COVAHIP_CHECK_HIP(ctx, hipGetLastError());
     return COVAHIP_OK;
 }
-// One update launch of geometry G: every update kernel takes (frames, src, the fields of MogUpdateArgs), where src is a BGR24
-// frame's bytes or a covahip_mog_yuv_src
+// One update launch of geometry G: every update kernel takes (frames, src, the fields of MogUpdateArgs with the shadow test's as
+// a MogShadowDev), where src is a BGR24 frame's bytes or a covahip_mog_yuv_src
 template <class G, class K, class Src>
 int mog_launch_update(covahip_ctx *ctx, const char *scope, K kernel, const uint8_t *frames, const Src &src, const MogUpdateArgs &a) {
     return mog_launch(ctx, scope, kernel, dim3(G::NPIX / mogdev::UPD_BLOCK, a.S), mogdev::UPD_BLOCK, 0, frames, src, a.state, a.par,
-                      a.nvalid, a.f0, a.nf, a.S, a.Tb, a.bits);
+                      a.nvalid, a.f0, a.nf, a.S, a.Tb, a.bits, mog_shadow_dev(a));
 }
 
 // The macroblock grid's kernels at working width `mw` (960 or 320; 640 runs mog.hip's own).  Pointers are device memory, the

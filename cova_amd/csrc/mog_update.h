@@ -1,0 +1,194 @@
+// The update kernels of the MoG labeller, all six, as templates over `bool SHADOW` (mog_dev.h: update_body_strided, shadow_pixel):
+//   k_mog_update          the reference grid's 640x360 working frames (launched by mog.hip)
+//   k_mog_grid_update     the macroblock grid's resident sizes (mog_grid.hip)
+//   k_mog_band_update     its 1440p and 4K sizes (mog_band.hip)
+//   k_mog_yuv_update      all of those on NV12 / I420 surfaces (mog_yuv.hip)
+//   k_mog_any_update, k_mog_any_yuv_update   any size, the geometry as arguments (mog_any.hip)
+// Each of those files instantiates and launches the SHADOW = false kernels, which are instruction for instruction the kernels
+// from before the shadow test existed; mog_shadow.hip instantiates and launches the SHADOW = true ones (covahip_mog_set_shadows
+// in a mode other than OFF).  The files' heads describe the kernels.
+//
+// No contraction in this code (see mog_dev.h); every file that includes it is built with the flags of mog.hip.
+#pragma once
+#pragma clang fp contract(off)
+
+#include "mog_dev.h"
+
+namespace mogdev {
+
+// source pixel(s) of working pixel (x, y) of one frame, resized as cv.resize INTER_LINEAR does for the three sizes: the copy
+// (640x360 sources), the 2x2 mean (1280x720) and the centre pick (1920x1080)
+template <int SRC>
+struct LoadPx {
+    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
+        if constexpr (SRC == MOG_LOAD_HALF) return LoadHalf<G640::MW>()(fr, x, y);
+        const uint8_t *q = SRC == MOG_LOAD_COPY ? fr + ((size_t)y * 640 + x) * 3 : fr + ((size_t)(3 * y + 1) * 1920 + 3 * x + 1) * 3;
+        return {(float)q[0], (float)q[1], (float)q[2]};
+    }
+};
+
+// SRC: MOG_LOAD_*.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of the call; bits: raw masks
+// [F][S][3600]; SHADOW, sh: the shadow test (update_body_strided)
+template <int SRC, bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
+                                                          const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
+                                                          int nf, int S, float Tb, unsigned long long *__restrict__ bits, MogShadowDev sh) {
+    update_body<G640, SHADOW>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
+}
+
+// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
+template <int MW, int MH, bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__restrict__ frames, size_t src_bytes,
+                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                                               unsigned long long *__restrict__ bits, MogShadowDev sh) {
+    update_body<Geom<MW, MH>, SHADOW>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
+}
+
+// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
+template <int MW, int MH, bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_band_update(const uint8_t *__restrict__ frames, size_t src_bytes,
+                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                                               unsigned long long *__restrict__ bits, MogShadowDev sh) {
+    update_body<Geom<MW, MH>, SHADOW>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
+}
+
+// frames: the launch's first frame of stream 0; par: (alphaT, prune) [F][S] of the call; bits: raw masks [F][S][G::NWORD]
+template <int MW, int MH, int FMT, int KIND, bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
+                                                              uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                                              const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                                              unsigned long long *__restrict__ bits, MogShadowDev sh) {
+    update_body_strided<Geom<MW, MH>, SHADOW>(LoadYuv<FMT, KIND>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid,
+                                              f0, nf, S, Tb, bits, sh);
+}
+
+// working pixel (x, y) of a BGR24 frame src_w wide: LoadHalf with the width as a member
+struct LoadHalfAny {
+    int src_w;
+    __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, int x, int y) const {
+        const uint8_t *a = fr + ((size_t)(2 * y) * src_w + 2 * x) * 3;
+        const uint8_t *b = a + (size_t)src_w * 3;
+        unsigned s0 = ((unsigned)a[0] + a[3] + b[0] + b[3] + 2) >> 2;
+        unsigned s1 = ((unsigned)a[1] + a[4] + b[1] + b[4] + 2) >> 2;
+        unsigned s2 = ((unsigned)a[2] + a[5] + b[2] + b[5] + 2) >> 2;
+        return {(float)s0, (float)s1, (float)s2};
+    }
+};
+
+// update_body_strided of mog_dev.h on the padded pitch: grid (ceil(P / UPD_BLOCK), S), bits [F][S][roww mh].  SHADOW, sh: as
+// there; a lane at x >= mw is no foreground, so it is in neither plane.
+template <bool SHADOW, class Load>
+__device__ __forceinline__ void update_any(Load load, const uint8_t *__restrict__ frames, long long frame_stride, long long stream_stride,
+                                           uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                           const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                           unsigned long long *__restrict__ bits, int mw, int mh, const MogShadowDev &sh) {
+    const int s = blockIdx.y;
+    int fend = nvalid[s] - f0;
+    fend = fend < nf ? fend : nf;
+    if (fend <= 0) return;                     // the same for the whole block
+    const int pitch = (mw + 63) / 64 * 64;
+    const size_t P = (size_t)pitch * mh;
+    const size_t p = (size_t)blockIdx.x * UPD_BLOCK + threadIdx.x;
+    if (p >= P) return;                        // whole waves: P is a multiple of 64
+    const int x = (int)(p % pitch), y = (int)(p / pitch);
+    const bool live = x < mw;                  // lane 0 of a wave always is
+    uint8_t *st = state + (size_t)s * (P * (5 * NMIX * 4 + 1));
+    float *gW = reinterpret_cast<float *>(st), *gV = gW + NMIX * P, *gM = gW + 2 * NMIX * P;
+    uint8_t *gN = st + (size_t)5 * NMIX * 4 * P;
+    float W[NMIX] = {}, V[NMIX] = {}, M[NMIX][3] = {};
+    int nm = 0;
+    const uint8_t *fr = frames + (long long)s * stream_stride;
+    typename Load::At at{};
+    typename Load::Raw cur{};
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < NMIX; k++) {
+            W[k] = gW[(size_t)k * P + p];
+            V[k] = gV[(size_t)k * P + p];
+#pragma unroll
+            for (int c = 0; c < 3; c++) M[k][c] = gM[(size_t)(k * 3 + c) * P + p];
+        }
+        nm = gN[p];
+        at = load.at(x, y);
+        cur = load(fr, at);
+    }
+    for (int f = 0; f < fend; f++) {
+        typename Load::Raw nxt = cur;
+        if (live && f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
+        const float2 pr = par[(size_t)(f0 + f) * S + s];
+        bool fg = false;
+        if constexpr (SHADOW) {
+            Px px{};
+            if (live) {
+                px = load.px(cur);
+                fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
+            }
+            shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * (P / 64) + p / 64, bits);
+        } else {
+            if (live) fg = mog2_pixel(W, V, M, nm, load.px(cur), pr.x, pr.y, Tb);
+            const unsigned long long word = __ballot(fg);
+            if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * (P / 64) + p / 64] = word;
+        }
+        cur = nxt;
+    }
+    if (live) {
+#pragma unroll
+        for (int k = 0; k < NMIX; k++) {
+            gW[(size_t)k * P + p] = W[k];
+            gV[(size_t)k * P + p] = V[k];
+#pragma unroll
+            for (int c = 0; c < 3; c++) gM[(size_t)(k * 3 + c) * P + p] = M[k][c];
+        }
+        gN[p] = (uint8_t)nm;
+    }
+}
+
+// frames: this launch's first frame, [nf][S][2 mh][2 mw][3]
+template <bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
+                                                              const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
+                                                              int nf, int S, float Tb, unsigned long long *__restrict__ bits, int mw, int mh,
+                                                              MogShadowDev sh) {
+    update_any<SHADOW>(PlainLoad<LoadHalfAny>{LoadHalfAny{2 * mw}}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state,
+                       par, nvalid, f0, nf, S, Tb, bits, mw, mh, sh);
+}
+
+// frames: the launch's first frame of stream 0, surfaces as `src` describes them
+template <int FMT, bool SHADOW>
+__global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
+                                                                  uint8_t *__restrict__ state, const float2 *__restrict__ par,
+                                                                  const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
+                                                                  unsigned long long *__restrict__ bits, int mw, int mh, MogShadowDev sh) {
+    update_any<SHADOW>(LoadYuv<FMT, YUV_HALF>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid, f0, nf, S, Tb, bits, mw,
+                       mh, sh);
+}
+
+}  // namespace mogdev
+
+// One update launch of the any-size kernels at working size mw x mh (as mog_launch_update for the templated geometries)
+template <class K, class Src>
+int mog_launch_update_any(covahip_ctx *ctx, const char *scope, K kernel, int mw, int mh, const uint8_t *frames, const Src &src,
+                          const MogUpdateArgs &a) {
+    constexpr int BLOCK = mogdev::UPD_BLOCK;
+    const size_t P = (size_t)mog_any_pitch(mw) * mh;
+    return mog_launch(ctx, scope, kernel, dim3((unsigned)((P + BLOCK - 1) / BLOCK), a.S), BLOCK, 0, frames, src, a.state, a.par, a.nvalid,
+                      a.f0, a.nf, a.S, a.Tb, a.bits, mw, mh, mog_shadow_dev(a));
+}
+
+// The SHADOW = true instance of whichever update kernel a labeller runs (mog_shadow.hip): what mog.hip's dispatch looks at, as a
+// value.  format: COVAHIP_MOG_FMT_* of the surfaces, 0 for BGR24 frames of src_bytes each (then src is not read); load:
+// MOG_LOAD_*; resident: the row's post form, which says whether a BGR24 labeller off the 640 wide working size runs
+// k_mog_grid_update or k_mog_band_update.
+struct MogShadowRoute {
+    bool any;
+    int format, load, mw, mh;
+    bool resident;
+};
+int covahip_mog_shadow_update(covahip_ctx *ctx, const MogShadowRoute &r, const uint8_t *frames, size_t src_bytes,
+                              const covahip_mog_yuv_src &src, const MogUpdateArgs &a);
+// counts [FS][2] (u32, device) = the set bits of shadow and of bits & ~shadow in each of FS planes of nword words; shadow may be
+// nullptr (then none)
+int covahip_mog_counts(covahip_ctx *ctx, const unsigned long long *bits, const unsigned long long *shadow, size_t nword, size_t FS,
+                       uint32_t *counts);

@@ -23,6 +23,7 @@
 #include "covahip.h"
 #include "internal.h"
 #include "mog_dev.h"
+#include "mog_update.h"
 
 namespace {
 
@@ -31,19 +32,9 @@ using namespace mogdev;
 constexpr int HALF = YUV_HALF, COPY = YUV_COPY, PICK = YUV_PICK;   // LoadYuv's kinds (mog_dev.h)
 constexpr int NV12 = COVAHIP_MOG_FMT_NV12, I420 = COVAHIP_MOG_FMT_I420;
 
-// frames: the launch's first frame of stream 0; par: (alphaT, prune) [F][S] of the call; bits: raw masks [F][S][G::NWORD]
-template <int MW, int MH, int FMT, int KIND>
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
-                                                              uint8_t *__restrict__ state, const float2 *__restrict__ par,
-                                                              const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
-                                                              unsigned long long *__restrict__ bits) {
-    update_body_strided<Geom<MW, MH>>(LoadYuv<FMT, KIND>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid, f0,
-                                      nf, S, Tb, bits);
-}
-
 template <class G, int KIND>
 int launch(covahip_ctx *ctx, int format, const uint8_t *frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
-    const auto kernel = format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND> : k_mog_yuv_update<G::MW, G::MH, I420, KIND>;
+    const auto kernel = format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND, false> : k_mog_yuv_update<G::MW, G::MH, I420, KIND, false>;
     return mog_launch_update<G>(ctx, "mog_yuv_update", kernel, frames, src, a);
 }
 

@@ -7,6 +7,8 @@
                source size from 256 to 4096 in both axes: 1280x960 gives 60x80 labels, 704x576 36x44
                labels="corner" (the default: the block's top-left pixel, the reference's ::8 subsample), ("cover", N) (1 where
                at least N / 64 of the block is foreground: small objects keep their labels) or "count" (0 .. 64, for inspection)
+               shadows="drop" | "keep" | (mode, tau) turns MOG2's shadow detection on (OpenCV's detectShadows, tau 0.5):
+               "drop" keeps cast shadows out of the labels, "keep" only marks them (127 in debug_masks, shadow_counts)
   label_dims   (label_h, label_w) of a source size on either grid, without a GPU; label_dims_any / work_dims_any: of any_size
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
   apply_yuv    the same labels from 8-bit 4:2:0 frames as decoders give them, NV12 or I420, at a row pitch, plane offsets and
@@ -23,6 +25,8 @@
     python -m cova_amd.mog --format nv12 --size 1920x1080 [--range full] IN.nv12 ...     (also --format i420)
     python -m cova_amd.mog --size 1280x720 --labels cover:32 IN.bgr ...       (a label where half the block is foreground)
     python -m cova_amd.mog --size 1280x720 --labels count IN.bgr:IN_count.dump           (then tools/label_cover.py picks N)
+    python -m cova_amd.mog --size 1280x720 --shadows drop:0.5 IN.bgr ...      (cast shadows stay out of the labels)
+    python -m cova_amd.mog --size 1280x720 --shadows keep:0.4 --shadow-report IN.bgr ... (labels as without; what drop would remove)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
 to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Bitstream decoding is not done here:
@@ -51,6 +55,29 @@ FORMATS = {"nv12": 1, "i420": 2}                # COVAHIP_MOG_FMT_*
 RANGES = {"limited": 0, "full": 1}              # COVAHIP_MOG_RANGE_*
 ANY_MIN, ANY_MAX = 256, 4096                    # COVAHIP_MOG_ANY_*: what any_size admits, per axis and even
 LABEL_MODES = {"corner": 0, "cover": 1, "count": 2}     # COVAHIP_MOG_LABELS_*
+SHADOW_MODES = {"off": 0, "drop": 1, "keep": 2}         # COVAHIP_MOG_SHADOWS_*
+SHADOW_TAU = 0.5                                        # OpenCV's default shadow threshold
+
+
+def shadow_mode(shadows):
+    """(mode name, tau) of a `shadows` value: None or "off", "drop", "keep" (tau = SHADOW_TAU), or (mode, tau) with mode "drop" or
+    "keep" and a finite 0 < tau <= 1.  tau is SHADOW_TAU where the mode does not read it.  Anything else raises ValueError."""
+    if shadows is None:
+        return "off", SHADOW_TAU
+    if isinstance(shadows, str):
+        name, tau = shadows, SHADOW_TAU
+    else:
+        try:
+            name, tau = shadows
+        except (TypeError, ValueError):
+            raise ValueError(f"shadows {shadows!r}: None, 'drop', 'keep' or (mode, tau)") from None
+        if name not in ("drop", "keep"):
+            raise ValueError(f"shadows {shadows!r}: only 'drop' and 'keep' take a tau")
+    if not isinstance(name, str) or name not in SHADOW_MODES:
+        raise ValueError(f"unknown shadow mode {name!r}: one of " + ", ".join(SHADOW_MODES))
+    if isinstance(tau, bool) or not isinstance(tau, (int, float, np.integer, np.floating)) or not (np.isfinite(tau) and 0 < tau <= 1):
+        raise ValueError(f"shadows {shadows!r}: tau must be a finite number with 0 < tau <= 1")
+    return name, float(tau)
 
 
 def label_mode(labels):
@@ -142,11 +169,14 @@ class MogLabeler:
     force_general=True (tests, measurements) takes at every size; the results do not depend on which.  `labels` is the label
     mode (label_mode; set_labels changes it later): "corner", the default, is the block's top-left pixel; ("cover", N) is 1 where
     64 * count >= N * inside for the block's foreground count and its pixels inside the image; "count" is that count, 0 .. 64,
-    which is for inspection and no trainer input."""
+    which is for inspection and no trainer input.  `shadows` (shadow_mode; set_shadows changes it later) turns MOG2's shadow
+    detection on: None, the default, is the reference's detectShadows=False; "drop" takes shadow pixels for background before
+    close, open and fill; "keep" runs the test and leaves the labels as they are without it; (mode, tau) gives the threshold."""
 
     def __init__(self, ctx, src_w: int, src_h: int, streams: int = 1, history: int = 9000, var_threshold: float = 32.0,
-                 grid: str = "reference", any_size: bool = False, force_general: bool = False, labels="corner"):
+                 grid: str = "reference", any_size: bool = False, force_general: bool = False, labels="corner", shadows=None):
         label_mode(labels)                                                   # ValueError before the ctx is touched
+        shadow_mode(shadows)
         if grid not in GRIDS:
             raise ValueError(f"unknown grid {grid!r}: one of " + ", ".join(GRIDS))
         any_size = any_size or force_general
@@ -175,6 +205,8 @@ class MogLabeler:
         self.work_w, self.work_h, self.label_w, self.label_h = (int(v.value) for v in d)
         if label_mode(labels)[0] != "corner":
             self.set_labels(labels)
+        if shadow_mode(shadows)[0] != "off":
+            self.set_shadows(shadows)
 
     def set_labels(self, labels):
         """The label mode of every later call (apply, apply_yuv, post_masks), for all streams: "corner", "count" or ("cover", N),
@@ -189,6 +221,31 @@ class MogLabeler:
         L.check(self._lib.covahip_mog_get_labels(self.handle, C.byref(mode), C.byref(n)), "covahip_mog_get_labels")
         name = {v: k for k, v in LABEL_MODES.items()}[mode.value]
         return (name, int(n.value)) if name == "cover" else name
+
+    def set_shadows(self, shadows):
+        """The shadow mode of every later apply / apply_yuv call, for all streams: None or "off", "drop", "keep", or (mode, tau).
+        The model does not depend on it, and reset keeps it."""
+        name, tau = shadow_mode(shadows)
+        L.check(self._lib.covahip_mog_set_shadows(self.handle, SHADOW_MODES[name], tau), "covahip_mog_set_shadows")
+
+    @property
+    def shadows(self):
+        """The shadow mode in force: None, or (mode, tau) with mode "drop" or "keep"."""
+        mode, tau = C.c_int(), C.c_float()
+        L.check(self._lib.covahip_mog_get_shadows(self.handle, C.byref(mode), C.byref(tau)), "covahip_mog_get_shadows")
+        name = {v: k for k, v in SHADOW_MODES.items()}[mode.value]
+        return None if name == "off" else (name, float(tau.value))
+
+    def shadow_counts(self):
+        """(shadow, foreground) of the last apply / apply_yuv call, u32 [F][S] each: the raw mask's pixels at 127 and at 255, counted
+        on the device.  Frames past a stream's n_valid give 0; without shadow detection `shadow` is all 0."""
+        nf = C.c_int()
+        L.check(self._lib.covahip_mog_shadow_counts(self.handle, None, None, 0, C.byref(nf)), "covahip_mog_shadow_counts")
+        shadow = np.zeros((nf.value, self.streams), np.uint32)
+        fg = np.zeros_like(shadow)
+        L.check(self._lib.covahip_mog_shadow_counts(self.handle, _ptr(shadow), _ptr(fg), shadow.size, C.byref(nf)),
+                "covahip_mog_shadow_counts", self.ctx.handle)
+        return shadow, fg
 
     def close(self):
         if getattr(self, "handle", None):
@@ -301,8 +358,8 @@ class MogLabeler:
         return {"W": W, "V": V, "M": M, "nmodes": nm, "n": int(n.value)}
 
     def debug_masks(self):
-        """(raw, filled) of the last apply call, u8 [F][S][work_h][work_w]: the MOG2 mask (0 / 255) and the mask after close, open
-        and hole fill (0 / 1)."""
+        """(raw, filled) of the last apply call, u8 [F][S][work_h][work_w]: the MOG2 mask (0 / 255; with shadow detection on 0 / 127 / 255,
+        127 = shadow, in "drop" and in "keep" mode alike) and the mask after close, open and hole fill (0 / 1)."""
         nf = C.c_int()
         L.check(self._lib.covahip_dev_mog_masks(self.handle, None, None, 0, C.byref(nf)), "covahip_dev_mog_masks")
         shape = (nf.value, self.streams, self.work_h, self.work_w)
@@ -517,6 +574,21 @@ def parse_labels(text: str):
     return "cover", int(num)
 
 
+def parse_shadows(text: str):
+    """off | drop[:TAU] | keep[:TAU] -> a `shadows` value of MogLabeler; TAU defaults to SHADOW_TAU."""
+    name, sep, num = text.partition(":")
+    if name not in SHADOW_MODES or (sep and name == "off"):
+        raise argparse.ArgumentTypeError(f"shadows {text!r}: off, drop[:TAU] or keep[:TAU]")
+    if name == "off":
+        return None
+    if not sep:
+        return name, SHADOW_TAU
+    try:
+        return shadow_mode((name, float(num)))
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"shadows {text!r}: TAU must be a number with 0 < TAU <= 1") from None
+
+
 def parse_io(arg: str):
     """IN[:OUT] -> (IN, OUT); OUT defaults to IN's name with `_gt.dump`."""
     src, sep, out = arg.rpartition(":")
@@ -556,6 +628,15 @@ def _args(argv):
                          "cover[:N], N in 1 .. 64 (default 1): 1 where at least N / 64 of the block's pixels inside the image are "
                          "foreground, so an object narrower than a block keeps its label; count: that number of pixels, a byte "
                          "0 .. 64 -- for inspection and for choosing N (tools/label_cover.py), not a trainer input")
+    ap.add_argument("--shadows", type=parse_shadows, default=None, metavar="off|drop[:TAU]|keep[:TAU]",
+                    help="MOG2's shadow detection (OpenCV's detectShadows; TAU, default 0.5, is how dark a shadow may be relative to "
+                         "the background).  off (the default): none, as the reference.  drop: shadow pixels count as background, so a "
+                         "vehicle's cast shadow stays out of its label.  keep: the test runs and the labels stay as without it -- with "
+                         "--shadow-report it shows what drop would remove.  Note: --balance of the trainer thresholds a frame's label sum, "
+                         "which shrinks under drop")
+    ap.add_argument("--shadow-report", action="store_true",
+                    help="print, per input, the mean share of shadow and of foreground pixels per frame (how TAU gets chosen for a "
+                         "camera); needs --shadows drop or keep")
     ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
     ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
     ap.add_argument("--history", type=int, default=9000)
@@ -591,6 +672,8 @@ def _args(argv):
         ap.error(f"--streams must be in [1, {MAX_STREAMS}]")
     if a.chunk < 1:
         ap.error("--chunk must be >= 1")
+    if a.shadow_report and a.shadows is None:
+        ap.error("--shadow-report needs --shadows drop or keep")
     if a.history < 1:
         ap.error("--history must be >= 1")
     if not (np.isfinite(a.var_threshold) and a.var_threshold > 0):
@@ -655,11 +738,13 @@ def main(argv=None) -> int:
     yuv = a.format != "bgr24"
     ctx = Context(a.device)
     mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid, any_size=a.any_size is not None,
-                     labels=a.labels)
+                     labels=a.labels, shadows=a.shadows)
     layout = yuv_tight(w, h, "nv12" if a.format == "nv12" else "i420", a.range, streams=S) if yuv else None
     frames = np.empty((a.chunk, S, w * h * 3 // 2) if yuv else (a.chunk, S, h, w, 3), np.uint8)
     labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)
     slots = [None] * S           # (source, output file, output name, start time) per stream slot
+    npix = mog.work_w * mog.work_h
+    tally = [[0, 0] for _ in range(S)]      # --shadow-report: shadow and foreground pixels of the slot's video so far
 
     def open_next(s):
         if not pending:
@@ -668,6 +753,7 @@ def main(argv=None) -> int:
         src, out = pending.pop(0)
         source = (y4m_open(src) if a.format == "y4m" else _RawSource(src, w * h * 3 // 2) if yuv else _Bgr24Source(src, w, h))
         slots[s] = (source, open(out, "wb"), out, time.perf_counter())
+        tally[s] = [0, 0]
         mog.reset(s)
 
     def finish(s):
@@ -676,6 +762,10 @@ def main(argv=None) -> int:
         f.close()
         dt = time.perf_counter() - t0
         print(f"{src.name}: {src.frames} frames, {src.frames / dt if dt > 0 else 0.0:.1f} frames/s -> {out}", file=sys.stderr)
+        if a.shadow_report:
+            per = max(src.frames, 1) * npix
+            print(f"{src.name}: shadow {tally[s][0] / per:.6f} foreground {tally[s][1] / per:.6f} of {npix} pixels per frame, "
+                  f"{src.frames} frames, --shadows {a.shadows[0]}:{a.shadows[1]:g}")
 
     try:
         for s in range(S):
@@ -698,6 +788,11 @@ def main(argv=None) -> int:
                 mog.apply_yuv(frames, layout, int(nv.max()), n_valid=nv, labels=labels[:int(nv.max())])
             else:
                 mog.apply(frames[:int(nv.max())], n_valid=nv, labels=labels[:int(nv.max())])
+            if a.shadow_report:
+                sh, fg = mog.shadow_counts()
+                for s in range(S):
+                    tally[s][0] += int(sh[:, s].sum())
+                    tally[s][1] += int(fg[:, s].sum())
             for s in range(S):
                 if nv[s]:
                     slots[s][1].write(np.ascontiguousarray(labels[:nv[s], s]).tobytes())

@@ -786,7 +786,7 @@ int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const 
  *        2x2 block; 1920x1080 (linear weights (1, 0) at an exact 3x scale) source pixel (3x + 1, 3y + 1);
  *   2. MOG2 of createBackgroundSubtractorMOG2(history, var_threshold, detectShadows = false), apply() with the default
  *      learning rate (below);
- *   3. fg = mask > 0;
+ *   3. fg = mask > 0 (with shadows dropped, covahip_mog_set_shadows: fg = mask == 255);
  *   4. close with a 4x4 ones kernel, then open with a 6x6 ones kernel.  OpenCV's anchor k/2, the same offsets for erode and
  *      dilate: the window at x covers x - 2 .. x + 1 (4x4) and x - 3 .. x + 2 (6x6) in both axes; outside the image is 0 for
  *      dilate and 1 for erode;
@@ -837,6 +837,27 @@ int covahip_train_eval_set_data(covahip_train *tr, covahip_train_data *d, const 
  *     4. if !fits: slot m = nmodes == 5 ? 4 : nmodes++; if nmodes == 1: W[m] = 1, else W[m] = alphaT and W[i] *= alpha1 for
  *        i < nmodes - 1; M[m] = data; V[m] = varInit; for i = nmodes - 1 down to 1: stop if alphaT < W[i-1], else swap;
  *     5. mask = bg ? 0 : 255.
+ *   2a. The shadow test (covahip_mog_set_shadows below; off by default, and then none of this runs).  It is detectShadowGMM of
+ *     OpenCV 4.x bgfg_gaussmix2.cpp, what createBackgroundSubtractorMOG2(.., detectShadows = true) adds, restated: this text is
+ *     the contract, and tests/test_mog_shadow_host.py compares it with cv2 wherever cv2 is installed.  Per pixel, after steps
+ *     1 - 4 on the UPDATED model (the new mode of step 4, the renormalised weights and the new nmodes included), only where bg
+ *     is false.  All values f32, every product and sum rounded on its own, the division correctly rounded; tau is the shadow
+ *     threshold:
+ *       tw = 0
+ *       for mode = 0 .. nmodes - 1:
+ *           num = ((0 + data0*M0) + data1*M1) + data2*M2;   den = ((0 + M0*M0) + M1*M1) + M2*M2     (M = M[mode])
+ *           if den == 0: not a shadow, stop
+ *           if num <= den && num >= tau * den:
+ *               a = num / den;  dD_c = a * M_c - data_c;  dist2a = ((0 + dD0*dD0) + dD1*dD1) + dD2*dD2
+ *               if dist2a < ((Tb * V[mode]) * a) * a: a shadow, stop
+ *           tw += W[mode];  if tw > TB: not a shadow, stop
+ *       not a shadow
+ *     mask = bg ? 0 : (shadow ? 127 : 255), OpenCV's values.  Two consequences, both checked by the tests:
+ *       frame 1: every pixel's only mode is the pixel itself, so num == den, a = 1 and dist2a = 0: every pixel that is not
+ *         (0, 0, 0) is a shadow, and a (0, 0, 0) pixel has den == 0 and is 255.  With shadows dropped, frame 1 is therefore
+ *         nearly all background, where without the test it is all foreground;
+ *       exact edges: after a constant (100, 120, 140) history, (50, 60, 70) is a shadow at tau = 0.5 (num = 22000 = tau * den
+ *         exactly); (49, 60, 70) is not.
  * Streams: n_streams independent videos advance in one call, each with its own model and frame count.  Memory: about 23 MB of
  * model per stream (101 bytes per working pixel: 52 MB at 960x540, 93 MB at 1280x720, 209 MB at 1920x1080; many 4K streams can
  * exhaust device memory, and create then answers COVAHIP_ERR_HIP).  Every call is synchronous. */
@@ -885,6 +906,26 @@ int  covahip_mog_create_any(covahip_ctx *ctx, const covahip_mog_cfg *cfg, covahi
 enum { COVAHIP_MOG_LABELS_CORNER = 0, COVAHIP_MOG_LABELS_COVER = 1, COVAHIP_MOG_LABELS_COUNT = 2 };
 int  covahip_mog_set_labels(covahip_mog *m, int mode, int min_cover);
 int  covahip_mog_get_labels(const covahip_mog *m, int *mode, int *min_cover);
+/* Shadow detection (step 2a), per labeller.  COVAHIP_MOG_SHADOWS_OFF, the default, is the reference's detectShadows = false:
+ * the test does not run, on the kernels that have none.  _DROP runs it and changes step 3 to fg = mask == 255: shadow pixels
+ * enter close, open and fill as background, so a vehicle's cast shadow stays out of its label.  _KEEP runs it and leaves step 3
+ * at mask > 0, which is what generate-mog.py would do with detectShadows = true: filled masks and labels are bit-identical to
+ * _OFF, only the raw mask (covahip_dev_mog_masks) and the counts below differ; it is the inspection mode, which shows what _DROP
+ * would remove before a label changes.  tau is read when mode != _OFF and must be finite with 0 < tau <= 1 (OpenCV's default
+ * is 0.5; a shadow is at least tau times as bright as the background).  COVAHIP_ERR_INVALID_ARG, with nothing changed: a NULL
+ * labeller, an unknown mode, such a tau.  covahip_mog_get_shadows gives the setting back (tau: the last one set, 0.5 at first);
+ * either pointer may be NULL.  The setting holds for every later covahip_mog_apply and covahip_mog_apply_yuv, for all streams,
+ * covahip_mog_reset keeps it, and it may change between calls.  The model does not depend on it (the test only reads the
+ * model): a labeller that switches modes has, bit for bit, the state of one that never did.
+ * covahip_mog_shadow_counts: of the last apply / apply_yuv call, per (frame, stream) as [n_frames][n_streams], the number of
+ * raw-mask pixels at 127 (shadow) and at 255 (foreground) inside the image, exact integers counted on the device.  Either array
+ * may be NULL; cap is the number of entries each holds, COVAHIP_ERR_OVERFLOW when that is fewer than n_frames * n_streams (with
+ * *n_frames set, so a call with both NULL asks for the size).  Frames past a stream's n_valid give 0; in _OFF mode shadow is all
+ * 0.  n_frames may be NULL. */
+enum { COVAHIP_MOG_SHADOWS_OFF = 0, COVAHIP_MOG_SHADOWS_DROP = 1, COVAHIP_MOG_SHADOWS_KEEP = 2 };
+int  covahip_mog_set_shadows(covahip_mog *m, int mode, float tau);
+int  covahip_mog_get_shadows(const covahip_mog *m, int *mode, float *tau);
+int  covahip_mog_shadow_counts(covahip_mog *m, uint32_t *shadow, uint32_t *foreground, size_t cap, int *n_frames);
 /* The labeller's working size and label grid; any pointer may be NULL. */
 int  covahip_mog_dims(const covahip_mog *m, int32_t *work_w, int32_t *work_h, int32_t *label_w, int32_t *label_h);
 /* frames u8 [n_frames][n_streams][src_h][src_w][3]; labels u8 [n_frames][n_streams][45][80] (mem_kind applies to both; n_valid is

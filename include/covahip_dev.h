@@ -79,7 +79,9 @@ int covahip_dev_pipe_queue_plan(struct covahip_pipe *pipe, int *lanes_on_upload_
 /* MoG labels (covahip_mog_apply) of the last call, expanded from its bit planes: raw = the MOG2 mask (0 / 255) and filled = the
  * mask after close, open and hole fill (0 / 1), each u8 [n_frames][n_streams][work_h][work_w] of the labeller's own working size
  * (covahip_mog_dims; 360 x 640 on the reference grid) (either may be NULL; cap = bytes of each; COVAHIP_ERR_OVERFLOW when too small).  *n_frames = that call's n_frames.  Frames past a stream's n_valid hold nothing
- * meaningful.  (tests/test_gpu_mog.py) */
+ * meaningful.  Where that call ran with shadow detection on (covahip_mog_set_shadows, a mode other than COVAHIP_MOG_SHADOWS_OFF)
+ * raw is OpenCV's three-valued mask, 0 / 127 / 255 with 127 = shadow, in _DROP and in _KEEP mode alike; filled is 0 / 1 as ever.
+ * (tests/test_gpu_mog.py, tests/test_gpu_mog_shadow.py) */
 struct covahip_mog;
 int covahip_dev_mog_masks(struct covahip_mog *m, uint8_t *raw, uint8_t *filled, size_t cap, int *n_frames);
 /* One stream's model: W f32 [5][P], V f32 [5][P], M f32 [5][3][P], nmodes u8 [P] and n (frames seen), P = work_w * work_h of

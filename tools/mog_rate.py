@@ -9,6 +9,8 @@
                                  (covahip_mog_create_any's kernels: any even size, beside the table's kernels where a size has both)
     python tools/mog_rate.py --grid macroblock --sizes 2560x1440 --labels corner,cover:1,count --no-host
                                  (the label modes side by side: one labeller each, timed call by call in turn)
+    python tools/mog_rate.py --sizes 1280x720 --streams 4 --frames 256 --shadows off,drop,keep --no-host
+                                 (shadow detection side by side: one labeller per mode, in the same turn-by-turn loop)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -20,7 +22,9 @@ numpy forward transform (BT.601, limited range), from tight 4:2:0 frames of 1.5 
 --general (macroblock grid) times the general kernels ("device_general": MogLabeler(force_general=True)) at any admitted size;
 at a size the table has too, the table's labeller ("device") is timed in the same process on the same frames, call by call in
 turn, so the two lines compare.  --labels lists label modes (corner, cover[:N], count): every device case is timed once per mode
-("device[cover:1]"), in the same turn-by-turn loop.
+("device[cover:1]"), in the same turn-by-turn loop.  --shadows lists shadow modes (off, drop[:TAU], keep[:TAU]) the same way
+("device[drop]"; with both lists every pair is a case); a line of a mode other than off has a "shadows" key and the clip's mean
+share of shadow and foreground pixels per frame, which is what the shadow test's cost depends on.
 """
 import argparse
 import json
@@ -83,9 +87,11 @@ def main():
     ap.add_argument("--no-host", action="store_true")
     ap.add_argument("--general", action="store_true", help="the general kernels (any even size of 256 .. 4096; implies --grid macroblock)")
     ap.add_argument("--labels", default="corner", help="label modes to time, comma-separated: corner, cover[:N], count")
+    ap.add_argument("--shadows", default="off", help="shadow modes to time, comma-separated: off, drop[:TAU], keep[:TAU]")
     a = ap.parse_args()
     try:
         label_modes = [(t, mog.parse_labels(t)) for t in a.labels.split(",")]
+        shadow_modes = [(t, mog.parse_shadows(t)) for t in a.shadows.split(",")]
     except argparse.ArgumentTypeError as e:
         ap.error(str(e))
     if a.general:
@@ -110,12 +116,15 @@ def main():
             labels = np.zeros((F, S) + (mog.label_dims_any(w, h) if a.general else mog.label_dims(w, h, a.grid)), np.uint8)
             # the labellers timed on the device, call by call in turn; the host case is the last one's
             cases = {}
-            for text, mode in label_modes:
-                tag = "" if text == "corner" else f"[{text}]"
-                if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
-                    cases["device" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, labels=mode)
-                if a.general:
-                    cases["device_general" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True, labels=mode)
+            for lt, lm in label_modes:
+                for st, sm in shadow_modes:
+                    tags = [t for t, plain in ((lt, "corner"), (st, "off")) if t != plain]
+                    tag = f"[{','.join(tags)}]" if tags else ""
+                    if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
+                        cases["device" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, labels=lm, shadows=sm)
+                    if a.general:
+                        cases["device_general" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True, labels=lm,
+                                                                       shadows=sm)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
 
@@ -151,6 +160,11 @@ def main():
                        "ms_per_call": round(med, 3), "frames_per_s": round(F * S / med * 1e3, 1), "ms_all": [round(x, 3) for x in ms[case]],
                        "kernel_ms": {k: round(v[0], 3) for k, v in prof.items() if k.startswith("mog_")},
                        "kernel_share_of_call": round(tot / med, 3) if med > 0 else None}
+                if m.shadows is not None:
+                    sh, fg = m.shadow_counts()
+                    npix = m.work_w * m.work_h
+                    rec.update(shadows=f"{m.shadows[0]}:{m.shadows[1]:g}", shadow_share=round(float(sh.mean()) / npix, 5),
+                               foreground_share=round(float(fg.mean()) / npix, 5))
                 print(json.dumps(rec), flush=True)
             ctx.free(d_f)
             ctx.free(d_l)
