@@ -1,25 +1,15 @@
 // MoG label generation (utils/generate-mog.py of the reference): per-pixel MOG2 background subtraction on a working image, then
 // close 4x4, open 6x6, hole fill and the ::8 subsample to the labels `tfrecordsink gt=` reads.  The arithmetic is stated in
 // include/covahip.h ("MoG labels"); tests/mog_ref.py is its numpy float32 restatement and the kernels match it bit for bit.
-// This file has the C-ABI and the kernels of the reference grid (every source resized to 640x360, 45x80 labels); the
-// macroblock grid's kernels (half-resolution working image) are mog_grid.hip and, for 1440p and 4K sources, mog_band.hip (the
-// post kernel in row bands); all three instantiate the device code of mog_dev.h.  covahip_mog_apply_yuv (NV12 / I420 surfaces at
-// the caller's pitch, offsets and strides) is checked and staged here and runs the update kernels of mog_yuv.hip.
-// covahip_mog_create_any (the macroblock grid at any even source size) makes a labeller that runs the kernels of mog_any.hip.
-// The update kernels themselves are templates of mog_update.h; with shadow detection on (covahip_mog_set_shadows) a call's update
-// launches go to their SHADOW instances in mog_shadow.hip, which also has the kernel behind covahip_mog_shadow_counts.
+// This file has the C-ABI and the host logic and no kernel: the geometries (the reference grid, every source resized to
+// 640x360 and 45x80 labels; the macroblock grid, half-resolution working image; covahip_mog_create_any, the macroblock grid at any
+// even source size), the checks and the staging of covahip_mog_apply and covahip_mog_apply_yuv (NV12 / I420 surfaces at the
+// caller's pitch, offsets and strides), and which kernels a call launches.  The update kernels are templates of mog_update.h,
+// instantiated in mog_update.hip and, for a call with shadow detection on (covahip_mog_set_shadows), in mog_shadow.hip, which
+// also has the kernel behind covahip_mog_shadow_counts; the post kernels are mog_post.hip's.  All of them run the device code of
+// mog_dev.h.
 //
-//   k_mog_update  one lane per working-size pixel and stream.  The five modes (weight, variance, mean) are read once per call
-//                 into registers, every frame of the call is applied to them, and they are written back once.  The source is
-//                 resized while it is read (copy, 2x2 mean or centre pick).  The foreground of a wave's 64 pixels (a row is
-//                 exactly ten waves wide) is one __ballot word: a frame's raw mask is 3,600 words, 28.8 KB.
-//   k_mog_post    one workgroup per (stream, frame): the bit plane in LDS, separable morphology on 64-bit words with shifts,
-//                 hole fill by seeding the background on the frame edge and propagating it (column sweeps + word-carry run
-//                 fill along rows) until a pass changes nothing, then the subsample (label_bit) or, in the label modes
-//                 COVAHIP_MOG_LABELS_COVER / _COUNT of covahip_mog_set_labels, the blocks' coverage (cover_labels).
-//
-// No contraction in this file (see mog_dev.h): every product and sum is rounded on its own, as the x86 builds of OpenCV
-// compute it, and the update kernel's ISA has no f32 fused multiply-add at all (DESIGN.md checks it).
+// No contraction in this file (see mog_dev.h); the arithmetic on the host, the learning rates, is in double.
 #pragma clang fp contract(off)
 
 #include <hip/hip_runtime.h>
@@ -39,40 +29,9 @@
 namespace {
 
 using namespace mogdev;
-using G = G640;                                // working size of the reference grid
-constexpr int MW = G::MW, ROWW = G::ROWW, NWORD = G::NWORD;
-constexpr int LW = G::LW, LH = G::LH, NLAB = G::NLAB;
-constexpr int POST_BLOCK = 256;
-static_assert(LW == COVAHIP_MOG_LABEL_W && LH == COVAHIP_MOG_LABEL_H && NLAB == NWORD, "geometry");
+static_assert(G640::LW == COVAHIP_MOG_LABEL_W && G640::LH == COVAHIP_MOG_LABEL_H, "the reference grid's geometry");
 // device budget for host frames staged per update launch (covahip_dev_mog_set_stage_budget changes it per labeller)
 constexpr size_t STAGE_BUDGET = (size_t)1 << 30;
-
-// bits: raw masks [F][S][3600]; filled_bits: the filled masks, same layout; labels [F][S][45][80]; mode, ncover: MogLabelArgs
-__global__ __launch_bounds__(POST_BLOCK) void k_mog_post(const unsigned long long *__restrict__ bits,
-                                                         unsigned long long *__restrict__ filled_bits, uint8_t *__restrict__ labels,
-                                                         const int32_t *__restrict__ nvalid, int S, int mode, int ncover) {
-    __shared__ unsigned long long A[NWORD], T[NWORD];
-    __shared__ int changed;
-    const int fs = blockIdx.x;
-    const int f = fs / S, s = fs % S;
-    if (f >= nvalid[s]) return;
-    const int tid = threadIdx.x;
-    const unsigned long long *src = bits + (size_t)fs * NWORD;
-    for (int i = tid; i < NWORD; i += POST_BLOCK) A[i] = src[i];
-    __syncthreads();
-    post_planes<G, POST_BLOCK>(A, T, &changed);
-    unsigned long long *dst = filled_bits + (size_t)fs * NWORD;
-    uint8_t *lab = labels + (size_t)fs * NLAB;
-    if (mode == COVAHIP_MOG_LABELS_CORNER) {
-        for (int i = tid; i < NWORD; i += POST_BLOCK) {
-            dst[i] = ~T[i];
-            lab[i] = label_bit(T, i / LW, i % LW, ROWW);   // NLAB == NWORD here
-        }
-    } else {
-        for (int i = tid; i < NWORD; i += POST_BLOCK) dst[i] = ~T[i];
-        cover_labels<POST_BLOCK>(T, lab, MW, G::MH, ROWW, mode, ncover);
-    }
-}
 
 // the highest band of the banded post kernel at working width mw: band_lds_bytes is linear in the staged rows (a window of 0
 // rows is its fixed part, of 1 row one row more), and a band stages HALO_UP + HALO_DOWN rows beside its own
@@ -94,11 +53,11 @@ struct covahip_mog {
     covahip_ctx *ctx = nullptr;
     covahip_mog_cfg cfg{};
     const MogGeomRow *row = nullptr;   // the (source size, grid) row of MOG_GEOMS, or &own
-    MogGeomRow own{};              // covahip_mog_create_any: this labeller's geometry, banded only, run by mog_any.hip
+    MogGeomRow own{};              // covahip_mog_create_any: this labeller's geometry, banded only, run by the general kernels
     bool any = false;
     MogDims alloc{};               // what the planes and the model are sized and laid out by: row->work, or with `any` its rows at
                                    // the pitch of mog_any_pitch
-    bool banded = false;           // the post kernel of mog_band.hip, where the row has it
+    bool banded = false;           // the banded post kernel, where the row has it
     int band_rows = 0;             // its band height; 0 = the automatic plan
     MogLabelArgs labels;           // covahip_mog_set_labels: how every post launch takes its labels
     int shadows = COVAHIP_MOG_SHADOWS_OFF;     // covahip_mog_set_shadows: every later apply call runs in this mode, with this tau
@@ -129,7 +88,7 @@ void free_mog(covahip_mog *m) {
     delete m;
 }
 
-// A checked covahip_mog_yuv: the surface as the kernels of mog_yuv.hip take it, and the bytes lo .. lo + ext of a frame that
+// A checked covahip_mog_yuv: the surface as the update kernels take it, and the bytes lo .. lo + ext of a frame that
 // hold its planes' rows (what a call from host memory stages per frame and stream).
 struct YuvPlan {
     int format = 0;
@@ -139,22 +98,12 @@ struct YuvPlan {
 
 // one update launch on device frames: BGR24 (yuv == nullptr) or the surfaces of `yuv`'s format as `src` describes them
 int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
-    covahip_ctx *ctx = m->ctx;
-    const int load = m->row->load;
-    if (a.shadows != COVAHIP_MOG_SHADOWS_OFF)  // the kernels' SHADOW instances, all of them in mog_shadow.hip
-        return covahip_mog_shadow_update(ctx, MogShadowRoute{m->any, yuv ? yuv->format : 0, load, m->row->work.mw, m->row->work.mh, m->row->resident},
-                                         d_frames, m->src_bytes, src, a);
-    if (m->any) {
-        const MogDims &w = m->row->work;
-        return yuv ? covahip_mog_any_yuv_update(ctx, yuv->format, w.mw, w.mh, d_frames, src, a)
-                   : covahip_mog_any_update(ctx, w.mw, w.mh, d_frames, m->src_bytes, a);
-    }
-    if (yuv) return covahip_mog_yuv_update(ctx, yuv->format, load, m->row->work.mw, d_frames, src, a);
-    if (m->row->work.mw != MW)             // the macroblock grid's other working sizes: the kernels beside the row's post kernels
-        return (m->row->resident ? covahip_mog_grid_update : covahip_mog_band_update)(ctx, m->row->work.mw, d_frames, m->src_bytes, a);
-    const auto kernel = load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY, false>
-                                              : (load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF, false> : k_mog_update<MOG_LOAD_PICK, false>);
-    return mog_launch_update<G>(ctx, "mog_update", kernel, d_frames, m->src_bytes, a);
+    if (yuv && yuv->format != COVAHIP_MOG_FMT_NV12 && yuv->format != COVAHIP_MOG_FMT_I420) return COVAHIP_ERR_INVALID_ARG;
+    const MogDims &w = m->row->work;
+    const MogRoute route{m->any, yuv ? yuv->format : 0, m->row->load, w.mw, w.mh, m->row->resident};
+    if (a.shadows == COVAHIP_MOG_SHADOWS_OFF) return mog_launch_route<false>(m->ctx, route, d_frames, m->src_bytes, src, a);
+    if (!a.shadow) return COVAHIP_ERR_INVALID_ARG;
+    return mog_launch_route<true>(m->ctx, route, d_frames, m->src_bytes, src, a);
 }
 
 // the post launch on the call's raw planes (m->bits): filled planes and labels of FS (frame, stream) pairs
@@ -166,15 +115,10 @@ int launch_post(covahip_mog *m, uint8_t *d_labels, const int32_t *d_nv, int S, s
         if (int rc = covahip_ensure_buffer(ctx, &m->plane, &m->plane_bytes, FS * m->alloc.nword() * 8)) return rc;
         int rows = m->band_rows, bands = 0;
         if (!rows) band_plan(m->alloc.mw, m->alloc.mh, &rows, &bands);
-        if (m->any)
-            return covahip_mog_any_post(ctx, m->row->work.mw, m->row->work.mh, bits, filled, static_cast<unsigned long long *>(m->plane),
-                                        d_labels, d_nv, S, FS, rows, m->labels);
-        return covahip_mog_band_post(ctx, m->row->work.mw, bits, filled, static_cast<unsigned long long *>(m->plane), d_labels, d_nv, S, FS,
-                                     rows, m->labels);
+        return covahip_mog_band_post(ctx, m->any, m->row->work.mw, m->row->work.mh, bits, filled, static_cast<unsigned long long *>(m->plane),
+                                     d_labels, d_nv, S, FS, rows, m->labels);
     }
-    if (m->row->work.mw != MW) return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS, m->labels);
-    return mog_launch(ctx, "mog_post", k_mog_post, dim3((unsigned)FS), POST_BLOCK, 0, bits, filled, d_labels, d_nv, S, m->labels.mode,
-                      m->labels.ncover);
+    return covahip_mog_grid_post(ctx, m->row->work.mw, bits, filled, d_labels, d_nv, S, FS, m->labels);
 }
 
 bool cfg_ok(const covahip_mog_cfg *cfg) {

@@ -1,16 +1,16 @@
-// Device code shared by the MoG label kernels of mog.hip (the reference grid: 640x360 working frames), mog_grid.hip (the
-// macroblock grid: half-resolution working frames) and mog_band.hip (the macroblock grid of 1440p and 4K sources, whose planes
-// are worked on in row bands): the MOG2 pixel update, the update kernel's body, and the morphology and
-// hole-fill passes of the post kernel, with the working geometry as a template parameter.  The arithmetic is stated in
-// include/covahip.h ("MoG labels").  mog_yuv.hip has the update kernels of all those geometries on NV12 / I420 surfaces, and
-// mog_any.hip the kernels of covahip_mog_create_any, whose geometry is an argument (it uses mog2_pixel and the loads of this
-// file and has runtime-width twins of the post passes).  There
-// is one update body (update_body_strided; update_body adapts a BGR24 load to it) and one set of morphology passes (the band
-// passes; the resident kernels run them on the whole frame).  Below the namespace is the host side the four files share: the
-// table of admitted geometries, Geom's runtime twin, the dispatch on the working width and the banded kernel's LDS formula.
+// Device code shared by the MoG label kernels, whatever their geometry (the reference grid: 640x360 working frames; the
+// macroblock grid: half-resolution working frames, those of 1440p and 4K sources worked on in row bands; covahip_mog_create_any:
+// the geometry as kernel arguments): the MOG2 pixel update and the shadow test, the update kernel's body and its loads, and the
+// post kernels' morphology and hole-fill passes.  The arithmetic is stated in include/covahip.h ("MoG labels").  There is one
+// update body for the table's geometries (update_body_strided; update_body adapts a BGR24 load to it; mog_update.h has the
+// kernels and the general sizes' update_any) and one set of post passes, which take the shape of a plane's rows as a policy
+// (FixedRows: a geometry of the table, all constants; AnyRows: values).  The resident post kernels run the passes on the whole
+// frame (post_planes), the banded ones band by band (post_banded, one driver for both row shapes); mog_post.hip has the kernels.
+// Below the namespace is the host side the files share: the table of admitted geometries, Geom's runtime twin, the dispatch on
+// the working width, the launch helpers and the post kernels' launch functions.
 //
-// No contraction in this code: every product and sum is rounded on its own, as the x86 builds of OpenCV compute it (both
-// translation units are also built with -ffp-contract=off).  The f32 divisions go through double: the f64 quotient is
+// No contraction in this code: every product and sum is rounded on its own, as the x86 builds of OpenCV compute it (every
+// translation unit that includes this is also built with -ffp-contract=off).  The f32 divisions go through double: the f64 quotient is
 // correctly rounded and 53 >= 2 * 24 + 2 bits, so rounding it to f32 gives the correctly rounded f32 quotient (double rounding
 // is innocuous for division at that width); unlike the f32 divide expansion this needs no f32 fused multiply-add, so the
 // update kernels' ISA has none at all (DESIGN.md checks it).
@@ -22,6 +22,7 @@
 #include <cfloat>
 #include <cstddef>
 #include <cstdint>
+#include <type_traits>
 #include <utility>
 #include <vector>
 
@@ -319,7 +320,7 @@ struct LoadHalf {
     }
 };
 
-// Working pixel (x, y) of an NV12 / I420 surface (mog_yuv.hip states the loads; mog_any.hip uses the HALF kind too).  KIND is how
+// Working pixel (x, y) of an NV12 / I420 surface (mog_update.h states the loads; the general kernels use the HALF kind too).  KIND is how
 // the working pixel comes from the source: YUV_HALF the 2x2 mean, YUV_COPY the pixel itself, YUV_PICK source pixel (3x + 1, 3y + 1).
 enum { YUV_HALF = 0, YUV_COPY = 1, YUV_PICK = 2 };
 
@@ -402,24 +403,64 @@ struct LoadYuv {
 };
 
 // ------------------------------------------------------------------------------------------------ post passes
+// The shape of a plane's rows as the passes see it: roww() words per row, of which the last holds the image in the bits of
+// tail(), in a frame mw() x mh().  Two models.  FixedRows: a working geometry of the table, everything a constant, the rows
+// full (tail() is all ones, so every expression on it folds away) and ROWW usable as an array bound.  AnyRows: the sizes as
+// values, of a labeller of covahip_mog_create_any, whose rows lie at a pitch of 64 roww pixels.  The bits at x >= mw of a row's
+// last word are outside the image:
+//   * every horizontal pass reads them as its neutral element (0 for dilate, 1 for erode) whatever the pass before left there;
+//     a vertical pass works column by column, so what it leaves there comes from there only;
+//   * the planes the banded driver writes (plane, filled_bits) have them clear;
+//   * for the fill they are wall: the band's copy of A in LDS has them set, so ~A, the background the fill walks through, has
+//     them clear; the seeds are the image's edge pixels, column mw - 1 on the right.
+template <int MW, int MH>
+struct FixedRows {
+    static constexpr bool FIXED = true;
+    static constexpr int ROWW = MW / 64;
+    static_assert(MW % 64 == 0, "full rows");
+    static constexpr int roww() { return ROWW; }
+    static constexpr int mw() { return MW; }
+    static constexpr int mh() { return MH; }
+    static constexpr unsigned long long tail() { return ~0ull; }
+};
+struct AnyRows {
+    static constexpr bool FIXED = false;
+    int roww_, mw_, mh_;
+    unsigned long long tail_;
+    __device__ __forceinline__ AnyRows(int mw, int mh)
+        : roww_((mw + 63) / 64), mw_(mw), mh_(mh), tail_((mw & 63) ? (1ull << (mw & 63)) - 1 : ~0ull) {}
+    __device__ __forceinline__ int roww() const { return roww_; }
+    __device__ __forceinline__ int mw() const { return mw_; }
+    __device__ __forceinline__ int mh() const { return mh_; }
+    __device__ __forceinline__ unsigned long long tail() const { return tail_; }
+};
+
 // Bit x of word w of a row is pixel 64 w + x.  A k x k window at x covers x - k/2 .. x + k - 1 - k/2 (OpenCV's anchor, the same
 // offsets for dilate and erode); outside the image is 0 for dilate and 1 for erode.  BLOCK = threads of the workgroup.
-// The passes work on a window of `nrows` whole rows of a frame ROWW words wide: the whole frame in the resident kernels (nrows
-// is G::MH there and folds away), a band and its halo in mog_band.hip (frames whose planes do not fit LDS).  That window is
+// The passes work on a window of `nrows` whole rows of a frame of shape `rs`: the whole frame in the resident kernels (nrows
+// is G::MH there and folds away), a band and its halo in the banded driver (frames whose planes do not fit LDS).  That window is
 // clipped to the frame, so a row beyond it is either outside the frame, where the neutral element is
 // what the pass wants, or a row of the frame that was not staged: then the neutral element is a stand-in, and the rows it
 // reaches (K/2 rows at the top, K - 1 - K/2 at the bottom of the window, per vertical pass) are not valid any more.  The
-// caller stages enough rows around its band for the valid region to end on the band.
-template <int ROWW, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void hpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
+// caller stages enough rows around its band for the valid region to end on the band.  nrows (N) is an int, or where the window
+// is the whole frame (post_planes) an integral_constant: those instances are then the resident kernels' own, with the height
+// a constant from the start, which the banded driver's instances of the same row shape would otherwise keep from them.
+template <int BLOCK, bool DIL, int K, class R, class N>
+__device__ __forceinline__ void hpass(R rs, const unsigned long long *in, unsigned long long *out, N nrows) {
     constexpr int A = K / 2, B = K - 1 - K / 2;
     constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    const int nword = nrows * ROWW;
+    const int roww = rs.roww();
+    const unsigned long long tail = rs.tail();
+    const int nword = nrows * roww;
     for (int i = threadIdx.x; i < nword; i += BLOCK) {
-        const int w = i % ROWW;
-        const unsigned long long c = in[i];
+        const int w = i % roww;
+        unsigned long long c = in[i];
         const unsigned long long pv = w > 0 ? in[i - 1] : NEU;
-        const unsigned long long nx = w < ROWW - 1 ? in[i + 1] : NEU;
+        unsigned long long nx = w < roww - 1 ? in[i + 1] : NEU;
+        if constexpr (!R::FIXED) {     // the last word's bits beyond the image read as the neutral element (w - 1 is never the last word)
+            if (w == roww - 1) c = DIL ? c & tail : c | ~tail;
+            if (w == roww - 2) nx = DIL ? nx & tail : nx | ~tail;
+        }
         unsigned long long r = c;
 #pragma unroll
         for (int d = -A; d <= B; d++) {
@@ -431,50 +472,51 @@ __device__ __forceinline__ void hpass_band(const unsigned long long *in, unsigne
     }
 }
 
-template <int ROWW, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void vpass_band(const unsigned long long *in, unsigned long long *out, int nrows) {
+template <int BLOCK, bool DIL, int K, class R, class N>
+__device__ __forceinline__ void vpass(R rs, const unsigned long long *in, unsigned long long *out, N nrows) {
     constexpr int A = K / 2, B = K - 1 - K / 2;
     constexpr unsigned long long NEU = DIL ? 0ull : ~0ull;
-    const int nword = nrows * ROWW;
+    const int roww = rs.roww();
+    const int nword = nrows * roww;
     for (int i = threadIdx.x; i < nword; i += BLOCK) {
-        const int y = i / ROWW;
+        const int y = i / roww;
         unsigned long long r = in[i];
 #pragma unroll
         for (int d = -A; d <= B; d++) {
             if (d == 0) continue;
-            const unsigned long long v = (y + d >= 0 && y + d < nrows) ? in[i + d * ROWW] : NEU;
+            const unsigned long long v = (y + d >= 0 && y + d < nrows) ? in[i + d * roww] : NEU;
             r = DIL ? (r | v) : (r & v);
         }
         out[i] = r;
     }
 }
 
-// one separable dilate (DIL) or erode K x K of the window in X (LDS, nrows x ROWW words, behind a barrier) through Y (the same
+// one separable dilate (DIL) or erode K x K of the window in X (LDS, nrows x roww words, behind a barrier) through Y (the same
 // size); the result is in X, behind a barrier
-template <int ROWW, int BLOCK, bool DIL, int K>
-__device__ __forceinline__ void morph_pass(unsigned long long *X, unsigned long long *Y, int nrows) {
-    hpass_band<ROWW, BLOCK, DIL, K>(X, Y, nrows);
+template <int BLOCK, bool DIL, int K, class R, class N>
+__device__ __forceinline__ void morph_pass(R rs, unsigned long long *X, unsigned long long *Y, N nrows) {
+    hpass<BLOCK, DIL, K>(rs, X, Y, nrows);
     __syncthreads();
-    vpass_band<ROWW, BLOCK, DIL, K>(Y, X, nrows);
+    vpass<BLOCK, DIL, K>(rs, Y, X, nrows);
     __syncthreads();
 }
 
 // close 4x4 and open 6x6 of the window in X, with Y as the other plane of the ping-pong.  Of the result's rows, 10 at the top
 // and 6 at the bottom are valid only where the window ends on the frame edge.
-template <int ROWW, int BLOCK>
-__device__ __forceinline__ void morph_band(unsigned long long *X, unsigned long long *Y, int nrows) {
-    morph_pass<ROWW, BLOCK, true, 4>(X, Y, nrows);
-    morph_pass<ROWW, BLOCK, false, 4>(X, Y, nrows);
-    morph_pass<ROWW, BLOCK, false, 6>(X, Y, nrows);
-    morph_pass<ROWW, BLOCK, true, 6>(X, Y, nrows);
+template <int BLOCK, class R, class N>
+__device__ __forceinline__ void morph_band(R rs, unsigned long long *X, unsigned long long *Y, N nrows) {
+    morph_pass<BLOCK, true, 4>(rs, X, Y, nrows);
+    morph_pass<BLOCK, false, 4>(rs, X, Y, nrows);
+    morph_pass<BLOCK, false, 6>(rs, X, Y, nrows);
+    morph_pass<BLOCK, true, 6>(rs, X, Y, nrows);
 }
 
-// the hole fill's seed in word w of row y of a frame mh rows high: the frame's edge pixels
-template <int ROWW>
-__device__ __forceinline__ unsigned long long edge_seed(int y, int w, int mh) {
-    unsigned long long edge = (y == 0 || y == mh - 1) ? ~0ull : 0ull;
+// the hole fill's seed in word w of row y: the image's edge pixels, rows 0 and mh - 1, columns 0 and mw - 1
+template <class R>
+__device__ __forceinline__ unsigned long long edge_seed(R rs, int y, int w) {
+    unsigned long long edge = (y == 0 || y == rs.mh() - 1) ? ~0ull : 0ull;
     if (w == 0) edge |= 1ull;
-    if (w == ROWW - 1) edge |= 1ull << 63;
+    if (w == rs.roww() - 1) edge = (edge | 1ull << ((rs.mw() - 1) & 63)) & rs.tail();
     return edge;
 }
 
@@ -528,10 +570,11 @@ __device__ __forceinline__ void cover_labels(const unsigned long long *T, uint8_
 template <class G, int BLOCK>
 __device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long long *T, int *changed) {
     constexpr int ROWW = G::ROWW, NWORD = G::NWORD, MH = G::MH;
+    constexpr FixedRows<G::MW, MH> rs;
     const int tid = threadIdx.x;
-    morph_band<ROWW, BLOCK>(A, T, MH);         // close 4x4, open 6x6 (separable) on the whole frame
+    morph_band<BLOCK>(rs, A, T, std::integral_constant<int, MH>{});   // close 4x4, open 6x6 (separable) on the whole frame
     // hole fill: T = background reached from the frame edge through 4-connected background (~A)
-    for (int i = tid; i < NWORD; i += BLOCK) T[i] = ~A[i] & edge_seed<ROWW>(i / ROWW, i % ROWW, MH);
+    for (int i = tid; i < NWORD; i += BLOCK) T[i] = ~A[i] & edge_seed(rs, i / ROWW, i % ROWW);
     for (;;) {
         if (tid == 0) *changed = 0;
         __syncthreads();
@@ -606,22 +649,24 @@ __device__ __forceinline__ void post_planes(unsigned long long *A, unsigned long
 // OR, so every lane first sweeps its own segment with nothing carried in and notes what leaves the segment (`out`) and which
 // columns are background in all of its rows (`pass`: what a carry would cross the segment through); the carry into a segment
 // then follows from the segments before it, and a second walk ORs in what the carry reaches, ending where it is blocked.  The
-// result is that of one lane walking the whole column.  carry: LDS, 2 x FILL_SEG x ROWW words; all threads call this.
+// result is that of one lane walking the whole column.  carry: LDS, 2 x FILL_SEG x roww words; all threads call this, and
+// roww x FILL_SEG of them have a segment.
 constexpr int FILL_SEG = 16;
-template <int ROWW, bool DOWN>
-__device__ __forceinline__ bool col_sweep_band(const unsigned long long *A, unsigned long long *T, int nrows,
-                                               unsigned long long *carry) {
+template <bool DOWN, class R>
+__device__ __forceinline__ bool col_sweep(R rs, const unsigned long long *A, unsigned long long *T, int nrows,
+                                          unsigned long long *carry) {
+    const int roww = rs.roww();
     const int tid = threadIdx.x;
-    const bool active = tid < ROWW * FILL_SEG;
-    const int w = tid % ROWW, sg = tid / ROWW;
+    const bool active = tid < roww * FILL_SEG;
+    const int w = tid % roww, sg = tid / roww;
     const int len = (nrows + FILL_SEG - 1) / FILL_SEG;
     const int ya = sg * len < nrows ? sg * len : nrows, yb = ya + len < nrows ? ya + len : nrows;   // this lane's rows (may be none)
-    unsigned long long *out = carry, *pass = carry + FILL_SEG * ROWW;
+    unsigned long long *out = carry, *pass = carry + FILL_SEG * roww;
     bool ch = false;
     if (active) {
         unsigned long long r = 0, p = ~0ull;
         for (int k = 0; k < yb - ya; k++) {
-            const int i = (DOWN ? ya + k : yb - 1 - k) * ROWW + w;
+            const int i = (DOWN ? ya + k : yb - 1 - k) * roww + w;
             const unsigned long long na = ~A[i], old = T[i], nw = old | (na & r);
             if (nw != old) {
                 T[i] = nw;
@@ -637,11 +682,11 @@ __device__ __forceinline__ bool col_sweep_band(const unsigned long long *A, unsi
     if (active) {
         unsigned long long d = 0;                      // what the segments walked before this one carry into it
         if (DOWN)
-            for (int k = 0; k < sg; k++) d = out[k * ROWW + w] | (pass[k * ROWW + w] & d);
+            for (int k = 0; k < sg; k++) d = out[k * roww + w] | (pass[k * roww + w] & d);
         else
-            for (int k = FILL_SEG - 1; k > sg; k--) d = out[k * ROWW + w] | (pass[k * ROWW + w] & d);
+            for (int k = FILL_SEG - 1; k > sg; k--) d = out[k * roww + w] | (pass[k * roww + w] & d);
         for (int k = 0; k < yb - ya && d; k++) {
-            const int i = (DOWN ? ya + k : yb - 1 - k) * ROWW + w;
+            const int i = (DOWN ? ya + k : yb - 1 - k) * roww + w;
             d &= ~A[i];
             const unsigned long long old = T[i], nw = old | d;
             if (nw != old) {
@@ -654,52 +699,96 @@ __device__ __forceinline__ bool col_sweep_band(const unsigned long long *A, unsi
     return ch;
 }
 
-// The two-phase loop of post_planes on a band: T (LDS, nrows x ROWW words, seeded by the caller, behind a barrier) grows
+// The banded post kernel's dynamic LDS at band height `rows` (post_banded lays it out, mog_post.hip sizes its launch with this, mog.hip
+// plans and validates band heights with it): the flags (fill loop, seeds of a visit, sweep), the column sweep's carries, then
+// two windows of a band and its halo, clipped to the frame.  The morphology stage is the larger of the two stages; the fill
+// needs only 2 x rows.
+constexpr int HALO_UP = 10, HALO_DOWN = 6;     // rows of input above / below an output row of close 4x4 + open 6x6
+constexpr size_t BAND_FLAG_BYTES = 16;
+constexpr size_t band_carry_bytes(int roww) { return (size_t)2 * FILL_SEG * roww * 8; }
+constexpr size_t band_lds_bytes(int mw, int mh, int rows) {
+    const int win = rows + HALO_UP + HALO_DOWN < mh ? rows + HALO_UP + HALO_DOWN : mh;
+    return BAND_FLAG_BYTES + band_carry_bytes(mw / 64) + (size_t)2 * win * (mw / 64) * 8;
+}
+
+// The two-phase loop of post_planes on a band: T (LDS, nrows x roww words, seeded by the caller, behind a barrier) grows
 // through the background ~A (LDS, the same size) until nothing changes.  Returns whether T changed at all (the same value in
-// every thread); ends behind a barrier.  The column sweep runs on FILL_SEG row segments per column (above).  The row fill keeps
-// the row in 2 x ROWW words per lane: the pass towards higher x adds what it reaches to the seeds of the pass towards lower x,
-// which fills the same runs as two passes from the same seeds.
-template <int ROWW, int BLOCK>
-__device__ __forceinline__ bool fill_band(const unsigned long long *A, unsigned long long *T, int nrows, int *changed,
+// every thread); ends behind a barrier.  The column sweep runs on FILL_SEG row segments per column (above).  The row fill has two
+// bodies that differ in where the row lives.  With ROWW a constant it is 2 x ROWW words in the lane's registers: the pass
+// towards higher x adds what it reaches to the seeds of the pass towards lower x, which fills the same runs as two passes from
+// the same seeds.  Otherwise it works on T in LDS word by word: the pass towards higher x leaves the seeds and what they
+// reached in T, the pass towards lower x starts from that.
+template <int BLOCK, class R>
+__device__ __forceinline__ bool fill_band(R rs, const unsigned long long *A, unsigned long long *T, int nrows, int *changed,
                                           unsigned long long *carry) {
-    static_assert(ROWW * FILL_SEG <= BLOCK, "one lane per word column and row segment");
+    if constexpr (R::FIXED) static_assert(R::ROWW * FILL_SEG <= BLOCK, "one lane per word column and row segment");
     const int tid = threadIdx.x;
     bool any = false;
     for (;;) {
         if (tid == 0) *changed = 0;
         __syncthreads();
         // vertical: down, then up (each ends behind a barrier)
-        const bool chd = col_sweep_band<ROWW, true>(A, T, nrows, carry);
-        const bool chu = col_sweep_band<ROWW, false>(A, T, nrows, carry);
+        const bool chd = col_sweep<true>(rs, A, T, nrows, carry);
+        const bool chu = col_sweep<false>(rs, A, T, nrows, carry);
         if (chd || chu) *changed = 1;
         // horizontal: one lane per row fills every background run that holds a reached pixel, carrying across words
         for (int y = tid; y < nrows; y += BLOCK) {
-            unsigned long long m[ROWW], sd[ROWW];
-#pragma unroll
-            for (int w = 0; w < ROWW; w++) {
-                m[w] = ~A[y * ROWW + w];
-                sd[w] = T[y * ROWW + w];
-            }
-            unsigned long long c = 0;
-#pragma unroll
-            for (int w = 0; w < ROWW; w++) {           // towards higher x: m + seeds ripples through each seeded run
-                const unsigned long long s1 = sd[w] | (c & m[w] & 1ull);
-                const unsigned long long t = m[w] + s1;
-                sd[w] = ((t ^ m[w]) | s1) & m[w];       // the seeds and what they reached: a superset of sd[w]
-                c = t < m[w] ? 1ull : 0ull;           // carried out of bit 63: the run goes on in the next word
-            }
-            c = 0;
             bool ch = false;
+            unsigned long long c = 0;
+            if constexpr (R::FIXED) {
+                constexpr int ROWW = R::ROWW;
+                unsigned long long m[ROWW], sd[ROWW];
 #pragma unroll
-            for (int w = ROWW - 1; w >= 0; w--) {      // towards lower x: the same on bit-reversed words
-                const unsigned long long rm = __builtin_bitreverse64(m[w]);
-                const unsigned long long s1 = __builtin_bitreverse64(sd[w]) | (c & rm & 1ull);
-                const unsigned long long t = rm + s1;
-                const unsigned long long nw = __builtin_bitreverse64(((t ^ rm) | s1) & rm);
-                c = t < rm ? 1ull : 0ull;
-                if (nw != T[y * ROWW + w]) {
-                    T[y * ROWW + w] = nw;
-                    ch = true;
+                for (int w = 0; w < ROWW; w++) {
+                    m[w] = ~A[y * ROWW + w];
+                    sd[w] = T[y * ROWW + w];
+                }
+#pragma unroll
+                for (int w = 0; w < ROWW; w++) {           // towards higher x: m + seeds ripples through each seeded run
+                    const unsigned long long s1 = sd[w] | (c & m[w] & 1ull);
+                    const unsigned long long t = m[w] + s1;
+                    sd[w] = ((t ^ m[w]) | s1) & m[w];       // the seeds and what they reached: a superset of sd[w]
+                    c = t < m[w] ? 1ull : 0ull;           // carried out of bit 63: the run goes on in the next word
+                }
+                c = 0;
+#pragma unroll
+                for (int w = ROWW - 1; w >= 0; w--) {      // towards lower x: the same on bit-reversed words
+                    const unsigned long long rm = __builtin_bitreverse64(m[w]);
+                    const unsigned long long s1 = __builtin_bitreverse64(sd[w]) | (c & rm & 1ull);
+                    const unsigned long long t = rm + s1;
+                    const unsigned long long nw = __builtin_bitreverse64(((t ^ rm) | s1) & rm);
+                    c = t < rm ? 1ull : 0ull;
+                    if (nw != T[y * ROWW + w]) {
+                        T[y * ROWW + w] = nw;
+                        ch = true;
+                    }
+                }
+            } else {
+                const int roww = rs.roww();
+                const unsigned long long *a = A + y * roww;
+                unsigned long long *t = T + y * roww;
+                for (int w = 0; w < roww; w++) {           // towards higher x
+                    const unsigned long long m = ~a[w], sd = t[w];
+                    const unsigned long long s1 = sd | (c & m & 1ull);
+                    const unsigned long long r = m + s1;
+                    const unsigned long long nw = ((r ^ m) | s1) & m;     // a superset of sd
+                    c = r < m ? 1ull : 0ull;
+                    if (nw != sd) {
+                        t[w] = nw;
+                        ch = true;
+                    }
+                }
+                c = 0;
+                for (int w = roww - 1; w >= 0; w--) {      // towards lower x
+                    const unsigned long long rm = __builtin_bitreverse64(~a[w]), sd = t[w];
+                    const unsigned long long s1 = __builtin_bitreverse64(sd) | (c & rm & 1ull);
+                    const unsigned long long r = rm + s1;
+                    const unsigned long long nw = __builtin_bitreverse64(((r ^ rm) | s1) & rm);
+                    c = r < rm ? 1ull : 0ull;
+                    if (nw != sd) {
+                        t[w] = nw;
+                        ch = true;
+                    }
                 }
             }
             if (ch) *changed = 1;
@@ -713,16 +802,100 @@ __device__ __forceinline__ bool fill_band(const unsigned long long *A, unsigned 
     return any;
 }
 
-// The banded post kernel's dynamic LDS at band height `rows` (mog_band.hip lays it out and sizes its launch with this, mog.hip
-// plans and validates band heights with it): the flags (fill loop, seeds of a visit, sweep), the column sweep's carries, then
-// two windows of a band and its halo, clipped to the frame.  The morphology stage is the larger of the two stages; the fill
-// needs only 2 x rows.
-constexpr int HALO_UP = 10, HALO_DOWN = 6;     // rows of input above / below an output row of close 4x4 + open 6x6
-constexpr size_t BAND_FLAG_BYTES = 16;
-constexpr size_t band_carry_bytes(int roww) { return (size_t)2 * FILL_SEG * roww * 8; }
-constexpr size_t band_lds_bytes(int mw, int mh, int rows) {
-    const int win = rows + HALO_UP + HALO_DOWN < mh ? rows + HALO_UP + HALO_DOWN : mh;
-    return BAND_FLAG_BYTES + band_carry_bytes(mw / 64) + (size_t)2 * win * (mw / 64) * 8;
+// The banded post kernels' body (mog_post.hip states the three stages), by all BLOCK threads of the workgroup of one (frame,
+// stream) pair on a frame of shape `rs`.  bits: raw masks [F][S][roww mh]; filled_bits: the filled masks, same layout (T while the
+// fill runs); plane: the mask after the morphology, same layout; labels [F][S][lh][lw]; rows: band height, >= 1; mode, ncover:
+// MogLabelArgs.  smem: the workgroup's dynamic LDS, band_lds_bytes(64 roww, mh, rows).
+template <int BLOCK, class R>
+__device__ __forceinline__ void post_banded(R rs, uint8_t *smem, const unsigned long long *__restrict__ bits,
+                                            unsigned long long *filled_bits, unsigned long long *plane, uint8_t *__restrict__ labels,
+                                            const int32_t *__restrict__ nvalid, int S, int rows, int mode, int ncover) {
+    const int roww = rs.roww(), mw = rs.mw(), mh = rs.mh();
+    const int nword = roww * mh, lw = (mw + 7) / 8, nlab = lw * ((mh + 7) / 8);
+    const unsigned long long tail = rs.tail();
+    // the layout band_lds_bytes sizes: flags ([0] fill loop, [1] a visit's seeds, [2] the sweep), carries, two windows
+    int *flags = reinterpret_cast<int *>(smem);
+    unsigned long long *carry = reinterpret_cast<unsigned long long *>(smem + BAND_FLAG_BYTES);
+    unsigned long long *P = reinterpret_cast<unsigned long long *>(smem + BAND_FLAG_BYTES + band_carry_bytes(roww));
+    const int fs = blockIdx.x;
+    const int f = fs / S, s = fs % S;
+    if (f >= nvalid[s]) return;
+    const int tid = threadIdx.x;
+    const unsigned long long *src = bits + (size_t)fs * nword;
+    unsigned long long *Ag = plane + (size_t)fs * nword, *Tg = filled_bits + (size_t)fs * nword;
+    const int nb = (mh + rows - 1) / rows;
+
+    // 1. morphology: close 4x4, open 6x6 on the band and its halo, clipped to the frame
+    for (int b = 0; b < nb; b++) {
+        const int y0 = b * rows, y1 = y0 + rows < mh ? y0 + rows : mh;
+        const int lo = y0 - HALO_UP > 0 ? y0 - HALO_UP : 0, hi = y1 + HALO_DOWN < mh ? y1 + HALO_DOWN : mh;
+        const int n = hi - lo;
+        unsigned long long *X = P, *Y = P + n * roww;
+        for (int i = tid; i < n * roww; i += BLOCK) X[i] = src[lo * roww + i];
+        __syncthreads();
+        morph_band<BLOCK>(rs, X, Y, n);
+        for (int i = tid; i < (y1 - y0) * roww; i += BLOCK) {
+            const int gi = y0 * roww + i;
+            const unsigned long long a = X[(y0 - lo) * roww + i] & (gi % roww == roww - 1 ? tail : ~0ull);
+            Ag[gi] = a;
+            Tg[gi] = ~a & edge_seed(rs, gi / roww, gi % roww);
+        }
+        __syncthreads();                                   // X is free for the next band; A and T are visible
+    }
+
+    // 2. hole fill: sweeps over the bands, down then up, until one changes nothing
+    for (bool first = true;; first = false) {
+        if (tid == 0) flags[2] = 0;                        // (every visit starts with a barrier)
+        for (int v = 0; v < 2 * nb - 1; v++) {
+            const int b = v < nb ? v : 2 * nb - 2 - v;
+            const int y0 = b * rows, y1 = y0 + rows < mh ? y0 + rows : mh;
+            const int n = y1 - y0;
+            if (tid == 0) flags[1] = 0;
+            __syncthreads();
+            // what the neighbouring bands' adjacent rows add to this band's first and last row (T has no bit beyond the image)
+            unsigned long long st = 0, sb = 0;
+            if (tid < roww) {
+                if (y0 > 0) st = ~Ag[y0 * roww + tid] & Tg[(y0 - 1) * roww + tid] & ~Tg[y0 * roww + tid];
+                if (y1 < mh) sb = ~Ag[(y1 - 1) * roww + tid] & Tg[y1 * roww + tid] & ~Tg[(y1 - 1) * roww + tid];
+                if (st | sb) flags[1] = 1;
+            }
+            __syncthreads();
+            const bool seeded = flags[1] != 0;
+            __syncthreads();                               // (the next visit clears the flag)
+            // a band visited before is at its own fixed point: without new seeds there is nothing to do in it
+            if (!(seeded || (first && v < nb))) continue;
+            unsigned long long *A = P, *T = P + n * roww;
+            for (int i = tid; i < n * roww; i += BLOCK) {
+                A[i] = Ag[y0 * roww + i] | (i % roww == roww - 1 ? ~tail : 0ull);   // beyond the image is wall
+                T[i] = Tg[y0 * roww + i];
+            }
+            __syncthreads();
+            if (tid < roww) {
+                T[tid] |= st;
+                T[(n - 1) * roww + tid] |= sb;
+            }
+            const bool grew = fill_band<BLOCK>(rs, A, T, n, &flags[0], carry);   // (starts and ends with a barrier)
+            if (seeded || grew) {
+                for (int i = tid; i < n * roww; i += BLOCK) Tg[y0 * roww + i] = T[i];
+                if (tid == 0) flags[2] = 1;
+            }
+        }
+        __syncthreads();
+        const int again = flags[2];
+        __syncthreads();
+        if (!again) break;
+    }
+
+    // 3. labels from T (the bits beyond the image are still clear in it: cover_labels masks them itself), then filled = ~T
+    // inside the image, in place
+    uint8_t *lab = labels + (size_t)fs * nlab;
+    if (mode == COVAHIP_MOG_LABELS_CORNER) {
+        for (int i = tid; i < nlab; i += BLOCK) lab[i] = label_bit(Tg, i / lw, i % lw, roww);
+    } else {
+        cover_labels<BLOCK>(Tg, lab, mw, mh, roww, mode, ncover);
+    }
+    __syncthreads();
+    for (int i = tid; i < nword; i += BLOCK) Tg[i] = ~Tg[i] & (i % roww == roww - 1 ? tail : ~0ull);
 }
 
 }  // namespace mogdev
@@ -753,8 +926,8 @@ static_assert(mog_dims_match<mogdev::G320>() && mog_dims_match<mogdev::G640>() &
               "MogDims restates Geom");
 
 // The admitted (source size, grid) pairs: the working size, how the update kernel loads a working pixel, and which forms of
-// the post kernel exist there (resident: both planes in LDS, mog.hip at 640 wide and mog_grid.hip; banded: mog_band.hip) with
-// the one a new labeller starts in.  Where the resident form does not exist the update kernel is mog_band.hip's too.  The
+// the post kernel exist there (resident: both planes in LDS; banded) with the one a new labeller starts in.  Where the resident
+// form does not exist the update launch's profile scope is mog_band_update.  The
 // macroblock grid works at half the source, so 1280x720 is the reference grid's row there and runs the same kernels.
 enum { MOG_LOAD_COPY = 0, MOG_LOAD_HALF = 1, MOG_LOAD_PICK = 2 };
 struct MogGeomRow {
@@ -829,31 +1002,19 @@ int mog_launch_update(covahip_ctx *ctx, const char *scope, K kernel, const uint8
                       a.nvalid, a.f0, a.nf, a.S, a.Tb, a.bits, mog_shadow_dev(a));
 }
 
-// The macroblock grid's kernels at working width `mw` (960 or 320; 640 runs mog.hip's own).  Pointers are device memory, the
-// layouts those of the kernels above; the launches go to ctx->stream and return without waiting.
-int covahip_mog_grid_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
+// The post kernels (mog_post.hip).  Pointers are device memory, the layouts those of the kernels above; the launches go to
+// ctx->stream and return without waiting.
+// The resident form at working width `mw` (640, 960 or 320): both planes in LDS.
 int covahip_mog_grid_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
                           uint8_t *labels, const int32_t *nvalid, int S, size_t FS, MogLabelArgs la);
-// The banded kernels (mog_band.hip) at working width `mw`: 1280 and 1920, whose planes do not fit LDS, and 960 (the post
-// kernel only, for comparison with the resident one).  plane: one more plane per (frame, stream), FS * NWORD words, for the
-// mask after the morphology; rows: the band height, 16 .. working height, with mogdev::band_lds_bytes within
+// The banded form.  Of the table at working width `mw`: 1280 and 1920, whose planes do not fit LDS, and 960 (for comparison
+// with the resident one).  With `any` the general kernel: the macroblock grid at any working size mw x mh, 128 <= mw, mh <= 2048,
+// as arguments of the kernel; rows of the planes and of the model then lie at a pitch of mog_any_pitch(mw) pixels, so the sizes
+// of a labeller's buffers are those of MogDims{mog_any_pitch(mw), mh}.  plane: one more plane per (frame, stream), FS * NWORD
+// words, for the mask after the morphology; rows: the band height, 16 .. mh, with mogdev::band_lds_bytes (at the pitch) within
 // COVAHIP_MOG_BAND_LDS_MAX (else COVAHIP_ERR_UNSUPPORTED).
 constexpr size_t COVAHIP_MOG_BAND_LDS_MAX = 160 * 1024 - 64;
-int covahip_mog_band_update(covahip_ctx *ctx, int mw, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
-int covahip_mog_band_post(covahip_ctx *ctx, int mw, const unsigned long long *bits, unsigned long long *filled_bits,
+constexpr int mog_any_pitch(int mw) { return (mw + 63) / 64 * 64; }
+int covahip_mog_band_post(covahip_ctx *ctx, bool any, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,
                           unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
                           MogLabelArgs la);
-// The update kernels on NV12 / I420 surfaces (mog_yuv.hip), all seven working geometries, on a covahip_mog_yuv_src (above).
-// load: MOG_LOAD_* of the labeller's row (copy and centre pick exist at working width 640 only)
-int covahip_mog_yuv_update(covahip_ctx *ctx, int format, int load, int mw, const uint8_t *frames, const covahip_mog_yuv_src &src,
-                           const MogUpdateArgs &a);
-// The general kernels (mog_any.hip): the macroblock grid at any working size mw x mh, 128 <= mw, mh <= 2048, as arguments of the
-// kernels.  Rows of the planes and of the model lie at a pitch of mog_any_pitch(mw) pixels, so the sizes of a labeller's buffers
-// are those of MogDims{mog_any_pitch(mw), mh}.  plane and rows as for covahip_mog_band_post, with band_lds_bytes at the pitch.
-constexpr int mog_any_pitch(int mw) { return (mw + 63) / 64 * 64; }
-int covahip_mog_any_update(covahip_ctx *ctx, int mw, int mh, const uint8_t *frames, size_t src_bytes, const MogUpdateArgs &a);
-int covahip_mog_any_yuv_update(covahip_ctx *ctx, int format, int mw, int mh, const uint8_t *frames, const covahip_mog_yuv_src &src,
-                               const MogUpdateArgs &a);
-int covahip_mog_any_post(covahip_ctx *ctx, int mw, int mh, const unsigned long long *bits, unsigned long long *filled_bits,
-                         unsigned long long *plane, uint8_t *labels, const int32_t *nvalid, int S, size_t FS, int rows,
-                         MogLabelArgs la);

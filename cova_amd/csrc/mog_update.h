@@ -1,16 +1,42 @@
-// The update kernels of the MoG labeller, all six, as templates over `bool SHADOW` (mog_dev.h: update_body_strided, shadow_pixel):
-//   k_mog_update          the reference grid's 640x360 working frames (launched by mog.hip)
-//   k_mog_grid_update     the macroblock grid's resident sizes (mog_grid.hip)
-//   k_mog_band_update     its 1440p and 4K sizes (mog_band.hip)
-//   k_mog_yuv_update      all of those on NV12 / I420 surfaces (mog_yuv.hip)
-//   k_mog_any_update, k_mog_any_yuv_update   any size, the geometry as arguments (mog_any.hip)
-// Each of those files instantiates and launches the SHADOW = false kernels, which are instruction for instruction the kernels
-// from before the shadow test existed; mog_shadow.hip instantiates and launches the SHADOW = true ones (covahip_mog_set_shadows
-// in a mode other than OFF).  The files' heads describe the kernels.
+// The update kernels of the MoG labeller, all five, as templates over `bool SHADOW` (mog_dev.h: update_body_strided, shadow_pixel),
+// and the one dispatch among them (mog_launch_route):
+//   k_mog_update          the reference grid's 640x360 working frames: one lane per working-size pixel and stream.  The five
+//                         modes (weight, variance, mean) are read once per call into registers, every frame of the call is
+//                         applied to them, and they are written back once.  The source is resized while it is read (copy,
+//                         2x2 mean or centre pick).  The foreground of a wave's 64 pixels (a row is exactly ten waves wide) is
+//                         one __ballot word: a frame's raw mask is 3,600 words, 28.8 KB.
+//   k_mog_grid_update     the macroblock grid's other working sizes (half the source: the 2x2 mean of LoadHalf): 960x540 and
+//                         320x180, and 1280x720 and 1920x1080 of 1440p and 4K sources.  A row is 15, 5, 20 or 30 waves wide, so
+//                         a wave's ballot is still one word of the plane.
+//   k_mog_yuv_update      all of those on NV12 / I420 surfaces that lie at a row pitch, plane offsets and frame / stream strides
+//                         of the caller's (covahip_mog_apply_yuv; include/covahip.h, "MoG labels", states the conversion):
+//                         update_body_strided with LoadYuv of mog_dev.h, whose WAIT makes it wait once before its loop.  KIND
+//                         is how the working pixel comes from the source:
+//     HALF  (the macroblock grid's half sizes and 1280x720 on either grid) a 16-bit word at byte 2x of Y rows 2y and 2y + 1 and,
+//           NV12, a 16-bit word at byte 2x of UV row y: three loads of 128 contiguous bytes per wave.  I420 loads one byte each
+//           of U and V at x of row y.  The four pixels of the 2x2 block share the chroma sample; each is converted, then the
+//           rounded mean per channel.
+//     COPY  (640x360 on the reference grid) the Y byte at (x, y) and the chroma sample at (x >> 1, y >> 1).
+//     PICK  (1920x1080 on the reference grid) the same at source pixel (3x + 1, 3y + 1).
+//                         The functor hands back the raw words; they become a pixel where mog2_pixel consumes it, so the loads
+//                         of frame f + 1 are in flight across frame f's update.  The range (limited / full) is six integers
+//                         passed by value, not a template axis.
+//   k_mog_any_update, k_mog_any_yuv_update   any size (covahip_mog_create_any), the geometry as arguments: the update body with
+//                         runtime sizes (update_any).  Everything per pixel lies on the padded pitch of 64 roww, roww =
+//                         ceil(mw / 64): pixel (x, y) is lane p = y * 64 roww + x of the update grid and entry p of the model's
+//                         arrays (W[5][P], V[5][P], M[5][3][P] f32, nmodes[P] u8 with P = 64 roww mh, as Geom lays them out at its
+//                         NPIX).  A wave is 64 consecutive x of one padded row, so its ballot is one plane word.  Lanes at
+//                         x >= mw load nothing, keep no model and ballot 0; the last block may be partial (P is a multiple of 64,
+//                         not of 256).  BGR24 (LoadHalfAny) and, with LoadYuv<.., HALF>, NV12 / I420.
+// mog_update.hip instantiates the dispatch, and with it the kernels, for SHADOW = false: those are instruction for instruction
+// the kernels from before the shadow test existed, and that file's object holds no other.  mog_shadow.hip instantiates it for
+// SHADOW = true (covahip_mog_set_shadows in a mode other than OFF).
 //
 // No contraction in this code (see mog_dev.h); every file that includes it is built with the flags of mog.hip.
 #pragma once
 #pragma clang fp contract(off)
+
+#include <type_traits>
 
 #include "mog_dev.h"
 
@@ -36,18 +62,10 @@ __global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restr
     update_body<G640, SHADOW>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
 }
 
-// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
+// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD].  All four
+// working sizes off 640x360, whichever form their post kernel has.
 template <int MW, int MH, bool SHADOW>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__restrict__ frames, size_t src_bytes,
-                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
-                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
-                                                               unsigned long long *__restrict__ bits, MogShadowDev sh) {
-    update_body<Geom<MW, MH>, SHADOW>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
-}
-
-// frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD]
-template <int MW, int MH, bool SHADOW>
-__global__ __launch_bounds__(UPD_BLOCK) void k_mog_band_update(const uint8_t *__restrict__ frames, size_t src_bytes,
                                                                uint8_t *__restrict__ state, const float2 *__restrict__ par,
                                                                const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
                                                                unsigned long long *__restrict__ bits, MogShadowDev sh) {
@@ -177,18 +195,61 @@ int mog_launch_update_any(covahip_ctx *ctx, const char *scope, K kernel, int mw,
                       a.f0, a.nf, a.S, a.Tb, a.bits, mw, mh, mog_shadow_dev(a));
 }
 
-// The SHADOW = true instance of whichever update kernel a labeller runs (mog_shadow.hip): what mog.hip's dispatch looks at, as a
-// value.  format: COVAHIP_MOG_FMT_* of the surfaces, 0 for BGR24 frames of src_bytes each (then src is not read); load:
-// MOG_LOAD_*; resident: the row's post form, which says whether a BGR24 labeller off the 640 wide working size runs
-// k_mog_grid_update or k_mog_band_update.
-struct MogShadowRoute {
+// Which update kernel a labeller runs, as a value.  format: COVAHIP_MOG_FMT_* of the surfaces, 0 for BGR24 frames of src_bytes
+// each (then src is not read); load: MOG_LOAD_*; mw x mh: the working size; resident: the row's post form, which names the
+// profile scope of a BGR24 labeller off the 640 wide working size (mog_update, or mog_band_update beside the banded post kernel).
+struct MogRoute {
     bool any;
     int format, load, mw, mh;
     bool resident;
 };
-int covahip_mog_shadow_update(covahip_ctx *ctx, const MogShadowRoute &r, const uint8_t *frames, size_t src_bytes,
-                              const covahip_mog_yuv_src &src, const MogUpdateArgs &a);
+
+// One update launch of the route's kernel, in its SHADOW instance.  The only copy of the dispatch: instantiated for false in
+// mog_update.hip and for true in mog_shadow.hip, and nowhere else (the declarations below).
+template <bool SHADOW>
+int mog_launch_route(covahip_ctx *ctx, const MogRoute &r, const uint8_t *frames, size_t src_bytes, const covahip_mog_yuv_src &src,
+                     const MogUpdateArgs &a) {
+    using namespace mogdev;
+    constexpr int NV12 = COVAHIP_MOG_FMT_NV12, I420 = COVAHIP_MOG_FMT_I420;
+    if (r.any) {
+        if (!r.format) return mog_launch_update_any(ctx, "mog_any_update", k_mog_any_update<SHADOW>, r.mw, r.mh, frames, src_bytes, a);
+        const auto kernel = r.format == NV12 ? k_mog_any_yuv_update<NV12, SHADOW> : k_mog_any_yuv_update<I420, SHADOW>;
+        return mog_launch_update_any(ctx, "mog_any_yuv_update", kernel, r.mw, r.mh, frames, src, a);
+    }
+    if (r.format)
+        return with_geom<G640, G320, G960, G1280, G1920>(r.mw, [&](auto g) -> int {
+            using G = decltype(g);
+            const auto launch = [&](auto kind) {
+                constexpr int KIND = decltype(kind)::value;
+                const auto kernel = r.format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND, SHADOW>
+                                                     : k_mog_yuv_update<G::MW, G::MH, I420, KIND, SHADOW>;
+                return mog_launch_update<G>(ctx, "mog_yuv_update", kernel, frames, src, a);
+            };
+            if (r.load == MOG_LOAD_HALF) return launch(std::integral_constant<int, YUV_HALF>{});
+            if constexpr (G::MW == 640) {      // copy and centre pick exist at the reference grid's working size only
+                if (r.load == MOG_LOAD_COPY) return launch(std::integral_constant<int, YUV_COPY>{});
+                if (r.load == MOG_LOAD_PICK) return launch(std::integral_constant<int, YUV_PICK>{});
+            }
+            return COVAHIP_ERR_UNSUPPORTED;
+        });
+    if (r.mw == G640::MW) {
+        const auto kernel = r.load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY, SHADOW>
+                                                    : (r.load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF, SHADOW> : k_mog_update<MOG_LOAD_PICK, SHADOW>);
+        return mog_launch_update<G640>(ctx, "mog_update", kernel, frames, src_bytes, a);
+    }
+    const auto grid = [&](auto g) {
+        using G = decltype(g);
+        return mog_launch_update<G>(ctx, r.resident ? "mog_update" : "mog_band_update", k_mog_grid_update<G::MW, G::MH, SHADOW>, frames,
+                                    src_bytes, a);
+    };
+    return r.resident ? with_geom<G960, G320>(r.mw, grid) : with_geom<G1920, G1280>(r.mw, grid);
+}
+extern template int mog_launch_route<false>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
+                                            const MogUpdateArgs &);
+extern template int mog_launch_route<true>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
+                                           const MogUpdateArgs &);
+
 // counts [FS][2] (u32, device) = the set bits of shadow and of bits & ~shadow in each of FS planes of nword words; shadow may be
-// nullptr (then none)
+// nullptr (then none).  mog_shadow.hip.
 int covahip_mog_counts(covahip_ctx *ctx, const unsigned long long *bits, const unsigned long long *shadow, size_t nword, size_t FS,
                        uint32_t *counts);

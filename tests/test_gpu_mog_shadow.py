@@ -6,7 +6,7 @@ restatement tests/mog_shadow_ref.py, bit for bit: there is no tolerance anywhere
      mask, the labels, shadow_counts and the model
        k_mog_update          640x360 on the reference grid, 640x360 working
        k_mog_grid_update     640x360 on the macroblock grid, 320x180 working
-       k_mog_band_update     2560x1440, 1280x720 working: 3 frames, one per call (the only size of the table that runs it)
+       the same, banded      2560x1440, 1280x720 working: 3 frames, one per call (the scope mog_band_update, beside the banded post)
        k_mog_yuv_update      NV12 at 640x360, a padded surface
        k_mog_any_update      266x258, 133x129 working: 59 dead lanes in every row's last word, which must be in no count
        k_mog_any_yuv_update  I420 at 266x258

@@ -1,11 +1,7 @@
-"""The MoG labeller at any even source size (covahip_mog_create_any, cova_amd.mog any_size=True; cova_amd/csrc/mog_any.hip) without a
+"""The MoG labeller at any even source size (covahip_mog_create_any, cova_amd.mog any_size=True; the general kernels) without a
 GPU: the refusals that come before the ctx is touched, the Python layer's and the command line's, the label shapes, the oracle's
-shapes at sizes whose working image is no multiple of 8 or 64, and the ISA of the translation unit."""
+shapes at sizes whose working image is no multiple of 8 or 64, and the ISA of the kernels."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +9,7 @@ import pytest
 from cova_amd import _lib as L
 from cova_amd import mog
 from tests import mog_grid_ref as G
+from tests import mog_isa
 
 
 def _cfg(w, h):
@@ -120,26 +117,8 @@ def test_oracle_shapes_at_sizes_of_no_table(size):
     assert lab.all()                                   # frame 1 is all foreground
 
 
-def test_any_kernels_isa_no_f32_fma_no_scratch(tmp_path):
-    """mog_any.hip with the flags of test_mog_host's ISA test: its three update kernels have no f32 fused multiply-add, and none
-    of its four kernels uses scratch."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "mog_any.s"
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-ffp-contract=off", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "cova_amd", "csrc"),
-                        "--cuda-device-only", "-S", "-o", str(out), os.path.join(root, "cova_amd", "csrc", "mog_any.hip")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    s = out.read_text()
-    bodies = re.findall(r"^(_Z\w*k_mog_any_\w*update\w*):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M)
-    assert len(bodies) == 3
-    for name, body in bodies:
-        assert not re.search(r"^\s+v_(fma|fmac|mac)_f32", body, re.M), name
-        assert not re.search(r"^\s+scratch_", body, re.M), name
-    meta = re.findall(r"\.name:\s+(\S*k_mog_any_\w*)\n(?:.*\n)*?.*\.private_segment_fixed_size:\s+(\d+)", s)
-    assert len(meta) == 4
-    for name, scratch in meta:
-        assert scratch == "0", name
+def test_any_kernels_isa_no_f32_fma_no_scratch():
+    """With the flags of test_mog_host's ISA test: the three general update kernels (mog_update.hip) have no f32 fused
+    multiply-add, and neither they nor the general post kernel (mog_post.hip) use scratch."""
+    mog_isa.assert_update_family(r"k_mog_any_\w*update", 3)
+    mog_isa.assert_post_family(r"k_mog_any_post", 1)

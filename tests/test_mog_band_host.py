@@ -1,11 +1,7 @@
-"""The MoG labeller at 2560x1440 and 3840x2160 (the macroblock grid's banded kernels, cova_amd/csrc/mog_band.hip) without a GPU:
+"""The MoG labeller at 2560x1440 and 3840x2160 (the macroblock grid's banded kernels, cova_amd/csrc/mog_post.hip) without a GPU:
 the size lists and label shapes, the argument checks that come before any GPU call, the command line, the oracle's shapes,
-the band plan, the planted masks the GPU tests use, and the ISA of the translation unit."""
+the band plan, the planted masks the GPU tests use, and the ISA of the kernels."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -14,6 +10,7 @@ from cova_amd import _lib as L
 from cova_amd import mog
 from tests import mog_band_ref as B
 from tests import mog_grid_ref as G
+from tests import mog_isa
 
 NEW = {(2560, 1440): ((1280, 720), (90, 160)), (3840, 2160): ((1920, 1080), (135, 240))}
 
@@ -136,26 +133,9 @@ def test_planted_masks_do_what_they_are_for():
     assert B.corner_blob(h, w)[-1, -1] and B.blocks(h, w, 0.3, 1).shape == (h, w)
 
 
-def test_band_kernels_isa_no_f32_fma_no_scratch(tmp_path):
-    """mog_band.hip with the flags of test_mog_host's ISA test: its two update kernels have no f32 fused multiply-add, and none
-    of its five kernels uses scratch (the 1920-wide post kernel holds 60 64-bit words per lane in the row fill)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "mog_band.s"
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-ffp-contract=off", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "cova_amd", "csrc"),
-                        "--cuda-device-only", "-S", "-o", str(out), os.path.join(root, "cova_amd", "csrc", "mog_band.hip")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    s = out.read_text()
-    bodies = re.findall(r"^(_Z\w*k_mog_band_update\w*):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M)
-    assert len(bodies) == 2
-    for name, body in bodies:
-        assert not re.search(r"^\s+v_(fma|fmac|mac)_f32", body, re.M), name
-        assert not re.search(r"^\s+scratch_", body, re.M), name
-    meta = re.findall(r"\.name:\s+(\S*k_mog_\w*)\n(?:.*\n)*?.*\.private_segment_fixed_size:\s+(\d+)", s)
-    assert len(meta) == 5
-    for name, scratch in meta:
-        assert scratch == "0", name
+def test_band_kernels_isa_no_f32_fma_no_scratch():
+    """With the flags of test_mog_host's ISA test: none of the three banded post kernels (mog_post.hip) uses scratch (the
+    1920-wide one holds 60 64-bit words per lane in the row fill).  The update kernels of these sizes are two of the four
+    instances test_mog_grid_host's ISA test counts and checks; they are named here so that they cannot leave unnoticed."""
+    mog_isa.assert_post_family(r"k_mog_band_post", 3)
+    mog_isa.assert_update_family(r"k_mog_grid_updateILi(1280|1920)E", 2)

@@ -1,11 +1,7 @@
 """The MoG labeller's macroblock grid without a GPU: the oracle composition (tests/mog_grid_ref.py) against tests/mog_ref.py, the
 label shapes, the planted masks the GPU tests use, the argument checks that come before any GPU call, the command line, and
-the ISA of the macroblock grid's translation unit."""
+the ISA of the macroblock grid's kernels."""
 import ctypes as C
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,6 +9,7 @@ import pytest
 from cova_amd import _lib as L
 from cova_amd import mog
 from tests import mog_grid_ref as G
+from tests import mog_isa
 from tests import mog_ref as R
 from tests.test_gpu_mog import synth_video
 
@@ -121,26 +118,9 @@ def test_cli_grid_parsing(capsys):
     assert "--grid" in capsys.readouterr().out
 
 
-def test_grid_kernels_isa_no_f32_fma_no_scratch(tmp_path):
-    """mog_grid.hip with the flags of test_mog_host's ISA test: its update kernels have no f32 fused multiply-add, and no kernel
-    in it uses scratch (the 960x540 post kernel holds 45 64-bit words per lane in the row fill)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "mog_grid.s"
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-ffp-contract=off", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "cova_amd", "csrc"),
-                        "--cuda-device-only", "-S", "-o", str(out), os.path.join(root, "cova_amd", "csrc", "mog_grid.hip")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    s = out.read_text()
-    bodies = re.findall(r"^(_Z\w*k_mog_grid_update\w*):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M)
-    assert len(bodies) == 2
-    for name, body in bodies:
-        assert not re.search(r"^\s+v_(fma|fmac|mac)_f32", body, re.M), name
-        assert not re.search(r"^\s+scratch_", body, re.M), name
-    meta = re.findall(r"\.name:\s+(\S*k_mog_\w*)\n(?:.*\n)*?.*\.private_segment_fixed_size:\s+(\d+)", s)
-    assert len(meta) == 4
-    for name, scratch in meta:
-        assert scratch == "0", name
+def test_grid_kernels_isa_no_f32_fma_no_scratch():
+    """With the flags of test_mog_host's ISA test: the macroblock grid's update kernels (mog_update.hip: one template at the four
+    working sizes off 640x360, those of 1440p and 4K sources among them) have no f32 fused multiply-add, and neither they nor its
+    resident post kernels (mog_post.hip) use scratch (the 960x540 post kernel holds 45 64-bit words per lane in the row fill)."""
+    mog_isa.assert_update_family(r"k_mog_grid_update", 4)
+    mog_isa.assert_post_family(r"k_mog_grid_postILi(960|320)E", 2)

@@ -324,30 +324,10 @@ def test_oracle_matches_opencv_where_available():
 
 
 # ------------------------------------------------------------------------------------------------ ISA of the update kernel
-def test_update_kernel_isa_no_f32_fma_no_scratch(tmp_path):
-    """The update kernels compile without contraction (no f32 fused multiply-add) and keep the five modes in registers."""
-    import os
-    import re
-    import shutil
-    import subprocess
+def test_update_kernel_isa_no_f32_fma_no_scratch():
+    """The reference grid's update kernels (mog_update.hip) compile without contraction (no f32 fused multiply-add) and keep the
+    five modes in registers; its post kernel (mog_post.hip, the resident template at 640x360) has no scratch either."""
+    from tests import mog_isa
 
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "mog.s"
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-ffp-contract=off", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "cova_amd", "csrc"),
-                        "--cuda-device-only", "-S", "-o", str(out), os.path.join(root, "cova_amd", "csrc", "mog.hip")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    s = out.read_text()
-    bodies = re.findall(r"^(_Z\w*k_mog_update\w*):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M)
-    assert len(bodies) == 3
-    for name, body in bodies:
-        assert not re.search(r"^\s+v_(fma|fmac|mac)_f32", body, re.M), name
-        assert not re.search(r"^\s+scratch_", body, re.M), name
-    meta = re.findall(r"\.name:\s+(\S*k_mog_\w*)\n(?:.*\n)*?.*\.private_segment_fixed_size:\s+(\d+)", s)
-    assert len(meta) == 4
-    for name, scratch in meta:
-        assert scratch == "0", name
+    mog_isa.assert_update_family(r"k_mog_update", 3)
+    mog_isa.assert_post_family(r"k_mog_grid_postILi640E", 1)

@@ -1,19 +1,16 @@
 """The MoG labeller's NV12 / I420 entry (covahip_mog_apply_yuv, cova_amd.mog.apply_yuv) without a GPU: the conversion's numpy
 restatement (tests/mog_yuv_ref.py) against known answers and, where cv2 exists, cv2.cvtColor; the layout structure and helper,
 the raw and YUV4MPEG2 readers, the command line, the argument checks that come before any GPU call, and the ISA of
-mog_yuv.hip."""
+the update kernels on surfaces."""
 import ctypes as C
 import io
-import os
-import re
-import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 from cova_amd import _lib as L
 from cova_amd import mog
+from tests import mog_isa
 from tests import mog_yuv_ref as Y
 
 
@@ -265,30 +262,9 @@ def test_cli_format_parsing(tmp_path, capsys):
 
 
 # ------------------------------------------------------------------------------------------------ ISA
-def test_yuv_kernels_isa_no_f32_fma_no_scratch(tmp_path):
-    """mog_yuv.hip with the flags of test_mog_host's ISA test: seven geometries x two formats of update kernel, none with an f32
-    fused multiply-add, none with scratch, each within 128 VGPRs (four waves per SIMD, as the BGR24 kernels)."""
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    if not os.path.exists(hipcc) and not shutil.which("hipcc"):
-        pytest.skip("hipcc not available")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = tmp_path / "mog_yuv.s"
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950",
-                        "-ffp-contract=off", "-I", os.path.join(root, "include"), "-I", os.path.join(root, "cova_amd", "csrc"),
-                        "--cuda-device-only", "-S", "-o", str(out), os.path.join(root, "cova_amd", "csrc", "mog_yuv.hip")],
-                       capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-2000:]
-    s = out.read_text()
-    bodies = re.findall(r"^(_Z\w*k_mog_yuv_update\w*):[^\n]*\n(.*?)^\.Lfunc_end", s, re.S | re.M)
-    assert len(bodies) == 14
-    for name, body in bodies:
-        assert not re.search(r"^\s+v_(fma|fmac|mac)_f32", body, re.M), name
-        assert not re.search(r"^\s+scratch_", body, re.M), name
-    meta = re.findall(r"\.name:\s+(\S*k_mog_\w*)\n(?:.*\n)*?.*\.private_segment_fixed_size:\s+(\d+)", s)
-    assert len(meta) == 14
-    for name, scratch in meta:
-        assert scratch == "0", name
-    vgprs = re.findall(r"\.name:\s+(\S*k_mog_\w*)\n(?:.*\n)*?.*\.vgpr_count:\s+(\d+)", s)
-    assert len(vgprs) == 14
-    for name, n in vgprs:
-        assert int(n) <= 128, (name, n)
+def test_yuv_kernels_isa_no_f32_fma_no_scratch():
+    """With the flags of test_mog_host's ISA test: seven geometries x two formats of update kernel on surfaces (mog_update.hip),
+    none with an f32 fused multiply-add, none with scratch, each within 128 VGPRs (four waves per SIMD, as the BGR24 kernels)."""
+    ks = mog_isa.assert_update_family(r"k_mog_yuv_update", 14)
+    for name, k in ks.items():
+        assert k["vgprs"] <= 128, (name, k["vgprs"])
