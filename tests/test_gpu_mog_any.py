@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 from cova_amd import mog
+from tests import mog_band_ref as B
 from tests import mog_grid_ref as G
 from tests import mog_ref as R
 from tests import mog_yuv_ref as Y
@@ -23,13 +24,18 @@ HIST = 16
 # source sizes: work 191x129 (63 bits in the last word, odd sizes, 191 * 129 and 192 * 129 no multiples of 256), 129x128 (one bit),
 # 132x136 (4 bits), 192x129 (whole words, a partial last block), 330x190, and a real camera's 640x480
 SIZES = [(382, 258), (258, 256), (264, 272), (384, 258), (660, 380), (1280, 960)]
+# (source size, frames) at the top of the admitted range: work 2048x128 (32 full words), 128x2048 (the maximal height),
+# 2047x129 (63 live bits behind 31 full words, odd sizes), and the two cameras the README names: 2592x1944 (work 1296x972, three
+# automatic bands) and 704x576 (work 352x288).  Short clips: the block moves from frame 1 on.  (tests/test_gpu_mog_any_range.py
+# has the one run at 4096x4096.)
+RANGE_SIZES = [((4096, 256), 4), ((256, 4096), 4), ((4094, 258), 4), ((2592, 1944), 3), ((704, 576), 4)]
 
 
-def any_clip(n, w, h, seed):
-    """synth_video with a 255 block of 80 x 100 source pixels that moves from frame 4 on."""
+def any_clip(n, w, h, seed, start=4):
+    """synth_video with a 255 block of 80 x 100 source pixels that moves from frame `start` on."""
     vid = synth_video(n, w, h, seed).copy()
-    for t in range(4, n):
-        x0, y0 = (40 + 24 * (t - 4)) % (w - 80), h // 2 - 50
+    for t in range(start, n):
+        x0, y0 = (40 + 24 * (t - start)) % (w - 80), h // 2 - 50
         vid[t, y0:y0 + 100, x0:x0 + 80] = 255
     return vid
 
@@ -40,9 +46,9 @@ def _oracle_is_a_test(raw, fill, lab):
 
 
 @functools.lru_cache(maxsize=None)
-def _ref(w, h, n, seed):
+def _ref(w, h, n, seed, start=4):
     """A clip and the CPU labeller's (raw, filled, labels, model) of it."""
-    vid = any_clip(n, w, h, seed)
+    vid = any_clip(n, w, h, seed, start)
     vid.setflags(write=False)
     ref = G.label_video_grid(vid, history=HIST)
     _oracle_is_a_test(*ref[:3])
@@ -67,11 +73,11 @@ def _check_call(m, labels, ref, s=0, what=""):
 
 
 # ------------------------------------------------------------------------------------------------ 1. against the oracle
-@pytest.mark.parametrize("size", SIZES, ids=lambda s: f"{s[0]}x{s[1]}")
-def test_bit_exact_against_oracle(ctx, size):
+@pytest.mark.parametrize("size,n", [(s, 6) for s in SIZES] + RANGE_SIZES,
+                         ids=[f"{s[0]}x{s[1]}" for s in SIZES + [r[0] for r in RANGE_SIZES]])
+def test_bit_exact_against_oracle(ctx, size, n):
     w, h = size
-    n = 6
-    vid, ref = _ref(w, h, n, w + h)
+    vid, ref = _ref(w, h, n, w + h, 4 if n == 6 else 1)
     m = _labeler(ctx, w, h)
     assert m.general
     labels = m.apply(vid[:, None])
@@ -86,16 +92,9 @@ PW, PH = 330, 190                                  # working size of a 660x380 s
 
 
 def _right_edge_case():
-    """Foreground columns mw - 3 .. mw - 1 over the full height (too thin for the opening: gone afterwards), and a slab at the
-    right edge with three cavities: one open to the edge at column mw - 1, which must not fill; one behind a wall of 4 columns,
-    which the morphology opens to the edge too; one behind a wall of 5, one pixel further in, which must fill."""
-    a = np.zeros((PH, PW), bool)
-    a[:, PW - 3:] = True
-    a[20:170, PW - 60:] = True
-    a[35:55, PW - 40:PW] = False
-    a[80:100, PW - 40:PW - 4] = False
-    a[125:145, PW - 40:PW - 5] = False
-    return a
+    """tests/mog_band_ref.right_edge at this working size: the thin strip at the right edge and the slab with the three cavities
+    (open to column mw - 1, behind a wall of 4 columns, behind a wall of 5)."""
+    return B.right_edge(PH, PW)
 
 
 @functools.lru_cache(maxsize=None)
@@ -137,12 +136,14 @@ def test_planted_masks_against_oracle(ctx, rows):
 RESIDENT, BANDED = ("mog_update", "mog_post"), ("mog_band_update", "mog_band_post")    # the table's profile scopes at a size
 
 
-@pytest.mark.parametrize("size,n,scopes", [((640, 360), 6, RESIDENT), ((1920, 1080), 2, RESIDENT), ((2560, 1440), 2, BANDED)],
-                         ids=["640x360", "1920x1080", "2560x1440"])
+@pytest.mark.parametrize("size,n,scopes", [((640, 360), 6, RESIDENT), ((1920, 1080), 2, RESIDENT), ((2560, 1440), 2, BANDED),
+                                           ((3840, 2160), 2, BANDED)],
+                         ids=["640x360", "1920x1080", "2560x1440", "3840x2160"])
 def test_general_kernels_equal_the_tables(ctx, size, n, scopes):
     """The general kernels against the table's on the same frames.  2560x1440 is the smallest table size that runs the templated
     banded kernels (1280x720 working, two bands of 360 by the automatic plan): there the compile-time and the runtime model of
-    the one banded driver are held against each other across a seam."""
+    the one banded driver are held against each other across a seam; 3840x2160 (1920x1080 working) does so at 30 words per row
+    and the automatic four bands, where tests/test_gpu_mog_band.py holds the table's side to the oracle."""
     w, h = size
     vid = any_clip(n, w, h, seed=7)[:, None]
     table = mog.MogLabeler(ctx, w, h, history=HIST, grid="macroblock")
