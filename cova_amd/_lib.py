@@ -294,6 +294,12 @@ PROTOTYPES = {
     "covahip_mog_yuv_tight": (C.c_int, [_P, C.c_int, C.c_int, C.POINTER(MogYuv)]),
     "covahip_mog_apply_yuv": (C.c_int, [_P, C.POINTER(MogYuv), _P, C.c_int, _P, _P, C.c_int]),
     "covahip_mog_reset": (C.c_int, [_P, C.c_int]),
+    "covahip_mog_state_size": (C.c_int, [_P, C.POINTER(C.c_size_t)]),
+    "covahip_mog_save_state": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "covahip_mog_load_state": (C.c_int, [_P, C.c_int, _P, C.c_size_t]),
+    "covahip_mog_set_frozen": (C.c_int, [_P, C.c_int, C.c_int]),
+    "covahip_mog_get_frozen": (C.c_int, [_P, C.c_int, C.POINTER(C.c_int)]),
+    "covahip_mog_background": (C.c_int, [_P, C.c_int, _P, C.c_size_t, C.c_int]),
     "covahip_mog_destroy": (None, [_P]),
 }
 

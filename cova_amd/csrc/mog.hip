@@ -7,7 +7,10 @@
 // caller's pitch, offsets and strides), and which kernels a call launches.  The update kernels are templates of mog_update.h,
 // instantiated in mog_update.hip and, for a call with shadow detection on (covahip_mog_set_shadows), in mog_shadow.hip, which
 // also has the kernel behind covahip_mog_shadow_counts; the post kernels are mog_post.hip's.  All of them run the device code of
-// mog_dev.h.
+// mog_dev.h.  The model as an object is here too: the state blob (covahip_mog_save_state / _load_state, host code around the
+// pitched copy of a model), the per-stream frozen flag (a call then launches the update kernels' frozen instances of
+// mog_frozen.hip on the frozen streams and the learning ones on the rest) and covahip_mog_background, whose kernel is
+// mog_frozen.hip's.
 //
 // No contraction in this file (see mog_dev.h); the arithmetic on the host, the learning rates, is in double.
 #pragma clang fp contract(off)
@@ -68,7 +71,10 @@ struct covahip_mog {
     void *d_counts = nullptr;      // covahip_mog_shadow_counts: (shadow, foreground) u32 [F][S][2]
     size_t shadow_bytes = 0, counts_bytes = 0;
     size_t src_bytes = 0;
-    std::vector<int64_t> n;        // frames each stream has seen
+    std::vector<int64_t> n;        // frames each stream has learned from
+    std::vector<uint8_t> frozen;   // covahip_mog_set_frozen, per stream: its frames are classified and the model stays
+    void *d_bg = nullptr;          // covahip_mog_background to host memory: the image(s) on the device
+    size_t bg_bytes = 0;
     uint8_t *state = nullptr;      // [S][state_bytes]
     void *bits = nullptr, *filled = nullptr, *d_frames = nullptr, *d_labels = nullptr, *d_par = nullptr;
     void *plane = nullptr;         // banded post: the mask after the morphology, as bits
@@ -82,7 +88,7 @@ struct covahip_mog {
 namespace {
 
 void free_mog(covahip_mog *m) {
-    for (void *p : {(void *)m->state, m->bits, m->filled, m->plane, m->d_frames, m->d_labels, m->d_par, m->shadow, m->d_counts})
+    for (void *p : {(void *)m->state, m->bits, m->filled, m->plane, m->d_frames, m->d_labels, m->d_par, m->shadow, m->d_counts, m->d_bg})
         if (p) hipFree(p);
     if (m->h_par) hipHostFree(m->h_par);
     delete m;
@@ -97,13 +103,34 @@ struct YuvPlan {
 };
 
 // one update launch on device frames: BGR24 (yuv == nullptr) or the surfaces of `yuv`'s format as `src` describes them
-int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a) {
+// in its learning or its frozen instance; a.nvalid says which streams the launch has
+int launch_update(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, const MogUpdateArgs &a,
+                  bool frozen) {
     if (yuv && yuv->format != COVAHIP_MOG_FMT_NV12 && yuv->format != COVAHIP_MOG_FMT_I420) return COVAHIP_ERR_INVALID_ARG;
     const MogDims &w = m->row->work;
     const MogRoute route{m->any, yuv ? yuv->format : 0, m->row->load, w.mw, w.mh, m->row->resident};
-    if (a.shadows == COVAHIP_MOG_SHADOWS_OFF) return mog_launch_route<false>(m->ctx, route, d_frames, m->src_bytes, src, a);
+    if (a.shadows == COVAHIP_MOG_SHADOWS_OFF)
+        return frozen ? mog_launch_route<false, true>(m->ctx, route, d_frames, m->src_bytes, src, a)
+                      : mog_launch_route<false, false>(m->ctx, route, d_frames, m->src_bytes, src, a);
     if (!a.shadow) return COVAHIP_ERR_INVALID_ARG;
-    return mog_launch_route<true>(m->ctx, route, d_frames, m->src_bytes, src, a);
+    return frozen ? mog_launch_route<true, true>(m->ctx, route, d_frames, m->src_bytes, src, a)
+                  : mog_launch_route<true, false>(m->ctx, route, d_frames, m->src_bytes, src, a);
+}
+
+// The update launch(es) of frames a.f0 .. a.f0 + a.nf of a call: the learning instance on the streams that learn and the frozen
+// one on the rest, each with the n_valid table that has 0 for the other's streams (the kernels skip those block-wise).  A
+// labeller with no frozen stream launches what it always has.
+int launch_updates(covahip_mog *m, const YuvPlan *yuv, const uint8_t *d_frames, const covahip_mog_yuv_src &src, MogUpdateArgs a,
+                   const int32_t *d_nv_learn, const int32_t *d_nv_frozen) {
+    if (d_nv_learn) {
+        a.nvalid = d_nv_learn;
+        if (int rc = launch_update(m, yuv, d_frames, src, a, false)) return rc;
+    }
+    if (d_nv_frozen) {
+        a.nvalid = d_nv_frozen;
+        if (int rc = launch_update(m, yuv, d_frames, src, a, true)) return rc;
+    }
+    return COVAHIP_OK;
 }
 
 // the post launch on the call's raw planes (m->bits): filled planes and labels of FS (frame, stream) pairs
@@ -146,6 +173,7 @@ int create_mog(covahip_ctx *ctx, const covahip_mog_cfg *cfg, const MogGeomRow *r
     m->banded = m->row->starts_banded;
     m->src_bytes = (size_t)cfg->src_w * cfg->src_h * 3;
     m->n.assign(cfg->n_streams, 0);
+    m->frozen.assign(cfg->n_streams, 0);
     const size_t sb = m->alloc.state_bytes() * cfg->n_streams;
     hipError_t e = hipMalloc(&m->state, sb);
     if (e == hipSuccess) e = hipMemsetAsync(m->state, 0, sb, ctx->stream);
@@ -157,6 +185,50 @@ int create_mog(covahip_ctx *ctx, const covahip_mog_cfg *cfg, const MogGeomRow *r
     }
     *out = m;
     return COVAHIP_OK;
+}
+
+// One stream's model between the device (rows at the pitch d.mw) and host arrays whose rows are dense, [work_h][work_w]: W, V
+// f32 [5][..], M f32 [5][3][..], nmodes u8 [..]; a NULL array is skipped.  to_host: the direction.  The copies go to ctx->stream;
+// the caller waits.  A padded row's lanes at x >= work_w are neither read nor written.
+int copy_model(covahip_mog *m, int stream, void *W, void *V, void *M, void *nmodes, bool to_host) {
+    covahip_ctx *ctx = m->ctx;
+    const MogDims &d = m->alloc;
+    uint8_t *st = m->state + (size_t)stream * d.state_bytes();
+    // elem: bytes per pixel and array
+    const struct { void *host; size_t off, end, elem; } parts[] = {{W, 0, d.off_v(), 4},
+                                                                   {V, d.off_v(), d.off_m(), 4},
+                                                                   {M, d.off_m(), d.off_n(), 4},
+                                                                   {nmodes, d.off_n(), d.state_bytes(), 1}};
+    const size_t mw = m->row->work.mw;
+    const hipMemcpyKind kind = to_host ? hipMemcpyDeviceToHost : hipMemcpyHostToDevice;
+    for (const auto &pt : parts) {
+        if (!pt.host) continue;
+        uint8_t *dev = st + pt.off;
+        const size_t dpitch = d.mw * pt.elem, hpitch = mw * pt.elem, rows = (pt.end - pt.off) / dpitch;
+        if (d.mw == (int)mw)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(to_host ? pt.host : (void *)dev, to_host ? (const void *)dev : pt.host, pt.end - pt.off, kind,
+                                                  ctx->stream));
+        else if (to_host)
+            COVAHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(pt.host, hpitch, dev, dpitch, hpitch, rows, kind, ctx->stream));
+        else
+            COVAHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(dev, dpitch, pt.host, hpitch, hpitch, rows, kind, ctx->stream));
+    }
+    return COVAHIP_OK;
+}
+
+// the state blob of include/covahip.h ("MoG labels", model state): a header of 64 bytes, 101 bytes per working pixel, the CRC
+constexpr uint32_t B_MAGIC = 0x4D485643, B_VERSION = 1;       // "CVHM"
+constexpr size_t B_HEADER = 64;
+constexpr size_t blob_bytes(size_t npix) { return B_HEADER + 101 * npix + 4; }
+template <class T>
+void put(uint8_t *p, size_t off, T v) {
+    std::memcpy(p + off, &v, sizeof(T));
+}
+template <class T>
+T get(const uint8_t *p, size_t off) {
+    T v;
+    std::memcpy(&v, p + off, sizeof(T));
+    return v;
 }
 
 }  // namespace
@@ -217,7 +289,10 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     const size_t FS = (size_t)n_frames * S;
     const size_t NWORD = m->alloc.nword(), NLAB = m->row->work.nlab();   // this labeller's geometry
     // per-stream, per-frame learning rates, in double as generate-mog.py's OpenCV computes them
-    const size_t par_bytes = FS * sizeof(float2) + S * sizeof(int32_t);
+    // (behind them n_valid [S], and where a stream is frozen the two launches' tables: n_valid of the learning streams with 0
+    // for the frozen ones, and the reverse)
+    const int n_frozen = (int)std::count(m->frozen.begin(), m->frozen.end(), 1);
+    const size_t par_bytes = FS * sizeof(float2) + (n_frozen ? 3 : 1) * S * sizeof(int32_t);
     if (m->h_par_bytes < par_bytes) {
         if (m->h_par) COVAHIP_CHECK_HIP(ctx, hipHostFree(m->h_par));
         m->h_par = nullptr;
@@ -233,13 +308,20 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
             const double lr = 1.0 / (double)den;
             hp[(size_t)f * S + s] = make_float2((float)lr, (float)(-lr * (double)FCT));
         }
-    std::memcpy(hp + FS, nv.data(), S * sizeof(int32_t));
+    int32_t *hnv = reinterpret_cast<int32_t *>(hp + FS);
+    std::memcpy(hnv, nv.data(), S * sizeof(int32_t));
+    if (n_frozen)
+        for (int s = 0; s < S; s++) {
+            hnv[S + s] = m->frozen[s] ? 0 : nv[s];
+            hnv[2 * S + s] = m->frozen[s] ? nv[s] : 0;
+        }
     if (int rc = covahip_ensure_buffer(ctx, &m->d_par, &m->par_bytes, par_bytes)) return rc;
     if (int rc = covahip_ensure_buffer(ctx, &m->bits, &m->bits_bytes, FS * NWORD * 8)) return rc;
     if (int rc = covahip_ensure_buffer(ctx, &m->filled, &m->filled_bytes, FS * NWORD * 8)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(m->d_par, hp, par_bytes, hipMemcpyHostToDevice, ctx->stream));
     const float2 *d_par = static_cast<const float2 *>(m->d_par);
     const int32_t *d_nv = reinterpret_cast<const int32_t *>(d_par + FS);
+    const int32_t *d_nv_learn = !n_frozen ? d_nv : (n_frozen < S ? d_nv + S : nullptr), *d_nv_frozen = n_frozen ? d_nv + 2 * S : nullptr;
     MogUpdateArgs a{m->state, d_par, d_nv, 0, n_frames, S, m->cfg.var_threshold, static_cast<unsigned long long *>(m->bits)};
     if (m->shadows != COVAHIP_MOG_SHADOWS_OFF) {
         if (int rc = covahip_ensure_buffer(ctx, &m->shadow, &m->shadow_bytes, FS * NWORD * 8)) return rc;
@@ -250,7 +332,7 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     covahip_mog_yuv_src src = yuv ? yuv->src : covahip_mog_yuv_src{};
     uint8_t *d_labels = labels;
     if (mem_kind == COVAHIP_MEM_DEVICE) {
-        if (int rc = launch_update(m, yuv, frames, src, a)) return rc;
+        if (int rc = launch_updates(m, yuv, frames, src, a, d_nv_learn, d_nv_frozen)) return rc;
     } else {
         // host memory: staged in launches of as many frames as fit the budget (the model is read and written once per launch).
         // Per (frame, stream) the extent lo .. lo + ext of the frame (a BGR24 frame: all of it) is staged, densely and
@@ -278,7 +360,7 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
                                                               hipMemcpyHostToDevice, ctx->stream));
                     }
             }
-            if (int rc = launch_update(m, yuv, d, src, a)) return rc;
+            if (int rc = launch_updates(m, yuv, d, src, a, d_nv_learn, d_nv_frozen)) return rc;
         }
         if (int rc = covahip_ensure_buffer(ctx, &m->d_labels, &m->labels_bytes, FS * NLAB)) return rc;
         d_labels = static_cast<uint8_t *>(m->d_labels);
@@ -289,7 +371,8 @@ int apply_frames(covahip_mog *m, const uint8_t *frames, const YuvPlan *yuv, int 
     if (mem_kind == COVAHIP_MEM_HOST)
         COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(labels, d_labels, FS * NLAB, hipMemcpyDeviceToHost, ctx->stream));
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    for (int s = 0; s < S; s++) m->n[s] += nv[s];
+    for (int s = 0; s < S; s++)
+        if (!m->frozen[s]) m->n[s] += nv[s];
     m->last_frames = n_frames;
     m->last_shadows = a.shadows;
     m->last_nv = nv;
@@ -547,22 +630,99 @@ int covahip_dev_mog_state(covahip_mog *m, int stream, float *W, float *V, float 
     covahip_ctx *ctx = m->ctx;
     COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
     if (int rc = covahip_primary_op(ctx)) return rc;
-    const MogDims &d = m->alloc;
-    const uint8_t *st = m->state + (size_t)stream * d.state_bytes();
-    // elem: bytes per pixel and array; the rows come back dense, [work_h][work_w], whatever the device's pitch (d.mw)
-    const struct { void *dst; size_t off, end, elem; } parts[] = {{W, 0, d.off_v(), 4},
-                                                                  {V, d.off_v(), d.off_m(), 4},
-                                                                  {M, d.off_m(), d.off_n(), 4},
-                                                                  {nmodes, d.off_n(), d.state_bytes(), 1}};
-    const size_t mw = m->row->work.mw;
-    for (const auto &pt : parts)
-        if (pt.dst && d.mw == (int)mw)
-            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(pt.dst, st + pt.off, pt.end - pt.off, hipMemcpyDeviceToHost, ctx->stream));
-        else if (pt.dst)
-            COVAHIP_CHECK_HIP(ctx, hipMemcpy2DAsync(pt.dst, mw * pt.elem, st + pt.off, d.mw * pt.elem, mw * pt.elem,
-                                                    (pt.end - pt.off) / (d.mw * pt.elem), hipMemcpyDeviceToHost, ctx->stream));
+    if (int rc = copy_model(m, stream, W, V, M, nmodes, true)) return rc;
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n) *n = m->n[stream];
+    return COVAHIP_OK;
+}
+
+int covahip_mog_state_size(const covahip_mog *m, size_t *n) {
+    if (!m || !n) return COVAHIP_ERR_INVALID_ARG;
+    *n = blob_bytes(m->row->work.npix());
+    return COVAHIP_OK;
+}
+
+int covahip_mog_save_state(covahip_mog *m, int stream, void *buf, size_t cap, size_t *n) {
+    if (!m || !n || stream < 0 || stream >= m->cfg.n_streams) return COVAHIP_ERR_INVALID_ARG;
+    const size_t P = m->row->work.npix(), need = blob_bytes(P);
+    *n = need;
+    if (!buf || cap < need) return COVAHIP_ERR_OVERFLOW;
+    covahip_ctx *ctx = m->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    uint8_t *p = static_cast<uint8_t *>(buf);
+    std::memset(p, 0, B_HEADER);
+    put<uint32_t>(p, 0, B_MAGIC);
+    put<uint32_t>(p, 4, B_VERSION);
+    put<int32_t>(p, 8, m->row->work.mw);
+    put<int32_t>(p, 12, m->row->work.mh);
+    put<int32_t>(p, 16, m->cfg.history);
+    put<float>(p, 20, m->cfg.var_threshold);
+    put<int64_t>(p, 24, m->n[stream]);
+    uint8_t *q = p + B_HEADER;                                 // W, V, M, nmodes, dense
+    if (int rc = copy_model(m, stream, q, q + 20 * P, q + 40 * P, q + 100 * P, true)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    put<uint32_t>(p, need - 4, covahip_crc32c(p, need - 4));
+    return COVAHIP_OK;
+}
+
+int covahip_mog_load_state(covahip_mog *m, int stream, const void *buf, size_t n) {
+    if (!m || !buf || stream < 0 || stream >= m->cfg.n_streams) return COVAHIP_ERR_INVALID_ARG;
+    const uint8_t *p = static_cast<const uint8_t *>(buf);
+    if (n < B_HEADER + 4 || get<uint32_t>(p, 0) != B_MAGIC || get<uint32_t>(p, 4) != B_VERSION) return COVAHIP_ERR_BAD_DATA;
+    const int32_t bw = get<int32_t>(p, 8), bh = get<int32_t>(p, 12);
+    if (bw < 1 || bh < 1 || bw > COVAHIP_MOG_ANY_MAX || bh > COVAHIP_MOG_ANY_MAX) return COVAHIP_ERR_BAD_DATA;
+    const size_t P = (size_t)bw * bh;
+    if (n != blob_bytes(P)) return COVAHIP_ERR_BAD_DATA;
+    if (get<uint32_t>(p, n - 4) != covahip_crc32c(p, n - 4)) return COVAHIP_ERR_BAD_DATA;
+    const int64_t frames = get<int64_t>(p, 24);
+    if (frames < 0) return COVAHIP_ERR_BAD_DATA;
+    const uint8_t *q = p + B_HEADER;
+    for (size_t i = 0; i < P; i++)
+        if (q[100 * P + i] > NMIX) return COVAHIP_ERR_BAD_DATA;
+    if (bw != m->row->work.mw || bh != m->row->work.mh) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = m->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    uint8_t *w = const_cast<uint8_t *>(q);                     // (copy_model only reads it in this direction)
+    if (int rc = copy_model(m, stream, w, w + 20 * P, w + 40 * P, w + 100 * P, false)) return rc;
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    m->n[stream] = frames;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_set_frozen(covahip_mog *m, int stream, int frozen) {
+    if (!m || stream < -1 || stream >= m->cfg.n_streams || (frozen != 0 && frozen != 1)) return COVAHIP_ERR_INVALID_ARG;
+    for (int s = 0; s < m->cfg.n_streams; s++)
+        if (stream < 0 || s == stream) m->frozen[s] = (uint8_t)frozen;
+    return COVAHIP_OK;
+}
+
+int covahip_mog_get_frozen(const covahip_mog *m, int stream, int *frozen) {
+    if (!m || !frozen || stream < 0 || stream >= m->cfg.n_streams) return COVAHIP_ERR_INVALID_ARG;
+    *frozen = m->frozen[stream];
+    return COVAHIP_OK;
+}
+
+int covahip_mog_background(covahip_mog *m, int stream, uint8_t *bgr, size_t cap, int mem_kind) {
+    if (!m || stream < -1 || stream >= m->cfg.n_streams) return COVAHIP_ERR_INVALID_ARG;
+    if (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE) return COVAHIP_ERR_INVALID_ARG;
+    const int ns = stream < 0 ? m->cfg.n_streams : 1, s0 = stream < 0 ? 0 : stream;
+    const size_t need = (size_t)ns * m->row->work.npix() * 3;
+    if (!bgr || cap < need) return COVAHIP_ERR_OVERFLOW;
+    covahip_ctx *ctx = m->ctx;
+    COVAHIP_CHECK_HIP(ctx, hipSetDevice(ctx->device));
+    if (int rc = covahip_primary_op(ctx)) return rc;
+    uint8_t *d_out = bgr;
+    if (mem_kind == COVAHIP_MEM_HOST) {
+        if (int rc = covahip_ensure_buffer(ctx, &m->d_bg, &m->bg_bytes, need)) return rc;
+        d_out = static_cast<uint8_t *>(m->d_bg);
+    }
+    const size_t sb = m->alloc.state_bytes();
+    if (int rc = covahip_mog_background_launch(ctx, m->state + (size_t)s0 * sb, sb, m->alloc.mw, m->row->work.mw, m->row->work.mh, ns, d_out))
+        return rc;
+    if (mem_kind == COVAHIP_MEM_HOST) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(bgr, d_out, need, hipMemcpyDeviceToHost, ctx->stream));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return COVAHIP_OK;
 }
 

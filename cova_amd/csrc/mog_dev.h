@@ -170,6 +170,28 @@ __device__ __forceinline__ bool mog2_pixel(float (&W)[NMIX], float (&V)[NMIX], f
     return !bg;
 }
 
+// One pixel classified against its model, which is only read (include/covahip.h, "MoG labels", frozen labelling): the walk of
+// mog2_pixel's step 2 without its writes, up to the first mode that fits; returns true when the pixel is foreground.  The mask
+// is the one mog2_pixel gives at alphaT = 0 on a model of finite values.  No division, nothing stored: `done` is the statement's
+// stop, so the unrolled loop keeps W, V and M in registers.
+__device__ __forceinline__ bool frozen_pixel(const float (&W)[NMIX], const float (&V)[NMIX], const float (&M)[NMIX][3], int nm,
+                                             const Px &px, float Tb) {
+    bool done = false, bg = false;
+    float tw = 0.f;
+#pragma unroll
+    for (int mode = 0; mode < NMIX; mode++) {
+        if (mode < nm && !done) {
+            const float d0 = M[mode][0] - px.c0, d1 = M[mode][1] - px.c1, d2 = M[mode][2] - px.c2;
+            const float dist2 = (d0 * d0 + d1 * d1) + d2 * d2;
+            const float var = V[mode];
+            if (tw < TB && dist2 < Tb * var) bg = true;
+            if (dist2 < TG * var) done = true;
+            tw = tw + W[mode];                 // (not read again where the walk has just ended)
+        }
+    }
+    return !bg;
+}
+
 // The shadow test of one foreground pixel on the model mog2_pixel has just left (include/covahip.h, "MoG labels", step 2a;
 // detectShadowGMM of OpenCV's MOG2): true when the pixel is a darker copy, by a factor a in [tau, 1], of a background mode's
 // mean.  The model is only read.  The returns of the statement are the `done` flag here, so the unrolled loop keeps W, V and M
@@ -225,6 +247,20 @@ __device__ __forceinline__ void shadow_ballots(bool fg, const float (&W)[NMIX], 
     }
 }
 
+// What a wave stores for a frame in the frozen instances: with SHADOW the two words of shadow_ballots (the test on the model
+// as it is), without it the one ballot word of the raw plane.  fg is false in a lane without a pixel.
+template <bool SHADOW>
+__device__ __forceinline__ void frame_ballots(bool fg, const float (&W)[NMIX], const float (&V)[NMIX], const float (&M)[NMIX][3], int nm,
+                                              const Px &px, float Tb, const MogShadowDev &sh, size_t word,
+                                              unsigned long long *__restrict__ bits) {
+    if constexpr (SHADOW) {
+        shadow_ballots(fg, W, V, M, nm, px, Tb, sh, word, bits);
+    } else {
+        const unsigned long long w = __ballot(fg);
+        if ((threadIdx.x & 63) == 0) bits[word] = w;
+    }
+}
+
 // The update kernel's body: one lane per working pixel and stream, grid (G::NPIX / UPD_BLOCK, S).  frames: the launch's first
 // frame of stream 0, with frames and streams at byte strides of the caller's; par: (alphaT, prune) [F][S] of the call; bits: raw
 // masks [F][S][G::NWORD].  A wave's 64 pixels lie in one row, so its ballot is one word of the plane.  `load.at(x, y)` gives
@@ -233,7 +269,7 @@ __device__ __forceinline__ void shadow_ballots(bool fg, const float (&W)[NMIX], 
 // in flight across this frame's mog2_pixel.  Load::WAIT says whether the body waits once before its loop (below).  SHADOW: the
 // shadow test runs on every foreground pixel and the wave stores two words per frame (shadow_ballots); without it `sh` is not
 // read and the body is the one it was before the test existed.
-template <class G, bool SHADOW, class Load>
+template <class G, bool SHADOW, bool FROZEN, class Load>
 __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__restrict__ frames, long long frame_stride,
                                                     long long stream_stride, uint8_t *__restrict__ state,
                                                     const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf,
@@ -267,17 +303,24 @@ __device__ __forceinline__ void update_body_strided(Load load, const uint8_t *__
     for (int f = 0; f < fend; f++) {
         typename Load::Raw nxt = cur;
         if (f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
-        const float2 pr = par[(size_t)(f0 + f) * S + s];
-        const Px px = load.px(cur);
-        const bool fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
-        if constexpr (SHADOW) {
-            shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * G::NWORD + p / 64, bits);
-        } else {
-            const unsigned long long word = __ballot(fg);
-            if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+        if constexpr (FROZEN) {
+            const Px px = load.px(cur);
+            frame_ballots<SHADOW>(frozen_pixel(W, V, M, nm, px, Tb), W, V, M, nm, px, Tb, sh,
+                                  ((size_t)(f0 + f) * S + s) * G::NWORD + p / 64, bits);
+        } else {                               // (the update's own lines, left as they were: its ISA is held to the letter)
+            const float2 pr = par[(size_t)(f0 + f) * S + s];
+            const Px px = load.px(cur);
+            const bool fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
+            if constexpr (SHADOW) {
+                shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * G::NWORD + p / 64, bits);
+            } else {
+                const unsigned long long word = __ballot(fg);
+                if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * G::NWORD + p / 64] = word;
+            }
         }
         cur = nxt;
     }
+    if constexpr (FROZEN) return;              // the model is as it was
 #pragma unroll
     for (int k = 0; k < NMIX; k++) {
         gW[(size_t)k * NPIX + p] = W[k];
@@ -299,11 +342,11 @@ struct PlainLoad {
     __device__ __forceinline__ Px operator()(const uint8_t *__restrict__ fr, const At &t) const { return load(fr, t.x, t.y); }
     __device__ __forceinline__ Px px(const Px &r) const { return r; }
 };
-template <class G, bool SHADOW, class L>
+template <class G, bool SHADOW, bool FROZEN, class L>
 __device__ __forceinline__ void update_body(L load, const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
                                             const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0, int nf, int S,
                                             float Tb, unsigned long long *__restrict__ bits, const MogShadowDev &sh) {
-    update_body_strided<G, SHADOW>(PlainLoad<L>{load}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par,
+    update_body_strided<G, SHADOW, FROZEN>(PlainLoad<L>{load}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state, par,
                                    nvalid, f0, nf, S, Tb, bits, sh);
 }
 

@@ -48,8 +48,7 @@ __global__ __launch_bounds__(COUNT_BLOCK) void k_mog_counts(const unsigned long 
 
 }  // namespace
 
-template int mog_launch_route<true>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
-                                    const MogUpdateArgs &);
+MOG_ROUTE_INSTANCE(true, false);
 
 int covahip_mog_counts(covahip_ctx *ctx, const unsigned long long *bits, const unsigned long long *shadow, size_t nword, size_t FS,
                        uint32_t *counts) {

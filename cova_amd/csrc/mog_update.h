@@ -30,7 +30,10 @@
 //                         not of 256).  BGR24 (LoadHalfAny) and, with LoadYuv<.., HALF>, NV12 / I420.
 // mog_update.hip instantiates the dispatch, and with it the kernels, for SHADOW = false: those are instruction for instruction
 // the kernels from before the shadow test existed, and that file's object holds no other.  mog_shadow.hip instantiates it for
-// SHADOW = true (covahip_mog_set_shadows in a mode other than OFF).
+// SHADOW = true (covahip_mog_set_shadows in a mode other than OFF).  FROZEN, the last axis of every kernel (false in both of
+// those files), is covahip_mog_set_frozen: the lane reads its model into registers as ever, classifies every frame of the call
+// against it (frozen_pixel of mog_dev.h, then the shadow test on the model as it is) and returns: no write-back, `par` is not
+// read, no division.  The ballots and the next frame's loads in flight are the update's.  mog_frozen.hip instantiates those.
 //
 // No contraction in this code (see mog_dev.h); every file that includes it is built with the flags of mog.hip.
 #pragma once
@@ -55,30 +58,30 @@ struct LoadPx {
 
 // SRC: MOG_LOAD_*.  frames: this launch's first frame, [nf][S][src]; par: (alphaT, prune) [F][S] of the call; bits: raw masks
 // [F][S][3600]; SHADOW, sh: the shadow test (update_body_strided)
-template <int SRC, bool SHADOW>
+template <int SRC, bool SHADOW, bool FROZEN>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
                                                           const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
                                                           int nf, int S, float Tb, unsigned long long *__restrict__ bits, MogShadowDev sh) {
-    update_body<G640, SHADOW>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
+    update_body<G640, SHADOW, FROZEN>(LoadPx<SRC>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
 }
 
 // frames: this launch's first frame, [nf][S][2 MH][2 MW][3]; par: (alphaT, prune) [F][S]; bits: raw masks [F][S][NWORD].  All four
 // working sizes off 640x360, whichever form their post kernel has.
-template <int MW, int MH, bool SHADOW>
+template <int MW, int MH, bool SHADOW, bool FROZEN>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_grid_update(const uint8_t *__restrict__ frames, size_t src_bytes,
                                                                uint8_t *__restrict__ state, const float2 *__restrict__ par,
                                                                const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
                                                                unsigned long long *__restrict__ bits, MogShadowDev sh) {
-    update_body<Geom<MW, MH>, SHADOW>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
+    update_body<Geom<MW, MH>, SHADOW, FROZEN>(LoadHalf<MW>(), frames, src_bytes, state, par, nvalid, f0, nf, S, Tb, bits, sh);
 }
 
 // frames: the launch's first frame of stream 0; par: (alphaT, prune) [F][S] of the call; bits: raw masks [F][S][G::NWORD]
-template <int MW, int MH, int FMT, int KIND, bool SHADOW>
+template <int MW, int MH, int FMT, int KIND, bool SHADOW, bool FROZEN>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
                                                               uint8_t *__restrict__ state, const float2 *__restrict__ par,
                                                               const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
                                                               unsigned long long *__restrict__ bits, MogShadowDev sh) {
-    update_body_strided<Geom<MW, MH>, SHADOW>(LoadYuv<FMT, KIND>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid,
+    update_body_strided<Geom<MW, MH>, SHADOW, FROZEN>(LoadYuv<FMT, KIND>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid,
                                               f0, nf, S, Tb, bits, sh);
 }
 
@@ -97,7 +100,7 @@ struct LoadHalfAny {
 
 // update_body_strided of mog_dev.h on the padded pitch: grid (ceil(P / UPD_BLOCK), S), bits [F][S][roww mh].  SHADOW, sh: as
 // there; a lane at x >= mw is no foreground, so it is in neither plane.
-template <bool SHADOW, class Load>
+template <bool SHADOW, bool FROZEN, class Load>
 __device__ __forceinline__ void update_any(Load load, const uint8_t *__restrict__ frames, long long frame_stride, long long stream_stride,
                                            uint8_t *__restrict__ state, const float2 *__restrict__ par,
                                            const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
@@ -135,22 +138,33 @@ __device__ __forceinline__ void update_any(Load load, const uint8_t *__restrict_
     for (int f = 0; f < fend; f++) {
         typename Load::Raw nxt = cur;
         if (live && f + 1 < fend) nxt = load(fr + (long long)(f + 1) * frame_stride, at);   // next frame's words in flight
-        const float2 pr = par[(size_t)(f0 + f) * S + s];
-        bool fg = false;
-        if constexpr (SHADOW) {
+        if constexpr (FROZEN) {
             Px px{};
+            bool fg = false;
             if (live) {
                 px = load.px(cur);
-                fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
+                fg = frozen_pixel(W, V, M, nm, px, Tb);
             }
-            shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * (P / 64) + p / 64, bits);
-        } else {
-            if (live) fg = mog2_pixel(W, V, M, nm, load.px(cur), pr.x, pr.y, Tb);
-            const unsigned long long word = __ballot(fg);
-            if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * (P / 64) + p / 64] = word;
+            frame_ballots<SHADOW>(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * (P / 64) + p / 64, bits);
+        } else {                               // (the update's own lines, left as they were)
+            const float2 pr = par[(size_t)(f0 + f) * S + s];
+            bool fg = false;
+            if constexpr (SHADOW) {
+                Px px{};
+                if (live) {
+                    px = load.px(cur);
+                    fg = mog2_pixel(W, V, M, nm, px, pr.x, pr.y, Tb);
+                }
+                shadow_ballots(fg, W, V, M, nm, px, Tb, sh, ((size_t)(f0 + f) * S + s) * (P / 64) + p / 64, bits);
+            } else {
+                if (live) fg = mog2_pixel(W, V, M, nm, load.px(cur), pr.x, pr.y, Tb);
+                const unsigned long long word = __ballot(fg);
+                if ((threadIdx.x & 63) == 0) bits[((size_t)(f0 + f) * S + s) * (P / 64) + p / 64] = word;
+            }
         }
         cur = nxt;
     }
+    if constexpr (FROZEN) return;              // the model is as it was
     if (live) {
 #pragma unroll
         for (int k = 0; k < NMIX; k++) {
@@ -164,22 +178,22 @@ __device__ __forceinline__ void update_any(Load load, const uint8_t *__restrict_
 }
 
 // frames: this launch's first frame, [nf][S][2 mh][2 mw][3]
-template <bool SHADOW>
+template <bool SHADOW, bool FROZEN>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_update(const uint8_t *__restrict__ frames, size_t src_bytes, uint8_t *__restrict__ state,
                                                               const float2 *__restrict__ par, const int32_t *__restrict__ nvalid, int f0,
                                                               int nf, int S, float Tb, unsigned long long *__restrict__ bits, int mw, int mh,
                                                               MogShadowDev sh) {
-    update_any<SHADOW>(PlainLoad<LoadHalfAny>{LoadHalfAny{2 * mw}}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state,
+    update_any<SHADOW, FROZEN>(PlainLoad<LoadHalfAny>{LoadHalfAny{2 * mw}}, frames, (long long)((size_t)S * src_bytes), (long long)src_bytes, state,
                        par, nvalid, f0, nf, S, Tb, bits, mw, mh, sh);
 }
 
 // frames: the launch's first frame of stream 0, surfaces as `src` describes them
-template <int FMT, bool SHADOW>
+template <int FMT, bool SHADOW, bool FROZEN>
 __global__ __launch_bounds__(UPD_BLOCK) void k_mog_any_yuv_update(const uint8_t *__restrict__ frames, covahip_mog_yuv_src src,
                                                                   uint8_t *__restrict__ state, const float2 *__restrict__ par,
                                                                   const int32_t *__restrict__ nvalid, int f0, int nf, int S, float Tb,
                                                                   unsigned long long *__restrict__ bits, int mw, int mh, MogShadowDev sh) {
-    update_any<SHADOW>(LoadYuv<FMT, YUV_HALF>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid, f0, nf, S, Tb, bits, mw,
+    update_any<SHADOW, FROZEN>(LoadYuv<FMT, YUV_HALF>{src}, frames, src.frame_stride, src.stream_stride, state, par, nvalid, f0, nf, S, Tb, bits, mw,
                        mh, sh);
 }
 
@@ -204,16 +218,17 @@ struct MogRoute {
     bool resident;
 };
 
-// One update launch of the route's kernel, in its SHADOW instance.  The only copy of the dispatch: instantiated for false in
-// mog_update.hip and for true in mog_shadow.hip, and nowhere else (the declarations below).
-template <bool SHADOW>
+// One update launch of the route's kernel, in its (SHADOW, FROZEN) instance.  The only copy of the dispatch: the learning
+// instances are instantiated in mog_update.hip (SHADOW = false) and mog_shadow.hip (true), the frozen ones in mog_frozen.hip, and
+// nowhere else (the declarations below).
+template <bool SHADOW, bool FROZEN>
 int mog_launch_route(covahip_ctx *ctx, const MogRoute &r, const uint8_t *frames, size_t src_bytes, const covahip_mog_yuv_src &src,
                      const MogUpdateArgs &a) {
     using namespace mogdev;
     constexpr int NV12 = COVAHIP_MOG_FMT_NV12, I420 = COVAHIP_MOG_FMT_I420;
     if (r.any) {
-        if (!r.format) return mog_launch_update_any(ctx, "mog_any_update", k_mog_any_update<SHADOW>, r.mw, r.mh, frames, src_bytes, a);
-        const auto kernel = r.format == NV12 ? k_mog_any_yuv_update<NV12, SHADOW> : k_mog_any_yuv_update<I420, SHADOW>;
+        if (!r.format) return mog_launch_update_any(ctx, "mog_any_update", k_mog_any_update<SHADOW, FROZEN>, r.mw, r.mh, frames, src_bytes, a);
+        const auto kernel = r.format == NV12 ? k_mog_any_yuv_update<NV12, SHADOW, FROZEN> : k_mog_any_yuv_update<I420, SHADOW, FROZEN>;
         return mog_launch_update_any(ctx, "mog_any_yuv_update", kernel, r.mw, r.mh, frames, src, a);
     }
     if (r.format)
@@ -221,8 +236,8 @@ int mog_launch_route(covahip_ctx *ctx, const MogRoute &r, const uint8_t *frames,
             using G = decltype(g);
             const auto launch = [&](auto kind) {
                 constexpr int KIND = decltype(kind)::value;
-                const auto kernel = r.format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND, SHADOW>
-                                                     : k_mog_yuv_update<G::MW, G::MH, I420, KIND, SHADOW>;
+                const auto kernel = r.format == NV12 ? k_mog_yuv_update<G::MW, G::MH, NV12, KIND, SHADOW, FROZEN>
+                                                     : k_mog_yuv_update<G::MW, G::MH, I420, KIND, SHADOW, FROZEN>;
                 return mog_launch_update<G>(ctx, "mog_yuv_update", kernel, frames, src, a);
             };
             if (r.load == MOG_LOAD_HALF) return launch(std::integral_constant<int, YUV_HALF>{});
@@ -233,23 +248,31 @@ int mog_launch_route(covahip_ctx *ctx, const MogRoute &r, const uint8_t *frames,
             return COVAHIP_ERR_UNSUPPORTED;
         });
     if (r.mw == G640::MW) {
-        const auto kernel = r.load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY, SHADOW>
-                                                    : (r.load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF, SHADOW> : k_mog_update<MOG_LOAD_PICK, SHADOW>);
+        const auto kernel = r.load == MOG_LOAD_COPY ? k_mog_update<MOG_LOAD_COPY, SHADOW, FROZEN>
+                                                    : (r.load == MOG_LOAD_HALF ? k_mog_update<MOG_LOAD_HALF, SHADOW, FROZEN> : k_mog_update<MOG_LOAD_PICK, SHADOW, FROZEN>);
         return mog_launch_update<G640>(ctx, "mog_update", kernel, frames, src_bytes, a);
     }
     const auto grid = [&](auto g) {
         using G = decltype(g);
-        return mog_launch_update<G>(ctx, r.resident ? "mog_update" : "mog_band_update", k_mog_grid_update<G::MW, G::MH, SHADOW>, frames,
+        return mog_launch_update<G>(ctx, r.resident ? "mog_update" : "mog_band_update", k_mog_grid_update<G::MW, G::MH, SHADOW, FROZEN>, frames,
                                     src_bytes, a);
     };
     return r.resident ? with_geom<G960, G320>(r.mw, grid) : with_geom<G1920, G1280>(r.mw, grid);
 }
-extern template int mog_launch_route<false>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
-                                            const MogUpdateArgs &);
-extern template int mog_launch_route<true>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
-                                           const MogUpdateArgs &);
+#define MOG_ROUTE_INSTANCE(SHADOW, FROZEN)                                                                                     \
+    template int mog_launch_route<SHADOW, FROZEN>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &, \
+                                                  const MogUpdateArgs &)
+extern MOG_ROUTE_INSTANCE(false, false);       // mog_update.hip
+extern MOG_ROUTE_INSTANCE(true, false);        // mog_shadow.hip
+extern MOG_ROUTE_INSTANCE(false, true);        // mog_frozen.hip, both
+extern MOG_ROUTE_INSTANCE(true, true);
 
 // counts [FS][2] (u32, device) = the set bits of shadow and of bits & ~shadow in each of FS planes of nword words; shadow may be
 // nullptr (then none).  mog_shadow.hip.
 int covahip_mog_counts(covahip_ctx *ctx, const unsigned long long *bits, const unsigned long long *shadow, size_t nword, size_t FS,
                        uint32_t *counts);
+
+// out u8 [streams][mh][mw][3] (device) = the background image of `streams` models from `state` on, one every state_bytes, laid
+// out at row pitch `pitch` (include/covahip.h, covahip_mog_background).  mog_frozen.hip.
+int covahip_mog_background_launch(covahip_ctx *ctx, const uint8_t *state, size_t state_bytes, int pitch, int mw, int mh, int streams,
+                                  uint8_t *out);

@@ -14,5 +14,4 @@
 #include "mog_dev.h"
 #include "mog_update.h"
 
-template int mog_launch_route<false>(covahip_ctx *, const MogRoute &, const uint8_t *, size_t, const covahip_mog_yuv_src &,
-                                     const MogUpdateArgs &);
+MOG_ROUTE_INSTANCE(false, false);

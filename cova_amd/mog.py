@@ -9,6 +9,10 @@
                at least N / 64 of the block is foreground: small objects keep their labels) or "count" (0 .. 64, for inspection)
                shadows="drop" | "keep" | (mode, tau) turns MOG2's shadow detection on (OpenCV's detectShadows, tau 0.5):
                "drop" keeps cast shadows out of the labels, "keep" only marks them (127 in debug_masks, shadow_counts)
+               save_state / load_state: one stream's model as a blob ("CVHM"; exact resume: a long recording is labelled in
+               pieces); set_frozen: label against the model without changing it (the second pass of learn-then-label);
+               background: the image the model takes for background, u8 BGR at the working size
+  read_state   a state blob's header fields and arrays, CRC verified, on the host; write_state is its inverse
   label_dims   (label_h, label_w) of a source size on either grid, without a GPU; label_dims_any / work_dims_any: of any_size
   read_bgr24   raw BGR24 frames (ffmpeg -f rawvideo -pix_fmt bgr24) from a file or stdin, in chunks
   apply_yuv    the same labels from 8-bit 4:2:0 frames as decoders give them, NV12 or I420, at a row pitch, plane offsets and
@@ -27,6 +31,8 @@
     python -m cova_amd.mog --size 1280x720 --labels count IN.bgr:IN_count.dump           (then tools/label_cover.py picks N)
     python -m cova_amd.mog --size 1280x720 --shadows drop:0.5 IN.bgr ...      (cast shadows stay out of the labels)
     python -m cova_amd.mog --size 1280x720 --shadows keep:0.4 --shadow-report IN.bgr ... (labels as without; what drop would remove)
+    python -m cova_amd.mog --size 1280x720 hour0.bgr --save-state h0.cvhm                (then: hour1.bgr --load-state h0.cvhm)
+    python -m cova_amd.mog --size 1280x720 clip.bgr --two-pass --background clip.ppm     (learn, then label against the settled model)
 
 Each input gets a stream slot; when a video ends its slot is reset and takes the next one, so every output is byte-identical
 to labelling that video alone.  The output defaults to the input's name with `_gt.dump`.  Bitstream decoding is not done here:
@@ -37,12 +43,14 @@ from __future__ import annotations
 import argparse
 import ctypes as C
 import os
+import struct
 import sys
 import time
 
 import numpy as np
 
 from . import _lib as L
+from .train import crc32c
 
 WORK_W, WORK_H = 640, 360
 LABEL_H, LABEL_W = 45, 80
@@ -57,6 +65,56 @@ ANY_MIN, ANY_MAX = 256, 4096                    # COVAHIP_MOG_ANY_*: what any_si
 LABEL_MODES = {"corner": 0, "cover": 1, "count": 2}     # COVAHIP_MOG_LABELS_*
 SHADOW_MODES = {"off": 0, "drop": 1, "keep": 2}         # COVAHIP_MOG_SHADOWS_*
 SHADOW_TAU = 0.5                                        # OpenCV's default shadow threshold
+STATE_MAGIC = 0x4D485643                                # "CVHM": a stream's model (include/covahip.h, "MoG labels", model state)
+STATE_VERSION = 1
+STATE_HEADER = 64
+
+
+def state_size(work_w: int, work_h: int) -> int:
+    """Bytes of the state blob of a work_w x work_h model: the header, 101 bytes per pixel, the CRC."""
+    return STATE_HEADER + 101 * work_w * work_h + 4
+
+
+def read_state(blob) -> dict:
+    """A state blob (MogLabeler.save_state) taken apart on the host: work_w, work_h, history, var_threshold, n and the arrays W, V
+    f32 [5][work_h][work_w], M f32 [5][3][work_h][work_w], nmodes u8 [work_h][work_w] (copies).  ValueError for what
+    covahip_mog_load_state answers COVAHIP_ERR_BAD_DATA to: a wrong magic, version, size or CRC, a nmodes above 5, n < 0."""
+    data = bytes(blob)
+    if len(data) < STATE_HEADER + 4:
+        raise ValueError(f"a state blob has at least {STATE_HEADER + 4} bytes, got {len(data)}")
+    magic, version, w, h, history, tb, n = struct.unpack_from("<IIiiifq", data, 0)
+    if magic != STATE_MAGIC or version != STATE_VERSION:
+        raise ValueError(f"not a MoG state blob: magic {magic:#x}, version {version}")
+    if w < 1 or h < 1 or len(data) != state_size(w, h):
+        raise ValueError(f"a {w}x{h} state blob has {state_size(max(w, 0), max(h, 0))} bytes, got {len(data)}")
+    if struct.unpack_from("<I", data, len(data) - 4)[0] != crc32c(memoryview(data)[:-4]):
+        raise ValueError("state blob: CRC mismatch")
+    P = w * h
+    f = np.frombuffer(data, "<f4", 25 * P, STATE_HEADER)
+    nm = np.frombuffer(data, np.uint8, P, STATE_HEADER + 100 * P)
+    if n < 0 or (nm > NMIX).any():
+        raise ValueError("state blob: n < 0 or a nmodes byte above 5")
+    return {"work_w": w, "work_h": h, "history": history, "var_threshold": tb, "n": n,
+            "W": f[:5 * P].reshape(NMIX, h, w).copy(), "V": f[5 * P:10 * P].reshape(NMIX, h, w).copy(),
+            "M": f[10 * P:].reshape(NMIX, 3, h, w).copy(), "nmodes": nm.reshape(h, w).copy()}
+
+
+def write_state(W, V, M, nmodes, n: int = 0, history: int = 9000, var_threshold: float = 32.0) -> bytes:
+    """read_state's inverse: the blob of a model given as arrays (W, V [5][h][w], M [5][3][h][w], nmodes [h][w]), for models built
+    by hand.  ValueError for shapes that do not agree, a nmodes above 5 or n < 0."""
+    nm = np.ascontiguousarray(nmodes)
+    if nm.ndim != 2 or (nm < 0).any() or (nm > NMIX).any() or n < 0:
+        raise ValueError("nmodes must be [work_h][work_w] of 0 .. 5, and n >= 0")
+    h, w = nm.shape
+    parts = []
+    for a, shape in ((W, (NMIX, h, w)), (V, (NMIX, h, w)), (M, (NMIX, 3, h, w))):
+        a = np.ascontiguousarray(a, dtype="<f4")
+        if a.shape != shape:
+            raise ValueError(f"an array of shape {a.shape}, expected {shape}")
+        parts.append(a.tobytes())
+    head = struct.pack("<IIiiifq", STATE_MAGIC, STATE_VERSION, w, h, history, var_threshold, n).ljust(STATE_HEADER, b"\0")
+    body = head + b"".join(parts) + nm.astype(np.uint8).tobytes()
+    return body + struct.pack("<I", crc32c(body))
 
 
 def shadow_mode(shadows):
@@ -357,6 +415,47 @@ class MogLabeler:
                 "covahip_dev_mog_state", self.ctx.handle)
         return {"W": W, "V": V, "M": M, "nmodes": nm, "n": int(n.value)}
 
+    def save_state(self, s: int) -> bytes:
+        """Stream s's model and frame count as a state blob (read_state takes it apart)."""
+        n = C.c_size_t()
+        L.check(self._lib.covahip_mog_state_size(self.handle, C.byref(n)), "covahip_mog_state_size")
+        buf = np.empty(n.value, np.uint8)
+        L.check(self._lib.covahip_mog_save_state(self.handle, s, _ptr(buf), buf.nbytes, C.byref(n)), "covahip_mog_save_state",
+                self.ctx.handle)
+        return buf.tobytes()
+
+    def load_state(self, s: int, blob):
+        """Stream s continues from a state blob of this working size, whatever labeller saved it: from here on it gives what the
+        saved stream would have given, bit for bit.  All or nothing: CovahipError (status 8: a damaged blob; status 1: a blob of another
+        working size) leaves the labeller as it was."""
+        data = np.frombuffer(bytes(blob), np.uint8)
+        L.check(self._lib.covahip_mog_load_state(self.handle, s, _ptr(data), data.nbytes), "covahip_mog_load_state", self.ctx.handle)
+
+    def set_frozen(self, frozen: bool, stream: int | None = None):
+        """Later calls classify stream `stream`'s frames (None: every stream's) against its model and leave the model and its
+        frame count as they are (frozen=True), or learn again (False).  reset keeps the setting."""
+        L.check(self._lib.covahip_mog_set_frozen(self.handle, -1 if stream is None else stream, int(bool(frozen))),
+                "covahip_mog_set_frozen")
+
+    @property
+    def frozen(self):
+        """Per stream, whether it is frozen: a tuple of `streams` bools."""
+        out = []
+        for s in range(self.streams):
+            v = C.c_int()
+            L.check(self._lib.covahip_mog_get_frozen(self.handle, s, C.byref(v)), "covahip_mog_get_frozen")
+            out.append(bool(v.value))
+        return tuple(out)
+
+    def background(self, s: int | None = None) -> np.ndarray:
+        """The background image of stream s's model, u8 [work_h][work_w][3] (B, G, R); None: of every stream, [S][work_h][work_w][3].
+        OpenCV's getBackgroundImage: the weighted mean of the modes whose weights add up to just above 0.9."""
+        shape = (self.work_h, self.work_w, 3)
+        out = np.empty(shape if s is not None else (self.streams,) + shape, np.uint8)
+        L.check(self._lib.covahip_mog_background(self.handle, -1 if s is None else s, _ptr(out), out.nbytes, L.MEM_HOST),
+                "covahip_mog_background", self.ctx.handle)
+        return out
+
     def debug_masks(self):
         """(raw, filled) of the last apply call, u8 [F][S][work_h][work_w]: the MOG2 mask (0 / 255; with shadow detection on 0 / 127 / 255,
         127 = shadow, in "drop" and in "keep" mode alike) and the mask after close, open and hole fill (0 / 1)."""
@@ -637,6 +736,21 @@ def _args(argv):
     ap.add_argument("--shadow-report", action="store_true",
                     help="print, per input, the mean share of shadow and of foreground pixels per frame (how TAU gets chosen for a "
                          "camera); needs --shadows drop or keep")
+    ap.add_argument("--load-state", nargs="+", action="extend", default=None, metavar="FILE",
+                    help="one state blob per input, in order (give the inputs first): the input's slot starts from the blob's model "
+                         "and frame count instead of an empty model")
+    ap.add_argument("--save-state", nargs="+", action="extend", default=None, metavar="FILE",
+                    help="one file per input, in order: the model is written there when the input ends (with --two-pass: the model "
+                         "its first pass ended with)")
+    ap.add_argument("--frozen", action="store_true",
+                    help="label without learning: every frame is classified against the loaded model, which stays as it is; needs "
+                         "--load-state")
+    ap.add_argument("--two-pass", action="store_true",
+                    help="per input, a first pass learns and writes nothing; then the input is read again and labelled against the "
+                         "learned model, frozen: the start of a clip gets a settled model.  Files only")
+    ap.add_argument("--background", nargs="+", action="extend", default=None, metavar="FILE",
+                    help="one binary PPM (RGB) per input, in order: the model's background image at the working size, written when "
+                         "the input ends")
     ap.add_argument("--streams", type=int, default=None, help="videos labelled side by side (default: inputs, at most 8)")
     ap.add_argument("--chunk", type=int, default=16, help="frames per stream and call")
     ap.add_argument("--history", type=int, default=9000)
@@ -681,8 +795,22 @@ def _args(argv):
     if sum(src == "-" for src, _ in a.inputs) > 1:
         ap.error("stdin ('-') can be read once")
     outs = [out for _, out in a.inputs]
+    for opt, files in (("--load-state", a.load_state), ("--save-state", a.save_state), ("--background", a.background)):
+        if files is not None and len(files) != len(a.inputs):
+            ap.error(f"{opt} takes one file per input: {len(files)} for {len(a.inputs)} inputs")
+        if files is not None and opt != "--load-state":
+            outs = outs + files
     if len(set(outs)) != len(outs):
         ap.error("two inputs write the same output")
+    if a.frozen and a.load_state is None:
+        ap.error("--frozen needs --load-state: an empty model calls everything foreground")
+    if a.two_pass and a.frozen:
+        ap.error("--two-pass learns in its first pass: it cannot go with --frozen")
+    if a.two_pass and any(src == "-" for src, _ in a.inputs):
+        ap.error("--two-pass reads every input twice: stdin ('-') cannot be one")
+    for f in a.load_state or ():
+        if not os.path.isfile(f):
+            ap.error(f"--load-state {f}: no such file")
     return a
 
 
@@ -734,7 +862,7 @@ def main(argv=None) -> int:
         y4m_range[0] = a.range          # from here on a header that names a range names this one
     w, h = a.size
     S = min(a.streams, len(a.inputs))
-    pending = list(a.inputs)
+    pending = [(i,) + io for i, io in enumerate(a.inputs)]
     yuv = a.format != "bgr24"
     ctx = Context(a.device)
     mog = MogLabeler(ctx, w, h, streams=S, history=a.history, var_threshold=a.var_threshold, grid=a.grid, any_size=a.any_size is not None,
@@ -742,7 +870,7 @@ def main(argv=None) -> int:
     layout = yuv_tight(w, h, "nv12" if a.format == "nv12" else "i420", a.range, streams=S) if yuv else None
     frames = np.empty((a.chunk, S, w * h * 3 // 2) if yuv else (a.chunk, S, h, w, 3), np.uint8)
     labels = np.zeros((a.chunk, S, mog.label_h, mog.label_w), np.uint8)
-    slots = [None] * S           # (source, output file, output name, start time) per stream slot
+    slots = [None] * S           # [source, output file, output name, start time, input index, first pass of two] per stream slot
     npix = mog.work_w * mog.work_h
     tally = [[0, 0] for _ in range(S)]      # --shadow-report: shadow and foreground pixels of the slot's video so far
 
@@ -750,15 +878,39 @@ def main(argv=None) -> int:
         if not pending:
             slots[s] = None
             return
-        src, out = pending.pop(0)
-        source = (y4m_open(src) if a.format == "y4m" else _RawSource(src, w * h * 3 // 2) if yuv else _Bgr24Source(src, w, h))
-        slots[s] = (source, open(out, "wb"), out, time.perf_counter())
+        i, src, out = pending.pop(0)
+        slots[s] = [open_source(src), open(out, "wb"), out, time.perf_counter(), i, a.two_pass]
         tally[s] = [0, 0]
-        mog.reset(s)
+        mog.set_frozen(a.frozen, s)
+        if a.load_state is None:
+            mog.reset(s)
+        else:
+            with open(a.load_state[i], "rb") as f:
+                mog.load_state(s, f.read())
+
+    def open_source(src):
+        return y4m_open(src) if a.format == "y4m" else _RawSource(src, w * h * 3 // 2) if yuv else _Bgr24Source(src, w, h)
+
+    def save_state(s):
+        if a.save_state is not None:
+            with open(a.save_state[slots[s][4]], "wb") as f:
+                f.write(mog.save_state(s))
 
     def finish(s):
-        src, f, out, t0 = slots[s]
+        """The slot's input has ended.  True: the slot is done with it; False: its first pass is, and the second begins."""
+        src, f, out, t0, i, learning = slots[s]
         src.close()
+        if learning:                   # --two-pass: the model is learned; now the same frames, frozen
+            save_state(s)
+            slots[s][0], slots[s][5] = open_source(src.name), False
+            tally[s] = [0, 0]
+            mog.set_frozen(True, s)
+            return False
+        if not a.two_pass:
+            save_state(s)
+        if a.background is not None:
+            with open(a.background[i], "wb") as g:
+                g.write(b"P6\n%d %d\n255\n" % (mog.work_w, mog.work_h) + np.ascontiguousarray(mog.background(s)[..., ::-1]).tobytes())
         f.close()
         dt = time.perf_counter() - t0
         print(f"{src.name}: {src.frames} frames, {src.frames / dt if dt > 0 else 0.0:.1f} frames/s -> {out}", file=sys.stderr)
@@ -766,6 +918,7 @@ def main(argv=None) -> int:
             per = max(src.frames, 1) * npix
             print(f"{src.name}: shadow {tally[s][0] / per:.6f} foreground {tally[s][1] / per:.6f} of {npix} pixels per frame, "
                   f"{src.frames} frames, --shadows {a.shadows[0]}:{a.shadows[1]:g}")
+        return True
 
     try:
         for s in range(S):
@@ -780,8 +933,8 @@ def main(argv=None) -> int:
                     if k:
                         nv[s] = k
                         break
-                    finish(s)          # this video has ended: the slot takes the next one
-                    open_next(s)
+                    if finish(s):      # this video has ended: the slot takes the next one
+                        open_next(s)
             if not nv.any():
                 break
             if yuv:
@@ -791,10 +944,12 @@ def main(argv=None) -> int:
             if a.shadow_report:
                 sh, fg = mog.shadow_counts()
                 for s in range(S):
+                    if slots[s] is None or slots[s][5]:
+                        continue
                     tally[s][0] += int(sh[:, s].sum())
                     tally[s][1] += int(fg[:, s].sum())
             for s in range(S):
-                if nv[s]:
+                if nv[s] and not slots[s][5]:
                     slots[s][1].write(np.ascontiguousarray(labels[:nv[s], s]).tobytes())
     finally:
         for s in range(S):

@@ -975,6 +975,63 @@ int  covahip_mog_apply_yuv(covahip_mog *m, const covahip_mog_yuv *lay, const uin
                            const int32_t *n_valid, uint8_t *labels, int mem_kind);
 /* Next video in that slot: model zeroed, n = 0. */
 int  covahip_mog_reset(covahip_mog *m, int stream);
+/* Model state: one stream's model as ONE little-endian blob, to keep, to look at and to put back.
+ *   offset  0  u32 magic "CVHM" (0x4D485643)     4  u32 version = 1        8  i32 work_w        12  i32 work_h
+ *          16  i32 history     20  f32 var_threshold (the creating cfg, for information: not compared)
+ *          24  i64 n (frames the stream has learned from)                  32 .. 63 zero
+ *          64  f32 W[5][P], f32 V[5][P], f32 M[5][3][P], u8 nmodes[P]      P = work_w * work_h, rows dense at work_w whatever
+ *              pitch the device uses (a covahip_mog_create_any labeller keeps its rows at work_w rounded up to 64)
+ *          end u32 CRC-32C (Castagnoli, as the trainer state uses it, unmasked) of every byte before it
+ *   64 + 101 P + 4 bytes: about 23 MB at 640x360.  Label mode, shadow mode and the frozen flag are settings, not state: they are
+ *   not in the blob, as the trainer's post is not in its checkpoint.
+ *   Contract -- exact resume.  Save stream s of any labeller after any sequence of calls and load the blob into stream t of any
+ *   labeller of the same working size: any source size, either grid, the table's kernels or the any-size ones, any number of
+ *   streams.  From then on, on frames whose working images are equal, both streams give bit-identical raw masks, filled masks,
+ *   labels, shadow counts and models; the stream's frame count is the blob's n, so the automatic learning rate continues where
+ *   it was.  save -> load -> save gives the same bytes.
+ * covahip_mog_state_size / covahip_mog_save_state: *n = the blob's size; COVAHIP_ERR_OVERFLOW when buf is NULL or cap < *n (as
+ * covahip_train_save_state).  Host memory, synchronous.
+ * covahip_mog_load_state: all or nothing, validated before anything is copied.  Wrong magic / version / size / CRC, a nmodes byte
+ * above 5, n < 0: COVAHIP_ERR_BAD_DATA; work_w / work_h not the labeller's, a bad stream, a NULL argument:
+ * COVAHIP_ERR_INVALID_ARG.  In every refusal the labeller is untouched. */
+int  covahip_mog_state_size(const covahip_mog *m, size_t *n);
+int  covahip_mog_save_state(covahip_mog *m, int stream, void *buf, size_t cap, size_t *n);
+int  covahip_mog_load_state(covahip_mog *m, int stream, const void *buf, size_t n);
+/* Frozen labelling, per stream (stream = -1: all of them; frozen 0 or 1, anything else COVAHIP_ERR_INVALID_ARG).  The setting
+ * holds for later covahip_mog_apply / covahip_mog_apply_yuv calls, covahip_mog_reset keeps it, and a new labeller has none frozen.
+ * A frozen stream's frames are classified against its model; the model and n are not changed by the call.  This is the
+ * well-defined form of OpenCV's apply(frame, 0), which is not safe in the letter of MOG2Invoker: a pixel that no mode fits opens
+ * a mode of weight alphaT = 0, and the next pixel that fits it computes k = alphaT / w = 0 / 0.  So it is a
+ * mode of its own, read-only, and not a learning rate.  Per pixel, f32, every product and sum rounded on its own:
+ *       bg = false; tw = 0
+ *       for mode = 0 .. nmodes - 1:
+ *           d = M[mode] - data;  dist2 = (d0*d0 + d1*d1) + d2*d2
+ *           if tw < TB && dist2 < Tb * V[mode]: bg = true
+ *           if dist2 < Tg * V[mode]: stop          (the first mode that fits ends the walk, as in the update)
+ *           tw = tw + W[mode]
+ *       mask = bg ? 0 : 255
+ * That is exactly the mask steps 1 - 5 give at alphaT = 0 on a model of finite values, with nothing written.  With shadows in
+ * _DROP or _KEEP the test of step 2a runs where bg is false, on the model AS IT IS: there is no updated model and no new mode.
+ * Close, open, fill and labels run as ever.  An empty model (after reset) gives all foreground.  A call with learning and frozen
+ * streams runs the update kernel on the former and the frozen one on the latter; per stream the result is bit-identical to a
+ * labeller that holds that stream alone.  With no stream frozen a call launches exactly the kernels it did before this
+ * setting existed.  A fixed learning rate (apply(frame, lr)) is not offered.  covahip_mog_get_frozen gives one stream's
+ * setting (0 <= stream < n_streams). */
+int  covahip_mog_set_frozen(covahip_mog *m, int stream, int frozen);
+int  covahip_mog_get_frozen(const covahip_mog *m, int stream, int *frozen);
+/* The background image the model believes in: u8 [work_h][work_w][3] (B, G, R) of one stream, dense; stream = -1: all streams,
+ * [n_streams][work_h][work_w][3].  cap: bytes at bgr; COVAHIP_ERR_OVERFLOW when bgr is NULL or cap is less than that.  mem_kind
+ * applies to bgr.  Synchronous; only reads the model.  It is getBackgroundImage_intern of OpenCV 4.x bgfg_gaussmix2.cpp,
+ * restated: this text is the contract.  Per pixel, f32, every product and sum rounded on its own:
+ *       acc_c = 0; tw = 0
+ *       for mode = 0 .. nmodes - 1:
+ *           acc_c = acc_c + W[mode] * M[mode][c]   (c = 0, 1, 2)
+ *           tw = tw + W[mode]
+ *           if tw > TB: stop
+ *       inv = |tw| > FLT_EPSILON ? 1 / tw (correctly rounded) : 0
+ *       out_c = saturate_u8(round_half_even(acc_c * inv))
+ * An empty model gives (0, 0, 0). */
+int  covahip_mog_background(covahip_mog *m, int stream, uint8_t *bgr, size_t cap, int mem_kind);
 void covahip_mog_destroy(covahip_mog *m);
 
 /* ------------------------------------------------------ sink formats, track export

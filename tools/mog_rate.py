@@ -11,6 +11,10 @@
                                  (the label modes side by side: one labeller each, timed call by call in turn)
     python tools/mog_rate.py --sizes 1280x720 --streams 4 --frames 256 --shadows off,drop,keep --no-host
                                  (shadow detection side by side: one labeller per mode, in the same turn-by-turn loop)
+    python tools/mog_rate.py --sizes 1280x720 --streams 4 --frames 256 --frozen off,on --no-host
+                                 (frozen labelling beside learning: one labeller each; the frozen one learns the warm-up call first)
+    python tools/mog_rate.py --grid macroblock --sizes 1280x720,3840x2160 --streams 1 --frames 8 --background --no-host
+                                 (covahip_mog_background to device memory: ms per call beside the bytes it moves)
 
 Two cases per (source size, streams), one JSON line each:
   device   frames and labels in device memory, the call timed with HIP events (both kernels and the per-call setup);
@@ -24,7 +28,10 @@ at a size the table has too, the table's labeller ("device") is timed in the sam
 turn, so the two lines compare.  --labels lists label modes (corner, cover[:N], count): every device case is timed once per mode
 ("device[cover:1]"), in the same turn-by-turn loop.  --shadows lists shadow modes (off, drop[:TAU], keep[:TAU]) the same way
 ("device[drop]"; with both lists every pair is a case); a line of a mode other than off has a "shadows" key and the clip's mean
-share of shadow and foreground pixels per frame, which is what the shadow test's cost depends on.
+share of shadow and foreground pixels per frame, which is what the shadow test's cost depends on.  --frozen lists off and / or on:
+"device[frozen]" is a labeller that learned the warm-up call and was frozen then (covahip_mog_set_frozen), timed in the same
+loop.  --background adds a line per (size, streams) with the time of covahip_mog_background of all streams into device memory,
+the bytes of model it reads at most (101 per pixel) and the bytes it writes (3 per pixel).
 """
 import argparse
 import json
@@ -88,7 +95,11 @@ def main():
     ap.add_argument("--general", action="store_true", help="the general kernels (any even size of 256 .. 4096; implies --grid macroblock)")
     ap.add_argument("--labels", default="corner", help="label modes to time, comma-separated: corner, cover[:N], count")
     ap.add_argument("--shadows", default="off", help="shadow modes to time, comma-separated: off, drop[:TAU], keep[:TAU]")
+    ap.add_argument("--frozen", default="off", help="off, on or both, comma-separated: time learning and / or frozen labellers")
+    ap.add_argument("--background", action="store_true", help="also time covahip_mog_background (all streams, device memory)")
     a = ap.parse_args()
+    if not set(a.frozen.split(",")) <= {"off", "on"}:
+        ap.error("--frozen takes off, on or off,on")
     try:
         label_modes = [(t, mog.parse_labels(t)) for t in a.labels.split(",")]
         shadow_modes = [(t, mog.parse_shadows(t)) for t in a.shadows.split(",")]
@@ -118,13 +129,14 @@ def main():
             cases = {}
             for lt, lm in label_modes:
                 for st, sm in shadow_modes:
-                    tags = [t for t, plain in ((lt, "corner"), (st, "off")) if t != plain]
-                    tag = f"[{','.join(tags)}]" if tags else ""
-                    if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
-                        cases["device" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, labels=lm, shadows=sm)
-                    if a.general:
-                        cases["device_general" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True, labels=lm,
-                                                                       shadows=sm)
+                    for fz in a.frozen.split(","):
+                        tags = [t for t, plain in ((lt, "corner"), (st, "off"), ("frozen" if fz == "on" else "", "")) if t != plain]
+                        tag = f"[{','.join(tags)}]" if tags else ""
+                        if not a.general or (w, h) in mog.GRID_SIZES[a.grid]:
+                            cases["device" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, labels=lm, shadows=sm)
+                        if a.general:
+                            cases["device_general" + tag] = mog.MogLabeler(ctx, w, h, streams=S, grid=a.grid, force_general=True,
+                                                                           labels=lm, shadows=sm)
             d_f, d_l = ctx.malloc(frames.nbytes), ctx.malloc(labels.nbytes)
             ctx.h2d(d_f, frames)
 
@@ -140,8 +152,11 @@ def main():
                 else:
                     m.apply(frames, labels=labels)
 
-            for m in cases.values():
+            for case, m in cases.items():
                 apply_device(m)                              # warm-up (buffers, code objects)
+                if "frozen" in case:                         # from here on against the model of the warm-up call
+                    m.set_frozen(True)
+                    apply_device(m)
             ms = {case: [] for case in cases}
             for _ in range(a.reps):
                 for case, m in cases.items():
@@ -166,9 +181,24 @@ def main():
                     rec.update(shadows=f"{m.shadows[0]}:{m.shadows[1]:g}", shadow_share=round(float(sh.mean()) / npix, 5),
                                foreground_share=round(float(fg.mean()) / npix, 5))
                 print(json.dumps(rec), flush=True)
+            m = list(cases.values())[-1]
+            if a.background:
+                npix = m.work_w * m.work_h
+                d_b = ctx.malloc(S * npix * 3)
+                bg = []
+                for i in range(a.reps + 1):                  # (the first call loads the code object)
+                    ctx.timer_start(0)
+                    mog.L.check(m._lib.covahip_mog_background(m.handle, -1, d_b, S * npix * 3, mog.L.MEM_DEVICE), "covahip_mog_background")
+                    ctx.timer_stop(0)
+                    bg.append(ctx.timer_ms(0))
+                ctx.free(d_b)
+                med = statistics.median(bg[1:])
+                print(json.dumps({"case": "background_general" if m.general else "background", "src": size, "grid": a.grid, "streams": S,
+                                  "work": f"{m.work_w}x{m.work_h}", "ms_per_call": round(med, 4), "read_mb_at_most": round(S * npix * 101 / 1e6, 2),
+                                  "write_mb": round(S * npix * 3 / 1e6, 2), "gb_per_s_at_most": round(S * npix * 104 / med / 1e6, 1),
+                                  "ms_all": [round(x, 4) for x in bg[1:]]}), flush=True)
             ctx.free(d_f)
             ctx.free(d_l)
-            m = list(cases.values())[-1]
             if not a.no_host:
                 apply_host()
                 wall = []
