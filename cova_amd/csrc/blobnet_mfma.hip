@@ -237,6 +237,19 @@ __device__ __forceinline__ void lds_barrier_vmem_but() {
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
 }
+// The issue order of a product loop whose LDS fragments come through a ring of AD registers, AD reads ahead of their use: left to
+// itself hipcc schedules "ds_read_b128; s_waitcnt lgkmcnt(0); v_mfma" with one fragment register, and with two to four waves per
+// SIMD the matrix pipe then idles for most of every LDS latency.  Called right behind the (unrolled) loop of NS reads, it pins
+// AD LDS reads in front, then PER MFMAs and -- while reads remain -- one LDS read per step.
+template <int NS, int AD, int PER = 1>
+__device__ __forceinline__ void pin_ring() {
+    __builtin_amdgcn_sched_group_barrier(0x100, AD, 0);
+#pragma unroll
+    for (int s = 0; s < NS; s++) {
+        __builtin_amdgcn_sched_group_barrier(0x008, PER, 0);
+        if (s + AD < NS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+    }
+}
 
 // LDS pixel swizzle: the 16-byte chunk c of tile pixel (xx, yy) sits at chunk c ^ s(xx, yy).  s comes
 // from a small linear family whose parameters the host picks per level and band geometry with a
@@ -308,7 +321,7 @@ struct EncArgs {
     uint32_t mWp, mNb, mRC;
     const void *zero;  // >= 16 zero bytes in global memory (source of halo / padding chunks)
     Swz swz;           // LDS pixel swizzle of this launch (choose_swz)
-    int scr_off;       // byte offset of the per-wave output transpose scratch (2 KB per wave) in LDS (WIDE)
+    int scr_off;       // byte offset of the per-wave output transpose scratch (2 KB per wave) in LDS
     int nbuf, buf_stride;   // LDS band buffers (1 or 2) and their distance in bytes
     ItemPlan plan;
     // PRE (level 1 of the carrier-frame path): `in` is the tensor P of enc0p_mfma, [F][H][W][CIN]; stack b takes its
@@ -505,7 +518,7 @@ __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
         const int rows = 2 * (((band + 1) * p.Hp) / p.nbands) - y0;
         const int n2 = rows + 2;
         lds_barrier();
-        {   // stage rows y0-1 .. y0+rows as fp16 (see enc0_mfma); the host keeps n2 * W/4 <= 2 * WG0
+        {   // stage rows y0-1 .. y0+rows as fp16 (the u8 -> fp16 conversion described above WG0); the host keeps n2 * W/4 <= 2 * WG0
             const int W4 = p.W >> 2;
             const int per_t = n2 * W4;
             // PACKED: two bytes per macroblock, min(type, 6) | min(mv_x, 6) << 3 | min(mv_y, 6) << 6 (covahip_carrier_pack) --
@@ -596,7 +609,7 @@ __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
                 co_ = __builtin_amdgcn_mfma_f32_16x16x32_f16(ao1, bo1, co_, 0, 0, 0);
                 _Float16 *sw = reinterpret_cast<_Float16 *>(scr + (k * 8 + 2 * g) * 32) + co;
                 // the fp32 value is made opaque before the conversion: hipcc would otherwise fuse the BN multiply-add and
-                // the conversion into one v_fma_mixlo_f16 (ONE rounding), while enc0_mfma rounds to fp32 and then to fp16
+                // the conversion into one v_fma_mixlo_f16 (ONE rounding), while the level's other forms round to fp32 and then to fp16
                 float v0 = pool4<ALLPOS>(ce[0], ce[1], co_[0], co_[1], e0, e1, e2);
                 float v1 = pool4<ALLPOS>(ce[2], ce[3], co_[2], co_[3], e0, e1, e2);
                 asm volatile("" : "+v"(v0), "+v"(v1));
@@ -629,7 +642,7 @@ __global__ __launch_bounds__(WG0, 4) void enc0p_mfma(Enc0pArgs p) {
 //     [tile base: wave-uniform] + [lane constant of the tap, set once per kernel] ^ [channel chunk << 5] + [T slice: immediate],
 // i.e. one add per tap and one xor per further channel chunk per tile, where the general form below evaluates the swizzle and
 // the pixel address for every tap of every tile (216 of the 270 vector instructions of a level-2 tile's matrix part).
-template <int CIN, int COUT, int TPAR, int OCC, int NWV, bool WIDE, bool ALLPOS, bool PRE = false, int TSZ = 0, bool MS = false>
+template <int CIN, int COUT, int TPAR, int OCC, int NWV, bool ALLPOS, bool PRE = false, int TSZ = 0, bool MS = false>
 __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
     constexpr int WGS = NWV * 64;
     constexpr int NT = COUT / 32, MG = NWV / NT, KC = CIN / 16, KSTEPS = 9 * KC;
@@ -860,9 +873,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
             // four slices are kept for the temporal MLP.
             half4 pb4[4];   // the pooled values of window g, T = 0..3, already as the temporal MLP's fp16 operand
             // The A fragments come through a ring of AD registers, AD MFMAs ahead of their use, across taps and across the
-            // T groups: left to itself hipcc schedules "ds_read_b128; s_waitcnt lgkmcnt(0); v_mfma" with one fragment
-            // register, and with two to four waves per SIMD the matrix pipe then idles for most of every LDS latency.
-            // sched_group_barrier (below the loop) pins that issue order.
+            // T groups; pin_ring (below the loop) pins that issue order.
             constexpr int NSG = 9 * KC * TPAR;            // MFMAs per T group
             constexpr int NS = NSG * (BN_T / TPAR);       // MFMAs per tile
             auto frag = [&](int s) -> half8 {
@@ -901,7 +912,7 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
                                                                                   acc[tt][4 * g + 3], e0, e1, e2);
                     }
                 }
-                // the issue order of the matrix and LDS-read instructions above: AD reads, then one read behind every MFMA
+                // pin_ring<NS, AD>(), written out: called as the function, this kernel's register allocation comes out differently
                 __builtin_amdgcn_sched_group_barrier(0x100, AD, 0);
 #pragma unroll
                 for (int s = 0; s < NS; s++) {
@@ -962,9 +973,10 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
             // lets the other three outputs of the temporal MLP and their stores fall away at compile time
             const int To = COUT == 128 ? 1 : p.To;
             __half *const ob = p.out + (size_t)b * To * tstride;   // wave-uniform; lanes add a 32-bit offset
-            if constexpr (WIDE) {
-                // wave-private LDS transpose (see enc0_mfma): S[t][window][32 channels], two 16-byte
-                // pieces per lane -> two global_store_dwordx4 per tile instead of sixteen 2-byte stores
+            {
+                // wave-private LDS transpose: lanes drop their fp16 values as S[t][window][32 channels] into the wave's 2 KB of
+                // scratch and take them back as two 16-byte pieces per lane -> two global_store_dwordx4 per tile instead of
+                // sixteen 2-byte stores
                 uint8_t *const scr = smem + p.scr_off + wave * 2048;
                 half4 o4[4];
                 if constexpr (CIN == 64) {   // 144 weight registers: one element at a time
@@ -994,27 +1006,6 @@ __global__ __launch_bounds__(NWV * 64, OCC) void enc_mfma(EncArgs p) {
                             const uint4 v = *reinterpret_cast<const uint4 *>(scr + (j * 64 + ll) * 16);
                             *reinterpret_cast<uint4 *>(ob + t * tstride + eo) = v;
                         }
-                    }
-                }
-            } else {
-                half4 o4[4];
-                if constexpr (CIN == 64) {   // 144 weight registers: one element at a time
-#pragma unroll
-                    for (int g = 0; g < 4; g++) tmix4h(tm, pb4[g], o4[g]);
-                } else {
-                    tmix4h<4>(tm, pb4, o4);
-                }
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    const half4 o = o4[g];
-                    const int owin = (TSZ > 0 ? 8 * t_tc : tile * 8) + 2 * g + kh;
-                    if (owin < (TSZ > 0 ? p.Wp : nwin)) {
-                        const int owy = TSZ > 0 ? t_wy : (int)fdiv(owin, p.mWp), owx = TSZ > 0 ? owin : owin - owy * p.Wp;
-                        const int gy = y0 / 2 + owy + p.oy, gx = owx + p.ox;
-                        const uint32_t eo = (uint32_t)((gy * p.Wo + gx) * COUT + co);
-#pragma unroll
-                        for (int t = 0; t < BN_T; t++)
-                            if (t < To) reinterpret_cast<_Float16 *>(ob + t * tstride)[eo] = o[t];
                     }
                 }
             }
@@ -1400,12 +1391,7 @@ __global__ __launch_bounds__(512, 4) void enc1_mfma(Enc1Args p) {
                     }
                 }
             }
-            __builtin_amdgcn_sched_group_barrier(0x100, AD, 0);
-#pragma unroll
-            for (int k = 0; k < 20; k++) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                if (k + AD < 20) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-            }
+            pin_ring<20, AD, 2>();   // (two products per fragment)
 #if E1_ABL == 3
             asm volatile("" :: "v"(tw.x), "v"(e0[0]), "v"(e1[0]), "v"(e0[1]), "v"(e1[1]));
             continue;
@@ -1614,12 +1600,7 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
                     acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ab[i % AD], bf[i >> 1], acc[t], 0, 0, 0);
                     if (i + AD < NS) ab[i % AD] = frag(i + AD);
                 }
-                __builtin_amdgcn_sched_group_barrier(0x100, AD, 0);
-#pragma unroll
-                for (int i = 0; i < NS; i++) {
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    if (i + AD < NS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                }
+                pin_ring<NS, AD>();
                 // pooled values of windows 2g + kh (g = 0..3) for the wave's T slices, rounded to fp16 (the MLP's operand)
                 half2v hp[4];
 #pragma unroll
@@ -1776,6 +1757,128 @@ __global__ __launch_bounds__(512, 2) void enc23_mfma(Enc23Args p) {
 // of 4 consecutive output channels -> one (u,v) decomposition per lane per tile and 8-byte packed
 // stores.  The last block (FINAL) has the final 1x1 conv folded in (no non-linearity between
 // them): 4 rows = the 4 parities, output = logit (+ threshold).
+
+// ---- the pieces that the decoder kernels share: each form calls them, so "the same products in the same order, the same epilogue
+// expression" holds between the forms by construction
+// A band's tile by LDS-DMA: concat(up, skip[t=0]) rows u0-1 .. u0+nu-1 of frame b, swept linearly in 16-byte chunks (64 per wave
+// instruction), swizzled; chunks outside the frame read the zero buffer.  Both sources hold relu'd values.  NW waves.
+template <int C1, int C2, int NW>
+__device__ __forceinline__ void dec_stage_band(const DecArgs &p, int b, int u0, int nu, uint8_t *dst, int wave, int lane) {
+    constexpr int C = C1 + C2, CPP = C / 8;
+    const int RC = (p.Wi + 2) * CPP;
+    const int nchunk = (nu + 1) * RC;
+    [[maybe_unused]] const __half *su = p.up + ((size_t)b) * p.Hi * p.Wi * C1;
+    [[maybe_unused]] const __half *ss = p.skip + ((size_t)b * p.Ts) * p.Hi * p.Wi * C2;
+    for (int s0 = wave * 64; s0 < nchunk; s0 += NW * 64) {
+        const int sidx = s0 + lane;
+        if (sidx < nchunk) {
+            const int r = fdiv(sidx, p.mRC), within = sidx - r * RC;
+            const int c = within / CPP, chp = within % CPP;
+            const int cb = (chp ^ swz_eval<CPP>(p.swz, c, r)) * 8;
+            const int y = u0 - 1 + r, x = c - 1;
+            const void *src = p.zero;
+            if (y >= 0 && y < p.Hi && x >= 0 && x < p.Wi) {
+                const size_t pix = (size_t)y * p.Wi + x;
+                if constexpr (C1 == 0) src = ss + pix * C2 + cb;
+                else if constexpr (C2 == 0) src = su + pix * C1 + cb;
+                else src = cb < C1 ? (const void *)(su + pix * C1 + cb) : (const void *)(ss + pix * C2 + (cb - C1));
+            }
+            glds16(src, dst + s0 * 16);
+        }
+    }
+}
+// The products of one tile of 32 grid positions: the lane's position is (ul, v) of the band in `tile` (TC pixels per row), 2x2
+// taps x C / 16 channel chunks in this order
+template <int C>
+__device__ __forceinline__ f32x16 dec_tile_acc(const uint8_t *tile, int TC, const Swz &swz, const half8 (&wf)[4 * (C / 16)], int ul, int v, int kh) {
+    constexpr int KC = C / 16, CPP = C / 8, PS = C * 2;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; r++) acc[r] = 0.f;
+#pragma unroll
+    for (int a = 0; a < 2; a++)
+#pragma unroll
+        for (int bb = 0; bb < 2; bb++) {
+            const int yy = ul + 1 - a, xx = v + 1 - bb;   // tile coordinates of input (u-a, v-b)
+            const int pbase = (yy * TC + xx) * PS;
+            const int s = swz_eval<CPP>(swz, xx, yy);
+#pragma unroll
+            for (int kc = 0; kc < KC; kc++) {
+                const half8 av = *reinterpret_cast<const half8 *>(tile + pbase + (((kc * 2 + kh) ^ s) * 16));
+                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[(a * 2 + bb) * KC + kc], av, acc, 0, 0, 0);
+            }
+        }
+    return acc;
+}
+// The last block's output of grid position (u, v) of frame b, for a lane of the kh == 0 half: accumulator rows 0..3 = the four
+// output parities (py, px) = (r >> 1, r & 1).  Logit = product + folded bias (+ PART: the position's partial logits, `part` = the
+// frame's), stored when the caller asked for logits; mask byte = logit > threshold (&& POST: keep map) into `mask`, LDS bytes
+// [row][Wd] that start at frame row Y0.
+template <bool PART, bool POST>
+__device__ __forceinline__ void dec_final_out(const DecArgs &p, const StackPost &sp, const f32x16 acc, float fbias, const f32x4 *part, int b, int u, int v,
+                                              uint8_t *mask, int Y0) {
+    const int GW = p.Wi + 1;
+    f32x4 pl = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (PART) pl = part[u * GW + v];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const int Y = 2 * u + (r >> 1) - p.cy, X = 2 * v + (r & 1) - p.cx;
+        if (Y >= 0 && Y < p.Hd && X >= 0 && X < p.Wd) {
+            float l = acc[r] + fbias;
+            if constexpr (PART) l += pl[r];
+            if (p.logits) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l;
+            bool fg = l > sp.thr;
+            if constexpr (POST) fg = fg && sp.keep[Y * p.Wd + X];
+            mask[(Y - Y0) * p.Wd + X] = fg ? 1 : 0;
+        }
+    }
+}
+// mask bytes LDS -> global memory, four at a time where the caller's alignment condition holds.  NTH threads.
+template <int NTH>
+__device__ __forceinline__ void dec_mask_out(const uint8_t *src, uint8_t *dst, int nbytes, bool aligned4, int tid) {
+    if (aligned4) {
+        for (int i = tid; i < nbytes / 4; i += NTH) reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(src)[i];
+    } else {
+        for (int i = tid; i < nbytes; i += NTH) dst[i] = src[i];
+    }
+}
+// ReLU(BN(acc)) of register group g (four consecutive output channels) as fp16
+__device__ __forceinline__ half4 dec_relu_bn4(const f32x16 acc, const float (&es)[16], const float (&eb)[16], int g) {
+    half4 o;
+#pragma unroll
+    for (int j = 0; j < 4; j++) o[j] = (_Float16)fmaxf(acc[4 * g + j] * es[4 * g + j] + eb[4 * g + j], 0.f);
+    return o;
+}
+// A frame's partial logits (src: fp32 [npos][4 parities]) into LDS: one 16-byte piece per grid position.  NW waves.
+template <int NW>
+__device__ __forceinline__ void dec_stage_part(const float *src, int npos, uint8_t *dst, int wave, int lane) {
+    const uint8_t *ps = reinterpret_cast<const uint8_t *>(src);
+    for (int s0 = wave * 64; s0 < npos; s0 += NW * 64)
+        if (s0 + lane < npos) glds16(ps + (size_t)(s0 + lane) * 16, dst + s0 * 16);
+}
+
+// A wave's weight fragments of M-tile mtile and its epilogue constants per register: reg 4g+j <-> row 8g + 4kh + j <-> (parity, co = row % COUT);
+// the last block has its folded bias instead.  A register group's four consecutive channels are one 16-byte load each of scale and
+// shift: epi is 16-byte aligned (the prepared blocks start at multiples of 256 bytes, and so does a model's stride under MS), as
+// dec012_load relies on for the same arrays
+template <int KSTEPS, int COUT, bool FINAL>
+__device__ __forceinline__ void dec_load_w(half8 (&wf)[KSTEPS], float (&es)[16], float (&eb)[16], float &fbias, const half8 *wfrag, const float *epi,
+                                           int mtile, int lane, int kh) {
+    static_assert(FINAL || (COUT % 4 == 0 && (COUT & (COUT - 1)) == 0), "a register group's four channels do not wrap");
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = wfrag[(mtile * KSTEPS + ks) * 64 + lane];
+    if constexpr (!FINAL) {   // registers 4g .. 4g+3: four consecutive channels, one 16-byte load each of scale and shift
+#pragma unroll
+        for (int g = 0; g < 4; g++) {
+            const int c0 = (mtile * 32 + 8 * g + 4 * kh) & (COUT - 1);
+            const f32x4 sc = *reinterpret_cast<const f32x4 *>(epi + c0), sh = *reinterpret_cast<const f32x4 *>(epi + COUT + c0);
+#pragma unroll
+            for (int j = 0; j < 4; j++) { es[4 * g + j] = sc[j]; eb[4 * g + j] = sh[j]; }
+        }
+    } else {
+        fbias = epi[0];
+    }
+}
 template <int C1, int C2, int COUT, bool FINAL, bool MS = false, bool POST = false>
 __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 4) * 64, 2) void dec_mfma(DecArgs p, DecMs pm, PostArg<POST> pp) {
     static_assert(FINAL || !POST, "post-processing belongs to the block that writes the mask");
@@ -1789,19 +1892,8 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
     const int kh = lane >> 5;
 
     half8 wf[KSTEPS];
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = p.wfrag[(mtile * KSTEPS + ks) * 64 + lane];
-    // per-register epilogue constants: reg 4g+j <-> row 8g + 4kh + j <-> (parity, co)
-    float es[16], eb[16];
-    if constexpr (!FINAL) {
-#pragma unroll
-        for (int r = 0; r < 16; r++) {
-            const int n = mtile * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-            es[r] = p.epi[n % COUT];
-            eb[r] = p.epi[COUT + n % COUT];
-        }
-    }
-    float fbias = FINAL ? p.epi[0] : 0.f;
+    float es[16], eb[16], fbias = 0.f;
+    dec_load_w<KSTEPS, COUT, FINAL>(wf, es, eb, fbias, p.wfrag, p.epi, mtile, lane, kh);
 
     const int n_items = p.B * p.nbands;
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
@@ -1809,57 +1901,20 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
         [[maybe_unused]] const StackPost sp = stack_post<POST, MS>(pp, pm.model_ids, b);
         if constexpr (MS) {   // every item takes its stack's weights: one copy in registers, no second one kept for a compare
             const uint32_t moff = model_off<MS>(pm.model_ids, pm.mstride, b);
-            const half8 *wfr = at_model(p.wfrag, moff);
-            const float *ep = at_model(p.epi, moff);
-#pragma unroll
-            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = wfr[(mtile * KSTEPS + ks) * 64 + lane];
-            if constexpr (!FINAL) {
-#pragma unroll
-                for (int r = 0; r < 16; r++) {
-                    const int n = mtile * 32 + (r & 3) + 8 * (r >> 2) + 4 * kh;
-                    es[r] = ep[n % COUT];
-                    eb[r] = ep[COUT + n % COUT];
-                }
-            } else {
-                fbias = ep[0];
-            }
+            dec_load_w<KSTEPS, COUT, FINAL>(wf, es, eb, fbias, at_model(p.wfrag, moff), at_model(p.epi, moff), mtile, lane, kh);
         }
         const int u0 = band * GH / p.nbands, u1 = (band + 1) * GH / p.nbands;
         const int nu = u1 - u0;   // grid rows of this band; tile rows = nu + 1 (input rows u0-1 .. u1-1)
         lds_barrier();
-        // ---- stage with LDS-DMA: concat(up, skip[t=0]); both sources hold relu'd values
-        {
-            const int RC = TC * CPP;
-            const int nchunk = (nu + 1) * RC;
-            const __half *su = p.up + ((size_t)b) * p.Hi * p.Wi * C1;  // unused when C1 == 0
-            const __half *ss = p.skip + ((size_t)b * p.Ts) * p.Hi * p.Wi * C2;
-            for (int s0 = wave * 64; s0 < nchunk; s0 += NW * 64) {
-                const int sidx = s0 + lane;
-                if (sidx < nchunk) {
-                    const int r = fdiv(sidx, p.mRC), within = sidx - r * RC;
-                    const int c = within / CPP, chp = within % CPP;
-                    const int cb = (chp ^ swz_eval<CPP>(p.swz, c, r)) * 8;
-                    const int y = u0 - 1 + r, x = c - 1;
-                    const void *src = p.zero;
-                    if (y >= 0 && y < p.Hi && x >= 0 && x < p.Wi) {
-                        const size_t pix = (size_t)y * p.Wi + x;
-                        if constexpr (C1 == 0) {
-                            src = ss + pix * C2 + cb;
-                        } else {
-                            if (cb < C1) src = su + pix * C1 + cb;
-                            else src = ss + pix * C2 + (cb - C1);
-                        }
-                    }
-                    glds16(src, smem + s0 * 16);
-                }
-            }
-        }
+        dec_stage_band<C1, C2, NW>(p, b, u0, nu, smem, wave, lane);
         wait_vmem();
         lds_barrier();
         // last block: the band's mask rows [Yb, Ye) are assembled in LDS behind the tile and leave
         // as coalesced 4-byte stores (they are contiguous in the mask tensor)
         uint8_t *const mrows = smem + p.mask_off;
         const int Yb = max(0, 2 * u0 - p.cy), Ye = min(p.Hd, 2 * u1 - p.cy);
+        [[maybe_unused]] const f32x4 *part = nullptr;   // C2 == 0: the frame's partial logits, from global memory
+        if constexpr (C2 == 0) part = reinterpret_cast<const f32x4 *>(p.part) + (size_t)b * GH * GW;
         // ---- compute over the band's flattened (u, v) positions
         const int npos = nu * GW;
         const int ntiles = (npos + 31) / 32;
@@ -1867,6 +1922,8 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
             const int q = tile * 32 + (lane & 31);
             const int qc = min(q, npos - 1);
             const int ul = fdiv(qc, p.mGW), v = qc - ul * GW;   // ul = u - u0
+            // dec_tile_acc<C>(smem, TC, p.swz, wf, ul, v, kh), written out: as the call, block 1's loop is scheduled differently and
+            // measured 0.9 % slower than the parent build, beyond its run-to-run spread
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[r] = 0.f;
@@ -1884,25 +1941,9 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
                     }
                 }
             if constexpr (FINAL) {
-                if (q >= npos) continue;
-                const int u = u0 + ul;
-                // rows 0..3 = parities (py,px) = (r>>1, r&1): only the kh == 0 half holds them
-                if (kh == 0) {
-                    f32x4 pl = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (C2 == 0) pl = reinterpret_cast<const f32x4 *>(p.part)[((size_t)b * GH + u) * GW + v];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int Y = 2 * u + (r >> 1) - p.cy, X = 2 * v + (r & 1) - p.cx;
-                        if (Y >= 0 && Y < p.Hd && X >= 0 && X < p.Wd) {
-                            float l = acc[r] + fbias;
-                            if constexpr (C2 == 0) l += pl[r];
-                            if (p.logits) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l;
-                            bool fg = l > sp.thr;
-                            if constexpr (POST) fg = fg && sp.keep[Y * p.Wd + X];
-                            mrows[(Y - Yb) * p.Wd + X] = fg ? 1 : 0;   // band mask, assembled in LDS
-                        }
-                    }
-                }
+                // only the kh == 0 half holds the parities' rows
+                if (q < npos && kh == 0)
+                    dec_final_out<C2 == 0, POST>(p, sp, acc, fbias, part, b, u0 + ul, v, mrows, Yb);
             } else {
                 // 16-byte stores through a wave-private LDS transpose: the wave's 32 rows (parity, channel) x 32
                 // positions are 64 contiguous bytes per position in the output tensor; lanes drop their 8-byte
@@ -1911,13 +1952,8 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
                 uint8_t *const scr = smem + p.scr_off + wave * 2048;
                 const int pos = lane & 31;
 #pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    half4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        o[j] = (_Float16)fmaxf(acc[4 * g + j] * es[4 * g + j] + eb[4 * g + j], 0.f);
-                    *reinterpret_cast<half4 *>(scr + pos * 64 + ((g ^ ((pos >> 2) & 3)) * 16) + kh * 8) = o;
-                }
+                for (int g = 0; g < 4; g++)
+                    *reinterpret_cast<half4 *>(scr + pos * 64 + ((g ^ ((pos >> 2) & 3)) * 16) + kh * 8) = dec_relu_bn4(acc, es, eb, g);
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1944,14 +1980,8 @@ __global__ __launch_bounds__(((FINAL ? 1 : 4 * COUT / 32) > 4 ? 4 * COUT / 32 : 
         if constexpr (FINAL) {
             if (p.mask) {
                 lds_barrier();
-                uint8_t *dst = p.mask + ((size_t)b * p.Hd + Yb) * p.Wd;
-                const int nbytes = (Ye - Yb) * p.Wd;
-                if ((p.Wd & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mask) & 3) == 0) {
-                    for (int i = tid; i < nbytes / 4; i += NW * 64)
-                        reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(mrows)[i];
-                } else {
-                    for (int i = tid; i < nbytes; i += NW * 64) dst[i] = mrows[i];
-                }
+                dec_mask_out<NW * 64>(mrows, p.mask + ((size_t)b * p.Hd + Yb) * p.Wd, (Ye - Yb) * p.Wd,
+                                      (p.Wd & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mask) & 3) == 0, tid);
             }
         }
     }
@@ -2113,12 +2143,7 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
             acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[ks], ring[ks % AD], acc, 0, 0, 0);
             if (ks + AD < KSTEPS) ring[ks % AD] = frag(ks + AD);
         }
-        __builtin_amdgcn_sched_group_barrier(0x100, AD, 0);
-#pragma unroll
-        for (int ks = 0; ks < KSTEPS; ks++) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-            if (ks + AD < KSTEPS) __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
+        pin_ring<KSTEPS, AD>();
         if constexpr (CN > 0 && COUT == 16) {
             // Block 2 into the row tail's tile (dec012_mfma<.., TAILF>; CN = 16 channels of 32 bytes per pixel, the 16-byte halves
             // swizzled by (xx >> 3) & 1).  Rows n0 + j, n0 = mtile*32 + 8 gq + 4 kh, with COUT = 16: parity 2 mtile + (gq >> 1), channels
@@ -2137,12 +2162,7 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
                         const int sw = (xx >> 3) & 1;
 #pragma unroll
                         for (int c = 0; c < 2; c++) {
-                            const int gq = 2 * px + c;
-                            half4 o;
-#pragma unroll
-                            for (int j = 0; j < 4; j++)
-                                o[j] = (_Float16)fmaxf(acc[4 * gq + j] * es[4 * gq + j] + eb[4 * gq + j], 0.f);
-                            *reinterpret_cast<half4 *>(pix + ((c ^ sw) * 16)) = o;
+                            *reinterpret_cast<half4 *>(pix + ((c ^ sw) * 16)) = dec_relu_bn4(acc, es, eb, 2 * px + c);
                         }
                     }
                 }
@@ -2162,25 +2182,16 @@ __device__ __forceinline__ void dec012_block(const uint8_t *lds0, const uint8_t 
                 uint8_t *const pix = next_tile + (yy * TCN + xx) * PSN + (cob & 7) * 2;
                 const int sw = swz_eval<CPPN>(gn.swz, xx, yy);
 #pragma unroll
-                for (int gq = 0; gq < 4; gq++) {
-                    half4 o;
-#pragma unroll
-                    for (int j = 0; j < 4; j++)
-                        o[j] = (_Float16)fmaxf(acc[4 * gq + j] * es[4 * gq + j] + eb[4 * gq + j], 0.f);
-                    *reinterpret_cast<half4 *>(pix + ((((cob >> 3) + gq) ^ sw) * 16)) = o;
-                }
+                for (int gq = 0; gq < 4; gq++)
+                    *reinterpret_cast<half4 *>(pix + ((((cob >> 3) + gq) ^ sw) * 16)) = dec_relu_bn4(acc, es, eb, gq);
             }
         } else {
             // 16-byte stores through a wave-private LDS transpose, as in dec_mfma
             uint8_t *const scr = scr_base + wave * 2048;
             const int pos = lane & 31;
 #pragma unroll
-            for (int gq = 0; gq < 4; gq++) {
-                half4 o;
-#pragma unroll
-                for (int j = 0; j < 4; j++) o[j] = (_Float16)fmaxf(acc[4 * gq + j] * es[4 * gq + j] + eb[4 * gq + j], 0.f);
-                *reinterpret_cast<half4 *>(scr + pos * 64 + ((gq ^ ((pos >> 2) & 3)) * 16) + kh * 8) = o;
-            }
+            for (int gq = 0; gq < 4; gq++)
+                *reinterpret_cast<half4 *>(scr + pos * 64 + ((gq ^ ((pos >> 2) & 3)) * 16) + kh * 8) = dec_relu_bn4(acc, es, eb, gq);
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -2491,7 +2502,7 @@ struct Dec3ccArgs {
 template <bool WV, bool PART, bool MS = false, bool POST = false>
 __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q, PostArg<POST> qp) {
     constexpr int C1 = 16, C2 = PART ? 0 : 16, C = C1 + C2, NW = ccbody::CC_THREADS / 64;
-    constexpr int KC = C / 16, KSTEPS = 4 * KC, CPP = C / 8, PS = C * 2;
+    constexpr int KSTEPS = 4 * (C / 16);
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const DecArgs &p = q.d;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -2509,108 +2520,41 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_mfma(Dec3ccArgs q, 
         const StackPost sp = stack_post<POST, MS>(qp, q.ms.model_ids, b);
         // the weight fragments are (re)loaded per frame: their registers are free again while bboxcc runs
         half8 wf[KSTEPS];
-        if constexpr (MS) {
-            const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
-            fbias = at_model(p.epi, moff)[0];
+        const uint32_t moff = model_off<MS>(q.ms.model_ids, q.ms.mstride, b);
+        if constexpr (MS) fbias = at_model(p.epi, moff)[0];
 #pragma unroll
-            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = at_model(p.wfrag, moff)[ks * 64 + lane];
-        } else {
-#pragma unroll
-            for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = p.wfrag[ks * 64 + lane];
-        }
-        auto stage = [&](int band, uint8_t *buf) {   // LDS-DMA of concat(up, skip[t=0]) rows u0-1 .. u1-1
-            const int u0 = band * GH / p.nbands, u1 = (band + 1) * GH / p.nbands;
-            const int RC = TC * CPP;
-            const int nchunk = (u1 - u0 + 1) * RC;
-            const __half *su = p.up + ((size_t)b) * p.Hi * p.Wi * C1;
-            const __half *ss = p.skip + ((size_t)b * p.Ts) * p.Hi * p.Wi * C2;
-            for (int s0 = wave * 64; s0 < nchunk; s0 += NW * 64) {
-                const int sidx = s0 + lane;
-                if (sidx < nchunk) {
-                    const int r = fdiv(sidx, p.mRC), within = sidx - r * RC;
-                    const int c = within / CPP, chp = within % CPP;
-                    const int cb = (chp ^ swz_eval<CPP>(p.swz, c, r)) * 8;
-                    const int y = u0 - 1 + r, x = c - 1;
-                    const void *src = p.zero;
-                    if (y >= 0 && y < p.Hi && x >= 0 && x < p.Wi) {
-                        const size_t pix = (size_t)y * p.Wi + x;
-                        src = (PART || cb < C1) ? (const void *)(su + pix * C1 + cb) : (const void *)(ss + pix * C2 + (cb - C1));
-                    }
-                    glds16(src, buf + s0 * 16);
-                }
-            }
-        };
+        for (int ks = 0; ks < KSTEPS; ks++) wf[ks] = (MS ? at_model(p.wfrag, moff) : p.wfrag)[ks * 64 + lane];
+        auto stage = [&](int u0, int u1, uint8_t *buf) { dec_stage_band<C1, C2, NW>(p, b, u0, u1 - u0, buf, wave, lane); };
         if (b != (int)blockIdx.x) lds_barrier();   // the previous frame's bboxcc is done with the band buffers it reuses (the first frame has none)
         PHASE_MARK(0);
-        if constexpr (PART) {   // the frame's partial logits: one 16-byte piece per grid position
-            const uint8_t *ps = reinterpret_cast<const uint8_t *>(p.part) + (size_t)b * GH * GW * 16;
-            const int nch = GH * GW;
-            for (int s0 = wave * 64; s0 < nch; s0 += NW * 64)
-                if (s0 + lane < nch) glds16(ps + (size_t)(s0 + lane) * 16, smem + q.part_off + s0 * 16);
-        }
-        stage(0, smem);
+        if constexpr (PART) dec_stage_part<NW>(p.part + (size_t)b * GH * GW * 4, GH * GW, smem + q.part_off, wave, lane);
+        stage(0, GH / p.nbands, smem);
         PHASE_MARK(1);   // requesting band 0 (+ weights)
         for (int band = 0; band < p.nbands; band++) {
             uint8_t *const cur = smem + (band & 1) * q.tile_bytes;
             wait_vmem();
             lds_barrier();   // this band has landed; every wave is done with the other buffer
             PHASE_MARK(2);   // band landing
-            if (band + 1 < p.nbands) stage(band + 1, smem + ((band + 1) & 1) * q.tile_bytes);
-            PHASE_MARK(3);   // requesting the next band
             const int u0 = band * GH / p.nbands, u1 = (band + 1) * GH / p.nbands;
+            if (band + 1 < p.nbands) stage(u1, (band + 2) * GH / p.nbands, smem + ((band + 1) & 1) * q.tile_bytes);
+            PHASE_MARK(3);   // requesting the next band
             const int npos = (u1 - u0) * GW;
             const int ntiles = (npos + 31) / 32;
             for (int tile = wave; tile < ntiles; tile += NW) {
                 const int qi = tile * 32 + (lane & 31);
                 const int qc = min(qi, npos - 1);
                 const int ul = fdiv(qc, p.mGW), v = qc - ul * GW;
-                f32x16 acc;
-#pragma unroll
-                for (int r = 0; r < 16; r++) acc[r] = 0.f;
-#pragma unroll
-                for (int a = 0; a < 2; a++)
-#pragma unroll
-                    for (int bb = 0; bb < 2; bb++) {
-                        const int yy = ul + 1 - a, xx = v + 1 - bb;
-                        const int pbase = (yy * TC + xx) * PS;
-                        const int s = swz_eval<CPP>(p.swz, xx, yy);
-#pragma unroll
-                        for (int kc = 0; kc < KC; kc++) {
-                            const half8 av = *reinterpret_cast<const half8 *>(cur + pbase + (((kc * 2 + kh) ^ s) * 16));
-                            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(wf[(a * 2 + bb) * KC + kc], av, acc, 0, 0, 0);
-                        }
-                    }
-                if (qi < npos && kh == 0) {   // rows 0..3 = the four output parities of position (u, v)
-                    const int u = u0 + ul;
-                    f32x4 pl = {0.f, 0.f, 0.f, 0.f};
-                    if constexpr (PART) pl = reinterpret_cast<const f32x4 *>(smem + q.part_off)[u * GW + v];
-#pragma unroll
-                    for (int r = 0; r < 4; r++) {
-                        const int Y = 2 * u + (r >> 1) - p.cy, X = 2 * v + (r & 1) - p.cx;
-                        if (Y >= 0 && Y < p.Hd && X >= 0 && X < p.Wd) {
-                            float l = acc[r] + fbias;
-                            if constexpr (PART) l += pl[r];
-                            if (p.logits) p.logits[((size_t)b * p.Hd + Y) * p.Wd + X] = l;
-                            bool fg = l > sp.thr;
-                            if constexpr (POST) fg = fg && sp.keep[Y * p.Wd + X];
-                            mfull[Y * p.Wd + X] = fg ? 1 : 0;
-                        }
-                    }
-                }
+                const f32x16 acc = dec_tile_acc<C>(cur, TC, p.swz, wf, ul, v, kh);
+                if (qi < npos && kh == 0)   // rows 0..3 = the four output parities of position (u, v)
+                    dec_final_out<PART, POST>(p, sp, acc, fbias, reinterpret_cast<const f32x4 *>(smem + q.part_off), b, u0 + ul, v, mfull, 0);
             }
         }
         PHASE_MARK(4);   // tiles
         lds_barrier();   // the frame's mask is complete; the band buffers are free
         PHASE_MARK(5);   // barrier
         if (p.mask) {
-            uint8_t *dst = p.mask + (size_t)b * p.Hd * p.Wd;
             const int nbytes = p.Hd * p.Wd;
-            if ((nbytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mask) & 3) == 0) {
-                for (int i = tid; i < nbytes / 4; i += NW * 64)
-                    reinterpret_cast<uint32_t *>(dst)[i] = reinterpret_cast<const uint32_t *>(mfull)[i];
-            } else {
-                for (int i = tid; i < nbytes; i += NW * 64) dst[i] = mfull[i];
-            }
+            dec_mask_out<NW * 64>(mfull, p.mask + (size_t)b * nbytes, nbytes, (nbytes & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mask) & 3) == 0, tid);
         }
         PHASE_MARK(6);   // mask out
         const int area = stack_area<POST, MS>(qp, q.ms.model_ids, b, q.area_thresh);
@@ -2676,12 +2620,7 @@ __global__ __launch_bounds__(ccbody::CC_THREADS) void dec3cc_rows_mfma(Dec3ccArg
         for (int ks = 0; ks < 4; ks++) wf[ks] = (MS ? at_model(p.wfrag, moff) : p.wfrag)[ks * 64 + lane];
         if (b != (int)blockIdx.x) lds_barrier();   // the previous frame's bboxcc is done with the tile buffer it reuses
         PHASE_MARK(0);
-        {   // the frame's partial logits: one 16-byte piece per grid position
-            const uint8_t *ps = reinterpret_cast<const uint8_t *>(p.part) + (size_t)b * GH * GW * 16;
-            const int nch = GH * GW;
-            for (int s0 = wave * 64; s0 < nch; s0 += NW * 64)
-                if (s0 + lane < nch) glds16(ps + (size_t)(s0 + lane) * 16, smem + q.part_off + s0 * 16);
-        }
+        dec_stage_part<NW>(p.part + (size_t)b * GH * GW * 4, GH * GW, smem + q.part_off, wave, lane);
         {   // the tile: rows 1 .. Hi by request (a wave takes whole rows), the border as zeros (bboxcc's arrays overwrite it every frame)
             const __half *su = p.up + (size_t)b * p.Hi * p.Wi * 16;
             const int NI = 2 * p.Wi;   // interior 16-byte pieces of a row
@@ -3069,6 +3008,10 @@ ItemPlan make_plan(int grid, int num_cu, int wgs_per_cu, int batch, int nbands, 
 // What every kernel here that needs more than the default 64 KB of dynamic LDS is opened to (covahip_open_lds): the 160 KB a CU
 // has, minus the 256 B the runtime keeps.
 constexpr size_t LDS_LIMIT = 160 * 1024 - 256;
+// A decoder band (plan_dec_block, plan_tail_fused): its grid rows when a frame's GH rows are cut into nb bands (the largest band's),
+// and the bytes of its input tile -- one input row more than grid rows, as a multiple of 16.
+inline int band_rows(int GH, int nb) { return (GH + nb - 1) / nb; }
+inline size_t band_tile_bytes(int rows, size_t row_bytes) { return (((size_t)rows + 1) * row_bytes + 15) & ~(size_t)15; }
 // Whether run_dec012 takes the form that ends in planes (dec012_mfma<.., TAILF> + cc_planes) on its own where it applies; the
 // developer switches reach it either way (DESIGN.md section 6 has the measurement that decides this).
 constexpr bool TAIL_IN_DEC012_AUTO = true;
@@ -3324,7 +3267,7 @@ bool run_enc23(const Fwd &f, int &rc) {
     // a mixed batch (model sets) takes it whenever it fits: the two-launch form's level-3 kernel cannot hold a per-stack model's
     // fragments without spilling ("Model sets")
     if (!((pays || m->fuse_enc23 == 2 || f.ms) && (W + 2) * 64 <= E23_RP2 && Wp <= 16 && Hp >= 1 && Hp3 >= 1 && Wp3 >= 1 &&
-          (size_t)std::max(2 * Hp3 + 2, H3 + 1) * (W3 + 2) * 128 <= (size_t)E3_TSZ && lds <= 160 * 1024 - 256))
+          (size_t)std::max(2 * Hp3 + 2, H3 + 1) * (W3 + 2) * 128 <= (size_t)E3_TSZ && lds <= LDS_LIMIT))
         return false;
     Enc23Args a;
     a.in = f.ws.act[2]; a.mid = f.ws.act[3]; a.out = f.ws.act[4];
@@ -3366,8 +3309,8 @@ int run_enc_level(const Fwd &f, int i) {
         nbands = std::min(f.ctx->enc_plan[i].nbands, Hp);
         nbuf = f.ctx->enc_plan[i].nbuf;
         const size_t need = (size_t)nbuf * BN_T * (2 * ((Hp + nbands - 1) / nbands) + 2) * TC * px_bytes + scr_bytes;
-        if (need > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
-        wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : (int)std::min<size_t>(2, (160 * 1024 - 256) / need);
+        if (need > LDS_LIMIT) return COVAHIP_ERR_UNSUPPORTED;
+        wgs_per_cu = (i == BN_LEVELS - 1) ? 1 : (int)std::min<size_t>(2, LDS_LIMIT / need);
     } else {
         // the band count that fits in LDS and minimises rounds x (rows + 1) (plan_bands)
         const size_t lds_cap = (wgs_per_cu == 1 ? 150 * 1024 : 80 * 1024) - scr_bytes;
@@ -3388,7 +3331,7 @@ int run_enc_level(const Fwd &f, int i) {
     }
     const size_t tile_bytes = rowtiles ? (size_t)BN_T * fix_tsz : (((size_t)BN_T * (RB + 2) * TC * px_bytes) + 15) & ~(size_t)15;
     const size_t lds = nbuf * tile_bytes + scr_bytes;
-    if (lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
+    if (lds > LDS_LIMIT) return COVAHIP_ERR_UNSUPPORTED;
     const int items = f.batch * nbands;
     const int grid = std::min(items, wgs_per_cu * f.num_cu);
     EncArgs a;
@@ -3409,15 +3352,15 @@ int run_enc_level(const Fwd &f, int i) {
         // (a null table means "stack b = frames 4b .. 4b+3" to this kernel: a carrier-frame call must bring its table)
         if (f.by_frames && !f.d_index && !f.dry) return COVAHIP_ERR_INVALID_ARG;
         return launched(f, with_bools([&](auto AP, auto MS) {
-            return launch(f, "enc1_mfma", enc_mfma<16, 32, 2, 4, 8, true, AP.value, true, 0, MS.value>, grid, 512, lds, a);
+            return launch(f, "enc1_mfma", enc_mfma<16, 32, 2, 4, 8, AP.value, true, 0, MS.value>, grid, 512, lds, a);
         }, ap, f.ms));
     }
     if (i == 2)
         return launched(f, with_bools([&](auto AP, auto ROWS, auto MS) {
-            return launch(f, "enc2_mfma", enc_mfma<32, 64, 4, 2, 4, true, AP.value, false, ROWS.value ? E2_TSZ : 0, MS.value>, grid, WG, lds, a);
+            return launch(f, "enc2_mfma", enc_mfma<32, 64, 4, 2, 4, AP.value, false, ROWS.value ? E2_TSZ : 0, MS.value>, grid, WG, lds, a);
         }, ap, rowtiles, f.ms));
     return launched(f, with_bools([&](auto AP, auto ROWS, auto MS) {
-        return launch(f, "enc3_mfma", enc_mfma<64, 128, 2, 2, 8, true, AP.value, false, ROWS.value ? E3_TSZ : 0, MS.value>, grid, 512, lds, a);
+        return launch(f, "enc3_mfma", enc_mfma<64, 128, 2, 2, 8, AP.value, false, ROWS.value ? E3_TSZ : 0, MS.value>, grid, 512, lds, a);
     }, ap, rowtiles, f.ms));
 }
 
@@ -3464,7 +3407,7 @@ bool run_dec012(const Fwd &f, int &rc, const TailPlan *tail, bool &tail_in) {
     }
     a.scr_off = (int)off;
     const size_t lds = off + 8 * 2048;
-    if (lds > 160 * 1024 - 256) return false;
+    if (lds > LDS_LIMIT) return false;
     a.out = f.ws.dact[2]; a.B = f.batch; a.zero = f.prep + pr->zero;
     a.model_ids = f.inp.model_ids; a.mstride = f.mstride;
     const int grid = std::min(f.batch, f.num_cu);
@@ -3545,19 +3488,20 @@ int plan_dec_block(const Fwd &f, int j, DecPlan &p) {
     const bool heavy = wbytes >= 192 * 1024 && (size_t)(GH + 1) * row_bytes <= 72 * 1024;
     int nbands = 1;
     if (!heavy)
-        while (nbands < GH && (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes > 30 * 1024 ||
+        while (nbands < GH && (((size_t)band_rows(GH, nbands) + 1) * row_bytes > 30 * 1024 ||
                                (long long)f.batch * nbands < 2LL * f.num_cu))
             nbands++;
     a.nbands = nbands; a.mNb = magic(nbands); a.mGW = magic(in.W + 1);
     a.mRC = magic((in.W + 2) * (ci_j / 8)); a.zero = f.prep + pr->zero;
-    a.swz = choose_swz(false, ci_j, in.W, 0, (GH + nbands - 1) / nbands);
-    const size_t tile_bytes = (((size_t)((GH + nbands - 1) / nbands) + 1) * row_bytes + 15) & ~(size_t)15;
-    const size_t mask_bytes = last ? ((((size_t)2 * ((GH + nbands - 1) / nbands) * out.W) + 15) & ~(size_t)15) : 0;
+    const int rows = band_rows(GH, nbands);
+    a.swz = choose_swz(false, ci_j, in.W, 0, rows);
+    const size_t tile_bytes = band_tile_bytes(rows, row_bytes);
+    const size_t mask_bytes = last ? ((((size_t)2 * rows * out.W) + 15) & ~(size_t)15) : 0;
     const size_t scr_bytes = last ? 0 : (size_t)std::max(4, 4 * m->dec_co[j] / 32) * 2048;   // one 2 KB transpose scratch per wave
     p.lds = tile_bytes + mask_bytes + scr_bytes;
     a.mask_off = (int)tile_bytes;
     a.scr_off = (int)tile_bytes;
-    if (p.lds > 160 * 1024 - 256) return COVAHIP_ERR_UNSUPPORTED;
+    if (p.lds > LDS_LIMIT) return COVAHIP_ERR_UNSUPPORTED;
     p.in = in; p.out = out; p.half = half; p.ci = ci_j; p.GH = GH; p.row_bytes = row_bytes;
     p.grid = std::min(f.batch * nbands, (heavy ? 1 : 4) * f.num_cu);
     return COVAHIP_OK;
@@ -3604,9 +3548,9 @@ bool plan_tail_fused(const Fwd &f, const DecPlan &p, TailPlan &tp) {
     int best_nb = 0;
     long long best_cost = -1;
     for (int nb = 1; nb <= GH; nb++) {
-        const size_t tb = (((size_t)((GH + nb - 1) / nb) + 1) * p.row_bytes + 15) & ~(size_t)15;
+        const size_t tb = band_tile_bytes(band_rows(GH, nb), p.row_bytes);
         const size_t nbuf = nb == 1 ? 1 : 2;   // the whole frame in one buffer when it fits
-        if (std::max(nbuf * tb, cc_bytes) + mfull + partb > 160 * 1024 - 512) continue;
+        if (std::max(nbuf * tb, cc_bytes) + mfull + partb > LDS_LIMIT - 256) continue;
         long long rounds = 0;   // tiles of 32 positions over 16 waves, band by band
         for (int k = 0; k < nb; k++) {
             const int nu = (k + 1) * GH / nb - k * GH / nb;
@@ -3616,11 +3560,11 @@ bool plan_tail_fused(const Fwd &f, const DecPlan &p, TailPlan &tp) {
         if (best_cost < 0 || cost < best_cost) { best_cost = cost; best_nb = nb; }
     }
     if (!best_nb) return false;
-    const size_t tb = (((size_t)((GH + best_nb - 1) / best_nb) + 1) * p.row_bytes + 15) & ~(size_t)15;
+    const size_t tb = band_tile_bytes(band_rows(GH, best_nb), p.row_bytes);
     t.d = p.a;
     t.ms = p.am;
     t.d.nbands = best_nb; t.d.mNb = magic(best_nb);
-    t.d.swz = choose_swz(false, p.ci, in.W, 0, (GH + best_nb - 1) / best_nb);
+    t.d.swz = choose_swz(false, p.ci, in.W, 0, band_rows(GH, best_nb));
     t.boxes = f.cc->boxes; t.counts = f.cc->counts;
     t.area_thresh = f.cc->area_thresh; t.max_boxes = f.cc->max_boxes;
     t.tile_bytes = (int)tb; t.cc_off = 0;
