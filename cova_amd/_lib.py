@@ -109,6 +109,11 @@ class HeatCfg(C.Structure):
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_thresh", C.c_int32), ("logit_thresh", C.c_void_p)]
 
 
+class AlignCfg(C.Structure):
+    """covahip_align_cfg (24 bytes)."""
+    _fields_ = [("max_shift", C.c_int32), ("min_mv", C.c_int32), ("class_mask", C.c_uint32), ("keep", C.c_void_p)]
+
+
 class MonitorCfg(C.Structure):
     _fields_ = [("h", C.c_int32), ("w", C.c_int32), ("n_models", C.c_int32), ("max_boxes", C.c_int32), ("attach", C.c_int32),
                 ("every", C.c_int32)]
@@ -267,6 +272,7 @@ PROTOTYPES = {
     "covahip_train_data_frames": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "covahip_train_data_gather": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_train_data_label_mass": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int]),
+    "covahip_train_data_align": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(AlignCfg), _P, _P, _P, C.c_int]),
     "covahip_train_data_destroy": (None, [_P]),
     "covahip_train_step_data": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(C.c_float)]),
     "covahip_train_step_set_data": (C.c_int, [_P, _P, _P, _P, _P, _P]),

@@ -262,6 +262,13 @@ int covahip_train_data_launch(covahip_train_data *d, int n, uint8_t *d_stack, ui
 int covahip_label_mass_launch(covahip_ctx *ctx, const uint8_t *d_gt, const uint32_t *d_bits, uint32_t *d_mass, int64_t first,
                               int64_t n, int hw);
 
+// train_align.hip: the alignment counts (covahip_train_data_align) of frames [at, at + m) of the recording [first, first + n) of
+// d_rec u16 / d_gt u8 [capacity][hw], in one launch on the ctx's stream: d_both u32 [m][2 S + 1], d_mov and d_lab u32 [m].
+// lut: bit (mv_x | mv_y << 3) = a record with these vectors moves; cmask: bit c = class c moves; d_bits as for the label mass.
+int covahip_align_launch(covahip_ctx *ctx, const uint16_t *d_rec, const uint8_t *d_gt, int64_t capacity, const uint32_t *d_bits,
+                         uint64_t lut, uint32_t cmask, int S, int64_t first, int64_t n, int64_t at, int64_t m, int hw,
+                         uint32_t *d_both, uint32_t *d_mov, uint32_t *d_lab);
+
 // blobnet.hip
 void covahip_blobnet_destroy(covahip_ctx *ctx);
 int covahip_blobnet_forward_dev(covahip_ctx *ctx, const uint8_t *d_stack, int batch, float *d_logits,

@@ -1,7 +1,8 @@
 // Device-resident training data (include/covahip.h, "Training data"): the frames of any number of recordings as two-byte
 // records (covahip_carrier_pack's packing) with their label bytes, and the launch that builds a training step's stacks and labels
 // from a table of frame indices, mirrored where a sample asks for it, straight into the trainer's staging.  The label mass of
-// the resident frames is served from here too (covahip_train_data_label_mass); its kernel lives in label_mass.hip.
+// the resident frames is served from here too (covahip_train_data_label_mass); its kernel lives in label_mass.hip.  So are the
+// label-alignment counts of a recording (covahip_train_data_align); their kernel lives in train_align.hip.
 //
 // Storage: rec u16 [capacity][h][w], gt u8 [capacity][h][w]; every element offset is 64-bit (a 16x16 set of 8.5 M frames is 4.4 GB
 // of records).  A frame of an odd h * w starts on an odd element, so the read side relies on 2-byte alignment only.
@@ -269,6 +270,62 @@ int covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t 
         if (int rc = covahip_label_mass_launch(ctx, d->gt, d_bits, out, first + at, m, hw)) return rc;
         if (host) {
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(mass + at, out, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the staging is written again by the next chunk
+        }
+    }
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_align(covahip_train_data *d, int64_t first, int64_t n, const covahip_align_cfg *cfg, uint32_t *both,
+                             uint32_t *mov, uint32_t *lab, int mem_kind) {
+    if (!d || !cfg || !both || !mov || !lab || n < 1 || first < 0 || (mem_kind != COVAHIP_MEM_HOST && mem_kind != COVAHIP_MEM_DEVICE))
+        return COVAHIP_ERR_INVALID_ARG;
+    if (n > d->frames || first > d->frames - n) return COVAHIP_ERR_INVALID_ARG;
+    if (cfg->max_shift < 0 || cfg->max_shift > 32 || cfg->min_mv < 0 || cfg->min_mv > 6 || (cfg->class_mask & ~0x7Fu)) return COVAHIP_ERR_INVALID_ARG;
+    if (cfg->min_mv == 0 && cfg->class_mask == 0) return COVAHIP_ERR_INVALID_ARG;   // nothing can move
+    const bool host = mem_kind == COVAHIP_MEM_HOST;
+    if (!host && ((reinterpret_cast<uintptr_t>(both) | reinterpret_cast<uintptr_t>(mov) | reinterpret_cast<uintptr_t>(lab)) & 3u))
+        return COVAHIP_ERR_INVALID_ARG;                                              // the launch stores whole counts
+    const int hw = d->h * d->w, S = cfg->max_shift;
+    const size_t nw = ((size_t)hw + 31) / 32, W = 2 * (size_t)S + 1;
+    std::vector<uint32_t> bits;
+    if (cfg->keep) {
+        bits.assign(nw, 0u);
+        bool any = false;
+        for (int i = 0; i < hw; i++)
+            if (cfg->keep[i]) bits[(size_t)i >> 5] |= 1u << (i & 31), any = true;
+        if (!any) return COVAHIP_ERR_INVALID_ARG;   // nothing would count
+    }
+    uint64_t lut = 0;                                // bit (mv_x | mv_y << 3): max(mv_x, mv_y) >= min_mv
+    for (int y = 0; y < 8 && cfg->min_mv; y++)
+        for (int x = 0; x < 8; x++)
+            if (std::max(x, y) >= cfg->min_mv) lut |= (uint64_t)1 << (x | y << 3);
+    covahip_ctx *ctx = d->ctx;
+    if (int rc = enter(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const uint32_t *d_bits = nullptr;
+    if (cfg->keep) {
+        if (int rc = d->keep_bits.reserve(ctx, nw)) return rc;
+        if (int rc = d->keep_bits.upload(ctx, bits.data(), nw, &d_bits)) return rc;
+    }
+    // a launch's frames: all of them, or for host outputs what the staging holds of the three tables
+    const size_t per = (W + 2) * sizeof(uint32_t);
+    const int64_t chunk = host ? std::min<int64_t>(n, (int64_t)std::max<size_t>(1, d->stage_budget / per)) : n;
+    if (host)
+        if (int rc = covahip_ensure_buffer(ctx, &d->stage, &d->stage_bytes, (size_t)chunk * per)) return rc;
+    uint32_t *st = static_cast<uint32_t *>(d->stage);
+    for (int64_t at = 0; at < n; at += chunk) {
+        const int64_t m = std::min(chunk, n - at);
+        uint32_t *o_both = host ? st : both + (size_t)at * W, *o_mov = host ? st + (size_t)chunk * W : mov + at;
+        uint32_t *o_lab = host ? st + (size_t)chunk * (W + 1) : lab + at;
+        if (int rc = covahip_align_launch(ctx, d->rec, d->gt, d->capacity, d_bits, lut, cfg->class_mask, S, first, n, at, m, hw, o_both,
+                                          o_mov, o_lab))
+            return rc;
+        if (host) {
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(both + (size_t)at * W, o_both, (size_t)m * W * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(mov + at, o_mov, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+            COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(lab + at, o_lab, (size_t)m * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
             COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));   // the staging is written again by the next chunk
         }
     }

@@ -12,6 +12,8 @@
                   mirrored, reversed; plain_samples: the table's windows as they are (validation, scoring); split_frames_tail;
                   balanced_samples: an epoch redrawn half from busy, half from quiet samples (TrainData.label_mass)
                   TrainerSet / Trainer .step_data, .evaluate_data, .fit_data take their batches from a TrainData by such arrays
+  alignment       per recording, where the labels stand against the records: TrainData.align counts on the device, align_scores
+                  and align_drift read the counts; windows / epoch_samples(label_shift=) apply the shift found
 
     python -m cova_amd.train RECORDS... -o blobnet.cvhw [--epochs 20 --batch 4 --seed 0 --h-mb 45 --w-mb 80]
 
@@ -81,6 +83,20 @@ macroblocks outside the camera's ignore region (counted on the device, TrainData
 every epoch keeps its length and draws each sample from the busy or the quiet windows with probability 1/2, each half walked in
 the epoch's order (balanced_samples).  The draws are a pure function of (--data-seed, epoch, model) too, and --resume takes
 --balance from the command line again.  Validation windows are never balanced, and --eval-only refuses the flag.
+
+Label alignment (include/covahip.h, covahip_train_data_align): records and labels come from different decoders, and a frame one
+of them dropped moves every label against its record without any score showing it,
+
+    python -m cova_amd.train CAM.tfrecord --windows overlap --align-report 8
+    python -m cova_amd.train CAM.tfrecord -o blobnet.cvhw --windows overlap --label-shift auto
+
+--align-report [S] trains nothing: per recording it counts on the device, for every frame shift s in -S .. S, the macroblocks
+that move in the records of frame f AND are labelled in frame f + s (B) and those that do either (U), prints the table with the
+best shift (largest B / U; TrainData.align, align_scores) and lists the frames where the best shift of a block of --align-window
+frames changes (align_drift): a frame lost half-way.  --label-shift N labels every window by its labelling frame + N, the table
+of windows shrunk so that this frame stays inside the recording (windows / epoch_samples label_shift); --label-shift auto[:S]
+measures each recording's own N and stops, naming the recording, when there is none, when it sits at +-S, or when it changes
+inside the recording.  Both need --windows.  The shift is a pure function of the data and the arguments: --resume stays exact.
 """
 from __future__ import annotations
 
@@ -607,20 +623,26 @@ def _strides(strides) -> tuple:
     return strides
 
 
-def windows(segments, mode: str = "skip", strides=(1,)) -> np.ndarray:
+def windows(segments, mode: str = "skip", strides=(1,), label_shift: int = 0) -> np.ndarray:
     """The windows of a model's segments (half-open ranges of frame indices of a TrainData, one contiguous recording each) as a
     table i64 [N][2] of (segment start, newest frame k) in canonical order: segment by segment, k ascending.  mode "skip": slide's
     groups, frames 4j .. 4j + 3 of the segment (k = start + 4j + 3); "overlap": every k of the segment.  Either way only k with
     k - 3 * min(strides) >= start: a window never crosses a segment boundary, and every window of the table fits at least one of
-    the strides (epoch_samples picks among those that fit)."""
+    the strides (epoch_samples picks among those that fit).
+    label_shift = s (alignment): the label that belongs to record frame f stands at frame f + s, and epoch_samples(label_shift=s)
+    labels a window by its labelling frame + s.  The table keeps that frame inside the segment for forward and reversed windows
+    alike: s > 0 drops the k with k + s >= segment end; s < 0 writes start + |s| as the start, which the rule above then holds
+    the oldest frame to.  0 is the table as it always was."""
     if mode not in ("skip", "overlap"):
         raise ValueError(f"mode = {mode!r}: 'skip' or 'overlap'")
     reach = (W.T - 1) * min(_strides(strides))
+    s = int(label_shift)
     rows = []
     for a, b in _segments(segments):
         k = np.arange(a + W.T - 1, a + (b - a) // W.T * W.T, W.T) if mode == "skip" else np.arange(a, b)
-        k = k[k - reach >= a].astype(np.int64)
-        rows.append(np.stack([np.full(k.size, a, np.int64), k], axis=1))
+        lo = a + max(-s, 0)
+        k = k[(k - reach >= lo) & (k + max(s, 0) < b)].astype(np.int64)
+        rows.append(np.stack([np.full(k.size, lo, np.int64), k], axis=1))
     return np.concatenate(rows) if rows else np.zeros((0, 2), np.int64)
 
 
@@ -632,7 +654,7 @@ def _draws(data_seed: int, epoch: int, model: int, site: int, n: int) -> np.ndar
 
 
 def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model: int = 0, shuffle: bool = False, flip=(),
-                  reverse: bool = False) -> np.ndarray:
+                  reverse: bool = False, label_shift=0) -> np.ndarray:
     """The covahip_train_sample array (dtype SAMPLE) of one epoch of one model over a windows() table: a pure function of its
     arguments, built on the header's splitmix64 (numpy's generators are not pinned across versions, and resume must be exact).
         key(site) = splitmix64(data_seed ^ splitmix64(epoch << 20 | model << 4 | site))
@@ -641,6 +663,8 @@ def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model
     r(2, i) >> 63 when "y" is in it; time reversal: r(3, i) >> 63 when `reverse` -- the frames are then listed oldest first and
     the OLDEST frame labels the sample; stride: the (r(4, i) mod m)-th, in the order given, of the m strides s with
     k - 3 s >= segment start.  A forward window at stride s is frames (k, k - s, k - 2s, k - 3s) labelled by frame k.
+    label_shift = s, or one s per row of the table (alignment; the table comes from windows(label_shift=s)): the sample is
+    labelled by its labelling frame + s, forward or reversed.  Nothing else changes, no draw among them.
     The key's word keeps its three fields apart for 0 <= site < 16, 0 <= model < 2^16 and 0 <= epoch < 2^44; anything outside is
     a ValueError."""
     table = np.asarray(table, dtype=np.int64).reshape(-1, 2)
@@ -668,7 +692,7 @@ def epoch_samples(table, strides=(1,), data_seed: int = 0, epoch: int = 0, model
         rev = (r(3) >> np.uint64(63)).astype(bool)
         frames = np.where(rev[:, None], frames[:, ::-1], frames)
     out["frame"] = frames
-    out["label"] = frames[:, 0]
+    out["label"] = frames[:, 0] + np.broadcast_to(np.asarray(label_shift, dtype=np.int64), (n,))
     if "x" in flip:
         out["flags"] |= (r(1) >> np.uint64(63)).astype(np.uint32)
     if "y" in flip:
@@ -821,6 +845,123 @@ class TrainData:
     def label_mass_device(self, d_mass: int, first: int = 0, n: int | None = None, keep=None) -> None:
         """The same into device memory: u32 [n] at d_mass, 4-byte aligned."""
         self._label_mass(first, n, keep, d_mass, L.MEM_DEVICE)
+
+    def _align(self, first, n, max_shift, keep, min_mv, classes, ptrs, kind):
+        first, n, max_shift = int(first), int(n), int(max_shift)
+        if keep is not None:
+            keep = np.ascontiguousarray(np.asarray(keep) != 0, dtype=np.uint8)
+            if keep.shape != (self.h, self.w):
+                raise ValueError(f"keep must be [{self.h}][{self.w}], got {keep.shape}")
+        mask = 0
+        for c in classes:
+            if not 0 <= int(c) <= 6:
+                raise ValueError(f"classes = {tuple(classes)}: packed macroblock classes are 0 .. 6")
+            mask |= 1 << int(c)
+        out = None
+        if ptrs is None:
+            wide = 2 * max_shift + 1 if 0 <= max_shift <= 32 else 1    # a refused call writes nothing
+            out = (np.empty((max(n, 0), wide), np.uint32), np.empty(max(n, 0), np.uint32), np.empty(max(n, 0), np.uint32))
+            ptrs = [o.ctypes.data for o in out]
+        cfg = L.AlignCfg(max_shift, int(min_mv), mask, None if keep is None else keep.ctypes.data)
+        L.check(self._lib.covahip_train_data_align(self.handle, first, n, C.byref(cfg), ptrs[0], ptrs[1], ptrs[2], kind),
+                "covahip_train_data_align", self.ctx.handle)
+        return out
+
+    def align(self, first: int, n: int, max_shift: int = 8, keep=None, min_mv: int = 1, classes=()):
+        """(both u32 [n][2 S + 1], mov u32 [n], lab u32 [n]) of ONE recording, frames [first, first + n), S = max_shift, counted on
+        the device (include/covahip.h, covahip_train_data_align): both[i][j] = the kept macroblocks that move in the records of
+        frame first + i and are labelled in frame first + i + j - S (0 where that frame lies outside the recording), mov[i] and
+        lab[i] the two counts on their own.  A macroblock moves when max(mv_x, mv_y) >= min_mv (0: the vectors decide nothing) or
+        its packed class is among `classes`.  align_scores reads the three."""
+        return self._align(first, n, max_shift, keep, min_mv, classes, None, L.MEM_HOST)
+
+    def align_device(self, d_both: int, d_mov: int, d_lab: int, first: int, n: int, max_shift: int = 8, keep=None, min_mv: int = 1,
+                     classes=()) -> None:
+        """The same into device memory, each pointer 4-byte aligned."""
+        self._align(first, n, max_shift, keep, min_mv, classes, [d_both, d_mov, d_lab], L.MEM_DEVICE)
+
+
+def _align_sums(both, mov, lab, lo: int, hi: int):
+    """Per shift (B, U) over the record frames i in [lo, hi) whose label frame i + s lies inside the recording, Python integers."""
+    n, wide = both.shape
+    S = wide // 2
+    cm, cl = np.concatenate([[0], np.cumsum(mov, dtype=np.int64)]), np.concatenate([[0], np.cumsum(lab, dtype=np.int64)])
+    out = []
+    for s in range(-S, S + 1):
+        a, b = max(lo, -s, 0), min(hi, n - s, n)
+        if a >= b:
+            out.append((0, 0))
+            continue
+        B = int(both[a:b, s + S].sum(dtype=np.int64))
+        out.append((B, int(cm[b] - cm[a]) + int(cl[b + s] - cl[a + s]) - B))
+    return out
+
+
+def _align_best(sums):
+    """The shift of largest B / U as exact fractions; ties: the smaller |s|, then the smaller s; None when every U is 0."""
+    S = len(sums) // 2
+    best = None
+    for s in sorted(range(-S, S + 1), key=lambda v: (abs(v), v)):
+        B, U = sums[s + S]
+        if U > 0 and (best is None or B * sums[best + S][1] > sums[best + S][0] * U):
+            best = s
+    return best
+
+
+def _align_arrays(both, mov, lab):
+    both, mov, lab = np.asarray(both), np.asarray(mov).reshape(-1), np.asarray(lab).reshape(-1)
+    if both.ndim != 2 or both.shape[1] % 2 != 1 or mov.shape != (both.shape[0],) or lab.shape != mov.shape:
+        raise ValueError(f"both {both.shape}, mov {mov.shape}, lab {lab.shape}: expected [n][2 S + 1], [n] and [n]")
+    return both, mov, lab
+
+
+def align_scores(both, mov, lab) -> dict:
+    """How well the labels of a recording sit on its records at every shift (TrainData.align's counts).  Per shift s, over the
+    frames i with 0 <= i + s < n: B(s) = sum both[i][s + S], M(s) = sum mov[i], L(s) = sum lab[i + s], and the union
+    U = M + L - B -- B / U is the overlap of "moves" and "labelled" as sets of (frame, macroblock).  Returns {"shifts", "B", "U"
+    (lists, Python integers), "best"}: the shift of largest B / U compared as exact fractions; on ties the smaller |s|, then the
+    smaller s; None when every U is 0.  s > 0: the label of record frame f stands at f + s (windows(label_shift=s))."""
+    both, mov, lab = _align_arrays(both, mov, lab)
+    sums = _align_sums(both, mov, lab, 0, both.shape[0])
+    S = both.shape[1] // 2
+    return {"shifts": list(range(-S, S + 1)), "B": [b for b, _ in sums], "U": [u for _, u in sums], "best": _align_best(sums)}
+
+
+def align_drift(both, mov, lab, window: int = 256) -> dict:
+    """align_scores' `best` per block of `window` record frames (the last block takes the remainder; a recording shorter than a
+    window is one block), and the changes: [(first frame of the block, its shift)] for every block whose shift differs from the
+    block before it that had one.  A frame lost in the middle of a recording shows as one change near the loss; a block in which
+    no moving macroblock meets a labelled one at any shift (a quiet stretch) has no shift, None, and changes nothing.  Returns {"window", "best" (one per block),
+    "changes"}; frames count from the recording's first."""
+    both, mov, lab = _align_arrays(both, mov, lab)
+    window = int(window)
+    if window < 1:
+        raise ValueError(f"window = {window}: at least one frame")
+    n = both.shape[0]
+    blocks = max(1, n // window)
+    best, changes, last = [], [], None
+    for b in range(blocks):
+        lo, hi = b * window, n if b == blocks - 1 else (b + 1) * window
+        sums = _align_sums(both, mov, lab, lo, hi)
+        s = _align_best(sums)
+        if s is not None and sums[s + both.shape[1] // 2][0] == 0:
+            s = None                                                       # no macroblock in common at any shift
+        best.append(s)
+        if s is not None:
+            if last is not None and s != last:
+                changes.append((lo, s))
+            last = s
+    return {"window": window, "best": best, "changes": changes}
+
+
+def alignment(data, segments, max_shift: int = 8, keep=None, min_mv: int = 1, classes=(), window: int = 256) -> list:
+    """align_scores and align_drift of every segment (recording) of a TrainData: one dict per segment with "segment" (a, b),
+    align_scores' entries and "drift" = align_drift's dict."""
+    out = []
+    for a, b in _segments(segments):
+        counts = data.align(a, b - a, max_shift, keep, min_mv, classes)
+        out.append({"segment": (a, b), **align_scores(*counts), "drift": align_drift(*counts, window)})
+    return out
 
 
 def _samples(samples) -> np.ndarray:
@@ -1166,15 +1307,16 @@ class TrainerSet(_State):
             at += n
         return outs
 
-    def _masses(self, data, tables, balance, log):
-        """fit_data(balance=...): per model (first frame, label mass of the frames its table spans, under its post's keep map)."""
+    def _masses(self, data, tables, balance, log, shifts):
+        """fit_data(balance=...): per model (first frame, label mass of the frames its table's labels span, under its post's keep map)."""
         out = []
         for k, t in enumerate(tables):
-            lo, hi = int(t[:, 0].min()), int(t[:, 1].max()) + 1
+            sh = np.broadcast_to(np.asarray(shifts[k], dtype=np.int64), (t.shape[0],))
+            lo, hi = int((t[:, 0] + np.minimum(sh, 0)).min()), int((t[:, 1] + np.maximum(sh, 0)).max()) + 1
             post = self.get_post(k)
             keep = None if post is None or post[1].all() else post[1]
             mass = data.label_mass(lo, hi - lo, keep)
-            busy = int((mass[t[:, 1] - lo] >= balance).sum())
+            busy = int((mass[t[:, 1] + sh - lo] >= balance).sum())
             if log:
                 log(f"{f'model {k}: ' if self._tag_models else ''}balance {balance}: {busy} busy / {t.shape[0] - busy} quiet windows")
             out.append((lo, mass))
@@ -1182,7 +1324,7 @@ class TrainerSet(_State):
 
     def fit_data(self, data, tables_per_model, epochs: int = 20, batch: int = 4, *, strides=(1,), shuffle: bool = False, flip=(),
                  reverse: bool = False, data_seed: int = 0, val_tables=None, schedule=keras_lr, log=None, keep: str = "last",
-                 checkpoint=None, start_epoch: int = 0, balance: int | None = None):
+                 checkpoint=None, start_epoch: int = 0, balance: int | None = None, label_shift=None):
         """fit() from a resident TrainData: tables_per_model[k] = model k's windows() table, and every epoch walks
         epoch_samples(table, strides, data_seed, epoch, model = k, shuffle, flip, reverse) of it -- a new order and new mirrors
         every epoch, a pure function of (data_seed, epoch, k), so a resumed run continues exactly.  Everything else is fit's:
@@ -1195,7 +1337,10 @@ class TrainerSet(_State):
         are taken once, before the first epoch, under the keep map of ITS post if it has one (TrainData.label_mass), and the
         log gains one line per model with the busy / quiet windows of its table (each classed by its newest frame, the label of
         the forward window).  Validation tables are never balanced.  Like the augmentation settings `balance` is not in the
-        checkpoint; None runs exactly what ran before the keyword existed."""
+        checkpoint; None runs exactly what ran before the keyword existed.
+        label_shift = one entry per model, epoch_samples' label_shift for that model's table (a shift, or one per row; the
+        tables come from windows(label_shift=...)); None is 0 everywhere.  A validation table that needs a shift is passed as
+        the SAMPLE array epoch_samples(table, (min(strides),), label_shift=...) makes of it."""
         _check_fit_args(val_tables, keep)
         if len(tables_per_model) != self.n_models:
             raise ValueError(f"{len(tables_per_model)} tables for {self.n_models} models")
@@ -1210,12 +1355,16 @@ class TrainerSet(_State):
         if min(sizes) == 0:
             raise ValueError("no training samples")
         current = {}
-        masses = None if balance is None else self._masses(data, tables, balance, log)
+        shifts = [0] * self.n_models if label_shift is None else list(label_shift)
+        if len(shifts) != self.n_models:
+            raise ValueError(f"{len(shifts)} label shifts for {self.n_models} models")
+        masses = None if balance is None else self._masses(data, tables, balance, log, shifts)
 
         def take_step(ep, st, lr):
             if current.get("epoch") != ep:
                 current["epoch"] = ep
-                current["samples"] = [epoch_samples(t, strides, data_seed, ep, k, shuffle, flip, reverse) for k, t in enumerate(tables)]
+                current["samples"] = [epoch_samples(t, strides, data_seed, ep, k, shuffle, flip, reverse, shifts[k])
+                                      for k, t in enumerate(tables)]
                 if masses is not None:
                     current["samples"] = [balanced_samples(s, mass, balance, mass_first=lo, data_seed=data_seed, epoch=ep, model=k)
                                           for k, (s, (lo, mass)) in enumerate(zip(current["samples"], masses))]
@@ -1311,6 +1460,8 @@ class Trainer(_State):
 
     def fit_data(self, data, table, epochs: int = 20, batch: int = 4, *, val_table=None, **kw):
         """TrainerSet.fit_data of the one table and val_table (or None), with its keywords: the one history."""
+        if kw.get("label_shift") is not None:
+            kw["label_shift"] = [kw["label_shift"]]
         return self._set.fit_data(data, [table], epochs, batch, val_tables=None if val_table is None else [val_table], **kw)[0]
 
 
@@ -1369,9 +1520,22 @@ def parse_args(argv=None):
                                                              "carries at least N labelled macroblocks the camera keeps, and half "
                                                              "from the quiet ones (the reference's utils/data/balance.py: 100 at "
                                                              "45x80); trains from the device-resident data set")
+    ap.add_argument("--align-report", type=int, nargs="?", const=8, metavar="S", help="train nothing: score every recording's labels "
+                    "against its records at the frame shifts -S .. S (default 8, at most 32) on the device-resident data set, "
+                    "print the table (shift, B, U, B/U) and the frames where the best shift changes, and exit; needs --windows")
+    ap.add_argument("--label-shift", type=_label_shift, metavar="N|auto[:S]", help="label every window by its labelling frame + N; "
+                    "'auto' measures every recording's own shift (within -S .. S, default 8) and stops when a recording has "
+                    "none, has it at the edge of the range, or changes it half-way; needs --windows")
+    ap.add_argument("--align-window", type=int, default=256, metavar="F", help="frames of a block of the drift list (default 256)")
     a = ap.parse_args(argv)
     a.resident = (a.windows is not None or a.stride is not None or a.flip is not None or a.reverse or a.shuffle
                   or a.data_seed is not None or a.balance is not None)
+    if (a.align_report is not None or a.label_shift is not None) and a.windows is None:
+        ap.error("--align-report / --label-shift read the device-resident data set: give --windows skip|overlap")
+    if a.align_report is not None and not 0 <= a.align_report <= 32:
+        ap.error("--align-report scores the shifts -S .. S, 0 <= S <= 32")
+    if a.align_window < 1:
+        ap.error("--align-window is a count of frames, at least 1")
     if a.eval_only and a.balance is not None:
         ap.error("--balance shapes a training's epochs; --eval-only scores every window once")
     if a.balance is not None and a.balance < 1:
@@ -1389,6 +1553,8 @@ def parse_args(argv=None):
             post_paths(a.records if a.as_set else None, a.post)
         except ValueError as e:
             ap.error(str(e))
+    if a.align_report is not None:
+        return a
     if a.eval_only:
         if a.resume:
             ap.error("--resume continues a training; --eval-only trains nothing")
@@ -1422,6 +1588,19 @@ def _stride_list(text):
         return _strides([int(v) for v in text.split(",")])
     except ValueError:
         raise argparse.ArgumentTypeError(f"strides are positive integers joined with commas, got {text!r}")
+
+
+def _label_shift(text):
+    """--label-shift: an integer, or auto[:S] as ("auto", S) with 1 <= S <= 32."""
+    try:
+        if text == "auto" or text.startswith("auto:"):
+            S = int(text[5:]) if text != "auto" else 8
+            if not 1 <= S <= 32:
+                raise ValueError
+            return ("auto", S)
+        return int(text)
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"a frame shift N, or auto[:S] with S in 1 .. 32, got {text!r}")
 
 
 def _rects(text):
@@ -1601,20 +1780,78 @@ def main_set(a) -> int:
     return 0
 
 
+def align_report_text(name: str, rec: dict) -> str:
+    """--align-report: one recording's alignment() entry as text -- the table (shift, B, U, B/U) and the drift list."""
+    a, b = rec["segment"]
+    best = rec["best"]
+    lines = [f"{name}: frames [{a}, {b}), best shift {'none' if best is None else format(best, '+d')}",
+             f"  {'shift':>5} {'B':>12} {'U':>12} {'B/U':>8}"]
+    for s, B, U in zip(rec["shifts"], rec["B"], rec["U"]):
+        lines.append(f"  {s:>+5d} {B:>12d} {U:>12d} {(B / U if U else 0.0):>8.4f}" + (" *" if s == best else ""))
+    ch = rec["drift"]["changes"]
+    lines.append(f"  drift (blocks of {rec['drift']['window']} frames): " +
+                 ("none" if not ch else ", ".join(f"frame {a + f}: shift {s:+d}" for f, s in ch)))
+    return "\n".join(lines)
+
+
+def auto_label_shift(name: str, rec: dict) -> int:
+    """--label-shift auto: the recording's `best`, or a ValueError naming the recording and the frames when one offset cannot be
+    trusted to fix it: no shift at all, the best at the edge of the range (the peak may lie outside), or a drift list."""
+    a, b = rec["segment"]
+    S, best, ch = rec["shifts"][-1], rec["best"], rec["drift"]["changes"]
+    where = f"--label-shift auto: {name}, frames [{a}, {b})"
+    if best is None:
+        raise ValueError(f"{where}: nothing moves and nothing is labelled, there is no shift to measure")
+    if abs(best) == S:
+        raise ValueError(f"{where}: the best shift {best:+d} sits at the edge of -{S} .. {S}; the peak may lie outside, try auto:{min(2 * S, 32)}")
+    if ch:
+        raise ValueError(f"{where}: the shift changes inside the recording (" + ", ".join(f"frame {a + f}: {s:+d}" for f, s in ch) +
+                         "); one offset cannot fix a recording that lost a frame half-way, cut it there")
+    return best
+
+
+def _recording_shifts(a, data, recs, keep):
+    """[(first, end, shift)] of one model's recordings [(name, (first, end))] under --label-shift; --align-report prints instead."""
+    if a.align_report is None and not isinstance(a.label_shift, tuple):
+        return [(lo, hi, a.label_shift or 0) for _, (lo, hi) in recs]
+    S = a.align_report if a.align_report is not None else a.label_shift[1]
+    found = alignment(data, [seg for _, seg in recs], S, keep, window=a.align_window)
+    if a.align_report is not None:
+        for (name, _), rec in zip(recs, found):
+            print(align_report_text(name, rec))
+        return None
+    out = []
+    for (name, (lo, hi)), rec in zip(recs, found):
+        out.append((lo, hi, auto_label_shift(name, rec)))
+        print(f"{name}: label shift {out[-1][2]:+d}", file=sys.stderr)
+    return out
+
+
+def _shifted_windows(segs, rec_shifts, mode, strides):
+    """(table, shift per row) of segments that each lie inside one of the recordings [(first, end, shift)]."""
+    tabs, rows = [np.zeros((0, 2), np.int64)], [np.zeros(0, np.int64)]
+    for lo, hi in segs:
+        s = next(sh for ra, rb, sh in rec_shifts if ra <= lo and hi <= rb)
+        tabs.append(windows([(lo, hi)], mode, strides, s))
+        rows.append(np.full(tabs[-1].shape[0], s, np.int64))
+    return np.concatenate(tabs), np.concatenate(rows)
+
+
 def main_resident(a) -> int:
-    """Training or scoring from a device-resident data set (--windows / --stride / --flip / --reverse / --shuffle / --data-seed / --balance):
-    every file is one segment, one data set serves all models of a --set, and the samples of an epoch are epoch_samples of the
-    model's windows."""
+    """Training or scoring from a device-resident data set (--windows / --stride / --flip / --reverse / --shuffle / --data-seed / --balance /
+    --label-shift; --align-report): every file is one segment, one data set serves all models of a --set, and the samples of an
+    epoch are epoch_samples of the model's windows."""
     from .elements import Context
 
     where = a.eval_only or a.output
     jobs = set_jobs(a.records, where) if a.as_set else [(list(a.records), where)]
     mode, strides = a.windows or "skip", a.stride or (1,)
-    files, val_files = [], []
+    files, val_files, rec_names = [], [], []
     for k, (fl, _) in enumerate(jobs):
         files.append([read_tfrecords(f, a.h_mb, a.w_mb) for f in fl])
         names = [] if not a.val else [f for f in a.val[k].split(",") if f] if a.as_set else list(a.val)
         val_files.append([read_tfrecords(f, a.h_mb, a.w_mb) for f in names])
+        rec_names.append([f for f, (fr, _) in zip(list(fl) + names, files[k] + val_files[k]) if fr.shape[0]])
     capacity = sum(fr.shape[0] for group in files + val_files for fr, _ in group)
     if not capacity:
         raise ValueError("the records hold no frames")
@@ -1622,17 +1859,37 @@ def main_resident(a) -> int:
     ctx = Context(a.device)
     data = TrainData(ctx, a.h_mb, a.w_mb, capacity)
     tables, val_tables = [], ([] if a.val or a.val_frac is not None else None)
+    shifted = a.label_shift is not None or a.align_report is not None
+    shifts = [] if a.label_shift is not None else None          # per model: the shift of every row of its table
     for k in range(len(jobs)):
         segs = [data.append(fr, gt) for fr, gt in files[k] if fr.shape[0]]
         vsegs = [data.append(fr, gt) for fr, gt in val_files[k] if fr.shape[0]]
+        if shifted:
+            rec_shifts = _recording_shifts(a, data, list(zip(rec_names[k], segs + vsegs)), None if posts is None else posts[k].get("keep"))
+            if rec_shifts is None:
+                continue
         if a.val_frac is not None:
             segs, vsegs = split_frames_tail(segs, a.val_frac)
-        tables.append(windows(segs, mode, strides))
-        if val_tables is not None:
-            val_tables.append(windows(vsegs, mode, strides))
+        if shifted:
+            t, sh = _shifted_windows(segs, rec_shifts, mode, strides)
+            tables.append(t)
+            shifts.append(sh)
+            if val_tables is not None:
+                vt, vsh = _shifted_windows(vsegs, rec_shifts, mode, strides)
+                val_tables.append(epoch_samples(vt, (min(strides),), label_shift=vsh))   # scored as they are, at their shift
+        else:
+            tables.append(windows(segs, mode, strides))
+            if val_tables is not None:
+                val_tables.append(windows(vsegs, mode, strides))
         print((f"model {k}: " if a.as_set else "") + f"{sum(b - s for s, b in segs)} frames -> {tables[k].shape[0]} windows of "
               f"{a.h_mb}x{a.w_mb}" + (f", {val_tables[k].shape[0]} to validate" if val_tables is not None else ""), file=sys.stderr)
     del files, val_files
+    if a.align_report is not None:
+        data.close()
+        ctx.close()
+        return 0
+    if a.eval_only and shifts is not None:
+        tables = [epoch_samples(t, (min(strides),), label_shift=sh) for t, sh in zip(tables, shifts)]
     if a.eval_only:
         ts = TrainerSet(ctx, a.h_mb, a.w_mb, weights=[_read_weights(p) for _, p in jobs], max_batch=a.batch)
         _apply_posts(ts, posts)
@@ -1656,7 +1913,7 @@ def main_resident(a) -> int:
         start = _resume(ts, a, len(jobs))
         ts.fit_data(data, tables, epochs=a.epochs, batch=a.batch, strides=strides, shuffle=a.shuffle, flip=a.flip or (),
                     reverse=a.reverse, data_seed=a.data_seed or 0, val_tables=val_tables, log=lambda s: print(s, file=sys.stderr),
-                    keep=a.keep, checkpoint=a.checkpoint, start_epoch=start, balance=a.balance)
+                    keep=a.keep, checkpoint=a.checkpoint, start_epoch=start, balance=a.balance, label_shift=shifts)
         for k, (_, out) in enumerate(jobs):
             with open(out, "wb") as f:
                 f.write(ts.best_weights_bytes(k) if a.keep == "best" else ts.weights_bytes(k))

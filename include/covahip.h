@@ -758,6 +758,36 @@ int  covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample
                                int mem_kind);
 int  covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t n, const uint8_t *keep_or_null, uint32_t *mass,
                                    int mem_kind);
+/* covahip_train_data_align: whether the labels of ONE recording, frames [first, first + n), stand at the frames of their records.
+ * Records come from the entropy front end and labels from a pixel decoder; a frame dropped by either moves every label by a few
+ * frames against its record, and nothing else in training shows it.  The counts compare where the records MOVE with where the
+ * labels are SET, per frame and per shift s in -S .. S.  The fields of a record are those covahip_carrier_pack stores: class in
+ * bits 0-2, mv_x in bits 3-5, mv_y in bits 6-8.
+ *       moves_f[p] = keep'[p] and (min_mv > 0 and max(mv_x, mv_y) >= min_mv   or   bit `class` of class_mask) of frame f at p,
+ *       set_f[p]   = keep'[p] and gt_f[p] != 0,            keep' as covahip_train_data_label_mass has it;
+ *   for i in [0, n), f = first + i, j in [0, 2 S + 1), s = j - S and g = f + s:
+ *       both[i][j] = #{p : moves_f[p] and set_g[p]} when first <= g < first + n, else 0 (a shift never reads a neighbouring
+ *                    recording),
+ *       mov[i]     = #{p : moves_f[p]},        lab[i] = #{p : set_f[p]}  (covahip_train_data_label_mass of the same frame and map).
+ *   Sign: s > 0 reads "the label that belongs to record frame f stands at f + s".  Integer counts, exact; a label byte at an
+ *   ignored macroblock counts nothing whatever its value (Contract G).  mem_kind applies to the three outputs (DEVICE outputs
+ *   4-byte aligned); host outputs move through the data set's staging in chunks of frames.  Every record and label byte is read
+ *   once per call, apart from 2 S label frames per 32 frames; the 2 S + 1 shifts are scored on bit planes in LDS.
+ *   COVAHIP_ERR_INVALID_ARG, checked on the host before anything is launched and with nothing written: a NULL pointer, n < 1, a
+ *   range outside the data set, max_shift outside 0 .. 32, min_mv outside 0 .. 6, a class bit >= 7, min_mv == 0 with
+ *   class_mask == 0 (nothing can move), a keep map without a single non-zero byte, an unknown mem_kind, a misaligned device
+ *   output. */
+typedef struct covahip_align_cfg {
+    int32_t  max_shift;   /* S: shifts -S .. S are scored; 0 <= S <= 32                                             */
+    int32_t  min_mv;      /* 1 .. 6: a macroblock MOVES when max(mv_x, mv_y) of its packed record >= min_mv; 0: the
+                             vectors decide nothing                                                                  */
+    uint32_t class_mask;  /* bit c, c in 0 .. 6: a macroblock whose packed class (min(class, 6)) is c moves whatever
+                             its vectors say; bits 7.. must be 0                                                     */
+    const uint8_t *keep;  /* HOST u8 [h_mb * w_mb] or NULL, covahip_train_set_post's keep' (non-zero = kept)         */
+} covahip_align_cfg;
+int  covahip_train_data_align(covahip_train_data *d, int64_t first, int64_t n, const covahip_align_cfg *cfg,
+                              uint32_t *both /* [n][2S+1] */, uint32_t *mov /* [n] */, uint32_t *lab /* [n] */,
+                              int mem_kind);
 void covahip_train_data_destroy(covahip_train_data *d);
 /* covahip_train_step / _step_set / _eval / _eval_set on samples of a data set: the gather launch writes the batch straight into
  * the trainer's own staging, in the packing the step expects; nothing is copied from the host but the table.  samples: packed in
