@@ -120,6 +120,13 @@ class MonitorCfg(C.Structure):
 
 
 MONITOR_AREA_BINS = 16
+INPUT_STACKED, INPUT_FRAMES, INPUT_PACKED = 0, 1, 2
+INPUT_BINS, INPUT_MOVE_BINS = 512, 16
+
+
+class RecordStats(C.Structure):
+    """covahip_record_stats: host pointers, each may be NULL."""
+    _fields_ = [(k, C.c_void_p) for k in ("frames", "hist", "hist_set", "set_total", "moving", "still_frames", "intra_frames", "move_hist")]
 
 
 class MogCfg(C.Structure):
@@ -272,6 +279,7 @@ PROTOTYPES = {
     "covahip_train_data_frames": (C.c_int, [_P, C.POINTER(C.c_int64)]),
     "covahip_train_data_gather": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int]),
     "covahip_train_data_label_mass": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int]),
+    "covahip_train_data_record_stats": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(RecordStats)]),
     "covahip_train_data_align": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(AlignCfg), _P, _P, _P, C.c_int]),
     "covahip_train_data_destroy": (None, [_P]),
     "covahip_train_step_data": (C.c_int, [_P, _P, _P, C.c_int, C.c_float, C.POINTER(C.c_float)]),
@@ -286,6 +294,10 @@ PROTOTYPES = {
     "covahip_monitor_add": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int]),
     "covahip_monitor_read": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "covahip_monitor_end": (C.c_int, [_P]),
+    "covahip_monitor_set_inputs": (C.c_int, [_P, C.c_int]),
+    "covahip_monitor_get_inputs": (C.c_int, [_P, C.POINTER(C.c_int)]),
+    "covahip_monitor_add_inputs": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, C.c_int]),
+    "covahip_monitor_read_inputs": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P]),
     "covahip_mog_default_cfg": (None, [C.POINTER(MogCfg)]),
     "covahip_mog_create": (C.c_int, [_P, C.POINTER(MogCfg), C.POINTER(_P)]),
     "covahip_mog_create_grid": (C.c_int, [_P, C.POINTER(MogCfg), C.c_int, C.POINTER(_P)]),
@@ -329,6 +341,7 @@ DEV_PROTOTYPES = {
     "covahip_dev_mog_set_post_form": (C.c_int, [_P, C.c_int, C.c_int]),
     "covahip_dev_mog_band_plan": (C.c_int, [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_size_t)]),
     "covahip_dev_monitor_slice": (C.c_int, [_P, C.c_int]),
+    "covahip_dev_input_flush": (C.c_int, [_P, C.c_int]),
     "covahip_dev_heat_set_stage": (C.c_int, [_P, _SZ]),
     "covahip_dev_train_data_set_stage": (C.c_int, [_P, _SZ]),
 }

@@ -485,7 +485,7 @@ static int filter_placed(covahip_ctx *ctx, covahip_blobnet *m, const uint8_t *d_
     int rc = filter_dev(ctx, in, batch, d_logits, d_mask, true, area_thresh, d_boxes, d_counts, max_boxes, n_frames > 0 ? nullptr : model_ids);
     // the serving monitor (monitor.hip): the batch's mask, counts and boxes are on the device and this is the stream that wrote them
     if (rc == COVAHIP_OK && batch > 0 && ctx->mon && ctx->mon->attached && !ctx->mon_suspended)
-        rc = covahip_monitor_hook(ctx, d_mask, d_counts, d_boxes, max_boxes, model_ids, batch);
+        rc = covahip_monitor_hook(ctx, d_mask, d_counts, d_boxes, max_boxes, model_ids, batch, &in);
     return rc;
 }
 

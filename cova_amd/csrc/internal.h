@@ -91,6 +91,14 @@ struct CovahipMonitor {
     size_t words = 0;
     int64_t batches_seen = 0, batches_counted = 0;
     MonTable lane[COVAHIP_MAX_LANES];   // attached: one per lane (lane 0's also serves the primary stream); stand-alone: [0] only
+    // covahip_monitor_set_inputs (input_stats.hip), null / empty while the input statistics are off.  i64 words per model:
+    // in_frames, still_frames, intra_frames, (spare) | hist [512] | move_hist [16] | moving [h][w]
+    unsigned long long *d_in = nullptr;
+    size_t in_words = 0;
+    // per-frame partials of a batch in flight, u64 [samples][2] per lane as `lane`, zero between batches
+    unsigned long long *in_scratch[COVAHIP_MAX_LANES] = {};
+    int in_samples = 0;          // samples a scratch holds
+    MonTable in_frames;          // stand-alone: a call's host frame list beyond what travels in the kernel arguments
 };
 
 struct covahip_ctx {
@@ -145,6 +153,7 @@ struct covahip_ctx {
     // filter steps bypass it (covahip_dev_graph_probe: a captured step must not carry a counted launch into its replays)
     CovahipMonitor *mon = nullptr;
     int mon_slice = 0;
+    int in_flush = 0;   // samples between two flushes of the input kernel's workgroup counters; 0: its default (covahip_dev_input_flush)
     bool mon_suspended = false;
 };
 
@@ -242,8 +251,15 @@ int covahip_bboxcc_launch(covahip_ctx *ctx, const uint8_t *d_mask, int batch, in
 // monitor.hip
 // The hook at the end of a filter step that succeeded, on ctx->stream (the lane that ran the batch): sees the batch and, every
 // `every`-th time, counts it with one launch.  Only called while an attached monitor is open and not suspended.
+// in: the batch's input as the forward took it (blobnet.h), for the input statistics; null: the inputs are not counted.
+struct BnInput;
 int covahip_monitor_hook(covahip_ctx *ctx, const uint8_t *d_mask, const int32_t *d_counts, const covahip_box *d_boxes, int max_boxes,
-                         const uint8_t *model_ids, int batch);
+                         const uint8_t *model_ids, int batch, const BnInput *in = nullptr);
+// input_stats.hip: the counted batch's inputs by the batch's plan (monitor_tab.h), on ctx->stream; frees what set_inputs allocated
+struct MonPlan;
+int covahip_monitor_hook_inputs(covahip_ctx *ctx, CovahipMonitor *mon, const MonPlan &plan, const uint8_t *model_ids, const BnInput &in,
+                                int batch);
+void covahip_monitor_free_inputs(CovahipMonitor *mon);
 void covahip_monitor_close(covahip_ctx *ctx, bool attached_only);   // drains the ctx and frees the monitor (if any)
 
 // train_data.hip: what the trainer's data entry points (train.hip) need of a covahip_train_data

@@ -23,45 +23,16 @@
 #include "blobnet.h"
 #include "covahip_dev.h"
 #include "internal.h"
+#include "monitor_tab.h"
 
 namespace {
 
 constexpr int MON_TILE = 256;            // macroblocks per mask workgroup: 64 lanes x 4 bytes
-constexpr int MON_KTAB = 256;            // samples whose order / slice table travels in the kernel arguments
 constexpr int MON_MIN_SLICE = 16;        // fewer samples than this do not pay for a slice's flush
 constexpr int MON_CHUNK = 16384;         // samples per launch of a stand-alone add
 constexpr int MON_SPILL = 255;           // samples a packed byte lane takes
 constexpr size_t MON_STAGE = (size_t)64 << 20;   // host samples are staged in pieces of at most this many bytes
 constexpr int MON_BINS = COVAHIP_MONITOR_AREA_BINS;
-
-// The three forms of the table.  A slice s of S covers positions [i0, i1) of the order; position i is sample `sample(i)`.
-struct MonUniform {   // one model: slices are ranges of the call's own order
-    int model, per_slice;
-};
-struct MonByValue {   // <= MON_KTAB samples: start[s] is slice s's first position (the next slice's start, or n, ends it)
-    uint8_t order[MON_KTAB], start[MON_KTAB], model[MON_KTAB];
-};
-struct MonByPtr {     // i32 [S starts][S models][n order] on the device
-    const int32_t *tab;
-};
-__device__ inline void mon_slice(const MonUniform &t, int s, int S, int n, int &m, int &i0, int &i1) {
-    m = t.model;
-    i0 = s * t.per_slice;
-    i1 = min(n, i0 + t.per_slice);
-}
-__device__ inline int mon_sample(const MonUniform &, int, int i) { return i; }
-__device__ inline void mon_slice(const MonByValue &t, int s, int S, int n, int &m, int &i0, int &i1) {
-    m = t.model[s];
-    i0 = t.start[s];
-    i1 = s + 1 < S ? (int)t.start[s + 1] : n;
-}
-__device__ inline int mon_sample(const MonByValue &t, int, int i) { return t.order[i]; }
-__device__ inline void mon_slice(const MonByPtr &t, int s, int S, int n, int &m, int &i0, int &i1) {
-    m = t.tab[S + s];
-    i0 = t.tab[s];
-    i1 = s + 1 < S ? t.tab[s + 1] : n;
-}
-__device__ inline int mon_sample(const MonByPtr &t, int S, int i) { return t.tab[2 * S + i]; }
 
 // every non-zero byte of v -> 1 (bit 0 of a byte ends up as the OR of its eight bits; what the shifts drag in from the byte above
 // never reaches bit 0)
@@ -205,26 +176,47 @@ void launch(covahip_ctx *ctx, const CovahipMonitor *mon, bool words, const uint8
                            mon->n_models, tiles, S, t, mon->d_tab);
 }
 
-// One launch over n device-resident samples on ctx->stream; tb: the table buffers of the lane (or of the primary stream).
-// n <= tb.cap / 3 when the batch is mixed and larger than MON_KTAB (the callers see to it).
-int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, MonTable &tb, const uint8_t *d_mask, const int32_t *d_counts,
-                const covahip_box *d_boxes, int max_boxes, const uint8_t *model_ids, int n) {
+// One launch over n device-resident samples on ctx->stream, by the batch's plan.
+int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, const MonPlan &plan, const uint8_t *d_mask, const int32_t *d_counts,
+                const covahip_box *d_boxes, int max_boxes, int n) {
     const int hw = mon->h * mon->w;
     const int tiles = (hw + MON_TILE - 1) / MON_TILE;
-    const int num_cu = std::max(1, ctx->props.multiProcessorCount);
-    // slices: enough workgroups for every CU, none shorter than MON_MIN_SLICE samples (or the developer's length)
-    const int want = (num_cu + tiles - 1) / tiles;
-    const int per = ctx->mon_slice > 0 ? ctx->mon_slice : std::max(MON_MIN_SLICE, (n + want - 1) / want);
     const bool words = hw % 4 == 0 && (reinterpret_cast<uintptr_t>(d_mask) & 3) == 0;
+    ProfScope ps(ctx, "monitor_count");
+    if (plan.kind == MonPlan::UNIFORM) launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, plan.S, plan.u);
+    else if (plan.kind == MonPlan::BY_VALUE) launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, plan.S, plan.v);
+    else launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, plan.S, plan.p);
+    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    return COVAHIP_OK;
+}
+
+int mon_tiles(const CovahipMonitor *mon) { return (mon->h * mon->w + MON_TILE - 1) / MON_TILE; }
+
+void free_monitor(CovahipMonitor *mon) {
+    if (!mon) return;
+    if (mon->d_tab) hipFree(mon->d_tab);
+    covahip_monitor_free_inputs(mon);
+    for (MonTable &tb : mon->lane) tb.release();
+    delete mon;
+}
+
+}  // namespace
+
+// n <= tb.cap / 3 when the batch is mixed and larger than MON_KTAB (the callers see to it).
+int covahip_monitor_plan(covahip_ctx *ctx, MonTable &tb, int tiles, int per_cu, int min_slice, const uint8_t *model_ids, int n,
+                         MonPlan *plan) {
+    const int num_cu = std::max(1, ctx->props.multiProcessorCount);
+    // slices: enough workgroups for every CU, none shorter than min_slice samples (or the developer's length)
+    const int want = (num_cu * per_cu + tiles - 1) / tiles;
+    const int per = ctx->mon_slice > 0 ? ctx->mon_slice : std::max(min_slice, (n + want - 1) / want);
     bool uniform = true;
     if (model_ids)
         for (int b = 1; b < n && uniform; b++) uniform = model_ids[b] == model_ids[0];
-    ProfScope ps(ctx, "monitor_count");
     if (uniform) {
         const int S = (n + per - 1) / per;
-        const MonUniform t{model_ids ? model_ids[0] : 0, (n + S - 1) / S};
-        launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, (n + t.per_slice - 1) / t.per_slice, t);
-        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+        plan->kind = MonPlan::UNIFORM;
+        plan->u = MonUniform{model_ids ? model_ids[0] : 0, (n + S - 1) / S};
+        plan->S = (n + plan->u.per_slice - 1) / plan->u.per_slice;
         return COVAHIP_OK;
     }
     // stable counting sort of the samples by model, each model's segment cut into slices of near-equal length
@@ -242,15 +234,15 @@ int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, MonTable &tb, const uint8
         }
     }
     const int S = (int)starts.size();
+    plan->S = S;
     if (n <= MON_KTAB) {
-        MonByValue t;
+        MonByValue &t = plan->v;
         std::memset(&t, 0, sizeof(t));
         int at[COVAHIP_MAX_MODELS];
         std::copy(seg, seg + COVAHIP_MAX_MODELS, at);
         for (int b = 0; b < n; b++) t.order[at[model_ids[b]]++] = (uint8_t)b;
         for (int s = 0; s < S; s++) t.start[s] = (uint8_t)starts[s], t.model[s] = (uint8_t)models[s];
-        launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, S, t);
-        COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+        plan->kind = MonPlan::BY_VALUE;
         return COVAHIP_OK;
     }
     std::vector<int32_t> table((size_t)2 * S + n);
@@ -263,26 +255,23 @@ int count_batch(covahip_ctx *ctx, CovahipMonitor *mon, MonTable &tb, const uint8
     }
     const int32_t *d_table = nullptr;   // (a counted batch never allocates: a table beyond what begin reserved is refused)
     if (int rc = tb.upload(ctx, table.data(), table.size(), &d_table)) return rc;
-    launch(ctx, mon, words, d_mask, d_counts, d_boxes, n, max_boxes, tiles, S, MonByPtr{d_table});
-    COVAHIP_CHECK_HIP(ctx, hipGetLastError());
+    plan->kind = MonPlan::BY_PTR;
+    plan->p = MonByPtr{d_table};
     return COVAHIP_OK;
 }
 
-void free_monitor(CovahipMonitor *mon) {
-    if (!mon) return;
-    if (mon->d_tab) hipFree(mon->d_tab);
-    for (MonTable &tb : mon->lane) tb.release();
-    delete mon;
-}
-
-}  // namespace
-
 int covahip_monitor_hook(covahip_ctx *ctx, const uint8_t *d_mask, const int32_t *d_counts, const covahip_box *d_boxes, int max_boxes,
-                         const uint8_t *model_ids, int batch) {
+                         const uint8_t *model_ids, int batch, const BnInput *in) {
     CovahipMonitor *mon = ctx->mon;
     const bool counted = mon->batches_seen % mon->every == 0;
-    if (counted)
-        if (int rc = count_batch(ctx, mon, mon->lane[ctx->cur_lane], d_mask, d_counts, d_boxes, max_boxes, model_ids, batch)) return rc;
+    if (counted) {
+        MonPlan plan;
+        if (int rc = covahip_monitor_plan(ctx, mon->lane[ctx->cur_lane], mon_tiles(mon), 1, MON_MIN_SLICE, model_ids, batch, &plan)) return rc;
+        if (int rc = count_batch(ctx, mon, plan, d_mask, d_counts, d_boxes, max_boxes, batch)) return rc;
+        // the batch's inputs (input_stats.hip) behind it on the same stream; a plan that lies in the lane's table is shared
+        if (mon->d_in && in)
+            if (int rc = covahip_monitor_hook_inputs(ctx, mon, plan, model_ids, *in, batch)) return rc;
+    }
     mon->batches_seen++;
     mon->batches_counted += counted;
     return COVAHIP_OK;
@@ -352,10 +341,14 @@ int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *co
     if (int prc = covahip_primary_op(ctx)) return prc;   // on the primary stream, behind all lanes
     const size_t hw = (size_t)mon->h * mon->w, mb = (size_t)mon->max_boxes;
     if (mem_kind == COVAHIP_MEM_DEVICE) {
-        for (int s0 = 0; s0 < n; s0 += MON_CHUNK)
-            if (int rc = count_batch(ctx, mon, mon->lane[0], mask + (size_t)s0 * hw, counts + s0, boxes ? boxes + (size_t)s0 * mb : nullptr,
-                                     mon->max_boxes, model_ids ? model_ids + s0 : nullptr, std::min(MON_CHUNK, n - s0)))
+        for (int s0 = 0; s0 < n; s0 += MON_CHUNK) {
+            const int c = std::min(MON_CHUNK, n - s0);
+            MonPlan plan;
+            if (int rc = covahip_monitor_plan(ctx, mon->lane[0], mon_tiles(mon), 1, MON_MIN_SLICE, model_ids ? model_ids + s0 : nullptr, c, &plan)) return rc;
+            if (int rc = count_batch(ctx, mon, plan, mask + (size_t)s0 * hw, counts + s0, boxes ? boxes + (size_t)s0 * mb : nullptr,
+                                     mon->max_boxes, c))
                 return rc;
+        }
     } else {   // staged in pieces: [mask][counts][boxes]
         const size_t per_sample = hw + sizeof(int32_t) + mb * sizeof(covahip_box);
         const int piece = (int)std::min<size_t>(std::min(n, MON_CHUNK), std::max<size_t>(1, MON_STAGE / per_sample));
@@ -370,7 +363,9 @@ int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *co
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(sm, mask + (size_t)s0 * hw, (size_t)c * hw, hipMemcpyHostToDevice, ctx->stream));
             COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(sc, counts + s0, (size_t)c * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
             if (mb) COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(sb, boxes + (size_t)s0 * mb, (size_t)c * mb * sizeof(covahip_box), hipMemcpyHostToDevice, ctx->stream));
-            if (int rc = count_batch(ctx, mon, mon->lane[0], sm, sc, sb, mon->max_boxes, model_ids ? model_ids + s0 : nullptr, c)) return rc;
+            MonPlan plan;
+            if (int rc = covahip_monitor_plan(ctx, mon->lane[0], mon_tiles(mon), 1, MON_MIN_SLICE, model_ids ? model_ids + s0 : nullptr, c, &plan)) return rc;
+            if (int rc = count_batch(ctx, mon, plan, sm, sc, sb, mon->max_boxes, c)) return rc;
         }
     }
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));   // the caller may overwrite its arrays
@@ -403,6 +398,7 @@ int covahip_monitor_read(covahip_ctx *ctx, int reset, int64_t *frames, int64_t *
     if (batches_counted) *batches_counted = mon->batches_counted;
     if (reset) {
         COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(mon->d_tab, 0, mon->words * sizeof(unsigned long long), ctx->stream));
+        if (mon->d_in) COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(mon->d_in, 0, mon->in_words * sizeof(unsigned long long), ctx->stream));
         COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(ctx->stream));
         mon->batches_seen = mon->batches_counted = 0;
     }

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "internal.h"
+#include "monitor_tab.h"
 
 namespace {
 
@@ -73,6 +74,9 @@ struct covahip_train_data {
     std::vector<uint16_t> pack;                                 // host staging of a host append
     size_t stage_budget = STAGE_BYTES;                          // covahip_dev_train_data_set_stage changes it per set
     ResidentTable<uint32_t> keep_bits;                          // label mass: the call's keep map, a bit per macroblock; reserved on first use
+    // record statistics: i64 [4 + 512 + 16 + hw] as one model of the input monitor | hist_set [512] | the launch pair's per-frame
+    // partials u64 [IN_CHUNK][2] (zero between calls); one allocation, on first use
+    unsigned long long *stats = nullptr;
 };
 
 namespace {
@@ -88,6 +92,7 @@ void free_data(covahip_train_data *d) {
     if (d->d_tab) hipFree(d->d_tab);
     if (d->h_tab) hipHostFree(d->h_tab);
     if (d->stage) hipFree(d->stage);
+    if (d->stats) hipFree(d->stats);
     d->keep_bits.release();
     delete d;
 }
@@ -274,6 +279,58 @@ int covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t 
         }
     }
     COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    return COVAHIP_OK;
+}
+
+int covahip_train_data_record_stats(covahip_train_data *d, int64_t first, int64_t n, const covahip_record_stats *out) {
+    if (!d || !out || n < 1 || first < 0) return COVAHIP_ERR_INVALID_ARG;
+    if (n > d->frames || first > d->frames - n) return COVAHIP_ERR_INVALID_ARG;
+    covahip_ctx *ctx = d->ctx;
+    if (int rc = enter(ctx)) return rc;
+    const hipStream_t s = ctx->stream;
+    const int hw = d->h * d->w;
+    const size_t words = covahip_input_words((size_t)hw), counts = words + IN_HIST;
+    const size_t total = counts + (size_t)IN_CHUNK * 2;
+    if (!d->stats) {
+        COVAHIP_CHECK_HIP(ctx, hipMalloc(reinterpret_cast<void **>(&d->stats), total * sizeof(unsigned long long)));
+        COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(d->stats, 0, total * sizeof(unsigned long long), s));
+    } else {   // the partials too: an earlier call that failed between its two launches may have left some
+        COVAHIP_CHECK_HIP(ctx, hipMemsetAsync(d->stats, 0, total * sizeof(unsigned long long), s));
+    }
+    MonTable none;   // (a one-model plan uploads nothing)
+    for (int64_t at = 0; at < n; at += IN_CHUNK) {
+        const int c = (int)std::min<int64_t>(IN_CHUNK, n - at);
+        MonPlan plan;
+        if (int rc = covahip_input_plan(ctx, none, hw, nullptr, c, &plan)) return rc;
+        InJob j;
+        j.src = reinterpret_cast<const uint8_t *>(d->rec);
+        j.packed = true;
+        j.stride = (size_t)hw * sizeof(uint16_t);
+        j.frames.off = (int)(first + at);
+        j.labels = d->gt;
+        j.tab = d->stats;
+        j.model_stride = words;
+        j.set_hist = d->stats + words;
+        j.scratch = d->stats + counts;
+        j.hw = hw;
+        if (int rc = covahip_input_count(ctx, j, plan, c)) return rc;
+    }
+    std::vector<int64_t> host(counts);
+    COVAHIP_CHECK_HIP(ctx, hipMemcpyAsync(host.data(), d->stats, counts * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    COVAHIP_CHECK_HIP(ctx, hipStreamSynchronize(s));
+    const int64_t *t = host.data();
+    if (out->frames) *out->frames = t[0];
+    if (out->still_frames) *out->still_frames = t[1];
+    if (out->intra_frames) *out->intra_frames = t[2];
+    if (out->hist) std::copy(t + IN_HEAD, t + IN_HEAD + IN_HIST, out->hist);
+    if (out->move_hist) std::copy(t + IN_HEAD + IN_HIST, t + IN_HEAD + IN_HIST + IN_MOVE_BINS, out->move_hist);
+    if (out->moving) std::copy(t + IN_HEAD + IN_HIST + IN_MOVE_BINS, t + words, out->moving);
+    if (out->hist_set) std::copy(t + words, t + counts, out->hist_set);
+    if (out->set_total) {
+        int64_t sum = 0;
+        for (size_t k = words; k < counts; k++) sum += t[k];
+        *out->set_total = sum;
+    }
     return COVAHIP_OK;
 }
 

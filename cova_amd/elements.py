@@ -272,6 +272,17 @@ class BlobNetInfer:
         from . import monitor
         return monitor.read(self.ctx, reset)
 
+    def monitor_set_inputs(self, on: bool = True):
+        """Switches the input statistics of the open monitor on or off (covahip_monitor_set_inputs): with them on, every counted
+        batch also counts the records it was fed -- histogram, moving map, still and all-intra frames -- in two more launches."""
+        from . import monitor
+        monitor.set_inputs(self.ctx, on)
+
+    def monitor_read_inputs(self, reset: bool = False) -> dict:
+        """The input tables (covahip_monitor_read_inputs; cova_amd.monitor.read_inputs); reset zeroes them (only) afterwards."""
+        from . import monitor
+        return monitor.read_inputs(self.ctx, reset)
+
     def monitor_end(self):
         """Closes the monitor (covahip_monitor_end)."""
         from . import monitor

@@ -97,6 +97,14 @@ frames changes (align_drift): a frame lost half-way.  --label-shift N labels eve
 of windows shrunk so that this frame stays inside the recording (windows / epoch_samples label_shift); --label-shift auto[:S]
 measures each recording's own N and stops, naming the recording, when there is none, when it sits at +-S, or when it changes
 inside the recording.  Both need --windows.  The shift is a pure function of the data and the arguments: --resume stays exact.
+
+    python -m cova_amd.train CAM.tfrecord --windows overlap --record-report [--save-inputs CAM.inputs.json]
+
+--record-report trains nothing either: per recording it counts the records on the device (TrainData.record_stats, the input
+monitor's quantities) and prints the class and vector marginals, the GoP estimate, the still share, the share of labelled
+macroblocks whose record is all skip and the share of moving macroblocks that are labelled -- whether the records carry the labels
+at all.  --save-inputs writes the counts of all recordings together: the baseline python -m cova_amd.monitor --input-baseline
+compares a deployed camera with.
 """
 from __future__ import annotations
 
@@ -842,6 +850,24 @@ class TrainData:
         ignore region sees, counted on the device (balanced_samples)."""
         return self._label_mass(first, n, keep, None, L.MEM_HOST)
 
+    def record_stats(self, first: int | None = None, n: int | None = None) -> dict:
+        """The input statistics of frames [first, first + n) (None: from 0 / up to `frames`), counted on the device
+        (include/covahip.h, covahip_train_data_record_stats): in_frames, still_frames, intra_frames, set_total (ints), hist and
+        hist_set i64 [512] (all records / the records at labelled macroblocks), moving i64 [h][w], move_hist i64 [16] -- the
+        quantities cova_amd.monitor.read_inputs gives per served camera, so monitor.input_report(stats, None) reads them and
+        monitor.save_inputs(path, stats, None) writes the baseline a deployed camera is compared with.  No keep map applies."""
+        first = 0 if first is None else int(first)
+        n = self.frames - first if n is None else int(n)
+        one = {k: np.zeros(1, np.int64) for k in ("frames", "set_total", "still_frames", "intra_frames")}
+        out = {"hist": np.zeros(L.INPUT_BINS, np.int64), "hist_set": np.zeros(L.INPUT_BINS, np.int64),
+               "moving": np.zeros((self.h, self.w), np.int64), "move_hist": np.zeros(L.INPUT_MOVE_BINS, np.int64)}
+        st = L.RecordStats(**{k: v.ctypes.data for k, v in {**one, **out}.items()})
+        L.check(self._lib.covahip_train_data_record_stats(self.handle, first, n, C.byref(st)), "covahip_train_data_record_stats",
+                self.ctx.handle)
+        out.update(in_frames=int(one["frames"][0]), set_total=int(one["set_total"][0]), still_frames=int(one["still_frames"][0]),
+                   intra_frames=int(one["intra_frames"][0]))
+        return out
+
     def label_mass_device(self, d_mass: int, first: int = 0, n: int | None = None, keep=None) -> None:
         """The same into device memory: u32 [n] at d_mass, 4-byte aligned."""
         self._label_mass(first, n, keep, d_mass, L.MEM_DEVICE)
@@ -1526,12 +1552,25 @@ def parse_args(argv=None):
     ap.add_argument("--label-shift", type=_label_shift, metavar="N|auto[:S]", help="label every window by its labelling frame + N; "
                     "'auto' measures every recording's own shift (within -S .. S, default 8) and stops when a recording has "
                     "none, has it at the edge of the range, or changes it half-way; needs --windows")
+    ap.add_argument("--record-report", action="store_true", help="train nothing: per recording, count the records on the "
+                    "device-resident data set and print the class and vector marginals, the GoP estimate, the still share, the share "
+                    "of labelled macroblocks whose record is all skip and the share of moving macroblocks that are labelled, and "
+                    "exit; needs --windows")
+    ap.add_argument("--save-inputs", nargs="+", metavar="JSON", help="with --record-report: write the input counts of all of a "
+                    "model's recordings together, one file per model -- the training baseline python -m cova_amd.monitor "
+                    "--input-baseline compares a deployed camera with")
     ap.add_argument("--align-window", type=int, default=256, metavar="F", help="frames of a block of the drift list (default 256)")
     a = ap.parse_args(argv)
     a.resident = (a.windows is not None or a.stride is not None or a.flip is not None or a.reverse or a.shuffle
                   or a.data_seed is not None or a.balance is not None)
     if (a.align_report is not None or a.label_shift is not None) and a.windows is None:
         ap.error("--align-report / --label-shift read the device-resident data set: give --windows skip|overlap")
+    if a.record_report and a.windows is None:
+        ap.error("--record-report reads the device-resident data set: give --windows skip|overlap")
+    if a.save_inputs and not a.record_report:
+        ap.error("--save-inputs writes what --record-report counts")
+    if a.save_inputs and len(a.save_inputs) != (len(a.records) if a.as_set else 1):
+        ap.error("--save-inputs takes one file per model")
     if a.align_report is not None and not 0 <= a.align_report <= 32:
         ap.error("--align-report scores the shifts -S .. S, 0 <= S <= 32")
     if a.align_window < 1:
@@ -1553,7 +1592,7 @@ def parse_args(argv=None):
             post_paths(a.records if a.as_set else None, a.post)
         except ValueError as e:
             ap.error(str(e))
-    if a.align_report is not None:
+    if a.align_report is not None or a.record_report:
         return a
     if a.eval_only:
         if a.resume:
@@ -1810,6 +1849,33 @@ def auto_label_shift(name: str, rec: dict) -> int:
     return best
 
 
+def record_report_text(name: str, st: dict) -> str:
+    """--record-report: one recording's TrainData.record_stats as text."""
+    from . import monitor
+    rep = monitor.input_report(st, None)
+    r = np.arange(L.INPUT_BINS)
+    total, moving = rep["macroblocks"], int(np.asarray(st["hist"])[(r & 0x1F8) != 0].sum())
+    set_moving = int(np.asarray(st["hist_set"])[(r & 0x1F8) != 0].sum())
+    skip_share = "n/a" if not st["set_total"] else f"{100.0 * int(st['hist_set'][0]) / st['set_total']:.2f} %"
+    lab_share = "n/a" if not moving else f"{100.0 * set_moving / moving:.2f} %"
+    return (monitor.format_input_report(rep, name) +
+            f"\n  labelled macroblocks {st['set_total']} of {total}: all-skip records among them {skip_share}; "
+            f"moving macroblocks that are labelled {lab_share}")
+
+
+def _record_report(a, data, recs, k):
+    """--record-report for model k's recordings [(name, (first, end))]; --save-inputs: their counts together."""
+    from . import monitor
+    total = None
+    for name, (lo, hi) in recs:
+        st = data.record_stats(lo, hi - lo)
+        print(record_report_text(name, st))
+        total = st if total is None else {key: total[key] + st[key] for key in st}
+    if a.save_inputs and total is not None:
+        monitor.save_inputs(a.save_inputs[k], total, None)
+        print(f"wrote {a.save_inputs[k]}")
+
+
 def _recording_shifts(a, data, recs, keep):
     """[(first, end, shift)] of one model's recordings [(name, (first, end))] under --label-shift; --align-report prints instead."""
     if a.align_report is None and not isinstance(a.label_shift, tuple):
@@ -1864,6 +1930,9 @@ def main_resident(a) -> int:
     for k in range(len(jobs)):
         segs = [data.append(fr, gt) for fr, gt in files[k] if fr.shape[0]]
         vsegs = [data.append(fr, gt) for fr, gt in val_files[k] if fr.shape[0]]
+        if a.record_report:
+            _record_report(a, data, list(zip(rec_names[k], segs + vsegs)), k)
+            continue
         if shifted:
             rec_shifts = _recording_shifts(a, data, list(zip(rec_names[k], segs + vsegs)), None if posts is None else posts[k].get("keep"))
             if rec_shifts is None:
@@ -1884,7 +1953,7 @@ def main_resident(a) -> int:
         print((f"model {k}: " if a.as_set else "") + f"{sum(b - s for s, b in segs)} frames -> {tables[k].shape[0]} windows of "
               f"{a.h_mb}x{a.w_mb}" + (f", {val_tables[k].shape[0]} to validate" if val_tables is not None else ""), file=sys.stderr)
     del files, val_files
-    if a.align_report is not None:
+    if a.align_report is not None or a.record_report:
         data.close()
         ctx.close()
         return 0

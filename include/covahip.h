@@ -352,6 +352,67 @@ int covahip_monitor_add(covahip_ctx *ctx, const uint8_t *mask, const int32_t *co
 int covahip_monitor_read(covahip_ctx *ctx, int reset, int64_t *frames, int64_t *fire, int64_t *boxes, int64_t *frames_with_boxes,
                          int64_t *truncated, int64_t *area_hist, int64_t *batches_seen, int64_t *batches_counted);
 int covahip_monitor_end(covahip_ctx *ctx);
+/* Input monitor: what records a camera SENDS, beside what the model makes of them.  The records are whatever the camera's encoder
+ * and the entropy front end make of the scene, and a firmware update, a bitrate cap or a frozen feed changes them without
+ * touching the scene or the model.  One set of exact integer statistics over packed records, behind served batches (an attached
+ * monitor), on a caller's inputs (covahip_monitor_add_inputs) and over resident training frames
+ * (covahip_train_data_record_stats, below).
+ * A record is what covahip_carrier_pack keeps of a macroblock's four bytes: c = min(byte0, 6), x = min(byte1, 6),
+ * y = min(byte2, 6), r = c | x << 3 | y << 6; byte 3 is ignored.  For data that is already packed r = value & 511: bits 9 and
+ * above are ignored and a field of 7 is counted as given.  Per counted frame f of h x w macroblocks p:
+ *   bin(p)       = r(p), 0 .. 511
+ *   moves(p)     = (r(p) & 0x1F8) != 0          -- either vector field is non-zero
+ *   intra(p)     = (r(p) & 7) >= 5
+ *   n_move(f)    = #{p : moves(p)}
+ *   still(f)     = every r(p) == 0              -- all skip and no vector: a frozen or duplicated picture
+ *   all_intra(f) = every intra(p)               -- an I picture; in_frames / intra_frames estimates the GoP length
+ * and per model m (the counted frames of model m's stacks), 64-bit counts:
+ *   in_frames[m]      += 1
+ *   hist[m][bin(p)]   += 1 for every p
+ *   moving[m][y][x]   += moves(p)
+ *   still_frames[m]   += still(f)
+ *   intra_frames[m]   += all_intra(f)
+ *   move_hist[m][k]   += 1 with k = 0 when n_move(f) == 0, else k = min(15, 1 + floor(log2 n_move(f)))
+ * NO keep map applies to any of them: the network's receptive field reads ignored macroblocks too, and the serving side and the
+ * training side must stay comparable.  All counts are exact and additive over calls and batches; they depend neither on the
+ * lanes, nor on the slicing, nor on the input form, nor on pointer alignment.
+ * Which frame is counted: each stack counts ONE frame for its model, its newest slice.  COVAHIP_INPUT_STACKED, u8
+ * [batch][4h][w][4]: row block 0 of stack b.  COVAHIP_INPUT_FRAMES, u8 [n_frames][h][w][4], and COVAHIP_INPUT_PACKED, u16
+ * [n_frames][h][w]: frame stack_index ? stack_index[4 b] : b + 3.  A frame that is the newest slice of two stacks is counted
+ * twice; sliding windows at gamma 1 count every stream frame once.
+ * covahip_monitor_set_inputs(ctx, on), on an open monitor, attached or stand-alone: drains the ctx as begin does and allocates
+ * (on = 1) or frees (on = 0) the input tables, (4 + 512 + 16 + h * w) words per model, zeroed; a call that changes nothing keeps
+ * the tables.  Off is the default, and with it off everything behaves as without this interface: the kernels a filter step
+ * launches and what covahip_monitor_read returns.  begin and end discard the setting with the monitor.
+ * Attached, inputs on: every counted filter batch (i % every == 0) also counts its inputs -- the stacked entries, the _frames[_m]
+ * and _frames_packed[_m] entries and covahip_pipe_submit -- on the lane that ran the batch, in two launches behind the
+ * monitor's own: no synchronisation, no allocation, no upload.
+ * covahip_monitor_add_inputs: the stand-alone feed, on the primary stream behind all lanes and synchronous, like
+ * covahip_monitor_add.  stack_index: HOST i32 [batch][4] or NULL (one stream in order: batch == n_frames - 3), validated as the
+ * _frames entries validate it (every index in [0, n_frames)); n_frames and stack_index are ignored for the stacked form.
+ * model_ids: HOST u8 [batch] or NULL = model 0.  Device pointers of any alignment: records are read 16 bytes at a time where the pointer
+ * and the frames lie on 16-byte boundaries, a record at a time on a record's boundary (4 bytes, 2 packed) and byte-wise off
+ * it; host data is staged in pieces.
+ * covahip_monitor_read_inputs: HOST outputs, each may be NULL: in_frames, still_frames, intra_frames i64 [n_models]; hist i64
+ * [n_models][512]; moving i64 [n_models][h][w]; move_hist i64 [n_models][16].  Drains like covahip_monitor_read.  reset != 0
+ * zeroes the input tables ONLY; covahip_monitor_read(reset = 1) zeroes what it always zeroed and, when they exist, the input
+ * tables too.
+ * Errors, all checked on the host before the GPU is touched, and a refused call changes nothing: COVAHIP_ERR_INVALID_ARG for a
+ * NULL ctx, no open monitor, on other than 0 / 1; for add_inputs also inputs not switched on, an attached monitor, an unknown
+ * form or mem_kind, batch < 0, NULL src with batch > 0, an id >= n_models, and for the two frame forms n_frames < 4, a NULL
+ * stack_index with batch != n_frames - 3, an index outside [0, n_frames); for read_inputs and get_inputs also inputs not
+ * switched on (read) or a NULL `on` (get).  batch == 0 is COVAHIP_OK and changes nothing. */
+#define COVAHIP_INPUT_STACKED 0
+#define COVAHIP_INPUT_FRAMES 1
+#define COVAHIP_INPUT_PACKED 2
+#define COVAHIP_INPUT_BINS 512
+#define COVAHIP_INPUT_MOVE_BINS 16
+int covahip_monitor_set_inputs(covahip_ctx *ctx, int on);
+int covahip_monitor_get_inputs(covahip_ctx *ctx, int *on);
+int covahip_monitor_add_inputs(covahip_ctx *ctx, const void *src, int form, int n_frames, const int32_t *stack_index, int batch,
+                               const uint8_t *model_ids, int mem_kind);
+int covahip_monitor_read_inputs(covahip_ctx *ctx, int reset, int64_t *in_frames, int64_t *hist, int64_t *moving,
+                                int64_t *still_frames, int64_t *intra_frames, int64_t *move_hist);
 /* Algorithmic MACs per frame of the loaded geometry. */
 int covahip_blobnet_macs_per_frame(covahip_ctx *ctx, int64_t *macs);
 /* ------------------------------------------------------------------- bboxcc
@@ -758,6 +819,28 @@ int  covahip_train_data_gather(covahip_train_data *d, const covahip_train_sample
                                int mem_kind);
 int  covahip_train_data_label_mass(covahip_train_data *d, int64_t first, int64_t n, const uint8_t *keep_or_null, uint32_t *mass,
                                    int mem_kind);
+/* covahip_train_data_record_stats: the input statistics of frames [first, first + n) of the data set, each counted once, as the
+ * serving side counts them ("Input monitor" above: the same quantities from the resident packed records, r = record & 511, as
+ * one model's; no keep map), so that a recording can be judged before training and compared with a deployed camera.  The
+ * training side adds what only it can know, from the label bytes:
+ *       hist_set[r(p)] += 1 for every macroblock p of the range whose label byte is non-zero,
+ *       set_total       = the number of such macroblocks = the sum of covahip_train_data_label_mass over the same frames
+ *                         without a keep map.
+ *   `out` holds HOST pointers, each may be NULL.  Every record and label byte is read once per call; any n up to the capacity in
+ *   one call.  The calling rules are covahip_train_data_label_mass's.
+ *   COVAHIP_ERR_INVALID_ARG, checked on the host before anything is launched and with nothing written: a NULL d or out, n < 1,
+ *   first < 0, first + n > frames. */
+typedef struct covahip_record_stats {
+    int64_t *frames;        /* [1]: n                                            */
+    int64_t *hist;          /* [512]                                             */
+    int64_t *hist_set;      /* [512]                                             */
+    int64_t *set_total;     /* [1]                                               */
+    int64_t *moving;        /* [h_mb][w_mb]                                      */
+    int64_t *still_frames;  /* [1]                                               */
+    int64_t *intra_frames;  /* [1]                                               */
+    int64_t *move_hist;     /* [16]                                              */
+} covahip_record_stats;
+int  covahip_train_data_record_stats(covahip_train_data *d, int64_t first, int64_t n, const covahip_record_stats *out);
 /* covahip_train_data_align: whether the labels of ONE recording, frames [first, first + n), stand at the frames of their records.
  * Records come from the entropy front end and labels from a pixel decoder; a frame dropped by either moves every label by a few
  * frames against its record, and nothing else in training shows it.  The counts compare where the records MOVE with where the

@@ -116,6 +116,12 @@ int covahip_dev_mog_band_plan(int work_w, int work_h, int *rows, int *bands, siz
  * every CU, at least 16 samples).  The counts do not depend on it; a slice longer than 255 samples makes the kernel's packed
  * byte counters spill, which the automatic choice reaches only with batches of thousands.  (tests/test_gpu_monitor.py) */
 int covahip_dev_monitor_slice(covahip_ctx *ctx, int samples);
+/* Input monitor (covahip_monitor_set_inputs, covahip_train_data_record_stats): its kernel runs by the slices of
+ * covahip_dev_monitor_slice and flushes a workgroup's 32-bit counters into the 64-bit tables every `samples` samples of a slice
+ * and at the slice's end; 0 restores the default of 2^20 (times the 2,048 macroblocks of a workgroup: 2^31, no counter wraps),
+ * which no batch reaches.  COVAHIP_ERR_INVALID_ARG outside 0 .. 2^20.  The counts do not depend on it.
+ * (tests/test_gpu_monitor_inputs.py) */
+int covahip_dev_input_flush(covahip_ctx *ctx, int samples);
 
 /* Device bytes of host samples (4 bytes of logit and 1 label byte per macroblock) that covahip_post_heat_add (COVAHIP_MEM_HOST)
  * stages per piece; 0 restores the default of 64 MiB.  A call whose samples exceed it is uploaded and counted in several pieces
